@@ -353,6 +353,130 @@ def layer_table(engine, batch):
     return rows
 
 
+class ClockProbeProcess:
+    """fnn_clock_probe_* run from a child process.  The probe is a kernel that runs for most of a step: on a stream of this
+    process it can share a hardware queue with a stream of the engine (a process opens few queues, GPU_MAX_HW_QUEUES, and
+    the engine runs four pipe streams besides the caller's), and everything behind it then waits (2490 instead of 3440
+    patches/s next to it with HIP's default of four queues, measured).  A process has hardware queues of its own, so from
+    a child the probe's wave never queues in front of the engine.  The child starts HIP and loads the library once (a
+    10 ms probe), then starts and stops one probe per request on its stdin; closing stdin ends it."""
+
+    def __init__(self, device):
+        import subprocess
+        code = f'import sys; sys.path.insert(0, {ROOT!r}); import bench; bench.clock_probe_child({int(device)})'
+        self._p = subprocess.Popen([sys.executable, '-c', code], stdin=subprocess.PIPE, stdout=subprocess.PIPE, bufsize=0)
+        self._buf = b''
+        while self._line(300.0) != 'ready':                     # (anything an import prints first is skipped)
+            pass
+
+    def _line(self, timeout):
+        import select
+        end = time.perf_counter() + timeout
+        while b'\n' not in self._buf:
+            if not select.select([self._p.stdout], [], [], max(0.0, end - time.perf_counter()))[0]:
+                self.close()
+                raise RuntimeError(f'clock probe process: no answer within {timeout} s')
+            chunk = os.read(self._p.stdout.fileno(), 4096)
+            if not chunk:
+                raise RuntimeError(f'clock probe process ended (exit code {self._p.wait()})')
+            self._buf += chunk
+        line, self._buf = self._buf.split(b'\n', 1)
+        return line.decode().strip()
+
+    def _ask(self, request, timeout):
+        self._p.stdin.write((request + '\n').encode())
+        return self._line(timeout)
+
+    def start(self, max_seconds):
+        """Returns once the probe's wave is launched."""
+        if self._ask(f'start {float(max_seconds)!r}', 60.0) != 'started':
+            raise RuntimeError('clock probe process: start failed')
+
+    def stop(self):
+        """(GHz the device held since start, seconds covered)."""
+        ghz, sec = self._ask('stop', 120.0).split()
+        return float(ghz), float(sec)
+
+    def close(self):
+        import subprocess
+        if self._p.poll() is None:
+            self._p.stdin.close()
+            try:
+                self._p.wait(timeout=30)
+            except subprocess.TimeoutExpired:
+                self._p.kill()
+                self._p.wait()
+
+
+def clock_probe_child(device):
+    """The child side of ClockProbeProcess: `start <max_seconds>` -> `started`, `stop` -> `<GHz> <seconds>`."""
+    from fast_nnunet_amd import capi
+    capi.clock_probe_stop(capi.clock_probe_start(device, 0.01))
+    out = sys.stdout
+    out.write('ready\n')
+    out.flush()
+    h = None
+    for request in sys.stdin:
+        words = request.split()
+        if words and words[0] == 'start':
+            h = capi.clock_probe_start(device, float(words[1]))
+            out.write('started\n')
+        elif words and words[0] == 'stop':
+            ghz, sec = capi.clock_probe_stop(h)
+            out.write(f'{ghz!r} {sec!r}\n')
+        out.flush()
+
+
+DUMP_BYTES = 60_000_000    # --dump-outputs: every file of one run together, npy headers included, stays under 64 MB
+DUMP_SEED = 0
+
+
+def step_arrays(out):
+    """What a caller of the timed path receives from one step, as named tensors: the logits (one GPU, fold ensemble,
+    --gather logits), the label map (--gather labels), or with --gather none the logits of the box this rank owns."""
+    if isinstance(out, tuple):                                   # ShardedPredictor without gather: (logits, owned box or None)
+        logits, own = out
+        if own is None:
+            return {}
+        sl = (slice(None), *[slice(own[0][d], own[1][d]) for d in range(len(own[0]))])
+        return {'logits_owned_box': logits[sl], 'owned_box': torch.tensor([list(own[0]), list(own[1])], dtype=torch.float64)}
+    return {('logits' if out.is_floating_point() else 'labels'): out}
+
+
+def dump_outputs(arrays, dirname, spatial_dims, budget=DUMP_BYTES, suffix=''):
+    """Writes every array as <dirname>/<name><suffix>.npy in float32 (float64 stays float64).  An array larger than its share
+    of `budget` is written as a fixed sample instead: the same seeded voxels every run, all leading channels at each
+    (<name>.npy [channels, n], or [n] without a channel dim), next to <name>_index.npy, the voxels' flat indices into the
+    spatial dims (float64, exact).  Returns what was written, for the JSON line."""
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    left = budget
+    order = sorted(arrays, key=lambda k: arrays[k].numel())     # small arrays whole first, the rest share what is left
+    for i, name in enumerate(order):
+        t = arrays[name]
+        dt, item = (torch.float64, 8) if t.dtype == torch.float64 else (torch.float32, 4)
+        share = left // (len(order) - i)
+        info = {'shape': list(t.shape), 'dtype': str(t.dtype).replace('torch.', '')}
+        if t.numel() * item <= share:
+            a = t.to(dt).cpu().numpy()
+            np.save(os.path.join(dirname, name + suffix + '.npy'), a)
+            left -= a.nbytes
+        else:
+            space = tuple(t.shape[-spatial_dims:])
+            lead = t.numel() // int(np.prod(space))
+            nvox = int(np.prod(space))
+            n = min(nvox, share // (lead * item + 8))
+            flat = np.sort(np.random.default_rng(DUMP_SEED).choice(nvox, n, replace=False))
+            idx = tuple(torch.from_numpy(c).to(t.device) for c in np.unravel_index(flat, space))
+            a = t[(Ellipsis, *idx)].to(dt).cpu().numpy()
+            np.save(os.path.join(dirname, name + suffix + '.npy'), a)
+            np.save(os.path.join(dirname, name + suffix + '_index.npy'), flat.astype(np.float64))
+            left -= a.nbytes + flat.size * 8
+            info['sampled_voxels'] = n
+        written[name + suffix] = info
+    return written
+
+
 ALSO = [('C1 iso128_r2', ['--workload', 'iso128_r2']),
         ('C4 iso128_teacher, 5-fold ensemble', ['--workload', 'iso128_teacher', '--folds', '5']),
         ('C5 resenc160_r2 f16', ['--workload', 'resenc160_r2']),
@@ -395,7 +519,8 @@ def also_block(device):
 
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this script (one per GPU) BEFORE anything in
-    this process touches the GPU, wait for them, and leave with the worst exit code.  Rank 0 prints the JSON line."""
+    this process touches the GPU, wait for them (a rank that fails stops the others), and leave with the worst exit code.
+    Rank 0 prints the JSON line."""
     import socket
     import subprocess
     s = socket.socket()
@@ -408,18 +533,32 @@ def spawn_ranks(n):
                    MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0')
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
     rc = 0
-    for p in procs:
-        rc = max(rc, abs(p.wait()))
+    running = list(procs)
+    while running:
+        for p in list(running):
+            if p.poll() is None:
+                continue
+            running.remove(p)
+            rc = max(rc, abs(p.returncode))
+            if p.returncode != 0:
+                # the other ranks would wait for this one in the process group's rendezvous or a collective for good (e.g.
+                # --gpus 2 on a box with one GPU: rank 1 has no device): stop them
+                for q in running:
+                    q.terminate()
+                for q in running:
+                    try:
+                        q.wait(timeout=30)
+                    except subprocess.TimeoutExpired:
+                        q.kill()
+                        q.wait()
+                    rc = max(rc, abs(q.returncode))
+                running = []
+                break
+        time.sleep(0.2)
     sys.exit(rc)
 
 
 def main():
-    # The clock probe (one extra untimed step, below) is a kernel that runs for most of a step on a stream of its own: with
-    # HIP's default of four hardware queues it shares one with a stream of the engine and everything behind it waits (2490
-    # instead of 3440 patches/s next to it, measured); with eight the step is the same with and without it (3440 / 3424).
-    # The timed steps themselves do not care (3440 / 3440, 3347 / 3357 on two boxes).  Read at HIP's initialisation, i.e.
-    # before the first torch.cuda call below.
-    os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
@@ -455,7 +594,13 @@ def main():
     ap.add_argument('--folds', type=int, default=1,
                     help='fold ensemble (BASELINE configs[3]: 5 folds of the teacher): the folds stay resident, their logits are '
                          'averaged on the device (fnn_predict_volume_ensemble); one step = one volume through ALL folds')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one returned as DIR/<name>.npy (float32): the whole array, '
+                         'or a fixed seeded sample of its voxels when it is larger (all files together under 64 MB); with '
+                         'several ranks every file carries _rank<r>')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     args.batch_given = args.batch is not None
     if args.batch is None:
         args.batch = 32
@@ -492,12 +637,14 @@ def main():
 
     clock = {}
 
-    def timed(step_fn, barrier, steps):
+    def timed(step_fn, barrier, steps, keep=None):
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
             out = step_fn()
+            if keep is not None and i == steps - 1:
+                keep['out'] = out                                # (--dump-outputs: what the last timed step returned)
             del out
         barrier()
         torch.cuda.synchronize()
@@ -534,29 +681,46 @@ def main():
         del out
         torch.cuda.synchronize()
         step_est = time.perf_counter() - t0
-    dt = timed(step_fn, barrier, args.steps)
+    last = {} if args.dump_outputs else None
+    dt = timed(step_fn, barrier, args.steps, keep=last)
+    dumped = None
+    if last is not None:
+        dumped = dump_outputs(step_arrays(last.pop('out')), args.dump_outputs, vol.dim() - 1, DUMP_BYTES // world,
+                              f'_rank{rank}' if world > 1 else '')
+        del last
     if step_est and not args.no_clock_probe and not args.no_roofline:
         # one extra, identical, UNTIMED step beside the clock probe (one sleeping wave, fnn_clock_probe_*): the shader clock the
         # device holds under this step.  Not in the timed region (it costs ~0.5 % there) and not in the profiled step below
         # (it stretches the per-launch durations by ~4 %, measured: 734 -> 700 TFLOP/s)
         step_timed = dt / args.steps
-        for attempt in range(3):                                 # (a short step's duration jitters by more than the gate: sampled again)
-            barrier()
-            torch.cuda.synchronize()
-            probe = capi.clock_probe_start(local_rank, min(30.0, 4.0 * step_est))
-            out = step_fn()                                      # (returns when the volume is done: the engine's entry points are synchronous)
-            clock['ghz'], clock['seconds'] = capi.clock_probe_stop(probe)   # raises the probe's flag and waits for ITS stream only
-            del out
-            torch.cuda.synchronize()
-            # the sample only counts when the probed step ran like the timed ones: with fewer hardware queues than streams (HIP
-            # initialised before main() set GPU_MAX_HW_QUEUES - a profiler's preload, an embedding process) the probe shares a queue
-            # with an engine stream and the step waits behind it; then the clock is that of a stalled device
-            tol = 0.15 if args.steps >= 3 else 0.35               # (one or two timed steps are themselves a noisy yardstick)
-            if (1 - tol) * step_timed <= clock['seconds'] <= (1 + tol) * step_timed:
-                break
-            if attempt == 2:
-                clock = {'rejected': f"probed step took {clock['seconds']:.3f} s against {step_timed:.3f} s timed: the probe disturbed the step "
-                                     f"(GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}), sample dropped"}
+        probe = ClockProbeProcess(local_rank) if rank == 0 else None   # (rank 0's clock is the one the line quotes)
+        try:
+            for attempt in range(3):                             # (a short step's duration jitters by more than the gate: sampled again)
+                barrier()
+                torch.cuda.synchronize()
+                if probe:
+                    probe.start(min(30.0, 4.0 * step_est))
+                out = step_fn()                                  # (returns when the volume is done: the engine's entry points are synchronous)
+                if probe:
+                    clock['ghz'], clock['seconds'] = probe.stop()
+                del out
+                torch.cuda.synchronize()
+                # the sample only counts when the probed step ran like the timed ones (else the clock is that of a disturbed
+                # step); every rank takes rank 0's decision, the step being collective
+                tol = 0.15 if args.steps >= 3 else 0.35           # (one or two timed steps are themselves a noisy yardstick)
+                ok = rank != 0 or (1 - tol) * step_timed <= clock['seconds'] <= (1 + tol) * step_timed
+                if distributed:
+                    t = torch.tensor([1.0 if ok else 0.0], device=device)
+                    dist.broadcast(t, 0)
+                    ok = bool(t.item())
+                if ok:
+                    break
+                if attempt == 2 and rank == 0:
+                    clock = {'rejected': f"probed step took {clock['seconds']:.3f} s against {step_timed:.3f} s timed: the probe "
+                                         f"disturbed the step, sample dropped"}
+        finally:
+            if probe:
+                probe.close()
     if distributed and args.gather != 'labels':
         out = labels_fn()                                        # (one untimed call: first-use allocations of this entry point)
         del out
@@ -628,6 +792,10 @@ def main():
                    'gpu_max_hw_queues': os.environ.get('GPU_MAX_HW_QUEUES'),
                    'parallelism': f'patch-sharded x{world}, patch-activation exchange + slab gather over RCCL' if distributed else 'single GPU'},
     }
+    if dumped is not None:
+        result['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped,
+                                  'note': 'what the last timed step returned (this rank\'s files); sampled arrays: seeded voxels, '
+                                          'flat spatial indices in <name>_index.npy'}
     if w['plan']:
         result['config']['plan'] = {'file': os.path.relpath(os.path.abspath(args.plan), ROOT), 'spacing': list(w['spacing']),
                                     'kernels': info['kernels'], 'strides': info['strides'], 'note': w['note']}

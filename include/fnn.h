@@ -407,7 +407,7 @@ int fnn_op_last_kernels(char *buf, int cap);
  * region it samples.)  bench.py runs one extra, untimed step beside it: under sustained MFMA load the chip lowers its
  * clock, and a roofline fraction priced at 2.4 GHz does not say how much of what the clock allows a
  * kernel uses.  The probe is not free: next to it per-launch durations stretch by ~4 %, and with HIP's default of four
- * hardware queues it can share a queue with a caller's stream, whose work then waits for it (GPU_MAX_HW_QUEUES=8). */
+ * hardware queues it can share a queue with a caller's stream, whose work then waits for it (bench.py runs it from a process of its own). */
 int fnn_clock_probe_start(int device, double max_seconds, void **probe);
 int fnn_clock_probe_stop(void *probe, double *ghz, double *seconds);
 

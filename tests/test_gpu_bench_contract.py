@@ -87,6 +87,34 @@ def test_bench_fold_ensemble_line():
     assert abs(j['value'] - 1000.0 * 2 * _patches(j) / j['ms_per_step']) / j['value'] < 1e-3
 
 
+def test_bench_dump_outputs_holds_what_the_last_timed_step_returned(tmp_path):
+    """`--dump-outputs DIR`: the logits a step returned, in float32 - 61 x 192^3 is larger than the 64 MB budget, so the
+    seeded sample of voxels - equal to what the same predictor on the same seeded inputs computes in this process at those
+    voxels.  (The engine is deterministic, so this does not tell the last timed step from another one.)"""
+    import numpy as np
+    import torch
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    d = tmp_path / 'dump'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--volume', '192', '--steps', '2', '--warmup', '0',
+                          '--no-cpu-baseline', '--no-roofline', '--no-from-host', '--dump-outputs', str(d)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])
+    assert j['steps'] == 2 and j['ms_per_step'] > 0
+    assert j['dump_outputs']['arrays']['logits']['shape'] == [61, 192, 192, 192]
+    files = sorted(os.listdir(d))
+    assert files == ['logits.npy', 'logits_index.npy'] and sum(os.path.getsize(d / f) for f in files) < 64e6
+    got, ix = np.load(d / 'logits.npy'), np.load(d / 'logits_index.npy').astype(np.int64)
+    assert got.dtype == np.float32 and got.shape == (61, ix.size)
+    dev = torch.device('cuda', 0)
+    p, _, _ = bench.build_predictor(bench.named_workload('bone_turbo_r2', 192), dev, 32, 'fp16')
+    logits = p.predict_sliding_window_return_logits(bench.synthetic_volume(192, dev))
+    want = logits.reshape(61, -1)[:, torch.from_numpy(ix).to(dev)].float().cpu().numpy()
+    assert np.array_equal(got, want)
+
+
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
     env = dict(os.environ, WORLD_SIZE='1', RANK='0', LOCAL_RANK='0')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1'], capture_output=True,

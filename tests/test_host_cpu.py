@@ -344,6 +344,33 @@ def test_bench_gpus_n_spawns_one_rank_per_gpu_and_propagates_failure():
     assert out2.returncode != 0 and 'WORLD_SIZE=1' in (out2.stderr + out2.stdout)
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: the headline step's logits (61 x 512^3 fp16, 16 GB) go out as float32 at the same seeded
+    voxels every run, every file together under 64 MB; the sample holds the values at the voxels its index file names;
+    an array that fits goes out whole."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(61, dtype=torch.half).view(61, 1, 1, 1).expand(61, 512, 512, 512)   # (a view: nothing allocated)
+    for d in ('a', 'b'):
+        bench.dump_outputs(bench.step_arrays(big), str(tmp_path / d), 3)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['logits.npy', 'logits_index.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) < 64e6
+    a, ix = np.load(tmp_path / 'a' / 'logits.npy'), np.load(tmp_path / 'a' / 'logits_index.npy')
+    assert a.dtype == np.float32 and ix.dtype == np.float64 and a.shape == (61, ix.size) and ix.size > 100000
+    assert (a == np.arange(61, dtype=np.float32)[:, None]).all()
+    assert np.array_equal(ix, np.load(tmp_path / 'b' / 'logits_index.npy'))
+    x = torch.randn(3, 20, 30, 40, generator=torch.Generator().manual_seed(0)).half()
+    bench.dump_outputs(bench.step_arrays(x), str(tmp_path / 'c'), 3, budget=100000)
+    a, ix = np.load(tmp_path / 'c' / 'logits.npy'), np.load(tmp_path / 'c' / 'logits_index.npy').astype(np.int64)
+    assert np.unique(ix).size == ix.size and np.array_equal(a, x.float().reshape(3, -1)[:, ix].numpy())
+    labels = torch.randint(0, 61, (20, 30, 40), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(bench.step_arrays(labels), str(tmp_path / 'd'), 3)
+    got = np.load(tmp_path / 'd' / 'labels.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, labels.float().numpy())
+
+
 def test_fp8_weight_quantiser_matches_torch_e4m3fn(capi):
     """FNN_PREC_F8 packs weights as OCP e4m3 on the host: the encoder must agree with torch's float8_e4m3fn (round to
     nearest even, subnormals down to 2^-9, saturation at +-448) on every value class."""

@@ -7,7 +7,6 @@ import sys
 import time
 
 os.environ.setdefault('FNN_KNOBS', '1')
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
