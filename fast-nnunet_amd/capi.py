@@ -66,7 +66,7 @@ class Profile(C.Structure):
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
            'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
-           'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
+           'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
 
@@ -133,6 +133,8 @@ def load_library() -> C.CDLL:
             fn = getattr(lib, name)
             fn.argtypes = [vp, C.c_char_p, i64]
             fn.restype = i64
+    lib.fnn_plan_table.argtypes = [C.POINTER(ArchDesc), i32, C.c_char_p, i64]
+    lib.fnn_plan_table.restype = i64
     lib.fnn_patch_work.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     I3 = C.POINTER(C.c_int)
     lib.fnn_op_conv3d.argtypes = [i32, i32, I3, f32p, i32, f32p, f32p, C.c_float, f32p, i32, f32p, f32p, C.c_float,
@@ -163,6 +165,23 @@ def check(rc: int, lib, handle=None):
     if rc == FNN_E_UNSUPPORTED:
         raise NotImplementedError(msg)
     raise RuntimeError(msg)            # FNN_E_INF, FNN_E_HIP, FNN_E_STATE
+
+
+_LAYER_KEYS = ('index', 'type', 'cin', 'cout', 'kernel', 'stride', 'in_dims', 'out_dims', 'flops', 'bytes', 'fused', 'picked')
+_LAYER_CONV = (int, str, int, int, str, str, str, str, float, float, int, str)
+
+
+def _layer_rows(rows):
+    return [dict((k, c(v)) for k, c, v in zip(_LAYER_KEYS, _LAYER_CONV, r)) for r in rows]
+
+
+def plan_table(desc: ArchDesc, max_batch: int):
+    """The layer plan fnn_create(desc, device, max_batch) would make, without a GPU: rows as Engine.layer_table()."""
+    lib = load_library()
+    n = check(lib.fnn_plan_table(C.byref(desc), int(max_batch), None, 0), lib)
+    buf = C.create_string_buffer(int(n))
+    lib.fnn_plan_table(C.byref(desc), int(max_batch), buf, n)
+    return _layer_rows(r.split('\t') for r in buf.value.decode().split('\n') if r)
 
 
 def _f32p(a: Optional[np.ndarray]):
@@ -383,10 +402,9 @@ class Engine:
         return [(int(r[0]), r[1], float(r[2]), float(r[3]), float(r[4]), r[5] if len(r) > 5 else '') for r in self._text(self.lib.fnn_profile_launches)]
 
     def layer_table(self):
-        """The engine's layer plan: dicts with index, type, cin, cout, kernel, stride, in_dims, out_dims, flops, bytes, fused."""
-        keys = ('index', 'type', 'cin', 'cout', 'kernel', 'stride', 'in_dims', 'out_dims', 'flops', 'bytes', 'fused')
-        conv = (int, str, int, int, str, str, str, str, float, float, int)
-        return [dict((k, c(v)) for k, c, v in zip(keys, conv, r)) for r in self._text(self.lib.fnn_layer_table)]
+        """The engine's layer plan: dicts with index, type, cin, cout, kernel, stride, in_dims, out_dims, flops, bytes, fused and
+        picked - the kernel chosen for a conv layer, as kernel_log() names it ('-' for other layers)."""
+        return _layer_rows(self._text(self.lib.fnn_layer_table))
 
     def patch_work(self):
         fl, by = C.c_double(), C.c_double()

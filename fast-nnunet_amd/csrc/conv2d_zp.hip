@@ -67,17 +67,16 @@ void conv_zp_pack(const float *W, int cout_real, int cout_pad, int cin_real0, in
                     }
 }
 
-// (waves along the columns, rows per wave) for a layer's plane, or false when the layer keeps the other kernels
-static bool zp_pick(const ConvParams &p, int &wc, int &th) {
+// (1, 3, 3) layers of stride 1 or (1, 2, 2) on the plane kernels (FNN_PACK_ZP: 32-channel chunks, 9 k-steps, one statistics
+// row per tile): the waves along the columns, rows per wave, cout blocks per workgroup and the half image for 16-channel
+// sources.  false: the layer keeps the other kernels.
+bool zp_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c) {
 #ifdef FNN_NORM_FP32
     return false;                                             // (the A-B build with fp32 normalise-on-load keeps the linear-tap kernels)
 #endif
-    static const bool off = fnn_knob("FNN_NO_ZP") != nullptr;                       // A-B aid
-    if (fnn_knob("FNN_CONV_V1") != nullptr) return false;                           // (read per call: the test of the generic kernel)
-    if (off || p.kd != 1 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.fp8) return false;
+    if (o.no_zp || o.conv_v1 || p.kd != 1 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.fp8) return false;
     const bool strided = p.sh == 2 && p.sw == 2;
     if (!strided && !(p.sh == 1 && p.sw == 1)) return false;
-    if (strided && fnn_knob("FNN_NO_ZPS") != nullptr) return false;                 // A-B aid
     // cout blocks in pairs; an odd number of blocks (16 output channels: the full-resolution level of an r = 2 student) one at a
     // time, only where no other kernel fits - depth < 4, i.e. `2d` configurations (at depth >= 4 the persistent 4 x 8 x 8 kernels
     // reach 4 TB/s on those layers) - and not strided (a down-sampling conv doubles its channels)
@@ -86,25 +85,31 @@ static bool zp_pick(const ConvParams &p, int &wc, int &th) {
     const int cmax = p.src[0].C > p.src[1].C ? p.src[0].C : p.src[1].C;
     // 32-bit byte offsets inside a batch item, and the 0x80000000 "not fetched" offset must lie beyond every tensor
     if (vox * 2 * (cmax > 0 ? cmax : 16) >= (1ll << 31) || vox * 2 * p.Cout >= (1ll << 31) || vox >= (1 << 24)) return false;
+    int wc, th;
     if (strided) {                                                                  // conv2d_zps_kernel: 8 x 32 or 16 x 16 output tiles
         const long long ivox = (long long)p.Di * p.Hi * p.Wi;
         if (ivox * 2 * (cmax > 0 ? cmax : 16) >= (1ll << 31) || ivox >= (1 << 24)) return false;
         wc = p.Wo > 16 ? 2 : 1; th = 4;
-        return true;
-    }
-    if (p.Wo > 32) { wc = 4; th = 8; }
+    } else if (p.Wo > 32) { wc = 4; th = 8; }
     else if (p.Wo > 16) { wc = 2; th = 8; }
     else { wc = 1; th = 4; }
+    const int rows = (4 / wc) * th, cols = wc * 16;
+    c.packing = FNN_PACK_ZP; c.ksteps = 9; c.chunks = conv_zp_chunks(p.src[0].C, p.n_src > 1 ? p.src[1].C : 0);
+    c.stats_slots = p.Do * ((p.Ho + rows - 1) / rows) * ((p.Wo + cols - 1) / cols);
+    if (strided) {
+        const bool four = (p.Cout / 16) % 4 == 0;
+        const bool half = p.n_src == 1 && p.src[0].C == 16 && !four && !o.zps_no_half;
+        const int nb = half ? 2 : four ? 4 : 2;
+        c.kernel = CK_ZPS; c.t[0] = nb; c.t[1] = wc; c.t[2] = half;
+        snprintf(c.name, sizeof c.name, half ? "conv2d_zps_kernel<%d,%d,half>" : "conv2d_zps_kernel<%d,%d>", nb, wc);
+        return true;
+    }
+    const bool half = p.src[0].C == 16 && (p.n_src < 2 || p.src[1].C == 16) && !o.zp_no_half;
+    const int nb = (p.Cout / 16) % 2 != 0 ? 1 : 2;           // an odd number of cout blocks: one per workgroup
+    c.kernel = CK_ZP; c.t[0] = th; c.t[1] = wc; c.t[2] = nb; c.t[3] = half;
+    if (nb == 2 && !half) snprintf(c.name, sizeof c.name, "conv2d_zp_kernel<%d,%d>", th, wc);
+    else snprintf(c.name, sizeof c.name, half ? "conv2d_zp_kernel<%d,%d,%d,half>" : "conv2d_zp_kernel<%d,%d,%d>", th, wc, nb);
     return true;
-}
-
-bool conv2d_zp_ok(const ConvParams &p) { int wc, th; return zp_pick(p, wc, th); }
-
-int conv2d_zp_stats_slots(const ConvParams &p) {
-    int wc, th;
-    if (!zp_pick(p, wc, th)) return FNN_STAT_REPL;
-    const int rows = (4 / wc) * th, cols = wc * 16;             // (the strided kernel: th = 4 -> 8 x 32 or 16 x 16)
-    return p.Do * ((p.Ho + rows - 1) / rows) * ((p.Wo + cols - 1) / cols);
 }
 
 namespace {
@@ -382,7 +387,6 @@ int launch_zp(ConvParams p, hipStream_t st) {
     p.tiles_d = p.Do;
     p.tiles_h = (p.Ho + ROWS - 1) / ROWS;
     p.tiles_w = (p.Wo + COLS - 1) / COLS;
-    if (p.stats_out && p.stats_slots < p.Do * p.tiles_h * p.tiles_w) return -1;   // (a plan sized for another tiling)
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void *)conv2d_zp_kernel<TH, WC, NB, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -394,8 +398,6 @@ int launch_zp(ConvParams p, hipStream_t st) {
     const long long tiles = (long long)p.N * p.Do * p.tiles_h * p.tiles_w;
     if (tiles >= (1ll << 31)) return -1;
     dim3 grid((unsigned)tiles, (p.Cout / 16) / NB);
-    if (NB == 2 && !HALF) fnn_note_kernel("conv2d_zp_kernel<%d,%d>", TH, WC);
-    else fnn_note_kernel(HALF ? "conv2d_zp_kernel<%d,%d,%d,half>" : "conv2d_zp_kernel<%d,%d,%d>", TH, WC, NB);
     hipLaunchKernelGGL((conv2d_zp_kernel<TH, WC, NB, HALF>), grid, dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -657,7 +659,6 @@ int launch_zps(ConvParams p, hipStream_t st) {
     p.tiles_d = p.Do;
     p.tiles_h = (p.Ho + ROWS - 1) / ROWS;
     p.tiles_w = (p.Wo + COLS - 1) / COLS;
-    if (p.stats_out && p.stats_slots < p.Do * p.tiles_h * p.tiles_w) return -1;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void *)conv2d_zps_kernel<NB, WC, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -669,28 +670,22 @@ int launch_zps(ConvParams p, hipStream_t st) {
     const long long tiles = (long long)p.N * p.Do * p.tiles_h * p.tiles_w;
     if (tiles >= (1ll << 31)) return -1;
     dim3 grid((unsigned)tiles, (p.Cout / 16) / NB);
-    fnn_note_kernel(HALF ? "conv2d_zps_kernel<%d,%d,half>" : "conv2d_zps_kernel<%d,%d>", NB, WC);
     hipLaunchKernelGGL((conv2d_zps_kernel<NB, WC, HALF>), grid, dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 }  // namespace
 
-// Runs the layer; the weights must have been packed as FNN_PACK_ZP and p.chunks = conv_zp_chunks(...).
-int launch_conv2d_zp(const ConvParams &p, hipStream_t st) {
-    int wc, th;
-    if (p.packing != FNN_PACK_ZP || p.ksteps != 9 || !zp_pick(p, wc, th)) return -1;
-    if (p.chunks != conv_zp_chunks(p.src[0].C, p.n_src > 1 ? p.src[1].C : 0)) return -1;
-    if (p.sh == 2) {
-        const bool four = (p.Cout / 16) % 4 == 0;
-        const bool half16 = p.n_src == 1 && p.src[0].C == 16 && !four && fnn_knob("FNN_ZPS_NO_HALF") == nullptr;   // (knob: A-B aid)
-        if (half16) return wc == 2 ? launch_zps<2, 2, true>(p, st) : launch_zps<2, 1, true>(p, st);
-        if (wc == 2) return four ? launch_zps<4, 2>(p, st) : launch_zps<2, 2>(p, st);
-        return four ? launch_zps<4, 1>(p, st) : launch_zps<2, 1>(p, st);
+// Runs the layer on the kernel zp_choose chose; the weights are packed as FNN_PACK_ZP and p.chunks counts 32-channel chunks.
+int launch_conv2d_zp(ConvParams p, const ConvChoice &c, hipStream_t st) {
+    const int wc = c.t[1];
+    if (c.kernel == CK_ZPS) {
+        if (c.t[2]) return wc == 2 ? launch_zps<2, 2, true>(p, st) : launch_zps<2, 1, true>(p, st);
+        if (wc == 2) return c.t[0] == 4 ? launch_zps<4, 2>(p, st) : launch_zps<2, 2>(p, st);
+        return c.t[0] == 4 ? launch_zps<4, 1>(p, st) : launch_zps<2, 1>(p, st);
     }
-    const bool half16 = p.src[0].C == 16 && (p.n_src < 2 || p.src[1].C == 16) && fnn_knob("FNN_ZP_NO_HALF") == nullptr;   // (knob: A-B aid)
-    if ((p.Cout / 16) % 2 != 0) {                             // an odd number of cout blocks: one per workgroup
-        if (half16) {
+    if (c.t[2] == 1) {
+        if (c.t[3]) {
             if (wc == 4) return launch_zp<8, 4, 1, true>(p, st);
             if (wc == 2) return launch_zp<8, 2, 1, true>(p, st);
             return launch_zp<4, 1, 1, true>(p, st);
@@ -699,7 +694,7 @@ int launch_conv2d_zp(const ConvParams &p, hipStream_t st) {
         if (wc == 2) return launch_zp<8, 2, 1>(p, st);
         return launch_zp<4, 1, 1>(p, st);
     }
-    if (half16) {
+    if (c.t[3]) {
         if (wc == 4) return launch_zp<8, 4, 2, true>(p, st);
         if (wc == 2) return launch_zp<8, 2, 2, true>(p, st);
         return launch_zp<4, 1, 2, true>(p, st);

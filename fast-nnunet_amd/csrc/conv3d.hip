@@ -501,7 +501,6 @@ static int launch_ldsk(ConvParams p, hipStream_t st) {
         attr_set = true;
     }
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    fnn_note_kernel("conv3d_lds_kernel<%d,%d,%d>", NB, MB, PF);
     hipLaunchKernelGGL((conv3d_lds_kernel<NB, MB, PF>), grid, dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -878,41 +877,22 @@ static int launch_persist_ks(ConvParams p, int wgs_per_cu, hipStream_t st, int g
     int gx = gx_exact > 0 ? gx_exact : 256 * wgs_per_cu;
     if (gx > total) gx = total;
     dim3 grid(gx, (p.Cout / 16) / NB);
-    fnn_note_kernel("conv3d_persist_kernel<%d,%d,%d,%d,%d,%d,%d>", NB, MB, (int)WRES, KS, CH, PF, (int)SBUF);
     hipLaunchKernelGGL((conv3d_persist_kernel<NB, MB, WRES, KS, CH, PF, SBUF>), grid, dim3(256), lds, st, p, total);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-template <int NB, int MB, bool WRES>
-static int launch_persist(const ConvParams &p, int wgs_per_cu, hipStream_t st) {
-    // fully unrolled k-loops for the two common tap counts (9 taps = 5 k-steps, 27 taps = 14); only instantiated
-    // for the thin single-cout-block layers that the persistent kernel is used for
-    if (NB == 1 && MB == 8 && WRES && p.ksteps == 5 && (p.chunks == 1 || p.chunks == 2)) {
-        // 4-deep tiles with a 4-element prefetch need 138-151 VGPRs and 36 KB of LDS: three workgroups per CU instead
-        // of two - more bytes in flight for these HBM-bound layers (+0.8 % on the benchmark).  Four (round 2: scale / shift
-        // through scalar loads, forced to 128 VGPRs: 44-132 B of scratch): 740 -> 895 us per launch; the scalar loads alone,
-        // at three workgroups: 817 us - SMEM shares lgkmcnt with the LDS reads of the k-loop and returns out of order, so every
-        // wait becomes a full drain
-        // (the 8-deep forms of these two were reachable through an A-B knob only and are gone: round 3)
-        const int ivox4 = (3 * p.sd + p.kd) * ((FNN_TILE_H - 1) * p.sh + p.kh) * ((FNN_TILE_W - 1) * p.sw + p.kw);
-        if (ivox4 * 2 <= 4 * 256 && persist_lds_bytes(p, 1, 4, true) * 3 <= 160 * 1024) {
-            if (p.chunks == 1) return launch_persist_ks<1, 4, true, 5, (NB == 1 && MB == 8 && WRES ? 1 : 0), (NB == 1 && MB == 8 && WRES ? 4 : 8)>(p, 3, st);
-            return launch_persist_ks<1, 4, true, 5, (NB == 1 && MB == 8 && WRES ? 2 : 0), (NB == 1 && MB == 8 && WRES ? 4 : 8)>(p, 3, st);
-        }
+// the instantiations conv_choose_linear can choose: (NB, MB, WRES, KS, CH, PF, SBUF) = c.t
+static int launch_persist(const ConvParams &p, const ConvChoice &c, hipStream_t st) {
+    const int mb = c.t[1], wres = c.t[2], ks = c.t[3], ch = c.t[4];
+    if (c.t[0] == 2) return launch_persist_ks<2, 2, true, 0, 1, 12, true>(p, c.wpc, st, c.gx);
+    if (ch == 1) return launch_persist_ks<1, 4, true, 5, 1, 4>(p, c.wpc, st);
+    if (ch == 2) return launch_persist_ks<1, 4, true, 5, 2, 4>(p, c.wpc, st);
+    if (mb == 8) {
+        if (wres) return ks == 5 ? launch_persist_ks<1, 8, true, 5>(p, c.wpc, st) : launch_persist_ks<1, 8, true, 0>(p, c.wpc, st);
+        return ks == 5 ? launch_persist_ks<1, 8, false, 5>(p, c.wpc, st) : launch_persist_ks<1, 8, false, 14>(p, c.wpc, st);
     }
-    if (NB == 1 && p.ksteps == 5) return launch_persist_ks<NB, MB, WRES, (NB == 1 ? 5 : 0)>(p, wgs_per_cu, st);
-    // 27 linear taps (a 3 x 3 x 3 layer the depth-shift kernels refuse: >= 2^23 voxels per item): 8-deep tiles never fit with
-    // resident weights, so that is the one unrolled form; whatever else turns up runs the runtime k-loop
-    if (NB == 1 && MB == 8 && !WRES && p.ksteps == 14) return launch_persist_ks<NB, MB, WRES, (NB == 1 && MB == 8 && !WRES ? 14 : 0)>(p, wgs_per_cu, st);
-    return launch_persist_ks<NB, MB, WRES, 0>(p, wgs_per_cu, st);
-}
-
-// travelling weights (WRES = false): ksteps is 5 or 14 here (launch_conv3d)
-template <int NB, int MB>
-static int launch_persist_ktaps(const ConvParams &p, int wgs_per_cu, hipStream_t st) {
-    if (p.ksteps == 5) return launch_persist_ks<NB, MB, false, 5>(p, wgs_per_cu, st);
-    if (MB == 8) return launch_persist_ks<NB, MB, false, (MB == 8 ? 14 : 5)>(p, wgs_per_cu, st);
-    return -1;                                                          // 27 taps at four planes fit with resident weights: not reached
+    if (wres) return ks == 5 ? launch_persist_ks<1, 4, true, 5>(p, c.wpc, st) : launch_persist_ks<1, 4, true, 0>(p, c.wpc, st);
+    return launch_persist_ks<1, 4, false, 5>(p, c.wpc, st);
 }
 
 size_t conv3d_lds_bytes(const ConvParams &p, int nb) {
@@ -968,7 +948,6 @@ int conv3d_pick_nb(int nblk) { return (nblk % 4 == 0) ? 4 : (nblk % 2 == 0) ? 2 
 template <int NB>
 static int launch_conv_nb(const ConvParams &p, hipStream_t st) {
     const size_t lds = conv3d_lds_bytes(p, NB);
-    if (lds > 160 * 1024) return -1;
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void *)conv3d_mfma_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -976,45 +955,39 @@ static int launch_conv_nb(const ConvParams &p, hipStream_t st) {
         attr_set = true;
     }
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    fnn_note_kernel("conv3d_mfma_kernel<%d> (generic fallback)", NB);
     hipLaunchKernelGGL(conv3d_mfma_kernel<NB>, grid, dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_conv3d(const ConvParams &p_in, hipStream_t st) {
+static void set_persist(ConvChoice &c, int nb, int mb, int wres, int ks, int ch, int pf, int sbuf, int wpc) {
+    c.kernel = CK_PERSIST;
+    const int t[7] = {nb, mb, wres, ks, ch, pf, sbuf};
+    for (int i = 0; i < 7; ++i) c.t[i] = t[i];
+    c.wpc = wpc;
+    snprintf(c.name, sizeof c.name, "conv3d_persist_kernel<%d,%d,%d,%d,%d,%d,%d>", nb, mb, wres, ks, ch, pf, sbuf);
+}
+
+static void set_ldsk(ConvChoice &c, int nb, int mb, int pf) {
+    c.kernel = CK_LDSK; c.t[0] = nb; c.t[1] = mb; c.t[2] = pf;
+    snprintf(c.name, sizeof c.name, "conv3d_lds_kernel<%d,%d,%d>", nb, mb, pf);
+}
+
+// The linear-tap kernels (FNN_PACK_LINEAR): persistent and one-tile-per-workgroup forms for stride 1, the strided kernels,
+// and the generic kernel that takes every shape.
+static bool conv_choose_linear(const ConvParams &p_in, const ConvOverrides &o, ConvChoice &c) {
     ConvParams p = p_in;
-    {
-        // the kernels address one batch item with 32-bit byte offsets (buffer stores, SGPR base + VGPR offset loads)
-        const unsigned long long out_item = 2ull * p.Do * p.Ho * p.Wo * p.Cout;
-        unsigned long long in_item = 0;
-        for (int i = 0; i < p.n_src; ++i) {
-            const unsigned long long b = 2ull * p.Di * p.Hi * p.Wi * p.src[i].C;
-            in_item = b > in_item ? b : in_item;
-        }
-        if (out_item >= (1ull << 31) || in_item >= (1ull << 32) || (long long)p.Di * p.Hi >= (1 << 24) || p.Wi >= (1 << 24)) return -1;
-    }
-    p.tile_d = FNN_TILE_D;
-    p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D;
+    c.packing = FNN_PACK_LINEAR; c.ksteps = conv3d_ksteps(FNN_PACK_LINEAR, p.kd * p.kh * p.kw); c.chunks = p.chunks;
+    p.ksteps = c.ksteps;
     p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
     p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
-    if (p.packing == FNN_PACK_ZR) return launch_conv3d_zr(p, st);      // weights are in that kernel's order
-    if (p.packing == FNN_PACK_ZP) return launch_conv2d_zp(p, st);
-    {
-        // 16-channel full-resolution (1, 3, 3) layers: the row-streaming kernel (conv3d_row.hip)
-        ThinParams tp{};
-        tp.c = p; tp.fuse = 0;
-        const int rc = launch_conv_row(tp, st);
-        if (rc != -1) return rc;
-    }
+    // decisions use the engine's planned batch, not this call's, so that a layer always runs the same
+    // variant (bit-reproducible statistics whatever the number of patches in the batch)
+    const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
     int nb = conv3d_pick_nb(p.Cout / 16);
-    const bool force_v1 = fnn_knob("FNN_CONV_V1") != nullptr;   // debugging aid, read per call: the test of the generic kernel sets it
-    if (!force_v1 && p.sd == 1 && p.sh == 1 && p.sw == 1) {
+    if (!o.conv_v1 && p.sd == 1 && p.sh == 1 && p.sw == 1) {
         // (cout blocks per workgroup, column blocks per wave): prefer the most work per staged byte,
         // but small feature maps need workgroups first - the deep layers are latency bound otherwise
         const int nblk = p.Cout / 16;
-        // decisions use the engine's planned batch, not this call's, so that a layer always runs the same
-        // variant (bit-reproducible statistics whatever the number of patches in the batch)
-        const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
         // ((4, 4) - four cout blocks per workgroup - kept 44 B of scratch per lane and is gone: round 3)
         const int cand[4][2] = {{2, 8}, {2, 4}, {1, 8}, {1, 4}};
         int pick = -1, best = -1;
@@ -1030,19 +1003,15 @@ int launch_conv3d(const ConvParams &p_in, hipStream_t st) {
         if (pick < 0) pick = best;
         nb = cand[pick][0];
         const int mbsel = cand[pick][1];
-        static const bool no_persist = fnn_knob("FNN_CONV_NO_PERSIST") != nullptr;
         // one cout block only: the NB = 2 / 4 forms need 272-644 B of scratch per lane next to their accumulators
-        if (!no_persist && p.ksteps <= 14 && nb == 1) {
+        if (p.ksteps <= 14 && nb == 1) {
             // persistent variants: a workgroup walks a range of tiles and prefetches across tile boundaries.
             // Weights resident in LDS when the whole cout group fits next to a double-buffered halo tile with
             // 2 workgroups per CU, otherwise they travel with the prefetch chunk by chunk.
-            static const int persist_mb = fnn_knob("FNN_PERSIST_MB") ? atoi(fnn_knob("FNN_PERSIST_MB")) : 8;          // A-B aids
-            static const int persist_wpc = fnn_knob("FNN_PERSIST_WPC") ? atoi(fnn_knob("FNN_PERSIST_WPC")) : 3;
-            for (int mb = mbsel < persist_mb ? mbsel : persist_mb; mb >= 4; mb -= 4) {
+            for (int mb = mbsel; mb >= 4; mb -= 4) {
                 const long long tiles = (long long)plan_n * ((p.Do + mb - 1) / mb) * p.tiles_h * p.tiles_w;
                 if (tiles < 256LL * 2 * 4) continue;
-                static const int persist_wres = fnn_knob("FNN_PERSIST_WRES") ? atoi(fnn_knob("FNN_PERSIST_WRES")) : 1;
-                for (int wres = persist_wres; wres >= 0; --wres) {
+                for (int wres = 1; wres >= 0; --wres) {
                     // travelling weights only for the unrolled forms (9 taps; 27 taps at 8 planes): a 1x1x1 (or 3-tap) layer whose
                     // weights do not fit - more than 800 input channels - takes the one-tile-per-workgroup kernels below (round 3:
                     // instantiations that no shape short of that reached)
@@ -1050,59 +1019,134 @@ int launch_conv3d(const ConvParams &p_in, hipStream_t st) {
                     const size_t lds = persist_lds_bytes(p, nb, mb, wres != 0);
                     const int per_cu = (int)((160 * 1024) / lds);
                     if (per_cu < 2) continue;
-                    const int wpc = per_cu > persist_wpc ? persist_wpc : per_cu;
-#define FNN_PERSIST(NBv, MBv) (wres ? launch_persist<NBv, MBv, true>(p, wpc, st) : launch_persist_ktaps<NBv, MBv>(p, wpc, st))
-                    return mb == 8 ? FNN_PERSIST(1, 8) : FNN_PERSIST(1, 4);
-#undef FNN_PERSIST
+                    const int wpc = per_cu > 3 ? 3 : per_cu;
+                    if (wres && mb == 8 && p.ksteps == 5 && (p.chunks == 1 || p.chunks == 2)) {
+                        // 4-deep tiles with a 4-element prefetch need 138-151 VGPRs and 36 KB of LDS: three workgroups per CU instead
+                        // of two - more bytes in flight for these HBM-bound layers (+0.8 % on the benchmark).  Four (round 2: scale / shift
+                        // through scalar loads, forced to 128 VGPRs: 44-132 B of scratch): 740 -> 895 us per launch; the scalar loads alone,
+                        // at three workgroups: 817 us - SMEM shares lgkmcnt with the LDS reads of the k-loop and returns out of order, so every
+                        // wait becomes a full drain
+                        // (the 8-deep forms of these two were reachable through an A-B knob only and are gone: round 3)
+                        const int ivox4 = (3 * p.sd + p.kd) * ((FNN_TILE_H - 1) * p.sh + p.kh) * ((FNN_TILE_W - 1) * p.sw + p.kw);
+                        if (ivox4 * 2 <= 4 * 256 && persist_lds_bytes(p, 1, 4, true) * 3 <= 160 * 1024) {
+                            set_persist(c, 1, 4, 1, 5, p.chunks, 4, 0, 3);
+                            return true;
+                        }
+                    }
+                    // fully unrolled k-loops for the two common tap counts (9 taps = 5 k-steps, 27 taps = 14); 27 linear taps (a
+                    // 3 x 3 x 3 layer the depth-shift kernels refuse: >= 2^23 voxels per item): 8-deep tiles never fit with resident
+                    // weights, so that is the one unrolled form; whatever else turns up runs the runtime k-loop
+                    set_persist(c, 1, mb, wres, p.ksteps == 5 ? 5 : wres ? 0 : 14, 0, 8, 0, wpc);
+                    return true;
                 }
             }
         }
         if (p.ksteps <= 14) {
-            if (nb == 1) return mbsel == 8 ? launch_ldsk<1, 8>(p, st) : launch_ldsk<1, 4>(p, st);
-            return mbsel == 8 ? launch_ldsk<2, 8>(p, st) : launch_ldsk<2, 4>(p, st);
+            set_ldsk(c, nb, mbsel, 8);
+            return true;
         }
     }
-    const bool strided_v1 = fnn_knob("FNN_CONV_STRIDED_V1") != nullptr;   // A-B aid (per call)
-    if (!force_v1 && !strided_v1) {
-        // stride (2, 2, 2) with whole groups of 64 output channels: one staged halo per group (conv3d_s2.hip)
-        const int rc = launch_conv3d_s2(p, st);
-        if (rc != -1) return rc;
-    }
-    if (!force_v1 && !strided_v1 && p.ksteps <= 14) {
+    if (!o.conv_v1 && s2_choose(p, c)) return true;          // stride (2, 2, 2) with whole groups of 64 output channels (conv3d_s2.hip)
+    if (!o.conv_v1 && p.ksteps <= 14) {
         // strided convs: 2 x 8 x 8 output tile, up to 16 halo elements per thread, <= 2 cout blocks
         const int nbs = (p.Cout / 16) % 2 == 0 ? 2 : 1;
         const int ID = (2 - 1) * p.sd + p.kd, IH = (FNN_TILE_H - 1) * p.sh + p.kh, IW = (FNN_TILE_W - 1) * p.sw + p.kw;
-        {
-            // persistent form (tile ranges, cross-tile prefetch) when every workgroup gets a good number of tiles:
-            // with one tile per workgroup and a single 16-channel chunk nothing hides the halo round trip
-            static const bool no_sp = fnn_knob("FNN_STRIDED_NO_PERSIST") != nullptr;            // A-B aid
-            const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
-            const long long tiles = (long long)plan_n * ((p.Do + 1) / 2) * p.tiles_h * p.tiles_w;
-            const int groups = (p.Cout / 16) / nbs;
-            if (!no_sp && nbs == 2 && ID * IH * IW * 2 <= 12 * 256 && persist_lds_bytes(p, 2, 2, false, false, 12) <= 80 * 1024 &&
-                tiles >= 8LL * (512 / groups) && 512 / groups >= 8) {
-                const int gx = 512 / groups;                       // 2 resident workgroups per CU over all cout groups
-                if (p.chunks == 1) {
-                    // weights resident next to a single halo buffer: the 28 KB of weight fragments no longer travel with
-                    // every 37 KB halo tile (+1 % on the benchmark)
-                    static const bool wres = fnn_knob("FNN_STRIDED_NO_WRES") == nullptr;              // A-B aid
-                    if (wres && persist_lds_bytes(p, 2, 2, true, true, 12) <= 80 * 1024)
-                        return launch_persist_ks<2, 2, true, 0, 1, 12, true>(p, 2, st, gx);
-                }
-                // (the forms whose weights travel with every halo tile - one chunk without room for resident weights,
-                // or several chunks - kept 20 / 48 B of scratch per lane and are gone: those layers take the
-                // one-tile-per-workgroup strided kernels below.  Round 3: no kernel of the library keeps scratch.)
-            }
+        // persistent form (tile ranges, cross-tile prefetch) when every workgroup gets a good number of tiles:
+        // with one tile per workgroup and a single 16-channel chunk nothing hides the halo round trip
+        const long long tiles = (long long)plan_n * ((p.Do + 1) / 2) * p.tiles_h * p.tiles_w;
+        const int groups = (p.Cout / 16) / nbs;
+        // weights resident next to a single halo buffer: the 28 KB of weight fragments no longer travel with every 37 KB halo
+        // tile (+1 % on the benchmark).  (The forms whose weights travel with every halo tile - one chunk without room for
+        // resident weights, or several chunks - kept 20 / 48 B of scratch per lane and are gone: those layers take the
+        // one-tile-per-workgroup strided kernels below.  Round 3: no kernel of the library keeps scratch.)
+        if (nbs == 2 && ID * IH * IW * 2 <= 12 * 256 && persist_lds_bytes(p, 2, 2, false, false, 12) <= 80 * 1024 &&
+            tiles >= 8LL * (512 / groups) && 512 / groups >= 8 && p.chunks == 1 && persist_lds_bytes(p, 2, 2, true, true, 12) <= 80 * 1024) {
+            set_persist(c, 2, 2, 1, 0, 1, 12, 1, 2);
+            c.gx = 512 / groups;                               // 2 resident workgroups per CU over all cout groups
+            return true;
         }
         if (ID * IH * IW * 2 <= 16 * 256 && ldsk_lds_bytes(p, nbs, 2) <= 80 * 1024) {
-            if (ID * IH * IW * 2 <= 8 * 256) return nbs == 2 ? launch_ldsk<2, 2, 8>(p, st) : launch_ldsk<1, 2, 8>(p, st);
-            return nbs == 2 ? launch_ldsk<2, 2, 16>(p, st) : launch_ldsk<1, 2, 16>(p, st);
+            set_ldsk(c, nbs, 2, ID * IH * IW * 2 <= 8 * 256 ? 8 : 16);
+            return true;
         }
     }
-    if (nb == 4) {
-        if (conv3d_lds_bytes(p, 4) <= 160 * 1024) return launch_conv_nb<4>(p, st);
-        return launch_conv_nb<2>(p, st);
+    if (nb == 4 && conv3d_lds_bytes(p, 4) > 160 * 1024) nb = 2;
+    if (conv3d_lds_bytes(p, nb) > 160 * 1024) return false;
+    c.kernel = CK_NB; c.t[0] = nb;
+    snprintf(c.name, sizeof c.name, "conv3d_mfma_kernel<%d> (generic fallback)", nb);
+    return true;
+}
+
+ConvOverrides ConvOverrides::from_env() {
+    ConvOverrides o;
+    o.conv_v1 = fnn_knob("FNN_CONV_V1") != nullptr;           // the test of the generic kernel
+    o.no_row = fnn_knob("FNN_NO_ROW") != nullptr;
+    o.no_stem_row = fnn_knob("FNN_NO_STEM_ROW") != nullptr;
+    o.no_zr6 = fnn_knob("FNN_NO_ZR6") != nullptr;
+    o.no_zq12 = fnn_knob("FNN_NO_ZQ12") != nullptr;           // conv3d_zr12_kernel instead (the tests compare the two kernels' bits)
+    o.no_zsw = fnn_knob("FNN_NO_ZSW") != nullptr;
+    o.no_zp = fnn_knob("FNN_NO_ZP") != nullptr;
+    o.zp_no_half = fnn_knob("FNN_ZP_NO_HALF") != nullptr;
+    o.zps_no_half = fnn_knob("FNN_ZPS_NO_HALF") != nullptr;
+    if (const char *v = fnn_knob("FNN_ZR_MIN_WGS")) o.zr_min_wgs = atoi(v);   // tools/fp8_sensitivity.py
+    if (const char *v = fnn_knob("FNN_FP8_LEVELS")) o.fp8_levels = atoi(v);   // tools/fp8_sensitivity.py
+    return o;
+}
+
+// The order of the families.  A fused layer: the row kernels, else the tile form.  Otherwise the plane kernels (ZP), the
+// depth-shift kernels (ZS / ZR), the row kernels, then the linear-tap kernels.
+bool conv_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c) {
+    c = ConvChoice{};
+    if (tp.fuse) {
+        ConvChoice t;
+        if (!thin_choose(tp, t)) return false;
+        if (!row_choose(tp, o, c)) c = t;
+        return true;
     }
-    if (nb == 2) return launch_conv_nb<2>(p, st);
-    return launch_conv_nb<1>(p, st);
+    const ConvParams &p = tp.c;
+    // the kernels address one batch item with 32-bit byte offsets (buffer stores, SGPR base + VGPR offset loads)
+    const unsigned long long out_item = 2ull * p.Do * p.Ho * p.Wo * p.Cout;
+    unsigned long long in_item = 0;
+    for (int i = 0; i < p.n_src; ++i) {
+        const unsigned long long b = 2ull * p.Di * p.Hi * p.Wi * p.src[i].C;
+        in_item = b > in_item ? b : in_item;
+    }
+    if (out_item >= (1ull << 31) || in_item >= (1ull << 32) || (long long)p.Di * p.Hi >= (1 << 24) || p.Wi >= (1 << 24)) return false;
+    if (zp_choose(p, o, c) || zr_choose(p, o, c)) return true;
+    c = ConvChoice{};
+    return row_choose(tp, o, c) || conv_choose_linear(p, o, c);
+}
+
+int launch_conv(const ThinParams &tp_in, const ConvChoice &c, hipStream_t st) {
+    if (c.kernel == CK_ROW_STEM && tp_in.Y * tp_in.Z >= (1ll << 30)) {
+        // the row form addresses the volume's planes with 32-bit offsets: a volume that large takes the tile form (the one
+        // choice the call makes)
+        ConvChoice t;
+        return thin_choose(tp_in, t) ? launch_conv(tp_in, t, st) : -1;
+    }
+    fnn_note_kernel("%s", c.name);
+    ThinParams tp = tp_in;
+    ConvParams &p = tp.c;
+    p.tile_d = FNN_TILE_D;
+    p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D;
+    p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
+    p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
+    switch (c.kernel) {
+        case CK_ZS: case CK_ZSP: case CK_ZSW: case CK_ZR: case CK_ZR8: case CK_ZQ12: case CK_ZR12: case CK_ZRW:
+            return launch_conv3d_zr(p, c, st);
+        case CK_ZP: case CK_ZPS: return launch_conv2d_zp(p, c, st);
+        case CK_ROW: case CK_ROW_STEM: return launch_conv_row(tp, c, st);
+        case CK_THIN: return launch_conv_thin(tp, c, st);
+        case CK_PERSIST: return launch_persist(p, c, st);
+        case CK_LDSK:
+            if (c.t[1] == 2) {
+                if (c.t[2] == 8) return c.t[0] == 2 ? launch_ldsk<2, 2, 8>(p, st) : launch_ldsk<1, 2, 8>(p, st);
+                return c.t[0] == 2 ? launch_ldsk<2, 2, 16>(p, st) : launch_ldsk<1, 2, 16>(p, st);
+            }
+            if (c.t[0] == 1) return c.t[1] == 8 ? launch_ldsk<1, 8>(p, st) : launch_ldsk<1, 4>(p, st);
+            return c.t[1] == 8 ? launch_ldsk<2, 8>(p, st) : launch_ldsk<2, 4>(p, st);
+        case CK_S2: return launch_conv3d_s2(p, c, st);
+        case CK_NB: return c.t[0] == 4 ? launch_conv_nb<4>(p, st) : c.t[0] == 2 ? launch_conv_nb<2>(p, st) : launch_conv_nb<1>(p, st);
+    }
+    return -1;
 }

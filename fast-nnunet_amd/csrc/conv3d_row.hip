@@ -874,7 +874,6 @@ int launch_row_t(ThinParams tp, hipStream_t st) {
     if (per_cu > cap) per_cu = cap;
     int gx = 256 * per_cu;
     if (gx > total) gx = total;
-    fnn_note_kernel("conv_row_kernel<%d,%d,%d>", NBLK, CH, (int)TCONV);
     hipLaunchKernelGGL((conv_row_kernel<NBLK, CH, TCONV>), dim3(gx), dim3(256), lds, st, tp, total, strips, SH);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -911,7 +910,6 @@ int launch_row_stem_t(ThinParams tp, hipStream_t st) {
     if (per_cu > cap) per_cu = cap;
     int gx = 256 * per_cu;
     if (gx > total) gx = total;
-    fnn_note_kernel("conv_row_stem_kernel<%d>", NBLK);
     hipLaunchKernelGGL((conv_row_stem_kernel<NBLK>), dim3(gx), dim3(256), lds, st, tp, total, strips, SH);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -929,33 +927,40 @@ int launch_row_stem(const ThinParams &tp, hipStream_t st) {
 
 }  // namespace
 
-// Can the row kernel run this layer?  tp.fuse = 0 (plain sources), FUSE_TCONV or FUSE_STEM (the producer then is a
-// one-channel (1, 3, 3) stem whose statistics pass is stem_row_kernel: engine.hip asks stem_row_ok too).
-bool conv_row_ok(const ThinParams &tp) {
-    const bool off = fnn_knob("FNN_NO_ROW") != nullptr;                              // A-B aid (read per call: tests toggle it)
+// The row kernels: 16-channel full-resolution (1, 3, 3) layers on rows of 64 .. 192 voxels.  tp.fuse = 0 (plain sources),
+// FUSE_TCONV or FUSE_STEM (the producer then is a one-channel (1, 3, 3) stem whose statistics pass is stem_row_kernel:
+// engine.hip asks stem_row_ok too).  false: the layer keeps the other kernels.
+bool row_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c) {
     const ConvParams &p = tp.c;
-    if (off || p.Cout != 16 || p.kd != 1 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.sh != 1 || p.sw != 1 || p.fp8) return false;
-    if (p.Di != p.Do || p.Hi != p.Ho || p.Wi != p.Wo || p.packing != FNN_PACK_LINEAR || p.ksteps != 5) return false;
+    if (o.no_row || p.Cout != 16 || p.kd != 1 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.sh != 1 || p.sw != 1 || p.fp8) return false;
+    if (p.Di != p.Do || p.Hi != p.Ho || p.Wi != p.Wo) return false;
     if ((p.Wi != 64 && p.Wi != 96 && p.Wi != 128 && p.Wi != 160 && p.Wi != 192) || p.Hi % 4 != 0 || p.Hi < 8) return false;
-    if (p.stats_out && p.stats_slots != FNN_STAT_REPL) return false;
     if (tp.fuse == FUSE_TCONV) {
         if (p.n_src != 2 || p.chunks != 2 || p.src[1].C != 16 || tp.low.C != 32) return false;
         if (tp.tsd != 1 || tp.tsh != 2 || tp.tsw != 2 || tp.Dl != p.Di || tp.Hl * 2 != p.Hi || tp.Wl * 2 != p.Wi) return false;
-        return true;
+    } else if (tp.fuse == FUSE_STEM) {
+        // (and the volume's planes below 2^30 voxels: launch_conv checks the call's volume)
+        if (o.no_stem_row || p.n_src != 1 || p.chunks != 1 || p.src[0].C != 16) return false;
+    } else {
+        if (tp.fuse != 0 || p.chunks != p.n_src || p.chunks < 1 || p.chunks > 2) return false;
+        for (int i = 0; i < p.n_src; ++i) if (p.src[i].C != 16) return false;
     }
-    if (tp.fuse == FUSE_STEM)
-        return fnn_knob("FNN_NO_STEM_ROW") == nullptr && p.n_src == 1 && p.chunks == 1 && p.src[0].C == 16 && tp.Y * tp.Z < (1ll << 30);
-    if (tp.fuse != 0) return false;
-    if (p.chunks != p.n_src || p.chunks < 1 || p.chunks > 2) return false;
-    for (int i = 0; i < p.n_src; ++i) if (p.src[i].C != 16) return false;
+    c.packing = FNN_PACK_LINEAR; c.ksteps = 5; c.chunks = p.chunks;
+    c.t[0] = p.Wi / 16;
+    if (tp.fuse == FUSE_STEM) {
+        c.kernel = CK_ROW_STEM;
+        snprintf(c.name, sizeof c.name, "conv_row_stem_kernel<%d>", c.t[0]);
+    } else {
+        c.kernel = CK_ROW; c.t[1] = tp.fuse == FUSE_TCONV ? 2 : p.chunks; c.t[2] = tp.fuse == FUSE_TCONV;
+        snprintf(c.name, sizeof c.name, "conv_row_kernel<%d,%d,%d>", c.t[0], c.t[1], c.t[2]);
+    }
     return true;
 }
 
-int launch_conv_row(const ThinParams &tp, hipStream_t st) {
-    if (!conv_row_ok(tp)) return -1;
-    if (tp.fuse == FUSE_TCONV) return launch_row_n<2, true>(tp, st);
-    if (tp.fuse == FUSE_STEM) return launch_row_stem(tp, st);
-    return tp.c.chunks == 1 ? launch_row_n<1, false>(tp, st) : launch_row_n<2, false>(tp, st);
+int launch_conv_row(const ThinParams &tp, const ConvChoice &c, hipStream_t st) {
+    if (c.kernel == CK_ROW_STEM) return launch_row_stem(tp, st);
+    if (c.t[2]) return launch_row_n<2, true>(tp, st);
+    return c.t[1] == 1 ? launch_row_n<1, false>(tp, st) : launch_row_n<2, false>(tp, st);
 }
 
 // stem in row form: one input channel, (1, 3, 3), 16 output channels, rows of 64 / 96 / 128 voxels

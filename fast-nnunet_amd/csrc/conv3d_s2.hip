@@ -341,12 +341,12 @@ __global__ __launch_bounds__(512, 1) void conv3d_s2_kernel(const ConvParams p, c
 
 }  // namespace
 
-bool conv3d_s2_ok(const ConvParams &p) {
-    static const bool off = fnn_knob("FNN_NO_S2") != nullptr;                        // A-B aid
-    if (off || p.kd != 3 || p.kh != 3 || p.kw != 3 || p.sd != 2 || p.sh != 2 || p.sw != 2 || p.fp8) return false;
+// 3x3x3 stride (2, 2, 2) with whole groups of 64 output channels: one staged halo per group.  false: the layer keeps the
+// 2 x 8 x 8 kernels (conv3d.hip)
+bool s2_choose(const ConvParams &p, ConvChoice &c) {
+    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.sd != 2 || p.sh != 2 || p.sw != 2 || p.fp8) return false;
     // whole groups of 64 output channels, or (round 5) a last group of 32: 160 = 64 + 64 + 32
-    if (p.packing != FNN_PACK_LINEAR || p.ksteps != S2_KS || p.Cout % 32 != 0 || p.Cout < 64) return false;
-    if (p.stats_out && p.stats_slots != FNN_STAT_REPL) return false;
+    if (p.Cout % 32 != 0 || p.Cout < 64) return false;
     if ((long long)p.Di * p.Hi * p.Wi >= (1 << 24)) return false;                  // 24-bit voxel index arithmetic in the kernel
     for (int i = 0; i < p.n_src; ++i)
         if (2ull * p.Di * p.Hi * p.Wi * p.src[i].C >= (1ull << 32)) return false;
@@ -355,12 +355,16 @@ bool conv3d_s2_ok(const ConvParams &p) {
     const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
     const long long units = (long long)plan_n * ((p.Do + 3) / 4) * ((p.Ho + 7) / 8) * ((p.Wo + 7) / 8) * ((p.Cout + 63) / 64);
     // (round 5: 384 instead of 768 - the 128 -> 160 layer at 20 x 6 x 6, 480 units, 170 -> 96 us against the 2 x 8 x 8 kernel)
-    static const int min_units = fnn_knob("FNN_S2_MIN_UNITS") ? atoi(fnn_knob("FNN_S2_MIN_UNITS")) : 384;       // A-B aid
-    return units >= min_units;
+    if (units < 384) return false;
+    c.kernel = CK_S2;
+    c.packing = FNN_PACK_LINEAR; c.ksteps = S2_KS; c.chunks = p.chunks;
+    const bool small = p.Ho <= 6 && p.Wo <= 6;                         // one tile per plane, input planes of at most 13 x 13 (with the padding)
+    c.t[0] = small ? 13 : 17; c.t[1] = small ? 3 : 4;
+    snprintf(c.name, sizeof c.name, small ? "conv3d_s2_kernel<13,3>" : "conv3d_s2_kernel");
+    return true;
 }
 
-int launch_conv3d_s2(ConvParams p, hipStream_t st) {
-    if (!conv3d_s2_ok(p)) return -1;
+int launch_conv3d_s2(ConvParams p, const ConvChoice &c, hipStream_t st) {
     p.tile_d = 4;
     p.tiles_d = (p.Do + 3) / 4; p.tiles_h = (p.Ho + 7) / 8; p.tiles_w = (p.Wo + 7) / 8;
     p.ident_ss = conv3d_identity_ss();
@@ -370,14 +374,13 @@ int launch_conv3d_s2(ConvParams p, hipStream_t st) {
     const size_t lds = (size_t)S2_ABYTES + S2_WBYTES + 128 * 8 + 8 * 32 * 2 * 4;
     static const int wgs_knob = fnn_knob("FNN_S2_WGS") ? atoi(fnn_knob("FNN_S2_WGS")) : 256;        // A-B aid: fewer persistent workgroups (CUs left to another stream's kernels)
     const int gx = total < wgs_knob ? total : wgs_knob;
-    const bool small = p.Ho <= 6 && p.Wo <= 6;                         // one tile per plane, input planes of at most 13 x 13 (with the padding)
+    const bool small = c.t[0] == 13;
     static bool attr_set[2] = {false, false};
     if (!attr_set[small]) {
         if (small) (void)hipFuncSetAttribute((const void *)conv3d_s2_kernel<13, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         else (void)hipFuncSetAttribute((const void *)conv3d_s2_kernel<17, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr_set[small] = true;
     }
-    fnn_note_kernel(small ? "conv3d_s2_kernel<13,3>" : "conv3d_s2_kernel");
     if (small) hipLaunchKernelGGL((conv3d_s2_kernel<13, 3>), dim3(gx), dim3(512), lds, st, p, total, groups);
     else hipLaunchKernelGGL((conv3d_s2_kernel<17, 4>), dim3(gx), dim3(512), lds, st, p, total, groups);
     return hipGetLastError() == hipSuccess ? 0 : -2;

@@ -872,8 +872,8 @@ static size_t thin_lds_bytes(int kd, int ch, int fuse, int ncls) {
            (fuse == FUSE_STEM ? (size_t)2 * RVOX * 4 : 0) + 256 + 4 * 16 * 2 * 8;
 }
 
-// Can launch_conv_thin run this layer?  (engine.hip asks before it plans the fusion)
-bool conv_thin_ok(const ThinParams &tp) {
+// Can the tile-form kernels run this fused layer?  (conv_choose asks before it tries the row kernels)
+static bool conv_thin_ok(const ThinParams &tp) {
     const ConvParams &p = tp.c;
     if (p.Cout != 16 || p.kh != 3 || p.kw != 3 || (p.kd != 1 && p.kd != 3) || p.sd != 1 || p.sh != 1 || p.sw != 1) return false;
     if (p.Di != p.Do || p.Hi != p.Ho || p.Wi != p.Wo) return false;
@@ -916,7 +916,6 @@ static int launch_thin_w(ThinParams tp, hipStream_t st) {
     if (per_cu > WPS) per_cu = WPS;
     int gx = 256 * per_cu;
     if (gx > total) gx = total;
-    fnn_note_kernel("conv_thin_kernel<%d,%d,%d,%d,%d>", KD, CH, FUSE, NCLS, WPS);
     hipLaunchKernelGGL((conv_thin_kernel<KD, CH, FUSE, NCLS, WPS>), dim3(gx), dim3(256), lds, st, tp, total);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -929,18 +928,22 @@ static int launch_thin_t(const ThinParams &tp, hipStream_t st) {
     return launch_thin_w<KD, CH, FUSE, NCLS, 2>(tp, st);
 }
 
-int launch_conv_thin(const ThinParams &tp, hipStream_t st) {
-    if (!conv_thin_ok(tp)) return -1;
-    {                                                                    // full rows (and stride (1, 2, 2) for the transposed conv): the row-streaming form
-        const int rc = launch_conv_row(tp, st);
-        if (rc != -1) return rc;
-    }
-    const int kd = tp.c.kd;
-    if (tp.fuse == FUSE_STEM) return kd == 1 ? launch_thin_t<1, 1, FUSE_STEM, 1>(tp, st) : launch_thin_t<3, 1, FUSE_STEM, 1>(tp, st);
+// A fused layer (tp.fuse = FUSE_STEM / FUSE_TCONV) in tile form: kernel depth, chunks, fusion, the transposed conv's stride
+// phases.  false: no kernel takes the fused layer (the engine then keeps the producer a launch of its own).
+bool thin_choose(const ThinParams &tp, ConvChoice &c) {
+    if (!conv_thin_ok(tp)) return false;
+    c.kernel = CK_THIN;
+    c.packing = FNN_PACK_LINEAR; c.ksteps = conv3d_ksteps(FNN_PACK_LINEAR, tp.c.kd * 9); c.chunks = tp.c.chunks;
     // FUSE_TCONV: (1, 3, 3) consumers behind a transposed conv of stride (1, 2, 2) or (2, 2, 2) (conv_thin_ok)
-    switch (tp.tsd * tp.tsh * tp.tsw) {
-        case 4: return launch_thin_t<1, 2, FUSE_TCONV, 4>(tp, st);
-        case 8: return launch_thin_t<1, 2, FUSE_TCONV, 8>(tp, st);
-    }
-    return -1;
+    if (tp.fuse == FUSE_STEM) { c.t[0] = tp.c.kd; c.t[1] = 1; c.t[3] = 1; }
+    else { c.t[0] = 1; c.t[1] = 2; c.t[3] = tp.tsd * tp.tsh * tp.tsw; }
+    c.t[2] = tp.fuse;
+    c.t[4] = 2;
+    snprintf(c.name, sizeof c.name, "conv_thin_kernel<%d,%d,%d,%d,%d>", c.t[0], c.t[1], c.t[2], c.t[3], c.t[4]);
+    return true;
+}
+
+int launch_conv_thin(const ThinParams &tp, const ConvChoice &c, hipStream_t st) {
+    if (tp.fuse == FUSE_STEM) return c.t[0] == 1 ? launch_thin_t<1, 1, FUSE_STEM, 1>(tp, st) : launch_thin_t<3, 1, FUSE_STEM, 1>(tp, st);
+    return c.t[3] == 4 ? launch_thin_t<1, 2, FUSE_TCONV, 4>(tp, st) : launch_thin_t<1, 2, FUSE_TCONV, 8>(tp, st);
 }

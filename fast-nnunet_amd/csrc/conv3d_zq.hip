@@ -301,21 +301,17 @@ __global__ __launch_bounds__(512, 2) void conv3d_zq12_kernel(const ConvParams p)
 
 }  // namespace
 
-// planes of 9 .. 12 x 9 .. 12 voxels, at least 8 deep, an even number of cout blocks; the layer's statistics buffer must have
-// a row per tile (conv3d_stats_slots)
-bool conv3d_zq12_ok(const ConvParams &p) {
-    const bool off = fnn_knob("FNN_NO_ZQ12") != nullptr;                             // A-B aid, read per call (the tests compare the two kernels' bits): conv3d_zr12_kernel instead
-    if (off || p.fp8 || p.packing != FNN_PACK_ZR || p.ksteps != ZQ_KS) return false;
-    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.sh != 1 || p.sw != 1) return false;
-    if ((p.Cout / 16) % 2 != 0 || p.Ho <= 8 || p.Ho > 12 || p.Wo <= 8 || p.Wo > 12 || p.Do < ZQ_TD) return false;
+// planes of 9 .. 12 x 9 .. 12 voxels, at least 8 deep, an even number of cout blocks (a 3x3x3 stride-1 layer the ZR kernels
+// take, zr_choose); the layer's statistics buffer must have a row per tile (stats_slots)
+bool conv3d_zq12_fits(const ConvParams &p, int stats_slots) {
+    if (p.fp8 || (p.Cout / 16) % 2 != 0 || p.Ho <= 8 || p.Ho > 12 || p.Wo <= 8 || p.Wo > 12 || p.Do < ZQ_TD) return false;
     // depth-8 tiles must not waste much more of the layer's depth than conv3d_zr12_kernel's depth-4 tiles do (Do = 10: 16
     // computed slices against 12, and 2 instead of 3 tiles per item to spread over the CUs)
     if (((p.Do + 7) / 8) * 8 * 10 > ((p.Do + 3) / 4) * 4 * 11) return false;
-    return !p.stats_out || p.stats_slots >= (p.Do + ZQ_TD - 1) / ZQ_TD;
+    return stats_slots >= (p.Do + ZQ_TD - 1) / ZQ_TD;
 }
 
 int launch_conv3d_zq12(ConvParams p, hipStream_t st) {
-    if (!conv3d_zq12_ok(p)) return -1;
     p.tile_d = ZQ_TD;
     p.tiles_d = (p.Do + ZQ_TD - 1) / ZQ_TD; p.tiles_h = 1; p.tiles_w = 1;
     static bool attr_set = false;
@@ -327,7 +323,6 @@ int launch_conv3d_zq12(ConvParams p, hipStream_t st) {
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     dim3 grid(p.N * p.tiles_d, (p.Cout / 16) / ZQ_NB);
-    fnn_note_kernel("conv3d_zq12_kernel");
     hipLaunchKernelGGL(conv3d_zq12_kernel, grid, dim3(ZQ_NT), ZQ_LDS, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

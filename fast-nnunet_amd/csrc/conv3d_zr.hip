@@ -39,56 +39,91 @@ int conv3d_pack_cout(int packing, int nblk, int cb, int m) {
     return (cb >> 1) * 32 + (m >> 2) * 8 + (cb & 1) * 4 + (m & 3);
 }
 
-// (cout blocks per workgroup, tile depth) the ZR kernel would run with, or false when the layer keeps the
-// linear-tap kernels: not 3x3x3 / stride 1, or too few workgroups to fill the chip.
-static bool zr_pick(const ConvParams &p, int &nb, int &td, int *th_out = nullptr) {
-    if (th_out) *th_out = 8;
-    static const bool off = fnn_knob("FNN_CONV_NO_ZR") != nullptr;                  // A-B aid
-    static const int max_cout = fnn_knob("FNN_ZR_MAX_COUT") ? atoi(fnn_knob("FNN_ZR_MAX_COUT")) : 1 << 30;
-    static const int min_cout = fnn_knob("FNN_ZR_MIN_COUT") ? atoi(fnn_knob("FNN_ZR_MIN_COUT")) : 0;
-    if (off || p.kd != 3 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.sh != 1 || p.sw != 1) return false;
-    if (p.Cout > max_cout || p.Cout < min_cout) return false;
-    const long long vox = (long long)p.Do * p.Ho * p.Wo;                            // (stride 1: the input's size too; the plan's probe sets only the output's)
+// The depth-shift kernels (FNN_PACK_ZR: 15 k-steps, one statistics row per tile): 3x3x3 layers of depth stride 1 with
+// enough workgroups to fill the chip - in-plane stride 2 on the ZS kernels, stride 1 on the ZR kernels.  false: the layer
+// keeps the other kernels.
+bool zr_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c) {
+    if (p.kd != 3 || p.kh != 3 || p.kw != 3 || p.sd != 1) return false;
+    const int nblk = p.Cout / 16;
+    const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
+    c.packing = FNN_PACK_ZR; c.ksteps = 15; c.chunks = p.chunks;
+    if (p.sh == 2 && p.sw == 2) {
+        // in-plane stride 2: an even number of cout blocks, enough tiles (conv3d_zs_kernel below)
+        if (p.fp8 || nblk % 2 != 0 || (long long)p.Di * p.Hi * p.Wi >= (1 << 23) || p.Do < 8) return false;
+        const int tiles_d = (p.Do + 7) / 8, tiles_h = (p.Ho + 3) / 4, tiles_w = (p.Wo + 7) / 8, groups = nblk / 2;
+        if ((long long)plan_n * tiles_d * tiles_h * tiles_w * (p.Cout / 32) < 768) return false;
+        c.stats_slots = tiles_d * tiles_h * tiles_w;
+        const bool persistent = p.chunks == 1 && p.n_src == 1 && plan_n * c.stats_slots >= 512 * 8;
+        if (persistent && !o.no_zsw && tiles_d >= 4) {
+            // single-chunk layers with at least four tiles along d: the walking form (round 4)
+            const long long cols = (long long)plan_n * tiles_h * tiles_w * groups;
+            int segs = 1;                                     // enough workgroups for several rounds of the chip's 512 slots, tiles permitting
+            while (cols * segs < 8 * 512 && segs * 2 <= tiles_d / 2) segs *= 2;
+            c.tps = (tiles_d + segs - 1) / segs;
+            c.segs = (tiles_d + c.tps - 1) / c.tps;
+            c.kernel = CK_ZSW;
+            snprintf(c.name, sizeof c.name, "conv3d_zsw_kernel");
+        } else if (persistent) {
+            // single-chunk layers: the persistent form (two workgroups per CU over all cout groups)
+            c.gx = 512 / groups < 8 ? 8 : 512 / groups;
+            c.kernel = CK_ZSP;
+            snprintf(c.name, sizeof c.name, "conv3d_zsp_kernel");
+        } else {
+            c.kernel = CK_ZS; c.t[0] = 2;
+            snprintf(c.name, sizeof c.name, "conv3d_zs_kernel<2>");
+        }
+        return true;
+    }
+    if (p.sh != 1 || p.sw != 1) return false;
+    const long long vox = (long long)p.Do * p.Ho * p.Wo;                            // (stride 1: the input's size too)
     if (vox >= (1 << 23)) return false;                                             // 24-bit voxel index arithmetic in the kernels
     // the staging's zero padding is a buffer offset of 0x80000000 that the range check must refuse: every source's batch
     // item (and the output's) stays below 2^31 bytes - bounded here by all input channels together
     if (vox * 32 * (p.chunks > 0 ? p.chunks : 1) >= (1ll << 31) || vox * 2 * p.Cout >= (1ll << 31)) return false;
-    const int nblk = p.Cout / 16;
-    nb = nblk % 2 == 0 ? 2 : 1;
-    const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
-    const long long th = (p.Ho + 7) / 8, tw = (p.Wo + 7) / 8;
+    const int nb = nblk % 2 == 0 ? 2 : 1;
+    const int th = (p.Ho + 7) / 8, tw = (p.Wo + 7) / 8;
     // planes of at most 6 x 8 voxels in a layer whose depth is a multiple of 10 (the 160-channel stages of the benchmark net:
     // 20 x 6 x 6): tiles of 10 x 6 x 8 on three waves (conv3d_zr_kernel<2, 10, 6>) - 75 % of the tile's columns and all of its
     // depth are output voxels (8 x 8 x 8 tiles: 47 %)
-    if (nb == 2 && !p.fp8 && p.Ho <= 6 && p.Wo <= 8 && p.Do >= 10 && p.Do % 10 == 0 && fnn_knob("FNN_NO_ZR6") == nullptr &&
+    if (nb == 2 && !p.fp8 && p.Ho <= 6 && p.Wo <= 8 && p.Do >= 10 && p.Do % 10 == 0 && !o.no_zr6 &&
         (long long)plan_n * (p.Do / 10) * (nblk / 2) >= 160) {
-        td = 10;
-        if (th_out) *th_out = 6;
+        c.stats_slots = ((p.Do + 9) / 10) * th * tw;
+        c.kernel = CK_ZR; c.t[0] = 2; c.t[1] = 10; c.t[2] = 6;
+        snprintf(c.name, sizeof c.name, "conv3d_zr_kernel<%d,%d,%d>", 2, 10, 6);
         return true;
     }
-    static const int td_max = fnn_knob("FNN_ZR_TD") ? atoi(fnn_knob("FNN_ZR_TD")) : 8;       // A-B aid
-    static const int min_wgs = fnn_knob("FNN_ZR_MIN_WGS") ? atoi(fnn_knob("FNN_ZR_MIN_WGS")) : 480;   // one round of 512 slots at TD = 8 beats two of 768 at TD = 4 (stage 4: 70 -> 64 us)
-    for (td = td_max; td >= 4; td -= 4) {
-        if (p.Do < td) continue;
-        if ((long long)plan_n * ((p.Do + td - 1) / td) * th * tw * (nblk / nb) >= min_wgs) return true;
+    // one round of 512 slots at TD = 8 beats two of 768 at TD = 4 (stage 4: 70 -> 64 us)
+    int td = 8;
+    while (td >= 4 && (p.Do < td || (long long)plan_n * ((p.Do + td - 1) / td) * th * tw * (nblk / nb) < o.zr_min_wgs)) td -= 4;
+    if (td < 4) return false;
+    c.stats_slots = ((p.Do + td - 1) / td) * th * tw;
+    c.t[0] = nb; c.t[1] = td;
+    if (p.fp8) {
+        c.kernel = CK_ZR8;
+        snprintf(c.name, sizeof c.name, "conv3d_zr8_kernel<%d,%d>", nb, td);
+    } else if (nb == 2 && !o.no_zq12 && conv3d_zq12_fits(p, c.stats_slots)) {
+        // planes of 9 .. 12 x 9 .. 12 voxels (two half-empty 8 x 8 tiles per axis): whole planes per tile.  Round 5: 8 x 12 x 12
+        // tiles, eight balanced waves (conv3d_zq.hip)
+        c.kernel = CK_ZQ12;
+        snprintf(c.name, sizeof c.name, "conv3d_zq12_kernel");
+    } else if (nb == 2 && p.Ho > 8 && p.Ho <= 12 && p.Wo > 8 && p.Wo <= 12 && c.stats_slots >= (p.Do + 3) / 4) {
+        c.kernel = CK_ZR12; c.t[0] = 4;                                          // (TD = 6: 60 B of scratch, -1.5 %; TD = 8: 140-224 B, -3 %)
+        snprintf(c.name, sizeof c.name, "conv3d_zr12_kernel<%d>", 4);
+    } else if (p.chunks == 1 && td == 8 && (p.Do + 7) / 8 >= 4) {
+        // one chunk (Cin <= 16) and at least four tiles along d: the walking form
+        const int tiles_d = (p.Do + 7) / 8;
+        const long long cols = (long long)plan_n * th * tw * (nblk / nb);
+        int segs = 1;                                         // enough workgroups for two rounds of the chip's slots, tiles permitting
+        while (cols * segs < 2 * 768 && segs * 2 <= tiles_d / 2) segs *= 2;
+        c.tps = (tiles_d + segs - 1) / segs;
+        c.segs = (tiles_d + c.tps - 1) / c.tps;
+        c.kernel = CK_ZRW;
+        snprintf(c.name, sizeof c.name, "conv3d_zrw_kernel<%d>", nb);
+    } else {
+        c.kernel = CK_ZR;
+        snprintf(c.name, sizeof c.name, "conv3d_zr_kernel<%d,%d>", nb, td);
     }
-    return false;
-}
-
-static bool zs_pick(const ConvParams &p);
-
-int conv3d_stats_slots(const ConvParams &p) {
-    int nb, td;
-    if (conv2d_zp_ok(p)) return conv2d_zp_stats_slots(p);
-    if (zs_pick(p)) return ((p.Do + 7) / 8) * ((p.Ho + 3) / 4) * ((p.Wo + 7) / 8);
-    if (!zr_pick(p, nb, td)) return FNN_STAT_REPL;
-    return ((p.Do + td - 1) / td) * ((p.Ho + 7) / 8) * ((p.Wo + 7) / 8);
-}
-
-int conv3d_packing(const ConvParams &p) {
-    int nb, td;
-    if (conv2d_zp_ok(p)) return FNN_PACK_ZP;                  // (1, 3, 3) stride 1, cout blocks in pairs: conv2d_zp.hip
-    return (zs_pick(p) || zr_pick(p, nb, td)) ? FNN_PACK_ZR : FNN_PACK_LINEAR;
+    return true;
 }
 
 // Epilogue of a ZR tile at NB = 2 in the interleaved channel order of conv3d_pack_cout: bias (after `osc` for the fp8
@@ -847,7 +882,6 @@ static int launch_zr12(ConvParams p, hipStream_t st) {
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     dim3 grid(p.N * p.tiles_d, (p.Cout / 16) / 2);
-    fnn_note_kernel("conv3d_zr12_kernel<%d>", TD);
     hipLaunchKernelGGL((conv3d_zr12_kernel<TD>), grid, dim3(576), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -1572,7 +1606,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
     finish(td1 - 1);
 }
 
-static int launch_zs(ConvParams p, hipStream_t st) {
+static int launch_zs(ConvParams p, const ConvChoice &c, hipStream_t st) {
     p.tile_d = 8;
     p.tiles_d = (p.Do + 7) / 8;
     p.tiles_h = (p.Ho + 3) / 4;
@@ -1586,54 +1620,29 @@ static int launch_zs(ConvParams p, hipStream_t st) {
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     const int total = p.N * p.tiles_d * p.tiles_h * p.tiles_w, groups = (p.Cout / 16) / 2;
-    static const bool no_zsp = fnn_knob("FNN_NO_ZSP") != nullptr;                  // A-B aid
-    const int plan_total = (p.plan_N > 0 ? p.plan_N : p.N) * p.tiles_d * p.tiles_h * p.tiles_w;   // the variant is a property of the layer, not of the batch
-    const bool no_zsw = fnn_knob("FNN_NO_ZSW") != nullptr;                         // A-B aid, read per call: a test compares the two kernels in one process
-    if (!no_zsp && !no_zsw && p.chunks == 1 && p.n_src == 1 && plan_total >= 512 * 8 && p.tiles_d >= 4) {
-        // single-chunk layers with at least four tiles along d: the walking form (round 4)
+    if (c.kernel == CK_ZSW) {
         const size_t ldsw = lds - (size_t)2 * 64 + 4 * 32 * 2 * 4;
         static bool attr_w = false;
         if (!attr_w) {
             (void)hipFuncSetAttribute((const void *)conv3d_zsw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr_w = true;
         }
-        const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
-        const long long cols = (long long)plan_n * p.tiles_h * p.tiles_w * groups;
-        int segs = 1;                                         // enough workgroups for several rounds of the chip's 512 slots, tiles permitting
-        while (cols * segs < 8 * 512 && segs * 2 <= p.tiles_d / 2) segs *= 2;
-        const int tps = (p.tiles_d + segs - 1) / segs;
-        segs = (p.tiles_d + tps - 1) / tps;
-        fnn_note_kernel("conv3d_zsw_kernel");
-        hipLaunchKernelGGL(conv3d_zsw_kernel, dim3(p.N * p.tiles_h * p.tiles_w * segs, groups), dim3(256), ldsw, st, p, segs, tps);
+        hipLaunchKernelGGL(conv3d_zsw_kernel, dim3(p.N * p.tiles_h * p.tiles_w * c.segs, groups), dim3(256), ldsw, st, p, c.segs, c.tps);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
-    if (!no_zsp && p.chunks == 1 && p.n_src == 1 && plan_total >= 512 * 8) {
-        // single-chunk layers: the persistent form (two workgroups per CU over all cout groups)
+    if (c.kernel == CK_ZSP) {
         const size_t ldsp = lds - (size_t)2 * 64 + 4 * 32 * 2 * 4;
         static bool attr_p = false;
         if (!attr_p) {
             (void)hipFuncSetAttribute((const void *)conv3d_zsp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr_p = true;
         }
-        int gx = 512 / groups;
-        if (gx < 8) gx = 8;
-        fnn_note_kernel("conv3d_zsp_kernel");
-        hipLaunchKernelGGL(conv3d_zsp_kernel, dim3(gx, groups), dim3(256), ldsp, st, p, total);
+        hipLaunchKernelGGL(conv3d_zsp_kernel, dim3(c.gx, groups), dim3(256), ldsp, st, p, total);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
     dim3 grid(total, groups);
-    fnn_note_kernel("conv3d_zs_kernel<2>");
     hipLaunchKernelGGL((conv3d_zs_kernel<2>), grid, dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// depth stride 1, in-plane stride 2, 3x3x3, an even number of cout blocks, enough tiles: the kernel above
-static bool zs_pick(const ConvParams &p) {
-    static const bool off = fnn_knob("FNN_CONV_NO_ZS") != nullptr;                 // A-B aid
-    if (off || p.kd != 3 || p.kh != 3 || p.kw != 3 || p.sd != 1 || p.sh != 2 || p.sw != 2 || p.fp8) return false;
-    if ((p.Cout / 16) % 2 != 0 || (long long)p.Di * p.Hi * p.Wi >= (1 << 23) || p.Do < 8) return false;
-    const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
-    return (long long)plan_n * ((p.Do + 7) / 8) * ((p.Ho + 3) / 4) * ((p.Wo + 7) / 8) * (p.Cout / 32) >= 768;
 }
 
 // ----------------------------------------------------------------------------
@@ -1846,10 +1855,7 @@ static int launch_zr8(ConvParams p, hipStream_t st) {
     }
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss || !p.oscale) return -2;
-    // one statistics row per tile: a plan that sized the rows for another tiling must not reach this kernel
-    if (p.stats_out && p.stats_slots < p.tiles_d * p.tiles_h * p.tiles_w) return -1;
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    fnn_note_kernel("conv3d_zr8_kernel<%d,%d>", NB, TD);
     hipLaunchKernelGGL((conv3d_zr8_kernel<NB, TD>), grid, dim3(256), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -1874,25 +1880,18 @@ static int launch_zr(ConvParams p, hipStream_t st) {
 #ifdef FNN_TMODE
     p.tmode = getenv("FNN_ZR_TMODE") ? atoi(getenv("FNN_ZR_TMODE")) : 0;     // timing-only proxies (wrong results): tools/zr_tmode.py
 #endif
-    if (TH == 8) fnn_note_kernel("conv3d_zr_kernel<%d,%d>", NB, TD); else fnn_note_kernel("conv3d_zr_kernel<%d,%d,%d>", NB, TD, TH);
     hipLaunchKernelGGL((conv3d_zr_kernel<NB, TD, TH>), grid, dim3(TH * 32), lds, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // the walking form for single-chunk layers: `segs` d-segments of `tps` tiles per in-plane window
 template <int NB>
-static int launch_zrw(ConvParams p, hipStream_t st) {
+static int launch_zrw(ConvParams p, const ConvChoice &c, hipStream_t st) {
     constexpr int TD = 8;
     p.tile_d = TD;
     p.tiles_d = (p.Do + TD - 1) / TD;
     p.tiles_h = (p.Ho + 7) / 8;
     p.tiles_w = (p.Wo + 7) / 8;
-    const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
-    const long long cols = (long long)plan_n * p.tiles_h * p.tiles_w * ((p.Cout / 16) / NB);
-    int segs = 1;                                             // enough workgroups for two rounds of the chip's slots, tiles permitting
-    while (cols * segs < 2 * 768 && segs * 2 <= p.tiles_d / 2) segs *= 2;
-    const int tps = (p.tiles_d + segs - 1) / segs;
-    segs = (p.tiles_d + tps - 1) / tps;
     const size_t lds = (size_t)((TD + 2) * 10 * 12 * 32) + (size_t)NB * 15 * 1024;
     static bool attr_set = false;
     if (!attr_set) {
@@ -1902,9 +1901,8 @@ static int launch_zrw(ConvParams p, hipStream_t st) {
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
-    dim3 grid(p.N * p.tiles_h * p.tiles_w * segs, (p.Cout / 16) / NB);
-    fnn_note_kernel("conv3d_zrw_kernel<%d>", NB);
-    hipLaunchKernelGGL((conv3d_zrw_kernel<NB>), grid, dim3(256), lds, st, p, segs, tps);
+    dim3 grid(p.N * p.tiles_h * p.tiles_w * c.segs, (p.Cout / 16) / NB);
+    hipLaunchKernelGGL((conv3d_zrw_kernel<NB>), grid, dim3(256), lds, st, p, c.segs, c.tps);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1954,28 +1952,21 @@ static int launch_zrw(ConvParams p, hipStream_t st) {
 // * PMC per wave and two-chunk tile (tools/pmc_layer.sh): 480 MFMAs = 7.7 k cycles, ~1280 other vector instructions
 //   before / ~900 after the staging rewrite, 417 scalar, 202 LDS; SQ_WAIT_ANY 15 % of the wave's life, issue stalls
 //   48 %, matrix pipe busy 50 -> 55 %; clock under 30 back-to-back launches 1.80 GHz, inside the network 2.13 GHz.
-// Runs the layer on the ZR kernel; the weights must have been packed as FNN_PACK_ZR (p.packing).
-int launch_conv3d_zr(const ConvParams &p, hipStream_t st) {
-    int nb, td, th;
-    if (p.packing == FNN_PACK_ZR && p.ksteps == 15 && zs_pick(p)) return launch_zs(p, st);
-    if (p.packing != FNN_PACK_ZR || p.ksteps != 15 || !zr_pick(p, nb, td, &th)) return -1;
-    if (th == 6) return launch_zr<2, 10, 6>(p, st);
-    if (p.fp8) {
-        if (nb == 2) return td == 8 ? launch_zr8<2, 8>(p, st) : launch_zr8<2, 4>(p, st);
-        return td == 8 ? launch_zr8<1, 8>(p, st) : launch_zr8<1, 4>(p, st);
+// Runs the layer on the kernel zr_choose chose; the weights are packed as FNN_PACK_ZR.
+int launch_conv3d_zr(ConvParams p, const ConvChoice &c, hipStream_t st) {
+    const int nb = c.t[0], td = c.t[1];
+    switch (c.kernel) {
+        case CK_ZS: case CK_ZSP: case CK_ZSW: return launch_zs(p, c, st);
+        case CK_ZR8:
+            if (nb == 2) return td == 8 ? launch_zr8<2, 8>(p, st) : launch_zr8<2, 4>(p, st);
+            return td == 8 ? launch_zr8<1, 8>(p, st) : launch_zr8<1, 4>(p, st);
+        case CK_ZQ12: return launch_conv3d_zq12(p, st);
+        case CK_ZR12: return launch_zr12<4>(p, st);
+        case CK_ZRW: return nb == 2 ? launch_zrw<2>(p, c, st) : launch_zrw<1>(p, c, st);
+        case CK_ZR:
+            if (c.t[2] == 6) return launch_zr<2, 10, 6>(p, st);
+            if (nb == 2) return td == 8 ? launch_zr<2, 8>(p, st) : launch_zr<2, 4>(p, st);
+            return td == 8 ? launch_zr<1, 8>(p, st) : launch_zr<1, 4>(p, st);
     }
-    {
-        // planes of 9 .. 12 x 9 .. 12 voxels (two half-empty 8 x 8 tiles per axis): whole planes per tile
-        static const bool no_zr12 = fnn_knob("FNN_NO_ZR12") != nullptr;                       // A-B aid
-        if (!no_zr12 && nb == 2 && conv3d_zq12_ok(p)) return launch_conv3d_zq12(p, st);   // round 5: 8 x 12 x 12 tiles, eight balanced waves (conv3d_zq.hip)
-        if (!no_zr12 && nb == 2 && p.Ho > 8 && p.Ho <= 12 && p.Wo > 8 && p.Wo <= 12 && conv3d_stats_slots(p) >= (p.Do + 3) / 4)
-            return launch_zr12<4>(p, st);                                            // (TD = 6: 60 B of scratch, -1.5 %; TD = 8: 140-224 B, -3 %)
-    }
-    {
-        // one chunk (Cin <= 16) and at least four tiles along d: the walking form
-        static const bool no_walk = fnn_knob("FNN_NO_ZRW") != nullptr;                        // A-B aid
-        if (!no_walk && p.chunks == 1 && td == 8 && (p.Do + 7) / 8 >= 4) return nb == 2 ? launch_zrw<2>(p, st) : launch_zrw<1>(p, st);
-    }
-    if (nb == 2) return td == 8 ? launch_zr<2, 8>(p, st) : launch_zr<2, 4>(p, st);
-    return td == 8 ? launch_zr<1, 8>(p, st) : launch_zr<1, 4>(p, st);
+    return -1;
 }

@@ -44,6 +44,8 @@ struct Layer {
     int64_t blob_w = 0, blob_b = 0, blob_g = 0, blob_beta = 0;
     int chunks = 0, ksteps = 0, packing = 0;
     int stats_slots = FNN_STAT_REPL;  // rows per item in the stats buffer: atomics' replicas, or one row per tile
+    ConvChoice cc;                    // CONV: the kernel chosen when the engine was planned (conv_choose); chunks / ksteps / packing /
+                                      // stats_slots above are its
     // conv3d_thin.hip: the stem as one MFMA per 16 voxels (w_off2 = its weight fragment in wpk); a CONV that recomputes
     // its producer while staging (fuse = FUSE_STEM / FUSE_TCONV); a producer whose output is never written (virtual)
     bool mfma_stem = false, virtual_out = false;
@@ -76,13 +78,13 @@ struct fnn_engine {
     int max_batch = 1;
     std::string err;
     bool fuse_enabled = true;               // FNN_NO_FUSE (read when the engine is created) keeps every layer a kernel of its own
-    // FNN_FUSE_STEM / FNN_FUSE_TCONV = 0 | 1.  The transposed-conv fusion is on (+1.2 % on the benchmark).  The stem
+    // FNN_FUSE_STEM = 0 | 1.  The transposed-conv fusion is always on (+1.2 % on the benchmark).  The stem
     // fusion is on where the row-streaming kernels take both halves (conv_row_stem_kernel + stem_row_kernel's statistics
     // pass, conv3d_row.hip); in tile form (FNN_FUSE_STEM=1 forces it) it is built and tested but slower than two kernels:
     // its consumer is instruction-bound (one MFMA per 16 halo voxels needs ~45 instructions around it), 1020 + 340 us
     // per batch against 575 + 756 us unfused.
     int fuse_stem = -1;                     // -1: where the row kernels run it
-    bool fuse_tconv = true;
+    ConvOverrides ov;                       // the test switches of the conv kernels' choice (read when the engine is created)
     std::vector<Layer> layers;
     int head_src = -1;                      // layer feeding the seg head
     int hblocks = 0, head_ksteps = 0;
@@ -400,58 +402,48 @@ int build_plan(fnn_engine *e) {
     e->blob_head_b = blob; blob += a.num_heads;
     e->blob_count = blob;
 
-    // ---- producers recomputed inside their consumer's staging (conv3d_thin.hip)
-    auto thin_probe = [&](const Layer &L, int fuse, const Layer *T) {
+    // The shape facts of a conv layer that its kernel's choice looks at (conv_choose); fuse / T: recomputing its producer T
+    auto conv_shape = [&](const Layer &L, int fuse, const Layer *T) {
         ThinParams tp{};
         ConvParams &q = tp.c;
+        q.plan_N = e->max_batch; q.N = e->max_batch; q.Cout = L.cout_pad;
         q.n_src = L.n_src; q.chunks = (L.cin_pad[0] + (L.n_src > 1 ? L.cin_pad[1] : 0)) / 16;
         q.src[0].C = L.cin_pad[0]; q.src[1].C = L.n_src > 1 ? L.cin_pad[1] : 0;
         q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
         q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
-        q.Cout = L.cout_pad; q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
+        q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
         tp.fuse = fuse;
         if (T) {
             tp.low.C = T->cin_pad[0];
             tp.Dl = T->in_dims[0]; tp.Hl = T->in_dims[1]; tp.Wl = T->in_dims[2];
             tp.tsd = T->s[0]; tp.tsh = T->s[1]; tp.tsw = T->s[2];
         } else { tp.tsd = tp.tsh = tp.tsw = 1; }
-        return conv_thin_ok(tp);
-    };
-    auto row_stem_probe = [&](const Layer &L, const Layer &P) {          // conv_row_stem_kernel + stem_row_kernel (statistics)
-        ThinParams tp{};
-        ConvParams &q = tp.c;
-        q.n_src = 1; q.chunks = L.cin_pad[0] / 16; q.src[0].C = L.cin_pad[0];
-        q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
-        q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
-        q.Cout = L.cout_pad; q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
-        q.packing = FNN_PACK_LINEAR; q.ksteps = conv3d_ksteps(FNN_PACK_LINEAR, L.k[0] * L.k[1] * L.k[2]);
-        tp.fuse = FUSE_STEM;
-        StemParams sp{};
-        sp.C = P.cin_real[0]; sp.kd = P.k[0]; sp.kh = P.k[1]; sp.kw = P.k[2]; sp.Cout = P.cout_pad;
-        sp.PD = P.out_dims[0]; sp.PH = P.out_dims[1]; sp.PW = P.out_dims[2];
-        return conv_row_ok(tp) && stem_row_ok(sp);
+        return tp;
     };
     for (Layer &L : e->layers)
         if (L.type == Layer::STEM) {
             if (!stem_mfma_ok(L.cin_real[0], L.k[0], L.k[1], L.k[2], L.cout_pad)) return fail(e, FNN_E_UNSUPPORTED, "stem conv shape");
             L.mfma_stem = true;
         }
-    if (a.spatial_dims != 2) {
+    // ---- producers recomputed inside their consumer's staging (conv3d_thin.hip, conv3d_row.hip): where a kernel takes the fused layer
+    if (a.spatial_dims != 2 && e->fuse_enabled) {
         std::vector<int> consumers(e->layers.size(), 0);
         for (const Layer &L : e->layers)
             for (int i = 0; i < L.n_src; ++i) if (L.src_layer[i] >= 0) consumers[L.src_layer[i]]++;
-        for (size_t li = 0; li < e->layers.size(); ++li) {
-            Layer &L = e->layers[li];
-            if (!e->fuse_enabled || L.type != Layer::CONV) continue;
-            const int s0 = L.src_layer[0];
-            if (s0 < 0) continue;
-            Layer &P = e->layers[s0];
-            if (e->fuse_stem != 0 && L.n_src == 1 && P.type == Layer::STEM && P.mfma_stem && P.cin_real[0] == 1 && P.cout_pad == 16 &&
-                consumers[s0] == 1 && P.k[0] == L.k[0] &&
-                thin_probe(L, FUSE_STEM, nullptr) && (e->fuse_stem == 1 || row_stem_probe(L, P))) {
-                L.fuse = FUSE_STEM; P.virtual_out = true;
-            } else if (e->fuse_tconv && L.n_src == 2 && P.type == Layer::TCONV && consumers[s0] == 1 && P.cout_pad == 16 && thin_probe(L, FUSE_TCONV, &P)) {
-                L.fuse = FUSE_TCONV; P.virtual_out = true;
+        for (Layer &L : e->layers) {
+            if (L.type != Layer::CONV || L.src_layer[0] < 0) continue;
+            Layer &P = e->layers[L.src_layer[0]];
+            if (consumers[L.src_layer[0]] != 1 || P.cout_pad != 16) continue;
+            ConvChoice c;
+            if (e->fuse_stem != 0 && L.n_src == 1 && P.type == Layer::STEM && P.mfma_stem && P.cin_real[0] == 1 && P.k[0] == L.k[0] &&
+                conv_choose(conv_shape(L, FUSE_STEM, nullptr), e->ov, c)) {
+                // by default only where the row kernels take both halves: conv_row_stem_kernel + stem_row_kernel (statistics)
+                StemParams sp{};
+                sp.C = P.cin_real[0]; sp.kd = P.k[0]; sp.kh = P.k[1]; sp.kw = P.k[2]; sp.Cout = P.cout_pad;
+                sp.PD = P.out_dims[0]; sp.PH = P.out_dims[1]; sp.PW = P.out_dims[2];
+                if (e->fuse_stem == 1 || (c.kernel == CK_ROW_STEM && stem_row_ok(sp))) { L.fuse = FUSE_STEM; L.cc = c; P.virtual_out = true; }
+            } else if (L.n_src == 2 && P.type == Layer::TCONV && conv_choose(conv_shape(L, FUSE_TCONV, &P), e->ov, c)) {
+                L.fuse = FUSE_TCONV; L.cc = c; P.virtual_out = true;
             }
         }
     }
@@ -484,33 +476,27 @@ int build_plan(fnn_engine *e) {
             if (L.mfma_stem) { L.w_off2 = wpk; wpk += (size_t)(L.cout_pad / 16) * stem_mfma_ksteps(L.cin_real[0], L.k[0] * L.k[1] * L.k[2]) * 512; }
         } else if (L.type == Layer::CONV) {
             const int T = L.k[0] * L.k[1] * L.k[2];
-            L.chunks = (L.cin_pad[0] + (L.n_src > 1 ? L.cin_pad[1] : 0)) / 16;
-            {
-                ConvParams q{};                               // the shape facts the launcher's variant choice looks at
-                q.plan_N = e->max_batch; q.N = e->max_batch; q.Cout = L.cout_pad; q.chunks = L.chunks;
-                q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
-                q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
-                q.n_src = L.n_src; q.src[0].C = L.cin_pad[0]; q.src[1].C = L.n_src > 1 ? L.cin_pad[1] : 0;
-                q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
+            if (!L.fuse) {
+                ThinParams tp = conv_shape(L, 0, nullptr);
                 // e4m3 operands: the stride-1 3x3x3 layers the fp8 ZR kernel takes (the strided depth-shift kernel is fp16 only).
-                // The probes see the SAME fp8 flag the launch will carry (the variant choice depends on it: the fp16-only
-                // six-row tiles) - packing, tile depth and statistics rows are then the launch's; a layer the fp8 pick refuses
-                // stays fp16 with whatever that pick gives it.
-                q.fp8 = a.precision == FNN_PREC_F8 && !L.fuse && T == 27 && L.s[0] == 1 && L.s[1] == 1 && L.s[2] == 1 &&
-                        !(L.src_layer[0] >= 0 && e->layers[L.src_layer[0]].type == Layer::GATHER);   // (the network input keeps fp16: the stem was never an fp8 layer)
-                if (q.fp8 && fnn_knob("FNN_FP8_LEVELS")) {
+                // The choice sees the fp8 flag the launch will carry (the fp16-only six-row tiles); a layer the fp8 choice
+                // refuses stays fp16 with whatever that choice gives it.
+                tp.c.fp8 = a.precision == FNN_PREC_F8 && T == 27 && L.s[0] == 1 && L.s[1] == 1 && L.s[2] == 1 &&
+                           !(L.src_layer[0] >= 0 && e->layers[L.src_layer[0]].type == Layer::GATHER);   // (the network input keeps fp16: the stem was never an fp8 layer)
+                if (tp.c.fp8 && e->ov.fp8_levels >= 0) {
                     // sensitivity studies (tools/fp8_sensitivity.py): e4m3 operands only at the resolution levels of the bit mask
                     // (level = how many times the patch's voxel count was divided by ~8 on the way to this layer's output)
                     const double P = (double)a.patch[0] * a.patch[1] * a.patch[2];
                     const int level = (int)std::lround(std::log2(P / (double)ovox) / 3.0);
-                    q.fp8 = ((atoi(fnn_knob("FNN_FP8_LEVELS")) >> level) & 1) != 0;
+                    tp.c.fp8 = ((e->ov.fp8_levels >> level) & 1) != 0;
                 }
-                L.packing = L.fuse ? FNN_PACK_LINEAR : conv3d_packing(q);
-                if (q.fp8 && L.packing != FNN_PACK_ZR) { q.fp8 = 0; L.packing = conv3d_packing(q); }
-                L.fp8 = q.fp8 != 0;
+                bool ok = conv_choose(tp, e->ov, L.cc);
+                if (tp.c.fp8 && L.cc.packing != FNN_PACK_ZR) { tp.c.fp8 = 0; ok = conv_choose(tp, e->ov, L.cc); }
+                if (!ok) return fail(e, FNN_E_UNSUPPORTED, "no conv kernel takes layer %zu (%dx%dx%d, stride %dx%dx%d, %d -> %d channels)",
+                                     (size_t)(&L - e->layers.data()), L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2], tp.c.chunks * 16, L.cout_pad);
+                L.fp8 = tp.c.fp8 != 0;
             }
-            if (L.packing == FNN_PACK_ZP) L.chunks = conv_zp_chunks(L.cin_pad[0], L.n_src > 1 ? L.cin_pad[1] : 0);   // 32-channel chunks
-            L.ksteps = conv3d_ksteps(L.packing, T);
+            L.packing = L.cc.packing; L.chunks = L.cc.chunks; L.ksteps = L.cc.ksteps;
             L.w_off = wpk; wpk += (size_t)(L.cout_pad / 16) * L.chunks * L.ksteps * 512;
         } else if (L.type == Layer::TCONV) {
             const int taps = L.s[0] * L.s[1] * L.s[2];
@@ -522,18 +508,7 @@ int build_plan(fnn_engine *e) {
         if (L.has_norm) { L.gamma_off = fp; fp += L.cout_pad; L.beta_off = fp; fp += L.cout_pad; }
         L.stats_slots = FNN_STAT_REPL;
         if (L.type == Layer::STEM) L.stats_slots = stem_mfma_stats_slots(L.out_dims[0], L.out_dims[1], L.out_dims[2]);
-        else if (L.type == Layer::CONV && L.fuse) L.stats_slots = FNN_STAT_REPL;
-        else if (L.type == Layer::CONV) {
-            ConvParams q{};
-            q.plan_N = e->max_batch; q.N = e->max_batch; q.Cout = L.cout_pad; q.chunks = L.chunks;
-            q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
-            q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
-            q.fp8 = L.fp8;
-            q.n_src = L.n_src; q.src[0].C = L.cin_pad[0]; q.src[1].C = L.n_src > 1 ? L.cin_pad[1] : 0;
-            q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
-            if (L.packing == FNN_PACK_ZP) q.chunks = (L.cin_pad[0] + (L.n_src > 1 ? L.cin_pad[1] : 0)) / 16;
-            L.stats_slots = conv3d_stats_slots(q);
-        }
+        else if (L.type == Layer::CONV) L.stats_slots = L.cc.stats_slots;
         L.stats_off = st; if (L.has_norm) st += (size_t)L.stats_slots * L.cout_pad * 2;
         L.ss_off = ssn; if (L.has_norm) ssn += L.cout_pad;
         L.out_off = act; act += ovox * L.cout_pad;
@@ -803,9 +778,9 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
             p.fp8 = L.fp8; p.oscale = L.fp8 ? fw.fparam + L.oscale_off : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
             p.tile_d = FNN_TILE_D;
             Scope sc(e, st, FAM_CONV, L.flops * nb, L.bytes * nb);
+            ThinParams tp{};
+            tp.c = p; tp.fuse = L.fuse;
             if (L.fuse) {
-                ThinParams tp{};
-                tp.c = p; tp.fuse = L.fuse;
                 const Layer &P = e->layers[L.src_layer[0]];
                 tp.fbias = fw.fparam + P.bias_off;
                 if (L.fuse == FUSE_STEM) {
@@ -819,9 +794,8 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
                     tp.Dl = P.in_dims[0]; tp.Hl = P.in_dims[1]; tp.Wl = P.in_dims[2];
                     tp.tsd = P.s[0]; tp.tsh = P.s[1]; tp.tsw = P.s[2];
                 }
-                rc = launch_conv_thin(tp, st);
-            } else
-            rc = launch_conv3d(p, st);
+            }
+            rc = launch_conv(tp, L.cc, st);
         } else if (L.type == Layer::GATHER) {
             PatchInputParams p{};
             p.vol = vol; p.vol_batch_stride = vol_batch_stride; p.C = L.cin_real[0]; p.Cpad = L.cout_pad;
@@ -1589,28 +1563,38 @@ int fnn_abi_version(void) { return FNN_ABI_VERSION; }
 
 const char *fnn_last_error(const fnn_engine *e) { return e ? e->err.c_str() : g_err.c_str(); }
 
+// up to 64 patches per forward, or - small patches (a 40 x 56 x 40 plan, a 2-D slice) - as many as give a forward 2^27 voxels
+// (64 patches of 128^3), at most 512: the deep layers of a small patch have too few voxels per item to fill the chip
+static int check_max_batch(const fnn_arch_desc *arch, int max_batch) {
+    const long long pv = (long long)arch->patch[0] * arch->patch[1] * arch->patch[2];
+    const long long cap = pv > 0 ? std::max<long long>(64, std::min<long long>(512, (1ll << 27) / pv)) : 64;
+    if (max_batch < 1 || max_batch > cap) return fail(nullptr, FNN_E_INVALID, "max_batch must be 1..%lld for this patch size", cap);
+    return 0;
+}
+
+// the engine's switches (read when it is created) and its layer plan; no HIP call
+static int plan_engine(fnn_engine *e, const fnn_arch_desc *arch, int max_batch) {
+    e->arch = *arch; e->max_batch = max_batch;
+    e->fuse_enabled = fnn_knob("FNN_NO_FUSE") == nullptr;
+    if (const char *v = fnn_knob("FNN_FUSE_STEM")) e->fuse_stem = atoi(v) != 0 ? 1 : 0;
+    e->ov = ConvOverrides::from_env();
+    e->gather_enabled = fnn_knob("FNN_NO_GATHER") == nullptr;
+    if (e->arch.eps <= 0) e->arch.eps = 1e-5f;
+    const int rc = build_plan(e);
+    if (rc != 0) g_err = e->err;
+    return rc;
+}
+
 int fnn_create(const fnn_arch_desc *arch, int device, int max_batch, fnn_engine **out) {
     if (!arch || !out) return fail(nullptr, FNN_E_INVALID, "NULL argument");
-    // up to 64 patches per forward, or - small patches (a 40 x 56 x 40 plan, a 2-D slice) - as many as give a forward 2^27 voxels
-    // (64 patches of 128^3), at most 512: the deep layers of a small patch have too few voxels per item to fill the chip
-    {
-        const long long pv = (long long)arch->patch[0] * arch->patch[1] * arch->patch[2];
-        const long long cap = pv > 0 ? std::max<long long>(64, std::min<long long>(512, (1ll << 27) / pv)) : 64;
-        if (max_batch < 1 || max_batch > cap) return fail(nullptr, FNN_E_INVALID, "max_batch must be 1..%lld for this patch size", cap);
-    }
+    if (int rc = check_max_batch(arch, max_batch)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, FNN_E_HIP, "no HIP device is available: the MI355X engine has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(nullptr, FNN_E_INVALID, "device %d out of range (%d visible)", device, ndev);
     fnn_engine *e = new fnn_engine();
-    e->arch = *arch; e->device = device; e->max_batch = max_batch;
-    e->fuse_enabled = fnn_knob("FNN_NO_FUSE") == nullptr;
-    if (const char *v = fnn_knob("FNN_FUSE_STEM")) e->fuse_stem = atoi(v) != 0 ? 1 : 0;
-    if (const char *v = fnn_knob("FNN_FUSE_TCONV")) e->fuse_tconv = atoi(v) != 0;
-    e->gather_enabled = fnn_knob("FNN_NO_GATHER") == nullptr;
-    if (e->arch.eps <= 0) e->arch.eps = 1e-5f;
-    int rc = build_plan(e);
-    if (rc != 0) { g_err = e->err; delete e; return rc; }
+    e->device = device;
+    if (int rc = plan_engine(e, arch, max_batch)) { delete e; return rc; }
     auto bail = [&](const char *what, hipError_t r) {
         fail(nullptr, FNN_E_HIP, "%s failed: %s", what, hipGetErrorString(r));
         fnn_destroy(e);
@@ -2128,11 +2112,11 @@ int64_t fnn_layer_table(const fnn_engine *e, char *buf, int64_t cap) {
     std::string all;
     for (size_t li = 0; li < e->layers.size(); ++li) {
         const Layer &L = e->layers[li];
-        char row[256];
-        snprintf(row, sizeof row, "%zu\t%s\t%d\t%d\t%dx%dx%d\t%dx%dx%d\t%dx%dx%d\t%dx%dx%d\t%.6g\t%.6g\t%d\n", li, ty[L.type],
+        char row[320];
+        snprintf(row, sizeof row, "%zu\t%s\t%d\t%d\t%dx%dx%d\t%dx%dx%d\t%dx%dx%d\t%dx%dx%d\t%.6g\t%.6g\t%d\t%s\n", li, ty[L.type],
                  L.cin_real[0] + (L.n_src > 1 ? L.cin_real[1] : 0), L.cout_real, L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2],
                  L.in_dims[0], L.in_dims[1], L.in_dims[2], L.out_dims[0], L.out_dims[1], L.out_dims[2], L.flops, L.bytes,
-                 L.virtual_out ? 1 : (L.fuse ? 2 : 0));
+                 L.virtual_out ? 1 : (L.fuse ? 2 : 0), L.type == Layer::CONV ? L.cc.name : "-");
         all += row;
     }
     if (buf && cap > 0) {
@@ -2141,6 +2125,14 @@ int64_t fnn_layer_table(const fnn_engine *e, char *buf, int64_t cap) {
         buf[n] = 0;
     }
     return (int64_t)all.size() + 1;
+}
+
+int64_t fnn_plan_table(const fnn_arch_desc *arch, int max_batch, char *buf, int64_t cap) {
+    if (!arch) return fail(nullptr, FNN_E_INVALID, "NULL argument");
+    if (int rc = check_max_batch(arch, max_batch)) return rc;
+    fnn_engine e;
+    if (int rc = plan_engine(&e, arch, max_batch)) return rc;
+    return fnn_layer_table(&e, buf, cap);
 }
 
 int fnn_patch_work(const fnn_engine *e, double *flops, double *act_bytes) {

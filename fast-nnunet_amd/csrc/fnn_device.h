@@ -92,10 +92,6 @@ struct ConvParams {
 #define FNN_PACK_ZP 2
 int conv_zp_chunks(int cin_pad0, int cin_pad1);
 void conv_zp_pack(const float *W, int cout_real, int cout_pad, int cin_real0, int cin_pad0, int cin_real1, int cin_pad1, unsigned short *dst);
-struct ConvParams;
-bool conv2d_zp_ok(const ConvParams &p);
-int conv2d_zp_stats_slots(const ConvParams &p);
-int launch_conv2d_zp(const ConvParams &p, hipStream_t st);
 
 struct StemParams {
     const float *vol;            // [C][X][Y][Z] fp32 (the padded volume)
@@ -372,22 +368,60 @@ int launch_fss_to_ssh(const float *fss, unsigned short *ssh, long long items, in
 int launch_avgpool(const PoolParams &p, hipStream_t st);
 int launch_combine(const CombineParams &p, hipStream_t st);
 bool combine_pool_ok(int D, int H, int W, int sd, int sh, int sw);     // can the combine launch write the pooled tensor of these strides too
-int launch_conv3d(const ConvParams &p, hipStream_t st);
 size_t conv3d_lds_bytes(const ConvParams &p, int nb);
 int conv3d_pick_nb(int nblk);
 const float *conv3d_identity_ss();
-// packing the launcher will expect for a layer of this shape (decided from the PLANNED batch size)
-int conv3d_packing(const ConvParams &p);
 const unsigned short *conv3d_identity_ssh();
 int conv3d_ksteps(int packing, int taps);
 int conv3d_kstep_tap(int packing, int ks, int half, int taps);     // linear tap index, or -1 = zero padding
 int conv3d_pack_cout(int packing, int nblk, int cb, int m);        // output channel in row m of cout block cb of the packed weights
-int launch_conv3d_zr(const ConvParams &p, hipStream_t st);
-bool conv3d_zq12_ok(const ConvParams &p);                               // conv3d_zq.hip: 3x3x3 stride 1 over planes of 9 .. 12 voxels per axis
-int launch_conv3d_zq12(ConvParams p, hipStream_t st);                  // -1 = not this kernel's layer
-bool conv3d_s2_ok(const ConvParams &p);                                  // conv3d_s2.hip: 3x3x3 stride (2,2,2), Cout % 64 == 0
-int launch_conv3d_s2(ConvParams p, hipStream_t st);                     // -1 = not this kernel's layer
-int conv3d_stats_slots(const ConvParams &p);                           // rows per item the layer's kernel writes into stats_out
+
+// ---- which kernel runs a conv layer: chosen once, from the layer's shape and the PLANNED batch (ConvParams::plan_N) ----
+// conv_choose (conv3d.hip) tries the families in their order; each family's *_choose lives next to its kernels and fills
+// in the variant.  The engine chooses when it is planned (fnn_create) and launches what it chose; the op entry points
+// choose per call.  Grids and tile totals are still computed from the call's N by the launchers.
+enum ConvKernel {
+    CK_NONE, CK_ZS, CK_ZSP, CK_ZSW, CK_ZR, CK_ZR8, CK_ZQ12, CK_ZR12, CK_ZRW,   // conv3d_zr.hip, conv3d_zq.hip (FNN_PACK_ZR)
+    CK_ZP, CK_ZPS,                                                         // conv2d_zp.hip (FNN_PACK_ZP)
+    CK_ROW, CK_ROW_STEM, CK_THIN,                                          // conv3d_row.hip, conv3d_thin.hip
+    CK_PERSIST, CK_LDSK, CK_S2, CK_NB                                      // conv3d.hip, conv3d_s2.hip
+};
+struct ConvChoice {
+    int kernel = CK_NONE;
+    int t[7] = {};                     // the kernel's template arguments, in the order of its name
+    int packing = 0, ksteps = 0, chunks = 0, stats_slots = FNN_STAT_REPL;   // what the weights and statistics rows are sized for
+    int wpc = 0;                       // persistent forms: workgroups per CU
+    int gx = 0;                        // persistent forms with a fixed grid
+    int segs = 0, tps = 0;             // walking forms: d-segments per in-plane window, tiles per segment
+    char name[64] = "";                // the kernel-log string (fnn_kernel_log)
+};
+// The test switches of the choice (fnn_knob), read by the caller where it chooses: ConvOverrides::from_env().
+struct ConvOverrides {
+    bool conv_v1 = false;              // FNN_CONV_V1: the generic kernel
+    bool no_row = false, no_stem_row = false, no_zr6 = false, no_zq12 = false, no_zsw = false, no_zp = false;
+    bool zp_no_half = false, zps_no_half = false;
+    int zr_min_wgs = 480;              // FNN_ZR_MIN_WGS
+    int fp8_levels = -1;               // FNN_FP8_LEVELS: e4m3 operands only at these resolution levels (bit mask; engine plans only)
+    static ConvOverrides from_env();
+};
+// tp.c: the layer's shape (sources' channels, dims, kernel, stride, Cout, fp8, plan_N; chunks = 16-channel chunks);
+// tp.fuse (and the FUSE_TCONV producer's shape) for a fused layer.  false: no kernel takes the layer.
+bool conv_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
+// tp.c carries the choice's packing / ksteps / chunks / stats_slots (and the weights packed for them)
+int launch_conv(const ThinParams &tp, const ConvChoice &c, hipStream_t st);
+// the families (conv_choose's order); a *_choose returns false when the layer is not the family's
+bool zp_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c);
+int launch_conv2d_zp(ConvParams p, const ConvChoice &c, hipStream_t st);
+bool zr_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c);
+int launch_conv3d_zr(ConvParams p, const ConvChoice &c, hipStream_t st);
+bool conv3d_zq12_fits(const ConvParams &p, int stats_slots);          // conv3d_zq.hip: 3x3x3 stride 1 over planes of 9 .. 12 voxels per axis
+int launch_conv3d_zq12(ConvParams p, hipStream_t st);
+bool row_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
+int launch_conv_row(const ThinParams &tp, const ConvChoice &c, hipStream_t st);
+bool thin_choose(const ThinParams &tp, ConvChoice &c);
+int launch_conv_thin(const ThinParams &tp, const ConvChoice &c, hipStream_t st);
+bool s2_choose(const ConvParams &p, ConvChoice &c);
+int launch_conv3d_s2(ConvParams p, const ConvChoice &c, hipStream_t st);
 int launch_tconv(const TconvParams &p, hipStream_t st);
 bool stem_mfma_ok(int C, int kd, int kh, int kw, int cout_pad);
 int stem_mfma_stats_slots(int PD, int PH, int PW);
@@ -397,10 +431,6 @@ int launch_stem_mfma(const StemParams &p, const f16 *wfrag, int N, hipStream_t s
 bool gather_ok(const GatherParams &p);
 int launch_gather(const GatherParams &p, hipStream_t st);
 int launch_quotient_check(unsigned long long *counts, hipStream_t st);   // counts[0] = differing pairs, [1] = pairs on the fast route, [2] = an example
-bool conv_thin_ok(const ThinParams &tp);
-int launch_conv_thin(const ThinParams &tp, hipStream_t st);
-bool conv_row_ok(const ThinParams &tp);                                 // conv3d_row.hip: tp.fuse = 0 or FUSE_TCONV
-int launch_conv_row(const ThinParams &tp, hipStream_t st);             // -1 = not this kernel's layer
 bool stem_row_ok(const StemParams &p);
 int launch_stem_row(const StemParams &p, int N, hipStream_t st);       // -1 = not this kernel's stem
 int launch_head(const HeadParams &p, hipStream_t st);

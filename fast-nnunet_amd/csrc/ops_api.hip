@@ -123,14 +123,17 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     p.pd = (k[0] - 1) / 2; p.ph = (k[1] - 1) / 2; p.pw = (k[2] - 1) / 2;
     p.Do = (p.Di + 2 * p.pd - p.kd) / p.sd + 1; p.Ho = (p.Hi + 2 * p.ph - p.kh) / p.sh + 1; p.Wo = (p.Wi + 2 * p.pw - p.kw) / p.sw + 1;
     p.Cout = cop; p.chunks = (cp1 + cp2) / 16;
-    p.packing = conv3d_packing(p); p.ksteps = conv3d_ksteps(p.packing, T);
-    p.stats_slots = conv3d_stats_slots(p);
+    ThinParams tp{};
+    tp.c = p;
+    ConvChoice cc;                                  // chosen per call, for this call's N (the engine chooses for its planned batch)
+    if (!conv_choose(tp, ConvOverrides::from_env(), cc)) return FNN_E_UNSUPPORTED;
+    p.packing = cc.packing; p.ksteps = cc.ksteps; p.chunks = cc.chunks; p.stats_slots = cc.stats_slots;
+    auto launch = [&]() { tp.c = p; return launch_conv(tp, cc, 0); };
     const size_t slots = (size_t)p.stats_slots;
     p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D; p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
     p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
     p.tile_d = FNN_TILE_D;
     // pack weights [cout][cin_tot][T] -> [cb][chunk][ks][lane][8]
-    if (p.packing == FNN_PACK_ZP) p.chunks = conv_zp_chunks(cp1, cp2);
     std::vector<uint16_t> wp((size_t)(cop / 16) * p.chunks * p.ksteps * 512, 0);
     if (p.packing == FNN_PACK_ZP) conv_zp_pack(w, cout, cop, cin, cp1, x2 ? cin2 : 0, cp2, wp.data());
     else
@@ -168,16 +171,16 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     if (!ddbg.alloc(dbg_n * 8)) return FNN_E_HIP;
     (void)hipMemset(ddbg.p, 0, dbg_n * 8);
     p.dbg = ddbg.as<unsigned long long>();
-    (void)launch_conv3d(p, 0);                      // warm-up
+    (void)launch();                      // warm-up
     (void)hipDeviceSynchronize();
     (void)hipMemset(dst.p, 0, (size_t)n * slots * cop * 16);
 #endif
     if (fnn_knob("FNN_OP_TIME")) {                    // diagnostic: mean duration of 30 launches of this layer (after 2 warm-ups)
         hipEvent_t e0, e1;
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-        for (int i = 0; i < 2; ++i) (void)launch_conv3d(p, 0);
+        for (int i = 0; i < 2; ++i) (void)launch();
         (void)hipEventRecord(e0, 0);
-        for (int i = 0; i < 30; ++i) (void)launch_conv3d(p, 0);
+        for (int i = 0; i < 30; ++i) (void)launch();
         (void)hipEventRecord(e1, 0);
         (void)hipDeviceSynchronize();
         float ms = 0.f;
@@ -191,7 +194,7 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
     (void)hipEventRecord(ev0, 0);
 #endif
-    const int rc = launch_conv3d(p, 0);
+    const int rc = launch();
     if (rc != 0) return rc == -1 ? FNN_E_UNSUPPORTED : FNN_E_HIP;
 #ifdef FNN_STAMPS
     (void)hipEventRecord(ev1, 0);

@@ -355,9 +355,10 @@ typedef struct fnn_profile {
 int fnn_set_profiling(fnn_engine *e, int enabled);
 int fnn_get_profile(const fnn_engine *e, fnn_profile *out);
 /* Which kernel variant served every launch of the last call made while profiling was on (one line per launch, in launch
- * order: "conv3d_zr_kernel<2,8>", "conv_row_kernel<6,1,0>", ...): the launchers choose variants from the layer shape and
- * the planned batch, and a silent fall-back to a generic kernel is otherwise invisible.  Returns the bytes needed
- * (with the terminating 0); writes at most `cap`.  No counterpart in the reference. */
+ * order: "conv3d_zr_kernel<2,8>", "conv_row_kernel<6,1,0>", ...).  A conv layer's kernel is chosen once, when the engine
+ * is created, from the layer shape and the planned batch: its line is the last column of fnn_layer_table, and
+ * fnn_plan_table shows the choice without a GPU.  Returns the bytes needed (with the terminating 0); writes at most
+ * `cap`.  No counterpart in the reference. */
 int64_t fnn_kernel_log(const fnn_engine *e, char *buf, int64_t cap);
 
 /* Per-launch rows of the same profiled call (measurement aid of bench.py --plan / tools/plan_sweep.py; additive in ABI 4,
@@ -366,9 +367,13 @@ int64_t fnn_kernel_log(const fnn_engine *e, char *buf, int64_t cap);
  *   the launch's two HIP events, algorithmic 2*MACs, algorithmic HBM bytes, kernel variant(s) as in fnn_kernel_log.
  * fnn_layer_table describes the layers those indices name: index, type, input channels, output channels, kernel, stride,
  * input dims, output dims, 2*MACs per patch, algorithmic bytes per patch, 1 = computed inside its consumer / 2 = a
- * consumer that recomputes its producer / 0.  Both return the bytes needed and write at most `cap`. */
+ * consumer that recomputes its producer / 0, the kernel chosen for a conv layer as fnn_kernel_log names it (- for other
+ * layers).  Both return the bytes needed and write at most `cap`.
+ * fnn_plan_table: the fnn_layer_table rows of an engine that fnn_create(arch, any device, max_batch) would plan - without
+ * a GPU (additive in ABI 4); a negative FNN_E_* code when that engine could not be created. */
 int64_t fnn_profile_launches(const fnn_engine *e, char *buf, int64_t cap);
 int64_t fnn_layer_table(const fnn_engine *e, char *buf, int64_t cap);
+int64_t fnn_plan_table(const fnn_arch_desc *arch, int max_batch, char *buf, int64_t cap);
 
 /* Algorithmic work of one patch forward: 2*MACs of convs, transposed convs and
  * the seg head; ideal fp16 activation bytes (each activation written once and
