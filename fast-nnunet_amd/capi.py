@@ -65,7 +65,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -120,6 +120,7 @@ def load_library() -> C.CDLL:
     lib.fnn_export_probabilities.argtypes = [vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(i64),
                                              C.POINTER(i32), vp, vp, i32, vp]
     lib.fnn_resample.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleDesc), vp, vp]
+    lib.fnn_keep_largest_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -268,6 +269,19 @@ def resample(in_ptr: int, shape, new_shape, order: int, separate_axis, half: boo
                      FNN_OUT_F16 if half else FNN_OUT_F32)
     check(lib.fnn_resample(in_ptr, (C.c_int64 * 4)(*[int(i) for i in shape]), (C.c_int64 * 3)(*[int(i) for i in new_shape]),
                            C.byref(d), out_ptr, stream), lib)
+
+
+def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, background_label: int,
+                            stream: int = 0):
+    """fnn_keep_largest_components on a device label map [X, Y, Z] in place; returns the voxels removed per set."""
+    lib = load_library()
+    table = np.ascontiguousarray(group_of_label, dtype=np.int32)
+    removed = np.zeros(max(int(n_groups), 1), np.int64)
+    check(lib.fnn_keep_largest_components(labels_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8,
+                                          (C.c_int64 * 3)(*[int(i) for i in shape]),
+                                          table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_groups),
+                                          int(background_label), removed.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
+    return removed[:int(n_groups)]
 
 
 def op_conv3d(x, w, bias, k, stride, gamma=None, beta=None, slope=1.0, x2=None, gamma2=None, beta2=None, slope2=1.0,

@@ -119,6 +119,7 @@ class Engine:
         self.verbose = verbose
         self.config: Optional[EngineConfig] = None
         self.predictor = None
+        self.postprocessing = None
 
     def set_config(self, ini_path: str) -> EngineConfig:
         self.config = load_engine_config(ini_path)
@@ -148,7 +149,19 @@ class Engine:
         pm = PlansManager(plans_with_engine_config(p.plans_manager.plans, name, cfg))
         p.plans_manager = pm
         p.configuration_manager = pm.get_configuration(name)
+        p.set_postprocessing(self.postprocessing)
         self.predictor = p
+
+    def set_postprocessing(self, postprocessing):
+        """Connected-component postprocessing of ``infer``'s label mask (``nnUNetPredictor.set_postprocessing``): the
+        path of a ``postprocessing.pkl``, a ``(pp_fns, pp_fn_kwargs)`` pair, or None (the default).  Kept across
+        ``set_workspace``."""
+        if isinstance(postprocessing, (str, os.PathLike)):
+            from .postprocessing import load_postprocessing_pkl
+            postprocessing = load_postprocessing_pkl(postprocessing)
+        if self.predictor is not None:
+            self.predictor.set_postprocessing(postprocessing)
+        self.postprocessing = postprocessing
 
     def infer(self, image: np.ndarray, spacing: Sequence[float]) -> np.ndarray:
         """``image``: ``[s0, s1, s2]`` or ``[1, s0, s1, s2]`` raw intensities in the axis order the model was

@@ -1,0 +1,210 @@
+"""nnU-Net's connected-component postprocessing on the GPU.
+
+Replaces ``nnunetv2.postprocessing.remove_connected_components`` (postprocessing/remove_connected_components.py):
+``remove_all_but_largest_component_from_segmentation`` (:21-33), ``apply_postprocessing`` (:36-39) and the
+``postprocessing.pkl`` that ``determine_postprocessing`` writes (:221, ``save_pickle((pp_fns, pp_fn_kwargs))``).
+
+The rule implemented (acvl_utils ``remove_all_but_largest_component`` as the reference calls it):
+
+* the mask of a step is ``seg in S``, S the union of ``labels_or_regions`` - an int is one label, a tuple a region
+  (evaluation/evaluate_predictions.py:66-73), a non-list argument one member;
+* the mask is labelled with full connectivity (skimage ``label(connectivity=None)``): 26 neighbours in 3-D, 8 in 2-D;
+* every component whose size equals the largest is kept (ties keep all of them); an empty mask changes nothing;
+* voxels in the mask and not kept become ``background_label``; the input is not modified, dtype and shape are kept.
+
+The labelling is ``fnn_keep_largest_components`` (csrc/postprocess.hip), which handles several disjoint label sets in
+one pass.  ``apply_postprocessing`` fuses consecutive steps into one pass where that gives the sequential result
+(``plan_passes``).  There is no CPU path for this module's own steps.
+"""
+from __future__ import annotations
+
+import io
+import pickle
+from typing import Callable, List, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import capi
+
+REFERENCE_NAME = ('nnunetv2.postprocessing.remove_connected_components',
+                  'remove_all_but_largest_component_from_segmentation')
+
+
+def label_set(labels_or_regions) -> frozenset:
+    """The label set S of one step: the union of its members (remove_connected_components.py:25-29)."""
+    members = labels_or_regions if isinstance(labels_or_regions, list) else [labels_or_regions]
+    out = set()
+    for m in members:
+        if np.isscalar(m) or isinstance(m, (np.integer, int)):
+            out.add(int(m))
+        else:
+            out.update(int(v) for v in m)
+    return frozenset(out)
+
+
+def _is_ours(fn) -> bool:
+    if fn is remove_all_but_largest_component_from_segmentation:
+        return True
+    return (getattr(fn, '__module__', None), getattr(fn, '__qualname__', None)) == REFERENCE_NAME
+
+
+def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> List[Tuple]:
+    """Group the steps into passes, in order.  Returns a list of ``('gpu', [(S, background_label, step), ...])`` and
+    ``('host', step)`` entries.  A step joins the open GPU pass only if its set is disjoint from every set already in
+    it, it has the same ``background_label``, and that background is not in its own set (otherwise voxels an earlier
+    step of the pass set to background would belong to its mask).  Any other callable runs on its own, on the host."""
+    passes: List[Tuple] = []
+    for k, (fn, kw) in enumerate(zip(pp_fns, pp_fn_kwargs)):
+        if not _is_ours(fn):
+            passes.append(('host', k))
+            continue
+        kw = dict(kw)
+        s = label_set(kw['labels_or_regions'])
+        bg = int(kw.get('background_label', 0))
+        cur = passes[-1] if passes and passes[-1][0] == 'gpu' else None
+        if cur is not None and bg not in s and all(bg == b and not (s & t) for t, b, _ in cur[1]):
+            cur[1].append((s, bg, k))
+        else:
+            passes.append(('gpu', [(s, bg, k)]))
+    return passes
+
+
+def _as_device_u(seg: torch.Tensor) -> Tuple[torch.Tensor, bool]:
+    """A contiguous private copy the kernel can work on in place: uint8 stays uint8, anything else is carried as the
+    bits of uint16 in int16 (values checked to lie in 0..65535)."""
+    if seg.dtype == torch.uint8:
+        return seg.clone(memory_format=torch.contiguous_format), False
+    if seg.dtype == torch.bool or seg.dtype.is_floating_point or seg.dtype.is_complex:
+        raise ValueError(f'label maps must have an integer dtype, got {seg.dtype}')
+    if seg.numel():
+        lo, hi = int(seg.min()), int(seg.max())
+        if lo < 0 or hi > 65535:
+            raise ValueError(f'label values must lie in 0..65535 (got {lo}..{hi})')
+    return seg.to(torch.int32).to(torch.int16).contiguous(), True
+
+
+def _run_passes(work: torch.Tensor, u16: bool, groups: List[List[frozenset]], backgrounds: List[int]):
+    """Apply GPU passes in order to the [X, Y, Z] device tensor ``work`` (in place)."""
+    limit = 65536 if u16 else 256
+    with torch.cuda.device(work.device):
+        stream = torch.cuda.current_stream(work.device).cuda_stream
+        for sets, bg in zip(groups, backgrounds):
+            if bg < 0 or bg >= limit:
+                raise ValueError(f'background_label {bg} does not fit the label map ({"uint16" if u16 else "uint8"})')
+            top = max((max(s) for s in sets if s), default=-1)
+            table = np.full(min(max(top + 1, 0), limit), -1, np.int32)
+            for g, s in enumerate(sets):
+                for v in s:
+                    if 0 <= v < limit:
+                        table[v] = g
+            capi.keep_largest_components(work.data_ptr(), u16, work.shape, table, len(sets), bg, stream)
+
+
+def _device_postprocess(seg: torch.Tensor, groups, backgrounds) -> torch.Tensor:
+    """Device tensor (2-D or 3-D) -> new device tensor of the same dtype and shape."""
+    if seg.ndim not in (2, 3):
+        raise ValueError(f'segmentation must be 2-D or 3-D, got shape {tuple(seg.shape)}')
+    work, u16 = _as_device_u(seg)
+    work3 = work.view(1, *work.shape) if work.ndim == 2 else work
+    _run_passes(work3, u16, groups, backgrounds)
+    if not u16:
+        return work
+    return (work.to(torch.int32) & 0xffff).to(seg.dtype)
+
+
+def _device() -> torch.device:
+    if not torch.cuda.is_available():
+        raise RuntimeError('connected-component postprocessing runs on an AMD GPU through the HIP engine; no GPU is visible')
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _postprocess(segmentation, groups, backgrounds):
+    """numpy in -> numpy out (same dtype); torch in -> new torch tensor on the input's device (CUDA work either way)."""
+    if isinstance(segmentation, torch.Tensor):
+        if segmentation.device.type == 'cuda':
+            return _device_postprocess(segmentation, groups, backgrounds)
+        out = _device_postprocess(segmentation.to(_device()), groups, backgrounds)
+        return out.to(segmentation.device)
+    arr = np.asarray(segmentation)
+    if arr.dtype.kind not in 'iu':
+        raise ValueError(f'label maps must have an integer dtype, got {arr.dtype}')
+    if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 65535):
+        raise ValueError(f'label values must lie in 0..65535 (got {int(arr.min())}..{int(arr.max())})')
+    if arr.dtype == np.uint8:
+        t = torch.from_numpy(np.ascontiguousarray(arr))
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32))
+    out = _device_postprocess(t.to(_device()), groups, backgrounds)
+    return out.cpu().numpy().astype(arr.dtype, copy=False)
+
+
+def remove_all_but_largest_component_from_segmentation(segmentation, labels_or_regions: Union[int, Tuple[int, ...],
+                                                                                                List[Union[int, Tuple[int, ...]]]],
+                                                       background_label: int = 0):
+    """Reference signature (remove_connected_components.py:21-33).  ``segmentation``: numpy (returns numpy of the same
+    dtype) or a torch tensor (returns a new tensor on its device), 2-D or 3-D, values 0..65535."""
+    return _postprocess(segmentation, [[label_set(labels_or_regions)]], [int(background_label)])
+
+
+def apply_postprocessing(segmentation, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]):
+    """``apply_postprocessing`` (remove_connected_components.py:36-39): every step in order, consecutive steps of
+    this module fused into one labelling pass where ``plan_passes`` allows it.  Other callables run as they are, on a
+    host (numpy) copy."""
+    is_torch = isinstance(segmentation, torch.Tensor)
+    seg = segmentation
+    gpu: List[Tuple[List[frozenset], int]] = []          # consecutive GPU passes: one upload / download for all of them
+
+    def flush(seg):
+        if gpu:
+            seg = _postprocess(seg, [g for g, _ in gpu], [b for _, b in gpu])
+            gpu.clear()
+        return seg
+
+    for kind, body in plan_passes(pp_fns, pp_fn_kwargs):
+        if kind == 'gpu':
+            gpu.append(([s for s, _, _ in body], body[0][1]))
+            continue
+        seg = flush(seg)
+        host = seg.cpu().numpy() if isinstance(seg, torch.Tensor) else np.asarray(seg)
+        res = np.asarray(pp_fns[body](np.copy(host), **pp_fn_kwargs[body]))
+        seg = torch.from_numpy(res).to(segmentation.device) if is_torch else res
+    seg = flush(seg)
+    if seg is segmentation:              # no step: still a new array, like the reference's copies
+        seg = segmentation.clone() if is_torch else np.copy(segmentation)
+    return seg
+
+
+class _RestrictedUnpickler(pickle.Unpickler):
+    """Reads ``postprocessing.pkl`` without nnunetv2: the reference's function maps onto this module's, numpy scalars
+    and dtypes may be rebuilt, every other global is refused."""
+    _NUMPY = {('numpy', 'dtype'), ('numpy.core.multiarray', 'scalar'), ('numpy._core.multiarray', 'scalar')}
+
+    def find_class(self, module, name):
+        if (module, name) in (REFERENCE_NAME, (__name__, REFERENCE_NAME[1])):      # also a pkl written with this module
+            return remove_all_but_largest_component_from_segmentation
+        if (module, name) in self._NUMPY:
+            return np.dtype if name == 'dtype' else _numpy_scalar
+        raise pickle.UnpicklingError(f'postprocessing.pkl names a global that is not allowed: {module}.{name}')
+
+
+def _numpy_scalar(dtype, data=None):
+    """numpy's scalar reconstructor, limited to plain numeric dtypes."""
+    dtype = np.dtype(dtype)
+    if dtype.kind not in 'biuf' or data is None:
+        raise pickle.UnpicklingError(f'numpy scalar of dtype {dtype} is not allowed in postprocessing.pkl')
+    return np.frombuffer(data, dtype=dtype, count=1)[0]
+
+
+def load_postprocessing_pkl(path_or_bytes) -> Tuple[List[Callable], List[dict]]:
+    """``(pp_fns, pp_fn_kwargs)`` from a reference ``postprocessing.pkl`` (path or bytes)."""
+    if isinstance(path_or_bytes, (bytes, bytearray)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, 'rb') as f:
+            data = f.read()
+    pp_fns, pp_fn_kwargs = _RestrictedUnpickler(io.BytesIO(data)).load()
+    pp_fns, pp_fn_kwargs = list(pp_fns), [dict(k) for k in pp_fn_kwargs]
+    if len(pp_fns) != len(pp_fn_kwargs):
+        raise pickle.UnpicklingError('postprocessing.pkl: as many kwargs as functions expected')
+    return pp_fns, pp_fn_kwargs

@@ -83,6 +83,7 @@ class nnUNetPredictor(object):
         self._engine: Optional[capi.Engine] = None
         self._spec: Optional[ArchSpec] = None
         self._active_fold = 0
+        self._postprocessing = None
 
     # ------------------------------------------------------------------ init
     def initialize_from_trained_model_folder(self, model_training_output_dir: str,
@@ -135,6 +136,28 @@ class nnUNetPredictor(object):
         self.label_manager = plans_manager.get_label_manager(dataset_json)
         self._reduction = None
         self._build_engine()
+
+    def set_postprocessing(self, postprocessing):
+        """Connected-component postprocessing for ``predict_single_npy_array`` (not in the reference's predictor, which
+        leaves it to ``nnUNetv2_apply_postprocessing``): the path of a ``postprocessing.pkl``, a ``(pp_fns,
+        pp_fn_kwargs)`` pair as that file holds, or None (the default: no postprocessing).  The steps run on the device
+        label map on the raw grid, before it is copied to the host; probabilities are never changed."""
+        from .postprocessing import load_postprocessing_pkl
+        if postprocessing is None:
+            self._postprocessing = None
+        elif isinstance(postprocessing, (str, os.PathLike)):
+            self._postprocessing = load_postprocessing_pkl(postprocessing)
+        else:
+            pp_fns, pp_fn_kwargs = postprocessing
+            if len(pp_fns) != len(pp_fn_kwargs):
+                raise ValueError('postprocessing: as many kwargs as functions expected')
+            self._postprocessing = (list(pp_fns), [dict(k) for k in pp_fn_kwargs])
+
+    def _labels_to_host(self, labels: torch.Tensor, u16: bool) -> np.ndarray:
+        if self._postprocessing is not None:
+            from .postprocessing import apply_postprocessing
+            labels = apply_postprocessing(labels, *self._postprocessing)
+        return labels.cpu().numpy().astype(np.uint16 if u16 else np.uint8)
 
     @staticmethod
     def auto_detect_available_folds(model_training_output_dir, checkpoint_name):
@@ -295,7 +318,7 @@ class nnUNetPredictor(object):
         if same_grid and not save_or_return_probabilities:
             seg = self.predict_segmentation_from_preprocessed_data(data)
             out = pp.revert_labels(seg, props, self.plans_manager, self.label_manager)
-            return out.cpu().numpy().astype(np.uint16 if u16 else np.uint8)
+            return self._labels_to_host(out, u16)
         self._check_input(data)
         with torch.cuda.device(self.device):
             logits = torch.empty((self._spec.num_heads, *data.shape[1:]), dtype=torch.half, device=self.device)
@@ -305,10 +328,10 @@ class nnUNetPredictor(object):
         if save_or_return_probabilities:
             out, probs = pp.convert_predicted_logits_to_segmentation_and_probabilities(
                 logits, self, self.plans_manager, self.configuration_manager, props)
-            return out.cpu().numpy().astype(np.uint16 if u16 else np.uint8), probs.cpu().numpy()
+            return self._labels_to_host(out, u16), probs.cpu().numpy()
         out = pp.convert_predicted_logits_to_segmentation_with_correct_shape(logits, self, self.plans_manager,
                                                                              self.configuration_manager, props)
-        return out.cpu().numpy().astype(np.uint16 if u16 else np.uint8)
+        return self._labels_to_host(out, u16)
 
     def _label_rule(self):
         """(regions_class_order or None, uint16?) - LabelManager.convert_logits_to_segmentation

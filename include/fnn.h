@@ -323,6 +323,17 @@ typedef struct fnn_resample_desc {
 int fnn_resample(const void *in, const int64_t shape[4], const int64_t new_shape[3],
                  const fnn_resample_desc *desc, void *out, void *stream);
 
+/* remove_all_but_largest_component_from_segmentation (postprocessing/remove_connected_components.py:21-33) for
+ * disjoint label sets at once (additive in ABI 4): labels [X][Y][Z] (FNN_LABEL_U8 / U16, device pointer) is changed in
+ * place.  group_of_label[v] (host, n_table entries) is the set of label value v, or -1; labels >= n_table are in no
+ * set.  Two 26-neighbours belong to one component iff their labels map to the same set.  Per set, every component
+ * whose size equals the set's largest is kept (ties keep all of them); every other voxel of the set becomes
+ * background_label.  removed (optional host [n_groups]) receives the voxels changed per set.  A zero-size volume
+ * returns 0; more than 2^31 - 1 voxels give FNN_E_UNSUPPORTED.  Scratch: 8 B per voxel, allocated inside the call. */
+int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t shape[3],
+                                const int32_t *group_of_label, int n_table, int n_groups,
+                                int background_label, int64_t *removed, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */
