@@ -65,7 +65,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -121,6 +121,9 @@ def load_library() -> C.CDLL:
                                              C.POINTER(i32), vp, vp, i32, vp]
     lib.fnn_resample.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleDesc), vp, vp]
     lib.fnn_keep_largest_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), vp]
+    lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
+                                        C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
+    lib.fnn_average_probabilities.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(C.c_int32), i64, vp, vp, i32, vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -282,6 +285,40 @@ def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label
                                           table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_groups),
                                           int(background_label), removed.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
     return removed[:int(n_groups)]
+
+
+def _order(regions_class_order, heads: int):
+    if regions_class_order is None:
+        return None
+    assert len(regions_class_order) == heads
+    return (C.c_int32 * heads)(*[int(c) for c in regions_class_order])
+
+
+def ensemble_export(logits_ptrs: Sequence[int], halves: Sequence[bool], heads: int, regions_class_order, bbox,
+                    shape_before_cropping, transpose_backward, avg_ptr: Optional[int], labels_ptr: int, uint16: bool,
+                    stream: int = 0):
+    """fnn_ensemble_export: the members' logits of the cropped grid (one device pointer each; fp16 where `halves`) ->
+    average probabilities (skipped when avg_ptr is None) + labels on the original grid."""
+    lib = load_library()
+    n = len(logits_ptrs)
+    assert len(halves) == n
+    flat = (C.c_int64 * 6)(*[int(v) for ab in bbox for v in ab])
+    check(lib.fnn_ensemble_export((C.c_void_p * max(n, 1))(*[int(p) for p in logits_ptrs]),
+                                  (C.c_int32 * max(n, 1))(*[FNN_OUT_F16 if h else FNN_OUT_F32 for h in halves]), n, int(heads),
+                                  _order(regions_class_order, heads), flat,
+                                  (C.c_int64 * 3)(*[int(i) for i in shape_before_cropping]),
+                                  (C.c_int32 * 3)(*[int(i) for i in transpose_backward]), avg_ptr, labels_ptr,
+                                  FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, stream), lib)
+
+
+def average_probabilities(probs_ptrs: Sequence[int], heads: int, regions_class_order, n_vox: int, avg_ptr: Optional[int],
+                          labels_ptr: int, uint16: bool, stream: int = 0):
+    """fnn_average_probabilities: float32 [heads, n_vox] device buffers -> average (skipped when avg_ptr is None) + labels."""
+    lib = load_library()
+    n = len(probs_ptrs)
+    check(lib.fnn_average_probabilities((C.c_void_p * max(n, 1))(*[int(p) for p in probs_ptrs]), n, int(heads),
+                                        _order(regions_class_order, heads), int(n_vox), avg_ptr, labels_ptr,
+                                        FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, stream), lib)
 
 
 def op_conv3d(x, w, bias, k, stride, gamma=None, beta=None, slope=1.0, x2=None, gamma2=None, beta2=None, slope2=1.0,

@@ -1,0 +1,187 @@
+"""Cross-configuration ensembling on the device (lifted: DESIGN.md section 6).
+
+Mirrors the inference-time half of the reference's ``nnunetv2.ensembling.ensemble`` (ensembling/ensemble.py:16-44):
+
+* ``average_probabilities`` - the float32 mean of several members' probabilities, in member order, bit for bit;
+* ``ensemble_probabilities`` - ``merge_files`` without the image writer: that average and
+  ``LabelManager.convert_logits_to_segmentation`` applied to it;
+* ``nnUNetEnsemblePredictor`` - ``predict_single_npy_array`` for an ensemble of configurations: every member
+  preprocesses the raw case and runs its own sliding window, and one ``fnn_ensemble_export`` call turns all members'
+  resampled logits into the averaged probabilities and the label map, without the ``.npz`` round trip.
+
+Image and file export (``ensemble_folders``, ``merge_files`` with output names) stay the caller's side.
+"""
+from __future__ import annotations
+
+import os
+from typing import List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import capi
+from .predictor import nnUNetPredictor
+
+MAX_MEMBERS = 16
+
+
+def _load_member(f) -> np.ndarray:
+    if isinstance(f, (str, os.PathLike)):
+        with np.load(f, allow_pickle=False) as z:          # object arrays raise ValueError here
+            a = z['probabilities']
+    else:
+        a = np.asarray(f)
+    if a.dtype not in (np.float32, np.float16):
+        raise ValueError(f'probabilities must be float32 or float16, got {a.dtype}')
+    return a
+
+
+def _label_rule(label_manager):
+    order = None
+    if label_manager.has_regions:
+        assert label_manager.regions_class_order is not None, \
+            'if region-based training is requested then you need to define regions_class_order!'
+        order = [int(c) for c in label_manager.regions_class_order]
+    return order, len(label_manager.foreground_labels) >= 255
+
+
+def _average_on_device(list_of_files_or_arrays, order, u16: bool, want_average: bool, device):
+    assert len(list_of_files_or_arrays), 'At least one file must be given in list_of_files'
+    if len(list_of_files_or_arrays) > MAX_MEMBERS:
+        raise ValueError(f'at most {MAX_MEMBERS} members')
+    device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if device.type != 'cuda':
+        raise RuntimeError('ensembling runs on the GPU; there is no CPU path')
+    with torch.cuda.device(device):
+        members, shape = [], None
+        for f in list_of_files_or_arrays:
+            a = _load_member(f)
+            if shape is None:
+                shape = a.shape
+            elif a.shape != shape:
+                raise ValueError(f'members have different shapes: {shape} and {a.shape}')
+            members.append(torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=torch.float32))
+        if len(shape) < 2:
+            raise ValueError('probabilities must have shape (c, x, y(, z))')
+        heads, n_vox = int(shape[0]), int(np.prod(shape[1:]))
+        if order is not None and len(order) != heads:
+            raise ValueError(f'{heads} channels, but {len(order)} entries in regions_class_order')
+        avg = torch.empty(shape, dtype=torch.float32, device=device) if want_average else None
+        labels = torch.empty(shape[1:], dtype=torch.int16 if u16 else torch.uint8, device=device)
+        capi.average_probabilities([m.data_ptr() for m in members], heads, order, n_vox,
+                                   None if avg is None else avg.data_ptr(), labels.data_ptr(), u16,
+                                   torch.cuda.current_stream(device).cuda_stream)
+    return avg, labels
+
+
+@torch.inference_mode()
+def average_probabilities(list_of_files_or_arrays: List[Union[str, np.ndarray]], device=None) -> np.ndarray:
+    """ensemble.py:16-28: ``.npz`` files (their ``probabilities``, loaded without pickle) or arrays -> float32 mean,
+    bit-identical to the reference's numpy loop (p_0 in float32, += p_i in order, /= n)."""
+    avg, _ = _average_on_device(list_of_files_or_arrays, None, False, True, device)
+    return avg.cpu().numpy()
+
+
+@torch.inference_mode()
+def ensemble_probabilities(list_of_files_or_arrays: List[Union[str, np.ndarray]], label_manager,
+                           return_probabilities: bool = False, device=None):
+    """``merge_files`` (ensemble.py:31-44) without the image writer: -> label map (uint8, or uint16 with 255 or more
+    foreground labels), and ``(labels, average)`` with ``return_probabilities``.  For region-based training the
+    reference applies the sigmoid to the averaged probabilities again before ``> 0.5``; so does this."""
+    order, u16 = _label_rule(label_manager)
+    avg, labels = _average_on_device(list_of_files_or_arrays, order, u16, return_probabilities, device)
+    labels = labels.cpu().numpy().view(np.uint16) if u16 else labels.cpu().numpy()
+    return (labels, avg.cpu().numpy()) if return_probabilities else labels
+
+
+def _label_signature(lm):
+    return (bool(lm.has_regions), None if lm.regions_class_order is None else [int(c) for c in lm.regions_class_order],
+            list(lm.all_labels), lm.all_regions, int(lm.num_segmentation_heads), lm.ignore_label)
+
+
+class nnUNetEnsemblePredictor(object):
+    """An ensemble of initialised ``nnUNetPredictor`` members (e.g. ``2d`` + ``3d_fullres``, or ``3d_fullres`` +
+    ``3d_lowres``, as ``nnUNetv2_find_best_configuration`` picks them), predicted on the device.
+
+    Memory: the members' resampled fp16 logits are resident at the same time - N x heads x cropped voxels x 2 B (two
+    members of a 61-class 512^3 case: 32.7 GB) - on top of one member's network-grid logits while it runs; a member's
+    network-grid logits are freed once they are resampled."""
+
+    def __init__(self, predictors: Sequence[nnUNetPredictor]):
+        predictors = list(predictors)
+        if not 1 <= len(predictors) <= MAX_MEMBERS:
+            raise ValueError(f'an ensemble has 1..{MAX_MEMBERS} members, got {len(predictors)}')
+        for p in predictors:
+            if not isinstance(p, nnUNetPredictor) or p.label_manager is None or p.plans_manager is None:
+                raise ValueError('every member must be an initialised nnUNetPredictor')
+        first = predictors[0]
+        for p in predictors[1:]:
+            if p.device != first.device:
+                raise ValueError(f'members on different devices: {first.device} and {p.device}')
+            if _label_signature(p.label_manager) != _label_signature(first.label_manager):
+                raise ValueError('members have different labels / regions: they cannot be averaged')
+            if [int(i) for i in p.plans_manager.transpose_forward] != [int(i) for i in first.plans_manager.transpose_forward]:
+                raise ValueError('members have different transpose_forward: their crops live on different grids')
+        self.predictors = predictors
+        self.device = first.device
+        self.label_manager = first.label_manager
+        self.plans_manager = first.plans_manager
+        self.verbose = first.verbose
+        self._postprocessing = None
+
+    def set_postprocessing(self, postprocessing):
+        """As ``nnUNetPredictor.set_postprocessing``: applied to the ensemble's device label map on the raw grid
+        before it is copied to the host; probabilities are never changed."""
+        nnUNetPredictor.set_postprocessing(self, postprocessing)
+
+    @torch.inference_mode()
+    def predict_single_npy_array(self, input_image: np.ndarray, image_properties: dict,
+                                 segmentation_previous_stage: Optional[Sequence[Optional[np.ndarray]]] = None,
+                                 output_file_truncated: str = None, save_or_return_probabilities: bool = False):
+        """Raw image ``[C, s0, s1, s2]`` + ``{'spacing': ...}`` -> ensembled label map on the raw grid (numpy, uint8 /
+        uint16), or ``(labels, float32 average probabilities [heads, s0, s1, s2])`` with
+        ``save_or_return_probabilities``: what ``merge_files`` makes of the members' exported probabilities.
+        ``segmentation_previous_stage``: None, or one entry per member (None for members that are no cascade stage)."""
+        if output_file_truncated is not None:
+            raise NotImplementedError('image file export is the caller\'s side (SURVEY.md 8: image I/O out of scope)')
+        n = len(self.predictors)
+        prev = [None] * n if segmentation_previous_stage is None else list(segmentation_previous_stage)
+        if len(prev) != n:
+            raise ValueError(f'segmentation_previous_stage: {len(prev)} entries for {n} members')
+        resident, props0 = [], None
+        for p, sp in zip(self.predictors, prev):
+            pp, data, props = p._preprocess_case(input_image, image_properties, sp)
+            if props0 is None:
+                props0 = props
+            elif [list(map(int, b)) for b in props['bbox_used_for_cropping']] != \
+                    [list(map(int, b)) for b in props0['bbox_used_for_cropping']] or \
+                    tuple(props['shape_after_cropping_and_before_resampling']) != \
+                    tuple(props0['shape_after_cropping_and_before_resampling']) or \
+                    tuple(props['shape_before_cropping']) != tuple(props0['shape_before_cropping']):
+                raise RuntimeError('members cropped the case differently: their probabilities cannot be averaged')
+            if self.verbose:
+                print('predicting')
+            logits = p._predict_case_logits(data)
+            del data
+            resident.append(pp.resample_logits_to_cropped_shape(logits, p.plans_manager, p.configuration_manager, props))
+            del logits
+        order, u16 = _label_rule(self.label_manager)
+        before = [int(i) for i in props0['shape_before_cropping']]
+        tb = [int(i) for i in self.plans_manager.transpose_backward]
+        grid = [before[j] for j in tb]
+        with torch.cuda.device(self.device):
+            resident = [lg.contiguous() for lg in resident]
+            avg = torch.empty((resident[0].shape[0], *grid), dtype=torch.float32, device=self.device) \
+                if save_or_return_probabilities else None
+            labels = torch.empty(grid, dtype=torch.int16 if u16 else torch.uint8, device=self.device)
+            capi.ensemble_export([lg.data_ptr() for lg in resident], [lg.dtype == torch.half for lg in resident],
+                                 resident[0].shape[0], order, props0['bbox_used_for_cropping'], before, tb,
+                                 None if avg is None else avg.data_ptr(), labels.data_ptr(), u16,
+                                 torch.cuda.current_stream(self.device).cuda_stream)
+            del resident
+            if u16:
+                labels = labels.to(torch.int32) & 0xffff
+        out = nnUNetPredictor._labels_to_host(self, labels, u16)
+        if save_or_return_probabilities:
+            return out, avg.cpu().numpy()
+        return out

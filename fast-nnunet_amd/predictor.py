@@ -292,9 +292,31 @@ class nnUNetPredictor(object):
         needs no resampling the labels are taken straight from the accumulators (no logits are materialised).
         ``save_or_return_probabilities=True`` returns ``(labels, float32 probabilities [heads, s0, s1, s2])`` like the
         reference (softmax / sigmoid, background probability 1 outside the crop box)."""
-        from .preprocess import DevicePreprocessor
         if output_file_truncated is not None:
             raise NotImplementedError('image file export is the caller\'s side (SURVEY.md 8: image I/O out of scope)')
+        pp, data, props = self._preprocess_case(input_image, image_properties, segmentation_previous_stage)
+        if self.verbose:
+            print('predicting')
+        u16 = len(self.label_manager.foreground_labels) >= 255
+        same_grid = tuple(data.shape[1:]) == tuple(props['shape_after_cropping_and_before_resampling'])
+        if same_grid and not save_or_return_probabilities:
+            seg = self.predict_segmentation_from_preprocessed_data(data)
+            out = pp.revert_labels(seg, props, self.plans_manager, self.label_manager)
+            return self._labels_to_host(out, u16)
+        logits = self._predict_case_logits(data)
+        if self.verbose:
+            print('resampling to original shape')
+        if save_or_return_probabilities:
+            out, probs = pp.convert_predicted_logits_to_segmentation_and_probabilities(
+                logits, self, self.plans_manager, self.configuration_manager, props)
+            return self._labels_to_host(out, u16), probs.cpu().numpy()
+        out = pp.convert_predicted_logits_to_segmentation_with_correct_shape(logits, self, self.plans_manager,
+                                                                             self.configuration_manager, props)
+        return self._labels_to_host(out, u16)
+
+    def _preprocess_case(self, input_image: np.ndarray, image_properties: dict, segmentation_previous_stage=None):
+        """-> (DevicePreprocessor, network input on the device, properties) for predict_single_npy_array."""
+        from .preprocess import DevicePreprocessor
         pp = DevicePreprocessor(self.device, verbose=self.verbose)
         props = dict(image_properties)
         if self.verbose:
@@ -311,27 +333,15 @@ class nnUNetPredictor(object):
             if data.shape[0] != self._spec.in_channels:
                 raise RuntimeError(f'cascade input has {data.shape[0]} channels (image + {len(fg)} foreground labels), '
                                    f'the network expects {self._spec.in_channels}')
-        if self.verbose:
-            print('predicting')
-        u16 = len(self.label_manager.foreground_labels) >= 255
-        same_grid = tuple(data.shape[1:]) == tuple(props['shape_after_cropping_and_before_resampling'])
-        if same_grid and not save_or_return_probabilities:
-            seg = self.predict_segmentation_from_preprocessed_data(data)
-            out = pp.revert_labels(seg, props, self.plans_manager, self.label_manager)
-            return self._labels_to_host(out, u16)
+        return pp, data, props
+
+    def _predict_case_logits(self, data: torch.Tensor) -> torch.Tensor:
+        """fp16 logits [heads, *network grid] on the device, the mean over the folds."""
         self._check_input(data)
         with torch.cuda.device(self.device):
             logits = torch.empty((self._spec.num_heads, *data.shape[1:]), dtype=torch.half, device=self.device)
             self._engine.predict_volume(data.data_ptr(), data.shape, self._opts(), logits.data_ptr(), n_folds=self._n_folds)
-        if self.verbose:
-            print('resampling to original shape')
-        if save_or_return_probabilities:
-            out, probs = pp.convert_predicted_logits_to_segmentation_and_probabilities(
-                logits, self, self.plans_manager, self.configuration_manager, props)
-            return self._labels_to_host(out, u16), probs.cpu().numpy()
-        out = pp.convert_predicted_logits_to_segmentation_with_correct_shape(logits, self, self.plans_manager,
-                                                                             self.configuration_manager, props)
-        return self._labels_to_host(out, u16)
+        return logits
 
     def _label_rule(self):
         """(regions_class_order or None, uint16?) - LabelManager.convert_logits_to_segmentation

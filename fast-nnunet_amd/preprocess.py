@@ -187,11 +187,10 @@ class DevicePreprocessor:
         return self.revert_labels(seg, properties_dict, plans_manager, predictor.label_manager)
 
     @torch.inference_mode()
-    def convert_predicted_logits_to_segmentation_and_probabilities(self, predicted_logits: torch.Tensor, predictor,
-                                                                   plans_manager, configuration_manager,
-                                                                   properties_dict: dict) -> Tuple[torch.Tensor, torch.Tensor]:
-        """export_prediction.py:16-70 with ``return_probabilities=True``: -> (label map, float32 probabilities
-        ``[heads, s0, s1, s2]``), both on the original image grid, both on the device."""
+    def resample_logits_to_cropped_shape(self, predicted_logits: torch.Tensor, plans_manager, configuration_manager,
+                                         properties_dict: dict) -> torch.Tensor:
+        """The resampling step of export_prediction.py:26-35: logits of the network grid ->
+        ``shape_after_cropping_and_before_resampling`` (returned as they are when the grids agree)."""
         spacing_transposed = [properties_dict['spacing'][i] for i in plans_manager.transpose_forward]
         target = list(configuration_manager.spacing)
         cropped = [int(i) for i in properties_dict['shape_after_cropping_and_before_resampling']]
@@ -201,6 +200,16 @@ class DevicePreprocessor:
         logits = predicted_logits
         if [int(i) for i in logits.shape[1:]] != cropped:
             logits = self.resample(logits, cropped, current_spacing, spacing_transposed, kw)
+        return logits
+
+    @torch.inference_mode()
+    def convert_predicted_logits_to_segmentation_and_probabilities(self, predicted_logits: torch.Tensor, predictor,
+                                                                   plans_manager, configuration_manager,
+                                                                   properties_dict: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """export_prediction.py:16-70 with ``return_probabilities=True``: -> (label map, float32 probabilities
+        ``[heads, s0, s1, s2]``), both on the original image grid, both on the device."""
+        logits = self.resample_logits_to_cropped_shape(predicted_logits, plans_manager, configuration_manager,
+                                                       properties_dict)
         order, u16 = predictor._label_rule()
         with torch.cuda.device(self.device):
             lg = logits.to(self.device)

@@ -334,6 +334,25 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
                                 const int32_t *group_of_label, int n_table, int n_groups,
                                 int background_label, int64_t *removed, void *stream);
 
+/* Cross-configuration ensembling (additive in ABI 4): average_probabilities + merge_files without the image writer
+ * (ensembling/ensemble.py:16-44), in one pass from the members' logits.  member_logits[m] (device, host array of
+ * n_members pointers, 1..16) are [heads][bbox extents] of dtype member_dtype[m] (FNN_OUT_F16 / FNN_OUT_F32; members may
+ * differ), the resampled logits fnn_export_probabilities takes.  Member m's probabilities are bit for bit what
+ * fnn_export_probabilities writes for it; the average is p_0 += p_1 ... in member order, then / (float)n_members
+ * (numpy's float32 average_probabilities, bit for bit).  The label rule is convert_logits_to_segmentation of the
+ * average (label_handling.py:183-195): argmax, first maximum wins; for regions sigmoid(average) > 0.5 painted in
+ * regions_class_order - the reference applies the sigmoid a second time, and so does this.
+ * avg_probs (nullable): float32 [heads][shape_before_cropping[transpose_backward[j]]]; labels: the same grid
+ * (FNN_LABEL_U8 / U16).  Synchronises the stream. */
+int fnn_ensemble_export(const void *const *member_logits, const int32_t *member_dtype, int n_members, int heads,
+                        const int32_t *regions_class_order, const int64_t bbox[6], const int64_t shape_before_cropping[3],
+                        const int32_t transpose_backward[3], float *avg_probs, void *labels, int label_dtype, void *stream);
+/* The .npz route (additive in ABI 4): the same average and label rule on member_probs[m], float32 [heads][n_vox] device
+ * buffers on the raw grid.  avg_probs (nullable): float32 [heads][n_vox]; labels [n_vox]. */
+int fnn_average_probabilities(const float *const *member_probs, int n_members, int heads,
+                              const int32_t *regions_class_order, int64_t n_vox, float *avg_probs, void *labels,
+                              int label_dtype, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */
