@@ -65,7 +65,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -124,6 +124,8 @@ def load_library() -> C.CDLL:
     lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
                                         C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
     lib.fnn_average_probabilities.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(C.c_int32), i64, vp, vp, i32, vp]
+    lib.fnn_confusion_counts.argtypes = [vp, C.POINTER(vp), i32, i32, i64, C.POINTER(C.c_int32), i32, i32, i32,
+                                         C.POINTER(i64), vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -285,6 +287,20 @@ def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label
                                           table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_groups),
                                           int(background_label), removed.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
     return removed[:int(n_groups)]
+
+
+def confusion_counts(ref_ptr: int, pred_ptrs: Sequence[int], uint16: bool, n_vox: int, class_of_value, n_classes: int,
+                     ignore_value: int = -1, stream: int = 0) -> np.ndarray:
+    """fnn_confusion_counts on device label maps; returns int64 [n_pred, n_classes + 1, n_classes + 1]."""
+    lib = load_library()
+    table = np.ascontiguousarray(class_of_value, dtype=np.int32)
+    n_pred = len(pred_ptrs)
+    counts = np.zeros((max(n_pred, 1), int(n_classes) + 1, int(n_classes) + 1), np.int64)
+    check(lib.fnn_confusion_counts(ref_ptr, (C.c_void_p * max(n_pred, 1))(*[int(p) for p in pred_ptrs]), n_pred,
+                                   FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, int(n_vox),
+                                   table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_classes),
+                                   int(ignore_value), counts.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
+    return counts[:n_pred]
 
 
 def _order(regions_class_order, heads: int):

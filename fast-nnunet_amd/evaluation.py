@@ -1,0 +1,300 @@
+"""nnU-Net's evaluation of predictions, on label arrays, counted on the GPU.
+
+Replaces ``nnunetv2.evaluation.evaluate_predictions`` (evaluation/evaluate_predictions.py) without the image
+reader-writer: ``compute_metrics`` (:88-118) and the aggregation of ``compute_metrics_on_folder`` (:149-175) take numpy
+arrays or torch tensors, and ``save_summary_json`` / ``load_summary_json`` (:33-60) keep the reference's file format.
+
+Two halves:
+
+* device - ``confusion_counts``: one ``fnn_confusion_counts`` pass (csrc/metrics.hip) turns a reference map and 1..4
+  predicted maps into exact [reference class][predicted class] matrices.  The classes are the distinct label values
+  named by ``labels_or_regions``, in ascending order (``count_classes``), plus "other" for every remaining value;
+* host - ``metrics_from_counts``: every label or region (a tuple is a union of labels) gets TP / FP / FN / TN from the
+  matrix, and the per-case dict is built with the reference's numpy scalar types and expressions, so the floats are
+  bit-identical to the reference's.  This half needs no GPU.
+"""
+from __future__ import annotations
+
+import copy
+import json
+import math
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import capi
+
+LabelOrRegion = Union[int, Tuple[int, ...]]
+MAX_PREDICTIONS_PER_PASS = 4
+
+
+# ---- classes of the count matrix ------------------------------------------------------------------------------------
+def _members(label_or_region) -> List[int]:
+    if np.isscalar(label_or_region) or isinstance(label_or_region, (int, np.integer)):
+        return [int(label_or_region)]
+    return [int(v) for v in label_or_region]
+
+
+def count_classes(labels_or_regions: Sequence[LabelOrRegion]) -> List[int]:
+    """The label values that get a class of their own, ascending; class ``len(result)`` is "other"."""
+    vals = sorted({v for r in labels_or_regions for v in _members(r)})
+    for v in vals:
+        if v < 0 or v > 65535:
+            raise ValueError(f'label {v} is outside 0..65535')
+    if len(vals) > 255:
+        raise ValueError(f'at most 255 distinct labels can be evaluated at once, got {len(vals)}')
+    return vals
+
+
+def class_table(values: Sequence[int]) -> np.ndarray:
+    """class_of_value for fnn_confusion_counts: class index of each label value, -1 for "other"."""
+    table = np.full(max(values) + 1 if len(values) else 0, -1, np.int32)
+    for k, v in enumerate(values):
+        table[v] = k
+    return table
+
+
+# ---- host half: metrics from a count matrix -------------------------------------------------------------------------
+def tp_fp_fn_tn(counts: np.ndarray, classes: Sequence[int]):
+    """(tp, fp, fn, tn) as numpy int64 of the union of ``classes`` (class indices) in one [C+1, C+1] matrix."""
+    counts = np.asarray(counts, dtype=np.int64)
+    inside = np.zeros(counts.shape[0], bool)
+    inside[list(classes)] = True
+    tp = counts[inside][:, inside].sum(dtype=np.int64)
+    fp = counts[~inside][:, inside].sum(dtype=np.int64)
+    fn = counts[inside][:, ~inside].sum(dtype=np.int64)
+    tn = counts[~inside][:, ~inside].sum(dtype=np.int64)
+    return tp, fp, fn, tn
+
+
+def metrics_of(tp, fp, fn, tn) -> dict:
+    """One entry of compute_metrics' ``results['metrics']`` (evaluate_predictions.py:104-117), same expressions."""
+    out = {}
+    if tp + fp + fn == 0:
+        out['Dice'] = np.nan
+        out['IoU'] = np.nan
+    else:
+        out['Dice'] = 2 * tp / (2 * tp + fp + fn)
+        out['IoU'] = tp / (tp + fp + fn)
+    out['FP'] = fp
+    out['TP'] = tp
+    out['FN'] = fn
+    out['TN'] = tn
+    out['n_pred'] = fp + tp
+    out['n_ref'] = fn + tp
+    return out
+
+
+def metrics_from_counts(counts: np.ndarray, labels_or_regions: Sequence[LabelOrRegion]) -> dict:
+    """``{label_or_region: {'Dice', 'IoU', 'FP', 'TP', 'FN', 'TN', 'n_pred', 'n_ref'}}`` from one [C+1, C+1] matrix
+    whose classes are ``count_classes(labels_or_regions)``."""
+    values = count_classes(labels_or_regions)
+    counts = np.asarray(counts)
+    if counts.shape != (len(values) + 1, len(values) + 1):
+        raise ValueError(f'count matrix of shape {counts.shape} does not match {len(values)} classes + other')
+    index = {v: k for k, v in enumerate(values)}
+    return {r: metrics_of(*tp_fp_fn_tn(counts, [index[v] for v in _members(r)])) for r in labels_or_regions}
+
+
+def case_result(metrics: dict, reference_file=None, prediction_file=None) -> dict:
+    return {'reference_file': reference_file, 'prediction_file': prediction_file, 'metrics': metrics}
+
+
+def json_ready(obj):
+    """A copy with numpy scalars as Python numbers, numpy integer keys as int, 1-D arrays and tuples as lists of
+    Python numbers; NaN stays a float.  What compute_metrics_on_folder makes of its results before it returns them."""
+    if isinstance(obj, dict):
+        return {(int(k) if isinstance(k, np.integer) else k): json_ready(v) for k, v in obj.items()}
+    if isinstance(obj, np.ndarray):
+        if obj.ndim != 1:
+            raise ValueError('only 1-D arrays can be exported')
+        return [json_ready(v) for v in obj.tolist()]
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(json_ready(v) for v in obj)
+    if isinstance(obj, np.bool_):
+        return bool(obj)
+    if isinstance(obj, np.integer):
+        return int(obj)
+    if isinstance(obj, np.floating):
+        return float(obj)
+    return obj
+
+
+def aggregate(results: List[dict], labels_or_regions: Sequence[LabelOrRegion]) -> dict:
+    """compute_metrics_on_folder's summary (:149-175) of per-case results: nanmean per class and metric, and
+    ``foreground_mean`` as the mean over every class whose key is not 0."""
+    if not results:
+        raise ValueError('no case to aggregate')
+    metric_list = list(results[0]['metrics'][labels_or_regions[0]].keys())
+    means = {}
+    for r in labels_or_regions:
+        means[r] = {}
+        for m in metric_list:
+            vals = [i['metrics'][r][m] for i in results]
+            if all(isinstance(v, float) and math.isnan(v) for v in vals):
+                means[r][m] = np.float64(np.nan)     # np.nanmean of all-NaN, without its warning
+            else:
+                means[r][m] = np.nanmean(vals)
+    foreground_mean = {}
+    for m in metric_list:
+        values = [means[k][m] for k in means.keys() if not (k == 0 or k == '0')]
+        foreground_mean[m] = np.mean(values)
+    return {'metric_per_case': [json_ready(i) for i in results], 'mean': json_ready(means),
+            'foreground_mean': json_ready(foreground_mean)}
+
+
+# ---- summary.json -----------------------------------------------------------------------------------------------------
+def label_or_region_to_key(label_or_region) -> str:
+    return str(label_or_region)
+
+
+def key_to_label_or_region(key: str):
+    try:
+        return int(key)
+    except ValueError:
+        parts = key.replace('(', '').replace(')', '').split(',')
+        return tuple(int(p) for p in parts if len(p) > 0)
+
+
+def _dump_json(obj, path: str):
+    with open(path, 'w') as f:
+        json.dump(json_ready(obj), f, sort_keys=True, indent=4)
+
+
+def save_summary_json(results: dict, output_file: str):
+    """The reference's summary.json: label / region keys as strings, sorted keys, NaN written as NaN."""
+    out = copy.deepcopy(results)
+    out['mean'] = {label_or_region_to_key(k): v for k, v in results['mean'].items()}
+    for case in out['metric_per_case']:
+        case['metrics'] = {label_or_region_to_key(k): v for k, v in case['metrics'].items()}
+    _dump_json(out, output_file)
+
+
+def load_summary_json(filename: str) -> dict:
+    with open(filename) as f:
+        results = json.load(f)
+    results['mean'] = {key_to_label_or_region(k): v for k, v in results['mean'].items()}
+    for case in results['metric_per_case']:
+        case['metrics'] = {key_to_label_or_region(k): v for k, v in case['metrics'].items()}
+    return results
+
+
+# ---- device half -------------------------------------------------------------------------------------------------------
+def _device() -> torch.device:
+    if not torch.cuda.is_available():
+        raise RuntimeError('evaluation counts on an AMD GPU through the HIP engine; no GPU is visible')
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def check_label_map(seg) -> Tuple[int, int]:
+    """(min, max) of an integer label map with values in 0..65535 (numpy or torch); anything else raises ValueError."""
+    if isinstance(seg, torch.Tensor):
+        if seg.dtype == torch.bool or seg.dtype.is_floating_point or seg.dtype.is_complex:
+            raise ValueError(f'label maps must have an integer dtype, got {seg.dtype}')
+        if seg.numel() == 0:
+            return 0, 0
+        lo, hi = int(seg.min()), int(seg.max())
+    else:
+        arr = np.asarray(seg)
+        if arr.dtype.kind not in 'iu':
+            raise ValueError(f'label maps must have an integer dtype, got {arr.dtype}')
+        if arr.size == 0:
+            return 0, 0
+        lo, hi = int(arr.min()), int(arr.max())
+    if lo < 0 or hi > 65535:
+        raise ValueError(f'label values must lie in 0..65535 (got {lo}..{hi})')
+    return lo, hi
+
+
+def _is_u8(seg) -> bool:
+    return seg.dtype == torch.uint8 if isinstance(seg, torch.Tensor) else np.asarray(seg).dtype == np.uint8
+
+
+def to_device_labels(seg, u16: bool, device: torch.device) -> torch.Tensor:
+    """A flat, contiguous, 16-byte aligned device tensor the kernel reads: uint8, or uint16 bits in int16.  A device
+    uint8 map is used in place when it already is one; the caller's map is never written."""
+    if isinstance(seg, torch.Tensor):
+        t = seg if seg.device.type == 'cuda' else seg.to(device)
+    else:
+        arr = np.asarray(seg)
+        t = torch.from_numpy(np.ascontiguousarray(arr if arr.dtype == np.uint8 else arr.astype(np.int32))).to(device)
+    if u16:
+        t = t.to(torch.int32).to(torch.int16) if t.dtype != torch.int16 else t
+    elif t.dtype != torch.uint8:
+        t = t.to(torch.uint8)
+    t = t.reshape(-1)
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def _shape(seg) -> tuple:
+    return tuple(seg.shape) if isinstance(seg, torch.Tensor) else np.shape(seg)
+
+
+def confusion_counts(seg_ref, seg_preds: Sequence, values: Sequence[int], ignore_label: Optional[int] = None,
+                     checked: bool = False) -> np.ndarray:
+    """Exact int64 [len(seg_preds), C + 1, C + 1] matrices [reference class][predicted class] of ``seg_ref`` against
+    every map in ``seg_preds``; class k is label value ``values[k]``, class C = len(values) every other value.
+    Reference voxels equal to ``ignore_label`` are not counted.  The reference map is read once per 4 predictions."""
+    if len(seg_preds) == 0:
+        raise ValueError('at least one prediction is needed')
+    maps = [seg_ref] + list(seg_preds)
+    for s in maps[1:]:
+        if _shape(s) != _shape(seg_ref):
+            raise ValueError(f'shape mismatch: reference {_shape(seg_ref)}, prediction {_shape(s)}')
+    if not checked:
+        for s in maps:
+            check_label_map(s)
+    u16 = not all(_is_u8(s) for s in maps)
+    values = list(values)
+    table = class_table(values)
+    ignore = -1 if ignore_label is None else int(ignore_label)
+    dev = next((s.device for s in maps if isinstance(s, torch.Tensor) and s.device.type == 'cuda'), None) or _device()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ref = to_device_labels(seg_ref, u16, dev)
+        out = []
+        for k in range(0, len(seg_preds), MAX_PREDICTIONS_PER_PASS):
+            preds = [to_device_labels(p, u16, dev) for p in seg_preds[k:k + MAX_PREDICTIONS_PER_PASS]]
+            out.append(capi.confusion_counts(ref.data_ptr(), [p.data_ptr() for p in preds], u16, ref.numel(), table,
+                                             len(values), ignore, stream))
+    return np.concatenate(out, axis=0)
+
+
+def _check_ignore(labels_or_regions, ignore_label):
+    if ignore_label is not None and any(int(ignore_label) in _members(r) for r in labels_or_regions):
+        raise ValueError(f'ignore label {ignore_label} is also one of the evaluated labels')
+
+
+def compute_metrics(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None,
+                    reference_file=None, prediction_file=None) -> dict:
+    """compute_metrics (evaluate_predictions.py:88-118) with arrays in place of the files: numpy arrays or torch
+    tensors of one shape (the reference's [1, X, Y, Z] included), integer labels 0..65535."""
+    labels_or_regions = list(labels_or_regions)
+    _check_ignore(labels_or_regions, ignore_label)
+    counts = confusion_counts(seg_ref, [seg_pred], count_classes(labels_or_regions), ignore_label)[0]
+    return case_result(metrics_from_counts(counts, labels_or_regions), reference_file, prediction_file)
+
+
+def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions: Sequence[LabelOrRegion],
+                              ignore_label: Optional[int] = None, names: Optional[Sequence[str]] = None,
+                              output_file: Optional[str] = None) -> dict:
+    """compute_metrics_on_folder (evaluate_predictions.py:121-177) on pairs of arrays: ``preds[i]`` is evaluated
+    against ``refs[i]``; ``names[i]`` (optional) fills reference_file / prediction_file.  Returns
+    ``{'metric_per_case', 'mean', 'foreground_mean'}``; writes it to ``output_file`` (.json) when given."""
+    if output_file is not None and not output_file.endswith('.json'):
+        raise ValueError('output_file should end with .json')
+    if len(refs) != len(preds):
+        raise ValueError(f'{len(refs)} references for {len(preds)} predictions')
+    if names is not None and len(names) != len(preds):
+        raise ValueError('one name per case expected')
+    labels_or_regions = list(labels_or_regions)
+    results = [compute_metrics(r, p, labels_or_regions, ignore_label,
+                               None if names is None else names[i], None if names is None else names[i])
+               for i, (r, p) in enumerate(zip(refs, preds))]
+    summary = aggregate(results, labels_or_regions)
+    if output_file is not None:
+        save_summary_json(summary, output_file)
+    return summary

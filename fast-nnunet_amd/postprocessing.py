@@ -208,3 +208,11 @@ def load_postprocessing_pkl(path_or_bytes) -> Tuple[List[Callable], List[dict]]:
     if len(pp_fns) != len(pp_fn_kwargs):
         raise pickle.UnpicklingError('postprocessing.pkl: as many kwargs as functions expected')
     return pp_fns, pp_fn_kwargs
+
+
+def determine_postprocessing(predictions, references, dataset_json_or_label_manager, output_folder=None,
+                             save_postprocessed=False, verbose=False, backend=None):
+    """``determine_postprocessing`` (remove_connected_components.py:52-245) on label maps, on the GPU; see
+    ``postprocessing_search.determine_postprocessing``."""
+    from .postprocessing_search import determine_postprocessing as run
+    return run(predictions, references, dataset_json_or_label_manager, output_folder, save_postprocessed, verbose, backend)

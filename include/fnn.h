@@ -353,6 +353,18 @@ int fnn_average_probabilities(const float *const *member_probs, int n_members, i
                               const int32_t *regions_class_order, int64_t n_vox, float *avg_probs, void *labels,
                               int label_dtype, void *stream);
 
+/* Confusion counts of a reference label map against 1..4 predicted maps of the same voxel count (additive in ABI 4), for
+ * compute_tp_fp_fn_tn (evaluation/evaluate_predictions.py:76-85) of every label at once.  ref and pred[p] (device,
+ * 16-byte aligned; pred a host array of n_pred pointers) hold n_vox labels of label_dtype (FNN_LABEL_U8 / U16).
+ * class_of_value[v] (host, n_table entries) is the class index of label value v (0..n_classes-1, n_classes <= 255);
+ * values >= n_table or mapped to -1 fall in class n_classes ("other").  Reference voxels whose value equals
+ * ignore_value (-1: none) are not counted.  counts (host) receives int64 [n_pred][n_classes+1][n_classes+1], indexed
+ * [pred map][reference class][predicted class].  Exact integers; n_vox is not limited to 2^31; zero voxels give all
+ * zeros.  The (other, other) bin is derived from the number of counted voxels.  Synchronises the stream. */
+int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, int label_dtype, int64_t n_vox,
+                         const int32_t *class_of_value, int n_table, int n_classes, int ignore_value,
+                         int64_t *counts, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */
