@@ -1083,6 +1083,7 @@ ConvOverrides ConvOverrides::from_env() {
     o.no_row = fnn_knob("FNN_NO_ROW") != nullptr;
     o.no_stem_row = fnn_knob("FNN_NO_STEM_ROW") != nullptr;
     o.no_zr6 = fnn_knob("FNN_NO_ZR6") != nullptr;
+    o.no_zrp = fnn_knob("FNN_NO_ZRP") != nullptr;             // conv3d_zr_kernel on the padded order (the tests compare the two orders' bits)
     o.no_zq12 = fnn_knob("FNN_NO_ZQ12") != nullptr;           // conv3d_zr12_kernel instead (the tests compare the two kernels' bits)
     o.no_zsw = fnn_knob("FNN_NO_ZSW") != nullptr;
     o.no_zp = fnn_knob("FNN_NO_ZP") != nullptr;

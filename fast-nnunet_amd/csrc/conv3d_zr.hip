@@ -9,7 +9,9 @@
 // feeds 3 MFMAs per cout block.  Per (chunk, tap pair) a wave issues TD + 2 activation reads and 3 NB weight
 // reads for 3 TD NB MFMAs - 0.33 LDS reads per MFMA at NB = 2, TD = 8 instead of 0.63 in the linear-tap
 // kernels, which at 32 output channels were bound by LDS bandwidth, not by the matrix cores.
-// Cost: the 9 in-plane taps pair up into 5 k-steps (one half padded) -> 30 tap slots instead of 28.
+// Cost: the 9 in-plane taps pair up into 5 k-steps (one half padded) -> 30 tap slots instead of 27.  FNN_PACK_ZRP (TH = 8)
+// removes the padding for pairs of chunks: the leftover tap 8 of chunk c (held in registers from chunk c's k-loop) and of
+// chunk c + 1 share one k-step -> 27 k-steps per 32 channels.
 //
 // Replaces the same reference code as conv3d.hip (ConvDropoutNormReLU stacks,
 // nnUNetDistillationTrainer.py:141-173).
@@ -18,12 +20,21 @@
 #include <type_traits>
 #include <cstdlib>
 
-int conv3d_ksteps(int packing, int taps) { return packing == FNN_PACK_ZR ? 15 : packing == FNN_PACK_ZP ? 9 : (taps + 1) / 2; }
+int conv3d_ksteps(int packing, int taps) {
+    return packing == FNN_PACK_ZR || packing == FNN_PACK_ZRP ? 15 : packing == FNN_PACK_ZP ? 9 : (taps + 1) / 2;
+}
 
-int conv3d_kstep_tap(int packing, int ks, int half, int taps) {
-    if (packing == FNN_PACK_ZR) {
-        const int pr = ks / 3, dz = ks % 3, t = 2 * pr + half;
-        return t < 9 ? dz * 9 + t : -1;
+int conv3d_kstep_tap(int packing, int ks, int half, int taps, int ch, int chunks, int *tch) {
+    *tch = ch;
+    if (packing == FNN_PACK_ZR || packing == FNN_PACK_ZRP) {
+        const int pr = ks / 3, dz = ks % 3;
+        if (pr < 4) return dz * 9 + 2 * pr + half;
+        // k-steps 12 .. 14: the leftover in-plane tap 8 - padded in FNN_PACK_ZR and in FNN_PACK_ZRP's unpaired last chunk,
+        // shared by the two chunks of a pair in FNN_PACK_ZRP (in the pair's second chunk; the first chunk's are zeros)
+        if (packing == FNN_PACK_ZR || (ch % 2 == 0 && ch + 1 == chunks)) return half ? -1 : dz * 9 + 8;
+        if (ch % 2 == 0) return -1;
+        *tch = ch - 1 + half;
+        return dz * 9 + 8;
     }
     const int t = 2 * ks + half;
     return t < taps ? t : -1;
@@ -35,7 +46,7 @@ int conv3d_kstep_tap(int packing, int ks, int half, int taps) {
 // 32-channel group - half the store instructions of the 8-byte form, whole 64-byte runs (the stores of this kernel
 // delayed the next workgroup's loads in the texture-address path: a timing-only build without them ran 14 % faster).
 int conv3d_pack_cout(int packing, int nblk, int cb, int m) {
-    if ((packing != FNN_PACK_ZR && packing != FNN_PACK_ZP) || nblk % 2 != 0) return cb * 16 + m;
+    if ((packing != FNN_PACK_ZR && packing != FNN_PACK_ZRP && packing != FNN_PACK_ZP) || nblk % 2 != 0) return cb * 16 + m;
     return (cb >> 1) * 32 + (m >> 2) * 8 + (cb & 1) * 4 + (m & 3);
 }
 
@@ -47,6 +58,10 @@ bool zr_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c) {
     const int nblk = p.Cout / 16;
     const int plan_n = p.plan_N > 0 ? p.plan_N : p.N;
     c.packing = FNN_PACK_ZR; c.ksteps = 15; c.chunks = p.chunks;
+    // conv3d_zr_kernel<NB, TD, 8> on two or more chunks takes the paired order (FNN_PACK_ZRP), decided from the shape before
+    // the overrides: a layer of the <2, 10, 6> form's shape keeps FNN_PACK_ZR under both kernels (its bits are the 8 x 8 x 8
+    // kernel's under FNN_NO_ZR6 - the tests compare them)
+    bool zr6_shape = false;
     if (p.sh == 2 && p.sw == 2) {
         // in-plane stride 2: an even number of cout blocks, enough tiles (conv3d_zs_kernel below)
         if (p.fp8 || nblk % 2 != 0 || (long long)p.Di * p.Hi * p.Wi >= (1 << 23) || p.Do < 8) return false;
@@ -85,8 +100,9 @@ bool zr_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c) {
     // planes of at most 6 x 8 voxels in a layer whose depth is a multiple of 10 (the 160-channel stages of the benchmark net:
     // 20 x 6 x 6): tiles of 10 x 6 x 8 on three waves (conv3d_zr_kernel<2, 10, 6>) - 75 % of the tile's columns and all of its
     // depth are output voxels (8 x 8 x 8 tiles: 47 %)
-    if (nb == 2 && !p.fp8 && p.Ho <= 6 && p.Wo <= 8 && p.Do >= 10 && p.Do % 10 == 0 && !o.no_zr6 &&
-        (long long)plan_n * (p.Do / 10) * (nblk / 2) >= 160) {
+    zr6_shape = nb == 2 && !p.fp8 && p.Ho <= 6 && p.Wo <= 8 && p.Do >= 10 && p.Do % 10 == 0 &&
+                (long long)plan_n * (p.Do / 10) * (nblk / 2) >= 160;
+    if (zr6_shape && !o.no_zr6) {
         c.stats_slots = ((p.Do + 9) / 10) * th * tw;
         c.kernel = CK_ZR; c.t[0] = 2; c.t[1] = 10; c.t[2] = 6;
         snprintf(c.name, sizeof c.name, "conv3d_zr_kernel<%d,%d,%d>", 2, 10, 6);
@@ -121,6 +137,7 @@ bool zr_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c) {
         snprintf(c.name, sizeof c.name, "conv3d_zrw_kernel<%d>", nb);
     } else {
         c.kernel = CK_ZR;
+        if (p.chunks >= 2 && !zr6_shape && !o.no_zrp) c.packing = FNN_PACK_ZRP;
         snprintf(c.name, sizeof c.name, "conv3d_zr_kernel<%d,%d>", nb, td);
     }
     return true;
@@ -238,6 +255,11 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
 
     f32x4 acc[TD][NB];
     fnn_u32x4v xr[ID], wr[NB][WPB];
+    // FNN_PACK_ZRP (TH = 8 only: the 6-row form has no registers to spare): chunk 2 i's leftover-tap operands, read in its
+    // k-loop, wait here for chunk 2 i + 1's (lanes of k-half 1 take that chunk's, k-half 0 keep these)
+    constexpr bool PAIR = TH == 8;
+    const bool paired = PAIR && p.packing == FNN_PACK_ZRP;
+    f16x8 xl[PAIR ? ID : 1];
 #ifdef FNN_NORM_FP32
     float scu[16], shu[16];                                   // the chunk's scale / shift rows: wave-uniform -> scalar loads
 #else
@@ -276,10 +298,13 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
 #endif
         voff = ok_hw ? (unsigned)hw_lin * (unsigned)(vs * 2) + cg * 16 : 0x80000000u;
         plane_bytes = (unsigned)p.Hi * p.Wi * vs * 2;
+        // the first chunk of a pair: its k-steps 12 .. 14 are zeros (the shared k-steps are the second chunk's) - the range
+        // check returns them without traffic
+        const int wbytes = paired && ch % 2 == 0 && ch + 1 < p.chunks ? 12 * 64 * 16 : WB * 16;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const f16 *wp = p.wpk + ((size_t)((cb0 + nb) * p.chunks + ch) * WB) * 8;
-            rw[nb] = __builtin_amdgcn_make_buffer_rsrc((void *)wp, 0, WB * 16, 0x00020000);
+            rw[nb] = __builtin_amdgcn_make_buffer_rsrc((void *)wp, 0, wbytes, 0x00020000);
         }
     };
 #ifndef FNN_ZR_SLICES
@@ -353,14 +378,30 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
                 if (u + 1 < WPB || wave < 3) *(fnn_u32x4v *)(smem + wlds + (nb * WB + u * NT) * 16) = wr[nb][u];
     };
     int toff[5];                                              // filled in after the first loads have left
-    auto kloop = [&](bool prefetch) {
+    const bool khalf1 = lane >= 32;                           // MFMA "B" lanes of k 16 .. 31 (the second tap of a pair)
+    // MODE (wave-uniform, one k-loop copy each): 0 = the padded order; 1 = first chunk of a pair: tap pair 4's operands go to
+    // xl, no MFMAs; 2 = second chunk of a pair: the shared k-steps FIRST - k-half 0 from xl (the first chunk's tap 8), k-half 1
+    // this chunk's - so that xl is dead before the other pairs' operands and the next chunk's prefetch registers are live
+    // (kept live through them it spilled)
+    auto kloop = [&](bool prefetch, auto mode_c) __attribute__((always_inline)) {
+        constexpr int MODE = decltype(mode_c)::value;
 #pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            if (prefetch && pr < SL) load_part(pr);
+        for (int i = 0; i < 5; ++i) {
+            const int pr = MODE == 2 ? (i + 4) % 5 : i;
+            if (prefetch && i < SL) load_part(i);
             const char *bp = sA + toff[pr];
+            if (MODE == 1 && pr == 4) {
+#pragma unroll
+                for (int pl = 0; pl < ID; ++pl) xl[pl] = *(const f16x8 *)(bp + pl * PS);
+                break;
+            }
             f16x8 xf[ID];
 #pragma unroll
             for (int pl = 0; pl < ID; ++pl) xf[pl] = *(const f16x8 *)(bp + pl * PS);
+            if (MODE == 2 && pr == 4) {
+#pragma unroll
+                for (int pl = 0; pl < ID; ++pl) xf[pl] = khalf1 ? xf[pl] : xl[pl];
+            }
 #pragma unroll
             for (int dz = 0; dz < 3; ++dz) {
                 f16x8 wf[NB];
@@ -375,7 +416,6 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
             __builtin_amdgcn_sched_barrier(0);                // keep the next pair's reads from being hoisted: registers
         }
     };
-
     prep(0);
 #pragma unroll
     for (int part = 0; part < SL; ++part) load_part(part);
@@ -399,7 +439,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
         const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
 #pragma unroll
         for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;   // padded slot: any finite data (its weights are 0)
+            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;   // padded slot: any finite data (its weights are 0); FNN_PACK_ZRP: tap 8
             const int row = 2 * wave + (r >> 3) + tp / 3, col2 = (r & 7) + tp % 3;
             toff[pr] = (row * PW + col2) * 32 + ((kh ^ (row & 1)) * 16);
         }
@@ -412,16 +452,36 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
     __syncthreads();
     FNN_STAMP();                                              // 2: first chunk staged
     // the last chunk is peeled off so that the wait for the prefetch sits on an unconditional path (see conv3d_lds_kernel)
-    for (int ch = 0; ch + 1 < p.chunks; ++ch) {
+    using M0 = std::integral_constant<int, 0>;
+    using M1 = std::integral_constant<int, 1>;
+    using M2 = std::integral_constant<int, 2>;
+    auto next_chunk = [&](int ch, auto mode_c) __attribute__((always_inline)) {   // k-loop of chunk ch, then stage ch + 1
         prep(ch + 1);
-        kloop(true);                                          // global loads stay in flight during the MFMAs
+        kloop(true, mode_c);                                  // global loads stay in flight during the MFMAs
         FNN_STAMP();                                          // k-loop done
         __syncthreads();                                      // every wave is done reading this chunk
         commit();
         __syncthreads();
         FNN_STAMP();                                          // next chunk staged
+    };
+    if (PAIR && paired) {
+        // one pair per iteration, straight-line: with the two orders' k-loops behind a branch in one loop body the
+        // prefetch registers of both arms spilled
+        int ch = 0;
+        for (; ch + 2 < p.chunks; ch += 2) {
+            next_chunk(ch, M1{});
+            next_chunk(ch + 1, M2{});
+        }
+        if (ch + 1 < p.chunks) {
+            next_chunk(ch, M1{});
+            kloop(false, M2{});
+        } else {
+            kloop(false, M0{});                               // an unpaired last chunk: the padded order
+        }
+    } else {
+        for (int ch = 0; ch + 1 < p.chunks; ++ch) next_chunk(ch, M0{});
+        kloop(false, M0{});
     }
-    kloop(false);
     FNN_STAMP();
     __syncthreads();
 
@@ -1952,7 +2012,10 @@ static int launch_zrw(ConvParams p, const ConvChoice &c, hipStream_t st) {
 // * PMC per wave and two-chunk tile (tools/pmc_layer.sh): 480 MFMAs = 7.7 k cycles, ~1280 other vector instructions
 //   before / ~900 after the staging rewrite, 417 scalar, 202 LDS; SQ_WAIT_ANY 15 % of the wave's life, issue stalls
 //   48 %, matrix pipe busy 50 -> 55 %; clock under 30 back-to-back launches 1.80 GHz, inside the network 2.13 GHz.
-// Runs the layer on the kernel zr_choose chose; the weights are packed as FNN_PACK_ZR.
+// Round 10: the paired order (FNN_PACK_ZRP) on conv3d_zr_kernel<NB, TD, 8> - 27 instead of 30 k-steps per two chunks.
+// v_mfma_f32_16x16x16_f16 issues in the cycles of 16x16x32 (tools/mfma_rate_probe.cpp: 17.3 vs 17.2 per SIMD), so the padded
+// half k-step could not simply be issued at K = 16; the saving needs the second chunk's tap 8 in the other k-half.
+// Runs the layer on the kernel zr_choose chose; the weights are packed as FNN_PACK_ZR (FNN_PACK_ZRP: conv3d_zr_kernel).
 int launch_conv3d_zr(ConvParams p, const ConvChoice &c, hipStream_t st) {
     const int nb = c.t[0], td = c.t[1];
     switch (c.kernel) {

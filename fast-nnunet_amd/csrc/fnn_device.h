@@ -90,6 +90,11 @@ struct ConvParams {
 //   FNN_PACK_ZP     : (1, 3, 3) stride 1, conv2d_zp.hip: chunks of 32 input channels (never across the two sources), 9 k-steps
 //                     per chunk, k-step dx * 3 + dy = the 32 channels of tap (dy, dx); ConvParams::chunks counts THESE chunks.
 #define FNN_PACK_ZP 2
+//   FNN_PACK_ZRP    : FNN_PACK_ZR with the leftover in-plane tap 8 of two consecutive chunks (2 i, 2 i + 1) sharing k-steps
+//                     12 .. 14 of chunk 2 i + 1 (half 0: chunk 2 i, half 1: chunk 2 i + 1); chunk 2 i's k-steps 12 .. 14 are
+//                     zeros.  An unpaired last chunk keeps the padded order.  27 k-steps per 32 channels instead of 30;
+//                     conv3d_zr_kernel (TH = 8) only.
+#define FNN_PACK_ZRP 3
 int conv_zp_chunks(int cin_pad0, int cin_pad1);
 void conv_zp_pack(const float *W, int cout_real, int cout_pad, int cin_real0, int cin_pad0, int cin_real1, int cin_pad1, unsigned short *dst);
 
@@ -373,7 +378,9 @@ int conv3d_pick_nb(int nblk);
 const float *conv3d_identity_ss();
 const unsigned short *conv3d_identity_ssh();
 int conv3d_ksteps(int packing, int taps);
-int conv3d_kstep_tap(int packing, int ks, int half, int taps);     // linear tap index, or -1 = zero padding
+// linear tap index of half `half` (k 16 half .. + 15) of k-step ks of chunk ch (of `chunks`), or -1 = zero padding;
+// *tch = the chunk whose 16 channels that half holds (ch except in FNN_PACK_ZRP's shared k-steps)
+int conv3d_kstep_tap(int packing, int ks, int half, int taps, int ch, int chunks, int *tch);
 int conv3d_pack_cout(int packing, int nblk, int cb, int m);        // output channel in row m of cout block cb of the packed weights
 
 // ---- which kernel runs a conv layer: chosen once, from the layer's shape and the PLANNED batch (ConvParams::plan_N) ----
@@ -381,7 +388,7 @@ int conv3d_pack_cout(int packing, int nblk, int cb, int m);        // output cha
 // in the variant.  The engine chooses when it is planned (fnn_create) and launches what it chose; the op entry points
 // choose per call.  Grids and tile totals are still computed from the call's N by the launchers.
 enum ConvKernel {
-    CK_NONE, CK_ZS, CK_ZSP, CK_ZSW, CK_ZR, CK_ZR8, CK_ZQ12, CK_ZR12, CK_ZRW,   // conv3d_zr.hip, conv3d_zq.hip (FNN_PACK_ZR)
+    CK_NONE, CK_ZS, CK_ZSP, CK_ZSW, CK_ZR, CK_ZR8, CK_ZQ12, CK_ZR12, CK_ZRW,   // conv3d_zr.hip, conv3d_zq.hip (FNN_PACK_ZR; CK_ZR: or ZRP)
     CK_ZP, CK_ZPS,                                                         // conv2d_zp.hip (FNN_PACK_ZP)
     CK_ROW, CK_ROW_STEM, CK_THIN,                                          // conv3d_row.hip, conv3d_thin.hip
     CK_PERSIST, CK_LDSK, CK_S2, CK_NB                                      // conv3d.hip, conv3d_s2.hip
@@ -398,7 +405,7 @@ struct ConvChoice {
 // The test switches of the choice (fnn_knob), read by the caller where it chooses: ConvOverrides::from_env().
 struct ConvOverrides {
     bool conv_v1 = false;              // FNN_CONV_V1: the generic kernel
-    bool no_row = false, no_stem_row = false, no_zr6 = false, no_zq12 = false, no_zsw = false, no_zp = false;
+    bool no_row = false, no_stem_row = false, no_zr6 = false, no_zrp = false, no_zq12 = false, no_zsw = false, no_zp = false;
     bool zp_no_half = false, zps_no_half = false;
     int zr_min_wgs = 480;              // FNN_ZR_MIN_WGS
     int fp8_levels = -1;               // FNN_FP8_LEVELS: e4m3 operands only at these resolution levels (bit mask; engine plans only)

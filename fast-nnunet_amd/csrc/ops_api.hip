@@ -142,7 +142,9 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
             for (int ks = 0; ks < p.ksteps; ++ks)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
-                        const int kk = 8 * (lane >> 4) + j, tap = conv3d_kstep_tap(p.packing, ks, kk >> 4, T), c = ch * 16 + (kk & 15);
+                        int tch;
+                        const int kk = 8 * (lane >> 4) + j, tap = conv3d_kstep_tap(p.packing, ks, kk >> 4, T, ch, p.chunks, &tch);
+                        const int c = tch * 16 + (kk & 15);
                         const int co = conv3d_pack_cout(p.packing, cop / 16, cb, lane & 15);
                         int src = 0, cl = c;
                         if (c >= cp1) { src = 1; cl = c - cp1; }
