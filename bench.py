@@ -15,8 +15,11 @@ resident in HBM.  N > 1 shards the patches of the SAME volume over the ranks
 the assembled label map (``--gather``); without a launcher ``--gpus N`` starts
 the N ranks itself.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus ``roofline`` and
-``cpu_baseline`` (N = 1 only).
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run does only what that
+line needs: set up, warm up, time the steps, write ``--dump-outputs``.  ``--full`` adds
+every other figure, each from steps or processes of its own after the timed ones: the
+``roofline`` block (a profiled step beside a clock probe), ``from_host``, ``cpu_baseline``
+and ``also`` (N = 1), the assembled-labels step and ``phases_profiled_step`` (N > 1).
 """
 from __future__ import annotations
 
@@ -493,8 +496,8 @@ def also_block(device):
     torch.cuda.empty_cache()
     out = {}
     for name, flags in ALSO:
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-also',
-               '--no-from-host'] + flags
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
+               '--no-also', '--no-from-host'] + flags
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -577,7 +580,13 @@ def main():
     ap.add_argument('--mirror', action='store_true',
                     help='test-time mirroring over all three axes (8 evaluations per patch; the reference default, off in the '
                          'bone_turbo .ini and in the bench line)')
-    ap.add_argument('--layers', action='store_true', help='add the per-layer table of the profiled step (always on with --plan)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, measure everything besides the headline as well: the roofline block (one profiled '
+                         'step, one step beside the clock probe), the steps from a host tensor, the CPU baseline and the `also` '
+                         'block (N = 1), the assembled-labels step and the profiled phases (N > 1).  The --no-* options below '
+                         'leave out parts of it')
+    ap.add_argument('--layers', action='store_true', help='add the per-layer table of the profiled step (needs --full; always on '
+                                                          'with --plan --full)')
     ap.add_argument('--no-from-host', action='store_true', help='skip the steps that start from a host tensor (ms_per_step_from_host)')
     ap.add_argument('--no-also', action='store_true',
                     help='skip the `also` block (N = 1, default workload only: 3 timed steps each of the other single-GPU BASELINE '
@@ -601,6 +610,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.layers and not args.full:
+        ap.error('--layers: the per-layer table comes from the profiled step of --full')
     args.batch_given = args.batch is not None
     if args.batch is None:
         args.batch = 32
@@ -688,7 +699,8 @@ def main():
         dumped = dump_outputs(step_arrays(last.pop('out')), args.dump_outputs, vol.dim() - 1, DUMP_BYTES // world,
                               f'_rank{rank}' if world > 1 else '')
         del last
-    if step_est and not args.no_clock_probe and not args.no_roofline:
+    roofline = args.full and not args.no_roofline
+    if step_est and roofline and not args.no_clock_probe:
         # one extra, identical, UNTIMED step beside the clock probe (one sleeping wave, fnn_clock_probe_*): the shader clock the
         # device holds under this step.  Not in the timed region (it costs ~0.5 % there) and not in the profiled step below
         # (it stretches the per-launch durations by ~4 %, measured: 734 -> 700 TFLOP/s)
@@ -721,13 +733,13 @@ def main():
         finally:
             if probe:
                 probe.close()
-    if distributed and args.gather != 'labels':
+    if args.full and distributed and args.gather != 'labels':
         out = labels_fn()                                        # (one untimed call: first-use allocations of this entry point)
         del out
         dt_labels = timed(labels_fn, barrier, max(1, min(args.steps, 5)))   # the step that ends with the label map on every rank
 
     from_host = None
-    if not distributed and not args.no_from_host and not w['plan'] and args.folds == 1:
+    if args.full and not distributed and not args.no_from_host and not w['plan'] and args.folds == 1:
         # The same step as a reference caller sees it: the preprocessed volume is a CPU tensor (what the preprocessing iterator
         # yields, data_iterators.py:116-117; `data.to(results_device)` at predict_from_raw_data.py:579).  The engine uploads it
         # in tiles on a copy stream under the first batches (engine.hip, stage_volume / upload_box).  Untimed extras.
@@ -814,7 +826,7 @@ def main():
         result['series_note'] = ('rounds 1-3 timed the N > 1 step with the label map assembled on every rank (--gather labels); since round 4 '
                                  '`value` is the N = 1 step sharded (--gather none: each rank ends with the fp16 logits of its box) and the '
                                  'assembled step is `value_labels_assembled` / `ms_per_step_labels_assembled`: compare like with like')
-    if distributed:
+    if args.full and distributed:
         # one extra, profiled step (the device is synchronised at every phase boundary, so it is slower than the timed
         # ones): where a rank's time goes and what it exchanges - per phase the MAX over ranks, bytes per rank as a list
         ph = runner.start_phases()
@@ -832,9 +844,10 @@ def main():
             'per_rank': {k: [int(v) for v in allv[:, i]] for i, k in enumerate(keys) if not k.endswith('_ms')},
             'mode': runner.last_mode,
             'rccl_ranks': dist.get_world_size()}
+    if distributed:
         assert dist.get_world_size() == args.gpus, 'the process group does not have one rank per requested GPU'
 
-    if not args.no_roofline:
+    if roofline:
         # one extra, identical step with HIP events around every launch (recorded by the engine on the
         # launch stream) -> duration of the dominant kernel family (the MFMA convs).  N > 1: every rank runs the step (it is
         # collective), rank 0's profile is quoted - of its last fnn_patch_features call, i.e. its interior patches
@@ -847,7 +860,7 @@ def main():
         kernel_counts = dict(collections.Counter(predictor._engine.kernel_log()))   # which variant served every launch of that volume (N > 1: of the last engine call)
         layer_rows = layer_table(predictor._engine, args.batch) if (w['plan'] or args.layers) else None
         predictor._engine.set_profiling(False)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline:
         achieved = pr.conv_flops / (pr.conv_ms * 1e-3) / 1e12 if pr.conv_ms > 0 else 0.0
         launches = max(1, pr.conv_launches)
         algo_bytes = pr.conv_bytes / launches
@@ -904,13 +917,13 @@ def main():
         }
         if layer_rows is not None:
             result['layers'] = layer_rows
-    if rank == 0 and not distributed and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not distributed and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(sd, info)
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not distributed and not args.no_also and not w['plan'] and args.workload == 'bone_turbo_r2' and args.folds == 1 \
-            and args.dtype == 'f16' and not args.mirror and args.accum == 'fp16' and args.volume == 512:
+    if args.full and rank == 0 and not distributed and not args.no_also and not w['plan'] and args.workload == 'bone_turbo_r2' \
+            and args.folds == 1 and args.dtype == 'f16' and not args.mirror and args.accum == 'fp16' and args.volume == 512:
         predictor._engine.close()                               # (every figure of this process is in `result` by now: its HBM goes back first)
         predictor._engine = None
         del vol

@@ -1,4 +1,5 @@
-"""bench.py prints ONE JSON line with the keys the driver reads (small volume, no CPU baseline leg)."""
+"""bench.py prints ONE JSON line with the keys the driver reads (small volume, no CPU baseline leg); a plain run carries the
+headline alone, `--full` the figures of its extra steps too."""
 import json
 import os
 import subprocess
@@ -12,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--volume', '192', '--steps', '1', '--warmup', '1',
-                          '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
@@ -32,6 +33,25 @@ def test_bench_json_line_contract():
     # s_memrealtime)
     assert 0.5 < r['clock_ghz'] < 3.2 and r['clock_sampled_s'] > 0
     assert abs(r['frac_at_clock'] - r['achieved'] / (r['peak'] * r['clock_ghz'] / 2.4)) < 2e-3
+
+
+def test_bench_plain_run_prints_the_headline_without_extra_steps():
+    """Without `--full` the run sets up, warms up, times its steps and prints the line: the headline keys with the same
+    meaning as in a full run, none of the figures that take steps or processes of their own."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--volume', '192', '--steps', '2', '--warmup', '1'],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+              'vs_baseline', 'dtype', 'data', 'config'):
+        assert k in j, k
+    assert j['n_gpus'] == 1 and j['steps'] == 2 and j['warmup'] == 1 and j['higher_is_better'] is True
+    assert j['unit'] == 'patches/s' and j['dtype'] == 'f16' and 'fp16 logits resident in HBM' in j['metric']
+    assert j['value'] > 0 and abs(j['value'] - 1000.0 * _patches(j) / j['ms_per_step']) / j['value'] < 1e-3
+    for k in ('roofline', 'from_host', 'ms_per_step_from_host', 'cpu_baseline', 'also', 'layers'):
+        assert k not in j, k
 
 
 def test_clock_probe_ends_by_itself_and_reads_a_plausible_clock():
@@ -60,7 +80,7 @@ def test_bench_force_sharded_single_rank_runs_the_multi_gpu_path():
     step is the N = 1 step sharded (fp16 logits of the owned box resident in HBM; the metric string says so), the
     assembled-labels step is a named extra key, and the line carries rank 0's roofline block."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--volume', '192', '--steps', '1', '--warmup', '1',
-                          '--gpus', '1', '--force-sharded'], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          '--gpus', '1', '--force-sharded', '--full'], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1

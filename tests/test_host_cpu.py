@@ -344,6 +344,17 @@ def test_bench_gpus_n_spawns_one_rank_per_gpu_and_propagates_failure():
     assert out2.returncode != 0 and 'WORLD_SIZE=1' in (out2.stderr + out2.stdout)
 
 
+def test_bench_layers_asks_for_full():
+    """The per-layer table comes from the profiled step, which only `--full` runs: `--layers` alone is refused before
+    anything touches a GPU rather than printing a line without the table."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--layers', '--steps', '1'],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 2 and '--full' in out.stderr
+    assert not [l for l in out.stdout.splitlines() if l.startswith('{')]
+
+
 def test_bench_dump_outputs_is_a_fixed_sample_under_64_mb(tmp_path):
     """bench.py --dump-outputs: the headline step's logits (61 x 512^3 fp16, 16 GB) go out as float32 at the same seeded
     voxels every run, every file together under 64 MB; the sample holds the values at the voxels its index file names;

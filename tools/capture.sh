@@ -1,11 +1,13 @@
 #!/bin/bash
-# usage (on the GPU box, from the repo root): bash tools/capture.sh <tag> [bench.py workload flags, e.g. --workload iso128_r2]
+# usage (on a machine with an MI355X, from the repository root): FNN_OUT=<folder> bash tools/capture.sh <tag> [bench.py workload flags,
+# e.g. --workload iso128_r2]; the files land in $FNN_OUT/cap_<tag>/ and $FNN_OUT/<round>_traffic.json
 # Collects what profiles/ holds per workload: kernel trace + stats + per-layer medians, the two PMC passes for HBM traffic
-# (separate runs, no trace domains next to --pmc), the MFMA-busy pass, and the plain bench line.  Every pass under `timeout`.
+# (separate runs, no trace domains next to --pmc), the MFMA-busy pass, and the bench line with --full.  Every pass under `timeout`.
 tag=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 round=${FNN_ROUND:-r06}
-out=$root/gpurun_out/cap_$tag
+dest=$(mkdir -p "${FNN_OUT:?FNN_OUT: the folder that receives the captures}" && cd "$FNN_OUT" && pwd)
+out=$dest/cap_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 key=$(cd $root && python3 -c "import bench, sys, argparse
@@ -36,12 +38,12 @@ cp $ks $out/kernel_stats.csv
 if [ -z "$SKIP_PMC" ]; then
 f=$(find $out/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1)
 w=$(find $out/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
-python tools/traffic.py $f $w $root/gpurun_out/${round}_traffic.json "$key" > $out/traffic.txt 2>&1
+python tools/traffic.py $f $w $dest/${round}_traffic.json "$key" > $out/traffic.txt 2>&1
 fi
 unset FNN_NO_PIPELINE
-cp $root/gpurun_out/${round}_traffic.json $root/profiles/${round}_traffic.json 2>/dev/null   # so that the bench line below quotes it
+cp $dest/${round}_traffic.json $root/profiles/${round}_traffic.json 2>/dev/null   # so that the bench line below quotes it
 extra=""; [[ "$*" == *--plan* ]] && extra="--no-cpu-baseline"          # (a plan line: no CPU leg - its oracle forward of a full-width teacher patch takes minutes)
-timeout 900 python bench.py $extra "$@" 2> $out/bench.err | grep "^{" > $out/bench.json
+timeout 900 python bench.py --full $extra "$@" 2> $out/bench.err | grep "^{" > $out/bench.json
 rm -rf $out/trace $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE
 tail -1 $out/bench.json | cut -c1-1200
 head -14 $out/trace_summary.txt

@@ -3,7 +3,7 @@
 
     python tools/plan_sweep.py [--plans tools/plans/a.json ...] [--out profiles/r06_plan_sweep] [--steps 3]
 
-Runs `bench.py --plan <file>` for every plan file (one process per plan), collects the JSON lines and writes
+Runs `bench.py --plan <file> --full` for every plan file (one process per plan), collects the JSON lines and writes
   <out>.json   every line as bench.py printed it (with its per-layer table)
   <out>.txt    per plan: patches/s, conv-family fraction of the MFMA peak, and per layer the kernel the launch rules
                picked with its microseconds per forward, algorithmic TFLOP/s and TB/s; then the list of CLIFFS:
@@ -73,7 +73,7 @@ def main():
     lines, failed = [], []
     for pf in plans:
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--plan', pf, '--steps', str(args.steps), '--warmup', str(args.warmup),
-               '--no-cpu-baseline', '--no-clock-probe'] + args.extra
+               '--full', '--no-cpu-baseline', '--no-clock-probe'] + args.extra
         print('+', ' '.join(cmd), flush=True)
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
