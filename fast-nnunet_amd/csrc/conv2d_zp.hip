@@ -32,7 +32,6 @@
 #include "fnn_device.h"
 #include "conv_common.h"
 #include <cstdlib>
-#include <cstring>
 
 // ---------------------------------------------------------------------------
 // host side: chunking and weight packing (FNN_PACK_ZP)
@@ -60,10 +59,7 @@ void conv_zp_pack(const float *W, int cout_real, int cout_pad, int cin_real0, in
                         const int co = conv3d_pack_cout(FNN_PACK_ZP, nblk, cb, lane & 15);
                         float v = 0.f;
                         if (co < cout_real && cl < creal) v = W[((size_t)co * cin_tot + (src ? cin_real0 : 0) + cl) * 9 + tap];
-                        const f16 h = (f16)v;
-                        unsigned short b;
-                        memcpy(&b, &h, 2);
-                        dst[((((size_t)cb * nch + ch) * 9 + ks) * 64 + lane) * 8 + j] = b;
+                        dst[((((size_t)cb * nch + ch) * 9 + ks) * 64 + lane) * 8 + j] = fnn_half_bits(v);
                     }
 }
 
@@ -387,19 +383,13 @@ int launch_zp(ConvParams p, hipStream_t st) {
     p.tiles_d = p.Do;
     p.tiles_h = (p.Ho + ROWS - 1) / ROWS;
     p.tiles_w = (p.Wo + COLS - 1) / COLS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv2d_zp_kernel<TH, WC, NB, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     const long long tiles = (long long)p.N * p.Do * p.tiles_h * p.tiles_w;
     if (tiles >= (1ll << 31)) return -1;
     dim3 grid((unsigned)tiles, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL((conv2d_zp_kernel<TH, WC, NB, HALF>), grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv2d_zp_kernel<TH, WC, NB, HALF>>(grid, dim3(256), lds, st, p);
 }
 
 // ----------------------------------------------------------------------------
@@ -659,19 +649,13 @@ int launch_zps(ConvParams p, hipStream_t st) {
     p.tiles_d = p.Do;
     p.tiles_h = (p.Ho + ROWS - 1) / ROWS;
     p.tiles_w = (p.Wo + COLS - 1) / COLS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv2d_zps_kernel<NB, WC, HALF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     const long long tiles = (long long)p.N * p.Do * p.tiles_h * p.tiles_w;
     if (tiles >= (1ll << 31)) return -1;
     dim3 grid((unsigned)tiles, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL((conv2d_zps_kernel<NB, WC, HALF>), grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv2d_zps_kernel<NB, WC, HALF>>(grid, dim3(256), lds, st, p);
 }
 
 }  // namespace

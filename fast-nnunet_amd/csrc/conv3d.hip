@@ -495,14 +495,8 @@ static int launch_ldsk(ConvParams p, hipStream_t st) {
     p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
     p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
     const size_t lds = ldsk_lds_bytes(p, NB, MB);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_lds_kernel<NB, MB, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL((conv3d_lds_kernel<NB, MB, PF>), grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_lds_kernel<NB, MB, PF>>(grid, dim3(256), lds, st, p);
 }
 
 // ----------------------------------------------------------------------------
@@ -869,16 +863,10 @@ static int launch_persist_ks(ConvParams p, int wgs_per_cu, hipStream_t st, int g
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     const size_t lds = persist_lds_bytes(p, NB, MB, WRES, SBUF, PF);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_persist_kernel<NB, MB, WRES, KS, CH, PF, SBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     int gx = gx_exact > 0 ? gx_exact : 256 * wgs_per_cu;
     if (gx > total) gx = total;
     dim3 grid(gx, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL((conv3d_persist_kernel<NB, MB, WRES, KS, CH, PF, SBUF>), grid, dim3(256), lds, st, p, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_persist_kernel<NB, MB, WRES, KS, CH, PF, SBUF>>(grid, dim3(256), lds, st, p, total);
 }
 
 // the instantiations conv_choose_linear can choose: (NB, MB, WRES, KS, CH, PF, SBUF) = c.t
@@ -946,17 +934,14 @@ const unsigned short *conv3d_identity_ssh() {
 int conv3d_pick_nb(int nblk) { return (nblk % 4 == 0) ? 4 : (nblk % 2 == 0) ? 2 : 1; }
 
 template <int NB>
-static int launch_conv_nb(const ConvParams &p, hipStream_t st) {
+static int launch_conv_nb(ConvParams p, hipStream_t st) {
+    p.tile_d = FNN_TILE_D;
+    p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D;
+    p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
+    p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
     const size_t lds = conv3d_lds_bytes(p, NB);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_mfma_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set = true;
-    }
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL(conv3d_mfma_kernel<NB>, grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_mfma_kernel<NB>>(grid, dim3(256), lds, st, p);
 }
 
 static void set_persist(ConvChoice &c, int nb, int mb, int wres, int ks, int ch, int pf, int sbuf, int wpc) {
@@ -1128,10 +1113,7 @@ int launch_conv(const ThinParams &tp_in, const ConvChoice &c, hipStream_t st) {
     fnn_note_kernel("%s", c.name);
     ThinParams tp = tp_in;
     ConvParams &p = tp.c;
-    p.tile_d = FNN_TILE_D;
-    p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D;
-    p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
-    p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
+    p.packing = c.packing; p.ksteps = c.ksteps; p.chunks = c.chunks; p.stats_slots = c.stats_slots;
     switch (c.kernel) {
         case CK_ZS: case CK_ZSP: case CK_ZSW: case CK_ZR: case CK_ZR8: case CK_ZQ12: case CK_ZR12: case CK_ZRW:
             return launch_conv3d_zr(p, c, st);

@@ -858,11 +858,6 @@ int launch_row_t(ThinParams tp, hipStream_t st) {
     const int total = p.N * p.Di * strips;
     constexpr int PB = (16 * NBLK + 2) * 32;
     const size_t lds = (size_t)CH * 12 * PB + 4 * 16 * 2 * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv_row_kernel<NBLK, CH, TCONV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     int per_cu = (int)((160 * 1024) / lds);
     // persistent workgroups per CU.  One chunk, rows of <= 128 voxels: LDS would take three, TWO are faster (round 6, profiles/r06_row_wpc.txt,
     // r06_row1_wpc_ab.txt: the 16 -> 16 layer at 160 x 96 x 96 609-620 us at three, 564-595 at two, 712 at one; the step does not notice; the fused
@@ -874,8 +869,7 @@ int launch_row_t(ThinParams tp, hipStream_t st) {
     if (per_cu > cap) per_cu = cap;
     int gx = 256 * per_cu;
     if (gx > total) gx = total;
-    hipLaunchKernelGGL((conv_row_kernel<NBLK, CH, TCONV>), dim3(gx), dim3(256), lds, st, tp, total, strips, SH);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv_row_kernel<NBLK, CH, TCONV>>(dim3(gx), dim3(256), lds, st, tp, total, strips, SH);
 }
 
 template <int CH, bool TCONV>
@@ -898,11 +892,6 @@ int launch_row_stem_t(ThinParams tp, hipStream_t st) {
     const int total = p.N * p.Di * strips;
     constexpr int W = 16 * NBLK;
     const size_t lds = (size_t)12 * (W + 2) * 32 + (size_t)2 * 6 * W * 8 + 4 * 16 * 2 * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv_row_stem_kernel<NBLK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     int per_cu = (int)((160 * 1024) / lds);
     int cap = NBLK <= 8 ? 3 : 2;
     static const int wpc_knob = fnn_knob("FNN_ROW_WPC") ? atoi(fnn_knob("FNN_ROW_WPC")) : 0;      // A-B aid (launch_row_t)
@@ -910,8 +899,7 @@ int launch_row_stem_t(ThinParams tp, hipStream_t st) {
     if (per_cu > cap) per_cu = cap;
     int gx = 256 * per_cu;
     if (gx > total) gx = total;
-    hipLaunchKernelGGL((conv_row_stem_kernel<NBLK>), dim3(gx), dim3(256), lds, st, tp, total, strips, SH);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv_row_stem_kernel<NBLK>>(dim3(gx), dim3(256), lds, st, tp, total, strips, SH);
 }
 
 int launch_row_stem(const ThinParams &tp, hipStream_t st) {

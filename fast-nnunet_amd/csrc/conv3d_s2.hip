@@ -374,14 +374,6 @@ int launch_conv3d_s2(ConvParams p, const ConvChoice &c, hipStream_t st) {
     const size_t lds = (size_t)S2_ABYTES + S2_WBYTES + 128 * 8 + 8 * 32 * 2 * 4;
     static const int wgs_knob = fnn_knob("FNN_S2_WGS") ? atoi(fnn_knob("FNN_S2_WGS")) : 256;        // A-B aid: fewer persistent workgroups (CUs left to another stream's kernels)
     const int gx = total < wgs_knob ? total : wgs_knob;
-    const bool small = c.t[0] == 13;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[small]) {
-        if (small) (void)hipFuncSetAttribute((const void *)conv3d_s2_kernel<13, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        else (void)hipFuncSetAttribute((const void *)conv3d_s2_kernel<17, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[small] = true;
-    }
-    if (small) hipLaunchKernelGGL((conv3d_s2_kernel<13, 3>), dim3(gx), dim3(512), lds, st, p, total, groups);
-    else hipLaunchKernelGGL((conv3d_s2_kernel<17, 4>), dim3(gx), dim3(512), lds, st, p, total, groups);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (c.t[0] == 13) return fnn_launch_lds<conv3d_s2_kernel<13, 3>>(dim3(gx), dim3(512), lds, st, p, total, groups);
+    return fnn_launch_lds<conv3d_s2_kernel<17, 4>>(dim3(gx), dim3(512), lds, st, p, total, groups);
 }

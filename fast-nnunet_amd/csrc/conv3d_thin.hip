@@ -406,6 +406,20 @@ bool stem_mfma_kmap(int C, int taps, int ks, int k, int *c, int *tap) {
     return true;
 }
 
+// lane (cout, k-group), element k = c * taps + tap (per channel group: stem_mfma_kmap)
+void stem_mfma_pack(const float *W, int C, int taps, int cout_real, int cout_pad, unsigned short *dst) {
+    const int KST = stem_mfma_ksteps(C, taps);
+    for (int cb = 0; cb < cout_pad / 16; ++cb)
+        for (int ks = 0; ks < KST; ++ks)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int co = cb * 16 + (lane & 15);
+                    int c = 0, tap = 0;
+                    const bool live = stem_mfma_kmap(C, taps, ks, 8 * (lane >> 4) + j, &c, &tap) && co < cout_real;
+                    dst[((size_t)(cb * KST + ks) * 64 + lane) * 8 + j] = fnn_half_bits(live ? W[((size_t)co * C + c) * taps + tap] : 0.f);
+                }
+}
+
 int stem_mfma_stats_slots(int PD, int PH, int PW) { return ((PD + STEMM_TD - 1) / STEMM_TD) * ((PH + 7) / 8) * ((PW + 7) / 8); }
 
 // `wfrag`: the stem weights as MFMA "A" fragments [cout block][k-step][64][8]; p.out == nullptr: statistics only.
@@ -423,11 +437,7 @@ int launch_stem_mfma(const StemParams &p_in, const f16 *wfrag, int N, hipStream_
     const int RVOX = (STEMM_TD - 1 + p.kd) * (7 + p.kh) * (7 + p.kw);
     const int cgn = p.C < STEMM_CG ? p.C : STEMM_CG, ngroups = (p.C + STEMM_CG - 1) / STEMM_CG;
     const size_t lds = (size_t)((cgn * RVOX + 3) & ~3) * 4 + (size_t)(ks / ngroups) * 32 * 4 + 4 * 16 * 2 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)stem_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    fnn_allow_lds<stem_mfma_kernel>();
     const bool no_one = fnn_knob("FNN_NO_STEM1") != nullptr;    // A-B aid, read per launch: a test compares the two kernels in one process
     if (p.C == 1 && p.kh == 3 && p.kw == 3 && (p.Cout == 16 || p.Cout == 32) && !no_one &&
         (size_t)p.PD * p.PH * p.PW * p.Cout * 2 < (1ull << 31) && p.Y * p.Z < (1 << 24) && (size_t)p.PD * p.Y * p.Z < (1ull << 30)) {
@@ -443,8 +453,7 @@ int launch_stem_mfma(const StemParams &p_in, const f16 *wfrag, int N, hipStream_
     }
     const dim3 grid(N * p.tiles_d * p.tiles_h * p.tiles_w, p.Cout / 16);
     fnn_note_kernel("stem_mfma_kernel");
-    hipLaunchKernelGGL(stem_mfma_kernel, grid, dim3(256), lds, st, p, wfrag, ks);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<stem_mfma_kernel>(grid, dim3(256), lds, st, p, wfrag, ks);
 }
 
 // ----------------------------------------------------------------------------
@@ -907,17 +916,11 @@ static int launch_thin_w(ThinParams tp, hipStream_t st) {
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     const size_t lds = thin_lds_bytes(KD, CH, FUSE, tp.tsd * tp.tsh * tp.tsw);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv_thin_kernel<KD, CH, FUSE, NCLS, WPS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     int per_cu = (int)((160 * 1024) / lds);
     if (per_cu > WPS) per_cu = WPS;
     int gx = 256 * per_cu;
     if (gx > total) gx = total;
-    hipLaunchKernelGGL((conv_thin_kernel<KD, CH, FUSE, NCLS, WPS>), dim3(gx), dim3(256), lds, st, tp, total);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv_thin_kernel<KD, CH, FUSE, NCLS, WPS>>(dim3(gx), dim3(256), lds, st, tp, total);
 }
 
 template <int KD, int CH, int FUSE, int NCLS>

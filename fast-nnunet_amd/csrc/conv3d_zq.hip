@@ -314,15 +314,9 @@ bool conv3d_zq12_fits(const ConvParams &p, int stats_slots) {
 int launch_conv3d_zq12(ConvParams p, hipStream_t st) {
     p.tile_d = ZQ_TD;
     p.tiles_d = (p.Do + ZQ_TD - 1) / ZQ_TD; p.tiles_h = 1; p.tiles_w = 1;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_zq12_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     dim3 grid(p.N * p.tiles_d, (p.Cout / 16) / ZQ_NB);
-    hipLaunchKernelGGL(conv3d_zq12_kernel, grid, dim3(ZQ_NT), ZQ_LDS, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_zq12_kernel>(grid, dim3(ZQ_NT), ZQ_LDS, st, p);
 }

@@ -18,7 +18,10 @@
 #include "fnn_device.h"
 #include "conv_common.h"
 #include <type_traits>
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <vector>
 
 int conv3d_ksteps(int packing, int taps) {
     return packing == FNN_PACK_ZR || packing == FNN_PACK_ZRP ? 15 : packing == FNN_PACK_ZP ? 9 : (taps + 1) / 2;
@@ -48,6 +51,65 @@ int conv3d_kstep_tap(int packing, int ks, int half, int taps, int ch, int chunks
 int conv3d_pack_cout(int packing, int nblk, int cb, int m) {
     if ((packing != FNN_PACK_ZR && packing != FNN_PACK_ZRP && packing != FNN_PACK_ZP) || nblk % 2 != 0) return cb * 16 + m;
     return (cb >> 1) * 32 + (m >> 2) * 8 + (cb & 1) * 4 + (m & 3);
+}
+
+size_t conv_packed_halves(const ConvChoice &c, int cout_pad) { return (size_t)(cout_pad / 16) * c.chunks * c.ksteps * 512; }
+
+uint8_t f2e4m3(float f) {
+    const uint8_t sign = std::signbit(f) ? 0x80 : 0;
+    float a = std::fabs(f);
+    if (!(a == a)) return sign | 0x7f;
+    if (a >= 448.f) return sign | 0x7e;
+    if (a < 0x1p-6f) {                                          // subnormal: multiples of 2^-9
+        const int q = (int)std::nearbyint(a * 512.f);           // 0 .. 8 (8 = the smallest normal)
+        return sign | (uint8_t)q;                               // q = 8 -> exponent field 1, mantissa 0 = 0x08
+    }
+    int e;
+    const float m = std::frexp(a, &e);                          // a = m * 2^e, m in [0.5, 1)
+    int q = (int)std::nearbyint(m * 16.f);                      // 8 .. 16
+    int E = e - 1;                                              // a = (q / 8) * 2^E
+    if (q == 16) { q = 8; ++E; }
+    if (E > 8 || (E == 8 && q > 14)) return sign | 0x7e;
+    return sign | (uint8_t)(((E + 7) << 3) | (q - 8));
+}
+
+// One loop over the fragment order for every packing but FNN_PACK_ZP; the element encoding is the only difference between
+// fp16 and fp8 (one scale per output channel: max |w| of the channel -> 448)
+void conv_pack_weights(const ConvParams &p, const ConvChoice &c, int cout_real, const int cin_real[2], const float *W, void *dst,
+                       float *scales) {
+    const int cin_real1 = p.n_src > 1 ? cin_real[1] : 0, cin_pad0 = p.src[0].C;
+    if (c.packing == FNN_PACK_ZP) {
+        conv_zp_pack(W, cout_real, p.Cout, cin_real[0], cin_pad0, cin_real1, p.n_src > 1 ? p.src[1].C : 0, (unsigned short *)dst);
+        return;
+    }
+    const int T = p.kd * p.kh * p.kw, cin_tot = cin_real[0] + cin_real1, nblk = p.Cout / 16;
+    std::vector<float> inv(p.Cout, 1.f);
+    if (p.fp8)
+        for (int co = 0; co < p.Cout; ++co) {
+            float mx = 0.f;
+            if (co < cout_real)
+                for (size_t i = 0; i < (size_t)cin_tot * T; ++i) mx = std::max(mx, std::fabs(W[(size_t)co * cin_tot * T + i]));
+            const float ws = mx > 0.f ? mx / 448.f : 1.f;
+            inv[co] = 1.f / ws;
+            scales[co] = ws / FNN_FP8_ACT_MULT;
+        }
+    for (int cb = 0; cb < nblk; ++cb)
+        for (int ch = 0; ch < c.chunks; ++ch)
+            for (int ks = 0; ks < c.ksteps; ++ks)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        const int k = 8 * (lane >> 4) + j;
+                        int tch;
+                        const int tap = conv3d_kstep_tap(c.packing, ks, k >> 4, T, ch, c.chunks, &tch), ci = tch * 16 + (k & 15);
+                        const int co = conv3d_pack_cout(c.packing, nblk, cb, lane & 15);
+                        const int src = ci >= cin_pad0, cl = src ? ci - cin_pad0 : ci;
+                        float v = 0.f;
+                        if (tap >= 0 && co < cout_real && cl < (src ? cin_real1 : cin_real[0]))
+                            v = W[((size_t)co * cin_tot + (src ? cin_real[0] : 0) + cl) * T + tap] * inv[co];
+                        const size_t i = ((((size_t)cb * c.chunks + ch) * c.ksteps + ks) * 64 + lane) * 8 + j;
+                        if (p.fp8) ((uint8_t *)dst)[i] = f2e4m3(v);
+                        else ((unsigned short *)dst)[i] = fnn_half_bits(v);
+                    }
 }
 
 // The depth-shift kernels (FNN_PACK_ZR: 15 k-steps, one statistics row per tile): 3x3x3 layers of depth stride 1 with
@@ -934,16 +996,10 @@ static int launch_zr12(ConvParams p, hipStream_t st) {
     p.tile_d = TD;
     p.tiles_d = (p.Do + TD - 1) / TD; p.tiles_h = 1; p.tiles_w = 1;
     const size_t lds = (size_t)((TD + 2) * 14 * 20 * 32) + (size_t)2 * 15 * 1024 + 9 * 32 * 2 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_zr12_kernel<TD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     dim3 grid(p.N * p.tiles_d, (p.Cout / 16) / 2);
-    hipLaunchKernelGGL((conv3d_zr12_kernel<TD>), grid, dim3(576), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_zr12_kernel<TD>>(grid, dim3(576), lds, st, p);
 }
 
 // ----------------------------------------------------------------------------
@@ -1672,37 +1728,19 @@ static int launch_zs(ConvParams p, const ConvChoice &c, hipStream_t st) {
     p.tiles_h = (p.Ho + 3) / 4;
     p.tiles_w = (p.Wo + 7) / 8;
     const size_t lds = (size_t)((10 * 9 * 17 * 32 + 1023) & ~1023) + (size_t)2 * 15 * 1024 + (size_t)2 * 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_zs_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    fnn_allow_lds<conv3d_zs_kernel<2>>();
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     const int total = p.N * p.tiles_d * p.tiles_h * p.tiles_w, groups = (p.Cout / 16) / 2;
     if (c.kernel == CK_ZSW) {
         const size_t ldsw = lds - (size_t)2 * 64 + 4 * 32 * 2 * 4;
-        static bool attr_w = false;
-        if (!attr_w) {
-            (void)hipFuncSetAttribute((const void *)conv3d_zsw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_w = true;
-        }
-        hipLaunchKernelGGL(conv3d_zsw_kernel, dim3(p.N * p.tiles_h * p.tiles_w * c.segs, groups), dim3(256), ldsw, st, p, c.segs, c.tps);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        return fnn_launch_lds<conv3d_zsw_kernel>(dim3(p.N * p.tiles_h * p.tiles_w * c.segs, groups), dim3(256), ldsw, st, p, c.segs, c.tps);
     }
     if (c.kernel == CK_ZSP) {
         const size_t ldsp = lds - (size_t)2 * 64 + 4 * 32 * 2 * 4;
-        static bool attr_p = false;
-        if (!attr_p) {
-            (void)hipFuncSetAttribute((const void *)conv3d_zsp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_p = true;
-        }
-        hipLaunchKernelGGL(conv3d_zsp_kernel, dim3(c.gx, groups), dim3(256), ldsp, st, p, total);
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        return fnn_launch_lds<conv3d_zsp_kernel>(dim3(c.gx, groups), dim3(256), ldsp, st, p, total);
     }
-    dim3 grid(total, groups);
-    hipLaunchKernelGGL((conv3d_zs_kernel<2>), grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_zs_kernel<2>>(dim3(total, groups), dim3(256), lds, st, p);
 }
 
 // ----------------------------------------------------------------------------
@@ -1908,16 +1946,10 @@ static int launch_zr8(ConvParams p, hipStream_t st) {
     p.tiles_h = (p.Ho + 7) / 8;
     p.tiles_w = (p.Wo + 7) / 8;
     const size_t lds = (size_t)(((TD + 2) * 10 * 2 * 192 + 1023) & ~1023) + (size_t)NB * 15 * 512 + (size_t)NB * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_zr8_kernel<NB, TD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss || !p.oscale) return -2;
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL((conv3d_zr8_kernel<NB, TD>), grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_zr8_kernel<NB, TD>>(grid, dim3(256), lds, st, p);
 }
 
 template <int NB, int TD, int TH = 8>
@@ -1928,11 +1960,6 @@ static int launch_zr(ConvParams p, hipStream_t st) {
     p.tiles_w = (p.Wo + 7) / 8;
     size_t lds = (size_t)((TD + 2) * (TH + 2) * 12 * 32) + (size_t)NB * 15 * 1024;
     if (const char *pad = fnn_knob("FNN_ZR_LDS_PAD")) lds += (size_t)atoi(pad);      // A-B aid: fewer ZR workgroups per CU (room for another stream's kernels)
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_zr_kernel<NB, TD, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
@@ -1940,8 +1967,7 @@ static int launch_zr(ConvParams p, hipStream_t st) {
 #ifdef FNN_TMODE
     p.tmode = getenv("FNN_ZR_TMODE") ? atoi(getenv("FNN_ZR_TMODE")) : 0;     // timing-only proxies (wrong results): tools/zr_tmode.py
 #endif
-    hipLaunchKernelGGL((conv3d_zr_kernel<NB, TD, TH>), grid, dim3(TH * 32), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_zr_kernel<NB, TD, TH>>(grid, dim3(TH * 32), lds, st, p);
 }
 
 // the walking form for single-chunk layers: `segs` d-segments of `tps` tiles per in-plane window
@@ -1953,17 +1979,11 @@ static int launch_zrw(ConvParams p, const ConvChoice &c, hipStream_t st) {
     p.tiles_h = (p.Ho + 7) / 8;
     p.tiles_w = (p.Wo + 7) / 8;
     const size_t lds = (size_t)((TD + 2) * 10 * 12 * 32) + (size_t)NB * 15 * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)conv3d_zrw_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     dim3 grid(p.N * p.tiles_h * p.tiles_w * c.segs, (p.Cout / 16) / NB);
-    hipLaunchKernelGGL((conv3d_zrw_kernel<NB>), grid, dim3(256), lds, st, p, c.segs, c.tps);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<conv3d_zrw_kernel<NB>>(grid, dim3(256), lds, st, p, c.segs, c.tps);
 }
 
 // A persistent form of this kernel (tile ranges per workgroup, cross-tile prefetch, like conv3d_persist_kernel) was

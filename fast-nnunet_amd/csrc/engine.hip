@@ -42,10 +42,10 @@ struct Layer {
     size_t ss_off = 0;                // float2 (scale, shift) per channel
     size_t out_off = 0;               // halves, activation arena (for batch = 1)
     int64_t blob_w = 0, blob_b = 0, blob_g = 0, blob_beta = 0;
-    int chunks = 0, ksteps = 0, packing = 0;
+    int ksteps = 0;                   // TCONV: k-steps of its packed weights
     int stats_slots = FNN_STAT_REPL;  // rows per item in the stats buffer: atomics' replicas, or one row per tile
-    ConvChoice cc;                    // CONV: the kernel chosen when the engine was planned (conv_choose); chunks / ksteps / packing /
-                                      // stats_slots above are its
+    ConvChoice cc;                    // CONV: the kernel chosen when the engine was planned (conv_choose); its weights are packed
+                                      // for it, and stats_slots above is its
     // conv3d_thin.hip: the stem as one MFMA per 16 voxels (w_off2 = its weight fragment in wpk); a CONV that recomputes
     // its producer while staging (fuse = FUSE_STEM / FUSE_TCONV); a producer whose output is never written (virtual)
     bool mfma_stem = false, virtual_out = false;
@@ -228,6 +228,26 @@ int upload_ints(fnn_engine *e, const int *src, size_t n, int **dev, size_t *dev_
 // ---------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------
+// The shape facts of a conv layer that its kernel's choice looks at (conv_choose); forward_batch launches the layer from
+// them.  fuse / T: recomputing its producer T
+ThinParams conv_shape(const fnn_engine *e, const Layer &L, int fuse = 0, const Layer *T = nullptr) {
+    ThinParams tp{};
+    ConvParams &q = tp.c;
+    q.plan_N = e->max_batch; q.N = e->max_batch; q.Cout = L.cout_pad; q.fp8 = L.fp8;
+    q.n_src = L.n_src; q.chunks = (L.cin_pad[0] + (L.n_src > 1 ? L.cin_pad[1] : 0)) / 16;
+    q.src[0].C = L.cin_pad[0]; q.src[1].C = L.n_src > 1 ? L.cin_pad[1] : 0;
+    q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
+    q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
+    q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
+    tp.fuse = fuse;
+    if (T) {
+        tp.low.C = T->cin_pad[0];
+        tp.Dl = T->in_dims[0]; tp.Hl = T->in_dims[1]; tp.Wl = T->in_dims[2];
+        tp.tsd = T->s[0]; tp.tsh = T->s[1]; tp.tsw = T->s[2];
+    } else { tp.tsd = tp.tsh = tp.tsw = 1; }
+    return tp;
+}
+
 int build_plan(fnn_engine *e) {
     const fnn_arch_desc &a = e->arch;
     if (a.kind != FNN_NET_PLAIN && a.kind != FNN_NET_RESENC) return fail(e, FNN_E_UNSUPPORTED, "unknown network kind %d", a.kind);
@@ -402,24 +422,6 @@ int build_plan(fnn_engine *e) {
     e->blob_head_b = blob; blob += a.num_heads;
     e->blob_count = blob;
 
-    // The shape facts of a conv layer that its kernel's choice looks at (conv_choose); fuse / T: recomputing its producer T
-    auto conv_shape = [&](const Layer &L, int fuse, const Layer *T) {
-        ThinParams tp{};
-        ConvParams &q = tp.c;
-        q.plan_N = e->max_batch; q.N = e->max_batch; q.Cout = L.cout_pad;
-        q.n_src = L.n_src; q.chunks = (L.cin_pad[0] + (L.n_src > 1 ? L.cin_pad[1] : 0)) / 16;
-        q.src[0].C = L.cin_pad[0]; q.src[1].C = L.n_src > 1 ? L.cin_pad[1] : 0;
-        q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
-        q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
-        q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
-        tp.fuse = fuse;
-        if (T) {
-            tp.low.C = T->cin_pad[0];
-            tp.Dl = T->in_dims[0]; tp.Hl = T->in_dims[1]; tp.Wl = T->in_dims[2];
-            tp.tsd = T->s[0]; tp.tsh = T->s[1]; tp.tsw = T->s[2];
-        } else { tp.tsd = tp.tsh = tp.tsw = 1; }
-        return tp;
-    };
     for (Layer &L : e->layers)
         if (L.type == Layer::STEM) {
             if (!stem_mfma_ok(L.cin_real[0], L.k[0], L.k[1], L.k[2], L.cout_pad)) return fail(e, FNN_E_UNSUPPORTED, "stem conv shape");
@@ -436,13 +438,13 @@ int build_plan(fnn_engine *e) {
             if (consumers[L.src_layer[0]] != 1 || P.cout_pad != 16) continue;
             ConvChoice c;
             if (e->fuse_stem != 0 && L.n_src == 1 && P.type == Layer::STEM && P.mfma_stem && P.cin_real[0] == 1 && P.k[0] == L.k[0] &&
-                conv_choose(conv_shape(L, FUSE_STEM, nullptr), e->ov, c)) {
+                conv_choose(conv_shape(e, L, FUSE_STEM), e->ov, c)) {
                 // by default only where the row kernels take both halves: conv_row_stem_kernel + stem_row_kernel (statistics)
                 StemParams sp{};
                 sp.C = P.cin_real[0]; sp.kd = P.k[0]; sp.kh = P.k[1]; sp.kw = P.k[2]; sp.Cout = P.cout_pad;
                 sp.PD = P.out_dims[0]; sp.PH = P.out_dims[1]; sp.PW = P.out_dims[2];
                 if (e->fuse_stem == 1 || (c.kernel == CK_ROW_STEM && stem_row_ok(sp))) { L.fuse = FUSE_STEM; L.cc = c; P.virtual_out = true; }
-            } else if (L.n_src == 2 && P.type == Layer::TCONV && conv_choose(conv_shape(L, FUSE_TCONV, &P), e->ov, c)) {
+            } else if (L.n_src == 2 && P.type == Layer::TCONV && conv_choose(conv_shape(e, L, FUSE_TCONV, &P), e->ov, c)) {
                 L.fuse = FUSE_TCONV; L.cc = c; P.virtual_out = true;
             }
         }
@@ -477,7 +479,7 @@ int build_plan(fnn_engine *e) {
         } else if (L.type == Layer::CONV) {
             const int T = L.k[0] * L.k[1] * L.k[2];
             if (!L.fuse) {
-                ThinParams tp = conv_shape(L, 0, nullptr);
+                ThinParams tp = conv_shape(e, L);
                 // e4m3 operands: the stride-1 3x3x3 layers the fp8 ZR kernel takes (the strided depth-shift kernel is fp16 only).
                 // The choice sees the fp8 flag the launch will carry (the fp16-only six-row tiles); a layer the fp8 choice
                 // refuses stays fp16 with whatever that choice gives it.
@@ -496,8 +498,7 @@ int build_plan(fnn_engine *e) {
                                      (size_t)(&L - e->layers.data()), L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2], tp.c.chunks * 16, L.cout_pad);
                 L.fp8 = tp.c.fp8 != 0;
             }
-            L.packing = L.cc.packing; L.chunks = L.cc.chunks; L.ksteps = L.cc.ksteps;
-            L.w_off = wpk; wpk += (size_t)(L.cout_pad / 16) * L.chunks * L.ksteps * 512;
+            L.w_off = wpk; wpk += conv_packed_halves(L.cc, L.cout_pad);
         } else if (L.type == Layer::TCONV) {
             const int taps = L.s[0] * L.s[1] * L.s[2];
             L.ksteps = (L.cin_pad[0] + 31) / 32;
@@ -540,102 +541,6 @@ int build_plan(fnn_engine *e) {
 // ---------------------------------------------------------------------------
 // weight packing (host)
 // ---------------------------------------------------------------------------
-inline uint16_t f2h_bits(float f) { f16 h = (f16)f; uint16_t b; memcpy(&b, &h, 2); return b; }
-
-void pack_conv(const Layer &L, const float *W, uint16_t *dst) {
-    const int T = L.k[0] * L.k[1] * L.k[2];
-    const int cin_tot = L.cin_real[0] + (L.n_src > 1 ? L.cin_real[1] : 0);
-    const int nblk = L.cout_pad / 16;
-    for (int cb = 0; cb < nblk; ++cb)
-        for (int ch = 0; ch < L.chunks; ++ch)
-            for (int ks = 0; ks < L.ksteps; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 8 * (lane >> 4) + j;
-                        int tch;
-                        const int tap = conv3d_kstep_tap(L.packing, ks, k >> 4, T, ch, L.chunks, &tch), c = tch * 16 + (k & 15);
-                        const int co = conv3d_pack_cout(L.packing, nblk, cb, lane & 15);
-                        int src = 0, cl = c;
-                        if (c >= L.cin_pad[0]) { src = 1; cl = c - L.cin_pad[0]; }
-                        float v = 0.f;
-                        if (tap >= 0 && co < L.cout_real && cl < L.cin_real[src]) {
-                            const int ci = (src ? L.cin_real[0] : 0) + cl;
-                            v = W[((size_t)co * cin_tot + ci) * T + tap];
-                        }
-                        dst[((((size_t)cb * L.chunks + ch) * L.ksteps + ks) * 64 + lane) * 8 + j] = f2h_bits(v);
-                    }
-}
-
-// OCP e4m3 ("fn": no infinities, 0x7f = NaN), round to nearest even, saturating at +-448
-uint8_t f2e4m3(float f) {
-    const uint8_t sign = std::signbit(f) ? 0x80 : 0;
-    float a = std::fabs(f);
-    if (!(a == a)) return sign | 0x7f;
-    if (a >= 448.f) return sign | 0x7e;
-    if (a < 0x1p-6f) {                                          // subnormal: multiples of 2^-9
-        const int q = (int)std::nearbyint(a * 512.f);           // 0 .. 8 (8 = the smallest normal)
-        return sign | (uint8_t)q;                               // q = 8 -> exponent field 1, mantissa 0 = 0x08
-    }
-    int e;
-    const float m = std::frexp(a, &e);                          // a = m * 2^e, m in [0.5, 1)
-    int q = (int)std::nearbyint(m * 16.f);                      // 8 .. 16
-    int E = e - 1;                                              // a = (q / 8) * 2^E
-    if (q == 16) { q = 8; ++E; }
-    if (E > 8 || (E == 8 && q > 14)) return sign | 0x7e;
-    return sign | (uint8_t)(((E + 7) << 3) | (q - 8));
-}
-
-// fp8 weights of a ZR layer: same fragment order as pack_conv at one byte per element, one scale per output channel
-// (max |w| of the channel -> 448); scales[co] = w_scale / FNN_FP8_ACT_MULT is what the kernel's epilogue multiplies by.
-#define FNN_FP8_ACT_MULT 8.0f
-void pack_conv_fp8(const Layer &L, const float *W, uint8_t *dst, float *scales) {
-    const int T = L.k[0] * L.k[1] * L.k[2];
-    const int cin_tot = L.cin_real[0] + (L.n_src > 1 ? L.cin_real[1] : 0);
-    const int nblk = L.cout_pad / 16;
-    std::vector<float> inv(L.cout_pad, 0.f);
-    for (int co = 0; co < L.cout_pad; ++co) {
-        float mx = 0.f;
-        if (co < L.cout_real)
-            for (size_t i = 0; i < (size_t)cin_tot * T; ++i) mx = std::max(mx, std::fabs(W[(size_t)co * cin_tot * T + i]));
-        const float ws = mx > 0.f ? mx / 448.f : 1.f;
-        inv[co] = 1.f / ws;
-        scales[co] = ws / FNN_FP8_ACT_MULT;
-    }
-    for (int cb = 0; cb < nblk; ++cb)
-        for (int ch = 0; ch < L.chunks; ++ch)
-            for (int ks = 0; ks < L.ksteps; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 8 * (lane >> 4) + j;
-                        int tch;
-                        const int tap = conv3d_kstep_tap(L.packing, ks, k >> 4, T, ch, L.chunks, &tch), c = tch * 16 + (k & 15);
-                        const int co = conv3d_pack_cout(L.packing, nblk, cb, lane & 15);
-                        int src = 0, cl = c;
-                        if (c >= L.cin_pad[0]) { src = 1; cl = c - L.cin_pad[0]; }
-                        float v = 0.f;
-                        if (tap >= 0 && co < L.cout_real && cl < L.cin_real[src]) {
-                            const int ci = (src ? L.cin_real[0] : 0) + cl;
-                            v = W[((size_t)co * cin_tot + ci) * T + tap] * inv[co];
-                        }
-                        dst[((((size_t)cb * L.chunks + ch) * L.ksteps + ks) * 64 + lane) * 8 + j] = f2e4m3(v);
-                    }
-}
-
-void pack_tconv(const Layer &L, const float *W, uint16_t *dst) {
-    const int taps = L.s[0] * L.s[1] * L.s[2];
-    const int nblk = L.cout_pad / 16;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int ks = 0; ks < L.ksteps; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int ci = ks * 32 + 8 * (lane >> 4) + j, co = cb * 16 + (lane & 15);
-                        float v = 0.f;
-                        if (ci < L.cin_real[0] && co < L.cout_real) v = W[((size_t)ci * L.cout_real + co) * taps + tap];
-                        dst[((((size_t)tap * nblk + cb) * L.ksteps + ks) * 64 + lane) * 8 + j] = f2h_bits(v);
-                    }
-}
-
 void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, uint16_t *dst) {
     for (int hb = 0; hb < hblocks; ++hb)
         for (int ks = 0; ks < ksteps; ++ks)
@@ -644,7 +549,7 @@ void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, uint
                     const int ci = ks * 32 + 8 * (lane >> 4) + j, h = hb * 16 + (lane & 15);
                     float v = 0.f;
                     if (ci < cin && h < heads) v = W[(size_t)h * cin + ci];
-                    dst[(((size_t)hb * ksteps + ks) * 64 + lane) * 8 + j] = f2h_bits(v);
+                    dst[(((size_t)hb * ksteps + ks) * 64 + lane) * 8 + j] = fnn_half_bits(v);
                 }
 }
 
@@ -753,48 +658,32 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
             p.Cout = L.cout_pad;
             p.w = fw.fparam + L.w_off; p.bias = fw.fparam + L.bias_off;
             p.out = out; p.stats_out = stats_out;
-            p.tiles_d = (p.PD + FNN_TILE_D - 1) / FNN_TILE_D;
-            p.tiles_h = (p.PH + FNN_TILE_H - 1) / FNN_TILE_H;
-            p.tiles_w = (p.PW + FNN_TILE_W - 1) / FNN_TILE_W;
             Scope sc(e, st, FAM_STEM, L.flops * nb, L.bytes * nb);
             if (L.virtual_out) p.out = nullptr;                       // statistics only: the consumer recomputes the values
             rc = launch_stem_mfma(p, fw.wpk + L.w_off2, nb, st);
         } else if (L.type == Layer::CONV) {
-            ConvParams p{};
-            p.n_src = L.n_src;
+            const Layer *P = L.fuse ? &e->layers[L.src_layer[0]] : nullptr;        // the producer a fused layer recomputes
+            ThinParams tp = conv_shape(e, L, L.fuse, L.fuse == FUSE_TCONV ? P : nullptr);
+            ConvParams &p = tp.c;
+            p.N = nb;
             for (int i = 0; i < L.n_src; ++i) p.src[i] = make_src(e, fw, L.src_layer[i], nb);
             if (L.n_src == 1) { p.src[1] = p.src[0]; p.src[1].C = 0; }
-            p.N = nb; p.plan_N = e->max_batch; p.Di = L.in_dims[0]; p.Hi = L.in_dims[1]; p.Wi = L.in_dims[2];
-            p.Do = L.out_dims[0]; p.Ho = L.out_dims[1]; p.Wo = L.out_dims[2];
-            p.Cout = L.cout_pad;
-            p.kd = L.k[0]; p.kh = L.k[1]; p.kw = L.k[2];
-            p.sd = L.s[0]; p.sh = L.s[1]; p.sw = L.s[2];
             p.pd = (L.k[0] - 1) / 2; p.ph = (L.k[1] - 1) / 2; p.pw = (L.k[2] - 1) / 2;
             p.wpk = fw.wpk + L.w_off; p.bias = fw.fparam + L.bias_off;
-            p.out = out; p.stats_out = stats_out; p.stats_slots = L.stats_slots;
+            p.out = out; p.stats_out = stats_out;
             if (L.chunk_major) { p.out_vs = 16; p.out_cs = 16LL * p.Do * p.Ho * p.Wo; }
-            p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D;
-            p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
-            p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
-            p.chunks = L.chunks; p.ksteps = L.ksteps; p.packing = L.packing;
-            p.fp8 = L.fp8; p.oscale = L.fp8 ? fw.fparam + L.oscale_off : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
-            p.tile_d = FNN_TILE_D;
+            p.oscale = L.fp8 ? fw.fparam + L.oscale_off : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
             Scope sc(e, st, FAM_CONV, L.flops * nb, L.bytes * nb);
-            ThinParams tp{};
-            tp.c = p; tp.fuse = L.fuse;
             if (L.fuse) {
-                const Layer &P = e->layers[L.src_layer[0]];
-                tp.fbias = fw.fparam + P.bias_off;
+                tp.fbias = fw.fparam + P->bias_off;
                 if (L.fuse == FUSE_STEM) {
-                    tp.fw = fw.wpk + P.w_off2;
+                    tp.fw = fw.wpk + P->w_off2;
                     tp.vol = vol; tp.vol_batch_stride = vol_batch_stride; tp.Y = vdim[1]; tp.Z = vdim[2];
                     tp.origins = origins_dev; tp.flip_d = flip[0]; tp.flip_h = flip[1]; tp.flip_w = flip[2];
-                    tp.fss = e->ss + P.ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
+                    tp.fss = e->ss + P->ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
                 } else {
-                    tp.fw = fw.wpk + P.w_off;
-                    tp.low = make_src(e, fw, P.src_layer[0], nb);
-                    tp.Dl = P.in_dims[0]; tp.Hl = P.in_dims[1]; tp.Wl = P.in_dims[2];
-                    tp.tsd = P.s[0]; tp.tsh = P.s[1]; tp.tsw = P.s[2];
+                    tp.fw = fw.wpk + P->w_off;
+                    tp.low = make_src(e, fw, P->src_layer[0], nb);
                 }
             }
             rc = launch_conv(tp, L.cc, st);
@@ -1667,27 +1556,12 @@ int fnn_load_weights(fnn_engine *e, int fold, const float *blob, int64_t count) 
                 for (int t = 0; t < T; ++t)
                     for (int co = 0; co < L.cout_real; ++co)
                         fp[L.w_off + ((size_t)c * T + t) * L.cout_pad + co] = W[((size_t)co * C + c) * T + t];
-            if (L.mfma_stem) {                                        // MFMA "A" fragments [cout block][k-step]: lane (cout, k-group), k = c * T + tap
-                const int KST = stem_mfma_ksteps(C, T);
-                for (int cb = 0; cb < L.cout_pad / 16; ++cb)
-                    for (int ks = 0; ks < KST; ++ks)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j) {
-                                const int co = cb * 16 + (lane & 15);
-                                int c = 0, tap = 0;
-                                const bool live = stem_mfma_kmap(C, T, ks, 8 * (lane >> 4) + j, &c, &tap) && co < L.cout_real;
-                                wpk[L.w_off2 + ((size_t)(cb * KST + ks) * 64 + lane) * 8 + j] =
-                                    f2h_bits(live ? W[((size_t)co * C + c) * T + tap] : 0.f);
-                            }
-            }
+            if (L.mfma_stem) stem_mfma_pack(W, C, T, L.cout_real, L.cout_pad, wpk.data() + L.w_off2);
         } else if (L.type == Layer::CONV) {
-            if (L.packing == FNN_PACK_ZP)
-                conv_zp_pack(W, L.cout_real, L.cout_pad, L.cin_real[0], L.cin_pad[0], L.n_src > 1 ? L.cin_real[1] : 0,
-                             L.n_src > 1 ? L.cin_pad[1] : 0, wpk.data() + L.w_off);
-            else if (L.fp8) pack_conv_fp8(L, W, (uint8_t *)(wpk.data() + L.w_off), fp.data() + L.oscale_off);
-            else pack_conv(L, W, wpk.data() + L.w_off);
+            conv_pack_weights(conv_shape(e, L).c, L.cc, L.cout_real, L.cin_real, W, wpk.data() + L.w_off,
+                              L.fp8 ? fp.data() + L.oscale_off : nullptr);
         } else {
-            pack_tconv(L, W, wpk.data() + L.w_off);
+            tconv_pack_weights(W, L.cin_real[0], L.cout_real, L.cout_pad, L.s[0] * L.s[1] * L.s[2], L.ksteps, wpk.data() + L.w_off);
         }
         for (int c = 0; c < L.cout_real; ++c) {
             // A conv bias in front of an InstanceNorm cancels exactly (the norm removes the channel mean), so it is
@@ -1706,7 +1580,7 @@ int fnn_load_weights(fnn_engine *e, int fold, const float *blob, int64_t count) 
         for (int h = 0; h < cnt; ++h) fp[e->gpass_bias_off + (size_t)k * 64 + h] = blob[e->blob_head_b + h0 + h];
         fp[e->gpass_bias_off + (size_t)k * 64 + cnt] = 1.f;
     }
-    if (!fw.wpk) HIPCHK(e, hipMalloc((void **)&fw.wpk, wpk.size() * 2 + 1024));   // (+ 1 KB: see fnn_op_conv3d)
+    if (!fw.wpk) HIPCHK(e, hipMalloc((void **)&fw.wpk, fnn_weight_alloc_bytes(wpk.size())));
     if (!fw.fparam) HIPCHK(e, hipMalloc((void **)&fw.fparam, fp.size() * 4));
     HIPCHK(e, hipMemcpy(fw.wpk, wpk.data(), wpk.size() * 2, hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(fw.fparam, fp.data(), fp.size() * 4, hipMemcpyHostToDevice));

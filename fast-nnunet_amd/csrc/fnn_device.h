@@ -366,6 +366,21 @@ struct StatsFinalizeParams {
     float inv_count, eps;
 };
 
+// Kernels that take more dynamic LDS than the default limit: the limit of kernel K is raised to 160 KiB once per instantiation
+template <auto K> void fnn_allow_lds() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+}
+// ... and launched with `lds` bytes of it: 0, or -2 = the launch failed
+template <auto K, class... A> int fnn_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const A &...args) {
+    fnn_allow_lds<K>();
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 // launchers (implemented in the .hip files)
 int launch_stats_finalize(const StatsFinalizeParams &p, int N, hipStream_t st);
 int launch_region_copy(void *feat, long long n_slots, const int *regions, int n, void *message, int PD, int PH, int PW, int C, bool pack, hipStream_t st);   // fnn_pack_regions / fnn_unpack_regions
@@ -414,8 +429,23 @@ struct ConvOverrides {
 // tp.c: the layer's shape (sources' channels, dims, kernel, stride, Cout, fp8, plan_N; chunks = 16-channel chunks);
 // tp.fuse (and the FUSE_TCONV producer's shape) for a fused layer.  false: no kernel takes the layer.
 bool conv_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
-// tp.c carries the choice's packing / ksteps / chunks / stats_slots (and the weights packed for them)
+// Runs the layer on the chosen kernel; packing / ksteps / chunks / stats_slots come from c (the weights are packed for them)
 int launch_conv(const ThinParams &tp, const ConvChoice &c, hipStream_t st);
+// ---- a conv layer's weights, packed on the host for the kernel the choice c runs (conv3d_zr.hip) ----
+// W: [cout][cin0 + cin1][taps] fp32 (cin_real: the sources' real channel counts); p: the layer's shape (src[i].C, Cout, kd / kh /
+// kw, fp8).  dst: [cout block][chunk][k-step][64 lanes][8] in fp16, or with p.fp8 e4m3 bytes and scales[Cout] = the per-cout
+// weight scale / FNN_FP8_ACT_MULT; FNN_PACK_ZP: conv_zp_pack's order.
+#define FNN_FP8_ACT_MULT 8.0f         // fp8: activations are quantised as e4m3(value * FNN_FP8_ACT_MULT)
+void conv_pack_weights(const ConvParams &p, const ConvChoice &c, int cout_real, const int cin_real[2], const float *W, void *dst,
+                       float *scales);
+size_t conv_packed_halves(const ConvChoice &c, int cout_pad);                  // the packed weights' size in halves
+// Bytes to allocate for a buffer of `halves` packed weights: the ZR kernels' last weight load of a block reads one wave
+// (1 KiB) past it - the bytes are dropped, the address must exist
+inline size_t fnn_weight_alloc_bytes(size_t halves) { return halves * 2 + 1024; }
+uint8_t f2e4m3(float f);              // OCP e4m3 ("fn"), round to nearest even, saturating at +-448
+inline unsigned short fnn_half_bits(float f) { return __builtin_bit_cast(unsigned short, (f16)f); }
+// transposed conv: W [cin][cout][taps] -> dst [tap][cout block][k-step][64][8] (TconvParams::wpk), ksteps = ceil(cin_pad / 32)
+void tconv_pack_weights(const float *W, int cin, int cout, int cout_pad, int taps, int ksteps, unsigned short *dst);
 // the families (conv_choose's order); a *_choose returns false when the layer is not the family's
 bool zp_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c);
 int launch_conv2d_zp(ConvParams p, const ConvChoice &c, hipStream_t st);
@@ -434,6 +464,8 @@ bool stem_mfma_ok(int C, int kd, int kh, int kw, int cout_pad);
 int stem_mfma_stats_slots(int PD, int PH, int PW);
 int stem_mfma_ksteps(int C, int taps);
 bool stem_mfma_kmap(int C, int taps, int ks, int k, int *c, int *tap);   // (channel, tap) of element k of k-step ks; false = padding
+// the stem's W [cout][C][taps] as MFMA "A" fragments [cout block][k-step][64][8] (launch_stem_mfma's wfrag)
+void stem_mfma_pack(const float *W, int C, int taps, int cout_real, int cout_pad, unsigned short *dst);
 int launch_stem_mfma(const StemParams &p, const f16 *wfrag, int N, hipStream_t st);    // p.out == nullptr: statistics only
 bool gather_ok(const GatherParams &p);
 int launch_gather(const GatherParams &p, hipStream_t st);

@@ -649,6 +649,20 @@ __global__ __launch_bounds__(256, 2) void tconv_mfma_kernel(const TconvParams p)
     }
 }
 
+void tconv_pack_weights(const float *W, int cin, int cout, int cout_pad, int taps, int ksteps, unsigned short *dst) {
+    const int nblk = cout_pad / 16;
+    for (int tap = 0; tap < taps; ++tap)
+        for (int cb = 0; cb < nblk; ++cb)
+            for (int ks = 0; ks < ksteps; ++ks)
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        const int ci = ks * 32 + 8 * (lane >> 4) + j, co = cb * 16 + (lane & 15);
+                        float v = 0.f;
+                        if (ci < cin && co < cout) v = W[((size_t)ci * cout + co) * taps + tap];
+                        dst[((((size_t)tap * nblk + cb) * ksteps + ks) * 64 + lane) * 8 + j] = fnn_half_bits(v);
+                    }
+}
+
 int launch_tconv(const TconvParams &p, hipStream_t st) {
     const int vox_in = p.Di * p.Hi * p.Wi;
     if ((long long)p.Di * p.Hi * p.Wi > (1 << 24)) return -1;       // the kernel's float-reciprocal index arithmetic
@@ -1062,11 +1076,7 @@ bool launch_head_first_visit_ok(const HeadParams &p) {
 
 int launch_head(const HeadParams &p, hipStream_t st) {
     const int P = p.PD * p.PH * p.PW;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void *)seg_head_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    fnn_allow_lds<seg_head_kernel>();
     dim3 grid((P + 255) / 256);
     if (p.mode == 0) {
         const size_t lds = (size_t)((p.src.C * 8 + 255) & ~255) + (size_t)4 * 32 * HEAD_LD * 4;
@@ -1083,8 +1093,7 @@ int launch_head(const HeadParams &p, hipStream_t st) {
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
     const size_t lds = (size_t)((p.src.C * 8 + 255) & ~255) + (size_t)4 * 64 * 65 * 4;
-    hipLaunchKernelGGL(seg_head_kernel, grid, dim3(256), lds, st, p);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return fnn_launch_lds<seg_head_kernel>(grid, dim3(256), lds, st, p);
 }
 
 // ----------------------------------------------------------------------------

@@ -16,7 +16,6 @@
 namespace {
 
 inline int pad16(int c) { return (c + 15) / 16 * 16; }
-inline uint16_t f2h_bits(float f) { f16 h = (f16)f; uint16_t b; memcpy(&b, &h, 2); return b; }
 inline float h2f_bits(uint16_t b) { f16 h; memcpy(&h, &b, 2); return (float)h; }
 
 struct DevBuf {
@@ -39,7 +38,7 @@ void to_ndhwc(const float *x, int n, int c, int cp, size_t vox, std::vector<uint
             double s1 = 0, s2 = 0;
             const float *src = x + ((size_t)b * c + ch) * vox;
             for (size_t v = 0; v < vox; ++v) {
-                const uint16_t hb = f2h_bits(src[v]);
+                const uint16_t hb = fnn_half_bits(src[v]);
                 out[cm ? ((size_t)b * cp / 16 + ch / 16) * vox * 16 + v * 16 + ch % 16 : ((size_t)b * vox + v) * cp + ch] = hb;
                 const double f = h2f_bits(hb);
                 s1 += f; s2 += f * f;
@@ -114,7 +113,6 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     if (!make_src(s1, x, n, cin, vox, gamma1, beta1, slope1, true)) return FNN_E_HIP;
     if (x2 && !make_src(s2, x2, n, cin2, vox, gamma2, beta2, slope2, true)) return FNN_E_HIP;
     const int cp1 = pad16(cin), cp2 = x2 ? pad16(cin2) : 0, cop = pad16(cout);
-    const int T = k[0] * k[1] * k[2], cin_tot = cin + (x2 ? cin2 : 0);
     ConvParams p{};
     p.n_src = nsrc; p.src[0] = s1.d;
     if (x2) p.src[1] = s2.d; else { p.src[1] = s1.d; p.src[1].C = 0; }
@@ -127,38 +125,16 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     tp.c = p;
     ConvChoice cc;                                  // chosen per call, for this call's N (the engine chooses for its planned batch)
     if (!conv_choose(tp, ConvOverrides::from_env(), cc)) return FNN_E_UNSUPPORTED;
-    p.packing = cc.packing; p.ksteps = cc.ksteps; p.chunks = cc.chunks; p.stats_slots = cc.stats_slots;
     auto launch = [&]() { tp.c = p; return launch_conv(tp, cc, 0); };
-    const size_t slots = (size_t)p.stats_slots;
-    p.tiles_d = (p.Do + FNN_TILE_D - 1) / FNN_TILE_D; p.tiles_h = (p.Ho + FNN_TILE_H - 1) / FNN_TILE_H;
-    p.tiles_w = (p.Wo + FNN_TILE_W - 1) / FNN_TILE_W;
-    p.tile_d = FNN_TILE_D;
-    // pack weights [cout][cin_tot][T] -> [cb][chunk][ks][lane][8]
-    std::vector<uint16_t> wp((size_t)(cop / 16) * p.chunks * p.ksteps * 512, 0);
-    if (p.packing == FNN_PACK_ZP) conv_zp_pack(w, cout, cop, cin, cp1, x2 ? cin2 : 0, cp2, wp.data());
-    else
-    for (int cb = 0; cb < cop / 16; ++cb)
-        for (int ch = 0; ch < p.chunks; ++ch)
-            for (int ks = 0; ks < p.ksteps; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        int tch;
-                        const int kk = 8 * (lane >> 4) + j, tap = conv3d_kstep_tap(p.packing, ks, kk >> 4, T, ch, p.chunks, &tch);
-                        const int c = tch * 16 + (kk & 15);
-                        const int co = conv3d_pack_cout(p.packing, cop / 16, cb, lane & 15);
-                        int src = 0, cl = c;
-                        if (c >= cp1) { src = 1; cl = c - cp1; }
-                        const int creal = src ? cin2 : cin;
-                        float v = 0.f;
-                        if (tap >= 0 && co < cout && cl < creal) v = w[((size_t)co * cin_tot + (src ? cin : 0) + cl) * T + tap];
-                        wp[((((size_t)cb * p.chunks + ch) * p.ksteps + ks) * 64 + lane) * 8 + j] = f2h_bits(v);
-                    }
+    const size_t slots = (size_t)cc.stats_slots;
+    std::vector<uint16_t> wp(conv_packed_halves(cc, cop), 0);
+    const int cin_real[2] = {cin, x2 ? cin2 : 0};
+    conv_pack_weights(p, cc, cout, cin_real, w, wp.data(), nullptr);
     std::vector<float> bp(cop, 0.f);
     if (bias) for (int i = 0; i < cout; ++i) bp[i] = bias[i];
     const size_t ovox = (size_t)p.Do * p.Ho * p.Wo;
     DevBuf dw, db, dout, dst;
-    // (+ 1 KB: the ZR kernels' last weight load of a block reads one wave past it - the bytes are dropped, the address must exist)
-    if (!dw.alloc(wp.size() * 2 + 1024) || !db.alloc(cop * 4) || !dout.alloc((size_t)n * ovox * cop * 2) ||
+    if (!dw.alloc(fnn_weight_alloc_bytes(wp.size())) || !db.alloc(cop * 4) || !dout.alloc((size_t)n * ovox * cop * 2) ||
         !dst.alloc((size_t)n * slots * cop * 16)) return FNN_E_HIP;
     (void)hipMemcpy(dw.p, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(db.p, bp.data(), cop * 4, hipMemcpyHostToDevice);
@@ -262,16 +238,7 @@ int fnn_op_conv_transpose3d(int device, int n, const int dims[3],
     p.sd = stride[0]; p.sh = stride[1]; p.sw = stride[2];
     p.Cout = cop; p.nblk = cop / 16; p.ksteps = (cp + 31) / 32;
     std::vector<uint16_t> wp((size_t)taps * p.nblk * p.ksteps * 512, 0);
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cb = 0; cb < p.nblk; ++cb)
-            for (int ks = 0; ks < p.ksteps; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int ci = ks * 32 + 8 * (lane >> 4) + j, co = cb * 16 + (lane & 15);
-                        float v = 0.f;
-                        if (ci < cin && co < cout) v = w[((size_t)ci * cout + co) * taps + tap];
-                        wp[((((size_t)tap * p.nblk + cb) * p.ksteps + ks) * 64 + lane) * 8 + j] = f2h_bits(v);
-                    }
+    tconv_pack_weights(w, cin, cout, cop, taps, p.ksteps, wp.data());
     std::vector<float> bp(cop, 0.f);
     if (bias) for (int i = 0; i < cout; ++i) bp[i] = bias[i];
     const size_t ovox = vox * taps;

@@ -1,6 +1,6 @@
 """The paired k-step order of conv3d_zr_kernel (FNN_PACK_ZRP): the leftover in-plane tap 8 of two consecutive 16-channel
 chunks shares one k-step, 27 k-steps per 32 input channels instead of 30.  The CPU test pins the operand map of the host
-packers; the GPU tests compare the paired kernel with its padded order (FNN_NO_ZRP) bit for bit on small integers, where
+packer; the GPU tests compare the paired kernel with its padded order (FNN_NO_ZRP) bit for bit on small integers, where
 fp32 accumulation is exact in either order, and against torch within the op tolerance."""
 import ctypes
 
