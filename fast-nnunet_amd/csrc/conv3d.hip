@@ -1103,6 +1103,17 @@ bool conv_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c) {
     return row_choose(tp, o, c) || conv_choose_linear(p, o, c);
 }
 
+// Whether e4m3 operands stick (tp.c.fp8 on entry: the caller asks for them): only the stride-1 layers of 27 taps that the
+// fp8 ZR kernel takes (the strided depth-shift kernel is fp16 only).  The choice sees the fp8 flag the launch will carry
+// (the fp16-only six-row tiles); a layer the fp8 choice refuses is chosen again with fp16 operands.
+bool conv_choose_fp8(ThinParams &tp, const ConvOverrides &o, ConvChoice &c) {
+    ConvParams &p = tp.c;
+    if (p.fp8 && !(p.kd * p.kh * p.kw == 27 && p.sd == 1 && p.sh == 1 && p.sw == 1)) p.fp8 = 0;
+    bool ok = conv_choose(tp, o, c);
+    if (p.fp8 && c.packing != FNN_PACK_ZR) { p.fp8 = 0; ok = conv_choose(tp, o, c); }
+    return ok;
+}
+
 int launch_conv(const ThinParams &tp_in, const ConvChoice &c, hipStream_t st) {
     if (c.kernel == CK_ROW_STEM && tp_in.Y * tp_in.Z >= (1ll << 30)) {
         // the row form addresses the volume's planes with 32-bit offsets: a volume that large takes the tile form (the one

@@ -89,8 +89,11 @@ void conv_pack_weights(const ConvParams &p, const ConvChoice &c, int cout_real, 
             float mx = 0.f;
             if (co < cout_real)
                 for (size_t i = 0; i < (size_t)cin_tot * T; ++i) mx = std::max(mx, std::fabs(W[(size_t)co * cin_tot * T + i]));
-            const float ws = mx > 0.f ? mx / 448.f : 1.f;
-            inv[co] = 1.f / ws;
+            float ws = mx / 448.f, iv = 1.f / ws;
+            // an all-zero cout, or one whose max |w| < ~1.3e-36 makes ws subnormal and 1 / ws infinite (0 * inf = NaN): zero
+            // weights, as the fp16 encoding rounds them
+            if (!(mx > 0.f) || !std::isfinite(iv)) { ws = 1.f; iv = 0.f; }
+            inv[co] = iv;
             scales[co] = ws / FNN_FP8_ACT_MULT;
         }
     for (int cb = 0; cb < nblk; ++cb)

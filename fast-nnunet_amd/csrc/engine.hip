@@ -477,13 +477,10 @@ int build_plan(fnn_engine *e) {
             L.w_off = fp; fp += (size_t)L.cin_real[0] * T * L.cout_pad;
             if (L.mfma_stem) { L.w_off2 = wpk; wpk += (size_t)(L.cout_pad / 16) * stem_mfma_ksteps(L.cin_real[0], L.k[0] * L.k[1] * L.k[2]) * 512; }
         } else if (L.type == Layer::CONV) {
-            const int T = L.k[0] * L.k[1] * L.k[2];
             if (!L.fuse) {
                 ThinParams tp = conv_shape(e, L);
-                // e4m3 operands: the stride-1 3x3x3 layers the fp8 ZR kernel takes (the strided depth-shift kernel is fp16 only).
-                // The choice sees the fp8 flag the launch will carry (the fp16-only six-row tiles); a layer the fp8 choice
-                // refuses stays fp16 with whatever that choice gives it.
-                tp.c.fp8 = a.precision == FNN_PREC_F8 && T == 27 && L.s[0] == 1 && L.s[1] == 1 && L.s[2] == 1 &&
+                // e4m3 operands where conv_choose_fp8 lets them stick (the stride-1 3x3x3 layers the fp8 ZR kernel takes)
+                tp.c.fp8 = a.precision == FNN_PREC_F8 &&
                            !(L.src_layer[0] >= 0 && e->layers[L.src_layer[0]].type == Layer::GATHER);   // (the network input keeps fp16: the stem was never an fp8 layer)
                 if (tp.c.fp8 && e->ov.fp8_levels >= 0) {
                     // sensitivity studies (tools/fp8_sensitivity.py): e4m3 operands only at the resolution levels of the bit mask
@@ -492,8 +489,7 @@ int build_plan(fnn_engine *e) {
                     const int level = (int)std::lround(std::log2(P / (double)ovox) / 3.0);
                     tp.c.fp8 = ((e->ov.fp8_levels >> level) & 1) != 0;
                 }
-                bool ok = conv_choose(tp, e->ov, L.cc);
-                if (tp.c.fp8 && L.cc.packing != FNN_PACK_ZR) { tp.c.fp8 = 0; ok = conv_choose(tp, e->ov, L.cc); }
+                const bool ok = conv_choose_fp8(tp, e->ov, L.cc);
                 if (!ok) return fail(e, FNN_E_UNSUPPORTED, "no conv kernel takes layer %zu (%dx%dx%d, stride %dx%dx%d, %d -> %d channels)",
                                      (size_t)(&L - e->layers.data()), L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2], tp.c.chunks * 16, L.cout_pad);
                 L.fp8 = tp.c.fp8 != 0;

@@ -429,6 +429,9 @@ struct ConvOverrides {
 // tp.c: the layer's shape (sources' channels, dims, kernel, stride, Cout, fp8, plan_N; chunks = 16-channel chunks);
 // tp.fuse (and the FUSE_TCONV producer's shape) for a fused layer.  false: no kernel takes the layer.
 bool conv_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
+// conv_choose for a layer whose caller asks for e4m3 operands (tp.c.fp8 = 1): the rule of where they stick, shared by the
+// engine's planner and fnn_op_conv3d.  On return tp.c.fp8 says whether the choice c runs them.
+bool conv_choose_fp8(ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
 // Runs the layer on the chosen kernel; packing / ksteps / chunks / stats_slots come from c (the weights are packed for them)
 int launch_conv(const ThinParams &tp, const ConvChoice &c, hipStream_t st);
 // ---- a conv layer's weights, packed on the host for the kernel the choice c runs (conv3d_zr.hip) ----

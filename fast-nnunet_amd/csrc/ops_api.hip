@@ -29,6 +29,9 @@ struct DevBuf {
 // FNN_OP_CHUNK_MAJOR=1 (next to FNN_KNOBS=1; read per call): tensors of more than 16 channels travel chunk-major
 // ([C / 16][voxels][16]; fnn_device.h, SrcDesc) through the conv / transposed-conv ops, as in the engine
 bool op_chunk_major(int cp) { const char *v = fnn_knob("FNN_OP_CHUNK_MAJOR"); return v && v[0] != '0' && cp > 16; }
+// FNN_OP_F8=1 (next to FNN_KNOBS=1; read per call): e4m3 operands on the layers the engine's FNN_PREC_F8 plan gives them
+// (conv_choose_fp8), weights and output scales packed as the engine packs them
+bool op_fp8() { const char *v = fnn_knob("FNN_OP_F8"); return v && v[0] != '0'; }
 
 void to_ndhwc(const float *x, int n, int c, int cp, size_t vox, std::vector<uint16_t> &out, std::vector<double> *stats, bool cm = false) {
     out.assign((size_t)n * vox * cp, 0);
@@ -121,26 +124,31 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     p.pd = (k[0] - 1) / 2; p.ph = (k[1] - 1) / 2; p.pw = (k[2] - 1) / 2;
     p.Do = (p.Di + 2 * p.pd - p.kd) / p.sd + 1; p.Ho = (p.Hi + 2 * p.ph - p.kh) / p.sh + 1; p.Wo = (p.Wi + 2 * p.pw - p.kw) / p.sw + 1;
     p.Cout = cop; p.chunks = (cp1 + cp2) / 16;
+    p.fp8 = op_fp8();
     ThinParams tp{};
     tp.c = p;
     ConvChoice cc;                                  // chosen per call, for this call's N (the engine chooses for its planned batch)
-    if (!conv_choose(tp, ConvOverrides::from_env(), cc)) return FNN_E_UNSUPPORTED;
+    if (!conv_choose_fp8(tp, ConvOverrides::from_env(), cc)) return FNN_E_UNSUPPORTED;
+    p.fp8 = tp.c.fp8;
     auto launch = [&]() { tp.c = p; return launch_conv(tp, cc, 0); };
     const size_t slots = (size_t)cc.stats_slots;
     std::vector<uint16_t> wp(conv_packed_halves(cc, cop), 0);
+    std::vector<float> scales(p.fp8 ? cop : 0, 0.f);
     const int cin_real[2] = {cin, x2 ? cin2 : 0};
-    conv_pack_weights(p, cc, cout, cin_real, w, wp.data(), nullptr);
+    conv_pack_weights(p, cc, cout, cin_real, w, wp.data(), p.fp8 ? scales.data() : nullptr);
     std::vector<float> bp(cop, 0.f);
     if (bias) for (int i = 0; i < cout; ++i) bp[i] = bias[i];
     const size_t ovox = (size_t)p.Do * p.Ho * p.Wo;
-    DevBuf dw, db, dout, dst;
+    DevBuf dw, db, dsc, dout, dst;
     if (!dw.alloc(fnn_weight_alloc_bytes(wp.size())) || !db.alloc(cop * 4) || !dout.alloc((size_t)n * ovox * cop * 2) ||
-        !dst.alloc((size_t)n * slots * cop * 16)) return FNN_E_HIP;
+        !dst.alloc((size_t)n * slots * cop * 16) || (p.fp8 && !dsc.alloc(cop * 4))) return FNN_E_HIP;
     (void)hipMemcpy(dw.p, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(db.p, bp.data(), cop * 4, hipMemcpyHostToDevice);
+    if (p.fp8) (void)hipMemcpy(dsc.p, scales.data(), cop * 4, hipMemcpyHostToDevice);
     (void)hipMemset(dst.p, 0, (size_t)n * slots * cop * 16);
     (void)hipMemset(dout.p, 0, (size_t)n * ovox * cop * 2);
     p.wpk = dw.as<f16>(); p.bias = db.as<float>(); p.out = dout.as<f16>(); p.stats_out = dst.as<double>();
+    p.oscale = p.fp8 ? dsc.as<float>() : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
     const bool ocm = op_chunk_major(cop);
     if (ocm) { p.out_vs = 16; p.out_cs = 16LL * (long long)ovox; }
 #ifdef FNN_STAMPS

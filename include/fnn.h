@@ -432,7 +432,11 @@ int fnn_patch_work(const fnn_engine *e, double *flops, double *act_bytes);
  * LeakyReLU(slopeK).  gammaK == NULL = identity.  A second input (x2 != NULL)
  * is the concat-free replacement of torch.cat((x, x2), 1).
  * stats_out (may be NULL): per (n, cout) sum and sum of squares of the
- * fp16-rounded outputs, doubles [n][cout][2]. */
+ * fp16-rounded outputs, doubles [n][cout][2].
+ * FNN_OP_F8=1 (honoured next to FNN_KNOBS=1, read per call): OCP e4m3
+ * operands where an FNN_PREC_F8 engine would give them (3x3x3 stride-1 layers
+ * the fp8 depth-shift kernel takes; other layers run their fp16 kernel), with
+ * the weights, output scales and activation multiplier the engine uses. */
 int fnn_op_conv3d(int device, int n, const int dims[3],
                   const float *x, int cin, const float *gamma1, const float *beta1, float slope1,
                   const float *x2, int cin2, const float *gamma2, const float *beta2, float slope2,
