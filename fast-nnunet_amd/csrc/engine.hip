@@ -19,6 +19,7 @@
 #include <climits>
 #include <vector>
 #include <thread>
+#include <variant>
 
 namespace {
 
@@ -66,6 +67,14 @@ struct FoldWeights {
     bool loaded = false;
 };
 
+// What one batch in flight writes: every layer's activations, the InstanceNorm statistics, and the (scale, shift) rows -
+// fp32 [layer][max_batch][2][C], followed by the same rows in fp16 (ssh_rows)
+struct Arena {
+    f16 *act = nullptr;
+    double *stats = nullptr;
+    float *ss = nullptr;
+};
+
 inline int pad16(int c) { return (c + 15) / 16 * 16; }
 // z pitch of the volume accumulators: rows start 16-byte aligned for the vectorised read-modify-write
 inline long long zpitch(long long z) { return (z + 7) / 8 * 8; }
@@ -95,17 +104,14 @@ struct fnn_engine {
     int64_t blob_count = 0;
     size_t wpk_halves = 0, fparam_floats = 0, stats_doubles = 0, act_halves = 0, ss_count = 0;
     std::vector<FoldWeights> folds;
-    f16 *act = nullptr;
-    double *stats = nullptr;
-    float *ss = nullptr;                    // [layer][max_batch][2][C]
-    // Batches in flight (fnn_accumulate / predict): one activation arena and one internal stream per batch in flight
+    // Batches in flight (fnn_accumulate / predict): one arena and one internal stream per batch in flight
     // (four by default since round 6, FNN_PIPES = 2..8; measured 2 -> 3: +1.5 %, 3 -> 4: +0.3 ... +0.9 %, beyond: nothing).  The network alternates between
     // HBM-bound (thin full-resolution convs, seg head) and MFMA-bound kernels; with the following batches' forwards on
     // the other streams they overlap.  The heads stay ordered (events), so the accumulation order - and with it every
     // rounding - is the reference's.  288 GB of HBM make the extra arenas free.
     static constexpr int MAXP = 8;
-    int n_pipe = 0;                         // arenas / streams allocated (0 until the first multi-batch run)
-    f16 *actp[MAXP] = {}; double *statsp[MAXP] = {}; float *ssp[MAXP] = {};      // [0] aliases act / stats / ss
+    Arena arena[MAXP];                      // [0]: fnn_create's, the one a single stream uses; [k > 0]: add_pipes
+    int n_pipe = 0;                         // streams allocated (0 until the first multi-batch run); arenas 1 .. n_pipe - 1 with them
     hipStream_t pipe[MAXP] = {};
     hipEvent_t ev_start = nullptr, ev_head[MAXP] = {}, ev_done[MAXP] = {};
     f16 *gauss = nullptr;
@@ -191,12 +197,35 @@ bool is_device_ptr(const void *p) {
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-int ensure(fnn_engine *e, void **p, size_t *have, size_t need) {
+template <class T> int ensure(fnn_engine *e, T **p, size_t *have, size_t need) {
     if (*have >= need && *p) return 0;
     if (*p) (void)hipFree(*p);
     *p = nullptr; *have = 0;
-    HIPCHK(e, hipMalloc(p, need));
+    HIPCHK(e, hipMalloc((void **)p, need));
     *have = need;
+    return 0;
+}
+
+// An arena's buffers in bytes - activations, statistics, scale / shift rows; returns their sum
+size_t arena_bytes(const fnn_engine *e, size_t b[3]) {
+    b[0] = e->act_halves * e->max_batch * sizeof(f16);
+    b[1] = e->stats_doubles * e->max_batch * sizeof(double);
+    b[2] = (e->ss_count * e->max_batch * 3 + 8) * sizeof(float);           // fp32 rows, then the fp16 rows (ssh_rows)
+    return b[0] + b[1] + b[2];
+}
+
+void arena_free(Arena &A) {
+    for (void *p : {(void *)A.act, (void *)A.stats, (void *)A.ss}) if (p) (void)hipFree(p);
+    A = Arena{};
+}
+
+int arena_alloc(fnn_engine *e, Arena &A) {
+    size_t b[3];
+    arena_bytes(e, b);
+    void **p[3] = {(void **)&A.act, (void **)&A.stats, (void **)&A.ss};
+    static const char *const name[3] = {"activations", "stats", "scale/shift"};
+    for (int i = 0; i < 3; ++i)
+        if (hipError_t r = hipMalloc(p[i], b[i])) { arena_free(A); return fail(e, FNN_E_HIP, "hipMalloc(%s) failed: %s", name[i], hipGetErrorString(r)); }
     return 0;
 }
 
@@ -206,11 +235,7 @@ int ensure(fnn_engine *e, void **p, size_t *have, size_t need) {
 int upload_ints(fnn_engine *e, const int *src, size_t n, int **dev, size_t *dev_cap, int **host, size_t *host_cap,
                 hipEvent_t *ev, hipStream_t st) {
     const size_t bytes = n * sizeof(int) + 64;
-    {
-        void *t = *dev;
-        if (int rc = ensure(e, &t, dev_cap, bytes)) return rc;
-        *dev = (int *)t;
-    }
+    if (int rc = ensure(e, dev, dev_cap, bytes)) return rc;
     if (!*ev) HIPCHK(e, hipEventCreateWithFlags(ev, hipEventDisableTiming));
     else HIPCHK(e, hipEventSynchronize(*ev));
     if (*host_cap < bytes) {
@@ -607,41 +632,47 @@ void collect_profile(fnn_engine *e, int64_t n_patches) {
 // ---------------------------------------------------------------------------
 // the fp16 scale / shift rows (SrcDesc::ssh) live behind the fp32 rows of the same arena: [ss_count * max_batch * 2 + 4] floats,
 // then ss_count * max_batch * 2 halves
-static unsigned short *ssh_rows(fnn_engine *e) { return (unsigned short *)(e->ss + e->ss_count * e->max_batch * 2 + 4); }
+unsigned short *ssh_rows(const fnn_engine *e, const Arena &A) { return (unsigned short *)(A.ss + e->ss_count * e->max_batch * 2 + 4); }
 
-SrcDesc make_src(fnn_engine *e, const FoldWeights &fw, int layer, int nb) {
+// A layer's output layout as SrcDesc::vs / cs: chunk-major (16, 16 x voxels), or channels-last - (0, 0), which the launch
+// parameters' out_vs / out_cs read as (C, 16)
+struct Layout { int vs; long long cs; };
+Layout layout(const Layer &L) {
+    return L.chunk_major ? Layout{16, 16LL * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]} : Layout{0, 0};
+}
+
+SrcDesc make_src(const fnn_engine *e, const Arena &A, int layer) {
     const Layer &L = e->layers[layer];
     SrcDesc s{};
-    s.ptr = e->act + L.out_off * e->max_batch;
+    s.ptr = A.act + L.out_off * e->max_batch;
     s.C = L.cout_pad;
-    if (L.chunk_major) { s.vs = 16; s.cs = 16LL * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]; }
-    else { s.vs = L.cout_pad; s.cs = 16; }
+    const Layout lay = layout(L);
+    s.vs = lay.vs ? lay.vs : L.cout_pad; s.cs = lay.vs ? lay.cs : 16;   // (spelled out: a one-source conv's src[1] is a copy with C = 0)
     if (L.has_norm) {
-        s.ss = e->ss + L.ss_off * e->max_batch * 2;
-        s.ssh = ssh_rows(e) + L.ss_off * e->max_batch * 2;           // halves: [N][C / 8][16] = 2 C per item
+        s.ss = A.ss + L.ss_off * e->max_batch * 2;
+        s.ssh = ssh_rows(e, A) + L.ss_off * e->max_batch * 2;        // halves: [N][C / 8][16] = 2 C per item
         s.slope = L.act ? e->arch.slope : 1.f;
     } else {
         s.ss = nullptr; s.ssh = nullptr; s.slope = 1.f;
     }
-    (void)fw;
-    (void)nb;
     return s;
 }
 
-// head_out / head_ss: where the network's last layer writes its raw output and its (scale, shift) rows instead of the
-// arena (the gather path keeps them per patch)
-int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch_stride, const long long vdim[3],
+// One batch's forward in arena A.  head_out / head_ss: where the network's last layer writes its raw output and its
+// (scale, shift) rows instead of the arena (the gather path keeps them per patch)
+int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, long long vol_batch_stride, const long long vdim[3],
                   const int *origins_dev, int nb, const int flip[3], hipStream_t st, f16 *head_out = nullptr,
                   float *head_ss = nullptr, unsigned short *head_ssh = nullptr) {
     const FoldWeights &fw = e->folds[fold];
-    HIPCHK(e, hipMemsetAsync(e->stats, 0, e->stats_doubles * e->max_batch * sizeof(double), st));
+    HIPCHK(e, hipMemsetAsync(A.stats, 0, e->stats_doubles * e->max_batch * sizeof(double), st));
     struct LayerMark { fnn_engine *e; ~LayerMark() { e->cur_layer = -1; } } mark{e};
     for (size_t li = 0; li < e->layers.size(); ++li) {
         const Layer &L = e->layers[li];
         e->cur_layer = (int)li;
-        f16 *out = e->act + L.out_off * e->max_batch;
+        f16 *out = A.act + L.out_off * e->max_batch;
         if (head_out && (int)li == e->head_src) out = head_out;
-        double *stats_out = L.has_norm ? e->stats + L.stats_off * e->max_batch : nullptr;
+        const Layout lay = layout(L);
+        double *stats_out = L.has_norm ? A.stats + L.stats_off * e->max_batch : nullptr;
         int rc = 0;
         if (L.type == Layer::STEM) {
             StemParams p{};
@@ -662,12 +693,12 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
             ThinParams tp = conv_shape(e, L, L.fuse, L.fuse == FUSE_TCONV ? P : nullptr);
             ConvParams &p = tp.c;
             p.N = nb;
-            for (int i = 0; i < L.n_src; ++i) p.src[i] = make_src(e, fw, L.src_layer[i], nb);
+            for (int i = 0; i < L.n_src; ++i) p.src[i] = make_src(e, A, L.src_layer[i]);
             if (L.n_src == 1) { p.src[1] = p.src[0]; p.src[1].C = 0; }
             p.pd = (L.k[0] - 1) / 2; p.ph = (L.k[1] - 1) / 2; p.pw = (L.k[2] - 1) / 2;
             p.wpk = fw.wpk + L.w_off; p.bias = fw.fparam + L.bias_off;
             p.out = out; p.stats_out = stats_out;
-            if (L.chunk_major) { p.out_vs = 16; p.out_cs = 16LL * p.Do * p.Ho * p.Wo; }
+            p.out_vs = lay.vs; p.out_cs = lay.cs;
             p.oscale = L.fp8 ? fw.fparam + L.oscale_off : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
             Scope sc(e, st, FAM_CONV, L.flops * nb, L.bytes * nb);
             if (L.fuse) {
@@ -676,10 +707,10 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
                     tp.fw = fw.wpk + P->w_off2;
                     tp.vol = vol; tp.vol_batch_stride = vol_batch_stride; tp.Y = vdim[1]; tp.Z = vdim[2];
                     tp.origins = origins_dev; tp.flip_d = flip[0]; tp.flip_h = flip[1]; tp.flip_w = flip[2];
-                    tp.fss = e->ss + P->ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
+                    tp.fss = A.ss + P->ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
                 } else {
                     tp.fw = fw.wpk + P->w_off;
-                    tp.low = make_src(e, fw, P->src_layer[0], nb);
+                    tp.low = make_src(e, A, P->src_layer[0]);
                 }
             }
             rc = launch_conv(tp, L.cc, st);
@@ -690,44 +721,41 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
             p.origins = origins_dev;
             p.flip_d = flip[0]; p.flip_h = flip[1]; p.flip_w = flip[2];
             p.PD = L.out_dims[0]; p.PH = L.out_dims[1]; p.PW = L.out_dims[2]; p.N = nb;
-            p.out = out;
-            if (L.chunk_major) { p.out_vs = 16; p.out_cs = 16LL * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]; }
+            p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs;
             Scope sc(e, st, FAM_STEM, 0, 2.0 * nb * (2.0 * L.cin_real[0] + L.cout_pad) * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]);
             rc = launch_patch_input(p, st);
         } else if (L.type == Layer::POOL) {
             if (L.pool_fused) continue;                               // written by the COMBINE launch of its source
             PoolParams p{};
-            p.src = make_src(e, fw, L.src_layer[0], nb);
+            p.src = make_src(e, A, L.src_layer[0]);
             p.N = nb; p.Di = L.in_dims[0]; p.Hi = L.in_dims[1]; p.Wi = L.in_dims[2];
             p.sd = L.s[0]; p.sh = L.s[1]; p.sw = L.s[2];
-            p.out = out;
-            if (L.chunk_major) { p.out_vs = 16; p.out_cs = 16LL * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]; }
+            p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs;
             Scope sc(e, st, FAM_TCONV, 0);
             rc = launch_avgpool(p, st);
         } else if (L.type == Layer::COMBINE) {
             CombineParams p{};
-            p.a = make_src(e, fw, L.src_layer[0], nb);
-            p.b = make_src(e, fw, L.src_layer[1], nb);
+            p.a = make_src(e, A, L.src_layer[0]);
+            p.b = make_src(e, A, L.src_layer[1]);
             p.vox = (long long)L.out_dims[0] * L.out_dims[1] * L.out_dims[2];
-            p.N = nb; p.slope = e->arch.slope; p.out = out;
-            if (L.chunk_major) { p.out_vs = 16; p.out_cs = 16LL * p.vox; }
+            p.N = nb; p.slope = e->arch.slope; p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs;
             if (L.pool_layer >= 0) {
                 const Layer &P = e->layers[L.pool_layer];
-                p.pool_out = e->act + P.out_off * e->max_batch;
+                const Layout pool = layout(P);
+                p.pool_out = A.act + P.out_off * e->max_batch;
                 p.D = L.out_dims[0]; p.H = L.out_dims[1]; p.W = L.out_dims[2];
                 p.psd = P.s[0]; p.psh = P.s[1]; p.psw = P.s[2];
-                if (P.chunk_major) { p.pool_vs = 16; p.pool_cs = 16LL * P.out_dims[0] * P.out_dims[1] * P.out_dims[2]; }
+                p.pool_vs = pool.vs; p.pool_cs = pool.cs;
             }
             Scope sc(e, st, FAM_TCONV, 0);
             rc = launch_combine(p, st);
         } else {
             TconvParams p{};
-            p.src = make_src(e, fw, L.src_layer[0], nb);
+            p.src = make_src(e, A, L.src_layer[0]);
             p.N = nb; p.Di = L.in_dims[0]; p.Hi = L.in_dims[1]; p.Wi = L.in_dims[2];
             p.sd = L.s[0]; p.sh = L.s[1]; p.sw = L.s[2];
             p.Cout = L.cout_pad; p.wpk = fw.wpk + L.w_off; p.bias = fw.fparam + L.bias_off;
-            p.out = out; p.ksteps = L.ksteps; p.nblk = L.cout_pad / 16;
-            if (L.chunk_major) { p.out_vs = 16; p.out_cs = 16LL * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]; }
+            p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs; p.ksteps = L.ksteps; p.nblk = L.cout_pad / 16;
             if (L.virtual_out) continue;                              // computed inside its consumer (conv3d_thin.hip)
             Scope sc(e, st, FAM_TCONV, L.flops * nb);
             rc = launch_tconv(p, st);
@@ -736,8 +764,8 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
         if (L.has_norm) {
             StatsFinalizeParams q{};
             q.stats = stats_out; q.gamma = fw.fparam + L.gamma_off; q.beta = fw.fparam + L.beta_off;
-            q.ss = e->ss + L.ss_off * e->max_batch * 2; q.C = L.cout_pad; q.nrep = L.stats_slots;
-            q.ssh = ssh_rows(e) + L.ss_off * e->max_batch * 2;
+            q.ss = A.ss + L.ss_off * e->max_batch * 2; q.C = L.cout_pad; q.nrep = L.stats_slots;
+            q.ssh = ssh_rows(e, A) + L.ss_off * e->max_batch * 2;
             if (head_ss && (int)li == e->head_src) q.ss = head_ss;
             if (head_ssh && (int)li == e->head_src) q.ssh = head_ssh;
             q.inv_count = 1.f / ((float)L.out_dims[0] * L.out_dims[1] * L.out_dims[2]); q.eps = e->arch.eps;
@@ -747,11 +775,11 @@ int forward_batch(fnn_engine *e, int fold, const float *vol, long long vol_batch
     return 0;
 }
 
-HeadParams make_head(fnn_engine *e, int fold, int b) {
+HeadParams make_head(const fnn_engine *e, const Arena &A, int fold, int b) {
     const fnn_arch_desc &a = e->arch;
     const FoldWeights &fw = e->folds[fold];
     HeadParams h{};
-    h.src = make_src(e, fw, e->head_src, 0);
+    h.src = make_src(e, A, e->head_src);
     h.b = b; h.PD = a.patch[0]; h.PH = a.patch[1]; h.PW = a.patch[2];
     h.heads = a.num_heads; h.hblocks = e->hblocks; h.ksteps = e->head_ksteps;
     h.wpk = fw.wpk + e->head_w_off; h.bias = fw.fparam + e->head_bias_off;
@@ -781,10 +809,6 @@ struct VolPlan {
     int64_t n_patches = 0;
 };
 
-int plan_volume_p(const int32_t patch[3], const int64_t sp[3], double step, bool two_d, VolPlan &vp);
-int plan_volume(const fnn_arch_desc &a, const int64_t sp[3], double step, VolPlan &vp) {
-    return plan_volume_p(a.patch, sp, step, a.spatial_dims == 2, vp);
-}
 // _internal_get_sliding_window_slicers (:506-538): padding to >= patch, tile starts per axis, x-major order.
 // two_d: the `2d` branch (:508-524) - the first axis is not tiled, every slice is visited once.
 int plan_volume_p(const int32_t patch[3], const int64_t sp[3], double step, bool two_d, VolPlan &vp) {
@@ -807,6 +831,13 @@ int plan_volume_p(const int32_t patch[3], const int64_t sp[3], double step, bool
         for (int64_t y : vp.steps[1])
             for (int64_t z : vp.steps[2]) { vp.origins.push_back((int)x); vp.origins.push_back((int)y); vp.origins.push_back((int)z); }
     vp.n_patches = (int64_t)vp.origins.size() / 3;
+    return 0;
+}
+
+// The plan of a call's volume (shape [C][X][Y][Z]); the call fails when the shape and the step size make none
+int plan_volume(fnn_engine *e, const int64_t shape[4], const fnn_opts &o, VolPlan &vp) {
+    if (plan_volume_p(e->arch.patch, shape + 1, o.tile_step_size, e->arch.spatial_dims == 2, vp) != 0)
+        return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
     return 0;
 }
 
@@ -852,80 +883,128 @@ inline int no_autocast(fnn_engine *e, const fnn_opts *o, const char *who) {
 
 struct Box { int64_t lo[3], hi[3]; };
 
+std::vector<int64_t> id_range(int64_t first, int64_t n) {
+    std::vector<int64_t> ids(n);
+    for (int64_t i = 0; i < n; ++i) ids[i] = first + i;
+    return ids;
+}
+
+// ---- argument checks the entry points share.  out_lo / out_hi: the box of the un-padded volume a call writes; `acc`:
+// the accumulator box (padded volume) it reads, or nullptr
+int check_out_box(fnn_engine *e, const VolPlan &vp, const int64_t shape[4], const int64_t out_lo[3], const int64_t out_hi[3],
+                  const Box *acc) {
+    for (int d = 0; d < 3; ++d) {
+        if (out_lo[d] < 0 || out_hi[d] > shape[1 + d] || out_lo[d] >= out_hi[d]) return fail(e, FNN_E_INVALID, "output box out of bounds");
+        if (acc && (out_lo[d] + vp.lo[d] < acc->lo[d] || out_hi[d] + vp.lo[d] > acc->hi[d]))
+            return fail(e, FNN_E_INVALID, "output box is not covered by the accumulator box");
+    }
+    return 0;
+}
+
+// labels of `classes` classes by argmax in the engine's label dtype (fnn_set_label_rule checks the region rule's)
+const char *const U16_HINT = ": fnn_set_label_rule(..., FNN_LABEL_U16)";
+int check_u8_labels(fnn_engine *e, int classes, const char *hint) {
+    if (e->label_u16 || e->label_mode != FNN_LABELS_ARGMAX || classes <= 256) return 0;
+    return fail(e, FNN_E_INVALID, "%d classes do not fit uint8 labels%s", classes, hint);
+}
+
+// Reads back the inf flag of the launches on `st` (synchronising it) and fails like the reference when one was set
+int check_inf(fnn_engine *e, hipStream_t st, const char *msg = "Encountered inf in predicted array.") {
+    int flag = 0;
+    HIPCHK(e, hipMemcpyAsync(&flag, e->inf_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return flag ? fail(e, FNN_E_INF, "%s", msg) : 0;
+}
+
 int upload_box(fnn_engine *e, int64_t x_lo, int64_t x_hi, int64_t y_lo, int64_t y_hi, hipStream_t st);     // (below, next to stage_volume)
 
 inline int acc_hp(const fnn_arch_desc &a) { return (a.num_heads + 1 + 7) / 8 * 8; }
 
-// Runs the listed patches and accumulates into `acc`, which covers `box` of the padded volume
-// ([bx][by][bz][HP], channels-last, channel num_heads = weight sum).
-// `fresh`: `ids` is the volume's whole patch list in visiting order and `acc` holds nothing yet (it need not even be
-// zeroed): voxels no earlier patch has touched are then written without being read (HeadParams::fx).
-// keep_features: no head, no accumulation - patch ids[i] leaves its last activation in e->feat[i] (gather path).
+// What run_patches makes of its patches.  AccBox: the seg head accumulates them into `acc`, which covers `box` of the padded volume ([bx][by][bz][HP],
+// channels-last, channel num_heads = weight sum).  `fresh`: the patches are the volume's whole list in visiting order and
+// `acc` holds nothing yet (it need not even be zeroed): voxels no earlier patch has touched are then written without
+// being read (HeadParams::fx).
+struct AccBox { void *acc; Box box; int acc_fp32; bool fresh; };
+// FeatSlots (gather path): no head; every evaluation of patch ids[i] leaves the last layer's raw output and InstanceNorm
+// rows in slot slot0 + i, item f * n_slots + slot for evaluation f.  fssh: the same rows in fp16 (the engine's slots; a
+// caller's rows are converted by fnn_gather_box), or nullptr.
+struct FeatSlots { void *feat; float *fss; unsigned short *fssh; int64_t slot0, n_slots; };
+using Target = std::variant<AccBox, FeatSlots>;
+
+// Where the patch at origin `oo` lands in an accumulator box, weighted how (HeadParams, PatchAccParams)
+template <class Params> void place_patch(Params &p, const fnn_engine *e, const fnn_opts &o, const AccBox &t, const int *oo) {
+    const Box &box = t.box;
+    p.gauss = o.use_gaussian ? e->gauss : e->ones;
+    p.acc = t.acc; p.AX = box.hi[0] - box.lo[0]; p.Y = box.hi[1] - box.lo[1]; p.Z = box.hi[2] - box.lo[2];
+    p.HP = acc_hp(e->arch); p.acc_fp32 = t.acc_fp32;
+    p.ox = oo[0] - (int)box.lo[0]; p.oy = oo[1] - (int)box.lo[1]; p.oz = oo[2] - (int)box.lo[2];
+}
+
+// Arenas and streams for `want` batches in flight (2 .. MAXP); *np: how many there are.  The arenas take at most half of
+// the device's memory (a full-width teacher's is 29 GB at batch 32, the 160^3 ResEnc student's 45 GB) and never what is
+// not free: fewer batches in flight then, not a failed call.
+int add_pipes(fnn_engine *e, int want, int *np) {
+    int NP = std::clamp(want, 2, (int)fnn_engine::MAXP);
+    if (e->n_pipe < NP) {
+        size_t b[3], free_b = 0, total_b = 0;
+        const size_t arena = arena_bytes(e, b);
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && arena > 0) {
+            const long long by_total = (long long)(total_b / 2 / arena), by_free = (long long)(free_b * 8 / 10 / arena) + e->n_pipe;
+            const long long cap = std::max<long long>(2, std::min(by_total, by_free));
+            if (NP > cap) NP = (int)std::max<long long>(cap, e->n_pipe);
+        }
+    }
+    if (!e->ev_start) HIPCHK(e, hipEventCreateWithFlags(&e->ev_start, hipEventDisableTiming));
+    for (int k = e->n_pipe; k < NP; ++k) {
+        if (k > 0 && !e->arena[k].act) if (int rc = arena_alloc(e, e->arena[k])) return rc;
+        HIPCHK(e, hipStreamCreateWithFlags(&e->pipe[k], hipStreamNonBlocking));
+        HIPCHK(e, hipEventCreateWithFlags(&e->ev_head[k], hipEventDisableTiming));
+        HIPCHK(e, hipEventCreateWithFlags(&e->ev_done[k], hipEventDisableTiming));
+        e->n_pipe = k + 1;
+    }
+    *np = NP;
+    return 0;
+}
+
+// Runs the listed patches (their origins already on the device) in balanced batches and hands every evaluation
+// (mirroring) to the target.  Several batches in flight (see fnn_engine::pipe): batch i runs on arena and stream
+// i % NP, its heads wait for the previous batch's; otherwise arena 0 on the caller's stream.  A volume still arriving
+// from the host is waited for tile by tile under each batch (upload_box).
 int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const fnn_opts &o,
-                const std::vector<int64_t> &ids, const int *ids_origins_dev, const Box &box, void *acc, int acc_fp32,
-                hipStream_t st, bool fresh = false, bool keep_features = false, int64_t slot0 = 0, int64_t n_slots = 0,
-                void *feat_ext = nullptr, float *fss_ext = nullptr) {
+                const std::vector<int64_t> &ids, const int *ids_origins_dev, const Target &t, hipStream_t st) {
     const fnn_arch_desc &a = e->arch;
+    const AccBox *ab = std::get_if<AccBox>(&t);
+    const FeatSlots *fs = std::get_if<FeatSlots>(&t);
     const long long vdim[3] = {(long long)vp.padded[0], (long long)vp.padded[1], (long long)vp.padded[2]};
     int B = o.batch > 0 ? o.batch : e->max_batch;
     if (B > e->max_batch) B = e->max_batch;
     const auto combos = mirror_combos(o);
     const bool tta = !combos.empty();
     const size_t P = (size_t)a.patch[0] * a.patch[1] * a.patch[2];
-    if (tta && !keep_features) {
-        void *pbuf = e->patch_buf;
-        if (int rc = ensure(e, &pbuf, &e->patch_buf_bytes, (size_t)B * a.num_heads * P * sizeof(float))) return rc;
-        e->patch_buf = (float *)pbuf;
-    }
+    if (tta && ab)
+        if (int rc = ensure(e, &e->patch_buf, &e->patch_buf_bytes, (size_t)B * a.num_heads * P * sizeof(float))) return rc;
     const int64_t np = (int64_t)ids.size();
     if (np > B) {                                           // balanced batches: 75 patches run as 19+19+19+18, not 24+24+24+3
         const int64_t nbat = (np + B - 1) / B;
         B = (int)((np + nbat - 1) / nbat);
     }
-    for (int64_t i = 0; i < np && !keep_features; ++i) {
+    for (int64_t i = 0; i < np && ab; ++i) {
         const int *oo = &vp.origins[ids[i] * 3];
         for (int d = 0; d < 3; ++d)
-            if (oo[d] < box.lo[d] || oo[d] + a.patch[d] > box.hi[d])
+            if (oo[d] < ab->box.lo[d] || oo[d] + a.patch[d] > ab->box.hi[d])
                 return fail(e, FNN_E_INVALID, "patch %lld lies outside the accumulator box", (long long)ids[i]);
     }
-    const size_t featC = keep_features ? (size_t)e->layers[e->head_src].cout_pad : 0;
-    // ---- several batches in flight (see fnn_engine::pipe)
+    const size_t featC = fs ? (size_t)e->layers[e->head_src].cout_pad : 0;
     static const bool no_pipe = fnn_knob("FNN_NO_PIPELINE") != nullptr;                // A-B aid
-    const bool pipelined = !no_pipe && (!tta || keep_features) && !e->profiling && np > B;
-    f16 *const act0 = e->act; double *const stats0 = e->stats; float *const ss0 = e->ss;
     static const int want_pipes = fnn_knob("FNN_PIPES") ? atoi(fnn_knob("FNN_PIPES")) : 4;   // round 6: four beat three by 0.3-0.9 % on C1 / C2 / C4 / C5 (profiles/r06_pipes_sweep.txt); beyond four: nothing
-    int NP = want_pipes < 2 ? 2 : (want_pipes > fnn_engine::MAXP ? fnn_engine::MAXP : want_pipes);
+    const bool pipelined = !no_pipe && (!tta || fs) && !e->profiling && np > B;
+    int NP = 1;
     if (pipelined) {
-        if (e->n_pipe < NP) {
-            // the arenas of the batches in flight take at most half of the device's memory (a full-width teacher's is 29 GB at
-            // batch 32, the 160^3 ResEnc student's 45 GB) and never what is not free: fewer batches in flight then, not a failed call
-            const size_t arena = e->act_halves * e->max_batch * sizeof(f16) + e->stats_doubles * e->max_batch * sizeof(double) +
-                                 (e->ss_count * e->max_batch * 3 + 8) * sizeof(float);
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && arena > 0) {
-                const long long by_total = (long long)(total_b / 2 / arena), by_free = (long long)(free_b * 8 / 10 / arena) + e->n_pipe;
-                const long long cap = std::max<long long>(2, std::min(by_total, by_free));
-                if (NP > cap) NP = (int)std::max<long long>(cap, e->n_pipe);
-            }
-        }
-        if (e->n_pipe < NP) {
-            if (!e->ev_start) HIPCHK(e, hipEventCreateWithFlags(&e->ev_start, hipEventDisableTiming));
-            for (int k = e->n_pipe; k < NP; ++k) {
-                if (k > 0) {
-                    HIPCHK(e, hipMalloc((void **)&e->actp[k], e->act_halves * e->max_batch * sizeof(f16)));
-                    HIPCHK(e, hipMalloc((void **)&e->statsp[k], e->stats_doubles * e->max_batch * sizeof(double)));
-                    HIPCHK(e, hipMalloc((void **)&e->ssp[k], (e->ss_count * e->max_batch * 3 + 8) * sizeof(float)));   // fp32 rows + fp16 rows (ssh_rows)
-                }
-                HIPCHK(e, hipStreamCreateWithFlags(&e->pipe[k], hipStreamNonBlocking));
-                HIPCHK(e, hipEventCreateWithFlags(&e->ev_head[k], hipEventDisableTiming));
-                HIPCHK(e, hipEventCreateWithFlags(&e->ev_done[k], hipEventDisableTiming));
-                e->n_pipe = k + 1;
-            }
-        }
-        e->actp[0] = act0; e->statsp[0] = stats0; e->ssp[0] = ss0;
+        if (int rc = add_pipes(e, want_pipes, &NP)) return rc;
         HIPCHK(e, hipEventRecord(e->ev_start, st));
         for (int k = 0; k < NP; ++k) HIPCHK(e, hipStreamWaitEvent(e->pipe[k], e->ev_start, 0));
     }
+    const bool fresh = ab && ab->fresh;
     std::vector<int> uniq[3];                             // distinct patch positions per axis (fresh: overlap with the previous one)
     if (fresh) {
         for (int d = 0; d < 3; ++d) {
@@ -941,20 +1020,13 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
         const int ov = *(it - 1) + a.patch[d] - oo[d];
         return ov > 0 ? ov : 0;
     };
-    struct Restore {                                      // whatever happens, the engine ends on its first arena
-        fnn_engine *e; f16 *a; double *s; float *ss;
-        ~Restore() { e->act = a; e->stats = s; e->ss = ss; }
-    } restore{e, act0, stats0, ss0};
-    hipStream_t user_st = st;
     int64_t bi = 0;
     for (int64_t p0 = 0; p0 < np; p0 += B, ++bi) {
         const int nb = (int)((np - p0 < B) ? np - p0 : B);
         const int *org = ids_origins_dev + p0 * 3;
         const int k = (int)(bi % NP);
-        if (pipelined) {
-            st = e->pipe[k];
-            e->act = e->actp[k]; e->stats = e->statsp[k]; e->ss = e->ssp[k];
-        }
+        const Arena &A = e->arena[k];
+        hipStream_t bst = pipelined ? e->pipe[k] : st;
         if (e->up.active) {                                   // a volume still arriving from the host: the box this batch's patches read
             int64_t lo[2] = {INT64_MAX, INT64_MAX}, hi[2] = {0, 0};   // (un-padded volume: padded == shape along every axis here)
             for (int b = 0; b < nb; ++b)
@@ -962,58 +1034,47 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
                     const int64_t o0 = vp.origins[ids[p0 + b] * 3 + d];
                     lo[d] = std::min(lo[d], o0); hi[d] = std::max(hi[d], o0 + a.patch[d]);
                 }
-            if (int rc = upload_box(e, lo[0], hi[0], lo[1], hi[1], st)) return rc;
+            if (int rc = upload_box(e, lo[0], hi[0], lo[1], hi[1], bst)) return rc;
         }
         for (size_t ci = 0; ci <= (tta ? combos.size() : 0); ++ci) {
             int flip[3] = {0, 0, 0};
             if (ci > 0) for (int ax : combos[ci - 1]) flip[ax] = 1;
-            if (keep_features) {                              // [evaluation][slot]: the batch's items stay contiguous
-                const size_t item = (size_t)ci * n_slots + slot0 + p0;
-                if (int rc = forward_batch(e, fold, vol_dev, 0, vdim, org, nb, flip, st,
-                                           (f16 *)(feat_ext ? feat_ext : e->feat) + item * P * featC,
-                                           (fss_ext ? fss_ext : (float *)e->featss) + item * 2 * featC,
-                                           feat_ext ? nullptr : (unsigned short *)e->featssh + item * 2 * featC)) return rc;
+            if (fs) {                                         // [evaluation][slot]: the batch's items stay contiguous
+                const size_t item = (size_t)ci * fs->n_slots + fs->slot0 + p0;
+                if (int rc = forward_batch(e, fold, A, vol_dev, 0, vdim, org, nb, flip, bst, (f16 *)fs->feat + item * P * featC,
+                                           fs->fss + item * 2 * featC, fs->fssh ? fs->fssh + item * 2 * featC : nullptr)) return rc;
                 continue;
             }
-            if (int rc = forward_batch(e, fold, vol_dev, 0, vdim, org, nb, flip, st)) return rc;
-            if (pipelined && bi > 0) HIPCHK(e, hipStreamWaitEvent(st, e->ev_head[(bi - 1) % NP], 0));   // heads in patch order
+            if (int rc = forward_batch(e, fold, A, vol_dev, 0, vdim, org, nb, flip, bst)) return rc;
+            if (pipelined && bi > 0) HIPCHK(e, hipStreamWaitEvent(bst, e->ev_head[(bi - 1) % NP], 0));   // heads in patch order
             for (int b = 0; b < nb; ++b) {
-                HeadParams h = make_head(e, fold, b);
+                HeadParams h = make_head(e, A, fold, b);
                 const int *oo = &vp.origins[ids[p0 + b] * 3];
-                h.gauss = o.use_gaussian ? e->gauss : e->ones;
-                h.acc = acc; h.AX = box.hi[0] - box.lo[0]; h.Y = box.hi[1] - box.lo[1]; h.Z = box.hi[2] - box.lo[2];
-                h.HP = acc_hp(a);
-                h.ox = oo[0] - (int)box.lo[0]; h.oy = oo[1] - (int)box.lo[1]; h.oz = oo[2] - (int)box.lo[2];
+                place_patch(h, e, o, *ab, oo);
                 h.flip_d = flip[0]; h.flip_h = flip[1]; h.flip_w = flip[2];
-                h.acc_fp32 = acc_fp32;
                 h.fx = first_visit(oo, 0); h.fy = first_visit(oo, 1); h.fz = first_visit(oo, 2);
                 if (tta) { h.mode = ci == 0 ? 1 : 2; h.patch_buf = e->patch_buf + (size_t)b * a.num_heads * P; }
-                Scope sc(e, st, FAM_HEAD, e->head_flops);
-                if (launch_head(h, st) != 0) return fail(e, FNN_E_HIP, "seg head launch failed");
+                Scope sc(e, bst, FAM_HEAD, e->head_flops);
+                if (launch_head(h, bst) != 0) return fail(e, FNN_E_HIP, "seg head launch failed");
             }
-            if (pipelined) HIPCHK(e, hipEventRecord(e->ev_head[k], st));
+            if (pipelined) HIPCHK(e, hipEventRecord(e->ev_head[k], bst));
         }
-        if (tta && !keep_features) {
+        if (tta && ab) {
             for (int b = 0; b < nb; ++b) {
-                const int *oo = &vp.origins[ids[p0 + b] * 3];
                 PatchAccParams q{};
+                place_patch(q, e, o, *ab, &vp.origins[ids[p0 + b] * 3]);
                 q.patch_buf = e->patch_buf + (size_t)b * a.num_heads * P;
                 q.n_div = (int)combos.size() + 1;
                 q.PD = a.patch[0]; q.PH = a.patch[1]; q.PW = a.patch[2]; q.heads = a.num_heads;
-                q.gauss = o.use_gaussian ? e->gauss : e->ones;
-                q.acc = acc; q.AX = box.hi[0] - box.lo[0]; q.Y = box.hi[1] - box.lo[1]; q.Z = box.hi[2] - box.lo[2];
-                q.HP = acc_hp(a);
-                q.ox = oo[0] - (int)box.lo[0]; q.oy = oo[1] - (int)box.lo[1]; q.oz = oo[2] - (int)box.lo[2];
-                q.acc_fp32 = acc_fp32;
-                Scope sc(e, st, FAM_HEAD, 0);
-                if (launch_patch_acc(q, st) != 0) return fail(e, FNN_E_HIP, "patch accumulate launch failed");
+                Scope sc(e, bst, FAM_HEAD, 0);
+                if (launch_patch_acc(q, bst) != 0) return fail(e, FNN_E_HIP, "patch accumulate launch failed");
             }
         }
     }
     if (pipelined) {
         for (int k = 0; k < NP; ++k) {
             HIPCHK(e, hipEventRecord(e->ev_done[k], e->pipe[k]));
-            HIPCHK(e, hipStreamWaitEvent(user_st, e->ev_done[k], 0));
+            HIPCHK(e, hipStreamWaitEvent(st, e->ev_done[k], 0));
         }
     }
     return 0;
@@ -1025,19 +1086,29 @@ bool is_pinned_host_ptr(const void *p) {
     return a.type == hipMemoryTypeHost;
 }
 
-// host -> pinned staging with a few threads: one core's memcpy (~10 GB/s) is slower than the link
-void parallel_copy(float *dst, const float *src, size_t n) {
-    const size_t min_part = 1u << 20;                                          // floats
-    int parts = (int)std::min<size_t>(4, (n + min_part - 1) / min_part);
-    if (parts <= 1) { memcpy(dst, src, n * sizeof(float)); return; }
+// Host -> pinned staging: `rows` rows of `w` floats, `pitch` floats apart in the source, packed.  One core's memcpy (~10 GB/s)
+// is slower than the link: up to 4 threads share a contiguous run (pitch == w) in parts of >= 2^20 floats, else whole rows
+// in parts of ~2^18 floats or more.  A thread that cannot be started leaves its part and the rest to the calling thread.
+void stage_copy(float *dst, const float *src, size_t w, size_t pitch, size_t rows) {
+    const bool run = pitch == w;
+    const size_t n = run ? w * rows : rows;                   // what is shared out: floats, or rows
+    const int parts = (int)std::max<size_t>(1, std::min<size_t>(4, run ? (n + (1u << 20) - 1) >> 20 : w * rows >> 18));
+    auto part = [=](size_t lo, size_t hi) {
+        if (run) memcpy(dst + lo, src + lo, (hi - lo) * sizeof(float));
+        else for (size_t r = lo; r < hi; ++r) memcpy(dst + r * w, src + r * pitch, w * sizeof(float));
+    };
     std::thread th[3];
     const size_t per = (n + parts - 1) / parts;
+    bool spawn = true;
     for (int t = 1; t < parts; ++t) {
-        const size_t lo = per * t, hi = std::min(n, lo + per);
-        th[t - 1] = std::thread([=] { if (hi > lo) memcpy(dst + lo, src + lo, (hi - lo) * sizeof(float)); });
+        const size_t lo = std::min(n, per * t), hi = std::min(n, per * (t + 1));
+        if (spawn) {
+            try { th[t - 1] = std::thread(part, lo, hi); continue; } catch (...) { spawn = false; }
+        }
+        part(lo, hi);
     }
-    memcpy(dst, src, std::min(n, per) * sizeof(float));
-    for (int t = 1; t < parts; ++t) th[t - 1].join();
+    part(0, std::min(n, per));
+    for (std::thread &x : th) if (x.joinable()) x.join();
 }
 
 // Issues the upload of every tile of [x_lo, x_hi) x [y_lo, y_hi) (planes x rows, whole z extent) that has not left yet, then makes `st` wait
@@ -1069,20 +1140,9 @@ int upload_box(fnn_engine *e, int64_t x_lo, int64_t x_hi, int64_t y_lo, int64_t 
                 u.next_stage = (k + 1) % fnn_engine::Upload::RING;
                 if (u.stage_used[k]) HIPCHK(e, hipEventSynchronize(u.stage_free[k]));          // its previous tile has left
                 const size_t tile = width / sizeof(float) * height;                            // floats per channel, packed
-                for (int c = 0; c < u.C; ++c) {
-                    const float *src0 = u.host + (((size_t)c * u.X + x0) * u.Y + y0) * row;
-                    float *dst0 = u.stage[k] + (size_t)c * tile;
-                    if (whole_rows) { parallel_copy(dst0, src0, tile); continue; }               // one contiguous run
-                    // rows y0 .. y1 of every plane of the tile: the planes shared out over a few host threads
-                    const size_t wf = width / sizeof(float), pf = pitch / sizeof(float);
-                    const int parts = (int)std::min<size_t>(4, std::max<size_t>(1, tile / (1u << 18)));
-                    auto planes = [=](size_t h0, size_t h1) { for (size_t hx = h0; hx < h1; ++hx) memcpy(dst0 + hx * wf, src0 + hx * pf, wf * sizeof(float)); };
-                    std::thread th[3];
-                    const size_t per = (height + parts - 1) / parts;
-                    for (int t = 1; t < parts; ++t) th[t - 1] = std::thread(planes, std::min(height, per * t), std::min(height, per * (t + 1)));
-                    planes(0, std::min(height, per));
-                    for (int t = 1; t < parts; ++t) th[t - 1].join();
-                }
+                for (int c = 0; c < u.C; ++c)
+                    stage_copy(u.stage[k] + (size_t)c * tile, u.host + (((size_t)c * u.X + x0) * u.Y + y0) * row, width / sizeof(float),
+                               pitch / sizeof(float), height);
                 for (int c = 0; c < u.C; ++c) {
                     const size_t off = (((size_t)c * u.X + x0) * u.Y + y0) * row;
                     HIPCHK(e, hipMemcpy2DAsync(u.dev + off, pitch, u.stage[k] + (size_t)c * tile, width, width, height, hipMemcpyHostToDevice, u.st));
@@ -1112,11 +1172,9 @@ int stage_volume(fnn_engine *e, const float *vol, const int64_t shape[4], const 
     const float *src = vol;
     const bool need_pad = vp.padded[0] != shape[1] || vp.padded[1] != shape[2] || vp.padded[2] != shape[3];
     fnn_engine::Upload &u = e->up;
-    u.active = false;
+    u.active = false; u.n_issued = 0;
     if (!is_device_ptr(vol)) {
-        void *t = e->vol_tmp;
-        if (int rc = ensure(e, &t, &e->vol_tmp_bytes, nin * sizeof(float))) return rc;
-        e->vol_tmp = (float *)t;
+        if (int rc = ensure(e, &e->vol_tmp, &e->vol_tmp_bytes, nin * sizeof(float))) return rc;
         src = e->vol_tmp;
         u.host = vol; u.dev = e->vol_tmp; u.C = (int)shape[0]; u.X = shape[1]; u.Y = shape[2]; u.Z = shape[3];
         u.pinned_src = is_pinned_host_ptr(vol);
@@ -1127,7 +1185,7 @@ int stage_volume(fnn_engine *e, const float *vol, const int64_t shape[4], const 
         u.slab_x = std::max<int64_t>(1, (int64_t)(slab_bytes / std::max<size_t>(1, rows_bytes)));
         u.nxs = (u.X + u.slab_x - 1) / u.slab_x; u.nyb = (u.Y + u.slab_y - 1) / u.slab_y;
         u.issued.assign((size_t)(u.nxs * u.nyb), 0);
-        u.n_issued = 0; u.ev_next = 0; u.last = nullptr;
+        u.ev_next = 0; u.last = nullptr;
         if (!u.st) HIPCHK(e, hipStreamCreateWithFlags(&u.st, hipStreamNonBlocking));
         if (!u.go) HIPCHK(e, hipEventCreateWithFlags(&u.go, hipEventDisableTiming));
         if (!u.pinned_src) {
@@ -1153,9 +1211,7 @@ int stage_volume(fnn_engine *e, const float *vol, const int64_t shape[4], const 
     }
     if (need_pad) {
         const size_t npad = (size_t)shape[0] * vp.padded[0] * vp.padded[1] * vp.padded[2];
-        void *t = e->vol_pad;
-        if (int rc = ensure(e, &t, &e->vol_pad_bytes, npad * sizeof(float))) return rc;
-        e->vol_pad = (float *)t;
+        if (int rc = ensure(e, &e->vol_pad, &e->vol_pad_bytes, npad * sizeof(float))) return rc;
         const long long s[3] = {(long long)shape[1], (long long)shape[2], (long long)shape[3]};
         const long long d[3] = {(long long)vp.padded[0], (long long)vp.padded[1], (long long)vp.padded[2]};
         const long long lo[3] = {(long long)vp.lo[0], (long long)vp.lo[1], (long long)vp.lo[2]};
@@ -1165,6 +1221,17 @@ int stage_volume(fnn_engine *e, const float *vol, const int64_t shape[4], const 
     *vol_dev = src;
     return 0;
 }
+
+// Ends a call's host-volume upload (stage_volume).  An error return after tiles have left the caller's pinned memory first
+// drains the copy stream, as the caller may free that memory once the call has failed; on success the caller's stream waits.
+struct UploadScope {
+    fnn_engine *e;
+    bool ok = false;
+    ~UploadScope() {
+        if (!ok && e->up.pinned_src && e->up.n_issued > 0) (void)hipStreamSynchronize(e->up.st);
+        e->up.active = false;
+    }
+};
 
 // Origins of the listed patches -> device (the stem conv reads them).
 int upload_origins(fnn_engine *e, const VolPlan &vp, const std::vector<int64_t> &ids, hipStream_t st) {
@@ -1204,12 +1271,10 @@ int accumulate_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const
     // 17 GB zero fill (and an eighth of the accumulator reads) is skipped.  Mirroring accumulates through the patch
     // buffer and the generic head kernel: those keep the zero fill.
     static const bool no_fv = fnn_knob("FNN_NO_FIRST_VISIT") != nullptr;            // A-B aid
-    const bool fresh = !no_fv && o.n_mirror_axes == 0 && launch_head_first_visit_ok(make_head(e, fold, 0));
+    const bool fresh = !no_fv && o.n_mirror_axes == 0 && launch_head_first_visit_ok(make_head(e, e->arena[0], fold, 0));
     if (!fresh) HIPCHK(e, hipMemsetAsync(e->acc, 0, bytes, st));
     for (int d = 0; d < 3; ++d) { box.lo[d] = 0; box.hi[d] = vp.padded[d]; }
-    std::vector<int64_t> ids(vp.n_patches);
-    for (int64_t i = 0; i < vp.n_patches; ++i) ids[i] = i;
-    return run_patches(e, fold, vol_dev, vp, o, ids, e->origins, box, e->acc, acc_fp32, st, fresh);
+    return run_patches(e, fold, vol_dev, vp, o, id_range(0, vp.n_patches), e->origins, AccBox{e->acc, box, acc_fp32, fresh}, st);
 }
 
 // The gather kernel's integer tables for a volume: tile starts (+ window bases of axes with more than 64 positions,
@@ -1230,23 +1295,44 @@ void gather_set_tables(GatherParams &g, const int *dev, const int off[3]) {
     g.windowed = 1;
 }
 
+// The gather kernel's parameters that follow from the engine, the fold, the volume's plan and shape, and the options.
+// Its callers add the feature buffers with their slots or ring, the tables, the output box and what is written.
+GatherParams gather_params(const fnn_engine *e, int fold, const VolPlan &vp, const int64_t shape[4], const fnn_opts &o) {
+    const fnn_arch_desc &a = e->arch;
+    const Layer &H = e->layers[e->head_src];
+    const FoldWeights &fw = e->folds[fold];
+    GatherParams g{};
+    g.heads = a.num_heads; g.hblocks = e->hblocks; g.C = H.cout_pad; g.slope = H.act ? a.slope : 1.f;
+    g.PD = a.patch[0]; g.PH = a.patch[1]; g.PW = a.patch[2];
+    g.nx = (int)vp.steps[0].size(); g.ny = (int)vp.steps[1].size(); g.nz = (int)vp.steps[2].size();
+    { int off[3]; g.windowed = gather_tables(a, vp, nullptr, off) ? 1 : 0; }
+    const auto combos = mirror_combos(o);
+    g.n_eval = 1 + (int)combos.size();
+    for (size_t ci = 0; ci < combos.size() && ci + 1 < 8; ++ci)    // (flipmask[0] = 0: the plain evaluation)
+        for (int ax : combos[ci]) g.flipmask[ci + 1] |= 1 << ax;
+    g.wpk = fw.wpk + e->head_w_off; g.bias = fw.fparam + e->head_bias_off;
+    g.n_pass = e->n_gpass; g.pass_wpk = fw.wpk + e->gpass_w_off; g.pass_bias = fw.fparam + e->gpass_bias_off;
+    g.gauss = o.use_gaussian ? e->gauss : e->ones;
+    g.lo_x = (int)vp.lo[0]; g.lo_y = (int)vp.lo[1]; g.lo_z = (int)vp.lo[2];
+    g.OX = shape[1]; g.OY = shape[2]; g.OZ = shape[3];
+    g.acc_mode = o.accum; g.inf_flag = e->inf_flag;
+    g.label_u16 = e->label_u16; g.order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
+    return g;
+}
+
 // Plan of the gather path (gather.hip) for a volume: how many x layers of patches are kept at a time.
 struct GatherPlan { bool ok = false; int n_eval = 1, ring = 0, cover = 1; size_t layer_items = 0, feat_bytes = 0; const char *why = ""; };
 
 // No gather when the head does not fit the kernel's registers or when not even the layers that cover one output slab fit
 // next to what is already allocated; otherwise the whole volume's patches when they fit (one launch at the end), else
 // a ring of `cover` layers with one launch per output slab.
-GatherPlan gather_plan(fnn_engine *e, const VolPlan &vp, const fnn_opts &o, size_t pending_bytes = 0) {
+GatherPlan gather_plan(fnn_engine *e, int fold, const VolPlan &vp, const int64_t shape[4], const fnn_opts &o, size_t pending_bytes) {
     GatherPlan gp;
     gp.why = "FNN_NO_GATHER is set or the output is not fp16";
     if (!e->gather_enabled || o.out_dtype != FNN_OUT_F16) return gp;
     const Layer &H = e->layers[e->head_src];
-    GatherParams g{};
-    g.heads = e->arch.num_heads; g.C = H.cout_pad; g.PD = e->arch.patch[0]; g.PH = e->arch.patch[1]; g.PW = e->arch.patch[2];
-    g.nx = (int)vp.steps[0].size(); g.ny = (int)vp.steps[1].size(); g.nz = (int)vp.steps[2].size();
-    gp.n_eval = 1 + (int)mirror_combos(o).size();
-    g.n_eval = gp.n_eval; g.n_pass = e->n_gpass;
-    { int off[3]; g.windowed = gather_tables(e->arch, vp, nullptr, off) ? 1 : 0; }
+    const GatherParams g = gather_params(e, fold, vp, shape, o);
+    gp.n_eval = g.n_eval;
     gp.why = "the network's head does not fit the gather kernel (a normalised last layer of <= 32 channels, <= 8 evaluations per patch, <= 64 tiles of one axis over a voxel)";
     if (!H.has_norm || e->head_ksteps != 1 || !gather_ok(g)) return gp;
     gp.why = "not enough free HBM for the patch activations that cover one output slab";
@@ -1276,9 +1362,7 @@ GatherPlan gather_plan(fnn_engine *e, const VolPlan &vp, const fnn_opts &o, size
 }
 
 int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const int64_t shape[4],
-                        const fnn_opts &o, const GatherPlan &gp, int mode, void *out, void *labels, const int *lab_order,
-                        hipStream_t st) {
-    const fnn_arch_desc &a = e->arch;
+                        const fnn_opts &o, const GatherPlan &gp, int mode, void *out, void *labels, hipStream_t st) {
     const Layer &H = e->layers[e->head_src];
     if (gp.feat_bytes > e->feat_bytes && e->acc) { (void)hipFree(e->acc); e->acc = nullptr; e->acc_bytes = 0; }
     if (int rc = ensure(e, &e->feat, &e->feat_bytes, gp.feat_bytes)) return rc;
@@ -1287,55 +1371,32 @@ int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const Vol
     if (int rc = ensure(e, &e->featssh, &e->featssh_bytes, (size_t)n_slots * gp.n_eval * 2 * H.cout_pad * sizeof(f16))) return rc;
     std::vector<int> steps;
     int win_off[3];
-    if (!gather_tables(a, vp, &steps, win_off)) return fail(e, FNN_E_UNSUPPORTED, "more than 64 tiles of one axis over a voxel");
+    if (!gather_tables(e->arch, vp, &steps, win_off)) return fail(e, FNN_E_UNSUPPORTED, "more than 64 tiles of one axis over a voxel");
     if (int rc = upload_ints(e, steps.data(), steps.size(), &e->steps_dev, &e->steps_cap, &e->steps_host, &e->steps_host_cap, &e->steps_ev, st)) return rc;
-    Box box;
-    for (int d = 0; d < 3; ++d) { box.lo[d] = 0; box.hi[d] = vp.padded[d]; }
-    const FoldWeights &fw = e->folds[fold];
-    GatherParams g{};
-    g.feat = (const f16 *)e->feat; g.fss = (const float *)e->featss; g.fssh = (const unsigned short *)e->featssh; g.C = H.cout_pad;
-    g.n_eval = gp.n_eval; g.n_slots = (int)n_slots; g.ring = gp.ring;
-    {
-        const auto combos = mirror_combos(o);
-        g.flipmask[0] = 0;
-        for (size_t ci = 0; ci < combos.size() && ci + 1 < 8; ++ci) {
-            int m = 0;
-            for (int ax : combos[ci]) m |= 1 << ax;
-            g.flipmask[ci + 1] = m;
-        }
-    }
-    g.slope = H.act ? a.slope : 1.f;
+    GatherParams g = gather_params(e, fold, vp, shape, o);
+    g.feat = (const f16 *)e->feat; g.fss = (const float *)e->featss; g.fssh = (const unsigned short *)e->featssh;
+    g.n_slots = (int)n_slots; g.ring = gp.ring;
     gather_set_tables(g, e->steps_dev, win_off);
-    g.nx = (int)vp.steps[0].size(); g.ny = (int)vp.steps[1].size(); g.nz = (int)vp.steps[2].size();
-    g.PD = a.patch[0]; g.PH = a.patch[1]; g.PW = a.patch[2];
-    g.wpk = fw.wpk + e->head_w_off; g.bias = fw.fparam + e->head_bias_off; g.heads = a.num_heads; g.hblocks = e->hblocks;
-    g.n_pass = e->n_gpass; g.pass_wpk = fw.wpk + e->gpass_w_off; g.pass_bias = fw.fparam + e->gpass_bias_off;
-    g.gauss = o.use_gaussian ? e->gauss : e->ones;
-    g.lo_x = (int)vp.lo[0]; g.lo_y = (int)vp.lo[1]; g.lo_z = (int)vp.lo[2];
-    g.OX = shape[1]; g.OY = shape[2]; g.OZ = shape[3];
-    g.y_lo = 0; g.y_hi = (int)shape[2]; g.z_lo = 0; g.z_hi = (int)shape[3]; g.slot_tab = nullptr;
-    g.acc_mode = o.accum; g.out_fp32 = 0;
+    g.y_lo = 0; g.y_hi = (int)shape[2]; g.z_lo = 0; g.z_hi = (int)shape[3];
     g.out_vec = out && shape[3] % 8 == 0 && ((size_t)out % 16) == 0;
-    g.mode = mode; g.out = out; g.labels = labels; g.label_u16 = e->label_u16; g.order = lab_order; g.inf_flag = e->inf_flag;
+    g.mode = mode; g.out = out; g.labels = labels;
     auto launch = [&](int x_lo, int x_hi, double n_patches) {
         g.x_lo = x_lo; g.x_hi = x_hi;
         Scope sc(e, st, FAM_HEAD, e->head_flops * n_patches * gp.n_eval);
         return launch_gather(g, st) == 0 ? 0 : fail(e, FNN_E_HIP, "gather launch failed");
     };
+    const FeatSlots slots{e->feat, (float *)e->featss, (unsigned short *)e->featssh, 0, n_slots};
     if (gp.ring == g.nx) {                                     // every patch of the volume is kept: one pass at the end
-        std::vector<int64_t> ids(vp.n_patches);
-        for (int64_t i = 0; i < vp.n_patches; ++i) ids[i] = i;
-        if (int rc = run_patches(e, fold, vol_dev, vp, o, ids, e->origins, box, nullptr, 0, st, false, true, 0, n_slots)) return rc;
+        if (int rc = run_patches(e, fold, vol_dev, vp, o, id_range(0, vp.n_patches), e->origins, slots, st)) return rc;
         return launch(0, (int)shape[1], (double)vp.n_patches);
     }
     // ring: after x layer ix the output slab up to the next layer's first voxel is complete (padded coordinates
     // [steps[ix], steps[ix + 1]); the un-padded range is clamped); the next layer then overwrites the oldest slot
     const int64_t L = (int64_t)gp.layer_items;
     for (int ix = 0; ix < g.nx; ++ix) {
-        std::vector<int64_t> ids(L);
-        for (int64_t i = 0; i < L; ++i) ids[i] = ix * L + i;
-        if (int rc = run_patches(e, fold, vol_dev, vp, o, ids, e->origins + ix * L * 3, box, nullptr, 0, st, false, true,
-                                 (ix % gp.ring) * L, n_slots)) return rc;
+        FeatSlots layer = slots;
+        layer.slot0 = (ix % gp.ring) * L;
+        if (int rc = run_patches(e, fold, vol_dev, vp, o, id_range(ix * L, L), e->origins + ix * L * 3, layer, st)) return rc;
         const int64_t p_lo = ix == 0 ? 0 : vp.steps[0][ix], p_hi = ix + 1 < g.nx ? vp.steps[0][ix + 1] : vp.padded[0];
         const int x_lo = (int)std::max<int64_t>(0, p_lo - vp.lo[0]), x_hi = (int)std::min<int64_t>(shape[1], p_hi - vp.lo[0]);
         if (x_hi > x_lo) if (int rc = launch(x_lo, x_hi, (double)L)) return rc;
@@ -1353,15 +1414,11 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)o->stream;
     VolPlan vp;
-    if (plan_volume(a, shape + 1, o->tile_step_size, vp) != 0) return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
+    if (int rc = plan_volume(e, shape, *o, vp)) return rc;
     const float *vol_dev = nullptr;
+    UploadScope upload{e};
     if (int rc = stage_volume(e, vol, shape, vp, st, &vol_dev, true)) return rc;
-    struct UploadDone { fnn_engine *e; ~UploadDone() { e->up.active = false; } } upload_done{e};
-    {
-        std::vector<int64_t> all(vp.n_patches);
-        for (int64_t i = 0; i < vp.n_patches; ++i) all[i] = i;
-        if (int rc = upload_origins(e, vp, all, st)) return rc;
-    }
+    if (int rc = upload_origins(e, vp, id_range(0, vp.n_patches), st)) return rc;
     const size_t nvox_out = (size_t)shape[1] * shape[2] * shape[3];
     const size_t nout = (size_t)a.num_heads * nvox_out;
     const size_t osz = o->out_dtype == FNN_OUT_F32 ? 4 : 2;
@@ -1378,7 +1435,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
         if (!maybe_direct && !out_on_dev && nout * osz > e->out_tmp_bytes) pending += nout * osz - e->out_tmp_bytes;
         if (labels && !lab_on_dev) pending += lab_bytes;
     }
-    const GatherPlan gp = gather_plan(e, vp, *o, pending);
+    const GatherPlan gp = gather_plan(e, fold0, vp, shape, *o, pending);
     if (!gp.ok && o->accum == FNN_ACC_FP16_AUTOCAST)
         return fail(e, FNN_E_UNSUPPORTED, "FNN_ACC_FP16_AUTOCAST needs the gather path: %s", gp.why);
     // argmax straight from the accumulators / the gather kernel's registers; with more than 63 classes the gather kernel
@@ -1394,8 +1451,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     void *lab_dev = labels;
     void *lab_tmp = nullptr;
     const int *lab_order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
-    if (labels && !e->label_u16 && e->label_mode == FNN_LABELS_ARGMAX && a.num_heads > 256)
-        return fail(e, FNN_E_INVALID, "%d classes do not fit uint8 labels: fnn_set_label_rule(..., FNN_LABEL_U16)", a.num_heads);
+    if (labels) if (int rc = check_u8_labels(e, a.num_heads, U16_HINT)) return rc;
     if (labels && !lab_on_dev) { HIPCHK(e, hipMalloc(&lab_tmp, lab_bytes)); lab_dev = lab_tmp; }
     HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
     e->ev_used = 0; e->klog.clear();
@@ -1405,7 +1461,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     for (int f = 0; f < n_folds && rc == 0; ++f) {
         if (gp.ok) {
             rc = gather_whole_volume(e, fold0 + f, vol_dev, vp, shape, *o, gp, f > 0 ? 1 : 0, labels_direct ? nullptr : out_dev,
-                                     labels_direct ? lab_dev : nullptr, lab_order, st);
+                                     labels_direct ? lab_dev : nullptr, st);
             continue;
         }
         Box box;
@@ -1422,21 +1478,65 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     if (rc == 0 && labels && !labels_direct)
         if (launch_argmax(out_dev, o->out_dtype == FNN_OUT_F32, a.num_heads, (long long)nvox_out, lab_dev, e->label_u16, lab_order, st) != 0)
             rc = fail(e, FNN_E_HIP, "argmax launch failed");
-    int flag = 0;
     if (rc == 0) {
-        hipError_t r1 = hipMemcpyAsync(&flag, e->inf_flag, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (r1 == hipSuccess && want_logits && !out_on_dev) r1 = hipMemcpyAsync(out, out_dev, nout * osz, hipMemcpyDeviceToHost, st);
+        hipError_t r1 = hipSuccess;
+        if (want_logits && !out_on_dev) r1 = hipMemcpyAsync(out, out_dev, nout * osz, hipMemcpyDeviceToHost, st);
         if (r1 == hipSuccess && labels && !lab_on_dev) r1 = hipMemcpyAsync(labels, lab_dev, lab_bytes, hipMemcpyDeviceToHost, st);
-        if (r1 == hipSuccess) r1 = hipStreamSynchronize(st);
         if (r1 != hipSuccess) rc = fail(e, FNN_E_HIP, "copy back failed: %s", hipGetErrorString(r1));
     }
+    if (rc == 0)
+        rc = check_inf(e, st, "Encountered inf in predicted array. Aborting... If this problem persists, reduce "
+                              "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32");
     if (lab_tmp) (void)hipFree(lab_tmp);
-    if (rc) return rc;
-    if (e->profiling) collect_profile(e, vp.n_patches * n_folds);
-    if (flag)
-        return fail(e, FNN_E_INF, "Encountered inf in predicted array. Aborting... If this problem persists, reduce "
-                                  "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32");
+    if (e->profiling && (rc == 0 || rc == FNN_E_INF)) collect_profile(e, vp.n_patches * n_folds);
+    upload.ok = rc == 0;
+    return rc;
+}
+
+// The patch entry points' common part (fnn_accumulate_patches, fnn_patch_features): the caller's patches of the volume
+// -> the target
+int run_listed_patches(fnn_engine *e, int fold, const float *vol, const int64_t shape[4], const fnn_opts &o, const VolPlan &vp,
+                       const int64_t *patch_ids, int64_t n_ids, const Target &t) {
+    const std::vector<int64_t> ids(patch_ids, patch_ids + n_ids);
+    for (int64_t id : ids) if (id < 0 || id >= vp.n_patches) return fail(e, FNN_E_INVALID, "patch id out of range");
+    if (ids.empty()) return 0;
+    hipStream_t st = (hipStream_t)o.stream;
+    const float *vol_dev = nullptr;
+    UploadScope upload{e};
+    if (int rc = stage_volume(e, vol, shape, vp, st, &vol_dev)) return rc;
+    if (int rc = upload_origins(e, vp, ids, st)) return rc;
+    e->ev_used = 0; e->klog.clear();
+    if (int rc = run_patches(e, fold, vol_dev, vp, o, ids, e->origins, t, st)) return rc;
+    if (e->profiling) { HIPCHK(e, hipStreamSynchronize(st)); collect_profile(e, n_ids); }
+    upload.ok = true;
     return 0;
+}
+
+// fnn_normalize_box (out) and fnn_labels_box (labels): an output box from an accumulator box
+int finalize_box(fnn_engine *e, const char *who, const void *acc, const int64_t shape[4], const fnn_opts *opts,
+                 const int64_t box_lo[3], const int64_t box_hi[3], const int64_t out_lo[3], const int64_t out_hi[3],
+                 void *out, void *labels) {
+    if (!e || !opts) return FNN_E_INVALID;
+    if (int rc = no_autocast(e, opts, who)) return rc;
+    void *dst = out ? out : labels;
+    if (!acc || !dst || !box_lo || !box_hi || !out_lo || !out_hi) return fail(e, FNN_E_INVALID, "NULL argument");
+    if (!is_device_ptr(acc) || !is_device_ptr(dst)) return fail(e, FNN_E_INVALID, "%s needs device pointers", who);
+    if (labels && acc_hp(e->arch) > 256)
+        return fail(e, FNN_E_UNSUPPORTED, "fnn_labels_box serves up to 254 classes (%d here): take the logits (fnn_normalize_box) and fnn_argmax_labels", e->arch.num_heads);
+    if (labels) if (int rc = check_u8_labels(e, e->arch.num_heads, U16_HINT)) return rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)opts->stream;
+    VolPlan vp;
+    if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
+    Box box;
+    for (int d = 0; d < 3; ++d) { box.lo[d] = box_lo[d]; box.hi[d] = box_hi[d]; }
+    if (int rc = check_out_box(e, vp, shape, out_lo, out_hi, &box)) return rc;
+    HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
+    const FinalizeParams f = make_finalize(e, acc, box, out_lo, out_hi, vp, shape, *opts, opts->accum == FNN_ACC_FP32, 0, out);
+    const int *order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
+    if (out && launch_finalize(f, st) != 0) return fail(e, FNN_E_HIP, "finalize launch failed");
+    if (labels && launch_labels_from_acc(f, labels, e->label_u16, order, st) != 0) return fail(e, FNN_E_HIP, "labels launch failed");
+    return check_inf(e, st);
 }
 
 }  // namespace
@@ -1489,9 +1589,7 @@ int fnn_create(const fnn_arch_desc *arch, int device, int max_batch, fnn_engine 
     };
     hipError_t r;
     if ((r = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", r);
-    if ((r = hipMalloc((void **)&e->act, e->act_halves * max_batch * sizeof(f16))) != hipSuccess) return bail("hipMalloc(activations)", r);
-    if ((r = hipMalloc((void **)&e->stats, e->stats_doubles * max_batch * sizeof(double))) != hipSuccess) return bail("hipMalloc(stats)", r);
-    if ((r = hipMalloc((void **)&e->ss, (e->ss_count * max_batch * 3 + 8) * sizeof(float))) != hipSuccess) return bail("hipMalloc(scale/shift)", r);
+    if (int rc = arena_alloc(e, e->arena[0])) { fnn_destroy(e); return rc; }
     if ((r = hipMalloc((void **)&e->inf_flag, sizeof(int))) != hipSuccess) return bail("hipMalloc(flag)", r);
     {
         const size_t P = (size_t)arch->patch[0] * arch->patch[1] * arch->patch[2];
@@ -1511,7 +1609,7 @@ void fnn_destroy(fnn_engine *e) {
         if (e->pipe[k]) (void)hipStreamDestroy(e->pipe[k]);
         if (e->ev_head[k]) (void)hipEventDestroy(e->ev_head[k]);
         if (e->ev_done[k]) (void)hipEventDestroy(e->ev_done[k]);
-        if (k > 0) { (void)hipFree(e->actp[k]); (void)hipFree(e->statsp[k]); (void)hipFree(e->ssp[k]); }
+        arena_free(e->arena[k]);
     }
     if (e->ev_start) (void)hipEventDestroy(e->ev_start);
     for (hipEvent_t ev : e->up.landed) (void)hipEventDestroy(ev);
@@ -1525,7 +1623,7 @@ void fnn_destroy(fnn_engine *e) {
     if (e->origins_ev) (void)hipEventDestroy(e->origins_ev);
     if (e->steps_host) (void)hipHostFree(e->steps_host);
     if (e->origins_host) (void)hipHostFree(e->origins_host);
-    void *ptrs[] = {e->feat, e->featss, e->featssh, e->steps_dev, e->ones, e->label_order, e->act, e->stats, e->ss, e->gauss, e->inf_flag, e->origins, e->acc, e->vol_tmp, e->vol_pad, e->out_tmp, e->patch_buf};
+    void *ptrs[] = {e->feat, e->featss, e->featssh, e->steps_dev, e->ones, e->label_order, e->gauss, e->inf_flag, e->origins, e->acc, e->vol_tmp, e->vol_pad, e->out_tmp, e->patch_buf};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &ev : e->evs) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     delete e;
@@ -1622,85 +1720,26 @@ int fnn_accumulate_patches(fnn_engine *e, int fold, const float *vol, const int6
     if (!vol || !acc || !box_lo || !box_hi || (n_ids > 0 && !patch_ids)) return fail(e, FNN_E_INVALID, "NULL argument");
     if (!is_device_ptr(acc)) return fail(e, FNN_E_INVALID, "accumulators must be device memory");
     HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)opts->stream;
     VolPlan vp;
-    if (plan_volume(e->arch, shape + 1, opts->tile_step_size, vp) != 0) return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
+    if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
     Box box;
     for (int d = 0; d < 3; ++d) {
         box.lo[d] = box_lo[d]; box.hi[d] = box_hi[d];
         if (box.lo[d] < 0 || box.hi[d] > vp.padded[d] || box.lo[d] >= box.hi[d]) return fail(e, FNN_E_INVALID, "box out of bounds");
     }
-    std::vector<int64_t> ids(patch_ids, patch_ids + n_ids);
-    for (int64_t id : ids) if (id < 0 || id >= vp.n_patches) return fail(e, FNN_E_INVALID, "patch id out of range");
-    if (ids.empty()) return 0;
-    const float *vol_dev = nullptr;
-    if (int rc = stage_volume(e, vol, shape, vp, st, &vol_dev)) return rc;
-    if (int rc = upload_origins(e, vp, ids, st)) return rc;
-    e->ev_used = 0; e->klog.clear();
-    if (int rc = run_patches(e, fold, vol_dev, vp, *opts, ids, e->origins, box, acc, opts->accum == FNN_ACC_FP32, st)) return rc;
-    if (e->profiling) { HIPCHK(e, hipStreamSynchronize(st)); collect_profile(e, n_ids); }
-    return 0;
+    return run_listed_patches(e, fold, vol, shape, *opts, vp, patch_ids, n_ids, AccBox{acc, box, opts->accum == FNN_ACC_FP32, false});
 }
 
 int fnn_normalize_box(fnn_engine *e, const void *acc, const int64_t shape[4], const fnn_opts *opts,
                       const int64_t box_lo[3], const int64_t box_hi[3], const int64_t out_lo[3], const int64_t out_hi[3],
                       void *out) {
-    if (!e || !opts) return FNN_E_INVALID;
-    if (int rc = no_autocast(e, opts, "fnn_normalize_box")) return rc;
-    if (!acc || !out || !box_lo || !box_hi || !out_lo || !out_hi) return fail(e, FNN_E_INVALID, "NULL argument");
-    if (!is_device_ptr(acc) || !is_device_ptr(out)) return fail(e, FNN_E_INVALID, "fnn_normalize_box needs device pointers");
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)opts->stream;
-    VolPlan vp;
-    if (plan_volume(e->arch, shape + 1, opts->tile_step_size, vp) != 0) return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
-    Box box;
-    for (int d = 0; d < 3; ++d) {
-        box.lo[d] = box_lo[d]; box.hi[d] = box_hi[d];
-        if (out_lo[d] < 0 || out_hi[d] > shape[1 + d] || out_lo[d] >= out_hi[d]) return fail(e, FNN_E_INVALID, "output box out of bounds");
-        if (out_lo[d] + vp.lo[d] < box.lo[d] || out_hi[d] + vp.lo[d] > box.hi[d])
-            return fail(e, FNN_E_INVALID, "output box is not covered by the accumulator box");
-    }
-    HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
-    FinalizeParams f = make_finalize(e, acc, box, out_lo, out_hi, vp, shape, *opts, opts->accum == FNN_ACC_FP32, 0, out);
-    if (launch_finalize(f, st) != 0) return fail(e, FNN_E_HIP, "finalize launch failed");
-    int flag = 0;
-    HIPCHK(e, hipMemcpyAsync(&flag, e->inf_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (flag) return fail(e, FNN_E_INF, "Encountered inf in predicted array.");
-    return 0;
+    return finalize_box(e, "fnn_normalize_box", acc, shape, opts, box_lo, box_hi, out_lo, out_hi, out, nullptr);
 }
 
 int fnn_labels_box(fnn_engine *e, const void *acc, const int64_t shape[4], const fnn_opts *opts,
                    const int64_t box_lo[3], const int64_t box_hi[3], const int64_t out_lo[3], const int64_t out_hi[3],
                    void *labels) {
-    if (!e || !opts) return FNN_E_INVALID;
-    if (int rc = no_autocast(e, opts, "fnn_labels_box")) return rc;
-    if (!acc || !labels || !box_lo || !box_hi || !out_lo || !out_hi) return fail(e, FNN_E_INVALID, "NULL argument");
-    if (!is_device_ptr(acc) || !is_device_ptr(labels)) return fail(e, FNN_E_INVALID, "fnn_labels_box needs device pointers");
-    if (acc_hp(e->arch) > 256)
-        return fail(e, FNN_E_UNSUPPORTED, "fnn_labels_box serves up to 254 classes (%d here): take the logits (fnn_normalize_box) and fnn_argmax_labels", e->arch.num_heads);
-    if (!e->label_u16 && e->label_mode == FNN_LABELS_ARGMAX && e->arch.num_heads > 256)
-        return fail(e, FNN_E_INVALID, "%d classes do not fit uint8 labels: fnn_set_label_rule(..., FNN_LABEL_U16)", e->arch.num_heads);
-    HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)opts->stream;
-    VolPlan vp;
-    if (plan_volume(e->arch, shape + 1, opts->tile_step_size, vp) != 0) return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
-    Box box;
-    for (int d = 0; d < 3; ++d) {
-        box.lo[d] = box_lo[d]; box.hi[d] = box_hi[d];
-        if (out_lo[d] < 0 || out_hi[d] > shape[1 + d] || out_lo[d] >= out_hi[d]) return fail(e, FNN_E_INVALID, "output box out of bounds");
-        if (out_lo[d] + vp.lo[d] < box.lo[d] || out_hi[d] + vp.lo[d] > box.hi[d])
-            return fail(e, FNN_E_INVALID, "output box is not covered by the accumulator box");
-    }
-    HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
-    FinalizeParams f = make_finalize(e, acc, box, out_lo, out_hi, vp, shape, *opts, opts->accum == FNN_ACC_FP32, 0, nullptr);
-    const int *order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
-    if (launch_labels_from_acc(f, labels, e->label_u16, order, st) != 0) return fail(e, FNN_E_HIP, "labels launch failed");
-    int flag = 0;
-    HIPCHK(e, hipMemcpyAsync(&flag, e->inf_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (flag) return fail(e, FNN_E_INF, "Encountered inf in predicted array.");
-    return 0;
+    return finalize_box(e, "fnn_labels_box", acc, shape, opts, box_lo, box_hi, out_lo, out_hi, nullptr, labels);
 }
 
 int64_t fnn_feature_channels(const fnn_engine *e) { return e ? e->layers[e->head_src].cout_pad : -1; }
@@ -1714,21 +1753,9 @@ int fnn_patch_features(fnn_engine *e, int fold, const float *vol, const int64_t 
     if (1 + (int)mirror_combos(*opts).size() > 8) return fail(e, FNN_E_UNSUPPORTED, "more than 8 evaluations per patch");
     if (!e->layers[e->head_src].has_norm) return fail(e, FNN_E_UNSUPPORTED, "the network's last layer has no InstanceNorm");
     HIPCHK(e, hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)opts->stream;
     VolPlan vp;
-    if (plan_volume(e->arch, shape + 1, opts->tile_step_size, vp) != 0) return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
-    std::vector<int64_t> ids(patch_ids, patch_ids + n_ids);
-    for (int64_t id : ids) if (id < 0 || id >= vp.n_patches) return fail(e, FNN_E_INVALID, "patch id out of range");
-    if (ids.empty()) return 0;
-    const float *vol_dev = nullptr;
-    if (int rc = stage_volume(e, vol, shape, vp, st, &vol_dev)) return rc;
-    if (int rc = upload_origins(e, vp, ids, st)) return rc;
-    Box box;
-    for (int d = 0; d < 3; ++d) { box.lo[d] = 0; box.hi[d] = vp.padded[d]; }
-    e->ev_used = 0; e->klog.clear();
-    if (int rc = run_patches(e, fold, vol_dev, vp, *opts, ids, e->origins, box, nullptr, 0, st, false, true, slot0, n_slots, feat, fss)) return rc;
-    if (e->profiling) { HIPCHK(e, hipStreamSynchronize(st)); collect_profile(e, n_ids); }
-    return 0;
+    if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
+    return run_listed_patches(e, fold, vol, shape, *opts, vp, patch_ids, n_ids, FeatSlots{feat, fss, nullptr, slot0, n_slots});
 }
 
 int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, const int32_t *slot_of_patch,
@@ -1739,24 +1766,19 @@ int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, 
     if (!is_device_ptr(feat) || !is_device_ptr(fss) || (out_logits && !is_device_ptr(out_logits)) || (labels && !is_device_ptr(labels)))
         return fail(e, FNN_E_INVALID, "fnn_gather_box needs device pointers");
     if (opts->out_dtype != FNN_OUT_F16) return fail(e, FNN_E_UNSUPPORTED, "fnn_gather_box: fp16 logits");
-    const auto combos = mirror_combos(*opts);
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)opts->stream;
     VolPlan vp;
-    if (plan_volume(e->arch, shape + 1, opts->tile_step_size, vp) != 0) return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
-    for (int d = 0; d < 3; ++d)
-        if (out_lo[d] < 0 || out_hi[d] > shape[1 + d] || out_lo[d] >= out_hi[d]) return fail(e, FNN_E_INVALID, "output box out of bounds");
-    const fnn_arch_desc &a = e->arch;
+    if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
+    if (int rc = check_out_box(e, vp, shape, out_lo, out_hi, nullptr)) return rc;
     const Layer &H = e->layers[e->head_src];
-    GatherParams g{};
-    g.heads = a.num_heads; g.C = H.cout_pad; g.PD = a.patch[0]; g.PH = a.patch[1]; g.PW = a.patch[2]; g.n_eval = 1 + (int)combos.size();
-    g.n_pass = e->n_gpass;
-    g.nx = (int)vp.steps[0].size(); g.ny = (int)vp.steps[1].size(); g.nz = (int)vp.steps[2].size();
+    GatherParams g = gather_params(e, fold, vp, shape, *opts);
     std::vector<int> tab;
     int win_off[3];
-    g.windowed = gather_tables(a, vp, &tab, win_off) ? 1 : 0;
+    (void)gather_tables(e->arch, vp, &tab, win_off);          // (g.windowed: whether it could)
+    // (labels of more than 256 classes end here too: the uint8 limit needs no check of its own)
     if (labels && e->n_gpass > 1)
-        return fail(e, FNN_E_UNSUPPORTED, "fnn_gather_box writes labels for <= 63 classes; with %d take the logits and fnn_argmax_labels", a.num_heads);
+        return fail(e, FNN_E_UNSUPPORTED, "fnn_gather_box writes labels for <= 63 classes; with %d take the logits and fnn_argmax_labels", e->arch.num_heads);
     if (!H.has_norm || e->head_ksteps != 1 || !gather_ok(g)) return fail(e, FNN_E_UNSUPPORTED, "this network's head does not fit the gather kernel");
     for (int64_t i = 0; i < vp.n_patches; ++i)
         if (slot_of_patch[i] >= n_slots) return fail(e, FNN_E_INVALID, "slot %d of patch %lld is beyond the %lld slots", slot_of_patch[i], (long long)i, (long long)n_slots);
@@ -1765,33 +1787,17 @@ int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, 
     for (int64_t i = 0; i < vp.n_patches; ++i) tab.push_back(slot_of_patch[i]);
     if (int rc = upload_ints(e, tab.data(), tab.size(), &e->steps_dev, &e->steps_cap, &e->steps_host, &e->steps_host_cap, &e->steps_ev, st)) return rc;
     HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
-    const FoldWeights &fw = e->folds[fold];
     {   // the kernel reads the InstanceNorm rows in the conv kernels' fp16 staging layout: converted from the caller's fp32 rows
         const size_t items = (size_t)n_slots * g.n_eval;
         if (int rc = ensure(e, &e->featssh, &e->featssh_bytes, items * 2 * H.cout_pad * sizeof(f16))) return rc;
         if (launch_fss_to_ssh(fss, (unsigned short *)e->featssh, (long long)items, H.cout_pad, st) != 0) return fail(e, FNN_E_HIP, "row conversion launch failed");
     }
     g.feat = (const f16 *)feat; g.fss = fss; g.fssh = (const unsigned short *)e->featssh;
-    g.n_slots = (int)n_slots; g.ring = 1; g.flipmask[0] = 0;       // evaluation f of slot s: item f * n_slots + s (fnn_patch_features)
-    for (size_t ci = 0; ci < combos.size() && ci + 1 < 8; ++ci) {
-        int m = 0;
-        for (int ax : combos[ci]) m |= 1 << ax;
-        g.flipmask[ci + 1] = m;
-    }
-    g.slope = H.act ? a.slope : 1.f;
+    g.n_slots = (int)n_slots; g.ring = 1;                       // evaluation f of slot s: item f * n_slots + s (fnn_patch_features)
     gather_set_tables(g, e->steps_dev, win_off);
     g.slot_tab = e->steps_dev + n_steps;
-    g.wpk = fw.wpk + e->head_w_off; g.bias = fw.fparam + e->head_bias_off; g.hblocks = e->hblocks;
-    g.pass_wpk = fw.wpk + e->gpass_w_off; g.pass_bias = fw.fparam + e->gpass_bias_off;
-    g.gauss = opts->use_gaussian ? e->gauss : e->ones;
-    g.lo_x = (int)vp.lo[0]; g.lo_y = (int)vp.lo[1]; g.lo_z = (int)vp.lo[2];
-    g.OX = shape[1]; g.OY = shape[2]; g.OZ = shape[3];
     g.x_lo = (int)out_lo[0]; g.x_hi = (int)out_hi[0]; g.y_lo = (int)out_lo[1]; g.y_hi = (int)out_hi[1];
     g.z_lo = (int)out_lo[2]; g.z_hi = (int)out_hi[2];
-    g.acc_mode = opts->accum; g.out_fp32 = 0; g.mode = 0; g.inf_flag = e->inf_flag;
-    g.label_u16 = e->label_u16; g.order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
-    if (labels && !e->label_u16 && e->label_mode == FNN_LABELS_ARGMAX && a.num_heads > 256)
-        return fail(e, FNN_E_INVALID, "%d classes do not fit uint8 labels", a.num_heads);
     e->ev_used = 0; e->klog.clear();
     if (out_logits) {
         g.out = out_logits; g.labels = nullptr;
@@ -1804,11 +1810,7 @@ int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, 
         Scope sc(e, st, FAM_HEAD, 0);
         if (launch_gather(g, st) != 0) return fail(e, FNN_E_HIP, "gather launch failed");
     }
-    int flag = 0;
-    HIPCHK(e, hipMemcpyAsync(&flag, e->inf_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (flag) return fail(e, FNN_E_INF, "Encountered inf in predicted array.");
-    return 0;
+    return check_inf(e, st);
 }
 
 static int region_copy(fnn_engine *e, void *feat, int64_t n_slots, const fnn_region *regions, int64_t n, void *message,
@@ -1847,9 +1849,7 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
     const size_t nin = (size_t)n * a.in_channels * P, nout = (size_t)n * a.num_heads * P;
     const float *xd = x;
     if (!is_device_ptr(x)) {
-        void *t = e->vol_tmp;
-        if (int rc = ensure(e, &t, &e->vol_tmp_bytes, nin * 4)) return rc;
-        e->vol_tmp = (float *)t;
+        if (int rc = ensure(e, &e->vol_tmp, &e->vol_tmp_bytes, nin * 4)) return rc;
         HIPCHK(e, hipMemcpyAsync(e->vol_tmp, x, nin * 4, hipMemcpyHostToDevice, st));
         xd = e->vol_tmp;
     }
@@ -1860,9 +1860,7 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
         od = (float *)e->out_tmp;
     }
     std::vector<int> zeros((size_t)e->max_batch * 3, 0);
-    void *t = e->origins;
-    if (int rc = ensure(e, &t, &e->origins_cap, zeros.size() * sizeof(int))) return rc;
-    e->origins = (int *)t;
+    if (int rc = ensure(e, &e->origins, &e->origins_cap, zeros.size() * sizeof(int))) return rc;
     HIPCHK(e, hipMemcpyAsync(e->origins, zeros.data(), zeros.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(e, hipStreamSynchronize(st));
     const long long vdim[3] = {a.patch[0], a.patch[1], a.patch[2]};
@@ -1870,10 +1868,10 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
     e->ev_used = 0; e->klog.clear();
     for (int p0 = 0; p0 < n; p0 += e->max_batch) {
         const int nb = (n - p0 < e->max_batch) ? n - p0 : e->max_batch;
-        if (int rc = forward_batch(e, fold, xd + (size_t)p0 * a.in_channels * P, (long long)(a.in_channels * P), vdim,
+        if (int rc = forward_batch(e, fold, e->arena[0], xd + (size_t)p0 * a.in_channels * P, (long long)(a.in_channels * P), vdim,
                                    e->origins, nb, flip, st)) return rc;
         for (int b = 0; b < nb; ++b) {
-            HeadParams h = make_head(e, fold, b);
+            HeadParams h = make_head(e, e->arena[0], fold, b);
             h.mode = 1; h.patch_buf = od + (size_t)(p0 + b) * a.num_heads * P;
             h.acc_fp32 = 1;
             Scope sc(e, st, FAM_HEAD, e->head_flops);
@@ -1911,7 +1909,7 @@ int fnn_argmax_labels(fnn_engine *e, const void *logits, int dtype, int heads, i
     if (!logits || !labels || heads < 1) return fail(e, FNN_E_INVALID, "bad argument");
     const bool regions = e->label_mode == FNN_LABELS_REGIONS;
     if (regions && heads != e->arch.num_heads) return fail(e, FNN_E_INVALID, "the region rule was set for %d heads, got %d", e->arch.num_heads, heads);
-    if (!regions && !e->label_u16 && heads > 256) return fail(e, FNN_E_INVALID, "%d classes do not fit uint8 labels", heads);
+    if (int rc = check_u8_labels(e, heads, "")) return rc;
     if (!is_device_ptr(logits) || !is_device_ptr(labels)) return fail(e, FNN_E_INVALID, "fnn_argmax_labels needs device pointers");
     HIPCHK(e, hipSetDevice(e->device));
     if (launch_argmax(logits, dtype == FNN_OUT_F32, heads, n_vox, labels, e->label_u16, regions ? e->label_order : nullptr,

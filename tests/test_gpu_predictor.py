@@ -291,6 +291,43 @@ def test_driver_bit_identical_to_oracle_driver_on_random_volumes(seed):
     _driver_case(case, mode, *SPECS[name])
 
 
+_PIPES_CHILD = r'''
+import os, sys
+import numpy as np
+import torch
+sys.path[:0] = [sys.argv[1], os.path.join(sys.argv[1], 'tests'), os.path.join(sys.argv[1], 'tests', 'golden')]
+from oracle.unet import synthetic_state_dict
+from test_gpu_predictor import SPECS, _bits, _predictor
+spec, patch = SPECS['toy3']
+image = torch.randn(1, 50, 37, 70, generator=torch.Generator().manual_seed(29))       # 6 x 4 x 4 tile positions
+p = _predictor(spec, patch, [synthetic_state_dict(spec, 77)], batch=3)
+np.save(sys.argv[2], _bits(p.predict_sliding_window_return_logits(image)))
+'''
+
+
+@pytest.mark.parametrize('gather', [True, False])
+def test_batches_in_flight_do_not_change_the_result(tmp_path, gather):
+    """Batches in flight run on arenas and streams of their own (run_patches: batch i on arena and stream i % pipes, the
+    heads in patch order).  96 patches in batches of 3, far more batches than pipes, give the same bits on one stream
+    (FNN_NO_PIPELINE), on two pipes (FNN_PIPES=2) and on the default four - on the gather path and on the accumulate path
+    (FNN_NO_GATHER).  The engine reads these knobs once per process: one child process per setting."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for i, knob in enumerate(({'FNN_NO_PIPELINE': '1'}, {'FNN_PIPES': '2'}, {})):
+        env = {k: v for k, v in os.environ.items() if k not in ('FNN_NO_PIPELINE', 'FNN_PIPES', 'FNN_NO_GATHER', 'FNN_GATHER_RING')}
+        env.update(knob, FNN_KNOBS='1')
+        if not gather:
+            env['FNN_NO_GATHER'] = '1'
+        out = str(tmp_path / f'logits{i}.npy')
+        r = subprocess.run([sys.executable, '-s', '-c', _PIPES_CHILD, root, out], env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        outs.append(np.load(out))
+    assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[0], outs[2])
+
+
 @pytest.mark.parametrize('shape,folds,accum', [((24, 40, 64), 1, 'fp16'), ((19, 23, 72), 2, 'fp16'), ((17, 16, 40), 1, 'fp32')])
 def test_driver_with_61_heads_uses_the_tiled_finalize(shape, folds, accum):
     """61 heads -> 64-channel accumulator rows: the vectorised seg head and the LDS-tiled finalize kernel
