@@ -66,7 +66,7 @@ class Profile(C.Structure):
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
            'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
-           'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
+           'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
 
@@ -146,6 +146,15 @@ def load_library() -> C.CDLL:
     lib.fnn_op_conv3d.argtypes = [i32, i32, I3, f32p, i32, f32p, f32p, C.c_float, f32p, i32, f32p, f32p, C.c_float,
                                   f32p, f32p, i32, I3, I3, f32p, C.POINTER(C.c_double)]
     lib.fnn_op_conv_transpose3d.argtypes = [i32, i32, I3, f32p, i32, f32p, f32p, C.c_float, f32p, f32p, i32, I3, f32p]
+    L3, u16p = C.POINTER(C.c_longlong), C.POINTER(C.c_uint16)
+    if hasattr(lib, 'fnn_op_avgpool'):                             # (absent from an older build picked with FNN_LIB for an A-B)
+        lib.fnn_op_avgpool.argtypes = [i32, i32, I3, f32p, i32, f32p, f32p, C.c_float, I3, i32, i32, f32p]
+        lib.fnn_op_combine.argtypes = [i32, i32, I3, i32, f32p, f32p, f32p, C.c_float, f32p, f32p, f32p, C.c_float, C.c_float, I3,
+                                       i32, i32, i32, i32, f32p, f32p]
+        lib.fnn_op_seg_head.argtypes = [i32, i32, i32, I3, f32p, f32p, f32p, C.c_float, i32, f32p, f32p, i32, i32, I3, u16p,
+                                        vp, i32, L3, I3, I3, f32p, C.POINTER(C.c_int)]
+        lib.fnn_op_patch_acc.argtypes = [i32, f32p, i32, I3, i32, u16p, vp, i32, L3, I3]
+        lib.fnn_op_patch_input.argtypes = [i32, f32p, i32, i32, L3, i32, I3, I3, I3, i32, i32, u16p]
     lib.fnn_op_quotient_check.argtypes = [i32, C.POINTER(C.c_uint64)]
     lib.fnn_op_last_kernels.argtypes = [C.c_char_p, i32]
     lib.fnn_clock_probe_start.argtypes = [i32, C.c_double, C.POINTER(C.c_void_p)]
@@ -377,8 +386,111 @@ def op_conv_transpose3d(x, w, bias, stride, gamma=None, beta=None, slope=1.0, de
     return y
 
 
+def _opt_f32(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+def _i3(v):
+    return (C.c_int * 3)(*[int(i) for i in v])
+
+
+def _u16p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
+def op_avgpool(x, stride, gamma=None, beta=None, slope=1.0, x_cm=False, y_cm=False, device=0):
+    """avgpool_kernel: AvgPool3d(stride, stride) of the transformed x [n,c,D,H,W] float32 (host) -> float32."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    n, c = x.shape[:2]
+    gamma, beta = _opt_f32(gamma), _opt_f32(beta)
+    y = np.zeros((n, c, *[x.shape[2 + i] // stride[i] for i in range(3)]), np.float32)
+    check(lib.fnn_op_avgpool(device, n, _i3(x.shape[2:]), _f32p(x), c, _f32p(gamma), _f32p(beta), slope, _i3(stride),
+                             int(x_cm), int(y_cm), _f32p(y)), lib)
+    return y
+
+
+def op_combine(a, b, slope, norm_a=None, slope_a=1.0, norm_b=None, slope_b=1.0, pool_stride=None, layouts=(0, 0, 0, 0), device=0):
+    """combine_kernel / combine_pool_kernel: LeakyReLU(T_a(a) + T_b(b), slope) for a, b [n,c,D,H,W]; norm_* = (gamma, beta) or
+    None; layouts = chunk-major flags of (a, b, out, pooled).  -> y, or (y, pooled) with a pool_stride."""
+    lib = load_library()
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    assert a.shape == b.shape
+    n, c = a.shape[:2]
+    ga, ba = (_opt_f32(norm_a[0]), _opt_f32(norm_a[1])) if norm_a is not None else (None, None)
+    gb, bb = (_opt_f32(norm_b[0]), _opt_f32(norm_b[1])) if norm_b is not None else (None, None)
+    y = np.zeros(a.shape, np.float32)
+    pooled = None if pool_stride is None else np.zeros((n, c, *[a.shape[2 + i] // pool_stride[i] for i in range(3)]), np.float32)
+    check(lib.fnn_op_combine(device, n, _i3(a.shape[2:]), c, _f32p(a), _f32p(ga), _f32p(ba), slope_a,
+                             _f32p(b), _f32p(gb), _f32p(bb), slope_b, slope, None if pool_stride is None else _i3(pool_stride),
+                             *[int(v) for v in layouts], _f32p(y), _f32p(pooled)), lib)
+    return y if pool_stride is None else (y, pooled)
+
+
+INT_MAX = 2 ** 31 - 1
+
+
+def op_seg_head(x, w, bias, item=0, mode=0, flips=(0, 0, 0), norm=None, slope=1.0, gauss_bits=None, acc=None, origin=(0, 0, 0),
+                first_visit=None, patch_buf=None, device=0):
+    """launch_head on item `item` of x [n,c,PD,PH,PW].  mode 0: acc [AX,Y,Z,HP] float16 or float32 is updated in place (a
+    contiguous array); modes 1 / 2: patch_buf [heads, PD*PH*PW] float32 in place.  -> does the kernel honour first_visit."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    n, c = x.shape[:2]
+    heads = w.shape[0]
+    assert w.shape == (heads, c)
+    g, bt = (_opt_f32(norm[0]), _opt_f32(norm[1])) if norm is not None else (None, None)
+    bias = _opt_f32(bias)
+    accp, fp32, box = None, 0, None
+    if mode == 0:
+        assert acc.flags['C_CONTIGUOUS'] and acc.dtype in (np.float16, np.float32) and acc.shape[3] == (heads + 1 + 7) // 8 * 8
+        accp, fp32, box = acc.ctypes.data_as(C.c_void_p), int(acc.dtype == np.float32), (C.c_longlong * 3)(*acc.shape[:3])
+    else:
+        assert patch_buf.flags['C_CONTIGUOUS'] and patch_buf.dtype == np.float32 and patch_buf.shape == (heads, int(np.prod(x.shape[2:])))
+    if gauss_bits is not None:
+        gauss_bits = np.ascontiguousarray(gauss_bits, np.uint16).reshape(-1)
+        assert gauss_bits.size == int(np.prod(x.shape[2:]))
+    honoured = C.c_int(0)
+    check(lib.fnn_op_seg_head(device, n, c, _i3(x.shape[2:]), _f32p(x), _f32p(g), _f32p(bt), slope, heads, _f32p(w), _f32p(bias),
+                              int(item), int(mode), _i3(flips), _u16p(gauss_bits), accp, fp32, box, _i3(origin),
+                              None if first_visit is None else _i3(first_visit), _f32p(patch_buf) if mode else None,
+                              C.byref(honoured)), lib)
+    return bool(honoured.value)
+
+
+def op_patch_acc(patch_buf, patch, n_div, acc, origin=(0, 0, 0), gauss_bits=None, device=0):
+    """patch_acc_kernel: acc [AX,Y,Z,HP] float16 / float32 (in place) += (patch_buf [heads, P] / n_div) * gaussian."""
+    lib = load_library()
+    patch_buf = np.ascontiguousarray(patch_buf, np.float32)
+    heads = patch_buf.shape[0]
+    assert acc.flags['C_CONTIGUOUS'] and acc.dtype in (np.float16, np.float32) and acc.shape[3] == (heads + 1 + 7) // 8 * 8
+    assert patch_buf.shape[1] == int(np.prod(patch))
+    if gauss_bits is not None:
+        gauss_bits = np.ascontiguousarray(gauss_bits, np.uint16).reshape(-1)
+        assert gauss_bits.size == patch_buf.shape[1]
+    check(lib.fnn_op_patch_acc(device, _f32p(patch_buf), heads, _i3(patch), int(n_div), _u16p(gauss_bits),
+                               acc.ctypes.data_as(C.c_void_p), int(acc.dtype == np.float32), (C.c_longlong * 3)(*acc.shape[:3]),
+                               _i3(origin)), lib)
+
+
+def op_patch_input(vol, origins, patch, cpad, flips=(0, 0, 0), chunk_major=False, device=0):
+    """patch_input_kernel: vol [C,X,Y,Z] (one volume for every item) or [n,C,X,Y,Z] float32 -> uint16 fp16 bits [n,cpad,PD,PH,PW]."""
+    lib = load_library()
+    vol = np.ascontiguousarray(vol, np.float32)
+    origins = np.ascontiguousarray(origins, np.int32).reshape(-1, 3)
+    n = origins.shape[0]
+    n_vol = 1 if vol.ndim == 4 else vol.shape[0]
+    c = vol.shape[-4]
+    out = np.zeros((n, cpad, *patch), np.uint16)
+    check(lib.fnn_op_patch_input(device, _f32p(vol), n_vol, c, (C.c_longlong * 3)(*vol.shape[-3:]), n,
+                                 origins.ctypes.data_as(C.POINTER(C.c_int)), _i3(flips), _i3(patch), int(cpad), int(chunk_major),
+                                 _u16p(out)), lib)
+    return out
+
+
 def op_last_kernels():
-    """Kernel variants launched by this thread's last op_conv3d / op_conv_transpose3d call."""
+    """Kernel variants launched by this thread's last op_* call."""
     lib = load_library()
     buf = C.create_string_buffer(4096)
     lib.fnn_op_last_kernels(buf, 4096)

@@ -562,7 +562,9 @@ int build_plan(fnn_engine *e) {
 // ---------------------------------------------------------------------------
 // weight packing (host)
 // ---------------------------------------------------------------------------
-void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, uint16_t *dst) {
+}  // namespace
+// (declared in fnn_device.h: the single-op entry points pack a head the same way)
+void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, unsigned short *dst) {
     for (int hb = 0; hb < hblocks; ++hb)
         for (int ks = 0; ks < ksteps; ++ks)
             for (int lane = 0; lane < 64; ++lane)
@@ -573,6 +575,13 @@ void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, uint
                     dst[(((size_t)hb * ksteps + ks) * 64 + lane) * 8 + j] = fnn_half_bits(v);
                 }
 }
+
+// bias row of the head kernels, [hblocks * 16]: the heads' biases, then the weight-sum channel (zero weights in pack_head,
+// bias 1: its "logit" is 1 and 1 * gaussian is the weight itself), zeros behind it
+void pack_head_bias(int heads, int hblocks, const float *bias, float *dst) {
+    for (int h = 0; h < hblocks * 16; ++h) dst[h] = h < heads ? (bias ? bias[h] : 0.f) : (h == heads ? 1.f : 0.f);
+}
+namespace {
 
 // ---------------------------------------------------------------------------
 // profiling helpers
@@ -1666,8 +1675,7 @@ int fnn_load_weights(fnn_engine *e, int fold, const float *blob, int64_t count) 
         }
     }
     pack_head(e->arch.num_heads, e->arch.features[0], e->hblocks, e->head_ksteps, blob + e->blob_head_w, wpk.data() + e->head_w_off);
-    for (int h = 0; h < e->arch.num_heads; ++h) fp[e->head_bias_off + h] = blob[e->blob_head_b + h];
-    fp[e->head_bias_off + e->arch.num_heads] = 1.f;         // accumulator channel `heads`: 1 * gaussian = the weight itself
+    pack_head_bias(e->arch.num_heads, e->hblocks, blob + e->blob_head_b, fp.data() + e->head_bias_off);
     for (int k = 0; k < (e->n_gpass > 1 ? e->n_gpass : 0); ++k) {      // gather passes: heads 63 k .. + cnt - 1, then the weight-sum row
         const int h0 = 63 * k, cnt = std::min(63, e->arch.num_heads - h0), cin = e->arch.features[0];
         pack_head(cnt, cin, 4, 1, blob + e->blob_head_w + (size_t)h0 * cin, wpk.data() + e->gpass_w_off + (size_t)k * 4 * 512);

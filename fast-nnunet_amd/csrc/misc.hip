@@ -1086,13 +1086,18 @@ int launch_head(const HeadParams &p, hipStream_t st) {
             // accumulator traffic (each line is touched once per patch: +1.3 % on the round-1 benchmark) and registers for two
             // workgroups per SIMD (177 VGPRs instead of 214).  The A-B variants of those choices (FNN_HEAD_RD / _NT / _MINB)
             // were six more kernels that nothing but a knob selected: gone (round 3).
+            fnn_note_kernel(p.acc_fp32 ? "seg_head_acc1_kernel<1,2>" : "seg_head_acc1_kernel<0,2,3,2>");
             if (p.acc_fp32) hipLaunchKernelGGL((seg_head_acc1_kernel<true, 2>), grid, dim3(256), lds, st, p);
             else hipLaunchKernelGGL((seg_head_acc1_kernel<false, 2, 3, 2>), grid, dim3(256), lds, st, p);
-        } else if (p.acc_fp32) hipLaunchKernelGGL(seg_head_acc_kernel<true>, grid, dim3(256), lds, st, p);
-        else hipLaunchKernelGGL(seg_head_acc_kernel<false>, grid, dim3(256), lds, st, p);
+        } else {
+            fnn_note_kernel("seg_head_acc_kernel<%d>", p.acc_fp32 ? 1 : 0);
+            if (p.acc_fp32) hipLaunchKernelGGL(seg_head_acc_kernel<true>, grid, dim3(256), lds, st, p);
+            else hipLaunchKernelGGL(seg_head_acc_kernel<false>, grid, dim3(256), lds, st, p);
+        }
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
     const size_t lds = (size_t)((p.src.C * 8 + 255) & ~255) + (size_t)4 * 64 * 65 * 4;
+    fnn_note_kernel("seg_head_kernel");
     return fnn_launch_lds<seg_head_kernel>(grid, dim3(256), lds, st, p);
 }
 
@@ -1126,6 +1131,7 @@ __global__ __launch_bounds__(256) void patch_acc_kernel(const PatchAccParams p) 
 
 int launch_patch_acc(const PatchAccParams &p, hipStream_t st) {
     const int P = p.PD * p.PH * p.PW;
+    fnn_note_kernel("patch_acc_kernel<%d>", p.acc_fp32 ? 1 : 0);
     if (p.acc_fp32) hipLaunchKernelGGL(patch_acc_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(patch_acc_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? 0 : -2;

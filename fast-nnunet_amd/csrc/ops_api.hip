@@ -61,11 +61,12 @@ struct SrcHolder {
 };
 
 bool make_src(SrcHolder &h, const float *x, int n, int c, size_t vox, const float *gamma, const float *beta, float slope,
-              bool layout_aware = false) {
+              bool layout_aware = false, int layout = -1) {
+    // layout: -1 = the FNN_OP_CHUNK_MAJOR knob decides (conv ops), 0 = channels-last, 1 = chunk-major (an argument of the body ops)
     const int cp = pad16(c);
     std::vector<uint16_t> a;
     std::vector<double> st;
-    const bool cm = layout_aware && op_chunk_major(cp);
+    const bool cm = layout < 0 ? layout_aware && op_chunk_major(cp) : layout != 0;
     to_ndhwc(x, n, c, cp, vox, a, gamma ? &st : nullptr, cm);
     if (!h.act.alloc(a.size() * 2)) return false;
     if (hipMemcpy(h.act.p, a.data(), a.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return false;
@@ -88,6 +89,40 @@ bool make_src(SrcHolder &h, const float *x, int n, int c, size_t vox, const floa
         h.d.ssh = h.ssh.as<unsigned short>();
         h.d.slope = slope;
     }
+    return true;
+}
+
+}  // namespace
+
+
+namespace {
+
+// device tensor [n][vox][cp] (channels-last) or [n][cp / 16][vox][16] (chunk-major), fp16 -> host float32 [n][c][vox]
+void from_device_layout(const std::vector<uint16_t> &ho, int n, int c, int cp, size_t vox, bool cm, float *y) {
+    for (int b = 0; b < n; ++b)
+        for (int ch = 0; ch < c; ++ch)
+            for (size_t v = 0; v < vox; ++v)
+                y[((size_t)b * c + ch) * vox + v] =
+                    h2f_bits(ho[cm ? ((size_t)b * cp / 16 + ch / 16) * vox * 16 + v * 16 + ch % 16 : ((size_t)b * vox + v) * cp + ch]);
+}
+
+// a body-op operand: make_src with the layout as an argument and the slope applied with or without a norm, as the kernels do
+bool make_body_src(SrcHolder &h, const float *x, int n, int c, size_t vox, const float *gamma, const float *beta, float slope, int cm) {
+    if (!make_src(h, x, n, c, vox, gamma, beta, slope, false, cm ? 1 : 0)) return false;
+    h.d.slope = slope;
+    return true;
+}
+
+bool upload(DevBuf &d, const void *src, size_t bytes) {
+    return d.alloc(bytes) && hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// Where a patch lands in an accumulator box: shared by the head and patch-accumulate ops
+struct AccArgs { void *acc; int acc_fp32; const long long *box; const int *origin; };
+bool acc_args_ok(const AccArgs &a, const int patch[3], int heads) {
+    if (!a.acc || !a.box || !a.origin || heads < 1) return false;
+    for (int i = 0; i < 3; ++i)
+        if (patch[i] < 1 || a.origin[i] < 0 || a.box[i] < 1 || (long long)a.origin[i] + patch[i] > a.box[i]) return false;
     return true;
 }
 
@@ -267,6 +302,201 @@ int fnn_op_conv_transpose3d(int device, int n, const int dims[3],
             for (size_t v = 0; v < ovox; ++v)
                 y[((size_t)b * cout + co) * ovox + v] =
                     h2f_bits(ho[ocm ? ((size_t)b * cop / 16 + co / 16) * ovox * 16 + v * 16 + co % 16 : ((size_t)b * ovox + v) * cop + co]);
+    return 0;
+}
+
+int fnn_op_avgpool(int device, int n, const int dims[3], const float *x, int c,
+                   const float *gamma, const float *beta, float slope, const int stride[3],
+                   int x_chunk_major, int y_chunk_major, float *y) {
+    if (!x || !y || !dims || !stride || n < 1 || c < 1) return FNN_E_INVALID;
+    for (int i = 0; i < 3; ++i) if (stride[i] < 1 || dims[i] < stride[i]) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    OpKlog klog;
+    const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
+    const int cp = pad16(c);
+    SrcHolder s;
+    if (!make_body_src(s, x, n, c, vox, gamma, beta, slope, x_chunk_major)) return FNN_E_HIP;
+    PoolParams p{};
+    p.src = s.d; p.N = n; p.Di = dims[0]; p.Hi = dims[1]; p.Wi = dims[2];
+    p.sd = stride[0]; p.sh = stride[1]; p.sw = stride[2];
+    const size_t ovox = (size_t)(dims[0] / stride[0]) * (dims[1] / stride[1]) * (dims[2] / stride[2]);
+    DevBuf dout;
+    if (!dout.alloc((size_t)n * ovox * cp * 2)) return FNN_E_HIP;
+    (void)hipMemset(dout.p, 0, (size_t)n * ovox * cp * 2);
+    p.out = dout.as<f16>();
+    if (y_chunk_major) { p.out_vs = 16; p.out_cs = 16LL * (long long)ovox; }
+    if (launch_avgpool(p, 0) != 0) return FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    std::vector<uint16_t> ho((size_t)n * ovox * cp);
+    (void)hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost);
+    from_device_layout(ho, n, c, cp, ovox, y_chunk_major != 0, y);
+    return 0;
+}
+
+int fnn_op_combine(int device, int n, const int dims[3], int c,
+                   const float *a, const float *gamma_a, const float *beta_a, float slope_a,
+                   const float *b, const float *gamma_b, const float *beta_b, float slope_b,
+                   float slope, const int pool_stride[3],
+                   int a_chunk_major, int b_chunk_major, int y_chunk_major, int pooled_chunk_major,
+                   float *y, float *pooled) {
+    if (!a || !b || !y || !dims || n < 1 || c < 1 || (pool_stride && !pooled)) return FNN_E_INVALID;
+    for (int i = 0; i < 3; ++i) if (dims[i] < 1) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    OpKlog klog;
+    const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
+    const int cp = pad16(c);
+    SrcHolder sa, sb;
+    if (!make_body_src(sa, a, n, c, vox, gamma_a, beta_a, slope_a, a_chunk_major)) return FNN_E_HIP;
+    if (!make_body_src(sb, b, n, c, vox, gamma_b, beta_b, slope_b, b_chunk_major)) return FNN_E_HIP;
+    CombineParams p{};
+    p.a = sa.d; p.b = sb.d; p.vox = (long long)vox; p.N = n; p.slope = slope;
+    DevBuf dout, dpool;
+    if (!dout.alloc((size_t)n * vox * cp * 2)) return FNN_E_HIP;
+    (void)hipMemset(dout.p, 0, (size_t)n * vox * cp * 2);
+    p.out = dout.as<f16>();
+    if (y_chunk_major) { p.out_vs = 16; p.out_cs = 16LL * (long long)vox; }
+    size_t pvox = 0;
+    if (pool_stride) {
+        // the launcher takes the strides combine_pool_kernel serves and sizes that are multiples of them; anything else is
+        // the caller's to send through fnn_op_avgpool, as the planner does
+        if (!combine_pool_ok(dims[0], dims[1], dims[2], pool_stride[0], pool_stride[1], pool_stride[2])) return FNN_E_UNSUPPORTED;
+        pvox = (size_t)(dims[0] / pool_stride[0]) * (dims[1] / pool_stride[1]) * (dims[2] / pool_stride[2]);
+        if (!dpool.alloc((size_t)n * pvox * cp * 2)) return FNN_E_HIP;
+        (void)hipMemset(dpool.p, 0, (size_t)n * pvox * cp * 2);
+        p.pool_out = dpool.as<f16>();
+        p.D = dims[0]; p.H = dims[1]; p.W = dims[2];
+        p.psd = pool_stride[0]; p.psh = pool_stride[1]; p.psw = pool_stride[2];
+        if (pooled_chunk_major) { p.pool_vs = 16; p.pool_cs = 16LL * (long long)pvox; }
+    }
+    const int rc = launch_combine(p, 0);
+    if (rc != 0) return rc == -1 ? FNN_E_UNSUPPORTED : FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    std::vector<uint16_t> ho((size_t)n * vox * cp);
+    (void)hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost);
+    from_device_layout(ho, n, c, cp, vox, y_chunk_major != 0, y);
+    if (pool_stride) {
+        ho.resize((size_t)n * pvox * cp);
+        (void)hipMemcpy(ho.data(), dpool.p, ho.size() * 2, hipMemcpyDeviceToHost);
+        from_device_layout(ho, n, c, cp, pvox, pooled_chunk_major != 0, pooled);
+    }
+    return 0;
+}
+
+int fnn_op_seg_head(int device, int n, int c, const int patch[3], const float *x,
+                    const float *gamma, const float *beta, float slope,
+                    int heads, const float *w, const float *bias,
+                    int item, int mode, const int flips[3], const unsigned short *gauss,
+                    void *acc, int acc_fp32, const long long box[3], const int origin[3], const int first_visit[3],
+                    float *patch_buf, int *first_visit_honoured) {
+    if (!x || !w || !patch || !flips || n < 1 || c < 1 || heads < 1 || item < 0 || item >= n || mode < 0 || mode > 2) return FNN_E_INVALID;
+    for (int i = 0; i < 3; ++i) if (patch[i] < 1) return FNN_E_INVALID;
+    const AccArgs aa{acc, acc_fp32, box, origin};
+    if (mode == 0 ? !acc_args_ok(aa, patch, heads) : !patch_buf) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    OpKlog klog;
+    const size_t P = (size_t)patch[0] * patch[1] * patch[2];
+    const int cp = pad16(c);
+    SrcHolder s;                                    // the head kernels read channels-last features
+    if (!make_body_src(s, x, n, c, P, gamma, beta, slope, 0)) return FNN_E_HIP;
+    HeadParams h{};
+    h.src = s.d; h.b = item; h.PD = patch[0]; h.PH = patch[1]; h.PW = patch[2];
+    h.heads = heads; h.hblocks = (heads + 1 + 15) / 16; h.ksteps = (cp + 31) / 32;      // as the engine plans them
+    h.HP = (heads + 1 + 7) / 8 * 8;
+    h.flip_d = flips[0]; h.flip_h = flips[1]; h.flip_w = flips[2];
+    h.mode = mode; h.acc_fp32 = acc_fp32;
+    h.fx = h.fy = h.fz = 0x7fffffff;
+    std::vector<uint16_t> wp((size_t)h.hblocks * h.ksteps * 512);
+    std::vector<float> bp((size_t)h.hblocks * 16);
+    pack_head(heads, c, h.hblocks, h.ksteps, w, wp.data());
+    pack_head_bias(heads, h.hblocks, bias, bp.data());
+    DevBuf dw, db, dg, dacc, dpb;
+    if (!upload(dw, wp.data(), wp.size() * 2) || !upload(db, bp.data(), bp.size() * 4)) return FNN_E_HIP;
+    h.wpk = dw.as<f16>(); h.bias = db.as<float>();
+    size_t acc_bytes = 0;
+    if (mode == 0) {
+        // the weight map: the caller's, or the all-ones map the engine keeps for use_gaussian = 0
+        std::vector<uint16_t> ones;
+        if (!gauss) ones.assign(P, fnn_half_bits(1.f));
+        if (!upload(dg, gauss ? gauss : ones.data(), P * 2)) return FNN_E_HIP;
+        h.gauss = dg.as<f16>();
+        h.AX = box[0]; h.Y = box[1]; h.Z = box[2];
+        h.ox = origin[0]; h.oy = origin[1]; h.oz = origin[2];
+        acc_bytes = (size_t)box[0] * box[1] * box[2] * h.HP * (acc_fp32 ? 4 : 2);
+        if (!upload(dacc, acc, acc_bytes)) return FNN_E_HIP;
+        h.acc = dacc.p;
+    } else {
+        if (!upload(dpb, patch_buf, (size_t)heads * P * 4)) return FNN_E_HIP;
+        h.patch_buf = dpb.as<float>();
+    }
+    const bool fv_ok = launch_head_first_visit_ok(h);
+    if (first_visit_honoured) *first_visit_honoured = fv_ok ? 1 : 0;
+    if (first_visit) {
+        const bool all_read = first_visit[0] == 0x7fffffff && first_visit[1] == 0x7fffffff && first_visit[2] == 0x7fffffff;
+        if (!fv_ok && !all_read) return FNN_E_UNSUPPORTED;
+        h.fx = first_visit[0]; h.fy = first_visit[1]; h.fz = first_visit[2];
+    }
+    if (launch_head(h, 0) != 0) return FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    if (mode == 0) (void)hipMemcpy(acc, dacc.p, acc_bytes, hipMemcpyDeviceToHost);
+    else (void)hipMemcpy(patch_buf, dpb.p, (size_t)heads * P * 4, hipMemcpyDeviceToHost);
+    return 0;
+}
+
+int fnn_op_patch_acc(int device, const float *patch_buf, int heads, const int patch[3], int n_div,
+                     const unsigned short *gauss, void *acc, int acc_fp32, const long long box[3], const int origin[3]) {
+    const AccArgs aa{acc, acc_fp32, box, origin};
+    if (!patch_buf || !patch || n_div < 1 || !acc_args_ok(aa, patch, heads)) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    OpKlog klog;
+    const size_t P = (size_t)patch[0] * patch[1] * patch[2];
+    PatchAccParams q{};
+    q.n_div = n_div; q.PD = patch[0]; q.PH = patch[1]; q.PW = patch[2]; q.heads = heads;
+    q.AX = box[0]; q.Y = box[1]; q.Z = box[2]; q.HP = (heads + 1 + 7) / 8 * 8;
+    q.ox = origin[0]; q.oy = origin[1]; q.oz = origin[2]; q.acc_fp32 = acc_fp32;
+    const size_t acc_bytes = (size_t)box[0] * box[1] * box[2] * q.HP * (acc_fp32 ? 4 : 2);
+    DevBuf dpb, dg, dacc;
+    if (!upload(dpb, patch_buf, (size_t)heads * P * 4) || !upload(dacc, acc, acc_bytes)) return FNN_E_HIP;
+    if (gauss && !upload(dg, gauss, P * 2)) return FNN_E_HIP;
+    q.patch_buf = dpb.as<float>(); q.gauss = gauss ? dg.as<f16>() : nullptr; q.acc = dacc.p;
+    if (launch_patch_acc(q, 0) != 0) return FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    (void)hipMemcpy(acc, dacc.p, acc_bytes, hipMemcpyDeviceToHost);
+    return 0;
+}
+
+int fnn_op_patch_input(int device, const float *vol, int n_vol, int c, const long long vdim[3],
+                       int n, const int *origins, const int flips[3], const int patch[3], int cpad, int chunk_major,
+                       unsigned short *out) {
+    if (!vol || !vdim || !origins || !flips || !patch || !out || n < 1 || c < 1 || cpad < c || cpad % 16 != 0) return FNN_E_INVALID;
+    if (n_vol != 1 && n_vol != n) return FNN_E_INVALID;
+    for (int b = 0; b < n; ++b)
+        for (int i = 0; i < 3; ++i)
+            if (patch[i] < 1 || origins[b * 3 + i] < 0 || (long long)origins[b * 3 + i] + patch[i] > vdim[i]) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    OpKlog klog;
+    const size_t P = (size_t)patch[0] * patch[1] * patch[2];
+    const size_t vvox = (size_t)vdim[0] * vdim[1] * vdim[2];
+    PatchInputParams p{};
+    DevBuf dvol, dorg, dout;
+    if (!upload(dvol, vol, (size_t)n_vol * c * vvox * 4) || !upload(dorg, origins, (size_t)n * 3 * 4)) return FNN_E_HIP;
+    if (!dout.alloc((size_t)n * P * cpad * 2)) return FNN_E_HIP;
+    (void)hipMemset(dout.p, 0xff, (size_t)n * P * cpad * 2);               // (NaN bits: the kernel writes the padding channels)
+    p.vol = dvol.as<float>(); p.vol_batch_stride = n_vol == 1 ? 0 : (long long)c * (long long)vvox;
+    p.C = c; p.Cpad = cpad; p.X = vdim[0]; p.Y = vdim[1]; p.Z = vdim[2];
+    p.origins = dorg.as<int>();
+    p.flip_d = flips[0]; p.flip_h = flips[1]; p.flip_w = flips[2];
+    p.PD = patch[0]; p.PH = patch[1]; p.PW = patch[2]; p.N = n;
+    p.out = dout.as<f16>();
+    if (chunk_major) { p.out_vs = 16; p.out_cs = 16LL * (long long)P; }
+    if (launch_patch_input(p, 0) != 0) return FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    std::vector<uint16_t> ho((size_t)n * P * cpad);
+    (void)hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost);
+    for (int b = 0; b < n; ++b)
+        for (int ch = 0; ch < cpad; ++ch)
+            for (size_t v = 0; v < P; ++v)
+                out[((size_t)b * cpad + ch) * P + v] =
+                    ho[chunk_major ? ((size_t)b * cpad / 16 + ch / 16) * P * 16 + v * 16 + ch % 16 : ((size_t)b * P + v) * cpad + ch];
     return 0;
 }
 

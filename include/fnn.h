@@ -446,7 +446,53 @@ int fnn_op_conv_transpose3d(int device, int n, const int dims[3],
                             const float *x, int cin, const float *gamma1, const float *beta1, float slope1,
                             const float *w, const float *bias, int cout, const int stride[3], float *y);
 
-/* The kernel variants the last fnn_op_conv3d / fnn_op_conv_transpose3d call of this thread launched, one per line (the
+/* ---- single-op entry points of the kernels between the convs (additive in ABI 4) ----
+ * The same conventions: host float32 NCDHW in / out, operands rounded to fp16 once by the library, gamma != NULL = the
+ * operand is a raw conv output whose InstanceNorm (statistics of the fp16-rounded values) is applied on load; here the
+ * LeakyReLU slope of an operand applies with or without a norm (1 = none).  Each call goes through the launcher the
+ * engine calls.  The layout of every device tensor is an ARGUMENT (x_chunk_major etc.: 0 = channels-last,
+ * 1 = [C / 16][voxels][16]), because the kernels take either on each operand and output separately.
+ *
+ * fnn_op_avgpool: AvgPool3d(stride, stride) of the transformed x (the skip path of a strided residual block),
+ *   y [n][c][D / s0][H / s1][W / s2].
+ * fnn_op_combine: y = LeakyReLU(T_a(a) + T_b(b), slope), the closing add of a residual block.  pool_stride != NULL:
+ *   the launch also writes AvgPool3d(pool_stride) of the fp16-rounded y into `pooled` (FNN_E_UNSUPPORTED for strides or
+ *   sizes the fused kernel does not take: the planner sends those through the pooling kernel). */
+int fnn_op_avgpool(int device, int n, const int dims[3], const float *x, int c,
+                   const float *gamma, const float *beta, float slope, const int stride[3],
+                   int x_chunk_major, int y_chunk_major, float *y);
+int fnn_op_combine(int device, int n, const int dims[3], int c,
+                   const float *a, const float *gamma_a, const float *beta_a, float slope_a,
+                   const float *b, const float *gamma_b, const float *beta_b, float slope_b,
+                   float slope, const int pool_stride[3],
+                   int a_chunk_major, int b_chunk_major, int y_chunk_major, int pooled_chunk_major,
+                   float *y, float *pooled);
+/* fnn_op_seg_head: the 1x1x1 seg head of batch item `item` of the features x [n][c][PD][PH][PW] (norm on load as above),
+ *   weights w [heads][c] and bias [heads] (NULL = 0) packed as the engine packs them, weight-sum row included.
+ *   mode 0: logits * gaussian accumulated into the box acc [box0][box1][box2][HP] (HP = round_up(heads + 1, 8); fp16 bits
+ *     or float32 by acc_fp32; in / out) at `origin`; gauss = fp16 bits [PD * PH * PW] or NULL (weight 1); channel `heads`
+ *     accumulates the weight.  first_visit (NULL = read every voxel): the thresholds of HeadParams - voxels with
+ *     d >= first_visit[0] && h >= [1] && w >= [2] are written as 0 + contribution without being read.  Only the
+ *     one-k-step kernels know them: *first_visit_honoured (may be NULL) says whether this call's kernel does, and
+ *     thresholds other than INT_MAX are FNN_E_UNSUPPORTED when it does not.
+ *   mode 1 / 2: patch_buf [heads][PD * PH * PW] float32 (in / out) = / += the logits, un-mirrored by `flips`.
+ * fnn_op_patch_acc: the mean of n_div mirrored evaluations (patch_buf / n_div) * gaussian accumulated into acc, as above.
+ * fnn_op_patch_input: patch windows of the volumes vol [n_vol][c][X][Y][Z] (n_vol = 1: one volume for every item, or
+ *   n_vol = n) at origins [n][3], mirrored by `flips` -> the fp16 bits of the network input, out [n][cpad][PD][PH][PW]
+ *   (the padding channels included). */
+int fnn_op_seg_head(int device, int n, int c, const int patch[3], const float *x,
+                    const float *gamma, const float *beta, float slope,
+                    int heads, const float *w, const float *bias,
+                    int item, int mode, const int flips[3], const unsigned short *gauss,
+                    void *acc, int acc_fp32, const long long box[3], const int origin[3], const int first_visit[3],
+                    float *patch_buf, int *first_visit_honoured);
+int fnn_op_patch_acc(int device, const float *patch_buf, int heads, const int patch[3], int n_div,
+                     const unsigned short *gauss, void *acc, int acc_fp32, const long long box[3], const int origin[3]);
+int fnn_op_patch_input(int device, const float *vol, int n_vol, int c, const long long vdim[3],
+                       int n, const int *origins, const int flips[3], const int patch[3], int cpad, int chunk_major,
+                       unsigned short *out);
+
+/* The kernel variants the last fnn_op_* call of this thread launched, one per line (the
  * launchers pick a variant from the layer's shape; the op tests pin which one a case exercises).  Returns the size needed. */
 int fnn_op_last_kernels(char *buf, int cap);
 
