@@ -20,6 +20,7 @@ FNN_ACC_FP16_REFERENCE, FNN_ACC_FP32, FNN_ACC_FP16_AUTOCAST = 0, 1, 2
 FNN_OUT_F16, FNN_OUT_F32 = 0, 1
 FNN_LABELS_ARGMAX, FNN_LABELS_REGIONS = 0, 1
 FNN_LABEL_U8, FNN_LABEL_U16 = 0, 1
+FNN_INTERP_LINEAR, FNN_INTERP_NEAREST_EXACT, FNN_INTERP_OTHER = 0, 1, 2
 FNN_NORM_NONE, FNN_NORM_ZSCORE, FNN_NORM_CT, FNN_NORM_RESCALE01, FNN_NORM_RGB01 = 0, 1, 2, 3, 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,6 +51,11 @@ class ResampleDesc(C.Structure):
     _fields_ = [('order', C.c_int32), ('separate_axis', C.c_int32), ('order_z', C.c_int32), ('dtype', C.c_int32)]
 
 
+class ResampleTorchDesc(C.Structure):
+    _fields_ = [('dtype', C.c_int32), ('separate_axis', C.c_int32), ('memefficient', C.c_int32), ('mode', C.c_int32),
+                ('aniso_axis_mode', C.c_int32)]
+
+
 class Opts(C.Structure):
     _fields_ = [('tile_step_size', C.c_double), ('use_gaussian', C.c_int32), ('n_mirror_axes', C.c_int32),
                 ('mirror_axes', C.c_int32 * 3), ('accum', C.c_int32), ('out_dtype', C.c_int32),
@@ -65,7 +71,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -120,6 +126,8 @@ def load_library() -> C.CDLL:
     lib.fnn_export_probabilities.argtypes = [vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(i64), C.POINTER(i64),
                                              C.POINTER(i32), vp, vp, i32, vp]
     lib.fnn_resample.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleDesc), vp, vp]
+    lib.fnn_resample_torch.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleTorchDesc), vp, vp]
+    lib.fnn_resample_torch_seg.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleTorchDesc), vp, vp]
     lib.fnn_keep_largest_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), vp]
     lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
                                         C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
@@ -283,6 +291,22 @@ def resample(in_ptr: int, shape, new_shape, order: int, separate_axis, half: boo
                      FNN_OUT_F16 if half else FNN_OUT_F32)
     check(lib.fnn_resample(in_ptr, (C.c_int64 * 4)(*[int(i) for i in shape]), (C.c_int64 * 3)(*[int(i) for i in new_shape]),
                            C.byref(d), out_ptr, stream), lib)
+
+
+def _interp_mode(name: str) -> int:
+    return {'linear': FNN_INTERP_LINEAR, 'nearest-exact': FNN_INTERP_NEAREST_EXACT}.get(name, FNN_INTERP_OTHER)
+
+
+def resample_torch(in_ptr: int, shape, new_shape, separate_axis, half: bool, out_ptr: int, stream: int = 0, is_seg: bool = False,
+                   memefficient: bool = False, mode: str = 'linear', aniso_axis_mode: str = 'nearest-exact'):
+    """resample_torch_fornnunet of a [C, ...] tensor: fp32 / fp16 (`half`) images and logits, or with `is_seg` int16 label
+    maps (the fp16-argmax rule, or the `memefficient` one).  Asynchronous on `stream`."""
+    lib = load_library()
+    d = ResampleTorchDesc(FNN_OUT_F16 if half else FNN_OUT_F32, -1 if separate_axis is None else int(separate_axis),
+                          int(bool(memefficient)), _interp_mode(mode), _interp_mode(aniso_axis_mode))
+    fn = lib.fnn_resample_torch_seg if is_seg else lib.fnn_resample_torch
+    check(fn(in_ptr, (C.c_int64 * 4)(*[int(i) for i in shape]), (C.c_int64 * 3)(*[int(i) for i in new_shape]),
+             C.byref(d), out_ptr, stream), lib)
 
 
 def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, background_label: int,

@@ -101,6 +101,15 @@ class ConfigurationManager:
                                                                        'force_separate_z': None})
 
     @property
+    def resampling_fn_seg_name(self) -> str:
+        return self.configuration.get('resampling_fn_seg', 'resample_data_or_seg_to_shape')
+
+    @property
+    def resampling_fn_seg_kwargs(self) -> dict:
+        return self.configuration.get('resampling_fn_seg_kwargs', {'is_seg': True, 'order': 1, 'order_z': 0,
+                                                                     'force_separate_z': None})
+
+    @property
     def resampling_fn_probabilities_name(self) -> str:
         return self.configuration.get('resampling_fn_probabilities', 'resample_data_or_seg_to_shape')
 

@@ -12,7 +12,7 @@ Mirrors, with the reference's argument names and property keys,
   revert cropping, ``transpose_backward``.
 
 Every numerical step is a HIP kernel behind ``include/fnn.h`` (``fnn_nonzero_bbox``, ``fnn_preprocess``,
-``fnn_resample``, ``fnn_argmax_labels``, ``fnn_revert_labels``); torch only owns the device buffers.  No CPU path.
+``fnn_resample``, ``fnn_resample_torch``, ``fnn_resample_torch_seg``, ``fnn_argmax_labels``, ``fnn_revert_labels``); torch only owns the device buffers.  No CPU path.
 """
 from __future__ import annotations
 
@@ -61,6 +61,47 @@ def compute_new_shape(old_shape: Sequence[int], old_spacing: Sequence[float], ne
     """preprocessing/resampling/default_resampling.py:25-31 (python ``round``: half to even)."""
     assert len(old_spacing) == len(old_shape) and len(old_shape) == len(new_spacing)
     return [int(round(i / j * k)) for i, j, k in zip(old_spacing, new_spacing, old_shape)]
+
+
+DEFAULT_RESAMPLING_FN = 'resample_data_or_seg_to_shape'
+TORCH_RESAMPLING_FN = 'resample_torch_fornnunet'
+NO_RESAMPLING_FNS = ('no_resampling_data_or_seg_to_shape', 'no_resampling_hack')     # upstream's name, the reference's name
+_TORCH_KWARGS = ('is_seg', 'num_threads', 'device', 'memefficient_seg_resampling', 'force_separate_z',
+                 'separate_z_anisotropy_threshold', 'mode', 'aniso_axis_mode')
+
+
+def plan_resampling(fn_name: str, kwargs: Optional[dict], current_spacing, new_spacing) -> dict:
+    """Which resampling path a configuration's ``resampling_fn_*`` name and kwargs select - the whole decision, without
+    a GPU.  -> ``{'path': 'default'}`` (``resample_data_or_seg_to_shape``: the B-spline family, which reads its kwargs
+    itself), ``{'path': 'none'}`` (the no-resampling planners: data passes as it is) or, for
+    ``resample_torch_fornnunet`` (preprocessing/resampling/resample_torch.py:96-154),
+    ``{'path': 'torch', 'separate_axis': None | 0..2, 'memefficient': bool}``.  ``num_threads`` and ``device`` are
+    accepted and ignored; ``mode`` other than ``'linear'`` and ``aniso_axis_mode`` other than ``'nearest-exact'`` raise
+    NotImplementedError; any other function name raises RuntimeError.
+
+    The reference's separate-z branch cannot run: ``determine_do_sep_z_and_axis`` returns the axis as an integer and
+    the branch then calls ``len(axis)`` on it (TypeError).  This builds what the branch states, as upstream nnU-Net
+    does with that line fixed: linear in the plane, then nearest-exact along the axis."""
+    kwargs = dict(kwargs or {})
+    if fn_name == DEFAULT_RESAMPLING_FN:
+        return {'path': 'default'}
+    if fn_name in NO_RESAMPLING_FNS:
+        return {'path': 'none'}
+    if fn_name != TORCH_RESAMPLING_FN:
+        raise RuntimeError(f"Unable to find resampling function named '{fn_name}': this engine implements "
+                           f"{DEFAULT_RESAMPLING_FN}, {TORCH_RESAMPLING_FN} and {NO_RESAMPLING_FNS[0]}")
+    unknown = sorted(set(kwargs) - set(_TORCH_KWARGS))
+    if unknown:
+        raise TypeError(f'{TORCH_RESAMPLING_FN}() got unexpected keyword arguments {unknown}')
+    if kwargs.get('mode', 'linear') != 'linear':
+        raise NotImplementedError(f"{TORCH_RESAMPLING_FN}: mode={kwargs['mode']!r} (only 'linear' is implemented)")
+    if kwargs.get('aniso_axis_mode', 'nearest-exact') != 'nearest-exact':
+        raise NotImplementedError(f"{TORCH_RESAMPLING_FN}: aniso_axis_mode={kwargs['aniso_axis_mode']!r} "
+                                  f"(only 'nearest-exact' is implemented)")
+    do_sep, axis = determine_do_sep_z_and_axis(kwargs.get('force_separate_z', None), current_spacing, new_spacing,
+                                               kwargs.get('separate_z_anisotropy_threshold', ANISO_THRESHOLD))
+    return {'path': 'torch', 'separate_axis': int(axis) if do_sep else None,
+            'memefficient': bool(kwargs.get('memefficient_seg_resampling', False))}
 
 
 class DevicePreprocessor:
@@ -115,7 +156,8 @@ class DevicePreprocessor:
             # normalisation happens before resampling, like the reference (:83-91)
             out = self.resample(out, new_shape, original_spacing, target_spacing,
                                 getattr(configuration_manager, 'resampling_fn_data_kwargs', None) or
-                                {'is_seg': False, 'order': 3, 'order_z': 0, 'force_separate_z': None})
+                                {'is_seg': False, 'order': 3, 'order_z': 0, 'force_separate_z': None},
+                                getattr(configuration_manager, 'resampling_fn_data_name', DEFAULT_RESAMPLING_FN))
             seg_out = None
             if seg_in is not None:
                 sg = torch.as_tensor(seg_in).to(self.device)
@@ -124,16 +166,30 @@ class DevicePreprocessor:
                 sg = sg[(slice(None), *[slice(lo, hi) for lo, hi in bbox])].to(torch.int16).contiguous()
                 seg_out = self.resample_seg(sg, new_shape, original_spacing, target_spacing,
                                             getattr(configuration_manager, 'resampling_fn_seg_kwargs', None) or
-                                            {'is_seg': True, 'order': 1, 'order_z': 0, 'force_separate_z': None})
+                                            {'is_seg': True, 'order': 1, 'order_z': 0, 'force_separate_z': None},
+                                            getattr(configuration_manager, 'resampling_fn_seg_name', DEFAULT_RESAMPLING_FN))
         return out, seg_out, properties
 
     @torch.inference_mode()
-    def resample_seg(self, seg: torch.Tensor, new_shape, current_spacing, new_spacing, kwargs: dict) -> torch.Tensor:
+    def resample_seg(self, seg: torch.Tensor, new_shape, current_spacing, new_spacing, kwargs: dict,
+                     fn_name: str = DEFAULT_RESAMPLING_FN) -> torch.Tensor:
         """``resample_data_or_seg_to_shape(seg, ..., is_seg=True, order, order_z=0)`` (default_resampling.py:113-196)
         with ``resize_segmentation`` (batchgenerators): order 0 resizes the label image; otherwise every label's mask
         is resized (``fnn_resample``, the images' kernel) and the voxels where it reaches 0.5 take the label, labels
         ascending.  Thresholding commutes with the nearest-neighbour pass along an anisotropic axis, so the per-slice
-        path is the same call with ``separate_axis``.  ``[C, x, y, z]`` integer tensor -> int16 on the device."""
+        path is the same call with ``separate_axis``.  ``[C, x, y, z]`` integer tensor -> int16 on the device.
+        ``fn_name`` is the configuration's ``resampling_fn_seg`` (``plan_resampling``): ``resample_torch_fornnunet``
+        runs ``fnn_resample_torch_seg`` - one pass, the fp16-argmax rule or the ``memefficient_seg_resampling`` one."""
+        plan = plan_resampling(fn_name, kwargs, current_spacing, new_spacing)
+        if plan['path'] != 'default':
+            with torch.cuda.device(self.device):
+                sg = seg.to(device=self.device, dtype=torch.int16).contiguous()
+                if plan['path'] == 'none' or [int(i) for i in sg.shape[1:]] == [int(i) for i in new_shape]:
+                    return sg
+                out = torch.empty((sg.shape[0], *[int(i) for i in new_shape]), dtype=torch.int16, device=self.device)
+                capi.resample_torch(sg.data_ptr(), sg.shape, new_shape, plan['separate_axis'], False, out.data_ptr(),
+                                    self._stream(), is_seg=True, memefficient=plan['memefficient'])
+            return out
         if int(kwargs.get('order_z', 0)) != 0:
             raise NotImplementedError('order_z != 0 for segmentations (the reference\'s plans use 0)')
         new_shape = [int(i) for i in new_shape]
@@ -152,11 +208,30 @@ class DevicePreprocessor:
         return out
 
     @torch.inference_mode()
-    def resample(self, data: torch.Tensor, new_shape, current_spacing, new_spacing, kwargs: dict) -> torch.Tensor:
+    def resample(self, data: torch.Tensor, new_shape, current_spacing, new_spacing, kwargs: dict,
+                 fn_name: str = DEFAULT_RESAMPLING_FN) -> torch.Tensor:
         """``resample_data_or_seg_to_shape(data, new_shape, current_spacing, new_spacing, **kwargs)`` for images /
-        logits (``is_seg`` False): fp32 or fp16 ``[C, x, y, z]`` on the device."""
+        logits (``is_seg`` False): fp32 or fp16 ``[C, x, y, z]`` on the device.  ``fn_name`` is the configuration's
+        ``resampling_fn_data`` / ``resampling_fn_probabilities`` (``plan_resampling``): ``resample_torch_fornnunet``
+        runs ``fnn_resample_torch`` (one fused linear pass; output dtype = input dtype), the no-resampling name
+        returns the data as it is, an unknown name raises."""
         if kwargs.get('is_seg', False):
             raise ValueError('is_seg=True: call resample_seg')
+        plan = plan_resampling(fn_name, kwargs, current_spacing, new_spacing)
+        if plan['path'] == 'none':
+            return data
+        if plan['path'] == 'torch':
+            with torch.cuda.device(self.device):
+                x = data.to(self.device)
+                if x.dtype not in (torch.float32, torch.half):
+                    x = x.float()
+                x = x.contiguous()
+                if [int(i) for i in x.shape[1:]] == [int(i) for i in new_shape]:
+                    return x
+                out = torch.empty((x.shape[0], *[int(i) for i in new_shape]), dtype=x.dtype, device=self.device)
+                capi.resample_torch(x.data_ptr(), x.shape, new_shape, plan['separate_axis'], x.dtype == torch.half,
+                                    out.data_ptr(), self._stream())
+            return out
         do_sep, axis = determine_do_sep_z_and_axis(kwargs.get('force_separate_z', None), current_spacing, new_spacing,
                                                    kwargs.get('separate_z_anisotropy_threshold', ANISO_THRESHOLD))
         with torch.cuda.device(self.device):
@@ -181,8 +256,9 @@ class DevicePreprocessor:
             else [spacing_transposed[0], *target]
         kw = getattr(configuration_manager, 'resampling_fn_probabilities_kwargs', None) or \
             {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
+        fn = getattr(configuration_manager, 'resampling_fn_probabilities_name', DEFAULT_RESAMPLING_FN)
         logits = self.resample(predicted_logits, properties_dict['shape_after_cropping_and_before_resampling'],
-                               current_spacing, spacing_transposed, kw)
+                               current_spacing, spacing_transposed, kw, fn)
         seg = predictor.convert_logits_to_segmentation(logits)
         return self.revert_labels(seg, properties_dict, plans_manager, predictor.label_manager)
 
@@ -197,9 +273,10 @@ class DevicePreprocessor:
         current_spacing = target if len(target) == len(cropped) else [spacing_transposed[0], *target]
         kw = getattr(configuration_manager, 'resampling_fn_probabilities_kwargs', None) or \
             {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
+        fn = getattr(configuration_manager, 'resampling_fn_probabilities_name', DEFAULT_RESAMPLING_FN)
         logits = predicted_logits
         if [int(i) for i in logits.shape[1:]] != cropped:
-            logits = self.resample(logits, cropped, current_spacing, spacing_transposed, kw)
+            logits = self.resample(logits, cropped, current_spacing, spacing_transposed, kw, fn)
         return logits
 
     @torch.inference_mode()

@@ -323,6 +323,30 @@ typedef struct fnn_resample_desc {
 int fnn_resample(const void *in, const int64_t shape[4], const int64_t new_shape[3],
                  const fnn_resample_desc *desc, void *out, void *stream);
 
+/* resample_torch_fornnunet of the reference (preprocessing/resampling/resample_torch.py:96-154; additive in ABI 4), the
+ * resampling family its `resample_with_torch` planners write into plans.json: per channel
+ * torch.nn.functional.interpolate(x.float(), new_shape, mode='trilinear', antialias=False) - align_corners=False, all
+ * float32 - or, with separate_axis >= 0, bilinear in the plane and the 'nearest-exact' slice along the axis.  (The
+ * reference's own separate-z branch raises a TypeError before it computes anything; this is what the branch states.)
+ * One fused pass, no scratch memory, asynchronous on `stream`.  in / out: [C][...] of `dtype` (fp16 input is widened
+ * exactly, fp16 output is the float32 result rounded once), device pointers.  An axis with in == out is the identity.
+ * fnn_resample_torch_seg: int16 labels -> int16 labels by resample_torch_simple(is_seg=True) (:51-85): the label whose
+ * (seg == u) * 1000 interpolated and rounded to fp16 is largest, the smallest label on ties; with `memefficient` the
+ * label whose float32 interpolated (seg == u) exceeds 0.5, else 0.  `dtype` is ignored.
+ * FNN_E_UNSUPPORTED for a mode other than linear / an aniso_axis_mode other than nearest-exact. */
+enum { FNN_INTERP_LINEAR = 0, FNN_INTERP_NEAREST_EXACT = 1, FNN_INTERP_OTHER = 2 };
+typedef struct fnn_resample_torch_desc {
+    int32_t dtype;               /* FNN_OUT_F16 / FNN_OUT_F32                                  */
+    int32_t separate_axis;       /* -1, or the anisotropic axis                                */
+    int32_t memefficient;        /* segmentations: memefficient_seg_resampling                 */
+    int32_t mode;                /* FNN_INTERP_LINEAR (kwargs['mode'] = 'linear')              */
+    int32_t aniso_axis_mode;     /* FNN_INTERP_NEAREST_EXACT (kwargs['aniso_axis_mode'])       */
+} fnn_resample_torch_desc;
+int fnn_resample_torch(const void *in, const int64_t shape[4], const int64_t new_shape[3],
+                       const fnn_resample_torch_desc *desc, void *out, void *stream);
+int fnn_resample_torch_seg(const int16_t *in, const int64_t shape[4], const int64_t new_shape[3],
+                           const fnn_resample_torch_desc *desc, int16_t *out, void *stream);
+
 /* remove_all_but_largest_component_from_segmentation (postprocessing/remove_connected_components.py:21-33) for
  * disjoint label sets at once (additive in ABI 4): labels [X][Y][Z] (FNN_LABEL_U8 / U16, device pointer) is changed in
  * place.  group_of_label[v] (host, n_table entries) is the set of label value v, or -1; labels >= n_table are in no
