@@ -133,12 +133,7 @@ __global__ __launch_bounds__(256, HALF && NB == 1 ? 3 : 2) void conv2d_zp_kernel
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware, bijective remap (blocks b and b + 8 share an XCD): neighbouring tiles share halo rows in one L2
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = __builtin_amdgcn_readfirstlane((xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx);
-    }
+    int t = __builtin_amdgcn_readfirstlane(fnn_xcd_tile(gridDim.x, blockIdx.x));
     const int tile_in_item = __builtin_amdgcn_readfirstlane(t % (p.Do * p.tiles_h * p.tiles_w));
     const int tw = __builtin_amdgcn_readfirstlane(t % p.tiles_w); t = __builtin_amdgcn_readfirstlane(t / p.tiles_w);
     const int th = __builtin_amdgcn_readfirstlane(t % p.tiles_h); t = __builtin_amdgcn_readfirstlane(t / p.tiles_h);
@@ -190,8 +185,7 @@ __global__ __launch_bounds__(256, HALF && NB == 1 ? 3 : 2) void conv2d_zp_kernel
         ch_ok = c_uni + 8 * q_st < sC && stager;                        // (the upper half of a source's last 16-channel chunk does not exist)
         {
             const int cq = ch_ok ? c_uni + 8 * q_st : 0;
-            const unsigned short *q = p.src[s].ssh ? p.src[s].ssh + ((size_t)n * sC + cq) * 2 : p.ident_ssh + cq * 2;
-            const zp_u32x4 *qv = (const zp_u32x4 *)q;
+            const zp_u32x4 *qv = (const zp_u32x4 *)fnn_ssh_rows(p.src[s].ssh, sC, n, cq, p.ident_ssh);
             ssv[0] = qv[0]; ssv[1] = qv[1];
         }
         const unsigned piece = (unsigned)cg4 * (unsigned)(cs * 2) + (unsigned)half * 16u;
@@ -235,16 +229,14 @@ __global__ __launch_bounds__(256, HALF && NB == 1 ? 3 : 2) void conv2d_zp_kernel
                 const int row = u * RPP + rp;                 // scalar
                 if (NP * RPP > IH && row >= IH) continue;     // (WC = 1: the last pass is half empty)
                 const int gh = oh0 - 1 + row;
-                f16x8 o = __builtin_bit_cast(f16x8, xr[u]) * sc_h + sh_h;
-                o = __builtin_elementwise_max(o, o * slope_h);
+                f16x8 o = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xr[u]), sc_h, sh_h, slope_h);
                 if ((unsigned)gh >= (unsigned)p.Hi) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};      // scalar condition: a row above / below the tensor
                 if (stager) *(f16x8 *)(sA + row * ROWB + lds_main) = o;
             }
         }
         if (has_x) {
             const f16x8 sc_h = __builtin_bit_cast(f16x8, okx ? ssv[0] : zero4), sh_h = __builtin_bit_cast(f16x8, okx ? ssv[1] : zero4);
-            f16x8 o = __builtin_bit_cast(f16x8, xx) * sc_h + sh_h;
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xx), sc_h, sh_h, slope_h);
             *(f16x8 *)(sA + lds_x) = o;
         }
 #pragma unroll
@@ -426,12 +418,7 @@ __global__ __launch_bounds__(256, HALF ? 2 : 1) void conv2d_zps_kernel(const Con
     static_assert(IH <= 64, "the extra input column of every row fits the 64 threads of a channel group");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = __builtin_amdgcn_readfirstlane((xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx);
-    }
+    int t = __builtin_amdgcn_readfirstlane(fnn_xcd_tile(gridDim.x, blockIdx.x));
     const int tile_in_item = __builtin_amdgcn_readfirstlane(t % (p.Do * p.tiles_h * p.tiles_w));
     const int tw = __builtin_amdgcn_readfirstlane(t % p.tiles_w); t = __builtin_amdgcn_readfirstlane(t / p.tiles_w);
     const int th = __builtin_amdgcn_readfirstlane(t % p.tiles_h); t = __builtin_amdgcn_readfirstlane(t / p.tiles_h);
@@ -483,8 +470,7 @@ __global__ __launch_bounds__(256, HALF ? 2 : 1) void conv2d_zps_kernel(const Con
         ch_ok = c_uni + 8 * q_st < sC && stager;
         {
             const int cq = ch_ok ? c_uni + 8 * q_st : 0;
-            const unsigned short *q = p.src[s].ssh ? p.src[s].ssh + ((size_t)n * sC + cq) * 2 : p.ident_ssh + cq * 2;
-            const zp_u32x4 *qv = (const zp_u32x4 *)q;
+            const zp_u32x4 *qv = (const zp_u32x4 *)fnn_ssh_rows(p.src[s].ssh, sC, n, cq, p.ident_ssh);
             ssv[0] = qv[0]; ssv[1] = qv[1];
         }
         const unsigned piece = (unsigned)cg4 * (unsigned)(cs * 2) + (unsigned)half * 16u;
@@ -525,16 +511,14 @@ __global__ __launch_bounds__(256, HALF ? 2 : 1) void conv2d_zps_kernel(const Con
                 const int row = u * RPP + rp;
                 if (NP * RPP > IH && row >= IH) continue;
                 const int gh = 2 * oh0 - 1 + row;
-                f16x8 o = __builtin_bit_cast(f16x8, xr[u]) * sc_h + sh_h;
-                o = __builtin_elementwise_max(o, o * slope_h);
+                f16x8 o = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xr[u]), sc_h, sh_h, slope_h);
                 if ((unsigned)gh >= (unsigned)p.Hi) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
                 if (stager) *(f16x8 *)(sA + row * ROWB + lds_main) = o;
             }
         }
         if (has_x) {
             const f16x8 sc_h = __builtin_bit_cast(f16x8, okx ? ssv[0] : zero4), sh_h = __builtin_bit_cast(f16x8, okx ? ssv[1] : zero4);
-            f16x8 o = __builtin_bit_cast(f16x8, xx) * sc_h + sh_h;
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xx), sc_h, sh_h, slope_h);
             *(f16x8 *)(sA + lds_x) = o;
         }
 #pragma unroll

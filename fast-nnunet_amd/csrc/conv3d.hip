@@ -279,12 +279,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_lds_kernel(const ConvParams p) 
     constexpr int TD = MB == 2 ? 2 : MB;                   // output tile depth
 
     // XCD-aware, bijective remap (blocks b and b + 8 share an XCD)
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
-    }
+    int t = fnn_xcd_tile(gridDim.x, blockIdx.x);
     const int tw = t % p.tiles_w; t /= p.tiles_w;
     const int th = t % p.tiles_h; t /= p.tiles_h;
     const int td = t % p.tiles_d;
@@ -543,8 +538,7 @@ __global__ __launch_bounds__(256, (NB == 1 && MB == 4 && WRES && PF == 4) ? 3 : 
     int t_begin, t_end;
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int g = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        const int g = fnn_xcd_tile(nwg, bid);
         t_begin = (int)((long long)total_tiles * g / nwg);
         t_end = (int)((long long)total_tiles * (g + 1) / nwg);
     }
@@ -667,7 +661,7 @@ __global__ __launch_bounds__(256, (NB == 1 && MB == 4 && WRES && PF == 4) ? 3 : 
         slope_next = p.src[s].slope;
         // scale / shift first (vmcnt retires in order: commit() needs them before the first halo element) and
         // unconditionally: the identity table stands in for a source without InstanceNorm
-        const float *qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_loc : p.ident_ss + c_loc;
+        const float *qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_loc : p.ident_ss + c_loc;   // (fnn_ss_rows: one more spilled SGPR here)
         const float *qh = p.src[s].ss ? qs + sC : p.ident_ss + 512 + c_loc;
         scr[0] = *(const float4 *)qs; scr[1] = *(const float4 *)(qs + 4);
         shr[0] = *(const float4 *)qh; shr[1] = *(const float4 *)(qh + 4);
@@ -684,28 +678,13 @@ __global__ __launch_bounds__(256, (NB == 1 && MB == 4 && WRES && PF == 4) ? 3 : 
         const f16 slope_h = (f16)slope_next;
         const float sc[8] = {scr[0].x, scr[0].y, scr[0].z, scr[0].w, scr[1].x, scr[1].y, scr[1].z, scr[1].w};
         const float sh[8] = {shr[0].x, shr[0].y, shr[0].z, shr[0].w, shr[1].x, shr[1].y, shr[1].z, shr[1].w};
-#ifndef FNN_NORM_FP32
-        // x*scale+shift with scale and shift rounded to fp16 (v_pk_fma_f16): in fp32 (convert, fma, convert back) the
-        // staging's normalisation was 8 % of the benchmark's time.  Measured cost in accuracy: relative RMSE of the 64^3
-        // student 1.56e-3 -> 1.64e-3 against the 5e-3 limit.  `make NORM_FP32=1` builds the fp32 form.
-        f16x8 sc_h, sh_h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)sc[j]; sh_h[j] = (f16)sh[j]; }
-#endif
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
             if (u * 256 >= IVOX * 2) continue;                          // uniform: no thread has an element u
             // branch-free: with `if (offv >= 0)` around the arithmetic the waits for the prefetch sat in conditional
             // blocks, and hipcc then had to assume at the loop head that loads (and the stores behind them) were
             // still pending - it drained the previous tile's stores before every prefetch
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)xr[u][j], sc[j], sh[j]);
-#else
-            f16x8 o = xr[u] * sc_h + sh_h;                               // 4 x v_pk_fma_f16 instead of 16 instructions
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[u], sc, sh, slope_h);
             if (offv[u] < 0) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};             // the conv's zero padding
             const int rel_u = FNN_REL(u);
             const int zd = rel_u >> 16, zh = (rel_u >> 8) & 255, zw = rel_u & 255;

@@ -55,8 +55,7 @@ __global__ __launch_bounds__(256, CH == 1 ? (NBLK <= 8 ? 3 : 2) : (NBLK <= 8 ? 2
     int u_begin, u_end;
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int g = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        const int g = fnn_xcd_tile(nwg, bid);
         u_begin = (int)((long long)total_units * g / nwg);
         u_end = (int)((long long)total_units * (g + 1) / nwg);
     }
@@ -133,8 +132,8 @@ __global__ __launch_bounds__(256, CH == 1 ? (NBLK <= 8 ? 3 : 2) : (NBLK <= 8 ? 2
 #pragma unroll
         for (int pc = 0; pc < NPL; ++pc) {
             const SrcDesc &S = p.src[TCONV ? 1 : pc];
-            const float *qs = S.ss ? S.ss + (size_t)(2 * n) * 16 : p.ident_ss;
-            const float *qh = S.ss ? qs + 16 : p.ident_ss + 512;
+            const float *qs, *qh;
+            fnn_ss_rows(S.ss, 16, n, 0, p.ident_ss, qs, qh);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 sc_h[pc][j] = (f16)(cg ? qs[8 + j] : qs[j]);
@@ -144,8 +143,8 @@ __global__ __launch_bounds__(256, CH == 1 ? (NBLK <= 8 ? 3 : 2) : (NBLK <= 8 ? 2
         }
         if (TCONV) {
             const SrcDesc &S = tp.low;
-            const float *qs = S.ss ? S.ss + (size_t)(2 * n) * 32 : p.ident_ss;
-            const float *qh = S.ss ? qs + 32 : p.ident_ss + 512;
+            const float *qs, *qh;
+            fnn_ss_rows(S.ss, 32, n, 0, p.ident_ss, qs, qh);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 lsc[j] = q == 0 ? qs[j] : q == 1 ? qs[8 + j] : q == 2 ? qs[16 + j] : qs[24 + j];
@@ -384,8 +383,7 @@ __global__ __launch_bounds__(256, NBLK <= 8 ? 8 : 6) void stem_row_kernel(const 
     int u_begin, u_end;
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int g = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        const int g = fnn_xcd_tile(nwg, bid);
         u_begin = (int)((long long)total_units * g / nwg);
         u_end = (int)((long long)total_units * (g + 1) / nwg);
     }
@@ -584,8 +582,7 @@ __global__ __launch_bounds__(256, NBLK <= 8 ? 3 : 2) void conv_row_stem_kernel(c
     int u_begin, u_end;
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int g = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        const int g = fnn_xcd_tile(nwg, bid);
         u_begin = (int)((long long)total_units * g / nwg);
         u_end = (int)((long long)total_units * (g + 1) / nwg);
     }

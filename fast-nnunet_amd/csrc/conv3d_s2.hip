@@ -58,8 +58,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_s2_kernel(const ConvParams p, c
     int u_begin, u_end;
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int g = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        const int g = fnn_xcd_tile(nwg, bid);
         u_begin = (int)((long long)total_units * g / nwg);
         u_end = (int)((long long)total_units * (g + 1) / nwg);
     }
@@ -152,8 +151,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_s2_kernel(const ConvParams p, c
         i_sp = (const char *)(p.src[s].ptr + (size_t)n * p.Di * p.Hi * p.Wi * sC + (c_loc >> 4) * FNN_CS(p.src[s]) + (c_loc & 15));
         i_sc2 = FNN_VS(p.src[s]) * 2;                                    // activation layout: fnn_device.h, SrcDesc
         slope_next = p.src[s].slope;
-        i_qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_loc : p.ident_ss + c_loc;
-        i_qh = p.src[s].ss ? i_qs + sC : p.ident_ss + 512 + c_loc;
+        fnn_ss_rows(p.src[s].ss, sC, n, c_loc, p.ident_ss, i_qs, i_qh);
         i_wp = (const f16x8 *)p.wpk + (size_t)(grp * S2_NB * p.chunks + ch) * per_cb;
     };
     auto issue_part = [&](int ks) {                                      // k-step 0: scale / shift; 1 ..: halo element ks - 1 and weight element ks - 1
@@ -179,21 +177,9 @@ __global__ __launch_bounds__(512, 1) void conv3d_s2_kernel(const ConvParams p, c
         const f16 slope_h = (f16)slope_next;
         const float sc[8] = {scr[0].x, scr[0].y, scr[0].z, scr[0].w, scr[1].x, scr[1].y, scr[1].z, scr[1].w};
         const float sh[8] = {shr[0].x, shr[0].y, shr[0].z, shr[0].w, shr[1].x, shr[1].y, shr[1].z, shr[1].w};
-#ifndef FNN_NORM_FP32
-        f16x8 sc_h, sh_h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)sc[j]; sh_h[j] = (f16)sh[j]; }
-#endif
 #pragma unroll
         for (int u = 0; u < S2_PF; ++u) {
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)xr[u][j], sc[j], sh[j]);
-#else
-            f16x8 o = xr[u] * sc_h + sh_h;
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[u], sc, sh, slope_h);
             if (offv[u] < 0) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};       // the conv's zero padding
             const unsigned ldso = ((u & 1) ? ldp[u >> 1] >> 16 : ldp[u >> 1] & 0xffffu) << 4;
             if (u + 1 < S2_PF || has_last) *(f16x8 *)(sA + ldso) = o;

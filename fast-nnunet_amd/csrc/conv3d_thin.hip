@@ -486,8 +486,7 @@ __global__ __launch_bounds__(256, WPS) void conv_thin_kernel(const ThinParams tp
     int t_begin, t_end;
     {
         const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int g = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+        const int g = fnn_xcd_tile(nwg, bid);
         t_begin = (int)((long long)total_tiles * g / nwg);
         t_end = (int)((long long)total_tiles * (g + 1) / nwg);
     }
@@ -642,8 +641,8 @@ __global__ __launch_bounds__(256, WPS) void conv_thin_kernel(const ThinParams tp
         const int vs = FNN_VS(S);                                        // activation layout: fnn_device.h, SrcDesc
         const char *sp = (const char *)(S.ptr + (size_t)n * p.Di * p.Hi * p.Wi * sC + (c_loc >> 4) * FNN_CS(S) + (c_loc & 15));
         slope_next = S.slope;
-        const float *qs = S.ss ? S.ss + (size_t)(2 * n) * sC + c_loc : p.ident_ss + c_loc;
-        const float *qh = S.ss ? qs + sC : p.ident_ss + 512 + c_loc;
+        const float *qs, *qh;
+        fnn_ss_rows(S.ss, sC, n, c_loc, p.ident_ss, qs, qh);
         scr[0] = *(const float4 *)qs; scr[1] = *(const float4 *)(qs + 4);
         shr[0] = *(const float4 *)qh; shr[1] = *(const float4 *)(qh + 4);
         __builtin_amdgcn_sched_barrier(0);
@@ -654,21 +653,9 @@ __global__ __launch_bounds__(256, WPS) void conv_thin_kernel(const ThinParams tp
         const f16 slope_h = (f16)slope_next;
         const float sc[8] = {scr[0].x, scr[0].y, scr[0].z, scr[0].w, scr[1].x, scr[1].y, scr[1].z, scr[1].w};
         const float sh[8] = {shr[0].x, shr[0].y, shr[0].z, shr[0].w, shr[1].x, shr[1].y, shr[1].z, shr[1].w};
-#ifndef FNN_NORM_FP32
-        f16x8 sc_h, sh_h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)sc[j]; sh_h[j] = (f16)sh[j]; }
-#endif
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)xr[u][j], sc[j], sh[j]);
-#else
-            f16x8 o = xr[u] * sc_h + sh_h;
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[u], sc, sh, slope_h);
             if (offv[u] < 0) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
             const int zd = rel[u] >> 16, zh = (rel[u] >> 8) & 255, zw = rel[u] & 255;
             if (rel[u] >= 0) *(f16x8 *)(dst + ((zd * IH + zh) * TH_PW + zw) * 32 + ((cg ^ (zh & 1)) * 16)) = o;
@@ -732,8 +719,8 @@ __global__ __launch_bounds__(256, WPS) void conv_thin_kernel(const ThinParams tp
         const int cc = c0 < sC ? c0 : 0;
         const int vs = FNN_VS(S);
         const char *sp = (const char *)(S.ptr + (size_t)n * tp.Dl * tp.Hl * tp.Wl * sC + (cc >> 4) * FNN_CS(S) + (cc & 15));
-        const float *qs = S.ss ? S.ss + (size_t)(2 * n) * sC + cc : p.ident_ss + cc;
-        const float *qh = S.ss ? qs + sC : p.ident_ss + 512 + cc;
+        const float *qs, *qh;
+        fnn_ss_rows(S.ss, sC, n, cc, p.ident_ss, qs, qh);
         scr[0] = *(const float4 *)qs; scr[1] = *(const float4 *)(qs + 4);
         shr[0] = *(const float4 *)qh; shr[1] = *(const float4 *)(qh + 4);
         __builtin_amdgcn_sched_barrier(0);
@@ -753,8 +740,7 @@ __global__ __launch_bounds__(256, WPS) void conv_thin_kernel(const ThinParams tp
         const float sh[8] = {shr[0].x, shr[0].y, shr[0].z, shr[0].w, shr[1].x, shr[1].y, shr[1].z, shr[1].w};
 #pragma unroll
         for (int j = 0; j < NLBW; ++j) {                                 // no branch per block (see stem_to_image)
-            f16x8 o = fnn_norm8(xr[j], sc, sh);                          // load_act_frag's arithmetic (misc.hip)
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[j], sc, sh, slope_h);                              // load_act_frag's arithmetic (misc.hip)
             if (!(l_ok[j] & 1)) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int cls = 0; cls < NCLS; ++cls) {

@@ -24,21 +24,20 @@
 // Replaces the stride-1 ConvDropoutNormReLU blocks of the reference's PlainConvEncoder / UNetDecoder at that stage
 // (nnUNetDistillationTrainer.py:141-173).
 #include "fnn_device.h"
-#include "conv_common.h"
+#include "conv_zr_common.h"
 #include <cstdlib>
 
 namespace {
 
 typedef unsigned zq_u32x4 __attribute__((ext_vector_type(4)));
-typedef int zq_i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int ZQ_TD = 8, ZQ_ID = ZQ_TD + 2, ZQ_IH = 14, ZQ_IW = 14, ZQ_PW = 20;
-constexpr int ZQ_PS = ZQ_IH * ZQ_PW * 32;                       // bytes per halo plane (8960)
-constexpr int ZQ_ABYTES = ZQ_ID * ZQ_PS;                        // 89600
+constexpr int ZQ_TD = 8, ZQ_ID = ZQ_TD + 2, ZQ_IH = 14, ZQ_IW = 14;
+using Zq12Lds = Zr12Lds<ZQ_TD, 8>;                              // conv3d_zr12_kernel's image, ten planes; eight waves' reduction floats
+constexpr int ZQ_PW = Zq12Lds::PW, ZQ_PS = Zq12Lds::PS;         // bytes per halo plane (8960)
+constexpr int ZQ_ABYTES = Zq12Lds::image;                       // 89600
 constexpr int ZQ_KS = 15, ZQ_WB = ZQ_KS * 64;                   // 16-byte weight elements per cout block and chunk (960)
 constexpr int ZQ_NT = 512, ZQ_NB = 2;
-constexpr int ZQ_WBYTES = ZQ_NB * ZQ_KS * 1024;                 // 30720
-constexpr int ZQ_LDS = ZQ_ABYTES + ZQ_WBYTES + 8 * 32 * 2 * 4;  // + the statistics' reduction floats
+constexpr int ZQ_WBYTES = Zq12Lds::weights;                     // 30720
 
 __global__ __launch_bounds__(512, 2) void conv3d_zq12_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -87,8 +86,7 @@ __global__ __launch_bounds__(512, 2) void conv3d_zq12_kernel(const ConvParams p)
         rx = __builtin_amdgcn_make_buffer_rsrc((void *)sp, 0, item_bytes, 0x00020000);
         slope_next = p.src[s].slope;
         {
-            const unsigned short *q = p.src[s].ssh ? p.src[s].ssh + ((size_t)n * sC + c_uni) * 2 : p.ident_ssh + c_uni * 2;
-            const zq_u32x4 *qv = (const zq_u32x4 *)(q + cg * 16);
+            const zq_u32x4 *qv = (const zq_u32x4 *)(fnn_ssh_rows(p.src[s].ssh, sC, n, c_uni, p.ident_ssh) + cg * 16);
             ssv[0] = qv[0]; ssv[1] = qv[1];
         }
         voff = ok_hw ? (unsigned)hw_lin * (unsigned)(vs * 2) + cg * 16 : 0x80000000u;
@@ -118,24 +116,13 @@ __global__ __launch_bounds__(512, 2) void conv3d_zq12_kernel(const ConvParams p)
     };
     auto commit = [&]() {
         const f16 slope_h = (f16)slope_next;
-        // x * scale + shift with scale and shift in fp16 (v_pk_fma_f16: fnn_norm8's arithmetic); a column outside the tensor:
-        // 0 * 0 + 0 = the conv's zero padding
+        // scale and shift in fp16 (fnn_norm_leaky8); a column outside the tensor: 0 * 0 + 0 = the conv's zero padding
         const zq_u32x4 zero4 = {0u, 0u, 0u, 0u};
         const f16x8 sc_h = __builtin_bit_cast(f16x8, ok_hw ? ssv[0] : zero4), sh_h = __builtin_bit_cast(f16x8, ok_hw ? ssv[1] : zero4);
         if (has_col) {
 #pragma unroll
-            for (int u = 0; u < ZQ_ID; ++u) {
-                const f16x8 x = __builtin_bit_cast(f16x8, xr[u]);
-#ifdef FNN_NORM_FP32
-                f16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)x[j], (float)sc_h[j], (float)sh_h[j]);
-#else
-                f16x8 o = x * sc_h + sh_h;
-#endif
-                o = __builtin_elementwise_max(o, o * slope_h);
-                *(f16x8 *)(sA + ldso0 + u * ZQ_PS) = o;
-            }
+            for (int u = 0; u < ZQ_ID; ++u)
+                *(f16x8 *)(sA + ldso0 + u * ZQ_PS) = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xr[u]), sc_h, sh_h, slope_h);
             if (pmask != (1u << ZQ_ID) - 1) {                  // border tiles along d: planes outside the tensor
                 unsigned pm = pmask;
                 asm volatile("" : "+s"(pm));
@@ -151,18 +138,10 @@ __global__ __launch_bounds__(512, 2) void conv3d_zq12_kernel(const ConvParams p)
         }
     };
 
-    // MFMA "B" operand of block 0 of the plane: lane = (voxel r of the 4 x 4 block, k-group): bit 1 of the k-group picks the
-    // tap of the pair, bit 0 the 8-channel half; + this wave's first halo plane.  A block's own offset is a scalar.
+    // MFMA "B" operand of block 0 of the plane (lane = voxel r of the 4 x 4 block) + this wave's first halo plane.  A block's
+    // own offset is a scalar.
     int toff[5];
-    {
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;   // padded slot: any finite data (its weights are 0)
-            const int row = (r >> 2) + tp / 3, cl = (r & 3) + tp % 3;
-            toff[pr] = (row * ZQ_PW + cl) * 32 + ((kh ^ (row & 1)) * 16) + dq * 2 * ZQ_PS;
-        }
-    }
+    zr_tap_offsets<ZQ_PW, true>(toff, lane, [](int r) { return r >> 2; }, [](int r) { return r & 3; }, dq * 2 * ZQ_PS);
     int boff[5];                                               // (4 bh rows: an even number, the swap parity is the lane's)
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
@@ -239,41 +218,11 @@ __global__ __launch_bounds__(512, 2) void conv3d_zq12_kernel(const ConvParams p)
         for (int nb = 0; nb < ZQ_NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        const unsigned item_bytes = (unsigned)p.Do * p.Ho * p.Wo * p.Cout * 2;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)n * (item_bytes >> 1), 0, item_bytes, 0x00020000);
-        const unsigned ovs2 = (unsigned)FNN_OVS(p) * 2;
-        const unsigned coff = (unsigned)(cb0 + (q >> 1)) * (unsigned)(FNN_OCS(p) * 2) + (unsigned)(q & 1) * 16;   // output layout: fnn_device.h
-        const f16x2 ones = {(f16)1.f, (f16)1.f};
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             if (i == 4 && nblk == 4) break;
             const int b = b0 + i, bh = (b * 11) >> 5, bw = b - bh * 3;
-            const int oh = 4 * bh + (r >> 2), ow = 4 * bw + (r & 3);
-            const bool ok_o = oh < p.Ho && ow < p.Wo;
-            f16x8 o[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int od = od0 + 2 * dq + h;
-                const bool ok = ok_o && od < p.Do;
-                const unsigned vo = ok ? (unsigned)((od * p.Ho + oh) * p.Wo + ow) * ovs2 + coff : 0x80000000u;
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    o[h][nb * 4 + 0] = (f16)(acc[i][h][nb][0] + bv[nb].x);
-                    o[h][nb * 4 + 1] = (f16)(acc[i][h][nb][1] + bv[nb].y);
-                    o[h][nb * 4 + 2] = (f16)(acc[i][h][nb][2] + bv[nb].z);
-                    o[h][nb * 4 + 3] = (f16)(acc[i][h][nb][3] + bv[nb].w);
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(zq_i32x4, o[h]), rsrc, vo, 0, 0);
-                if (!ok) o[h] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f16x2 pr2 = {o[0][nb * 4 + j], o[1][nb * 4 + j]};
-                    t1[nb][j] = __builtin_amdgcn_fdot2(pr2, ones, t1[nb][j], false);
-                    t2[nb][j] = __builtin_amdgcn_fdot2(pr2, pr2, t2[nb][j], false);
-                }
+            zr_epilogue_pair<2>(p, acc[i], bv, n, od0 + 2 * dq, 4 * bh + (r >> 2), 4 * bw + (r & 3), cb0, lane, t1, t2);
         }
         if (p.stats_out) {
 #pragma unroll
@@ -318,5 +267,5 @@ int launch_conv3d_zq12(ConvParams p, hipStream_t st) {
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     dim3 grid(p.N * p.tiles_d, (p.Cout / 16) / ZQ_NB);
-    return fnn_launch_lds<conv3d_zq12_kernel>(grid, dim3(ZQ_NT), ZQ_LDS, st, p);
+    return fnn_launch_lds<conv3d_zq12_kernel>(grid, dim3(ZQ_NT), Zq12Lds::bytes(), st, p);
 }

@@ -17,103 +17,9 @@
 // nnUNetDistillationTrainer.py:141-173).
 #include "fnn_device.h"
 #include "conv_common.h"
+#include "conv_zr_common.h"
 #include <type_traits>
-#include <algorithm>
-#include <cmath>
 #include <cstdlib>
-#include <vector>
-
-int conv3d_ksteps(int packing, int taps) {
-    return packing == FNN_PACK_ZR || packing == FNN_PACK_ZRP ? 15 : packing == FNN_PACK_ZP ? 9 : (taps + 1) / 2;
-}
-
-int conv3d_kstep_tap(int packing, int ks, int half, int taps, int ch, int chunks, int *tch) {
-    *tch = ch;
-    if (packing == FNN_PACK_ZR || packing == FNN_PACK_ZRP) {
-        const int pr = ks / 3, dz = ks % 3;
-        if (pr < 4) return dz * 9 + 2 * pr + half;
-        // k-steps 12 .. 14: the leftover in-plane tap 8 - padded in FNN_PACK_ZR and in FNN_PACK_ZRP's unpaired last chunk,
-        // shared by the two chunks of a pair in FNN_PACK_ZRP (in the pair's second chunk; the first chunk's are zeros)
-        if (packing == FNN_PACK_ZR || (ch % 2 == 0 && ch + 1 == chunks)) return half ? -1 : dz * 9 + 8;
-        if (ch % 2 == 0) return -1;
-        *tch = ch - 1 + half;
-        return dz * 9 + 8;
-    }
-    const int t = 2 * ks + half;
-    return t < taps ? t : -1;
-}
-
-// Output channel that row m of cout block cb of the packed weights computes.  The ZR kernels at two cout blocks per
-// workgroup (an even block count) interleave the two blocks' rows in groups of four: MFMA lane quarter q then holds
-// channels q * 8 .. q * 8 + 7 of a voxel (4 from each block) = ONE 16-byte store, and four lanes cover the 64 bytes of a
-// 32-channel group - half the store instructions of the 8-byte form, whole 64-byte runs (the stores of this kernel
-// delayed the next workgroup's loads in the texture-address path: a timing-only build without them ran 14 % faster).
-int conv3d_pack_cout(int packing, int nblk, int cb, int m) {
-    if ((packing != FNN_PACK_ZR && packing != FNN_PACK_ZRP && packing != FNN_PACK_ZP) || nblk % 2 != 0) return cb * 16 + m;
-    return (cb >> 1) * 32 + (m >> 2) * 8 + (cb & 1) * 4 + (m & 3);
-}
-
-size_t conv_packed_halves(const ConvChoice &c, int cout_pad) { return (size_t)(cout_pad / 16) * c.chunks * c.ksteps * 512; }
-
-uint8_t f2e4m3(float f) {
-    const uint8_t sign = std::signbit(f) ? 0x80 : 0;
-    float a = std::fabs(f);
-    if (!(a == a)) return sign | 0x7f;
-    if (a >= 448.f) return sign | 0x7e;
-    if (a < 0x1p-6f) {                                          // subnormal: multiples of 2^-9
-        const int q = (int)std::nearbyint(a * 512.f);           // 0 .. 8 (8 = the smallest normal)
-        return sign | (uint8_t)q;                               // q = 8 -> exponent field 1, mantissa 0 = 0x08
-    }
-    int e;
-    const float m = std::frexp(a, &e);                          // a = m * 2^e, m in [0.5, 1)
-    int q = (int)std::nearbyint(m * 16.f);                      // 8 .. 16
-    int E = e - 1;                                              // a = (q / 8) * 2^E
-    if (q == 16) { q = 8; ++E; }
-    if (E > 8 || (E == 8 && q > 14)) return sign | 0x7e;
-    return sign | (uint8_t)(((E + 7) << 3) | (q - 8));
-}
-
-// One loop over the fragment order for every packing but FNN_PACK_ZP; the element encoding is the only difference between
-// fp16 and fp8 (one scale per output channel: max |w| of the channel -> 448)
-void conv_pack_weights(const ConvParams &p, const ConvChoice &c, int cout_real, const int cin_real[2], const float *W, void *dst,
-                       float *scales) {
-    const int cin_real1 = p.n_src > 1 ? cin_real[1] : 0, cin_pad0 = p.src[0].C;
-    if (c.packing == FNN_PACK_ZP) {
-        conv_zp_pack(W, cout_real, p.Cout, cin_real[0], cin_pad0, cin_real1, p.n_src > 1 ? p.src[1].C : 0, (unsigned short *)dst);
-        return;
-    }
-    const int T = p.kd * p.kh * p.kw, cin_tot = cin_real[0] + cin_real1, nblk = p.Cout / 16;
-    std::vector<float> inv(p.Cout, 1.f);
-    if (p.fp8)
-        for (int co = 0; co < p.Cout; ++co) {
-            float mx = 0.f;
-            if (co < cout_real)
-                for (size_t i = 0; i < (size_t)cin_tot * T; ++i) mx = std::max(mx, std::fabs(W[(size_t)co * cin_tot * T + i]));
-            float ws = mx / 448.f, iv = 1.f / ws;
-            // an all-zero cout, or one whose max |w| < ~1.3e-36 makes ws subnormal and 1 / ws infinite (0 * inf = NaN): zero
-            // weights, as the fp16 encoding rounds them
-            if (!(mx > 0.f) || !std::isfinite(iv)) { ws = 1.f; iv = 0.f; }
-            inv[co] = iv;
-            scales[co] = ws / FNN_FP8_ACT_MULT;
-        }
-    for (int cb = 0; cb < nblk; ++cb)
-        for (int ch = 0; ch < c.chunks; ++ch)
-            for (int ks = 0; ks < c.ksteps; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 8 * (lane >> 4) + j;
-                        int tch;
-                        const int tap = conv3d_kstep_tap(c.packing, ks, k >> 4, T, ch, c.chunks, &tch), ci = tch * 16 + (k & 15);
-                        const int co = conv3d_pack_cout(c.packing, nblk, cb, lane & 15);
-                        const int src = ci >= cin_pad0, cl = src ? ci - cin_pad0 : ci;
-                        float v = 0.f;
-                        if (tap >= 0 && co < cout_real && cl < (src ? cin_real1 : cin_real[0]))
-                            v = W[((size_t)co * cin_tot + (src ? cin_real[0] : 0) + cl) * T + tap] * inv[co];
-                        const size_t i = ((((size_t)cb * c.chunks + ch) * c.ksteps + ks) * 64 + lane) * 8 + j;
-                        if (p.fp8) ((uint8_t *)dst)[i] = f2e4m3(v);
-                        else ((unsigned short *)dst)[i] = fnn_half_bits(v);
-                    }
-}
 
 // The depth-shift kernels (FNN_PACK_ZR: 15 k-steps, one statistics row per tile): 3x3x3 layers of depth stride 1 with
 // enough workgroups to fill the chip - in-plane stride 2 on the ZS kernels, stride 1 on the ZR kernels.  false: the layer
@@ -208,54 +114,6 @@ bool zr_choose(const ConvParams &p, const ConvOverrides &o, ConvChoice &c) {
     return true;
 }
 
-// Epilogue of a ZR tile at NB = 2 in the interleaved channel order of conv3d_pack_cout: bias (after `osc` for the fp8
-// form), round to fp16, one 16-byte channels-last store per (voxel, lane), statistics as in tile_epilogue (conv_common.h).
-typedef int fnn_i32x4 __attribute__((ext_vector_type(4)));
-template <int TD, bool BIAS = true>
-static __device__ __forceinline__ void zr_epilogue_pair(const ConvParams &p, const f32x4 (&acc)[TD][2], const float4 (&bv)[2],
-                                                        int n, int od0, int oh0, int ow0, int cb0, int wave, int lane,
-                                                        float (&t1)[2][4], float (&t2)[2][4]) {
-    const int q = lane >> 4, r = lane & 15;
-    const unsigned item_bytes = (unsigned)p.Do * p.Ho * p.Wo * p.Cout * 2;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)n * (item_bytes >> 1), 0,
-                                                                           item_bytes, 0x00020000);
-    const unsigned ovs2 = (unsigned)FNN_OVS(p) * 2;
-    const unsigned coff = (unsigned)(cb0 + (q >> 1)) * (unsigned)(FNN_OCS(p) * 2) + (unsigned)(q & 1) * 16;   // output layout: fnn_device.h
-    const int oh = oh0 + 2 * wave + (r >> 3), ow = ow0 + (r & 7);
-    const bool ok_hw = oh < p.Ho && ow < p.Wo;
-    const f16x2 ones = {(f16)1.f, (f16)1.f};
-#pragma unroll
-    for (int mb = 0; mb < TD; mb += 2) {
-        f16x8 o[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int od = od0 + mb + h;
-            const bool ok = ok_hw && od < p.Do;
-            unsigned voff = ok ? (unsigned)((od * p.Ho + oh) * p.Wo + ow) * ovs2 + coff : 0x80000000u;
-#ifdef FNN_TMODE
-            if (p.tmode & 4) voff = 0x80000000u;
-#endif
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                o[h][nb * 4 + 0] = (f16)(BIAS ? acc[mb + h][nb][0] + bv[nb].x : acc[mb + h][nb][0]);
-                o[h][nb * 4 + 1] = (f16)(BIAS ? acc[mb + h][nb][1] + bv[nb].y : acc[mb + h][nb][1]);
-                o[h][nb * 4 + 2] = (f16)(BIAS ? acc[mb + h][nb][2] + bv[nb].z : acc[mb + h][nb][2]);
-                o[h][nb * 4 + 3] = (f16)(BIAS ? acc[mb + h][nb][3] + bv[nb].w : acc[mb + h][nb][3]);
-            }
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fnn_i32x4, o[h]), rsrc, voff, 0, 0);
-            if (!ok) o[h] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f16x2 pr = {o[0][nb * 4 + j], o[1][nb * 4 + j]};
-                t1[nb][j] = __builtin_amdgcn_fdot2(pr, ones, t1[nb][j], false);
-                t2[nb][j] = __builtin_amdgcn_fdot2(pr, pr, t2[nb][j], false);
-            }
-    }
-}
-
 // Staging (round 3): a thread owns one COLUMN of the halo - (row zh, column zw, 8-channel half cg), 200 of the 256
 // threads - and walks the TD + 2 planes.  Everything that used to be a per-element table (16 registers and ~35 VALU
 // instructions per element to build: 43 % of the kernel's vector instructions sat in front of the first load) is now
@@ -275,21 +133,16 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
     FNN_STAMP_DECL
     FNN_STAMP();                                              // 0: entry
     constexpr int NT = TH * 32;                               // threads: one wave per pair of tile rows
-    constexpr int IH = TH + 2, IW = 10, PW = 12, ID = TD + 2;   // halo tile, row pitch 12 = 4 (mod 8) voxels
-    constexpr int PS = IH * PW * 32;                          // bytes per halo plane
-    constexpr int ABYTES = ID * PS;                           // no rounding: at TD = 4 the workgroup is 42 LDS granules (3 per CU)
+    using L = ZrLds<NB, TD, TH>;
+    constexpr int IH = TH + 2, IW = 10, PW = L::PW, ID = TD + 2;   // halo tile
+    constexpr int PS = L::PS, ABYTES = L::image;
     constexpr int KS = 15;
     constexpr int WB = KS * 64;                               // 16-byte weight elements per cout block and chunk
     constexpr int WPB = (WB + NT - 1) / NT;                   // loads per thread and cout block (256 threads: the last one by waves 0 .. 2 only)
     static_assert(WB - (WPB - 1) * NT == 192, "the last weight element group covers exactly waves 0 .. 2");
 
     // XCD-aware, bijective remap (blocks b and b + 8 share an XCD)
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = __builtin_amdgcn_readfirstlane((xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx);
-    }
+    int t = __builtin_amdgcn_readfirstlane(fnn_xcd_tile(gridDim.x, blockIdx.x));
     const int tw = __builtin_amdgcn_readfirstlane(t % p.tiles_w); t = __builtin_amdgcn_readfirstlane(t / p.tiles_w);
     const int th = __builtin_amdgcn_readfirstlane(t % p.tiles_h); t = __builtin_amdgcn_readfirstlane(t / p.tiles_h);
     const int td = __builtin_amdgcn_readfirstlane(t % p.tiles_d);
@@ -350,14 +203,13 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
         rx = __builtin_amdgcn_make_buffer_rsrc((void *)sp, 0, item_bytes, 0x00020000);
         slope_next = p.src[s].slope;
 #ifdef FNN_NORM_FP32
-        const float *qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_uni : p.ident_ss + c_uni;
-        const float *qh = p.src[s].ss ? qs + sC : p.ident_ss + 512 + c_uni;
+        const float *qs, *qh;
+        fnn_ss_rows(p.src[s].ss, sC, n, c_uni, p.ident_ss, qs, qh);
 #pragma unroll
         for (int j = 0; j < 16; ++j) { scu[j] = qs[j]; shu[j] = qh[j]; }
 #else
         {
-            const unsigned short *q = p.src[s].ssh ? p.src[s].ssh + ((size_t)n * sC + c_uni) * 2 : p.ident_ssh + c_uni * 2;
-            const fnn_u32x4v *qv = (const fnn_u32x4v *)(q + cg * 16);
+            const fnn_u32x4v *qv = (const fnn_u32x4v *)(fnn_ssh_rows(p.src[s].ssh, sC, n, c_uni, p.ident_ssh) + cg * 16);
             ssv[0] = qv[0]; ssv[1] = qv[1];
         }
 #endif
@@ -404,29 +256,19 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
             sh[j] = ok_hw ? (cg ? shu[8 + j] : shu[j]) : 0.f;
         }
 #else
-        // x*scale+shift with scale and shift rounded to fp16 (v_pk_fma_f16): in fp32 (convert, fma, convert back) the
-        // staging's normalisation was 8 % of the benchmark's time.  Measured cost in accuracy: relative RMSE of the 64^3
-        // student 1.56e-3 -> 1.64e-3 against the 5e-3 limit.  `make NORM_FP32=1` builds the fp32 form.
-        // A column outside the tensor: 0 * 0 + 0 = the conv's zero padding.
+        // scale and shift in fp16 (fnn_norm_leaky8, conv_common.h).  A column outside the tensor: 0 * 0 + 0 = the conv's zero padding.
         const fnn_u32x4v zero4 = {0u, 0u, 0u, 0u};
-        const f16x8 sc_h = __builtin_bit_cast(f16x8, ok_hw ? ssv[0] : zero4), sh_h = __builtin_bit_cast(f16x8, ok_hw ? ssv[1] : zero4);
+        const f16x8 sc = __builtin_bit_cast(f16x8, ok_hw ? ssv[0] : zero4), sh = __builtin_bit_cast(f16x8, ok_hw ? ssv[1] : zero4);
 #endif
         if (has_col) {
 #pragma unroll
-            for (int u = 0; u < ID; ++u) {
-                const f16x8 x = __builtin_bit_cast(f16x8, xr[u]);
-#ifdef FNN_NORM_FP32
-                f16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)x[j], sc[j], sh[j]);
-#else
-                f16x8 o = x * sc_h + sh_h;                                   // 4 x v_pk_fma_f16 instead of 16 instructions
-#endif
-                o = __builtin_elementwise_max(o, o * slope_h);
-                *(f16x8 *)(sA + ldso0 + u * PS) = o;
-            }
+            for (int u = 0; u < ID; ++u)
+                *(f16x8 *)(sA + ldso0 + u * PS) = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xr[u]), sc, sh, slope_h);
             if (pmask != (1u << ID) - 1) {                    // border tiles along d: planes outside the tensor (a clamped plane's data were written above)
                 unsigned pm = pmask;
+#ifdef FNN_NORM_FP32
+                pm = __builtin_amdgcn_readfirstlane(pm);      // (in this build pmask arrives here in a VGPR: "illegal VGPR to SGPR copy")
+#endif
                 asm volatile("" : "+s"(pm));                  // (hoisted out of the chunk loop the tests become lane masks: 20 SGPRs, spilled)
 #pragma unroll
                 for (int u = 0; u < ID; ++u)
@@ -467,18 +309,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
 #pragma unroll
                 for (int pl = 0; pl < ID; ++pl) xf[pl] = khalf1 ? xf[pl] : xl[pl];
             }
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                f16x8 wf[NB];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) wf[nb] = *(const f16x8 *)(sW + ((nb * KS + pr * 3 + dz) * 64 + lane) * 16);
-#pragma unroll
-                for (int j = 0; j < TD; ++j)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb], xf[j + dz], acc[j][nb], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);                // keep the next pair's reads from being hoisted: registers
+            zr_pair_mfma<TD, NB, KS>(acc, xf, sW, pr, lane);
         }
     };
     prep(0);
@@ -499,7 +330,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
             for (int nb = 0; nb < NB; ++nb) acc[j][nb] = b0[nb];
     }
     // MFMA "B" operand: lane = (voxel r of the wave's two rows, k-group): k-group bit 1 picks the tap of the pair,
-    // bit 0 the 8-channel half
+    // bit 0 the 8-channel half.  (zr_tap_offsets' text, kept here: through the helper <1, 8> took 168 instead of 165 VGPRs)
     {
         const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
 #pragma unroll
@@ -560,7 +391,7 @@ __global__ __launch_bounds__(TH * 32, 2) void conv3d_zr_kernel(const ConvParams 
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        if constexpr (NB == 2) zr_epilogue_pair<TD, false>(p, acc, bv, n, od0, oh0, ow0, cb0, wave, lane, t1, t2);
+        if constexpr (NB == 2) zr_epilogue_pair<TD, false>(p, acc, bv, n, od0, oh0 + 2 * wave + ((lane & 15) >> 3), ow0 + (lane & 7), cb0, lane, t1, t2);
         else tile_epilogue<NB, TD, true, false>(p, acc, bv, n, od0, oh0, ow0, cb0, wave, lane, t1, t2);
         if (p.stats_out) stats_to_global<NB, true, NB == 2, TH / 2>(p, t1, t2, (float *)smem, n, cb0, wave, lane, tid, (td * p.tiles_h + th) * p.tiles_w + tw);
     }
@@ -587,15 +418,11 @@ template <int NB>
 __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void conv3d_zrw_kernel(const ConvParams p, const int segs, const int tps) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int TD = 8, IH = 10, IW = 10, PW = 12, ID = TD + 2;
-    constexpr int PS = IH * PW * 32, ABYTES = ID * PS, KS = 15, WB = KS * 64, WPB = (WB + 255) / 256;
+    using L = ZrLds<NB, 8>;
+    constexpr int TD = 8, IH = 10, IW = 10, PW = L::PW, ID = TD + 2;
+    constexpr int PS = L::PS, ABYTES = L::image, KS = 15, WB = KS * 64, WPB = (WB + 255) / 256;
 
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = __builtin_amdgcn_readfirstlane((xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx);
-    }
+    int t = __builtin_amdgcn_readfirstlane(fnn_xcd_tile(gridDim.x, blockIdx.x));
     const int tw = __builtin_amdgcn_readfirstlane(t % p.tiles_w); t = __builtin_amdgcn_readfirstlane(t / p.tiles_w);
     const int th = __builtin_amdgcn_readfirstlane(t % p.tiles_h); t = __builtin_amdgcn_readfirstlane(t / p.tiles_h);
     const int seg = __builtin_amdgcn_readfirstlane(t % segs);
@@ -629,18 +456,17 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void conv3d_zrw_kernel(const 
 #ifdef FNN_NORM_FP32
     float sc[8], sh[8];
     {
-        const float *qs = p.src[0].ss ? p.src[0].ss + (size_t)(2 * n) * sC : p.ident_ss;
-        const float *qh = p.src[0].ss ? qs + sC : p.ident_ss + 512;
+        const float *qs, *qh;
+        fnn_ss_rows(p.src[0].ss, sC, n, 0, p.ident_ss, qs, qh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sc[j] = ok_hw ? qs[cg * 8 + j] : 0.f; sh[j] = ok_hw ? qh[cg * 8 + j] : 0.f; }
     }
 #else
-    f16x8 sc_h, sh_h;
+    f16x8 sc, sh;
     {
-        const unsigned short *q = p.src[0].ssh ? p.src[0].ssh + (size_t)n * sC * 2 : p.ident_ssh;
-        const fnn_u32x4v *qv = (const fnn_u32x4v *)(q + cg * 16);
+        const fnn_u32x4v *qv = (const fnn_u32x4v *)(fnn_ssh_rows(p.src[0].ssh, sC, n, 0, p.ident_ssh) + cg * 16);
         const fnn_u32x4v zero4 = {0u, 0u, 0u, 0u};
-        sc_h = __builtin_bit_cast(f16x8, ok_hw ? qv[0] : zero4); sh_h = __builtin_bit_cast(f16x8, ok_hw ? qv[1] : zero4);
+        sc = __builtin_bit_cast(f16x8, ok_hw ? qv[0] : zero4); sh = __builtin_bit_cast(f16x8, ok_hw ? qv[1] : zero4);
     }
 #endif
 
@@ -660,15 +486,7 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void conv3d_zrw_kernel(const 
 #pragma unroll
         for (int u = 0; u < ID; ++u) {
             if (u < u0) continue;
-            const f16x8 x = __builtin_bit_cast(f16x8, xr[u]);
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)x[j], sc[j], sh[j]);
-#else
-            f16x8 o = x * sc_h + sh_h;
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xr[u]), sc, sh, slope_h);
             const int gd = td * TD - 1 + u;                   // (scalar)
             if ((unsigned)gd >= (unsigned)p.Di) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
             *(f16x8 *)(sA + ldso0 + ((k0 + u) % ID) * PS) = o;
@@ -681,25 +499,7 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void conv3d_zrw_kernel(const 
         int roff[ID];                                         // (scalars) where the tile's ten planes sit in the ring
 #pragma unroll
         for (int pl = 0; pl < ID; ++pl) roff[pl] = ((k0 + pl) % ID) * PS;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const char *bp = sA + toff[pr];
-            f16x8 xf[ID];
-#pragma unroll
-            for (int pl = 0; pl < ID; ++pl) xf[pl] = *(const f16x8 *)(bp + roff[pl]);
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                f16x8 wf[NB];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) wf[nb] = *(const f16x8 *)(sW + ((nb * KS + pr * 3 + dz) * 64 + lane) * 16);
-#pragma unroll
-                for (int j = 0; j < TD; ++j)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb], xf[j + dz], acc[j][nb], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        zr_kloop<TD, NB, KS>(acc, sA, toff, sW, lane, [&](int pl) { return roff[pl]; });
     };
 
     // ---- prologue: the first tile's ten planes and the weights
@@ -716,15 +516,7 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void conv3d_zrw_kernel(const 
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
         b0[nb] = *(const f32x4 *)(p.bias + cb0 * 16 + (NB == 2 ? (lane >> 4) * 8 + nb * 4 : nb * 16 + (lane >> 4) * 4));
-    {
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;
-            const int row = 2 * wave + (r >> 3) + tp / 3, col2 = (r & 7) + tp % 3;
-            toff[pr] = (row * PW + col2) * 32 + ((kh ^ (row & 1)) * 16);
-        }
-    }
+    zr_tap_offsets<PW, true>(toff, lane, [=](int r) { return 2 * wave + (r >> 3); }, [](int r) { return r & 7; });
     stage(td0, 0);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
@@ -742,7 +534,7 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void conv3d_zrw_kernel(const 
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        if constexpr (NB == 2) zr_epilogue_pair<TD, false>(p, acc, bv, n, td * TD, oh0, ow0, cb0, wave, lane, t1, t2);
+        if constexpr (NB == 2) zr_epilogue_pair<TD, false>(p, acc, bv, n, td * TD, oh0 + 2 * wave + ((lane & 15) >> 3), ow0 + (lane & 7), cb0, lane, t1, t2);
         else tile_epilogue<NB, TD, true, false>(p, acc, bv, n, td * TD, oh0, ow0, cb0, wave, lane, t1, t2);
         if (p.stats_out) stats_to_global_at<NB, true, NB == 2>(p, t1, t2, sred_at, n, cb0, wave, lane, tid, (td * p.tiles_h + th) * p.tiles_w + tw);
         else __syncthreads();
@@ -786,9 +578,9 @@ __global__ __launch_bounds__(576, 1) void conv3d_zr12_kernel(const ConvParams p)
     constexpr int NB = 2, NT = 576;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    constexpr int IH = 14, IW = 14, PW = 20, ID = TD + 2;
-    constexpr int PS = IH * PW * 32;
-    constexpr int ABYTES = ID * PS;
+    using L = Zr12Lds<TD, 9>;
+    constexpr int IH = 14, IW = 14, PW = L::PW, ID = TD + 2;
+    constexpr int PS = L::PS, ABYTES = L::image;
     constexpr int KS = 15;
     constexpr int IELEM = ID * IH * IW * 2;
     constexpr int PF = (IELEM + NT - 1) / NT;
@@ -802,7 +594,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_zr12_kernel(const ConvParams p)
 
     char *sA = smem;
     char *sW = smem + ABYTES;
-    float *sRed = (float *)(sW + NB * KS * 1024);             // [9 waves][32][2]
+    float *sRed = (float *)(sW + L::weights);                 // [9 waves][32][2]
 
     const int cg = tid & 1;
     int offv[PF], ldso[PF];
@@ -828,8 +620,8 @@ __global__ __launch_bounds__(576, 1) void conv3d_zr12_kernel(const ConvParams p)
         const int vs = FNN_VS(p.src[s]);                      // activation layout: fnn_device.h, SrcDesc
         const char *sp = (const char *)(p.src[s].ptr + (size_t)n * p.Di * p.Hi * p.Wi * sC + (c_uni >> 4) * FNN_CS(p.src[s]));
         slope_next = p.src[s].slope;
-        const float *qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_uni : p.ident_ss + c_uni;
-        const float *qh = p.src[s].ss ? qs + sC : p.ident_ss + 512 + c_uni;
+        const float *qs, *qh;
+        fnn_ss_rows(p.src[s].ss, sC, n, c_uni, p.ident_ss, qs, qh);
 #pragma unroll
         for (int j = 0; j < 16; ++j) { scu[j] = qs[j]; shu[j] = qh[j]; }
 #pragma unroll
@@ -848,22 +640,10 @@ __global__ __launch_bounds__(576, 1) void conv3d_zr12_kernel(const ConvParams p)
         float sc[8], sh[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sc[j] = cg ? scu[8 + j] : scu[j]; sh[j] = cg ? shu[8 + j] : shu[j]; }
-#ifndef FNN_NORM_FP32
-        f16x8 sc_h, sh_h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)sc[j]; sh_h[j] = (f16)sh[j]; }
-#endif
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
             if ((u + 1) * NT > IELEM && offv[u] == -2) continue;
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)xr[u][j], sc[j], sh[j]);
-#else
-            f16x8 o = xr[u] * sc_h + sh_h;
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[u], sc, sh, slope_h);
             if (offv[u] < 0) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};      // the conv's zero padding
             *(f16x8 *)(sA + ldso[u]) = o;
         }
@@ -875,41 +655,11 @@ __global__ __launch_bounds__(576, 1) void conv3d_zr12_kernel(const ConvParams p)
     };
     int toff[5];
     f32x4 acc[TD][NB];
-    auto kloop = [&]() {
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const char *bp = sA + toff[pr];
-            f16x8 xf[ID];
-#pragma unroll
-            for (int pl = 0; pl < ID; ++pl) xf[pl] = *(const f16x8 *)(bp + pl * PS);
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                f16x8 wf[NB];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) wf[nb] = *(const f16x8 *)(sW + ((nb * KS + pr * 3 + dz) * 64 + lane) * 16);
-#pragma unroll
-                for (int j = 0; j < TD; ++j)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb], xf[j + dz], acc[j][nb], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
+    auto kloop = [&]() { zr_kloop<TD, NB, KS>(acc, sA, toff, sW, lane, [](int pl) { return pl * PS; }); };
 
     issue(0);
     __builtin_amdgcn_sched_barrier(0);
-    {
-        // MFMA "B" operand: lane = (voxel r of the wave's 4 x 4 block, k-group): bit 1 of the k-group picks the tap of the
-        // pair, bit 0 the 8-channel half
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;
-            const int row = 4 * bh + (r >> 2) + tp / 3, col = 4 * bw + (r & 3) + tp % 3;
-            toff[pr] = (row * PW + col) * 32 + ((kh ^ (row & 1)) * 16);
-        }
-    }
+    zr_tap_offsets<PW, true>(toff, lane, [=](int r) { return 4 * bh + (r >> 2); }, [=](int r) { return 4 * bw + (r & 3); });   // the wave's 4 x 4 block
 #pragma unroll
     for (int j = 0; j < TD; ++j)
 #pragma unroll
@@ -936,40 +686,7 @@ __global__ __launch_bounds__(576, 1) void conv3d_zr12_kernel(const ConvParams p)
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        const unsigned item_bytes = (unsigned)p.Do * p.Ho * p.Wo * p.Cout * 2;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)n * (item_bytes >> 1), 0, item_bytes, 0x00020000);
-        const unsigned ovs2 = (unsigned)FNN_OVS(p) * 2;
-        const unsigned coff = (unsigned)(cb0 + (q >> 1)) * (unsigned)(FNN_OCS(p) * 2) + (unsigned)(q & 1) * 16;   // output layout: fnn_device.h
-        const int oh = 4 * bh + (r >> 2), ow = 4 * bw + (r & 3);
-        const bool ok_hw = oh < p.Ho && ow < p.Wo;
-        const f16x2 ones = {(f16)1.f, (f16)1.f};
-#pragma unroll
-        for (int mb = 0; mb < TD; mb += 2) {
-            f16x8 o[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int od = od0 + mb + h;
-                const bool ok = ok_hw && od < p.Do;
-                const unsigned voff = ok ? (unsigned)((od * p.Ho + oh) * p.Wo + ow) * ovs2 + coff : 0x80000000u;
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    o[h][nb * 4 + 0] = (f16)(acc[mb + h][nb][0] + bv[nb].x);
-                    o[h][nb * 4 + 1] = (f16)(acc[mb + h][nb][1] + bv[nb].y);
-                    o[h][nb * 4 + 2] = (f16)(acc[mb + h][nb][2] + bv[nb].z);
-                    o[h][nb * 4 + 3] = (f16)(acc[mb + h][nb][3] + bv[nb].w);
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fnn_i32x4, o[h]), rsrc, voff, 0, 0);
-                if (!ok) o[h] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f16x2 pr = {o[0][nb * 4 + j], o[1][nb * 4 + j]};
-                    t1[nb][j] = __builtin_amdgcn_fdot2(pr, ones, t1[nb][j], false);
-                    t2[nb][j] = __builtin_amdgcn_fdot2(pr, pr, t2[nb][j], false);
-                }
-        }
+        zr_epilogue_pair<TD>(p, acc, bv, n, od0, 4 * bh + (r >> 2), 4 * bw + (r & 3), cb0, lane, t1, t2);
         if (p.stats_out) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
@@ -998,11 +715,10 @@ template <int TD>
 static int launch_zr12(ConvParams p, hipStream_t st) {
     p.tile_d = TD;
     p.tiles_d = (p.Do + TD - 1) / TD; p.tiles_h = 1; p.tiles_w = 1;
-    const size_t lds = (size_t)((TD + 2) * 14 * 20 * 32) + (size_t)2 * 15 * 1024 + 9 * 32 * 2 * 4;
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     dim3 grid(p.N * p.tiles_d, (p.Cout / 16) / 2);
-    return fnn_launch_lds<conv3d_zr12_kernel<TD>>(grid, dim3(576), lds, st, p);
+    return fnn_launch_lds<conv3d_zr12_kernel<TD>>(grid, dim3(576), Zr12Lds<TD, 9>::bytes(), st, p);
 }
 
 // ----------------------------------------------------------------------------
@@ -1021,22 +737,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_zs_kernel(const ConvParams p) {
     static_assert(NB == 2, "two cout blocks per workgroup");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    using L = ZsLds<NB, false>;
     constexpr int TD = 8, TH = 4, TDW = 4;                    // output tile depth x height (x 8 wide); depth slices per wave
-    constexpr int ID = TD + 2, IH = 2 * TH + 1, IW = 17, PW = 17;
-    constexpr int PS = IH * PW * 32;
-    constexpr int ABYTES = (ID * PS + 1023) & ~1023;
+    constexpr int ID = TD + 2, IH = 2 * TH + 1, IW = 17, PW = L::PW;
+    constexpr int PS = L::PS, ABYTES = L::image;
     constexpr int KS = 15;
     constexpr int IELEM = ID * IH * IW * 2;
     constexpr int PF = (IELEM + 255) / 256;
     constexpr int WTOT = NB * KS * 64;
     constexpr int WPF = (WTOT + 255) / 256;
 
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
-    }
+    int t = fnn_xcd_tile(gridDim.x, blockIdx.x);
     const int tw = t % p.tiles_w; t /= p.tiles_w;
     const int th = t % p.tiles_h; t /= p.tiles_h;
     const int td = t % p.tiles_d;
@@ -1047,7 +758,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zs_kernel(const ConvParams p) {
 
     char *sA = smem;                                          // halo image: [ID][IH][PW] voxels x 32 B
     char *sW = smem + ABYTES;                                 // [NB][15][64 lanes][16 B]
-    float *sBias = (float *)(sW + NB * KS * 1024);
+    float *sBias = (float *)(sW + L::weights);
 
     int toff[5];
     f32x4 acc[TDW][NB];
@@ -1087,6 +798,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zs_kernel(const ConvParams p) {
         const int vs = FNN_VS(p.src[s]);                      // activation layout: fnn_device.h, SrcDesc
         const char *sp = (const char *)(p.src[s].ptr + (size_t)n * p.Di * p.Hi * p.Wi * sC + (c_uni >> 4) * FNN_CS(p.src[s]));
         slope_next = p.src[s].slope;
+        // (fnn_ss_rows' text, kept here: through the helper the kernel's SGPR spills moved, 10 -> 6)
         const float *qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_uni : p.ident_ss + c_uni;
         const float *qh = p.src[s].ss ? qs + sC : p.ident_ss + 512 + c_uni;
 #pragma unroll
@@ -1102,22 +814,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_zs_kernel(const ConvParams p) {
         float sc[8], sh[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sc[j] = cg ? scu[8 + j] : scu[j]; sh[j] = cg ? shu[8 + j] : shu[j]; }
-#ifndef FNN_NORM_FP32
-        f16x8 sc_h, sh_h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)sc[j]; sh_h[j] = (f16)sh[j]; }
-#endif
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
             if ((u + 1) * 256 > IELEM && offv[u] == -2) continue;
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)xr[u][j], sc[j], sh[j]);
-#else
-            f16x8 o = xr[u] * sc_h + sh_h;
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[u], sc, sh, slope_h);
             if (offv[u] < 0) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
             *(f16x8 *)(sA + ldso[u]) = o;
         }
@@ -1127,42 +827,13 @@ __global__ __launch_bounds__(256, 2) void conv3d_zs_kernel(const ConvParams p) {
             if ((u + 1) * 256 <= WTOT || idx < WTOT) ((f16x8 *)sW)[idx] = wr[u];
         }
     };
-    auto kloop = [&]() {
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const char *bp = sA + toff[pr];
-            f16x8 xf[TDW + 2];
-#pragma unroll
-            for (int pl = 0; pl < TDW + 2; ++pl) xf[pl] = *(const f16x8 *)(bp + pl * PS);
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                f16x8 wf[NB];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) wf[nb] = *(const f16x8 *)(sW + ((nb * KS + pr * 3 + dz) * 64 + lane) * 16);
-#pragma unroll
-                for (int j = 0; j < TDW; ++j)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb], xf[j + dz], acc[j][nb], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
+    auto kloop = [&]() { zr_kloop<TDW, NB, KS>(acc, sA, toff, sW, lane, [](int pl) { return pl * PS; }); };
 
     if (tid < NB * 16) sBias[tid] = p.bias[cb0 * 16 + tid];
     issue(0);
     __builtin_amdgcn_sched_barrier(0);
-    {
-        // MFMA "B" operand: lane = (voxel r of the wave's two output rows, k-group): k-group bit 1 picks the tap of the
-        // pair, bit 0 the 8-channel half; the voxel's input position is twice its output position + the tap
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;
-            const int row = 2 * (2 * hp + (r >> 3)) + tp / 3, col = 2 * (r & 7) + tp % 3;
-            toff[pr] = (TDW * dh) * PS + (row * PW + col) * 32 + kh * 16;
-        }
-    }
+    // the wave's two output rows from its first plane on; the voxel's input position is twice its output position + the tap
+    zr_tap_offsets<PW, false>(toff, lane, [=](int r) { return 2 * (2 * hp + (r >> 3)); }, [](int r) { return 2 * (r & 7); }, (TDW * dh) * PS);
 #pragma unroll
     for (int j = 0; j < TDW; ++j)
 #pragma unroll
@@ -1191,40 +862,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zs_kernel(const ConvParams p) {
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        const unsigned item_bytes = (unsigned)p.Do * p.Ho * p.Wo * p.Cout * 2;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)n * (item_bytes >> 1), 0, item_bytes, 0x00020000);
-        const unsigned ovs2 = (unsigned)FNN_OVS(p) * 2;
-        const unsigned coff = (unsigned)(cb0 + (q >> 1)) * (unsigned)(FNN_OCS(p) * 2) + (unsigned)(q & 1) * 16;   // output layout: fnn_device.h
-        const int oh = oh0 + 2 * hp + (r >> 3), ow = ow0 + (r & 7);
-        const bool ok_hw = oh < p.Ho && ow < p.Wo;
-        const f16x2 ones = {(f16)1.f, (f16)1.f};
-#pragma unroll
-        for (int mb = 0; mb < TDW; mb += 2) {
-            f16x8 o[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int od = od0 + TDW * dh + mb + h;
-                const bool ok = ok_hw && od < p.Do;
-                const unsigned voff = ok ? (unsigned)((od * p.Ho + oh) * p.Wo + ow) * ovs2 + coff : 0x80000000u;
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    o[h][nb * 4 + 0] = (f16)(acc[mb + h][nb][0] + bv[nb].x);
-                    o[h][nb * 4 + 1] = (f16)(acc[mb + h][nb][1] + bv[nb].y);
-                    o[h][nb * 4 + 2] = (f16)(acc[mb + h][nb][2] + bv[nb].z);
-                    o[h][nb * 4 + 3] = (f16)(acc[mb + h][nb][3] + bv[nb].w);
-                }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fnn_i32x4, o[h]), rsrc, voff, 0, 0);
-                if (!ok) o[h] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            }
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const f16x2 pr = {o[0][nb * 4 + j], o[1][nb * 4 + j]};
-                    t1[nb][j] = __builtin_amdgcn_fdot2(pr, ones, t1[nb][j], false);
-                    t2[nb][j] = __builtin_amdgcn_fdot2(pr, pr, t2[nb][j], false);
-                }
-        }
+        zr_epilogue_pair<TDW>(p, acc, bv, n, od0 + TDW * dh, oh0 + 2 * hp + (r >> 3), ow0 + (r & 7), cb0, lane, t1, t2);
         if (p.stats_out) stats_to_global<NB, true, true>(p, t1, t2, (float *)smem, n, cb0, wave, lane, tid, (td * p.tiles_h + th) * p.tiles_w + tw);
     }
 }
@@ -1241,10 +879,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsp_kernel(const ConvParams p, 
     constexpr int NB = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    using L = ZsLds<NB, true>;
     constexpr int TD = 8, TH = 4, TDW = 4;
-    constexpr int ID = TD + 2, IH = 2 * TH + 1, IW = 17, PW = 17;
-    constexpr int PS = IH * PW * 32;
-    constexpr int ABYTES = (ID * PS + 1023) & ~1023;
+    constexpr int ID = TD + 2, IH = 2 * TH + 1, IW = 17, PW = L::PW;
+    constexpr int PS = L::PS, ABYTES = L::image;
     constexpr int KS = 15;
     constexpr int IELEM = ID * IH * IW * 2;
     constexpr int PF = (IELEM + 255) / 256;
@@ -1253,15 +891,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsp_kernel(const ConvParams p, 
 
     char *sA = smem;
     char *sW = smem + ABYTES;                                 // [NB][15][64 lanes][16 B]: resident
-    float *sRed = (float *)(sW + NB * KS * 1024);             // [4 waves][32][2]
+    float *sRed = (float *)(sW + L::weights);                 // [4 waves][32][2]
 
     // this workgroup's tiles: t = first + i * stride inside its XCD's contiguous range
     int t_first, t_stride, t_end;
     {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        const int wg_lo = xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd;      // first workgroup of the XCD
-        const int wg_n = xcd < rm ? qd + 1 : qd;
+        const int nwg = gridDim.x, idx = blockIdx.x >> 3;
+        int wg_lo, wg_n;                                      // the XCD's workgroups
+        fnn_xcd_range(nwg, blockIdx.x, wg_lo, wg_n);
         const int r_lo = (int)((long long)total_tiles * wg_lo / nwg), r_hi = (int)((long long)total_tiles * (wg_lo + wg_n) / nwg);
         t_first = r_lo + idx; t_stride = wg_n; t_end = r_hi;
     }
@@ -1286,15 +923,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsp_kernel(const ConvParams p, 
     const bool has_last = tid + (PF - 1) * 256 < IELEM;
 #define ZSP_REL(u) ((relp[(u) >> 1] >> (((u) & 1) * 16)) & 0x1fffu)
     int toff[5];
-    {
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;
-            const int row = 2 * (2 * hp + (r >> 3)) + tp / 3, col = 2 * (r & 7) + tp % 3;
-            toff[pr] = (TDW * dh) * PS + (row * PW + col) * 32 + kh * 16;
-        }
-    }
+    zr_tap_offsets<PW, false>(toff, lane, [=](int r) { return 2 * (2 * hp + (r >> 3)); }, [](int r) { return 2 * (r & 7); }, (TDW * dh) * PS);
     const int q = lane >> 4, r = lane & 15;
     float4 bv[NB];
 #pragma unroll
@@ -1326,8 +955,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsp_kernel(const ConvParams p, 
         const int sC = p.src[0].C;
         const int vs = FNN_VS(p.src[0]);
         const char *sp = (const char *)(p.src[0].ptr + (size_t)n * p.Di * p.Hi * p.Wi * sC);
-        const float *qs = p.src[0].ss ? p.src[0].ss + (size_t)(2 * n) * sC : p.ident_ss;
-        const float *qh = p.src[0].ss ? qs + sC : p.ident_ss + 512;
+        const float *qs, *qh;
+        fnn_ss_rows(p.src[0].ss, sC, n, 0, p.ident_ss, qs, qh);
 #pragma unroll
         for (int j = 0; j < 16; ++j) { scu[j] = qs[j]; shu[j] = qh[j]; }
 #pragma unroll
@@ -1339,21 +968,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsp_kernel(const ConvParams p, 
         float sc[8], sh[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sc[j] = cg ? scu[8 + j] : scu[j]; sh[j] = cg ? shu[8 + j] : shu[j]; }
-#ifndef FNN_NORM_FP32
-        f16x8 sc_h, sh_h;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)sc[j]; sh_h[j] = (f16)sh[j]; }
-#endif
 #pragma unroll
         for (int u = 0; u < PF; ++u) {
-#ifdef FNN_NORM_FP32
-            f16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)xr[u][j], sc[j], sh[j]);
-#else
-            f16x8 o = xr[u] * sc_h + sh_h;
-#endif
-            o = __builtin_elementwise_max(o, o * slope_h);
+            f16x8 o = fnn_norm_leaky8(xr[u], sc, sh, slope_h);
             if (offv[u] < 0) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
             unsigned t = ZSP_REL(u);
             asm volatile("" : "+v"(t));
@@ -1399,7 +1016,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsp_kernel(const ConvParams p, 
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        // ---- epilogue of tile t (as conv3d_zs_kernel): bias, 16-byte stores, statistics row
+        // ---- epilogue of tile t (as conv3d_zs_kernel): bias, 16-byte stores, statistics row.  (zr_kloop's text above and
+        // zr_epilogue_pair's below, kept here: through either helper this kernel's register counts moved, 92 -> 94 SGPRs,
+        // 208 -> 206 VGPRs)
         float t1[NB][4], t2[NB][4];
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
@@ -1481,20 +1100,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
     constexpr int NB = 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    using L = ZsLds<NB, true>;
     constexpr int TD = 8, TH = 4, TDW = 4;
-    constexpr int ID = TD + 2, IH = 2 * TH + 1, IW = 17, PW = 17;
-    constexpr int PS = IH * PW * 32;
-    constexpr int ABYTES = (ID * PS + 1023) & ~1023;
+    constexpr int ID = TD + 2, IH = 2 * TH + 1, IW = 17, PW = L::PW;
+    constexpr int PS = L::PS, ABYTES = L::image;
     constexpr int KS = 15, WB = KS * 64, WPB = (WB + 255) / 256;
     constexpr int NCOL = IH * IW * 2;                         // 306 (row, column, half) elements per plane
     const int hp = wave & 1, dh = wave >> 1;
 
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = __builtin_amdgcn_readfirstlane((xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx);
-    }
+    int t = __builtin_amdgcn_readfirstlane(fnn_xcd_tile(gridDim.x, blockIdx.x));
     const int tw = __builtin_amdgcn_readfirstlane(t % p.tiles_w); t = __builtin_amdgcn_readfirstlane(t / p.tiles_w);
     const int th = __builtin_amdgcn_readfirstlane(t % p.tiles_h); t = __builtin_amdgcn_readfirstlane(t / p.tiles_h);
     const int seg = __builtin_amdgcn_readfirstlane(t % segs);
@@ -1506,7 +1120,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
 
     char *sA = smem;                                          // ring of ID halo planes: plane 8 td0 - 1 + k sits in slot k % ID
     char *sW = smem + ABYTES;                                 // [NB][15][64 lanes][16 B], resident
-    float *sRed = (float *)(sW + NB * KS * 1024);             // [4 waves][32][2]
+    float *sRed = (float *)(sW + L::weights);                 // [4 waves][32][2]
 
     // ---- this thread's one or two elements of a plane
     const int sC = p.src[0].C, vs = FNN_VS(p.src[0]);
@@ -1529,24 +1143,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
         ldso[k] = (zh * PW + zw) * 32 + cg * 16;
     }
     const f16 slope_h = (f16)p.src[0].slope;
-#ifdef FNN_NORM_FP32
+    // conv3d_zsp_kernel's arithmetic: the fp32 rows, rounded to fp16 by fnn_norm8 (stats_finalize_kernel's ssh rows hold the same roundings)
     float sc[8], sh[8];
     {
-        const float *qs = p.src[0].ss ? p.src[0].ss + (size_t)(2 * n) * sC : p.ident_ss;
-        const float *qh = p.src[0].ss ? qs + sC : p.ident_ss + 512;
+        const float *qs, *qh;
+        fnn_ss_rows(p.src[0].ss, sC, n, 0, p.ident_ss, qs, qh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { sc[j] = qs[cg * 8 + j]; sh[j] = qh[cg * 8 + j]; }
     }
-#else
-    f16x8 sc_h, sh_h;
-    {
-        // conv3d_zsp_kernel's arithmetic: the fp32 rows rounded to fp16 here (stats_finalize_kernel's ssh rows hold the same roundings)
-        const float *qs = p.src[0].ss ? p.src[0].ss + (size_t)(2 * n) * sC : p.ident_ss;
-        const float *qh = p.src[0].ss ? qs + sC : p.ident_ss + 512;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { sc_h[j] = (f16)qs[cg * 8 + j]; sh_h[j] = (f16)qh[cg * 8 + j]; }
-    }
-#endif
 
     fnn_u32x4v xr[2][ID];
     auto load_planes = [&](int td, int u0) {                  // the planes u0 .. 9 of tile td: 8 td - 1 + u, clamped (see stage())
@@ -1570,30 +1174,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
             char *dst = sA + ((k0 + u) % ID) * PS;
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const f16x8 x = __builtin_bit_cast(f16x8, xr[k][u]);
-#ifdef FNN_NORM_FP32
-                f16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)x[j], sc[j], sh[j]);
-#else
-                f16x8 o = x * sc_h + sh_h;
-#endif
-                o = __builtin_elementwise_max(o, o * slope_h);
+                f16x8 o = fnn_norm_leaky8(__builtin_bit_cast(f16x8, xr[k][u]), sc, sh, slope_h);
                 if (!okc[k] || !plane_ok) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};     // the conv's zero padding
                 if (has[k]) *(f16x8 *)(dst + ldso[k]) = o;
             }
         }
     };
     int toff[5];
-    {
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;
-            const int row = 2 * (2 * hp + (r >> 3)) + tp / 3, col = 2 * (r & 7) + tp % 3;
-            toff[pr] = (row * PW + col) * 32 + kh * 16;
-        }
-    }
+    zr_tap_offsets<PW, false>(toff, lane, [=](int r) { return 2 * (2 * hp + (r >> 3)); }, [](int r) { return 2 * (r & 7); });
     const int q = lane >> 4, r = lane & 15;
     float4 bv[NB];
 #pragma unroll
@@ -1608,27 +1196,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
         for (int j = 0; j < TDW; ++j)
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) acc[j][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const char *bp = sA + toff[pr];
-            f16x8 xf[TDW + 2];
-#pragma unroll
-            for (int pl = 0; pl < TDW + 2; ++pl) xf[pl] = *(const f16x8 *)(bp + roff[pl]);
-#pragma unroll
-            for (int dz = 0; dz < 3; ++dz) {
-                f16x8 wf[NB];
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) wf[nb] = *(const f16x8 *)(sW + ((nb * KS + pr * 3 + dz) * 64 + lane) * 16);
-#pragma unroll
-                for (int j = 0; j < TDW; ++j)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        acc[j][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[nb], xf[j + dz], acc[j][nb], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        zr_kloop<TDW, NB, KS>(acc, sA, toff, sW, lane, [&](int pl) { return roff[pl]; });
     };
-    const f16x2 ones = {(f16)1.f, (f16)1.f};
     auto finish = [&](int td) {                               // conv3d_zsp_kernel's epilogue: bias, 16-byte stores, statistics row (+ a barrier)
         const int od0 = td * TD;
         float t1[NB][4], t2[NB][4];
@@ -1636,41 +1205,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zsw_kernel(const ConvParams p, 
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        {
-            const unsigned ob = (unsigned)p.Do * p.Ho * p.Wo * p.Cout * 2;
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)n * (ob >> 1), 0, ob, 0x00020000);
-            const unsigned ovs2 = (unsigned)FNN_OVS(p) * 2;
-            const unsigned coff = (unsigned)(cb0 + (q >> 1)) * (unsigned)(FNN_OCS(p) * 2) + (unsigned)(q & 1) * 16;   // output layout: fnn_device.h
-            const int oh = oh0 + 2 * hp + (r >> 3), ow = ow0 + (r & 7);
-            const bool ok_hw = oh < p.Ho && ow < p.Wo;
-#pragma unroll
-            for (int mb = 0; mb < TDW; mb += 2) {
-                f16x8 o[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int od = od0 + TDW * dh + mb + h;
-                    const bool ok = ok_hw && od < p.Do;
-                    const unsigned vo = ok ? (unsigned)((od * p.Ho + oh) * p.Wo + ow) * ovs2 + coff : 0x80000000u;
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) {
-                        o[h][nb * 4 + 0] = (f16)(acc[mb + h][nb][0] + bv[nb].x);
-                        o[h][nb * 4 + 1] = (f16)(acc[mb + h][nb][1] + bv[nb].y);
-                        o[h][nb * 4 + 2] = (f16)(acc[mb + h][nb][2] + bv[nb].z);
-                        o[h][nb * 4 + 3] = (f16)(acc[mb + h][nb][3] + bv[nb].w);
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fnn_i32x4, o[h]), rsrc, vo, 0, 0);
-                    if (!ok) o[h] = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
-                }
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const f16x2 pr = {o[0][nb * 4 + j], o[1][nb * 4 + j]};
-                        t1[nb][j] = __builtin_amdgcn_fdot2(pr, ones, t1[nb][j], false);
-                        t2[nb][j] = __builtin_amdgcn_fdot2(pr, pr, t2[nb][j], false);
-                    }
-            }
-        }
+        zr_epilogue_pair<TDW>(p, acc, bv, n, od0 + TDW * dh, oh0 + 2 * hp + (r >> 3), ow0 + (r & 7), cb0, lane, t1, t2);
         if (p.stats_out) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
@@ -1730,20 +1265,17 @@ static int launch_zs(ConvParams p, const ConvChoice &c, hipStream_t st) {
     p.tiles_d = (p.Do + 7) / 8;
     p.tiles_h = (p.Ho + 3) / 4;
     p.tiles_w = (p.Wo + 7) / 8;
-    const size_t lds = (size_t)((10 * 9 * 17 * 32 + 1023) & ~1023) + (size_t)2 * 15 * 1024 + (size_t)2 * 64;
     fnn_allow_lds<conv3d_zs_kernel<2>>();
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss) return -2;
     const int total = p.N * p.tiles_d * p.tiles_h * p.tiles_w, groups = (p.Cout / 16) / 2;
     if (c.kernel == CK_ZSW) {
-        const size_t ldsw = lds - (size_t)2 * 64 + 4 * 32 * 2 * 4;
-        return fnn_launch_lds<conv3d_zsw_kernel>(dim3(p.N * p.tiles_h * p.tiles_w * c.segs, groups), dim3(256), ldsw, st, p, c.segs, c.tps);
+        return fnn_launch_lds<conv3d_zsw_kernel>(dim3(p.N * p.tiles_h * p.tiles_w * c.segs, groups), dim3(256), ZsLds<2, true>::bytes(), st, p, c.segs, c.tps);
     }
     if (c.kernel == CK_ZSP) {
-        const size_t ldsp = lds - (size_t)2 * 64 + 4 * 32 * 2 * 4;
-        return fnn_launch_lds<conv3d_zsp_kernel>(dim3(c.gx, groups), dim3(256), ldsp, st, p, total);
+        return fnn_launch_lds<conv3d_zsp_kernel>(dim3(c.gx, groups), dim3(256), ZsLds<2, true>::bytes(), st, p, total);
     }
-    return fnn_launch_lds<conv3d_zs_kernel<2>>(dim3(total, groups), dim3(256), lds, st, p);
+    return fnn_launch_lds<conv3d_zs_kernel<2>>(dim3(total, groups), dim3(256), ZsLds<2, false>::bytes(), st, p);
 }
 
 // ----------------------------------------------------------------------------
@@ -1767,21 +1299,16 @@ template <int NB, int TD>
 __global__ __launch_bounds__(256, 2) void conv3d_zr8_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    using L = Zr8Lds<NB, TD>;
     constexpr int IH = 10, IW = 10, ID = TD + 2;
-    constexpr int SUB = 192, PS = IH * 2 * SUB;               // sub-row pitch, bytes per halo plane
-    constexpr int ABYTES = (ID * PS + 1023) & ~1023;
+    constexpr int SUB = L::SUB, PS = L::PS, ABYTES = L::image;   // sub-row pitch, bytes per halo plane
     constexpr int KS = 15;
     constexpr int IELEM = ID * IH * IW * 2;
     constexpr int PF = (IELEM + 255) / 256;
     constexpr int WTOT = NB * KS * 32;                        // 16-byte pieces (two lanes' fragments) per chunk
     constexpr int WPF = (WTOT + 255) / 256;
 
-    int t;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        t = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
-    }
+    int t = fnn_xcd_tile(gridDim.x, blockIdx.x);
     const int tw = t % p.tiles_w; t /= p.tiles_w;
     const int th = t % p.tiles_h; t /= p.tiles_h;
     const int td = t % p.tiles_d;
@@ -1791,7 +1318,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zr8_kernel(const ConvParams p) 
 
     char *sA = smem;
     char *sW = smem + ABYTES;                                 // [NB][15][64 lanes][8 B]
-    float *sBias = (float *)(sW + NB * KS * 512);             // [NB * 16] bias, then [NB * 16] output scales
+    float *sBias = (float *)(sW + L::weights);                // [NB * 16] bias, then [NB * 16] output scales
 
     int toff[5];
     f32x4 acc[TD][NB];
@@ -1832,6 +1359,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zr8_kernel(const ConvParams p) 
         const int vs = FNN_VS(p.src[s]);                      // activation layout: fnn_device.h, SrcDesc
         const char *sp = (const char *)(p.src[s].ptr + (size_t)n * p.Di * p.Hi * p.Wi * sC + (c_uni >> 4) * FNN_CS(p.src[s]));
         slope_next = p.src[s].slope;
+        // (fnn_ss_rows' text, kept here: through the helper every instantiation took three more SGPRs)
         const float *qs = p.src[s].ss ? p.src[s].ss + (size_t)(2 * n) * sC + c_loc : p.ident_ss + c_loc;
         const float *qh = p.src[s].ss ? qs + sC : p.ident_ss + 512 + c_loc;
         scr[0] = *(const float4 *)qs; scr[1] = *(const float4 *)(qs + 4);
@@ -1894,15 +1422,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zr8_kernel(const ConvParams p) 
     issue(0);
     __builtin_amdgcn_sched_barrier(0);
     if (tid < NB * 16) { sBias[tid] = p.bias[cb0 * 16 + tid]; sBias[NB * 16 + tid] = p.oscale[cb0 * 16 + tid]; }
-    {
-        const int r = lane & 15, hl = lane >> 5, kh = (lane >> 4) & 1;
-#pragma unroll
-        for (int pr = 0; pr < 5; ++pr) {
-            const int tp = 2 * pr + hl < 9 ? 2 * pr + hl : 8;
-            const int row = 2 * wave + (r >> 3) + tp / 3, col = (r & 7) + tp % 3;
-            toff[pr] = (row * 2 + kh) * SUB + col * 8;
-        }
-    }
+    zr_tap_offsets(toff, lane, [=](int r) { return 2 * wave + (r >> 3); }, [](int r) { return r & 7; }, [](int row, int col, int kh) { return (row * 2 + kh) * SUB + col * 8; });
 #pragma unroll
     for (int j = 0; j < TD; ++j)
 #pragma unroll
@@ -1936,7 +1456,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zr8_kernel(const ConvParams p) 
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { t1[nb][j] = 0.f; t2[nb][j] = 0.f; }
-        if constexpr (NB == 2) zr_epilogue_pair<TD>(p, acc, bv, n, od0, oh0, ow0, cb0, wave, lane, t1, t2);
+        if constexpr (NB == 2) zr_epilogue_pair<TD>(p, acc, bv, n, od0, oh0 + 2 * wave + ((lane & 15) >> 3), ow0 + (lane & 7), cb0, lane, t1, t2);
         else tile_epilogue<NB, TD, true>(p, acc, bv, n, od0, oh0, ow0, cb0, wave, lane, t1, t2);
         if (p.stats_out) stats_to_global<NB, true, NB == 2>(p, t1, t2, (float *)smem, n, cb0, wave, lane, tid, (td * p.tiles_h + th) * p.tiles_w + tw);
     }
@@ -1948,11 +1468,10 @@ static int launch_zr8(ConvParams p, hipStream_t st) {
     p.tiles_d = (p.Do + TD - 1) / TD;
     p.tiles_h = (p.Ho + 7) / 8;
     p.tiles_w = (p.Wo + 7) / 8;
-    const size_t lds = (size_t)(((TD + 2) * 10 * 2 * 192 + 1023) & ~1023) + (size_t)NB * 15 * 512 + (size_t)NB * 128;
     p.ident_ss = conv3d_identity_ss();
     if (!p.ident_ss || !p.oscale) return -2;
     dim3 grid(p.N * p.tiles_d * p.tiles_h * p.tiles_w, (p.Cout / 16) / NB);
-    return fnn_launch_lds<conv3d_zr8_kernel<NB, TD>>(grid, dim3(256), lds, st, p);
+    return fnn_launch_lds<conv3d_zr8_kernel<NB, TD>>(grid, dim3(256), Zr8Lds<NB, TD>::bytes(), st, p);
 }
 
 template <int NB, int TD, int TH = 8>
@@ -1961,7 +1480,7 @@ static int launch_zr(ConvParams p, hipStream_t st) {
     p.tiles_d = (p.Do + TD - 1) / TD;
     p.tiles_h = (p.Ho + 7) / 8;
     p.tiles_w = (p.Wo + 7) / 8;
-    size_t lds = (size_t)((TD + 2) * (TH + 2) * 12 * 32) + (size_t)NB * 15 * 1024;
+    size_t lds = ZrLds<NB, TD, TH>::bytes();
     if (const char *pad = fnn_knob("FNN_ZR_LDS_PAD")) lds += (size_t)atoi(pad);      // A-B aid: fewer ZR workgroups per CU (room for another stream's kernels)
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
@@ -1981,12 +1500,11 @@ static int launch_zrw(ConvParams p, const ConvChoice &c, hipStream_t st) {
     p.tiles_d = (p.Do + TD - 1) / TD;
     p.tiles_h = (p.Ho + 7) / 8;
     p.tiles_w = (p.Wo + 7) / 8;
-    const size_t lds = (size_t)((TD + 2) * 10 * 12 * 32) + (size_t)NB * 15 * 1024;
     p.ident_ss = conv3d_identity_ss();
     p.ident_ssh = conv3d_identity_ssh();
     if (!p.ident_ss || !p.ident_ssh) return -2;
     dim3 grid(p.N * p.tiles_h * p.tiles_w * c.segs, (p.Cout / 16) / NB);
-    return fnn_launch_lds<conv3d_zrw_kernel<NB>>(grid, dim3(256), lds, st, p, c.segs, c.tps);
+    return fnn_launch_lds<conv3d_zrw_kernel<NB>>(grid, dim3(256), ZrLds<NB, TD>::bytes(), st, p, c.segs, c.tps);
 }
 
 // A persistent form of this kernel (tile ranges per workgroup, cross-tile prefetch, like conv3d_persist_kernel) was

@@ -1,6 +1,53 @@
-// conv_common.h - pieces shared by the MFMA conv kernels (conv3d.hip, conv3d_zr.hip)
+// conv_common.h - pieces shared by the MFMA conv kernels (every conv*.hip; the depth-shift family's own: conv_zr_common.h)
 #pragma once
 #include "fnn_device.h"
+
+// XCD-aware, bijective remap of the workgroup number: the hardware deals blocks round-robin to the 8 XCDs (blocks b and
+// b + 8 share one), so block `bid` of `nwg` becomes tile (or range) fnn_xcd_tile(nwg, bid) - the XCD's blocks get one
+// contiguous run of tiles, and neighbouring tiles share their halos in one L2.
+// fnn_xcd_range: the run itself - the first workgroup number of bid's XCD and how many it has.
+static __device__ __forceinline__ int fnn_xcd_tile(int nwg, int bid) {
+    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+    return (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+}
+static __device__ __forceinline__ void fnn_xcd_range(int nwg, int bid, int &wg_lo, int &wg_n) {
+    const int qd = nwg >> 3, rm = nwg & 7, xcd = bid & 7;
+    wg_lo = xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd;
+    wg_n = xcd < rm ? qd + 1 : qd;
+}
+
+// ----------------------------------------------------------------------------
+// normalise-on-load: the producer's InstanceNorm + LeakyReLU while a conv stages its input
+// ----------------------------------------------------------------------------
+// qs, qh: batch item n's scale row and shift row from channel c on of a source with C channels (ss = SrcDesc::ss), or the
+// identity's (conv3d_identity_ss).  (The source's fields by value: a reference into the kernel's arguments is a generic
+// pointer until late in the compiler's pipeline, and the kernels' instruction order - their register counts - moved with it.)
+static __device__ __forceinline__ void fnn_ss_rows(const float *ss, int C, int n, int c, const float *ident_ss, const float *&qs, const float *&qh) {
+    qs = ss ? ss + (size_t)(2 * n) * C + c : ident_ss + c;
+    qh = ss ? qs + C : ident_ss + 512 + c;
+}
+// ... and the fp16 rows in the staging layout (ssh = SrcDesc::ssh: per 8 channels 8 scales, then 8 shifts), c a multiple of 8
+static __device__ __forceinline__ const unsigned short *fnn_ssh_rows(const unsigned short *ssh, int C, int n, int c, const unsigned short *ident_ssh) {
+    return ssh ? ssh + ((size_t)n * C + c) * 2 : ident_ssh + c * 2;
+}
+// LeakyReLU(x * scale + shift) of 8 channels, fnn_norm8's arithmetic (fnn_device.h).  fp32 rows:
+static __device__ __forceinline__ f16x8 fnn_norm_leaky8(const f16x8 &x, const float (&sc)[8], const float (&sh)[8], f16 slope_h) {
+    const f16x8 o = fnn_norm8(x, sc, sh);
+    return __builtin_elementwise_max(o, o * slope_h);
+}
+// fp16 rows: x*scale+shift with scale and shift rounded to fp16 (4 x v_pk_fma_f16 instead of 16 instructions): in fp32
+// (convert, fma, convert back) the staging's normalisation was 8 % of the benchmark's time.  Measured cost in accuracy:
+// relative RMSE of the 64^3 student 1.56e-3 -> 1.64e-3 against the 5e-3 limit.  `make NORM_FP32=1` builds the fp32 form.
+static __device__ __forceinline__ f16x8 fnn_norm_leaky8(const f16x8 &x, const f16x8 &sc_h, const f16x8 &sh_h, f16 slope_h) {
+#ifdef FNN_NORM_FP32
+    f16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (f16)fmaf((float)x[j], (float)sc_h[j], (float)sh_h[j]);
+#else
+    const f16x8 o = x * sc_h + sh_h;
+#endif
+    return __builtin_elementwise_max(o, o * slope_h);
+}
 
 // ----------------------------------------------------------------------------
 // shared pieces of the stride-1 MFMA conv kernels

@@ -392,7 +392,7 @@ size_t conv3d_lds_bytes(const ConvParams &p, int nb);
 int conv3d_pick_nb(int nblk);
 const float *conv3d_identity_ss();
 const unsigned short *conv3d_identity_ssh();
-int conv3d_ksteps(int packing, int taps);
+int conv3d_ksteps(int packing, int taps);                          // (conv_pack.hip, as conv3d_kstep_tap and conv3d_pack_cout)
 // linear tap index of half `half` (k 16 half .. + 15) of k-step ks of chunk ch (of `chunks`), or -1 = zero padding;
 // *tch = the chunk whose 16 channels that half holds (ch except in FNN_PACK_ZRP's shared k-steps)
 int conv3d_kstep_tap(int packing, int ks, int half, int taps, int ch, int chunks, int *tch);
@@ -434,7 +434,7 @@ bool conv_choose(const ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
 bool conv_choose_fp8(ThinParams &tp, const ConvOverrides &o, ConvChoice &c);
 // Runs the layer on the chosen kernel; packing / ksteps / chunks / stats_slots come from c (the weights are packed for them)
 int launch_conv(const ThinParams &tp, const ConvChoice &c, hipStream_t st);
-// ---- a conv layer's weights, packed on the host for the kernel the choice c runs (conv3d_zr.hip) ----
+// ---- a conv layer's weights, packed on the host for the kernel the choice c runs (conv_pack.hip) ----
 // W: [cout][cin0 + cin1][taps] fp32 (cin_real: the sources' real channel counts); p: the layer's shape (src[i].C, Cout, kd / kh /
 // kw, fp8).  dst: [cout block][chunk][k-step][64 lanes][8] in fp16, or with p.fp8 e4m3 bytes and scales[Cout] = the per-cout
 // weight scale / FNN_FP8_ACT_MULT; FNN_PACK_ZP: conv_zp_pack's order.
