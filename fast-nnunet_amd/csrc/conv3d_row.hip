@@ -211,9 +211,9 @@ __global__ __launch_bounds__(256, CH == 1 ? (NBLK <= 8 ? 3 : 2) : (NBLK <= 8 ? 2
                     const int lrow = lbase + lr;
                     const bool ok = lrow >= 0 && lrow < Hl;
 #ifdef FNN_NORM_FP32
-                    f16x8 o = fnn_norm8(xl[t], lsc, lsh);                // load_act_frag's arithmetic (misc.hip)
+                    f16x8 o = fnn_norm8(xl[t], lsc, lsh);                // load_act_frag's arithmetic (act_load.h)
 #else
-                    f16x8 o = xl[t] * lsc_h + lsh_h;                     // fnn_norm8 = load_act_frag's arithmetic (misc.hip) on the pre-rounded rows
+                    f16x8 o = xl[t] * lsc_h + lsh_h;                     // fnn_norm8 = load_act_frag's arithmetic (act_load.h) on the pre-rounded rows
 #endif
                     o = __builtin_elementwise_max(o, o * lslope);
                     char *dst = smem + (slot * 4 + 2 * lr) * PB + bl * 1024;
@@ -223,9 +223,7 @@ __global__ __launch_bounds__(256, CH == 1 ? (NBLK <= 8 ? 3 : 2) : (NBLK <= 8 ? 2
 #pragma unroll
                     for (int cls = 0; cls < 4; ++cls)
                         dd[cls] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fwf[cls], o, (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#ifndef FNN_STEM_SERIAL
                     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                     for (int cls = 0; cls < 4; ++cls) {
                         f16x4 h;
@@ -683,7 +681,6 @@ __global__ __launch_bounds__(256, NBLK <= 8 ? 3 : 2) void conv_row_stem_kernel(c
             for (int b = 0; b < NBLK; ++b) *(f16x4 *)(dst + b * 512) = (f16x4){0, 0, 0, 0};
             return;
         }
-#ifndef FNN_STEM_SERIAL
         // the row's MFMAs back to back into their own registers, then their commits (written per block, hipcc puts every block's
         // result into the same four registers: MFMA, eight wait states, the commit - NBLK times in a row per step)
         f32x4 dd[NBLK];
@@ -701,18 +698,6 @@ __global__ __launch_bounds__(256, NBLK <= 8 ? 3 : 2) void conv_row_stem_kernel(c
             o = __builtin_elementwise_max(o, o * sslope);
             *(f16x4 *)(dst + b * 512) = o;
         }
-#else
-#pragma unroll
-        for (int b = 0; b < NBLK; ++b) {
-            const f16x4 ea = *(const f16x4 *)(pa + b * 128), eb = *(const f16x4 *)(pb + b * 128);
-            const f16x8 xb = {ea[0], ea[1], ea[2], ea[3], eb[0], eb[1], eb[2], eb[3]};
-            const f32x4 dd = __builtin_amdgcn_mfma_f32_16x16x32_f16(swf, xb, sbv, 0, 0, 0);      // bias = the C operand: stem_row_kernel's value
-            f16x4 o = {(f16)dd[0], (f16)dd[1], (f16)dd[2], (f16)dd[3]};
-            o = o * ssc + ssh;                                           // conv_row_kernel's commit on it
-            o = __builtin_elementwise_max(o, o * sslope);
-            *(f16x4 *)(dst + b * 512) = o;
-        }
-#endif
     };
 
     // ---- statistics and the conv step: conv_row_kernel<NBLK, 1, false>

@@ -24,7 +24,7 @@
 // 568 us against 337 us per batch, fused consumer 1417 us against 1020 us (the d16 loads chain through their destination
 // registers and the 32x32 MFMA's result arrives 64 cycles late).  The 16x16x32 form below stays.
 //
-// Replaces (with conv3d.hip / misc.hip) the ConvDropoutNormReLU stacks and the transpconvs of the reference's
+// Replaces (with conv3d.hip / tconv.hip) the ConvDropoutNormReLU stacks and the transpconvs of the reference's
 // PlainConvUNet decoder, nnUNetDistillationTrainer.py:141-173; patch slicing predict_from_raw_data.py:560-566.
 #include "fnn_device.h"
 #include "conv_common.h"
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(256, WPS) void conv_thin_kernel(const ThinParams tp
         const float sh[8] = {shr[0].x, shr[0].y, shr[0].z, shr[0].w, shr[1].x, shr[1].y, shr[1].z, shr[1].w};
 #pragma unroll
         for (int j = 0; j < NLBW; ++j) {                                 // no branch per block (see stem_to_image)
-            f16x8 o = fnn_norm_leaky8(xr[j], sc, sh, slope_h);                              // load_act_frag's arithmetic (misc.hip)
+            f16x8 o = fnn_norm_leaky8(xr[j], sc, sh, slope_h);                              // load_act_frag's arithmetic (act_load.h)
             if (!(l_ok[j] & 1)) o = (f16x8){0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int cls = 0; cls < NCLS; ++cls) {

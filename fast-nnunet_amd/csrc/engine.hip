@@ -341,7 +341,7 @@ int build_plan(fnn_engine *e) {
     // The first conv of the network.  One input channel in 3-D: the stem kernels (conv3d_thin.hip / conv3d_row.hip: the window
     // of the fp32 volume in LDS, one MFMA per 16 voxels).  More channels (multi-modal MR, a cascade's one-hot channels) or a
     // `2d` configuration (depth-1 tiles: a sixteenth of that kernel's tile): the patches' windows are first written as an fp16
-    // tensor with the channels padded to 16 (patch_input_kernel, misc.hip) and the stem is an ordinary conv layer on the MFMA
+    // tensor with the channels padded to 16 (patch_input_kernel, body.hip) and the stem is an ordinary conv layer on the MFMA
     // conv kernels - plan sweep, round 6: the generic multi-channel stem took 17 % (4 channels) to 55 % (14) of a forward.
     auto add_stem = [&](int cin, int cout, const int32_t *k, const int *d) {
         const bool via_conv = (cin >= 2 || a.spatial_dims == 2) && fnn_knob("FNN_STEM_DIRECT") == nullptr;   // (knob: A-B aid / the tests of the generic stem kernel)

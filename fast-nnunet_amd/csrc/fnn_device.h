@@ -311,7 +311,7 @@ static __device__ __forceinline__ f16x8 fnn_norm8(const f16x8 &x, const float (&
 
 // The network input of a batch of patches as an fp16 tensor: patch windows of the fp32 volume (mirroring applied), the
 // channel count padded to a multiple of 16 with zeros - what the stem conv of a multi-channel (or `2d`) configuration reads
-// through the regular MFMA conv kernels (misc.hip, patch_input_kernel).
+// through the regular MFMA conv kernels (body.hip, patch_input_kernel).
 struct PatchInputParams {
     const float *vol;            // [C][X][Y][Z] fp32 (the padded volume)
     long long vol_batch_stride;  // elements between the volumes of consecutive batch items (0 = one volume)

@@ -21,16 +21,10 @@
 //
 // Replaces _internal_predict_sliding_window_return_logits' accumulation and normalisation (:602-625) and, for the
 // label entry points, LabelManager.convert_logits_to_segmentation (label_handling.py:144-195).
-#include "fnn_device.h"
+#include "output_common.h"
 #include <cstdlib>
 
 namespace {
-
-static __device__ __forceinline__ float acc_add_product_1(float a, float t, float g) {
-#pragma clang fp contract(off)
-    const float c = t * g;                                     // the reference rounds the product before the add: no fma
-    return a + c;
-}
 
 // FNN_ACC_FP16_AUTOCAST: the product of two fp16 numbers rounded to fp16, then an fp16 + fp16 add rounded to fp16 -
 // torch's half arithmetic (computed in fp32, rounded once: the fp32 product of two halves is exact, and an fp32 sum of
@@ -76,30 +70,13 @@ static __device__ __forceinline__ f16x2 quot_sign(f16x2 q, f16x2 a) {          /
     return __builtin_bit_cast(f16x2, r);
 }
 
-struct Pick {                                                  // LabelPick of misc.hip over this lane's heads, mergeable
-    float best; int arg; int nan; int hit;
-};
-
 }  // namespace
 
-// fp16-valued running sum (one half of a packed pair) + fp32 product, rounded to fp32 exactly like v_add_f32:
-// v_fma_mix_f32 reads the half in place (a * 1.0 + c, the product is exact), so the up-convert and the add are ONE
-// instruction (tools/hw_probe.cpp compares the bits with (float)a + c for every fp16 a, subnormals and NaNs included).
-// The rounding to fp16 stays a separate v_cvt_pk_f16_f32: the reference rounds twice (fp32 sum, then the fp16 store).
-static __device__ __forceinline__ float add_half_lo(unsigned a2, float c) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(a2), "v"(c));
-    return r;
-}
-static __device__ __forceinline__ float add_half_hi(unsigned a2, float c) {
-    float r;
-    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(a2), "v"(c));
-    return r;
-}
-static __device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
+// How the fp16 sums take a visit's fp32 product (the asm statements of consume() below): fp16-valued running sum (one half
+// of a packed pair) + fp32 product, rounded to fp32 exactly like v_add_f32 - v_fma_mix_f32 reads the half in place
+// (a * 1.0 + c, the product is exact), so the up-convert and the add are ONE instruction (tools/hw_probe.cpp compares the
+// bits with (float)a + c for every fp16 a, subnormals and NaNs included).  The rounding to fp16 stays a separate
+// v_cvt_pk_f16_f32: the reference rounds twice (fp32 sum, then the fp16 store).
 
 // What one visit (a patch that covers part of the wave's 64-voxel run, one mirrored evaluation of it) brings in: the raw
 // feature vectors of the four 16-voxel groups, the evaluation's InstanceNorm rows, the patch's Gaussian weights
@@ -175,11 +152,11 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
     f32x4 bv[HB];
 #pragma unroll
     for (int hb = 0; hb < HB; ++hb) {
-        const int hbc = hb < p.hblocks ? hb : p.hblocks - 1;     // HB = 4 with 3 blocks: the copy's rows are >= heads, ignored
+        const int hbc = head_block(hb, p.hblocks);                // HB = 4 with 3 blocks: the copy's rows are >= heads, ignored
         // the packed K = 32 fragments: lane (r, q') holds k = 8 q' .. 8 q' + 7 of head r; a K = 16 lane (r, q) wants k = 4 q .. 4 q + 3
-        if (K16) wf[hb] = *(const FV *)(p.wpk + ((size_t)hbc * 64 + r + 16 * (q >> 1)) * 8 + 4 * (q & 1));
-        else wf[hb] = *(const FV *)(p.wpk + ((size_t)hbc * 64 + lane) * 8);
-        bv[hb] = *(const f32x4 *)(p.bias + hbc * 16 + q * 4);
+        if constexpr (K16) wf[hb] = *(const FV *)(p.wpk + ((size_t)hbc * 64 + r + 16 * (q >> 1)) * 8 + 4 * (q & 1));
+        else wf[hb] = head_frag(p.wpk, hbc, 1, 0, lane);
+        bv[hb] = head_bias(p.bias, hbc, q);
     }
     constexpr bool ACC32 = ACCM == 1, ACH = ACCM == 2, PKS = ACCM != 1;   // PKS: the sums are fp16 values - kept as fp16 pairs (half the registers)
     f32x4 acc[G][HB];                                          // [16-voxel group][head block] x 4 heads: fp16-valued unless ACC32
@@ -230,11 +207,7 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
 #pragma unroll
             for (int gv = 0; gv < GV; ++gv) {
                 const int g = g0 + gv;
-#ifdef FNN_GATHER_NOREACH
-                const bool reach = true;
-#else
                 const bool reach = zlo + 16 * g + 15 >= 0 && zlo + 16 * g < p.PW;
-#endif
                 const unsigned vo = reach ? b - (unsigned)g * 16u * c2 : 0x80000000u;
                 if constexpr (K16) v.x[gv] = __builtin_bit_cast(XV, __builtin_amdgcn_raw_buffer_load_b64(rf, vo, 0, 0));
                 else v.x[gv] = __builtin_bit_cast(XV, __builtin_amdgcn_raw_buffer_load_b128(rf, vo, 0, 0));
@@ -244,11 +217,7 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
 #pragma unroll
             for (int gv = 0; gv < GV; ++gv) {
                 const int g = g0 + gv;
-#ifdef FNN_GATHER_NOREACH
-                const bool reach = true;
-#else
                 const bool reach = zlo + 16 * g + 15 >= 0 && zlo + 16 * g < p.PW;
-#endif
                 const unsigned vo = reach ? b + (unsigned)g * 16u * c2 : 0x80000000u;
                 if constexpr (K16) v.x[gv] = __builtin_bit_cast(XV, __builtin_amdgcn_raw_buffer_load_b64(rf, vo, 0, 0));
                 else v.x[gv] = __builtin_bit_cast(XV, __builtin_amdgcn_raw_buffer_load_b128(rf, vo, 0, 0));
@@ -302,15 +271,11 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
     // ballots, a patch's start a v_readlane: no memory access between visits apart from a sharded caller's slot table.
     constexpr int NEVER = 0x3fffffff;                          // a tile start no coordinate reaches
     // (an axis with more than 64 positions: the 64 from the first tile that reaches this coordinate - GatherParams::base_x)
-#ifdef FNN_GATHER_NOWIN
-    constexpr int bx = 0, by = 0, bz = 0;
-#else
     // (scalars: x, y, z0 come from the wave's index, which hipcc does not know to be wave-uniform - as vector values the bases
     // made every visit's tile indices, the ring rule's modulo and the slot vector arithmetic: +2 ms on the benchmark volume)
     const int bx = __builtin_amdgcn_readfirstlane(p.base_x ? p.base_x[__builtin_amdgcn_readfirstlane(xp)] : 0);
     const int by = __builtin_amdgcn_readfirstlane(p.base_y ? p.base_y[__builtin_amdgcn_readfirstlane(yp)] : 0);
     const int bz = __builtin_amdgcn_readfirstlane(p.base_z ? p.base_z[__builtin_amdgcn_readfirstlane(zp0)] : 0);
-#endif
     const int tx = bx + lane < p.nx ? sx[bx + lane] : NEVER, ty = by + lane < p.ny ? sy[by + lane] : NEVER, tz = bz + lane < p.nz ? sz[bz + lane] : NEVER;
     const unsigned long long MX = __builtin_amdgcn_ballot_w64(tx <= xp && xp - tx < p.PD);
     const unsigned long long MY = __builtin_amdgcn_ballot_w64(ty <= yp && yp - ty < p.PH);
@@ -335,14 +300,12 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
     const auto consume = [&](GatherVisit<G, K16> &v, const GatherGeo &e) {
         pin(v);
         const int dz0 = zl - e.oz;                             // this lane's z inside the patch, group 0
-#ifndef FNN_GATHER_WEIGHT_PER_GROUP
         // the four groups' Gaussian weights (one ds_bpermute each) requested up front: per group the request sat right in front of
         // its wait, and the wait in front of the group's MFMAs
         f16 ghs[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) ghs[g] = weight_of(v, g);
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             // a patch that starts or ends inside the run leaves whole 16-voxel groups untouched: skip them
@@ -351,16 +314,11 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
             const unsigned long long inm = __builtin_amdgcn_ballot_w64(in);
             if (inm == 0) continue;
             const FV o = normed(v, g);
-#ifndef FNN_GATHER_WEIGHT_PER_GROUP
             const f16 gh = ghs[g];
-#else
-            const f16 gh = weight_of(v, g);
-#endif
             const float gw = (float)gh;
             // channel `heads` has zero weights and bias 1: its product is the weight itself; the product is rounded
             // before the sum (no fma), one rounding to fp16 per visit; lanes outside the patch keep their sums (and
             // signed zeros)
-#if !defined(FNN_GATHER_NOMIX) && !defined(FNN_GATHER_SELECT) && !defined(FNN_GATHER_EXEC_PER_BLOCK)
             if constexpr (!ACH && PKS && HB == 4) {
                 // all four head blocks of the group under ONE EXEC window (two writes of EXEC per group visit instead of eight):
                 // the four MFMAs and the sixteen products first (all lanes), then the sixteen add + up-convert and the eight
@@ -412,8 +370,6 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                 }
                 continue;
             }
-#endif
-#if !defined(FNN_GATHER_SELECT) && !defined(FNN_GATHER_EXEC_PER_BLOCK)
             if constexpr (ACH && HB == 4) {
                 // the autocast arithmetic the same way: the rounded logits' products and the sums' adds (v_pk_mul_f16, v_pk_add_f16: the
                 // instructions hipcc emits for acc_add_product_h2) of all four head blocks under one EXEC window - no selects
@@ -453,7 +409,6 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                 }
                 continue;
             }
-#endif
             // (fewer head blocks, fp32 sums: per block; the MFMAs still back to back into their own registers)
             f32x4 dd[HB];
 #pragma unroll
@@ -471,10 +426,9 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                     a2[0] = in ? n01 : a2[0];
                     a2[1] = in ? n23 : a2[1];
                 } else if (PKS) {
-#if !defined(FNN_GATHER_NOMIX) && !defined(FNN_GATHER_SELECT)
                     // Round 5: the four sums of a head block are updated under an EXEC mask of the lanes inside the patch instead
                     // of through one select per pair (`if (in) a = v` comes back from hipcc as v_cndmask): the up-convert + add
-                    // (v_fma_mix_f32, as add_half_lo / _hi) and the rounding to fp16 pairs of all four values in ONE asm
+                    // (v_fma_mix_f32, above) and the rounding to fp16 pairs of all four values in ONE asm
                     // statement, so that nothing else is scheduled between the two writes of EXEC.  The products are formed
                     // outside (all lanes): hipcc places the wait states between the MFMA and its first reader there.
                     {
@@ -496,23 +450,10 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                         ah[PKS ? g : 0][hb][0] = __builtin_bit_cast(f16x2, a01);
                         ah[PKS ? g : 0][hb][1] = __builtin_bit_cast(f16x2, a23);
                     }
-#else
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        f16x2 &a2 = ah[PKS ? g : 0][hb][k];
-#ifdef FNN_GATHER_NOMIX
-                        const f16x2 nv = round_h2(acc_add_product_1((float)a2[0], d[2 * k], gw), acc_add_product_1((float)a2[1], d[2 * k + 1], gw));
-#else
-                        const unsigned au = __builtin_bit_cast(unsigned, a2);
-                        const f16x2 nv = round_h2(add_half_lo(au, mul_rn(d[2 * k], gw)), add_half_hi(au, mul_rn(d[2 * k + 1], gw)));
-#endif
-                        a2 = in ? nv : a2;
-                    }
-#endif
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float sv = acc_add_product_1(acc[g][hb][j], d[j], gw);
+                        const float sv = acc_add_product(acc[g][hb][j], d[j], gw);
                         acc[g][hb][j] = in ? sv : acc[g][hb][j];
                     }
                 }
@@ -615,10 +556,10 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                                 const float t1 = div_n(tsum[g2][hb][2 * k + 1]);
                                 if (PKS) {
                                     f16x2 &a2 = ah[PKS ? g : 0][hb][k];
-                                    const f16x2 nv = round_h2(acc_add_product_1((float)a2[0], t0, gw), acc_add_product_1((float)a2[1], t1, gw));
+                                    const f16x2 nv = round_h2(acc_add_product((float)a2[0], t0, gw), acc_add_product((float)a2[1], t1, gw));
                                     a2 = in[g] ? nv : a2;
                                 } else {
-                                    const float s0 = acc_add_product_1(acc[g][hb][2 * k], t0, gw), s1 = acc_add_product_1(acc[g][hb][2 * k + 1], t1, gw);
+                                    const float s0 = acc_add_product(acc[g][hb][2 * k], t0, gw), s1 = acc_add_product(acc[g][hb][2 * k + 1], t1, gw);
                                     acc[g][hb][2 * k] = in[g] ? s0 : acc[g][hb][2 * k];
                                     acc[g][hb][2 * k + 1] = in[g] ? s1 : acc[g][hb][2 * k + 1];
                                 }
@@ -772,7 +713,7 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                     const int z = z0 + 16 * g + r;
                     if (q == 0 && z < p.z_hi) {
                         const size_t o = ((size_t)x * p.OY + y) * p.OZ + z;
-                        if (p.label_u16) ((uint16_t *)p.labels)[o] = (uint16_t)lab; else ((uint8_t *)p.labels)[o] = (uint8_t)lab;
+                        store_label(p.labels, p.label_u16, o, lab);
                     }
                     continue;
                 }
@@ -805,45 +746,23 @@ __global__ __launch_bounds__(256, (!TTA && ACCM != 1) ? (K16 ? 4 : 3) : (TTA && 
                 }
         }
         if (LABELS) {
-            // LabelPick (misc.hip): argmax with torch's rules - the first NaN wins, else the largest value, the lowest
-            // head among equals - is a maximum under a total order, so the lane picks over ITS 16 heads (ascending: a
-            // strict compare keeps the first) and the four lanes of a voxel merge once, comparing head indices on ties:
-            // 4 cross-lane moves per 16 voxels and lane instead of 32.  Measured and dropped: maximum by max3 + two
-            // cross-lane steps, then the lowest head that equals it, with this chain kept for groups that hold a NaN -
-            // 7x fewer instructions on the usual path, 35 instead of 29 ms.
-            // Regions: the highest head above the threshold - a plain maximum of indices.
-            float b = 0.f; int a = -1; bool n = false; int h = -1;
+            // The label rule (LabelPick, output_common.h) is a maximum under a total order, so the lane picks over ITS 16
+            // heads (ascending) and the four lanes of a voxel merge once, comparing head indices on ties: 6 cross-lane
+            // moves per 16 voxels and lane instead of 32.  Measured and dropped: maximum by max3 + two cross-lane steps,
+            // then the lowest head that equals it, with this chain kept for groups that hold a NaN - 7x fewer
+            // instructions on the usual path, 35 instead of 29 ms.
+            LabelPick pick;
 #pragma unroll
             for (int hb = 0; hb < HB; ++hb)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int head = hb * 16 + q * 4 + j;
-                    const float v = (float)qh[hb][j >> 1][j & 1];
-                    if (head < p.heads) {
-                        if (v > 0x1.8p-24f) h = head;
-                        if (a < 0) { b = v; a = head; n = v != v; }
-                        else if (!n && (v > b || v != v)) { b = v; a = head; n = v != v; }
-                    }
+                    if (head < p.heads) pick.feed(head, (float)qh[hb][j >> 1][j & 1]);
                 }
 #pragma unroll
-            for (int m = 16; m < 64; m <<= 1) {
-                const float ob = __shfl_xor(b, m, 64);
-                const int oa = __shfl_xor(a, m, 64);
-                const bool on = ob != ob;
-                bool take;                                     // is the other lane's pick the better one?
-                if (a < 0) take = true;
-                else if (oa < 0) take = false;
-                else if (n || on) take = on && (!n || oa < a);
-                else take = ob > b || (ob == b && oa < a);
-                if (take) { b = ob; a = oa; n = on; }
-                if (p.order) { const int oh = __shfl_xor(h, m, 64); h = h > oh ? h : oh; }
-            }
+            for (int m = 16; m < 64; m <<= 1) pick.merge(pick.across(m));
             const int z = z0 + 16 * g + r;
-            if (q == 0 && z < p.z_hi) {
-                const int lab = p.order ? (h >= 0 ? p.order[h] : 0) : a;
-                const size_t o = ((size_t)x * p.OY + y) * p.OZ + z;
-                if (p.label_u16) ((uint16_t *)p.labels)[o] = (uint16_t)lab; else ((uint8_t *)p.labels)[o] = (uint8_t)lab;
-            }
+            if (q == 0 && z < p.z_hi) store_label(p.labels, p.label_u16, ((size_t)x * p.OY + y) * p.OZ + z, pick.label(p.order));
         } else {
             // logits: transpose through LDS so that a head's 64 z values leave as one 128-byte row
 #pragma unroll

@@ -1,4 +1,4 @@
-"""float64 restatement of the kernels between the convs (csrc/misc.hip: avgpool_kernel, combine_kernel,
+"""float64 restatement of the kernels between the convs (csrc/body.hip, head.hip: avgpool_kernel, combine_kernel,
 combine_pool_kernel, the seg-head family, patch_acc_kernel, patch_input_kernel) that tests/test_gpu_body_ops.py compares the
 device against, one op at a time.  Plain numpy, no device code.
 

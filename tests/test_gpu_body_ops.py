@@ -1,4 +1,4 @@
-"""Per-op parity of the kernels between the convs on a real MI355X (csrc/misc.hip): avgpool_kernel, combine_kernel,
+"""Per-op parity of the kernels between the convs on a real MI355X (csrc/body.hip, head.hip): avgpool_kernel, combine_kernel,
 combine_pool_kernel<2,2,2> / <1,2,2>, seg_head_kernel, seg_head_acc_kernel<ACC32>, seg_head_acc1_kernel<...>,
 patch_acc_kernel<ACC32> and patch_input_kernel, each called once through its fnn_op_* entry point (the engine's own
 launcher) and compared with tests/body_ref.py: the float64 value of that one operation and a per-element bound summed
@@ -403,7 +403,7 @@ def test_head_patch_buffer_heads(heads):
 @pytest.mark.parametrize('fp32', [False, True], ids=['acc16', 'acc32'])
 @pytest.mark.parametrize('heads,c', [(3, 32), (17, 16), (64, 48), (118, 160)])
 def test_fused_accumulate_equals_patch_buffer_then_patch_acc(heads, c, fp32):
-    """misc.hip: the logits of every seg-head kernel agree bit for bit (the bias is the MFMA's C operand in each), and
+    """head.hip: the logits of every seg-head kernel agree bit for bit (the bias is the MFMA's C operand in each), and
     both accumulate forms state the same roundings (fl32(t * g), never fused; fl32(a + c); one rounding to fp16): without
     mirroring and with n_div = 1 (x / 1 is exact) the two paths must leave the same accumulator bits"""
     capi = _capi()

@@ -1402,3 +1402,111 @@ def test_pack_and_unpack_regions_are_the_strided_copies_they_replace(mirror):
             assert torch.equal(land, ref)
             checked += 1
     assert checked >= 8
+
+
+def _crafted_sums(heads, seed):
+    """fp16 sums [heads][16][16][32] for the label rule (weight sum 1: logit = sum), and what they hold.  Per voxel small integers,
+    two random heads raised to a common maximum; voxel v < heads carries one NaN, at head v (so every head wins somewhere);
+    a fifth of the others one or two NaN heads; a few voxels only negative values (the region rule's label 0)."""
+    rs = np.random.RandomState(seed)
+    box = (16, 16, 32)
+    n = box[0] * box[1] * box[2]
+    v = rs.randint(-8, 8, size=(heads, n)).astype(np.float32)
+    neg = np.arange(n) >= n - 64
+    v[:, neg] = -1 - np.abs(v[:, neg])
+    a = rs.randint(0, heads, size=n)
+    b = (a + rs.randint(1, heads, size=n)) % heads                      # != a
+    top = v.max(0) + 1
+    idx = np.arange(n)
+    v[a, idx] = top
+    v[b, idx] = top
+    nan1 = np.full(n, -1)
+    nan2 = np.full(n, -1)
+    nan1[:heads] = np.arange(heads)
+    some = (rs.rand(n) < 0.2) & (idx >= heads) & ~neg
+    nan1[some] = rs.randint(0, heads, size=int(some.sum()))
+    two = some & (rs.rand(n) < 0.5)
+    nan2[two] = rs.randint(0, heads, size=int(two.sum()))
+    v[nan1[nan1 >= 0], idx[nan1 >= 0]] = np.nan
+    v[nan2[nan2 >= 0], idx[nan2 >= 0]] = np.nan
+    sums = torch.from_numpy(v).half().reshape(heads, *box)
+    return sums, dict(a=a, b=b, nan1=nan1, nan2=nan2, plain=(nan1 < 0) & ~neg, neg=neg)
+
+
+@pytest.mark.parametrize('accum', ['fp16', 'fp32'])
+@pytest.mark.parametrize('heads,order', [(3, None), (9, None), (61, None), (250, None), (9, [1, 300, 2, 7, 260, 3, 9, 4, 5]),
+                                         (9, [1, 200, 2, 7, 255, 3, 9, 4, 5])])
+def test_labels_from_crafted_accumulators_follow_numpys_argmax_and_the_region_rule(heads, order, accum):
+    """fnn_labels_box on one patch-sized box of crafted accumulators (channel `heads` = 1.0: logit = sum): ties for the
+    maximum, NaN heads (the first one wins, whatever finite value stands at a lower head), the region rule.  3 / 9 / 61 /
+    250 heads are labels_from_acc_coop_kernel with 1 / 2 / 8 / 32 lanes per voxel, whose partial picks are merged across
+    lanes; region values above 255 take the one-lane uint16 kernel.  Expected: the oracle's rule on the fp16 sums, exactly."""
+    spec = UNetSpec('plain', 1, heads, [16, 32], [(3, 3, 3)] * 2, [(1, 1, 1), (2, 2, 2)], [2, 2], [2])
+    patch = (16, 16, 32)
+    p = _predictor(spec, patch, [synthetic_state_dict(spec, 77)], accumulate_in=accum)
+    sums, info = _crafted_sums(heads, 900 + heads)
+    want = osw.logits_to_labels(sums, order).long()
+    u16 = order is not None and max(order) > 255
+    hp = p._engine.accumulator_channels
+    assert hp == (heads + 1 + 7) // 8 * 8
+    acc = torch.zeros((*patch, hp), dtype=torch.float32 if accum == 'fp32' else torch.half)
+    acc[..., :heads] = sums.permute(1, 2, 3, 0).to(acc.dtype)
+    acc[..., heads] = 1.0
+    acc = acc.cuda()
+    labels = torch.full(patch, -1 if u16 else 255, dtype=torch.int16 if u16 else torch.uint8, device='cuda')
+    p._engine.set_label_rule(order, uint16=u16)
+    p._engine.labels_box(acc.data_ptr(), (1, *patch), p._opts(), (0, 0, 0), patch, (0, 0, 0), patch, labels.data_ptr())
+    torch.cuda.synchronize()
+    got = (labels.to(torch.int32) & 0xffff).long().cpu() if u16 else labels.long().cpu()
+    # the test's own coverage
+    a, b, nan1, nan2 = info['a'], info['b'], info['nan1'], info['nan2']
+    flat = want.reshape(-1).numpy()
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    plain = info['plain']
+    if order is None:
+        assert set(flat.tolist()) == set(range(heads))                   # every head wins somewhere
+        assert np.array_equal(flat[plain], lo[plain])                    # a tie: the lower head
+        first_nan = np.where(nan2 >= 0, np.minimum(nan1, nan2), nan1)
+        assert np.array_equal(flat[nan1 >= 0], first_nan[nan1 >= 0])     # a NaN: the first one
+        assert ((nan1 >= 0) & (lo < first_nan)).sum() > 20               # ... with a larger finite value at a lower head
+        assert (nan2 >= 0).sum() > 200
+        if heads > 8:
+            # ties whose heads lie in different 8-channel pieces (different lanes of the cooperative kernel), the lower head
+            # at the earlier and at the later place inside its piece
+            cross = plain & (lo // 8 != hi // 8)
+            assert (cross & (lo % 8 > hi % 8)).sum() > 20
+            assert heads == 9 or (cross & (lo % 8 < hi % 8)).sum() > 20   # (9 heads: the second piece holds head 8 alone)
+            assert ((nan2 >= 0) & (nan1 // 8 != nan2 // 8)).sum() > 20   # two NaN heads in different pieces
+    else:
+        assert set(flat.tolist()) == set(order) | {0}
+    assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize('accum', ['fp16', 'fp16_autocast'])
+@pytest.mark.parametrize('nan_rows,winner', [((7, 17), 7), ((17,), 17)])
+def test_gather_labels_with_nan_heads_take_the_first_nan(nan_rows, winner, accum):
+    """The gather chain's label pick when heads are NaN: 20 heads are two head blocks, a lane of gather_head_kernel holds heads
+    4 q .. 4 q + 3 of each block - head 17 sits in a LOWER lane than head 7 - and the four lanes of a voxel merge their picks
+    comparing head indices.  Labels must be numpy's argmax of the engine's own logits: the first NaN head, everywhere."""
+    heads = 20
+    spec = UNetSpec('plain', 1, heads, [16, 32], [(3, 3, 3)] * 2, [(1, 1, 1), (2, 2, 2)], [2, 2], [2])
+    patch = (16, 16, 32)
+    sd = synthetic_state_dict(spec, 540)
+    key = sorted(k for k in sd if 'seg_layers' in k and k.endswith('weight'))[-1]
+    assert sd[key].shape[0] == heads
+    for r in nan_rows:
+        sd[key][r] = float('nan')
+    os.environ.pop('FNN_NO_GATHER', None)
+    p = _predictor(spec, patch, [sd], accumulate_in=accum)
+    image = torch.randn(1, 24, 20, 40, generator=torch.Generator().manual_seed(43))
+    logits = p.predict_sliding_window_return_logits(image).float().cpu()
+    for r in range(heads):
+        assert bool(torch.isnan(logits[r]).all()) == (r in nan_rows)
+    p._engine.set_profiling(True)
+    labels = p.predict_segmentation_from_preprocessed_data(image)
+    log = p._engine.kernel_log()
+    p._engine.set_profiling(False)
+    assert any(k.startswith('gather_head_kernel<2,') and k.split(',')[2] == '1' for k in log), log
+    want = logits.numpy().argmax(0)
+    assert (want == winner).all()
+    assert np.array_equal(labels.cpu().numpy().astype(np.int64), want)

@@ -493,7 +493,7 @@ def test_committed_counter_traffic_belongs_to_the_kernel_sources_in_the_tree():
 
 def test_the_library_reads_its_environment_only_through_the_knob_switch():
     """a production libfnn_hip.so must not change kernels because an unrelated process exported FNN_PIPES.
-    Every FNN_* variable of the HIP sources is read through fnn_knob() (csrc/misc.hip), which answers nullptr unless
+    Every FNN_* variable of the HIP sources is read through fnn_knob() (csrc/knob.hip), which answers nullptr unless
     FNN_KNOBS is set to something other than 0; the only direct getenv calls are that switch itself and the timing-only
     FNN_ZR_TMODE inside `#ifdef FNN_TMODE` (a diagnostic build that is never shipped).  The Python side reads FNN_LIB behind the
     same switch.  Scans the sources."""
@@ -514,10 +514,10 @@ def test_the_library_reads_its_environment_only_through_the_knob_switch():
             for m in re.finditer(r'\bgetenv\s*\(\s*("?)([A-Za-z_0-9]*)', code):
                 direct.append((name, ln, m.group(2), depth_tmode > 0))
             knobs.update(re.findall(r'fnn_knob\("([A-Z0-9_]+)"\)', code))
-    allowed = {('misc.hip', 'FNN_KNOBS'), ('misc.hip', 'name')}
+    allowed = {('knob.hip', 'FNN_KNOBS'), ('knob.hip', 'name')}
     for name, ln, var, in_tmode in direct:
         assert in_tmode or (name, var) in allowed, f'{name}:{ln} reads {var or "the environment"} without the FNN_KNOBS switch'
-    body = open(os.path.join(src_dir, 'misc.hip')).read()
+    body = open(os.path.join(src_dir, 'knob.hip')).read()
     m = re.search(r'const char \*fnn_knob\(const char \*name\) \{(.*?)\n\}', body, re.S)
     assert m and 'getenv("FNN_KNOBS")' in m.group(1) and 'on ? getenv(name) : nullptr' in m.group(1)
     assert len(knobs) >= 40 and all(k.startswith('FNN_') for k in knobs)
