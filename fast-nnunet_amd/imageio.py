@@ -1,0 +1,479 @@
+"""Image files in and out: a single-file NIfTI-1 reader and writer whose voxels are decoded on the device.
+
+Restates, with the reference's method names and property keys, what its ``NibabelIO`` and ``SimpleITKIO`` classes
+(imageio/nibabel_reader_writer.py:26-98, imageio/simpleitk_reader_writer.py:23-129) do for ``.nii`` / ``.nii.gz`` files,
+without nibabel or SimpleITK: the header is parsed with ``struct``, ``.gz`` files are inflated with ``zlib`` and the
+voxel bytes go to the device as they lie in the file, where ``fnn_decode_voxels`` (csrc/imageio.hip) turns them into the
+float32 ``[C, z, y, x]`` tensor ``DevicePreprocessor.run_case_npy`` takes - half the upload of an int16 CT, a quarter for
+uint8, and no host cast.
+
+* array order: the reference's ``(z, y, x)``, which is the file's own memory order (x fastest): no transpose;
+* values: nibabel's ``get_fdata()`` (float64 scaling, ``get_slope_inter`` rules) cast to float32;
+* ``properties``: ``'spacing'`` (reversed ``abs(pixdim[1:4])``), ``'nibabel_stuff': {'original_affine'}`` (sform, else
+  qform, else the base affine) and ``'sitk_stuff'`` (the same geometry in ITK's LPS convention - restated from published
+  behaviour and not pinned against SimpleITK);
+* ``write_seg``: the header ``nibabel.Nifti1Image(seg, affine)`` saves (pinned byte for byte by the reference's output
+  fixture), gzip level 1.
+
+The header is untrusted: every length is checked against the file before anything is uploaded or launched.
+"""
+from __future__ import annotations
+
+import gzip
+import os
+import struct
+import warnings
+import zlib
+from typing import List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import capi
+
+# NIfTI datatype code -> (numpy dtype character, bytes per voxel); what fnn_decode_voxels serves
+DATATYPES = {2: ('u1', 1), 256: ('i1', 1), 4: ('i2', 2), 512: ('u2', 2), 8: ('i4', 4), 768: ('u4', 4), 16: ('f4', 4),
+             64: ('f8', 8)}
+_OTHER_DATATYPES = {1: 'binary', 32: 'complex64', 128: 'RGB24', 1024: 'int64', 1280: 'uint64', 1536: 'float128',
+                    1792: 'complex128', 2048: 'complex256', 2304: 'RGBA32'}
+SUPPORTED_FILE_ENDINGS = ('.nii', '.nii.gz')
+_OTHER_FILE_ENDINGS = ('.hdr', '.img', '.img.gz', '.hdr.gz', '.nrrd', '.mha', '.mhd', '.gipl', '.tif', '.tiff', '.png', '.bmp')
+HEADER_BYTES = 348
+MIN_VOX_OFFSET = 352
+
+
+class NiftiHeader:
+    """The fields of a NIfTI-1 header this engine reads, checked (``fname`` only names the file in messages)."""
+
+    def __init__(self, head: bytes, fname: str = '<bytes>'):
+        def bad(msg):
+            return RuntimeError(f'{fname}: {msg}')
+
+        if len(head) < HEADER_BYTES + 4:
+            raise bad(f'{len(head)} bytes are no NIfTI-1 header (352 expected)')
+        size_le, = struct.unpack_from('<i', head, 0)
+        size_be, = struct.unpack_from('>i', head, 0)
+        if size_le == HEADER_BYTES:
+            e = '<'
+        elif size_be == HEADER_BYTES:
+            e = '>'
+        elif 540 in (size_le, size_be):
+            raise NotImplementedError(f'{fname}: NIfTI-2 files are not read (single-file NIfTI-1 only)')
+        else:
+            raise bad(f'sizeof_hdr is {size_le}, not 348 in either byte order: no NIfTI-1 file')
+        magic = bytes(head[344:348])
+        if magic == b'ni1\0':
+            raise NotImplementedError(f'{fname}: .hdr / .img pairs (magic "ni1") are not read (single-file NIfTI-1 only)')
+        if magic != b'n+1\0':
+            raise bad(f'magic {magic!r} is not "n+1"')
+        self.endian = e
+        self.byteswap = e == '>'
+        dim = struct.unpack_from(e + '8h', head, 40)
+        if dim[0] != 3:
+            raise bad(f'dim[0] = {dim[0]}: only 3-D images are read (2-D and 4-D files are not)')
+        if min(dim[1:4]) < 1:
+            raise bad(f'extents {dim[1:4]} must be positive')
+        self.shape_xyz = tuple(int(i) for i in dim[1:4])
+        self.datatype, self.bitpix = (int(i) for i in struct.unpack_from(e + '2h', head, 70))
+        if self.datatype not in DATATYPES:
+            raise NotImplementedError(f'{fname}: NIfTI datatype {self.datatype} '
+                                      f'({_OTHER_DATATYPES.get(self.datatype, "unknown")}) is not read')
+        self.dtype_char, self.bytes_per_voxel = DATATYPES[self.datatype]
+        if self.bitpix != 8 * self.bytes_per_voxel:
+            raise bad(f'datatype {self.datatype} has {8 * self.bytes_per_voxel} bits per voxel, bitpix says {self.bitpix}')
+        self.pixdim = np.array(struct.unpack_from(e + '8f', head, 76), dtype=np.float32)
+        vox_offset, slope, inter = struct.unpack_from(e + '3f', head, 108)
+        if not np.isfinite(vox_offset) or vox_offset < MIN_VOX_OFFSET or vox_offset != int(vox_offset):
+            raise bad(f'vox_offset {vox_offset} (a whole number >= 352 expected)')
+        self.vox_offset = int(vox_offset)
+        self.n_vox = self.shape_xyz[0] * self.shape_xyz[1] * self.shape_xyz[2]
+        self.n_bytes = self.n_vox * self.bytes_per_voxel
+        # nibabel's get_slope_inter: slope 0 / non-finite = no scaling; a valid slope with a non-finite intercept is an error
+        slope, inter = float(np.float32(slope)), float(np.float32(inter))
+        if slope == 0 or not np.isfinite(slope):
+            slope, inter = 1.0, 0.0
+        elif not np.isfinite(inter):
+            raise bad('valid scl_slope but invalid scl_inter')
+        self.slope, self.inter = slope, inter
+        self.scale = not (slope == 1.0 and inter == 0.0)
+        self.qform_code, self.sform_code = (int(i) for i in struct.unpack_from(e + '2h', head, 252))
+        self.quatern = np.array(struct.unpack_from(e + '6f', head, 256), dtype=np.float32)
+        self.srow = np.array(struct.unpack_from(e + '12f', head, 280), dtype=np.float32).reshape(3, 4)
+        self.spacing = [float(abs(self.pixdim[3])), float(abs(self.pixdim[2])), float(abs(self.pixdim[1]))]
+        self.affine = self._best_affine()
+
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        """(z, y, x): the array order of the reference."""
+        return self.shape_xyz[::-1]
+
+    def _best_affine(self) -> np.ndarray:
+        a = np.eye(4, dtype=np.float64)
+        if self.sform_code > 0:
+            a[:3] = self.srow.astype(np.float64)
+            return a
+        zooms = self.pixdim[1:4].astype(np.float64)
+        if self.qform_code > 0:
+            b, c, d = (float(v) for v in self.quatern[:3])
+            w2 = 1.0 - (b * b + c * c + d * d)
+            if w2 < 0:                               # NIfTI-1: a = 0 and (b, c, d) normalised
+                n = (b * b + c * c + d * d) ** 0.5
+                b, c, d, aq = b / n, c / n, d / n, 0.0
+            else:
+                aq = w2 ** 0.5
+            r = np.array([[aq * aq + b * b - c * c - d * d, 2 * b * c - 2 * aq * d, 2 * b * d + 2 * aq * c],
+                          [2 * b * c + 2 * aq * d, aq * aq + c * c - b * b - d * d, 2 * c * d - 2 * aq * b],
+                          [2 * b * d - 2 * aq * c, 2 * c * d + 2 * aq * b, aq * aq + d * d - c * c - b * b]])
+            qfac = -1.0 if self.pixdim[0] < 0 else 1.0
+            a[:3, :3] = r * (zooms * np.array([1.0, 1.0, qfac]))[None]
+            a[:3, 3] = self.quatern[3:].astype(np.float64)
+            return a
+        # neither form: nibabel's base affine - the zooms on the diagonal (x flipped, its Analyze default), the centre
+        # voxel at the origin
+        zooms = zooms * np.array([-1.0, 1.0, 1.0])
+        a[:3, :3] = np.diag(zooms)
+        a[:3, 3] = -(np.array(self.shape_xyz, dtype=np.float64) - 1) / 2.0 * zooms
+        return a
+
+
+def sitk_stuff_from_affine(affine: np.ndarray) -> dict:
+    """A RAS voxel-to-world affine as ITK states the geometry (LPS): spacing and origin in (x, y, z) order, direction the
+    row-major 3x3 cosines."""
+    lps = np.diag([-1.0, -1.0, 1.0, 1.0]) @ np.asarray(affine, dtype=np.float64)
+    spacing = np.sqrt((lps[:3, :3] ** 2).sum(0))
+    safe = np.where(spacing > 0, spacing, 1.0)
+    direction = lps[:3, :3] / safe[None]
+    return {'spacing': tuple(float(i) for i in spacing), 'origin': tuple(float(i) for i in lps[:3, 3]),
+            'direction': tuple(float(i) for i in direction.reshape(-1))}
+
+
+def affine_from_sitk_stuff(stuff: dict) -> np.ndarray:
+    lps = np.eye(4, dtype=np.float64)
+    lps[:3, :3] = np.asarray(stuff['direction'], dtype=np.float64).reshape(3, 3) * np.asarray(stuff['spacing'], dtype=np.float64)[None]
+    lps[:3, 3] = np.asarray(stuff['origin'], dtype=np.float64)
+    return np.diag([-1.0, -1.0, 1.0, 1.0]) @ lps
+
+
+def _check_ending(fname: str) -> bool:
+    """-> gzipped?  Raises NotImplementedError for every format but single-file NIfTI."""
+    low = str(fname).lower()
+    if low.endswith('.nii.gz'):
+        return True
+    if low.endswith('.nii'):
+        return False
+    for end in _OTHER_FILE_ENDINGS:
+        if low.endswith(end):
+            raise NotImplementedError(f'{fname}: {end} files are not read (this engine reads .nii and .nii.gz)')
+    raise NotImplementedError(f'{fname}: unknown file ending (this engine reads .nii and .nii.gz)')
+
+
+class _FileStream:
+    """Sequential reads of a file's (inflated) bytes."""
+
+    def __init__(self, fname: str):
+        self.fname = fname
+        gz = _check_ending(fname)                    # (before the file is touched: another format is refused by its name)
+        self.f = open(fname, 'rb')
+        self.z = zlib.decompressobj(wbits=31) if gz else None
+        self.pending = b''
+
+    def close(self):
+        self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _more(self) -> bytes:
+        """The next piece of (inflated) bytes, b'' at the end (of the file, or of the gzip member)."""
+        if self.z is None:
+            return self.f.read(1 << 20)
+        while not self.z.eof:
+            raw = self.z.unconsumed_tail or self.f.read(1 << 20)
+            if not raw:
+                return b''
+            out = self.z.decompress(raw, 1 << 22)
+            if out:
+                return out
+        return b''
+
+    def readinto(self, dst: memoryview) -> int:
+        """Fills dst as far as the file reaches; -> bytes written."""
+        n = 0
+        try:
+            while n < len(dst):
+                if not self.pending:
+                    self.pending = self._more()
+                    if not self.pending:
+                        break
+                take = min(len(self.pending), len(dst) - n)
+                dst[n:n + take] = self.pending[:take]
+                self.pending = self.pending[take:]
+                n += take
+        except zlib.error as err:
+            raise RuntimeError(f'{self.fname}: corrupt gzip stream ({err})') from None
+        return n
+
+    def read(self, n: int) -> bytes:
+        buf = bytearray(n)
+        return bytes(buf[:self.readinto(memoryview(buf))])
+
+    def skip(self, n: int) -> int:
+        done = 0
+        scratch = memoryview(bytearray(min(n, 1 << 16))) if n else None
+        while done < n:
+            got = self.readinto(scratch[:min(len(scratch), n - done)])
+            if not got:
+                break
+            done += got
+        return done
+
+
+def read_header(fname: str) -> NiftiHeader:
+    with _FileStream(fname) as s:
+        return NiftiHeader(s.read(MIN_VOX_OFFSET), fname)
+
+
+def read_voxel_bytes(fname: str, hdr: NiftiHeader, dst: np.ndarray) -> None:
+    """The file's ``hdr.n_bytes`` voxel bytes into ``dst`` (uint8, at least that long): pure host work, which is what the
+    reader thread of ``predict_from_files`` runs.  RuntimeError when the file ends before its header says it should."""
+    view = memoryview(dst).cast('B')[:hdr.n_bytes]
+    with _FileStream(fname) as s:
+        if s.skip(hdr.vox_offset) != hdr.vox_offset or s.readinto(view) != hdr.n_bytes:
+            raise RuntimeError(f'{fname}: the file ends before vox_offset {hdr.vox_offset} + {hdr.n_vox} voxels of '
+                               f'{hdr.bytes_per_voxel} bytes (truncated?)')
+
+
+def check_case(fnames: Sequence[str], hdrs: Sequence[NiftiHeader]) -> None:
+    """The files of one case: equal shapes and spacings (RuntimeError), equal affines (a warning) - as the reference."""
+    if any(h.shape != hdrs[0].shape for h in hdrs):
+        raise RuntimeError(f'Not all input images have the same shape! Shapes: {[h.shape for h in hdrs]} '
+                           f'Image files: {list(fnames)}')
+    if any(not np.array_equal(h.affine, hdrs[0].affine) for h in hdrs):
+        warnings.warn(f'Not all input images have the same original_affines! Affines: {[h.affine for h in hdrs]} '
+                      f'Image files: {list(fnames)}. It is up to you to decide whether that\'s a problem.')
+    if any(h.spacing != hdrs[0].spacing for h in hdrs):
+        raise RuntimeError(f'Not all input images have the same spacing_for_nnunet! This might be caused by them not '
+                           f'having the same affine. spacings_for_nnunet: {[h.spacing for h in hdrs]} '
+                           f'Image files: {list(fnames)}')
+
+
+def case_properties(hdr: NiftiHeader) -> dict:
+    return {'nibabel_stuff': {'original_affine': hdr.affine.copy()}, 'sitk_stuff': sitk_stuff_from_affine(hdr.affine),
+            'spacing': list(hdr.spacing)}
+
+
+def decode_on_host(hdr: NiftiHeader, raw: np.ndarray) -> np.ndarray:
+    """numpy's statement of fnn_decode_voxels: float32 (z, y, x) from the file's voxel bytes."""
+    v = np.frombuffer(memoryview(raw).cast('B')[:hdr.n_bytes], dtype=np.dtype(hdr.endian + hdr.dtype_char))
+    if hdr.scale:
+        v = v.astype(np.float64)
+        if hdr.slope != 1.0:
+            v = v * np.float64(hdr.slope)
+        if hdr.inter != 0.0:
+            v = v + np.float64(hdr.inter)
+    with np.errstate(over='ignore', invalid='ignore'):
+        return v.astype(np.float32).reshape(hdr.shape)
+
+
+class StagedCase:
+    """The files of one case between the host and the device: headers (checked), and one pinned byte buffer per file that a
+    host thread fills."""
+
+    def __init__(self, fnames, hdrs, buffers):
+        self.fnames, self.hdrs, self.buffers = list(fnames), list(hdrs), list(buffers)
+
+    def fill(self):
+        """Host only (file reads and zlib): may run on a thread."""
+        for f, h, b in zip(self.fnames, self.hdrs, self.buffers):
+            read_voxel_bytes(f, h, b.numpy())
+        return self
+
+
+class NiftiIO:
+    """``read_images`` / ``read_seg`` / ``write_seg`` of the reference's reader-writer classes for single-file NIfTI-1."""
+    supported_file_endings = list(SUPPORTED_FILE_ENDINGS)
+
+    def __init__(self, device=None):
+        self._device = device
+        self._pinned = {}                            # slot -> list of pinned uint8 tensors, grown on demand
+
+    # ------------------------------------------------------------------ device side
+    def _dev(self):
+        import torch
+        if self._device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError('NiftiIO decodes voxels on the GPU and none is visible '
+                                   '(read_images(..., on_device=False) is the numpy route)')
+            self._device = torch.device('cuda', torch.cuda.current_device())
+        return torch.device(self._device)
+
+    def stage(self, fnames: Sequence[str], slot: int = 0) -> StagedCase:
+        """Headers read and checked, pinned staging buffers of slot ``slot`` sized for the case (allocated here, by the
+        calling thread: the thread that later runs ``StagedCase.fill`` makes no GPU runtime call)."""
+        import torch
+        hdrs = [read_header(f) for f in fnames]
+        check_case(fnames, hdrs)
+        self._dev()
+        bufs = self._pinned.setdefault(slot, [])
+        for i, h in enumerate(hdrs):
+            need = max(16, h.n_bytes)
+            if i >= len(bufs):
+                bufs.append(torch.empty(need, dtype=torch.uint8, pin_memory=True))
+            elif bufs[i].numel() < need:
+                bufs[i] = torch.empty(need, dtype=torch.uint8, pin_memory=True)
+        return StagedCase(fnames, hdrs, bufs[:len(hdrs)])
+
+    def decode(self, staged: StagedCase):
+        """A filled StagedCase -> (float32 ``[C, z, y, x]`` device tensor, properties).  Uploads every file's bytes and
+        decodes them on the current stream, then synchronises: the staging buffers are free again on return."""
+        import torch
+        dev = self._dev()
+        hdr0 = staged.hdrs[0]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            out = torch.empty((len(staged.hdrs), *hdr0.shape), dtype=torch.float32, device=dev)
+            keep = []
+            for c, (h, b) in enumerate(zip(staged.hdrs, staged.buffers)):
+                raw = torch.empty(max(16, h.n_bytes), dtype=torch.uint8, device=dev)      # (the allocator aligns to 512 bytes)
+                raw[:h.n_bytes].copy_(b[:h.n_bytes], non_blocking=True)
+                capi.decode_voxels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter,
+                                   out[c].data_ptr(), stream.cuda_stream)
+                keep.append(raw)
+            stream.synchronize()
+        return out, case_properties(hdr0)
+
+    # ------------------------------------------------------------------ the reference's interface
+    def read_images(self, image_fnames: Union[List[str], Tuple[str, ...]], on_device: bool = True):
+        """-> (float32 ``[C, z, y, x]``, properties): a device tensor, or with ``on_device=False`` the same values as a
+        numpy array computed on the host."""
+        image_fnames = [str(f) for f in image_fnames]
+        if on_device:
+            return self.decode(self.stage(image_fnames).fill())
+        hdrs = [read_header(f) for f in image_fnames]
+        check_case(image_fnames, hdrs)
+        images = []
+        for f, h in zip(image_fnames, hdrs):
+            raw = np.empty(h.n_bytes, dtype=np.uint8)
+            read_voxel_bytes(f, h, raw)
+            images.append(decode_on_host(h, raw)[None])
+        return np.vstack(images), case_properties(hdrs[0])
+
+    def read_seg(self, seg_fname: str, on_device: bool = True):
+        return self.read_images((seg_fname,), on_device=on_device)
+
+    def write_seg(self, seg, output_fname: str, properties: dict) -> None:
+        write_nifti_seg(seg, output_fname, properties)
+
+
+# ---------------------------------------------------------------------- writing
+def _quaternion_of(affine: np.ndarray):
+    """(qfac, zooms, (b, c, d)) of an affine's rotation part, as nibabel's ``set_qform`` derives them: column norms are the
+    zooms, a left-handed matrix flips the third column (qfac = -1), the nearest orthogonal matrix (polar decomposition
+    through the SVD) gives the unit quaternion - the eigenvector of the largest eigenvalue of Bar-Itzhack's symmetric
+    matrix, with a >= 0."""
+    rzs = np.asarray(affine, dtype=np.float64)[:3, :3]
+    zooms = np.sqrt((rzs * rzs).sum(0))
+    zooms = np.where(zooms == 0, 1.0, zooms)
+    r = rzs / zooms
+    qfac = 1.0
+    if np.linalg.det(r) <= 0:
+        qfac = -1.0
+        r = r.copy()
+        r[:, 2] *= -1
+    p, _, q = np.linalg.svd(r)
+    m = p @ q
+    xx, yx, zx, xy, yy, zy, xz, yz, zz = m.reshape(-1)
+    k = np.array([[xx - yy - zz, 0, 0, 0],
+                  [yx + xy, yy - xx - zz, 0, 0],
+                  [zx + xz, zy + yz, zz - xx - yy, 0],
+                  [yz - zy, zx - xz, xy - yx, xx + yy + zz]]) / 3.0
+    vals, vecs = np.linalg.eigh(k)
+    x, y, z, w = vecs[:, np.argmax(vals)]
+    if w < 0:
+        x, y, z = -x, -y, -z
+    return qfac, zooms, (x, y, z)
+
+
+def nifti1_header_bytes(shape_xyz, datatype: int, affine: np.ndarray) -> bytes:
+    """The 352 bytes (header + empty extension flag) of a little-endian single-file NIfTI-1 image of ``shape_xyz`` voxels with
+    ``affine`` as the sform (code 2, 'aligned') and, with code 0, as the qform - what ``nibabel.Nifti1Image(array,
+    affine)`` saves."""
+    affine = np.asarray(affine, dtype=np.float64)
+    qfac, zooms, quat = _quaternion_of(affine)
+    h = bytearray(MIN_VOX_OFFSET)
+    struct.pack_into('<i', h, 0, HEADER_BYTES)
+    struct.pack_into('<8h', h, 40, 3, *[int(i) for i in shape_xyz], 1, 1, 1, 1)
+    struct.pack_into('<2h', h, 70, int(datatype), 8 * DATATYPES[int(datatype)][1])
+    struct.pack_into('<8f', h, 76, qfac, *[float(z) for z in zooms], 1.0, 1.0, 1.0, 1.0)
+    struct.pack_into('<3f', h, 108, float(MIN_VOX_OFFSET), 1.0, 0.0)
+    struct.pack_into('<2h', h, 252, 0, 2)
+    struct.pack_into('<6f', h, 256, *[float(q) for q in quat], *[float(t) for t in affine[:3, 3]])
+    struct.pack_into('<12f', h, 280, *[float(v) for v in affine[:3].reshape(-1)])
+    h[344:348] = b'n+1\0'
+    return bytes(h)
+
+
+def write_nifti_seg(seg, output_fname: str, properties: dict) -> None:
+    """``NibabelIO.write_seg``: ``seg`` (z, y, x) as uint8 (uint16 from a maximum of 255 on) with the case's affine
+    (``nibabel_stuff`` if the properties have it, else rebuilt from ``sitk_stuff``).  The file appears under its name
+    only when it is complete."""
+    gz = _check_ending(output_fname)
+    seg = np.asarray(seg.cpu() if hasattr(seg, 'cpu') else seg)
+    assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
+    u16 = seg.size > 0 and np.max(seg) >= 255
+    data = np.ascontiguousarray(seg.astype('<u2' if u16 else np.uint8, copy=False))
+    if 'nibabel_stuff' in properties:
+        affine = properties['nibabel_stuff']['original_affine']
+    elif 'sitk_stuff' in properties:
+        affine = affine_from_sitk_stuff(properties['sitk_stuff'])
+    else:
+        raise RuntimeError('write_seg: the properties carry neither nibabel_stuff nor sitk_stuff')
+    head = nifti1_header_bytes(seg.shape[::-1], 512 if u16 else 2, affine)
+    tmp = f'{output_fname}.part{os.getpid()}'
+    try:
+        with open(tmp, 'wb') as f:
+            if gz:
+                with gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=f, mtime=0) as g:
+                    g.write(head)
+                    g.write(memoryview(data).cast('B'))
+            else:
+                f.write(head)
+                f.write(memoryview(data).cast('B'))
+        os.replace(tmp, output_fname)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+# ---------------------------------------------------------------------- which class a plan or a file ending names
+_NIFTI_CLASS_NAMES = ('NibabelIO', 'SimpleITKIO', 'NiftiIO')
+_OTHER_CLASS_NAMES = ('NibabelIOWithReorient', 'SimpleITKIOWithReorient', 'NaturalImage2DIO', 'Tiff3DIO')
+
+
+def reader_writer_class_by_name(name: str):
+    """``recursive_find_reader_writer_by_name`` (imageio/reader_writer_registry.py:73-79) for this engine: the plain
+    NIfTI readers of the reference are ``NiftiIO``; every other class is refused by name."""
+    if name in _NIFTI_CLASS_NAMES:
+        return NiftiIO
+    if name in _OTHER_CLASS_NAMES:
+        raise NotImplementedError(f'image reader-writer {name} is not implemented (NibabelIO and SimpleITKIO are, for '
+                                  f'.nii and .nii.gz files)')
+    raise NotImplementedError(f"Unable to find reader writer class '{name}': this engine implements NibabelIO and "
+                              f"SimpleITKIO for .nii and .nii.gz files")
+
+
+def determine_reader_writer_from_file_ending(file_ending: str):
+    if str(file_ending).lower() in SUPPORTED_FILE_ENDINGS:
+        return NiftiIO
+    raise NotImplementedError(f'Unable to determine a reader for file ending {file_ending}: this engine reads '
+                              f'.nii and .nii.gz')
+
+
+def determine_reader_writer_from_dataset_json(dataset_json: dict):
+    """imageio/reader_writer_registry.py:23-38 without the trial read of an example file."""
+    name = dataset_json.get('overwrite_image_reader_writer')
+    if name is not None and name != 'None':
+        return reader_writer_class_by_name(name)
+    return determine_reader_writer_from_file_ending(dataset_json['file_ending'])

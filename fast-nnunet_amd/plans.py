@@ -259,6 +259,14 @@ class PlansManager:
         return self.plans['plans_name']
 
     @property
+    def image_reader_writer_class(self):
+        """plans_handler.py:282-283: the class the plan's ``image_reader_writer`` names.  ``NibabelIO`` and ``SimpleITKIO``
+        are this engine's ``NiftiIO`` (.nii / .nii.gz); the ``...WithReorient`` classes and every other reader raise
+        NotImplementedError naming the class."""
+        from .imageio import reader_writer_class_by_name
+        return reader_writer_class_by_name(self.plans['image_reader_writer'])
+
+    @property
     def transpose_forward(self) -> List[int]:
         return self.plans['transpose_forward']
 

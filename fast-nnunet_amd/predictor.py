@@ -18,6 +18,9 @@ from __future__ import annotations
 
 import itertools
 import os
+import pickle
+import threading
+from copy import deepcopy
 from typing import List, Optional, Tuple, Union
 
 import numpy as np
@@ -84,6 +87,7 @@ class nnUNetPredictor(object):
         self._spec: Optional[ArchSpec] = None
         self._active_fold = 0
         self._postprocessing = None
+        self._rw = None
 
     # ------------------------------------------------------------------ init
     def initialize_from_trained_model_folder(self, model_training_output_dir: str,
@@ -208,6 +212,7 @@ class nnUNetPredictor(object):
         g = compute_gaussian(patch, sigma_scale=1. / 8, value_scaling_factor=10, device=torch.device('cpu'))
         self._engine.set_gaussian(g.contiguous().view(torch.int16).numpy().view(np.uint16))
         self._spec = spec
+        self._rw = None
         self._n_folds = len(sds)
         self._active_fold = 0
 
@@ -291,9 +296,22 @@ class nnUNetPredictor(object):
         ``convert_predicted_logits_to_segmentation_with_correct_shape`` (export_prediction.py:16-53).  When the case
         needs no resampling the labels are taken straight from the accumulators (no logits are materialised).
         ``save_or_return_probabilities=True`` returns ``(labels, float32 probabilities [heads, s0, s1, s2])`` like the
-        reference (softmax / sigmoid, background probability 1 outside the crop box)."""
+        reference (softmax / sigmoid, background probability 1 outside the crop box).  With ``output_file_truncated`` the
+        result is written instead (``<truncated><file_ending>``, and with probabilities ``.npz`` and ``.pkl``) and None
+        is returned."""
+        seg, probs, props = self._predict_case(input_image, image_properties, segmentation_previous_stage,
+                                               save_or_return_probabilities)
         if output_file_truncated is not None:
-            raise NotImplementedError('image file export is the caller\'s side (SURVEY.md 8: image I/O out of scope)')
+            # export_prediction_from_logits (export_prediction.py:74-110): <truncated><file_ending> through the plans'
+            # reader-writer, with probabilities also <truncated>.npz and the properties as <truncated>.pkl; returns None
+            self._export_case(seg, probs, props, output_file_truncated)
+            return None
+        return (seg, probs) if save_or_return_probabilities else seg
+
+    def _predict_case(self, input_image, image_properties: dict, segmentation_previous_stage=None,
+                      save_or_return_probabilities: bool = False):
+        """-> (labels on the raw grid (numpy), float32 probabilities or None, the case's properties after preprocessing).
+        ``input_image`` is a numpy array or a tensor (a resident one stays where it is)."""
         pp, data, props = self._preprocess_case(input_image, image_properties, segmentation_previous_stage)
         if self.verbose:
             print('predicting')
@@ -302,17 +320,17 @@ class nnUNetPredictor(object):
         if same_grid and not save_or_return_probabilities:
             seg = self.predict_segmentation_from_preprocessed_data(data)
             out = pp.revert_labels(seg, props, self.plans_manager, self.label_manager)
-            return self._labels_to_host(out, u16)
+            return self._labels_to_host(out, u16), None, props
         logits = self._predict_case_logits(data)
         if self.verbose:
             print('resampling to original shape')
         if save_or_return_probabilities:
             out, probs = pp.convert_predicted_logits_to_segmentation_and_probabilities(
                 logits, self, self.plans_manager, self.configuration_manager, props)
-            return self._labels_to_host(out, u16), probs.cpu().numpy()
+            return self._labels_to_host(out, u16), probs.cpu().numpy(), props
         out = pp.convert_predicted_logits_to_segmentation_with_correct_shape(logits, self, self.plans_manager,
                                                                              self.configuration_manager, props)
-        return self._labels_to_host(out, u16)
+        return self._labels_to_host(out, u16), None, props
 
     def _preprocess_case(self, input_image: np.ndarray, image_properties: dict, segmentation_previous_stage=None):
         """-> (DevicePreprocessor, network input on the device, properties) for predict_single_npy_array."""
@@ -404,3 +422,269 @@ class nnUNetPredictor(object):
             self._engine.forward_patches(xd.data_ptr(), x.shape[0], out.data_ptr(), fold=self._active_fold,
                                          stream=torch.cuda.current_stream(self.device).cuda_stream)
         return out
+
+    # ----------------------------------------------------------------- files
+    def _reader_writer(self):
+        """The plans' ``image_reader_writer`` class (``PlansManager.image_reader_writer_class``), or - for plans that do
+        not name one - the class the dataset's file ending selects; one instance per predictor (it owns pinned staging)."""
+        if self._rw is None:
+            from .imageio import determine_reader_writer_from_dataset_json
+            if 'image_reader_writer' in self.plans_manager.plans:
+                cls = self.plans_manager.image_reader_writer_class
+            else:
+                cls = determine_reader_writer_from_dataset_json(self.dataset_json)
+            self._rw = cls(self.device)
+        return self._rw
+
+    def _export_files(self, seg: np.ndarray, probs: Optional[np.ndarray], props: dict, output_file_truncated: str):
+        """Host only (numpy, zlib, file writes): what the writer thread of ``predict_from_files`` runs.  Every file
+        appears under its name when it is complete."""
+        made = []
+        try:
+            if probs is not None:
+                for ending, dump in (('.npz', lambda f: np.savez_compressed(f, probabilities=probs)),
+                                     ('.pkl', lambda f: pickle.dump(props, f))):
+                    tmp = f'{output_file_truncated}{ending}.part{os.getpid()}'
+                    made.append(tmp)
+                    with open(tmp, 'wb') as f:
+                        dump(f)
+                    os.replace(tmp, output_file_truncated + ending)
+            self._reader_writer().write_seg(seg, output_file_truncated + self.dataset_json['file_ending'], props)
+        finally:
+            for tmp in made:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+
+    def _export_case(self, seg, probs, props, output_file_truncated):
+        self._reader_writer()                                   # (made by the calling thread)
+        self._export_files(seg, probs, props, output_file_truncated)
+
+    def _manage_input_and_output_lists(self, list_of_lists_or_source_folder: Union[str, List[List[str]]],
+                                       output_folder_or_list_of_truncated_output_files: Union[None, str, List[str]],
+                                       folder_with_segs_from_prev_stage: str = None, overwrite: bool = True,
+                                       part_id: int = 0, num_parts: int = 1, save_probabilities: bool = False):
+        """predict_from_raw_data.py:166-205: the cases of this part, their truncated output names and previous-stage
+        files; with ``overwrite=False`` the cases whose output exists (label file, and ``.npz`` when probabilities are
+        asked for) are dropped."""
+        ending = self.dataset_json['file_ending']
+        if isinstance(list_of_lists_or_source_folder, str):
+            list_of_lists_or_source_folder = create_lists_from_splitted_dataset_folder(list_of_lists_or_source_folder, ending)
+        print(f'There are {len(list_of_lists_or_source_folder)} cases in the source folder')
+        cases = list_of_lists_or_source_folder[part_id::num_parts]
+        caseids = [os.path.basename(i[0])[:-(len(ending) + 5)] for i in cases]
+        print(f'I am processing {part_id} out of {num_parts} (max process ID is {num_parts - 1}, we start counting with 0!)')
+        print(f'There are {len(caseids)} cases that I would like to predict')
+        if isinstance(output_folder_or_list_of_truncated_output_files, str):
+            truncated = [os.path.join(output_folder_or_list_of_truncated_output_files, i) for i in caseids]
+        elif isinstance(output_folder_or_list_of_truncated_output_files, list):
+            truncated = output_folder_or_list_of_truncated_output_files[part_id::num_parts]
+        else:
+            truncated = None
+        prev = [os.path.join(folder_with_segs_from_prev_stage, i + ending) if folder_with_segs_from_prev_stage is not None
+                else None for i in caseids]
+        if not overwrite and truncated is not None:
+            done = [os.path.isfile(i + ending) for i in truncated]
+            if save_probabilities:
+                done = [i and os.path.isfile(j + '.npz') for i, j in zip(done, truncated)]
+            todo = [i for i, j in enumerate(done) if not j]
+            truncated = [truncated[i] for i in todo]
+            cases = [cases[i] for i in todo]
+            prev = [prev[i] for i in todo]
+            print(f'overwrite was set to {overwrite}, so I am only working on cases that haven\'t been predicted yet. '
+                  f'That\'s {len(todo)} cases.')
+        return cases, truncated, prev
+
+    def _prepare_files_run(self, call_kwargs: dict, sequential: bool):
+        """What both file entry points do before the first case (predict_from_raw_data.py:221-261 / :691-730): the output
+        folder with the call's arguments, dataset.json and plans.json; the cascade assertion; the lists."""
+        import json
+        target = call_kwargs['output_folder_or_list_of_truncated_output_files']
+        if isinstance(target, str):
+            output_folder = target
+        elif isinstance(target, list):
+            output_folder = os.path.dirname(target[0]) if target else None
+            if output_folder is not None and len(output_folder) == 0:
+                output_folder = os.path.curdir
+        else:
+            output_folder = None
+        if output_folder is not None:
+            os.makedirs(output_folder, exist_ok=True)
+            for name, obj, sort in (('predict_from_raw_data_args.json', deepcopy(call_kwargs), True),
+                                    ('dataset.json', self.dataset_json, False), ('plans.json', self.plans_manager.plans, False)):
+                with open(os.path.join(output_folder, name), 'w') as f:
+                    json.dump(obj, f, indent=4, sort_keys=sort)
+        folder_prev = call_kwargs.get('folder_with_segs_from_prev_stage')
+        if self.configuration_manager.previous_stage_name is not None:
+            assert folder_prev is not None, \
+                f'The requested configuration is a cascaded network. It requires the segmentations of the previous ' \
+                f'stage ({self.configuration_manager.previous_stage_name}) as input. Please provide the folder where' \
+                f' they are located via folder_with_segs_from_prev_stage'
+        return self._manage_input_and_output_lists(
+            call_kwargs['list_of_lists_or_source_folder'], target, folder_prev, call_kwargs['overwrite'],
+            0 if sequential else call_kwargs['part_id'], 1 if sequential else call_kwargs['num_parts'],
+            call_kwargs['save_probabilities'])
+
+    def _run_staged_case(self, rw, staged, staged_prev, save_probabilities: bool):
+        """The GPU part of one case: staged file bytes -> (labels, probabilities or None, properties)."""
+        data, props = rw.decode(staged)
+        seg_prev = rw.decode(staged_prev)[0] if staged_prev is not None else None
+        if staged.fnames and self.verbose:
+            print(f'predicting {os.path.basename(staged.fnames[0])}')
+        return self._predict_case(data, props, seg_prev, save_probabilities)
+
+    @staticmethod
+    def _result(seg, probs, save_probabilities):
+        return (seg, probs) if save_probabilities else seg
+
+    def predict_from_files(self,
+                           list_of_lists_or_source_folder: Union[str, List[List[str]]],
+                           output_folder_or_list_of_truncated_output_files: Union[str, None, List[str]],
+                           save_probabilities: bool = False,
+                           overwrite: bool = True,
+                           num_processes_preprocessing: int = 3,
+                           num_processes_segmentation_export: int = 3,
+                           folder_with_segs_from_prev_stage: str = None,
+                           num_parts: int = 1,
+                           part_id: int = 0):
+        """predict_from_raw_data.py:207-268 with every numerical step on the device.  Host work overlaps the GPU: one
+        reader thread inflates case i + 1 into pinned memory and one writer thread compresses case i - 1 while the
+        calling thread - the only one that touches the GPU - runs case i.  The two ``num_processes_*`` arguments only say
+        whether those threads exist (0: that side runs inline); no process is started.  With an output target the files
+        are written and None entries returned like the reference's export; without one the label maps are returned (or
+        ``(labels, probabilities)``)."""
+        assert part_id <= num_parts, ('Part ID must be smaller than num_parts. Remember that we start counting with 0. '
+                                      'So if there are 3 parts then valid part IDs are 0, 1, 2')
+        kwargs = dict(list_of_lists_or_source_folder=list_of_lists_or_source_folder,
+                      output_folder_or_list_of_truncated_output_files=output_folder_or_list_of_truncated_output_files,
+                      save_probabilities=save_probabilities, overwrite=overwrite,
+                      num_processes_preprocessing=num_processes_preprocessing,
+                      num_processes_segmentation_export=num_processes_segmentation_export,
+                      folder_with_segs_from_prev_stage=folder_with_segs_from_prev_stage, num_parts=num_parts, part_id=part_id)
+        cases, truncated, prev = self._prepare_files_run(kwargs, sequential=False)
+        if len(cases) == 0:
+            return
+        return self._predict_cases(cases, truncated, prev, save_probabilities,
+                                   read_thread=int(num_processes_preprocessing) > 0,
+                                   write_thread=int(num_processes_segmentation_export) > 0)
+
+    def predict_from_files_sequential(self,
+                                      list_of_lists_or_source_folder: Union[str, List[List[str]]],
+                                      output_folder_or_list_of_truncated_output_files: Union[str, None, List[str]],
+                                      save_probabilities: bool = False,
+                                      overwrite: bool = True,
+                                      folder_with_segs_from_prev_stage: str = None):
+        """predict_from_raw_data.py:682-767: the same work as ``predict_from_files``, case after case on the calling thread."""
+        kwargs = dict(list_of_lists_or_source_folder=list_of_lists_or_source_folder,
+                      output_folder_or_list_of_truncated_output_files=output_folder_or_list_of_truncated_output_files,
+                      save_probabilities=save_probabilities, overwrite=overwrite,
+                      folder_with_segs_from_prev_stage=folder_with_segs_from_prev_stage)
+        cases, truncated, prev = self._prepare_files_run(kwargs, sequential=True)
+        if len(cases) == 0:
+            return
+        return self._predict_cases(cases, truncated, prev, save_probabilities, read_thread=False, write_thread=False)
+
+    @torch.inference_mode()
+    def _predict_cases(self, cases, truncated, prev, save_probabilities, read_thread: bool, write_thread: bool):
+        rw = self._reader_writer()
+        if truncated is None:
+            truncated = [None] * len(cases)
+        ret = []
+        reader = _HostWorker('fnn-reader') if read_thread else None
+        writer = _HostWorker('fnn-writer') if write_thread else None
+
+        def stage(i):
+            """Headers and pinned buffers on this thread; the bytes on the reader thread (or here)."""
+            staged = rw.stage(cases[i], slot=2 * (i % 2))
+            staged_prev = rw.stage([prev[i]], slot=2 * (i % 2) + 1) if prev[i] is not None else None
+            fill = (lambda: (staged.fill(), staged_prev.fill() if staged_prev is not None else None))
+            return staged, staged_prev, (reader.submit(fill) if reader is not None else fill())
+
+        try:
+            nxt = stage(0)
+            pending = None                                       # the writer's job for the previous case
+            for i in range(len(cases)):
+                staged, staged_prev, job = nxt
+                if reader is not None:
+                    job.result()                                 # case i's bytes are in pinned memory (or the read failed)
+                # case i + 1 is read while case i runs; its slot's buffers were released when case i - 1 was decoded
+                nxt = stage(i + 1) if i + 1 < len(cases) else None
+                seg, probs, props = self._run_staged_case(rw, staged, staged_prev, save_probabilities)
+                if truncated[i] is None:
+                    ret.append(self._result(seg, probs, save_probabilities))
+                    continue
+                if pending is not None:
+                    pending.result()                             # at most one case waits for the disk
+                export = (lambda a=(seg, probs, props, truncated[i]): self._export_files(*a))
+                pending = writer.submit(export) if writer is not None else export()
+                ret.append(None)
+            if pending is not None:
+                pending.result()
+        finally:
+            for w in (reader, writer):
+                if w is not None:
+                    w.close()
+        return ret
+
+
+class _Job:
+    def __init__(self, fn):
+        self.fn, self.done, self.value, self.error = fn, threading.Event(), None, None
+
+    def result(self):
+        self.done.wait()
+        if self.error is not None:
+            raise self.error
+        return self.value
+
+
+class _HostWorker:
+    """One thread that runs host-only jobs (file reads, zlib, file writes) in order; it never makes a GPU call."""
+
+    def __init__(self, name: str):
+        import queue
+        self.q = queue.Queue()
+        self.t = threading.Thread(target=self._run, name=name, daemon=True)
+        self.t.start()
+
+    def _run(self):
+        while True:
+            job = self.q.get()
+            if job is None:
+                return
+            try:
+                job.value = job.fn()
+            except BaseException as e:                           # handed to the thread that waits for the job
+                job.error = e
+            job.done.set()
+
+    def submit(self, fn) -> _Job:
+        job = _Job(fn)
+        self.q.put(job)
+        return job
+
+    def close(self):
+        """Runs what is queued, then ends the thread."""
+        self.q.put(None)
+        self.t.join()
+
+
+def get_identifiers_from_splitted_dataset_folder(folder: str, file_ending: str):
+    """utilities/utils.py:27-34: the sorted unique case identifiers of a folder of ``<case>_XXXX<ending>`` files."""
+    files = sorted(i for i in os.listdir(folder) if os.path.isfile(os.path.join(folder, i)) and i.endswith(file_ending))
+    crop = len(file_ending) + 5
+    return sorted(set(i[:-crop] for i in files))
+
+
+def create_lists_from_splitted_dataset_folder(folder: str, file_ending: str, identifiers: List[str] = None,
+                                              num_processes: int = 12) -> List[List[str]]:
+    """utilities/utils.py:42-56: per case the sorted files ``<case>_dddd<ending>`` (four digits).  ``num_processes`` is
+    accepted and ignored: no process is started."""
+    import re
+    if identifiers is None:
+        identifiers = get_identifiers_from_splitted_dataset_folder(folder, file_ending)
+    files = sorted(i for i in os.listdir(folder) if os.path.isfile(os.path.join(folder, i)) and i.endswith(file_ending))
+    out = []
+    for ident in identifiers:
+        p = re.compile(re.escape(ident) + r'_\d\d\d\d' + re.escape(file_ending))
+        out.append([os.path.join(folder, i) for i in files if p.fullmatch(i)])
+    return out

@@ -389,6 +389,19 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
                          const int32_t *class_of_value, int n_table, int n_classes, int ignore_value,
                          int64_t *counts, void *stream);
 
+/* The voxels of an image file as the file holds them -> float32 (additive in ABI 4): what the reference's
+ * NibabelIO.read_images ends with (imageio/nibabel_reader_writer.py:56 and :89 - get_fdata() in float64, then
+ * np.vstack(..., dtype=float32, casting='unsafe')) for one file, without the host cast.  raw: device pointer to the first
+ * voxel, 16-byte aligned (FNN_E_INVALID otherwise), n_vox elements of nifti_datatype: 2 uint8, 256 int8, 4 int16,
+ * 512 uint16, 8 int32, 768 uint32, 16 float32, 64 float64; any other code (complex, RGB, 64-bit integers, ...) is
+ * FNN_E_UNSUPPORTED.  byteswap != 0: the bytes of every element are reversed before it is interpreted.  out: float32
+ * on the device, 4-byte aligned (channel c of a [C, ...] tensor starts c * n_vox floats in, whatever n_vox is).
+ * scale == 0: out = (float)v, one rounding to nearest even.  scale != 0: out = (float)((double)v * slope + inter), the
+ * product and the sum each rounded to float64 (no fused multiply-add), the multiply skipped when slope == 1 and the add
+ * when inter == 0.  One pass, no scratch memory, asynchronous on `stream`; n_vox == 0 returns 0. */
+int fnn_decode_voxels(const void *raw, int nifti_datatype, int byteswap, int64_t n_vox, int scale, double slope,
+                      double inter, float *out, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */

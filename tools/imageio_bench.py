@@ -1,0 +1,195 @@
+"""Image files on one MI355X: what the route from a NIfTI file to the float32 [C, z, y, x] device tensor that
+DevicePreprocessor.run_case_npy takes costs, split into its parts, next to the route a caller had before NiftiIO (host decode
+with numpy, astype(float32), then predict_single_npy_array's upload of the float32 array); the decode kernel's rate next to
+a plain device copy of the same bytes; the write of a label map; and predict_from_files (reader and writer threads)
+against predict_from_files_sequential on four cases.
+
+The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, so that gzip has something to do), written
+as .nii.gz (level 1, like the writer) and as .nii.
+
+usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192] [--out FILE]
+"""
+import argparse
+import gzip
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+COPY_TBS = 6.29          # MI355X_MICROARCH: float4 copy, measured
+
+
+def wall(fn, reps):
+    ts, out = [], None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts)), min(ts), max(ts), out
+
+
+def events(fn, reps, dev):
+    ts = []
+    for r in range(reps + 1):                     # the first call is the warm-up
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if r:
+            ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), min(ts), max(ts)
+
+
+def synthetic_ct(shape, seed):
+    rng = np.random.default_rng(seed)
+    z, y, x = np.meshgrid(*[np.linspace(-1, 1, s, dtype=np.float32) for s in shape], indexing='ij', sparse=True)
+    body = (z * z * 0.8 + y * y + x * x) < 0.7
+    v = np.where(body, 40 + 300 * np.sin(6 * x) * np.cos(5 * y + 3 * z), -1000).astype(np.float32)
+    v += rng.integers(-12, 13, shape, dtype=np.int16)
+    return v.astype(np.int16)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n', type=int, default=512)
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--cases', type=int, default=4)
+    ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    from fast_nnunet_amd import capi, nnUNetPredictor
+    from fast_nnunet_amd import imageio as fio
+    from fast_nnunet_amd.plans import PlansManager
+    from oracle.topology import UNetSpec
+    from oracle.unet import synthetic_state_dict
+
+    dev = torch.device('cuda', 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    n = a.n
+    lines = [f'imageio_bench: int16 volume {n}^3 ({n ** 3 * 2 / 2 ** 20:.0f} MiB of voxels, {n ** 3 * 4 / 2 ** 20:.0f} MiB as float32); '
+             f'device {torch.cuda.get_device_name(dev)}',
+             f'median of {a.reps} (min, max); host steps by wall clock, device steps by events on the stream']
+
+    def say(text):
+        lines.append(text)
+        print(text, flush=True)
+
+    def row(name, t, extra=''):
+        say(f'{name:<66s}: {t[0]:9.2f} ms  (min {t[1]:.2f} max {t[2]:.2f}){extra}')
+
+    with tempfile.TemporaryDirectory() as tmp:
+        vol = synthetic_ct((n, n, n), 1)
+        props = {'nibabel_stuff': {'original_affine': np.diag([0.8, 0.8, 1.25, 1.0])}}
+        head = fio.nifti1_header_bytes((n, n, n), 4, props['nibabel_stuff']['original_affine'])
+        f_gz, f_nii = os.path.join(tmp, 'ct_0000.nii.gz'), os.path.join(tmp, 'ct_0000.nii')
+        with open(f_nii, 'wb') as f:
+            f.write(head)
+            f.write(vol.tobytes())
+        t0 = time.perf_counter()
+        with open(f_gz, 'wb') as raw, gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=raw, mtime=0) as g:
+            g.write(head)
+            g.write(vol.tobytes())
+        say(f'synthetic files: .nii {os.path.getsize(f_nii) / 2 ** 20:.0f} MiB, .nii.gz {os.path.getsize(f_gz) / 2 ** 20:.0f} MiB '
+            f'(gzip level 1 took {time.perf_counter() - t0:.1f} s)')
+
+        rw = fio.NiftiIO(dev)
+        for f in (f_gz, f_nii):
+            tag = '.nii.gz' if f.endswith('.gz') else '.nii'
+            say(f'--- this route, {tag}: file bytes -> pinned memory -> device -> fnn_decode_voxels')
+            staged = rw.stage([f])
+            h = staged.hdrs[0]
+            row(f'{tag}: file read' + (' + inflate' if tag == '.nii.gz' else '') + ' into pinned memory (host)', wall(staged.fill, a.reps)[:3])
+            raw = torch.empty(h.n_bytes, dtype=torch.uint8, device=dev)
+            out = torch.empty((1, *h.shape), dtype=torch.float32, device=dev)
+            t = events(lambda: raw.copy_(staged.buffers[0][:h.n_bytes], non_blocking=True), a.reps, dev)
+            row(f'{tag}: upload of the voxel bytes ({h.n_bytes / 2 ** 20:.0f} MiB, pinned)', t, f'  {h.n_bytes / t[0] / 1e6:.1f} GB/s')
+            t = events(lambda: capi.decode_voxels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter,
+                                                  out.data_ptr(), stream), a.reps, dev)
+            moved = h.n_bytes + 4 * h.n_vox
+            row(f'{tag}: fnn_decode_voxels int16 -> float32', t,
+                f'  {moved / t[0] / 1e6:.0f} GB/s of {moved / 1e9:.2f} GB = {100 * moved / t[0] / 1e6 / (COPY_TBS * 1e3):.1f} % of {COPY_TBS} TB/s')
+            if tag == '.nii.gz':
+                t = events(lambda: capi.decode_voxels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, 1, 0.5, -3.0,
+                                                      out.data_ptr(), stream), a.reps, dev)
+                row(f'{tag}: fnn_decode_voxels with slope and intercept (float64 arithmetic)', t, f'  {moved / t[0] / 1e6:.0f} GB/s')
+                src = torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+                dst = torch.empty_like(src)
+                t = events(lambda: dst.copy_(src), a.reps, dev)
+                row(f'plain device copy moving the same bytes ({moved // 2 / 2 ** 20:.0f} MiB read + written)', t, f'  {moved / t[0] / 1e6:.0f} GB/s')
+                del src, dst
+            del raw, out
+            row(f'{tag}: read_images, file -> float32 tensor on the device (all of the above)', wall(lambda: rw.read_images([f]), a.reps)[:3])
+
+            say(f'--- the route before, {tag}: host decode with numpy, astype(float32), upload of the float32 array')
+
+            def host_bytes():
+                if tag == '.nii.gz':
+                    with gzip.open(f, 'rb') as g:
+                        return g.read()
+                with open(f, 'rb') as g:
+                    return g.read()
+            t_read = wall(host_bytes, a.reps)
+            row(f'{tag}: file read' + (' + inflate' if tag == '.nii.gz' else '') + ' (host)', t_read[:3])
+            blob = t_read[3]
+            t_cast = wall(lambda: np.frombuffer(blob, dtype='<i2', offset=352).reshape(1, n, n, n).astype(np.float32), a.reps)
+            row(f'{tag}: astype(float32) (host)', t_cast[:3])
+            arr = t_cast[3]
+            t_up = wall(lambda: (torch.as_tensor(arr).to(device=dev, dtype=torch.float32).contiguous(), torch.cuda.synchronize(dev)), a.reps)
+            row(f'{tag}: upload of the float32 array ({arr.nbytes / 2 ** 20:.0f} MiB, pageable)', t_up[:3], f'  {arr.nbytes / t_up[0] / 1e6:.1f} GB/s')
+            say(f'{tag}: sum of the three' + ' ' * 45 + f': {t_read[0] + t_cast[0] + t_up[0]:9.2f} ms')
+            del blob, arr
+
+        say('--- writing a label map')
+        coarse = np.random.default_rng(2).integers(0, 5, (n // 32,) * 3).astype(np.uint8)
+        seg = coarse.repeat(32, 0).repeat(32, 1).repeat(32, 2)
+        for name in ('seg.nii.gz', 'seg.nii'):
+            t = wall(lambda: fio.write_nifti_seg(seg, os.path.join(tmp, name), props), a.reps)
+            row(f'write_seg {name}, uint8 {n}^3 ({os.path.getsize(os.path.join(tmp, name)) / 2 ** 20:.1f} MiB on disk)', t[:3])
+        del vol, seg
+
+        say(f'--- predict_from_files on {a.cases} cases of {tuple(a.case_shape)} int16 .nii.gz, toy network (patch 32 x 64 x 64), no mirroring')
+        patch = (32, 64, 64)
+        spec = UNetSpec('plain', 1, 3, [16, 32, 32], [(3, 3, 3)] * 3, [(1, 1, 1), (2, 2, 2), (2, 2, 2)], [2, 2, 2], [2, 2])
+        pm = PlansManager({'dataset_name': 'Dataset996_Bench', 'plans_name': 'nnUNetPlans', 'transpose_forward': [0, 1, 2],
+                           'transpose_backward': [0, 1, 2], 'image_reader_writer': 'NibabelIO',
+                           'foreground_intensity_properties_per_channel': {},
+                           'configurations': {'3d_fullres': {
+                               'patch_size': list(patch), 'spacing': [1.25, 0.8, 0.8], 'normalization_schemes': ['ZScoreNormalization'],
+                               'use_mask_for_norm': [False],
+                               'architecture': {'network_class_name': 'PlainConvUNet', 'arch_kwargs': {}, '_kw_requires_import': []}}}})
+        dj = {'labels': {'background': 0, 'a': 1, 'b': 2}, 'channel_names': {'0': 'CT'}, 'file_ending': '.nii.gz'}
+        p = nnUNetPredictor(tile_step_size=0.5, use_gaussian=True, use_mirroring=False, device=dev, allow_tqdm=False, patches_per_forward=4)
+        p.manual_initialization(None, pm, pm.get_configuration('3d_fullres'), [synthetic_state_dict(spec, 3)], dj, 'nnUNetTrainer', None)
+        src = os.path.join(tmp, 'cases')
+        os.makedirs(src)
+        for i in range(a.cases):
+            v = synthetic_ct(tuple(a.case_shape), 10 + i)
+            hd = fio.nifti1_header_bytes(tuple(a.case_shape)[::-1], 4, props['nibabel_stuff']['original_affine'])
+            with open(os.path.join(src, f'case{i}_0000.nii.gz'), 'wb') as raw, \
+                    gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=raw, mtime=0) as g:
+                g.write(hd)
+                g.write(v.tobytes())
+        p.predict_from_files_sequential(src, os.path.join(tmp, 'warm'))
+        t_seq = wall(lambda: p.predict_from_files_sequential(src, os.path.join(tmp, 'seq')), a.reps)
+        t_thr = wall(lambda: p.predict_from_files(src, os.path.join(tmp, 'thr')), a.reps)
+        row('predict_from_files_sequential (read, GPU, write one after the other)', t_seq[:3])
+        row('predict_from_files (reader thread, writer thread)', t_thr[:3], f'  {t_seq[0] / t_thr[0]:.2f}x')
+        same = all(open(os.path.join(tmp, 'seq', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'thr', f'case{i}.nii.gz'), 'rb').read()
+                   for i in range(a.cases))
+        say(f'the two forms wrote identical files: {same}')
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
