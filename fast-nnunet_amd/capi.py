@@ -21,6 +21,7 @@ FNN_OUT_F16, FNN_OUT_F32 = 0, 1
 FNN_LABELS_ARGMAX, FNN_LABELS_REGIONS = 0, 1
 FNN_LABEL_U8, FNN_LABEL_U16 = 0, 1
 FNN_INTERP_LINEAR, FNN_INTERP_NEAREST_EXACT, FNN_INTERP_OTHER = 0, 1, 2
+FNN_RESAMPLE_DEFAULT, FNN_RESAMPLE_TORCH = 0, 1
 FNN_NORM_NONE, FNN_NORM_ZSCORE, FNN_NORM_CT, FNN_NORM_RESCALE01, FNN_NORM_RGB01 = 0, 1, 2, 3, 4
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -128,6 +129,7 @@ def load_library() -> C.CDLL:
     lib.fnn_resample.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleDesc), vp, vp]
     lib.fnn_resample_torch.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleTorchDesc), vp, vp]
     lib.fnn_resample_torch_seg.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleTorchDesc), vp, vp]
+    lib.fnn_resample_labels.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64), i32, i32, vp, i32, vp, i32, vp]
     lib.fnn_keep_largest_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), vp]
     lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
                                         C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
@@ -308,6 +310,19 @@ def resample_torch(in_ptr: int, shape, new_shape, separate_axis, half: bool, out
     fn = lib.fnn_resample_torch_seg if is_seg else lib.fnn_resample_torch
     check(fn(in_ptr, (C.c_int64 * 4)(*[int(i) for i in shape]), (C.c_int64 * 3)(*[int(i) for i in new_shape]),
              C.byref(d), out_ptr, stream), lib)
+
+
+def resample_labels(logits_ptr: int, half: bool, shape, new_shape, family: int, separate_axis, order_ptr: Optional[int],
+                    n_regions: int, labels_ptr: int, uint16: bool, stream: int = 0):
+    """fnn_resample_labels: logits [heads, *shape[1:]] of the network grid (fp32, or fp16 when `half`) -> labels [new_shape],
+    resampled by `family` (FNN_RESAMPLE_DEFAULT: order 1, order_z 0; FNN_RESAMPLE_TORCH) and put through the label rule in
+    one pass.  order_ptr: None (argmax) or n_regions = heads int32 of regions_class_order in DEVICE memory.  Asynchronous on
+    `stream`; op_last_kernels() names the kernel that ran."""
+    lib = load_library()
+    check(lib.fnn_resample_labels(logits_ptr, FNN_OUT_F16 if half else FNN_OUT_F32, (C.c_int64 * 4)(*[int(i) for i in shape]),
+                                  (C.c_int64 * 3)(*[int(i) for i in new_shape]), int(family),
+                                  -1 if separate_axis is None else int(separate_axis), order_ptr, int(n_regions), labels_ptr,
+                                  FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, stream), lib)
 
 
 def decode_voxels(raw_ptr: int, nifti_datatype: int, byteswap: bool, n_vox: int, scale: bool, slope: float, inter: float,
@@ -524,7 +539,7 @@ def op_patch_input(vol, origins, patch, cpad, flips=(0, 0, 0), chunk_major=False
 
 
 def op_last_kernels():
-    """Kernel variants launched by this thread's last op_* call."""
+    """Kernel variants launched by this thread's last op_* (or resample_labels) call."""
     lib = load_library()
     buf = C.create_string_buffer(4096)
     lib.fnn_op_last_kernels(buf, 4096)

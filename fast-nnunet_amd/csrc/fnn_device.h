@@ -273,6 +273,8 @@ const char *fnn_knob(const char *name);
 // Which kernel variant a launcher picked: recorded per launch while the engine profiles (fnn_kernel_log), a no-op otherwise.
 void fnn_note_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
 void fnn_klog_target(void *vector_of_strings);          // where this thread's notes go (nullptr: nowhere)
+void fnn_op_klog_begin();                               // ops_api.hip: this thread's notes go to the log fnn_op_last_kernels reads ...
+void fnn_op_klog_end();                                 // ... until here
 
 static __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
 

@@ -134,6 +134,9 @@ struct OpKlog {
     OpKlog() { g_op_kernels.clear(); fnn_klog_target(&g_op_kernels); }
     ~OpKlog() { fnn_klog_target(nullptr); }
 };
+// the same log for a call of an entry point outside this file (fnn_resample_labels)
+void fnn_op_klog_begin() { g_op_kernels.clear(); fnn_klog_target(&g_op_kernels); }
+void fnn_op_klog_end() { fnn_klog_target(nullptr); }
 
 extern "C" {
 

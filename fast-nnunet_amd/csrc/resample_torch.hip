@@ -23,9 +23,7 @@
 // 300 for everyone else).  Only the labels at the 8 taps (4 in the plane) can score above 0, so a thread gathers those,
 // evaluates the score of every distinct one in registers and picks: no one-hot tensor, no unique(), no buffer.
 // memefficient_seg_resampling=True is the other rule: the float32 score of (seg == u) above 0.5 takes the label, else 0.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
-#include <cmath>
+#include "resample_torch_common.h"
 
 void fnn_set_global_error(const char *msg);      // engine.hip
 
@@ -38,74 +36,6 @@ static bool dev_ptr(const void *p) {
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
-
-struct RGeo {
-    long long in[3], out[3];
-    float scale[3];            // (float)in / (float)out
-    int sep;                   // the nearest-exact axis or -1
-    unsigned plane_blocks;     // blocks of 256 output voxels per x slab
-    unsigned plane;            // out[1] * out[2]
-};
-
-// the two taps of output index o along axis a and their weights
-static __device__ __forceinline__ void axis_taps(const RGeo &g, int a, long long o, long long &i0, long long &i1, float &w0, float &w1) {
-    const long long n = g.in[a];
-    if (n == g.out[a]) { i0 = i1 = o; w0 = 1.f; w1 = 0.f; return; }
-    if (a == g.sep) {
-        long long s = (long long)floorf(__fmul_rn((float)o + 0.5f, g.scale[a]));
-        s = s > n - 1 ? n - 1 : s;
-        i0 = i1 = s; w0 = 1.f; w1 = 0.f;
-        return;
-    }
-    float src = __fmaf_rn(g.scale[a], (float)o + 0.5f, -0.5f);
-    src = src < 0.f ? 0.f : src;
-    long long f = (long long)src;
-    f = f > n - 1 ? n - 1 : f;
-    i0 = f; i1 = f + (f < n - 1 ? 1 : 0);
-    float l1 = __fsub_rn(src, (float)f);
-    l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-    w1 = l1; w0 = __fsub_rn(1.f, l1);
-}
-
-struct Taps {
-    long long off[8];          // input offsets of the corners, index = 4 * x tap + 2 * y tap + z tap
-    float wx0, wx1, wy0, wy1, wz0, wz1;
-    long long o;               // output offset inside a channel
-    bool live;
-};
-
-static __device__ __forceinline__ Taps make_taps(const RGeo &g) {
-    Taps t;
-    const unsigned ox = blockIdx.x / g.plane_blocks;
-    const unsigned j = (blockIdx.x - ox * g.plane_blocks) * 256u + threadIdx.x;
-    t.live = j < g.plane;
-    const unsigned oy = t.live ? j / (unsigned)g.out[2] : 0u;
-    const unsigned oz = t.live ? j - oy * (unsigned)g.out[2] : 0u;
-    long long x[2], y[2], z[2];
-    axis_taps(g, 0, ox, x[0], x[1], t.wx0, t.wx1);
-    axis_taps(g, 1, oy, y[0], y[1], t.wy0, t.wy1);
-    axis_taps(g, 2, oz, z[0], z[1], t.wz0, t.wz1);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t.off[k] = (x[k >> 2] * g.in[1] + y[(k >> 1) & 1]) * g.in[2] + z[k & 1];
-    t.o = (long long)ox * g.plane + j;
-    return t;
-}
-
-// w0 * a + w1 * b as torch's CPU kernel rounds it: the second product rounded, then one fused multiply-add - measured
-// bit for bit against F.interpolate on float32 inputs (either other order is one step off on about half the values)
-static __device__ __forceinline__ float mix(float a, float b, float w0, float w1) { return __fmaf_rn(w0, a, __fmul_rn(w1, b)); }
-
-static __device__ __forceinline__ float blend(const Taps &t, const float (&v)[8]) {
-    const float a = mix(mix(v[0], v[1], t.wz0, t.wz1), mix(v[2], v[3], t.wz0, t.wz1), t.wy0, t.wy1);
-    const float b = mix(mix(v[4], v[5], t.wz0, t.wz1), mix(v[6], v[7], t.wz0, t.wz1), t.wy0, t.wy1);
-    return mix(a, b, t.wx0, t.wx1);
-}
-
-// float32 result -> storage type.  For fp16 the conversion must stay an instruction of its own: folded into the last
-// fused multiply-add (v_fma_mixlo_f16) the exact sum is rounded to fp16 once, where torch rounds it to float32 first -
-// measured as 1e-4 of the values one fp16 step off.  The canonicalize keeps the two apart and costs no instruction.
-template <typename T> static __device__ __forceinline__ T store_cast(float v) { return (T)v; }
-template <> __device__ __forceinline__ f16 store_cast<f16>(float v) { return (f16)__builtin_canonicalizef(v); }
 
 template <typename T>
 __global__ __launch_bounds__(256) void rt_image_kernel(const T *__restrict__ in, RGeo g, int C, T *__restrict__ out) {
@@ -223,20 +153,6 @@ __global__ __launch_bounds__(256) void rt_seg_kernel(const short *__restrict__ i
     }
 }
 
-static int geometry(const int64_t shape[4], const int64_t new_shape[3], int sep, RGeo &g, const char **why) {
-    g.sep = sep;
-    for (int a = 0; a < 3; ++a) {
-        g.in[a] = shape[1 + a]; g.out[a] = new_shape[a];
-        if (g.in[a] > (1 << 24) || g.out[a] > (1 << 24)) { *why = "an axis longer than 2^24 is not implemented (float32 coordinates)"; return FNN_E_UNSUPPORTED; }
-        g.scale[a] = (float)g.in[a] / (float)g.out[a];
-    }
-    const long long plane = g.out[1] * g.out[2];
-    const long long pb = (plane + 255) / 256;
-    if (plane >= (1LL << 31) || pb * g.out[0] >= (1LL << 31) || shape[0] >= (1LL << 31)) { *why = "output too large for one launch"; return FNN_E_UNSUPPORTED; }
-    g.plane = (unsigned)plane; g.plane_blocks = (unsigned)pb;
-    return FNN_OK;
-}
-
 static int check_args(const void *in, const int64_t *shape, const int64_t *new_shape, const fnn_resample_torch_desc *d,
                       const void *out) {
     if (!in || !shape || !new_shape || !d || !out) return fail_msg(FNN_E_INVALID, "NULL argument");
@@ -258,7 +174,7 @@ extern "C" int fnn_resample_torch(const void *in, const int64_t shape[4], const 
     if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fail_msg(FNN_E_INVALID, "unknown dtype");
     RGeo g{};
     const char *why = "";
-    if ((rc = geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fail_msg(rc, why);
+    if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fail_msg(rc, why);
     hipStream_t st = (hipStream_t)stream;
     if (d->dtype == FNN_OUT_F32) launch_image((const float *)in, g, (int)shape[0], (float *)out, st);
     else launch_image((const f16 *)in, g, (int)shape[0], (f16 *)out, st);
@@ -272,7 +188,7 @@ extern "C" int fnn_resample_torch_seg(const int16_t *in, const int64_t shape[4],
     if (rc != FNN_OK) return rc;
     RGeo g{};
     const char *why = "";
-    if ((rc = geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fail_msg(rc, why);
+    if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fail_msg(rc, why);
     const dim3 grid(g.plane_blocks * (unsigned)g.out[0]), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (d->memefficient) hipLaunchKernelGGL(rt_seg_kernel<true>, grid, block, 0, st, (const short *)in, g, (int)shape[0], (short *)out);

@@ -50,7 +50,8 @@ class nnUNetPredictor(object):
                  allow_tqdm: bool = True,
                  accumulate_in: str = 'fp16',
                  patches_per_forward: int = 4,
-                 compute_dtype: str = 'f16'):
+                 compute_dtype: str = 'f16',
+                 fused_label_export: bool = True):
         """Same knobs as the reference (:40-65) plus two engine choices:
 
         accumulate_in  'fp16' reproduces the reference's half accumulators and their rounding per patch visit as the
@@ -61,6 +62,10 @@ class nnUNetPredictor(object):
         patches_per_forward  how many patches one network forward batches.
         compute_dtype  'f16' (default: the mode every parity statement is for) or 'f8': OCP e4m3 operands in
                        the 3x3x3 stride-1 convolutions (BASELINE config 5; budget in DESIGN.md).
+        fused_label_export  a case whose logits are resampled back (file spacing != target spacing) gets its labels from
+                       ``fnn_resample_labels`` - interpolation and label rule in one pass, no resampled logits in memory
+                       (order-1 default plans and torch-resampling plans); False: resample, then the label rule - the
+                       same labels.
         """
         self.verbose = verbose
         self.verbose_preprocessing = verbose_preprocessing
@@ -83,6 +88,7 @@ class nnUNetPredictor(object):
         if compute_dtype not in ('f16', 'f8'):
             raise ValueError("compute_dtype must be 'f16' or 'f8'")
         self.compute_dtype = compute_dtype
+        self.fused_label_export = bool(fused_label_export)
         self._engine: Optional[capi.Engine] = None
         self._spec: Optional[ArchSpec] = None
         self._active_fold = 0

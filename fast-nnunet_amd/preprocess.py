@@ -12,7 +12,8 @@ Mirrors, with the reference's argument names and property keys,
   revert cropping, ``transpose_backward``.
 
 Every numerical step is a HIP kernel behind ``include/fnn.h`` (``fnn_nonzero_bbox``, ``fnn_preprocess``,
-``fnn_resample``, ``fnn_resample_torch``, ``fnn_resample_torch_seg``, ``fnn_argmax_labels``, ``fnn_revert_labels``); torch only owns the device buffers.  No CPU path.
+``fnn_resample``, ``fnn_resample_torch``, ``fnn_resample_torch_seg``, ``fnn_resample_labels``, ``fnn_argmax_labels``,
+``fnn_revert_labels``); torch only owns the device buffers.  No CPU path.
 """
 from __future__ import annotations
 
@@ -104,12 +105,37 @@ def plan_resampling(fn_name: str, kwargs: Optional[dict], current_spacing, new_s
             'memefficient': bool(kwargs.get('memefficient_seg_resampling', False))}
 
 
+def plan_label_export(fn_name: str, kwargs: Optional[dict], current_spacing, new_spacing, in_shape, out_shape) -> dict:
+    """How the labels of a case come out of its logits ``[heads, *in_shape]`` on the grid ``out_shape`` under the
+    configuration's ``resampling_fn_probabilities`` - the whole decision, without a GPU.
+    -> ``{'path': ..., 'separate_axis': None | 0..2}`` with path
+
+    * ``'same-grid'``: nothing is resampled (equal grids, or a no-resampling planner): the label rule on the logits;
+    * ``'fused-default'``: ``resample_data_or_seg_to_shape`` with ``order == 1`` and ``order_z == 0`` (what every standard
+      plan asks for probabilities) - ``fnn_resample_labels`` interpolates and picks in one pass;
+    * ``'fused-torch'``: ``resample_torch_fornnunet`` - the same entry, the torch family's arithmetic;
+    * ``'two-step'``: any other order: the resampled logits are written (``fnn_resample``), then the label rule.
+
+    What ``plan_resampling`` refuses is refused here with the same exception."""
+    plan = plan_resampling(fn_name, kwargs, current_spacing, new_spacing)
+    if plan['path'] == 'none' or [int(i) for i in in_shape] == [int(i) for i in out_shape]:
+        return {'path': 'same-grid', 'separate_axis': None}
+    if plan['path'] == 'torch':
+        return {'path': 'fused-torch', 'separate_axis': plan['separate_axis']}
+    kwargs = dict(kwargs or {})
+    do_sep, axis = determine_do_sep_z_and_axis(kwargs.get('force_separate_z', None), current_spacing, new_spacing,
+                                               kwargs.get('separate_z_anisotropy_threshold', ANISO_THRESHOLD))
+    fused = int(kwargs.get('order', 3)) == 1 and int(kwargs.get('order_z', 0)) == 0
+    return {'path': 'fused-default' if fused else 'two-step', 'separate_axis': int(axis) if do_sep else None}
+
+
 class DevicePreprocessor:
     def __init__(self, device: torch.device = torch.device('cuda'), verbose: bool = False):
         if device.type != 'cuda':
             raise RuntimeError('DevicePreprocessor has no CPU path: pass a GPU device')
         self.device = device
         self.verbose = verbose
+        self._region_orders = {}          # regions_class_order -> its int32 copy on the device (fnn_resample_labels reads it there)
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -257,10 +283,45 @@ class DevicePreprocessor:
         kw = getattr(configuration_manager, 'resampling_fn_probabilities_kwargs', None) or \
             {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
         fn = getattr(configuration_manager, 'resampling_fn_probabilities_name', DEFAULT_RESAMPLING_FN)
-        logits = self.resample(predicted_logits, properties_dict['shape_after_cropping_and_before_resampling'],
-                               current_spacing, spacing_transposed, kw, fn)
+        cropped = properties_dict['shape_after_cropping_and_before_resampling']
+        if getattr(predictor, 'fused_label_export', False):
+            # no resampled logits [heads, *cropped] in between: interpolation and label rule in one pass
+            plan = plan_label_export(fn, kw, current_spacing, spacing_transposed, predicted_logits.shape[1:], cropped)
+            if plan['path'] in ('fused-default', 'fused-torch'):
+                order, u16 = predictor._label_rule()
+                seg = self.resample_logits_to_labels(predicted_logits, cropped, plan['path'] == 'fused-torch',
+                                                     plan['separate_axis'], order, u16)
+                return self.revert_labels(seg, properties_dict, plans_manager, predictor.label_manager)
+        logits = self.resample(predicted_logits, cropped, current_spacing, spacing_transposed, kw, fn)
         seg = predictor.convert_logits_to_segmentation(logits)
         return self.revert_labels(seg, properties_dict, plans_manager, predictor.label_manager)
+
+    @torch.inference_mode()
+    def resample_logits_to_labels(self, logits: torch.Tensor, new_shape, torch_family: bool, separate_axis,
+                                  regions_class_order, u16: bool) -> torch.Tensor:
+        """``fnn_resample_labels``: logits ``[heads, x, y, z]`` (fp16 / fp32) -> the labels of the logits resampled to
+        ``new_shape`` (default family at order 1, or the torch family), bit for bit those of ``resample`` followed by the
+        label rule, without the resampled tensor.  ``regions_class_order`` None is the argmax rule.  -> uint8, or the
+        int32-carried uint16 (``u16``) of the predictor, on the device."""
+        new_shape = [int(i) for i in new_shape]
+        with torch.cuda.device(self.device):
+            lg = logits.to(self.device)
+            if lg.dtype not in (torch.half, torch.float32):
+                lg = lg.float()
+            lg = lg.contiguous()
+            order_ptr = None
+            if regions_class_order is not None:
+                key = tuple(int(c) for c in regions_class_order)
+                if key not in self._region_orders:
+                    self._region_orders[key] = torch.tensor(key, dtype=torch.int32, device=self.device)
+                order_ptr = self._region_orders[key].data_ptr()
+            labels = torch.empty(new_shape, dtype=torch.int16 if u16 else torch.uint8, device=self.device)
+            capi.resample_labels(lg.data_ptr(), lg.dtype == torch.half, lg.shape, new_shape,
+                                 capi.FNN_RESAMPLE_TORCH if torch_family else capi.FNN_RESAMPLE_DEFAULT, separate_axis,
+                                 order_ptr, lg.shape[0], labels.data_ptr(), u16, self._stream())
+            if u16:
+                labels = labels.to(torch.int32) & 0xffff
+        return labels
 
     @torch.inference_mode()
     def resample_logits_to_cropped_shape(self, predicted_logits: torch.Tensor, plans_manager, configuration_manager,

@@ -347,6 +347,18 @@ int fnn_resample_torch(const void *in, const int64_t shape[4], const int64_t new
 int fnn_resample_torch_seg(const int16_t *in, const int64_t shape[4], const int64_t new_shape[3],
                            const fnn_resample_torch_desc *desc, int16_t *out, void *stream);
 
+/* resample + label rule in one pass (additive in ABI 4): logits [heads][in] (FNN_OUT_F16 / FNN_OUT_F32) on the network
+ * grid -> labels [new_shape] (FNN_LABEL_U8 / U16), bit for bit the labels of fnn_resample (order 1, order_z 0) or
+ * fnn_resample_torch followed by fnn_argmax_labels - without the resampled tensor [heads][new_shape] in between.
+ * family: FNN_RESAMPLE_DEFAULT (resample_data_or_seg_to_shape, order 1, order_z 0) or FNN_RESAMPLE_TORCH
+ * (resample_torch_fornnunet, linear / nearest-exact).  separate_axis -1 or 0..2.  regions_class_order NULL = argmax
+ * rule (first maximum, first NaN); else n_regions = heads entries IN DEVICE MEMORY, the region rule painted in that
+ * order.  Any number of heads.  Device pointers, one launch, no allocation, no synchronisation. */
+enum { FNN_RESAMPLE_DEFAULT = 0, FNN_RESAMPLE_TORCH = 1 };
+int fnn_resample_labels(const void *logits, int dtype, const int64_t shape[4], const int64_t new_shape[3],
+                        int family, int separate_axis, const int32_t *regions_class_order, int n_regions,
+                        void *labels, int label_dtype, void *stream);
+
 /* remove_all_but_largest_component_from_segmentation (postprocessing/remove_connected_components.py:21-33) for
  * disjoint label sets at once (additive in ABI 4): labels [X][Y][Z] (FNN_LABEL_U8 / U16, device pointer) is changed in
  * place.  group_of_label[v] (host, n_table entries) is the set of label value v, or -1; labels >= n_table are in no
