@@ -296,7 +296,9 @@ static __device__ __forceinline__ fnn_u32x4r pair_to_b128(const f16x4 &a, const 
 // x * scale + shift of a fragment of 8 channels, the engine's normalise-on-load: scale and shift rounded to fp16, one
 // v_pk_fma_f16 per channel pair (make NORM_FP32=1: fp32 fma, then one rounding).  Every kernel that stages or consumes a
 // raw conv output goes through this form, so that paths that must agree bit for bit (fused / unfused transposed conv,
-// gather / accumulate seg head) do.
+// gather / accumulate seg head) do - except conv3d_mfma_kernel and conv3d_lds_kernel (conv3d.hip), which keep the fp32
+// rows and an fp32 fma per value: no bit identity runs through them, and the fp32 form is what holds the staging bound
+// at mean = 30 sigma on the small layers they take (tests/test_gpu_configs.py; tests/conv_ref.py stage32 restates it).
 static __device__ __forceinline__ f16x8 fnn_norm8(const f16x8 &x, const float (&sc)[8], const float (&sh)[8]) {
 #ifdef FNN_NORM_FP32
     f16x8 o;
