@@ -72,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_reorient', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -137,6 +137,7 @@ def load_library() -> C.CDLL:
     lib.fnn_confusion_counts.argtypes = [vp, C.POINTER(vp), i32, i32, i64, C.POINTER(C.c_int32), i32, i32, i32,
                                          C.POINTER(i64), vp]
     lib.fnn_decode_voxels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
+    lib.fnn_reorient.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -332,6 +333,16 @@ def decode_voxels(raw_ptr: int, nifti_datatype: int, byteswap: bool, n_vox: int,
     lib = load_library()
     check(lib.fnn_decode_voxels(raw_ptr, int(nifti_datatype), int(bool(byteswap)), int(n_vox), int(bool(scale)),
                                 float(slope), float(inter), out_ptr, stream), lib)
+
+
+def reorient(in_ptr: int, elem_bytes: int, shape_in, src_axis, flip, out_ptr: int, stream: int = 0):
+    """fnn_reorient: the C-order 3-D array of `elem_bytes`-byte elements at in_ptr (device) flipped and permuted into
+    out_ptr (device, shape ``[shape_in[a] for a in src_axis]``): ``out[i] = in[j]`` with ``j[src_axis[d]] = shape_in[src_axis[d]]
+    - 1 - i[d]`` where ``flip[d]``, else ``i[d]``.  Asynchronous on `stream`."""
+    lib = load_library()
+    check(lib.fnn_reorient(in_ptr, int(elem_bytes), (C.c_int64 * 3)(*[int(i) for i in shape_in]),
+                           (C.c_int32 * 3)(*[int(i) for i in src_axis]), (C.c_int32 * 3)(*[int(bool(i)) for i in flip]),
+                           out_ptr, stream), lib)
 
 
 def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, background_label: int,

@@ -15,6 +15,10 @@ uint8, and no host cast.
 * ``write_seg``: the header ``nibabel.Nifti1Image(seg, affine)`` saves (pinned byte for byte by the reference's output
   fixture), gzip level 1.
 
+``NiftiReorientIO`` is the reference's ``NibabelIOWithReorient`` (imageio/nibabel_reader_writer.py:101-190) on top of it:
+images brought to RAS+ behind the decode and labels back to the file's frame before their download, each by one
+``fnn_reorient`` pass (csrc/reorient.hip); nibabel's orientation rules are restated below, unpinned against nibabel.
+
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
 from __future__ import annotations
@@ -312,9 +316,13 @@ class NiftiIO:
     def stage(self, fnames: Sequence[str], slot: int = 0) -> StagedCase:
         """Headers read and checked, pinned staging buffers of slot ``slot`` sized for the case (allocated here, by the
         calling thread: the thread that later runs ``StagedCase.fill`` makes no GPU runtime call)."""
-        import torch
         hdrs = [read_header(f) for f in fnames]
         check_case(fnames, hdrs)
+        return StagedCase(fnames, hdrs, self._pinned_buffers(hdrs, slot))
+
+    def _pinned_buffers(self, hdrs: Sequence[NiftiHeader], slot: int):
+        """One pinned byte buffer of slot ``slot`` per header, grown on demand."""
+        import torch
         self._dev()
         bufs = self._pinned.setdefault(slot, [])
         for i, h in enumerate(hdrs):
@@ -323,7 +331,7 @@ class NiftiIO:
                 bufs.append(torch.empty(need, dtype=torch.uint8, pin_memory=True))
             elif bufs[i].numel() < need:
                 bufs[i] = torch.empty(need, dtype=torch.uint8, pin_memory=True)
-        return StagedCase(fnames, hdrs, bufs[:len(hdrs)])
+        return bufs[:len(hdrs)]
 
     def decode(self, staged: StagedCase):
         """A filled StagedCase -> (float32 ``[C, z, y, x]`` device tensor, properties).  Uploads every file's bytes and
@@ -415,22 +423,20 @@ def nifti1_header_bytes(shape_xyz, datatype: int, affine: np.ndarray) -> bytes:
     return bytes(h)
 
 
-def write_nifti_seg(seg, output_fname: str, properties: dict) -> None:
-    """``NibabelIO.write_seg``: ``seg`` (z, y, x) as uint8 (uint16 from a maximum of 255 on) with the case's affine
-    (``nibabel_stuff`` if the properties have it, else rebuilt from ``sitk_stuff``).  The file appears under its name
-    only when it is complete."""
-    gz = _check_ending(output_fname)
+def _label_voxels(seg) -> Tuple[np.ndarray, bool]:
+    """-> (contiguous uint8 array, or little-endian uint16 from a maximum of 255 on; is it uint16)."""
     seg = np.asarray(seg.cpu() if hasattr(seg, 'cpu') else seg)
     assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
     u16 = seg.size > 0 and np.max(seg) >= 255
-    data = np.ascontiguousarray(seg.astype('<u2' if u16 else np.uint8, copy=False))
-    if 'nibabel_stuff' in properties:
-        affine = properties['nibabel_stuff']['original_affine']
-    elif 'sitk_stuff' in properties:
-        affine = affine_from_sitk_stuff(properties['sitk_stuff'])
-    else:
-        raise RuntimeError('write_seg: the properties carry neither nibabel_stuff nor sitk_stuff')
-    head = nifti1_header_bytes(seg.shape[::-1], 512 if u16 else 2, affine)
+    return np.ascontiguousarray(seg.astype('<u2' if u16 else np.uint8, copy=False)), u16
+
+
+def write_label_file(seg, output_fname: str, affine: np.ndarray) -> None:
+    """``seg`` (z, y, x), in the file's own frame, as a NIfTI-1 label file with ``affine``.  The file appears under its name
+    only when it is complete."""
+    gz = _check_ending(output_fname)
+    data, u16 = _label_voxels(seg)
+    head = nifti1_header_bytes(data.shape[::-1], 512 if u16 else 2, affine)
     tmp = f'{output_fname}.part{os.getpid()}'
     try:
         with open(tmp, 'wb') as f:
@@ -447,6 +453,268 @@ def write_nifti_seg(seg, output_fname: str, properties: dict) -> None:
             os.remove(tmp)
 
 
+def write_nifti_seg(seg, output_fname: str, properties: dict) -> None:
+    """``NibabelIO.write_seg``: ``seg`` (z, y, x) as uint8 (uint16 from a maximum of 255 on) with the case's affine
+    (``nibabel_stuff`` if the properties have it, else rebuilt from ``sitk_stuff``).  The file appears under its name
+    only when it is complete."""
+    _check_ending(output_fname)
+    if 'nibabel_stuff' in properties:
+        affine = properties['nibabel_stuff']['original_affine']
+    elif 'sitk_stuff' in properties:
+        affine = affine_from_sitk_stuff(properties['sitk_stuff'])
+    else:
+        raise RuntimeError('write_seg: the properties carry neither nibabel_stuff nor sitk_stuff')
+    write_label_file(seg, output_fname, affine)
+
+
+# ---------------------------------------------------------------------- orientation (NibabelIOWithReorient)
+# nibabel's orientation rules, restated from its published behaviour (orientations.py: io_orientation, ornt_transform,
+# inv_ornt_aff, apply_orientation; SpatialImage.as_reoriented) - nibabel is not a dependency and none of this is pinned
+# against it.  An orientation is a (3, 2) float array: row i = (the output axis the array's axis i lies along, +1 / -1),
+# in nibabel's (x, y, z) index space.
+RAS_ORNT = np.array([[0.0, 1.0], [1.0, 1.0], [2.0, 1.0]])        # axcodes2ornt('RAS'): the identity
+
+
+def io_orientation(affine: np.ndarray) -> np.ndarray:
+    """The orientation of the array axes of ``affine`` relative to RAS+: columns of the 3x3 part divided by their norms
+    (a zero norm counts as 1), replaced by the nearest orthogonal matrix (``P @ Qs`` of the SVD, singular values below
+    ``S.max() * 3 * eps`` dropped); then the array axes in order each take the world axis with the largest absolute entry
+    of their column, the direction its sign, and that world axis is taken out for the axes that follow."""
+    rzs = np.asarray(affine, dtype=np.float64)[:3, :3]
+    zooms = np.sqrt(np.sum(rzs * rzs, axis=0))
+    zooms[zooms == 0] = 1
+    rs = rzs / zooms
+    p, s, qs = np.linalg.svd(rs, full_matrices=False)
+    keep = s > s.max() * 3 * np.finfo(s.dtype).eps
+    r = np.dot(p[:, keep], qs[keep])
+    ornt = np.full((3, 2), np.nan)
+    for in_ax in range(3):
+        col = r[:, in_ax]
+        if not np.allclose(col, 0):
+            out_ax = int(np.argmax(np.abs(col)))
+            ornt[in_ax] = [out_ax, -1.0 if col[out_ax] < 0 else 1.0]
+            r[out_ax, :] = 0
+    if np.isnan(ornt).any():
+        raise RuntimeError(f'the affine\n{np.asarray(affine)}\nhas an array axis without a direction: no orientation')
+    return ornt
+
+
+def ornt_transform(start_ornt: np.ndarray, end_ornt: np.ndarray) -> np.ndarray:
+    """The orientation that takes an array in ``start_ornt`` to ``end_ornt``."""
+    out = np.empty((3, 2))
+    for end_in, (end_out, end_flip) in enumerate(end_ornt):
+        for start_in, (start_out, start_flip) in enumerate(start_ornt):
+            if end_out == start_out:
+                out[start_in] = [end_in, 1.0 if start_flip == end_flip else -1.0]
+                break
+        else:
+            raise ValueError(f'Unable to find out axis {end_out} in start_ornt')
+    return out
+
+
+def inv_ornt_aff(ornt: np.ndarray, shape_xyz) -> np.ndarray:
+    """The 4x4 matrix from indices of the array after ``ornt`` to indices of the array before it (``shape_xyz``: before)."""
+    shape = np.array(shape_xyz[:3], dtype=np.float64)
+    undo_reorder = np.eye(4)[[int(i) for i in ornt[:, 0]] + [3], :]
+    undo_flip = np.diag(list(ornt[:, 1]) + [1.0])
+    center = -(shape - 1) / 2.0
+    undo_flip[:3, 3] = ornt[:, 1] * center - center
+    return np.dot(undo_flip, undo_reorder)
+
+
+def apply_orientation(arr_xyz: np.ndarray, ornt: np.ndarray) -> np.ndarray:
+    """numpy's route, in nibabel's index space: every axis whose direction is -1 flipped, then ``transpose(argsort(ornt[:, 0]))``."""
+    out = np.asarray(arr_xyz)
+    for ax in range(3):
+        if ornt[ax, 1] == -1:
+            out = np.flip(out, ax)
+    return out.transpose(np.argsort(ornt[:, 0]))
+
+
+def is_identity_ornt(ornt: np.ndarray) -> bool:
+    return bool(np.array_equal(ornt, RAS_ORNT))
+
+
+def reorient_args(ornt: np.ndarray) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """``(src_axis, flip)`` of ``fnn_reorient`` (and of ``reorient_on_host``) for the engine's arrays - the one place where
+    nibabel's index space meets the engine's.  An engine array is (z, y, x): its axis d is nibabel's axis 2 - d.  The
+    reoriented array's nibabel axis o is the original's axis ``inv[o]`` (``inv = argsort(ornt[:, 0])``), counted backwards
+    when ``ornt[inv[o], 1]`` is -1; so output axis d = 2 - o reads input axis ``2 - inv[2 - d]``."""
+    inv = np.argsort(ornt[:, 0])
+    src = tuple(2 - int(inv[2 - d]) for d in range(3))
+    flip = tuple(int(ornt[int(inv[2 - d]), 1] == -1) for d in range(3))
+    return src, flip
+
+
+def reorient_on_host(arr_zyx: np.ndarray, src_axis, flip) -> np.ndarray:
+    """numpy's statement of fnn_reorient: ``out[i] = arr[j]``, ``j[src_axis[d]] = i[d]``, counted backwards where ``flip[d]``."""
+    out = np.asarray(arr_zyx).transpose(src_axis)
+    axes = tuple(d for d in range(3) if flip[d])
+    return np.ascontiguousarray(np.flip(out, axes) if axes else out)
+
+
+class Reorientation:
+    """What ``as_reoriented(io_orientation(affine))`` does to one image of ``shape_xyz`` voxels, and the way back."""
+
+    def __init__(self, affine: np.ndarray, shape_xyz, file_spacing: Optional[Sequence[float]] = None):
+        self.original_affine = np.asarray(affine, dtype=np.float64)
+        self.shape_xyz = tuple(int(i) for i in shape_xyz)
+        self.ornt = io_orientation(self.original_affine)
+        self.identity = is_identity_ornt(self.ornt)
+        self.src_axis, self.flip = reorient_args(self.ornt)
+        shape_zyx = self.shape_xyz[::-1]
+        self.ras_shape = tuple(shape_zyx[a] for a in self.src_axis)          # (z, y, x) of the reoriented array
+        if self.identity:
+            # nibabel returns the image itself: its affine, and the zooms the file states
+            self.reoriented_affine = self.original_affine.copy()
+            self.spacing = None if file_spacing is None else [float(i) for i in file_spacing]
+        else:
+            self.reoriented_affine = np.dot(self.original_affine, inv_ornt_aff(self.ornt, self.shape_xyz))
+            self.spacing = None
+        if self.spacing is None:
+            # the new image's header takes its zooms from the affine (set_qform): float32 column norms, reversed
+            norms = np.sqrt(np.sum(self.reoriented_affine[:3, :3] ** 2, axis=0))
+            self.spacing = [float(np.float32(i)) for i in norms[::-1]]
+
+
+def restore_orientation(properties: dict, ras_shape_zyx) -> Tuple[Tuple[int, int, int], Tuple[int, int, int], np.ndarray]:
+    """``NibabelIOWithReorient.write_seg``'s way back for a RAS-frame array of ``ras_shape_zyx``: ``(src_axis, flip)`` that
+    bring it to the file's frame, and the restored affine ``reoriented_affine @ inv_ornt_aff(from_canonical, ras shape)``
+    the written header carries (the reference saves that one, not ``original_affine``)."""
+    stuff = properties['nibabel_stuff']
+    from_canonical = ornt_transform(RAS_ORNT, io_orientation(stuff['original_affine']))
+    src_axis, flip = reorient_args(from_canonical)
+    reoriented = np.asarray(stuff['reoriented_affine'], dtype=np.float64)
+    if is_identity_ornt(from_canonical):
+        return src_axis, flip, reoriented
+    restored = np.dot(reoriented, inv_ornt_aff(from_canonical, tuple(ras_shape_zyx)[::-1]))
+    return src_axis, flip, restored
+
+
+class FileFrameLabels:
+    """A label map already in its file's frame, with the affine its header takes: what the calling thread of the file
+    pipeline hands to the writer thread, which then only casts, compresses and writes."""
+
+    def __init__(self, voxels_zyx: np.ndarray, affine: np.ndarray):
+        self.voxels, self.affine = voxels_zyx, affine
+
+
+def check_case_reoriented(fnames: Sequence[str], orients: Sequence[Reorientation]) -> None:
+    """The files of one case after reorientation: equal shapes and spacings (RuntimeError), equal reoriented affines (a
+    warning) - as the reference's NibabelIOWithReorient."""
+    if any(o.ras_shape != orients[0].ras_shape for o in orients):
+        raise RuntimeError(f'Not all input images have the same shape! Shapes: {[o.ras_shape for o in orients]} '
+                           f'Image files: {list(fnames)}')
+    if any(not np.array_equal(o.reoriented_affine, orients[0].reoriented_affine) for o in orients):
+        warnings.warn(f'Not all input images have the same reoriented_affines! Affines: '
+                      f'{[o.reoriented_affine for o in orients]} Image files: {list(fnames)}. It is up to you to decide '
+                      f'whether that\'s a problem.')
+    if any(o.spacing != orients[0].spacing for o in orients):
+        raise RuntimeError(f'Not all input images have the same spacing_for_nnunet! This might be caused by them not '
+                           f'having the same affine. spacings_for_nnunet: {[o.spacing for o in orients]} '
+                           f'Image files: {list(fnames)}')
+
+
+class NiftiReorientIO(NiftiIO):
+    """The reference's ``NibabelIOWithReorient`` (imageio/nibabel_reader_writer.py:101-190): every image is brought to
+    RAS+ on reading and the label map back to the file's frame on writing.  On the device both are one ``fnn_reorient``
+    pass (csrc/reorient.hip) behind ``fnn_decode_voxels`` and before the download of the labels; an image that is RAS+
+    already takes neither the pass nor the temporary."""
+
+    @staticmethod
+    def _orient(hdrs: Sequence[NiftiHeader]) -> List[Reorientation]:
+        return [Reorientation(h.affine, h.shape_xyz, h.spacing) for h in hdrs]
+
+    @staticmethod
+    def _properties(o: Reorientation) -> dict:
+        return {'nibabel_stuff': {'original_affine': o.original_affine.copy(), 'reoriented_affine': o.reoriented_affine.copy()},
+                'spacing': list(o.spacing)}
+
+    def stage(self, fnames: Sequence[str], slot: int = 0) -> StagedCase:
+        """As ``NiftiIO.stage``; the case is checked after reorientation and carries its ``Reorientation`` per file."""
+        hdrs = [read_header(f) for f in fnames]
+        orients = self._orient(hdrs)
+        check_case_reoriented(fnames, orients)
+        staged = StagedCase(fnames, hdrs, self._pinned_buffers(hdrs, slot))
+        staged.orients = orients
+        return staged
+
+    def decode(self, staged: StagedCase):
+        """A filled StagedCase -> (float32 ``[C, *ras_shape]`` device tensor, properties): every file decoded into a
+        temporary in the file's frame and reoriented into its channel (decoded straight into the channel when the file
+        is RAS+ already).  Synchronises: the staging buffers are free again on return."""
+        import torch
+        dev = self._dev()
+        o0 = staged.orients[0]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            out = torch.empty((len(staged.hdrs), *o0.ras_shape), dtype=torch.float32, device=dev)
+            keep = []
+            for c, (h, o, b) in enumerate(zip(staged.hdrs, staged.orients, staged.buffers)):
+                raw = torch.empty(max(16, h.n_bytes), dtype=torch.uint8, device=dev)
+                raw[:h.n_bytes].copy_(b[:h.n_bytes], non_blocking=True)
+                keep.append(raw)
+                if o.identity:
+                    capi.decode_voxels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter,
+                                       out[c].data_ptr(), stream.cuda_stream)
+                    continue
+                tmp = torch.empty(h.shape, dtype=torch.float32, device=dev)
+                keep.append(tmp)
+                capi.decode_voxels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter,
+                                   tmp.data_ptr(), stream.cuda_stream)
+                capi.reorient(tmp.data_ptr(), 4, h.shape, o.src_axis, o.flip, out[c].data_ptr(), stream.cuda_stream)
+            stream.synchronize()
+        return out, self._properties(o0)
+
+    def read_images(self, image_fnames: Union[List[str], Tuple[str, ...]], on_device: bool = True):
+        image_fnames = [str(f) for f in image_fnames]
+        if on_device:
+            return self.decode(self.stage(image_fnames).fill())
+        hdrs = [read_header(f) for f in image_fnames]
+        orients = self._orient(hdrs)
+        check_case_reoriented(image_fnames, orients)
+        images = []
+        for f, h, o in zip(image_fnames, hdrs, orients):
+            raw = np.empty(h.n_bytes, dtype=np.uint8)
+            read_voxel_bytes(f, h, raw)
+            images.append(reorient_on_host(decode_on_host(h, raw), o.src_axis, o.flip)[None])
+        return np.vstack(images), self._properties(orients[0])
+
+    def labels_to_file_frame(self, seg, properties: dict) -> FileFrameLabels:
+        """A RAS-frame label map (z, y, x) -> its file's frame with the restored affine.  A device tensor (uint8, or the
+        two-byte int16 / uint16) is reoriented by ``fnn_reorient`` on the current stream and then downloaded; a numpy array
+        is reoriented by numpy and no GPU call is made."""
+        src_axis, flip, restored = restore_orientation(properties, tuple(seg.shape))
+        original = np.asarray(properties['nibabel_stuff']['original_affine'], dtype=np.float64)
+        if not np.allclose(original, restored):
+            warnings.warn(f'Restored affine does not match original affine.\nOriginal affine\n{original}\n'
+                          f'Restored affine\n{restored}')
+        if not hasattr(seg, 'data_ptr'):
+            return FileFrameLabels(reorient_on_host(np.asarray(seg), src_axis, flip), restored)
+        import torch
+        if seg.device.type != 'cuda':
+            return FileFrameLabels(reorient_on_host(seg.numpy(), src_axis, flip), restored)
+        if src_axis == (0, 1, 2) and not any(flip):
+            return FileFrameLabels(seg.cpu().numpy(), restored)
+        if seg.element_size() not in (1, 2, 4):
+            raise NotImplementedError(f'label maps of {seg.dtype} are not reoriented on the device (1-, 2- and 4-byte elements are)')
+        with torch.cuda.device(seg.device):
+            seg = seg.contiguous()
+            out = torch.empty(tuple(seg.shape[a] for a in src_axis), dtype=seg.dtype, device=seg.device)
+            capi.reorient(seg.data_ptr(), seg.element_size(), tuple(seg.shape), src_axis, flip, out.data_ptr(),
+                          torch.cuda.current_stream(seg.device).cuda_stream)
+            return FileFrameLabels(out.cpu().numpy(), restored)
+
+    def write_seg(self, seg, output_fname: str, properties: dict) -> None:
+        """``seg`` is in the RAS frame (z, y, x) like the reference's, or a ``FileFrameLabels`` made earlier by
+        ``labels_to_file_frame``.  The header carries the restored affine."""
+        _check_ending(output_fname)
+        if not isinstance(seg, FileFrameLabels):
+            assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
+            seg = self.labels_to_file_frame(seg, properties)
+        write_label_file(seg.voxels, output_fname, seg.affine)
+
+
 # ---------------------------------------------------------------------- which class a plan or a file ending names
 _NIFTI_CLASS_NAMES = ('NibabelIO', 'SimpleITKIO', 'NiftiIO')
 _OTHER_CLASS_NAMES = ('NibabelIOWithReorient', 'SimpleITKIOWithReorient', 'NaturalImage2DIO', 'Tiff3DIO')
@@ -459,7 +727,7 @@ def reader_writer_class_by_name(name: str):
         return NiftiIO
     if name in _OTHER_CLASS_NAMES:
         raise NotImplementedError(f'image reader-writer {name} is not implemented (NibabelIO and SimpleITKIO are, for '
-                                  f'.nii and .nii.gz files)')
+                                  f'.nii and .nii.gz files; prediction_reader_writer_class also serves NibabelIOWithReorient)')
     raise NotImplementedError(f"Unable to find reader writer class '{name}': this engine implements NibabelIO and "
                               f"SimpleITKIO for .nii and .nii.gz files")
 
@@ -477,3 +745,20 @@ def determine_reader_writer_from_dataset_json(dataset_json: dict):
     if name is not None and name != 'None':
         return reader_writer_class_by_name(name)
     return determine_reader_writer_from_file_ending(dataset_json['file_ending'])
+
+
+def prediction_reader_writer_class(plans_manager, dataset_json: dict):
+    """The reader-writer class ``nnUNetPredictor`` predicts from files with.  ``NibabelIOWithReorient`` - named by the plans'
+    ``image_reader_writer`` or by the dataset's ``overwrite_image_reader_writer`` - is ``NiftiReorientIO``; everything else
+    is what the registry functions above say: the plans' class, or for plans that name none the dataset's.
+    (``SimpleITKIOWithReorient`` stays refused: it rests on ITK's DICOMOrient letters and on ITK's choice between qform and
+    sform, neither of which can be checked here.)"""
+    plans_name = plans_manager.plans.get('image_reader_writer')
+    overwrite = dataset_json.get('overwrite_image_reader_writer')
+    if 'SimpleITKIOWithReorient' in (plans_name, overwrite):
+        return reader_writer_class_by_name('SimpleITKIOWithReorient')                 # (raises)
+    if 'NibabelIOWithReorient' in (plans_name, overwrite):
+        return NiftiReorientIO
+    if plans_name is not None:
+        return plans_manager.image_reader_writer_class
+    return determine_reader_writer_from_dataset_json(dataset_json)

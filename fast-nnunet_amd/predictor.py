@@ -169,6 +169,21 @@ class nnUNetPredictor(object):
             labels = apply_postprocessing(labels, *self._postprocessing)
         return labels.cpu().numpy().astype(np.uint16 if u16 else np.uint8)
 
+    def _labels_out(self, labels: torch.Tensor, u16: bool, props: dict, for_file: bool):
+        """The labels of a case on the host.  When they are bound for a file and the reader-writer reorients, they are brought
+        to the file's frame on the device first (after the postprocessing, which sees the RAS frame) and come back as the
+        ``FileFrameLabels`` its ``write_seg`` takes: the writer thread does no strided copy."""
+        rw = self._reader_writer() if for_file else None
+        if rw is None or not hasattr(rw, 'labels_to_file_frame'):
+            return self._labels_to_host(labels, u16)
+        if self._postprocessing is not None:
+            from .postprocessing import apply_postprocessing
+            labels = apply_postprocessing(labels, *self._postprocessing)
+        labels = labels.to(torch.int16) if u16 else labels.to(torch.uint8)       # (int16: the two bytes of the uint16 file type)
+        out = rw.labels_to_file_frame(labels, props)
+        out.voxels = out.voxels.view(np.uint16) if u16 else out.voxels
+        return out
+
     @staticmethod
     def auto_detect_available_folds(model_training_output_dir, checkpoint_name):
         print('use_folds is None, attempting to auto detect available folds')
@@ -306,7 +321,7 @@ class nnUNetPredictor(object):
         result is written instead (``<truncated><file_ending>``, and with probabilities ``.npz`` and ``.pkl``) and None
         is returned."""
         seg, probs, props = self._predict_case(input_image, image_properties, segmentation_previous_stage,
-                                               save_or_return_probabilities)
+                                               save_or_return_probabilities, for_file=output_file_truncated is not None)
         if output_file_truncated is not None:
             # export_prediction_from_logits (export_prediction.py:74-110): <truncated><file_ending> through the plans'
             # reader-writer, with probabilities also <truncated>.npz and the properties as <truncated>.pkl; returns None
@@ -315,9 +330,10 @@ class nnUNetPredictor(object):
         return (seg, probs) if save_or_return_probabilities else seg
 
     def _predict_case(self, input_image, image_properties: dict, segmentation_previous_stage=None,
-                      save_or_return_probabilities: bool = False):
+                      save_or_return_probabilities: bool = False, for_file: bool = False):
         """-> (labels on the raw grid (numpy), float32 probabilities or None, the case's properties after preprocessing).
-        ``input_image`` is a numpy array or a tensor (a resident one stays where it is)."""
+        ``input_image`` is a numpy array or a tensor (a resident one stays where it is).  ``for_file``: the labels go to
+        the reader-writer's ``write_seg`` (``_labels_out``); the probabilities stay in the frame of ``input_image``."""
         pp, data, props = self._preprocess_case(input_image, image_properties, segmentation_previous_stage)
         if self.verbose:
             print('predicting')
@@ -326,17 +342,17 @@ class nnUNetPredictor(object):
         if same_grid and not save_or_return_probabilities:
             seg = self.predict_segmentation_from_preprocessed_data(data)
             out = pp.revert_labels(seg, props, self.plans_manager, self.label_manager)
-            return self._labels_to_host(out, u16), None, props
+            return self._labels_out(out, u16, props, for_file), None, props
         logits = self._predict_case_logits(data)
         if self.verbose:
             print('resampling to original shape')
         if save_or_return_probabilities:
             out, probs = pp.convert_predicted_logits_to_segmentation_and_probabilities(
                 logits, self, self.plans_manager, self.configuration_manager, props)
-            return self._labels_to_host(out, u16), probs.cpu().numpy(), props
+            return self._labels_out(out, u16, props, for_file), probs.cpu().numpy(), props
         out = pp.convert_predicted_logits_to_segmentation_with_correct_shape(logits, self, self.plans_manager,
                                                                              self.configuration_manager, props)
-        return self._labels_to_host(out, u16), None, props
+        return self._labels_out(out, u16, props, for_file), None, props
 
     def _preprocess_case(self, input_image: np.ndarray, image_properties: dict, segmentation_previous_stage=None):
         """-> (DevicePreprocessor, network input on the device, properties) for predict_single_npy_array."""
@@ -432,14 +448,12 @@ class nnUNetPredictor(object):
     # ----------------------------------------------------------------- files
     def _reader_writer(self):
         """The plans' ``image_reader_writer`` class (``PlansManager.image_reader_writer_class``), or - for plans that do
-        not name one - the class the dataset's file ending selects; one instance per predictor (it owns pinned staging)."""
+        not name one - the class the dataset's file ending selects, and ``NiftiReorientIO`` where either names
+        ``NibabelIOWithReorient`` (``imageio.prediction_reader_writer_class``); one instance per predictor (it owns pinned
+        staging)."""
         if self._rw is None:
-            from .imageio import determine_reader_writer_from_dataset_json
-            if 'image_reader_writer' in self.plans_manager.plans:
-                cls = self.plans_manager.image_reader_writer_class
-            else:
-                cls = determine_reader_writer_from_dataset_json(self.dataset_json)
-            self._rw = cls(self.device)
+            from .imageio import prediction_reader_writer_class
+            self._rw = prediction_reader_writer_class(self.plans_manager, self.dataset_json)(self.device)
         return self._rw
 
     def _export_files(self, seg: np.ndarray, probs: Optional[np.ndarray], props: dict, output_file_truncated: str):
@@ -530,13 +544,13 @@ class nnUNetPredictor(object):
             0 if sequential else call_kwargs['part_id'], 1 if sequential else call_kwargs['num_parts'],
             call_kwargs['save_probabilities'])
 
-    def _run_staged_case(self, rw, staged, staged_prev, save_probabilities: bool):
+    def _run_staged_case(self, rw, staged, staged_prev, save_probabilities: bool, for_file: bool = False):
         """The GPU part of one case: staged file bytes -> (labels, probabilities or None, properties)."""
         data, props = rw.decode(staged)
         seg_prev = rw.decode(staged_prev)[0] if staged_prev is not None else None
         if staged.fnames and self.verbose:
             print(f'predicting {os.path.basename(staged.fnames[0])}')
-        return self._predict_case(data, props, seg_prev, save_probabilities)
+        return self._predict_case(data, props, seg_prev, save_probabilities, for_file=for_file)
 
     @staticmethod
     def _result(seg, probs, save_probabilities):
@@ -614,7 +628,8 @@ class nnUNetPredictor(object):
                     job.result()                                 # case i's bytes are in pinned memory (or the read failed)
                 # case i + 1 is read while case i runs; its slot's buffers were released when case i - 1 was decoded
                 nxt = stage(i + 1) if i + 1 < len(cases) else None
-                seg, probs, props = self._run_staged_case(rw, staged, staged_prev, save_probabilities)
+                seg, probs, props = self._run_staged_case(rw, staged, staged_prev, save_probabilities,
+                                                          for_file=truncated[i] is not None)
                 if truncated[i] is None:
                     ret.append(self._result(seg, probs, save_probabilities))
                     continue

@@ -414,6 +414,20 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
 int fnn_decode_voxels(const void *raw, int nifti_datatype, int byteswap, int64_t n_vox, int scale, double slope,
                       double inter, float *out, void *stream);
 
+/* Flip and permute the axes of a C-order 3-D array on the device (additive in ABI 4): what the reference's
+ * NibabelIOWithReorient does with numpy on the host (as_reoriented on read, and again on the label map on write).
+ * in: shape_in[0..2] elements of elem_bytes bytes (1, 2 or 4: uint8 / uint16 labels, float32 images; anything else is
+ * FNN_E_UNSUPPORTED).  out has the shape shape_in[src_axis[0]], shape_in[src_axis[1]], shape_in[src_axis[2]] and
+ *   out[i0, i1, i2] = in[j],  j[src_axis[d]] = flip[d] ? shape_in[src_axis[d]] - 1 - i_d : i_d
+ * - numpy's flip and transpose, bit for bit.  Both pointers are device pointers aligned to the element only (channel c of
+ * an odd-sized [C, z, y, x] tensor); nothing is read or written outside the two arrays.  FNN_E_INVALID before any launch:
+ * NULL or host pointers, pointers not aligned to the element, a src_axis that is no permutation of 0, 1, 2, a negative
+ * extent, overlapping in and out ranges; FNN_E_UNSUPPORTED: more elements than one launch addresses.  An extent of 0
+ * (no elements) returns 0 with nothing launched.  src_axis[2] == 2 is a row copy (reversed rows when flip[2]), anything
+ * else a tiled transpose through LDS.  One pass, no scratch memory, asynchronous on `stream`. */
+int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_in[3], const int32_t src_axis[3],
+                 const int32_t flip[3], void *out, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */

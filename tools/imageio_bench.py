@@ -2,12 +2,15 @@
 DevicePreprocessor.run_case_npy takes costs, split into its parts, next to the route a caller had before NiftiIO (host decode
 with numpy, astype(float32), then predict_single_npy_array's upload of the float32 array); the decode kernel's rate next to
 a plain device copy of the same bytes; the write of a label map; and predict_from_files (reader and writer threads)
-against predict_from_files_sequential on four cases.
+against predict_from_files_sequential on four cases; and (``--section reorient`` runs these rows alone) fnn_reorient on an
+n^3 case - float32 forward and uint8 backward, one orientation per kernel path - next to a device-to-device copy of the
+same bytes and to numpy's flip / transpose on the host.
 
 The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, so that gzip has something to do), written
 as .nii.gz (level 1, like the writer) and as .nii.
 
-usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192] [--out FILE]
+usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
+                                                          [--section all|reorient] [--out FILE]
 """
 import argparse
 import gzip
@@ -57,6 +60,32 @@ def synthetic_ct(shape, seed):
     return v.astype(np.int16)
 
 
+def bench_reorient(n, reps, dev, say, row):
+    """fnn_reorient on n^3 elements: the decoded float32 voxels into the RAS frame (forward) and the uint8 labels back
+    (backward), a flip-only orientation (the row path) and one that moves the fastest axis (the tiled transpose)."""
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import imageio as fio
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    say(f'--- fnn_reorient, {n}^3 elements; events around the call, the first call is the warm-up; numpy by wall clock')
+    shape = (n, n, n)
+    rng = np.random.default_rng(5)
+    for what, dt, tdt in (('float32 forward', np.float32, torch.float32), ('uint8 backward', np.uint8, torch.uint8)):
+        host = rng.integers(0, 200, shape, dtype=np.uint8).astype(dt)
+        src = torch.from_numpy(host).to(dev)
+        dst = torch.empty_like(src)
+        moved = 2 * host.nbytes
+        t = events(lambda: dst.copy_(src), reps, dev)
+        row(f'{what}: device-to-device copy of the same bytes ({host.nbytes / 2 ** 20:.0f} MiB)', t, f'  {moved / t[0] / 1e6:.0f} GB/s')
+        for path, src_axis, flip in (('flip only (rows)', (0, 1, 2), (0, 1, 1)), ('fastest axis moved (transpose)', (2, 0, 1), (0, 1, 0))):
+            t = events(lambda: capi.reorient(src.data_ptr(), host.itemsize, shape, src_axis, flip, dst.data_ptr(), stream), reps, dev)
+            row(f'{what}: fnn_reorient, {path}', t,
+                f'  {moved / t[0] / 1e6:.0f} GB/s = {100 * moved / t[0] / 1e6 / (COPY_TBS * 1e3):.1f} % of {COPY_TBS} TB/s')
+            same = np.array_equal(dst.cpu().numpy().reshape(-1)[::4099], fio.reorient_on_host(host, src_axis, flip).reshape(-1)[::4099])
+            tn = wall(lambda: fio.reorient_on_host(host, src_axis, flip), reps)
+            row(f'{what}: numpy flip / transpose on the host, {path}', tn[:3], f'  {tn[0] / t[0]:.0f}x the kernel; equal samples: {same}')
+        del src, dst, host
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
@@ -64,6 +93,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
+    ap.add_argument('--section', choices=('all', 'reorient'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -84,6 +114,11 @@ def main():
 
     def row(name, t, extra=''):
         say(f'{name:<66s}: {t[0]:9.2f} ms  (min {t[1]:.2f} max {t[2]:.2f}){extra}')
+
+    if a.section == 'reorient':
+        bench_reorient(n, a.reps, dev, say, row)
+        write_out(a.out, lines)
+        return
 
     with tempfile.TemporaryDirectory() as tmp:
         vol = synthetic_ct((n, n, n), 1)
@@ -155,6 +190,8 @@ def main():
             row(f'write_seg {name}, uint8 {n}^3 ({os.path.getsize(os.path.join(tmp, name)) / 2 ** 20:.1f} MiB on disk)', t[:3])
         del vol, seg
 
+        bench_reorient(n, a.reps, dev, say, row)
+
         say(f'--- predict_from_files on {a.cases} cases of {tuple(a.case_shape)} int16 .nii.gz, toy network (patch 32 x 64 x 64), no mirroring')
         patch = (32, 64, 64)
         spec = UNetSpec('plain', 1, 3, [16, 32, 32], [(3, 3, 3)] * 3, [(1, 1, 1), (2, 2, 2), (2, 2, 2)], [2, 2, 2], [2, 2])
@@ -185,9 +222,13 @@ def main():
         same = all(open(os.path.join(tmp, 'seq', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'thr', f'case{i}.nii.gz'), 'rb').read()
                    for i in range(a.cases))
         say(f'the two forms wrote identical files: {same}')
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
+    write_out(a.out, lines)
+
+
+def write_out(out, lines):
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
 
 
