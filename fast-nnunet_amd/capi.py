@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -72,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_reorient', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -138,6 +138,9 @@ def load_library() -> C.CDLL:
                                          C.POINTER(i64), vp]
     lib.fnn_decode_voxels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
     lib.fnn_reorient.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
+    lib.fnn_deflate_bound.argtypes = [i64]
+    lib.fnn_deflate_bound.restype = i64
+    lib.fnn_deflate_labels.argtypes = [vp, i32, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_uint32), vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -343,6 +346,23 @@ def reorient(in_ptr: int, elem_bytes: int, shape_in, src_axis, flip, out_ptr: in
     check(lib.fnn_reorient(in_ptr, int(elem_bytes), (C.c_int64 * 3)(*[int(i) for i in shape_in]),
                            (C.c_int32 * 3)(*[int(i) for i in src_axis]), (C.c_int32 * 3)(*[int(bool(i)) for i in flip]),
                            out_ptr, stream), lib)
+
+
+def deflate_bound(n_bytes: int) -> int:
+    """fnn_deflate_bound: an output capacity that always suffices for n_bytes of labels (host only)."""
+    return int(load_library().fnn_deflate_bound(int(n_bytes)))
+
+
+def deflate_labels(in_ptr: int, in_elem_bytes: int, n_elems: int, narrow_if_fits: bool, out_ptr: int, out_cap: int,
+                   stream: int = 0) -> Tuple[int, int, int]:
+    """fnn_deflate_labels: n_elems labels of 1 or 2 bytes at in_ptr (device, 16-byte aligned) -> a raw-deflate fragment at
+    out_ptr (device, out_cap >= deflate_bound(n_elems * in_elem_bytes)).  Returns ``(bytes written, bytes per element in the
+    file, CRC-32 of the file bytes)``; synchronises `stream`."""
+    lib = load_library()
+    out_bytes, file_elem, crc = C.c_int64(-1), C.c_int(0), C.c_uint32(0)
+    check(lib.fnn_deflate_labels(in_ptr, int(in_elem_bytes), int(n_elems), int(bool(narrow_if_fits)), out_ptr, int(out_cap),
+                                 C.byref(out_bytes), C.byref(file_elem), C.byref(crc), stream), lib)
+    return int(out_bytes.value), int(file_elem.value), int(crc.value)
 
 
 def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, background_label: int,

@@ -1,0 +1,129 @@
+// deflate_core.h - what one lane of the deflate encoder does with its segment (csrc/deflate.hip), written so that the same
+// text compiles for the host: the token rule, the fixed-Huffman codes, the bit writer and the CRC-32 field arithmetic.
+// tests/deflate_ref.py restates all of it in Python; the GPU tests compare the two byte for byte.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define DF_HD __host__ __device__ __forceinline__
+#else
+#define DF_HD inline
+#endif
+
+constexpr int DF_SEG = 256;                     // input bytes a lane tokenises on its own
+constexpr int DF_LANES = 64;
+constexpr int DF_CHUNK = DF_SEG * DF_LANES;     // input bytes of one wave: one independent, byte-aligned piece of the stream
+constexpr int DF_PITCH = DF_SEG / 4 + 1;        // dwords between two segments in LDS: odd, so that lane l's dword i lies on bank
+                                                // (l + i) % 32 and the 32 lanes ds_read_b32 serves at once fall on 32 banks
+constexpr uint32_t DF_POLY = 0xEDB88320u;       // CRC-32, reflected
+constexpr int DF_FRAME_BITS = 3 + 7 + 3;        // block header, end-of-block code, header of the empty stored block
+// the most a chunk takes: every byte a 9-bit literal, the framing rounded up to a byte, 00 00 FF FF
+constexpr int DF_CHUNK_MAX_BYTES = (DF_CHUNK * 9 + DF_FRAME_BITS + 7) / 8 + 4;
+static_assert(DF_SEG <= 258, "a run inside one segment must fit one match");
+
+// a * b modulo the CRC-32 polynomial in the reflected representation (bit 31 is x^0)
+DF_HD uint32_t df_mulmod(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = (b >> 1) ^ ((b & 1) ? DF_POLY : 0u);
+    }
+    return p;
+}
+
+// x^(8 n_bytes) from x2k[k] = x^(2^k): repeated squaring, one product per set bit of the exponent
+DF_HD uint32_t df_xpow8(unsigned long long n_bytes, const uint32_t *x2k) {
+    uint32_t r = 0;
+    unsigned long long e = n_bytes;
+    for (int k = 3; e; ++k, e >>= 1)
+        if (e & 1) r = r ? df_mulmod(r, x2k[k]) : x2k[k];
+    return r ? r : 0x80000000u;
+}
+
+DF_HD unsigned df_rev(unsigned v, int n) { return __builtin_bitreverse32(v) >> (32 - n); }
+
+// the fixed code of a literal byte (RFC 1951 3.2.6), as the bits go into the stream
+DF_HD void df_literal(unsigned v, unsigned &code, int &n) {
+    if (v < 144) { code = df_rev(0x30 + v, 8); n = 8; }
+    else { code = df_rev(0x190 + v - 144, 9); n = 9; }
+}
+
+// a match of `len` (3 .. 258) at the distance of one element (ELEM = 1 or 2 bytes: distance codes 0 and 1, five bits, no
+// extra bits): length symbol, its extra bits, distance code
+template <int ELEM> DF_HD void df_match(int len, unsigned &code, int &n) {
+    int sym, eb = 0;
+    unsigned extra = 0;
+    const int l = len - 3;
+    if (l < 8) sym = 257 + l;
+    else if (len == 258) sym = 285;
+    else {
+        eb = 29 - __builtin_clz((unsigned)l);           // floor(log2(l)) - 2: 1 .. 5
+        sym = 261 + 4 * eb + ((l >> eb) & 3);
+        extra = (unsigned)l & ((1u << eb) - 1);
+    }
+    if (sym < 280) { code = df_rev(sym - 256, 7); n = 7; }
+    else { code = df_rev(0xC0 + sym - 280, 8); n = 8; }
+    code |= extra << n;
+    n += eb;
+    code |= (ELEM == 2 ? 16u : 0u) << n;                 // the 5-bit distance code, reversed
+    n += 5;
+}
+
+// The token rule.  A byte that equals the byte one element before it (inside the segment) extends the current run; a run
+// of 3 or more is one match, a shorter one its literals.  The greedy statement of tests/deflate_ref.py gives the same
+// tokens, because a run never exceeds DF_SEG - ELEM < 258.  `seg`: the segment's dwords; `len` <= DF_SEG bytes.
+template <int ELEM, class Sink> DF_HD void df_walk(const unsigned *seg, int len, Sink &s) {
+    int run = 0;
+    unsigned h1 = 0, h2 = 0, w = 0;                      // the two bytes before q
+    auto flush = [&]() {
+        if (run >= 3) s.match(run);
+        else if (run == 2) { s.literal(h2); s.literal(h1); }
+        else if (run == 1) s.literal(h1);
+    };
+    for (int q = 0; q < len; ++q) {
+        if ((q & 3) == 0) w = seg[q >> 2];
+        const unsigned b = w & 255u;
+        w >>= 8;
+        s.byte(b);
+        if (q >= ELEM && b == (ELEM == 1 ? h1 : h2)) ++run;
+        else { flush(); s.literal(b); run = 0; }
+        h2 = h1;
+        h1 = b;
+    }
+    flush();
+}
+
+// pass 1: the bits a segment takes, and its CRC-32 (tab: the 256-entry byte table)
+template <int ELEM> struct DfCount {
+    const uint32_t *tab;
+    unsigned bits = 0;
+    uint32_t crc = 0xFFFFFFFFu;
+    DF_HD void byte(unsigned b) { crc = tab[(crc ^ b) & 255u] ^ (crc >> 8); }
+    DF_HD void literal(unsigned v) { bits += v < 144 ? 8 : 9; }
+    DF_HD void match(int len) { unsigned c; int n; df_match<ELEM>(len, c, n); bits += n; }
+};
+
+// pass 2: the bits themselves, OR-ed into a zeroed buffer from bit `pos` on.  Neighbouring lanes share the dword in which
+// one's bits end and the next one's begin: the OR is atomic on the device, and its result does not depend on the order.
+template <int ELEM> struct DfEmit {
+    unsigned *buf;
+    int w, n;
+    unsigned long long acc = 0;
+    DF_HD DfEmit(unsigned *b, unsigned pos) : buf(b), w((int)(pos >> 5)), n((int)(pos & 31)) {}
+    DF_HD void word_or(unsigned *p, unsigned v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        atomicOr(p, v);
+#else
+        *p |= v;
+#endif
+    }
+    DF_HD void put(unsigned v, int nb) {                 // n < 32 and nb <= 18
+        acc |= (unsigned long long)v << n;
+        n += nb;
+        if (n >= 32) { word_or(buf + w, (unsigned)acc); ++w; acc >>= 32; n -= 32; }
+    }
+    DF_HD void finish() { if (n > 0) word_or(buf + w, (unsigned)acc); }
+    DF_HD void byte(unsigned) {}
+    DF_HD void literal(unsigned v) { unsigned c; int nb; df_literal(v, c, nb); put(c, nb); }
+    DF_HD void match(int len) { unsigned c; int nb; df_match<ELEM>(len, c, nb); put(c, nb); }
+};

@@ -19,6 +19,10 @@ uint8, and no host cast.
 images brought to RAS+ behind the decode and labels back to the file's frame before their download, each by one
 ``fnn_reorient`` pass (csrc/reorient.hip); nibabel's orientation rules are restated below, unpinned against nibabel.
 
+``NiftiIO.compress_labels`` is the opt-in write route that never downloads the label map: ``fnn_deflate_labels``
+(csrc/deflate.hip) turns the device labels into a deflate fragment, and ``write_seg`` only puts the gzip member together
+around it (``DeviceCompressedLabels``, ``compressed_label_file_bytes``).
+
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
 from __future__ import annotations
@@ -374,6 +378,36 @@ class NiftiIO:
     def write_seg(self, seg, output_fname: str, properties: dict) -> None:
         write_nifti_seg(seg, output_fname, properties)
 
+    def _file_frame_on_device(self, seg, properties: dict):
+        """-> (the device label map in its file's frame, the affine its header takes)."""
+        return seg, _affine_of(properties)
+
+    def compress_labels(self, seg, properties: dict) -> 'DeviceCompressedLabels':
+        """A device label map (z, y, x; uint8, or the two-byte int16 / uint16) -> the deflate fragment of its voxels as the
+        ``.nii.gz`` file holds them, made by ``fnn_deflate_labels`` on the current stream: what comes back from the device
+        is the fragment, not the map.  The file type is ``_label_voxels``' (uint16 from a maximum of 255 on).  ``write_seg``
+        takes the result.  Synchronises."""
+        import torch
+        if not hasattr(seg, 'data_ptr') or seg.device.type != 'cuda':
+            raise TypeError('compress_labels takes a label map on the GPU (arrays on the host go to write_seg as they are)')
+        assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
+        if seg.dtype not in (torch.uint8, torch.int16, torch.uint16):
+            raise NotImplementedError(f'label maps of {seg.dtype} are not compressed on the device (uint8, int16 and uint16 are)')
+        with torch.cuda.device(seg.device):
+            seg, affine = self._file_frame_on_device(seg, properties)
+            seg = seg.contiguous()
+            if seg.element_size() == 1 and seg.numel() > 0 and int(seg.max()) >= 255:
+                seg = seg.to(torch.int16)                        # (a uint8 map that holds 255 is a uint16 file)
+            if seg.data_ptr() % 16:
+                seg = seg.clone()
+            n, size = seg.numel(), seg.element_size()
+            cap = capi.deflate_bound(n * size)
+            out = torch.empty(max(cap, 16), dtype=torch.uint8, device=seg.device)
+            n_out, file_size, crc = capi.deflate_labels(seg.data_ptr(), size, n, True, out.data_ptr(), cap,
+                                                        torch.cuda.current_stream(seg.device).cuda_stream)
+            fragment = out[:n_out].cpu().numpy().tobytes()
+        return DeviceCompressedLabels(fragment, crc, n * file_size, tuple(seg.shape), file_size == 2, affine)
+
 
 # ---------------------------------------------------------------------- writing
 def _quaternion_of(affine: np.ndarray):
@@ -431,16 +465,83 @@ def _label_voxels(seg) -> Tuple[np.ndarray, bool]:
     return np.ascontiguousarray(seg.astype('<u2' if u16 else np.uint8, copy=False)), u16
 
 
+# ---- labels compressed on the device
+GZIP_HEADER = bytes.fromhex('1f8b08000000000004ff')              # what GzipFile(filename='', mtime=0, compresslevel=1) writes
+_CRC_POLY = 0xEDB88320
+
+
+def _crc_mulmod(a: int, b: int) -> int:
+    """a * b modulo the CRC-32 polynomial, both in the reflected representation (bit 31 is x^0)."""
+    p = 0
+    for i in range(32):
+        if a & (0x80000000 >> i):
+            p ^= b
+        b = (b >> 1) ^ (_CRC_POLY if b & 1 else 0)
+    return p
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int) -> int:
+    """``zlib.crc32(A + B)`` from ``zlib.crc32(A)``, ``zlib.crc32(B)`` and ``len(B)`` (zlib's crc32_combine, which Python does
+    not expose): ``crc(A) * x^(8 len(B)) + crc(B)`` in the CRC's field, the power by repeated squaring."""
+    power, square, e = 0x80000000, 0x40000000, 8 * int(len_b)    # x^0, x^1
+    while e:
+        if e & 1:
+            power = _crc_mulmod(power, square)
+        square = _crc_mulmod(square, square)
+        e >>= 1
+    return _crc_mulmod(int(crc_a), power) ^ int(crc_b)
+
+
+class DeviceCompressedLabels:
+    """A label map in its file's frame that was compressed on the device: the deflate ``fragment`` of its voxel bytes
+    (byte aligned, not final), their ``crc32`` and count ``n_bytes``, the map's ``shape`` (z, y, x), whether the file is
+    ``uint16``, and the ``affine`` its header takes.  The writer only assembles the file around it."""
+
+    def __init__(self, fragment: bytes, crc32: int, n_bytes: int, shape, uint16: bool, affine: np.ndarray):
+        self.fragment, self.crc32, self.n_bytes = bytes(fragment), int(crc32), int(n_bytes)
+        self.shape, self.uint16, self.affine = tuple(int(i) for i in shape), bool(uint16), affine
+        self.ndim = len(self.shape)
+
+
+def compressed_label_file_bytes(labels: DeviceCompressedLabels, affine: Optional[np.ndarray] = None) -> bytes:
+    """The ``.nii.gz`` file of ``labels``: one gzip member - the header ``write_label_file`` has always written; the NIfTI
+    header as raw deflate, flushed to a byte without ending the stream; the device's fragment; the final empty fixed block;
+    the CRC-32 of header plus voxels and their length modulo 2^32.  ``gzip.decompress`` gives the bytes of the host route's
+    file."""
+    head = nifti1_header_bytes(labels.shape[::-1], 512 if labels.uint16 else 2, labels.affine if affine is None else affine)
+    z = zlib.compressobj(1, zlib.DEFLATED, -15)
+    head_z = z.compress(head) + z.flush(zlib.Z_SYNC_FLUSH)
+    crc = crc32_combine(zlib.crc32(head), labels.crc32, labels.n_bytes)
+    return b''.join((GZIP_HEADER, head_z, labels.fragment, b'\x03\x00',
+                     struct.pack('<II', crc, (len(head) + labels.n_bytes) & 0xFFFFFFFF)))
+
+
+def _affine_of(properties: dict) -> np.ndarray:
+    if 'nibabel_stuff' in properties:
+        return properties['nibabel_stuff']['original_affine']
+    if 'sitk_stuff' in properties:
+        return affine_from_sitk_stuff(properties['sitk_stuff'])
+    raise RuntimeError('write_seg: the properties carry neither nibabel_stuff nor sitk_stuff')
+
+
 def write_label_file(seg, output_fname: str, affine: np.ndarray) -> None:
-    """``seg`` (z, y, x), in the file's own frame, as a NIfTI-1 label file with ``affine``.  The file appears under its name
-    only when it is complete."""
+    """``seg`` (z, y, x), in the file's own frame, as a NIfTI-1 label file with ``affine``; a ``DeviceCompressedLabels`` is
+    only assembled and written (``.nii.gz`` names only).  The file appears under its name only when it is complete."""
     gz = _check_ending(output_fname)
-    data, u16 = _label_voxels(seg)
-    head = nifti1_header_bytes(data.shape[::-1], 512 if u16 else 2, affine)
+    compressed = isinstance(seg, DeviceCompressedLabels)
+    if compressed:
+        if not gz:
+            raise ValueError(f'{output_fname}: labels compressed on the device make a .nii.gz file')
+        blob = compressed_label_file_bytes(seg, affine)
+    else:
+        data, u16 = _label_voxels(seg)
+        head = nifti1_header_bytes(data.shape[::-1], 512 if u16 else 2, affine)
     tmp = f'{output_fname}.part{os.getpid()}'
     try:
         with open(tmp, 'wb') as f:
-            if gz:
+            if compressed:
+                f.write(blob)
+            elif gz:
                 with gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=f, mtime=0) as g:
                     g.write(head)
                     g.write(memoryview(data).cast('B'))
@@ -458,13 +559,9 @@ def write_nifti_seg(seg, output_fname: str, properties: dict) -> None:
     (``nibabel_stuff`` if the properties have it, else rebuilt from ``sitk_stuff``).  The file appears under its name
     only when it is complete."""
     _check_ending(output_fname)
-    if 'nibabel_stuff' in properties:
-        affine = properties['nibabel_stuff']['original_affine']
-    elif 'sitk_stuff' in properties:
-        affine = affine_from_sitk_stuff(properties['sitk_stuff'])
-    else:
-        raise RuntimeError('write_seg: the properties carry neither nibabel_stuff nor sitk_stuff')
-    write_label_file(seg, output_fname, affine)
+    if isinstance(seg, DeviceCompressedLabels):
+        return write_label_file(seg, output_fname, seg.affine)
+    write_label_file(seg, output_fname, _affine_of(properties))
 
 
 # ---------------------------------------------------------------------- orientation (NibabelIOWithReorient)
@@ -694,8 +791,14 @@ class NiftiReorientIO(NiftiIO):
         import torch
         if seg.device.type != 'cuda':
             return FileFrameLabels(reorient_on_host(seg.numpy(), src_axis, flip), restored)
+        return FileFrameLabels(self._reorient_on_device(seg, src_axis, flip).cpu().numpy(), restored)
+
+    @staticmethod
+    def _reorient_on_device(seg, src_axis, flip):
+        """A device label map through ``fnn_reorient`` on the current stream (itself when there is nothing to do)."""
+        import torch
         if src_axis == (0, 1, 2) and not any(flip):
-            return FileFrameLabels(seg.cpu().numpy(), restored)
+            return seg
         if seg.element_size() not in (1, 2, 4):
             raise NotImplementedError(f'label maps of {seg.dtype} are not reoriented on the device (1-, 2- and 4-byte elements are)')
         with torch.cuda.device(seg.device):
@@ -703,12 +806,25 @@ class NiftiReorientIO(NiftiIO):
             out = torch.empty(tuple(seg.shape[a] for a in src_axis), dtype=seg.dtype, device=seg.device)
             capi.reorient(seg.data_ptr(), seg.element_size(), tuple(seg.shape), src_axis, flip, out.data_ptr(),
                           torch.cuda.current_stream(seg.device).cuda_stream)
-            return FileFrameLabels(out.cpu().numpy(), restored)
+            return out
+
+    def _file_frame_on_device(self, seg, properties: dict):
+        """The RAS-frame device label map brought to its file's frame by ``fnn_reorient``, and the restored affine: what
+        ``compress_labels`` then compresses."""
+        src_axis, flip, restored = restore_orientation(properties, tuple(seg.shape))
+        original = np.asarray(properties['nibabel_stuff']['original_affine'], dtype=np.float64)
+        if not np.allclose(original, restored):
+            warnings.warn(f'Restored affine does not match original affine.\nOriginal affine\n{original}\n'
+                          f'Restored affine\n{restored}')
+        return self._reorient_on_device(seg, src_axis, flip), restored
 
     def write_seg(self, seg, output_fname: str, properties: dict) -> None:
         """``seg`` is in the RAS frame (z, y, x) like the reference's, or a ``FileFrameLabels`` made earlier by
-        ``labels_to_file_frame``.  The header carries the restored affine."""
+        ``labels_to_file_frame``, or the ``DeviceCompressedLabels`` of ``compress_labels``.  The header carries the restored
+        affine."""
         _check_ending(output_fname)
+        if isinstance(seg, DeviceCompressedLabels):
+            return write_label_file(seg, output_fname, seg.affine)
         if not isinstance(seg, FileFrameLabels):
             assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
             seg = self.labels_to_file_frame(seg, properties)

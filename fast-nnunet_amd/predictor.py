@@ -51,8 +51,9 @@ class nnUNetPredictor(object):
                  accumulate_in: str = 'fp16',
                  patches_per_forward: int = 4,
                  compute_dtype: str = 'f16',
-                 fused_label_export: bool = True):
-        """Same knobs as the reference (:40-65) plus two engine choices:
+                 fused_label_export: bool = True,
+                 compress_on_device: bool = False):
+        """Same knobs as the reference (:40-65) plus the engine's choices:
 
         accumulate_in  'fp16' reproduces the reference's half accumulators and their rounding per patch visit as the
                        reference computes them WITHOUT autocast (its CPU path: fp32 logits and products, one rounding
@@ -66,6 +67,10 @@ class nnUNetPredictor(object):
                        ``fnn_resample_labels`` - interpolation and label rule in one pass, no resampled logits in memory
                        (order-1 default plans and torch-resampling plans); False: resample, then the label rule - the
                        same labels.
+        compress_on_device  labels bound for a ``.nii.gz`` file are compressed by ``fnn_deflate_labels`` on the GPU and
+                       only the compressed bytes are downloaded; the file holds the same header and voxels behind another
+                       (larger, valid) deflate stream.  False (default): the host's gzip, byte for byte as before.
+                       Returned arrays, ``.npz`` and ``.pkl`` are the same either way.
         """
         self.verbose = verbose
         self.verbose_preprocessing = verbose_preprocessing
@@ -89,6 +94,7 @@ class nnUNetPredictor(object):
             raise ValueError("compute_dtype must be 'f16' or 'f8'")
         self.compute_dtype = compute_dtype
         self.fused_label_export = bool(fused_label_export)
+        self.compress_on_device = bool(compress_on_device)
         self._engine: Optional[capi.Engine] = None
         self._spec: Optional[ArchSpec] = None
         self._active_fold = 0
@@ -172,8 +178,16 @@ class nnUNetPredictor(object):
     def _labels_out(self, labels: torch.Tensor, u16: bool, props: dict, for_file: bool):
         """The labels of a case on the host.  When they are bound for a file and the reader-writer reorients, they are brought
         to the file's frame on the device first (after the postprocessing, which sees the RAS frame) and come back as the
-        ``FileFrameLabels`` its ``write_seg`` takes: the writer thread does no strided copy."""
+        ``FileFrameLabels`` its ``write_seg`` takes: the writer thread does no strided copy.  With ``compress_on_device``
+        and a ``.nii.gz`` target they are also compressed here, on the calling thread, and come back as the
+        ``DeviceCompressedLabels`` that ``write_seg`` only assembles: the label map itself is never downloaded."""
         rw = self._reader_writer() if for_file else None
+        if rw is not None and self.compress_on_device and hasattr(rw, 'compress_labels') \
+                and str(self.dataset_json['file_ending']).lower().endswith('.nii.gz'):
+            if self._postprocessing is not None:
+                from .postprocessing import apply_postprocessing
+                labels = apply_postprocessing(labels, *self._postprocessing)
+            return rw.compress_labels(labels.to(torch.int16) if u16 else labels.to(torch.uint8), props)
         if rw is None or not hasattr(rw, 'labels_to_file_frame'):
             return self._labels_to_host(labels, u16)
         if self._postprocessing is not None:

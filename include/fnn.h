@@ -428,6 +428,24 @@ int fnn_decode_voxels(const void *raw, int nifti_datatype, int byteswap, int64_t
 int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_in[3], const int32_t src_axis[3],
                  const int32_t flip[3], void *out, void *stream);
 
+/* A label map on the device -> the deflate bytes of its voxels in a .nii.gz file (additive in ABI 4; no counterpart in the
+ * reference, whose nibabel writer compresses on the host).  in: n_elems little-endian labels of in_elem_bytes (1 or 2)
+ * bytes, device pointer, 16-byte aligned.  narrow_if_fits != 0: a 2-byte map whose maximum - found here - is below 255 is
+ * written as uint8, as the host writer does; *file_elem_bytes says which (1 for no elements).  out (device, any alignment,
+ * out_cap >= fnn_deflate_bound(n_elems * in_elem_bytes) bytes) receives *out_bytes bytes: a fragment of a raw deflate
+ * stream (RFC 1951) that leaves its reader byte aligned and not at the end - independent chunks of 16 KiB of file bytes,
+ * each one non-final fixed-Huffman block followed by an empty stored block; a match has the distance of one element and
+ * lies inside one 256-byte segment of its chunk.  A stream is closed behind it with the final empty fixed block 03 00.
+ * *crc32: zlib's CRC-32 of the file bytes.  The bytes depend on the input alone: the same on every run.
+ * Synchronises the stream (it reports sizes).  n_elems == 0: 0 bytes, CRC 0, nothing launched.  FNN_E_INVALID before any
+ * launch: NULL or host pointers, a misaligned `in`, an element size other than 1 or 2, an out_cap below the bound;
+ * FNN_E_UNSUPPORTED: more than 2^31 - 1 chunks (32 TiB).  Nothing is written outside out[0, *out_bytes).  Scratch,
+ * allocated inside the call: 2 B per 256 file bytes and 16 B per chunk.
+ * fnn_deflate_bound (host only): a capacity that always suffices - every byte a 9-bit literal, 6 bytes per chunk. */
+int64_t fnn_deflate_bound(int64_t n_bytes);
+int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
+                       int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */

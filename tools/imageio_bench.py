@@ -4,13 +4,15 @@ with numpy, astype(float32), then predict_single_npy_array's upload of the float
 a plain device copy of the same bytes; the write of a label map; and predict_from_files (reader and writer threads)
 against predict_from_files_sequential on four cases; and (``--section reorient`` runs these rows alone) fnn_reorient on an
 n^3 case - float32 forward and uint8 backward, one orientation per kernel path - next to a device-to-device copy of the
-same bytes and to numpy's flip / transpose on the host.
+same bytes and to numpy's flip / transpose on the host; and (``--section deflate``, these rows alone) fnn_deflate_labels on
+a synthetic 61-label map of n^3 voxels as uint8 and uint16 and on the golden mask tiled to a similar size, next to a device
+copy of the same bytes, to zlib level 1 on this machine's CPU, and the download of the fragment next to that of the map.
 
 The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, so that gzip has something to do), written
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient] [--out FILE]
+                                                          [--section all|reorient|deflate] [--out FILE]
 """
 import argparse
 import gzip
@@ -86,6 +88,64 @@ def bench_reorient(n, reps, dev, say, row):
         del src, dst, host
 
 
+def label_map(n, dev, seed=18):
+    """A seeded map of n^3 voxels: 60 ellipsoids (labels 1 .. 60, later ones on top) on background 0, made on the device."""
+    g = torch.Generator().manual_seed(seed)
+    centre, radius = torch.rand(60, 3, generator=g) * n, (0.04 + 0.14 * torch.rand(60, 3, generator=g)) * n
+    ax = [torch.arange(n, dtype=torch.float32, device=dev).reshape([-1 if d == k else 1 for d in range(3)]) for k in range(3)]
+    labels = torch.zeros((n, n, n), dtype=torch.uint8, device=dev)
+    for k in range(60):
+        inside = sum(((ax[d] - float(centre[k, d])) / float(radius[k, d])) ** 2 for d in range(3)) < 1.0
+        labels[inside] = k + 1
+    return labels
+
+
+def bench_deflate(n, reps, dev, say, row):
+    """fnn_deflate_labels (csrc/deflate.hip) against zlib level 1 on this machine's CPU and a device copy of the same bytes."""
+    import zlib
+    from fast_nnunet_amd import capi
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    say(f'--- fnn_deflate_labels; events around the call (it allocates its scratch and synchronises), the first call is the '
+        f'warm-up; zlib level 1 on this machine, one thread, by wall clock')
+    golden = os.path.join(ROOT, 'tests', 'golden', 'example_ct_sm_T300_output.nii.gz')
+    blob = gzip.decompress(open(golden, 'rb').read())
+    mask = np.frombuffer(blob[352:], np.uint8).reshape(30, 101, 122)
+    reps_of = [max(1, round(n / s)) for s in mask.shape]
+    synth = label_map(n, dev)
+    inputs = [(f'61 labels, uint8 {n}^3', synth), (f'61 labels, uint16 {n}^3 (values x 1000)', synth.to(torch.int16) * 1000),
+              (f'golden mask tiled {reps_of} -> uint8 {tuple(r * s for r, s in zip(reps_of, mask.shape))}',
+               torch.from_numpy(np.tile(mask, reps_of)).to(dev))]
+    for name, labels in inputs:
+        n_bytes = labels.numel() * labels.element_size()
+        cap = capi.deflate_bound(n_bytes)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        res = []
+        t = events(lambda: res.append(capi.deflate_labels(labels.data_ptr(), labels.element_size(), labels.numel(), True,
+                                                          out.data_ptr(), cap, stream)), reps, dev)
+        n_out, file_size, crc = res[-1]
+        say(f'{name}: {n_bytes / 2 ** 20:.0f} MiB of labels, {file_size} byte(s) per voxel in the file')
+        row('  fnn_deflate_labels', t, f'  {n_bytes / t[0] / 1e6:.1f} GB/s of labels; fragment {n_out / 2 ** 20:.2f} MiB')
+        dst = torch.empty_like(labels)
+        tc = events(lambda: dst.copy_(labels), reps, dev)
+        row('  device-to-device copy of the same bytes', tc, f'  {2 * n_bytes / tc[0] / 1e6:.0f} GB/s; the encoder takes {t[0] / tc[0]:.1f}x')
+        del dst
+        td = wall(lambda: labels.cpu(), reps)
+        row(f'  download of the labels ({n_bytes / 2 ** 20:.0f} MiB, pageable)', td[:3], f'  {n_bytes / td[0] / 1e6:.1f} GB/s')
+        tf = wall(lambda: out[:n_out].cpu(), reps)
+        row(f'  download of the fragment ({n_out / 2 ** 20:.2f} MiB, pageable)', tf[:3])
+        raw = td[3].numpy().tobytes()
+        tz = wall(lambda: zlib.compress(raw, 1), 1)
+        frag = tf[3].numpy().tobytes()
+        d = zlib.decompressobj(-15)
+        same = d.decompress(frag + b'\x03\x00') == raw and zlib.crc32(raw) == crc
+        row('  zlib.compress(level 1) of the same bytes (host)', tz[:3],
+            f'  {n_bytes / tz[0] / 1e6:.2f} GB/s; {len(tz[3]) / 2 ** 20:.2f} MiB: the fragment is {n_out / len(tz[3]):.2f}x that; '
+            f'{tz[0] / t[0]:.0f}x the kernel\'s time')
+        say(f'  the fragment inflates to the labels and the CRC is zlib\'s: {same}')
+        del out, raw, frag, labels
+    del inputs, synth
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
@@ -93,7 +153,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -115,8 +175,8 @@ def main():
     def row(name, t, extra=''):
         say(f'{name:<66s}: {t[0]:9.2f} ms  (min {t[1]:.2f} max {t[2]:.2f}){extra}')
 
-    if a.section == 'reorient':
-        bench_reorient(n, a.reps, dev, say, row)
+    if a.section in ('reorient', 'deflate'):
+        (bench_reorient if a.section == 'reorient' else bench_deflate)(n, a.reps, dev, say, row)
         write_out(a.out, lines)
         return
 
@@ -191,6 +251,7 @@ def main():
         del vol, seg
 
         bench_reorient(n, a.reps, dev, say, row)
+        bench_deflate(n, a.reps, dev, say, row)
 
         say(f'--- predict_from_files on {a.cases} cases of {tuple(a.case_shape)} int16 .nii.gz, toy network (patch 32 x 64 x 64), no mirroring')
         patch = (32, 64, 64)
