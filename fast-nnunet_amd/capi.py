@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -72,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -141,6 +141,10 @@ def load_library() -> C.CDLL:
     lib.fnn_deflate_bound.argtypes = [i64]
     lib.fnn_deflate_bound.restype = i64
     lib.fnn_deflate_labels.argtypes = [vp, i32, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_uint32), vp]
+    lib.fnn_deflate_masks_work_bytes.argtypes = [i64, i32]
+    lib.fnn_deflate_masks_work_bytes.restype = i64
+    lib.fnn_deflate_masks_count.argtypes = [vp, i32, i64, C.POINTER(C.c_int32), i32, vp, i64, C.POINTER(i64), C.POINTER(C.c_uint32), vp]
+    lib.fnn_deflate_masks_emit.argtypes = [vp, i32, i64, C.POINTER(C.c_int32), i32, vp, vp, i64, vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -363,6 +367,42 @@ def deflate_labels(in_ptr: int, in_elem_bytes: int, n_elems: int, narrow_if_fits
     check(lib.fnn_deflate_labels(in_ptr, int(in_elem_bytes), int(n_elems), int(bool(narrow_if_fits)), out_ptr, int(out_cap),
                                  C.byref(out_bytes), C.byref(file_elem), C.byref(crc), stream), lib)
     return int(out_bytes.value), int(file_elem.value), int(crc.value)
+
+
+def deflate_masks_work_bytes(n_elems: int, n_labels: int) -> int:
+    """fnn_deflate_masks_work_bytes: the size of the device buffer ``deflate_masks_count`` fills for ``deflate_masks_emit``
+    (host only)."""
+    return int(load_library().fnn_deflate_masks_work_bytes(int(n_elems), int(n_labels)))
+
+
+def _label_array(labels):
+    labels = [int(i) for i in labels]
+    if any(not -2 ** 31 <= i < 2 ** 31 for i in labels):
+        raise AssertionError('a label lies outside [0, 65535]')
+    return (C.c_int32 * max(len(labels), 1))(*labels), len(labels)
+
+
+def deflate_masks_count(in_ptr: int, in_elem_bytes: int, n_elems: int, labels, work_ptr: int, work_cap: int,
+                        stream: int = 0) -> Tuple[List[int], List[int]]:
+    """fnn_deflate_masks_count: for the map of n_elems labels of 1 or 2 bytes at in_ptr (device, 16-byte aligned) and every
+    value in ``labels``, the size of the raw-deflate fragment of the mask ``map == value`` and zlib's CRC-32 of the mask
+    bytes -> ``(sizes, crcs)``.  work_ptr: a device buffer of ``deflate_masks_work_bytes`` bytes that ``deflate_masks_emit``
+    then reads.  Synchronises `stream`."""
+    lib = load_library()
+    arr, n = _label_array(labels)
+    sizes, crcs = (C.c_int64 * max(n, 1))(), (C.c_uint32 * max(n, 1))()
+    check(lib.fnn_deflate_masks_count(in_ptr, int(in_elem_bytes), int(n_elems), arr, n, work_ptr, int(work_cap), sizes, crcs,
+                                      stream), lib)
+    return [int(sizes[i]) for i in range(n)], [int(crcs[i]) for i in range(n)]
+
+
+def deflate_masks_emit(in_ptr: int, in_elem_bytes: int, n_elems: int, labels, work_ptr: int, out_ptr: int, out_cap: int,
+                       stream: int = 0) -> None:
+    """fnn_deflate_masks_emit: the fragments ``deflate_masks_count`` sized (same map, same labels, its work buffer), one
+    behind the other at out_ptr (device, any alignment, out_cap >= their sum).  The kernel runs asynchronously on `stream`."""
+    lib = load_library()
+    arr, n = _label_array(labels)
+    check(lib.fnn_deflate_masks_emit(in_ptr, int(in_elem_bytes), int(n_elems), arr, n, work_ptr, out_ptr, int(out_cap), stream), lib)
 
 
 def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, background_label: int,

@@ -1,6 +1,7 @@
-// deflate_core.h - what one lane of the deflate encoder does with its segment (csrc/deflate.hip), written so that the same
-// text compiles for the host: the token rule, the fixed-Huffman codes, the bit writer and the CRC-32 field arithmetic.
-// tests/deflate_ref.py restates all of it in Python; the GPU tests compare the two byte for byte.
+// deflate_core.h - what one lane of the deflate encoders does with its segment (csrc/deflate.hip, csrc/deflate_masks.hip),
+// written so that the same text compiles for the host: the token rule, the fixed-Huffman codes, the bit writer, the CRC-32
+// field arithmetic, and at the end the per-label mask form with its constant zero chunk.
+// tests/deflate_ref.py and tests/deflate_masks_ref.py restate all of it in Python; the GPU tests compare byte for byte.
 #pragma once
 #include <cstdint>
 
@@ -127,3 +128,63 @@ template <int ELEM> struct DfEmit {
     DF_HD void literal(unsigned v) { unsigned c; int nb; df_literal(v, c, nb); put(c, nb); }
     DF_HD void match(int len) { unsigned c; int nb; df_match<ELEM>(len, c, nb); put(c, nb); }
 };
+
+// ---- per-label masks (csrc/deflate_masks.hip; tests/deflate_masks_ref.py restates it) --------------------------------
+// The mask of label l is the uint8 array m[i] = (seg[i] == l).  Its fragment is the chain of chunks of the format above
+// with one change: a full chunk in which l does not occur is not tokenised by segments but is the constant zero chunk -
+// literal 0, 63 matches of 258 and one of 129 at distance 1 - of DF_ZERO_CHUNK_BYTES bytes (the segment rule takes 214).
+constexpr int DF_ZERO_CHUNK_BYTES = 112;
+// the most a mask's chunk takes: its bytes are 0 and 1, 8-bit literals
+constexpr int DF_MASK_CHUNK_MAX_BYTES = (DF_CHUNK * 8 + DF_FRAME_BITS + 7) / 8 + 4;
+
+// df_walk<1> over the mask bytes of one segment, compared on read: `seg` holds the segment's labels of ELEM bytes (all 16
+// bits of a 2-byte label are compared), `len` <= DF_SEG of them
+template <int ELEM, class Sink> DF_HD void df_walk_mask(const unsigned *seg, int len, unsigned label, Sink &s) {
+    int run = 0;
+    unsigned h1 = 0, h2 = 0, w = 0;
+    auto flush = [&]() {
+        if (run >= 3) s.match(run);
+        else if (run == 2) { s.literal(h2); s.literal(h1); }
+        else if (run == 1) s.literal(h1);
+    };
+    for (int q = 0; q < len; ++q) {
+        unsigned v;
+        if (ELEM == 1) {
+            if ((q & 3) == 0) w = seg[q >> 2];
+            v = w & 255u;
+            w >>= 8;
+        } else {
+            if ((q & 1) == 0) w = seg[q >> 1];
+            v = w & 0xFFFFu;
+            w >>= 16;
+        }
+        const unsigned b = v == label ? 1u : 0u;
+        s.byte(b);
+        if (q >= 1 && b == h1) ++run;
+        else { flush(); s.literal(b); run = 0; }
+        h2 = h1;
+        h1 = b;
+    }
+    flush();
+}
+
+// the bits of a segment without its CRC: what the emit pass needs to place the lanes
+struct DfBits {
+    unsigned bits = 0;
+    DF_HD void byte(unsigned) {}
+    DF_HD void literal(unsigned v) { bits += v < 144 ? 8 : 9; }
+    DF_HD void match(int len) { unsigned c; int n; df_match<1>(len, c, n); bits += n; }
+};
+
+// the zero chunk, built with the emitter itself (host): `out` takes DF_ZERO_CHUNK_BYTES bytes
+inline void df_zero_chunk(uint8_t *out) {
+    unsigned buf[DF_ZERO_CHUNK_BYTES / 4] = {};
+    DfEmit<1> em(buf, 0);
+    em.put(2u, 3);                                       // BFINAL = 0, BTYPE = 01
+    em.literal(0);
+    for (int i = 0; i < 63; ++i) em.match(258);
+    em.match(129);
+    em.finish();                                         // end-of-block, the stored block's header and LEN are zeros
+    for (int b = 0; b < DF_ZERO_CHUNK_BYTES; ++b) out[b] = (uint8_t)(buf[b >> 2] >> ((b & 3) * 8));
+    out[DF_ZERO_CHUNK_BYTES - 2] = out[DF_ZERO_CHUNK_BYTES - 1] = 0xFF;
+}

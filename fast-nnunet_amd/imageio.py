@@ -21,7 +21,8 @@ images brought to RAS+ behind the decode and labels back to the file's frame bef
 
 ``NiftiIO.compress_labels`` is the opt-in write route that never downloads the label map: ``fnn_deflate_labels``
 (csrc/deflate.hip) turns the device labels into a deflate fragment, and ``write_seg`` only puts the gzip member together
-around it (``DeviceCompressedLabels``, ``compressed_label_file_bytes``).
+around it (``DeviceCompressedLabels``, ``compressed_label_file_bytes``).  ``NiftiIO.compress_label_masks`` does the same for
+the per-label mask files of ``jhu.JHUPredictor``: all masks of a map in one pass (csrc/deflate_masks.hip).
 
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
@@ -407,6 +408,41 @@ class NiftiIO:
                                                         torch.cuda.current_stream(seg.device).cuda_stream)
             fragment = out[:n_out].cpu().numpy().tobytes()
         return DeviceCompressedLabels(fragment, crc, n * file_size, tuple(seg.shape), file_size == 2, affine)
+
+    def compress_label_masks(self, seg, labels: Sequence[int], properties: dict) -> List['DeviceCompressedLabels']:
+        """A device label map (z, y, x; uint8, int16 or uint16) and label values -> per value the compressed uint8 mask
+        ``seg == value`` as its ``.nii.gz`` file holds it, in the order of ``labels``: the map is brought to its file's frame
+        once (``_file_frame_on_device``), ``fnn_deflate_masks_count`` sizes all fragments, ``fnn_deflate_masks_emit`` writes
+        them into one buffer of exactly that size, and that buffer is what comes back from the device - neither the map nor
+        a mask is downloaded.  ``write_seg`` takes each result.  Synchronises."""
+        import torch
+        if not hasattr(seg, 'data_ptr') or seg.device.type != 'cuda':
+            raise TypeError('compress_label_masks takes a label map on the GPU (masks of a host array go to write_seg as they are)')
+        assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
+        if seg.dtype not in (torch.uint8, torch.int16, torch.uint16):
+            raise NotImplementedError(f'label maps of {seg.dtype} are not compressed on the device (uint8, int16 and uint16 are)')
+        labels = [int(i) for i in labels]
+        if not labels:
+            return []
+        with torch.cuda.device(seg.device):
+            seg, affine = self._file_frame_on_device(seg, properties)
+            seg = seg.contiguous()
+            if seg.data_ptr() % 16:
+                seg = seg.clone()
+            n, size, shape = seg.numel(), seg.element_size(), tuple(seg.shape)
+            stream = torch.cuda.current_stream(seg.device).cuda_stream
+            work_cap = capi.deflate_masks_work_bytes(n, len(labels))
+            work = torch.empty(max(work_cap, 16), dtype=torch.uint8, device=seg.device)
+            sizes, crcs = capi.deflate_masks_count(seg.data_ptr(), size, n, labels, work.data_ptr(), work_cap, stream)
+            total = sum(sizes)
+            out = torch.empty(max(total, 16), dtype=torch.uint8, device=seg.device)
+            capi.deflate_masks_emit(seg.data_ptr(), size, n, labels, work.data_ptr(), out.data_ptr(), total, stream)
+            blob = out[:total].cpu().numpy().tobytes()           # (the copy waits for the kernel on the stream)
+        made, at = [], 0
+        for nb, crc in zip(sizes, crcs):
+            made.append(DeviceCompressedLabels(blob[at:at + nb], crc, n, shape, False, affine))
+            at += nb
+        return made
 
 
 # ---------------------------------------------------------------------- writing

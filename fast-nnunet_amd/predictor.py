@@ -483,11 +483,15 @@ class nnUNetPredictor(object):
                     with open(tmp, 'wb') as f:
                         dump(f)
                     os.replace(tmp, output_file_truncated + ending)
-            self._reader_writer().write_seg(seg, output_file_truncated + self.dataset_json['file_ending'], props)
+            self._write_label_files(seg, props, output_file_truncated)
         finally:
             for tmp in made:
                 if os.path.exists(tmp):
                     os.remove(tmp)
+
+    def _write_label_files(self, seg, props: dict, output_file_truncated: str):
+        """What ``_labels_out`` made of a case, as the case's label file(s): here the one label map (a subclass writes others)."""
+        self._reader_writer().write_seg(seg, output_file_truncated + self.dataset_json['file_ending'], props)
 
     def _export_case(self, seg, probs, props, output_file_truncated):
         self._reader_writer()                                   # (made by the calling thread)

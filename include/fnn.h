@@ -446,6 +446,43 @@ int64_t fnn_deflate_bound(int64_t n_bytes);
 int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
                        int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, void *stream);
 
+/* One label map on the device -> one deflate fragment per requested label, of the uint8 mask m[i] = (in[i] == label): the
+ * voxel bytes of the per-label mask files of JHU_inference.py's export (<case>/predictions/<label_name>.nii.gz), in one
+ * pass over the map per phase (additive in ABI 4).  Stateless, in two phases, because no useful capacity is known before
+ * the sizes are: fnn_deflate_masks_count reports them, fnn_deflate_masks_emit writes the fragments.
+ * in: n_elems little-endian labels of in_elem_bytes (1 or 2) bytes, device pointer, 16-byte aligned; a 2-byte label is
+ * compared in all 16 bits.  labels: n_labels host values in [0, 65535] in any order; a value the map cannot hold (300 on a
+ * 1-byte map) gives the all-zero mask; a value named twice is FNN_E_INVALID (so n_labels <= 65536, which is also what the
+ * launch geometry addresses: one workgroup per label in the scan).
+ * A fragment is fnn_deflate_labels' stream of the mask bytes - independent 16 KiB chunks, each a non-final fixed-Huffman
+ * block and an empty stored block, matches at distance 1 inside 256-byte segments - with one change: a full chunk in which
+ * the label does not occur is the constant "zero chunk" of 112 bytes (block header, literal 0, 63 matches of 258 and one
+ * of 129 at distance 1, end-of-block, the empty stored block).  A chunk in which it occurs, and a last partial chunk
+ * always, is tokenised by segments as before.  Closed with 03 00 a fragment inflates to the mask; it is never longer than
+ * fnn_deflate_labels' fragment of the mask; the bytes depend on the input alone.
+ * work: a device buffer, 16-byte aligned, of at least fnn_deflate_masks_work_bytes(n_elems, n_labels) bytes (host only;
+ * 0 for arguments the calls refuse).  With C = ceil(n_elems / 16384) chunks, L = n_labels and r16 = rounding up to 16:
+ *   384 + r16(4 L) + r16(8 (L + 1)) + r16(8 L) + r16(4 L) + 8 L C + r16(2 L C)
+ * - the CRC field's powers and the zero chunk (384 B), the labels, the fragments' offsets in `out`, their sizes and CRCs,
+ * and per (label, chunk) 8 B (the chunk's CRC, then its offset in the fragment) and 2 B (its size; 0 = the zero chunk,
+ * which is also how presence is kept).  Nothing is kept per segment.
+ * fnn_deflate_masks_count fills work, synchronises the stream and reports, per label in the order given, the fragment's
+ * size and zlib's CRC-32 of the mask bytes (frag_bytes, crc32: host arrays of n_labels).
+ * fnn_deflate_masks_emit takes the same in, n_elems and labels and the work count filled (anything else is
+ * FNN_E_INVALID where it can be told: the labels are compared with those in work) and writes fragment k at offset
+ * sum(frag_bytes[:k]) of out (device, any alignment); out_cap must be at least the sum of all sizes, and nothing is
+ * written outside out[0, sum).  It reads the sum back from work (waiting for what the stream held before), then launches
+ * asynchronously on `stream`.
+ * n_elems == 0: sizes 0, CRC 0, nothing launched.  FNN_E_INVALID before any launch, with a message: NULL or host pointers
+ * (in, work, out), a misaligned in or work, an element size other than 1 or 2, a negative n_elems, n_labels < 1, a label
+ * outside [0, 65535], a duplicate label, a work_cap or out_cap that is too small.  FNN_E_UNSUPPORTED: more than 2^31 - 1
+ * chunks. */
+int64_t fnn_deflate_masks_work_bytes(int64_t n_elems, int n_labels);
+int fnn_deflate_masks_count(const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
+                            void *work, int64_t work_cap, int64_t *frag_bytes, uint32_t *crc32, void *stream);
+int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
+                           const void *work, void *out, int64_t out_cap, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */

@@ -6,13 +6,16 @@ against predict_from_files_sequential on four cases; and (``--section reorient``
 n^3 case - float32 forward and uint8 backward, one orientation per kernel path - next to a device-to-device copy of the
 same bytes and to numpy's flip / transpose on the host; and (``--section deflate``, these rows alone) fnn_deflate_labels on
 a synthetic 61-label map of n^3 voxels as uint8 and uint16 and on the golden mask tiled to a similar size, next to a device
-copy of the same bytes, to zlib level 1 on this machine's CPU, and the download of the fragment next to that of the map.
+copy of the same bytes, to zlib level 1 on this machine's CPU, and the download of the fragment next to that of the map; and
+(``--section masks``, these rows alone) the per-label mask files of JHUPredictor: fnn_deflate_masks_count + fnn_deflate_masks_emit
+on synthetic maps of 61 and 118 labels and on the golden mask tiled, next to one fnn_deflate_labels call per mask materialised on
+the device, to zlib level 1 of a mask on the CPU times the number of labels, and the sizes that are downloaded and written.
 
 The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, so that gzip has something to do), written
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient|deflate] [--out FILE]
+                                                          [--section all|reorient|deflate|masks] [--out FILE]
 """
 import argparse
 import gzip
@@ -88,13 +91,13 @@ def bench_reorient(n, reps, dev, say, row):
         del src, dst, host
 
 
-def label_map(n, dev, seed=18):
-    """A seeded map of n^3 voxels: 60 ellipsoids (labels 1 .. 60, later ones on top) on background 0, made on the device."""
+def label_map(n, dev, seed=18, k=60):
+    """A seeded map of n^3 voxels: k ellipsoids (labels 1 .. k, later ones on top) on background 0, made on the device."""
     g = torch.Generator().manual_seed(seed)
-    centre, radius = torch.rand(60, 3, generator=g) * n, (0.04 + 0.14 * torch.rand(60, 3, generator=g)) * n
+    centre, radius = torch.rand(k, 3, generator=g) * n, (0.04 + 0.14 * torch.rand(k, 3, generator=g)) * n
     ax = [torch.arange(n, dtype=torch.float32, device=dev).reshape([-1 if d == k else 1 for d in range(3)]) for k in range(3)]
     labels = torch.zeros((n, n, n), dtype=torch.uint8, device=dev)
-    for k in range(60):
+    for k in range(k):
         inside = sum(((ax[d] - float(centre[k, d])) / float(radius[k, d])) ** 2 for d in range(3)) < 1.0
         labels[inside] = k + 1
     return labels
@@ -146,6 +149,88 @@ def bench_deflate(n, reps, dev, say, row):
     del inputs, synth
 
 
+def bench_masks(n, reps, dev, say, row):
+    """fnn_deflate_masks_count + fnn_deflate_masks_emit (csrc/deflate_masks.hip): every foreground label's mask of one map."""
+    import zlib
+    from fast_nnunet_amd import capi
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    C = 16384
+    say('--- fnn_deflate_masks_count + fnn_deflate_masks_emit: one uint8 mask fragment per foreground label; events around the '
+        'calls (work and out allocated before), the first call is the warm-up; zlib level 1 on this machine, one thread, by wall clock')
+    golden = os.path.join(ROOT, 'tests', 'golden', 'example_ct_sm_T300_output.nii.gz')
+    mask = np.frombuffer(gzip.decompress(open(golden, 'rb').read())[352:], np.uint8).reshape(30, 101, 122)
+    reps_of = [max(1, round(n / s)) for s in mask.shape]
+    synth61, synth118 = label_map(n, dev), label_map(n, dev, k=117)
+    inputs = [(f'61 labels (60 masks), uint8 {n}^3', synth61, list(range(1, 61))),
+              (f'118 labels (117 masks), uint8 {n}^3', synth118, list(range(1, 118))),
+              (f'118 labels (117 masks), 2-byte {n}^3 (values x 257)', synth118.to(torch.int16) * 257, [257 * i for i in range(1, 118)]),
+              (f'golden mask tiled {reps_of} -> uint8 {tuple(r * s for r, s in zip(reps_of, mask.shape))}',
+               torch.from_numpy(np.tile(mask, reps_of)).to(dev), [int(i) for i in np.unique(mask) if i])]
+    del synth61, synth118
+    for name, labels, wanted in inputs:
+        labels = labels.contiguous()
+        nel, size, L = labels.numel(), labels.element_size(), len(wanted)
+        chunks = (nel + C - 1) // C
+        flat = labels.reshape(-1).to(torch.int64) & 0xFFFF
+        pad = torch.nn.functional.pad(flat, (0, chunks * C - nel), value=int(flat[-1])).view(chunks, C)
+        seen = torch.zeros((chunks, 65536 if size == 2 else 256), dtype=torch.uint8, device=dev)
+        seen.scatter_(1, pad, 1)
+        pairs = int(seen[:, wanted].sum()) + (L - int(seen[-1, wanted].sum()) if nel % C else 0)
+        del flat, pad, seen
+        work_cap = capi.deflate_masks_work_bytes(nel, L)
+        work = torch.empty(work_cap, dtype=torch.uint8, device=dev)
+        res = []
+        t_count = events(lambda: res.append(capi.deflate_masks_count(labels.data_ptr(), size, nel, wanted, work.data_ptr(), work_cap, stream)),
+                         reps, dev)
+        sizes, crcs = res[-1]
+        total = sum(sizes)
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        t_emit = events(lambda: capi.deflate_masks_emit(labels.data_ptr(), size, nel, wanted, work.data_ptr(), out.data_ptr(), total, stream),
+                        reps, dev)
+
+        def both():
+            capi.deflate_masks_count(labels.data_ptr(), size, nel, wanted, work.data_ptr(), work_cap, stream)
+            capi.deflate_masks_emit(labels.data_ptr(), size, nel, wanted, work.data_ptr(), out.data_ptr(), total, stream)
+        t = events(both, reps, dev)
+        say(f'{name}: {nel * size / 2 ** 20:.0f} MiB of labels, {L} masks of {nel / 2 ** 20:.0f} MiB; {chunks} chunks, '
+            f'{pairs} of {chunks * L} (chunk, label) pairs are walked = {pairs / chunks:.2f} walks of the volume; work {work_cap / 2 ** 20:.1f} MiB')
+        row('  count + emit', t, f'  {L * nel / t[0] / 1e6:.0f} GB/s of mask bytes; all fragments {total / 2 ** 20:.2f} MiB')
+        row('    fnn_deflate_masks_count alone (synchronises)', t_count)
+        row('    fnn_deflate_masks_emit alone', t_emit)
+        # (a) what there was before: every mask materialised on the device and encoded by fnn_deflate_labels
+        cap = capi.deflate_bound(nel)
+        out_a = torch.empty(cap, dtype=torch.uint8, device=dev)
+        got_a = []
+
+        def one_by_one():
+            got_a.clear()
+            for v in wanted:
+                m = (labels == v).to(torch.uint8)
+                got_a.append(capi.deflate_labels(m.data_ptr(), 1, nel, False, out_a.data_ptr(), cap, stream)[0])
+        ta = events(one_by_one, reps, dev)
+        row(f'  (a) {L} x (mask on the device + fnn_deflate_labels)', ta,
+            f'  {ta[0] / t[0]:.1f}x count + emit; fragments {sum(got_a) / 2 ** 20:.2f} MiB, here {total / sum(got_a):.2f}x that')
+        # (b) the host writer: zlib level 1 of one mask, times the number of masks
+        mid = L // 2
+        host_mask = (labels == wanted[mid]).to(torch.uint8).cpu().numpy().tobytes()
+        tz = wall(lambda: zlib.compress(host_mask, 1), 1)
+        empty = zlib.compress(bytes(nel), 1)
+        row(f'  (b) zlib.compress(level 1) of one mask (host), label {wanted[mid]}', tz[:3],
+            f'  x {L} masks = {tz[0] * L / 1e3:.1f} s = {tz[0] * L / t[0]:.0f}x count + emit; {len(tz[3])} B, its fragment {sizes[mid]} B '
+            f'= {sizes[mid] / len(tz[3]):.2f}x; an empty mask: zlib {len(empty)} B, fragment {112 * (nel // C)} B + the last chunk')
+        # (c) what is downloaded
+        td = wall(lambda: out.cpu(), reps)
+        row(f'  (c) download of all fragments ({total / 2 ** 20:.2f} MiB, pageable)', td[:3],
+            f'  the label map is {nel * size / 2 ** 20:.0f} MiB, the masks {L * nel / 2 ** 20:.0f} MiB')
+        blob = td[3].numpy()
+        at = sum(sizes[:mid])
+        d = zlib.decompressobj(-15)
+        same = d.decompress(blob[at:at + sizes[mid]].tobytes() + b'\x03\x00') == host_mask and zlib.crc32(host_mask) == crcs[mid]
+        say(f'  the fragment of label {wanted[mid]} inflates to its mask and the CRC is zlib\'s: {same}')
+        del out, out_a, work, labels, blob, host_mask
+    del inputs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
@@ -153,7 +238,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient', 'deflate'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -175,8 +260,8 @@ def main():
     def row(name, t, extra=''):
         say(f'{name:<66s}: {t[0]:9.2f} ms  (min {t[1]:.2f} max {t[2]:.2f}){extra}')
 
-    if a.section in ('reorient', 'deflate'):
-        (bench_reorient if a.section == 'reorient' else bench_deflate)(n, a.reps, dev, say, row)
+    if a.section in ('reorient', 'deflate', 'masks'):
+        {'reorient': bench_reorient, 'deflate': bench_deflate, 'masks': bench_masks}[a.section](n, a.reps, dev, say, row)
         write_out(a.out, lines)
         return
 
