@@ -2,51 +2,31 @@
 //
 //   fnn_deflate_labels   1- or 2-byte labels -> a fragment of a deflate stream, its size, and the CRC-32 of the file bytes
 //
-// The fragment is a concatenation of independent chunks of DF_CHUNK = 16 KiB of file bytes.  A chunk is one non-final
-// fixed-Huffman block (RFC 1951 3.2.6), its end-of-block code and an empty stored block (000, pad, 00 00 FF FF), which
-// ends it on a byte; no match reaches outside its chunk.  One wave encodes one chunk, lane l the DF_SEG = 256 bytes
-// [256 l, 256 l + 256) of it: a byte that equals the byte one element before it inside the segment extends a run, a run of
-// 3 or more becomes one match at the distance of one element, everything else a literal (deflate_core.h - the text both
-// passes and the host model share).  Label maps are long runs along x, which is what this rule finds.
+// The stream format, and what a lane does with its segment of a chunk, is deflate_core.h; the steps of a wave are
+// deflate_wave.h.  One wave encodes one chunk.  The rule - runs of equal elements become matches - finds what label maps
+// are made of: long runs along x.
 //
 //   deflate_max_kernel              the maximum of a 2-byte map (a maximum below 255 is written as uint8, as the host writer does)
 //   deflate_count_kernel<E, N>      a chunk -> LDS with 16-byte loads (N: every second byte of a 2-byte map), each lane
 //                                   walks its segment: the bits of its tokens (kept, 2 B per segment) and its CRC-32.
-//                                   The wave adds the bits up to the chunk's bytes and folds the 64 CRCs into the chunk's
-//                                   (crc(A | B) = crc(A) x^(8 |B|) + crc(B) in the reflected CRC-32 field).
+//                                   The wave adds the bits up to the chunk's bytes and folds the 64 CRCs into the chunk's.
 //   deflate_scan_kernel             chunk sizes -> chunk offsets in `out`, one block
 //   deflate_emit_kernel<E, N>       the chunk again; a wave scan of the kept bit counts gives every lane its first bit, the
-//                                   lanes OR their codes into a zeroed LDS bit buffer (ds_or_b32: the order of the lanes does
-//                                   not change the result, so the bytes are the same on every run), which is laid out
-//                                   so that its 16-byte vectors are the aligned 16-byte vectors of `out`: whole vectors are
-//                                   stored whole, the chunk's first and last bytes one by one.
+//                                   lanes OR their codes into the wave's bit buffer, which is stored by aligned vectors.
 //
 // LDS: segments at a pitch of 65 dwords (lane l's dword i on bank (l + i) % 32: the lanes' walks do not collide); the
 // count kernel 17.5 KiB, the emit kernel 34.3 KiB.  Nothing is written outside out[0, out_bytes); no kernel keeps scratch.
 #include "fnn_device.h"
-#include "deflate_core.h"
+#include "deflate_wave.h"
 #include "../../include/fnn.h"
 #include <climits>
 #include <cstdint>
 #include <vector>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int DF_OUT_VECS = (15 + DF_CHUNK_MAX_BYTES + 15) / 16;      // the bit buffer: a chunk's bytes behind up to 15 of its predecessor's
 constexpr int DF_SCAN_THREADS = 1024;
 constexpr int DF_MAX_THREADS = 256;
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 __global__ __launch_bounds__(DF_MAX_THREADS) void deflate_max_kernel(const uint16_t *in, long long n, unsigned *max_out) {
     const long long vecs = n / 8, stride = (long long)gridDim.x * DF_MAX_THREADS;
@@ -101,11 +81,6 @@ static __device__ __forceinline__ int load_chunk(const uint8_t *in, long long n_
     return len;
 }
 
-static __device__ __forceinline__ int seg_len(int chunk_len, int lane) {
-    const int l = chunk_len - lane * DF_SEG;
-    return l < 0 ? 0 : (l > DF_SEG ? DF_SEG : l);
-}
-
 template <int ELEM, bool NARROW>
 __global__ __launch_bounds__(DF_LANES) void deflate_count_kernel(const uint8_t *in, long long n_bytes, const uint32_t *x2k,
                                                                  uint16_t *seg_bits, unsigned *chunk_bytes, uint32_t *chunk_crc) {
@@ -114,33 +89,18 @@ __global__ __launch_bounds__(DF_LANES) void deflate_count_kernel(const uint8_t *
     __shared__ uint32_t s_x2k[64];
     const int lane = threadIdx.x;
     const long long c = blockIdx.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint32_t t = lane * 4 + k;
-        for (int i = 0; i < 8; ++i) t = (t >> 1) ^ ((t & 1) ? DF_POLY : 0u);
-        s_tab[lane * 4 + k] = t;
-    }
+    df_crc_table<DF_LANES>(s_tab, lane);
     s_x2k[lane] = x2k[lane];
     const int len = load_chunk<NARROW>(in, n_bytes, c, s_in);
     __syncthreads();
-    int mylen = seg_len(len, lane);
+    const int mylen = df_seg_len(len, lane);
     DfCount<ELEM> cnt{s_tab};
-    df_walk<ELEM>(s_in + lane * DF_PITCH, mylen, cnt);
+    df_walk<ELEM>(DfBytes{s_in + lane * DF_PITCH}, mylen, cnt);
     seg_bits[c * DF_LANES + lane] = (uint16_t)cnt.bits;
-    unsigned bits = cnt.bits;
-    for (int s = 32; s > 0; s >>= 1) bits += (unsigned)__shfl_xor((int)bits, s);
-    // lane l takes over lanes l .. l + 2 s - 1: its own bytes, then those of lane l + s
-    uint32_t crc = ~cnt.crc;
-    for (int s = 1; s < DF_LANES; s <<= 1) {
-        const uint32_t ocrc = (uint32_t)__shfl_down((int)crc, s);
-        const int olen = __shfl_down(mylen, s);
-        if ((lane & (2 * s - 1)) == 0 && olen > 0) {
-            crc = df_mulmod(crc, df_xpow8((unsigned long long)olen, s_x2k)) ^ ocrc;
-            mylen += olen;
-        }
-    }
+    const unsigned bits = df_wave_sum(cnt.bits);
+    const uint32_t crc = df_wave_crc(~cnt.crc, mylen, s_x2k, lane);
     if (lane == 0) {
-        chunk_bytes[c] = (bits + DF_FRAME_BITS + 7) / 8 + 4;
+        chunk_bytes[c] = df_chunk_bytes(bits);
         chunk_crc[c] = crc;
     }
 }
@@ -170,53 +130,23 @@ template <int ELEM, bool NARROW>
 __global__ __launch_bounds__(DF_LANES) void deflate_emit_kernel(const uint8_t *in, long long n_bytes, const uint16_t *seg_bits,
                                                                 const unsigned *chunk_bytes, const long long *off, uint8_t *out) {
     __shared__ unsigned s_in[DF_LANES * DF_PITCH];
-    __shared__ u32x4 s_out[DF_OUT_VECS];
+    __shared__ u32x4 s_out[DF_OUT_VECS(DF_CHUNK_MAX_BYTES)];
     const int lane = threadIdx.x;
     const long long c = blockIdx.x;
     const int len = load_chunk<NARROW>(in, n_bytes, c, s_in);
     uint8_t *dst = out + off[c];
     const int mis = (int)((uintptr_t)dst & 15);                  // the chunk begins `mis` bytes into an aligned 16 bytes of `out`
     const int nbytes = (int)chunk_bytes[c];
-    const int vecs = (mis + nbytes + 15) / 16;                   // <= DF_OUT_VECS
-    for (int v = lane; v < vecs; v += DF_LANES) s_out[v] = (u32x4){0u, 0u, 0u, 0u};
-    const unsigned bits = seg_bits[c * DF_LANES + lane];
-    unsigned incl = bits;
-    for (int s = 1; s < DF_LANES; s <<= 1) {
-        const unsigned up = (unsigned)__shfl_up((int)incl, s);
-        if (lane >= s) incl += up;
-    }
+    const int vecs = (mis + nbytes + 15) / 16;                   // <= DF_OUT_VECS(DF_CHUNK_MAX_BYTES)
+    df_wave_zero(s_out, vecs, lane);
+    const unsigned first_bit = df_lane_first_bit(seg_bits[c * DF_LANES + lane], lane);
     __syncthreads();
-    unsigned *buf = (unsigned *)s_out;
-    DfEmit<ELEM> em(buf, (unsigned)mis * 8 + (lane == 0 ? 0u : 3u + incl - bits));
-    if (lane == 0) em.put(2u, 3);                                // BFINAL = 0, BTYPE = 01
-    df_walk<ELEM>(s_in + lane * DF_PITCH, seg_len(len, lane), em);
-    em.finish();
-    // end-of-block, the stored block's header, its padding and its LEN are zeros, which the buffer holds; NLEN = FF FF
-    if (lane < 2) {
-        const int b = mis + nbytes - 2 + lane;
-        atomicOr(buf + (b >> 2), 0xFFu << ((b & 3) * 8));
-    }
+    df_wave_emit<ELEM>((unsigned *)s_out, mis, nbytes, first_bit, lane, DfBytes{s_in + lane * DF_PITCH}, df_seg_len(len, lane));
     __syncthreads();
-    uint8_t *base = dst - mis;
-    for (int v = lane; v < vecs; v += DF_LANES) {
-        const int lo = v * 16;
-        if (lo >= mis && lo + 16 <= mis + nbytes) {
-            *(u32x4 *)(base + lo) = s_out[v];
-        } else {
-            const int b0 = lo < mis ? mis : lo, b1 = lo + 16 < mis + nbytes ? lo + 16 : mis + nbytes;
-            for (int b = b0; b < b1; ++b) base[b] = (uint8_t)(buf[b >> 2] >> ((b & 3) * 8));
-        }
-    }
+    df_wave_store(dst, mis, nbytes, vecs, s_out, lane);
 }
 
-struct Tables {
-    uint32_t x2k[64];                                            // x^(2^k) modulo the CRC-32 polynomial
-    Tables() {
-        x2k[0] = 0x40000000u;
-        for (int k = 1; k < 64; ++k) x2k[k] = df_mulmod(x2k[k - 1], x2k[k - 1]);
-    }
-};
-static const Tables g_tables;
+static const DfTables g_tables;
 
 template <int ELEM, bool NARROW>
 static void launch_pair(int pass, const uint8_t *in, long long n_bytes, long long chunks, const uint32_t *x2k, uint16_t *seg_bits,
@@ -232,14 +162,6 @@ static void launch_pair(int pass, const uint8_t *in, long long n_bytes, long lon
     }
 }
 
-static size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// this thread's kernel notes go to the log fnn_op_last_kernels reads: a refused call leaves it empty
-struct Klog {
-    Klog() { fnn_op_klog_begin(); }
-    ~Klog() { fnn_op_klog_end(); }
-};
-
 }  // namespace
 
 extern "C" int64_t fnn_deflate_bound(int64_t n_bytes) {
@@ -250,28 +172,28 @@ extern "C" int64_t fnn_deflate_bound(int64_t n_bytes) {
 
 extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out,
                                   int64_t out_cap, int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, void *stream) {
-    Klog klog;
-    if (!in || !out || !out_bytes || !file_elem_bytes || !crc32) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (in_elem_bytes != 1 && in_elem_bytes != 2) return fail_msg(FNN_E_INVALID, "fnn_deflate_labels: labels of 1 or 2 bytes are served");
-    if (n_elems < 0) return fail_msg(FNN_E_INVALID, "fnn_deflate_labels: negative element count");
-    if ((uintptr_t)in % 16) return fail_msg(FNN_E_INVALID, "fnn_deflate_labels: in must be aligned to 16 bytes");
+    FnnOpKlog klog;
+    if (!in || !out || !out_bytes || !file_elem_bytes || !crc32) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (in_elem_bytes != 1 && in_elem_bytes != 2) return fnn_fail(FNN_E_INVALID, "fnn_deflate_labels: labels of 1 or 2 bytes are served");
+    if (n_elems < 0) return fnn_fail(FNN_E_INVALID, "fnn_deflate_labels: negative element count");
+    if ((uintptr_t)in % 16) return fnn_fail(FNN_E_INVALID, "fnn_deflate_labels: in must be aligned to 16 bytes");
     // one block per chunk: 2^31 - 1 chunks of 16 KiB
     if (n_elems > ((int64_t)INT_MAX * DF_CHUNK) / in_elem_bytes)
-        return fail_msg(FNN_E_UNSUPPORTED, "fnn_deflate_labels: too many bytes for one launch sequence");
+        return fnn_fail(FNN_E_UNSUPPORTED, "fnn_deflate_labels: too many bytes for one launch sequence");
     const long long in_bytes = (long long)n_elems * in_elem_bytes;
-    if (out_cap < fnn_deflate_bound(in_bytes)) return fail_msg(FNN_E_INVALID, "fnn_deflate_labels: out_cap is below fnn_deflate_bound");
-    if (!dev_ptr(in) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "fnn_deflate_labels needs device pointers (no CPU path)");
+    if (out_cap < fnn_deflate_bound(in_bytes)) return fnn_fail(FNN_E_INVALID, "fnn_deflate_labels: out_cap is below fnn_deflate_bound");
+    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_deflate_labels needs device pointers (no CPU path)");
     *out_bytes = 0;
     *crc32 = 0;
     *file_elem_bytes = narrow_if_fits ? 1 : in_elem_bytes;
     if (n_elems == 0) return FNN_OK;
 
     const long long max_chunks = (in_bytes + DF_CHUNK - 1) / DF_CHUNK;
-    const size_t o_max = 0, o_x2k = 16, o_off = o_x2k + sizeof(g_tables.x2k), o_bytes = o_off + round16((size_t)(max_chunks + 1) * 8),
-                 o_crc = o_bytes + round16((size_t)max_chunks * 4), o_bits = o_crc + round16((size_t)max_chunks * 4),
+    const size_t o_max = 0, o_x2k = 16, o_off = o_x2k + sizeof(g_tables.x2k), o_bytes = o_off + df_align16((size_t)(max_chunks + 1) * 8),
+                 o_crc = o_bytes + df_align16((size_t)max_chunks * 4), o_bits = o_crc + df_align16((size_t)max_chunks * 4),
                  total = o_bits + (size_t)max_chunks * DF_LANES * 2;
     char *scratch = nullptr;
-    if (hipMalloc((void **)&scratch, total) != hipSuccess) { (void)hipGetLastError(); return fail_msg(FNN_E_HIP, "hipMalloc failed (deflate scratch)"); }
+    if (hipMalloc((void **)&scratch, total) != hipSuccess) { (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, "hipMalloc failed (deflate scratch)"); }
     unsigned *d_max = (unsigned *)(scratch + o_max);
     uint32_t *d_x2k = (uint32_t *)(scratch + o_x2k);
     long long *d_off = (long long *)(scratch + o_off);
@@ -315,13 +237,11 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
     if (r == hipSuccess) r = hipMemcpyAsync(h_crc.data(), d_crc, (size_t)chunks * 4, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     (void)hipFree(scratch);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     uint32_t crc = 0;
     const uint32_t x_chunk = df_xpow8(DF_CHUNK, g_tables.x2k);
-    for (long long c = 0; c < chunks; ++c) {
-        const long long len = c + 1 < chunks ? DF_CHUNK : n_bytes - c * DF_CHUNK;
-        crc = df_mulmod(crc, len == DF_CHUNK ? x_chunk : df_xpow8((unsigned long long)len, g_tables.x2k)) ^ h_crc[(size_t)c];
-    }
+    for (long long c = 0; c < chunks; ++c)
+        crc = df_crc_append(crc, h_crc[(size_t)c], c + 1 < chunks ? DF_CHUNK : n_bytes - c * DF_CHUNK, g_tables.x2k, x_chunk);
     *out_bytes = h_total;
     *file_elem_bytes = elem;
     *crc32 = crc;

@@ -5,50 +5,44 @@
 //   fnn_deflate_masks_count   sizes and CRC-32s of all fragments; what it found stays in `work`
 //   fnn_deflate_masks_emit    the fragments, one behind the other
 //
-// The stream format is deflate.hip's - independent chunks of DF_CHUNK = 16 KiB of mask bytes, each a non-final
-// fixed-Huffman block and an empty stored block, lane l of a wave tokenising segment l - with one change: a full chunk in
-// which the label does not occur is the constant zero chunk of DF_ZERO_CHUNK_BYTES = 112 bytes (deflate_core.h).  A 16 KiB
-// piece of an anatomical label map holds very few labels, so nearly every (chunk, label) pair is that constant, and the
-// walk work follows the pairs whose label occurs.
+// The stream format is deflate.hip's (deflate_core.h; the steps of a wave: deflate_wave.h) over the mask bytes, with the one
+// change stated there: a full chunk in which the label does not occur is the constant zero chunk.  A 16 KiB piece of an
+// anatomical label map holds very few labels, so nearly every (chunk, label) pair is that constant, and the walk work
+// follows the pairs whose label occurs.
 //
 //   deflate_masks_count_kernel<E>   one workgroup (4 waves) per chunk: the chunk's labels of E bytes -> LDS with 16-byte loads,
 //                                   marking a bitset by value on the way.  Per requested label that occurs (and for every
 //                                   label in a last partial chunk) one wave walks the chunk comparing on read
-//                                   (df_walk_mask: no mask bytes are stored) -> the pair's bytes (2 B) and CRC-32.  Pairs
+//                                   (DfMask: no mask bytes are stored) -> the pair's bytes (2 B) and CRC-32.  Pairs
 //                                   whose label is absent are not touched: their size stays 0 = "zero chunk".
 //   deflate_masks_scan_kernel       one workgroup per label: the sizes of its chunks -> their offsets in its fragment, the
 //                                   fragment's size, and the fold of the chunks' CRCs (the zero chunk's term is a constant).
 //   deflate_masks_emit_kernel<E>    the chunk and the bitset again (2 waves).  Absent labels: the 112 constant bytes, 8 lanes
-//                                   per pair, from a table that holds the constant at each of the 16 alignments, so that
-//                                   whole aligned 16-byte vectors of `out` are stored whole and the ends byte by byte.
-//                                   Present labels: a wave walks twice - the bits per lane, then the codes OR-ed into its
-//                                   zeroed bit buffer (ds_or_b32, order independent) - and stores as deflate_emit_kernel.
+//                                   per pair, from a table that holds the constant at each of the 16 alignments: an image
+//                                   that df_store_vec takes like a bit buffer.  Present labels: a wave walks twice - the
+//                                   bits per lane, then the codes into its bit buffer - and stores as deflate_emit_kernel.
 //
 // LDS.  A segment of 256 labels lies at a pitch of 64 E + 1 dwords (odd: the lanes' walks fall on different banks), so
 // the chunk takes 16.25 KiB (E = 1) or 32.25 KiB (E = 2); the bitset 32 B or 8 KiB.  count: + the CRC table 1 KiB, the
 // powers 256 B, the list of present labels 1 KiB = 18.6 KiB / 42.6 KiB, static.  emit: + the alignment table 2 KiB, the
-// list 0.5 KiB and per wave a bit buffer of (15 + DF_MASK_CHUNK_MAX_BYTES + 15) / 16 vectors = 16.03 KiB: with two waves
+// list 0.5 KiB and per wave a bit buffer of DF_OUT_VECS(DF_MASK_CHUNK_MAX_BYTES) vectors = 16.03 KiB: with two waves
 // 50.9 KiB / 74.9 KiB, dynamic (three / two workgroups per CU).  deflate.hip's layout - a padded image of the mask bytes
 // per wave next to its bit buffer - would need 34.6 KiB per wave on top of the chunk.
 // Nothing is written outside out[0, sum of the fragment sizes); no kernel keeps scratch.
 #include "fnn_device.h"
-#include "deflate_core.h"
+#include "deflate_wave.h"
 #include "../../include/fnn.h"
 #include <climits>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MK_COUNT_WAVES = 4, MK_COUNT_THREADS = MK_COUNT_WAVES * DF_LANES;
 constexpr int MK_EMIT_WAVES = 2, MK_EMIT_THREADS = MK_EMIT_WAVES * DF_LANES;
 constexpr int MK_SCAN_THREADS = 1024;
-constexpr int MK_OUT_VECS = (15 + DF_MASK_CHUNK_MAX_BYTES + 15) / 16;     // a wave's bit buffer
+constexpr int MK_OUT_VECS = DF_OUT_VECS(DF_MASK_CHUNK_MAX_BYTES);         // a wave's bit buffer
 constexpr int MK_MAX_LABELS = 65536;                                      // every value of a 2-byte label once
 constexpr int MK_ZERO_PITCH = 128;                                        // the zero chunk behind up to 15 bytes, in whole vectors
 
@@ -61,16 +55,6 @@ template <int E> struct MkLayout {
 };
 static_assert(MkLayout<1>::IN_DW % 4 == 0 && MkLayout<2>::IN_DW % 4 == 0, "the parts behind the chunk stay 16-byte aligned");
 
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
-static size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // `work`: what count leaves for emit
 struct MkWork {
     size_t o_x2k, o_zero, o_labels, o_frag, o_fbytes, o_fcrc, o_slots, o_sizes, total;
@@ -79,22 +63,19 @@ struct MkWork {
         o_x2k = 0;                                       // x^(2^k) modulo the CRC polynomial, 64 x 4 B
         o_zero = 256;                                    // the zero chunk, 112 B in 128
         o_labels = o_zero + 128;                         // the labels, 4 B each
-        o_frag = o_labels + round16(4 * L);              // where each fragment begins in `out`, and the end of the last: 8 B each
-        o_fbytes = o_frag + round16(8 * (L + 1));        // the fragments' sizes, 8 B each
-        o_fcrc = o_fbytes + round16(8 * L);              // their CRCs, 4 B each
-        o_slots = o_fcrc + round16(4 * L);               // per (label, chunk): the chunk's CRC, then its offset in the fragment, 8 B
+        o_frag = o_labels + df_align16(4 * L);           // where each fragment begins in `out`, and the end of the last: 8 B each
+        o_fbytes = o_frag + df_align16(8 * (L + 1));     // the fragments' sizes, 8 B each
+        o_fcrc = o_fbytes + df_align16(8 * L);           // their CRCs, 4 B each
+        o_slots = o_fcrc + df_align16(4 * L);            // per (label, chunk): the chunk's CRC, then its offset in the fragment, 8 B
         o_sizes = o_slots + 8 * pairs;                   // per (label, chunk): the chunk's bytes, 0 = the zero chunk, 2 B
-        total = o_sizes + round16(2 * pairs);
+        total = o_sizes + df_align16(2 * pairs);
     }
 };
 
-struct Tables {
-    uint32_t x2k[64];                                    // x^(2^k) modulo the CRC-32 polynomial
+struct MkTables : DfTables {
     uint8_t zero[128];                                   // the zero chunk
     uint32_t zero_crc;                                   // zlib's CRC-32 of DF_CHUNK zero bytes
-    Tables() {
-        x2k[0] = 0x40000000u;
-        for (int k = 1; k < 64; ++k) x2k[k] = df_mulmod(x2k[k - 1], x2k[k - 1]);
+    MkTables() {
         memset(zero, 0, sizeof(zero));
         df_zero_chunk(zero);
         uint32_t c = 0xFFFFFFFFu;
@@ -102,7 +83,7 @@ struct Tables {
         zero_crc = ~c;
     }
 };
-static const Tables g_tables;
+static const MkTables g_tables;
 
 // chunk `c` of the map -> s_in (segment s at dword s * PITCH), every value met marked in s_bits (zeroed before);
 // -> the chunk's length in elements.  Nothing past element n is read.
@@ -135,11 +116,6 @@ static __device__ __forceinline__ int load_chunk_and_mark(const uint8_t *in, lon
     return len;
 }
 
-static __device__ __forceinline__ int seg_len(int chunk_len, int lane) {
-    const int l = chunk_len - lane * DF_SEG;
-    return l < 0 ? 0 : (l > DF_SEG ? DF_SEG : l);
-}
-
 template <int E> static __device__ __forceinline__ bool occurs(const unsigned *s_bits, int label) {
     return (unsigned)label < MkLayout<E>::VALUES && ((s_bits[label >> 5] >> (label & 31)) & 1u);
 }
@@ -157,11 +133,7 @@ __global__ __launch_bounds__(MK_COUNT_THREADS) void deflate_masks_count_kernel(c
     __shared__ int s_n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long c = blockIdx.x;
-    {
-        uint32_t t = tid;
-        for (int i = 0; i < 8; ++i) t = (t >> 1) ^ ((t & 1) ? DF_POLY : 0u);
-        s_tab[tid] = t;
-    }
+    df_crc_table<MK_COUNT_THREADS>(s_tab, tid);
     if (tid < 64) s_x2k[tid] = x2k[tid];
     for (int i = tid; i < Lay::BITS_DW; i += MK_COUNT_THREADS) s_bits[i] = 0u;
     __syncthreads();
@@ -176,23 +148,13 @@ __global__ __launch_bounds__(MK_COUNT_THREADS) void deflate_masks_count_kernel(c
         const int np = s_n;
         for (int i = wave; i < np; i += MK_COUNT_WAVES) {
             const int kk = s_list[i];
-            int mylen = seg_len(len, lane);
+            const int mylen = df_seg_len(len, lane);
             DfCount<1> cnt{s_tab};
-            df_walk_mask<E>(s_in + lane * Lay::PITCH, mylen, (unsigned)labels[kk], cnt);
-            unsigned bits = cnt.bits;
-            for (int s = 32; s > 0; s >>= 1) bits += (unsigned)__shfl_xor((int)bits, s);
-            // lane l takes over lanes l .. l + 2 s - 1: its own bytes, then those of lane l + s
-            uint32_t crc = ~cnt.crc;
-            for (int s = 1; s < DF_LANES; s <<= 1) {
-                const uint32_t ocrc = (uint32_t)__shfl_down((int)crc, s);
-                const int olen = __shfl_down(mylen, s);
-                if ((lane & (2 * s - 1)) == 0 && olen > 0) {
-                    crc = df_mulmod(crc, df_xpow8((unsigned long long)olen, s_x2k)) ^ ocrc;
-                    mylen += olen;
-                }
-            }
+            df_walk<1>(DfMask<E>{s_in + lane * Lay::PITCH, (unsigned)labels[kk]}, mylen, cnt);
+            const unsigned bits = df_wave_sum(cnt.bits);
+            const uint32_t crc = df_wave_crc(~cnt.crc, mylen, s_x2k, lane);
             if (lane == 0) {
-                sizes[(long long)kk * chunks + c] = (uint16_t)((bits + DF_FRAME_BITS + 7) / 8 + 4);
+                sizes[(long long)kk * chunks + c] = (uint16_t)df_chunk_bytes(bits);
                 slots[(long long)kk * chunks + c] = crc;
             }
         }
@@ -222,7 +184,7 @@ __global__ __launch_bounds__(MK_SCAN_THREADS) void deflate_masks_scan_kernel(con
         const unsigned s = sz[i];
         sum += s ? s : DF_ZERO_CHUNK_BYTES;
         const int li = i == chunks - 1 ? last_len : DF_CHUNK;
-        crc = df_mulmod(crc, li == DF_CHUNK ? x_chunk : df_xpow8((unsigned long long)li, s_x2k)) ^ (s ? (uint32_t)sl[i] : zero_crc);
+        crc = df_crc_append(crc, s ? (uint32_t)sl[i] : zero_crc, (unsigned long long)li, s_x2k, x_chunk);
         len += li;
     }
     s_sum[t] = sum;
@@ -233,7 +195,7 @@ __global__ __launch_bounds__(MK_SCAN_THREADS) void deflate_masks_scan_kernel(con
         const long long add = t >= s ? s_sum[t - s] : 0;
         // thread t takes over threads t .. t + 2 s - 1: its own chunks, then those of thread t + s (which does not write here)
         if ((t & (2 * s - 1)) == 0 && s_len[t + s] > 0) {
-            s_crc[t] = df_mulmod(s_crc[t], df_xpow8((unsigned long long)s_len[t + s], s_x2k)) ^ s_crc[t + s];
+            s_crc[t] = df_crc_append(s_crc[t], s_crc[t + s], (unsigned long long)s_len[t + s], s_x2k, x_chunk);
             s_len[t] += s_len[t + s];
         }
         __syncthreads();
@@ -289,14 +251,7 @@ __global__ __launch_bounds__(MK_EMIT_THREADS) void deflate_masks_emit_kernel(con
             if (at < 0 || at + DF_ZERO_CHUNK_BYTES > total) continue;     // (a `work` that count did not fill must not reach outside `out`)
             uint8_t *dst = out + at;
             const int mis = (int)((uintptr_t)dst & 15);
-            uint8_t *base = dst - mis;
-            const uint8_t *src = s_zero + mis * MK_ZERO_PITCH;
-            if (lo >= mis && lo + 16 <= mis + DF_ZERO_CHUNK_BYTES) {
-                *(u32x4 *)(base + lo) = *(const u32x4 *)(src + lo);
-            } else {
-                const int b0 = lo < mis ? mis : lo, b1 = lo + 16 < mis + DF_ZERO_CHUNK_BYTES ? lo + 16 : mis + DF_ZERO_CHUNK_BYTES;
-                for (int b = b0; b < b1; ++b) base[b] = src[b];
-            }
+            df_store_vec(dst - mis, lo, mis, DF_ZERO_CHUNK_BYTES, s_zero + mis * MK_ZERO_PITCH);
         }
         __syncthreads();
         const int np = *s_n;
@@ -315,60 +270,29 @@ __global__ __launch_bounds__(MK_EMIT_THREADS) void deflate_masks_emit_kernel(con
                 mis = (int)((uintptr_t)dst & 15);                // the chunk begins `mis` bytes into an aligned 16 bytes of `out`
                 vecs = (mis + nbytes + 15) / 16;                 // <= MK_OUT_VECS
                 if (vecs > MK_OUT_VECS) vecs = MK_OUT_VECS;      // (a `work` that count did not fill must not reach past the buffer)
-                for (int v = lane; v < vecs; v += DF_LANES) my_out[v] = (u32x4){0u, 0u, 0u, 0u};
-                DfBits cnt;
-                df_walk_mask<E>(s_in + lane * Lay::PITCH, seg_len(len, lane), label, cnt);
+                df_wave_zero(my_out, vecs, lane);
+                DfCount<1, false> cnt;
+                df_walk<1>(DfMask<E>{s_in + lane * Lay::PITCH, label}, df_seg_len(len, lane), cnt);
                 bits = cnt.bits;
             }
-            unsigned incl = bits;
-            for (int s = 1; s < DF_LANES; s <<= 1) {
-                const unsigned up = (unsigned)__shfl_up((int)incl, s);
-                if (lane >= s) incl += up;
-            }
-            const unsigned all_bits = (unsigned)__shfl((int)incl, DF_LANES - 1);
+            unsigned all_bits;
+            const unsigned first_bit = df_lane_first_bit(bits, lane, &all_bits);
             // what the walk is about to write must be what count sized, or the buffer and `out` would be overrun
-            const bool fits = act && (int)((all_bits + DF_FRAME_BITS + 7) / 8 + 4) == nbytes && nbytes <= DF_MASK_CHUNK_MAX_BYTES;
+            const bool fits = act && (int)df_chunk_bytes(all_bits) == nbytes && nbytes <= DF_MASK_CHUNK_MAX_BYTES;
             __syncthreads();
-            if (fits) {
-                DfEmit<1> em(buf, (unsigned)mis * 8 + (lane == 0 ? 0u : 3u + incl - bits));
-                if (lane == 0) em.put(2u, 3);                    // BFINAL = 0, BTYPE = 01
-                df_walk_mask<E>(s_in + lane * Lay::PITCH, seg_len(len, lane), label, em);
-                em.finish();
-                // end-of-block, the stored block's header, its padding and its LEN are zeros, which the buffer holds; NLEN = FF FF
-                if (lane < 2) {
-                    const int b = mis + nbytes - 2 + lane;
-                    atomicOr(buf + (b >> 2), 0xFFu << ((b & 3) * 8));
-                }
-            }
+            if (fits) df_wave_emit<1>(buf, mis, nbytes, first_bit, lane, DfMask<E>{s_in + lane * Lay::PITCH, label}, df_seg_len(len, lane));
             __syncthreads();
-            if (fits) {
-                uint8_t *base = dst - mis;
-                for (int v = lane; v < vecs; v += DF_LANES) {
-                    const int lo = v * 16;
-                    if (lo >= mis && lo + 16 <= mis + nbytes) {
-                        *(u32x4 *)(base + lo) = my_out[v];
-                    } else {
-                        const int b0 = lo < mis ? mis : lo, b1 = lo + 16 < mis + nbytes ? lo + 16 : mis + nbytes;
-                        for (int b = b0; b < b1; ++b) base[b] = (uint8_t)(buf[b >> 2] >> ((b & 3) * 8));
-                    }
-                }
-            }
+            if (fits) df_wave_store(dst, mis, nbytes, vecs, my_out, lane);
         }
         __syncthreads();                                         // the list is read out before the next tile resets it
     }
 }
 
-// this thread's kernel notes go to the log fnn_op_last_kernels reads: a refused call leaves it empty
-struct Klog {
-    Klog() { fnn_op_klog_begin(); }
-    ~Klog() { fnn_op_klog_end(); }
-};
-
 // what both calls refuse before they launch anything -> 0, or the code (the message is set)
 static int check_common(const char *who, const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
                         const void *work) {
     static thread_local char msg[160];
-    auto fail = [&](int code, const char *what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return fail_msg(code, msg); };
+    auto fail = [&](int code, const char *what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return fnn_fail(code, msg); };
     if (!in || !labels || !work) return fail(FNN_E_INVALID, "NULL argument");
     if (in_elem_bytes != 1 && in_elem_bytes != 2) return fail(FNN_E_INVALID, "labels of 1 or 2 bytes are served");
     if (n_elems < 0) return fail(FNN_E_INVALID, "negative element count");
@@ -395,12 +319,12 @@ extern "C" int64_t fnn_deflate_masks_work_bytes(int64_t n_elems, int n_labels) {
 
 extern "C" int fnn_deflate_masks_count(const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
                                        void *work, int64_t work_cap, int64_t *frag_bytes, uint32_t *crc32, void *stream) {
-    Klog klog;
-    if (!frag_bytes || !crc32) return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_count: NULL argument");
+    FnnOpKlog klog;
+    if (!frag_bytes || !crc32) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_count: NULL argument");
     if (const int rc = check_common("fnn_deflate_masks_count", in, in_elem_bytes, n_elems, labels, n_labels, work)) return rc;
     const MkWork w(n_elems, n_labels);
-    if (work_cap < (int64_t)w.total) return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_count: work_cap is below fnn_deflate_masks_work_bytes");
-    if (!dev_ptr(in) || !dev_ptr(work)) return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_count needs device pointers for in and work (no CPU path)");
+    if (work_cap < (int64_t)w.total) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_count: work_cap is below fnn_deflate_masks_work_bytes");
+    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(work)) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_count needs device pointers for in and work (no CPU path)");
     for (int k = 0; k < n_labels; ++k) { frag_bytes[k] = 0; crc32[k] = 0; }
     if (n_elems == 0) return FNN_OK;
 
@@ -446,19 +370,19 @@ extern "C" int fnn_deflate_masks_count(const void *in, int in_elem_bytes, int64_
     }
     if (r != hipSuccess) {
         for (int k = 0; k < n_labels; ++k) { frag_bytes[k] = 0; crc32[k] = 0; }
-        return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+        return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     }
     return FNN_OK;
 }
 
 extern "C" int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
                                       const void *work, void *out, int64_t out_cap, void *stream) {
-    Klog klog;
-    if (!out) return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_emit: NULL argument");
+    FnnOpKlog klog;
+    if (!out) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: NULL argument");
     if (const int rc = check_common("fnn_deflate_masks_emit", in, in_elem_bytes, n_elems, labels, n_labels, work)) return rc;
-    if (out_cap < 0) return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_emit: out_cap is negative");
-    if (!dev_ptr(in) || !dev_ptr(work) || !dev_ptr(out))
-        return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_emit needs device pointers for in, work and out (no CPU path)");
+    if (out_cap < 0) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: out_cap is negative");
+    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(work) || !fnn_dev_ptr(out))
+        return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit needs device pointers for in, work and out (no CPU path)");
     if (n_elems == 0) return FNN_OK;
 
     const MkWork w(n_elems, n_labels);
@@ -472,10 +396,10 @@ extern "C" int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t
     hipError_t r = hipMemcpyAsync(&total, d_frag + n_labels, 8, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipMemcpyAsync(h_labels.data(), base + w.o_labels, (size_t)n_labels * 4, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     if (memcmp(h_labels.data(), labels, (size_t)n_labels * 4) != 0)
-        return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_emit: work was not filled by fnn_deflate_masks_count for these labels");
-    if (total < 0 || out_cap < total) return fail_msg(FNN_E_INVALID, "fnn_deflate_masks_emit: out_cap is below the sum of the fragment sizes");
+        return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: work was not filled by fnn_deflate_masks_count for these labels");
+    if (total < 0 || out_cap < total) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: out_cap is below the sum of the fragment sizes");
     int rc;
     if (in_elem_bytes == 1)
         rc = fnn_launch_lds<deflate_masks_emit_kernel<1>>(dim3((unsigned)chunks), dim3(MK_EMIT_THREADS), (size_t)MkLayout<1>::EMIT_LDS, st,
@@ -488,6 +412,6 @@ extern "C" int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t
                                                           (const uint16_t *)(base + w.o_sizes), (const unsigned long long *)(base + w.o_slots), d_frag,
                                                           (const uint8_t *)(base + w.o_zero), (uint8_t *)out, total);
     fnn_note_kernel("deflate_masks_emit_kernel<%d>", in_elem_bytes);
-    if (rc != 0) return fail_msg(FNN_E_HIP, "fnn_deflate_masks_emit: the launch failed");
+    if (rc != 0) return fnn_fail(FNN_E_HIP, "fnn_deflate_masks_emit: the launch failed");
     return FNN_OK;
 }

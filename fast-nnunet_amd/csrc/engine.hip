@@ -169,8 +169,14 @@ struct fnn_engine {
     fnn_profile prof{};
 };
 
-// message of an entry point that has no engine handle (prep.hip)
+// what the entry points that have no engine handle share (fnn_device.h)
 void fnn_set_global_error(const char *msg) { g_err = msg ? msg : ""; }
+int fnn_fail(int code, const char *msg) { fnn_set_global_error(msg); return code; }
+bool fnn_dev_ptr(const void *p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
 
 namespace {
 
@@ -190,12 +196,6 @@ int fail(fnn_engine *e, int code, const char *fmt, ...) {
         hipError_t _r = (call);                                                                      \
         if (_r != hipSuccess) return fail(e, FNN_E_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
     } while (0)
-
-bool is_device_ptr(const void *p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
 
 template <class T> int ensure(fnn_engine *e, T **p, size_t *have, size_t need) {
     if (*have >= need && *p) return 0;
@@ -1182,7 +1182,7 @@ int stage_volume(fnn_engine *e, const float *vol, const int64_t shape[4], const 
     const bool need_pad = vp.padded[0] != shape[1] || vp.padded[1] != shape[2] || vp.padded[2] != shape[3];
     fnn_engine::Upload &u = e->up;
     u.active = false; u.n_issued = 0;
-    if (!is_device_ptr(vol)) {
+    if (!fnn_dev_ptr(vol)) {
         if (int rc = ensure(e, &e->vol_tmp, &e->vol_tmp_bytes, nin * sizeof(float))) return rc;
         src = e->vol_tmp;
         u.host = vol; u.dev = e->vol_tmp; u.C = (int)shape[0]; u.X = shape[1]; u.Y = shape[2]; u.Z = shape[3];
@@ -1432,8 +1432,8 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     const size_t nout = (size_t)a.num_heads * nvox_out;
     const size_t osz = o->out_dtype == FNN_OUT_F32 ? 4 : 2;
     const bool want_logits = out != nullptr;
-    const bool out_on_dev = out && is_device_ptr(out);
-    const bool lab_on_dev = labels && is_device_ptr(labels);
+    const bool out_on_dev = out && fnn_dev_ptr(out);
+    const bool lab_on_dev = labels && fnn_dev_ptr(labels);
     const size_t lab_bytes = nvox_out * (e->label_u16 ? 2 : 1);
     // (the plan first: nothing is allocated yet when it refuses the request, and it decides how labels are formed; the
     // staging buffers that ARE allocated afterwards - fp16 / fp32 logits when the caller's are on the host or the labels
@@ -1529,7 +1529,7 @@ int finalize_box(fnn_engine *e, const char *who, const void *acc, const int64_t 
     if (int rc = no_autocast(e, opts, who)) return rc;
     void *dst = out ? out : labels;
     if (!acc || !dst || !box_lo || !box_hi || !out_lo || !out_hi) return fail(e, FNN_E_INVALID, "NULL argument");
-    if (!is_device_ptr(acc) || !is_device_ptr(dst)) return fail(e, FNN_E_INVALID, "%s needs device pointers", who);
+    if (!fnn_dev_ptr(acc) || !fnn_dev_ptr(dst)) return fail(e, FNN_E_INVALID, "%s needs device pointers", who);
     if (labels && acc_hp(e->arch) > 256)
         return fail(e, FNN_E_UNSUPPORTED, "fnn_labels_box serves up to 254 classes (%d here): take the logits (fnn_normalize_box) and fnn_argmax_labels", e->arch.num_heads);
     if (labels) if (int rc = check_u8_labels(e, e->arch.num_heads, U16_HINT)) return rc;
@@ -1726,7 +1726,7 @@ int fnn_accumulate_patches(fnn_engine *e, int fold, const float *vol, const int6
     if (int rc = check_ready(e, fold, opts)) return rc;
     if (int rc = no_autocast(e, opts, "fnn_accumulate_patches")) return rc;
     if (!vol || !acc || !box_lo || !box_hi || (n_ids > 0 && !patch_ids)) return fail(e, FNN_E_INVALID, "NULL argument");
-    if (!is_device_ptr(acc)) return fail(e, FNN_E_INVALID, "accumulators must be device memory");
+    if (!fnn_dev_ptr(acc)) return fail(e, FNN_E_INVALID, "accumulators must be device memory");
     HIPCHK(e, hipSetDevice(e->device));
     VolPlan vp;
     if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
@@ -1756,7 +1756,7 @@ int fnn_patch_features(fnn_engine *e, int fold, const float *vol, const int64_t 
                        const int64_t *patch_ids, int64_t n_ids, void *feat, float *fss, int64_t slot0, int64_t n_slots) {
     if (int rc = check_ready(e, fold, opts)) return rc;
     if (!vol || !feat || !fss || (n_ids > 0 && !patch_ids)) return fail(e, FNN_E_INVALID, "NULL argument");
-    if (!is_device_ptr(feat) || !is_device_ptr(fss)) return fail(e, FNN_E_INVALID, "feature buffers must be device memory");
+    if (!fnn_dev_ptr(feat) || !fnn_dev_ptr(fss)) return fail(e, FNN_E_INVALID, "feature buffers must be device memory");
     if (slot0 < 0 || n_slots < slot0 + n_ids) return fail(e, FNN_E_INVALID, "slots [%lld, %lld) do not fit %lld slots", (long long)slot0, (long long)(slot0 + n_ids), (long long)n_slots);
     if (1 + (int)mirror_combos(*opts).size() > 8) return fail(e, FNN_E_UNSUPPORTED, "more than 8 evaluations per patch");
     if (!e->layers[e->head_src].has_norm) return fail(e, FNN_E_UNSUPPORTED, "the network's last layer has no InstanceNorm");
@@ -1771,7 +1771,7 @@ int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, 
                    void *out_logits, void *labels) {
     if (int rc = check_ready(e, fold, opts)) return rc;
     if (!feat || !fss || !slot_of_patch || !out_lo || !out_hi || (!out_logits && !labels)) return fail(e, FNN_E_INVALID, "NULL argument");
-    if (!is_device_ptr(feat) || !is_device_ptr(fss) || (out_logits && !is_device_ptr(out_logits)) || (labels && !is_device_ptr(labels)))
+    if (!fnn_dev_ptr(feat) || !fnn_dev_ptr(fss) || (out_logits && !fnn_dev_ptr(out_logits)) || (labels && !fnn_dev_ptr(labels)))
         return fail(e, FNN_E_INVALID, "fnn_gather_box needs device pointers");
     if (opts->out_dtype != FNN_OUT_F16) return fail(e, FNN_E_UNSUPPORTED, "fnn_gather_box: fp16 logits");
     HIPCHK(e, hipSetDevice(e->device));
@@ -1826,7 +1826,7 @@ static int region_copy(fnn_engine *e, void *feat, int64_t n_slots, const fnn_reg
     if (!e) return FNN_E_INVALID;
     if (n == 0) return 0;
     if (!feat || !regions || !message || n < 0 || n_slots < 1) return fail(e, FNN_E_INVALID, "bad argument");
-    if (!is_device_ptr(feat) || !is_device_ptr(regions) || !is_device_ptr(message))
+    if (!fnn_dev_ptr(feat) || !fnn_dev_ptr(regions) || !fnn_dev_ptr(message))
         return fail(e, FNN_E_INVALID, "fnn_pack_regions / fnn_unpack_regions need device pointers (the region table too)");
     if (n > 65535) return fail(e, FNN_E_INVALID, "more than 65535 regions in one message");
     static_assert(sizeof(fnn_region) == 40, "fnn_region is ten 32-bit words");
@@ -1856,13 +1856,13 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
     const size_t P = (size_t)a.patch[0] * a.patch[1] * a.patch[2];
     const size_t nin = (size_t)n * a.in_channels * P, nout = (size_t)n * a.num_heads * P;
     const float *xd = x;
-    if (!is_device_ptr(x)) {
+    if (!fnn_dev_ptr(x)) {
         if (int rc = ensure(e, &e->vol_tmp, &e->vol_tmp_bytes, nin * 4)) return rc;
         HIPCHK(e, hipMemcpyAsync(e->vol_tmp, x, nin * 4, hipMemcpyHostToDevice, st));
         xd = e->vol_tmp;
     }
     float *od = logits;
-    const bool out_dev = is_device_ptr(logits);
+    const bool out_dev = fnn_dev_ptr(logits);
     if (!out_dev) {
         if (int rc = ensure(e, &e->out_tmp, &e->out_tmp_bytes, nout * 4)) return rc;
         od = (float *)e->out_tmp;
@@ -1918,7 +1918,7 @@ int fnn_argmax_labels(fnn_engine *e, const void *logits, int dtype, int heads, i
     const bool regions = e->label_mode == FNN_LABELS_REGIONS;
     if (regions && heads != e->arch.num_heads) return fail(e, FNN_E_INVALID, "the region rule was set for %d heads, got %d", e->arch.num_heads, heads);
     if (int rc = check_u8_labels(e, heads, "")) return rc;
-    if (!is_device_ptr(logits) || !is_device_ptr(labels)) return fail(e, FNN_E_INVALID, "fnn_argmax_labels needs device pointers");
+    if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(labels)) return fail(e, FNN_E_INVALID, "fnn_argmax_labels needs device pointers");
     HIPCHK(e, hipSetDevice(e->device));
     if (launch_argmax(logits, dtype == FNN_OUT_F32, heads, n_vox, labels, e->label_u16, regions ? e->label_order : nullptr,
                       (hipStream_t)stream) != 0)

@@ -22,21 +22,11 @@
 
 #pragma clang fp contract(off)
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
 
 constexpr int ENS_MAX_MEMBERS = 16;
 constexpr int ENS_THREADS = 256;
 constexpr int ENS_VEC_MAX_MEMBERS = 8;           // the VEC = 4 kernels keep 2 x 4 floats of softmax state per member
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 static int check_perm(const int32_t t[3]) {
     int seen = 0;
@@ -234,7 +224,7 @@ static hipError_t upload_order(const int32_t *regions_class_order, int heads, hi
 static int finish(hipError_t r, hipStream_t st, int *order) {
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     if (order) (void)hipFree(order);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }
 
@@ -246,23 +236,23 @@ int fnn_ensemble_export(const void *const *member_logits, const int32_t *member_
                         const int32_t *regions_class_order, const int64_t bbox[6], const int64_t shape_before_cropping[3],
                         const int32_t transpose_backward[3], float *avg_probs, void *labels, int label_dtype, void *stream) {
     if (!member_logits || !member_dtype || !bbox || !shape_before_cropping || !transpose_backward || !labels)
-        return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (n_members < 1 || n_members > ENS_MAX_MEMBERS) return fail_msg(FNN_E_INVALID, "n_members must be 1..16");
+        return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (n_members < 1 || n_members > ENS_MAX_MEMBERS) return fnn_fail(FNN_E_INVALID, "n_members must be 1..16");
     for (int m = 0; m < n_members; ++m) {
-        if (!member_logits[m]) return fail_msg(FNN_E_INVALID, "NULL member logits");
-        if (member_dtype[m] != FNN_OUT_F16 && member_dtype[m] != FNN_OUT_F32) return fail_msg(FNN_E_INVALID, "unknown member logits dtype");
+        if (!member_logits[m]) return fnn_fail(FNN_E_INVALID, "NULL member logits");
+        if (member_dtype[m] != FNN_OUT_F16 && member_dtype[m] != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown member logits dtype");
     }
-    if (heads < 1 || heads > 4096) return fail_msg(FNN_E_INVALID, "bad number of heads");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
-    if (check_perm(transpose_backward) != 0) return fail_msg(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
+    if (heads < 1 || heads > 4096) return fnn_fail(FNN_E_INVALID, "bad number of heads");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (check_perm(transpose_backward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
     EnsembleArgs a{};
     for (int d = 0; d < 3; ++d) {
         a.lo[d] = bbox[2 * d]; a.e[d] = bbox[2 * d + 1] - bbox[2 * d];
-        if (a.lo[d] < 0 || a.e[d] < 1 || bbox[2 * d + 1] > shape_before_cropping[d]) return fail_msg(FNN_E_INVALID, "bbox outside shape_before_cropping");
+        if (a.lo[d] < 0 || a.e[d] < 1 || bbox[2 * d + 1] > shape_before_cropping[d]) return fnn_fail(FNN_E_INVALID, "bbox outside shape_before_cropping");
     }
     for (int m = 0; m < n_members; ++m)
-        if (!dev_ptr(member_logits[m])) return fail_msg(FNN_E_INVALID, "fnn_ensemble_export needs device pointers (no CPU path)");
-    if (!dev_ptr(labels) || (avg_probs && !dev_ptr(avg_probs))) return fail_msg(FNN_E_INVALID, "fnn_ensemble_export needs device pointers (no CPU path)");
+        if (!fnn_dev_ptr(member_logits[m])) return fnn_fail(FNN_E_INVALID, "fnn_ensemble_export needs device pointers (no CPU path)");
+    if (!fnn_dev_ptr(labels) || (avg_probs && !fnn_dev_ptr(avg_probs))) return fnn_fail(FNN_E_INVALID, "fnn_ensemble_export needs device pointers (no CPU path)");
     for (int j = 0; j < 3; ++j) { a.o[j] = shape_before_cropping[transpose_backward[j]]; a.tb[j] = transpose_backward[j]; }
     a.N = n_members; a.H = heads; a.avg = avg_probs;
     for (int m = 0; m < n_members; ++m) {
@@ -275,7 +265,7 @@ int fnn_ensemble_export(const void *const *member_logits, const int32_t *member_
     for (int m = 0; m < n_members; ++m) vec = vec && aligned(member_logits[m], 16);
     const long long n = a.o[0] * a.o[1] * a.o[2];
     const int V = vec ? 4 : 1;
-    if ((n / V + ENS_THREADS - 1) / ENS_THREADS > UINT_MAX) return fail_msg(FNN_E_UNSUPPORTED, "output grid too large");
+    if ((n / V + ENS_THREADS - 1) / ENS_THREADS > UINT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "output grid too large");
     hipStream_t st = (hipStream_t)stream;
     int *order = nullptr;
     hipError_t r = upload_order(regions_class_order, heads, st, &order);
@@ -296,17 +286,17 @@ int fnn_ensemble_export(const void *const *member_logits, const int32_t *member_
 
 int fnn_average_probabilities(const float *const *member_probs, int n_members, int heads, const int32_t *regions_class_order,
                               int64_t n_vox, float *avg_probs, void *labels, int label_dtype, void *stream) {
-    if (!member_probs || !labels) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (n_members < 1 || n_members > ENS_MAX_MEMBERS) return fail_msg(FNN_E_INVALID, "n_members must be 1..16");
+    if (!member_probs || !labels) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (n_members < 1 || n_members > ENS_MAX_MEMBERS) return fnn_fail(FNN_E_INVALID, "n_members must be 1..16");
     for (int m = 0; m < n_members; ++m)
-        if (!member_probs[m]) return fail_msg(FNN_E_INVALID, "NULL member probabilities");
-    if (heads < 1 || heads > 4096) return fail_msg(FNN_E_INVALID, "bad number of heads");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
-    if (n_vox < 0) return fail_msg(FNN_E_INVALID, "negative n_vox");
+        if (!member_probs[m]) return fnn_fail(FNN_E_INVALID, "NULL member probabilities");
+    if (heads < 1 || heads > 4096) return fnn_fail(FNN_E_INVALID, "bad number of heads");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (n_vox < 0) return fnn_fail(FNN_E_INVALID, "negative n_vox");
     if (n_vox == 0) return FNN_OK;
     for (int m = 0; m < n_members; ++m)
-        if (!dev_ptr(member_probs[m])) return fail_msg(FNN_E_INVALID, "fnn_average_probabilities needs device pointers (no CPU path)");
-    if (!dev_ptr(labels) || (avg_probs && !dev_ptr(avg_probs))) return fail_msg(FNN_E_INVALID, "fnn_average_probabilities needs device pointers (no CPU path)");
+        if (!fnn_dev_ptr(member_probs[m])) return fnn_fail(FNN_E_INVALID, "fnn_average_probabilities needs device pointers (no CPU path)");
+    if (!fnn_dev_ptr(labels) || (avg_probs && !fnn_dev_ptr(avg_probs))) return fnn_fail(FNN_E_INVALID, "fnn_average_probabilities needs device pointers (no CPU path)");
     EnsembleArgs a{};
     a.N = n_members; a.H = heads; a.avg = avg_probs;
     const size_t lbytes = label_dtype == FNN_LABEL_U16 ? 2 : 1;
@@ -318,7 +308,7 @@ int fnn_average_probabilities(const float *const *member_probs, int n_members, i
     }
     hipStream_t st = (hipStream_t)stream;
     const int V = vec ? 4 : 1;
-    if ((n_vox / V + ENS_THREADS - 1) / ENS_THREADS > UINT_MAX) return fail_msg(FNN_E_UNSUPPORTED, "too many voxels");
+    if ((n_vox / V + ENS_THREADS - 1) / ENS_THREADS > UINT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "too many voxels");
     int *order = nullptr;
     hipError_t r = upload_order(regions_class_order, heads, st, &order);
     a.order = order;

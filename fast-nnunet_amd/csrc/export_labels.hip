@@ -30,17 +30,7 @@
 #include "resample_torch_common.h"
 #include <type_traits>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 constexpr int HEADS_IN_FLIGHT = 4;     // heads whose tap loads are issued before the first of them is blended
 
@@ -211,21 +201,21 @@ static void launch(int mask, const T *in, const G &g, int heads, const int *orde
 extern "C" int fnn_resample_labels(const void *logits, int dtype, const int64_t shape[4], const int64_t new_shape[3],
                                    int family, int separate_axis, const int32_t *regions_class_order, int n_regions,
                                    void *labels, int label_dtype, void *stream) {
-    if (!logits || !shape || !new_shape || !labels) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (family != FNN_RESAMPLE_DEFAULT && family != FNN_RESAMPLE_TORCH) return fail_msg(FNN_E_UNSUPPORTED, "unknown resampling family");
-    if (dtype != FNN_OUT_F16 && dtype != FNN_OUT_F32) return fail_msg(FNN_E_INVALID, "unknown dtype");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
-    if (separate_axis < -1 || separate_axis > 2) return fail_msg(FNN_E_INVALID, "separate_axis must be -1 .. 2");
-    if (shape[0] < 1) return fail_msg(FNN_E_INVALID, "heads must be at least 1");
-    for (int a = 1; a < 4; ++a) if (shape[a] < 1) return fail_msg(FNN_E_INVALID, "bad shape");
-    for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fail_msg(FNN_E_INVALID, "bad new_shape");
-    if (regions_class_order && n_regions != shape[0]) return fail_msg(FNN_E_INVALID, "regions_class_order needs one entry per head");
-    if (!regions_class_order && label_dtype == FNN_LABEL_U8 && shape[0] > 256) return fail_msg(FNN_E_INVALID, "more than 256 heads need uint16 labels");
-    if (!dev_ptr(logits) || !dev_ptr(labels) || (regions_class_order && !dev_ptr(regions_class_order)))
-        return fail_msg(FNN_E_INVALID, "fnn_resample_labels needs device pointers (no CPU path)");
+    if (!logits || !shape || !new_shape || !labels) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (family != FNN_RESAMPLE_DEFAULT && family != FNN_RESAMPLE_TORCH) return fnn_fail(FNN_E_UNSUPPORTED, "unknown resampling family");
+    if (dtype != FNN_OUT_F16 && dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown dtype");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (separate_axis < -1 || separate_axis > 2) return fnn_fail(FNN_E_INVALID, "separate_axis must be -1 .. 2");
+    if (shape[0] < 1) return fnn_fail(FNN_E_INVALID, "heads must be at least 1");
+    for (int a = 1; a < 4; ++a) if (shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad shape");
+    for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad new_shape");
+    if (regions_class_order && n_regions != shape[0]) return fnn_fail(FNN_E_INVALID, "regions_class_order needs one entry per head");
+    if (!regions_class_order && label_dtype == FNN_LABEL_U8 && shape[0] > 256) return fnn_fail(FNN_E_INVALID, "more than 256 heads need uint16 labels");
+    if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(labels) || (regions_class_order && !fnn_dev_ptr(regions_class_order)))
+        return fnn_fail(FNN_E_INVALID, "fnn_resample_labels needs device pointers (no CPU path)");
     RGeo rg{};                                                 // the grid rule and its limits are the torch family's for both
     const char *why = "";
-    if (int rc = rt_geometry(shape, new_shape, separate_axis, rg, &why)) return fail_msg(rc, why);
+    if (int rc = rt_geometry(shape, new_shape, separate_axis, rg, &why)) return fnn_fail(rc, why);
     int mask = 0;
     for (int a = 0; a < 3; ++a) if (shape[1 + a] != new_shape[a] && a != separate_axis) mask |= 1 << a;
     const int heads = (int)shape[0], u16 = label_dtype == FNN_LABEL_U16;
@@ -243,6 +233,6 @@ extern "C" int fnn_resample_labels(const void *logits, int dtype, const int64_t 
         else launch(mask, (const f16 *)logits, g, heads, order, labels, u16, st);
     }
     fnn_op_klog_end();
-    if (hipGetLastError() != hipSuccess) return fail_msg(FNN_E_HIP, "fnn_resample_labels: launch failed");
+    if (hipGetLastError() != hipSuccess) return fnn_fail(FNN_E_HIP, "fnn_resample_labels: launch failed");
     return FNN_OK;
 }

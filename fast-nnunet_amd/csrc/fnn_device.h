@@ -275,6 +275,14 @@ void fnn_note_kernel(const char *fmt, ...) __attribute__((format(printf, 1, 2)))
 void fnn_klog_target(void *vector_of_strings);          // where this thread's notes go (nullptr: nowhere)
 void fnn_op_klog_begin();                               // ops_api.hip: this thread's notes go to the log fnn_op_last_kernels reads ...
 void fnn_op_klog_end();                                 // ... until here
+struct FnnOpKlog {                                      // ... for a scope: a call that is refused leaves the log empty
+    FnnOpKlog() { fnn_op_klog_begin(); }
+    ~FnnOpKlog() { fnn_op_klog_end(); }
+};
+// What the entry points outside engine.hip share (engine.hip):
+void fnn_set_global_error(const char *msg);             // the message of an entry point that has no engine handle
+int fnn_fail(int code, const char *msg);                // sets that message -> code
+bool fnn_dev_ptr(const void *p);                        // device or managed memory?
 
 static __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
 

@@ -25,21 +25,11 @@
 
 #pragma clang fp contract(off)
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
 
 constexpr int DEC_THREADS = 256;
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 struct DecodeArgs {
     const void *raw;             // 16-byte aligned
@@ -149,17 +139,17 @@ template <typename T> static hipError_t launch_decode(DecodeArgs a, int *rc, hip
 
 extern "C" int fnn_decode_voxels(const void *raw, int nifti_datatype, int byteswap, int64_t n_vox, int scale, double slope,
                                  double inter, float *out, void *stream) {
-    if (!raw || !out) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (n_vox < 0) return fail_msg(FNN_E_INVALID, "negative n_vox");
-    if ((uintptr_t)raw % 16) return fail_msg(FNN_E_INVALID, "fnn_decode_voxels: raw must be 16-byte aligned");
-    if ((uintptr_t)out % 4) return fail_msg(FNN_E_INVALID, "fnn_decode_voxels: out must be 4-byte aligned");
+    if (!raw || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (n_vox < 0) return fnn_fail(FNN_E_INVALID, "negative n_vox");
+    if ((uintptr_t)raw % 16) return fnn_fail(FNN_E_INVALID, "fnn_decode_voxels: raw must be 16-byte aligned");
+    if ((uintptr_t)out % 4) return fnn_fail(FNN_E_INVALID, "fnn_decode_voxels: out must be 4-byte aligned");
     switch (nifti_datatype) {
     case 2: case 256: case 4: case 512: case 8: case 768: case 16: case 64: break;
-    default: return fail_msg(FNN_E_UNSUPPORTED, "fnn_decode_voxels: NIfTI datatype not served (uint8, int8, int16, uint16, int32, "
+    default: return fnn_fail(FNN_E_UNSUPPORTED, "fnn_decode_voxels: NIfTI datatype not served (uint8, int8, int16, uint16, int32, "
                                                 "uint32, float32 and float64 are)");
     }
     if (n_vox == 0) return FNN_OK;
-    if (!dev_ptr(raw) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "fnn_decode_voxels needs device pointers (no CPU path)");
+    if (!fnn_dev_ptr(raw) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_decode_voxels needs device pointers (no CPU path)");
     DecodeArgs a{};
     a.raw = raw; a.out = out; a.n_vox = n_vox;
     a.head = (int)(((16 - ((uintptr_t)out & 15)) & 15) / 4);
@@ -180,7 +170,7 @@ extern "C" int fnn_decode_voxels(const void *raw, int nifti_datatype, int bytesw
     case 16: r = launch_decode<float>(a, &rc, st); break;
     default: r = launch_decode<double>(a, &rc, st); break;
     }
-    if (rc != FNN_OK) return fail_msg(rc, "fnn_decode_voxels: too many voxels for one launch");
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (rc != FNN_OK) return fnn_fail(rc, "fnn_decode_voxels: too many voxels for one launch");
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }

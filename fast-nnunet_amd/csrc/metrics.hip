@@ -15,17 +15,7 @@
 #include "../../include/fnn.h"
 #include <climits>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 constexpr int CM_THREADS = 512;
 constexpr int CM_MAX_PRED = 4;
@@ -215,26 +205,26 @@ extern "C" {
 int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, int label_dtype, int64_t n_vox,
                          const int32_t *class_of_value, int n_table, int n_classes, int ignore_value, int64_t *counts,
                          void *stream) {
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
-    if (n_pred < 1 || n_pred > CM_MAX_PRED) return fail_msg(FNN_E_INVALID, "fnn_confusion_counts: n_pred must be 1..4");
-    if (n_classes < 0 || n_classes > CM_MAX_CLASSES) return fail_msg(FNN_E_INVALID, "fnn_confusion_counts: n_classes must be 0..255");
-    if (n_vox < 0) return fail_msg(FNN_E_INVALID, "negative voxel count");
-    if (n_table < 0 || (n_table > 0 && !class_of_value)) return fail_msg(FNN_E_INVALID, "bad class table");
-    if (!counts || !pred) return fail_msg(FNN_E_INVALID, "NULL pred or counts");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (n_pred < 1 || n_pred > CM_MAX_PRED) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: n_pred must be 1..4");
+    if (n_classes < 0 || n_classes > CM_MAX_CLASSES) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: n_classes must be 0..255");
+    if (n_vox < 0) return fnn_fail(FNN_E_INVALID, "negative voxel count");
+    if (n_table < 0 || (n_table > 0 && !class_of_value)) return fnn_fail(FNN_E_INVALID, "bad class table");
+    if (!counts || !pred) return fnn_fail(FNN_E_INVALID, "NULL pred or counts");
     for (int v = 0; v < n_table; ++v)
         if (class_of_value[v] < -1 || class_of_value[v] >= n_classes)
-            return fail_msg(FNN_E_INVALID, "class_of_value entry outside [-1, n_classes)");
+            return fnn_fail(FNN_E_INVALID, "class_of_value entry outside [-1, n_classes)");
     const int cols = n_classes + 1;
     const size_t n_counts = (size_t)n_pred * cols * cols;
     for (size_t k = 0; k < n_counts; ++k) counts[k] = 0;
     if (n_vox == 0) return FNN_OK;
     const size_t esize = label_dtype == FNN_LABEL_U16 ? 2 : 1;
     const int max_value = label_dtype == FNN_LABEL_U16 ? 65535 : 255;
-    if (!ref || !dev_ptr(ref)) return fail_msg(FNN_E_INVALID, "fnn_confusion_counts needs device label maps (no CPU path)");
-    if ((uintptr_t)ref & 15) return fail_msg(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
+    if (!ref || !fnn_dev_ptr(ref)) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts needs device label maps (no CPU path)");
+    if ((uintptr_t)ref & 15) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
     for (int p = 0; p < n_pred; ++p) {
-        if (!pred[p] || !dev_ptr(pred[p])) return fail_msg(FNN_E_INVALID, "fnn_confusion_counts needs device label maps (no CPU path)");
-        if ((uintptr_t)pred[p] & 15) return fail_msg(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
+        if (!pred[p] || !fnn_dev_ptr(pred[p])) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts needs device label maps (no CPU path)");
+        if ((uintptr_t)pred[p] & 15) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
     }
 
     // the table the kernel reads: values the dtype cannot hold dropped, trailing "other" entries trimmed
@@ -250,7 +240,7 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     int dev = 0, cus = 0;
     hipError_t r = hipGetDevice(&dev);
     if (r == hipSuccess) r = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (r != hipSuccess) { delete[] htab; (void)hipGetLastError(); return fail_msg(FNN_E_HIP, hipGetErrorString(r)); }
+    if (r != hipSuccess) { delete[] htab; (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, hipGetErrorString(r)); }
     const long long per_chunk_vox = (long long)(16 / esize);
     const long long n_chunks = n_vox / per_chunk_vox;
     long long blocks = (n_chunks + CM_THREADS - 1) / CM_THREADS;
@@ -259,7 +249,7 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     const long long need = (n_vox + CM_MAX_WG_VOX - 1) / CM_MAX_WG_VOX;
     if (blocks < need) blocks = need;
     if (blocks < 1) blocks = 1;
-    if (blocks > INT_MAX) { delete[] htab; return fail_msg(FNN_E_UNSUPPORTED, "fnn_confusion_counts: volume too large"); }
+    if (blocks > INT_MAX) { delete[] htab; return fnn_fail(FNN_E_UNSUPPORTED, "fnn_confusion_counts: volume too large"); }
 
     // scratch: counts [n_counts] u64 | counted u64 | table [n_tab] u8
     const size_t off_table = (n_counts + 1) * 8;
@@ -268,7 +258,7 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     if (hipMalloc((void **)&scratch, bytes) != hipSuccess) {
         delete[] htab;
         (void)hipGetLastError();
-        return fail_msg(FNN_E_HIP, "hipMalloc failed (confusion counts)");
+        return fnn_fail(FNN_E_HIP, "hipMalloc failed (confusion counts)");
     }
     unsigned long long *dcounts = (unsigned long long *)scratch;
     hipStream_t st = (hipStream_t)stream;
@@ -299,7 +289,7 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     (void)hipFree(scratch);
     delete[] htab;
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     // the ("other", "other") bin of every prediction: counted voxels minus every other bin
     const size_t oo = (size_t)n_classes * cols + n_classes;
     for (int p = 0; p < n_pred; ++p) {

@@ -130,11 +130,7 @@ bool acc_args_ok(const AccArgs &a, const int patch[3], int heads) {
 
 // kernel variants of the last fnn_op_* call of this thread (fnn_note_kernel at the launch sites): fnn_op_last_kernels
 static thread_local std::vector<std::string> g_op_kernels;
-struct OpKlog {
-    OpKlog() { g_op_kernels.clear(); fnn_klog_target(&g_op_kernels); }
-    ~OpKlog() { fnn_klog_target(nullptr); }
-};
-// the same log for a call of an entry point outside this file (fnn_resample_labels)
+// (FnnOpKlog, fnn_device.h, holds it for a scope - here and in the entry points outside this file)
 void fnn_op_klog_begin() { g_op_kernels.clear(); fnn_klog_target(&g_op_kernels); }
 void fnn_op_klog_end() { fnn_klog_target(nullptr); }
 
@@ -147,7 +143,7 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
                   float *y, double *stats_out) {
     if (!x || !w || !y || !dims || !k || !stride || n < 1 || cin < 1 || cout < 1) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
     const int nsrc = x2 ? 2 : 1;
     SrcHolder s1, s2;
@@ -273,7 +269,7 @@ int fnn_op_conv_transpose3d(int device, int n, const int dims[3],
                             const float *w, const float *bias, int cout, const int stride[3], float *y) {
     if (!x || !w || !y || !dims || !stride || n < 1 || cin < 1 || cout < 1) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
     SrcHolder s1;
     if (!make_src(s1, x, n, cin, vox, gamma1, beta1, slope1, true)) return FNN_E_HIP;
@@ -314,7 +310,7 @@ int fnn_op_avgpool(int device, int n, const int dims[3], const float *x, int c,
     if (!x || !y || !dims || !stride || n < 1 || c < 1) return FNN_E_INVALID;
     for (int i = 0; i < 3; ++i) if (stride[i] < 1 || dims[i] < stride[i]) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
     const int cp = pad16(c);
     SrcHolder s;
@@ -345,7 +341,7 @@ int fnn_op_combine(int device, int n, const int dims[3], int c,
     if (!a || !b || !y || !dims || n < 1 || c < 1 || (pool_stride && !pooled)) return FNN_E_INVALID;
     for (int i = 0; i < 3; ++i) if (dims[i] < 1) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
     const int cp = pad16(c);
     SrcHolder sa, sb;
@@ -396,7 +392,7 @@ int fnn_op_seg_head(int device, int n, int c, const int patch[3], const float *x
     const AccArgs aa{acc, acc_fp32, box, origin};
     if (mode == 0 ? !acc_args_ok(aa, patch, heads) : !patch_buf) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t P = (size_t)patch[0] * patch[1] * patch[2];
     const int cp = pad16(c);
     SrcHolder s;                                    // the head kernels read channels-last features
@@ -450,7 +446,7 @@ int fnn_op_patch_acc(int device, const float *patch_buf, int heads, const int pa
     const AccArgs aa{acc, acc_fp32, box, origin};
     if (!patch_buf || !patch || n_div < 1 || !acc_args_ok(aa, patch, heads)) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t P = (size_t)patch[0] * patch[1] * patch[2];
     PatchAccParams q{};
     q.n_div = n_div; q.PD = patch[0]; q.PH = patch[1]; q.PW = patch[2]; q.heads = heads;
@@ -476,7 +472,7 @@ int fnn_op_patch_input(int device, const float *vol, int n_vol, int c, const lon
         for (int i = 0; i < 3; ++i)
             if (patch[i] < 1 || origins[b * 3 + i] < 0 || (long long)origins[b * 3 + i] + patch[i] > vdim[i]) return FNN_E_INVALID;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    OpKlog klog;
+    FnnOpKlog klog;
     const size_t P = (size_t)patch[0] * patch[1] * patch[2];
     const size_t vvox = (size_t)vdim[0] * vdim[1] * vdim[2];
     PatchInputParams p{};

@@ -24,17 +24,7 @@
 #include "../../include/fnn.h"
 #include <climits>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 constexpr int CC_THREADS = 256;
 constexpr int CC_TILE = 1024;          // voxels per tile: 4 per thread
@@ -312,21 +302,21 @@ extern "C" {
 
 int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t shape[3], const int32_t *group_of_label, int n_table,
                                 int n_groups, int background_label, int64_t *removed, void *stream) {
-    if (!shape) return fail_msg(FNN_E_INVALID, "NULL shape");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
+    if (!shape) return fnn_fail(FNN_E_INVALID, "NULL shape");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
     const int max_label = label_dtype == FNN_LABEL_U16 ? 65535 : 255;
-    if (background_label < 0 || background_label > max_label) return fail_msg(FNN_E_INVALID, "background_label outside the label dtype");
-    if (shape[0] < 0 || shape[1] < 0 || shape[2] < 0) return fail_msg(FNN_E_INVALID, "negative shape");
-    if (n_groups < 0 || n_table < 0 || (n_table > 0 && !group_of_label)) return fail_msg(FNN_E_INVALID, "bad label-set table");
+    if (background_label < 0 || background_label > max_label) return fnn_fail(FNN_E_INVALID, "background_label outside the label dtype");
+    if (shape[0] < 0 || shape[1] < 0 || shape[2] < 0) return fnn_fail(FNN_E_INVALID, "negative shape");
+    if (n_groups < 0 || n_table < 0 || (n_table > 0 && !group_of_label)) return fnn_fail(FNN_E_INVALID, "bad label-set table");
     for (int v = 0; v < n_table; ++v)
-        if (group_of_label[v] < -1 || group_of_label[v] >= n_groups) return fail_msg(FNN_E_INVALID, "group_of_label entry outside [-1, n_groups)");
+        if (group_of_label[v] < -1 || group_of_label[v] >= n_groups) return fnn_fail(FNN_E_INVALID, "group_of_label entry outside [-1, n_groups)");
     if (removed)
         for (int k = 0; k < n_groups; ++k) removed[k] = 0;
     if (shape[0] == 0 || shape[1] == 0 || shape[2] == 0) return FNN_OK;
     if (shape[0] > INT_MAX || shape[1] > INT_MAX || shape[2] > INT_MAX || shape[0] * shape[1] > INT_MAX ||
         shape[0] * shape[1] * shape[2] > INT_MAX)
-        return fail_msg(FNN_E_UNSUPPORTED, "fnn_keep_largest_components: more than 2^31 - 1 voxels");
-    if (!labels || !dev_ptr(labels)) return fail_msg(FNN_E_INVALID, "fnn_keep_largest_components needs a device label map (no CPU path)");
+        return fnn_fail(FNN_E_UNSUPPORTED, "fnn_keep_largest_components: more than 2^31 - 1 voxels");
+    if (!labels || !fnn_dev_ptr(labels)) return fnn_fail(FNN_E_INVALID, "fnn_keep_largest_components needs a device label map (no CPU path)");
     const int n_tab = n_table < max_label + 1 ? n_table : max_label + 1;      // labels the dtype cannot hold are never looked up
     if (n_groups == 0 || n_tab == 0) return FNN_OK;                              // no set: nothing changes
     const int n = (int)(shape[0] * shape[1] * shape[2]);
@@ -346,7 +336,7 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
     const size_t off_removed = (off_gmax + (size_t)n_groups * 4 + 7) & ~(size_t)7;
     const size_t bytes = off_removed + (size_t)n_groups * 8;
     char *scratch = nullptr;
-    if (hipMalloc((void **)&scratch, bytes) != hipSuccess) { (void)hipGetLastError(); return fail_msg(FNN_E_HIP, "hipMalloc failed (8 B per voxel of scratch)"); }
+    if (hipMalloc((void **)&scratch, bytes) != hipSuccess) { (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, "hipMalloc failed (8 B per voxel of scratch)"); }
     int *parent = (int *)scratch, *size = (int *)(scratch + off_size), *table = (int *)(scratch + off_table);
     int *gmax = (int *)(scratch + off_gmax);
     unsigned long long *rem = (unsigned long long *)(scratch + off_removed);
@@ -370,7 +360,7 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
         for (int k = 0; k < n_groups; ++k) removed[k] = (int64_t)hrem[k];
     delete[] hrem;
     (void)hipFree(scratch);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }
 

@@ -16,7 +16,6 @@
 #include <cmath>
 
 extern "C" const char *fnn_last_error(const fnn_engine *e);
-void fnn_set_global_error(const char *msg);      // engine.hip
 
 namespace {
 
@@ -25,14 +24,6 @@ struct PrepGeom {
     int tf[3];                   // transposed axis a = raw axis tf[a]
     int C;
 };
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
 
 // ---- bounding box of the voxels where any channel is non-zero, in transposed coordinates
 __global__ __launch_bounds__(256) void bbox_kernel(const float *raw, PrepGeom g, int *box /* lo[3], hi[3] (inclusive) */) {
@@ -264,16 +255,16 @@ static int check_perm(const int32_t t[3]) {
 extern "C" {
 
 int fnn_nonzero_bbox(const float *raw, const int64_t shape[4], const int32_t transpose_forward[3], int64_t bbox[6], void *stream) {
-    if (!raw || !shape || !transpose_forward || !bbox) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_forward) != 0) return fail_msg(FNN_E_INVALID, "transpose_forward is not a permutation of (0, 1, 2)");
-    if (shape[0] < 1 || shape[0] > 8 || shape[1] < 1 || shape[2] < 1 || shape[3] < 1) return fail_msg(FNN_E_INVALID, "bad shape (1..8 channels)");
-    if (!dev_ptr(raw)) return fail_msg(FNN_E_INVALID, "fnn_nonzero_bbox needs a device pointer (no CPU path)");
+    if (!raw || !shape || !transpose_forward || !bbox) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (check_perm(transpose_forward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_forward is not a permutation of (0, 1, 2)");
+    if (shape[0] < 1 || shape[0] > 8 || shape[1] < 1 || shape[2] < 1 || shape[3] < 1) return fnn_fail(FNN_E_INVALID, "bad shape (1..8 channels)");
+    if (!fnn_dev_ptr(raw)) return fnn_fail(FNN_E_INVALID, "fnn_nonzero_bbox needs a device pointer (no CPU path)");
     hipStream_t st = (hipStream_t)stream;
     PrepGeom g{};
     for (int d = 0; d < 3; ++d) { g.s[d] = shape[1 + d]; g.tf[d] = transpose_forward[d]; }
     g.C = (int)shape[0];
     int *box = nullptr;
-    if (hipMalloc((void **)&box, 6 * sizeof(int)) != hipSuccess) return fail_msg(FNN_E_HIP, "hipMalloc failed");
+    if (hipMalloc((void **)&box, 6 * sizeof(int)) != hipSuccess) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
     const int init[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
     int h[6];
     hipError_t r = hipMemcpyAsync(box, init, sizeof(init), hipMemcpyHostToDevice, st);
@@ -284,7 +275,7 @@ int fnn_nonzero_bbox(const float *raw, const int64_t shape[4], const int32_t tra
     if (r == hipSuccess) r = hipMemcpyAsync(h, box, sizeof(h), hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     (void)hipFree(box);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     for (int a = 0; a < 3; ++a) {
         if (h[3 + a] < 0) { bbox[2 * a] = 0; bbox[2 * a + 1] = shape[1 + transpose_forward[a]]; }   // empty mask: the full extent
         else { bbox[2 * a] = h[a]; bbox[2 * a + 1] = h[3 + a] + 1; }
@@ -294,21 +285,21 @@ int fnn_nonzero_bbox(const float *raw, const int64_t shape[4], const int32_t tra
 
 int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t transpose_forward[3], const int64_t bbox[6],
                    const fnn_norm_desc *norm, float *out, void *stream) {
-    if (!raw || !shape || !transpose_forward || !bbox || !norm || !out) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_forward) != 0) return fail_msg(FNN_E_INVALID, "transpose_forward is not a permutation of (0, 1, 2)");
-    if (shape[0] < 1 || shape[0] > 8) return fail_msg(FNN_E_INVALID, "1..8 channels");
-    if (!dev_ptr(raw) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "fnn_preprocess needs device pointers (no CPU path)");
+    if (!raw || !shape || !transpose_forward || !bbox || !norm || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (check_perm(transpose_forward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_forward is not a permutation of (0, 1, 2)");
+    if (shape[0] < 1 || shape[0] > 8) return fnn_fail(FNN_E_INVALID, "1..8 channels");
+    if (!fnn_dev_ptr(raw) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_preprocess needs device pointers (no CPU path)");
     hipStream_t st = (hipStream_t)stream;
     PrepParams p{};
     for (int d = 0; d < 3; ++d) { p.g.s[d] = shape[1 + d]; p.g.tf[d] = transpose_forward[d]; }
     p.g.C = (int)shape[0];
     for (int a = 0; a < 3; ++a) {
         p.lo[a] = bbox[2 * a]; p.ext[a] = bbox[2 * a + 1] - bbox[2 * a];
-        if (p.lo[a] < 0 || p.ext[a] < 1 || bbox[2 * a + 1] > shape[1 + transpose_forward[a]]) return fail_msg(FNN_E_INVALID, "bbox outside the (transposed) image");
+        if (p.lo[a] < 0 || p.ext[a] < 1 || bbox[2 * a + 1] > shape[1 + transpose_forward[a]]) return fnn_fail(FNN_E_INVALID, "bbox outside the (transposed) image");
     }
     const long long n = p.ext[0] * p.ext[1] * p.ext[2];
     double *sums = nullptr;
-    if (hipMalloc((void **)&sums, 8 * 5 * sizeof(double)) != hipSuccess) return fail_msg(FNN_E_HIP, "hipMalloc failed");
+    if (hipMalloc((void **)&sums, 8 * 5 * sizeof(double)) != hipSuccess) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
     hipError_t r = hipSuccess;
     bool want_mask = false;
     for (int c = 0; c < p.g.C; ++c) {
@@ -321,7 +312,7 @@ int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t trans
         int *changed = nullptr;
         if (hipMalloc((void **)&mask, (size_t)n) != hipSuccess || hipMalloc((void **)&changed, sizeof(int)) != hipSuccess) {
             (void)hipFree(sums); (void)hipFree(mask);
-            return fail_msg(FNN_E_HIP, "hipMalloc failed");
+            return fnn_fail(FNN_E_HIP, "hipMalloc failed");
         }
         hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, raw, p, mask);
         for (int iter = 0; iter < 4096 && r == hipSuccess; ++iter) {
@@ -376,7 +367,7 @@ int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t trans
             }
         } else if (d.scheme != FNN_NORM_NONE && d.scheme != FNN_NORM_RGB01) {
             (void)hipFree(sums); (void)hipFree(mask);
-            return fail_msg(FNN_E_UNSUPPORTED, "unknown normalisation scheme");
+            return fnn_fail(FNN_E_UNSUPPORTED, "unknown normalisation scheme");
         }
     }
     if (r == hipSuccess) {
@@ -387,20 +378,20 @@ int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t trans
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     (void)hipFree(sums);
     (void)hipFree(mask);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }
 
 int fnn_revert_labels(const void *seg, int label_dtype, const int64_t bbox[6], const int64_t shape_before_cropping[3],
                       const int32_t transpose_backward[3], void *out, void *stream) {
-    if (!seg || !bbox || !shape_before_cropping || !transpose_backward || !out) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_backward) != 0) return fail_msg(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
-    if (!dev_ptr(seg) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "fnn_revert_labels needs device pointers (no CPU path)");
+    if (!seg || !bbox || !shape_before_cropping || !transpose_backward || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (check_perm(transpose_backward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (!fnn_dev_ptr(seg) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_revert_labels needs device pointers (no CPU path)");
     long long lo[3], ext[3], o[3];
     for (int a = 0; a < 3; ++a) {
         lo[a] = bbox[2 * a]; ext[a] = bbox[2 * a + 1] - bbox[2 * a];
-        if (lo[a] < 0 || ext[a] < 1 || bbox[2 * a + 1] > shape_before_cropping[a]) return fail_msg(FNN_E_INVALID, "bbox outside shape_before_cropping");
+        if (lo[a] < 0 || ext[a] < 1 || bbox[2 * a + 1] > shape_before_cropping[a]) return fnn_fail(FNN_E_INVALID, "bbox outside shape_before_cropping");
     }
     for (int j = 0; j < 3; ++j) o[j] = shape_before_cropping[transpose_backward[j]];
     const long long n = o[0] * o[1] * o[2];
@@ -414,23 +405,23 @@ int fnn_revert_labels(const void *seg, int label_dtype, const int64_t bbox[6], c
                            o[0], o[1], o[2], transpose_backward[0], transpose_backward[1], transpose_backward[2], (uint8_t *)out);
     hipError_t r = hipGetLastError();
     if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }
 
 int fnn_export_probabilities(const void *logits, int logits_dtype, int heads, const int32_t *regions_class_order,
                              const int64_t bbox[6], const int64_t shape_before_cropping[3],
                              const int32_t transpose_backward[3], float *probs, void *labels, int label_dtype, void *stream) {
-    if (!logits || !bbox || !shape_before_cropping || !transpose_backward || !probs || !labels) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_backward) != 0) return fail_msg(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fail_msg(FNN_E_INVALID, "unknown label dtype");
-    if (logits_dtype != FNN_OUT_F16 && logits_dtype != FNN_OUT_F32) return fail_msg(FNN_E_INVALID, "unknown logits dtype");
-    if (heads < 1 || heads > 4096) return fail_msg(FNN_E_INVALID, "bad number of heads");
-    if (!dev_ptr(logits) || !dev_ptr(probs) || !dev_ptr(labels)) return fail_msg(FNN_E_INVALID, "fnn_export_probabilities needs device pointers (no CPU path)");
+    if (!logits || !bbox || !shape_before_cropping || !transpose_backward || !probs || !labels) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (check_perm(transpose_backward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
+    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (logits_dtype != FNN_OUT_F16 && logits_dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown logits dtype");
+    if (heads < 1 || heads > 4096) return fnn_fail(FNN_E_INVALID, "bad number of heads");
+    if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(probs) || !fnn_dev_ptr(labels)) return fnn_fail(FNN_E_INVALID, "fnn_export_probabilities needs device pointers (no CPU path)");
     long long lo[3], ext[3], o[3];
     for (int a = 0; a < 3; ++a) {
         lo[a] = bbox[2 * a]; ext[a] = bbox[2 * a + 1] - bbox[2 * a];
-        if (lo[a] < 0 || ext[a] < 1 || bbox[2 * a + 1] > shape_before_cropping[a]) return fail_msg(FNN_E_INVALID, "bbox outside shape_before_cropping");
+        if (lo[a] < 0 || ext[a] < 1 || bbox[2 * a + 1] > shape_before_cropping[a]) return fnn_fail(FNN_E_INVALID, "bbox outside shape_before_cropping");
     }
     for (int j = 0; j < 3; ++j) o[j] = shape_before_cropping[transpose_backward[j]];
     const long long n = o[0] * o[1] * o[2];
@@ -438,7 +429,7 @@ int fnn_export_probabilities(const void *logits, int logits_dtype, int heads, co
     int *order = nullptr;
     hipError_t r = hipSuccess;
     if (regions_class_order) {
-        if (hipMalloc((void **)&order, heads * sizeof(int)) != hipSuccess) return fail_msg(FNN_E_HIP, "hipMalloc failed");
+        if (hipMalloc((void **)&order, heads * sizeof(int)) != hipSuccess) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
         r = hipMemcpyAsync(order, regions_class_order, heads * sizeof(int), hipMemcpyHostToDevice, st);
     }
     const dim3 grid((unsigned)((n + 255) / 256));
@@ -457,7 +448,7 @@ int fnn_export_probabilities(const void *logits, int logits_dtype, int heads, co
 #undef FNN_EXPORT_LAUNCH
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     if (order) (void)hipFree(order);
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }
 

@@ -33,22 +33,12 @@
 #include <climits>
 #include <cstdint>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
 
 constexpr int RO_THREADS = 256;
 constexpr int RO_TILE = 64;
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 template <int SZ> struct elem_of;
 template <> struct elem_of<1> { typedef uint8_t type; };
@@ -237,26 +227,26 @@ template <int SZ> static hipError_t launch_reorient(const ReorientArgs &a, bool 
 
 extern "C" int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_in[3], const int32_t src_axis[3],
                             const int32_t flip[3], void *out, void *stream) {
-    if (!in || !out || !shape_in || !src_axis || !flip) return fail_msg(FNN_E_INVALID, "NULL argument");
+    if (!in || !out || !shape_in || !src_axis || !flip) return fnn_fail(FNN_E_INVALID, "NULL argument");
     if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
-        return fail_msg(FNN_E_UNSUPPORTED, "fnn_reorient: elements of 1, 2 or 4 bytes are served");
+        return fnn_fail(FNN_E_UNSUPPORTED, "fnn_reorient: elements of 1, 2 or 4 bytes are served");
     int seen = 0;
     for (int d = 0; d < 3; ++d) {
-        if (src_axis[d] < 0 || src_axis[d] > 2) return fail_msg(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
+        if (src_axis[d] < 0 || src_axis[d] > 2) return fnn_fail(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
         seen |= 1 << src_axis[d];
     }
-    if (seen != 7) return fail_msg(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
+    if (seen != 7) return fnn_fail(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
     long long n = 1;
     for (int d = 0; d < 3; ++d) {
-        if (shape_in[d] < 0) return fail_msg(FNN_E_INVALID, "fnn_reorient: negative extent");
+        if (shape_in[d] < 0) return fnn_fail(FNN_E_INVALID, "fnn_reorient: negative extent");
         if (__builtin_mul_overflow(n, (long long)shape_in[d], &n) || n > (LLONG_MAX >> 4))
-            return fail_msg(FNN_E_UNSUPPORTED, "fnn_reorient: too many elements for one launch");
+            return fnn_fail(FNN_E_UNSUPPORTED, "fnn_reorient: too many elements for one launch");
     }
     if ((uintptr_t)in % elem_bytes || (uintptr_t)out % elem_bytes)
-        return fail_msg(FNN_E_INVALID, "fnn_reorient: in and out must be aligned to the element size");
+        return fnn_fail(FNN_E_INVALID, "fnn_reorient: in and out must be aligned to the element size");
     if (n == 0) return FNN_OK;
     const uintptr_t bytes = (uintptr_t)n * elem_bytes, ia = (uintptr_t)in, oa = (uintptr_t)out;
-    if (ia < oa + bytes && oa < ia + bytes) return fail_msg(FNN_E_INVALID, "fnn_reorient: in and out overlap");
+    if (ia < oa + bytes && oa < ia + bytes) return fnn_fail(FNN_E_INVALID, "fnn_reorient: in and out overlap");
 
     const long long in_stride[3] = {(long long)shape_in[1] * shape_in[2], (long long)shape_in[2], 1};
     long long o[3], st[3], base = 0;
@@ -288,8 +278,8 @@ extern "C" int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_
         const long long outer = o[1 - a.q];
         blocks = a.tq * a.t2 > INT_MAX / outer ? (long long)INT_MAX + 1 : a.tq * a.t2 * outer;
     }
-    if (blocks > INT_MAX) return fail_msg(FNN_E_UNSUPPORTED, "fnn_reorient: too many elements for one launch");
-    if (!dev_ptr(in) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "fnn_reorient needs device pointers (no CPU path)");
+    if (blocks > INT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "fnn_reorient: too many elements for one launch");
+    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_reorient needs device pointers (no CPU path)");
     hipStream_t s = (hipStream_t)stream;
     hipError_t r;
     switch (elem_bytes) {
@@ -297,6 +287,6 @@ extern "C" int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_
     case 2: r = launch_reorient<2>(a, rows, blocks, s); break;
     default: r = launch_reorient<4>(a, rows, blocks, s); break;
     }
-    if (r != hipSuccess) return fail_msg(FNN_E_HIP, hipGetErrorString(r));
+    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     return FNN_OK;
 }

@@ -17,20 +17,10 @@
 #include <cfloat>
 #include <cmath>
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
 
 constexpr int NPAD = 12;       // scipy _prepad_for_spline_filter, mode 'nearest'
 constexpr int KT = 30;         // FIR half length
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 struct Geo {
     long long in[3], out[3];   // spatial sizes
@@ -226,16 +216,16 @@ static int run(const T *in, const int64_t shape[4], const int64_t new_shape[3], 
 
 extern "C" int fnn_resample(const void *in, const int64_t shape[4], const int64_t new_shape[3], const fnn_resample_desc *d,
                             void *out, void *stream) {
-    if (!in || !shape || !new_shape || !d || !out) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (d->order != 0 && d->order != 1 && d->order != 3) return fail_msg(FNN_E_UNSUPPORTED, "interpolation order must be 0, 1 or 3");
-    if (d->separate_axis < -1 || d->separate_axis > 2) return fail_msg(FNN_E_INVALID, "separate_axis must be -1 .. 2");
-    if (d->separate_axis >= 0 && d->order_z != 0) return fail_msg(FNN_E_UNSUPPORTED, "order_z other than 0 is not implemented");
-    if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fail_msg(FNN_E_INVALID, "unknown dtype");
-    for (int a = 0; a < 4; ++a) if (shape[a] < 1) return fail_msg(FNN_E_INVALID, "bad shape");
-    for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fail_msg(FNN_E_INVALID, "bad new_shape");
-    if (!dev_ptr(in) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "fnn_resample needs device pointers (no CPU path)");
+    if (!in || !shape || !new_shape || !d || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (d->order != 0 && d->order != 1 && d->order != 3) return fnn_fail(FNN_E_UNSUPPORTED, "interpolation order must be 0, 1 or 3");
+    if (d->separate_axis < -1 || d->separate_axis > 2) return fnn_fail(FNN_E_INVALID, "separate_axis must be -1 .. 2");
+    if (d->separate_axis >= 0 && d->order_z != 0) return fnn_fail(FNN_E_UNSUPPORTED, "order_z other than 0 is not implemented");
+    if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown dtype");
+    for (int a = 0; a < 4; ++a) if (shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad shape");
+    for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad new_shape");
+    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_resample needs device pointers (no CPU path)");
     const int rc = d->dtype == FNN_OUT_F32 ? run<float>((const float *)in, shape, new_shape, *d, (float *)out, (hipStream_t)stream)
                                            : run<f16>((const f16 *)in, shape, new_shape, *d, (f16 *)out, (hipStream_t)stream);
-    if (rc != 0) return fail_msg(FNN_E_HIP, "resample kernels failed");
+    if (rc != 0) return fnn_fail(FNN_E_HIP, "resample kernels failed");
     return FNN_OK;
 }

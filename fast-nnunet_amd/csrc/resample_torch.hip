@@ -25,17 +25,7 @@
 // memefficient_seg_resampling=True is the other rule: the float32 score of (seg == u) above 0.5 takes the label, else 0.
 #include "resample_torch_common.h"
 
-void fnn_set_global_error(const char *msg);      // engine.hip
-
 namespace {
-
-static int fail_msg(int code, const char *msg) { fnn_set_global_error(msg); return code; }
-
-static bool dev_ptr(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void rt_image_kernel(const T *__restrict__ in, RGeo g, int C, T *__restrict__ out) {
@@ -155,13 +145,13 @@ __global__ __launch_bounds__(256) void rt_seg_kernel(const short *__restrict__ i
 
 static int check_args(const void *in, const int64_t *shape, const int64_t *new_shape, const fnn_resample_torch_desc *d,
                       const void *out) {
-    if (!in || !shape || !new_shape || !d || !out) return fail_msg(FNN_E_INVALID, "NULL argument");
-    if (d->mode != FNN_INTERP_LINEAR) return fail_msg(FNN_E_UNSUPPORTED, "mode other than 'linear' is not implemented");
-    if (d->aniso_axis_mode != FNN_INTERP_NEAREST_EXACT) return fail_msg(FNN_E_UNSUPPORTED, "aniso_axis_mode other than 'nearest-exact' is not implemented");
-    if (d->separate_axis < -1 || d->separate_axis > 2) return fail_msg(FNN_E_INVALID, "separate_axis must be -1 .. 2");
-    for (int a = 0; a < 4; ++a) if (shape[a] < 1) return fail_msg(FNN_E_INVALID, "bad shape");
-    for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fail_msg(FNN_E_INVALID, "bad new_shape");
-    if (!dev_ptr(in) || !dev_ptr(out)) return fail_msg(FNN_E_INVALID, "the torch resampling kernels need device pointers (no CPU path)");
+    if (!in || !shape || !new_shape || !d || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
+    if (d->mode != FNN_INTERP_LINEAR) return fnn_fail(FNN_E_UNSUPPORTED, "mode other than 'linear' is not implemented");
+    if (d->aniso_axis_mode != FNN_INTERP_NEAREST_EXACT) return fnn_fail(FNN_E_UNSUPPORTED, "aniso_axis_mode other than 'nearest-exact' is not implemented");
+    if (d->separate_axis < -1 || d->separate_axis > 2) return fnn_fail(FNN_E_INVALID, "separate_axis must be -1 .. 2");
+    for (int a = 0; a < 4; ++a) if (shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad shape");
+    for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad new_shape");
+    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "the torch resampling kernels need device pointers (no CPU path)");
     return FNN_OK;
 }
 
@@ -171,14 +161,14 @@ extern "C" int fnn_resample_torch(const void *in, const int64_t shape[4], const 
                                   const fnn_resample_torch_desc *d, void *out, void *stream) {
     int rc = check_args(in, shape, new_shape, d, out);
     if (rc != FNN_OK) return rc;
-    if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fail_msg(FNN_E_INVALID, "unknown dtype");
+    if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown dtype");
     RGeo g{};
     const char *why = "";
-    if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fail_msg(rc, why);
+    if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fnn_fail(rc, why);
     hipStream_t st = (hipStream_t)stream;
     if (d->dtype == FNN_OUT_F32) launch_image((const float *)in, g, (int)shape[0], (float *)out, st);
     else launch_image((const f16 *)in, g, (int)shape[0], (f16 *)out, st);
-    if (hipGetLastError() != hipSuccess) return fail_msg(FNN_E_HIP, "fnn_resample_torch: launch failed");
+    if (hipGetLastError() != hipSuccess) return fnn_fail(FNN_E_HIP, "fnn_resample_torch: launch failed");
     return FNN_OK;
 }
 
@@ -188,11 +178,11 @@ extern "C" int fnn_resample_torch_seg(const int16_t *in, const int64_t shape[4],
     if (rc != FNN_OK) return rc;
     RGeo g{};
     const char *why = "";
-    if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fail_msg(rc, why);
+    if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fnn_fail(rc, why);
     const dim3 grid(g.plane_blocks * (unsigned)g.out[0]), block(256);
     hipStream_t st = (hipStream_t)stream;
     if (d->memefficient) hipLaunchKernelGGL(rt_seg_kernel<true>, grid, block, 0, st, (const short *)in, g, (int)shape[0], (short *)out);
     else hipLaunchKernelGGL(rt_seg_kernel<false>, grid, block, 0, st, (const short *)in, g, (int)shape[0], (short *)out);
-    if (hipGetLastError() != hipSuccess) return fail_msg(FNN_E_HIP, "fnn_resample_torch_seg: launch failed");
+    if (hipGetLastError() != hipSuccess) return fnn_fail(FNN_E_HIP, "fnn_resample_torch_seg: launch failed");
     return FNN_OK;
 }
