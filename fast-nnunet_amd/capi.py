@@ -72,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -137,6 +137,7 @@ def load_library() -> C.CDLL:
     lib.fnn_confusion_counts.argtypes = [vp, C.POINTER(vp), i32, i32, i64, C.POINTER(C.c_int32), i32, i32, i32,
                                          C.POINTER(i64), vp]
     lib.fnn_decode_voxels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
+    lib.fnn_decode_labels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, i32, vp, vp, vp]
     lib.fnn_reorient.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     lib.fnn_deflate_bound.argtypes = [i64]
     lib.fnn_deflate_bound.restype = i64
@@ -340,6 +341,20 @@ def decode_voxels(raw_ptr: int, nifti_datatype: int, byteswap: bool, n_vox: int,
     lib = load_library()
     check(lib.fnn_decode_voxels(raw_ptr, int(nifti_datatype), int(bool(byteswap)), int(n_vox), int(bool(scale)),
                                 float(slope), float(inter), out_ptr, stream), lib)
+
+
+LABEL_FLAG_NOT_INTEGRAL, LABEL_FLAG_NEGATIVE, LABEL_FLAG_TOO_LARGE = 1, 2, 4
+
+
+def decode_labels(raw_ptr: int, nifti_datatype: int, byteswap: bool, n_vox: int, scale: bool, slope: float, inter: float,
+                  out_bytes: int, out_ptr: int, status_ptr: int, stream: int = 0):
+    """fnn_decode_labels: n_vox voxels of a NIfTI datatype at raw_ptr (device, 16-byte aligned) -> uint8 (out_bytes 1) or
+    uint16 (2) labels at out_ptr (device, element aligned); what is no label stores 0.  status_ptr: two int32 on the
+    device - the LABEL_FLAG_* of all voxels OR-ed, the largest valid label - zeroed and written on `stream`,
+    asynchronously."""
+    lib = load_library()
+    check(lib.fnn_decode_labels(raw_ptr, int(nifti_datatype), int(bool(byteswap)), int(n_vox), int(bool(scale)),
+                                float(slope), float(inter), int(out_bytes), out_ptr, status_ptr, stream), lib)
 
 
 def reorient(in_ptr: int, elem_bytes: int, shape_in, src_axis, flip, out_ptr: int, stream: int = 0):

@@ -9,11 +9,16 @@ Mirrors the inference-time half of the reference's ``nnunetv2.ensembling.ensembl
   preprocesses the raw case and runs its own sliding window, and one ``fnn_ensemble_export`` call turns all members'
   resampled logits into the averaged probabilities and the label map, without the ``.npz`` round trip.
 
-Image and file export (``ensemble_folders``, ``merge_files`` with output names) stay the caller's side.
+``merge_files`` and ``ensemble_folders`` (ensemble.py:31-110) are the reference's folder commands on top of it: the members'
+``.npz`` files are averaged on the device and the label file goes through the writer, one case at a time behind a reader
+and a writer thread.  File output on ``nnUNetEnsemblePredictor`` stays out.
 """
 from __future__ import annotations
 
+import io
 import os
+import pickle
+import shutil
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -185,3 +190,147 @@ class nnUNetEnsemblePredictor(object):
         if save_or_return_probabilities:
             return out, avg.cpu().numpy()
         return out
+
+
+# ---- folders -----------------------------------------------------------------------------------------------------------
+class _PropertiesUnpickler(pickle.Unpickler):
+    """Reads the properties ``.pkl`` next to a member's ``.npz`` without running what it names: numpy arrays and scalars of
+    plain numeric dtypes and builtin containers are rebuilt, every other global is refused."""
+    _MULTIARRAY = ('numpy.core.multiarray', 'numpy._core.multiarray')
+    _BUILTINS = {'set': set, 'frozenset': frozenset, 'slice': slice, 'complex': complex, 'bytearray': bytearray, 'range': range}
+
+    def find_class(self, module, name):
+        if (module, name) == ('numpy', 'ndarray'):
+            return np.ndarray
+        if (module, name) == ('numpy', 'dtype'):
+            return _plain_dtype
+        if module in self._MULTIARRAY and name == '_reconstruct':
+            return _reconstruct_array
+        if module in self._MULTIARRAY and name == 'scalar':
+            return _plain_scalar
+        if module == 'builtins' and name in self._BUILTINS:
+            return self._BUILTINS[name]
+        if (module, name) == ('collections', 'OrderedDict'):
+            import collections
+            return collections.OrderedDict
+        raise pickle.UnpicklingError(f'the properties pickle names a global that is not allowed: {module}.{name}')
+
+
+def _plain_dtype(*args, **kwargs):
+    dt = np.dtype(*args, **kwargs)
+    if dt.hasobject or dt.kind not in 'biufc':
+        raise pickle.UnpicklingError(f'numpy dtype {dt} is not allowed in a properties pickle')
+    return dt
+
+
+def _reconstruct_array(cls, shape, typecode):
+    if cls is not np.ndarray:
+        raise pickle.UnpicklingError('only plain numpy arrays are allowed in a properties pickle')
+    return np.ndarray.__new__(np.ndarray, shape, typecode)
+
+
+def _plain_scalar(dtype, data=None):
+    dtype = np.dtype(dtype)
+    if dtype.kind not in 'biuf' or data is None:
+        raise pickle.UnpicklingError(f'numpy scalar of dtype {dtype} is not allowed in a properties pickle')
+    return np.frombuffer(data, dtype=dtype, count=1)[0]
+
+
+def load_properties_pkl(path_or_bytes) -> dict:
+    """The properties a prediction was exported with (``<case>.pkl`` next to ``<case>.npz``), loaded without pickle's
+    freedom to import and call."""
+    if isinstance(path_or_bytes, (bytes, bytearray)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, 'rb') as f:
+            data = f.read()
+    return _PropertiesUnpickler(io.BytesIO(data)).load()
+
+
+def _write_merged(image_reader_writer, seg, avg, properties, output_filename_truncated: str, output_file_ending: str):
+    """Host only: the merged case's files, each under its name only when it is complete."""
+    made = []
+    try:
+        if avg is not None:
+            for ending, dump in (('.npz', lambda f: np.savez_compressed(f, probabilities=avg)),
+                                 ('.pkl', lambda f: pickle.dump(properties, f))):
+                tmp = f'{output_filename_truncated}{ending}.part{os.getpid()}'
+                made.append(tmp)
+                with open(tmp, 'wb') as f:
+                    dump(f)
+                os.replace(tmp, output_filename_truncated + ending)
+        image_reader_writer.write_seg(seg, output_filename_truncated + output_file_ending, properties)
+    finally:
+        for tmp in made:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+
+def _merge_on_device(members, properties, image_reader_writer, label_manager, save_probabilities: bool):
+    """The GPU part of ``merge_files`` -> (what the writer takes as the label map, the average on the host or None)."""
+    from .label_folders import labels_for_writer
+    order, u16 = _label_rule(label_manager)
+    avg, labels = _average_on_device(members, order, u16, save_probabilities, None)
+    if labels.ndim != 3:
+        raise ValueError(f'probabilities of shape {tuple(avg.shape) if avg is not None else labels.shape}: the label file needs (c, z, y, x)')
+    return labels_for_writer(image_reader_writer, labels, properties), None if avg is None else avg.cpu().numpy()
+
+
+@torch.inference_mode()
+def merge_files(list_of_files: Sequence[str], output_filename_truncated: str, output_file_ending: str, image_reader_writer,
+                label_manager, save_probabilities: bool = False):
+    """``merge_files`` (ensemble.py:31-45): the properties of the first member's ``.pkl``, the members' ``.npz`` averaged and
+    turned into labels on the device, the label file through the writer.  With ``save_probabilities`` the average goes to
+    ``.npz`` and the *properties* to ``.pkl`` (the reference pickles the probability array there, which no reader of that
+    pair expects)."""
+    list_of_files = [str(f) for f in list_of_files]
+    properties = load_properties_pkl(list_of_files[0][:-4] + '.pkl')
+    seg, avg = _merge_on_device(list_of_files, properties, image_reader_writer, label_manager, save_probabilities)
+    _write_merged(image_reader_writer, seg, avg, properties, output_filename_truncated, output_file_ending)
+
+
+@torch.inference_mode()
+def ensemble_folders(list_of_input_folders: List[str], output_folder: str, save_merged_probabilities: bool = False,
+                     num_processes: int = 8, dataset_json_file_or_dict=None, plans_json_file_or_dict=None):
+    """``ensemble_folders`` (ensemble.py:48-110).  If plans and dataset json are not specified, those of the first folder are
+    taken.  The members are the folders' ``.npz`` files and every folder must hold the same set.  A reader thread loads the
+    next case's members and a writer thread writes the previous case's files while the calling thread averages this one on
+    the device; ``num_processes`` is accepted and ignored."""
+    from .imageio import prediction_reader_writer_class
+    from .label_folders import load_json, run_pipeline, subfiles
+    from .plans import PlansManager
+    if dataset_json_file_or_dict is not None:
+        dataset_json = load_json(dataset_json_file_or_dict) if isinstance(dataset_json_file_or_dict, str) else dataset_json_file_or_dict
+    else:
+        dataset_json = load_json(os.path.join(list_of_input_folders[0], 'dataset.json'))
+    if plans_json_file_or_dict is not None:
+        plans = load_json(plans_json_file_or_dict) if isinstance(plans_json_file_or_dict, str) else plans_json_file_or_dict
+    else:
+        plans = load_json(os.path.join(list_of_input_folders[0], 'plans.json'))
+    plans_manager = PlansManager(plans)
+    files_per_folder = [set(subfiles(i, suffix='.npz', join=False)) for i in list_of_input_folders]
+    s = set(files_per_folder[0])
+    for f in files_per_folder[1:]:
+        s.update(f)
+    for f in files_per_folder:
+        assert len(s.difference(f)) == 0, 'Not all folders contain the same files for ensembling. Please only ' \
+                                          'provide folders that contain the predictions'
+    names = sorted(s)
+    lists_of_lists_of_files = [[os.path.join(fl, fi) for fl in list_of_input_folders] for fi in names]
+    output_files_truncated = [os.path.join(output_folder, fi[:-4]) for fi in names]
+    rw = prediction_reader_writer_class(plans_manager, dataset_json)()
+    label_manager = plans_manager.get_label_manager(dataset_json)
+    os.makedirs(output_folder, exist_ok=True)
+    shutil.copy(os.path.join(list_of_input_folders[0], 'dataset.json'), output_folder)
+    ending = dataset_json['file_ending']
+
+    def stage(i):
+        files = lists_of_lists_of_files[i]
+        return lambda: ([_load_member(f) for f in files], load_properties_pkl(files[0][:-4] + '.pkl'))
+
+    def run(i, data):
+        members, properties = data
+        seg, avg = _merge_on_device(members, properties, rw, label_manager, save_merged_probabilities)
+        return None, (lambda: _write_merged(rw, seg, avg, properties, output_files_truncated[i], ending))
+
+    run_pipeline(len(names), stage, run, write_thread=True)

@@ -4,6 +4,10 @@ Replaces ``nnunetv2.evaluation.evaluate_predictions`` (evaluation/evaluate_predi
 reader-writer: ``compute_metrics`` (:88-118) and the aggregation of ``compute_metrics_on_folder`` (:149-175) take numpy
 arrays or torch tensors, and ``save_summary_json`` / ``load_summary_json`` (:33-60) keep the reference's file format.
 
+``compute_metrics_on_folder`` / ``compute_metrics_on_folder2`` / ``compute_metrics_on_folder_simple`` (:121-212) are the
+reference's folder commands on top of it: the label files are read as labels on the device (``NiftiIO.read_label_map``'s
+kernel), one case at a time behind a reader thread.
+
 Two halves:
 
 * device - ``confusion_counts``: one ``fnn_confusion_counts`` pass (csrc/metrics.hip) turns a reference map and 1..4
@@ -18,6 +22,7 @@ from __future__ import annotations
 import copy
 import json
 import math
+import os
 from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -298,3 +303,91 @@ def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions
     if output_file is not None:
         save_summary_json(summary, output_file)
     return summary
+
+
+# ---- folders -----------------------------------------------------------------------------------------------------------
+DEFAULT_NUM_PROCESSES = 8
+
+
+def _paired_files(folder_ref: str, folder_pred: str, file_ending: str, chill: bool):
+    """The reference's pairing (:133-139): the cases are the sorted prediction files, the reference list is built from
+    their names; ``chill=False`` asserts that every reference file has a prediction."""
+    from .label_folders import subfiles
+    files_pred = subfiles(folder_pred, suffix=file_ending, join=False)
+    files_ref = subfiles(folder_ref, suffix=file_ending, join=False)
+    if not chill:
+        present = [os.path.isfile(os.path.join(folder_pred, i)) for i in files_ref]
+        assert all(present), 'Not all files in folder_ref exist in folder_pred'
+    return [os.path.join(folder_ref, i) for i in files_pred], [os.path.join(folder_pred, i) for i in files_pred]
+
+
+def compute_metrics_on_files(files_ref: Sequence[str], files_pred: Sequence[str], image_reader_writer,
+                             labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None) -> List[dict]:
+    """``compute_metrics`` (:88-118) for every pair of label files: both are decoded to labels on the device and counted
+    by ``fnn_confusion_counts``; the reader thread inflates the next pair meanwhile.  A pair of different shapes raises a
+    ValueError that names both files."""
+    from .label_folders import run_label_cases
+    labels_or_regions = list(labels_or_regions)
+    _check_ignore(labels_or_regions, ignore_label)
+    values = count_classes(labels_or_regions)
+    cases = [[r, p] for r, p in zip(files_ref, files_pred)]
+
+    def run(i, maps):
+        (ref, _), (pred, _) = maps
+        if tuple(ref.shape) != tuple(pred.shape):
+            raise ValueError(f'shape mismatch: reference {cases[i][0]} is {tuple(ref.shape)}, prediction {cases[i][1]} is '
+                             f'{tuple(pred.shape)}')
+        counts = confusion_counts(ref, [pred], values, ignore_label, checked=True)[0]
+        return case_result(metrics_from_counts(counts, labels_or_regions), cases[i][0], cases[i][1]), None
+
+    return run_label_cases(image_reader_writer, cases, run)
+
+
+def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Optional[str], image_reader_writer,
+                              file_ending: str, regions_or_labels: Sequence[LabelOrRegion], ignore_label: Optional[int] = None,
+                              num_processes: int = DEFAULT_NUM_PROCESSES, chill: bool = True) -> dict:
+    """compute_metrics_on_folder (:121-173).  ``output_file`` must end with .json; can be None.  ``image_reader_writer``: an
+    instance of this package's reader-writer classes.  ``num_processes`` is accepted and ignored: no process is started."""
+    if output_file is not None:
+        assert output_file.endswith('.json'), 'output_file should end with .json'
+    files_ref, files_pred = _paired_files(folder_ref, folder_pred, file_ending, chill)
+    regions_or_labels = list(regions_or_labels)
+    results = compute_metrics_on_files(files_ref, files_pred, image_reader_writer, regions_or_labels, ignore_label)
+    result = aggregate(results, regions_or_labels)
+    if output_file is not None:
+        save_summary_json(result, output_file)
+    return result
+
+
+def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_file: str, plans_file: str,
+                               output_file: Optional[str] = None, num_processes: int = DEFAULT_NUM_PROCESSES,
+                               chill: bool = False):
+    """compute_metrics_on_folder2 (:177-196): labels or regions, ignore label, file ending and the reader-writer from
+    ``dataset.json`` and the plans; ``output_file`` defaults to ``<folder_pred>/summary.json``."""
+    from .imageio import determine_reader_writer_from_dataset_json
+    from .label_folders import load_json
+    from .plans import PlansManager
+    dataset_json = load_json(dataset_json_file)
+    rw = determine_reader_writer_from_dataset_json(dataset_json)()
+    if output_file is None:
+        output_file = os.path.join(folder_pred, 'summary.json')
+    lm = PlansManager(plans_file).get_label_manager(dataset_json)
+    compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, dataset_json['file_ending'],
+                              lm.foreground_regions if lm.has_regions else lm.foreground_labels, lm.ignore_label,
+                              num_processes, chill=chill)
+
+
+def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: Sequence[int], output_file: Optional[str] = None,
+                                     num_processes: int = DEFAULT_NUM_PROCESSES, ignore_label: Optional[int] = None,
+                                     chill: bool = False):
+    """compute_metrics_on_folder_simple (:199-212): the file ending is that of the first reference file (``.nii.gz``
+    whole, where the reference's ``os.path.splitext`` would keep ``.gz`` and then match the same files)."""
+    from .imageio import determine_reader_writer_from_file_ending
+    from .label_folders import subfiles
+    example_file = subfiles(folder_ref, join=True)[0]
+    file_ending = '.nii.gz' if example_file.lower().endswith('.nii.gz') else os.path.splitext(example_file)[-1]
+    rw = determine_reader_writer_from_file_ending(file_ending)()
+    if output_file is None:
+        output_file = os.path.join(folder_pred, 'summary.json')
+    compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, file_ending, labels, ignore_label=ignore_label,
+                              num_processes=num_processes, chill=chill)

@@ -24,6 +24,11 @@ images brought to RAS+ behind the decode and labels back to the file's frame bef
 around it (``DeviceCompressedLabels``, ``compressed_label_file_bytes``).  ``NiftiIO.compress_label_masks`` does the same for
 the per-label mask files of ``jhu.JHUPredictor``: all masks of a map in one pass (csrc/deflate_masks.hip).
 
+``NiftiIO.read_label_map`` reads a label file as labels: ``fnn_decode_labels`` (csrc/imageio.hip) turns the file's voxel
+bytes into the uint8 / uint16 map the counting, labelling and compressing kernels take, and reports what is no label - a
+file with such a voxel is refused (the reference would carry the voxel along as a value that equals no label).  The folder
+front-ends (``evaluation.compute_metrics_on_folder``, ``postprocessing.apply_postprocessing_to_folder``, ...) read with it.
+
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
 from __future__ import annotations
@@ -286,6 +291,49 @@ def decode_on_host(hdr: NiftiHeader, raw: np.ndarray) -> np.ndarray:
         return v.astype(np.float32).reshape(hdr.shape)
 
 
+# ---------------------------------------------------------------------- label files
+LABEL_FLAG_NOT_INTEGRAL, LABEL_FLAG_NEGATIVE, LABEL_FLAG_TOO_LARGE = \
+    capi.LABEL_FLAG_NOT_INTEGRAL, capi.LABEL_FLAG_NEGATIVE, capi.LABEL_FLAG_TOO_LARGE
+
+
+def label_bytes(hdr: NiftiHeader) -> int:
+    """The width ``read_label_map`` decodes a file to: 1 byte for the 1-byte datatypes, else 2."""
+    return 1 if hdr.bytes_per_voxel == 1 else 2
+
+
+def labels_on_host(hdr: NiftiHeader, raw: np.ndarray, out_bytes: Optional[int] = None) -> Tuple[np.ndarray, int, int]:
+    """numpy's statement of fnn_decode_labels -> (uint8 / uint16 (z, y, x), flags, largest valid label).  The value judged
+    is ``decode_on_host``'s float32 (an integer datatype without scaling is judged as the integer); a voxel that is no label
+    - not integral or not finite (1), else negative (2), else above the type's maximum (4) - is 0 and raises its flag."""
+    out_bytes = label_bytes(hdr) if out_bytes is None else int(out_bytes)
+    top = 255 if out_bytes == 1 else 65535
+    if hdr.dtype_char[0] in 'iu' and not hdr.scale:
+        v = np.frombuffer(memoryview(raw).cast('B')[:hdr.n_bytes], dtype=np.dtype(hdr.endian + hdr.dtype_char)).astype(np.int64)
+        odd = np.zeros(v.shape, bool)
+    else:
+        v = decode_on_host(hdr, raw).reshape(-1)
+        with np.errstate(invalid='ignore'):
+            odd = ~np.isfinite(v) | (v != np.trunc(v))
+    with np.errstate(invalid='ignore'):
+        neg = ~odd & (v < 0)
+        big = ~odd & (v > top)
+    flags = (LABEL_FLAG_NOT_INTEGRAL if odd.any() else 0) | (LABEL_FLAG_NEGATIVE if neg.any() else 0) | \
+        (LABEL_FLAG_TOO_LARGE if big.any() else 0)
+    labels = np.where(odd | neg | big, 0, v).astype(np.uint8 if out_bytes == 1 else np.uint16)
+    return labels.reshape(hdr.shape), flags, int(labels.max()) if labels.size else 0
+
+
+def label_flags_error(fname: str, flags: int, out_bytes: int) -> RuntimeError:
+    said = []
+    if flags & LABEL_FLAG_NOT_INTEGRAL:
+        said.append('voxels that are not integral or not finite')
+    if flags & LABEL_FLAG_NEGATIVE:
+        said.append('negative voxels')
+    if flags & LABEL_FLAG_TOO_LARGE:
+        said.append(f'voxels above {255 if out_bytes == 1 else 65535}, the largest label a {out_bytes}-byte map holds')
+    return RuntimeError(f'{fname}: not a label file: it holds ' + ', '.join(said))
+
+
 class StagedCase:
     """The files of one case between the host and the device: headers (checked), and one pinned byte buffer per file that a
     host thread fills."""
@@ -356,6 +404,76 @@ class NiftiIO:
                 keep.append(raw)
             stream.synchronize()
         return out, case_properties(hdr0)
+
+    # ------------------------------------------------------------------ label files
+    def stage_label_files(self, fnames: Sequence[str], slot: int = 0) -> StagedCase:
+        """As ``stage`` for label files that are read one by one (a reference and a prediction, say): every header checked
+        on its own, nothing compared between the files."""
+        fnames = [str(f) for f in fnames]
+        hdrs = [read_header(f) for f in fnames]
+        staged = StagedCase(fnames, hdrs, self._pinned_buffers(hdrs, slot))
+        self._orient_labels(staged)
+        return staged
+
+    def _orient_labels(self, staged: StagedCase) -> None:
+        """What ``_label_frame`` needs to know about the files beyond their headers: here nothing."""
+
+    def _label_frame(self, staged: StagedCase, i: int, labels):
+        """File i's decoded map (device tensor or numpy array, in the file's frame) -> (the map as this class hands it out,
+        its properties)."""
+        return labels, case_properties(staged.hdrs[i])
+
+    def decode_label_maps(self, staged: StagedCase) -> list:
+        """A filled StagedCase -> per file ``(labels (z, y, x), properties)``: device tensors of uint8, or of int16 that carry
+        the bits of uint16 (the engine's two-byte label type).  Every file's bytes are uploaded and decoded by
+        ``fnn_decode_labels`` on the current stream - 1 byte wide for the 1-byte datatypes, else 2 bytes and narrowed to
+        uint8 when the largest label is below 256.  RuntimeError naming the file when it holds what is no label.
+        Synchronises: the staging buffers are free again on return."""
+        import torch
+        dev = self._dev()
+        n = len(staged.hdrs)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            status = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+            maps, keep = [], []
+            for i, (h, b) in enumerate(zip(staged.hdrs, staged.buffers)):
+                raw = torch.empty(max(16, h.n_bytes), dtype=torch.uint8, device=dev)      # (the allocator aligns to 512 bytes)
+                raw[:h.n_bytes].copy_(b[:h.n_bytes], non_blocking=True)
+                keep.append(raw)
+                wide = label_bytes(h) == 2
+                out = torch.empty(h.shape, dtype=torch.int16 if wide else torch.uint8, device=dev)
+                capi.decode_labels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter, 2 if wide else 1,
+                                   out.data_ptr(), status[i].data_ptr(), stream.cuda_stream)
+                maps.append(out)
+            said = status.cpu().numpy()                          # (waits for the stream)
+            made = []
+            for i, (f, h, m) in enumerate(zip(staged.fnames, staged.hdrs, maps)):
+                if said[i, 0]:
+                    raise label_flags_error(f, int(said[i, 0]), label_bytes(h))
+                if m.dtype == torch.int16 and said[i, 1] < 256:
+                    m = m.to(torch.uint8)
+                made.append(self._label_frame(staged, i, m))
+        return made
+
+    def read_label_map(self, fname: str, on_device: bool = True):
+        """A label file as labels -> ``(labels (z, y, x), properties)``: on the device ``decode_label_maps``' tensor; with
+        ``on_device=False`` the same values as a numpy uint8 / uint16 array, computed and checked with numpy (no GPU
+        call).  A file with a voxel that is no label - not integral, negative, above the map's maximum - raises a
+        RuntimeError that names it."""
+        fname = str(fname)
+        if on_device:
+            return self.decode_label_maps(self.stage_label_files([fname]).fill())[0]
+        hdr = read_header(fname)
+        raw = np.empty(hdr.n_bytes, dtype=np.uint8)
+        read_voxel_bytes(fname, hdr, raw)
+        labels, flags, top = labels_on_host(hdr, raw)
+        if flags:
+            raise label_flags_error(fname, flags, label_bytes(hdr))
+        if labels.dtype == np.uint16 and top < 256:
+            labels = labels.astype(np.uint8)
+        staged = StagedCase([fname], [hdr], [None])
+        self._orient_labels(staged)
+        return self._label_frame(staged, 0, labels)
 
     # ------------------------------------------------------------------ the reference's interface
     def read_images(self, image_fnames: Union[List[str], Tuple[str, ...]], on_device: bool = True):
@@ -798,6 +916,16 @@ class NiftiReorientIO(NiftiIO):
                 capi.reorient(tmp.data_ptr(), 4, h.shape, o.src_axis, o.flip, out[c].data_ptr(), stream.cuda_stream)
             stream.synchronize()
         return out, self._properties(o0)
+
+    def _orient_labels(self, staged: StagedCase) -> None:
+        staged.orients = self._orient(staged.hdrs)
+
+    def _label_frame(self, staged: StagedCase, i: int, labels):
+        """The map brought to RAS+: a device tensor by ``fnn_reorient`` on the current stream, a numpy array by numpy."""
+        o = staged.orients[i]
+        if hasattr(labels, 'data_ptr'):
+            return self._reorient_on_device(labels, o.src_axis, o.flip), self._properties(o)
+        return reorient_on_host(labels, o.src_axis, o.flip), self._properties(o)
 
     def read_images(self, image_fnames: Union[List[str], Tuple[str, ...]], on_device: bool = True):
         image_fnames = [str(f) for f in image_fnames]

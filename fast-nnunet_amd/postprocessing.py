@@ -13,12 +13,16 @@ The rule implemented (acvl_utils ``remove_all_but_largest_component`` as the ref
 * voxels in the mask and not kept become ``background_label``; the input is not modified, dtype and shape are kept.
 
 The labelling is ``fnn_keep_largest_components`` (csrc/postprocess.hip), which handles several disjoint label sets in
-one pass.  ``apply_postprocessing`` fuses consecutive steps into one pass where that gives the sequential result
+one pass.  ``load_postprocess_save`` (:42-50) and ``apply_postprocessing_to_folder`` (:247-294) do the same for label files:
+read as labels on the device, post-processed there and written by the predictions' writer behind a reader and a writer
+thread; ``determine_postprocessing_on_folder`` is the reference's search on folders (postprocessing_search.py).
+``apply_postprocessing`` fuses consecutive steps into one pass where that gives the sequential result
 (``plan_passes``).  There is no CPU path for this module's own steps.
 """
 from __future__ import annotations
 
 import io
+import os
 import pickle
 from typing import Callable, List, Sequence, Tuple, Union
 
@@ -216,3 +220,79 @@ def determine_postprocessing(predictions, references, dataset_json_or_label_mana
     ``postprocessing_search.determine_postprocessing``."""
     from .postprocessing_search import determine_postprocessing as run
     return run(predictions, references, dataset_json_or_label_manager, output_folder, save_postprocessed, verbose, backend)
+
+
+# ---- label files ---------------------------------------------------------------------------------------------------------
+def _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress_on_device: bool):
+    """The GPU part of one file: decoded labels -> what ``rw.write_seg`` takes on a thread that makes no GPU call."""
+    from .label_folders import as_plain_labels, labels_for_writer
+    seg = apply_postprocessing(as_plain_labels(labels), pp_fns, pp_fn_kwargs)
+    return labels_for_writer(rw, seg, props, compress_on_device)
+
+
+def load_postprocess_save(segmentation_file: str, output_fname: str, image_reader_writer, pp_fns: Sequence[Callable],
+                          pp_fn_kwargs: Sequence[dict], compress_on_device: bool = False):
+    """``load_postprocess_save`` (remove_connected_components.py:42-50): the file is read as labels on the device,
+    post-processed there and written with its own properties."""
+    labels, props = image_reader_writer.read_label_map(segmentation_file)
+    out = _postprocessed_for_writer(image_reader_writer, labels, props, pp_fns, pp_fn_kwargs, compress_on_device)
+    image_reader_writer.write_seg(out, output_fname, props)
+
+
+def apply_postprocessing_to_files(input_files: Sequence[str], output_files: Sequence[str], image_reader_writer,
+                                  pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict], compress_on_device: bool = False):
+    """``load_postprocess_save`` for every pair of names, pipelined: a reader thread inflates the next file and a writer
+    thread compresses and writes the previous one while the calling thread - the only one that touches the GPU - decodes
+    and post-processes this one.  A file appears under its name only when it is complete."""
+    from .label_folders import run_label_cases
+    rw = image_reader_writer
+    input_files, output_files = list(input_files), list(output_files)
+
+    def run(i, maps):
+        labels, props = maps[0]
+        out = _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress_on_device)
+        return None, (lambda: rw.write_seg(out, output_files[i], props))
+
+    run_label_cases(rw, [[f] for f in input_files], run, write_thread=True)
+
+
+def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict],
+                                   plans_file_or_dict=None, dataset_json_file_or_dict=None, num_processes=8,
+                                   compress_on_device: bool = False) -> None:
+    """``apply_postprocessing_to_folder`` (remove_connected_components.py:247-294).  If plans_file_or_dict or
+    dataset_json_file_or_dict are None, they are looked for in input_folder.  ``num_processes`` is accepted and ignored;
+    ``compress_on_device`` writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded)."""
+    from .imageio import prediction_reader_writer_class
+    from .label_folders import load_json, subfiles
+    from .plans import PlansManager
+    if plans_file_or_dict is None:
+        expected_plans_file = os.path.join(input_folder, 'plans.json')
+        if not os.path.isfile(expected_plans_file):
+            raise RuntimeError(f'Expected plans file missing: {expected_plans_file}. The plans file should have been '
+                               f'created while running nnUNetv2_predict. Sadge. If the folder you want to apply '
+                               f'postprocessing to was create from an ensemble then just specify one of the '
+                               f'plans files of the ensemble members in plans_file_or_dict')
+        plans_file_or_dict = load_json(expected_plans_file)
+    plans_manager = PlansManager(plans_file_or_dict)
+    if dataset_json_file_or_dict is None:
+        expected_dataset_json_file = os.path.join(input_folder, 'dataset.json')
+        if not os.path.isfile(expected_dataset_json_file):
+            raise RuntimeError(f'Expected plans file missing: {expected_dataset_json_file}. The dataset.json should have been '
+                               f'copied while running nnUNetv2_predict/nnUNetv2_ensemble. Sadge.')
+        dataset_json_file_or_dict = load_json(expected_dataset_json_file)
+    dataset_json = dataset_json_file_or_dict if isinstance(dataset_json_file_or_dict, dict) else load_json(dataset_json_file_or_dict)
+    rw = prediction_reader_writer_class(plans_manager, dataset_json)()
+    os.makedirs(output_folder, exist_ok=True)
+    files = subfiles(input_folder, suffix=dataset_json['file_ending'], join=False)
+    apply_postprocessing_to_files([os.path.join(input_folder, i) for i in files], [os.path.join(output_folder, i) for i in files],
+                                  rw, pp_fns, pp_fn_kwargs, compress_on_device)
+
+
+def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str, plans_file_or_dict=None,
+                                       dataset_json_file_or_dict=None, num_processes: int = 8,
+                                       keep_postprocessed_files: bool = True):
+    """The reference's ``determine_postprocessing`` (remove_connected_components.py:52-244) on folders of label files; see
+    ``postprocessing_search.determine_postprocessing_on_folder``."""
+    from .postprocessing_search import determine_postprocessing_on_folder as run
+    return run(folder_predictions, folder_ref, plans_file_or_dict, dataset_json_file_or_dict, num_processes,
+               keep_postprocessed_files)

@@ -12,6 +12,10 @@ on label arrays in place of folders:
 Every comparison is made on the summary values the reference reads back from its summary.json files (float64, NaN
 compares False).  Labelling is ``fnn_keep_largest_components``, counting ``fnn_confusion_counts``; the metrics are
 computed on the host from the counts (``evaluation.metrics_from_counts``).  One case is on the device at a time.
+
+``determine_postprocessing_on_folder`` is the reference's function itself, on folders of label files: the same search fed
+by ``FolderBackend``, which reads a case's files as labels on the device when the search asks for them (a reader thread
+inflates the next case's meanwhile) and keeps the candidates the search holds between steps deflated on the host.
 """
 from __future__ import annotations
 
@@ -58,6 +62,30 @@ def _label_manager(dataset_json_or_label_manager) -> LabelManager:
     return dataset_json_or_label_manager
 
 
+class LabelFile:
+    """A label file that stands in for its map in ``determine_postprocessing``: the header's shape now, the labels when
+    ``FolderBackend.put`` reads them."""
+
+    def __init__(self, fname: str):
+        from .imageio import read_header
+        self.fname = str(fname)
+        self.shape = tuple(read_header(self.fname).shape)
+
+
+class PackedLabels:
+    """A label map between two steps of the search, deflated (level 1) on the host."""
+
+    def __init__(self, arr: np.ndarray):
+        import zlib
+        arr = np.ascontiguousarray(arr)
+        self.shape, self.dtype = arr.shape, arr.dtype
+        self.blob = zlib.compress(memoryview(arr).cast('B'), 1)
+
+    def array(self) -> np.ndarray:
+        import zlib
+        return np.frombuffer(bytearray(zlib.decompress(self.blob)), dtype=self.dtype).reshape(self.shape)
+
+
 def _cases(predictions, references) -> List[Tuple[str, object, object]]:
     """(name, prediction, reference) in the order of the sorted prediction names; a sequence is named by position."""
     if not isinstance(predictions, Mapping):
@@ -77,8 +105,9 @@ def _cases(predictions, references) -> List[Tuple[str, object, object]]:
             raise ValueError(f'{n}: shape mismatch: reference {ev._shape(r)}, prediction {ev._shape(p)}')
         if len(ev._shape(p)) not in (2, 3):
             raise ValueError(f'{n}: label maps must be 2-D or 3-D, got shape {ev._shape(p)}')
-        ev.check_label_map(p)
-        ev.check_label_map(r)
+        for m in (p, r):
+            if not isinstance(m, LabelFile):                     # (a file is checked by the kernel that decodes it)
+                ev.check_label_map(m)
         out.append((n, p, r))
     return out
 
@@ -92,7 +121,9 @@ def _device_map(seg, dev: torch.device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr if arr.dtype == np.uint8 else arr.astype(np.int32))).to(dev)
 
 
-def _host_copy(seg) -> np.ndarray:
+def _host_copy(seg):
+    if isinstance(seg, (LabelFile, PackedLabels)):               # (immutable: the search never writes its sources)
+        return seg
     return seg.detach().cpu().numpy().copy() if isinstance(seg, torch.Tensor) else np.array(seg, copy=True)
 
 
@@ -116,10 +147,14 @@ def _class_mean_dice(per_case: List[dict], key) -> float:
     return float(np.nanmean(vals))
 
 
-def _write_outputs(output_folder: str, baseline: dict, final: dict, pp_fns, pp_fn_kwargs):
-    os.makedirs(os.path.join(output_folder, 'postprocessed'), exist_ok=True)
-    ev.save_summary_json(baseline, os.path.join(output_folder, 'summary.json'))
-    ev.save_summary_json(final, os.path.join(output_folder, 'postprocessed', 'summary.json'))
+def _write_outputs(output_folder: str, baseline: dict, final: dict, pp_fns, pp_fn_kwargs, write_baseline: bool = True,
+                   write_final: bool = True):
+    os.makedirs(output_folder, exist_ok=True)
+    if write_baseline:
+        ev.save_summary_json(baseline, os.path.join(output_folder, 'summary.json'))
+    if write_final:
+        os.makedirs(os.path.join(output_folder, 'postprocessed'), exist_ok=True)
+        ev.save_summary_json(final, os.path.join(output_folder, 'postprocessed', 'summary.json'))
     save_postprocessing_pkl(pp_fns, pp_fn_kwargs, os.path.join(output_folder, 'postprocessing.pkl'))
     doc = {
         'input_folder': {'foreground_mean': baseline['foreground_mean'],
@@ -171,6 +206,25 @@ def determine_postprocessing(predictions: Union[Sequence, Mapping[str, object]],
     ``postprocessed/summary.json`` (final), ``postprocessing.pkl`` (loadable by nnU-Net itself) and
     ``postprocessing.json``; with ``save_postprocessed`` also ``postprocessed/<name>.npy``.  The inputs are not
     modified.  ``backend``: the labelling and counting operations (default: the GPU, ``DeviceBackend``)."""
+    cases, pp_fns, pp_fn_kwargs, baseline, final, be = _search(predictions, references, dataset_json_or_label_manager, verbose,
+                                                               backend)
+    if output_folder is not None:
+        _write_outputs(output_folder, baseline, final, pp_fns, pp_fn_kwargs)
+        if save_postprocessed:
+            for name, pred, _ in cases:
+                out = be.apply(_host_copy(pred), pp_fns, pp_fn_kwargs)
+                fname = name if name.endswith('.npy') else name + '.npy'
+                np.save(os.path.join(output_folder, 'postprocessed', fname), np.asarray(out))
+    # the reference hands back the kwargs after its JSON export turned numpy integers into Python ones (the pkl keeps
+    # the numpy integers)
+    return pp_fns, [ev.json_ready(k) for k in pp_fn_kwargs]
+
+
+def _search(predictions, references, dataset_json_or_label_manager, verbose: bool = False, backend=None,
+            baseline: Optional[dict] = None):
+    """The search itself -> (cases, pp_fns, pp_fn_kwargs with numpy integers, baseline summary, final summary, backend).
+    ``baseline``: a summary of the predictions made earlier (the reference reuses an existing summary.json); its per-case
+    metrics then stand for the ones counted here."""
     lm = _label_manager(dataset_json_or_label_manager)
     fg_labels = [np.int64(v) for v in lm.foreground_labels]          # the reference's labels come from np.unique
     labels_or_regions = list(lm.foreground_regions) if lm.has_regions else list(fg_labels)
@@ -182,6 +236,7 @@ def determine_postprocessing(predictions: Union[Sequence, Mapping[str, object]],
     if not cases:
         raise ValueError('no prediction to evaluate')
     be = backend if backend is not None else DeviceBackend()
+    begin_pass = getattr(be, 'begin_pass', lambda sources, refs: None)   # (a backend that reads ahead learns the order)
     names = [n for n, _, _ in cases]
     values = ev.count_classes(labels_or_regions)
     fg_set = pp.label_set(list(fg_labels))
@@ -192,6 +247,7 @@ def determine_postprocessing(predictions: Union[Sequence, Mapping[str, object]],
     src_lab_m, fg_lab_m = [], []    # label datasets: metrics of the fused per-label candidates of both sources
     fg_maps = []                    # region datasets: the whole-foreground candidates (host)
     with be.context():
+        begin_pass([p for _, p, _ in cases], [r for _, _, r in cases])
         for name, pred, ref in cases:
             p, r = be.put(pred), be.put(ref)
             f = be.keep_largest(p, [fg_set])
@@ -214,7 +270,12 @@ def determine_postprocessing(predictions: Union[Sequence, Mapping[str, object]],
                 fg_maps.append(be.host(f))
             del p, r, f, maps
 
-    baseline = _summary(base_m, names, labels_or_regions)
+    if baseline is None:
+        baseline = _summary(base_m, names, labels_or_regions)
+    else:
+        if len(baseline['metric_per_case']) != len(cases):
+            raise ValueError(f"the summary given as baseline has {len(baseline['metric_per_case'])} cases, the folder {len(cases)}")
+        base_m = [c['metrics'] for c in baseline['metric_per_case']]
     fg_summary = _summary(fg_m, names, labels_or_regions)
     pp_fns, pp_fn_kwargs = [], []
     step = pp.remove_all_but_largest_component_from_segmentation
@@ -249,6 +310,7 @@ def determine_postprocessing(predictions: Union[Sequence, Mapping[str, object]],
             for region in labels_or_regions:
                 s = pp.label_set(region)
                 cand_maps, cand_m = [], []
+                begin_pass(sources, [r for _, _, r in cases])
                 for (name, _, ref), src in zip(cases, sources):
                     c = be.keep_largest(be.put(src), [s])
                     counts = be.counts(be.put(ref), [c], values, ignore)[0]
@@ -265,13 +327,125 @@ def determine_postprocessing(predictions: Union[Sequence, Mapping[str, object]],
                     say(f'Removing all but the largest component for {region} did not improve results!')
 
     final = _summary(current, names, labels_or_regions)
-    if output_folder is not None:
-        _write_outputs(output_folder, baseline, final, pp_fns, pp_fn_kwargs)
-        if save_postprocessed:
-            for name, pred, _ in cases:
-                out = be.apply(_host_copy(pred), pp_fns, pp_fn_kwargs)
-                fname = name if name.endswith('.npy') else name + '.npy'
-                np.save(os.path.join(output_folder, 'postprocessed', fname), np.asarray(out))
-    # the reference hands back the kwargs after its JSON export turned numpy integers into Python ones (the pkl keeps
-    # the numpy integers)
+    return cases, pp_fns, pp_fn_kwargs, baseline, final, be
+
+
+class FolderBackend(DeviceBackend):
+    """``DeviceBackend`` for sources that are label files (``LabelFile``) or deflated maps (``PackedLabels``): ``put`` reads a
+    file as labels on the device (``decode_label_maps``); ``begin_pass`` tells it the order in which a pass over the cases
+    will ask, so that one ``_HostWorker`` inflates the files of the next case into the other slot of pinned buffers while
+    this one runs; ``host`` deflates what the search keeps between steps.  One case is on the device at a time and the
+    folder is never in host memory as a whole.  Used as a context manager: the reader thread lives inside the ``with``."""
+
+    def __init__(self, rw):
+        DeviceBackend.__init__(self)
+        self.rw = rw
+        self.reader = None
+        self.plan, self.at, self.job, self.ready = [], 0, None, {}
+
+    def __enter__(self):
+        from .predictor import _HostWorker
+        self.reader = _HostWorker('fnn-reader')
+        return self
+
+    def __exit__(self, *exc):
+        if self.reader is not None:
+            self.reader.close()
+            self.reader = None
+
+    def _submit(self, k: int):
+        files = self.plan[k]
+        if not files:
+            return None
+        return self.reader.submit(self.rw.stage_label_files(files, slot=k % 2).fill)
+
+    def begin_pass(self, sources, refs):
+        if self.job is not None:
+            self.job.done.wait()                                 # (nothing of an abandoned pass stays in flight)
+        self.plan = [[m.fname for m in pair if isinstance(m, LabelFile)] for pair in zip(sources, refs)]
+        self.at, self.ready = 0, {}
+        self.job = self._submit(0) if self.plan else None
+
+    def _read(self, fname: str):
+        if fname not in self.ready and self.at < len(self.plan) and fname in self.plan[self.at]:
+            staged = self.job.result()
+            self.at += 1
+            self.job = self._submit(self.at) if self.at < len(self.plan) else None
+            self.ready = {f: m for f, (m, _) in zip(staged.fnames, self.rw.decode_label_maps(staged))}
+        if fname in self.ready:
+            return self.ready.pop(fname)
+        # asked out of order: read here and now, through a slot of pinned buffers that the reader thread never fills
+        return self.rw.decode_label_maps(self.rw.stage_label_files([fname], slot=2).fill())[0][0]
+
+    def put(self, seg):
+        if isinstance(seg, LabelFile):
+            from .label_folders import as_plain_labels
+            return as_plain_labels(self._read(seg.fname))
+        if isinstance(seg, PackedLabels):
+            seg = seg.array()
+        return DeviceBackend.put(self, seg)
+
+    def host(self, seg):
+        return PackedLabels(seg.cpu().numpy())
+
+
+def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str, plans_file_or_dict=None,
+                                       dataset_json_file_or_dict=None, num_processes: int = 8,
+                                       keep_postprocessed_files: bool = True, verbose: bool = True):
+    """The reference's ``determine_postprocessing`` (remove_connected_components.py:52-244) on folders of label files.
+
+    Leaves what the reference leaves: ``summary.json`` in ``folder_predictions`` (an existing one is reused, as the
+    reference reuses it), ``postprocessing.pkl``, ``postprocessing.json``, and - unless ``keep_postprocessed_files`` is
+    False - ``postprocessed/<files>`` with ``postprocessed/summary.json``; no ``temp`` folder is made.  Plans or
+    dataset.json given as None are looked for in ``folder_predictions``.  ``num_processes`` is accepted and ignored.
+    Returns ``(pp_fns, pp_fn_kwargs)``."""
+    from .imageio import prediction_reader_writer_class
+    from .label_folders import load_json, subfiles
+    from .plans import PlansManager
+    if plans_file_or_dict is None:
+        expected_plans_file = os.path.join(folder_predictions, 'plans.json')
+        if not os.path.isfile(expected_plans_file):
+            raise RuntimeError(f'Expected plans file missing: {expected_plans_file}. The plans files should have been '
+                               f'created while running nnUNetv2_predict. Sadge.')
+        plans_file_or_dict = load_json(expected_plans_file)
+    plans_manager = PlansManager(plans_file_or_dict)
+    if dataset_json_file_or_dict is None:
+        expected_dataset_json_file = os.path.join(folder_predictions, 'dataset.json')
+        if not os.path.isfile(expected_dataset_json_file):
+            raise RuntimeError(f'Expected plans file missing: {expected_dataset_json_file}. The plans files should have been '
+                               f'created while running nnUNetv2_predict. Sadge.')
+        dataset_json_file_or_dict = load_json(expected_dataset_json_file)
+    dataset_json = dataset_json_file_or_dict if isinstance(dataset_json_file_or_dict, dict) else load_json(dataset_json_file_or_dict)
+    rw = prediction_reader_writer_class(plans_manager, dataset_json)()
+    ending = dataset_json['file_ending']
+    predicted_files = subfiles(folder_predictions, suffix=ending, join=False)
+    ref_files = subfiles(folder_ref, suffix=ending, join=False)
+    if not all(i in predicted_files for i in ref_files):
+        print('WARNING: Not all files in folder_ref were found in folder_predictions. Determining postprocessing '
+              'should always be done on the entire dataset!')
+    if not predicted_files:
+        raise ValueError(f'no {ending} file in {folder_predictions}')
+    missing = [i for i in predicted_files if not os.path.isfile(os.path.join(folder_ref, i))]
+    if missing:
+        raise ValueError(f'predictions without a reference: {missing[:5]}')
+    summary_file = os.path.join(folder_predictions, 'summary.json')
+    known = ev.load_summary_json(summary_file) if os.path.isfile(summary_file) else None
+    preds = {i: LabelFile(os.path.join(folder_predictions, i)) for i in predicted_files}
+    refs = {i: LabelFile(os.path.join(folder_ref, i)) for i in predicted_files}
+    with FolderBackend(rw) as be:
+        _, pp_fns, pp_fn_kwargs, baseline, final, _ = _search(preds, refs, plans_manager.get_label_manager(dataset_json),
+                                                              verbose, be, baseline=known)
+    output_folder = os.path.join(folder_predictions, 'postprocessed')
+    if known is None:
+        for case, name in zip(baseline['metric_per_case'], predicted_files):
+            case['reference_file'] = os.path.join(folder_ref, name)
+            case['prediction_file'] = os.path.join(folder_predictions, name)
+    for case, name in zip(final['metric_per_case'], predicted_files):
+        case['reference_file'] = os.path.join(folder_ref, name)
+        case['prediction_file'] = os.path.join(output_folder, name)
+    _write_outputs(folder_predictions, baseline, final, pp_fns, pp_fn_kwargs, write_baseline=known is None,
+                   write_final=keep_postprocessed_files)
+    if keep_postprocessed_files:
+        pp.apply_postprocessing_to_files([os.path.join(folder_predictions, i) for i in predicted_files],
+                                         [os.path.join(output_folder, i) for i in predicted_files], rw, pp_fns, pp_fn_kwargs)
     return pp_fns, [ev.json_ready(k) for k in pp_fn_kwargs]

@@ -414,6 +414,26 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
 int fnn_decode_voxels(const void *raw, int nifti_datatype, int byteswap, int64_t n_vox, int scale, double slope,
                       double inter, float *out, void *stream);
 
+/* The voxels of a label file as the file holds them -> a label map (additive in ABI 4): what the reference's read_seg
+ * value is compared against with ==, as integers the counting and labelling kernels take, without the float32 tensor
+ * and the cast behind it.  raw, nifti_datatype, byteswap, n_vox, scale, slope, inter: as fnn_decode_voxels.  The value
+ * judged for a voxel is exactly the float32 fnn_decode_voxels stores for it (an integer datatype without scaling is
+ * judged as the integer it is, which says the same).  out_bytes: 1 (uint8) or 2 (the bits of uint16); out: device
+ * pointer aligned to the element only (a slice of a larger tensor).  A voxel whose value is integral and lies in
+ * [0, 255] (out_bytes 1) or [0, 65535] (out_bytes 2) is valid and is stored as that integer.  Every other voxel stores 0
+ * and raises a flag: 1 not integral or not finite, 2 negative, 4 above the output type's maximum.  status: two int32
+ * on the device - [0] the flags of all voxels OR-ed, [1] the largest valid label (0 when there is none); the call zeroes
+ * them on `stream` before the launch, and after the stream is synchronised both are exact and the same on every run.
+ * FNN_E_INVALID before any launch: NULL or host pointers, raw not 16-byte aligned, out or status not aligned to their
+ * element, out_bytes other than 1 or 2, negative n_vox; FNN_E_UNSUPPORTED: any other datatype code, more voxels than one
+ * launch addresses.  n_vox == 0 zeroes status and launches nothing.  Nothing is read outside raw[0, n_vox * sizeof(T))
+ * or written outside out[0, n_vox * out_bytes) and status[0..1].  One pass, no scratch memory, asynchronous on `stream`. */
+#define FNN_LABEL_FLAG_NOT_INTEGRAL 1
+#define FNN_LABEL_FLAG_NEGATIVE 2
+#define FNN_LABEL_FLAG_TOO_LARGE 4
+int fnn_decode_labels(const void *raw, int nifti_datatype, int byteswap, int64_t n_vox, int scale, double slope,
+                      double inter, int out_bytes, void *out, int32_t *status, void *stream);
+
 /* Flip and permute the axes of a C-order 3-D array on the device (additive in ABI 4): what the reference's
  * NibabelIOWithReorient does with numpy on the host (as_reoriented on read, and again on the label map on write).
  * in: shape_in[0..2] elements of elem_bytes bytes (1, 2 or 4: uint8 / uint16 labels, float32 images; anything else is

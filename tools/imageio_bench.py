@@ -9,13 +9,17 @@ a synthetic 61-label map of n^3 voxels as uint8 and uint16 and on the golden mas
 copy of the same bytes, to zlib level 1 on this machine's CPU, and the download of the fragment next to that of the map; and
 (``--section masks``, these rows alone) the per-label mask files of JHUPredictor: fnn_deflate_masks_count + fnn_deflate_masks_emit
 on synthetic maps of 61 and 118 labels and on the golden mask tiled, next to one fnn_deflate_labels call per mask materialised on
-the device, to zlib level 1 of a mask on the CPU times the number of labels, and the sizes that are downloaded and written.
+the device, to zlib level 1 of a mask on the CPU times the number of labels, and the sizes that are downloaded and written; and
+(``--section label_files``, these rows alone, written to profiles/r21_label_files.txt unless ``--out`` says otherwise)
+fnn_decode_labels on the int16 and the uint8 bytes of an n^3 label map next to fnn_decode_voxels followed by the cast it
+replaces and to a device copy of the same bytes, and compute_metrics_on_folder on a few generated cases of n^3 voxels, per
+case and split into inflate, upload, decode and count.
 
 The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, so that gzip has something to do), written
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient|deflate|masks] [--out FILE]
+                                                          [--section all|reorient|deflate|masks|label_files] [--out FILE]
 """
 import argparse
 import gzip
@@ -53,6 +57,24 @@ def events(fn, reps, dev):
         e1.synchronize()
         if r:
             ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), min(ts), max(ts)
+
+
+def events_batched(fn, calls, windows, dev):
+    """ms per call: `calls` calls of fn inside one pair of events, `windows` such windows after one warm-up window -> (median,
+    min, max) of the windows' per-call times.  For calls of a fraction of a millisecond, whose single-call window would hold
+    as much enqueue cost as kernel."""
+    ts = []
+    for r in range(windows + 1):
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        e1.synchronize()
+        if r:
+            ts.append(e0.elapsed_time(e1) / calls)
     return float(np.median(ts)), min(ts), max(ts)
 
 
@@ -231,6 +253,87 @@ def bench_masks(n, reps, dev, say, row):
     del inputs
 
 
+def bench_label_files(n, reps, cases, dev, say, row):
+    """fnn_decode_labels (csrc/imageio.hip) and the folder evaluation that reads with it."""
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import evaluation as ev
+    from fast_nnunet_amd import imageio as fio
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    calls, windows = 100, max(reps, 5)
+    say(f'--- fnn_decode_labels, a 61-label map of {n}^3 voxels; outputs allocated before; ms per call from {calls} calls inside one '
+        f'pair of events, median (min, max) of {windows} such windows after a warm-up window')
+    labels = label_map(n, dev)
+    n_vox = labels.numel()
+    status = torch.zeros(2, dtype=torch.int32, device=dev)
+    f32 = torch.empty(n_vox, dtype=torch.float32, device=dev)
+    for what, code, size, raw, out_dt in (('int16 file bytes -> 2-byte labels', 4, 2, labels.to(torch.int16).reshape(-1).view(torch.uint8), torch.int16),
+                                          ('uint8 file bytes -> uint8 labels', 2, 1, labels.reshape(-1), torch.uint8)):
+        raw = raw.contiguous()
+        out = torch.empty(n_vox, dtype=out_dt, device=dev)
+        moved = n_vox * size * 2
+        t = events_batched(lambda: capi.decode_labels(raw.data_ptr(), code, False, n_vox, False, 1.0, 0.0, size, out.data_ptr(),
+                                                      status.data_ptr(), stream), calls, windows, dev)
+        row(f'{what}: fnn_decode_labels', t,
+            f'  {moved / t[0] / 1e6:.0f} GB/s of {moved / 1e9:.2f} GB = {100 * moved / t[0] / 1e6 / (COPY_TBS * 1e3):.1f} % of {COPY_TBS} TB/s; '
+            f'status {status.tolist()}')
+        same = bool((out.reshape(labels.shape) == labels).all())
+
+        def before():
+            capi.decode_voxels(raw.data_ptr(), code, False, n_vox, False, 1.0, 0.0, f32.data_ptr(), stream)
+            out.copy_(f32)
+        tb = events_batched(before, calls, windows, dev)
+        row(f'{what}: fnn_decode_voxels + the cast of its float32 ({4 * n_vox / 2 ** 20:.0f} MiB)', tb, f'  {tb[0] / t[0]:.1f}x fnn_decode_labels')
+        dst = torch.empty_like(raw)
+        tc = events_batched(lambda: dst.copy_(raw), calls, windows, dev)
+        row(f'{what}: device copy of the same bytes ({n_vox * size / 2 ** 20:.0f} MiB)', tc,
+            f'  {moved / tc[0] / 1e6:.0f} GB/s; the decode takes {t[0] / tc[0]:.2f}x; labels equal the map: {same}')
+        del out, dst, raw
+    del f32
+
+    say(f'--- compute_metrics_on_folder, {cases} cases of {n}^3 voxels: uint8 .nii.gz references, int16 .nii.gz predictions (gzip level 1), '
+        f'60 foreground labels; wall clock')
+    with tempfile.TemporaryDirectory() as tmp:
+        ref_dir, pred_dir = os.path.join(tmp, 'ref'), os.path.join(tmp, 'pred')
+        os.makedirs(ref_dir), os.makedirs(pred_dir)
+        affine = np.diag([0.8, 0.8, 1.25, 1.0])
+        for i in range(cases):
+            ref = label_map(n, dev, seed=30 + i)
+            pred = ref.clone()
+            pred[i::7] = 0
+            for folder, arr, code in ((ref_dir, ref.cpu().numpy(), 2), (pred_dir, pred.cpu().numpy().astype('<i2'), 4)):
+                with open(os.path.join(folder, f'case{i}.nii.gz'), 'wb') as raw, \
+                        gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=raw, mtime=0) as g:
+                    g.write(fio.nifti1_header_bytes((n, n, n), code, affine))
+                    g.write(arr.tobytes())
+            del ref, pred
+        sizes = [os.path.getsize(os.path.join(d, 'case0.nii.gz')) / 2 ** 20 for d in (ref_dir, pred_dir)]
+        say(f'case0 on disk: reference {sizes[0]:.1f} MiB, prediction {sizes[1]:.1f} MiB')
+        rw = fio.NiftiIO(dev)
+        lor = list(range(1, 61))
+        ev.compute_metrics_on_folder(ref_dir, pred_dir, None, rw, '.nii.gz', lor)                    # warm-up
+        t = wall(lambda: ev.compute_metrics_on_folder(ref_dir, pred_dir, os.path.join(pred_dir, 'summary.json'), rw, '.nii.gz', lor), reps)
+        row(f'compute_metrics_on_folder, {cases} cases (reader thread)', t[:3], f'  {t[0] / cases:.1f} ms per case')
+        pair = [os.path.join(ref_dir, 'case0.nii.gz'), os.path.join(pred_dir, 'case0.nii.gz')]
+        staged = rw.stage_label_files(pair)
+        row('  one case, inflate: both files into pinned memory (host)', wall(staged.fill, reps)[:3])
+        raws = [torch.empty(h.n_bytes, dtype=torch.uint8, device=dev) for h in staged.hdrs]
+        outs = [torch.empty(h.shape, dtype=torch.uint8 if h.bytes_per_voxel == 1 else torch.int16, device=dev) for h in staged.hdrs]
+        total = sum(h.n_bytes for h in staged.hdrs)
+        tu = events(lambda: [r.copy_(b[:h.n_bytes], non_blocking=True) for r, b, h in zip(raws, staged.buffers, staged.hdrs)], reps, dev)
+        row(f'  one case, upload: both files ({total / 2 ** 20:.0f} MiB, pinned)', tu, f'  {total / tu[0] / 1e6:.1f} GB/s')
+        td = events(lambda: [capi.decode_labels(r.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter,
+                                                fio.label_bytes(h), o.data_ptr(), status.data_ptr(), stream)
+                             for r, o, h in zip(raws, outs, staged.hdrs)], reps, dev)
+        row('  one case, decode: fnn_decode_labels on both', td)
+        values = ev.count_classes(lor)
+        tcnt = wall(lambda: ev.confusion_counts(outs[0], [outs[1]], values, None, checked=True), reps)
+        row('  one case, count: confusion_counts (uint8 against 2-byte: the reference map is widened first)', tcnt[:3])
+        narrow = outs[1].to(torch.uint8)
+        tcn = wall(lambda: ev.confusion_counts(outs[0], [narrow], values, None, checked=True), reps)
+        row('  one case, count: confusion_counts after the narrowing read_label_map does (uint8 against uint8)', tcn[:3])
+        row('  one case, decode_label_maps (upload, decode, status, narrowing)', wall(lambda: rw.decode_label_maps(staged), reps)[:3])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
@@ -238,7 +341,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -260,6 +363,10 @@ def main():
     def row(name, t, extra=''):
         say(f'{name:<66s}: {t[0]:9.2f} ms  (min {t[1]:.2f} max {t[2]:.2f}){extra}')
 
+    if a.section == 'label_files':
+        bench_label_files(n, a.reps, a.cases, dev, say, row)
+        write_out(a.out or os.path.join(ROOT, 'profiles', 'r21_label_files.txt'), lines)
+        return
     if a.section in ('reorient', 'deflate', 'masks'):
         {'reorient': bench_reorient, 'deflate': bench_deflate, 'masks': bench_masks}[a.section](n, a.reps, dev, say, row)
         write_out(a.out, lines)
