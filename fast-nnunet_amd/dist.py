@@ -30,6 +30,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .case_pipeline import as_plain_labels
+from .plans import label_rule
+
 Box = Tuple[Tuple[int, int, int], Tuple[int, int, int]]          # (lo, hi) in padded-volume coordinates
 
 
@@ -675,7 +678,7 @@ class ShardedPredictor:
         p = self.p
         p._check_input(data)
         eng = p._engine
-        order, u16 = p._label_rule()
+        order, u16 = label_rule(p.label_manager)
         with torch.cuda.device(p.device):
             x = data.to(device=p.device, dtype=torch.float32).contiguous()
             eng.set_label_rule(order, uint16=u16)
@@ -708,6 +711,4 @@ class ShardedPredictor:
                 gather_owned_boxes(labels, owns, self.rank, self.group)
                 if self.phases is not None:
                     self.phases['assemble_all_gather_ms'] += (self._tick() - t0) * 1e3
-            if u16:
-                labels = labels.to(torch.int32) & 0xffff
-        return labels
+        return as_plain_labels(labels)

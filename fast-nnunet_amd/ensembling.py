@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from . import capi
+from .case_pipeline import as_plain_labels, export_case_files, labels_for_writer, run_pipeline
+from .plans import label_rule
 from .predictor import nnUNetPredictor
 
 MAX_MEMBERS = 16
@@ -39,15 +41,6 @@ def _load_member(f) -> np.ndarray:
     if a.dtype not in (np.float32, np.float16):
         raise ValueError(f'probabilities must be float32 or float16, got {a.dtype}')
     return a
-
-
-def _label_rule(label_manager):
-    order = None
-    if label_manager.has_regions:
-        assert label_manager.regions_class_order is not None, \
-            'if region-based training is requested then you need to define regions_class_order!'
-        order = [int(c) for c in label_manager.regions_class_order]
-    return order, len(label_manager.foreground_labels) >= 255
 
 
 def _average_on_device(list_of_files_or_arrays, order, u16: bool, want_average: bool, device):
@@ -93,7 +86,7 @@ def ensemble_probabilities(list_of_files_or_arrays: List[Union[str, np.ndarray]]
     """``merge_files`` (ensemble.py:31-44) without the image writer: -> label map (uint8, or uint16 with 255 or more
     foreground labels), and ``(labels, average)`` with ``return_probabilities``.  For region-based training the
     reference applies the sigmoid to the averaged probabilities again before ``> 0.5``; so does this."""
-    order, u16 = _label_rule(label_manager)
+    order, u16 = label_rule(label_manager)
     avg, labels = _average_on_device(list_of_files_or_arrays, order, u16, return_probabilities, device)
     labels = labels.cpu().numpy().view(np.uint16) if u16 else labels.cpu().numpy()
     return (labels, avg.cpu().numpy()) if return_probabilities else labels
@@ -170,7 +163,7 @@ class nnUNetEnsemblePredictor(object):
             del data
             resident.append(pp.resample_logits_to_cropped_shape(logits, p.plans_manager, p.configuration_manager, props))
             del logits
-        order, u16 = _label_rule(self.label_manager)
+        order, u16 = label_rule(self.label_manager)
         before = [int(i) for i in props0['shape_before_cropping']]
         tb = [int(i) for i in self.plans_manager.transpose_backward]
         grid = [before[j] for j in tb]
@@ -184,9 +177,7 @@ class nnUNetEnsemblePredictor(object):
                                  None if avg is None else avg.data_ptr(), labels.data_ptr(), u16,
                                  torch.cuda.current_stream(self.device).cuda_stream)
             del resident
-            if u16:
-                labels = labels.to(torch.int32) & 0xffff
-        out = nnUNetPredictor._labels_to_host(self, labels, u16)
+        out = nnUNetPredictor._labels_out(self, as_plain_labels(labels), props0, for_file=False)
         if save_or_return_probabilities:
             return out, avg.cpu().numpy()
         return out
@@ -247,29 +238,9 @@ def load_properties_pkl(path_or_bytes) -> dict:
     return _PropertiesUnpickler(io.BytesIO(data)).load()
 
 
-def _write_merged(image_reader_writer, seg, avg, properties, output_filename_truncated: str, output_file_ending: str):
-    """Host only: the merged case's files, each under its name only when it is complete."""
-    made = []
-    try:
-        if avg is not None:
-            for ending, dump in (('.npz', lambda f: np.savez_compressed(f, probabilities=avg)),
-                                 ('.pkl', lambda f: pickle.dump(properties, f))):
-                tmp = f'{output_filename_truncated}{ending}.part{os.getpid()}'
-                made.append(tmp)
-                with open(tmp, 'wb') as f:
-                    dump(f)
-                os.replace(tmp, output_filename_truncated + ending)
-        image_reader_writer.write_seg(seg, output_filename_truncated + output_file_ending, properties)
-    finally:
-        for tmp in made:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-
-
 def _merge_on_device(members, properties, image_reader_writer, label_manager, save_probabilities: bool):
     """The GPU part of ``merge_files`` -> (what the writer takes as the label map, the average on the host or None)."""
-    from .label_folders import labels_for_writer
-    order, u16 = _label_rule(label_manager)
+    order, u16 = label_rule(label_manager)
     avg, labels = _average_on_device(members, order, u16, save_probabilities, None)
     if labels.ndim != 3:
         raise ValueError(f'probabilities of shape {tuple(avg.shape) if avg is not None else labels.shape}: the label file needs (c, z, y, x)')
@@ -286,7 +257,8 @@ def merge_files(list_of_files: Sequence[str], output_filename_truncated: str, ou
     list_of_files = [str(f) for f in list_of_files]
     properties = load_properties_pkl(list_of_files[0][:-4] + '.pkl')
     seg, avg = _merge_on_device(list_of_files, properties, image_reader_writer, label_manager, save_probabilities)
-    _write_merged(image_reader_writer, seg, avg, properties, output_filename_truncated, output_file_ending)
+    export_case_files(output_filename_truncated, avg, properties, lambda: image_reader_writer.write_seg(
+        seg, output_filename_truncated + output_file_ending, properties))
 
 
 @torch.inference_mode()
@@ -296,18 +268,9 @@ def ensemble_folders(list_of_input_folders: List[str], output_folder: str, save_
     taken.  The members are the folders' ``.npz`` files and every folder must hold the same set.  A reader thread loads the
     next case's members and a writer thread writes the previous case's files while the calling thread averages this one on
     the device; ``num_processes`` is accepted and ignored."""
-    from .imageio import prediction_reader_writer_class
-    from .label_folders import load_json, run_pipeline, subfiles
-    from .plans import PlansManager
-    if dataset_json_file_or_dict is not None:
-        dataset_json = load_json(dataset_json_file_or_dict) if isinstance(dataset_json_file_or_dict, str) else dataset_json_file_or_dict
-    else:
-        dataset_json = load_json(os.path.join(list_of_input_folders[0], 'dataset.json'))
-    if plans_json_file_or_dict is not None:
-        plans = load_json(plans_json_file_or_dict) if isinstance(plans_json_file_or_dict, str) else plans_json_file_or_dict
-    else:
-        plans = load_json(os.path.join(list_of_input_folders[0], 'plans.json'))
-    plans_manager = PlansManager(plans)
+    from .label_folders import folder_plans_and_dataset, subfiles
+    plans_manager, dataset_json, rw = folder_plans_and_dataset(list_of_input_folders[0], plans_json_file_or_dict,
+                                                               dataset_json_file_or_dict)
     files_per_folder = [set(subfiles(i, suffix='.npz', join=False)) for i in list_of_input_folders]
     s = set(files_per_folder[0])
     for f in files_per_folder[1:]:
@@ -318,7 +281,6 @@ def ensemble_folders(list_of_input_folders: List[str], output_folder: str, save_
     names = sorted(s)
     lists_of_lists_of_files = [[os.path.join(fl, fi) for fl in list_of_input_folders] for fi in names]
     output_files_truncated = [os.path.join(output_folder, fi[:-4]) for fi in names]
-    rw = prediction_reader_writer_class(plans_manager, dataset_json)()
     label_manager = plans_manager.get_label_manager(dataset_json)
     os.makedirs(output_folder, exist_ok=True)
     shutil.copy(os.path.join(list_of_input_folders[0], 'dataset.json'), output_folder)
@@ -331,6 +293,7 @@ def ensemble_folders(list_of_input_folders: List[str], output_folder: str, save_
     def run(i, data):
         members, properties = data
         seg, avg = _merge_on_device(members, properties, rw, label_manager, save_merged_probabilities)
-        return None, (lambda: _write_merged(rw, seg, avg, properties, output_files_truncated[i], ending))
+        return None, (lambda: export_case_files(output_files_truncated[i], avg, properties, lambda: rw.write_seg(
+            seg, output_files_truncated[i] + ending, properties)))
 
     run_pipeline(len(names), stage, run, write_thread=True)

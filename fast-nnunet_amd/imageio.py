@@ -501,24 +501,30 @@ class NiftiIO:
         """-> (the device label map in its file's frame, the affine its header takes)."""
         return seg, _affine_of(properties)
 
-    def compress_labels(self, seg, properties: dict) -> 'DeviceCompressedLabels':
-        """A device label map (z, y, x; uint8, or the two-byte int16 / uint16) -> the deflate fragment of its voxels as the
-        ``.nii.gz`` file holds them, made by ``fnn_deflate_labels`` on the current stream: what comes back from the device
-        is the fragment, not the map.  The file type is ``_label_voxels``' (uint16 from a maximum of 255 on).  ``write_seg``
-        takes the result.  Synchronises."""
+    def _compressible(self, seg, properties: dict, caller: str, host_route: str):
+        """What both compress methods do first: the checks, then -> (the device label map in its file's frame, contiguous
+        and 16-byte aligned; the affine its header takes)."""
         import torch
         if not hasattr(seg, 'data_ptr') or seg.device.type != 'cuda':
-            raise TypeError('compress_labels takes a label map on the GPU (arrays on the host go to write_seg as they are)')
+            raise TypeError(f'{caller} takes a label map on the GPU ({host_route} go to write_seg as they are)')
         assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
         if seg.dtype not in (torch.uint8, torch.int16, torch.uint16):
             raise NotImplementedError(f'label maps of {seg.dtype} are not compressed on the device (uint8, int16 and uint16 are)')
         with torch.cuda.device(seg.device):
             seg, affine = self._file_frame_on_device(seg, properties)
             seg = seg.contiguous()
+            return (seg.clone() if seg.data_ptr() % 16 else seg), affine
+
+    def compress_labels(self, seg, properties: dict) -> 'DeviceCompressedLabels':
+        """A device label map (z, y, x; uint8, or the two-byte int16 / uint16) -> the deflate fragment of its voxels as the
+        ``.nii.gz`` file holds them, made by ``fnn_deflate_labels`` on the current stream: what comes back from the device
+        is the fragment, not the map.  The file type is ``_label_voxels``' (uint16 from a maximum of 255 on).  ``write_seg``
+        takes the result.  Synchronises."""
+        import torch
+        seg, affine = self._compressible(seg, properties, 'compress_labels', 'arrays on the host')
+        with torch.cuda.device(seg.device):
             if seg.element_size() == 1 and seg.numel() > 0 and int(seg.max()) >= 255:
-                seg = seg.to(torch.int16)                        # (a uint8 map that holds 255 is a uint16 file)
-            if seg.data_ptr() % 16:
-                seg = seg.clone()
+                seg = seg.to(torch.int16)                        # (a uint8 map that holds 255 is a uint16 file; a new, aligned tensor)
             n, size = seg.numel(), seg.element_size()
             cap = capi.deflate_bound(n * size)
             out = torch.empty(max(cap, 16), dtype=torch.uint8, device=seg.device)
@@ -534,19 +540,11 @@ class NiftiIO:
         them into one buffer of exactly that size, and that buffer is what comes back from the device - neither the map nor
         a mask is downloaded.  ``write_seg`` takes each result.  Synchronises."""
         import torch
-        if not hasattr(seg, 'data_ptr') or seg.device.type != 'cuda':
-            raise TypeError('compress_label_masks takes a label map on the GPU (masks of a host array go to write_seg as they are)')
-        assert seg.ndim == 3, 'segmentation must be 3d (z, y, x)'
-        if seg.dtype not in (torch.uint8, torch.int16, torch.uint16):
-            raise NotImplementedError(f'label maps of {seg.dtype} are not compressed on the device (uint8, int16 and uint16 are)')
         labels = [int(i) for i in labels]
+        seg, affine = self._compressible(seg, properties, 'compress_label_masks', 'masks of a host array')
         if not labels:
             return []
         with torch.cuda.device(seg.device):
-            seg, affine = self._file_frame_on_device(seg, properties)
-            seg = seg.contiguous()
-            if seg.data_ptr() % 16:
-                seg = seg.clone()
             n, size, shape = seg.numel(), seg.element_size(), tuple(seg.shape)
             stream = torch.cuda.current_stream(seg.device).cuda_stream
             work_cap = capi.deflate_masks_work_bytes(n, len(labels))
@@ -941,21 +939,25 @@ class NiftiReorientIO(NiftiIO):
             images.append(reorient_on_host(decode_on_host(h, raw), o.src_axis, o.flip)[None])
         return np.vstack(images), self._properties(orients[0])
 
-    def labels_to_file_frame(self, seg, properties: dict) -> FileFrameLabels:
-        """A RAS-frame label map (z, y, x) -> its file's frame with the restored affine.  A device tensor (uint8, or the
-        two-byte int16 / uint16) is reoriented by ``fnn_reorient`` on the current stream and then downloaded; a numpy array
-        is reoriented by numpy and no GPU call is made."""
+    @staticmethod
+    def _restore(seg, properties: dict):
+        """``restore_orientation`` for the RAS-frame map ``seg``; warns, as the reference, when the restored affine is not the file's."""
         src_axis, flip, restored = restore_orientation(properties, tuple(seg.shape))
         original = np.asarray(properties['nibabel_stuff']['original_affine'], dtype=np.float64)
         if not np.allclose(original, restored):
             warnings.warn(f'Restored affine does not match original affine.\nOriginal affine\n{original}\n'
                           f'Restored affine\n{restored}')
-        if not hasattr(seg, 'data_ptr'):
-            return FileFrameLabels(reorient_on_host(np.asarray(seg), src_axis, flip), restored)
-        import torch
-        if seg.device.type != 'cuda':
-            return FileFrameLabels(reorient_on_host(seg.numpy(), src_axis, flip), restored)
-        return FileFrameLabels(self._reorient_on_device(seg, src_axis, flip).cpu().numpy(), restored)
+        return src_axis, flip, restored
+
+    def labels_to_file_frame(self, seg, properties: dict) -> FileFrameLabels:
+        """A RAS-frame label map (z, y, x) -> its file's frame with the restored affine.  A device tensor (uint8, or the
+        two-byte int16 / uint16) is reoriented by ``fnn_reorient`` on the current stream and then downloaded; a numpy array
+        is reoriented by numpy and no GPU call is made."""
+        if hasattr(seg, 'data_ptr') and seg.device.type == 'cuda':
+            seg, restored = self._file_frame_on_device(seg, properties)
+            return FileFrameLabels(seg.cpu().numpy(), restored)
+        src_axis, flip, restored = self._restore(seg, properties)
+        return FileFrameLabels(reorient_on_host(seg.numpy() if hasattr(seg, 'data_ptr') else np.asarray(seg), src_axis, flip), restored)
 
     @staticmethod
     def _reorient_on_device(seg, src_axis, flip):
@@ -975,11 +977,7 @@ class NiftiReorientIO(NiftiIO):
     def _file_frame_on_device(self, seg, properties: dict):
         """The RAS-frame device label map brought to its file's frame by ``fnn_reorient``, and the restored affine: what
         ``compress_labels`` then compresses."""
-        src_axis, flip, restored = restore_orientation(properties, tuple(seg.shape))
-        original = np.asarray(properties['nibabel_stuff']['original_affine'], dtype=np.float64)
-        if not np.allclose(original, restored):
-            warnings.warn(f'Restored affine does not match original affine.\nOriginal affine\n{original}\n'
-                          f'Restored affine\n{restored}')
+        src_axis, flip, restored = self._restore(seg, properties)
         return self._reorient_on_device(seg, src_axis, flip), restored
 
     def write_seg(self, seg, output_fname: str, properties: dict) -> None:

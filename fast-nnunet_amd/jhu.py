@@ -23,8 +23,8 @@ import os
 from typing import List, Tuple
 
 import numpy as np
-import torch
 
+from .case_pipeline import device_compressor
 from .predictor import nnUNetPredictor
 
 
@@ -44,23 +44,14 @@ class JHUPredictor(nnUNetPredictor):
                                       'region-based datasets are not served (neither by the reference\'s export)')
         super()._build_engine()
 
-    def _masks_on_device(self, rw) -> bool:
-        return self.compress_on_device and hasattr(rw, 'compress_label_masks') \
-            and str(self.dataset_json['file_ending']).lower().endswith('.nii.gz')
+    def _label_files(self, rw):
+        """One mask file per foreground label: on the device route ``labels_for_writer`` makes the list of compressed masks
+        (else the label map, as ``nnUNetPredictor`` hands it over) and ``_write_masks`` writes either."""
+        masks = device_compressor(rw, self.compress_on_device, self.dataset_json['file_ending'], 'compress_label_masks')
+        labels = list(self.label_manager.foreground_labels)
+        return (None if masks is None else lambda seg, props: masks(seg, labels, props)), self._write_masks
 
-    def _labels_out(self, labels: torch.Tensor, u16: bool, props: dict, for_file: bool):
-        """As ``nnUNetPredictor._labels_out`` (the label map on the host, in the file's frame where the reader-writer
-        reorients); on the device route the list of compressed masks, one per foreground label."""
-        rw = self._reader_writer() if for_file else None
-        if rw is None or not self._masks_on_device(rw):
-            return super()._labels_out(labels, u16, props, for_file)     # (which compresses under the same condition only)
-        if self._postprocessing is not None:
-            from .postprocessing import apply_postprocessing
-            labels = apply_postprocessing(labels, *self._postprocessing)
-        labels = labels.to(torch.int16) if u16 else labels.to(torch.uint8)
-        return rw.compress_label_masks(labels, list(self.label_manager.foreground_labels), props)
-
-    def _write_label_files(self, seg, props: dict, output_file_truncated: str):
+    def _write_masks(self, seg, props: dict, output_file_truncated: str):
         """Host only: the writer thread's part.  ``seg``: the list ``compress_label_masks`` made, or the label map (a numpy
         array in the frame ``write_seg`` expects, or ``FileFrameLabels``)."""
         from .imageio import FileFrameLabels

@@ -211,6 +211,17 @@ class LabelManager:
         return len(self.foreground_regions) if self.has_regions else len(self.all_labels)
 
 
+def label_rule(label_manager: LabelManager) -> Tuple[Optional[List[int]], bool]:
+    """(regions_class_order or None, uint16?) - LabelManager.convert_logits_to_segmentation
+    (label_handling.py:163-181) and the dtype rule of export_prediction.py:45-46."""
+    order = None
+    if label_manager.has_regions:
+        assert label_manager.regions_class_order is not None, \
+            'if region-based training is requested then you need to define regions_class_order!'
+        order = [int(c) for c in label_manager.regions_class_order]
+    return order, len(label_manager.foreground_labels) >= 255
+
+
 class PlansManager:
     def __init__(self, plans_file_or_dict: Union[str, dict]):
         if isinstance(plans_file_or_dict, dict):

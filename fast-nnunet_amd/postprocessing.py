@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import capi
+from .case_pipeline import as_plain_labels, labels_for_writer
 
 REFERENCE_NAME = ('nnunetv2.postprocessing.remove_connected_components',
                   'remove_all_but_largest_component_from_segmentation')
@@ -114,7 +115,7 @@ def _device_postprocess(seg: torch.Tensor, groups, backgrounds) -> torch.Tensor:
     _run_passes(work3, u16, groups, backgrounds)
     if not u16:
         return work
-    return (work.to(torch.int32) & 0xffff).to(seg.dtype)
+    return as_plain_labels(work).to(seg.dtype)
 
 
 def _device() -> torch.device:
@@ -225,9 +226,8 @@ def determine_postprocessing(predictions, references, dataset_json_or_label_mana
 # ---- label files ---------------------------------------------------------------------------------------------------------
 def _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress_on_device: bool):
     """The GPU part of one file: decoded labels -> what ``rw.write_seg`` takes on a thread that makes no GPU call."""
-    from .label_folders import as_plain_labels, labels_for_writer
     seg = apply_postprocessing(as_plain_labels(labels), pp_fns, pp_fn_kwargs)
-    return labels_for_writer(rw, seg, props, compress_on_device)
+    return labels_for_writer(rw, seg, props, compress=rw.compress_labels if compress_on_device else None)
 
 
 def load_postprocess_save(segmentation_file: str, output_fname: str, image_reader_writer, pp_fns: Sequence[Callable],
@@ -262,26 +262,14 @@ def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns
     """``apply_postprocessing_to_folder`` (remove_connected_components.py:247-294).  If plans_file_or_dict or
     dataset_json_file_or_dict are None, they are looked for in input_folder.  ``num_processes`` is accepted and ignored;
     ``compress_on_device`` writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded)."""
-    from .imageio import prediction_reader_writer_class
-    from .label_folders import load_json, subfiles
-    from .plans import PlansManager
-    if plans_file_or_dict is None:
-        expected_plans_file = os.path.join(input_folder, 'plans.json')
-        if not os.path.isfile(expected_plans_file):
-            raise RuntimeError(f'Expected plans file missing: {expected_plans_file}. The plans file should have been '
-                               f'created while running nnUNetv2_predict. Sadge. If the folder you want to apply '
-                               f'postprocessing to was create from an ensemble then just specify one of the '
-                               f'plans files of the ensemble members in plans_file_or_dict')
-        plans_file_or_dict = load_json(expected_plans_file)
-    plans_manager = PlansManager(plans_file_or_dict)
-    if dataset_json_file_or_dict is None:
-        expected_dataset_json_file = os.path.join(input_folder, 'dataset.json')
-        if not os.path.isfile(expected_dataset_json_file):
-            raise RuntimeError(f'Expected plans file missing: {expected_dataset_json_file}. The dataset.json should have been '
-                               f'copied while running nnUNetv2_predict/nnUNetv2_ensemble. Sadge.')
-        dataset_json_file_or_dict = load_json(expected_dataset_json_file)
-    dataset_json = dataset_json_file_or_dict if isinstance(dataset_json_file_or_dict, dict) else load_json(dataset_json_file_or_dict)
-    rw = prediction_reader_writer_class(plans_manager, dataset_json)()
+    from .label_folders import folder_plans_and_dataset, subfiles
+    _, dataset_json, rw = folder_plans_and_dataset(
+        input_folder, plans_file_or_dict, dataset_json_file_or_dict,
+        'Expected plans file missing: {}. The plans file should have been created while running nnUNetv2_predict. Sadge. '
+        'If the folder you want to apply postprocessing to was create from an ensemble then just specify one of the '
+        'plans files of the ensemble members in plans_file_or_dict',
+        'Expected plans file missing: {}. The dataset.json should have been copied while running '
+        'nnUNetv2_predict/nnUNetv2_ensemble. Sadge.')
     os.makedirs(output_folder, exist_ok=True)
     files = subfiles(input_folder, suffix=dataset_json['file_ending'], join=False)
     apply_postprocessing_to_files([os.path.join(input_folder, i) for i in files], [os.path.join(output_folder, i) for i in files],

@@ -30,6 +30,7 @@ import torch
 
 from . import evaluation as ev
 from . import postprocessing as pp
+from .case_pipeline import HostWorker, as_plain_labels
 from .plans import LabelManager
 
 
@@ -333,7 +334,7 @@ def _search(predictions, references, dataset_json_or_label_manager, verbose: boo
 class FolderBackend(DeviceBackend):
     """``DeviceBackend`` for sources that are label files (``LabelFile``) or deflated maps (``PackedLabels``): ``put`` reads a
     file as labels on the device (``decode_label_maps``); ``begin_pass`` tells it the order in which a pass over the cases
-    will ask, so that one ``_HostWorker`` inflates the files of the next case into the other slot of pinned buffers while
+    will ask, so that one ``HostWorker`` inflates the files of the next case into the other slot of pinned buffers while
     this one runs; ``host`` deflates what the search keeps between steps.  One case is on the device at a time and the
     folder is never in host memory as a whole.  Used as a context manager: the reader thread lives inside the ``with``."""
 
@@ -344,8 +345,7 @@ class FolderBackend(DeviceBackend):
         self.plan, self.at, self.job, self.ready = [], 0, None, {}
 
     def __enter__(self):
-        from .predictor import _HostWorker
-        self.reader = _HostWorker('fnn-reader')
+        self.reader = HostWorker('fnn-reader')
         return self
 
     def __exit__(self, *exc):
@@ -379,7 +379,6 @@ class FolderBackend(DeviceBackend):
 
     def put(self, seg):
         if isinstance(seg, LabelFile):
-            from .label_folders import as_plain_labels
             return as_plain_labels(self._read(seg.fname))
         if isinstance(seg, PackedLabels):
             seg = seg.array()
@@ -399,24 +398,10 @@ def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str,
     False - ``postprocessed/<files>`` with ``postprocessed/summary.json``; no ``temp`` folder is made.  Plans or
     dataset.json given as None are looked for in ``folder_predictions``.  ``num_processes`` is accepted and ignored.
     Returns ``(pp_fns, pp_fn_kwargs)``."""
-    from .imageio import prediction_reader_writer_class
-    from .label_folders import load_json, subfiles
-    from .plans import PlansManager
-    if plans_file_or_dict is None:
-        expected_plans_file = os.path.join(folder_predictions, 'plans.json')
-        if not os.path.isfile(expected_plans_file):
-            raise RuntimeError(f'Expected plans file missing: {expected_plans_file}. The plans files should have been '
-                               f'created while running nnUNetv2_predict. Sadge.')
-        plans_file_or_dict = load_json(expected_plans_file)
-    plans_manager = PlansManager(plans_file_or_dict)
-    if dataset_json_file_or_dict is None:
-        expected_dataset_json_file = os.path.join(folder_predictions, 'dataset.json')
-        if not os.path.isfile(expected_dataset_json_file):
-            raise RuntimeError(f'Expected plans file missing: {expected_dataset_json_file}. The plans files should have been '
-                               f'created while running nnUNetv2_predict. Sadge.')
-        dataset_json_file_or_dict = load_json(expected_dataset_json_file)
-    dataset_json = dataset_json_file_or_dict if isinstance(dataset_json_file_or_dict, dict) else load_json(dataset_json_file_or_dict)
-    rw = prediction_reader_writer_class(plans_manager, dataset_json)()
+    from .label_folders import folder_plans_and_dataset, subfiles
+    missing = 'Expected plans file missing: {}. The plans files should have been created while running nnUNetv2_predict. Sadge.'
+    plans_manager, dataset_json, rw = folder_plans_and_dataset(folder_predictions, plans_file_or_dict,
+                                                               dataset_json_file_or_dict, missing, missing)
     ending = dataset_json['file_ending']
     predicted_files = subfiles(folder_predictions, suffix=ending, join=False)
     ref_files = subfiles(folder_ref, suffix=ending, join=False)

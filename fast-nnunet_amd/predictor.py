@@ -18,8 +18,6 @@ from __future__ import annotations
 
 import itertools
 import os
-import pickle
-import threading
 from copy import deepcopy
 from typing import List, Optional, Tuple, Union
 
@@ -28,14 +26,10 @@ import torch
 
 from . import capi
 from .arch import ArchSpec, check_against_plans, ops_from_plans, spec_from_state_dict, weight_blob
-from .plans import ConfigurationManager, PlansManager, determine_num_input_channels
+from .case_pipeline import as_plain_labels, device_compressor, export_case_files, labels_for_writer, run_pipeline
+from .label_folders import load_json
+from .plans import ConfigurationManager, PlansManager, determine_num_input_channels, label_rule
 from .sliding_window import compute_gaussian, compute_steps_for_sliding_window
-
-
-def _load_json(path):
-    import json
-    with open(path) as f:
-        return json.load(f)
 
 
 class nnUNetPredictor(object):
@@ -108,8 +102,8 @@ class nnUNetPredictor(object):
         """Model folder -> plans, dataset.json, per-fold weights (:67-129)."""
         if use_folds is None:
             use_folds = nnUNetPredictor.auto_detect_available_folds(model_training_output_dir, checkpoint_name)
-        dataset_json = _load_json(os.path.join(model_training_output_dir, 'dataset.json'))
-        plans_manager = PlansManager(_load_json(os.path.join(model_training_output_dir, 'plans.json')))
+        dataset_json = load_json(os.path.join(model_training_output_dir, 'dataset.json'))
+        plans_manager = PlansManager(load_json(os.path.join(model_training_output_dir, 'plans.json')))
         if isinstance(use_folds, (str, int)):
             use_folds = [use_folds]
         parameters, trainer_name, configuration_name, mirror_axes, init_args = [], None, None, None, {}
@@ -169,34 +163,16 @@ class nnUNetPredictor(object):
                 raise ValueError('postprocessing: as many kwargs as functions expected')
             self._postprocessing = (list(pp_fns), [dict(k) for k in pp_fn_kwargs])
 
-    def _labels_to_host(self, labels: torch.Tensor, u16: bool) -> np.ndarray:
+    def _labels_out(self, labels: torch.Tensor, props: dict, for_file: bool):
+        """The labels of a case as they leave the device: postprocessed (in the frame of the image as it was read), then
+        ``labels_for_writer`` in the label manager's width - the host array, or when they are bound for a file whatever the
+        reader-writer's ``write_seg`` takes without a GPU call (``_label_files`` says whether that is compressed here)."""
         if self._postprocessing is not None:
             from .postprocessing import apply_postprocessing
             labels = apply_postprocessing(labels, *self._postprocessing)
-        return labels.cpu().numpy().astype(np.uint16 if u16 else np.uint8)
-
-    def _labels_out(self, labels: torch.Tensor, u16: bool, props: dict, for_file: bool):
-        """The labels of a case on the host.  When they are bound for a file and the reader-writer reorients, they are brought
-        to the file's frame on the device first (after the postprocessing, which sees the RAS frame) and come back as the
-        ``FileFrameLabels`` its ``write_seg`` takes: the writer thread does no strided copy.  With ``compress_on_device``
-        and a ``.nii.gz`` target they are also compressed here, on the calling thread, and come back as the
-        ``DeviceCompressedLabels`` that ``write_seg`` only assembles: the label map itself is never downloaded."""
         rw = self._reader_writer() if for_file else None
-        if rw is not None and self.compress_on_device and hasattr(rw, 'compress_labels') \
-                and str(self.dataset_json['file_ending']).lower().endswith('.nii.gz'):
-            if self._postprocessing is not None:
-                from .postprocessing import apply_postprocessing
-                labels = apply_postprocessing(labels, *self._postprocessing)
-            return rw.compress_labels(labels.to(torch.int16) if u16 else labels.to(torch.uint8), props)
-        if rw is None or not hasattr(rw, 'labels_to_file_frame'):
-            return self._labels_to_host(labels, u16)
-        if self._postprocessing is not None:
-            from .postprocessing import apply_postprocessing
-            labels = apply_postprocessing(labels, *self._postprocessing)
-        labels = labels.to(torch.int16) if u16 else labels.to(torch.uint8)       # (int16: the two bytes of the uint16 file type)
-        out = rw.labels_to_file_frame(labels, props)
-        out.voxels = out.voxels.view(np.uint16) if u16 else out.voxels
-        return out
+        return labels_for_writer(rw, labels, props, label_rule(self.label_manager)[1],
+                                 self._label_files(rw)[0] if for_file else None)
 
     @staticmethod
     def auto_detect_available_folds(model_training_output_dir, checkpoint_name):
@@ -351,22 +327,21 @@ class nnUNetPredictor(object):
         pp, data, props = self._preprocess_case(input_image, image_properties, segmentation_previous_stage)
         if self.verbose:
             print('predicting')
-        u16 = len(self.label_manager.foreground_labels) >= 255
         same_grid = tuple(data.shape[1:]) == tuple(props['shape_after_cropping_and_before_resampling'])
         if same_grid and not save_or_return_probabilities:
             seg = self.predict_segmentation_from_preprocessed_data(data)
             out = pp.revert_labels(seg, props, self.plans_manager, self.label_manager)
-            return self._labels_out(out, u16, props, for_file), None, props
+            return self._labels_out(out, props, for_file), None, props
         logits = self._predict_case_logits(data)
         if self.verbose:
             print('resampling to original shape')
         if save_or_return_probabilities:
             out, probs = pp.convert_predicted_logits_to_segmentation_and_probabilities(
                 logits, self, self.plans_manager, self.configuration_manager, props)
-            return self._labels_out(out, u16, props, for_file), probs.cpu().numpy(), props
+            return self._labels_out(out, props, for_file), probs.cpu().numpy(), props
         out = pp.convert_predicted_logits_to_segmentation_with_correct_shape(logits, self, self.plans_manager,
                                                                              self.configuration_manager, props)
-        return self._labels_out(out, u16, props, for_file), None, props
+        return self._labels_out(out, props, for_file), None, props
 
     def _preprocess_case(self, input_image: np.ndarray, image_properties: dict, segmentation_previous_stage=None):
         """-> (DevicePreprocessor, network input on the device, properties) for predict_single_npy_array."""
@@ -397,17 +372,6 @@ class nnUNetPredictor(object):
             self._engine.predict_volume(data.data_ptr(), data.shape, self._opts(), logits.data_ptr(), n_folds=self._n_folds)
         return logits
 
-    def _label_rule(self):
-        """(regions_class_order or None, uint16?) - LabelManager.convert_logits_to_segmentation
-        (label_handling.py:163-181) and the dtype rule of export_prediction.py:45-46."""
-        lm = self.label_manager
-        order = None
-        if lm.has_regions:
-            assert lm.regions_class_order is not None, \
-                'if region-based training is requested then you need to define regions_class_order!'
-            order = [int(c) for c in lm.regions_class_order]
-        return order, len(lm.foreground_labels) >= 255
-
     def predict_segmentation_from_preprocessed_data(self, data: torch.Tensor) -> torch.Tensor:
         """Label map on the device, skipping the full-logit D2H copy the reference pays at :386 before
         ``convert_logits_to_segmentation`` (label_handling.py:144-195): argmax for plain labels, sigmoid > 0.5
@@ -415,22 +379,20 @@ class nnUNetPredictor(object):
         has no uint16 arithmetic) when the dataset has >= 255 foreground labels (export_prediction.py:45-46).
         With one fold the labels are taken straight from the accumulators; the logits are never written."""
         self._check_input(data)
-        order, u16 = self._label_rule()
+        order, u16 = label_rule(self.label_manager)
         with torch.cuda.device(self.device):
             x = self._resident_or_host(data)
             self._engine.set_label_rule(order, uint16=u16)
             labels = torch.empty(x.shape[1:], dtype=torch.int16 if u16 else torch.uint8, device=self.device)
             self._engine.predict_labels(x.data_ptr(), x.shape, self._opts(), labels.data_ptr(), n_folds=self._n_folds)
-            if u16:
-                labels = labels.to(torch.int32) & 0xffff
-        return labels
+        return as_plain_labels(labels)
 
     def convert_logits_to_segmentation(self, predicted_logits: torch.Tensor) -> torch.Tensor:
         """``LabelManager.convert_logits_to_segmentation`` (label_handling.py:183-195) on resident logits
         ``[heads, X, Y, Z]`` (fp16 or fp32, on the device)."""
         from . import capi
         assert predicted_logits.ndim == 4 and predicted_logits.shape[0] == self._spec.num_heads
-        order, u16 = self._label_rule()
+        order, u16 = label_rule(self.label_manager)
         with torch.cuda.device(self.device):
             lg = predicted_logits.to(self.device)
             if lg.dtype not in (torch.half, torch.float32):
@@ -441,9 +403,7 @@ class nnUNetPredictor(object):
             self._engine.argmax_labels(lg.data_ptr(), capi.FNN_OUT_F32 if lg.dtype == torch.float32 else capi.FNN_OUT_F16,
                                        lg.shape[0], lg[0].numel(), labels.data_ptr(),
                                        torch.cuda.current_stream(self.device).cuda_stream)
-            if u16:
-                labels = labels.to(torch.int32) & 0xffff
-        return labels
+        return as_plain_labels(labels)
 
     @torch.inference_mode()
     def forward_patches(self, x: torch.Tensor) -> torch.Tensor:
@@ -470,32 +430,19 @@ class nnUNetPredictor(object):
             self._rw = prediction_reader_writer_class(self.plans_manager, self.dataset_json)(self.device)
         return self._rw
 
-    def _export_files(self, seg: np.ndarray, probs: Optional[np.ndarray], props: dict, output_file_truncated: str):
-        """Host only (numpy, zlib, file writes): what the writer thread of ``predict_from_files`` runs.  Every file
-        appears under its name when it is complete."""
-        made = []
-        try:
-            if probs is not None:
-                for ending, dump in (('.npz', lambda f: np.savez_compressed(f, probabilities=probs)),
-                                     ('.pkl', lambda f: pickle.dump(props, f))):
-                    tmp = f'{output_file_truncated}{ending}.part{os.getpid()}'
-                    made.append(tmp)
-                    with open(tmp, 'wb') as f:
-                        dump(f)
-                    os.replace(tmp, output_file_truncated + ending)
-            self._write_label_files(seg, props, output_file_truncated)
-        finally:
-            for tmp in made:
-                if os.path.exists(tmp):
-                    os.remove(tmp)
-
-    def _write_label_files(self, seg, props: dict, output_file_truncated: str):
-        """What ``_labels_out`` made of a case, as the case's label file(s): here the one label map (a subclass writes others)."""
-        self._reader_writer().write_seg(seg, output_file_truncated + self.dataset_json['file_ending'], props)
+    def _label_files(self, rw):
+        """The label file(s) of a case, here the one label map (a subclass makes others) -> ``(compress, write)``: what
+        compresses the device labels on the calling thread (``labels_for_writer``'s ``compress``; None: they are not), and
+        the host-only ``write(seg, props, output_file_truncated)`` that takes what ``_labels_out`` made."""
+        ending = self.dataset_json['file_ending']
+        return (device_compressor(rw, self.compress_on_device, ending),
+                lambda seg, props, truncated: rw.write_seg(seg, truncated + ending, props))
 
     def _export_case(self, seg, probs, props, output_file_truncated):
-        self._reader_writer()                                   # (made by the calling thread)
-        self._export_files(seg, probs, props, output_file_truncated)
+        """Host only (numpy, zlib, file writes) once the reader-writer exists: what the writer thread of
+        ``predict_from_files`` runs."""
+        write = self._label_files(self._reader_writer())[1]
+        export_case_files(output_file_truncated, probs, props, lambda: write(seg, props, output_file_truncated))
 
     def _manage_input_and_output_lists(self, list_of_lists_or_source_folder: Union[str, List[List[str]]],
                                        output_folder_or_list_of_truncated_output_files: Union[None, str, List[str]],
@@ -623,88 +570,23 @@ class nnUNetPredictor(object):
 
     @torch.inference_mode()
     def _predict_cases(self, cases, truncated, prev, save_probabilities, read_thread: bool, write_thread: bool):
-        rw = self._reader_writer()
+        rw = self._reader_writer()                              # (made by the calling thread)
         if truncated is None:
             truncated = [None] * len(cases)
-        ret = []
-        reader = _HostWorker('fnn-reader') if read_thread else None
-        writer = _HostWorker('fnn-writer') if write_thread else None
 
         def stage(i):
             """Headers and pinned buffers on this thread; the bytes on the reader thread (or here)."""
             staged = rw.stage(cases[i], slot=2 * (i % 2))
             staged_prev = rw.stage([prev[i]], slot=2 * (i % 2) + 1) if prev[i] is not None else None
-            fill = (lambda: (staged.fill(), staged_prev.fill() if staged_prev is not None else None))
-            return staged, staged_prev, (reader.submit(fill) if reader is not None else fill())
+            return lambda: (staged.fill(), staged_prev.fill() if staged_prev is not None else None)
 
-        try:
-            nxt = stage(0)
-            pending = None                                       # the writer's job for the previous case
-            for i in range(len(cases)):
-                staged, staged_prev, job = nxt
-                if reader is not None:
-                    job.result()                                 # case i's bytes are in pinned memory (or the read failed)
-                # case i + 1 is read while case i runs; its slot's buffers were released when case i - 1 was decoded
-                nxt = stage(i + 1) if i + 1 < len(cases) else None
-                seg, probs, props = self._run_staged_case(rw, staged, staged_prev, save_probabilities,
-                                                          for_file=truncated[i] is not None)
-                if truncated[i] is None:
-                    ret.append(self._result(seg, probs, save_probabilities))
-                    continue
-                if pending is not None:
-                    pending.result()                             # at most one case waits for the disk
-                export = (lambda a=(seg, probs, props, truncated[i]): self._export_files(*a))
-                pending = writer.submit(export) if writer is not None else export()
-                ret.append(None)
-            if pending is not None:
-                pending.result()
-        finally:
-            for w in (reader, writer):
-                if w is not None:
-                    w.close()
-        return ret
+        def run(i, filled):
+            seg, probs, props = self._run_staged_case(rw, *filled, save_probabilities, for_file=truncated[i] is not None)
+            if truncated[i] is None:
+                return self._result(seg, probs, save_probabilities), None
+            return None, (lambda: self._export_case(seg, probs, props, truncated[i]))
 
-
-class _Job:
-    def __init__(self, fn):
-        self.fn, self.done, self.value, self.error = fn, threading.Event(), None, None
-
-    def result(self):
-        self.done.wait()
-        if self.error is not None:
-            raise self.error
-        return self.value
-
-
-class _HostWorker:
-    """One thread that runs host-only jobs (file reads, zlib, file writes) in order; it never makes a GPU call."""
-
-    def __init__(self, name: str):
-        import queue
-        self.q = queue.Queue()
-        self.t = threading.Thread(target=self._run, name=name, daemon=True)
-        self.t.start()
-
-    def _run(self):
-        while True:
-            job = self.q.get()
-            if job is None:
-                return
-            try:
-                job.value = job.fn()
-            except BaseException as e:                           # handed to the thread that waits for the job
-                job.error = e
-            job.done.set()
-
-    def submit(self, fn) -> _Job:
-        job = _Job(fn)
-        self.q.put(job)
-        return job
-
-    def close(self):
-        """Runs what is queued, then ends the thread."""
-        self.q.put(None)
-        self.t.join()
+        return run_pipeline(len(cases), stage, run, read_thread, write_thread)
 
 
 def get_identifiers_from_splitted_dataset_folder(folder: str, file_ending: str):

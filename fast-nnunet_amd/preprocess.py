@@ -23,6 +23,8 @@ import numpy as np
 import torch
 
 from . import capi
+from .case_pipeline import as_plain_labels
+from .plans import label_rule
 
 _SCHEMES = {'NoNormalization': capi.FNN_NORM_NONE, 'ZScoreNormalization': capi.FNN_NORM_ZSCORE,
             'CTNormalization': capi.FNN_NORM_CT, 'RescaleTo01Normalization': capi.FNN_NORM_RESCALE01,
@@ -288,7 +290,7 @@ class DevicePreprocessor:
             # no resampled logits [heads, *cropped] in between: interpolation and label rule in one pass
             plan = plan_label_export(fn, kw, current_spacing, spacing_transposed, predicted_logits.shape[1:], cropped)
             if plan['path'] in ('fused-default', 'fused-torch'):
-                order, u16 = predictor._label_rule()
+                order, u16 = label_rule(predictor.label_manager)
                 seg = self.resample_logits_to_labels(predicted_logits, cropped, plan['path'] == 'fused-torch',
                                                      plan['separate_axis'], order, u16)
                 return self.revert_labels(seg, properties_dict, plans_manager, predictor.label_manager)
@@ -319,9 +321,7 @@ class DevicePreprocessor:
             capi.resample_labels(lg.data_ptr(), lg.dtype == torch.half, lg.shape, new_shape,
                                  capi.FNN_RESAMPLE_TORCH if torch_family else capi.FNN_RESAMPLE_DEFAULT, separate_axis,
                                  order_ptr, lg.shape[0], labels.data_ptr(), u16, self._stream())
-            if u16:
-                labels = labels.to(torch.int32) & 0xffff
-        return labels
+        return as_plain_labels(labels)
 
     @torch.inference_mode()
     def resample_logits_to_cropped_shape(self, predicted_logits: torch.Tensor, plans_manager, configuration_manager,
@@ -348,7 +348,7 @@ class DevicePreprocessor:
         ``[heads, s0, s1, s2]``), both on the original image grid, both on the device."""
         logits = self.resample_logits_to_cropped_shape(predicted_logits, plans_manager, configuration_manager,
                                                        properties_dict)
-        order, u16 = predictor._label_rule()
+        order, u16 = label_rule(predictor.label_manager)
         with torch.cuda.device(self.device):
             lg = logits.to(self.device)
             if lg.dtype not in (torch.half, torch.float32):
@@ -362,9 +362,7 @@ class DevicePreprocessor:
             capi.export_probabilities(lg.data_ptr(), lg.dtype == torch.half, lg.shape[0], order,
                                       properties_dict['bbox_used_for_cropping'], before, tb, probs.data_ptr(),
                                       labels.data_ptr(), u16, self._stream())
-            if u16:
-                labels = labels.to(torch.int32) & 0xffff
-        return labels, probs
+        return as_plain_labels(labels), probs
 
     @torch.inference_mode()
     def revert_labels(self, segmentation: torch.Tensor, properties: dict, plans_manager, label_manager) -> torch.Tensor:
@@ -378,6 +376,4 @@ class DevicePreprocessor:
             out = torch.empty([before[j] for j in tb], dtype=seg.dtype, device=self.device)
             capi.revert_labels(seg.data_ptr(), u16, properties['bbox_used_for_cropping'], before, tb, out.data_ptr(),
                                self._stream())
-            if u16:
-                out = out.to(torch.int32) & 0xffff
-        return out
+        return as_plain_labels(out)

@@ -224,11 +224,6 @@ def test_determine_postprocessing_makes_an_output_folder_that_does_not_exist_yet
 # ---------------------------------------------------------------------------------------------------------------
 # the properties pickle
 # ---------------------------------------------------------------------------------------------------------------
-class _NoLabelFiles:
-    def _write_label_files(self, seg, props, output_file_truncated):
-        pass
-
-
 def _properties():
     affine = np.diag([1.5, 1.5, 2.0, 1.0])
     return {'nibabel_stuff': {'original_affine': affine, 'reoriented_affine': affine.copy()},
@@ -249,11 +244,11 @@ def _same_properties(a, b):
 
 def test_properties_unpickler_loads_what_the_predictor_exports(tmp_path):
     from fast_nnunet_amd import ensembling as ens
-    from fast_nnunet_amd.predictor import nnUNetPredictor
+    from fast_nnunet_amd.case_pipeline import export_case_files
     props = _properties()
     probs = np.zeros((2, 3, 4, 5), np.float32)
     trunc = os.path.join(tmp_path, 'case')
-    nnUNetPredictor._export_files(_NoLabelFiles(), np.zeros((3, 4, 5), np.uint8), probs, props, trunc)
+    export_case_files(trunc, probs, props, lambda: None)         # (what the predictor's writer runs; no label file here)
     assert sorted(os.listdir(tmp_path)) == ['case.npz', 'case.pkl']
     got = ens.load_properties_pkl(trunc + '.pkl')
     assert _same_properties(got, props)
