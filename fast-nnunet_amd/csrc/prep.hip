@@ -7,7 +7,8 @@
 //   fnn_revert_labels   label map back to the uncropped, untransposed grid (inference/export_prediction.py:43-53)
 //
 // All three are HBM-bound element-wise / reduction kernels: one pass over the raw volume for the box, one pass
-// for the statistics of the schemes that need them, one read + one write for the result.
+// for the statistics of the schemes that need them (two for ZScore: the mean, then the squared deviations about it),
+// one read + one write for the result.
 #include "fnn_device.h"
 #include "../../include/fnn.h"
 #include <cfloat>
@@ -71,8 +72,11 @@ static __device__ __forceinline__ long long raw_index(const PrepParams &p, long 
     return (r[0] * p.g.s[1] + r[1]) * p.g.s[2] + r[2];
 }
 
-// ---- per-channel statistics over the crop box: sum, sum of squares (double), min, max
-__global__ __launch_bounds__(256) void stats_kernel(const float *raw, PrepParams p, int c, double *sums /*[3]: sum, sumsq, count*/, unsigned *mm /*[2] ordered*/) {
+// ---- per-channel statistics over the crop box: sum and sum of squares of (x - shift) (double), min, max.  ZScore runs it
+// twice: shift = 0 for the mean, then shift = mean for the squared deviations - E[x^2] - mean^2 in one pass cancels on a
+// channel that is nearly constant far from zero (mean 16384, std 0.002: what is left is rounding noise).  A NaN makes min and max NaN,
+// like numpy's.
+__global__ __launch_bounds__(256) void stats_kernel(const float *raw, PrepParams p, int c, double shift, double *sums /*[3]: sum, sumsq, count*/, unsigned *mm /*[2] ordered*/) {
     __shared__ double ssum[3][4];
     __shared__ unsigned smm[2];
     if (threadIdx.x == 0) { smm[0] = 0xffffffffu; smm[1] = 0u; }
@@ -80,17 +84,20 @@ __global__ __launch_bounds__(256) void stats_kernel(const float *raw, PrepParams
     const long long n = p.ext[0] * p.ext[1] * p.ext[2], nraw = p.g.s[0] * p.g.s[1] * p.g.s[2];
     double s1 = 0, s2 = 0, cnt = 0;
     float mn = FLT_MAX, mx = -FLT_MAX;
-    bool any = false;
+    bool any = false, nan = false;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const long long t2 = i % p.ext[2], t1 = (i / p.ext[2]) % p.ext[1], t0 = i / (p.ext[2] * p.ext[1]);
         const float v = raw[(long long)c * nraw + raw_index(p, t0, t1, t2)];
         if (p.use_mask[c] && p.mask[i] == 2) continue;          // outside the filled non-zero mask
-        s1 += (double)v; s2 += (double)v * (double)v; cnt += 1.0;
+        const double d = (double)v - shift;
+        s1 += d; s2 += d * d; cnt += 1.0;
         mn = v < mn ? v : mn; mx = v > mx ? v : mx;
+        nan |= v != v;
         any = true;
     }
-    // order-preserving map float -> unsigned for the atomics
+    // order-preserving map float -> unsigned for the atomics; -NaN sorts below -inf and +NaN above +inf
     auto ord = [](float f) { unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
+    if (nan) { mn = __uint_as_float(0xffc00000u); mx = __uint_as_float(0x7fc00000u); }
     if (any) { atomicMin(&smm[0], ord(mn)); atomicMax(&smm[1], ord(mx)); }
     for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off); cnt += __shfl_down(cnt, off); }
     if ((threadIdx.x & 63) == 0) { ssum[0][threadIdx.x >> 6] = s1; ssum[1][threadIdx.x >> 6] = s2; ssum[2][threadIdx.x >> 6] = cnt; }
@@ -119,22 +126,26 @@ __global__ __launch_bounds__(256) void mask_init_kernel(const float *raw, PrepPa
     m[i] = nz ? 0 : (face ? 2 : 1);
 }
 
-// One sweep: every thread owns a line along `axis` and carries "outside" forwards and backwards through runs of
-// background; a voxel also turns outside when a neighbour on another line already is (checked along the way).
-__global__ __launch_bounds__(256) void mask_sweep_kernel(PrepParams p, int axis, uint8_t *m, int *changed) {
+// One sweep: every thread owns `seg` voxels of a line along `axis` (the whole line when the box has lines enough to fill
+// the device) and carries "outside" forwards and backwards through runs of background, starting from the voxel before /
+// behind its segment; a voxel also turns outside when a neighbour on another line already is (checked along the way).
+// A sweep that changes nothing has looked at all six neighbours of every background voxel, whatever `seg` is.
+__global__ __launch_bounds__(256) void mask_sweep_kernel(PrepParams p, int axis, long long seg, uint8_t *m, int *changed) {
     const long long e[3] = {p.ext[0], p.ext[1], p.ext[2]};
     const int a1 = axis == 0 ? 1 : 0, a2 = axis == 2 ? 1 : 2;
     const long long lines = e[a1] * e[a2];
-    const long long l = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (l >= lines) return;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long l = t % lines, k0 = (t / lines) * seg;
+    if (k0 >= e[axis]) return;
+    const long long k1 = k0 + seg < e[axis] ? k0 + seg : e[axis];
     const long long c1 = l / e[a2], c2 = l % e[a2];
     const long long st[3] = {e[1] * e[2], e[2], 1};
     const long long base = c1 * st[a1] + c2 * st[a2];
     bool any = false;
     for (int dir = 0; dir < 2; ++dir) {
-        bool carry = false;
-        for (long long k = 0; k < e[axis]; ++k) {
-            const long long pos = dir ? e[axis] - 1 - k : k;
+        bool carry = dir ? (k1 < e[axis] && m[base + k1 * st[axis]] == 2) : (k0 > 0 && m[base + (k0 - 1) * st[axis]] == 2);
+        for (long long k = k0; k < k1; ++k) {
+            const long long pos = dir ? k1 - 1 - (k - k0) : k;
             const long long i = base + pos * st[axis];
             uint8_t v = m[i];
             if (v == 1) {
@@ -315,19 +326,32 @@ int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t trans
             return fnn_fail(FNN_E_HIP, "hipMalloc failed");
         }
         hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, raw, p, mask);
-        for (int iter = 0; iter < 4096 && r == hipSuccess; ++iter) {
+        // Iterations until one changes nothing.  Each one before it turns at least one voxel outside, so no box takes more
+        // than n + 1 (a corridor that winds through a thin box does take thousands): running out of them is an error,
+        // never a mask that is silently wrong.
+        bool converged = false;
+        for (long long iter = 0; iter <= n && r == hipSuccess && !converged; ++iter) {
             int h = 0;
             r = hipMemcpyAsync(changed, &h, sizeof(int), hipMemcpyHostToDevice, st);
             for (int axis = 0; axis < 3 && r == hipSuccess; ++axis) {
+                // a thread per line where that makes 64 Ki threads, else the lines cut into segments of 32 voxels or more
                 const long long lines = n / p.ext[axis];
-                hipLaunchKernelGGL(mask_sweep_kernel, dim3((unsigned)((lines + 255) / 256)), dim3(256), 0, st, p, axis, mask, changed);
+                const long long cuts = lines >= 65536 ? 1 : (65536 + lines - 1) / lines;
+                long long seg = (p.ext[axis] + cuts - 1) / cuts;
+                seg = seg < 32 ? 32 : seg;
+                const long long threads = lines * ((p.ext[axis] + seg - 1) / seg);
+                hipLaunchKernelGGL(mask_sweep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, axis, seg, mask, changed);
                 r = hipGetLastError();
             }
             if (r == hipSuccess) r = hipMemcpyAsync(&h, changed, sizeof(int), hipMemcpyDeviceToHost, st);
             if (r == hipSuccess) r = hipStreamSynchronize(st);
-            if (r != hipSuccess || !h) break;
+            converged = r == hipSuccess && !h;
         }
         (void)hipFree(changed);
+        if (r == hipSuccess && !converged) {
+            (void)hipFree(sums); (void)hipFree(mask);
+            return fnn_fail(FNN_E_HIP, "the fill-holes sweeps of the non-zero mask did not converge");
+        }
         p.mask = mask;
     }
     for (int c = 0; c < p.g.C && r == hipSuccess; ++c) {
@@ -347,7 +371,7 @@ int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t trans
             if (r == hipSuccess) r = hipMemcpyAsync(mm, mi, sizeof(mi), hipMemcpyHostToDevice, st);
             long long blocks = (n + 255) / 256;
             if (blocks > 256 * 16) blocks = 256 * 16;
-            if (r == hipSuccess) { hipLaunchKernelGGL(stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, p, c, sc, mm); r = hipGetLastError(); }
+            if (r == hipSuccess) { hipLaunchKernelGGL(stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, p, c, 0.0, sc, mm); r = hipGetLastError(); }
             if (r == hipSuccess) r = hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, st);
             if (r == hipSuccess) r = hipMemcpyAsync(hm, mm, sizeof(hm), hipMemcpyDeviceToHost, st);
             if (r == hipSuccess) r = hipStreamSynchronize(st);
@@ -356,14 +380,22 @@ int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t trans
             if (d.scheme == FNN_NORM_ZSCORE) {
                 const double cntd = hs[2] > 0 ? hs[2] : 1.0;             // voxels inside the mask (all of them without one)
                 const double mean = hs[0] / cntd;
-                double var = hs[1] / cntd - mean * mean;
-                var = var > 0 ? var : 0;
+                // second pass: the squared deviations about the mean (and the sum of the deviations, which takes out
+                // what the rounding of the mean left in)
+                r = hipMemcpyAsync(sc, z, sizeof(z), hipMemcpyHostToDevice, st);
+                if (r == hipSuccess) { hipLaunchKernelGGL(stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, p, c, mean, sc, mm); r = hipGetLastError(); }
+                if (r == hipSuccess) r = hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, st);
+                if (r == hipSuccess) r = hipStreamSynchronize(st);
+                if (r != hipSuccess) break;
+                const double dev = hs[0] / cntd;
+                double var = hs[1] / cntd - dev * dev;
+                var = var < 0 ? 0 : var;                                      // NaN stays NaN, like numpy's std
                 const float stdf = (float)sqrt(var);
-                p.a[c] = (float)mean; p.b[c] = stdf > 1e-8f ? stdf : 1e-8f;
+                p.a[c] = (float)mean; p.b[c] = 1e-8f > stdf ? 1e-8f : stdf;   // python's max(std, 1e-8): a NaN std stays
             } else {
                 const float mn = unord(hm[0]), mx = unord(hm[1]);
                 const float range = mx - mn;                                   // = (image - image.min()).max() in fp32
-                p.a[c] = mn; p.b[c] = range > 1e-8f ? range : 1e-8f;
+                p.a[c] = mn; p.b[c] = range < 1e-8f ? 1e-8f : range;            // np.clip(max, 1e-8, None): NaN stays NaN
             }
         } else if (d.scheme != FNN_NORM_NONE && d.scheme != FNN_NORM_RGB01) {
             (void)hipFree(sums); (void)hipFree(mask);

@@ -283,7 +283,10 @@ typedef struct fnn_norm_desc {
  * ['bbox_used_for_cropping'] of the reference. */
 int fnn_nonzero_bbox(const float *raw, const int64_t shape[4], const int32_t transpose_forward[3],
                      int64_t bbox[6], void *stream);
-/* out: float32 [C][bbox extents] = normalise(crop(transpose(raw))); norm[C]. */
+/* out: float32 [C][bbox extents] = normalise(crop(transpose(raw))); norm[C].
+ * ZScore: mean and std from float64 sums in two passes, each rounded to float32 once.  NaN and inf go where numpy sends
+ * them: a NaN voxel makes a RescaleTo01 or ZScore channel NaN throughout, an inf voxel a ZScore channel (its std is NaN,
+ * and max(NaN, 1e-8) is NaN).  use_mask: the filled mask is found by sweeps repeated until nothing changes. */
 int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t transpose_forward[3],
                    const int64_t bbox[6], const fnn_norm_desc *norm, float *out, void *stream);
 /* The label half of convert_predicted_logits_to_segmentation_with_correct_shape

@@ -1,8 +1,9 @@
 """f-2 / f-3 on the device: crop-to-nonzero box, transpose, intensity normalisation and the label revert against
 vectors produced by the reference's own functions (tests/golden/preprocess.npz) and against the oracle on
 larger random cases.  CT / RescaleTo01 / RGBTo01 / NoNormalization are bit-exact (three fp32 roundings in the
-reference's order); ZScoreNormalization uses double-precision statistics where numpy sums pairwise in fp32:
-tolerance 2e-6 relative to the data range."""
+reference's order); ZScoreNormalization uses double-precision two-pass statistics (the mean, then the squared
+deviations about it) where numpy sums pairwise in fp32: tolerance 2e-6 relative to the data range here, and bit for
+bit one of the nine outputs an exactly rounded mean and std admit in tests/test_gpu_prep_ops.py."""
 import os
 
 import numpy as np
