@@ -29,9 +29,8 @@
 // 50.9 KiB / 74.9 KiB, dynamic (three / two workgroups per CU).  deflate.hip's layout - a padded image of the mask bytes
 // per wave next to its bit buffer - would need 34.6 KiB per wave on top of the chunk.
 // Nothing is written outside out[0, sum of the fragment sizes); no kernel keeps scratch.
-#include "fnn_device.h"
+#include "host_call.h"
 #include "deflate_wave.h"
-#include "../../include/fnn.h"
 #include <climits>
 #include <cstdint>
 #include <cstring>
@@ -291,8 +290,7 @@ __global__ __launch_bounds__(MK_EMIT_THREADS) void deflate_masks_emit_kernel(con
 // what both calls refuse before they launch anything -> 0, or the code (the message is set)
 static int check_common(const char *who, const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
                         const void *work) {
-    static thread_local char msg[160];
-    auto fail = [&](int code, const char *what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return fnn_fail(code, msg); };
+    auto fail = [&](int code, const char *what) { return fnn_failf(code, "%s: %s", who, what); };
     if (!in || !labels || !work) return fail(FNN_E_INVALID, "NULL argument");
     if (in_elem_bytes != 1 && in_elem_bytes != 2) return fail(FNN_E_INVALID, "labels of 1 or 2 bytes are served");
     if (n_elems < 0) return fail(FNN_E_INVALID, "negative element count");
@@ -324,7 +322,7 @@ extern "C" int fnn_deflate_masks_count(const void *in, int in_elem_bytes, int64_
     if (const int rc = check_common("fnn_deflate_masks_count", in, in_elem_bytes, n_elems, labels, n_labels, work)) return rc;
     const MkWork w(n_elems, n_labels);
     if (work_cap < (int64_t)w.total) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_count: work_cap is below fnn_deflate_masks_work_bytes");
-    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(work)) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_count needs device pointers for in and work (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_deflate_masks_count", {in, work}, "device pointers for in and work")) return rc;
     for (int k = 0; k < n_labels; ++k) { frag_bytes[k] = 0; crc32[k] = 0; }
     if (n_elems == 0) return FNN_OK;
 
@@ -337,40 +335,28 @@ extern "C" int fnn_deflate_masks_count(const void *in, int in_elem_bytes, int64_
     uint32_t *d_fcrc = (uint32_t *)(base + w.o_fcrc);
     unsigned long long *d_slots = (unsigned long long *)(base + w.o_slots);
     uint16_t *d_sizes = (uint16_t *)(base + w.o_sizes);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t r = hipMemcpyAsync(d_x2k, g_tables.x2k, sizeof(g_tables.x2k), hipMemcpyHostToDevice, st);
-    if (r == hipSuccess) r = hipMemcpyAsync(base + w.o_zero, g_tables.zero, sizeof(g_tables.zero), hipMemcpyHostToDevice, st);
-    if (r == hipSuccess) r = hipMemcpyAsync(d_labels, labels, (size_t)n_labels * 4, hipMemcpyHostToDevice, st);
-    if (r == hipSuccess) r = hipMemsetAsync(d_sizes, 0, (size_t)n_labels * (size_t)chunks * 2, st);      // every pair: the zero chunk
-    if (r == hipSuccess) {
-        if (in_elem_bytes == 1)
-            hipLaunchKernelGGL((deflate_masks_count_kernel<1>), dim3((unsigned)chunks), dim3(MK_COUNT_THREADS), 0, st, (const uint8_t *)in,
-                               (long long)n_elems, d_labels, n_labels, d_x2k, chunks, d_sizes, d_slots);
-        else
-            hipLaunchKernelGGL((deflate_masks_count_kernel<2>), dim3((unsigned)chunks), dim3(MK_COUNT_THREADS), 0, st, (const uint8_t *)in,
-                               (long long)n_elems, d_labels, n_labels, d_x2k, chunks, d_sizes, d_slots);
-        fnn_note_kernel("deflate_masks_count_kernel<%d>", in_elem_bytes);
-        r = hipGetLastError();
-    }
-    if (r == hipSuccess) {
-        hipLaunchKernelGGL(deflate_masks_scan_kernel, dim3((unsigned)n_labels), dim3(MK_SCAN_THREADS), 0, st, d_sizes, d_slots, chunks, last_len,
-                           g_tables.zero_crc, d_x2k, d_fbytes, d_fcrc);
-        fnn_note_kernel("deflate_masks_scan_kernel");
-        r = hipGetLastError();
-    }
+    HipCall call(stream);
+    call.copy(d_x2k, g_tables.x2k, sizeof(g_tables.x2k), hipMemcpyHostToDevice);
+    call.copy(base + w.o_zero, g_tables.zero, sizeof(g_tables.zero), hipMemcpyHostToDevice);
+    call.copy(d_labels, labels, (size_t)n_labels * 4, hipMemcpyHostToDevice);
+    call.fill(d_sizes, 0, (size_t)n_labels * (size_t)chunks * 2);                                        // every pair: the zero chunk
+    if (call.ok()) fnn_note_kernel("deflate_masks_count_kernel<%d>", in_elem_bytes);
+    call.launch(in_elem_bytes == 1 ? deflate_masks_count_kernel<1> : deflate_masks_count_kernel<2>, dim3((unsigned)chunks),
+                dim3(MK_COUNT_THREADS), 0, (const uint8_t *)in, (long long)n_elems, d_labels, n_labels, d_x2k, chunks, d_sizes, d_slots);
+    if (call.ok()) fnn_note_kernel("deflate_masks_scan_kernel");
+    call.launch(deflate_masks_scan_kernel, dim3((unsigned)n_labels), dim3(MK_SCAN_THREADS), 0, d_sizes, d_slots, chunks, last_len,
+                g_tables.zero_crc, d_x2k, d_fbytes, d_fcrc);
     std::vector<long long> h_bytes((size_t)n_labels), h_frag((size_t)n_labels + 1);
-    if (r == hipSuccess) r = hipMemcpyAsync(h_bytes.data(), d_fbytes, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st);
-    if (r == hipSuccess) r = hipMemcpyAsync(crc32, d_fcrc, (size_t)n_labels * 4, hipMemcpyDeviceToHost, st);
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (r == hipSuccess) {
+    call.copy(h_bytes.data(), d_fbytes, (size_t)n_labels * 8, hipMemcpyDeviceToHost);
+    call.copy(crc32, d_fcrc, (size_t)n_labels * 4, hipMemcpyDeviceToHost);
+    if (call.sync()) {
         h_frag[0] = 0;
         for (int k = 0; k < n_labels; ++k) { frag_bytes[k] = h_bytes[(size_t)k]; h_frag[(size_t)k + 1] = h_frag[(size_t)k] + h_bytes[(size_t)k]; }
-        r = hipMemcpyAsync(d_frag, h_frag.data(), ((size_t)n_labels + 1) * 8, hipMemcpyHostToDevice, st);
-        if (r == hipSuccess) r = hipStreamSynchronize(st);
+        call.copy(d_frag, h_frag.data(), ((size_t)n_labels + 1) * 8, hipMemcpyHostToDevice);
     }
-    if (r != hipSuccess) {
+    if (!call.sync()) {
         for (int k = 0; k < n_labels; ++k) { frag_bytes[k] = 0; crc32[k] = 0; }
-        return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
+        return call.fail();
     }
     return FNN_OK;
 }
@@ -381,8 +367,7 @@ extern "C" int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t
     if (!out) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: NULL argument");
     if (const int rc = check_common("fnn_deflate_masks_emit", in, in_elem_bytes, n_elems, labels, n_labels, work)) return rc;
     if (out_cap < 0) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: out_cap is negative");
-    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(work) || !fnn_dev_ptr(out))
-        return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit needs device pointers for in, work and out (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_deflate_masks_emit", {in, work, out}, "device pointers for in, work and out")) return rc;
     if (n_elems == 0) return FNN_OK;
 
     const MkWork w(n_elems, n_labels);
@@ -393,10 +378,10 @@ extern "C" int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t
     // the sizes count left: the labels and the end of the last fragment (count has synchronised; this waits for nothing new)
     std::vector<int32_t> h_labels((size_t)n_labels);
     long long total = -1;
-    hipError_t r = hipMemcpyAsync(&total, d_frag + n_labels, 8, hipMemcpyDeviceToHost, st);
-    if (r == hipSuccess) r = hipMemcpyAsync(h_labels.data(), base + w.o_labels, (size_t)n_labels * 4, hipMemcpyDeviceToHost, st);
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
+    HipCall call(stream);
+    call.copy(&total, d_frag + n_labels, 8, hipMemcpyDeviceToHost);
+    call.copy(h_labels.data(), base + w.o_labels, (size_t)n_labels * 4, hipMemcpyDeviceToHost);
+    if (!call.sync()) return call.fail();
     if (memcmp(h_labels.data(), labels, (size_t)n_labels * 4) != 0)
         return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: work was not filled by fnn_deflate_masks_count for these labels");
     if (total < 0 || out_cap < total) return fnn_fail(FNN_E_INVALID, "fnn_deflate_masks_emit: out_cap is below the sum of the fragment sizes");

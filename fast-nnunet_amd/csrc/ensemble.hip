@@ -14,8 +14,7 @@
 // multiples of 4 (the common case) VEC = 4: 8-byte (fp16) or 16-byte (fp32) loads per member and head, 16-byte stores
 // of the average.  The softmax needs three passes over a member's heads (max, sum, probability); the first reads the
 // logits from HBM, the other two re-read the same lines, as export_prob_kernel does.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <climits>
 #include <cmath>
 #include <cstdint>
@@ -28,19 +27,12 @@ constexpr int ENS_MAX_MEMBERS = 16;
 constexpr int ENS_THREADS = 256;
 constexpr int ENS_VEC_MAX_MEMBERS = 8;           // the VEC = 4 kernels keep 2 x 4 floats of softmax state per member
 
-static int check_perm(const int32_t t[3]) {
-    int seen = 0;
-    for (int i = 0; i < 3; ++i) { if (t[i] < 0 || t[i] > 2) return -1; seen |= 1 << t[i]; }
-    return seen == 7 ? 0 : -1;
-}
-
 struct EnsembleArgs {
     const void *member[ENS_MAX_MEMBERS];     // [H][e0][e1][e2] logits (export) / [H][n] float32 probabilities (average)
     unsigned f32_mask;                       // bit m: member m is float32 (else fp16)
     int N, H;
     const int *order;                        // regions_class_order on the device, or nullptr for plain labels
-    long long lo[3], e[3], o[3];             // crop box origin / extent (transposed axes), output grid
-    int tb[3];
+    CropBox box;                             // export: crop box (transposed axes) and output grid
     float *avg;                              // [H][o0][o1][o2] or nullptr
 };
 
@@ -98,19 +90,17 @@ static __device__ __forceinline__ void merge_rule(const EnsembleArgs &a, int h, 
 // + labels [o0][o1][o2] on the raw grid.  Member m's probability of head h is export_prob_kernel's expression for it.
 template <int VEC, int MAXN, typename LT>
 __global__ __launch_bounds__(ENS_THREADS) void ensemble_export_kernel(EnsembleArgs a, LT *labels) {
-    const long long n = a.o[0] * a.o[1] * a.o[2];
+    const long long n = a.box.o[0] * a.box.o[1] * a.box.o[2];
     const long long i = ((long long)blockIdx.x * ENS_THREADS + threadIdx.x) * VEC;
     if (i >= n) return;
-    const long long oc[3] = {i / (a.o[1] * a.o[2]), (i / a.o[2]) % a.o[1], i % a.o[2]};
-    long long t[3];
-    t[a.tb[0]] = oc[0]; t[a.tb[1]] = oc[1]; t[a.tb[2]] = oc[2];
-    const long long d0 = t[0] - a.lo[0], d1 = t[1] - a.lo[1], d2 = t[2] - a.lo[2];
+    size_t v;
+    const bool inside = crop_box_voxel(a.box, i, v);
     int label[VEC];
     float best[VEC], acc[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; ++k) { label[k] = 0; best[k] = -1.f; }
     // VEC = 4 only runs when the box's z edges and the rows are multiples of 4: the 4 voxels are all in or all out
-    if (!(d0 >= 0 && d0 < a.e[0] && d1 >= 0 && d1 < a.e[1] && d2 >= 0 && d2 < a.e[2])) {
+    if (!inside) {
         // every member's probability is 1 for the background / 0 elsewhere (revert_cropping_on_probabilities, 0 for
         // every region), so the average is too, and both rules give label 0
         if (a.avg)
@@ -122,7 +112,7 @@ __global__ __launch_bounds__(ENS_THREADS) void ensemble_export_kernel(EnsembleAr
         store_labels<VEC, LT>(labels, i, label);
         return;
     }
-    const size_t plane = (size_t)a.e[0] * a.e[1] * a.e[2], v = ((size_t)d0 * a.e[1] + d1) * a.e[2] + d2;
+    const size_t plane = (size_t)a.box.e[0] * a.box.e[1] * a.box.e[2];
     const float fn = (float)a.N;
     float x[VEC];
     if (a.order) {
@@ -212,22 +202,6 @@ __global__ __launch_bounds__(ENS_THREADS) void average_probabilities_kernel(Ense
 
 static bool aligned(const void *p, size_t bytes) { return ((uintptr_t)p % bytes) == 0; }
 
-// regions_class_order -> device copy (nullptr for plain labels); the caller frees it
-static hipError_t upload_order(const int32_t *regions_class_order, int heads, hipStream_t st, int **order) {
-    *order = nullptr;
-    if (!regions_class_order) return hipSuccess;
-    hipError_t r = hipMalloc((void **)order, heads * sizeof(int));
-    if (r != hipSuccess) { *order = nullptr; return r; }
-    return hipMemcpyAsync(*order, regions_class_order, heads * sizeof(int), hipMemcpyHostToDevice, st);
-}
-
-static int finish(hipError_t r, hipStream_t st, int *order) {
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (order) (void)hipFree(order);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
-    return FNN_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -240,48 +214,41 @@ int fnn_ensemble_export(const void *const *member_logits, const int32_t *member_
     if (n_members < 1 || n_members > ENS_MAX_MEMBERS) return fnn_fail(FNN_E_INVALID, "n_members must be 1..16");
     for (int m = 0; m < n_members; ++m) {
         if (!member_logits[m]) return fnn_fail(FNN_E_INVALID, "NULL member logits");
-        if (member_dtype[m] != FNN_OUT_F16 && member_dtype[m] != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown member logits dtype");
+        if (int rc = fnn_check_float_dtype(member_dtype[m], "member logits dtype")) return rc;
     }
     if (heads < 1 || heads > 4096) return fnn_fail(FNN_E_INVALID, "bad number of heads");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
-    if (check_perm(transpose_backward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
+    if (int rc = fnn_check_perm(transpose_backward, "transpose_backward")) return rc;
     EnsembleArgs a{};
-    for (int d = 0; d < 3; ++d) {
-        a.lo[d] = bbox[2 * d]; a.e[d] = bbox[2 * d + 1] - bbox[2 * d];
-        if (a.lo[d] < 0 || a.e[d] < 1 || bbox[2 * d + 1] > shape_before_cropping[d]) return fnn_fail(FNN_E_INVALID, "bbox outside shape_before_cropping");
-    }
+    if (int rc = crop_box_fill(a.box, bbox, shape_before_cropping, transpose_backward)) return rc;
     for (int m = 0; m < n_members; ++m)
-        if (!fnn_dev_ptr(member_logits[m])) return fnn_fail(FNN_E_INVALID, "fnn_ensemble_export needs device pointers (no CPU path)");
-    if (!fnn_dev_ptr(labels) || (avg_probs && !fnn_dev_ptr(avg_probs))) return fnn_fail(FNN_E_INVALID, "fnn_ensemble_export needs device pointers (no CPU path)");
-    for (int j = 0; j < 3; ++j) { a.o[j] = shape_before_cropping[transpose_backward[j]]; a.tb[j] = transpose_backward[j]; }
+        if (int rc = fnn_need_dev("fnn_ensemble_export", {member_logits[m]})) return rc;
+    if (int rc = fnn_need_dev("fnn_ensemble_export", {labels})) return rc;
+    if (avg_probs)
+        if (int rc = fnn_need_dev("fnn_ensemble_export", {avg_probs})) return rc;
     a.N = n_members; a.H = heads; a.avg = avg_probs;
     for (int m = 0; m < n_members; ++m) {
         a.member[m] = member_logits[m];
         if (member_dtype[m] == FNN_OUT_F32) a.f32_mask |= 1u << m;
     }
+    const CropBox &b = a.box;
     const size_t lbytes = label_dtype == FNN_LABEL_U16 ? 2 : 1;
-    bool vec = a.tb[0] == 0 && a.tb[1] == 1 && a.tb[2] == 2 && a.o[2] % 4 == 0 && a.lo[2] % 4 == 0 && a.e[2] % 4 == 0 &&
+    bool vec = b.tb[0] == 0 && b.tb[1] == 1 && b.tb[2] == 2 && b.o[2] % 4 == 0 && b.lo[2] % 4 == 0 && b.e[2] % 4 == 0 &&
                n_members <= ENS_VEC_MAX_MEMBERS && aligned(labels, 4 * lbytes) && (!avg_probs || aligned(avg_probs, 16));
     for (int m = 0; m < n_members; ++m) vec = vec && aligned(member_logits[m], 16);
-    const long long n = a.o[0] * a.o[1] * a.o[2];
+    const long long n = b.o[0] * b.o[1] * b.o[2];
     const int V = vec ? 4 : 1;
     if ((n / V + ENS_THREADS - 1) / ENS_THREADS > UINT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "output grid too large");
-    hipStream_t st = (hipStream_t)stream;
-    int *order = nullptr;
-    hipError_t r = upload_order(regions_class_order, heads, st, &order);
-    a.order = order;
+    HipCall call(stream);
+    const DevBuf order = upload_order(regions_class_order, heads, call);
+    a.order = order.as<int>();
     const dim3 grid((unsigned)((n / V + ENS_THREADS - 1) / ENS_THREADS));
-    if (r == hipSuccess) {
-        if (vec) {
-            if (label_dtype == FNN_LABEL_U16) hipLaunchKernelGGL((ensemble_export_kernel<4, ENS_VEC_MAX_MEMBERS, uint16_t>), grid, dim3(ENS_THREADS), 0, st, a, (uint16_t *)labels);
-            else hipLaunchKernelGGL((ensemble_export_kernel<4, ENS_VEC_MAX_MEMBERS, uint8_t>), grid, dim3(ENS_THREADS), 0, st, a, (uint8_t *)labels);
-        } else {
-            if (label_dtype == FNN_LABEL_U16) hipLaunchKernelGGL((ensemble_export_kernel<1, ENS_MAX_MEMBERS, uint16_t>), grid, dim3(ENS_THREADS), 0, st, a, (uint16_t *)labels);
-            else hipLaunchKernelGGL((ensemble_export_kernel<1, ENS_MAX_MEMBERS, uint8_t>), grid, dim3(ENS_THREADS), 0, st, a, (uint8_t *)labels);
-        }
-        r = hipGetLastError();
-    }
-    return finish(r, st, order);
+    fnn_by_label(label_dtype, [&](auto lt) {
+        using LT = decltype(lt);
+        if (vec) call.launch(ensemble_export_kernel<4, ENS_VEC_MAX_MEMBERS, LT>, grid, dim3(ENS_THREADS), 0, a, (LT *)labels);
+        else call.launch(ensemble_export_kernel<1, ENS_MAX_MEMBERS, LT>, grid, dim3(ENS_THREADS), 0, a, (LT *)labels);
+    });
+    return call.finish();
 }
 
 int fnn_average_probabilities(const float *const *member_probs, int n_members, int heads, const int32_t *regions_class_order,
@@ -291,12 +258,14 @@ int fnn_average_probabilities(const float *const *member_probs, int n_members, i
     for (int m = 0; m < n_members; ++m)
         if (!member_probs[m]) return fnn_fail(FNN_E_INVALID, "NULL member probabilities");
     if (heads < 1 || heads > 4096) return fnn_fail(FNN_E_INVALID, "bad number of heads");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
     if (n_vox < 0) return fnn_fail(FNN_E_INVALID, "negative n_vox");
     if (n_vox == 0) return FNN_OK;
     for (int m = 0; m < n_members; ++m)
-        if (!fnn_dev_ptr(member_probs[m])) return fnn_fail(FNN_E_INVALID, "fnn_average_probabilities needs device pointers (no CPU path)");
-    if (!fnn_dev_ptr(labels) || (avg_probs && !fnn_dev_ptr(avg_probs))) return fnn_fail(FNN_E_INVALID, "fnn_average_probabilities needs device pointers (no CPU path)");
+        if (int rc = fnn_need_dev("fnn_average_probabilities", {member_probs[m]})) return rc;
+    if (int rc = fnn_need_dev("fnn_average_probabilities", {labels})) return rc;
+    if (avg_probs)
+        if (int rc = fnn_need_dev("fnn_average_probabilities", {avg_probs})) return rc;
     EnsembleArgs a{};
     a.N = n_members; a.H = heads; a.avg = avg_probs;
     const size_t lbytes = label_dtype == FNN_LABEL_U16 ? 2 : 1;
@@ -306,24 +275,18 @@ int fnn_average_probabilities(const float *const *member_probs, int n_members, i
         a.f32_mask |= 1u << m;
         vec = vec && aligned(member_probs[m], 16);
     }
-    hipStream_t st = (hipStream_t)stream;
     const int V = vec ? 4 : 1;
     if ((n_vox / V + ENS_THREADS - 1) / ENS_THREADS > UINT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "too many voxels");
-    int *order = nullptr;
-    hipError_t r = upload_order(regions_class_order, heads, st, &order);
-    a.order = order;
+    HipCall call(stream);
+    const DevBuf order = upload_order(regions_class_order, heads, call);
+    a.order = order.as<int>();
     const dim3 grid((unsigned)((n_vox / V + ENS_THREADS - 1) / ENS_THREADS));
-    if (r == hipSuccess) {
-        if (vec) {
-            if (label_dtype == FNN_LABEL_U16) hipLaunchKernelGGL((average_probabilities_kernel<4, uint16_t>), grid, dim3(ENS_THREADS), 0, st, a, (long long)n_vox, (uint16_t *)labels);
-            else hipLaunchKernelGGL((average_probabilities_kernel<4, uint8_t>), grid, dim3(ENS_THREADS), 0, st, a, (long long)n_vox, (uint8_t *)labels);
-        } else {
-            if (label_dtype == FNN_LABEL_U16) hipLaunchKernelGGL((average_probabilities_kernel<1, uint16_t>), grid, dim3(ENS_THREADS), 0, st, a, (long long)n_vox, (uint16_t *)labels);
-            else hipLaunchKernelGGL((average_probabilities_kernel<1, uint8_t>), grid, dim3(ENS_THREADS), 0, st, a, (long long)n_vox, (uint8_t *)labels);
-        }
-        r = hipGetLastError();
-    }
-    return finish(r, st, order);
+    fnn_by_label(label_dtype, [&](auto lt) {
+        using LT = decltype(lt);
+        if (vec) call.launch(average_probabilities_kernel<4, LT>, grid, dim3(ENS_THREADS), 0, a, (long long)n_vox, (LT *)labels);
+        else call.launch(average_probabilities_kernel<1, LT>, grid, dim3(ENS_THREADS), 0, a, (long long)n_vox, (LT *)labels);
+    });
+    return call.finish();
 }
 
 }  // extern "C"

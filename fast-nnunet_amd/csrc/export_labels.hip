@@ -28,6 +28,7 @@
 // registers under compile-time indices.
 #include "output_common.h"
 #include "resample_torch_common.h"
+#include "host_call.h"
 #include <type_traits>
 
 namespace {
@@ -203,16 +204,17 @@ extern "C" int fnn_resample_labels(const void *logits, int dtype, const int64_t 
                                    void *labels, int label_dtype, void *stream) {
     if (!logits || !shape || !new_shape || !labels) return fnn_fail(FNN_E_INVALID, "NULL argument");
     if (family != FNN_RESAMPLE_DEFAULT && family != FNN_RESAMPLE_TORCH) return fnn_fail(FNN_E_UNSUPPORTED, "unknown resampling family");
-    if (dtype != FNN_OUT_F16 && dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown dtype");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (int rc = fnn_check_float_dtype(dtype)) return rc;
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
     if (separate_axis < -1 || separate_axis > 2) return fnn_fail(FNN_E_INVALID, "separate_axis must be -1 .. 2");
     if (shape[0] < 1) return fnn_fail(FNN_E_INVALID, "heads must be at least 1");
     for (int a = 1; a < 4; ++a) if (shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad shape");
     for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad new_shape");
     if (regions_class_order && n_regions != shape[0]) return fnn_fail(FNN_E_INVALID, "regions_class_order needs one entry per head");
     if (!regions_class_order && label_dtype == FNN_LABEL_U8 && shape[0] > 256) return fnn_fail(FNN_E_INVALID, "more than 256 heads need uint16 labels");
-    if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(labels) || (regions_class_order && !fnn_dev_ptr(regions_class_order)))
-        return fnn_fail(FNN_E_INVALID, "fnn_resample_labels needs device pointers (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_resample_labels", {logits, labels})) return rc;
+    if (regions_class_order)
+        if (int rc = fnn_need_dev("fnn_resample_labels", {regions_class_order})) return rc;
     RGeo rg{};                                                 // the grid rule and its limits are the torch family's for both
     const char *why = "";
     if (int rc = rt_geometry(shape, new_shape, separate_axis, rg, &why)) return fnn_fail(rc, why);

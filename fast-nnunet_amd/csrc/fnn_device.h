@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/fnn.h"
 
 typedef _Float16 f16;
 typedef f16 f16x8 __attribute__((ext_vector_type(8)));
@@ -285,6 +286,36 @@ int fnn_fail(int code, const char *msg);                // sets that message -> 
 bool fnn_dev_ptr(const void *p);                        // device or managed memory?
 
 static __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
+
+// The crop box of a case on its way back to the raw grid (export_prediction.py:43-53): labels or logits live on the
+// transposed, cropped grid [e0][e1][e2]; the output grid is shape_before_cropping in the original axis order.
+struct CropBox {
+    long long lo[3], e[3];       // origin and extent of the box on the transposed axes
+    long long o[3];              // the output grid
+    int tb[3];                   // transpose_backward: output axis j = transposed axis tb[j]
+};
+// host: the box from bbox (lo, hi per transposed axis), which must lie inside `before` (the transposed shape before
+// cropping) - else FNN_E_INVALID with `outside` as the message - and, given transpose_backward, the output grid.  Without
+// one (nullptr: fnn_preprocess, which needs lo and e only) o and tb are left as the caller's `CropBox b{}` zeroed them
+inline int crop_box_fill(CropBox &b, const int64_t bbox[6], const int64_t before[3], const int32_t *transpose_backward,
+                         const char *outside = "bbox outside shape_before_cropping") {
+    for (int a = 0; a < 3; ++a) {
+        b.lo[a] = bbox[2 * a]; b.e[a] = bbox[2 * a + 1] - bbox[2 * a];
+        if (b.lo[a] < 0 || b.e[a] < 1 || bbox[2 * a + 1] > before[a]) return fnn_fail(FNN_E_INVALID, outside);
+    }
+    for (int j = 0; transpose_backward && j < 3; ++j) { b.tb[j] = transpose_backward[j]; b.o[j] = before[b.tb[j]]; }
+    return FNN_OK;
+}
+// device: voxel i of the output grid -> is it inside the box, and then its index v in the cropped grid
+static __device__ __forceinline__ bool crop_box_voxel(const CropBox &b, long long i, size_t &v) {
+    const long long oc[3] = {i / (b.o[1] * b.o[2]), (i / b.o[2]) % b.o[1], i % b.o[2]};
+    long long t[3];
+    t[b.tb[0]] = oc[0]; t[b.tb[1]] = oc[1]; t[b.tb[2]] = oc[2];
+    const long long d0 = t[0] - b.lo[0], d1 = t[1] - b.lo[1], d2 = t[2] - b.lo[2];
+    if (!(d0 >= 0 && d0 < b.e[0] && d1 >= 0 && d1 < b.e[1] && d2 >= 0 && d2 < b.e[2])) return false;
+    v = ((size_t)d0 * b.e[1] + d1) * b.e[2] + d2;
+    return true;
+}
 
 // Two MFMA results of the same 16 voxels or of two column blocks (lane = voxel r, channels 4 q .. 4 q + 3 of each) -> one
 // 16-byte store per lane:

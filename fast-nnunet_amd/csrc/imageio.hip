@@ -20,8 +20,7 @@
 // chunk is its neighbour's first: the same cache line, no HBM traffic).  The elements before the body and those behind
 // its last whole group whose chunks lie inside the input (`edge` elements, < 2 V + 4) go one per thread through the
 // scalar path of the same launch.  Nothing is read outside raw[0, n_vox * sizeof(T)) or written outside out[0, n_vox).
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <climits>
 #include <cstdint>
 #include <cstring>
@@ -290,7 +289,7 @@ extern "C" int fnn_decode_voxels(const void *raw, int nifti_datatype, int bytesw
                                                 "uint32, float32 and float64 are)");
     }
     if (n_vox == 0) return FNN_OK;
-    if (!fnn_dev_ptr(raw) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_decode_voxels needs device pointers (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_decode_voxels", {raw, out})) return rc;
     DecodeArgs a{};
     a.raw = raw; a.out = out; a.n_vox = n_vox;
     a.head = (int)(((16 - ((uintptr_t)out & 15)) & 15) / 4);
@@ -329,8 +328,9 @@ extern "C" int fnn_decode_labels(const void *raw, int nifti_datatype, int bytesw
     default: return fnn_fail(FNN_E_UNSUPPORTED, "fnn_decode_labels: NIfTI datatype not served (uint8, int8, int16, uint16, int32, "
                                                 "uint32, float32 and float64 are)");
     }
-    if (!fnn_dev_ptr(status)) return fnn_fail(FNN_E_INVALID, "fnn_decode_labels needs device pointers (no CPU path)");
-    if (n_vox > 0 && (!fnn_dev_ptr(raw) || !fnn_dev_ptr(out))) return fnn_fail(FNN_E_INVALID, "fnn_decode_labels needs device pointers (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_decode_labels", {status})) return rc;
+    if (n_vox > 0)
+        if (int rc = fnn_need_dev("fnn_decode_labels", {raw, out})) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t r = hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st);
     if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));

@@ -11,9 +11,9 @@
 //   - the ("other", "other") bin - background in nnU-Net's use - is never counted: the host derives it from the
 //     number of counted voxels, which each workgroup adds once.
 // Integers only: the result does not depend on scheduling.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <climits>
+#include <vector>
 
 namespace {
 
@@ -189,12 +189,12 @@ __global__ __launch_bounds__(CM_THREADS) void cm_count_kernel(CMArgs a) {
 }
 
 template <typename T>
-void launch_np(int n_pred, dim3 grid, hipStream_t st, const CMArgs &a) {
+void launch_np(int n_pred, dim3 grid, const CMArgs &a, HipCall &call) {
     switch (n_pred) {
-    case 1: hipLaunchKernelGGL((cm_count_kernel<T, 1>), grid, dim3(CM_THREADS), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((cm_count_kernel<T, 2>), grid, dim3(CM_THREADS), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((cm_count_kernel<T, 3>), grid, dim3(CM_THREADS), 0, st, a); break;
-    default: hipLaunchKernelGGL((cm_count_kernel<T, 4>), grid, dim3(CM_THREADS), 0, st, a); break;
+    case 1: call.launch(cm_count_kernel<T, 1>, grid, dim3(CM_THREADS), 0, a); break;
+    case 2: call.launch(cm_count_kernel<T, 2>, grid, dim3(CM_THREADS), 0, a); break;
+    case 3: call.launch(cm_count_kernel<T, 3>, grid, dim3(CM_THREADS), 0, a); break;
+    default: call.launch(cm_count_kernel<T, 4>, grid, dim3(CM_THREADS), 0, a); break;
     }
 }
 
@@ -205,7 +205,7 @@ extern "C" {
 int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, int label_dtype, int64_t n_vox,
                          const int32_t *class_of_value, int n_table, int n_classes, int ignore_value, int64_t *counts,
                          void *stream) {
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
     if (n_pred < 1 || n_pred > CM_MAX_PRED) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: n_pred must be 1..4");
     if (n_classes < 0 || n_classes > CM_MAX_CLASSES) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: n_classes must be 0..255");
     if (n_vox < 0) return fnn_fail(FNN_E_INVALID, "negative voxel count");
@@ -220,17 +220,16 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     if (n_vox == 0) return FNN_OK;
     const size_t esize = label_dtype == FNN_LABEL_U16 ? 2 : 1;
     const int max_value = label_dtype == FNN_LABEL_U16 ? 65535 : 255;
-    if (!ref || !fnn_dev_ptr(ref)) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts needs device label maps (no CPU path)");
-    if ((uintptr_t)ref & 15) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
-    for (int p = 0; p < n_pred; ++p) {
-        if (!pred[p] || !fnn_dev_ptr(pred[p])) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts needs device label maps (no CPU path)");
-        if ((uintptr_t)pred[p] & 15) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
+    for (int p = -1; p < n_pred; ++p) {                              // the reference map, then every prediction
+        const void *map = p < 0 ? ref : pred[p];
+        if (int rc = fnn_need_dev("fnn_confusion_counts", {map}, "device label maps")) return rc;
+        if ((uintptr_t)map & 15) return fnn_fail(FNN_E_INVALID, "fnn_confusion_counts: label maps must be 16-byte aligned");
     }
 
     // the table the kernel reads: values the dtype cannot hold dropped, trailing "other" entries trimmed
     int n_tab = n_table < max_value + 1 ? n_table : max_value + 1;
     while (n_tab > 0 && class_of_value[n_tab - 1] < 0) --n_tab;
-    unsigned char *htab = new unsigned char[n_tab > 0 ? n_tab : 1];
+    std::vector<unsigned char> htab((size_t)(n_tab > 0 ? n_tab : 1));
     for (int v = 0; v < n_tab; ++v) htab[v] = (unsigned char)(class_of_value[v] < 0 ? n_classes : class_of_value[v]);
 
     // reference rows per launch: the whole matrix when it fits the LDS histogram, else bands of rows
@@ -240,7 +239,7 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     int dev = 0, cus = 0;
     hipError_t r = hipGetDevice(&dev);
     if (r == hipSuccess) r = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (r != hipSuccess) { delete[] htab; (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, hipGetErrorString(r)); }
+    if (r != hipSuccess) { (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, hipGetErrorString(r)); }
     const long long per_chunk_vox = (long long)(16 / esize);
     const long long n_chunks = n_vox / per_chunk_vox;
     long long blocks = (n_chunks + CM_THREADS - 1) / CM_THREADS;
@@ -249,47 +248,39 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
     const long long need = (n_vox + CM_MAX_WG_VOX - 1) / CM_MAX_WG_VOX;
     if (blocks < need) blocks = need;
     if (blocks < 1) blocks = 1;
-    if (blocks > INT_MAX) { delete[] htab; return fnn_fail(FNN_E_UNSUPPORTED, "fnn_confusion_counts: volume too large"); }
+    if (blocks > INT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "fnn_confusion_counts: volume too large");
 
     // scratch: counts [n_counts] u64 | counted u64 | table [n_tab] u8
     const size_t off_table = (n_counts + 1) * 8;
-    const size_t bytes = off_table + (size_t)(n_tab > 0 ? n_tab : 1);
-    char *scratch = nullptr;
-    if (hipMalloc((void **)&scratch, bytes) != hipSuccess) {
-        delete[] htab;
-        (void)hipGetLastError();
-        return fnn_fail(FNN_E_HIP, "hipMalloc failed (confusion counts)");
-    }
-    unsigned long long *dcounts = (unsigned long long *)scratch;
-    hipStream_t st = (hipStream_t)stream;
-    r = hipMemsetAsync(scratch, 0, off_table, st);
-    if (r == hipSuccess && n_tab > 0) r = hipMemcpyAsync(scratch + off_table, htab, (size_t)n_tab, hipMemcpyHostToDevice, st);
+    DevBuf scratch;
+    if (!scratch.alloc(off_table + htab.size())) return fnn_fail(FNN_E_HIP, "hipMalloc failed (confusion counts)");
+    unsigned long long *dcounts = scratch.as<unsigned long long>();
+    HipCall call(stream);
+    call.fill(scratch.p, 0, off_table);
+    if (n_tab > 0) call.copy(scratch.as<char>(off_table), htab.data(), (size_t)n_tab, hipMemcpyHostToDevice);
 
     CMArgs a{};
     a.ref = ref;
     for (int p = 0; p < n_pred; ++p) a.pred[p] = pred[p];
     a.n_chunks = n_chunks;
     a.n_vox = n_vox;
-    a.gtable = (const unsigned char *)(scratch + off_table);
+    a.gtable = scratch.as<unsigned char>(off_table);
     a.n_table = n_tab;
     a.n_classes = n_classes;
     a.ignore = ignore_value >= 0 && ignore_value <= max_value ? ignore_value : -1;
     a.counts = dcounts;
     a.counted = dcounts + n_counts;
-    for (int lo = 0; r == hipSuccess && lo < cols; lo += band) {
+    for (int lo = 0; lo < cols; lo += band) {
         a.row_lo = lo;
         a.rows = cols - lo < band ? cols - lo : band;
-        if (label_dtype == FNN_LABEL_U16) launch_np<uint16_t>(n_pred, dim3((unsigned)blocks), st, a);
-        else launch_np<uint8_t>(n_pred, dim3((unsigned)blocks), st, a);
-        r = hipGetLastError();
+        fnn_by_label(label_dtype, [&](auto lt) { launch_np<decltype(lt)>(n_pred, dim3((unsigned)blocks), a, call); });
     }
-    if (r == hipSuccess) r = hipMemcpyAsync(counts, dcounts, (n_counts + 1) * 8 - 8, hipMemcpyDeviceToHost, st);
+    call.copy(counts, dcounts, n_counts * 8, hipMemcpyDeviceToHost);
     unsigned long long counted = 0;
-    if (r == hipSuccess) r = hipMemcpyAsync(&counted, dcounts + n_counts, 8, hipMemcpyDeviceToHost, st);
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    (void)hipFree(scratch);
-    delete[] htab;
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
+    call.copy(&counted, dcounts + n_counts, 8, hipMemcpyDeviceToHost);
+    call.sync();
+    scratch.free();
+    if (!call.ok()) return call.fail();
     // the ("other", "other") bin of every prediction: counted voxels minus every other bin
     const size_t oo = (size_t)n_classes * cols + n_classes;
     for (int p = 0; p < n_pred; ++p) {

@@ -5,11 +5,11 @@
 // around a kernel: convert to fp16 channels-last with padded channels, pack the
 // weights into MFMA fragment order, provide the producer-side InstanceNorm
 // statistics, launch, convert back.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -18,12 +18,11 @@ namespace {
 inline int pad16(int c) { return (c + 15) / 16 * 16; }
 inline float h2f_bits(uint16_t b) { f16 h; memcpy(&h, &b, 2); return (float)h; }
 
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t n) { return hipMalloc(&p, n ? n : 16) == hipSuccess; }
-    template <class T> T *as() { return (T *)p; }
-};
+// Element (batch item b, channel ch, voxel v) of a device tensor of cp (padded) channels: channels-last [n][vox][cp], or
+// chunk-major [n][cp / 16][vox][16] (fnn_device.h, SrcDesc)
+inline size_t layout_index(bool chunk_major, int b, int ch, size_t v, int cp, size_t vox) {
+    return chunk_major ? ((size_t)b * cp / 16 + ch / 16) * vox * 16 + v * 16 + ch % 16 : ((size_t)b * vox + v) * cp + ch;
+}
 
 // NCDHW fp32 -> NDHWC fp16 with channel padding; also the per-(n,c) statistics of the rounded values
 // FNN_OP_CHUNK_MAJOR=1 (next to FNN_KNOBS=1; read per call): tensors of more than 16 channels travel chunk-major
@@ -42,7 +41,7 @@ void to_ndhwc(const float *x, int n, int c, int cp, size_t vox, std::vector<uint
             const float *src = x + ((size_t)b * c + ch) * vox;
             for (size_t v = 0; v < vox; ++v) {
                 const uint16_t hb = fnn_half_bits(src[v]);
-                out[cm ? ((size_t)b * cp / 16 + ch / 16) * vox * 16 + v * 16 + ch % 16 : ((size_t)b * vox + v) * cp + ch] = hb;
+                out[layout_index(cm, b, ch, v, cp, vox)] = hb;
                 const double f = h2f_bits(hb);
                 s1 += f; s2 += f * f;
             }
@@ -102,8 +101,7 @@ void from_device_layout(const std::vector<uint16_t> &ho, int n, int c, int cp, s
     for (int b = 0; b < n; ++b)
         for (int ch = 0; ch < c; ++ch)
             for (size_t v = 0; v < vox; ++v)
-                y[((size_t)b * c + ch) * vox + v] =
-                    h2f_bits(ho[cm ? ((size_t)b * cp / 16 + ch / 16) * vox * 16 + v * 16 + ch % 16 : ((size_t)b * vox + v) * cp + ch]);
+                y[((size_t)b * c + ch) * vox + v] = h2f_bits(ho[layout_index(cm, b, ch, v, cp, vox)]);
 }
 
 // a body-op operand: make_src with the layout as an argument and the slope applied with or without a norm, as the kernels do
@@ -249,8 +247,7 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     for (int b = 0; b < n; ++b)
         for (int co = 0; co < cout; ++co) {
             for (size_t v = 0; v < ovox; ++v)
-                y[((size_t)b * cout + co) * ovox + v] =
-                    h2f_bits(ho[ocm ? ((size_t)b * cop / 16 + co / 16) * ovox * 16 + v * 16 + co % 16 : ((size_t)b * ovox + v) * cop + co]);
+                y[((size_t)b * cout + co) * ovox + v] = h2f_bits(ho[layout_index(ocm, b, co, v, cop, ovox)]);
             if (stats_out) {
                 double a = 0, q = 0;
                 for (size_t r = 0; r < slots; ++r) {
@@ -296,11 +293,7 @@ int fnn_op_conv_transpose3d(int device, int n, const int dims[3],
     if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
     std::vector<uint16_t> ho((size_t)n * ovox * cop);
     (void)hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost);
-    for (int b = 0; b < n; ++b)
-        for (int co = 0; co < cout; ++co)
-            for (size_t v = 0; v < ovox; ++v)
-                y[((size_t)b * cout + co) * ovox + v] =
-                    h2f_bits(ho[ocm ? ((size_t)b * cop / 16 + co / 16) * ovox * 16 + v * 16 + co % 16 : ((size_t)b * ovox + v) * cop + co]);
+    from_device_layout(ho, n, cout, cop, ovox, ocm, y);
     return 0;
 }
 
@@ -494,8 +487,7 @@ int fnn_op_patch_input(int device, const float *vol, int n_vol, int c, const lon
     for (int b = 0; b < n; ++b)
         for (int ch = 0; ch < cpad; ++ch)
             for (size_t v = 0; v < P; ++v)
-                out[((size_t)b * cpad + ch) * P + v] =
-                    ho[chunk_major ? ((size_t)b * cpad / 16 + ch / 16) * P * 16 + v * 16 + ch % 16 : ((size_t)b * P + v) * cpad + ch];
+                out[((size_t)b * cpad + ch) * P + v] = ho[layout_index(chunk_major != 0, b, ch, v, cpad, P)];
     return 0;
 }
 
@@ -539,8 +531,12 @@ __global__ void clock_probe_kernel(unsigned long long *out, const int *flag, uns
 struct ClockProbe {
     int device = 0;
     hipStream_t st = nullptr;
-    unsigned long long *out = nullptr;
+    DevBuf out;                                               // 4 x u64
     int *flag = nullptr;                                      // mapped host memory
+    ~ClockProbe() {
+        if (flag) (void)hipHostFree(flag);
+        if (st) (void)hipStreamDestroy(st);
+    }
 };
 }  // namespace
 
@@ -548,35 +544,29 @@ int fnn_clock_probe_start(int device, double max_seconds, void **probe) {
     if (!probe || !(max_seconds > 0) || max_seconds > 60) return FNN_E_INVALID;
     *probe = nullptr;
     if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
-    ClockProbe *c = new ClockProbe;
+    std::unique_ptr<ClockProbe> c(new ClockProbe);
     c->device = device;
     int *dflag = nullptr;
-    if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || hipMalloc((void **)&c->out, 32) != hipSuccess ||
+    if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || !c->out.alloc(32) ||
         hipHostMalloc((void **)&c->flag, sizeof(int), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&dflag, c->flag, 0) != hipSuccess) {
-        if (c->flag) (void)hipHostFree(c->flag);
-        if (c->out) (void)hipFree(c->out);
-        if (c->st) (void)hipStreamDestroy(c->st);
-        delete c;
+        hipHostGetDevicePointer((void **)&dflag, c->flag, 0) != hipSuccess)
         return FNN_E_HIP;
-    }
     *c->flag = 0;
-    (void)hipMemsetAsync(c->out, 0, 32, c->st);
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, c->st, c->out, dflag, (unsigned long long)(max_seconds * 1e8));
-    if (hipGetLastError() != hipSuccess) { (void)hipHostFree(c->flag); (void)hipFree(c->out); (void)hipStreamDestroy(c->st); delete c; return FNN_E_HIP; }
-    *probe = c;
+    (void)hipMemsetAsync(c->out.p, 0, 32, c->st);
+    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, c->st, c->out.as<unsigned long long>(), dflag, (unsigned long long)(max_seconds * 1e8));
+    if (hipGetLastError() != hipSuccess) return FNN_E_HIP;
+    *probe = c.release();
     return FNN_OK;
 }
 
 int fnn_clock_probe_stop(void *probe, double *ghz, double *seconds) {
-    ClockProbe *c = (ClockProbe *)probe;
+    std::unique_ptr<ClockProbe> c((ClockProbe *)probe);
     if (!c) return FNN_E_INVALID;
     (void)hipSetDevice(c->device);
     __atomic_store_n(c->flag, 1, __ATOMIC_RELEASE);
     unsigned long long h[4] = {0, 0, 0, 0};
-    const bool ok = hipStreamSynchronize(c->st) == hipSuccess && hipMemcpy(h, c->out, 32, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipHostFree(c->flag); (void)hipFree(c->out); (void)hipStreamDestroy(c->st);
-    delete c;
+    const bool ok = hipStreamSynchronize(c->st) == hipSuccess && hipMemcpy(h, c->out.p, 32, hipMemcpyDeviceToHost) == hipSuccess;
+    c.reset();
     if (!ok || h[1] == 0) return FNN_E_HIP;
     if (ghz) *ghz = (double)h[0] / (double)h[1] * 0.1;        // s_memrealtime: 100 MHz
     if (seconds) *seconds = (double)h[1] * 1e-8;

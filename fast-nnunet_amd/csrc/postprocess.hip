@@ -20,9 +20,9 @@
 // Per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores: inside phases 2 and 3 every
 // read of parent[] is an agent-scope relaxed atomic load (sc1), and every write an agent-scope atomic.  A stale read
 // only costs a retry: the atomicMin's returned value is the truth.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <climits>
+#include <vector>
 
 namespace {
 
@@ -279,21 +279,21 @@ __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(T *labels, const i
 }
 
 template <typename T>
-hipError_t launch_all(T *labels, const int *table, const CCGeom &g, int n, int n_groups, T background, int *parent, int *size,
-                      int *gmax, unsigned long long *removed, hipStream_t st) {
+void launch_all(T *labels, const int *table, const CCGeom &g, int n, int n_groups, T background, int *parent, int *size,
+                int *gmax, unsigned long long *removed, HipCall &call) {
     const long long tiles = (long long)((g.X + (1 << g.sx) - 1) >> g.sx) * g.tiles_y * g.tiles_z;
     const unsigned vox_blocks = (unsigned)((n + CC_THREADS - 1) / CC_THREADS);
     const unsigned run_blocks = (unsigned)(((long long)n + (long long)CC_THREADS * CC_RUN - 1) / ((long long)CC_THREADS * CC_RUN));
     const unsigned red_blocks = vox_blocks < 2048u ? vox_blocks : 2048u;
-    hipLaunchKernelGGL(cc_tile_merge_kernel<T>, dim3((unsigned)tiles), dim3(CC_THREADS), 0, st, labels, table, g, parent);
-    hipLaunchKernelGGL(cc_cross_merge_kernel<T>, dim3((unsigned)tiles), dim3(CC_THREADS), 0, st, labels, table, g, parent);
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(vox_blocks), dim3(CC_THREADS), 0, st, parent, n);
-    hipLaunchKernelGGL(cc_count_kernel, dim3(run_blocks), dim3(CC_THREADS), 0, st, parent, n, size);
-    hipLaunchKernelGGL(cc_group_max_kernel<T>, dim3(red_blocks), dim3(CC_THREADS), 0, st, labels, table, g.n_table, parent, size, n,
-                       n_groups, gmax);
-    hipLaunchKernelGGL(cc_apply_kernel<T>, dim3(red_blocks), dim3(CC_THREADS), 0, st, labels, table, g.n_table, parent, size, gmax,
-                       n, n_groups, background, removed);
-    return hipGetLastError();
+    const dim3 block(CC_THREADS);
+    call.launch(cc_tile_merge_kernel<T>, dim3((unsigned)tiles), block, 0, labels, table, g, parent);
+    call.launch(cc_cross_merge_kernel<T>, dim3((unsigned)tiles), block, 0, labels, table, g, parent);
+    call.launch(cc_flatten_kernel, dim3(vox_blocks), block, 0, parent, n);
+    call.launch(cc_count_kernel, dim3(run_blocks), block, 0, parent, n, size);
+    call.launch(cc_group_max_kernel<T>, dim3(red_blocks), block, 0, labels, table, g.n_table, parent,
+                size, n, n_groups, gmax);
+    call.launch(cc_apply_kernel<T>, dim3(red_blocks), block, 0, labels, table, g.n_table, parent, size,
+                gmax, n, n_groups, background, removed);
 }
 
 }  // namespace
@@ -303,7 +303,7 @@ extern "C" {
 int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t shape[3], const int32_t *group_of_label, int n_table,
                                 int n_groups, int background_label, int64_t *removed, void *stream) {
     if (!shape) return fnn_fail(FNN_E_INVALID, "NULL shape");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
     const int max_label = label_dtype == FNN_LABEL_U16 ? 65535 : 255;
     if (background_label < 0 || background_label > max_label) return fnn_fail(FNN_E_INVALID, "background_label outside the label dtype");
     if (shape[0] < 0 || shape[1] < 0 || shape[2] < 0) return fnn_fail(FNN_E_INVALID, "negative shape");
@@ -316,7 +316,7 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
     if (shape[0] > INT_MAX || shape[1] > INT_MAX || shape[2] > INT_MAX || shape[0] * shape[1] > INT_MAX ||
         shape[0] * shape[1] * shape[2] > INT_MAX)
         return fnn_fail(FNN_E_UNSUPPORTED, "fnn_keep_largest_components: more than 2^31 - 1 voxels");
-    if (!labels || !fnn_dev_ptr(labels)) return fnn_fail(FNN_E_INVALID, "fnn_keep_largest_components needs a device label map (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_keep_largest_components", {labels}, "a device label map")) return rc;
     const int n_tab = n_table < max_label + 1 ? n_table : max_label + 1;      // labels the dtype cannot hold are never looked up
     if (n_groups == 0 || n_tab == 0) return FNN_OK;                              // no set: nothing changes
     const int n = (int)(shape[0] * shape[1] * shape[2]);
@@ -334,33 +334,22 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
     // one scratch block: parent [n] | size [n] | table [n_tab] | gmax [n_groups] | removed [n_groups] (8-B aligned)
     const size_t off_size = (size_t)n * 4, off_table = off_size + (size_t)n * 4, off_gmax = off_table + (size_t)n_tab * 4;
     const size_t off_removed = (off_gmax + (size_t)n_groups * 4 + 7) & ~(size_t)7;
-    const size_t bytes = off_removed + (size_t)n_groups * 8;
-    char *scratch = nullptr;
-    if (hipMalloc((void **)&scratch, bytes) != hipSuccess) { (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, "hipMalloc failed (8 B per voxel of scratch)"); }
-    int *parent = (int *)scratch, *size = (int *)(scratch + off_size), *table = (int *)(scratch + off_table);
-    int *gmax = (int *)(scratch + off_gmax);
-    unsigned long long *rem = (unsigned long long *)(scratch + off_removed);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t r = hipMemcpyAsync(table, group_of_label, (size_t)n_tab * 4, hipMemcpyHostToDevice, st);
-    if (r == hipSuccess) r = hipMemsetAsync(size, 0, (size_t)n * 4, st);
-    if (r == hipSuccess) r = hipMemsetAsync(gmax, 0, (size_t)(off_removed - off_gmax) + (size_t)n_groups * 8, st);
-    if (r == hipSuccess) {
-        if (label_dtype == FNN_LABEL_U16)
-            r = launch_all<uint16_t>((uint16_t *)labels, table, g, n, n_groups, (uint16_t)background_label, parent, size, gmax, rem, st);
-        else
-            r = launch_all<uint8_t>((uint8_t *)labels, table, g, n, n_groups, (uint8_t)background_label, parent, size, gmax, rem, st);
-    }
-    unsigned long long *hrem = nullptr;
-    if (r == hipSuccess && removed && n_groups > 0) {
-        hrem = new unsigned long long[n_groups];
-        r = hipMemcpyAsync(hrem, rem, (size_t)n_groups * 8, hipMemcpyDeviceToHost, st);
-    }
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (r == hipSuccess && hrem)
-        for (int k = 0; k < n_groups; ++k) removed[k] = (int64_t)hrem[k];
-    delete[] hrem;
-    (void)hipFree(scratch);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
+    DevBuf scratch;
+    if (!scratch.alloc(off_removed + (size_t)n_groups * 8)) return fnn_fail(FNN_E_HIP, "hipMalloc failed (8 B per voxel of scratch)");
+    int *parent = scratch.as<int>(), *size = scratch.as<int>(off_size), *table = scratch.as<int>(off_table), *gmax = scratch.as<int>(off_gmax);
+    unsigned long long *rem = scratch.as<unsigned long long>(off_removed);
+    HipCall call(stream);
+    call.copy(table, group_of_label, (size_t)n_tab * 4, hipMemcpyHostToDevice);
+    call.fill(size, 0, (size_t)n * 4);
+    call.fill(gmax, 0, (size_t)(off_removed - off_gmax) + (size_t)n_groups * 8);
+    fnn_by_label(label_dtype, [&](auto lt) {
+        using LT = decltype(lt);
+        launch_all<LT>((LT *)labels, table, g, n, n_groups, (LT)background_label, parent, size, gmax, rem, call);
+    });
+    std::vector<unsigned long long> hrem(removed ? (size_t)n_groups : 0);
+    if (removed) call.copy(hrem.data(), rem, (size_t)n_groups * 8, hipMemcpyDeviceToHost);
+    if (!call.sync()) return call.fail();
+    for (size_t k = 0; k < hrem.size(); ++k) removed[k] = (int64_t)hrem[k];
     return FNN_OK;
 }
 

@@ -9,8 +9,7 @@
 // All three are HBM-bound element-wise / reduction kernels: one pass over the raw volume for the box, one pass
 // for the statistics of the schemes that need them (two for ZScore: the mean, then the squared deviations about it),
 // one read + one write for the result.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <cfloat>
 #include <climits>
 #include <cstdio>
@@ -194,19 +193,12 @@ __global__ __launch_bounds__(256) void apply_kernel(const float *raw, PrepParams
 
 // ---- labels [b0][b1][b2] (transposed, cropped) -> out [s0][s1][s2] in the original axis order
 template <typename LT>
-__global__ __launch_bounds__(256) void revert_kernel(const LT *seg, long long lo0, long long lo1, long long lo2, long long e0,
-                                                     long long e1, long long e2, long long o0, long long o1, long long o2,
-                                                     int tb0, int tb1, int tb2, LT *out) {
-    const long long n = o0 * o1 * o2;
+__global__ __launch_bounds__(256) void revert_kernel(const LT *seg, CropBox b, LT *out) {
+    const long long n = b.o[0] * b.o[1] * b.o[2];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const long long oc[3] = {i / (o1 * o2), (i / o2) % o1, i % o2};
-    long long t[3];
-    t[tb0] = oc[0]; t[tb1] = oc[1]; t[tb2] = oc[2];                     // out axis j = transposed axis tb[j]
-    const long long d0 = t[0] - lo0, d1 = t[1] - lo1, d2 = t[2] - lo2;
-    LT v = 0;
-    if (d0 >= 0 && d0 < e0 && d1 >= 0 && d1 < e1 && d2 >= 0 && d2 < e2) v = seg[(d0 * e1 + d1) * e2 + d2];
-    out[i] = v;
+    size_t v;
+    out[i] = crop_box_voxel(b, i, v) ? seg[v] : (LT)0;
 }
 
 // ---- logits [H][b0][b1][b2] (transposed, cropped grid) -> probabilities [H][s0][s1][s2] + labels [s0][s1][s2] on the
@@ -214,23 +206,18 @@ __global__ __launch_bounds__(256) void revert_kernel(const LT *seg, long long lo
 // probabilities, both reverted croppings (background probability 1 outside the box for plain labels), transposes back.
 // expf / the division follow the device's fp32 library: probabilities agree with torch's CPU softmax to ~1e-7.
 template <typename IT, typename LT>
-__global__ __launch_bounds__(256) void export_prob_kernel(const IT *logits, int H, const int *order, long long lo0, long long lo1,
-                                                          long long lo2, long long e0, long long e1, long long e2, long long o0,
-                                                          long long o1, long long o2, int tb0, int tb1, int tb2, float *probs,
+__global__ __launch_bounds__(256) void export_prob_kernel(const IT *logits, int H, const int *order, CropBox b, float *probs,
                                                           LT *labels) {
-    const long long n = o0 * o1 * o2;
+    const long long n = b.o[0] * b.o[1] * b.o[2];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const long long oc[3] = {i / (o1 * o2), (i / o2) % o1, i % o2};
-    long long t[3];
-    t[tb0] = oc[0]; t[tb1] = oc[1]; t[tb2] = oc[2];
-    const long long d0 = t[0] - lo0, d1 = t[1] - lo1, d2 = t[2] - lo2;
-    if (!(d0 >= 0 && d0 < e0 && d1 >= 0 && d1 < e1 && d2 >= 0 && d2 < e2)) {
+    size_t v;
+    if (!crop_box_voxel(b, i, v)) {
         for (int h = 0; h < H; ++h) probs[(size_t)h * n + i] = (!order && h == 0) ? 1.f : 0.f;
         labels[i] = 0;
         return;
     }
-    const size_t plane = (size_t)e0 * e1 * e2, v = ((size_t)d0 * e1 + d1) * e2 + d2;
+    const size_t plane = (size_t)b.e[0] * b.e[1] * b.e[2];
     if (order) {
         int seg = 0;
         for (int h = 0; h < H; ++h) {
@@ -255,10 +242,71 @@ __global__ __launch_bounds__(256) void export_prob_kernel(const IT *logits, int 
     labels[i] = (LT)arg;
 }
 
-static int check_perm(const int32_t t[3]) {
-    int seen = 0;
-    for (int i = 0; i < 3; ++i) { if (t[i] < 0 || t[i] > 2) return -1; seen |= 1 << t[i]; }
-    return seen == 7 ? 0 : -1;
+// ---- seg = where(binary_fill_holes(nonzero_mask), 0, -1) of crop_to_nonzero (cropping.py:19-39), as a byte map of the n
+// voxels of the crop box.  FNN_OK also when a HIP call failed: that stays in the call's status
+static int fill_holes_mask(const float *raw, const PrepParams &p, long long n, uint8_t *mask, HipCall &call) {
+    DevBuf changed;
+    if (!changed.alloc(sizeof(int))) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
+    call.launch(mask_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, raw, p, mask);
+    // Iterations until one changes nothing.  Each one before it turns at least one voxel outside, so no box takes more
+    // than n + 1 (a corridor that winds through a thin box does take thousands): running out of them is an error,
+    // never a mask that is silently wrong.
+    bool converged = false;
+    for (long long iter = 0; iter <= n && call.ok() && !converged; ++iter) {
+        int h = 0;
+        call.copy(changed.p, &h, sizeof(int), hipMemcpyHostToDevice);
+        for (int axis = 0; axis < 3; ++axis) {
+            // a thread per line where that makes 64 Ki threads, else the lines cut into segments of 32 voxels or more
+            const long long lines = n / p.ext[axis];
+            const long long cuts = lines >= 65536 ? 1 : (65536 + lines - 1) / lines;
+            long long seg = (p.ext[axis] + cuts - 1) / cuts;
+            seg = seg < 32 ? 32 : seg;
+            const long long threads = lines * ((p.ext[axis] + seg - 1) / seg);
+            call.launch(mask_sweep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p, axis, seg, mask, changed.as<int>());
+        }
+        call.copy(&h, changed.p, sizeof(int), hipMemcpyDeviceToHost);
+        converged = call.sync() && !h;
+    }
+    if (call.ok() && !converged) return fnn_fail(FNN_E_HIP, "the fill-holes sweeps of the non-zero mask did not converge");
+    return FNN_OK;
+}
+
+// ---- ZScore / RescaleTo01: the statistics of channel c over the crop box -> p.a[c], p.b[c].  sc: 5 doubles of device
+// scratch (sum, sum of squares, count | min, max as ordered unsigned)
+static void channel_stats(const float *raw, PrepParams &p, int c, long long n, double *sc, HipCall &call) {
+    unsigned *mm = (unsigned *)(sc + 3);
+    const double z[3] = {0, 0, 0};
+    const unsigned mi[2] = {0xffffffffu, 0u};
+    double hs[3]; unsigned hm[2];
+    long long blocks = (n + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    auto pass = [&](double shift) {
+        call.copy(sc, z, sizeof(z), hipMemcpyHostToDevice);
+        call.launch(stats_kernel, dim3((unsigned)blocks), dim3(256), 0, raw, p, c, shift, sc, mm);
+        call.copy(hs, sc, sizeof(hs), hipMemcpyDeviceToHost);
+    };
+    call.copy(mm, mi, sizeof(mi), hipMemcpyHostToDevice);
+    pass(0.0);
+    call.copy(hm, mm, sizeof(hm), hipMemcpyDeviceToHost);
+    if (!call.sync()) return;
+    if (p.scheme[c] == FNN_NORM_ZSCORE) {
+        const double cntd = hs[2] > 0 ? hs[2] : 1.0;             // voxels inside the mask (all of them without one)
+        const double mean = hs[0] / cntd;
+        // second pass: the squared deviations about the mean (and the sum of the deviations, which takes out
+        // what the rounding of the mean left in)
+        pass(mean);
+        if (!call.sync()) return;
+        const double dev = hs[0] / cntd;
+        double var = hs[1] / cntd - dev * dev;
+        var = var < 0 ? 0 : var;                                      // NaN stays NaN, like numpy's std
+        const float stdf = (float)sqrt(var);
+        p.a[c] = (float)mean; p.b[c] = 1e-8f > stdf ? 1e-8f : stdf;   // python's max(std, 1e-8): a NaN std stays
+    } else {
+        auto unord = [](unsigned u) { u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; return __builtin_bit_cast(float, u); };
+        const float mn = unord(hm[0]), mx = unord(hm[1]);
+        const float range = mx - mn;                                   // = (image - image.min()).max() in fp32
+        p.a[c] = mn; p.b[c] = range < 1e-8f ? 1e-8f : range;            // np.clip(max, 1e-8, None): NaN stays NaN
+    }
 }
 
 }  // namespace
@@ -267,26 +315,24 @@ extern "C" {
 
 int fnn_nonzero_bbox(const float *raw, const int64_t shape[4], const int32_t transpose_forward[3], int64_t bbox[6], void *stream) {
     if (!raw || !shape || !transpose_forward || !bbox) return fnn_fail(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_forward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_forward is not a permutation of (0, 1, 2)");
+    if (int rc = fnn_check_perm(transpose_forward, "transpose_forward")) return rc;
     if (shape[0] < 1 || shape[0] > 8 || shape[1] < 1 || shape[2] < 1 || shape[3] < 1) return fnn_fail(FNN_E_INVALID, "bad shape (1..8 channels)");
-    if (!fnn_dev_ptr(raw)) return fnn_fail(FNN_E_INVALID, "fnn_nonzero_bbox needs a device pointer (no CPU path)");
-    hipStream_t st = (hipStream_t)stream;
+    if (int rc = fnn_need_dev("fnn_nonzero_bbox", {raw}, "a device pointer")) return rc;
     PrepGeom g{};
     for (int d = 0; d < 3; ++d) { g.s[d] = shape[1 + d]; g.tf[d] = transpose_forward[d]; }
     g.C = (int)shape[0];
-    int *box = nullptr;
-    if (hipMalloc((void **)&box, 6 * sizeof(int)) != hipSuccess) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
+    DevBuf box;
+    if (!box.alloc(6 * sizeof(int))) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
     const int init[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
     int h[6];
-    hipError_t r = hipMemcpyAsync(box, init, sizeof(init), hipMemcpyHostToDevice, st);
     const long long n = g.s[0] * g.s[1] * g.s[2];
     long long blocks = (n + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
-    if (r == hipSuccess) { hipLaunchKernelGGL(bbox_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, g, box); r = hipGetLastError(); }
-    if (r == hipSuccess) r = hipMemcpyAsync(h, box, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    (void)hipFree(box);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
+    HipCall call(stream);
+    call.copy(box.p, init, sizeof(init), hipMemcpyHostToDevice);
+    call.launch(bbox_kernel, dim3((unsigned)blocks), dim3(256), 0, raw, g, box.as<int>());
+    call.copy(h, box.p, sizeof(h), hipMemcpyDeviceToHost);
+    if (!call.sync()) return call.fail();
     for (int a = 0; a < 3; ++a) {
         if (h[3 + a] < 0) { bbox[2 * a] = 0; bbox[2 * a + 1] = shape[1 + transpose_forward[a]]; }   // empty mask: the full extent
         else { bbox[2 * a] = h[a]; bbox[2 * a + 1] = h[3 + a] + 1; }
@@ -297,191 +343,86 @@ int fnn_nonzero_bbox(const float *raw, const int64_t shape[4], const int32_t tra
 int fnn_preprocess(const float *raw, const int64_t shape[4], const int32_t transpose_forward[3], const int64_t bbox[6],
                    const fnn_norm_desc *norm, float *out, void *stream) {
     if (!raw || !shape || !transpose_forward || !bbox || !norm || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_forward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_forward is not a permutation of (0, 1, 2)");
+    if (int rc = fnn_check_perm(transpose_forward, "transpose_forward")) return rc;
     if (shape[0] < 1 || shape[0] > 8) return fnn_fail(FNN_E_INVALID, "1..8 channels");
-    if (!fnn_dev_ptr(raw) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_preprocess needs device pointers (no CPU path)");
-    hipStream_t st = (hipStream_t)stream;
+    if (int rc = fnn_need_dev("fnn_preprocess", {raw, out})) return rc;
     PrepParams p{};
-    for (int d = 0; d < 3; ++d) { p.g.s[d] = shape[1 + d]; p.g.tf[d] = transpose_forward[d]; }
+    int64_t transposed[3];
+    for (int d = 0; d < 3; ++d) { p.g.s[d] = shape[1 + d]; p.g.tf[d] = transpose_forward[d]; transposed[d] = shape[1 + transpose_forward[d]]; }
     p.g.C = (int)shape[0];
-    for (int a = 0; a < 3; ++a) {
-        p.lo[a] = bbox[2 * a]; p.ext[a] = bbox[2 * a + 1] - bbox[2 * a];
-        if (p.lo[a] < 0 || p.ext[a] < 1 || bbox[2 * a + 1] > shape[1 + transpose_forward[a]]) return fnn_fail(FNN_E_INVALID, "bbox outside the (transposed) image");
-    }
-    const long long n = p.ext[0] * p.ext[1] * p.ext[2];
-    double *sums = nullptr;
-    if (hipMalloc((void **)&sums, 8 * 5 * sizeof(double)) != hipSuccess) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
-    hipError_t r = hipSuccess;
+    CropBox box{};
+    if (int rc = crop_box_fill(box, bbox, transposed, nullptr, "bbox outside the (transposed) image")) return rc;
+    for (int a = 0; a < 3; ++a) { p.lo[a] = box.lo[a]; p.ext[a] = box.e[a]; }
+    // every channel's scheme before the first device call: an unknown one is refused with nothing run.  The mask and
+    // statistics kernels therefore see scheme / lower / upper (and CT's a, b) of all channels filled in; they read use_mask,
+    // mask and the shape only, and must not come to rely on the rest either way
     bool want_mask = false;
     for (int c = 0; c < p.g.C; ++c) {
-        p.use_mask[c] = norm[c].scheme == FNN_NORM_ZSCORE && norm[c].use_mask;
-        want_mask |= p.use_mask[c] != 0;
-    }
-    uint8_t *mask = nullptr;
-    if (want_mask) {
-        // seg = where(binary_fill_holes(nonzero_mask), 0, -1) of crop_to_nonzero (cropping.py:19-39), as a byte map
-        int *changed = nullptr;
-        if (hipMalloc((void **)&mask, (size_t)n) != hipSuccess || hipMalloc((void **)&changed, sizeof(int)) != hipSuccess) {
-            (void)hipFree(sums); (void)hipFree(mask);
-            return fnn_fail(FNN_E_HIP, "hipMalloc failed");
-        }
-        hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, raw, p, mask);
-        // Iterations until one changes nothing.  Each one before it turns at least one voxel outside, so no box takes more
-        // than n + 1 (a corridor that winds through a thin box does take thousands): running out of them is an error,
-        // never a mask that is silently wrong.
-        bool converged = false;
-        for (long long iter = 0; iter <= n && r == hipSuccess && !converged; ++iter) {
-            int h = 0;
-            r = hipMemcpyAsync(changed, &h, sizeof(int), hipMemcpyHostToDevice, st);
-            for (int axis = 0; axis < 3 && r == hipSuccess; ++axis) {
-                // a thread per line where that makes 64 Ki threads, else the lines cut into segments of 32 voxels or more
-                const long long lines = n / p.ext[axis];
-                const long long cuts = lines >= 65536 ? 1 : (65536 + lines - 1) / lines;
-                long long seg = (p.ext[axis] + cuts - 1) / cuts;
-                seg = seg < 32 ? 32 : seg;
-                const long long threads = lines * ((p.ext[axis] + seg - 1) / seg);
-                hipLaunchKernelGGL(mask_sweep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, axis, seg, mask, changed);
-                r = hipGetLastError();
-            }
-            if (r == hipSuccess) r = hipMemcpyAsync(&h, changed, sizeof(int), hipMemcpyDeviceToHost, st);
-            if (r == hipSuccess) r = hipStreamSynchronize(st);
-            converged = r == hipSuccess && !h;
-        }
-        (void)hipFree(changed);
-        if (r == hipSuccess && !converged) {
-            (void)hipFree(sums); (void)hipFree(mask);
-            return fnn_fail(FNN_E_HIP, "the fill-holes sweeps of the non-zero mask did not converge");
-        }
-        p.mask = mask;
-    }
-    for (int c = 0; c < p.g.C && r == hipSuccess; ++c) {
         const fnn_norm_desc &d = norm[c];
+        if (d.scheme != FNN_NORM_NONE && d.scheme != FNN_NORM_ZSCORE && d.scheme != FNN_NORM_CT && d.scheme != FNN_NORM_RESCALE01 &&
+            d.scheme != FNN_NORM_RGB01)
+            return fnn_fail(FNN_E_UNSUPPORTED, "unknown normalisation scheme");
         p.scheme[c] = d.scheme;
         p.a[c] = 0.f; p.b[c] = 1.f; p.lower[c] = d.lower; p.upper[c] = d.upper;
-        if (d.scheme == FNN_NORM_CT) {
-            p.a[c] = d.mean; p.b[c] = d.std > 1e-8f ? d.std : 1e-8f;           // max(std_intensity, 1e-8)
-        } else if (d.scheme == FNN_NORM_ZSCORE || d.scheme == FNN_NORM_RESCALE01) {
-            // statistics of this channel over the crop box
-            double *sc = sums + c * 5;
-            unsigned *mm = (unsigned *)(sc + 3);
-            const double z[3] = {0, 0, 0};
-            const unsigned mi[2] = {0xffffffffu, 0u};
-            double hs[3]; unsigned hm[2];
-            r = hipMemcpyAsync(sc, z, sizeof(z), hipMemcpyHostToDevice, st);
-            if (r == hipSuccess) r = hipMemcpyAsync(mm, mi, sizeof(mi), hipMemcpyHostToDevice, st);
-            long long blocks = (n + 255) / 256;
-            if (blocks > 256 * 16) blocks = 256 * 16;
-            if (r == hipSuccess) { hipLaunchKernelGGL(stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, p, c, 0.0, sc, mm); r = hipGetLastError(); }
-            if (r == hipSuccess) r = hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, st);
-            if (r == hipSuccess) r = hipMemcpyAsync(hm, mm, sizeof(hm), hipMemcpyDeviceToHost, st);
-            if (r == hipSuccess) r = hipStreamSynchronize(st);
-            if (r != hipSuccess) break;
-            auto unord = [](unsigned u) { u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; return __builtin_bit_cast(float, u); };
-            if (d.scheme == FNN_NORM_ZSCORE) {
-                const double cntd = hs[2] > 0 ? hs[2] : 1.0;             // voxels inside the mask (all of them without one)
-                const double mean = hs[0] / cntd;
-                // second pass: the squared deviations about the mean (and the sum of the deviations, which takes out
-                // what the rounding of the mean left in)
-                r = hipMemcpyAsync(sc, z, sizeof(z), hipMemcpyHostToDevice, st);
-                if (r == hipSuccess) { hipLaunchKernelGGL(stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, raw, p, c, mean, sc, mm); r = hipGetLastError(); }
-                if (r == hipSuccess) r = hipMemcpyAsync(hs, sc, sizeof(hs), hipMemcpyDeviceToHost, st);
-                if (r == hipSuccess) r = hipStreamSynchronize(st);
-                if (r != hipSuccess) break;
-                const double dev = hs[0] / cntd;
-                double var = hs[1] / cntd - dev * dev;
-                var = var < 0 ? 0 : var;                                      // NaN stays NaN, like numpy's std
-                const float stdf = (float)sqrt(var);
-                p.a[c] = (float)mean; p.b[c] = 1e-8f > stdf ? 1e-8f : stdf;   // python's max(std, 1e-8): a NaN std stays
-            } else {
-                const float mn = unord(hm[0]), mx = unord(hm[1]);
-                const float range = mx - mn;                                   // = (image - image.min()).max() in fp32
-                p.a[c] = mn; p.b[c] = range < 1e-8f ? 1e-8f : range;            // np.clip(max, 1e-8, None): NaN stays NaN
-            }
-        } else if (d.scheme != FNN_NORM_NONE && d.scheme != FNN_NORM_RGB01) {
-            (void)hipFree(sums); (void)hipFree(mask);
-            return fnn_fail(FNN_E_UNSUPPORTED, "unknown normalisation scheme");
-        }
+        if (d.scheme == FNN_NORM_CT) { p.a[c] = d.mean; p.b[c] = d.std > 1e-8f ? d.std : 1e-8f; }   // max(std_intensity, 1e-8)
+        p.use_mask[c] = d.scheme == FNN_NORM_ZSCORE && d.use_mask;
+        want_mask |= p.use_mask[c] != 0;
     }
-    if (r == hipSuccess) {
-        const long long total = n * p.g.C;
-        hipLaunchKernelGGL(apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, raw, p, out);
-        r = hipGetLastError();
+    const long long n = p.ext[0] * p.ext[1] * p.ext[2];
+    DevBuf sums, mask;
+    if (!sums.alloc(8 * 5 * sizeof(double)) || (want_mask && !mask.alloc((size_t)n))) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
+    HipCall call(stream);
+    if (want_mask) {
+        if (int rc = fill_holes_mask(raw, p, n, mask.as<uint8_t>(), call)) return rc;
+        p.mask = mask.as<uint8_t>();
     }
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    (void)hipFree(sums);
-    (void)hipFree(mask);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
-    return FNN_OK;
+    for (int c = 0; c < p.g.C; ++c)
+        if (p.scheme[c] == FNN_NORM_ZSCORE || p.scheme[c] == FNN_NORM_RESCALE01) channel_stats(raw, p, c, n, sums.as<double>() + c * 5, call);
+    call.launch(apply_kernel, dim3((unsigned)((n * p.g.C + 255) / 256)), dim3(256), 0, raw, p, out);
+    return call.finish();
 }
 
 int fnn_revert_labels(const void *seg, int label_dtype, const int64_t bbox[6], const int64_t shape_before_cropping[3],
                       const int32_t transpose_backward[3], void *out, void *stream) {
     if (!seg || !bbox || !shape_before_cropping || !transpose_backward || !out) return fnn_fail(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_backward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
-    if (!fnn_dev_ptr(seg) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_revert_labels needs device pointers (no CPU path)");
-    long long lo[3], ext[3], o[3];
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = bbox[2 * a]; ext[a] = bbox[2 * a + 1] - bbox[2 * a];
-        if (lo[a] < 0 || ext[a] < 1 || bbox[2 * a + 1] > shape_before_cropping[a]) return fnn_fail(FNN_E_INVALID, "bbox outside shape_before_cropping");
-    }
-    for (int j = 0; j < 3; ++j) o[j] = shape_before_cropping[transpose_backward[j]];
-    const long long n = o[0] * o[1] * o[2];
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (label_dtype == FNN_LABEL_U16)
-        hipLaunchKernelGGL(revert_kernel<uint16_t>, grid, dim3(256), 0, st, (const uint16_t *)seg, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2],
-                           o[0], o[1], o[2], transpose_backward[0], transpose_backward[1], transpose_backward[2], (uint16_t *)out);
-    else
-        hipLaunchKernelGGL(revert_kernel<uint8_t>, grid, dim3(256), 0, st, (const uint8_t *)seg, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2],
-                           o[0], o[1], o[2], transpose_backward[0], transpose_backward[1], transpose_backward[2], (uint8_t *)out);
-    hipError_t r = hipGetLastError();
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
-    return FNN_OK;
+    if (int rc = fnn_check_perm(transpose_backward, "transpose_backward")) return rc;
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
+    if (int rc = fnn_need_dev("fnn_revert_labels", {seg, out})) return rc;
+    CropBox box{};
+    if (int rc = crop_box_fill(box, bbox, shape_before_cropping, transpose_backward)) return rc;
+    const long long n = box.o[0] * box.o[1] * box.o[2];
+    HipCall call(stream);
+    fnn_by_label(label_dtype, [&](auto lt) {
+        using LT = decltype(lt);
+        call.launch(revert_kernel<LT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const LT *)seg, box, (LT *)out);
+    });
+    return call.finish();
 }
 
 int fnn_export_probabilities(const void *logits, int logits_dtype, int heads, const int32_t *regions_class_order,
                              const int64_t bbox[6], const int64_t shape_before_cropping[3],
                              const int32_t transpose_backward[3], float *probs, void *labels, int label_dtype, void *stream) {
     if (!logits || !bbox || !shape_before_cropping || !transpose_backward || !probs || !labels) return fnn_fail(FNN_E_INVALID, "NULL argument");
-    if (check_perm(transpose_backward) != 0) return fnn_fail(FNN_E_INVALID, "transpose_backward is not a permutation of (0, 1, 2)");
-    if (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16) return fnn_fail(FNN_E_INVALID, "unknown label dtype");
-    if (logits_dtype != FNN_OUT_F16 && logits_dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown logits dtype");
+    if (int rc = fnn_check_perm(transpose_backward, "transpose_backward")) return rc;
+    if (int rc = fnn_check_label_dtype(label_dtype)) return rc;
+    if (int rc = fnn_check_float_dtype(logits_dtype, "logits dtype")) return rc;
     if (heads < 1 || heads > 4096) return fnn_fail(FNN_E_INVALID, "bad number of heads");
-    if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(probs) || !fnn_dev_ptr(labels)) return fnn_fail(FNN_E_INVALID, "fnn_export_probabilities needs device pointers (no CPU path)");
-    long long lo[3], ext[3], o[3];
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = bbox[2 * a]; ext[a] = bbox[2 * a + 1] - bbox[2 * a];
-        if (lo[a] < 0 || ext[a] < 1 || bbox[2 * a + 1] > shape_before_cropping[a]) return fnn_fail(FNN_E_INVALID, "bbox outside shape_before_cropping");
-    }
-    for (int j = 0; j < 3; ++j) o[j] = shape_before_cropping[transpose_backward[j]];
-    const long long n = o[0] * o[1] * o[2];
-    hipStream_t st = (hipStream_t)stream;
-    int *order = nullptr;
-    hipError_t r = hipSuccess;
-    if (regions_class_order) {
-        if (hipMalloc((void **)&order, heads * sizeof(int)) != hipSuccess) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
-        r = hipMemcpyAsync(order, regions_class_order, heads * sizeof(int), hipMemcpyHostToDevice, st);
-    }
-    const dim3 grid((unsigned)((n + 255) / 256));
-    const int tb0 = transpose_backward[0], tb1 = transpose_backward[1], tb2 = transpose_backward[2];
-#define FNN_EXPORT_LAUNCH(IT, LT)                                                                                              \
-    hipLaunchKernelGGL((export_prob_kernel<IT, LT>), grid, dim3(256), 0, st, (const IT *)logits, heads, order, lo[0], lo[1],   \
-                       lo[2], ext[0], ext[1], ext[2], o[0], o[1], o[2], tb0, tb1, tb2, probs, (LT *)labels)
-    if (r == hipSuccess) {
-        if (logits_dtype == FNN_OUT_F16) {
-            if (label_dtype == FNN_LABEL_U16) FNN_EXPORT_LAUNCH(_Float16, uint16_t); else FNN_EXPORT_LAUNCH(_Float16, uint8_t);
-        } else {
-            if (label_dtype == FNN_LABEL_U16) FNN_EXPORT_LAUNCH(float, uint16_t); else FNN_EXPORT_LAUNCH(float, uint8_t);
-        }
-        r = hipGetLastError();
-    }
-#undef FNN_EXPORT_LAUNCH
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    if (order) (void)hipFree(order);
-    if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
-    return FNN_OK;
+    if (int rc = fnn_need_dev("fnn_export_probabilities", {logits, probs, labels})) return rc;
+    CropBox box{};
+    if (int rc = crop_box_fill(box, bbox, shape_before_cropping, transpose_backward)) return rc;
+    const long long n = box.o[0] * box.o[1] * box.o[2];
+    HipCall call(stream);
+    const DevBuf order = upload_order(regions_class_order, heads, call);
+    if (regions_class_order && !order.p) return fnn_fail(FNN_E_HIP, "hipMalloc failed");
+    fnn_by_float(logits_dtype, [&](auto it) {
+        fnn_by_label(label_dtype, [&](auto lt) {
+            using IT = decltype(it);
+            using LT = decltype(lt);
+            call.launch(export_prob_kernel<IT, LT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const IT *)logits, heads,
+                        order.as<int>(), box, probs, (LT *)labels);
+        });
+    });
+    return call.finish();
 }
 
 }  // extern "C"

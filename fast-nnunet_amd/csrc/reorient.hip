@@ -28,8 +28,7 @@
 //     all 32 banks once.
 //
 // Nothing is read outside in[0, n) or written outside out[0, n).  Neither kernel keeps scratch.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <climits>
 #include <cstdint>
 
@@ -230,12 +229,7 @@ extern "C" int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_
     if (!in || !out || !shape_in || !src_axis || !flip) return fnn_fail(FNN_E_INVALID, "NULL argument");
     if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
         return fnn_fail(FNN_E_UNSUPPORTED, "fnn_reorient: elements of 1, 2 or 4 bytes are served");
-    int seen = 0;
-    for (int d = 0; d < 3; ++d) {
-        if (src_axis[d] < 0 || src_axis[d] > 2) return fnn_fail(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
-        seen |= 1 << src_axis[d];
-    }
-    if (seen != 7) return fnn_fail(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
+    if (!fnn_is_perm(src_axis)) return fnn_fail(FNN_E_INVALID, "fnn_reorient: src_axis must be a permutation of 0, 1, 2");
     long long n = 1;
     for (int d = 0; d < 3; ++d) {
         if (shape_in[d] < 0) return fnn_fail(FNN_E_INVALID, "fnn_reorient: negative extent");
@@ -279,7 +273,7 @@ extern "C" int fnn_reorient(const void *in, int elem_bytes, const int64_t shape_
         blocks = a.tq * a.t2 > INT_MAX / outer ? (long long)INT_MAX + 1 : a.tq * a.t2 * outer;
     }
     if (blocks > INT_MAX) return fnn_fail(FNN_E_UNSUPPORTED, "fnn_reorient: too many elements for one launch");
-    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_reorient needs device pointers (no CPU path)");
+    if (int rc = fnn_need_dev("fnn_reorient", {in, out})) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipError_t r;
     switch (elem_bytes) {

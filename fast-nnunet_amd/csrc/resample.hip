@@ -12,10 +12,10 @@
 // parallel and coalesced instead of one serial recursion per line.  All arithmetic is fp64 like the reference's
 // (`data.astype(float)`); agreement with scipy's zoom is ~1e-14 relative, i.e. results are the same fp32 / fp16
 // numbers except where a value sits on a rounding boundary.
-#include "fnn_device.h"
-#include "../../include/fnn.h"
+#include "host_call.h"
 #include <cfloat>
 #include <cmath>
+#include <vector>
 
 namespace {
 
@@ -160,8 +160,9 @@ __global__ __launch_bounds__(256) void interp_kernel(const double *C, Geo g, con
     out[i] = (T)acc;
 }
 
+// false: an allocation or a HIP call failed
 template <typename T>
-static int run(const T *in, const int64_t shape[4], const int64_t new_shape[3], const fnn_resample_desc &d, T *out, hipStream_t st) {
+static bool run(const T *in, const int64_t shape[4], const int64_t new_shape[3], const fnn_resample_desc &d, T *out, HipCall &call) {
     Geo g{};
     g.sep = d.separate_axis; g.order = d.order;
     bool same = true;
@@ -172,44 +173,32 @@ static int run(const T *in, const int64_t shape[4], const int64_t new_shape[3], 
         g.pd[a] = g.in[a] + 2 * g.pad[a];
     }
     const long long nin = g.in[0] * g.in[1] * g.in[2], nout = g.out[0] * g.out[1] * g.out[2];
-    if (same) {                                               // "no resampling necessary" (:193-195)
-        if (hipMemcpyAsync(out, in, (size_t)shape[0] * nin * sizeof(T), hipMemcpyDeviceToDevice, st) != hipSuccess) return -2;
-        return hipStreamSynchronize(st) == hipSuccess ? 0 : -2;
-    }
+    if (same)                                                 // "no resampling necessary" (:193-195)
+        return call.copy(out, in, (size_t)shape[0] * nin * sizeof(T), hipMemcpyDeviceToDevice).sync();
     const long long npd = g.pd[0] * g.pd[1] * g.pd[2];
     const int slices = g.sep < 0 ? 1 : (int)g.in[g.sep];
-    double *P = nullptr, *Q = nullptr;
-    unsigned *mm = nullptr;
-    if (hipMalloc((void **)&P, (size_t)npd * 8) != hipSuccess) return -2;
-    if (d.order == 3 && hipMalloc((void **)&Q, (size_t)npd * 8) != hipSuccess) { (void)hipFree(P); return -2; }
-    if (hipMalloc((void **)&mm, (size_t)slices * 8) != hipSuccess) { (void)hipFree(P); (void)hipFree(Q); return -2; }
+    DevBuf P, Q, mm;
+    if (!P.alloc((size_t)npd * 8) || (d.order == 3 && !Q.alloc((size_t)npd * 8)) || !mm.alloc((size_t)slices * 8)) return false;
     std::vector<unsigned> init((size_t)slices * 2);
     for (int s = 0; s < slices; ++s) { init[2 * s] = 0xffffffffu; init[2 * s + 1] = 0u; }
-    hipError_t r = hipSuccess;
-    for (int64_t c = 0; c < shape[0] && r == hipSuccess; ++c) {
+    const dim3 pd_grid((unsigned)((npd + 255) / 256));
+    for (int64_t c = 0; c < shape[0] && call.ok(); ++c) {
         const T *inc = in + c * nin;
-        r = hipMemcpyAsync(mm, init.data(), init.size() * 4, hipMemcpyHostToDevice, st);
-        if (r != hipSuccess) break;
+        call.copy(mm.p, init.data(), init.size() * 4, hipMemcpyHostToDevice);
         const long long per = g.sep < 0 ? nin : nin / g.in[g.sep];
         long long bx = (per + 255) / 256; if (bx > 2048) bx = 2048;
-        hipLaunchKernelGGL(minmax_kernel<T>, dim3((unsigned)bx, (unsigned)slices), dim3(256), 0, st, inc, g, mm);
-        hipLaunchKernelGGL(pad_kernel<T>, dim3((unsigned)((npd + 255) / 256)), dim3(256), 0, st, inc, g, P);
-        const double *coef = P;
-        if (d.order == 3) {
-            double *src = P, *dst = Q;
-            for (int a = 0; a < 3; ++a) {
-                if (a == g.sep) continue;
-                hipLaunchKernelGGL(fir_kernel, dim3((unsigned)((npd + 255) / 256)), dim3(256), 0, st, src, g, a, dst);
-                double *t = src; src = dst; dst = t;
-            }
-            coef = src;
+        call.launch(minmax_kernel<T>, dim3((unsigned)bx, (unsigned)slices), dim3(256), 0, inc, g, mm.as<unsigned>());
+        call.launch(pad_kernel<T>, pd_grid, dim3(256), 0, inc, g, P.as<double>());
+        double *src = P.as<double>(), *dst = Q.as<double>();
+        for (int a = 0; a < 3 && d.order == 3; ++a) {
+            if (a == g.sep) continue;
+            call.launch(fir_kernel, pd_grid, dim3(256), 0, (const double *)src, g, a, dst);
+            double *t = src; src = dst; dst = t;
         }
-        hipLaunchKernelGGL(interp_kernel<T>, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, coef, g, mm, out + c * nout);
-        r = hipGetLastError();
+        call.launch(interp_kernel<T>, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, (const double *)src, g,
+                    (const unsigned *)mm.as<unsigned>(), out + c * nout);
     }
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    (void)hipFree(P); (void)hipFree(Q); (void)hipFree(mm);
-    return r == hipSuccess ? 0 : -2;
+    return call.sync();
 }
 
 }  // namespace
@@ -220,12 +209,14 @@ extern "C" int fnn_resample(const void *in, const int64_t shape[4], const int64_
     if (d->order != 0 && d->order != 1 && d->order != 3) return fnn_fail(FNN_E_UNSUPPORTED, "interpolation order must be 0, 1 or 3");
     if (d->separate_axis < -1 || d->separate_axis > 2) return fnn_fail(FNN_E_INVALID, "separate_axis must be -1 .. 2");
     if (d->separate_axis >= 0 && d->order_z != 0) return fnn_fail(FNN_E_UNSUPPORTED, "order_z other than 0 is not implemented");
-    if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown dtype");
+    if (int rc = fnn_check_float_dtype(d->dtype)) return rc;
     for (int a = 0; a < 4; ++a) if (shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad shape");
     for (int a = 0; a < 3; ++a) if (new_shape[a] < 1) return fnn_fail(FNN_E_INVALID, "bad new_shape");
-    if (!fnn_dev_ptr(in) || !fnn_dev_ptr(out)) return fnn_fail(FNN_E_INVALID, "fnn_resample needs device pointers (no CPU path)");
-    const int rc = d->dtype == FNN_OUT_F32 ? run<float>((const float *)in, shape, new_shape, *d, (float *)out, (hipStream_t)stream)
-                                           : run<f16>((const f16 *)in, shape, new_shape, *d, (f16 *)out, (hipStream_t)stream);
-    if (rc != 0) return fnn_fail(FNN_E_HIP, "resample kernels failed");
-    return FNN_OK;
+    if (int rc = fnn_need_dev("fnn_resample", {in, out})) return rc;
+    HipCall call(stream);
+    const bool ok = fnn_by_float(d->dtype, [&](auto t) {
+        using T = decltype(t);
+        return run<T>((const T *)in, shape, new_shape, *d, (T *)out, call);
+    });
+    return ok ? FNN_OK : fnn_fail(FNN_E_HIP, "resample kernels failed");
 }

@@ -24,6 +24,7 @@
 // evaluates the score of every distinct one in registers and picks: no one-hot tensor, no unique(), no buffer.
 // memefficient_seg_resampling=True is the other rule: the float32 score of (seg == u) above 0.5 takes the label, else 0.
 #include "resample_torch_common.h"
+#include "host_call.h"
 
 namespace {
 
@@ -161,13 +162,12 @@ extern "C" int fnn_resample_torch(const void *in, const int64_t shape[4], const 
                                   const fnn_resample_torch_desc *d, void *out, void *stream) {
     int rc = check_args(in, shape, new_shape, d, out);
     if (rc != FNN_OK) return rc;
-    if (d->dtype != FNN_OUT_F16 && d->dtype != FNN_OUT_F32) return fnn_fail(FNN_E_INVALID, "unknown dtype");
+    if ((rc = fnn_check_float_dtype(d->dtype)) != FNN_OK) return rc;
     RGeo g{};
     const char *why = "";
     if ((rc = rt_geometry(shape, new_shape, d->separate_axis, g, &why)) != FNN_OK) return fnn_fail(rc, why);
     hipStream_t st = (hipStream_t)stream;
-    if (d->dtype == FNN_OUT_F32) launch_image((const float *)in, g, (int)shape[0], (float *)out, st);
-    else launch_image((const f16 *)in, g, (int)shape[0], (f16 *)out, st);
+    fnn_by_float(d->dtype, [&](auto t) { using T = decltype(t); launch_image((const T *)in, g, (int)shape[0], (T *)out, st); });
     if (hipGetLastError() != hipSuccess) return fnn_fail(FNN_E_HIP, "fnn_resample_torch: launch failed");
     return FNN_OK;
 }

@@ -66,7 +66,35 @@ KERNEL_CASES = [
 ]
 
 
-@pytest.mark.parametrize('case', KERNEL_CASES, ids=[c[0] for c in KERNEL_CASES])
+# The crop-box map (fnn_device.h, crop_box_voxel) under all six permutations: a grid of three different extents, none a
+# multiple of 4, the box inside on all six faces; then the identity transpose with the z box on multiples of 4 (the VEC = 4
+# kernel) and the same case with lo[2] = 3 (VEC = 1).  Two members each, so that the average is not one member's export.
+CROP_MAP_CASES = [(f'perm_{"".join(map(str, tb))}', 2, [F16, F32], 3, None, (5, 6, 7), [[1, 4], [2, 5], [1, 6]], tb)
+                  for tb in [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]] + [
+    ('z_box_4_to_8_vec4', 2, [F16, F32], 3, None, (3, 5, 8), [[1, 3], [1, 4], [4, 8]], (0, 1, 2)),
+    ('z_box_3_to_7_vec1', 2, [F16, F32], 3, None, (3, 5, 8), [[1, 3], [1, 4], [3, 7]], (0, 1, 2)),
+]
+
+
+@pytest.mark.parametrize('case', CROP_MAP_CASES, ids=[c[0] for c in CROP_MAP_CASES])
+def test_ensemble_export_puts_the_box_where_the_oracle_puts_it(case):
+    """The export kernel shares the map, so the comparison below cannot see a map that is wrong in both: here the voxels
+    come from the oracle's numpy revert - exact 1 / 0 / label 0 outside the box; inside, each member within the 5e-7 of
+    test_gpu_preprocess's export rule, so their average within that plus the two roundings (half an ulp of 1 each) of + and /."""
+    from oracle import preprocess as opre
+    name, n, dtypes, heads, order, before, bbox, tb = case
+    cropped = [hi - lo for lo, hi in bbox]
+    lgs = [_member_logits(100 * len(name) + m, heads, cropped, dtypes[m]) for m in range(n)]
+    refs = [opre.export_with_probabilities(lg.cpu().numpy(), bbox, before, tb, 4)[1] for lg in lgs]
+    inside = opre.revert_labels(np.ones(cropped, np.uint8), bbox, before, tb, 4).astype(bool)
+    avg, labels = _ensemble(lgs, heads, order, bbox, before, tb)
+    got, want = avg.cpu().numpy(), ensemble_ref.average(refs)
+    assert np.array_equal(got[:, ~inside].view(np.uint32), want[:, ~inside].view(np.uint32)), name
+    assert not _labels_np(labels, False)[~inside].any(), name
+    assert np.abs(got - want).max() <= 5e-7 + 2 * 2.0 ** -24, name
+
+
+@pytest.mark.parametrize('case', KERNEL_CASES + CROP_MAP_CASES, ids=[c[0] for c in KERNEL_CASES + CROP_MAP_CASES])
 def test_ensemble_export_equals_per_member_export_and_numpy_average(case):
     name, n, dtypes, heads, order, before, bbox, tb = case
     u16 = heads > 255

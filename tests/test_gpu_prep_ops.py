@@ -209,6 +209,71 @@ def test_revert_labels_under_every_permutation(box, u16):
         assert got.dtype == want.dtype and np.array_equal(got, want), tf
 
 
+# ---- (d') the crop-box map shared by revert_kernel and export_prob_kernel (fnn_device.h, crop_box_voxel) ---------------------
+CROP_BEFORE, CROP_BOX = (5, 6, 7), [[1, 4], [2, 5], [1, 6]]          # three extents, none a multiple of 4; inside on all six faces
+
+
+@pytest.mark.parametrize('tf', R.PERMS, ids=lambda t: ''.join(map(str, t)))
+def test_crop_box_map_of_revert_and_export_under_every_permutation(tf):
+    """Labels exactly opre.revert_labels; probabilities by the rule of test_gpu_preprocess (5e-7 of the oracle's softmax,
+    labels equal where the oracle's top two differ by more than 1e-6) - and outside the box, where nothing is computed,
+    exactly the background's 1 / the others' 0 and label 0, at exactly the oracle's voxels."""
+    from fast_nnunet_amd import capi
+    tb = [int(i) for i in np.argsort(tf)]
+    cropped = [hi - lo for lo, hi in CROP_BOX]
+    rng = np.random.default_rng(11)
+    grid = [CROP_BEFORE[j] for j in tb]
+    st = torch.cuda.current_stream().cuda_stream
+    for u16 in (False, True):
+        seg = rng.integers(1, 60000 if u16 else 255, cropped).astype(np.uint16 if u16 else np.uint8)
+        want = opre.revert_labels(seg, CROP_BOX, CROP_BEFORE, tb, 300 if u16 else 4)
+        out = torch.full(want.shape, -1 if u16 else 255, dtype=torch.int16 if u16 else torch.uint8, device='cuda')
+        capi.revert_labels(_dev(seg.view(np.int16) if u16 else seg).data_ptr(), u16, CROP_BOX, CROP_BEFORE, tb, out.data_ptr())
+        got = out.cpu().numpy()
+        assert np.array_equal(got.view(np.uint16) if u16 else got, want), (tf, u16)
+        assert (want != 0).sum() == seg.size                      # (every cropped voxel landed somewhere: no label is 0)
+    H = 3
+    logits = (rng.standard_normal((H, *cropped)) * 3).astype(np.float32)
+    want_l, want_p = opre.export_with_probabilities(logits, CROP_BOX, CROP_BEFORE, tb, 4)
+    inside = opre.revert_labels(np.ones(cropped, np.uint8), CROP_BOX, CROP_BEFORE, tb, 4).astype(bool)
+    for half in (False, True):
+        lg = _dev(logits.astype(np.float16) if half else logits)
+        wl, wp = (opre.export_with_probabilities(logits.astype(np.float16), CROP_BOX, CROP_BEFORE, tb, 4) if half else (want_l, want_p))
+        probs = torch.full((H, *grid), -1.0, dtype=torch.float32, device='cuda')
+        labels = torch.full(grid, 255, dtype=torch.uint8, device='cuda')
+        capi.export_probabilities(lg.data_ptr(), half, H, None, CROP_BOX, CROP_BEFORE, tb, probs.data_ptr(), labels.data_ptr(), False, st)
+        got_p, got_l = probs.cpu().numpy(), labels.cpu().numpy()
+        assert np.array_equal(_bits(got_p[:, ~inside]), _bits(wp[:, ~inside])) and not got_l[~inside].any(), (tf, half)
+        assert np.abs(got_p - wp).max() <= 5e-7, (tf, half)
+        top2 = np.sort(wp, 0)[-2:]
+        decided = (top2[1] - top2[0] > 1e-6) | (top2[1] == top2[0])
+        assert decided.mean() > 0.99 and np.array_equal(got_l[decided], wl[decided]), (tf, half)
+
+
+def test_crop_boxes_outside_their_grid_are_refused_in_both_wordings():
+    """Behind the device-pointer check, so only a GPU reaches them: fnn_preprocess checks the box against the transposed
+    image, fnn_revert_labels and fnn_export_probabilities against shape_before_cropping; an unknown normalisation scheme
+    is refused before anything runs and writes nothing."""
+    from fast_nnunet_amd import capi
+    lib = capi.load_library()
+    raw = _dev(np.ones((1, 4, 5, 6), np.float32))
+    for box in ([[0, 7], [0, 5], [0, 4]], [[-1, 6], [0, 5], [0, 4]], [[0, 6], [2, 2], [0, 4]]):      # transposed (2, 1, 0): 6 x 5 x 4
+        out = torch.empty(1, 6, 5, 4, device='cuda')
+        with pytest.raises(AssertionError, match=re.escape('bbox outside the (transposed) image')):
+            capi.preprocess(raw.data_ptr(), (1, 4, 5, 6), (2, 1, 0), box, [R.norm_desc('RGBTo01Normalization')], out.data_ptr())
+    seg = torch.ones(4, 5, 6, dtype=torch.uint8, device='cuda')
+    out = torch.empty(4, 5, 6, dtype=torch.uint8, device='cuda')
+    with pytest.raises(AssertionError, match='bbox outside shape_before_cropping'):
+        capi.revert_labels(seg.data_ptr(), False, [[0, 4], [0, 6], [0, 6]], (4, 5, 6), (0, 1, 2), out.data_ptr())
+    import ctypes as C
+    out = torch.full((1, 4, 5, 6), 7.0, device='cuda')
+    desc = (capi.NormDesc * 1)(capi.NormDesc(77, 0.0, 1.0, 0.0, 1.0, 0))
+    rc = lib.fnn_preprocess(raw.data_ptr(), (C.c_int64 * 4)(1, 4, 5, 6), (C.c_int32 * 3)(0, 1, 2), (C.c_int64 * 6)(0, 4, 0, 5, 0, 6),
+                            desc, out.data_ptr(), None)
+    assert rc == capi.FNN_E_UNSUPPORTED and lib.fnn_last_error(None) == b'unknown normalisation scheme'
+    assert bool((out == 7.0).all())
+
+
 # ---- (e) resample edges -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('shape,new_shape,order,axis', R.RESAMPLE_EDGE_CASES)
 def test_resample_with_axes_of_length_one_and_two(shape, new_shape, order, axis):

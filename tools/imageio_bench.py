@@ -13,13 +13,15 @@ the device, to zlib level 1 of a mask on the CPU times the number of labels, and
 (``--section label_files``, these rows alone, written to profiles/r21_label_files.txt unless ``--out`` says otherwise)
 fnn_decode_labels on the int16 and the uint8 bytes of an n^3 label map next to fnn_decode_voxels followed by the cast it
 replaces and to a device copy of the same bytes, and compute_metrics_on_folder on a few generated cases of n^3 voxels, per
-case and split into inflate, upload, decode and count.
+case and split into inflate, upload, decode and count.  ``--section read`` runs the file -> device rows of both files alone and
+``--section predict_files`` the two predict_from_files rows alone, with the defaults of the full run: for repeating those
+rows in many fresh processes (profiles/r24_host_prologue.txt).
 
 The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, so that gzip has something to do), written
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient|deflate|masks|label_files] [--out FILE]
+                                                          [--section all|reorient|deflate|masks|label_files|predict_files|read] [--out FILE]
 """
 import argparse
 import gzip
@@ -334,6 +336,47 @@ def bench_label_files(n, reps, cases, dev, say, row):
         row('  one case, decode_label_maps (upload, decode, status, narrowing)', wall(lambda: rw.decode_label_maps(staged), reps)[:3])
 
 
+def bench_predict_files(a, dev, say, row, tmp):
+    """predict_from_files_sequential and predict_from_files on a.cases generated cases under tmp (``--section predict_files``
+    runs these rows alone)."""
+    from fast_nnunet_amd import nnUNetPredictor
+    from fast_nnunet_amd import imageio as fio
+    from fast_nnunet_amd.plans import PlansManager
+    from oracle.topology import UNetSpec
+    from oracle.unet import synthetic_state_dict
+    props = {'nibabel_stuff': {'original_affine': np.diag([0.8, 0.8, 1.25, 1.0])}}
+    say(f'--- predict_from_files on {a.cases} cases of {tuple(a.case_shape)} int16 .nii.gz, toy network (patch 32 x 64 x 64), no mirroring')
+    patch = (32, 64, 64)
+    spec = UNetSpec('plain', 1, 3, [16, 32, 32], [(3, 3, 3)] * 3, [(1, 1, 1), (2, 2, 2), (2, 2, 2)], [2, 2, 2], [2, 2])
+    pm = PlansManager({'dataset_name': 'Dataset996_Bench', 'plans_name': 'nnUNetPlans', 'transpose_forward': [0, 1, 2],
+                       'transpose_backward': [0, 1, 2], 'image_reader_writer': 'NibabelIO',
+                       'foreground_intensity_properties_per_channel': {},
+                       'configurations': {'3d_fullres': {
+                           'patch_size': list(patch), 'spacing': [1.25, 0.8, 0.8], 'normalization_schemes': ['ZScoreNormalization'],
+                           'use_mask_for_norm': [False],
+                           'architecture': {'network_class_name': 'PlainConvUNet', 'arch_kwargs': {}, '_kw_requires_import': []}}}})
+    dj = {'labels': {'background': 0, 'a': 1, 'b': 2}, 'channel_names': {'0': 'CT'}, 'file_ending': '.nii.gz'}
+    p = nnUNetPredictor(tile_step_size=0.5, use_gaussian=True, use_mirroring=False, device=dev, allow_tqdm=False, patches_per_forward=4)
+    p.manual_initialization(None, pm, pm.get_configuration('3d_fullres'), [synthetic_state_dict(spec, 3)], dj, 'nnUNetTrainer', None)
+    src = os.path.join(tmp, 'cases')
+    os.makedirs(src)
+    for i in range(a.cases):
+        v = synthetic_ct(tuple(a.case_shape), 10 + i)
+        hd = fio.nifti1_header_bytes(tuple(a.case_shape)[::-1], 4, props['nibabel_stuff']['original_affine'])
+        with open(os.path.join(src, f'case{i}_0000.nii.gz'), 'wb') as raw, \
+                gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=raw, mtime=0) as g:
+            g.write(hd)
+            g.write(v.tobytes())
+    p.predict_from_files_sequential(src, os.path.join(tmp, 'warm'))
+    t_seq = wall(lambda: p.predict_from_files_sequential(src, os.path.join(tmp, 'seq')), a.reps)
+    t_thr = wall(lambda: p.predict_from_files(src, os.path.join(tmp, 'thr')), a.reps)
+    row('predict_from_files_sequential (read, GPU, write one after the other)', t_seq[:3])
+    row('predict_from_files (reader thread, writer thread)', t_thr[:3], f'  {t_seq[0] / t_thr[0]:.2f}x')
+    same = all(open(os.path.join(tmp, 'seq', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'thr', f'case{i}.nii.gz'), 'rb').read()
+               for i in range(a.cases))
+    say(f'the two forms wrote identical files: {same}')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
@@ -341,7 +384,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'predict_files', 'read'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -366,6 +409,11 @@ def main():
     if a.section == 'label_files':
         bench_label_files(n, a.reps, a.cases, dev, say, row)
         write_out(a.out or os.path.join(ROOT, 'profiles', 'r21_label_files.txt'), lines)
+        return
+    if a.section == 'predict_files':
+        with tempfile.TemporaryDirectory() as tmp:
+            bench_predict_files(a, dev, say, row, tmp)
+        write_out(a.out, lines)
         return
     if a.section in ('reorient', 'deflate', 'masks'):
         {'reorient': bench_reorient, 'deflate': bench_deflate, 'masks': bench_masks}[a.section](n, a.reps, dev, say, row)
@@ -414,6 +462,8 @@ def main():
                 del src, dst
             del raw, out
             row(f'{tag}: read_images, file -> float32 tensor on the device (all of the above)', wall(lambda: rw.read_images([f]), a.reps)[:3])
+            if a.section == 'read':                       # these rows alone
+                continue
 
             say(f'--- the route before, {tag}: host decode with numpy, astype(float32), upload of the float32 array')
 
@@ -434,6 +484,10 @@ def main():
             say(f'{tag}: sum of the three' + ' ' * 45 + f': {t_read[0] + t_cast[0] + t_up[0]:9.2f} ms')
             del blob, arr
 
+        if a.section == 'read':
+            write_out(a.out, lines)
+            return
+
         say('--- writing a label map')
         coarse = np.random.default_rng(2).integers(0, 5, (n // 32,) * 3).astype(np.uint8)
         seg = coarse.repeat(32, 0).repeat(32, 1).repeat(32, 2)
@@ -445,36 +499,7 @@ def main():
         bench_reorient(n, a.reps, dev, say, row)
         bench_deflate(n, a.reps, dev, say, row)
 
-        say(f'--- predict_from_files on {a.cases} cases of {tuple(a.case_shape)} int16 .nii.gz, toy network (patch 32 x 64 x 64), no mirroring')
-        patch = (32, 64, 64)
-        spec = UNetSpec('plain', 1, 3, [16, 32, 32], [(3, 3, 3)] * 3, [(1, 1, 1), (2, 2, 2), (2, 2, 2)], [2, 2, 2], [2, 2])
-        pm = PlansManager({'dataset_name': 'Dataset996_Bench', 'plans_name': 'nnUNetPlans', 'transpose_forward': [0, 1, 2],
-                           'transpose_backward': [0, 1, 2], 'image_reader_writer': 'NibabelIO',
-                           'foreground_intensity_properties_per_channel': {},
-                           'configurations': {'3d_fullres': {
-                               'patch_size': list(patch), 'spacing': [1.25, 0.8, 0.8], 'normalization_schemes': ['ZScoreNormalization'],
-                               'use_mask_for_norm': [False],
-                               'architecture': {'network_class_name': 'PlainConvUNet', 'arch_kwargs': {}, '_kw_requires_import': []}}}})
-        dj = {'labels': {'background': 0, 'a': 1, 'b': 2}, 'channel_names': {'0': 'CT'}, 'file_ending': '.nii.gz'}
-        p = nnUNetPredictor(tile_step_size=0.5, use_gaussian=True, use_mirroring=False, device=dev, allow_tqdm=False, patches_per_forward=4)
-        p.manual_initialization(None, pm, pm.get_configuration('3d_fullres'), [synthetic_state_dict(spec, 3)], dj, 'nnUNetTrainer', None)
-        src = os.path.join(tmp, 'cases')
-        os.makedirs(src)
-        for i in range(a.cases):
-            v = synthetic_ct(tuple(a.case_shape), 10 + i)
-            hd = fio.nifti1_header_bytes(tuple(a.case_shape)[::-1], 4, props['nibabel_stuff']['original_affine'])
-            with open(os.path.join(src, f'case{i}_0000.nii.gz'), 'wb') as raw, \
-                    gzip.GzipFile(filename='', mode='wb', compresslevel=1, fileobj=raw, mtime=0) as g:
-                g.write(hd)
-                g.write(v.tobytes())
-        p.predict_from_files_sequential(src, os.path.join(tmp, 'warm'))
-        t_seq = wall(lambda: p.predict_from_files_sequential(src, os.path.join(tmp, 'seq')), a.reps)
-        t_thr = wall(lambda: p.predict_from_files(src, os.path.join(tmp, 'thr')), a.reps)
-        row('predict_from_files_sequential (read, GPU, write one after the other)', t_seq[:3])
-        row('predict_from_files (reader thread, writer thread)', t_thr[:3], f'  {t_seq[0] / t_thr[0]:.2f}x')
-        same = all(open(os.path.join(tmp, 'seq', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'thr', f'case{i}.nii.gz'), 'rb').read()
-                   for i in range(a.cases))
-        say(f'the two forms wrote identical files: {same}')
+        bench_predict_files(a, dev, say, row, tmp)
     write_out(a.out, lines)
 
 

@@ -75,6 +75,8 @@ if len(sys.argv) > 3:
             doc = {}
     if doc.get('csrc_sha256') != sha:
         doc = {'note': 'rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), reads x2 per the gfx950 correction; '
-                       'bench.py --steps 1 --warmup 0 per workload key', 'csrc_sha256': sha, 'workloads': {}}
+                       'bench.py --steps 1 --warmup 0 per workload key; the passes are the two counter passes of tools/capture.sh '
+                       '(FNN_KNOBS=1 FNN_NO_PIPELINE=1, no tracing next to --pmc), which may be run on their own', 'csrc_sha256': sha,
+               'workloads': {}}
     doc['workloads'][key] = {'families': out}
     json.dump(doc, open(sys.argv[3], 'w'), indent=1)
