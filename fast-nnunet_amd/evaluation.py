@@ -361,14 +361,15 @@ def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Op
 
 def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_file: str, plans_file: str,
                                output_file: Optional[str] = None, num_processes: int = DEFAULT_NUM_PROCESSES,
-                               chill: bool = False):
+                               chill: bool = False, inflate_on_device: bool = False):
     """compute_metrics_on_folder2 (:177-196): labels or regions, ignore label, file ending and the reader-writer from
-    ``dataset.json`` and the plans; ``output_file`` defaults to ``<folder_pred>/summary.json``."""
+    ``dataset.json`` and the plans; ``output_file`` defaults to ``<folder_pred>/summary.json``.  ``inflate_on_device``: label
+    files written with ``compress_on_device=True`` are inflated on the GPU (``NiftiIO(inflate_on_device=True)``)."""
     from .imageio import determine_reader_writer_from_dataset_json
     from .label_folders import load_json
     from .plans import PlansManager
     dataset_json = load_json(dataset_json_file)
-    rw = determine_reader_writer_from_dataset_json(dataset_json)()
+    rw = determine_reader_writer_from_dataset_json(dataset_json)(inflate_on_device=inflate_on_device)
     if output_file is None:
         output_file = os.path.join(folder_pred, 'summary.json')
     lm = PlansManager(plans_file).get_label_manager(dataset_json)
@@ -379,14 +380,15 @@ def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_f
 
 def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: Sequence[int], output_file: Optional[str] = None,
                                      num_processes: int = DEFAULT_NUM_PROCESSES, ignore_label: Optional[int] = None,
-                                     chill: bool = False):
+                                     chill: bool = False, inflate_on_device: bool = False):
     """compute_metrics_on_folder_simple (:199-212): the file ending is that of the first reference file (``.nii.gz``
-    whole, where the reference's ``os.path.splitext`` would keep ``.gz`` and then match the same files)."""
+    whole, where the reference's ``os.path.splitext`` would keep ``.gz`` and then match the same files).
+    ``inflate_on_device``: as ``compute_metrics_on_folder2``."""
     from .imageio import determine_reader_writer_from_file_ending
     from .label_folders import subfiles
     example_file = subfiles(folder_ref, join=True)[0]
     file_ending = '.nii.gz' if example_file.lower().endswith('.nii.gz') else os.path.splitext(example_file)[-1]
-    rw = determine_reader_writer_from_file_ending(file_ending)()
+    rw = determine_reader_writer_from_file_ending(file_ending)(inflate_on_device=inflate_on_device)
     if output_file is None:
         output_file = os.path.join(folder_pred, 'summary.json')
     compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, file_ending, labels, ignore_label=ignore_label,

@@ -29,6 +29,11 @@ bytes into the uint8 / uint16 map the counting, labelling and compressing kernel
 file with such a voxel is refused (the reference would carry the voxel along as a value that equals no label).  The folder
 front-ends (``evaluation.compute_metrics_on_folder``, ``postprocessing.apply_postprocessing_to_folder``, ...) read with it.
 
+``NiftiIO(inflate_on_device=True)`` is the opt-in read route for exactly those files: ``StagedCase.fill`` stages the
+compressed file as it is when ``chunked_layout`` recognises it, and ``decode_label_maps`` lets ``fnn_inflate_segments``
+(csrc/inflate.hip) inflate it on the device, certified by the call's status and the gzip trailer's CRC-32.  Files written by
+zlib (references, scanner images), image files and everything the device refuses are inflated by zlib on the host, as ever.
+
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
 from __future__ import annotations
@@ -334,17 +339,104 @@ def label_flags_error(fname: str, flags: int, out_bytes: int) -> RuntimeError:
     return RuntimeError(f'{fname}: not a label file: it holds ' + ', '.join(said))
 
 
+class ChunkedLayout:
+    """Where the voxel stream of a ``.nii.gz`` file written with ``compress_on_device=True`` lies, for ``fnn_inflate_segments``:
+    the raw deflate bytes ``file[first:first + in_bytes]`` inflate to the voxel bytes, ``starts`` (int64, relative to
+    ``first``, ascending from 0) are the candidates for segment starts, ``header_crc`` is the CRC-32 of the ``vox_offset``
+    bytes in front of the voxels and ``crc32`` the gzip trailer's, of all of them."""
+
+    def __init__(self, first: int, in_bytes: int, starts: np.ndarray, header_crc: int, crc32: int):
+        self.first, self.in_bytes, self.starts = int(first), int(in_bytes), starts
+        self.header_crc, self.crc32 = int(header_crc), int(crc32)
+
+
+CHUNK_MARKER = b'\x00\x00\xff\xff'                              # the empty stored block that ends a segment on a byte
+HEADER_SEGMENT_SEARCH = 1 << 16                                  # the header's segment must end in the first 64 KiB of the file
+
+
+def _marker_ends(blob: bytes, lo: int, hi: int) -> List[int]:
+    found, at = [], blob.find(CHUNK_MARKER, lo, hi)
+    while at >= 0:
+        found.append(at + 4)
+        at = blob.find(CHUNK_MARKER, at + 1, hi)
+    return found
+
+
+def _chunked_by_its_ends(head10: bytes, tail14: bytes) -> bool:
+    """The O(1) test an ordinary zlib file fails: the gzip header ``write_label_file`` writes (magic, deflate, no flags), and a
+    stream that ends with an empty stored block and the final empty fixed block in front of the trailer."""
+    return len(head10) == 10 and head10[:4] == b'\x1f\x8b\x08\x00' and len(tail14) == 14 and tail14[:6] == CHUNK_MARKER + b'\x03\x00'
+
+
+def chunked_layout(file_bytes, hdr: NiftiHeader) -> Optional[ChunkedLayout]:
+    """The layout of a whole ``.nii.gz`` file for the device inflate, or None for a file that is not laid out as
+    ``compressed_label_file_bytes`` lays it out (then the host inflates it, as ever).  Host only.  Nothing here is trusted
+    later: the device call certifies the chain of segments and the sizes, the caller the CRC-32.
+
+    * O(1) first: gzip magic, CM 8 and FLG 0 in the first 10 bytes, and ``file[-14:-8] == 00 00 FF FF 03 00``;
+    * the trailer's ISIZE is ``(vox_offset + n_bytes) mod 2^32``;
+    * the header's segment: the first end ``m`` of a marker 00 00 FF FF at which zlib inflates ``file[10:m]`` (closed with
+      03 00) to exactly ``vox_offset`` bytes; markers are looked for in the first HEADER_SEGMENT_SEARCH bytes only;
+    * the candidates: ``m`` and the end of every marker in ``file[m:len - 10]`` that lies below ``len - 10``."""
+    blob = bytes(file_bytes)
+    n = len(blob)
+    if n < 10 + 5 + 6 + 8 or not _chunked_by_its_ends(blob[:10], blob[-14:]):
+        return None
+    crc, isize = struct.unpack('<II', blob[-8:])
+    if isize != (hdr.vox_offset + hdr.n_bytes) & 0xFFFFFFFF:
+        return None
+    end = n - 10                                                 # the stream's end: behind the last marker, before 03 00
+    for m in _marker_ends(blob, 10, min(end, 10 + HEADER_SEGMENT_SEARCH)):
+        z = zlib.decompressobj(-15)
+        try:
+            head = z.decompress(blob[10:m] + b'\x03\x00', hdr.vox_offset + 1)
+        except zlib.error:
+            continue
+        if z.eof and len(head) == hdr.vox_offset and not z.unused_data and not z.unconsumed_tail:
+            break
+    else:
+        return None
+    if m >= end:
+        return None
+    starts = np.array([m] + [e for e in _marker_ends(blob, m, end) if e < end], dtype=np.int64) - m
+    return ChunkedLayout(m, end - m, starts, zlib.crc32(head), crc)
+
+
 class StagedCase:
     """The files of one case between the host and the device: headers (checked), and one pinned byte buffer per file that a
-    host thread fills."""
+    host thread fills.  ``layouts[i]`` is None when buffer i holds the file's voxel bytes, and the ``ChunkedLayout`` when it
+    holds the whole compressed file for the device to inflate (label files of a reader with ``inflate_on_device``)."""
 
-    def __init__(self, fnames, hdrs, buffers):
+    def __init__(self, fnames, hdrs, buffers, inflate_on_device: bool = False):
         self.fnames, self.hdrs, self.buffers = list(fnames), list(hdrs), list(buffers)
+        self.inflate_on_device = bool(inflate_on_device)
+        self.layouts = [None] * len(self.fnames)
+
+    def _stage_compressed(self, fname: str, hdr: NiftiHeader, buf) -> Optional[ChunkedLayout]:
+        """The whole file into ``buf`` when it is a chunked ``.nii.gz`` that fits (the buffer is sized by the voxel bytes)."""
+        if not str(fname).lower().endswith('.nii.gz'):
+            return None
+        with open(fname, 'rb') as f:
+            size = os.fstat(f.fileno()).st_size
+            if size > buf.numel() or size < 32:
+                return None
+            head10 = f.read(10)
+            f.seek(size - 14)
+            if not _chunked_by_its_ends(head10, f.read(14)):
+                return None
+            f.seek(0)
+            blob = f.read()
+        layout = chunked_layout(blob, hdr)
+        if layout is not None:
+            buf.numpy()[:len(blob)] = np.frombuffer(blob, dtype=np.uint8)
+        return layout
 
     def fill(self):
         """Host only (file reads and zlib): may run on a thread."""
-        for f, h, b in zip(self.fnames, self.hdrs, self.buffers):
-            read_voxel_bytes(f, h, b.numpy())
+        for i, (f, h, b) in enumerate(zip(self.fnames, self.hdrs, self.buffers)):
+            self.layouts[i] = self._stage_compressed(f, h, b) if self.inflate_on_device else None
+            if self.layouts[i] is None:
+                read_voxel_bytes(f, h, b.numpy())
         return self
 
 
@@ -352,9 +444,13 @@ class NiftiIO:
     """``read_images`` / ``read_seg`` / ``write_seg`` of the reference's reader-writer classes for single-file NIfTI-1."""
     supported_file_endings = list(SUPPORTED_FILE_ENDINGS)
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, inflate_on_device: bool = False):
         self._device = device
         self._pinned = {}                            # slot -> list of pinned uint8 tensors, grown on demand
+        # opt-in: label files written with compress_on_device=True are inflated by fnn_inflate_segments (csrc/inflate.hip)
+        # instead of zlib; which route each label file took is counted here
+        self.inflate_on_device = bool(inflate_on_device)
+        self.inflate_stats = {'device': 0, 'host': 0, 'fallback': 0}
 
     # ------------------------------------------------------------------ device side
     def _dev(self):
@@ -411,7 +507,7 @@ class NiftiIO:
         on its own, nothing compared between the files."""
         fnames = [str(f) for f in fnames]
         hdrs = [read_header(f) for f in fnames]
-        staged = StagedCase(fnames, hdrs, self._pinned_buffers(hdrs, slot))
+        staged = StagedCase(fnames, hdrs, self._pinned_buffers(hdrs, slot), self.inflate_on_device)
         self._orient_labels(staged)
         return staged
 
@@ -428,6 +524,10 @@ class NiftiIO:
         the bits of uint16 (the engine's two-byte label type).  Every file's bytes are uploaded and decoded by
         ``fnn_decode_labels`` on the current stream - 1 byte wide for the 1-byte datatypes, else 2 bytes and narrowed to
         uint8 when the largest label is below 256.  RuntimeError naming the file when it holds what is no label.
+        A file staged compressed (``inflate_on_device``) is uploaded as it is and inflated by ``fnn_inflate_segments`` into
+        the same byte tensor; the result is taken only if the call certifies it (status 0) and its CRC-32, combined with the
+        header's, is the gzip trailer's - anything else re-reads the file with zlib on this thread, which is the route the
+        file takes without the flag and the one that says what is wrong with a corrupt file.
         Synchronises: the staging buffers are free again on return."""
         import torch
         dev = self._dev()
@@ -438,7 +538,13 @@ class NiftiIO:
             maps, keep = [], []
             for i, (h, b) in enumerate(zip(staged.hdrs, staged.buffers)):
                 raw = torch.empty(max(16, h.n_bytes), dtype=torch.uint8, device=dev)      # (the allocator aligns to 512 bytes)
-                raw[:h.n_bytes].copy_(b[:h.n_bytes], non_blocking=True)
+                if staged.layouts[i] is None:
+                    self.inflate_stats['host'] += 1
+                    inflated = False
+                else:
+                    inflated = self._inflate_staged(staged, i, raw, stream, keep)
+                if not inflated:
+                    raw[:h.n_bytes].copy_(b[:h.n_bytes], non_blocking=True)
                 keep.append(raw)
                 wide = label_bytes(h) == 2
                 out = torch.empty(h.shape, dtype=torch.int16 if wide else torch.uint8, device=dev)
@@ -454,6 +560,23 @@ class NiftiIO:
                     m = m.to(torch.uint8)
                 made.append(self._label_frame(staged, i, m))
         return made
+
+    def _inflate_staged(self, staged: StagedCase, i: int, raw, stream, keep: list) -> bool:
+        """File i, staged compressed -> its voxel bytes in ``raw`` by the device inflate: True.  False: the device route
+        refused it, and the staging buffer now holds the voxel bytes ``read_voxel_bytes`` made of the file."""
+        import torch
+        h, b, lay = staged.hdrs[i], staged.buffers[i], staged.layouts[i]
+        comp = torch.empty(max(16, lay.in_bytes), dtype=torch.uint8, device=raw.device)
+        comp[:lay.in_bytes].copy_(b[lay.first:lay.first + lay.in_bytes], non_blocking=True)
+        keep.append(comp)
+        status, crc = capi.inflate_segments(comp.data_ptr(), lay.in_bytes, lay.starts, raw.data_ptr(), h.n_bytes, stream.cuda_stream)
+        if status == capi.FNN_INFLATE_OK and crc32_combine(lay.header_crc, crc, h.n_bytes) == lay.crc32:
+            self.inflate_stats['device'] += 1
+            return True
+        self.inflate_stats['fallback'] += 1                      # (the call synchronised: the staging buffer is free)
+        staged.layouts[i] = None
+        read_voxel_bytes(staged.fnames[i], h, b.numpy())
+        return False
 
     def read_label_map(self, fname: str, on_device: bool = True):
         """A label file as labels -> ``(labels (z, y, x), properties)``: on the device ``decode_label_maps``' tensor; with

@@ -32,10 +32,12 @@ def run_label_cases(rw, cases: Sequence[Sequence[str]], run: Callable, write_thr
 
 
 def folder_plans_and_dataset(folder: str, plans_file_or_dict=None, dataset_json_file_or_dict=None,
-                             missing_plans: Optional[str] = None, missing_dataset: Optional[str] = None):
+                             missing_plans: Optional[str] = None, missing_dataset: Optional[str] = None,
+                             inflate_on_device: bool = False):
     """Plans and dataset.json as given (a dict or a file name), or looked for in ``folder`` -> (PlansManager, dataset.json,
     an instance of the reader-writer they name).  ``missing_*``: the caller's RuntimeError text for a file that is not in
-    the folder, ``{}`` standing for its name (None: opening it raises)."""
+    the folder, ``{}`` standing for its name (None: opening it raises).  ``inflate_on_device``: the reader-writer inflates
+    label files written with ``compress_on_device=True`` on the GPU (``NiftiIO(inflate_on_device=True)``)."""
     from .imageio import prediction_reader_writer_class
     from .plans import PlansManager
 
@@ -48,4 +50,4 @@ def folder_plans_and_dataset(folder: str, plans_file_or_dict=None, dataset_json_
 
     plans_manager = PlansManager(given_or_found(plans_file_or_dict, 'plans.json', missing_plans))
     dataset_json = given_or_found(dataset_json_file_or_dict, 'dataset.json', missing_dataset)
-    return plans_manager, dataset_json, prediction_reader_writer_class(plans_manager, dataset_json)()
+    return plans_manager, dataset_json, prediction_reader_writer_class(plans_manager, dataset_json)(inflate_on_device=inflate_on_device)

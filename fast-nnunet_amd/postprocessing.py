@@ -258,10 +258,11 @@ def apply_postprocessing_to_files(input_files: Sequence[str], output_files: Sequ
 
 def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict],
                                    plans_file_or_dict=None, dataset_json_file_or_dict=None, num_processes=8,
-                                   compress_on_device: bool = False) -> None:
+                                   compress_on_device: bool = False, inflate_on_device: bool = False) -> None:
     """``apply_postprocessing_to_folder`` (remove_connected_components.py:247-294).  If plans_file_or_dict or
     dataset_json_file_or_dict are None, they are looked for in input_folder.  ``num_processes`` is accepted and ignored;
-    ``compress_on_device`` writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded)."""
+    ``compress_on_device`` writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded);
+    ``inflate_on_device`` reads input files that were written that way through ``fnn_inflate_segments`` (no zlib on the host)."""
     from .label_folders import folder_plans_and_dataset, subfiles
     _, dataset_json, rw = folder_plans_and_dataset(
         input_folder, plans_file_or_dict, dataset_json_file_or_dict,
@@ -269,7 +270,7 @@ def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns
         'If the folder you want to apply postprocessing to was create from an ensemble then just specify one of the '
         'plans files of the ensemble members in plans_file_or_dict',
         'Expected plans file missing: {}. The dataset.json should have been copied while running '
-        'nnUNetv2_predict/nnUNetv2_ensemble. Sadge.')
+        'nnUNetv2_predict/nnUNetv2_ensemble. Sadge.', inflate_on_device=inflate_on_device)
     os.makedirs(output_folder, exist_ok=True)
     files = subfiles(input_folder, suffix=dataset_json['file_ending'], join=False)
     apply_postprocessing_to_files([os.path.join(input_folder, i) for i in files], [os.path.join(output_folder, i) for i in files],
@@ -278,9 +279,9 @@ def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns
 
 def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str, plans_file_or_dict=None,
                                        dataset_json_file_or_dict=None, num_processes: int = 8,
-                                       keep_postprocessed_files: bool = True):
+                                       keep_postprocessed_files: bool = True, inflate_on_device: bool = False):
     """The reference's ``determine_postprocessing`` (remove_connected_components.py:52-244) on folders of label files; see
     ``postprocessing_search.determine_postprocessing_on_folder``."""
     from .postprocessing_search import determine_postprocessing_on_folder as run
     return run(folder_predictions, folder_ref, plans_file_or_dict, dataset_json_file_or_dict, num_processes,
-               keep_postprocessed_files)
+               keep_postprocessed_files, inflate_on_device=inflate_on_device)

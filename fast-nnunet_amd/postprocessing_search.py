@@ -390,18 +390,21 @@ class FolderBackend(DeviceBackend):
 
 def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str, plans_file_or_dict=None,
                                        dataset_json_file_or_dict=None, num_processes: int = 8,
-                                       keep_postprocessed_files: bool = True, verbose: bool = True):
+                                       keep_postprocessed_files: bool = True, verbose: bool = True,
+                                       inflate_on_device: bool = False):
     """The reference's ``determine_postprocessing`` (remove_connected_components.py:52-244) on folders of label files.
 
     Leaves what the reference leaves: ``summary.json`` in ``folder_predictions`` (an existing one is reused, as the
     reference reuses it), ``postprocessing.pkl``, ``postprocessing.json``, and - unless ``keep_postprocessed_files`` is
     False - ``postprocessed/<files>`` with ``postprocessed/summary.json``; no ``temp`` folder is made.  Plans or
     dataset.json given as None are looked for in ``folder_predictions``.  ``num_processes`` is accepted and ignored.
-    Returns ``(pp_fns, pp_fn_kwargs)``."""
+    ``inflate_on_device``: predictions written with ``compress_on_device=True``, which the search reads several times, are
+    inflated on the GPU (``NiftiIO(inflate_on_device=True)``).  Returns ``(pp_fns, pp_fn_kwargs)``."""
     from .label_folders import folder_plans_and_dataset, subfiles
     missing = 'Expected plans file missing: {}. The plans files should have been created while running nnUNetv2_predict. Sadge.'
     plans_manager, dataset_json, rw = folder_plans_and_dataset(folder_predictions, plans_file_or_dict,
-                                                               dataset_json_file_or_dict, missing, missing)
+                                                               dataset_json_file_or_dict, missing, missing,
+                                                               inflate_on_device=inflate_on_device)
     ending = dataset_json['file_ending']
     predicted_files = subfiles(folder_predictions, suffix=ending, join=False)
     ref_files = subfiles(folder_ref, suffix=ending, join=False)

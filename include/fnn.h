@@ -506,6 +506,48 @@ int fnn_deflate_masks_count(const void *in, int in_elem_bytes, int64_t n_elems, 
 int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t n_elems, const int32_t *labels, int n_labels,
                            const void *work, void *out, int64_t out_cap, void *stream);
 
+/* A raw deflate stream on the device that is a chain of byte-aligned segments -> its bytes (additive in ABI 4; no
+ * counterpart in the reference, which inflates with zlib on the host).  A general deflate stream cannot be inflated in
+ * parallel; the fragments of fnn_deflate_labels and fnn_deflate_masks_emit, and what zlib writes with Z_FIXED between
+ * Z_FULL_FLUSH points, can.  A segment starts at a byte and is a run of non-final blocks, stored (LEN / NLEN checked) or
+ * fixed Huffman, up to and including the first empty stored block (.. 00 00 FF FF), behind which it ends on a byte; no
+ * match reaches back past its own first output byte, it makes at most FNN_INFLATE_SEGMENT_MAX output bytes and takes at
+ * most 18480 input bytes (csrc/inflate_core.h derives the number).
+ * in: in_bytes bytes, device pointer, 16-byte aligned, claimed to be a chain of segments from byte 0 to byte in_bytes.
+ * starts: n_starts HOST positions where a segment may start, strictly ascending, starts[0] == 0, all below in_bytes;
+ * positions that start no segment are allowed (the caller finds candidates by the marker 00 00 FF FF, which also occurs
+ * inside data).  out: device pointer, 16-byte aligned, of exactly out_bytes bytes.  *crc32, *status: host words.
+ * Count pass: one wave per candidate decodes from starts[i] and records where the segment ended, the bytes it made and
+ * why it stopped.  Chain, on the host: from candidate 0 on, the end of a member must be in_bytes (the chain is closed) or
+ * a candidate (the next member).  Emit pass, launched only for a closed chain whose sizes sum to out_bytes: one wave per
+ * member decodes again into LDS, stores its bytes at the member's offset in `out` (whole aligned 16-byte vectors, the ends
+ * singly) and leaves their CRC-32; the host folds these in chain order into *crc32.
+ * Returns 0 with *status == FNN_INFLATE_OK: out[0, out_bytes) holds the inflated bytes and *crc32 zlib's CRC-32 of them;
+ * the bytes are the same on every run.  Returns 0 with *status != 0: the stream is not served - the reason of the first
+ * member of the chain that was refused, FNN_INFLATE_CHAIN, or FNN_INFLATE_SIZE - and out's contents are unspecified;
+ * nothing is launched past the point of knowing.  Candidates off the chain are ignored, whatever they decoded to.  In
+ * every case nothing is read outside in[0, in_bytes) or written outside out[0, out_bytes), and every loop of the decoder
+ * is bounded by the two budgets of a segment, whatever the input holds.  n_starts == 0 or in_bytes == 0: nothing is
+ * launched, CRC 0, status FNN_INFLATE_OK when out_bytes == 0 too and FNN_INFLATE_SIZE otherwise.
+ * Synchronises the stream (it reports status).  FNN_E_INVALID before any launch, with a message: NULL arguments, negative
+ * sizes, a misaligned in or out, starts that do not begin at 0, do not ascend or reach in_bytes, host pointers for in or
+ * out; FNN_E_UNSUPPORTED: more than 2^31 - 1 candidates.  Scratch, allocated inside the call: 48 B per candidate. */
+#define FNN_INFLATE_SEGMENT_MAX 16384
+#define FNN_INFLATE_OK 0
+#define FNN_INFLATE_DYNAMIC 1   /* a block with dynamic tables (BTYPE 2): not served                                      */
+#define FNN_INFLATE_BTYPE3 2    /* BTYPE 3                                                                              */
+#define FNN_INFLATE_FINAL 3     /* a block with BFINAL set inside the chain                                             */
+#define FNN_INFLATE_SYMBOL 4    /* literal / length symbol 286 or 287, distance symbol 30 or 31                         */
+#define FNN_INFLATE_NLEN 5      /* a stored block whose NLEN is not the complement of LEN                               */
+#define FNN_INFLATE_DISTANCE 6  /* a match that reaches back past the segment's first output byte                       */
+#define FNN_INFLATE_OUTPUT 7    /* a segment of more than FNN_INFLATE_SEGMENT_MAX output bytes                          */
+#define FNN_INFLATE_INPUT 8     /* a segment of more input bytes than its budget                                        */
+#define FNN_INFLATE_END 9       /* the input ended inside a segment                                                     */
+#define FNN_INFLATE_CHAIN 10    /* a member ended short of in_bytes at a position that is no candidate                  */
+#define FNN_INFLATE_SIZE 11     /* the members' sizes do not sum to out_bytes                                           */
+int fnn_inflate_segments(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
+                         int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream);
+
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one
  * axis; returns the number of steps written (<= cap) or a negative error. */

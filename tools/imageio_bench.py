@@ -13,7 +13,12 @@ the device, to zlib level 1 of a mask on the CPU times the number of labels, and
 (``--section label_files``, these rows alone, written to profiles/r21_label_files.txt unless ``--out`` says otherwise)
 fnn_decode_labels on the int16 and the uint8 bytes of an n^3 label map next to fnn_decode_voxels followed by the cast it
 replaces and to a device copy of the same bytes, and compute_metrics_on_folder on a few generated cases of n^3 voxels, per
-case and split into inflate, upload, decode and count.  ``--section read`` runs the file -> device rows of both files alone and
+case and split into inflate, upload, decode and count; and (``--section inflate``, these rows alone, written to
+profiles/r25_inflate.txt unless ``--out`` says otherwise) fnn_inflate_segments on the fragments fnn_deflate_labels makes of an
+n^3 map - 61 labels as uint8 and uint16 (long runs) and a map without runs (every byte a literal) - and on the fragments of
+60 masks, next to zlib's inflate of the same bytes on this machine's CPU and a device copy of the output, and
+compute_metrics_on_folder and apply_postprocessing_to_folder per case with ``inflate_on_device`` off and on over predictions
+written with ``compress_on_device=True``.  ``--section read`` runs the file -> device rows of both files alone and
 ``--section predict_files`` the two predict_from_files rows alone, with the defaults of the full run: for repeating those
 rows in many fresh processes (profiles/r24_host_prologue.txt).
 
@@ -21,7 +26,7 @@ The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, 
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient|deflate|masks|label_files|predict_files|read] [--out FILE]
+                                                          [--section all|reorient|deflate|masks|label_files|inflate|predict_files|read] [--out FILE]
 """
 import argparse
 import gzip
@@ -336,6 +341,139 @@ def bench_label_files(n, reps, cases, dev, say, row):
         row('  one case, decode_label_maps (upload, decode, status, narrowing)', wall(lambda: rw.decode_label_maps(staged), reps)[:3])
 
 
+def bench_inflate(n, reps, cases, dev, say, row):
+    """fnn_inflate_segments (csrc/inflate.hip) against zlib's inflate on this machine's CPU and a device copy of the output,
+    and the folder commands that read with it."""
+    import zlib
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import evaluation as ev
+    from fast_nnunet_amd import imageio as fio
+    from fast_nnunet_amd import postprocessing as pp
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    calls, windows = 10, max(reps, 5)
+    say(f'--- fnn_inflate_segments on fragments made by the device encoders; in and out allocated before, the call allocates its '
+        f'scratch and synchronises; ms per call from {calls} calls inside one pair of events, median (min, max) of {windows} such '
+        f'windows after a warm-up window; zlib on this machine, one thread, by wall clock')
+
+    def candidates(frag):
+        return np.array([0] + [e for e in fio._marker_ends(frag, 0, len(frag)) if e < len(frag)], dtype=np.int64)
+
+    synth = label_map(n, dev)
+    noise = torch.randint(0, 61, (n, n, n), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(7))
+    inputs = [(f'61 labels, uint8 {n}^3 (long runs)', synth), (f'61 labels, uint16 {n}^3 (values x 1000; long runs)', synth.to(torch.int16) * 1000),
+              (f'random labels 0 .. 60, uint8 {n}^3 (no runs: every byte a literal)', noise)]
+    for name, labels in inputs:
+        n_bytes = labels.numel() * labels.element_size()
+        cap = capi.deflate_bound(n_bytes)
+        frag_dev = torch.empty(cap, dtype=torch.uint8, device=dev)
+        n_in, _, crc_enc = capi.deflate_labels(labels.data_ptr(), labels.element_size(), labels.numel(), False, frag_dev.data_ptr(), cap, stream)
+        frag = frag_dev[:n_in].cpu().numpy().tobytes()
+        tscan = wall(lambda: candidates(frag), reps)
+        starts = tscan[3]
+        out = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+        res = []
+        t = events_batched(lambda: res.append(capi.inflate_segments(frag_dev.data_ptr(), n_in, starts, out.data_ptr(), n_bytes, stream)),
+                           calls, windows, dev)
+        same = res[-1] == (0, crc_enc) and bool((out == labels.reshape(-1).view(torch.uint8)).all())
+        say(f'{name}: fragment {n_in / 2 ** 20:.2f} MiB -> {n_bytes / 2 ** 20:.0f} MiB, {len(starts)} candidates')
+        row('  fnn_inflate_segments (count pass, chain on the host, emit pass)', t,
+            f'  {n_bytes / t[0] / 1e6:.1f} GB/s of output; status and CRC good, bytes equal the map: {same}')
+        row('  host: candidate scan of the fragment (bytes.find)', tscan[:3])
+        dst = torch.empty_like(out)
+        tc = events_batched(lambda: dst.copy_(out), calls, windows, dev)
+        fits = '; a cache rate: source and destination fit the Infinity Cache' if 2 * n_bytes <= 256 * 2 ** 20 else ''
+        row('  device-to-device copy of the output bytes', tc, f'  {2 * n_bytes / tc[0] / 1e6:.0f} GB/s; the decoder takes {t[0] / tc[0]:.0f}x{fits}')
+        tz = wall(lambda: zlib.decompressobj(-15).decompress(frag + b'\x03\x00'), reps)
+        row('  zlib inflate of the same fragment (host)', tz[:3],
+            f'  {n_bytes / tz[0] / 1e6:.2f} GB/s; {tz[0] / t[0]:.0f}x the device call\'s time; CRC equal: {zlib.crc32(tz[3]) == res[-1][1]}')
+        host_file = zlib.compress(tz[3], 1)
+        tzz = wall(lambda: zlib.decompress(host_file), reps)
+        row(f'  zlib inflate of zlib\'s own level-1 stream of these bytes ({len(host_file) / 2 ** 20:.2f} MiB, host)', tzz[:3])
+        del frag_dev, out, dst, frag, host_file
+    del noise, inputs
+
+    wanted = list(range(1, 61))
+    nel = synth.numel()
+    work_cap = capi.deflate_masks_work_bytes(nel, len(wanted))
+    work = torch.empty(work_cap, dtype=torch.uint8, device=dev)
+    sizes, crcs = capi.deflate_masks_count(synth.data_ptr(), 1, nel, wanted, work.data_ptr(), work_cap, stream)
+    blob_dev = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+    capi.deflate_masks_emit(synth.data_ptr(), 1, nel, wanted, work.data_ptr(), blob_dev.data_ptr(), sum(sizes), stream)
+    blob = blob_dev.cpu().numpy().tobytes()
+    frags, at = [], 0
+    for nb in sizes:
+        frags.append(blob[at:at + nb])
+        at += nb
+    frag_devs = [torch.frombuffer(bytearray(f), dtype=torch.uint8).to(dev) for f in frags]      # each 16-byte aligned
+    startss = [candidates(f) for f in frags]
+    out = torch.empty(nel, dtype=torch.uint8, device=dev)
+    got = []
+
+    def all_masks():
+        got.clear()
+        for fd, f, st in zip(frag_devs, frags, startss):
+            got.append(capi.inflate_segments(fd.data_ptr(), len(f), st, out.data_ptr(), nel, stream))
+    t = events_batched(all_masks, 1, windows, dev)
+    good = got == [(0, c) for c in crcs] and bool((out == (synth.reshape(-1) == wanted[-1])).all())
+    say(f'60 masks of the 61-label map: fragments {sum(sizes) / 2 ** 20:.2f} MiB -> 60 x {nel / 2 ** 20:.0f} MiB, {sum(len(s) for s in startss)} candidates')
+    row('  60 x fnn_inflate_segments, one per mask, into one buffer', t,
+        f'  {t[0] / 60:.2f} ms per mask, {60 * nel / t[0] / 1e6:.0f} GB/s of mask bytes; status and CRCs good, the last mask equal: {good}')
+    mid = 30
+    tz = wall(lambda: zlib.decompressobj(-15).decompress(frags[mid] + b'\x03\x00'), reps)
+    row(f'  zlib inflate of one mask\'s fragment (host), label {wanted[mid]}', tz[:3], f'  x 60 = {60 * tz[0]:.0f} ms = {60 * tz[0] / t[0]:.0f}x')
+    del work, blob_dev, frag_devs, out, frags, blob
+
+    say(f'--- folder commands, {cases} cases of {n}^3 voxels, 60 foreground labels: predictions written with compress_on_device=True; '
+        f'per-case wall clock with inflate_on_device off (the route before) and on')
+    plans = {'dataset_name': 'd', 'plans_name': 'p', 'image_reader_writer': 'NibabelIO', 'configurations': {}}
+    dj = {'labels': dict({'background': 0}, **{f'l{i}': i for i in wanted}), 'file_ending': '.nii.gz', 'channel_names': {'0': 'CT'}}
+    with tempfile.TemporaryDirectory() as tmp:
+        ref_z, ref_d, pred_dir = (os.path.join(tmp, d) for d in ('ref_zlib', 'ref_device', 'pred'))
+        for d in (ref_z, ref_d, pred_dir):
+            os.makedirs(d)
+        writer = fio.NiftiIO(dev)
+        props = {'nibabel_stuff': {'original_affine': np.diag([0.8, 0.8, 1.25, 1.0])}}
+        for i in range(cases):
+            ref = label_map(n, dev, seed=30 + i)
+            pred = ref.clone()
+            pred[i::7] = 0
+            writer.write_seg(ref.cpu().numpy(), os.path.join(ref_z, f'case{i}.nii.gz'), props)
+            writer.write_seg(writer.compress_labels(ref, props), os.path.join(ref_d, f'case{i}.nii.gz'), props)
+            writer.write_seg(writer.compress_labels(pred, props), os.path.join(pred_dir, f'case{i}.nii.gz'), props)
+            del ref, pred
+        sizes = [os.path.getsize(os.path.join(d, 'case0.nii.gz')) / 2 ** 20 for d in (ref_z, ref_d, pred_dir)]
+        say(f'case0 on disk: reference by zlib {sizes[0]:.1f} MiB, reference by the device {sizes[1]:.1f} MiB, prediction {sizes[2]:.1f} MiB')
+        for what, ref_dir in (('references written by zlib (they inflate on the host either way)', ref_z), ('references written on the device too', ref_d)):
+            made = {}
+            for flag in (False, True):
+                rw = fio.NiftiIO(dev, inflate_on_device=flag)
+                ev.compute_metrics_on_folder(ref_dir, pred_dir, None, rw, '.nii.gz', wanted)                 # warm-up
+                t = wall(lambda: ev.compute_metrics_on_folder(ref_dir, pred_dir, None, rw, '.nii.gz', wanted), reps)
+                made[flag] = t
+                row(f'compute_metrics_on_folder, {what[:34]}.., flag {"on" if flag else "off"}', t[:3],
+                    f'  {t[0] / cases:.1f} ms per case; routes {rw.inflate_stats}')
+            say(f'  {what}: {made[False][0] / made[True][0]:.2f}x; equal results: {repr(made[False][3]) == repr(made[True][3])}')
+        fns, kwargs = [pp.remove_all_but_largest_component_from_segmentation], [{'labels_or_regions': wanted}]
+        made = {}
+        for flag in (False, True):
+            out_dir = os.path.join(tmp, f'post_{int(flag)}')
+            run = lambda: pp.apply_postprocessing_to_folder(pred_dir, out_dir, fns, kwargs, plans, dj, compress_on_device=True,   # noqa: E731
+                                                            inflate_on_device=flag)
+            run()                                                                                            # warm-up
+            made[flag] = wall(run, reps)
+            row(f'apply_postprocessing_to_folder (compress_on_device), flag {"on" if flag else "off"}', made[flag][:3],
+                f'  {made[flag][0] / cases:.1f} ms per case')
+        same = all(open(os.path.join(tmp, 'post_0', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'post_1', f'case{i}.nii.gz'), 'rb').read()
+                   for i in range(cases))
+        say(f'  apply_postprocessing_to_folder: {made[False][0] / made[True][0]:.2f}x; identical output files: {same}')
+        pair = [os.path.join(ref_d, 'case0.nii.gz'), os.path.join(pred_dir, 'case0.nii.gz')]
+        for flag in (False, True):
+            rw = fio.NiftiIO(dev, inflate_on_device=flag)
+            staged = rw.stage_label_files(pair)
+            row(f'  one case, both files device-written, flag {"on" if flag else "off"}: StagedCase.fill (host)', wall(staged.fill, reps)[:3])
+            row(f'  one case, both files device-written, flag {"on" if flag else "off"}: decode_label_maps', wall(lambda: rw.decode_label_maps(staged), reps)[:3])
+
+
 def bench_predict_files(a, dev, say, row, tmp):
     """predict_from_files_sequential and predict_from_files on a.cases generated cases under tmp (``--section predict_files``
     runs these rows alone)."""
@@ -384,7 +522,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'predict_files', 'read'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'inflate', 'predict_files', 'read'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -409,6 +547,10 @@ def main():
     if a.section == 'label_files':
         bench_label_files(n, a.reps, a.cases, dev, say, row)
         write_out(a.out or os.path.join(ROOT, 'profiles', 'r21_label_files.txt'), lines)
+        return
+    if a.section == 'inflate':
+        bench_inflate(n, a.reps, a.cases, dev, say, row)
+        write_out(a.out or os.path.join(ROOT, 'profiles', 'r25_inflate.txt'), lines)
         return
     if a.section == 'predict_files':
         with tempfile.TemporaryDirectory() as tmp:
