@@ -72,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -136,6 +136,8 @@ def load_library() -> C.CDLL:
     lib.fnn_average_probabilities.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(C.c_int32), i64, vp, vp, i32, vp]
     lib.fnn_confusion_counts.argtypes = [vp, C.POINTER(vp), i32, i32, i64, C.POINTER(C.c_int32), i32, i32, i32,
                                          C.POINTER(i64), vp]
+    lib.fnn_surface_count.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(i64), C.POINTER(i64), vp]
+    lib.fnn_surface_distances.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(C.c_double), vp, i64, vp]
     lib.fnn_decode_voxels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
     lib.fnn_decode_labels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, i32, vp, vp, vp]
     lib.fnn_reorient.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
@@ -466,6 +468,40 @@ def confusion_counts(ref_ptr: int, pred_ptrs: Sequence[int], uint16: bool, n_vox
                                    table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_classes),
                                    int(ignore_value), counts.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
     return counts[:n_pred]
+
+
+def _member_table(member):
+    member = np.ascontiguousarray(member, dtype=np.uint8)
+    if member.ndim != 2:
+        raise ValueError('member must be [n_regions, n_table]')
+    return member, member.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def surface_count(ref_ptr: int, pred_ptr: int, uint16: bool, shape, member, stream: int = 0):
+    """fnn_surface_count on two device label maps (z, y, x); ``member`` uint8 [n_regions, n_table].  Returns
+    (n_surface int64 [n_regions, 2] = surface voxels of ref and of pred, boxes int64 [n_regions, 6])."""
+    lib = load_library()
+    member, mp = _member_table(member)
+    n_regions, n_table = member.shape
+    n_surface = np.zeros((max(n_regions, 1), 2), np.int64)
+    boxes = np.zeros((max(n_regions, 1), 6), np.int64)
+    check(lib.fnn_surface_count(ref_ptr, pred_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8,
+                                (C.c_int64 * 3)(*[int(i) for i in shape]), mp, int(n_table), int(n_regions),
+                                n_surface.ctypes.data_as(C.POINTER(C.c_int64)), boxes.ctypes.data_as(C.POINTER(C.c_int64)),
+                                stream), lib)
+    return n_surface[:n_regions], boxes[:n_regions]
+
+
+def surface_distances(ref_ptr: int, pred_ptr: int, uint16: bool, shape, member, spacing, sq_dist_ptr: int, cap: int,
+                      stream: int = 0) -> None:
+    """fnn_surface_distances: the squared distances of every region with two non-empty sides into the device buffer of
+    ``cap`` doubles at ``sq_dist_ptr``, in the order ``surface_count``'s sizes give (pred's surface, then ref's)."""
+    lib = load_library()
+    member, mp = _member_table(member)
+    n_regions, n_table = member.shape
+    check(lib.fnn_surface_distances(ref_ptr, pred_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8,
+                                    (C.c_int64 * 3)(*[int(i) for i in shape]), mp, int(n_table), int(n_regions),
+                                    (C.c_double * 3)(*[float(s) for s in spacing]), sq_dist_ptr, int(cap), stream), lib)
 
 
 def _order(regions_class_order, heads: int):

@@ -16,6 +16,11 @@ Two halves:
 * host - ``metrics_from_counts``: every label or region (a tuple is a union of labels) gets TP / FP / FN / TN from the
   matrix, and the per-case dict is built with the reference's numpy scalar types and expressions, so the floats are
   bit-identical to the reference's.  This half needs no GPU.
+
+Beyond the reference, on request (``surface_metrics=True``): the boundary metrics HD, HD95, ASSD and NSD with medpy's
+definitions.  ``surface_distances`` gets the exact distances from every surface voxel of one mask to the surface of the
+other from ``fnn_surface_count`` / ``fnn_surface_distances`` (csrc/surface.hip); ``surface_metrics_of`` is the host half,
+plain numpy expressions on the downloaded distances.
 """
 from __future__ import annotations
 
@@ -273,22 +278,155 @@ def _check_ignore(labels_or_regions, ignore_label):
         raise ValueError(f'ignore label {ignore_label} is also one of the evaluated labels')
 
 
+# ---- surface distances and the boundary metrics ---------------------------------------------------------------------------
+SURFACE_KEYS = ('HD', 'HD95', 'ASSD', 'NSD', 'n_surf_pred', 'n_surf_ref')
+MAX_SURFACE_REGIONS = 1024
+
+
+def _check_surface_request(surface_metrics: bool, ignore_label, spacing):
+    if not surface_metrics:
+        return
+    if ignore_label is not None:
+        raise ValueError(f'surface metrics are refused together with an ignore label ({ignore_label}): a boundary next to '
+                         f'ignored voxels has no agreed meaning')
+    if spacing is None:
+        raise ValueError('surface metrics need the voxel spacing (z, y, x)')
+
+
+def region_members(labels_or_regions: Sequence[LabelOrRegion]) -> np.ndarray:
+    """member for fnn_surface_count: uint8 [n_regions, largest label + 1], 1 where the label belongs to the region."""
+    regions = [_members(r) for r in labels_or_regions]
+    if not 1 <= len(regions) <= MAX_SURFACE_REGIONS:
+        raise ValueError(f'1..{MAX_SURFACE_REGIONS} labels or regions can be measured at once, got {len(regions)}')
+    for v in (v for r in regions for v in r):
+        if v < 0 or v > 65535:
+            raise ValueError(f'label {v} is outside 0..65535')
+    member = np.zeros((len(regions), max((v for r in regions for v in r), default=0) + 1), np.uint8)
+    for k, r in enumerate(regions):
+        member[k, r] = 1
+    return member
+
+
+def _volume_shape(shape: tuple) -> tuple:
+    """(z, y, x) of a label map's shape; leading axes of length 1 (the reference's [1, X, Y, Z]) are dropped."""
+    shape = tuple(int(i) for i in shape)
+    while len(shape) > 3 and shape[0] == 1:
+        shape = shape[1:]
+    if len(shape) != 3:
+        raise ValueError(f'surface distances are measured on 3-D label maps, got shape {shape}')
+    return shape
+
+
+def _spacing3(spacing) -> tuple:
+    sp = tuple(float(s) for s in np.asarray(spacing, dtype=np.float64).reshape(-1))
+    if len(sp) != 3 or not all(math.isfinite(s) and s > 0 for s in sp):
+        raise ValueError(f'spacing must be three finite positive numbers (z, y, x), got {spacing}')
+    return sp
+
+
+def _surface_distances(seg_ref, seg_pred, labels_or_regions, spacing, checked: bool = False):
+    """-> ({r: (dp, dr)}, n_surface int64 [n_regions, 2] = |S(ref_r)|, |S(pred_r)|, boxes int64 [n_regions, 6])."""
+    labels_or_regions = list(labels_or_regions)
+    if _shape(seg_ref) != _shape(seg_pred):
+        raise ValueError(f'shape mismatch: reference {_shape(seg_ref)}, prediction {_shape(seg_pred)}')
+    shape, sp, member = _volume_shape(_shape(seg_ref)), _spacing3(spacing), region_members(labels_or_regions)
+    if not checked:
+        for s in (seg_ref, seg_pred):
+            check_label_map(s)
+    u16 = not (_is_u8(seg_ref) and _is_u8(seg_pred))
+    dev = next((s.device for s in (seg_ref, seg_pred) if isinstance(s, torch.Tensor) and s.device.type == 'cuda'), None) or _device()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ref, pred = to_device_labels(seg_ref, u16, dev), to_device_labels(seg_pred, u16, dev)
+        n_surface, boxes = capi.surface_count(ref.data_ptr(), pred.data_ptr(), u16, shape, member, stream)
+        both = (n_surface[:, 0] > 0) & (n_surface[:, 1] > 0)
+        total = int(n_surface[both].sum())
+        buf = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        capi.surface_distances(ref.data_ptr(), pred.data_ptr(), u16, shape, member, sp, buf.data_ptr(), total, stream)
+        dist = np.sqrt(buf[:total].cpu().numpy())
+    out, at = {}, 0
+    for k, r in enumerate(labels_or_regions):
+        n_r, n_p = (int(n_surface[k, 0]), int(n_surface[k, 1])) if both[k] else (0, 0)
+        out[r] = (dist[at:at + n_p], dist[at + n_p:at + n_p + n_r])
+        at += n_p + n_r
+    return out, n_surface, boxes
+
+
+def surface_distances(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], spacing) -> dict:
+    """``{label_or_region: (dp, dr)}``: float64 arrays of the distances from every surface voxel of the prediction to the
+    reference's surface and the other way round, in raster order; both empty where either mask is.  The surface of a mask is
+    the mask minus its 6-neighbourhood erosion (outside the volume is background); distances are Euclidean in the units of
+    ``spacing`` (z, y, x), bit for bit ``distance_transform_edt(~S(other), sampling=spacing)[S(this)]``.  Label maps as
+    ``confusion_counts`` takes them, 3-D (leading axes of length 1 are dropped)."""
+    return _surface_distances(seg_ref, seg_pred, labels_or_regions, spacing)[0]
+
+
+def surface_metrics_of(dp, dr, n_p, n_r, tolerance) -> dict:
+    """The host half: medpy's hd / hd95 / assd and the normalised surface Dice at ``tolerance`` from the directed distances
+    ``dp`` (prediction to reference) and ``dr``; ``n_p`` / ``n_r`` are the surface voxels of the prediction / reference.
+    NaN where either mask is empty (as Dice of an empty pair; medpy raises there)."""
+    out = {}
+    if n_p == 0 or n_r == 0:
+        out['HD'] = out['HD95'] = out['ASSD'] = out['NSD'] = np.nan
+    else:
+        out['HD'] = max(dp.max(), dr.max())
+        out['HD95'] = np.percentile(np.hstack((dp, dr)), 95)
+        out['ASSD'] = np.mean((dp.mean(), dr.mean()))
+        out['NSD'] = ((dp <= tolerance).sum() + (dr <= tolerance).sum()) / (n_p + n_r)
+    out['n_surf_pred'] = np.int64(n_p)
+    out['n_surf_ref'] = np.int64(n_r)
+    return out
+
+
+def _tolerance_of(nsd_tolerance, label_or_region) -> float:
+    if isinstance(nsd_tolerance, dict):
+        if label_or_region not in nsd_tolerance:
+            raise ValueError(f'nsd_tolerance names no tolerance for {label_or_region}')
+        return float(nsd_tolerance[label_or_region])
+    return float(nsd_tolerance)
+
+
+def compute_surface_metrics(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], spacing, nsd_tolerance=1.0,
+                            checked: bool = False) -> dict:
+    """``{label_or_region: {'HD', 'HD95', 'ASSD', 'NSD', 'n_surf_pred', 'n_surf_ref'}}``.  ``nsd_tolerance``: a number, or a
+    dict with one per label or region, in the units of ``spacing``."""
+    labels_or_regions = list(labels_or_regions)
+    tol = {r: _tolerance_of(nsd_tolerance, r) for r in labels_or_regions}
+    dist, n_surface, _ = _surface_distances(seg_ref, seg_pred, labels_or_regions, spacing, checked)
+    return {r: surface_metrics_of(*dist[r], int(n_surface[k, 1]), int(n_surface[k, 0]), tol[r])
+            for k, r in enumerate(labels_or_regions)}
+
+
+def _with_surface(metrics: dict, surface: dict) -> dict:
+    for r, m in metrics.items():
+        m.update(surface[r])
+    return metrics
+
+
 def compute_metrics(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None,
-                    reference_file=None, prediction_file=None) -> dict:
+                    reference_file=None, prediction_file=None, *, surface_metrics: bool = False, spacing=None,
+                    nsd_tolerance=1.0) -> dict:
     """compute_metrics (evaluate_predictions.py:88-118) with arrays in place of the files: numpy arrays or torch
-    tensors of one shape (the reference's [1, X, Y, Z] included), integer labels 0..65535."""
+    tensors of one shape (the reference's [1, X, Y, Z] included), integer labels 0..65535.  ``surface_metrics``: every
+    label's dict also gets ``compute_surface_metrics``' six keys for ``spacing`` (z, y, x) and ``nsd_tolerance``."""
     labels_or_regions = list(labels_or_regions)
     _check_ignore(labels_or_regions, ignore_label)
+    _check_surface_request(surface_metrics, ignore_label, spacing)
     counts = confusion_counts(seg_ref, [seg_pred], count_classes(labels_or_regions), ignore_label)[0]
-    return case_result(metrics_from_counts(counts, labels_or_regions), reference_file, prediction_file)
+    metrics = metrics_from_counts(counts, labels_or_regions)
+    if surface_metrics:
+        _with_surface(metrics, compute_surface_metrics(seg_ref, seg_pred, labels_or_regions, spacing, nsd_tolerance, checked=True))
+    return case_result(metrics, reference_file, prediction_file)
 
 
 def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions: Sequence[LabelOrRegion],
                               ignore_label: Optional[int] = None, names: Optional[Sequence[str]] = None,
-                              output_file: Optional[str] = None) -> dict:
+                              output_file: Optional[str] = None, *, surface_metrics: bool = False, spacing=None,
+                              nsd_tolerance=1.0) -> dict:
     """compute_metrics_on_folder (evaluate_predictions.py:121-177) on pairs of arrays: ``preds[i]`` is evaluated
     against ``refs[i]``; ``names[i]`` (optional) fills reference_file / prediction_file.  Returns
-    ``{'metric_per_case', 'mean', 'foreground_mean'}``; writes it to ``output_file`` (.json) when given."""
+    ``{'metric_per_case', 'mean', 'foreground_mean'}``; writes it to ``output_file`` (.json) when given.
+    ``surface_metrics``: as ``compute_metrics``; ``spacing`` is one (z, y, x) for all cases or one per case."""
     if output_file is not None and not output_file.endswith('.json'):
         raise ValueError('output_file should end with .json')
     if len(refs) != len(preds):
@@ -296,8 +434,15 @@ def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions
     if names is not None and len(names) != len(preds):
         raise ValueError('one name per case expected')
     labels_or_regions = list(labels_or_regions)
+    _check_surface_request(surface_metrics, ignore_label, spacing)
+    spacings = [None] * len(preds)
+    if surface_metrics:
+        spacings = [spacing] * len(preds) if np.ndim(spacing) == 1 else list(spacing)
+        if len(spacings) != len(preds):
+            raise ValueError('one spacing for all cases or one per case expected')
     results = [compute_metrics(r, p, labels_or_regions, ignore_label,
-                               None if names is None else names[i], None if names is None else names[i])
+                               None if names is None else names[i], None if names is None else names[i],
+                               surface_metrics=surface_metrics, spacing=spacings[i], nsd_tolerance=nsd_tolerance)
                for i, (r, p) in enumerate(zip(refs, preds))]
     summary = aggregate(results, labels_or_regions)
     if output_file is not None:
@@ -322,37 +467,53 @@ def _paired_files(folder_ref: str, folder_pred: str, file_ending: str, chill: bo
 
 
 def compute_metrics_on_files(files_ref: Sequence[str], files_pred: Sequence[str], image_reader_writer,
-                             labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None) -> List[dict]:
+                             labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None, *,
+                             surface_metrics: bool = False, spacing=None, nsd_tolerance=1.0) -> List[dict]:
     """``compute_metrics`` (:88-118) for every pair of label files: both are decoded to labels on the device and counted
     by ``fnn_confusion_counts``; the reader thread inflates the next pair meanwhile.  A pair of different shapes raises a
-    ValueError that names both files."""
+    ValueError that names both files.  ``surface_metrics``: every label's dict also gets ``compute_surface_metrics``' six
+    keys, measured with the spacing of the reference file; a prediction whose spacing differs (``np.allclose``) raises a
+    ValueError that names both files.  ``spacing`` (z, y, x), when given, is used for every case in place of the files' own,
+    which are then not compared."""
     from .label_folders import run_label_cases
     labels_or_regions = list(labels_or_regions)
     _check_ignore(labels_or_regions, ignore_label)
+    _check_surface_request(surface_metrics, ignore_label, ())
     values = count_classes(labels_or_regions)
     cases = [[r, p] for r, p in zip(files_ref, files_pred)]
 
     def run(i, maps):
-        (ref, _), (pred, _) = maps
+        (ref, ref_props), (pred, pred_props) = maps
         if tuple(ref.shape) != tuple(pred.shape):
             raise ValueError(f'shape mismatch: reference {cases[i][0]} is {tuple(ref.shape)}, prediction {cases[i][1]} is '
                              f'{tuple(pred.shape)}')
         counts = confusion_counts(ref, [pred], values, ignore_label, checked=True)[0]
-        return case_result(metrics_from_counts(counts, labels_or_regions), cases[i][0], cases[i][1]), None
+        metrics = metrics_from_counts(counts, labels_or_regions)
+        if surface_metrics:
+            of_ref, of_pred = list(ref_props['spacing']), list(pred_props['spacing'])
+            if spacing is None and (len(of_ref) != len(of_pred) or not np.allclose(of_ref, of_pred)):
+                raise ValueError(f'spacing mismatch: reference {cases[i][0]} has {tuple(of_ref)}, prediction {cases[i][1]} has '
+                                 f'{tuple(of_pred)}')
+            _with_surface(metrics, compute_surface_metrics(ref, pred, labels_or_regions, of_ref if spacing is None else spacing,
+                                                           nsd_tolerance, checked=True))
+        return case_result(metrics, cases[i][0], cases[i][1]), None
 
     return run_label_cases(image_reader_writer, cases, run)
 
 
 def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Optional[str], image_reader_writer,
                               file_ending: str, regions_or_labels: Sequence[LabelOrRegion], ignore_label: Optional[int] = None,
-                              num_processes: int = DEFAULT_NUM_PROCESSES, chill: bool = True) -> dict:
+                              num_processes: int = DEFAULT_NUM_PROCESSES, chill: bool = True, *, surface_metrics: bool = False,
+                              spacing=None, nsd_tolerance=1.0) -> dict:
     """compute_metrics_on_folder (:121-173).  ``output_file`` must end with .json; can be None.  ``image_reader_writer``: an
-    instance of this package's reader-writer classes.  ``num_processes`` is accepted and ignored: no process is started."""
+    instance of this package's reader-writer classes.  ``num_processes`` is accepted and ignored: no process is started.
+    ``surface_metrics`` / ``spacing`` / ``nsd_tolerance``: as ``compute_metrics_on_files``."""
     if output_file is not None:
         assert output_file.endswith('.json'), 'output_file should end with .json'
     files_ref, files_pred = _paired_files(folder_ref, folder_pred, file_ending, chill)
     regions_or_labels = list(regions_or_labels)
-    results = compute_metrics_on_files(files_ref, files_pred, image_reader_writer, regions_or_labels, ignore_label)
+    results = compute_metrics_on_files(files_ref, files_pred, image_reader_writer, regions_or_labels, ignore_label,
+                                       surface_metrics=surface_metrics, spacing=spacing, nsd_tolerance=nsd_tolerance)
     result = aggregate(results, regions_or_labels)
     if output_file is not None:
         save_summary_json(result, output_file)
@@ -361,10 +522,12 @@ def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Op
 
 def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_file: str, plans_file: str,
                                output_file: Optional[str] = None, num_processes: int = DEFAULT_NUM_PROCESSES,
-                               chill: bool = False, inflate_on_device: bool = False):
+                               chill: bool = False, inflate_on_device: bool = False, *, surface_metrics: bool = False,
+                               spacing=None, nsd_tolerance=1.0):
     """compute_metrics_on_folder2 (:177-196): labels or regions, ignore label, file ending and the reader-writer from
     ``dataset.json`` and the plans; ``output_file`` defaults to ``<folder_pred>/summary.json``.  ``inflate_on_device``: label
-    files written with ``compress_on_device=True`` are inflated on the GPU (``NiftiIO(inflate_on_device=True)``)."""
+    files written with ``compress_on_device=True`` are inflated on the GPU (``NiftiIO(inflate_on_device=True)``).
+    ``surface_metrics`` / ``spacing`` / ``nsd_tolerance``: as ``compute_metrics_on_files``."""
     from .imageio import determine_reader_writer_from_dataset_json
     from .label_folders import load_json
     from .plans import PlansManager
@@ -375,15 +538,17 @@ def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_f
     lm = PlansManager(plans_file).get_label_manager(dataset_json)
     compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, dataset_json['file_ending'],
                               lm.foreground_regions if lm.has_regions else lm.foreground_labels, lm.ignore_label,
-                              num_processes, chill=chill)
+                              num_processes, chill=chill, surface_metrics=surface_metrics, spacing=spacing,
+                              nsd_tolerance=nsd_tolerance)
 
 
 def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: Sequence[int], output_file: Optional[str] = None,
                                      num_processes: int = DEFAULT_NUM_PROCESSES, ignore_label: Optional[int] = None,
-                                     chill: bool = False, inflate_on_device: bool = False):
+                                     chill: bool = False, inflate_on_device: bool = False, *, surface_metrics: bool = False,
+                                     spacing=None, nsd_tolerance=1.0):
     """compute_metrics_on_folder_simple (:199-212): the file ending is that of the first reference file (``.nii.gz``
     whole, where the reference's ``os.path.splitext`` would keep ``.gz`` and then match the same files).
-    ``inflate_on_device``: as ``compute_metrics_on_folder2``."""
+    ``inflate_on_device``, ``surface_metrics``, ``spacing``, ``nsd_tolerance``: as ``compute_metrics_on_folder2``."""
     from .imageio import determine_reader_writer_from_file_ending
     from .label_folders import subfiles
     example_file = subfiles(folder_ref, join=True)[0]
@@ -392,4 +557,5 @@ def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: 
     if output_file is None:
         output_file = os.path.join(folder_pred, 'summary.json')
     compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, file_ending, labels, ignore_label=ignore_label,
-                              num_processes=num_processes, chill=chill)
+                              num_processes=num_processes, chill=chill, surface_metrics=surface_metrics, spacing=spacing,
+                              nsd_tolerance=nsd_tolerance)

@@ -404,6 +404,32 @@ int fnn_confusion_counts(const void *ref, const void *const *pred, int n_pred, i
                          const int32_t *class_of_value, int n_table, int n_classes, int ignore_value,
                          int64_t *counts, void *stream);
 
+/* Surface distances between a reference and a predicted label map (additive in ABI 4), for the boundary metrics HD, HD95,
+ * ASSD and NSD of every label or region of a case; the reference has no such function, the definitions are medpy's.
+ * ref, pred: device label maps [shape[0]][shape[1]][shape[2]] = (z, y, x) of label_dtype (FNN_LABEL_U8 / U16), aligned to
+ * their element.  member (host, [n_regions][n_table]): member[r][v] != 0 - label value v belongs to region r; values >=
+ * n_table belong to nothing; 1..1024 regions.  The mask of a region is the union of its values; its surface S is the mask
+ * minus its erosion with the 6-neighbourhood, everything outside the volume counting as background.
+ * fnn_surface_count: n_surface (host [n_regions][2]) receives |S(ref_r)| and |S(pred_r)|, boxes (host [n_regions][6]) the
+ * [lo, hi) box of ref_r | pred_r per axis as lo_z, hi_z, lo_y, hi_y, lo_x, hi_x - all zero when both are empty.
+ * fnn_surface_distances: sq_dist (device, 8-byte aligned, room for cap doubles) receives, region after region, for every
+ * voxel a of S(pred_r) in raster order min over b in S(ref_r) of ((sz dz)^2 + (sy dy)^2) + (sx dx)^2 with spacing = (sz,
+ * sy, sx) - float64, evaluated in that order, the minimum taken over the evaluated values - and then the same for every
+ * voxel of S(ref_r) against S(pred_r).  A region with an empty side contributes nothing.  cap below the total
+ * (sum of n_surface[r][0] + n_surface[r][1] over the regions with two non-empty sides) is FNN_E_INVALID and writes nothing.
+ * Nothing is read outside the two maps, nothing is written outside sq_dist[0, total); the same input gives the same bytes.
+ * Both synchronise the stream.  FNN_E_INVALID before any launch, with a message: NULL or host pointers, an unknown label
+ * dtype, n_regions outside 1..1024, negative n_table, a negative extent, misaligned maps or sq_dist, a spacing that is not
+ * finite and positive, a negative cap; FNN_E_UNSUPPORTED: more than 2^31 - 1 voxels.  A volume without voxels gives zeros.
+ * Scratch, allocated inside the call: 16 B + 24 B per region and 8 B per table value and 64 regions; fnn_surface_distances
+ * also 12 B per voxel of the largest region box (8 B for the transform's y-pass values and 4 B for its z-pass voxel counts:
+ * the passes are out of place so that a line longer than the LDS tile can be walked in pieces) + 4 B per 1024 box voxels
+ * for the compaction's scan. */
+int fnn_surface_count(const void *ref, const void *pred, int label_dtype, const int64_t shape[3], const uint8_t *member,
+                      int n_table, int n_regions, int64_t *n_surface, int64_t *boxes, void *stream);
+int fnn_surface_distances(const void *ref, const void *pred, int label_dtype, const int64_t shape[3], const uint8_t *member,
+                          int n_table, int n_regions, const double spacing[3], double *sq_dist, int64_t cap, void *stream);
+
 /* The voxels of an image file as the file holds them -> float32 (additive in ABI 4): what the reference's
  * NibabelIO.read_images ends with (imageio/nibabel_reader_writer.py:56 and :89 - get_fdata() in float64, then
  * np.vstack(..., dtype=float32, casting='unsafe')) for one file, without the host cast.  raw: device pointer to the first

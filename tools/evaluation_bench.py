@@ -4,6 +4,11 @@ on a smaller case next to them.
 
 usage (repo root, GPU box): python tools/evaluation_bench.py [--n 512] [--cases 3] [--reps 10] [--out FILE]
 Kernel times: run it under rocprofv3 --kernel-trace --stats.
+
+--section surface: the surface-distance entries (fnn_surface_count, fnn_surface_distances) on a 61-label pair whose
+prediction is the reference with perturbed boundaries, the scipy route for three labels on this machine's CPU, and
+compute_metrics_on_folder with and without surface_metrics; writes profiles/r26_surface_metrics.txt unless --out names
+another file.
 """
 import argparse
 import os
@@ -30,14 +35,153 @@ def noisy(seg, seed, frac=0.002):
     return out
 
 
+def organ_map(n, seed=61):
+    """60 ellipsoids of labels 1..60 with semi-axes n/32 .. n/6 at random places (later ones paint over earlier ones): compact
+    label boxes, as organs have."""
+    rng = np.random.default_rng(seed)
+    seg = np.zeros((n, n, n), np.uint8)
+    for label in range(1, 61):
+        radii = rng.integers(max(2, n // 32), max(3, n // 6), 3)
+        centre = [int(rng.integers(r, n - r)) for r in radii]
+        box = tuple(slice(c - r, c + r + 1) for c, r in zip(centre, radii))
+        z, y, x = np.ogrid[tuple(slice(-int(r), int(r) + 1) for r in radii)]
+        inside = (z / radii[0]) ** 2 + (y / radii[1]) ** 2 + (x / radii[2]) ** 2 <= 1.0
+        seg[box][inside] = label
+    return seg
+
+
+def perturbed_boundaries(seg, seed):
+    """The map with every boundary moved by one voxel along x inside about half of its 16^3 blocks."""
+    rng = np.random.default_rng(seed)
+    blocks = rng.random(tuple((n + 15) // 16 for n in seg.shape)) < 0.5
+    where = np.repeat(np.repeat(np.repeat(blocks, 16, 0), 16, 1), 16, 2)[:seg.shape[0], :seg.shape[1], :seg.shape[2]]
+    moved = np.roll(seg, 1, axis=2)
+    moved[:, :, 0] = seg[:, :, 0]
+    return np.where(where, moved, seg)
+
+
+def _events(dev, fn, reps):
+    ts = []
+    for r in range(reps + 1):
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        if r:
+            ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), min(ts), max(ts), out
+
+
+def surface_section(a):
+    import tempfile
+    from scipy import ndimage as ndi
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import evaluation as ev
+    from fast_nnunet_amd.imageio import NiftiIO
+    dev = torch.device('cuda', 0)
+    spacing = (2.5, 0.7421875, 0.7421875)
+    labels = list(range(1, 61))
+    ref = organ_map(a.n)
+    pred = perturbed_boundaries(ref, 7)
+    member = ev.region_members(labels)
+    d_ref, d_pred = torch.from_numpy(ref).to(dev).reshape(-1), torch.from_numpy(pred).to(dev).reshape(-1)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    lines = [f'evaluation_bench --section surface: {a.n}^3 uint8 pair, 61 labels (60 ellipsoids measured, organ_map), prediction = reference with '
+             f'boundaries moved by one voxel in half of the 16^3 blocks; {int((ref != pred).sum())} voxels differ; spacing {spacing}; '
+             f'device {torch.cuda.get_device_name(dev)}',
+             f'device calls: median (min, max) of {a.reps} after one warm-up, events around the call (scratch allocation, '
+             f'launches and the synchronising copy-back of the sizes included)']
+    ms, lo, hi, (n_surface, boxes) = _events(
+        dev, lambda: capi.surface_count(d_ref.data_ptr(), d_pred.data_ptr(), False, ref.shape, member, stream), a.reps)
+    lines.append(f'fnn_surface_count, 60 regions: {ms:.2f} ms (min {lo:.2f} max {hi:.2f})')
+    both = (n_surface[:, 0] > 0) & (n_surface[:, 1] > 0)
+    total = int(n_surface[both].sum())
+    volumes = np.prod(boxes[:, 1::2] - boxes[:, 0::2], axis=1)
+    buf = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+    ms, lo, hi, _ = _events(dev, lambda: capi.surface_distances(d_ref.data_ptr(), d_pred.data_ptr(), False, ref.shape, member, spacing,
+                                                                buf.data_ptr(), total, stream), a.reps)
+    lines.append(f'fnn_surface_distances, {int(both.sum())} regions with two sides, {total} distances: {ms:.2f} ms (min {lo:.2f} max '
+                 f'{hi:.2f}); box voxels walked (both directions): {2 * int(volumes[both].sum())} = '
+                 f'{2 * volumes[both].sum() / ref.size:.2f} volumes; largest box {int(volumes.max())} voxels '
+                 f'({int(volumes.max()) * 12 / 2 ** 20:.0f} MiB of scratch)')
+    t0 = time.perf_counter()
+    host = buf[:total].cpu().numpy()
+    lines.append(f'download of the distances: {total * 8 / 1e6:.1f} MB in {(time.perf_counter() - t0) * 1e3:.2f} ms')
+    t0 = time.perf_counter()
+    got = ev.compute_surface_metrics(d_ref.reshape(ref.shape), d_pred.reshape(ref.shape), labels, spacing, checked=True)
+    lines.append(f'compute_surface_metrics (count, distances, download, numpy metrics of 60 labels): '
+                 f'{(time.perf_counter() - t0) * 1e3:.1f} ms')
+
+    # the scipy route on this machine's CPU for three labels, cropped to the same boxes and on the whole volume
+    structure = ndi.generate_binary_structure(3, 1)
+
+    def scipy_route(mr, mp):
+        t = time.perf_counter()
+        sr_, sp_ = mr & ~ndi.binary_erosion(mr, structure, border_value=0), mp & ~ndi.binary_erosion(mp, structure, border_value=0)
+        dp = ndi.distance_transform_edt(~sr_, sampling=spacing)[sp_]
+        dr = ndi.distance_transform_edt(~sp_, sampling=spacing)[sr_]
+        return time.perf_counter() - t, dp, dr
+
+    offsets = np.concatenate([[0], np.cumsum(np.where(both, n_surface.sum(1), 0))])
+    picked = [int(k) for k in np.argsort(volumes)[[len(volumes) // 4, len(volumes) // 2, -1]] if both[k]]
+    lines.append(f'scipy route (binary_erosion + distance_transform_edt + indexing, both directions) on this machine\'s CPU, '
+                 f'labels {[labels[k] for k in picked]} (a small, the median and the largest box):')
+    for n_done, k in enumerate(picked):
+        z0, z1, y0, y1, x0, x1 = (int(v) for v in boxes[k])
+        mr, mp = ref == labels[k], pred == labels[k]
+        # a margin of one voxel keeps the faces of the crop off the mask where the volume goes on
+        crop = (slice(max(z0 - 1, 0), z1 + 1), slice(max(y0 - 1, 0), y1 + 1), slice(max(x0 - 1, 0), x1 + 1))
+        t_crop, dp, dr = scipy_route(mr[crop], mp[crop])
+        mine = np.sqrt(host[offsets[k]:offsets[k + 1]])
+        equal = np.array_equal(mine, np.concatenate([dp, dr]))
+        close = equal or bool(np.allclose(mine, np.concatenate([dp, dr]), rtol=1e-12, atol=0))
+        line = (f'  label {labels[k]}: box {z1 - z0} x {y1 - y0} x {x1 - x0}, {len(mine)} distances; cropped {t_crop:.2f} s; '
+                f'device values equal scipy\'s bit for bit: {equal} (within rtol 1e-12: {close})')
+        if n_done < a.uncropped_labels:
+            t_full, dp_f, dr_f = scipy_route(mr, mp)
+            line += f'; uncropped {t_full:.1f} s, same values: {np.array_equal(dp_f, dp) and np.array_equal(dr_f, dr)}'
+        lines.append(line)
+        print(line, flush=True)
+
+    # the folder command with and without the flag
+    rw = NiftiIO()
+    with tempfile.TemporaryDirectory() as tmp:
+        fr, fp = os.path.join(tmp, 'ref'), os.path.join(tmp, 'pred')
+        os.makedirs(fr), os.makedirs(fp)
+        affine = np.diag([spacing[2], spacing[1], spacing[0], 1.0])
+        for c in range(a.cases):
+            r = ref if c == 0 else organ_map(a.n, seed=62 + c)
+            rw.write_seg(r, os.path.join(fr, f'case{c}.nii.gz'), {'nibabel_stuff': {'original_affine': affine}})
+            rw.write_seg(perturbed_boundaries(r, 7 + c), os.path.join(fp, f'case{c}.nii.gz'), {'nibabel_stuff': {'original_affine': affine}})
+        for flag in (False, True):
+            ev.compute_metrics_on_folder(fr, fp, None, rw, '.nii.gz', labels, surface_metrics=flag)        # warm-up
+            t0 = time.perf_counter()
+            summary = ev.compute_metrics_on_folder(fr, fp, None, rw, '.nii.gz', labels, surface_metrics=flag)
+            t = time.perf_counter() - t0
+            lines.append(f'compute_metrics_on_folder, {a.cases} cases of {a.n}^3 (files written by zlib, inflated on the host), '
+                         f'surface_metrics={flag}: {t / a.cases * 1e3:.0f} ms per case; keys per label {len(summary["mean"][1])}')
+    lines.append(f'label 1 of case 0: HD {got[1]["HD"]:.4f} HD95 {got[1]["HD95"]:.4f} ASSD {got[1]["ASSD"]:.4f} NSD {got[1]["NSD"]:.4f}')
+    text = '\n'.join(lines)
+    print(text)
+    out = a.out or os.path.join(ROOT, 'profiles', 'r26_surface_metrics.txt')
+    with open(out, 'w') as fh:
+        fh.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--section', choices=('counts', 'surface'), default='counts')
+    ap.add_argument('--uncropped-labels', type=int, default=3, help='surface: of the three scipy labels, how many also run uncropped')
     ap.add_argument('--n', type=int, default=512)
     ap.add_argument('--cases', type=int, default=3)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--cpu-n', type=int, default=192)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.section == 'surface':
+        return surface_section(a)
     from fast_nnunet_amd import capi
     from fast_nnunet_amd import evaluation as ev
     from fast_nnunet_amd import postprocessing as pp
