@@ -886,7 +886,7 @@ const float *conv3d_identity_ss() {
     if (!tab[dev]) {
         float h[1024];
         for (int i = 0; i < 512; ++i) { h[i] = 1.f; h[512 + i] = 0.f; }
-        float *d = nullptr;
+        float *d = nullptr;                                       // made once per process and device, never freed: no owner (owned.h)
         if (hipMalloc((void **)&d, sizeof(h)) != hipSuccess) return nullptr;
         if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
         tab[dev] = d;
@@ -902,7 +902,7 @@ const unsigned short *conv3d_identity_ssh() {
     if (!tab[dev]) {
         unsigned short h[1024];
         for (int i = 0; i < 1024; ++i) h[i] = (i & 8) ? 0 : 0x3c00;
-        unsigned short *d = nullptr;
+        unsigned short *d = nullptr;                              // (never freed either)
         if (hipMalloc((void **)&d, sizeof(h)) != hipSuccess) return nullptr;
         if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
         tab[dev] = d;

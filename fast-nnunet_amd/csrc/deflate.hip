@@ -18,6 +18,7 @@
 // count kernel 17.5 KiB, the emit kernel 34.3 KiB.  Nothing is written outside out[0, out_bytes); no kernel keeps scratch.
 #include "fnn_device.h"
 #include "deflate_wave.h"
+#include "owned.h"
 #include "../../include/fnn.h"
 #include <climits>
 #include <cstdint>
@@ -192,14 +193,14 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
     const size_t o_max = 0, o_x2k = 16, o_off = o_x2k + sizeof(g_tables.x2k), o_bytes = o_off + df_align16((size_t)(max_chunks + 1) * 8),
                  o_crc = o_bytes + df_align16((size_t)max_chunks * 4), o_bits = o_crc + df_align16((size_t)max_chunks * 4),
                  total = o_bits + (size_t)max_chunks * DF_LANES * 2;
-    char *scratch = nullptr;
-    if (hipMalloc((void **)&scratch, total) != hipSuccess) { (void)hipGetLastError(); return fnn_fail(FNN_E_HIP, "hipMalloc failed (deflate scratch)"); }
-    unsigned *d_max = (unsigned *)(scratch + o_max);
-    uint32_t *d_x2k = (uint32_t *)(scratch + o_x2k);
-    long long *d_off = (long long *)(scratch + o_off);
-    unsigned *d_bytes = (unsigned *)(scratch + o_bytes);
-    uint32_t *d_crc = (uint32_t *)(scratch + o_crc);
-    uint16_t *d_bits = (uint16_t *)(scratch + o_bits);
+    DevBuf scratch;
+    if (!scratch.alloc(total)) return fnn_fail(FNN_E_HIP, "hipMalloc failed (deflate scratch)");
+    unsigned *d_max = scratch.as<unsigned>(o_max);
+    uint32_t *d_x2k = scratch.as<uint32_t>(o_x2k);
+    long long *d_off = scratch.as<long long>(o_off);
+    unsigned *d_bytes = scratch.as<unsigned>(o_bytes);
+    uint32_t *d_crc = scratch.as<uint32_t>(o_crc);
+    uint16_t *d_bits = scratch.as<uint16_t>(o_bits);
     hipStream_t st = (hipStream_t)stream;
     hipError_t r = hipMemcpyAsync(d_x2k, g_tables.x2k, sizeof(g_tables.x2k), hipMemcpyHostToDevice, st);
     int elem = in_elem_bytes;
@@ -236,7 +237,6 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
     if (r == hipSuccess) r = hipMemcpyAsync(&h_total, d_off + chunks, 8, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipMemcpyAsync(h_crc.data(), d_crc, (size_t)chunks * 4, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipStreamSynchronize(st);
-    (void)hipFree(scratch);
     if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     uint32_t crc = 0;
     const uint32_t x_chunk = df_xpow8(DF_CHUNK, g_tables.x2k);

@@ -7,6 +7,7 @@
 // predict_from_raw_data.py:560-680 (x-major patch order, Gaussian weighting,
 // accumulate, normalise, un-pad; mirroring; fold ensembling).
 #include "fnn_device.h"
+#include "host_upload.h"
 #include "../../include/fnn.h"
 
 #include <cmath>
@@ -17,8 +18,8 @@
 #include <string>
 #include <algorithm>
 #include <climits>
+#include <memory>
 #include <vector>
-#include <thread>
 #include <variant>
 
 namespace {
@@ -62,17 +63,14 @@ struct Layer {
 };
 
 struct FoldWeights {
-    f16 *wpk = nullptr;
-    float *fparam = nullptr;
+    DevBuf wpk, fparam;                // f16 fragments; floats
     bool loaded = false;
 };
 
 // What one batch in flight writes: every layer's activations, the InstanceNorm statistics, and the (scale, shift) rows -
 // fp32 [layer][max_batch][2][C], followed by the same rows in fp16 (ssh_rows)
 struct Arena {
-    f16 *act = nullptr;
-    double *stats = nullptr;
-    float *ss = nullptr;
+    DevBuf act, stats, ss;             // f16; double; float
 };
 
 inline int pad16(int c) { return (c + 15) / 16 * 16; }
@@ -110,59 +108,34 @@ struct fnn_engine {
     // the other streams they overlap.  The heads stay ordered (events), so the accumulation order - and with it every
     // rounding - is the reference's.  288 GB of HBM make the extra arenas free.
     static constexpr int MAXP = 8;
-    Arena arena[MAXP];                      // [0]: fnn_create's, the one a single stream uses; [k > 0]: add_pipes
+    struct Pipe { Arena arena; Stream st; Event head, done; };
+    Pipe pipe[MAXP];                        // arena [0]: fnn_create's, the one a single stream uses; [k > 0]: add_pipes
     int n_pipe = 0;                         // streams allocated (0 until the first multi-batch run); arenas 1 .. n_pipe - 1 with them
-    hipStream_t pipe[MAXP] = {};
-    hipEvent_t ev_start = nullptr, ev_head[MAXP] = {}, ev_done[MAXP] = {};
-    f16 *gauss = nullptr;
-    f16 *ones = nullptr;                    // weight map of use_gaussian = 0 (the kernels load the map unconditionally)
-    int *inf_flag = nullptr;
+    Event ev_start;
+    // Every buffer below is made where it is first needed and only ever grows (DevBuf::reserve)
+    DevBuf gauss;                           // f16
+    DevBuf ones;                            // f16: weight map of use_gaussian = 0 (the kernels load the map unconditionally)
+    DevBuf inf_flag;                        // int
     // label rule of the label-map entry points (fnn_set_label_rule)
     int label_mode = FNN_LABELS_ARGMAX, label_u16 = 0;
-    int *label_order = nullptr;             // device: regions_class_order[num_heads]
-    int *origins = nullptr; size_t origins_cap = 0;
-    int *origins_host = nullptr; size_t origins_host_cap = 0; hipEvent_t origins_ev = nullptr;   // pinned staging, as for steps_dev below
-    void *acc = nullptr; size_t acc_bytes = 0;
-    float *vol_tmp = nullptr; size_t vol_tmp_bytes = 0;
-    // A volume that arrives in HOST memory (the reference's callers hand over the CPU tensor of the preprocessing iterator,
-    // predict_from_raw_data.py:579 `data = data.to(results_device)`): it is uploaded in tiles (planes x rows) on a copy stream of
-    // the engine's, and a batch of patches starts as soon as the tiles under its patches have landed - the patch order is
-    // x-major, y next (:532-537), so the tiles are needed roughly in the order they travel.  Pinned source: DMA straight from it; pageable
-    // source: through a ring of pinned staging buffers filled by a few host threads.
-    struct Upload {
-        bool active = false, pinned_src = false;
-        const float *host = nullptr; float *dev = nullptr;
-        int C = 0; int64_t X = 0, Y = 0, Z = 0;
-        // the volume travels in tiles of slab_x planes x slab_y rows x the whole z extent (x-major patch order: the first batch's
-        // patches cover the first x layer and a part of y - it starts when THOSE tiles have landed, not the whole layer)
-        int64_t slab_x = 1, slab_y = 1, nxs = 0, nyb = 0;
-        std::vector<char> issued;              // [nxs][nyb]
-        size_t n_issued = 0;
-        std::vector<hipEvent_t> landed;        // event pool (kept between calls): one per upload_box call that issued something
-        size_t ev_next = 0;
-        hipEvent_t last = nullptr;             // the youngest recorded event: everything issued so far lies in front of it
-        hipStream_t st = nullptr;
-        static constexpr int RING = 3;
-        float *stage[RING] = {}; size_t stage_bytes = 0; hipEvent_t stage_free[RING] = {}; bool stage_used[RING] = {};
-        int next_stage = 0;
-        hipEvent_t go = nullptr;
-    } up;
-    float *vol_pad = nullptr; size_t vol_pad_bytes = 0;
-    void *out_tmp = nullptr; size_t out_tmp_bytes = 0;
-    float *patch_buf = nullptr; size_t patch_buf_bytes = 0;
+    DevBuf label_order;                     // int: regions_class_order[num_heads]
+    IntTable origins;                       // the patches' origins, [n][3]
+    DevBuf acc;
+    DevBuf vol_tmp;                         // float: a host caller's volume / patches
+    HostUpload up;                          // a volume that arrives in host memory, on its way into vol_tmp (host_upload.h)
+    DevBuf vol_pad;                         // float
+    DevBuf out_tmp;
+    DevBuf patch_buf;                       // float
     // gather path (gather.hip): the last conv's raw output and InstanceNorm of every patch of the volume
-    void *feat = nullptr; size_t feat_bytes = 0;
-    void *featss = nullptr; size_t featss_bytes = 0;
-    void *featssh = nullptr; size_t featssh_bytes = 0;   // the same rows in fp16, staging layout (GatherParams::fssh)
-    int *steps_dev = nullptr; size_t steps_cap = 0;
-    int *steps_host = nullptr; size_t steps_host_cap = 0;   // pinned staging of the tile-start / slot tables (no stream sync for a host temporary)
-    hipEvent_t steps_ev = nullptr;                          // the previous upload from steps_host has been read
+    DevBuf feat, featss;
+    DevBuf featssh;                         // the same rows in fp16, staging layout (GatherParams::fssh)
+    IntTable steps;                         // the tile-start / slot tables
     std::vector<std::string> klog;          // kernel variants of the last profiled call, one entry per launch (fnn_kernel_log)
     bool gather_enabled = true;             // FNN_NO_GATHER (read when the engine is created): always accumulate in HBM
     double head_flops = 0, patch_flops = 0, patch_act_bytes = 0;
     // profiling
     bool profiling = false;
-    struct Ev { hipEvent_t a, b; int family; double flops, bytes; int layer; size_t klog_lo, klog_hi; };
+    struct Ev { Event a, b; int family; double flops, bytes; int layer; size_t klog_lo, klog_hi; };
     std::vector<Ev> evs; size_t ev_used = 0;
     int cur_layer = -1;                     // layer index of the launches being issued (-1: head / gather / finalize)
     std::vector<std::string> launch_rows;   // fnn_profile_launches: one row per timed launch of the last profiled call
@@ -197,15 +170,6 @@ int fail(fnn_engine *e, int code, const char *fmt, ...) {
         if (_r != hipSuccess) return fail(e, FNN_E_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
     } while (0)
 
-template <class T> int ensure(fnn_engine *e, T **p, size_t *have, size_t need) {
-    if (*have >= need && *p) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *have = 0;
-    HIPCHK(e, hipMalloc((void **)p, need));
-    *have = need;
-    return 0;
-}
-
 // An arena's buffers in bytes - activations, statistics, scale / shift rows; returns their sum
 size_t arena_bytes(const fnn_engine *e, size_t b[3]) {
     b[0] = e->act_halves * e->max_batch * sizeof(f16);
@@ -214,39 +178,13 @@ size_t arena_bytes(const fnn_engine *e, size_t b[3]) {
     return b[0] + b[1] + b[2];
 }
 
-void arena_free(Arena &A) {
-    for (void *p : {(void *)A.act, (void *)A.stats, (void *)A.ss}) if (p) (void)hipFree(p);
-    A = Arena{};
-}
-
 int arena_alloc(fnn_engine *e, Arena &A) {
     size_t b[3];
     arena_bytes(e, b);
-    void **p[3] = {(void **)&A.act, (void **)&A.stats, (void **)&A.ss};
+    DevBuf *const buf[3] = {&A.act, &A.stats, &A.ss};
     static const char *const name[3] = {"activations", "stats", "scale/shift"};
     for (int i = 0; i < 3; ++i)
-        if (hipError_t r = hipMalloc(p[i], b[i])) { arena_free(A); return fail(e, FNN_E_HIP, "hipMalloc(%s) failed: %s", name[i], hipGetErrorString(r)); }
-    return 0;
-}
-
-// Small integer tables (patch origins, tile starts, a sharded caller's slot table) -> device without a stream
-// synchronisation: the host copy lives in a pinned buffer the engine owns; the only wait is for the PREVIOUS upload from
-// that buffer to have been read (an event that has long fired by the next call).
-int upload_ints(fnn_engine *e, const int *src, size_t n, int **dev, size_t *dev_cap, int **host, size_t *host_cap,
-                hipEvent_t *ev, hipStream_t st) {
-    const size_t bytes = n * sizeof(int) + 64;
-    if (int rc = ensure(e, dev, dev_cap, bytes)) return rc;
-    if (!*ev) HIPCHK(e, hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    else HIPCHK(e, hipEventSynchronize(*ev));
-    if (*host_cap < bytes) {
-        if (*host) (void)hipHostFree(*host);
-        *host = nullptr; *host_cap = 0;
-        HIPCHK(e, hipHostMalloc((void **)host, bytes, hipHostMallocDefault));
-        *host_cap = bytes;
-    }
-    memcpy(*host, src, n * sizeof(int));
-    HIPCHK(e, hipMemcpyAsync(*dev, *host, n * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipEventRecord(*ev, st));
+        if (hipError_t r = buf[i]->reserve(b[i])) { A = Arena{}; return fail(e, FNN_E_HIP, "hipMalloc(%s) failed: %s", name[i], hipGetErrorString(r)); }
     return 0;
 }
 
@@ -595,8 +533,8 @@ struct Scope {
         if (!e->profiling) return;
         if (e->ev_used == e->evs.size()) {
             fnn_engine::Ev ev{};
-            if (hipEventCreate(&ev.a) != hipSuccess || hipEventCreate(&ev.b) != hipSuccess) return;
-            e->evs.push_back(ev);
+            if (ev.a.create(hipEventDefault) != hipSuccess || ev.b.create(hipEventDefault) != hipSuccess) return;
+            e->evs.push_back(std::move(ev));
         }
         idx = (int)e->ev_used++;
         e->evs[idx].family = family; e->evs[idx].flops = flops; e->evs[idx].bytes = bytes;
@@ -641,7 +579,7 @@ void collect_profile(fnn_engine *e, int64_t n_patches) {
 // ---------------------------------------------------------------------------
 // the fp16 scale / shift rows (SrcDesc::ssh) live behind the fp32 rows of the same arena: [ss_count * max_batch * 2 + 4] floats,
 // then ss_count * max_batch * 2 halves
-unsigned short *ssh_rows(const fnn_engine *e, const Arena &A) { return (unsigned short *)(A.ss + e->ss_count * e->max_batch * 2 + 4); }
+unsigned short *ssh_rows(const fnn_engine *e, const Arena &A) { return (unsigned short *)(A.ss.as<float>() + e->ss_count * e->max_batch * 2 + 4); }
 
 // A layer's output layout as SrcDesc::vs / cs: chunk-major (16, 16 x voxels), or channels-last - (0, 0), which the launch
 // parameters' out_vs / out_cs read as (C, 16)
@@ -653,12 +591,12 @@ Layout layout(const Layer &L) {
 SrcDesc make_src(const fnn_engine *e, const Arena &A, int layer) {
     const Layer &L = e->layers[layer];
     SrcDesc s{};
-    s.ptr = A.act + L.out_off * e->max_batch;
+    s.ptr = A.act.as<f16>() + L.out_off * e->max_batch;
     s.C = L.cout_pad;
     const Layout lay = layout(L);
     s.vs = lay.vs ? lay.vs : L.cout_pad; s.cs = lay.vs ? lay.cs : 16;   // (spelled out: a one-source conv's src[1] is a copy with C = 0)
     if (L.has_norm) {
-        s.ss = A.ss + L.ss_off * e->max_batch * 2;
+        s.ss = A.ss.as<float>() + L.ss_off * e->max_batch * 2;
         s.ssh = ssh_rows(e, A) + L.ss_off * e->max_batch * 2;        // halves: [N][C / 8][16] = 2 C per item
         s.slope = L.act ? e->arch.slope : 1.f;
     } else {
@@ -672,16 +610,18 @@ SrcDesc make_src(const fnn_engine *e, const Arena &A, int layer) {
 int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, long long vol_batch_stride, const long long vdim[3],
                   const int *origins_dev, int nb, const int flip[3], hipStream_t st, f16 *head_out = nullptr,
                   float *head_ss = nullptr, unsigned short *head_ssh = nullptr) {
-    const FoldWeights &fw = e->folds[fold];
-    HIPCHK(e, hipMemsetAsync(A.stats, 0, e->stats_doubles * e->max_batch * sizeof(double), st));
+    f16 *const wpk = e->folds[fold].wpk.as<f16>(), *const act = A.act.as<f16>();
+    float *const fparam = e->folds[fold].fparam.as<float>(), *const ss = A.ss.as<float>();
+    double *const stats = A.stats.as<double>();
+    HIPCHK(e, hipMemsetAsync(stats, 0, e->stats_doubles * e->max_batch * sizeof(double), st));
     struct LayerMark { fnn_engine *e; ~LayerMark() { e->cur_layer = -1; } } mark{e};
     for (size_t li = 0; li < e->layers.size(); ++li) {
         const Layer &L = e->layers[li];
         e->cur_layer = (int)li;
-        f16 *out = A.act + L.out_off * e->max_batch;
+        f16 *out = act + L.out_off * e->max_batch;
         if (head_out && (int)li == e->head_src) out = head_out;
         const Layout lay = layout(L);
-        double *stats_out = L.has_norm ? A.stats + L.stats_off * e->max_batch : nullptr;
+        double *stats_out = L.has_norm ? stats + L.stats_off * e->max_batch : nullptr;
         int rc = 0;
         if (L.type == Layer::STEM) {
             StemParams p{};
@@ -692,11 +632,11 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
             p.PD = L.out_dims[0]; p.PH = L.out_dims[1]; p.PW = L.out_dims[2];
             p.kd = L.k[0]; p.kh = L.k[1]; p.kw = L.k[2];
             p.Cout = L.cout_pad;
-            p.w = fw.fparam + L.w_off; p.bias = fw.fparam + L.bias_off;
+            p.w = fparam + L.w_off; p.bias = fparam + L.bias_off;
             p.out = out; p.stats_out = stats_out;
             Scope sc(e, st, FAM_STEM, L.flops * nb, L.bytes * nb);
             if (L.virtual_out) p.out = nullptr;                       // statistics only: the consumer recomputes the values
-            rc = launch_stem_mfma(p, fw.wpk + L.w_off2, nb, st);
+            rc = launch_stem_mfma(p, wpk + L.w_off2, nb, st);
         } else if (L.type == Layer::CONV) {
             const Layer *P = L.fuse ? &e->layers[L.src_layer[0]] : nullptr;        // the producer a fused layer recomputes
             ThinParams tp = conv_shape(e, L, L.fuse, L.fuse == FUSE_TCONV ? P : nullptr);
@@ -705,20 +645,20 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
             for (int i = 0; i < L.n_src; ++i) p.src[i] = make_src(e, A, L.src_layer[i]);
             if (L.n_src == 1) { p.src[1] = p.src[0]; p.src[1].C = 0; }
             p.pd = (L.k[0] - 1) / 2; p.ph = (L.k[1] - 1) / 2; p.pw = (L.k[2] - 1) / 2;
-            p.wpk = fw.wpk + L.w_off; p.bias = fw.fparam + L.bias_off;
+            p.wpk = wpk + L.w_off; p.bias = fparam + L.bias_off;
             p.out = out; p.stats_out = stats_out;
             p.out_vs = lay.vs; p.out_cs = lay.cs;
-            p.oscale = L.fp8 ? fw.fparam + L.oscale_off : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
+            p.oscale = L.fp8 ? fparam + L.oscale_off : nullptr; p.act_mult = FNN_FP8_ACT_MULT;
             Scope sc(e, st, FAM_CONV, L.flops * nb, L.bytes * nb);
             if (L.fuse) {
-                tp.fbias = fw.fparam + P->bias_off;
+                tp.fbias = fparam + P->bias_off;
                 if (L.fuse == FUSE_STEM) {
-                    tp.fw = fw.wpk + P->w_off2;
+                    tp.fw = wpk + P->w_off2;
                     tp.vol = vol; tp.vol_batch_stride = vol_batch_stride; tp.Y = vdim[1]; tp.Z = vdim[2];
                     tp.origins = origins_dev; tp.flip_d = flip[0]; tp.flip_h = flip[1]; tp.flip_w = flip[2];
-                    tp.fss = A.ss + P->ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
+                    tp.fss = ss + P->ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
                 } else {
-                    tp.fw = fw.wpk + P->w_off;
+                    tp.fw = wpk + P->w_off;
                     tp.low = make_src(e, A, P->src_layer[0]);
                 }
             }
@@ -751,7 +691,7 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
             if (L.pool_layer >= 0) {
                 const Layer &P = e->layers[L.pool_layer];
                 const Layout pool = layout(P);
-                p.pool_out = A.act + P.out_off * e->max_batch;
+                p.pool_out = act + P.out_off * e->max_batch;
                 p.D = L.out_dims[0]; p.H = L.out_dims[1]; p.W = L.out_dims[2];
                 p.psd = P.s[0]; p.psh = P.s[1]; p.psw = P.s[2];
                 p.pool_vs = pool.vs; p.pool_cs = pool.cs;
@@ -763,7 +703,7 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
             p.src = make_src(e, A, L.src_layer[0]);
             p.N = nb; p.Di = L.in_dims[0]; p.Hi = L.in_dims[1]; p.Wi = L.in_dims[2];
             p.sd = L.s[0]; p.sh = L.s[1]; p.sw = L.s[2];
-            p.Cout = L.cout_pad; p.wpk = fw.wpk + L.w_off; p.bias = fw.fparam + L.bias_off;
+            p.Cout = L.cout_pad; p.wpk = wpk + L.w_off; p.bias = fparam + L.bias_off;
             p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs; p.ksteps = L.ksteps; p.nblk = L.cout_pad / 16;
             if (L.virtual_out) continue;                              // computed inside its consumer (conv3d_thin.hip)
             Scope sc(e, st, FAM_TCONV, L.flops * nb);
@@ -772,8 +712,8 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
         if (rc != 0) return fail(e, rc == -1 ? FNN_E_UNSUPPORTED : FNN_E_HIP, "kernel launch failed at layer %zu (rc=%d)", li, rc);
         if (L.has_norm) {
             StatsFinalizeParams q{};
-            q.stats = stats_out; q.gamma = fw.fparam + L.gamma_off; q.beta = fw.fparam + L.beta_off;
-            q.ss = A.ss + L.ss_off * e->max_batch * 2; q.C = L.cout_pad; q.nrep = L.stats_slots;
+            q.stats = stats_out; q.gamma = fparam + L.gamma_off; q.beta = fparam + L.beta_off;
+            q.ss = ss + L.ss_off * e->max_batch * 2; q.C = L.cout_pad; q.nrep = L.stats_slots;
             q.ssh = ssh_rows(e, A) + L.ss_off * e->max_batch * 2;
             if (head_ss && (int)li == e->head_src) q.ss = head_ss;
             if (head_ssh && (int)li == e->head_src) q.ssh = head_ssh;
@@ -791,7 +731,7 @@ HeadParams make_head(const fnn_engine *e, const Arena &A, int fold, int b) {
     h.src = make_src(e, A, e->head_src);
     h.b = b; h.PD = a.patch[0]; h.PH = a.patch[1]; h.PW = a.patch[2];
     h.heads = a.num_heads; h.hblocks = e->hblocks; h.ksteps = e->head_ksteps;
-    h.wpk = fw.wpk + e->head_w_off; h.bias = fw.fparam + e->head_bias_off;
+    h.wpk = fw.wpk.as<f16>() + e->head_w_off; h.bias = fw.fparam.as<float>() + e->head_bias_off;
     h.fx = h.fy = h.fz = INT_MAX;                           // every voxel is read unless run_patches knows better
     return h;
 }
@@ -877,7 +817,7 @@ int check_ready(fnn_engine *e, int fold, const fnn_opts *o) {
     if (!o) return fail(e, FNN_E_INVALID, "opts is NULL");
     if (fold < 0 || fold >= (int)e->folds.size() || !e->folds[fold].loaded) return fail(e, FNN_E_STATE, "weights of fold %d are not loaded", fold);
     if (!(o->tile_step_size > 0 && o->tile_step_size <= 1)) return fail(e, FNN_E_INVALID, "step_size must be larger than 0 and smaller or equal to 1");
-    if (o->use_gaussian && !e->gauss) return fail(e, FNN_E_STATE, "use_gaussian is set but fnn_set_gaussian was not called");
+    if (o->use_gaussian && !e->gauss.p) return fail(e, FNN_E_STATE, "use_gaussian is set but fnn_set_gaussian was not called");
     if (o->n_mirror_axes < 0 || o->n_mirror_axes > 3) return fail(e, FNN_E_INVALID, "n_mirror_axes out of range");
     for (int i = 0; i < o->n_mirror_axes; ++i)
         if (o->mirror_axes[i] < 0 || o->mirror_axes[i] > 2) return fail(e, FNN_E_INVALID, "mirror_axes does not match the dimension of the input!");
@@ -920,12 +860,10 @@ int check_u8_labels(fnn_engine *e, int classes, const char *hint) {
 // Reads back the inf flag of the launches on `st` (synchronising it) and fails like the reference when one was set
 int check_inf(fnn_engine *e, hipStream_t st, const char *msg = "Encountered inf in predicted array.") {
     int flag = 0;
-    HIPCHK(e, hipMemcpyAsync(&flag, e->inf_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(&flag, e->inf_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
     return flag ? fail(e, FNN_E_INF, "%s", msg) : 0;
 }
-
-int upload_box(fnn_engine *e, int64_t x_lo, int64_t x_hi, int64_t y_lo, int64_t y_hi, hipStream_t st);     // (below, next to stage_volume)
 
 inline int acc_hp(const fnn_arch_desc &a) { return (a.num_heads + 1 + 7) / 8 * 8; }
 
@@ -943,7 +881,7 @@ using Target = std::variant<AccBox, FeatSlots>;
 // Where the patch at origin `oo` lands in an accumulator box, weighted how (HeadParams, PatchAccParams)
 template <class Params> void place_patch(Params &p, const fnn_engine *e, const fnn_opts &o, const AccBox &t, const int *oo) {
     const Box &box = t.box;
-    p.gauss = o.use_gaussian ? e->gauss : e->ones;
+    p.gauss = (o.use_gaussian ? e->gauss : e->ones).as<f16>();
     p.acc = t.acc; p.AX = box.hi[0] - box.lo[0]; p.Y = box.hi[1] - box.lo[1]; p.Z = box.hi[2] - box.lo[2];
     p.HP = acc_hp(e->arch); p.acc_fp32 = t.acc_fp32;
     p.ox = oo[0] - (int)box.lo[0]; p.oy = oo[1] - (int)box.lo[1]; p.oz = oo[2] - (int)box.lo[2];
@@ -963,12 +901,13 @@ int add_pipes(fnn_engine *e, int want, int *np) {
             if (NP > cap) NP = (int)std::max<long long>(cap, e->n_pipe);
         }
     }
-    if (!e->ev_start) HIPCHK(e, hipEventCreateWithFlags(&e->ev_start, hipEventDisableTiming));
+    HIPCHK(e, e->ev_start.create());
     for (int k = e->n_pipe; k < NP; ++k) {
-        if (k > 0 && !e->arena[k].act) if (int rc = arena_alloc(e, e->arena[k])) return rc;
-        HIPCHK(e, hipStreamCreateWithFlags(&e->pipe[k], hipStreamNonBlocking));
-        HIPCHK(e, hipEventCreateWithFlags(&e->ev_head[k], hipEventDisableTiming));
-        HIPCHK(e, hipEventCreateWithFlags(&e->ev_done[k], hipEventDisableTiming));
+        fnn_engine::Pipe &p = e->pipe[k];
+        if (k > 0 && !p.arena.act.p) if (int rc = arena_alloc(e, p.arena)) return rc;
+        HIPCHK(e, p.st.create());
+        HIPCHK(e, p.head.create());
+        HIPCHK(e, p.done.create());
         e->n_pipe = k + 1;
     }
     *np = NP;
@@ -978,7 +917,7 @@ int add_pipes(fnn_engine *e, int want, int *np) {
 // Runs the listed patches (their origins already on the device) in balanced batches and hands every evaluation
 // (mirroring) to the target.  Several batches in flight (see fnn_engine::pipe): batch i runs on arena and stream
 // i % NP, its heads wait for the previous batch's; otherwise arena 0 on the caller's stream.  A volume still arriving
-// from the host is waited for tile by tile under each batch (upload_box).
+// from the host is waited for tile by tile under each batch (HostUpload::need).
 int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const fnn_opts &o,
                 const std::vector<int64_t> &ids, const int *ids_origins_dev, const Target &t, hipStream_t st) {
     const fnn_arch_desc &a = e->arch;
@@ -991,7 +930,7 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
     const bool tta = !combos.empty();
     const size_t P = (size_t)a.patch[0] * a.patch[1] * a.patch[2];
     if (tta && ab)
-        if (int rc = ensure(e, &e->patch_buf, &e->patch_buf_bytes, (size_t)B * a.num_heads * P * sizeof(float))) return rc;
+        HIPCHK(e, e->patch_buf.reserve((size_t)B * a.num_heads * P * sizeof(float)));
     const int64_t np = (int64_t)ids.size();
     if (np > B) {                                           // balanced batches: 75 patches run as 19+19+19+18, not 24+24+24+3
         const int64_t nbat = (np + B - 1) / B;
@@ -1011,7 +950,7 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
     if (pipelined) {
         if (int rc = add_pipes(e, want_pipes, &NP)) return rc;
         HIPCHK(e, hipEventRecord(e->ev_start, st));
-        for (int k = 0; k < NP; ++k) HIPCHK(e, hipStreamWaitEvent(e->pipe[k], e->ev_start, 0));
+        for (int k = 0; k < NP; ++k) HIPCHK(e, hipStreamWaitEvent(e->pipe[k].st, e->ev_start, 0));
     }
     const bool fresh = ab && ab->fresh;
     std::vector<int> uniq[3];                             // distinct patch positions per axis (fresh: overlap with the previous one)
@@ -1034,8 +973,8 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
         const int nb = (int)((np - p0 < B) ? np - p0 : B);
         const int *org = ids_origins_dev + p0 * 3;
         const int k = (int)(bi % NP);
-        const Arena &A = e->arena[k];
-        hipStream_t bst = pipelined ? e->pipe[k] : st;
+        const Arena &A = e->pipe[k].arena;
+        hipStream_t bst = pipelined ? (hipStream_t)e->pipe[k].st : st;
         if (e->up.active) {                                   // a volume still arriving from the host: the box this batch's patches read
             int64_t lo[2] = {INT64_MAX, INT64_MAX}, hi[2] = {0, 0};   // (un-padded volume: padded == shape along every axis here)
             for (int b = 0; b < nb; ++b)
@@ -1043,7 +982,7 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
                     const int64_t o0 = vp.origins[ids[p0 + b] * 3 + d];
                     lo[d] = std::min(lo[d], o0); hi[d] = std::max(hi[d], o0 + a.patch[d]);
                 }
-            if (int rc = upload_box(e, lo[0], hi[0], lo[1], hi[1], bst)) return rc;
+            HIPCHK(e, e->up.need(lo[0], hi[0], lo[1], hi[1], bst));
         }
         for (size_t ci = 0; ci <= (tta ? combos.size() : 0); ++ci) {
             int flip[3] = {0, 0, 0};
@@ -1055,24 +994,24 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
                 continue;
             }
             if (int rc = forward_batch(e, fold, A, vol_dev, 0, vdim, org, nb, flip, bst)) return rc;
-            if (pipelined && bi > 0) HIPCHK(e, hipStreamWaitEvent(bst, e->ev_head[(bi - 1) % NP], 0));   // heads in patch order
+            if (pipelined && bi > 0) HIPCHK(e, hipStreamWaitEvent(bst, e->pipe[(bi - 1) % NP].head, 0));   // heads in patch order
             for (int b = 0; b < nb; ++b) {
                 HeadParams h = make_head(e, A, fold, b);
                 const int *oo = &vp.origins[ids[p0 + b] * 3];
                 place_patch(h, e, o, *ab, oo);
                 h.flip_d = flip[0]; h.flip_h = flip[1]; h.flip_w = flip[2];
                 h.fx = first_visit(oo, 0); h.fy = first_visit(oo, 1); h.fz = first_visit(oo, 2);
-                if (tta) { h.mode = ci == 0 ? 1 : 2; h.patch_buf = e->patch_buf + (size_t)b * a.num_heads * P; }
+                if (tta) { h.mode = ci == 0 ? 1 : 2; h.patch_buf = e->patch_buf.as<float>() + (size_t)b * a.num_heads * P; }
                 Scope sc(e, bst, FAM_HEAD, e->head_flops);
                 if (launch_head(h, bst) != 0) return fail(e, FNN_E_HIP, "seg head launch failed");
             }
-            if (pipelined) HIPCHK(e, hipEventRecord(e->ev_head[k], bst));
+            if (pipelined) HIPCHK(e, hipEventRecord(e->pipe[k].head, bst));
         }
         if (tta && ab) {
             for (int b = 0; b < nb; ++b) {
                 PatchAccParams q{};
                 place_patch(q, e, o, *ab, &vp.origins[ids[p0 + b] * 3]);
-                q.patch_buf = e->patch_buf + (size_t)b * a.num_heads * P;
+                q.patch_buf = e->patch_buf.as<float>() + (size_t)b * a.num_heads * P;
                 q.n_div = (int)combos.size() + 1;
                 q.PD = a.patch[0]; q.PH = a.patch[1]; q.PW = a.patch[2]; q.heads = a.num_heads;
                 Scope sc(e, bst, FAM_HEAD, 0);
@@ -1082,164 +1021,44 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
     }
     if (pipelined) {
         for (int k = 0; k < NP; ++k) {
-            HIPCHK(e, hipEventRecord(e->ev_done[k], e->pipe[k]));
-            HIPCHK(e, hipStreamWaitEvent(st, e->ev_done[k], 0));
+            HIPCHK(e, hipEventRecord(e->pipe[k].done, e->pipe[k].st));
+            HIPCHK(e, hipStreamWaitEvent(st, e->pipe[k].done, 0));
         }
     }
-    return 0;
-}
-
-bool is_pinned_host_ptr(const void *p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
-// Host -> pinned staging: `rows` rows of `w` floats, `pitch` floats apart in the source, packed.  One core's memcpy (~10 GB/s)
-// is slower than the link: up to 4 threads share a contiguous run (pitch == w) in parts of >= 2^20 floats, else whole rows
-// in parts of ~2^18 floats or more.  A thread that cannot be started leaves its part and the rest to the calling thread.
-void stage_copy(float *dst, const float *src, size_t w, size_t pitch, size_t rows) {
-    const bool run = pitch == w;
-    const size_t n = run ? w * rows : rows;                   // what is shared out: floats, or rows
-    const int parts = (int)std::max<size_t>(1, std::min<size_t>(4, run ? (n + (1u << 20) - 1) >> 20 : w * rows >> 18));
-    auto part = [=](size_t lo, size_t hi) {
-        if (run) memcpy(dst + lo, src + lo, (hi - lo) * sizeof(float));
-        else for (size_t r = lo; r < hi; ++r) memcpy(dst + r * w, src + r * pitch, w * sizeof(float));
-    };
-    std::thread th[3];
-    const size_t per = (n + parts - 1) / parts;
-    bool spawn = true;
-    for (int t = 1; t < parts; ++t) {
-        const size_t lo = std::min(n, per * t), hi = std::min(n, per * (t + 1));
-        if (spawn) {
-            try { th[t - 1] = std::thread(part, lo, hi); continue; } catch (...) { spawn = false; }
-        }
-        part(lo, hi);
-    }
-    part(0, std::min(n, per));
-    for (std::thread &x : th) if (x.joinable()) x.join();
-}
-
-// Issues the upload of every tile of [x_lo, x_hi) x [y_lo, y_hi) (planes x rows, whole z extent) that has not left yet, then makes `st` wait
-// for everything issued so far (one copy stream: in order).
-int upload_box(fnn_engine *e, int64_t x_lo, int64_t x_hi, int64_t y_lo, int64_t y_hi, hipStream_t st) {
-    fnn_engine::Upload &u = e->up;
-    if (!u.active) return 0;
-    x_lo = std::max<int64_t>(0, x_lo); y_lo = std::max<int64_t>(0, y_lo);
-    x_hi = std::min(u.X, x_hi); y_hi = std::min(u.Y, y_hi);
-    if (x_hi <= x_lo || y_hi <= y_lo) { x_lo = 0; x_hi = std::min<int64_t>(u.X, 1); y_lo = 0; y_hi = std::min<int64_t>(u.Y, 1); }
-    const size_t row = (size_t)u.Z, pitch = (size_t)u.Y * u.Z * sizeof(float);
-    bool any = false;
-    for (int64_t xs = x_lo / u.slab_x; xs <= (x_hi - 1) / u.slab_x && u.n_issued < u.issued.size(); ++xs)
-        for (int64_t yb = y_lo / u.slab_y; yb <= (y_hi - 1) / u.slab_y; ++yb) {
-            char &done = u.issued[(size_t)(xs * u.nyb + yb)];
-            if (done) continue;
-            done = 1; ++u.n_issued; any = true;
-            const int64_t x0 = xs * u.slab_x, x1 = std::min(u.X, x0 + u.slab_x), y0 = yb * u.slab_y, y1 = std::min(u.Y, y0 + u.slab_y);
-            const size_t width = (size_t)(y1 - y0) * row * sizeof(float), height = (size_t)(x1 - x0);
-            const bool whole_rows = y0 == 0 && y1 == u.Y;     // the tile is one contiguous run
-            if (u.pinned_src) {
-                for (int c = 0; c < u.C; ++c) {
-                    const size_t off = (((size_t)c * u.X + x0) * u.Y + y0) * row;
-                    if (whole_rows) HIPCHK(e, hipMemcpyAsync(u.dev + off, u.host + off, width * height, hipMemcpyHostToDevice, u.st));
-                    else HIPCHK(e, hipMemcpy2DAsync(u.dev + off, pitch, u.host + off, pitch, width, height, hipMemcpyHostToDevice, u.st));
-                }
-            } else {
-                const int k = u.next_stage;
-                u.next_stage = (k + 1) % fnn_engine::Upload::RING;
-                if (u.stage_used[k]) HIPCHK(e, hipEventSynchronize(u.stage_free[k]));          // its previous tile has left
-                const size_t tile = width / sizeof(float) * height;                            // floats per channel, packed
-                for (int c = 0; c < u.C; ++c)
-                    stage_copy(u.stage[k] + (size_t)c * tile, u.host + (((size_t)c * u.X + x0) * u.Y + y0) * row, width / sizeof(float),
-                               pitch / sizeof(float), height);
-                for (int c = 0; c < u.C; ++c) {
-                    const size_t off = (((size_t)c * u.X + x0) * u.Y + y0) * row;
-                    HIPCHK(e, hipMemcpy2DAsync(u.dev + off, pitch, u.stage[k] + (size_t)c * tile, width, width, height, hipMemcpyHostToDevice, u.st));
-                }
-                HIPCHK(e, hipEventRecord(u.stage_free[k], u.st));
-                u.stage_used[k] = true;
-            }
-        }
-    if (any) {
-        if (u.ev_next == u.landed.size()) {
-            hipEvent_t ev;
-            HIPCHK(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            u.landed.push_back(ev);
-        }
-        u.last = u.landed[u.ev_next++];
-        HIPCHK(e, hipEventRecord(u.last, u.st));
-    }
-    if (u.last) HIPCHK(e, hipStreamWaitEvent(st, u.last, 0));
     return 0;
 }
 
 // Brings the input volume onto the device and pads it when smaller than the patch.  `slabbed`: the caller's batches call
-// upload_box() for the box their patches read (run_patches); otherwise the whole volume is waited for here.
+// e->up.need() for the box their patches read (run_patches); otherwise the whole volume is waited for here.
 int stage_volume(fnn_engine *e, const float *vol, const int64_t shape[4], const VolPlan &vp, hipStream_t st,
                  const float **vol_dev, bool slabbed = false) {
     const size_t nin = (size_t)shape[0] * shape[1] * shape[2] * shape[3];
     const float *src = vol;
     const bool need_pad = vp.padded[0] != shape[1] || vp.padded[1] != shape[2] || vp.padded[2] != shape[3];
-    fnn_engine::Upload &u = e->up;
-    u.active = false; u.n_issued = 0;
     if (!fnn_dev_ptr(vol)) {
-        if (int rc = ensure(e, &e->vol_tmp, &e->vol_tmp_bytes, nin * sizeof(float))) return rc;
-        src = e->vol_tmp;
-        u.host = vol; u.dev = e->vol_tmp; u.C = (int)shape[0]; u.X = shape[1]; u.Y = shape[2]; u.Z = shape[3];
-        u.pinned_src = is_pinned_host_ptr(vol);
-        // tiles of ~4 MiB per channel: an eighth of the rows (at least 16) x as many planes as fill the tile
-        const size_t slab_bytes = fnn_knob("FNN_UPLOAD_SLAB_BYTES") ? (size_t)atoll(fnn_knob("FNN_UPLOAD_SLAB_BYTES")) : (4u << 20);   // tests: many tiles in a small volume
-        u.slab_y = fnn_knob("FNN_UPLOAD_WHOLE_ROWS") ? u.Y : std::min<int64_t>(u.Y, std::max<int64_t>(16, (u.Y + 7) / 8));          // (knob: x slabs only - the first form)
-        const size_t rows_bytes = (size_t)u.slab_y * u.Z * sizeof(float);
-        u.slab_x = std::max<int64_t>(1, (int64_t)(slab_bytes / std::max<size_t>(1, rows_bytes)));
-        u.nxs = (u.X + u.slab_x - 1) / u.slab_x; u.nyb = (u.Y + u.slab_y - 1) / u.slab_y;
-        u.issued.assign((size_t)(u.nxs * u.nyb), 0);
-        u.ev_next = 0; u.last = nullptr;
-        if (!u.st) HIPCHK(e, hipStreamCreateWithFlags(&u.st, hipStreamNonBlocking));
-        if (!u.go) HIPCHK(e, hipEventCreateWithFlags(&u.go, hipEventDisableTiming));
-        if (!u.pinned_src) {
-            const size_t need = (size_t)u.C * u.slab_x * rows_bytes;
-            if (u.stage_bytes < need) {
-                for (int k = 0; k < fnn_engine::Upload::RING; ++k) {
-                    if (u.stage[k]) { if (u.stage_used[k]) (void)hipEventSynchronize(u.stage_free[k]); (void)hipHostFree(u.stage[k]); u.stage[k] = nullptr; }
-                    u.stage_used[k] = false;
-                }
-                u.stage_bytes = 0;
-                for (int k = 0; k < fnn_engine::Upload::RING; ++k) {
-                    HIPCHK(e, hipHostMalloc((void **)&u.stage[k], need, hipHostMallocDefault));
-                    if (!u.stage_free[k]) HIPCHK(e, hipEventCreateWithFlags(&u.stage_free[k], hipEventDisableTiming));
-                }
-                u.stage_bytes = need;
-            }
-        }
-        // the copy stream starts behind whatever the caller's stream still does with the staging area
-        HIPCHK(e, hipEventRecord(u.go, st));
-        HIPCHK(e, hipStreamWaitEvent(u.st, u.go, 0));
-        u.active = true;
-        if (!slabbed || need_pad) { if (int rc = upload_box(e, 0, u.X, 0, u.Y, st)) return rc; u.active = false; }
+        HIPCHK(e, e->vol_tmp.reserve(nin * sizeof(float)));
+        src = e->vol_tmp.as<float>();
+        HIPCHK(e, e->up.begin(vol, e->vol_tmp.as<float>(), (int)shape[0], shape[1], shape[2], shape[3], st));
+        if (!slabbed || need_pad) { HIPCHK(e, e->up.need(0, shape[1], 0, shape[2], st)); e->up.active = false; }
     }
     if (need_pad) {
         const size_t npad = (size_t)shape[0] * vp.padded[0] * vp.padded[1] * vp.padded[2];
-        if (int rc = ensure(e, &e->vol_pad, &e->vol_pad_bytes, npad * sizeof(float))) return rc;
+        HIPCHK(e, e->vol_pad.reserve(npad * sizeof(float)));
         const long long s[3] = {(long long)shape[1], (long long)shape[2], (long long)shape[3]};
         const long long d[3] = {(long long)vp.padded[0], (long long)vp.padded[1], (long long)vp.padded[2]};
         const long long lo[3] = {(long long)vp.lo[0], (long long)vp.lo[1], (long long)vp.lo[2]};
-        if (launch_pad_volume(src, e->vol_pad, (int)shape[0], s, d, lo, st) != 0) return fail(e, FNN_E_HIP, "pad launch failed");
-        src = e->vol_pad;
+        if (launch_pad_volume(src, e->vol_pad.as<float>(), (int)shape[0], s, d, lo, st) != 0) return fail(e, FNN_E_HIP, "pad launch failed");
+        src = e->vol_pad.as<float>();
     }
     *vol_dev = src;
     return 0;
 }
 
-// Ends a call's host-volume upload (stage_volume).  An error return after tiles have left the caller's pinned memory first
-// drains the copy stream, as the caller may free that memory once the call has failed; on success the caller's stream waits.
-struct UploadScope {
+// Ends a call's host-volume upload (stage_volume) however the call returns: HostUpload::finish
+struct UploadGuard {
     fnn_engine *e;
     bool ok = false;
-    ~UploadScope() {
-        if (!ok && e->up.pinned_src && e->up.n_issued > 0) (void)hipStreamSynchronize(e->up.st);
-        e->up.active = false;
-    }
+    ~UploadGuard() { (void)e->up.finish(ok); }
 };
 
 // Origins of the listed patches -> device (the stem conv reads them).
@@ -1247,7 +1066,8 @@ int upload_origins(fnn_engine *e, const VolPlan &vp, const std::vector<int64_t> 
     std::vector<int> host(ids.size() * 3);
     for (size_t i = 0; i < ids.size(); ++i)
         for (int d = 0; d < 3; ++d) host[i * 3 + d] = vp.origins[ids[i] * 3 + d];
-    return upload_ints(e, host.data(), host.size(), &e->origins, &e->origins_cap, &e->origins_host, &e->origins_host_cap, &e->origins_ev, st);
+    HIPCHK(e, e->origins.upload(host.data(), host.size(), st));
+    return 0;
 }
 
 FinalizeParams make_finalize(fnn_engine *e, const void *acc, const Box &box, const int64_t out_lo[3],
@@ -1264,7 +1084,7 @@ FinalizeParams make_finalize(fnn_engine *e, const void *acc, const Box &box, con
     f.out_X = shape[1]; f.out_Y = shape[2]; f.out_Z = shape[3];
     f.out_x = out_lo[0]; f.out_y = out_lo[1]; f.out_z = out_lo[2];
     f.heads = e->arch.num_heads; f.acc_fp32 = acc_fp32; f.out_fp32 = o.out_dtype == FNN_OUT_F32;
-    f.mode = mode; f.out = out; f.inf_flag = e->inf_flag;
+    f.mode = mode; f.out = out; f.inf_flag = e->inf_flag.as<int>();
     return f;
 }
 
@@ -1275,15 +1095,15 @@ int accumulate_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const
     const size_t esz = acc_fp32 ? 4 : 2;
     const size_t nvox = (size_t)vp.padded[0] * vp.padded[1] * vp.padded[2];
     const size_t bytes = nvox * acc_hp(a) * esz;
-    if (int rc = ensure(e, &e->acc, &e->acc_bytes, bytes)) return rc;
+    HIPCHK(e, e->acc.reserve(bytes));
     // The whole list in visiting order: the seg head writes every voxel's first visit without reading it, so the
     // 17 GB zero fill (and an eighth of the accumulator reads) is skipped.  Mirroring accumulates through the patch
     // buffer and the generic head kernel: those keep the zero fill.
     static const bool no_fv = fnn_knob("FNN_NO_FIRST_VISIT") != nullptr;            // A-B aid
-    const bool fresh = !no_fv && o.n_mirror_axes == 0 && launch_head_first_visit_ok(make_head(e, e->arena[0], fold, 0));
-    if (!fresh) HIPCHK(e, hipMemsetAsync(e->acc, 0, bytes, st));
+    const bool fresh = !no_fv && o.n_mirror_axes == 0 && launch_head_first_visit_ok(make_head(e, e->pipe[0].arena, fold, 0));
+    if (!fresh) HIPCHK(e, hipMemsetAsync(e->acc.p, 0, bytes, st));
     for (int d = 0; d < 3; ++d) { box.lo[d] = 0; box.hi[d] = vp.padded[d]; }
-    return run_patches(e, fold, vol_dev, vp, o, id_range(0, vp.n_patches), e->origins, AccBox{e->acc, box, acc_fp32, fresh}, st);
+    return run_patches(e, fold, vol_dev, vp, o, id_range(0, vp.n_patches), e->origins.data(), AccBox{e->acc.p, box, acc_fp32, fresh}, st);
 }
 
 // The gather kernel's integer tables for a volume: tile starts (+ window bases of axes with more than 64 positions,
@@ -1319,13 +1139,13 @@ GatherParams gather_params(const fnn_engine *e, int fold, const VolPlan &vp, con
     g.n_eval = 1 + (int)combos.size();
     for (size_t ci = 0; ci < combos.size() && ci + 1 < 8; ++ci)    // (flipmask[0] = 0: the plain evaluation)
         for (int ax : combos[ci]) g.flipmask[ci + 1] |= 1 << ax;
-    g.wpk = fw.wpk + e->head_w_off; g.bias = fw.fparam + e->head_bias_off;
-    g.n_pass = e->n_gpass; g.pass_wpk = fw.wpk + e->gpass_w_off; g.pass_bias = fw.fparam + e->gpass_bias_off;
-    g.gauss = o.use_gaussian ? e->gauss : e->ones;
+    g.wpk = fw.wpk.as<f16>() + e->head_w_off; g.bias = fw.fparam.as<float>() + e->head_bias_off;
+    g.n_pass = e->n_gpass; g.pass_wpk = fw.wpk.as<f16>() + e->gpass_w_off; g.pass_bias = fw.fparam.as<float>() + e->gpass_bias_off;
+    g.gauss = (o.use_gaussian ? e->gauss : e->ones).as<f16>();
     g.lo_x = (int)vp.lo[0]; g.lo_y = (int)vp.lo[1]; g.lo_z = (int)vp.lo[2];
     g.OX = shape[1]; g.OY = shape[2]; g.OZ = shape[3];
-    g.acc_mode = o.accum; g.inf_flag = e->inf_flag;
-    g.label_u16 = e->label_u16; g.order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
+    g.acc_mode = o.accum; g.inf_flag = e->inf_flag.as<int>();
+    g.label_u16 = e->label_u16; g.order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order.as<int>() : nullptr;
     return g;
 }
 
@@ -1361,7 +1181,7 @@ GatherPlan gather_plan(fnn_engine *e, int fold, const VolPlan &vp, const int64_t
     const double frac = fnn_knob("FNN_GATHER_MEM_FRACTION") ? atof(fnn_knob("FNN_GATHER_MEM_FRACTION")) : 0.6;
     const int force_ring = fnn_knob("FNN_GATHER_RING") ? atoi(fnn_knob("FNN_GATHER_RING")) : 0;     // tests: a ring although all fits
     // (the accumulators are not needed then; `pending_bytes`: what the caller still allocates after this plan - output / label staging)
-    const double budget = frac * ((double)(free_b + e->feat_bytes + e->acc_bytes) - (double)pending_bytes);
+    const double budget = frac * ((double)(free_b + e->feat.bytes + e->acc.bytes) - (double)pending_bytes);
     if (!force_ring && (double)layer_bytes * nx <= budget) gp.ring = nx;
     else if ((double)layer_bytes * gp.cover <= budget) gp.ring = std::min(nx, std::max(gp.cover, force_ring));
     else return gp;
@@ -1373,19 +1193,19 @@ GatherPlan gather_plan(fnn_engine *e, int fold, const VolPlan &vp, const int64_t
 int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const int64_t shape[4],
                         const fnn_opts &o, const GatherPlan &gp, int mode, void *out, void *labels, hipStream_t st) {
     const Layer &H = e->layers[e->head_src];
-    if (gp.feat_bytes > e->feat_bytes && e->acc) { (void)hipFree(e->acc); e->acc = nullptr; e->acc_bytes = 0; }
-    if (int rc = ensure(e, &e->feat, &e->feat_bytes, gp.feat_bytes)) return rc;
+    if (gp.feat_bytes > e->feat.bytes) e->acc.free();
+    HIPCHK(e, e->feat.reserve(gp.feat_bytes));
     const int64_t n_slots = (int64_t)gp.layer_items * gp.ring;
-    if (int rc = ensure(e, &e->featss, &e->featss_bytes, (size_t)n_slots * gp.n_eval * 2 * H.cout_pad * sizeof(float))) return rc;
-    if (int rc = ensure(e, &e->featssh, &e->featssh_bytes, (size_t)n_slots * gp.n_eval * 2 * H.cout_pad * sizeof(f16))) return rc;
+    HIPCHK(e, e->featss.reserve((size_t)n_slots * gp.n_eval * 2 * H.cout_pad * sizeof(float)));
+    HIPCHK(e, e->featssh.reserve((size_t)n_slots * gp.n_eval * 2 * H.cout_pad * sizeof(f16)));
     std::vector<int> steps;
     int win_off[3];
     if (!gather_tables(e->arch, vp, &steps, win_off)) return fail(e, FNN_E_UNSUPPORTED, "more than 64 tiles of one axis over a voxel");
-    if (int rc = upload_ints(e, steps.data(), steps.size(), &e->steps_dev, &e->steps_cap, &e->steps_host, &e->steps_host_cap, &e->steps_ev, st)) return rc;
+    HIPCHK(e, e->steps.upload(steps.data(), steps.size(), st));
     GatherParams g = gather_params(e, fold, vp, shape, o);
-    g.feat = (const f16 *)e->feat; g.fss = (const float *)e->featss; g.fssh = (const unsigned short *)e->featssh;
+    g.feat = e->feat.as<f16>(); g.fss = e->featss.as<float>(); g.fssh = e->featssh.as<unsigned short>();
     g.n_slots = (int)n_slots; g.ring = gp.ring;
-    gather_set_tables(g, e->steps_dev, win_off);
+    gather_set_tables(g, e->steps.data(), win_off);
     g.y_lo = 0; g.y_hi = (int)shape[2]; g.z_lo = 0; g.z_hi = (int)shape[3];
     g.out_vec = out && shape[3] % 8 == 0 && ((size_t)out % 16) == 0;
     g.mode = mode; g.out = out; g.labels = labels;
@@ -1394,9 +1214,9 @@ int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const Vol
         Scope sc(e, st, FAM_HEAD, e->head_flops * n_patches * gp.n_eval);
         return launch_gather(g, st) == 0 ? 0 : fail(e, FNN_E_HIP, "gather launch failed");
     };
-    const FeatSlots slots{e->feat, (float *)e->featss, (unsigned short *)e->featssh, 0, n_slots};
+    const FeatSlots slots{e->feat.p, e->featss.as<float>(), e->featssh.as<unsigned short>(), 0, n_slots};
     if (gp.ring == g.nx) {                                     // every patch of the volume is kept: one pass at the end
-        if (int rc = run_patches(e, fold, vol_dev, vp, o, id_range(0, vp.n_patches), e->origins, slots, st)) return rc;
+        if (int rc = run_patches(e, fold, vol_dev, vp, o, id_range(0, vp.n_patches), e->origins.data(), slots, st)) return rc;
         return launch(0, (int)shape[1], (double)vp.n_patches);
     }
     // ring: after x layer ix the output slab up to the next layer's first voxel is complete (padded coordinates
@@ -1405,7 +1225,7 @@ int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const Vol
     for (int ix = 0; ix < g.nx; ++ix) {
         FeatSlots layer = slots;
         layer.slot0 = (ix % gp.ring) * L;
-        if (int rc = run_patches(e, fold, vol_dev, vp, o, id_range(ix * L, L), e->origins + ix * L * 3, layer, st)) return rc;
+        if (int rc = run_patches(e, fold, vol_dev, vp, o, id_range(ix * L, L), e->origins.data() + ix * L * 3, layer, st)) return rc;
         const int64_t p_lo = ix == 0 ? 0 : vp.steps[0][ix], p_hi = ix + 1 < g.nx ? vp.steps[0][ix + 1] : vp.padded[0];
         const int x_lo = (int)std::max<int64_t>(0, p_lo - vp.lo[0]), x_hi = (int)std::min<int64_t>(shape[1], p_hi - vp.lo[0]);
         if (x_hi > x_lo) if (int rc = launch(x_lo, x_hi, (double)L)) return rc;
@@ -1425,7 +1245,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     VolPlan vp;
     if (int rc = plan_volume(e, shape, *o, vp)) return rc;
     const float *vol_dev = nullptr;
-    UploadScope upload{e};
+    UploadGuard upload{e};
     if (int rc = stage_volume(e, vol, shape, vp, st, &vol_dev, true)) return rc;
     if (int rc = upload_origins(e, vp, id_range(0, vp.n_patches), st)) return rc;
     const size_t nvox_out = (size_t)shape[1] * shape[2] * shape[3];
@@ -1441,7 +1261,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     size_t pending = 0;
     {
         const bool maybe_direct = labels && !want_logits && n_folds == 1 && e->n_gpass == 1;
-        if (!maybe_direct && !out_on_dev && nout * osz > e->out_tmp_bytes) pending += nout * osz - e->out_tmp_bytes;
+        if (!maybe_direct && !out_on_dev && nout * osz > e->out_tmp.bytes) pending += nout * osz - e->out_tmp.bytes;
         if (labels && !lab_on_dev) pending += lab_bytes;
     }
     const GatherPlan gp = gather_plan(e, fold0, vp, shape, *o, pending);
@@ -1454,15 +1274,15 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     const bool labels_direct = labels && !want_logits && n_folds == 1 && !(gp.ok && e->n_gpass > 1) && (gp.ok || acc_hp(a) <= 256);
     void *out_dev = out;
     if (!labels_direct && !out_on_dev) {
-        if (int rc = ensure(e, &e->out_tmp, &e->out_tmp_bytes, nout * osz)) return rc;
-        out_dev = e->out_tmp;
+        HIPCHK(e, e->out_tmp.reserve(nout * osz));
+        out_dev = e->out_tmp.p;
     }
     void *lab_dev = labels;
-    void *lab_tmp = nullptr;
-    const int *lab_order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
+    DevBuf lab_tmp;
+    const int *lab_order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order.as<int>() : nullptr;
     if (labels) if (int rc = check_u8_labels(e, a.num_heads, U16_HINT)) return rc;
-    if (labels && !lab_on_dev) { HIPCHK(e, hipMalloc(&lab_tmp, lab_bytes)); lab_dev = lab_tmp; }
-    HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
+    if (labels && !lab_on_dev) { HIPCHK(e, lab_tmp.reserve(lab_bytes)); lab_dev = lab_tmp.p; }
+    HIPCHK(e, hipMemsetAsync(e->inf_flag.p, 0, sizeof(int), st));
     e->ev_used = 0; e->klog.clear();
     const int acc_fp32 = o->accum == FNN_ACC_FP32;
     const int64_t zero3[3] = {0, 0, 0}, full3[3] = {shape[1], shape[2], shape[3]};
@@ -1476,13 +1296,13 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
         Box box;
         rc = accumulate_whole_volume(e, fold0 + f, vol_dev, vp, *o, box, st);
         if (rc) break;
-        FinalizeParams fp = make_finalize(e, e->acc, box, zero3, full3, vp, shape, *o, acc_fp32, f > 0 ? 1 : 0, out_dev);
+        FinalizeParams fp = make_finalize(e, e->acc.p, box, zero3, full3, vp, shape, *o, acc_fp32, f > 0 ? 1 : 0, out_dev);
         Scope sc(e, st, FAM_FINAL, 0);
         if (labels_direct) { if (launch_labels_from_acc(fp, lab_dev, e->label_u16, lab_order, st) != 0) rc = fail(e, FNN_E_HIP, "labels launch failed"); }
         else if (launch_finalize(fp, st) != 0) rc = fail(e, FNN_E_HIP, "finalize launch failed");
     }
     if (rc == 0 && !labels_direct && n_folds > 1)
-        if (launch_scale_output(out_dev, o->out_dtype == FNN_OUT_F32, (long long)nout, n_folds, e->inf_flag, st) != 0)
+        if (launch_scale_output(out_dev, o->out_dtype == FNN_OUT_F32, (long long)nout, n_folds, e->inf_flag.as<int>(), st) != 0)
             rc = fail(e, FNN_E_HIP, "scale launch failed");
     if (rc == 0 && labels && !labels_direct)
         if (launch_argmax(out_dev, o->out_dtype == FNN_OUT_F32, a.num_heads, (long long)nvox_out, lab_dev, e->label_u16, lab_order, st) != 0)
@@ -1496,7 +1316,6 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     if (rc == 0)
         rc = check_inf(e, st, "Encountered inf in predicted array. Aborting... If this problem persists, reduce "
                               "value_scaling_factor in compute_gaussian or increase the dtype of predicted_logits to fp32");
-    if (lab_tmp) (void)hipFree(lab_tmp);
     if (e->profiling && (rc == 0 || rc == FNN_E_INF)) collect_profile(e, vp.n_patches * n_folds);
     upload.ok = rc == 0;
     return rc;
@@ -1511,11 +1330,11 @@ int run_listed_patches(fnn_engine *e, int fold, const float *vol, const int64_t 
     if (ids.empty()) return 0;
     hipStream_t st = (hipStream_t)o.stream;
     const float *vol_dev = nullptr;
-    UploadScope upload{e};
+    UploadGuard upload{e};
     if (int rc = stage_volume(e, vol, shape, vp, st, &vol_dev)) return rc;
     if (int rc = upload_origins(e, vp, ids, st)) return rc;
     e->ev_used = 0; e->klog.clear();
-    if (int rc = run_patches(e, fold, vol_dev, vp, o, ids, e->origins, t, st)) return rc;
+    if (int rc = run_patches(e, fold, vol_dev, vp, o, ids, e->origins.data(), t, st)) return rc;
     if (e->profiling) { HIPCHK(e, hipStreamSynchronize(st)); collect_profile(e, n_ids); }
     upload.ok = true;
     return 0;
@@ -1540,9 +1359,9 @@ int finalize_box(fnn_engine *e, const char *who, const void *acc, const int64_t 
     Box box;
     for (int d = 0; d < 3; ++d) { box.lo[d] = box_lo[d]; box.hi[d] = box_hi[d]; }
     if (int rc = check_out_box(e, vp, shape, out_lo, out_hi, &box)) return rc;
-    HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
+    HIPCHK(e, hipMemsetAsync(e->inf_flag.p, 0, sizeof(int), st));
     const FinalizeParams f = make_finalize(e, acc, box, out_lo, out_hi, vp, shape, *opts, opts->accum == FNN_ACC_FP32, 0, out);
-    const int *order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order : nullptr;
+    const int *order = e->label_mode == FNN_LABELS_REGIONS ? e->label_order.as<int>() : nullptr;
     if (out && launch_finalize(f, st) != 0) return fail(e, FNN_E_HIP, "finalize launch failed");
     if (labels && launch_labels_from_acc(f, labels, e->label_u16, order, st) != 0) return fail(e, FNN_E_HIP, "labels launch failed");
     return check_inf(e, st);
@@ -1588,53 +1407,28 @@ int fnn_create(const fnn_arch_desc *arch, int device, int max_batch, fnn_engine 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, FNN_E_HIP, "no HIP device is available: the MI355X engine has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(nullptr, FNN_E_INVALID, "device %d out of range (%d visible)", device, ndev);
-    fnn_engine *e = new fnn_engine();
+    std::unique_ptr<fnn_engine> e(new fnn_engine());
     e->device = device;
-    if (int rc = plan_engine(e, arch, max_batch)) { delete e; return rc; }
-    auto bail = [&](const char *what, hipError_t r) {
-        fail(nullptr, FNN_E_HIP, "%s failed: %s", what, hipGetErrorString(r));
-        fnn_destroy(e);
-        return FNN_E_HIP;
-    };
-    hipError_t r;
-    if ((r = hipSetDevice(device)) != hipSuccess) return bail("hipSetDevice", r);
-    if (int rc = arena_alloc(e, e->arena[0])) { fnn_destroy(e); return rc; }
-    if ((r = hipMalloc((void **)&e->inf_flag, sizeof(int))) != hipSuccess) return bail("hipMalloc(flag)", r);
+    if (int rc = plan_engine(e.get(), arch, max_batch)) return rc;
+    HIPCHK(nullptr, hipSetDevice(device));
+    if (int rc = arena_alloc(e.get(), e->pipe[0].arena)) return rc;
+    HIPCHK(nullptr, e->inf_flag.reserve(sizeof(int)));
     {
         const size_t P = (size_t)arch->patch[0] * arch->patch[1] * arch->patch[2];
         std::vector<uint16_t> one(P, 0x3c00);                                       // fp16 1.0
-        if ((r = hipMalloc((void **)&e->ones, P * 2)) != hipSuccess) return bail("hipMalloc(ones)", r);
-        if ((r = hipMemcpy(e->ones, one.data(), P * 2, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(ones)", r);
+        HIPCHK(nullptr, e->ones.reserve(P * 2));
+        HIPCHK(nullptr, hipMemcpy(e->ones.p, one.data(), P * 2, hipMemcpyHostToDevice));
     }
-    *out = e;
+    *out = e.release();
     return 0;
 }
 
+// Every resource is a member that frees itself (owned.h): their order in fnn_engine carries no meaning, because the device
+// is idle before the first of them goes.
 void fnn_destroy(fnn_engine *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    for (auto &f : e->folds) { if (f.wpk) (void)hipFree(f.wpk); if (f.fparam) (void)hipFree(f.fparam); }
-    for (int k = 0; k < fnn_engine::MAXP; ++k) {
-        if (e->pipe[k]) (void)hipStreamDestroy(e->pipe[k]);
-        if (e->ev_head[k]) (void)hipEventDestroy(e->ev_head[k]);
-        if (e->ev_done[k]) (void)hipEventDestroy(e->ev_done[k]);
-        arena_free(e->arena[k]);
-    }
-    if (e->ev_start) (void)hipEventDestroy(e->ev_start);
-    for (hipEvent_t ev : e->up.landed) (void)hipEventDestroy(ev);
-    for (int k = 0; k < fnn_engine::Upload::RING; ++k) {
-        if (e->up.stage[k]) (void)hipHostFree(e->up.stage[k]);
-        if (e->up.stage_free[k]) (void)hipEventDestroy(e->up.stage_free[k]);
-    }
-    if (e->up.go) (void)hipEventDestroy(e->up.go);
-    if (e->up.st) (void)hipStreamDestroy(e->up.st);
-    if (e->steps_ev) (void)hipEventDestroy(e->steps_ev);
-    if (e->origins_ev) (void)hipEventDestroy(e->origins_ev);
-    if (e->steps_host) (void)hipHostFree(e->steps_host);
-    if (e->origins_host) (void)hipHostFree(e->origins_host);
-    void *ptrs[] = {e->feat, e->featss, e->featssh, e->steps_dev, e->ones, e->label_order, e->gauss, e->inf_flag, e->origins, e->acc, e->vol_tmp, e->vol_pad, e->out_tmp, e->patch_buf};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    for (auto &ev : e->evs) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
+    (void)hipDeviceSynchronize();
     delete e;
 }
 
@@ -1682,10 +1476,10 @@ int fnn_load_weights(fnn_engine *e, int fold, const float *blob, int64_t count) 
         for (int h = 0; h < cnt; ++h) fp[e->gpass_bias_off + (size_t)k * 64 + h] = blob[e->blob_head_b + h0 + h];
         fp[e->gpass_bias_off + (size_t)k * 64 + cnt] = 1.f;
     }
-    if (!fw.wpk) HIPCHK(e, hipMalloc((void **)&fw.wpk, fnn_weight_alloc_bytes(wpk.size())));
-    if (!fw.fparam) HIPCHK(e, hipMalloc((void **)&fw.fparam, fp.size() * 4));
-    HIPCHK(e, hipMemcpy(fw.wpk, wpk.data(), wpk.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(fw.fparam, fp.data(), fp.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(e, fw.wpk.reserve(fnn_weight_alloc_bytes(wpk.size())));
+    HIPCHK(e, fw.fparam.reserve(fp.size() * 4));
+    HIPCHK(e, hipMemcpy(fw.wpk.p, wpk.data(), wpk.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(fw.fparam.p, fp.data(), fp.size() * 4, hipMemcpyHostToDevice));
     fw.loaded = true;
     return 0;
 }
@@ -1695,8 +1489,8 @@ int fnn_set_gaussian(fnn_engine *e, const uint16_t *half_bits, int64_t count) {
     const int64_t P = (int64_t)e->arch.patch[0] * e->arch.patch[1] * e->arch.patch[2];
     if (!half_bits || count != P) return fail(e, FNN_E_INVALID, "gaussian must have %lld values", (long long)P);
     HIPCHK(e, hipSetDevice(e->device));
-    if (!e->gauss) HIPCHK(e, hipMalloc((void **)&e->gauss, P * 2));
-    HIPCHK(e, hipMemcpy(e->gauss, half_bits, P * 2, hipMemcpyHostToDevice));
+    HIPCHK(e, e->gauss.reserve(P * 2));
+    HIPCHK(e, hipMemcpy(e->gauss.p, half_bits, P * 2, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1793,17 +1587,17 @@ int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, 
     // tile starts (+ window bases), then the slot table, in one device buffer
     const size_t n_steps = tab.size();
     for (int64_t i = 0; i < vp.n_patches; ++i) tab.push_back(slot_of_patch[i]);
-    if (int rc = upload_ints(e, tab.data(), tab.size(), &e->steps_dev, &e->steps_cap, &e->steps_host, &e->steps_host_cap, &e->steps_ev, st)) return rc;
-    HIPCHK(e, hipMemsetAsync(e->inf_flag, 0, sizeof(int), st));
+    HIPCHK(e, e->steps.upload(tab.data(), tab.size(), st));
+    HIPCHK(e, hipMemsetAsync(e->inf_flag.p, 0, sizeof(int), st));
     {   // the kernel reads the InstanceNorm rows in the conv kernels' fp16 staging layout: converted from the caller's fp32 rows
         const size_t items = (size_t)n_slots * g.n_eval;
-        if (int rc = ensure(e, &e->featssh, &e->featssh_bytes, items * 2 * H.cout_pad * sizeof(f16))) return rc;
-        if (launch_fss_to_ssh(fss, (unsigned short *)e->featssh, (long long)items, H.cout_pad, st) != 0) return fail(e, FNN_E_HIP, "row conversion launch failed");
+        HIPCHK(e, e->featssh.reserve(items * 2 * H.cout_pad * sizeof(f16)));
+        if (launch_fss_to_ssh(fss, e->featssh.as<unsigned short>(), (long long)items, H.cout_pad, st) != 0) return fail(e, FNN_E_HIP, "row conversion launch failed");
     }
-    g.feat = (const f16 *)feat; g.fss = fss; g.fssh = (const unsigned short *)e->featssh;
+    g.feat = (const f16 *)feat; g.fss = fss; g.fssh = e->featssh.as<unsigned short>();
     g.n_slots = (int)n_slots; g.ring = 1;                       // evaluation f of slot s: item f * n_slots + s (fnn_patch_features)
-    gather_set_tables(g, e->steps_dev, win_off);
-    g.slot_tab = e->steps_dev + n_steps;
+    gather_set_tables(g, e->steps.data(), win_off);
+    g.slot_tab = e->steps.data() + n_steps;
     g.x_lo = (int)out_lo[0]; g.x_hi = (int)out_hi[0]; g.y_lo = (int)out_lo[1]; g.y_hi = (int)out_hi[1];
     g.z_lo = (int)out_lo[2]; g.z_hi = (int)out_hi[2];
     e->ev_used = 0; e->klog.clear();
@@ -1857,29 +1651,28 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
     const size_t nin = (size_t)n * a.in_channels * P, nout = (size_t)n * a.num_heads * P;
     const float *xd = x;
     if (!fnn_dev_ptr(x)) {
-        if (int rc = ensure(e, &e->vol_tmp, &e->vol_tmp_bytes, nin * 4)) return rc;
-        HIPCHK(e, hipMemcpyAsync(e->vol_tmp, x, nin * 4, hipMemcpyHostToDevice, st));
-        xd = e->vol_tmp;
+        HIPCHK(e, e->vol_tmp.reserve(nin * 4));
+        HIPCHK(e, hipMemcpyAsync(e->vol_tmp.p, x, nin * 4, hipMemcpyHostToDevice, st));
+        xd = e->vol_tmp.as<float>();
     }
     float *od = logits;
     const bool out_dev = fnn_dev_ptr(logits);
     if (!out_dev) {
-        if (int rc = ensure(e, &e->out_tmp, &e->out_tmp_bytes, nout * 4)) return rc;
-        od = (float *)e->out_tmp;
+        HIPCHK(e, e->out_tmp.reserve(nout * 4));
+        od = e->out_tmp.as<float>();
     }
     std::vector<int> zeros((size_t)e->max_batch * 3, 0);
-    if (int rc = ensure(e, &e->origins, &e->origins_cap, zeros.size() * sizeof(int))) return rc;
-    HIPCHK(e, hipMemcpyAsync(e->origins, zeros.data(), zeros.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(e, e->origins.upload(zeros.data(), zeros.size(), st));
     HIPCHK(e, hipStreamSynchronize(st));
     const long long vdim[3] = {a.patch[0], a.patch[1], a.patch[2]};
     const int flip[3] = {0, 0, 0};
     e->ev_used = 0; e->klog.clear();
     for (int p0 = 0; p0 < n; p0 += e->max_batch) {
         const int nb = (n - p0 < e->max_batch) ? n - p0 : e->max_batch;
-        if (int rc = forward_batch(e, fold, e->arena[0], xd + (size_t)p0 * a.in_channels * P, (long long)(a.in_channels * P), vdim,
-                                   e->origins, nb, flip, st)) return rc;
+        if (int rc = forward_batch(e, fold, e->pipe[0].arena, xd + (size_t)p0 * a.in_channels * P, (long long)(a.in_channels * P), vdim,
+                                   e->origins.data(), nb, flip, st)) return rc;
         for (int b = 0; b < nb; ++b) {
-            HeadParams h = make_head(e, e->arena[0], fold, b);
+            HeadParams h = make_head(e, e->pipe[0].arena, fold, b);
             h.mode = 1; h.patch_buf = od + (size_t)(p0 + b) * a.num_heads * P;
             h.acc_fp32 = 1;
             Scope sc(e, st, FAM_HEAD, e->head_flops);
@@ -1904,8 +1697,8 @@ int fnn_set_label_rule(fnn_engine *e, int mode, const int32_t *regions_class_ord
             if (regions_class_order[i] < 0 || regions_class_order[i] > limit)
                 return fail(e, FNN_E_INVALID, "regions_class_order[%d] = %d does not fit the label dtype", i, regions_class_order[i]);
         HIPCHK(e, hipSetDevice(e->device));
-        if (!e->label_order) HIPCHK(e, hipMalloc((void **)&e->label_order, sizeof(int) * (size_t)e->arch.num_heads));
-        HIPCHK(e, hipMemcpy(e->label_order, regions_class_order, sizeof(int) * (size_t)n_regions, hipMemcpyHostToDevice));
+        HIPCHK(e, e->label_order.reserve(sizeof(int) * (size_t)e->arch.num_heads));
+        HIPCHK(e, hipMemcpy(e->label_order.p, regions_class_order, sizeof(int) * (size_t)n_regions, hipMemcpyHostToDevice));
     }
     e->label_mode = mode;
     e->label_u16 = label_dtype == FNN_LABEL_U16;
@@ -1920,7 +1713,7 @@ int fnn_argmax_labels(fnn_engine *e, const void *logits, int dtype, int heads, i
     if (int rc = check_u8_labels(e, heads, "")) return rc;
     if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(labels)) return fail(e, FNN_E_INVALID, "fnn_argmax_labels needs device pointers");
     HIPCHK(e, hipSetDevice(e->device));
-    if (launch_argmax(logits, dtype == FNN_OUT_F32, heads, n_vox, labels, e->label_u16, regions ? e->label_order : nullptr,
+    if (launch_argmax(logits, dtype == FNN_OUT_F32, heads, n_vox, labels, e->label_u16, regions ? e->label_order.as<int>() : nullptr,
                       (hipStream_t)stream) != 0)
         return fail(e, FNN_E_HIP, "argmax launch failed");
     return 0;

@@ -1,38 +1,14 @@
 // host_call.h - the host side of one call of an entry point outside the engine (prep, resample, export_labels, postprocess,
-// ensemble, metrics, imageio, reorient, deflate_masks, ops_api): owned scratch, the status chain of one call on
+// ensemble, metrics, imageio, reorient, deflate_masks, ops_api): owned scratch (DevBuf, owned.h), the status chain of one call on
 // one stream, the refusals the entries share and the dispatch from a dtype code to an element type.  Host code only: no
 // kernel and no __device__ function lives here.
 #pragma once
 #include "fnn_device.h"
+#include "owned.h"
 #include "../../include/fnn.h"
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
-
-// One hipMalloc block, freed when its owner goes out of scope.  A refused allocation reads HIP's sticky last-error state
-// away, so that the next entry point's hipGetLastError() after a good launch does not report it.  Sites that cut one block
-// into several regions take them at byte offsets: as<T>(offset).
-struct DevBuf {
-    void *p = nullptr;
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { free(); }
-    void free() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    bool alloc(size_t n, hipError_t *why = nullptr) {                // *why: what hipMalloc answered
-        const hipError_t r = hipMalloc(&p, n ? n : 16);
-        if (why) *why = r;
-        if (r == hipSuccess) return true;
-        p = nullptr;
-        (void)hipGetLastError();
-        return false;
-    }
-    template <class T> T *as(size_t byte_offset = 0) const { return (T *)((char *)p + byte_offset); }
-};
 
 int fnn_failf(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 inline int fnn_failf(int code, const char *fmt, ...) {

@@ -194,8 +194,8 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
     (void)hipMemset(dst.p, 0, (size_t)n * slots * cop * 16);
 #endif
     if (fnn_knob("FNN_OP_TIME")) {                    // diagnostic: mean duration of 30 launches of this layer (after 2 warm-ups)
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+        Event e0, e1;
+        (void)e0.create(hipEventDefault); (void)e1.create(hipEventDefault);
         for (int i = 0; i < 2; ++i) (void)launch();
         (void)hipEventRecord(e0, 0);
         for (int i = 0; i < 30; ++i) (void)launch();
@@ -204,12 +204,11 @@ int fnn_op_conv3d(int device, int n, const int dims[3],
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         fprintf(stderr, "[op time] conv3d %d+%d -> %d at %dx%dx%d, N = %d: %.1f us per launch\n", cin, cin2, cout, p.Di, p.Hi, p.Wi, n, ms * (1000.f / 30.f));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         (void)hipMemset(dst.p, 0, (size_t)n * slots * cop * 16);
     }
 #ifdef FNN_STAMPS
-    hipEvent_t ev0, ev1;
-    (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
+    Event ev0, ev1;
+    (void)ev0.create(hipEventDefault); (void)ev1.create(hipEventDefault);
     (void)hipEventRecord(ev0, 0);
 #endif
     const int rc = launch();
@@ -530,13 +529,9 @@ __global__ void clock_probe_kernel(unsigned long long *out, const int *flag, uns
 }
 struct ClockProbe {
     int device = 0;
-    hipStream_t st = nullptr;
+    Stream st;
     DevBuf out;                                               // 4 x u64
-    int *flag = nullptr;                                      // mapped host memory
-    ~ClockProbe() {
-        if (flag) (void)hipHostFree(flag);
-        if (st) (void)hipStreamDestroy(st);
-    }
+    PinnedBuf flag;                                           // one int in mapped host memory
 };
 }  // namespace
 
@@ -547,11 +542,10 @@ int fnn_clock_probe_start(int device, double max_seconds, void **probe) {
     std::unique_ptr<ClockProbe> c(new ClockProbe);
     c->device = device;
     int *dflag = nullptr;
-    if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || !c->out.alloc(32) ||
-        hipHostMalloc((void **)&c->flag, sizeof(int), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&dflag, c->flag, 0) != hipSuccess)
+    if (c->st.create() != hipSuccess || !c->out.alloc(32) || c->flag.reserve(sizeof(int), hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&dflag, c->flag.p, 0) != hipSuccess)
         return FNN_E_HIP;
-    *c->flag = 0;
+    *c->flag.as<int>() = 0;
     (void)hipMemsetAsync(c->out.p, 0, 32, c->st);
     hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, c->st, c->out.as<unsigned long long>(), dflag, (unsigned long long)(max_seconds * 1e8));
     if (hipGetLastError() != hipSuccess) return FNN_E_HIP;
@@ -563,7 +557,7 @@ int fnn_clock_probe_stop(void *probe, double *ghz, double *seconds) {
     std::unique_ptr<ClockProbe> c((ClockProbe *)probe);
     if (!c) return FNN_E_INVALID;
     (void)hipSetDevice(c->device);
-    __atomic_store_n(c->flag, 1, __ATOMIC_RELEASE);
+    __atomic_store_n(c->flag.as<int>(), 1, __ATOMIC_RELEASE);
     unsigned long long h[4] = {0, 0, 0, 0};
     const bool ok = hipStreamSynchronize(c->st) == hipSuccess && hipMemcpy(h, c->out.p, 32, hipMemcpyDeviceToHost) == hipSuccess;
     c.reset();
