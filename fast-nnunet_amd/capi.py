@@ -72,7 +72,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -138,7 +138,9 @@ def load_library() -> C.CDLL:
                                          C.POINTER(i64), vp]
     lib.fnn_surface_count.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(i64), C.POINTER(i64), vp]
     lib.fnn_surface_distances.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(C.c_double), vp, i64, vp]
-    lib.fnn_decode_voxels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
+    if hasattr(lib, 'fnn_instance_overlaps'):                      # (absent from an older build picked with FNN_LIB for an A-B)
+        lib.fnn_instance_overlaps.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, vp, i64, C.POINTER(i64), vp]
+    lib.fnn_decode_voxels.argtypes =[vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
     lib.fnn_decode_labels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, i32, vp, vp, vp]
     lib.fnn_reorient.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
     lib.fnn_deflate_bound.argtypes = [i64]
@@ -502,6 +504,44 @@ def surface_distances(ref_ptr: int, pred_ptr: int, uint16: bool, shape, member, 
     check(lib.fnn_surface_distances(ref_ptr, pred_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8,
                                     (C.c_int64 * 3)(*[int(i) for i in shape]), mp, int(n_table), int(n_regions),
                                     (C.c_double * 3)(*[float(s) for s in spacing]), sq_dist_ptr, int(cap), stream), lib)
+
+
+INSTANCE_FIRST_CAPACITY = 65536        # records the first call of instance_overlaps has room for
+
+
+def instance_overlaps_call(ref_ptr: int, pred_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, records_ptr: int,
+                           cap: int, stream: int = 0) -> np.ndarray:
+    """One fnn_instance_overlaps call on two device label maps [X, Y, Z] with a device buffer of ``cap`` records of three
+    int32 at ``records_ptr``.  Returns int64 (ref components, pred components, pieces); the buffer was written iff their sum
+    is at most ``cap``."""
+    lib = load_library()
+    table = np.ascontiguousarray(group_of_label, dtype=np.int32)
+    n_out = np.zeros(3, np.int64)
+    check(lib.fnn_instance_overlaps(ref_ptr, pred_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8,
+                                    (C.c_int64 * 3)(*[int(i) for i in shape]), table.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    int(table.size), int(n_groups), records_ptr, int(cap),
+                                    n_out.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
+    return n_out
+
+
+def instance_overlaps(ref_ptr: int, pred_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, stream: int = 0, *,
+                      first_capacity: int = INSTANCE_FIRST_CAPACITY):
+    """fnn_instance_overlaps with the record buffer owned here: a call with room for ``first_capacity`` records and, when
+    that was short, one more with the exact size.  Returns (n_out int64 [3], records int32 [sum(n_out), 3] on the host, the
+    number of calls made)."""
+    import torch
+    dev = torch.device('cuda', torch.cuda.current_device())
+    cap, calls = max(int(first_capacity), 1), 0
+    while True:
+        buf = torch.empty(cap * 3, dtype=torch.int32, device=dev)
+        n_out = instance_overlaps_call(ref_ptr, pred_ptr, uint16, shape, group_of_label, n_groups, buf.data_ptr(), cap, stream)
+        calls += 1
+        total = int(n_out.sum())
+        if total <= cap:
+            return n_out, buf[:total * 3].cpu().numpy().reshape(total, 3), calls
+        if calls == 2:
+            raise EngineError(f'fnn_instance_overlaps asked for {total} records after it was given {cap}')
+        cap = total
 
 
 def _order(regions_class_order, heads: int):

@@ -4,229 +4,21 @@
 //                                 (postprocessing/remove_connected_components.py:21-33) for several disjoint label
 //                                 sets in one pass
 //
-// Label-aware 3-D connected components (26-connectivity) by union-find over int32 voxel indices, in six launches:
-//   1. tile_merge    init + union inside a 1024-voxel tile through LDS; every voxel's global parent is the global
-//                    index of its tile-local root (-1 outside every set);
-//   2. cross_merge   the 13 "backward" neighbours (smaller linear index) that lie outside the voxel's tile, linked
-//                    lock-free: atomicMin(&parent[a], b) with a > b, retried on the returned value (Playne & Hawick);
+// Label-aware 3-D connected components (26-connectivity) by union-find over int32 voxel indices, in six launches; the
+// first four are cc_label.h's (its header comment holds the invariants and the memory rules of parent[]):
+//   1. tile_merge    init + union inside a 1024-voxel tile through LDS;
+//   2. cross_merge   the backward neighbours outside the voxel's tile, linked lock-free;
 //   3. flatten       parent[i] = root(i);
 //   4. count         size[root] += 1, aggregated per thread run and per wave before the atomic;
 //   5. group_max     per set, the largest component size (atomicMax by roots, through an LDS table per workgroup);
 //   6. apply         voxels of a set whose component is smaller than the set's maximum become background_label.
-//
-// Invariants that make every phase end by construction (no spin on another workgroup's value, no recursion):
-// parent[i] <= i always, and parent[] changes only through atomicMin to a smaller index, so every find walks a
-// strictly decreasing chain even when it reads stale values; a union retries with a strictly smaller larger-root.
-// Per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores: inside phases 2 and 3 every
-// read of parent[] is an agent-scope relaxed atomic load (sc1), and every write an agent-scope atomic.  A stale read
-// only costs a retry: the atomicMin's returned value is the truth.
-#include "host_call.h"
+#include "cc_label.h"
 #include <climits>
 #include <vector>
 
 namespace {
 
-constexpr int CC_THREADS = 256;
-constexpr int CC_TILE = 1024;          // voxels per tile: 4 per thread
 constexpr int CC_LDS_GROUPS = 4096;    // sets counted through an LDS table per workgroup (more: straight global atomics)
-constexpr int CC_RUN = 16;             // consecutive voxels per thread in the size count
-
-struct CCGeom {
-    int X, Y, Z;                       // volume [X][Y][Z], X * Y * Z <= INT_MAX
-    int sx, sy, sz;                    // tile = (1 << sx) x (1 << sy) x (1 << sz) = CC_TILE voxels
-    int tiles_y, tiles_z;
-    int n_table;                       // labels >= n_table are in no set
-};
-
-// the 13 neighbours with a smaller linear index: dx = -1 (9), dx = 0 and dy = -1 (3), dx = dy = 0 and dz = -1 (1)
-__constant__ signed char c_back[13][3] = {
-    {-1, -1, -1}, {-1, -1, 0}, {-1, -1, 1}, {-1, 0, -1}, {-1, 0, 0}, {-1, 0, 1}, {-1, 1, -1}, {-1, 1, 0}, {-1, 1, 1},
-    {0, -1, -1}, {0, -1, 0}, {0, -1, 1}, {0, 0, -1}};
-
-template <typename T>
-__device__ __forceinline__ int group_of(const T *labels, int i, const int *table, int n_table) {
-    const int v = labels[i];
-    return v < n_table ? table[v] : -1;
-}
-
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int min_agent(int *p, int v) {
-    return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int ld_wg(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// ---- union-find inside a tile (LDS, local indices; local order = global order inside a tile)
-__device__ int local_find(const int *lp, int x) {
-    int p = ld_wg(lp + x);
-    while (p != x) { x = p; p = ld_wg(lp + x); }
-    return x;
-}
-__device__ void local_union(int *lp, int a, int b) {
-    while (true) {
-        a = local_find(lp, a);
-        b = local_find(lp, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(lp + a, b);
-        if (old == a) return;
-        a = old;                       // a was linked meanwhile: link its new parent instead (old < a)
-    }
-}
-
-// ---- union-find over the volume (global indices); path halving through atomicMin keeps parent[i] <= i
-__device__ int global_find(int *parent, int x) {
-    while (true) {
-        const int p = ld_agent(parent + x);
-        if (p == x) return x;
-        const int gp = ld_agent(parent + p);
-        if (gp == p) return p;
-        (void)min_agent(parent + x, gp);
-        x = gp;
-    }
-}
-__device__ void global_union(int *parent, int a, int b) {
-    while (true) {
-        a = global_find(parent, a);
-        b = global_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = min_agent(parent + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__device__ __forceinline__ void tile_coords(const CCGeom &g, int l, int &lx, int &ly, int &lz) {
-    lz = l & ((1 << g.sz) - 1);
-    ly = (l >> g.sz) & ((1 << g.sy) - 1);
-    lx = l >> (g.sz + g.sy);
-}
-__device__ __forceinline__ void tile_origin(const CCGeom &g, int &x0, int &y0, int &z0) {
-    const int t = blockIdx.x;
-    const int tz = t % g.tiles_z, ty = (t / g.tiles_z) % g.tiles_y, tx = t / (g.tiles_z * g.tiles_y);
-    x0 = tx << g.sx; y0 = ty << g.sy; z0 = tz << g.sz;
-}
-
-// 1. init + merge inside the tile
-template <typename T>
-__global__ __launch_bounds__(CC_THREADS) void cc_tile_merge_kernel(const T *labels, const int *table, CCGeom g, int *parent) {
-    __shared__ int lp[CC_TILE];
-    __shared__ int lg[CC_TILE];
-    int x0, y0, z0;
-    tile_origin(g, x0, y0, z0);
-    const int TY = 1 << g.sy, TZ = 1 << g.sz;
-    for (int l = threadIdx.x; l < CC_TILE; l += CC_THREADS) {
-        int lx, ly, lz;
-        tile_coords(g, l, lx, ly, lz);
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        int grp = -1;
-        if (x < g.X && y < g.Y && z < g.Z) grp = group_of(labels, (x * g.Y + y) * g.Z + z, table, g.n_table);
-        lg[l] = grp;
-        lp[l] = grp >= 0 ? l : -1;
-    }
-    __syncthreads();
-    for (int l = threadIdx.x; l < CC_TILE; l += CC_THREADS) {
-        const int grp = lg[l];
-        if (grp < 0) continue;
-        int lx, ly, lz;
-        tile_coords(g, l, lx, ly, lz);
-#pragma unroll
-        for (int k = 0; k < 13; ++k) {
-            const int nx = lx + c_back[k][0], ny = ly + c_back[k][1], nz = lz + c_back[k][2];
-            if (nx < 0 || ny < 0 || nz < 0 || ny >= TY || nz >= TZ) continue;
-            const int nl = (nx * TY + ny) * TZ + nz;
-            if (lg[nl] == grp) local_union(lp, l, nl);
-        }
-    }
-    __syncthreads();
-    for (int l = threadIdx.x; l < CC_TILE; l += CC_THREADS) {
-        int lx, ly, lz;
-        tile_coords(g, l, lx, ly, lz);
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        if (x >= g.X || y >= g.Y || z >= g.Z) continue;
-        int v = -1;
-        if (lg[l] >= 0) {
-            int rx, ry, rz;
-            tile_coords(g, local_find(lp, l), rx, ry, rz);
-            v = ((x0 + rx) * g.Y + (y0 + ry)) * g.Z + (z0 + rz);
-        }
-        parent[(x * g.Y + y) * g.Z + z] = v;
-    }
-}
-
-// 2. link across tile borders: the backward neighbours of a voxel that lie in another tile
-template <typename T>
-__global__ __launch_bounds__(CC_THREADS) void cc_cross_merge_kernel(const T *labels, const int *table, CCGeom g, int *parent) {
-    int x0, y0, z0;
-    tile_origin(g, x0, y0, z0);
-    const int TX = 1 << g.sx, TY = 1 << g.sy, TZ = 1 << g.sz;
-    for (int l = threadIdx.x; l < CC_TILE; l += CC_THREADS) {
-        int lx, ly, lz;
-        tile_coords(g, l, lx, ly, lz);
-        // only voxels on a tile face have neighbours in another tile
-        if (lx > 0 && ly > 0 && lz > 0 && ly < TY - 1 && lz < TZ - 1) continue;
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        if (x >= g.X || y >= g.Y || z >= g.Z) continue;
-        const int i = (x * g.Y + y) * g.Z + z;
-        const int grp = group_of(labels, i, table, g.n_table);
-        if (grp < 0) continue;
-        for (int k = 0; k < 13; ++k) {
-            const int ox = lx + c_back[k][0], oy = ly + c_back[k][1], oz = lz + c_back[k][2];
-            if (ox >= 0 && oy >= 0 && oz >= 0 && oy < TY && oz < TZ && ox < TX) continue;    // inside the tile: done by 1.
-            const int nx = x + c_back[k][0], ny = y + c_back[k][1], nz = z + c_back[k][2];
-            if (nx < 0 || ny < 0 || nz < 0 || ny >= g.Y || nz >= g.Z) continue;
-            const int j = (nx * g.Y + ny) * g.Z + nz;
-            if (group_of(labels, j, table, g.n_table) == grp) global_union(parent, i, j);
-        }
-    }
-}
-
-// 3. every voxel points at its root
-__global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int *parent, int n) {
-    const int i = blockIdx.x * CC_THREADS + threadIdx.x;
-    if (i >= n) return;
-    const int p = ld_agent(parent + i);
-    if (p < 0 || p == i) return;
-    int r = p, q = ld_agent(parent + r);
-    while (q != r) { r = q; q = ld_agent(parent + r); }
-    if (r != p) (void)min_agent(parent + i, r);
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// 4. component sizes: each thread counts a run of CC_RUN consecutive voxels, then the lanes of a wave that end on the
-// same root add together - a component of 10^7 voxels costs one atomic per wave, not one per voxel
-__global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const int *parent, int n, int *size) {
-    const long long start = ((long long)blockIdx.x * CC_THREADS + threadIdx.x) * CC_RUN;
-    int cur = -1, cnt = 0;
-    for (int k = 0; k < CC_RUN; ++k) {
-        const long long i = start + k;
-        if (i >= n) break;
-        const int r = parent[i];
-        if (r < 0) continue;
-        if (r != cur) {
-            if (cur >= 0) atomicAdd(size + cur, cnt);
-            cur = r;
-            cnt = 0;
-        }
-        ++cnt;
-    }
-    const int lane = threadIdx.x & 63;
-    unsigned long long act = __ballot(cur >= 0);
-    while (act) {                                        // wave-uniform: every lane runs every iteration
-        const int leader = __ffsll((long long)act) - 1;
-        const int r = __shfl(cur, leader);
-        const bool mine = cur == r;
-        const int s = wave_sum(mine ? cnt : 0);
-        if (lane == leader) atomicAdd(size + r, s);
-        if (mine) cur = -1;
-        act = __ballot(cur >= 0);
-    }
-}
 
 // 5. per set, the largest component
 template <typename T>
@@ -281,15 +73,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(T *labels, const i
 template <typename T>
 void launch_all(T *labels, const int *table, const CCGeom &g, int n, int n_groups, T background, int *parent, int *size,
                 int *gmax, unsigned long long *removed, HipCall &call) {
-    const long long tiles = (long long)((g.X + (1 << g.sx) - 1) >> g.sx) * g.tiles_y * g.tiles_z;
-    const unsigned vox_blocks = (unsigned)((n + CC_THREADS - 1) / CC_THREADS);
-    const unsigned run_blocks = (unsigned)(((long long)n + (long long)CC_THREADS * CC_RUN - 1) / ((long long)CC_THREADS * CC_RUN));
+    const unsigned vox_blocks = cc_vox_blocks(n);
     const unsigned red_blocks = vox_blocks < 2048u ? vox_blocks : 2048u;
     const dim3 block(CC_THREADS);
-    call.launch(cc_tile_merge_kernel<T>, dim3((unsigned)tiles), block, 0, labels, table, g, parent);
-    call.launch(cc_cross_merge_kernel<T>, dim3((unsigned)tiles), block, 0, labels, table, g, parent);
-    call.launch(cc_flatten_kernel, dim3(vox_blocks), block, 0, parent, n);
-    call.launch(cc_count_kernel, dim3(run_blocks), block, 0, parent, n, size);
+    cc_label(call, CCLabelMap<T>{labels, table}, g, n, parent);
+    cc_sizes(call, parent, n, size);
     call.launch(cc_group_max_kernel<T>, dim3(red_blocks), block, 0, labels, table, g.n_table, parent,
                 size, n, n_groups, gmax);
     call.launch(cc_apply_kernel<T>, dim3(red_blocks), block, 0, labels, table, g.n_table, parent, size,
@@ -321,15 +109,7 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
     if (n_groups == 0 || n_tab == 0) return FNN_OK;                              // no set: nothing changes
     const int n = (int)(shape[0] * shape[1] * shape[2]);
 
-    CCGeom g{};
-    g.X = (int)shape[0]; g.Y = (int)shape[1]; g.Z = (int)shape[2];
-    // 8 x 8 x 16 tiles (28 % of the voxels on a face); thin volumes (2-D configurations: X = 1) in-plane tiles
-    if (g.X >= 8) { g.sx = 3; g.sy = 3; g.sz = 4; }
-    else if (g.X >= 4) { g.sx = 2; g.sy = 4; g.sz = 4; }
-    else { g.sx = 0; g.sy = 5; g.sz = 5; }
-    g.tiles_y = (g.Y + (1 << g.sy) - 1) >> g.sy;
-    g.tiles_z = (g.Z + (1 << g.sz) - 1) >> g.sz;
-    g.n_table = n_tab;
+    const CCGeom g = cc_geom(shape, n_tab);
 
     // one scratch block: parent [n] | size [n] | table [n_tab] | gmax [n_groups] | removed [n_groups] (8-B aligned)
     const size_t off_size = (size_t)n * 4, off_table = off_size + (size_t)n * 4, off_gmax = off_table + (size_t)n_tab * 4;

@@ -21,6 +21,11 @@ Beyond the reference, on request (``surface_metrics=True``): the boundary metric
 definitions.  ``surface_distances`` gets the exact distances from every surface voxel of one mask to the surface of the
 other from ``fnn_surface_count`` / ``fnn_surface_distances`` (csrc/surface.hip); ``surface_metrics_of`` is the host half,
 plain numpy expressions on the downloaded distances.
+
+And (``instance_metrics=True``) the lesion-wise metrics per 26-connected component: detection recall / precision / F1 with
+the autoPET rule, the voxels of missed and of false-positive lesions, and panoptic quality at IoU > 0.5.
+``instance_overlaps`` gets both maps' component sizes and the pairs' overlaps from ``fnn_instance_overlaps``
+(csrc/instance.hip); ``instance_metrics_of`` is the host half, numpy expressions on exact integers.
 """
 from __future__ import annotations
 
@@ -397,36 +402,197 @@ def compute_surface_metrics(seg_ref, seg_pred, labels_or_regions: Sequence[Label
             for k, r in enumerate(labels_or_regions)}
 
 
-def _with_surface(metrics: dict, surface: dict) -> dict:
+def _with_keys(metrics: dict, more: dict) -> dict:
     for r, m in metrics.items():
-        m.update(surface[r])
+        m.update(more[r])
     return metrics
+
+
+_with_surface = _with_keys         # its name while the surface keys were the only ones
+
+
+# ---- connected components, their overlaps and the lesion-wise metrics ----------------------------------------------------
+INSTANCE_KEYS = ('n_inst_ref', 'n_inst_pred', 'inst_TP', 'inst_FN', 'inst_FP', 'inst_recall', 'inst_precision', 'inst_F1',
+                 'FN_inst_vox', 'FP_inst_vox', 'PQ', 'SQ', 'RQ')
+MAX_INSTANCE_GROUPS = 1024
+
+
+def _check_instance_request(instance_metrics: bool, ignore_label):
+    if instance_metrics and ignore_label is not None:
+        raise ValueError(f'instance metrics are refused together with an ignore label ({ignore_label}): a component next to '
+                         f'ignored voxels has no agreed extent')
+
+
+def plan_instance_calls(labels_or_regions: Sequence[LabelOrRegion]) -> List[List[int]]:
+    """The labels or regions (by position) grouped into calls of pairwise disjoint label sets, by the greedy rule of
+    ``postprocessing.plan_passes``: each joins the first call none of whose sets it meets, else opens a new one.  The order
+    of the calls means nothing here, so any earlier call may take it, not only the open one; a call holds at most
+    ``MAX_INSTANCE_GROUPS`` sets."""
+    calls: List[Tuple[List[int], set]] = []
+    for k, r in enumerate(labels_or_regions):
+        s = set(_members(r))
+        for v in s:
+            if v < 0 or v > 65535:
+                raise ValueError(f'label {v} is outside 0..65535')
+        for idx, used in calls:
+            if len(idx) < MAX_INSTANCE_GROUPS and not (used & s):
+                idx.append(k)
+                used |= s
+                break
+        else:
+            calls.append(([k], set(s)))
+    return [idx for idx, _ in calls]
+
+
+def _rank_in_group(group: np.ndarray, n_groups: int) -> np.ndarray:
+    """The position of every record among the records of its own group, the order kept."""
+    order = np.argsort(group, kind='stable')
+    starts = np.searchsorted(group[order], np.arange(n_groups))
+    rank = np.empty(len(group), np.int64)
+    rank[order] = np.arange(len(group)) - starts[group[order]]
+    return rank
+
+
+def overlaps_from_records(n_out, records: np.ndarray, n_groups: int) -> List[dict]:
+    """fnn_instance_overlaps' records -> per group ``{'ref_sizes', 'pred_sizes', 'pairs'}``: the pieces of one (pred component,
+    ref component) pair are added up, and roots become positions in the group's size lists.  No GPU call."""
+    n_ref, n_pred, n_pieces = (int(v) for v in n_out)
+    rec = np.asarray(records, dtype=np.int64).reshape(-1, 3)
+    if len(rec) != n_ref + n_pred + n_pieces:
+        raise ValueError(f'{len(rec)} records for {n_ref} + {n_pred} + {n_pieces}')
+    ref, pred, pieces = rec[:n_ref], rec[n_ref:n_ref + n_pred], rec[n_ref + n_pred:]
+    ref_rank, pred_rank = _rank_in_group(ref[:, 0], n_groups), _rank_in_group(pred[:, 0], n_groups)
+    at_pred, at_ref = np.searchsorted(pred[:, 1], pieces[:, 0]), np.searchsorted(ref[:, 1], pieces[:, 1])
+    piece_group = pred[at_pred, 0] if n_pieces else np.zeros(0, np.int64)
+    out = []
+    for g in range(n_groups):
+        mine = piece_group == g
+        pi, ri, size = pred_rank[at_pred[mine]], ref_rank[at_ref[mine]], pieces[mine, 2]
+        n_r = int((ref[:, 0] == g).sum())
+        uniq, inverse = np.unique(pi * max(n_r, 1) + ri, return_inverse=True)
+        overlap = np.zeros(len(uniq), np.int64)
+        np.add.at(overlap, inverse.reshape(-1), size)
+        pairs = np.stack([uniq // max(n_r, 1), uniq % max(n_r, 1), overlap], axis=1).astype(np.int64).reshape(-1, 3)
+        out.append({'ref_sizes': ref[ref[:, 0] == g, 2].copy(), 'pred_sizes': pred[pred[:, 0] == g, 2].copy(), 'pairs': pairs})
+    return out
+
+
+def instance_overlaps(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], checked: bool = False, *,
+                      first_capacity: Optional[int] = None, calls_made: Optional[list] = None) -> dict:
+    """``{label_or_region: {'ref_sizes', 'pred_sizes', 'pairs'}}``: the sizes (int64) of the 26-connected components of the
+    reference's and of the prediction's mask, in raster order of the components' first voxels, and ``pairs`` int64 [k, 3] of
+    (pred index, ref index, voxels in both) for every pair that shares a voxel, sorted by those indices.  A region is the
+    union of its labels; outside the volume is background.  Label maps as ``confusion_counts`` takes them, 3-D (leading axes of
+    length 1 are dropped).  Disjoint labels or regions go through one ``fnn_instance_overlaps`` call, overlapping ones
+    through ``plan_instance_calls``' few.  ``first_capacity``: ``capi.instance_overlaps``'; ``calls_made`` (a list) receives
+    the C calls made per call of the plan."""
+    labels_or_regions = list(labels_or_regions)
+    if _shape(seg_ref) != _shape(seg_pred):
+        raise ValueError(f'shape mismatch: reference {_shape(seg_ref)}, prediction {_shape(seg_pred)}')
+    shape, plan = _volume_shape(_shape(seg_ref)), plan_instance_calls(labels_or_regions)
+    if not checked:
+        for s in (seg_ref, seg_pred):
+            check_label_map(s)
+    u16 = not (_is_u8(seg_ref) and _is_u8(seg_pred))
+    kw = {} if first_capacity is None else {'first_capacity': first_capacity}
+    dev = next((s.device for s in (seg_ref, seg_pred) if isinstance(s, torch.Tensor) and s.device.type == 'cuda'), None) or _device()
+    out = {}
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ref, pred = to_device_labels(seg_ref, u16, dev), to_device_labels(seg_pred, u16, dev)
+        for idx in plan:
+            sets = [_members(labels_or_regions[k]) for k in idx]
+            table = np.full(max((v for s in sets for v in s), default=-1) + 1, -1, np.int32)
+            for g, s in enumerate(sets):
+                table[s] = g
+            n_out, records, calls = capi.instance_overlaps(ref.data_ptr(), pred.data_ptr(), u16, shape, table, len(idx), stream, **kw)
+            if calls_made is not None:
+                calls_made.append(calls)
+            for k, lists in zip(idx, overlaps_from_records(n_out, records, len(idx))):
+                out[labels_or_regions[k]] = lists
+    return {r: out[r] for r in labels_or_regions}
+
+
+def instance_metrics_of(ref_sizes, pred_sizes, pairs) -> dict:
+    """The host half: ``INSTANCE_KEYS`` from the component sizes of the reference (n of them) and of the prediction (m) and
+    the pair table ``(pred index, ref index, overlap)``.  A reference component is detected when anything overlaps it (the
+    autoPET rule); a predicted component that touches nothing is a false positive; ``FN_inst_vox`` / ``FP_inst_vox`` are the
+    voxels of the undetected / the false-positive components.  Panoptic quality counts the pairs with IoU > 0.5 (at most one
+    per component): ``RQ = tp / (tp + (m - tp) / 2 + (n - tp) / 2)``, ``SQ`` their mean IoU in the order of ``pairs`` (0.0
+    without one), ``PQ = SQ * RQ``.  Counts are np.int64, ratios np.float64; NaN where a denominator's side is empty.
+    Exact integers in, numpy expressions - no GPU call."""
+    ref_sizes = np.asarray(ref_sizes, dtype=np.int64).reshape(-1)
+    pred_sizes = np.asarray(pred_sizes, dtype=np.int64).reshape(-1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 3)
+    n, m = np.int64(len(ref_sizes)), np.int64(len(pred_sizes))
+    pairs = pairs[pairs[:, 2] > 0]
+    hit_ref, hit_pred = np.zeros(n, bool), np.zeros(m, bool)
+    hit_pred[pairs[:, 0]] = True
+    hit_ref[pairs[:, 1]] = True
+    nan = np.float64(np.nan)
+    out = {'n_inst_ref': n, 'n_inst_pred': m}
+    tp = out['inst_TP'] = hit_ref.sum(dtype=np.int64)
+    out['inst_FN'] = n - tp
+    fp = out['inst_FP'] = (~hit_pred).sum(dtype=np.int64)
+    recall = out['inst_recall'] = tp / n if n > 0 else nan
+    precision = out['inst_precision'] = (m - fp) / m if m > 0 else nan
+    if np.isnan(recall) or np.isnan(precision):
+        out['inst_F1'] = nan
+    elif precision + recall == 0:
+        out['inst_F1'] = np.float64(0.0)
+    else:
+        out['inst_F1'] = 2 * precision * recall / (precision + recall)
+    out['FN_inst_vox'] = ref_sizes[~hit_ref].sum(dtype=np.int64)
+    out['FP_inst_vox'] = pred_sizes[~hit_pred].sum(dtype=np.int64)
+    if n == 0 and m == 0:
+        out['PQ'] = out['SQ'] = out['RQ'] = nan
+        return out
+    union = pred_sizes[pairs[:, 0]] + ref_sizes[pairs[:, 1]] - pairs[:, 2]
+    matched = 2 * pairs[:, 2] > union                                   # IoU > 0.5 on the integers
+    q = matched.sum(dtype=np.int64)
+    rq = q / (q + 0.5 * (m - q) + 0.5 * (n - q))
+    sq = np.mean(pairs[matched, 2] / union[matched]) if q > 0 else np.float64(0.0)
+    out['PQ'] = sq * rq
+    out['SQ'] = sq
+    out['RQ'] = rq
+    return out
+
+
+def compute_instance_metrics(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], checked: bool = False) -> dict:
+    """``{label_or_region: {INSTANCE_KEYS}}`` of one case: ``instance_overlaps`` on the device, ``instance_metrics_of`` here."""
+    lists = instance_overlaps(seg_ref, seg_pred, labels_or_regions, checked)
+    return {r: instance_metrics_of(v['ref_sizes'], v['pred_sizes'], v['pairs']) for r, v in lists.items()}
 
 
 def compute_metrics(seg_ref, seg_pred, labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None,
                     reference_file=None, prediction_file=None, *, surface_metrics: bool = False, spacing=None,
-                    nsd_tolerance=1.0) -> dict:
+                    nsd_tolerance=1.0, instance_metrics: bool = False) -> dict:
     """compute_metrics (evaluate_predictions.py:88-118) with arrays in place of the files: numpy arrays or torch
     tensors of one shape (the reference's [1, X, Y, Z] included), integer labels 0..65535.  ``surface_metrics``: every
-    label's dict also gets ``compute_surface_metrics``' six keys for ``spacing`` (z, y, x) and ``nsd_tolerance``."""
+    label's dict also gets ``compute_surface_metrics``' six keys for ``spacing`` (z, y, x) and ``nsd_tolerance``.
+    ``instance_metrics``: and, behind them, ``compute_instance_metrics``' ``INSTANCE_KEYS``."""
     labels_or_regions = list(labels_or_regions)
     _check_ignore(labels_or_regions, ignore_label)
     _check_surface_request(surface_metrics, ignore_label, spacing)
+    _check_instance_request(instance_metrics, ignore_label)
     counts = confusion_counts(seg_ref, [seg_pred], count_classes(labels_or_regions), ignore_label)[0]
     metrics = metrics_from_counts(counts, labels_or_regions)
     if surface_metrics:
-        _with_surface(metrics, compute_surface_metrics(seg_ref, seg_pred, labels_or_regions, spacing, nsd_tolerance, checked=True))
+        _with_keys(metrics, compute_surface_metrics(seg_ref, seg_pred, labels_or_regions, spacing, nsd_tolerance, checked=True))
+    if instance_metrics:
+        _with_keys(metrics, compute_instance_metrics(seg_ref, seg_pred, labels_or_regions, checked=True))
     return case_result(metrics, reference_file, prediction_file)
 
 
 def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions: Sequence[LabelOrRegion],
                               ignore_label: Optional[int] = None, names: Optional[Sequence[str]] = None,
                               output_file: Optional[str] = None, *, surface_metrics: bool = False, spacing=None,
-                              nsd_tolerance=1.0) -> dict:
+                              nsd_tolerance=1.0, instance_metrics: bool = False) -> dict:
     """compute_metrics_on_folder (evaluate_predictions.py:121-177) on pairs of arrays: ``preds[i]`` is evaluated
     against ``refs[i]``; ``names[i]`` (optional) fills reference_file / prediction_file.  Returns
     ``{'metric_per_case', 'mean', 'foreground_mean'}``; writes it to ``output_file`` (.json) when given.
-    ``surface_metrics``: as ``compute_metrics``; ``spacing`` is one (z, y, x) for all cases or one per case."""
+    ``surface_metrics``, ``instance_metrics``: as ``compute_metrics``; ``spacing`` is one (z, y, x) for all cases or one per
+    case."""
     if output_file is not None and not output_file.endswith('.json'):
         raise ValueError('output_file should end with .json')
     if len(refs) != len(preds):
@@ -435,6 +601,7 @@ def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions
         raise ValueError('one name per case expected')
     labels_or_regions = list(labels_or_regions)
     _check_surface_request(surface_metrics, ignore_label, spacing)
+    _check_instance_request(instance_metrics, ignore_label)
     spacings = [None] * len(preds)
     if surface_metrics:
         spacings = [spacing] * len(preds) if np.ndim(spacing) == 1 else list(spacing)
@@ -442,7 +609,8 @@ def compute_metrics_on_arrays(refs: Sequence, preds: Sequence, labels_or_regions
             raise ValueError('one spacing for all cases or one per case expected')
     results = [compute_metrics(r, p, labels_or_regions, ignore_label,
                                None if names is None else names[i], None if names is None else names[i],
-                               surface_metrics=surface_metrics, spacing=spacings[i], nsd_tolerance=nsd_tolerance)
+                               surface_metrics=surface_metrics, spacing=spacings[i], nsd_tolerance=nsd_tolerance,
+                               instance_metrics=instance_metrics)
                for i, (r, p) in enumerate(zip(refs, preds))]
     summary = aggregate(results, labels_or_regions)
     if output_file is not None:
@@ -468,17 +636,20 @@ def _paired_files(folder_ref: str, folder_pred: str, file_ending: str, chill: bo
 
 def compute_metrics_on_files(files_ref: Sequence[str], files_pred: Sequence[str], image_reader_writer,
                              labels_or_regions: Sequence[LabelOrRegion], ignore_label: Optional[int] = None, *,
-                             surface_metrics: bool = False, spacing=None, nsd_tolerance=1.0) -> List[dict]:
+                             surface_metrics: bool = False, spacing=None, nsd_tolerance=1.0,
+                             instance_metrics: bool = False) -> List[dict]:
     """``compute_metrics`` (:88-118) for every pair of label files: both are decoded to labels on the device and counted
     by ``fnn_confusion_counts``; the reader thread inflates the next pair meanwhile.  A pair of different shapes raises a
     ValueError that names both files.  ``surface_metrics``: every label's dict also gets ``compute_surface_metrics``' six
     keys, measured with the spacing of the reference file; a prediction whose spacing differs (``np.allclose``) raises a
     ValueError that names both files.  ``spacing`` (z, y, x), when given, is used for every case in place of the files' own,
-    which are then not compared."""
+    which are then not compared.  ``instance_metrics``: and, behind them, ``compute_instance_metrics``' ``INSTANCE_KEYS``, from the
+    two maps already on the device."""
     from .label_folders import run_label_cases
     labels_or_regions = list(labels_or_regions)
     _check_ignore(labels_or_regions, ignore_label)
     _check_surface_request(surface_metrics, ignore_label, ())
+    _check_instance_request(instance_metrics, ignore_label)
     values = count_classes(labels_or_regions)
     cases = [[r, p] for r, p in zip(files_ref, files_pred)]
 
@@ -494,8 +665,10 @@ def compute_metrics_on_files(files_ref: Sequence[str], files_pred: Sequence[str]
             if spacing is None and (len(of_ref) != len(of_pred) or not np.allclose(of_ref, of_pred)):
                 raise ValueError(f'spacing mismatch: reference {cases[i][0]} has {tuple(of_ref)}, prediction {cases[i][1]} has '
                                  f'{tuple(of_pred)}')
-            _with_surface(metrics, compute_surface_metrics(ref, pred, labels_or_regions, of_ref if spacing is None else spacing,
-                                                           nsd_tolerance, checked=True))
+            _with_keys(metrics, compute_surface_metrics(ref, pred, labels_or_regions, of_ref if spacing is None else spacing,
+                                                        nsd_tolerance, checked=True))
+        if instance_metrics:
+            _with_keys(metrics, compute_instance_metrics(ref, pred, labels_or_regions, checked=True))
         return case_result(metrics, cases[i][0], cases[i][1]), None
 
     return run_label_cases(image_reader_writer, cases, run)
@@ -504,16 +677,17 @@ def compute_metrics_on_files(files_ref: Sequence[str], files_pred: Sequence[str]
 def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Optional[str], image_reader_writer,
                               file_ending: str, regions_or_labels: Sequence[LabelOrRegion], ignore_label: Optional[int] = None,
                               num_processes: int = DEFAULT_NUM_PROCESSES, chill: bool = True, *, surface_metrics: bool = False,
-                              spacing=None, nsd_tolerance=1.0) -> dict:
+                              spacing=None, nsd_tolerance=1.0, instance_metrics: bool = False) -> dict:
     """compute_metrics_on_folder (:121-173).  ``output_file`` must end with .json; can be None.  ``image_reader_writer``: an
     instance of this package's reader-writer classes.  ``num_processes`` is accepted and ignored: no process is started.
-    ``surface_metrics`` / ``spacing`` / ``nsd_tolerance``: as ``compute_metrics_on_files``."""
+    ``surface_metrics`` / ``spacing`` / ``nsd_tolerance`` / ``instance_metrics``: as ``compute_metrics_on_files``."""
     if output_file is not None:
         assert output_file.endswith('.json'), 'output_file should end with .json'
     files_ref, files_pred = _paired_files(folder_ref, folder_pred, file_ending, chill)
     regions_or_labels = list(regions_or_labels)
     results = compute_metrics_on_files(files_ref, files_pred, image_reader_writer, regions_or_labels, ignore_label,
-                                       surface_metrics=surface_metrics, spacing=spacing, nsd_tolerance=nsd_tolerance)
+                                       surface_metrics=surface_metrics, spacing=spacing, nsd_tolerance=nsd_tolerance,
+                                       instance_metrics=instance_metrics)
     result = aggregate(results, regions_or_labels)
     if output_file is not None:
         save_summary_json(result, output_file)
@@ -523,11 +697,11 @@ def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Op
 def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_file: str, plans_file: str,
                                output_file: Optional[str] = None, num_processes: int = DEFAULT_NUM_PROCESSES,
                                chill: bool = False, inflate_on_device: bool = False, *, surface_metrics: bool = False,
-                               spacing=None, nsd_tolerance=1.0):
+                               spacing=None, nsd_tolerance=1.0, instance_metrics: bool = False):
     """compute_metrics_on_folder2 (:177-196): labels or regions, ignore label, file ending and the reader-writer from
     ``dataset.json`` and the plans; ``output_file`` defaults to ``<folder_pred>/summary.json``.  ``inflate_on_device``: label
     files written with ``compress_on_device=True`` are inflated on the GPU (``NiftiIO(inflate_on_device=True)``).
-    ``surface_metrics`` / ``spacing`` / ``nsd_tolerance``: as ``compute_metrics_on_files``."""
+    ``surface_metrics`` / ``spacing`` / ``nsd_tolerance`` / ``instance_metrics``: as ``compute_metrics_on_files``."""
     from .imageio import determine_reader_writer_from_dataset_json
     from .label_folders import load_json
     from .plans import PlansManager
@@ -539,16 +713,17 @@ def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_f
     compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, dataset_json['file_ending'],
                               lm.foreground_regions if lm.has_regions else lm.foreground_labels, lm.ignore_label,
                               num_processes, chill=chill, surface_metrics=surface_metrics, spacing=spacing,
-                              nsd_tolerance=nsd_tolerance)
+                              nsd_tolerance=nsd_tolerance, instance_metrics=instance_metrics)
 
 
 def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: Sequence[int], output_file: Optional[str] = None,
                                      num_processes: int = DEFAULT_NUM_PROCESSES, ignore_label: Optional[int] = None,
                                      chill: bool = False, inflate_on_device: bool = False, *, surface_metrics: bool = False,
-                                     spacing=None, nsd_tolerance=1.0):
+                                     spacing=None, nsd_tolerance=1.0, instance_metrics: bool = False):
     """compute_metrics_on_folder_simple (:199-212): the file ending is that of the first reference file (``.nii.gz``
     whole, where the reference's ``os.path.splitext`` would keep ``.gz`` and then match the same files).
-    ``inflate_on_device``, ``surface_metrics``, ``spacing``, ``nsd_tolerance``: as ``compute_metrics_on_folder2``."""
+    ``inflate_on_device``, ``surface_metrics``, ``spacing``, ``nsd_tolerance``, ``instance_metrics``: as
+    ``compute_metrics_on_folder2``."""
     from .imageio import determine_reader_writer_from_file_ending
     from .label_folders import subfiles
     example_file = subfiles(folder_ref, join=True)[0]
@@ -558,4 +733,4 @@ def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: 
         output_file = os.path.join(folder_pred, 'summary.json')
     compute_metrics_on_folder(folder_ref, folder_pred, output_file, rw, file_ending, labels, ignore_label=ignore_label,
                               num_processes=num_processes, chill=chill, surface_metrics=surface_metrics, spacing=spacing,
-                              nsd_tolerance=nsd_tolerance)
+                              nsd_tolerance=nsd_tolerance, instance_metrics=instance_metrics)

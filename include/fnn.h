@@ -430,6 +430,29 @@ int fnn_surface_count(const void *ref, const void *pred, int label_dtype, const 
 int fnn_surface_distances(const void *ref, const void *pred, int label_dtype, const int64_t shape[3], const uint8_t *member,
                           int n_table, int n_regions, const double spacing[3], double *sq_dist, int64_t cap, void *stream);
 
+/* The connected components of a reference and a predicted label map and their overlaps (additive in ABI 4), for the
+ * lesion-wise metrics of every label or region of a case (detection F1, false-positive / false-negative lesion volume,
+ * panoptic quality); the reference has no such function.  ref, pred: device label maps [shape[0]][shape[1]][shape[2]] of
+ * label_dtype (FNN_LABEL_U8 / U16), aligned to their element.  group_of_label, n_table, n_groups: as
+ * fnn_keep_largest_components - two 26-neighbours are one component iff their values map to the same set; 1..1024 sets;
+ * everything outside the volume is background.  A piece is a 26-connected component of the joint map J[v] = g + 1 where
+ * the values of both maps at v belong to set g, else 0; every piece lies in exactly one component of each map, so the
+ * overlap of a (pred component, ref component) pair is the sum of its pieces.
+ * n_out (host) always receives {ref components, pred components, pieces}.  records (device, 4-byte aligned, room for cap
+ * records of three int32) is written only when cap >= n_out[0] + n_out[1] + n_out[2]; otherwise nothing is written and the
+ * call still returns 0 - the caller compares and calls again.  In this order: the ref components, then the pred components,
+ * each as (set, root, size), root being the linear index of the component's first voxel in raster order, ascending in root;
+ * then the pieces as (root of their pred component, root of their ref component, size), ascending in the piece's own first
+ * voxel.  No atomic output cursor: the same input gives the same bytes.  Synchronises the stream.
+ * FNN_E_INVALID before any launch, with a message: NULL or host pointers for the maps or records, an unknown label dtype,
+ * n_groups outside 1..1024, a negative n_table, a table entry outside -1 .. n_groups - 1, a negative extent, a misaligned
+ * pointer, a negative cap, a NULL n_out; FNN_E_UNSUPPORTED: more than 2^31 - 1 voxels.  A volume without voxels gives zeros.
+ * Scratch, allocated inside the call: 16 B per voxel (the parents of the three labellings and one size array they use in
+ * turn) + 12 B per 1024 voxels (the compaction's scan) + 12 B + 4 B per table value. */
+int fnn_instance_overlaps(const void *ref, const void *pred, int label_dtype, const int64_t shape[3],
+                          const int32_t *group_of_label, int n_table, int n_groups, int32_t *records, int64_t cap,
+                          int64_t n_out[3], void *stream);
+
 /* The voxels of an image file as the file holds them -> float32 (additive in ABI 4): what the reference's
  * NibabelIO.read_images ends with (imageio/nibabel_reader_writer.py:56 and :89 - get_fdata() in float64, then
  * np.vstack(..., dtype=float32, casting='unsafe')) for one file, without the host cast.  raw: device pointer to the first

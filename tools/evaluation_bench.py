@@ -9,6 +9,11 @@ Kernel times: run it under rocprofv3 --kernel-trace --stats.
 prediction is the reference with perturbed boundaries, the scipy route for three labels on this machine's CPU, and
 compute_metrics_on_folder with and without surface_metrics; writes profiles/r26_surface_metrics.txt unless --out names
 another file.
+
+--section instance: fnn_instance_overlaps on the same 60-ellipsoid pair and on a pair of 20000 small lesions - the call, its
+three labellings against one fnn_keep_largest_components on the same map, the scipy route (two labellings + np.unique of the
+paired ids) for one label on this machine's CPU, and compute_metrics_on_folder with and without instance_metrics; writes
+profiles/r27_instance_metrics.txt unless --out names another file.
 """
 import argparse
 import os
@@ -170,9 +175,122 @@ def surface_section(a):
         fh.write(text + '\n')
 
 
+def lesion_map(n, seed=27, lesions=20000, keep=1.0, extra=0):
+    """``lesions`` ellipsoids of label 1 with semi-axes 1..3 at random places: many small components.  ``keep`` < 1 leaves a
+    random part of them out and ``extra`` adds others (a prediction with misses and false positives); the same seed places
+    the same lesions."""
+    rng = np.random.default_rng(seed)
+    centres, radii = rng.integers(4, n - 4, (lesions, 3)), rng.integers(1, 4, (lesions, 3))
+    pick = np.random.default_rng(seed + 1)
+    kept = pick.random(lesions) < keep
+    centres = np.concatenate([centres[kept], pick.integers(4, n - 4, (extra, 3))])
+    radii = np.concatenate([radii[kept], pick.integers(1, 4, (extra, 3))])
+    seg = np.zeros((n, n, n), np.uint8)
+    for c, r in zip(centres, radii):
+        z, y, x = np.ogrid[tuple(slice(-int(v), int(v) + 1) for v in r)]
+        inside = (z / r[0]) ** 2 + (y / r[1]) ** 2 + (x / r[2]) ** 2 <= 1.0
+        seg[tuple(slice(int(a - b), int(a + b) + 1) for a, b in zip(c, r))][inside] = 1
+    return seg
+
+
+def instance_section(a):
+    import tempfile
+    from scipy import ndimage as ndi
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import evaluation as ev
+    from fast_nnunet_amd.imageio import NiftiIO
+    dev = torch.device('cuda', 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    organs = organ_map(a.n)
+    lesions = lesion_map(a.n)
+    maps = {'organs': (organs, perturbed_boundaries(organs, 7), list(range(1, 61))),
+            'lesions': (lesions, np.roll(lesion_map(a.n, keep=0.8, extra=2000), 1, axis=2), [1])}
+    lines = [f'evaluation_bench --section instance: {a.n}^3 uint8 pairs; device {torch.cuda.get_device_name(dev)}',
+             '  organs: 60 ellipsoids (organ_map), prediction = reference with boundaries moved by one voxel in half of the 16^3 blocks',
+             '  lesions: 20000 ellipsoids of label 1 with semi-axes 1..3 (lesion_map), prediction = 80 % of them and 2000 others, '
+             'rolled by one voxel along x',
+             f'device calls: median (min, max) of {a.reps} after one warm-up, events around the call (scratch allocation, launches '
+             f'and the synchronising copy-back of the counts included)']
+    full = np.ones((3, 3, 3), int)
+    for name, (ref, pred, labels) in maps.items():
+        table = np.full(max(labels) + 1, -1, np.int32)
+        table[labels] = np.arange(len(labels))
+        d_ref, d_pred = torch.from_numpy(ref).to(dev), torch.from_numpy(pred).to(dev)
+        probe = torch.empty(3, dtype=torch.int32, device=dev)
+        n_out = capi.instance_overlaps_call(d_ref.data_ptr(), d_pred.data_ptr(), False, ref.shape, table, len(labels),
+                                            probe.data_ptr(), 0, stream)
+        total = int(n_out.sum())
+        buf = torch.empty(max(total, 1) * 3, dtype=torch.int32, device=dev)
+        lines.append(f'{name}: {len(labels)} label(s); foreground voxels {int((ref > 0).sum())} / {int((pred > 0).sum())}; components '
+                     f'{int(n_out[0])} ref, {int(n_out[1])} pred, {int(n_out[2])} pieces')
+        for what, cap in (('records written', total), ('cap 0: the labellings and the counts only', 0)):
+            ms, lo, hi, _ = _events(dev, lambda: capi.instance_overlaps_call(d_ref.data_ptr(), d_pred.data_ptr(), False, ref.shape, table,
+                                                                             len(labels), buf.data_ptr(), cap, stream), a.reps)
+            lines.append(f'  fnn_instance_overlaps, {what}: {ms:.2f} ms (min {lo:.2f} max {hi:.2f})')
+        ts = []
+        for r in range(a.reps + 1):
+            work = d_ref.clone()
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            capi.keep_largest_components(work.data_ptr(), False, ref.shape, table, len(labels), 0, stream)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            if r:
+                ts.append(e0.elapsed_time(e1))
+        lines.append(f'  one fnn_keep_largest_components on the reference map (one labelling, same sets): {np.median(ts):.2f} ms (min '
+                     f'{min(ts):.2f} max {max(ts):.2f})')
+        t0 = time.perf_counter()
+        got = ev.compute_instance_metrics(d_ref, d_pred, labels, checked=True)
+        lines.append(f'  compute_instance_metrics (call, download of {total * 12 / 1e6:.2f} MB, numpy merge and metrics of {len(labels)} '
+                     f'label(s)): {(time.perf_counter() - t0) * 1e3:.1f} ms')
+        # the host route on this machine's CPU for one label: two labellings and the unique pairs
+        label = labels[len(labels) // 2]
+        t0 = time.perf_counter()
+        ids_r, n_r = ndi.label(ref == label, full)
+        ids_p, n_p = ndi.label(pred == label, full)
+        both = (ids_r > 0) & (ids_p > 0)
+        key, count = np.unique(ids_p[both].astype(np.int64) * (n_r + 1) + ids_r[both], return_counts=True)
+        t_host = time.perf_counter() - t0
+        mine = ev.instance_overlaps(d_ref, d_pred, [label], checked=True)[label]
+        same = (len(mine['ref_sizes']) == n_r and len(mine['pred_sizes']) == n_p and
+                np.array_equal(mine['pairs'][:, 2], count) and
+                np.array_equal(mine['pairs'][:, 0] * (n_r + 1) + mine['pairs'][:, 1], key - (n_r + 1) - 1))
+        lines.append(f'  host route for label {label} alone (scipy.ndimage.label with the full structure on both masks + np.unique of the '
+                     f'paired ids) on this machine\'s CPU: {t_host:.2f} s; {n_r} / {n_p} components, {len(key)} pairs; the device\'s lists '
+                     f'are the same: {same}')
+        m = got[label]
+        lines.append(f'  label {label}: inst_F1 {m["inst_F1"]:.4f} recall {m["inst_recall"]:.4f} precision {m["inst_precision"]:.4f} '
+                     f'FN_inst_vox {m["FN_inst_vox"]} FP_inst_vox {m["FP_inst_vox"]} PQ {m["PQ"]:.4f} SQ {m["SQ"]:.4f} RQ {m["RQ"]:.4f}')
+        print('\n'.join(lines[-7:]), flush=True)
+
+    # the folder command with and without the flag
+    rw = NiftiIO()
+    props = {'nibabel_stuff': {'original_affine': np.eye(4)}}
+    for name, (ref, pred, labels) in maps.items():
+        with tempfile.TemporaryDirectory() as tmp:
+            fr, fp = os.path.join(tmp, 'ref'), os.path.join(tmp, 'pred')
+            os.makedirs(fr), os.makedirs(fp)
+            for c in range(a.cases):
+                rw.write_seg(np.roll(ref, 3 * c, axis=0), os.path.join(fr, f'case{c}.nii.gz'), props)
+                rw.write_seg(np.roll(pred, 3 * c, axis=0), os.path.join(fp, f'case{c}.nii.gz'), props)
+            for flag in (False, True):
+                ev.compute_metrics_on_folder(fr, fp, None, rw, '.nii.gz', labels, instance_metrics=flag)        # warm-up
+                t0 = time.perf_counter()
+                summary = ev.compute_metrics_on_folder(fr, fp, None, rw, '.nii.gz', labels, instance_metrics=flag)
+                t = time.perf_counter() - t0
+                lines.append(f'compute_metrics_on_folder, {name}, {a.cases} cases of {a.n}^3 (files written by zlib, inflated on the host), '
+                             f'instance_metrics={flag}: {t / a.cases * 1e3:.0f} ms per case; keys per label {len(summary["mean"][labels[0]])}')
+    text = '\n'.join(lines)
+    print(text)
+    out = a.out or os.path.join(ROOT, 'profiles', 'r27_instance_metrics.txt')
+    with open(out, 'w') as fh:
+        fh.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--section', choices=('counts', 'surface'), default='counts')
+    ap.add_argument('--section', choices=('counts', 'surface', 'instance'), default='counts')
     ap.add_argument('--uncropped-labels', type=int, default=3, help='surface: of the three scipy labels, how many also run uncropped')
     ap.add_argument('--n', type=int, default=512)
     ap.add_argument('--cases', type=int, default=3)
@@ -182,6 +300,8 @@ def main():
     a = ap.parse_args()
     if a.section == 'surface':
         return surface_section(a)
+    if a.section == 'instance':
+        return instance_section(a)
     from fast_nnunet_amd import capi
     from fast_nnunet_amd import evaluation as ev
     from fast_nnunet_amd import postprocessing as pp
