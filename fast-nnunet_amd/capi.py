@@ -73,7 +73,7 @@ class Profile(C.Structure):
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
            'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
-           'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
+           'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
 
@@ -180,6 +180,11 @@ def load_library() -> C.CDLL:
                                         vp, i32, L3, I3, I3, f32p, C.POINTER(C.c_int)]
         lib.fnn_op_patch_acc.argtypes = [i32, f32p, i32, I3, i32, u16p, vp, i32, L3, I3]
         lib.fnn_op_patch_input.argtypes = [i32, f32p, i32, i32, L3, i32, I3, I3, I3, i32, i32, u16p]
+    if hasattr(lib, 'fnn_op_stem'):                                # (absent from an older build picked with FNN_LIB for an A-B)
+        f64p = C.POINTER(C.c_double)
+        lib.fnn_op_stem.argtypes = [i32, f32p, i32, i32, L3, i32, I3, I3, I3, f32p, f32p, i32, I3, f32p, f64p]
+        lib.fnn_op_conv_fused.argtypes = [i32, i32, i32, I3, f32p, i32, L3, I3, I3, f32p, i32, I3, f32p, f32p, f32p, C.c_float,
+                                          f32p, f32p, f32p, f32p, C.c_float, f32p, f32p, I3, f32p, f64p]
     lib.fnn_op_quotient_check.argtypes = [i32, C.POINTER(C.c_uint64)]
     lib.fnn_op_last_kernels.argtypes = [C.c_char_p, i32]
     lib.fnn_clock_probe_start.argtypes = [i32, C.c_double, C.POINTER(C.c_void_p)]
@@ -719,6 +724,68 @@ def op_patch_input(vol, origins, patch, cpad, flips=(0, 0, 0), chunk_major=False
                                  origins.ctypes.data_as(C.POINTER(C.c_int)), _i3(flips), _i3(patch), int(cpad), int(chunk_major),
                                  _u16p(out)), lib)
     return out
+
+
+FUSE_STEM, FUSE_TCONV = 1, 2
+
+
+def _f64p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def op_stem(vol, origins, patch, w, bias, flips=(0, 0, 0), want_stats=False, device=0):
+    """launch_stem_mfma on patch windows of vol [C,X,Y,Z] (one volume for every item) or [n,C,X,Y,Z] float32 at origins [n,3]:
+    w [cout,C,kd,kh,kw] -> y [n,cout,*patch] float32 (and the statistics [n,cout,2])."""
+    lib = load_library()
+    vol = np.ascontiguousarray(vol, np.float32)
+    origins = np.ascontiguousarray(origins, np.int32).reshape(-1, 3)
+    w, bias = np.ascontiguousarray(w, np.float32), _opt_f32(bias)
+    n, n_vol, c, cout = origins.shape[0], 1 if vol.ndim == 4 else vol.shape[0], vol.shape[-4], w.shape[0]
+    assert w.shape[1] == c
+    y = np.zeros((n, cout, *patch), np.float32)
+    stats = np.zeros((n, cout, 2), np.float64) if want_stats else None
+    check(lib.fnn_op_stem(device, _f32p(vol), n_vol, c, (C.c_longlong * 3)(*vol.shape[-3:]), n,
+                          origins.ctypes.data_as(C.POINTER(C.c_int)), _i3(flips), _i3(patch), _f32p(w), _f32p(bias), cout,
+                          _i3(w.shape[2:]), _f32p(y), _f64p(stats)), lib)
+    return (y, stats) if want_stats else y
+
+
+def op_conv_fused_stem(vol, origins, patch, stem_w, stem_bias, stem_norm, stem_slope, w, bias, flips=(0, 0, 0), device=0):
+    """fnn_op_conv_fused, mode FUSE_STEM: vol [1,X,Y,Z] or [n,1,X,Y,Z]; stem_w [16,1,*k], stem_norm = (gamma, beta); w [16,16,*k]
+    -> (y [n,16,*patch], statistics [n,16,2])."""
+    lib = load_library()
+    vol = np.ascontiguousarray(vol, np.float32)
+    origins = np.ascontiguousarray(origins, np.int32).reshape(-1, 3)
+    stem_w, w = np.ascontiguousarray(stem_w, np.float32), np.ascontiguousarray(w, np.float32)
+    stem_bias, bias, g, b = _opt_f32(stem_bias), _opt_f32(bias), _opt_f32(stem_norm[0]), _opt_f32(stem_norm[1])
+    n, n_vol = origins.shape[0], 1 if vol.ndim == 4 else vol.shape[0]
+    assert vol.shape[-4] == 1 and stem_w.shape[:2] == (16, 1) and w.shape[:2] == (16, 16) and stem_w.shape[2:] == w.shape[2:]
+    y, stats = np.zeros((n, 16, *patch), np.float32), np.zeros((n, 16, 2), np.float64)
+    check(lib.fnn_op_conv_fused(device, FUSE_STEM, n, _i3(patch), _f32p(vol), n_vol, (C.c_longlong * 3)(*vol.shape[-3:]),
+                                origins.ctypes.data_as(C.POINTER(C.c_int)), _i3(flips), None, 0, None, None, None, None, 1.0,
+                                _f32p(stem_w), _f32p(stem_bias), _f32p(g), _f32p(b), stem_slope, _f32p(w), _f32p(bias),
+                                _i3(w.shape[2:]), _f32p(y), _f64p(stats)), lib)
+    return y, stats
+
+
+def op_conv_fused_tconv(low, low_norm, low_slope, tw, tbias, tstride, skip, skip_norm, skip_slope, w, bias, device=0):
+    """fnn_op_conv_fused, mode FUSE_TCONV: low [n,16|32,Dl,Hl,Wl] (norm = (gamma, beta) or None), tw [low_c,16,*tstride];
+    skip [n,16,D,H,W]; w [16,32,1,3,3] over (up, skip) -> (y [n,16,D,H,W], statistics [n,16,2])."""
+    lib = load_library()
+    low, skip = np.ascontiguousarray(low, np.float32), np.ascontiguousarray(skip, np.float32)
+    tw, w = np.ascontiguousarray(tw, np.float32), np.ascontiguousarray(w, np.float32)
+    tbias, bias = _opt_f32(tbias), _opt_f32(bias)
+    lg, lb = (_opt_f32(low_norm[0]), _opt_f32(low_norm[1])) if low_norm is not None else (None, None)
+    sg, sb = (_opt_f32(skip_norm[0]), _opt_f32(skip_norm[1])) if skip_norm is not None else (None, None)
+    n, low_c = low.shape[:2]
+    dims = skip.shape[2:]
+    assert tuple(dims) == tuple(low.shape[2 + i] * tstride[i] for i in range(3)) and skip.shape[:2] == (n, 16)
+    assert tw.shape == (low_c, 16, *tstride) and w.shape[:2] == (16, 32)
+    y, stats = np.zeros((n, 16, *dims), np.float32), np.zeros((n, 16, 2), np.float64)
+    check(lib.fnn_op_conv_fused(device, FUSE_TCONV, n, _i3(dims), None, 0, None, None, None, _f32p(low), low_c, _i3(tstride),
+                                _f32p(skip), _f32p(sg), _f32p(sb), skip_slope, _f32p(tw), _f32p(tbias), _f32p(lg), _f32p(lb),
+                                low_slope, _f32p(w), _f32p(bias), _i3(w.shape[2:]), _f32p(y), _f64p(stats)), lib)
+    return y, stats
 
 
 def op_last_kernels():

@@ -490,6 +490,186 @@ int fnn_op_patch_input(int device, const float *vol, int n_vol, int c, const lon
     return 0;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The stem of a batch of patch windows as forward_batch launches it: the fp32 volumes, the origins, StemParams with p.w in
+// [C][taps][Cout] and the stem_mfma_pack fragments, one zeroed statistics row per slot
+struct StemHolder {
+    DevBuf vol, org, w, bias, frag, stats;
+    StemParams p{};
+    int cop = 0, slots = 0;
+    size_t P = 0;
+};
+
+int make_stem(StemHolder &h, const float *vol, int n_vol, int c, const long long vdim[3], int n, const int *origins, const int flips[3],
+              const int patch[3], const float *w, const float *bias, int cout, const int k[3]) {
+    if (!vol || !vdim || !origins || !flips || !patch || !w || !k || n < 1 || c < 1 || cout < 1) return FNN_E_INVALID;
+    if (n_vol != 1 && n_vol != n) return FNN_E_INVALID;
+    for (int b = 0; b < n; ++b)
+        for (int i = 0; i < 3; ++i)
+            if (patch[i] < 1 || origins[b * 3 + i] < 0 || (long long)origins[b * 3 + i] + patch[i] > vdim[i]) return FNN_E_INVALID;
+    h.cop = pad16(cout);
+    if (!stem_mfma_ok(c, k[0], k[1], k[2], h.cop)) return FNN_E_UNSUPPORTED;
+    const int T = k[0] * k[1] * k[2];
+    const size_t vvox = (size_t)vdim[0] * vdim[1] * vdim[2];
+    h.P = (size_t)patch[0] * patch[1] * patch[2];
+    h.slots = stem_mfma_stats_slots(patch[0], patch[1], patch[2]);
+    std::vector<float> wt((size_t)c * T * h.cop, 0.f), bp(h.cop, 0.f);
+    for (int ci = 0; ci < c; ++ci)
+        for (int t = 0; t < T; ++t)
+            for (int co = 0; co < cout; ++co) wt[((size_t)ci * T + t) * h.cop + co] = w[((size_t)co * c + ci) * T + t];
+    if (bias) for (int i = 0; i < cout; ++i) bp[i] = bias[i];
+    std::vector<uint16_t> frag((size_t)(h.cop / 16) * stem_mfma_ksteps(c, T) * 512, 0);
+    stem_mfma_pack(w, c, T, cout, h.cop, frag.data());
+    const size_t stat_bytes = (size_t)n * h.slots * h.cop * 16;
+    if (!upload(h.vol, vol, (size_t)n_vol * c * vvox * 4) || !upload(h.org, origins, (size_t)n * 3 * 4) || !upload(h.w, wt.data(), wt.size() * 4) ||
+        !upload(h.bias, bp.data(), bp.size() * 4) || !upload(h.frag, frag.data(), frag.size() * 2) || !h.stats.alloc(stat_bytes)) return FNN_E_HIP;
+    (void)hipMemset(h.stats.p, 0, stat_bytes);
+    StemParams &p = h.p;
+    p.vol = h.vol.as<float>(); p.vol_batch_stride = n_vol == 1 ? 0 : (long long)c * (long long)vvox; p.C = c;
+    p.X = vdim[0]; p.Y = vdim[1]; p.Z = vdim[2];
+    p.origins = h.org.as<int>();
+    p.flip_d = flips[0]; p.flip_h = flips[1]; p.flip_w = flips[2];
+    p.PD = patch[0]; p.PH = patch[1]; p.PW = patch[2];
+    p.kd = k[0]; p.kh = k[1]; p.kw = k[2];
+    p.Cout = h.cop;
+    p.w = h.w.as<float>(); p.bias = h.bias.as<float>();
+    p.stats_out = h.stats.as<double>();
+    return FNN_OK;
+}
+
+// statistics rows [n][slots][cop][2] on the device -> host [n][cout][2], summed over the slot rows
+void sum_stat_rows(const DevBuf &dst, int n, size_t slots, int cout, int cop, double *stats_out) {
+    std::vector<double> hs((size_t)n * slots * cop * 2);
+    (void)hipMemcpy(hs.data(), dst.p, hs.size() * 8, hipMemcpyDeviceToHost);
+    for (int b = 0; b < n; ++b)
+        for (int co = 0; co < cout; ++co) {
+            double a = 0, q = 0;
+            for (size_t r = 0; r < slots; ++r) {
+                a += hs[(((size_t)b * slots + r) * cop + co) * 2];
+                q += hs[(((size_t)b * slots + r) * cop + co) * 2 + 1];
+            }
+            stats_out[((size_t)b * cout + co) * 2] = a;
+            stats_out[((size_t)b * cout + co) * 2 + 1] = q;
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+int fnn_op_stem(int device, const float *vol, int n_vol, int c, const long long vdim[3],
+                int n, const int *origins, const int flips[3], const int patch[3],
+                const float *w, const float *bias, int cout, const int k[3], float *y, double *stats_out) {
+    if (!y) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    FnnOpKlog klog;
+    StemHolder s;
+    if (const int rc = make_stem(s, vol, n_vol, c, vdim, n, origins, flips, patch, w, bias, cout, k)) return rc;
+    DevBuf dout;
+    if (!dout.alloc((size_t)n * s.P * s.cop * 2)) return FNN_E_HIP;
+    (void)hipMemset(dout.p, 0, (size_t)n * s.P * s.cop * 2);
+    s.p.out = dout.as<f16>();
+    const int rc = launch_stem_mfma(s.p, s.frag.as<f16>(), n, 0);
+    if (rc != 0) return rc == -1 ? FNN_E_UNSUPPORTED : FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    std::vector<uint16_t> ho((size_t)n * s.P * s.cop);
+    (void)hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost);
+    from_device_layout(ho, n, cout, s.cop, s.P, false, y);
+    if (stats_out) sum_stat_rows(s.stats, n, (size_t)s.slots, cout, s.cop, stats_out);
+    return 0;
+}
+
+int fnn_op_conv_fused(int device, int mode, int n, const int dims[3],
+                      const float *vol, int n_vol, const long long vdim[3], const int *origins, const int flips[3],
+                      const float *low, int low_c, const int tstride[3],
+                      const float *skip, const float *skip_gamma, const float *skip_beta, float skip_slope,
+                      const float *pw, const float *pbias, const float *pgamma, const float *pbeta, float pslope,
+                      const float *w, const float *bias, const int k[3], float *y, double *stats_out) {
+    if ((mode != FUSE_STEM && mode != FUSE_TCONV) || !dims || !pw || !w || !k || !y || n < 1) return FNN_E_INVALID;
+    for (int i = 0; i < 3; ++i) if (dims[i] < 1 || (k[i] != 1 && k[i] != 3)) return FNN_E_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return FNN_E_HIP;
+    FnnOpKlog klog;
+    const size_t vox = (size_t)dims[0] * dims[1] * dims[2];
+    const int cop = 16;
+    DevBuf dout, dst;
+    if (!dout.alloc((size_t)n * vox * cop * 2)) return FNN_E_HIP;
+    (void)hipMemset(dout.p, 0, (size_t)n * vox * cop * 2);
+    ThinParams tp{};
+    ConvParams &p = tp.c;
+    tp.fuse = mode;
+    p.N = n; p.Di = p.Do = dims[0]; p.Hi = p.Ho = dims[1]; p.Wi = p.Wo = dims[2];
+    p.kd = k[0]; p.kh = k[1]; p.kw = k[2]; p.sd = p.sh = p.sw = 1;
+    p.pd = (k[0] - 1) / 2; p.ph = (k[1] - 1) / 2; p.pw = (k[2] - 1) / 2;
+    p.Cout = cop;
+    tp.tsd = tp.tsh = tp.tsw = 1;
+    StemHolder s;
+    SrcHolder slow, sskip;
+    DevBuf dg, db, dss, dssh, dfw, dfb;
+    int cin_real[2] = {16, 0};
+    if (mode == FUSE_STEM) {
+        // the stem's statistics pass, their (scale, shift) rows, then the consumer that recomputes the stem while it stages
+        if (!pgamma || !pbeta) return FNN_E_INVALID;
+        if (const int rc = make_stem(s, vol, n_vol, 1, vdim, n, origins, flips, dims, pw, pbias, 16, k)) return rc;
+        s.p.out = nullptr;
+        const int rc = launch_stem_mfma(s.p, s.frag.as<f16>(), n, 0);
+        if (rc != 0) return rc == -1 ? FNN_E_UNSUPPORTED : FNN_E_HIP;
+        if (!upload(dg, pgamma, 16 * 4) || !upload(db, pbeta, 16 * 4) || !dss.alloc((size_t)n * 16 * 8) || !dssh.alloc((size_t)n * 16 * 4)) return FNN_E_HIP;
+        StatsFinalizeParams q{};
+        q.stats = s.stats.as<double>(); q.gamma = dg.as<float>(); q.beta = db.as<float>();
+        q.ss = dss.as<float>(); q.ssh = dssh.as<unsigned short>(); q.C = 16; q.nrep = s.slots; q.inv_count = 1.f / (float)vox; q.eps = 1e-5f;
+        if (launch_stats_finalize(q, n, 0) != 0) return FNN_E_HIP;
+        p.n_src = 1; p.chunks = 1;
+        p.src[0].ptr = dout.as<f16>();                                // the stem's output is virtual: never read
+        p.src[0].C = 16; p.src[0].ss = dss.as<float>(); p.src[0].ssh = dssh.as<unsigned short>(); p.src[0].slope = pslope;
+        p.src[1] = p.src[0]; p.src[1].C = 0;
+        tp.fw = s.frag.as<f16>(); tp.fbias = s.p.bias;
+        tp.vol = s.p.vol; tp.vol_batch_stride = s.p.vol_batch_stride; tp.Y = s.p.Y; tp.Z = s.p.Z;
+        tp.origins = s.p.origins; tp.flip_d = s.p.flip_d; tp.flip_h = s.p.flip_h; tp.flip_w = s.p.flip_w;
+        tp.fss = dss.as<float>(); tp.fslope = pslope;
+    } else {
+        if (!low || !skip || !tstride || (low_c != 16 && low_c != 32)) return FNN_E_INVALID;
+        for (int i = 0; i < 3; ++i) if (tstride[i] < 1 || tstride[i] > 2 || dims[i] % tstride[i]) return FNN_E_INVALID;
+        tp.tsd = tstride[0]; tp.tsh = tstride[1]; tp.tsw = tstride[2];
+        tp.Dl = dims[0] / tp.tsd; tp.Hl = dims[1] / tp.tsh; tp.Wl = dims[2] / tp.tsw;
+        const int taps = tp.tsd * tp.tsh * tp.tsw, ksteps = (low_c + 31) / 32;
+        if (!make_src(slow, low, n, low_c, (size_t)tp.Dl * tp.Hl * tp.Wl, pgamma, pbeta, pslope, true)) return FNN_E_HIP;
+        if (!make_src(sskip, skip, n, 16, vox, skip_gamma, skip_beta, skip_slope, true)) return FNN_E_HIP;
+        std::vector<uint16_t> fw((size_t)taps * ksteps * 512, 0);
+        tconv_pack_weights(pw, low_c, 16, 16, taps, ksteps, fw.data());
+        std::vector<float> fb(16, 0.f);
+        if (pbias) for (int i = 0; i < 16; ++i) fb[i] = pbias[i];
+        if (!upload(dfw, fw.data(), fw.size() * 2) || !upload(dfb, fb.data(), 16 * 4)) return FNN_E_HIP;
+        p.n_src = 2; p.chunks = 2;
+        p.src[0] = sskip.d; p.src[1] = sskip.d;                       // src[0], the transposed conv's output, is virtual: never read
+        tp.low = slow.d;
+        tp.fw = dfw.as<f16>(); tp.fbias = dfb.as<float>();
+        cin_real[1] = 16;
+    }
+    ConvChoice cc;
+    if (!conv_choose(tp, ConvOverrides::from_env(), cc)) return FNN_E_UNSUPPORTED;
+    const size_t slots = (size_t)cc.stats_slots;
+    std::vector<uint16_t> wp(conv_packed_halves(cc, cop), 0);
+    conv_pack_weights(p, cc, 16, cin_real, w, wp.data(), nullptr);
+    std::vector<float> bp(cop, 0.f);
+    if (bias) for (int i = 0; i < 16; ++i) bp[i] = bias[i];
+    DevBuf dw, dbias;
+    if (!dw.alloc(fnn_weight_alloc_bytes(wp.size())) || !upload(dbias, bp.data(), cop * 4) || !dst.alloc((size_t)n * slots * cop * 16)) return FNN_E_HIP;
+    (void)hipMemcpy(dw.p, wp.data(), wp.size() * 2, hipMemcpyHostToDevice);
+    (void)hipMemset(dst.p, 0, (size_t)n * slots * cop * 16);
+    p.wpk = dw.as<f16>(); p.bias = dbias.as<float>(); p.out = dout.as<f16>(); p.stats_out = dst.as<double>();
+    const int rc = launch_conv(tp, cc, 0);
+    if (rc != 0) return rc == -1 ? FNN_E_UNSUPPORTED : FNN_E_HIP;
+    if (hipDeviceSynchronize() != hipSuccess) return FNN_E_HIP;
+    std::vector<uint16_t> ho((size_t)n * vox * cop);
+    (void)hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost);
+    from_device_layout(ho, n, 16, cop, vox, false, y);
+    if (stats_out) sum_stat_rows(dst, n, slots, 16, cop, stats_out);
+    return 0;
+}
+
 int fnn_op_last_kernels(char *buf, int cap) {
     std::string all;
     for (const std::string &k : g_op_kernels) { all += k; all += '\n'; }

@@ -723,6 +723,30 @@ int fnn_op_patch_acc(int device, const float *patch_buf, int heads, const int pa
 int fnn_op_patch_input(int device, const float *vol, int n_vol, int c, const long long vdim[3],
                        int n, const int *origins, const int flips[3], const int patch[3], int cpad, int chunk_major,
                        unsigned short *out);
+/* fnn_op_stem: the network's first conv on patch windows of the fp32 volumes vol [n_vol][c][X][Y][Z] (n_vol = 1 or n) at
+ *   origins [n][3], mirrored by `flips` (the output is not mirrored back), zero padding at the PATCH border; weights
+ *   w [cout][c][kd][kh][kw], bias [cout] (NULL = 0), packed as the engine packs them; the launcher picks the kernel.
+ *   -> y [n][cout][PD][PH][PW] and, with stats_out, [n][cout][2] = (sum, sum of squares) of the rounded outputs summed over
+ *   the slot rows.
+ * fnn_op_conv_fused: a 16-channel stride-1 conv (weights w, bias, kernel k) that recomputes its producer while it stages, as
+ *   the engine runs the pair.  dims = the consumer's (input = output) size.
+ *   mode 1 (stem): the producer is the one-channel stem (pw [16][1][k], pbias) of the windows of vol [n_vol][1][X][Y][Z] at
+ *     origins / flips, with InstanceNorm (pgamma, pbeta) and LeakyReLU pslope; w [16][16][k].  Runs the stem's statistics pass,
+ *     their finalisation, then the consumer.  low / tstride / skip* are not read.
+ *   mode 2 (transposed conv): the producer is ConvTranspose3d (kernel = stride = tstride; pw [low_c][16][taps], pbias) of
+ *     low [n][low_c][dims / tstride] normalised on load with (pgamma, pbeta, pslope; NULL = identity); the consumer reads its
+ *     output ("up", channels 0 .. 15) next to skip [n][16][dims] with its own (skip_gamma, skip_beta, skip_slope);
+ *     w [16][32][1][3][3].  vol / vdim / origins / flips are not read.
+ *   -> y [n][16][dims] and, with stats_out, the consumer's statistics [n][16][2].  FNN_E_UNSUPPORTED: no kernel fuses the pair. */
+int fnn_op_stem(int device, const float *vol, int n_vol, int c, const long long vdim[3],
+                int n, const int *origins, const int flips[3], const int patch[3],
+                const float *w, const float *bias, int cout, const int k[3], float *y, double *stats_out);
+int fnn_op_conv_fused(int device, int mode, int n, const int dims[3],
+                      const float *vol, int n_vol, const long long vdim[3], const int *origins, const int flips[3],
+                      const float *low, int low_c, const int tstride[3],
+                      const float *skip, const float *skip_gamma, const float *skip_beta, float skip_slope,
+                      const float *pw, const float *pbias, const float *pgamma, const float *pbeta, float pslope,
+                      const float *w, const float *bias, const int k[3], float *y, double *stats_out);
 
 /* The kernel variants the last fnn_op_* call of this thread launched, one per line (the
  * launchers pick a variant from the layer's shape; the op tests pin which one a case exercises).  Returns the size needed. */

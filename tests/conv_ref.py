@@ -1,5 +1,5 @@
 """float64 restatement of the f16 conv and transposed-conv path (csrc/conv3d*.hip, conv2d_zp.hip, conv3d_row.hip, tconv.hip)
-that tests/test_gpu_conv_exact.py compares the device with BIT FOR BIT.  Plain numpy and torch CPU, no device code.
+that tests/test_gpu_conv_exact.py and tests/test_gpu_stem_fused_exact.py compare the device with BIT FOR BIT.  Plain numpy and torch CPU, no device code.
 
 The route is data on which the kernels' arithmetic is exact, so that there is one right answer whatever the order of the
 fp32 sums: fits_exact / stats_fit_exact say when that holds.  Roundings restated, and where they are made:
@@ -20,6 +20,11 @@ fp32 sums: fits_exact / stats_fit_exact say when that holds.  Roundings restated
                          exact in fp32; every partial sum is exact when fits_exact holds.
   store                  conv_common.h tile_epilogue (and each family's own): f16(acc + bias), one rounding of the exact value
                          when fits_exact holds -> conv_exact / tconv_exact round the float64 result straight to fp16.
+  stem (stem_exact)      conv3d_thin.hip / conv3d_row.hip: the patch window of the fp32 volume, mirrored, x and w rounded to fp16,
+                         zero padding at the PATCH border, then accumulation and store as above.  A fused consumer recomputes
+                         exactly these stored values (f16 of the stem's sum) before it normalises them: fused_stem_staged.
+  fused transposed conv  conv3d_thin.hip / conv3d_row.hip: "up" = f16(tconv(stage16(low)) + bias), the bits tconv_mfma_kernel
+                         stores, concatenated in front of the staged skip: fused_tconv_staged.
   statistics             tile_epilogue's v_dot2_f32_f16 chains, row16_sum, the workgroup sum in double, replica atomics or
                          slot rows, fnn_op_conv3d's sum over the rows: sums of the fp16-rounded outputs - integers in units of
                          the outputs' quantum, exact in every order when stats_fit_exact holds.
@@ -211,3 +216,42 @@ def craft_norm(x, S, H, eps=1e-5):
     gamma = (S * root).astype(np.float32)
     beta = (H + mean * (gamma.astype(np.float64) / root)).astype(np.float32)
     return gamma, beta
+
+
+def stem_window(vol, origin, flips, patch):
+    """the patch window [C, *patch] the stem reads from the volume vol [C, X, Y, Z], mirrored along the flagged axes (the
+    output is NOT mirrored back: the seg head un-mirrors)"""
+    vol = np.asarray(vol)
+    x = vol[(slice(None),) + tuple(slice(int(o), int(o) + int(p)) for o, p in zip(origin, patch))]
+    assert x.shape[1:] == tuple(patch), 'the patch leaves the volume'
+    for ax in range(3):
+        if flips[ax]:
+            x = np.flip(x, 1 + ax)
+    return np.ascontiguousarray(x)
+
+
+def stem_exact(vol, origin, flips, patch, w, bias, fast=False):
+    """The stem on one patch of vol [C, X, Y, Z] -> (t, y16) [1, cout, *patch] as conv_exact: window, mirror, x and w rounded
+    to fp16, zero padding at the patch border (conv_exact's)"""
+    x = h16(stem_window(vol, origin, flips, patch))[None]
+    w = np.asarray(w)
+    return conv_exact(x, h16(w), bias, w.shape[2:], (1, 1, 1), fast=fast)
+
+
+def stem_batch(vol, origins, flips, patch, w, bias, fast=False):
+    """stem_exact over a batch: vol [C, X, Y, Z] (one volume) or [n, C, X, Y, Z] -> y16 [n, cout, *patch]"""
+    vol = np.asarray(vol)
+    return np.concatenate([stem_exact(vol if vol.ndim == 4 else vol[i], o, flips, patch, w, bias, fast)[1] for i, o in enumerate(origins)])
+
+
+def fused_stem_staged(y16, norm, slope, margin=1.0):
+    """what a FUSE_STEM consumer multiplies: stage16 of the stem's stored values -> (value, lo, hi, ambiguous)"""
+    return stage16(y16, norm, slope, margin=margin)
+
+
+def fused_tconv_staged(low, low_norm, low_slope, tw, tbias, stride, skip, skip_norm, skip_slope, margin=1.0, fast=False):
+    """what a FUSE_TCONV consumer multiplies: concat(f16(tconv(stage16(low))), stage16(skip)) -> (value, ambiguous)"""
+    a, _, _, amb = stage16(low, low_norm, low_slope, margin=margin)
+    up = tconv_exact(a, tw, tbias, stride, fast=fast)[1]
+    b, _, _, amb2 = stage16(skip, skip_norm, skip_slope, margin=margin)
+    return np.concatenate((up, b), 1), amb + amb2

@@ -174,6 +174,22 @@ def test_persistent_cases_have_range_seams_inside_items():
     assert seen == set(G.PERSISTENT_WGS)
 
 
+def test_row_over_grid_cases_walk_units_across_planes_and_items():
+    """the row kernels' units are (plane, strip) pairs, workgroup g's range [units g / grid, units (g + 1) / grid): with more
+    units than workgroups some ranges hold two units - a step from plane to plane - and one of them ends an item"""
+    for cid, grid in G.ROW_OVER_GRID.items():
+        c = G.BY_ID[cid]
+        D, H, W = c.dims
+        assert c.kernel.startswith('conv_row_kernel<4,') and W == 64 and H % 4 == 0 and H <= 64       # one strip per plane (pick_strips)
+        lds = (2 if c.cin2 else 1) * 12 * (W + 2) * 32 + 4 * 16 * 2 * 8
+        assert grid == 256 * min(160 * 1024 // lds, 2)
+        units = c.n * D
+        assert units > grid
+        ranges = [(units * g // grid, units * (g + 1) // grid) for g in range(grid)]
+        assert sum(b - a >= 2 for a, b in ranges) >= 1
+        assert sum(b - a >= 2 and a // D != (b - 1) // D for a, b in ranges) >= 1
+
+
 def test_committed_tconv_cases_meet_the_launch_rule_they_name():
     for c in G.DENSE_CASES:
         if c.kind != 'tconv':

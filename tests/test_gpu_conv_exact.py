@@ -106,6 +106,10 @@ DENSE_CASES = [
     _c('row-96-two-src', 2, 16, 16, 16, (4, 48, 96), K133, S1, 'conv_row_kernel<6,2,0>'),
     _c('row-160', 1, 16, 0, 16, (4, 12, 160), K133, S1, 'conv_row_kernel<10,1,0>'),
     _c('row-192-two-src', 1, 16, 16, 16, (4, 16, 192), K133, S1, 'conv_row_kernel<12,2,0>'),
+    # more (plane, strip) units than the persistent grid (ROW_OVER_GRID): a workgroup walks from unit to unit, across planes and
+    # - 7 x 86 = 602 units is the smallest such count - across an item boundary (CPU test)
+    _c('row-64-over-grid', 7, 16, 0, 16, (86, 8, 64), K133, S1, 'conv_row_kernel<4,1,0>'),
+    _c('row-64-two-src-over-grid', 7, 16, 16, 16, (86, 8, 64), K133, S1, 'conv_row_kernel<4,2,0>'),
     # ---- plane kernels (conv2d_zp.hip), stride 1 and (1, 2, 2), half image and FNN_ZP_NO_HALF / FNN_ZPS_NO_HALF
     _c('zp-8-4', 2, 32, 0, 32, (1, 19, 70), K133, S1, 'conv2d_zp_kernel<8,4>'),
     _c('zp-8-2-two-src-cm', 2, 48, 16, 32, (3, 21, 30), K133, S1, 'conv2d_zp_kernel<8,2>', CM),
@@ -161,7 +165,7 @@ REQUIRED_KERNELS = {
     'conv3d_zr_kernel<1,8>', 'conv3d_zr_kernel<1,4>', 'conv3d_zr_kernel<2,8>', 'conv3d_zr_kernel<2,4>', 'conv3d_zrw_kernel<1>',
     'conv3d_zrw_kernel<2>', 'conv3d_zr12_kernel<4>', 'conv3d_zq12_kernel', 'conv3d_zr_kernel<2,10,6>', 'conv3d_zs_kernel<2>',
     'conv3d_zsp_kernel', 'conv3d_zsw_kernel', 'conv3d_s2_kernel', 'conv3d_s2_kernel<13,3>', 'conv_row_kernel<4,1,0>',
-    'conv_row_kernel<6,2,0>', 'conv_row_kernel<10,1,0>', 'conv_row_kernel<12,2,0>', 'conv2d_zp_kernel<8,4>', 'conv2d_zp_kernel<8,2>',
+    'conv_row_kernel<4,2,0>', 'conv_row_kernel<6,2,0>', 'conv_row_kernel<10,1,0>', 'conv_row_kernel<12,2,0>', 'conv2d_zp_kernel<8,4>', 'conv2d_zp_kernel<8,2>',
     'conv2d_zp_kernel<4,1>', 'conv2d_zp_kernel<8,4,2,half>', 'conv2d_zp_kernel<8,4,1,half>', 'conv2d_zp_kernel<8,4,1>',
     'conv2d_zps_kernel<4,2>', 'conv2d_zps_kernel<2,2>', 'conv2d_zps_kernel<2,2,half>', 'conv2d_zps_kernel<4,1>',
     'tconv_mfma_kernel<1,2>', 'tconv_mfma_kernel<1,4>', 'tconv_mfma_kernel<2,2>', 'tconv_mfma_kernel<2,4>',
@@ -175,6 +179,9 @@ STORE_CASES = ['generic-2', 'lds-pad-8-24', 'lds-s222', 'persist-9tap', 'persist
 # workgroups of the persistent forms' grids (conv3d.hip: 256 CUs x wpc >= 2, or c.gx = 512; conv3d_zr.hip zsp: 512;
 # conv3d_s2.hip: 256): more than any such case's items
 PERSISTENT_WGS = {'conv3d_persist_kernel': 512, 'conv3d_zsp_kernel': 512, 'conv3d_s2_kernel': 256}
+# the row kernels' grid (conv3d_row.hip launch_row_t: 256 CUs x min(what LDS admits, cap); W = 64: cap = 2 for one chunk
+# (25856 B: six fit) and for two (51200 B: three fit)): fewer than these cases' units
+ROW_OVER_GRID = {'row-64-over-grid': 512, 'row-64-two-src-over-grid': 512}
 STORE_MODES = ('ties', 'subnormal')
 # (d): constant / near-constant channels through norm-on-load: three channels (padded to 16: the shift must not reach the
 # padding), (1, 3, 3) taps of +-1 - few enough products that the sums of these arbitrary fp16 values stay exact (CPU test)
