@@ -57,6 +57,12 @@ class ResampleTorchDesc(C.Structure):
                 ('aniso_axis_mode', C.c_int32)]
 
 
+class EnsembleMember(C.Structure):
+    """fnn_ensemble_member: one member's logits on its own network grid (transposed axes)."""
+    _fields_ = [('logits', C.c_void_p), ('shape', C.c_int64 * 3), ('dtype', C.c_int32), ('family', C.c_int32),
+                ('separate_axis', C.c_int32)]
+
+
 class Opts(C.Structure):
     _fields_ = [('tile_step_size', C.c_double), ('use_gaussian', C.c_int32), ('n_mirror_axes', C.c_int32),
                 ('mirror_axes', C.c_int32 * 3), ('accum', C.c_int32), ('out_dtype', C.c_int32),
@@ -72,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -134,6 +140,8 @@ def load_library() -> C.CDLL:
     lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
                                         C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
     lib.fnn_average_probabilities.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(C.c_int32), i64, vp, vp, i32, vp]
+    lib.fnn_ensemble_resample_export.argtypes = [C.POINTER(EnsembleMember), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
+                                                 C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
     lib.fnn_confusion_counts.argtypes = [vp, C.POINTER(vp), i32, i32, i64, C.POINTER(C.c_int32), i32, i32, i32,
                                          C.POINTER(i64), vp]
     lib.fnn_surface_count.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(i64), C.POINTER(i64), vp]
@@ -571,6 +579,27 @@ def ensemble_export(logits_ptrs: Sequence[int], halves: Sequence[bool], heads: i
                                   (C.c_int64 * 3)(*[int(i) for i in shape_before_cropping]),
                                   (C.c_int32 * 3)(*[int(i) for i in transpose_backward]), avg_ptr, labels_ptr,
                                   FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, stream), lib)
+
+
+def ensemble_resample_export(members: Sequence[Tuple], heads: int, regions_class_order, bbox, shape_before_cropping,
+                             transpose_backward, avg_ptr: Optional[int], labels_ptr: int, uint16: bool, stream: int = 0):
+    """fnn_ensemble_resample_export: the members' logits on their own network grids - one ``(device pointer, half, shape[3],
+    family, separate_axis or None)`` each - -> average probabilities (skipped when avg_ptr is None) + labels on the original
+    grid, bit for bit those of ``resample`` (order 1, order_z 0) / ``resample_torch`` per member followed by
+    ``ensemble_export``, without the resampled tensors.  A member whose shape equals the box's extents is taken as it is.
+    op_last_kernels() names the kernel that ran."""
+    lib = load_library()
+    n = len(members)
+    table = (EnsembleMember * max(n, 1))()
+    for e, (ptr, half, shape, family, sep) in zip(table, members):
+        e.logits, e.dtype, e.family = int(ptr), FNN_OUT_F16 if half else FNN_OUT_F32, int(family)
+        e.shape = (C.c_int64 * 3)(*[int(i) for i in shape])
+        e.separate_axis = -1 if sep is None else int(sep)
+    flat = (C.c_int64 * 6)(*[int(v) for ab in bbox for v in ab])
+    check(lib.fnn_ensemble_resample_export(table, n, int(heads), _order(regions_class_order, heads), flat,
+                                           (C.c_int64 * 3)(*[int(i) for i in shape_before_cropping]),
+                                           (C.c_int32 * 3)(*[int(i) for i in transpose_backward]), avg_ptr, labels_ptr,
+                                           FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, stream), lib)
 
 
 def average_probabilities(probs_ptrs: Sequence[int], heads: int, regions_class_order, n_vox: int, avg_ptr: Optional[int],

@@ -14,6 +14,7 @@
 // multiples of 4 (the common case) VEC = 4: 8-byte (fp16) or 16-byte (fp32) loads per member and head, 16-byte stores
 // of the average.  The softmax needs three passes over a member's heads (max, sum, probability); the first reads the
 // logits from HBM, the other two re-read the same lines, as export_prob_kernel does.
+#include "ensemble_common.h"
 #include "host_call.h"
 #include <climits>
 #include <cmath>
@@ -23,7 +24,6 @@
 
 namespace {
 
-constexpr int ENS_MAX_MEMBERS = 16;
 constexpr int ENS_THREADS = 256;
 constexpr int ENS_VEC_MAX_MEMBERS = 8;           // the VEC = 4 kernels keep 2 x 4 floats of softmax state per member
 
@@ -75,15 +75,9 @@ static __device__ __forceinline__ void store_labels(LT *labels, size_t idx, cons
     for (int k = 0; k < VEC; ++k) labels[idx + k] = (LT)v[k];
 }
 
-// The merge rule on the averaged value of head h (ensemble.py:42 -> label_handling.py:183-195).  Regions: the reference
-// hands the averaged PROBABILITIES to convert_logits_to_segmentation, which applies the sigmoid a second time before
-// `> 0.5`; this is mirrored on purpose.  Plain labels: argmax, the first maximum wins.
+// the merge rule on the averaged value of head h: ensemble_common.h
 static __device__ __forceinline__ void merge_rule(const EnsembleArgs &a, int h, float v, float &best, int &label) {
-    if (a.order) {
-        if (1.f / (1.f + expf(-v)) > 0.5f) label = a.order[h];
-    } else if (v > best) {
-        best = v; label = h;
-    }
+    ensemble_merge_rule(a.order, h, v, best, label);
 }
 
 // ---- N members' logits [H][e0][e1][e2] (transposed, cropped grid) -> average probabilities [H][o0][o1][o2] (optional)

@@ -306,14 +306,19 @@ inline int crop_box_fill(CropBox &b, const int64_t bbox[6], const int64_t before
     for (int j = 0; transpose_backward && j < 3; ++j) { b.tb[j] = transpose_backward[j]; b.o[j] = before[b.tb[j]]; }
     return FNN_OK;
 }
-// device: voxel i of the output grid -> is it inside the box, and then its index v in the cropped grid
-static __device__ __forceinline__ bool crop_box_voxel(const CropBox &b, long long i, size_t &v) {
+// device: voxel i of the output grid -> its coordinates d in the cropped grid (transposed axes), and is it inside the box
+static __device__ __forceinline__ bool crop_box_coords(const CropBox &b, long long i, long long (&d)[3]) {
     const long long oc[3] = {i / (b.o[1] * b.o[2]), (i / b.o[2]) % b.o[1], i % b.o[2]};
     long long t[3];
     t[b.tb[0]] = oc[0]; t[b.tb[1]] = oc[1]; t[b.tb[2]] = oc[2];
-    const long long d0 = t[0] - b.lo[0], d1 = t[1] - b.lo[1], d2 = t[2] - b.lo[2];
-    if (!(d0 >= 0 && d0 < b.e[0] && d1 >= 0 && d1 < b.e[1] && d2 >= 0 && d2 < b.e[2])) return false;
-    v = ((size_t)d0 * b.e[1] + d1) * b.e[2] + d2;
+    d[0] = t[0] - b.lo[0]; d[1] = t[1] - b.lo[1]; d[2] = t[2] - b.lo[2];
+    return d[0] >= 0 && d[0] < b.e[0] && d[1] >= 0 && d[1] < b.e[1] && d[2] >= 0 && d[2] < b.e[2];
+}
+// ... -> is it inside the box, and then its index v in the cropped grid
+static __device__ __forceinline__ bool crop_box_voxel(const CropBox &b, long long i, size_t &v) {
+    long long d[3];
+    if (!crop_box_coords(b, i, d)) return false;
+    v = ((size_t)d[0] * b.e[1] + d[1]) * b.e[2] + d[2];
     return true;
 }
 

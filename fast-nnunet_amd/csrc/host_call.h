@@ -1,5 +1,5 @@
 // host_call.h - the host side of one call of an entry point outside the engine (prep, resample, export_labels, postprocess,
-// ensemble, metrics, imageio, reorient, deflate_masks, ops_api): owned scratch (DevBuf, owned.h), the status chain of one call on
+// ensemble, ensemble_resample, metrics, imageio, reorient, deflate_masks, ops_api): owned scratch (DevBuf, owned.h), the status chain of one call on
 // one stream, the refusals the entries share and the dispatch from a dtype code to an element type.  Host code only: no
 // kernel and no __device__ function lives here.
 #pragma once

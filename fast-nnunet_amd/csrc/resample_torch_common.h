@@ -40,6 +40,17 @@ struct Taps {
     bool live;
 };
 
+// the corners and weights of output voxel (ox, oy, oz); o and live are the caller's
+static __device__ __forceinline__ void make_taps(const RGeo &g, long long ox, long long oy, long long oz, Taps &t) {
+    long long x[2], y[2], z[2];
+    axis_taps(g, 0, ox, x[0], x[1], t.wx0, t.wx1);
+    axis_taps(g, 1, oy, y[0], y[1], t.wy0, t.wy1);
+    axis_taps(g, 2, oz, z[0], z[1], t.wz0, t.wz1);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) t.off[k] = (x[k >> 2] * g.in[1] + y[(k >> 1) & 1]) * g.in[2] + z[k & 1];
+}
+
+// ... of the voxel a thread of a launch of plane_blocks * out[0] blocks of 256 owns
 static __device__ __forceinline__ Taps make_taps(const RGeo &g) {
     Taps t;
     const unsigned ox = blockIdx.x / g.plane_blocks;
@@ -47,12 +58,7 @@ static __device__ __forceinline__ Taps make_taps(const RGeo &g) {
     t.live = j < g.plane;
     const unsigned oy = t.live ? j / (unsigned)g.out[2] : 0u;
     const unsigned oz = t.live ? j - oy * (unsigned)g.out[2] : 0u;
-    long long x[2], y[2], z[2];
-    axis_taps(g, 0, ox, x[0], x[1], t.wx0, t.wx1);
-    axis_taps(g, 1, oy, y[0], y[1], t.wy0, t.wy1);
-    axis_taps(g, 2, oz, z[0], z[1], t.wz0, t.wz1);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t.off[k] = (x[k >> 2] * g.in[1] + y[(k >> 1) & 1]) * g.in[2] + z[k & 1];
+    make_taps(g, ox, oy, oz, t);
     t.o = (long long)ox * g.plane + j;
     return t;
 }

@@ -5,13 +5,17 @@ Mirrors the inference-time half of the reference's ``nnunetv2.ensembling.ensembl
 * ``average_probabilities`` - the float32 mean of several members' probabilities, in member order, bit for bit;
 * ``ensemble_probabilities`` - ``merge_files`` without the image writer: that average and
   ``LabelManager.convert_logits_to_segmentation`` applied to it;
-* ``nnUNetEnsemblePredictor`` - ``predict_single_npy_array`` for an ensemble of configurations: every member
-  preprocesses the raw case and runs its own sliding window, and one ``fnn_ensemble_export`` call turns all members'
-  resampled logits into the averaged probabilities and the label map, without the ``.npz`` round trip.
+* ``nnUNetEnsemblePredictor`` - ``predict_single_npy_array`` and ``predict_from_files`` for an ensemble of
+  configurations: every member preprocesses the raw case and runs its own sliding window, and one
+  ``fnn_ensemble_resample_export`` call turns all members' network-grid logits into the averaged probabilities and the
+  label map - without the ``.npz`` round trip and without a member's resampled logits ever being written (members whose
+  plans resample at another order than 1 are resampled first and go through ``fnn_ensemble_export``: the same bytes).
+  The file methods are the predictor's: the case loop of ``case_pipeline.run_pipeline`` with a reader and a writer
+  thread, the case read and decoded once for all members.
 
 ``merge_files`` and ``ensemble_folders`` (ensemble.py:31-110) are the reference's folder commands on top of it: the members'
 ``.npz`` files are averaged on the device and the label file goes through the writer, one case at a time behind a reader
-and a writer thread.  File output on ``nnUNetEnsemblePredictor`` stays out.
+and a writer thread.
 """
 from __future__ import annotations
 
@@ -99,13 +103,22 @@ def _label_signature(lm):
 
 class nnUNetEnsemblePredictor(object):
     """An ensemble of initialised ``nnUNetPredictor`` members (e.g. ``2d`` + ``3d_fullres``, or ``3d_fullres`` +
-    ``3d_lowres``, as ``nnUNetv2_find_best_configuration`` picks them), predicted on the device.
+    ``3d_lowres``, as ``nnUNetv2_find_best_configuration`` picks them), predicted on the device: arrays
+    (``predict_single_npy_array``) or files (``predict_from_files``, ``predict_from_files_sequential``).
 
-    Memory: the members' resampled fp16 logits are resident at the same time - N x heads x cropped voxels x 2 B (two
-    members of a 61-class 512^3 case: 32.7 GB) - on top of one member's network-grid logits while it runs; a member's
-    network-grid logits are freed once they are resampled."""
+    fused_export  the step from the members' logits to the ensemble's labels is one ``fnn_ensemble_resample_export`` call
+                  on the members' network-grid logits whenever every member's plan allows it (``plan_ensemble_export``:
+                  order-1 default plans, torch-resampling plans, equal grids); False, or a member that resamples at another
+                  order: every member's logits are resampled to the cropped grid first and ``fnn_ensemble_export`` reads
+                  those - the same bytes.  ``export_stats`` counts the cases by the route they took.
+    compress_on_device  as ``nnUNetPredictor``'s: the ensemble's label file is compressed on the GPU.
 
-    def __init__(self, predictors: Sequence[nnUNetPredictor]):
+    Memory: the fused step keeps only the members' network-grid logits resident (N x heads x network-grid voxels x 2 B; a
+    ``3d_lowres`` member at twice the spacing is an eighth of the cropped grid).  The two-step route keeps the members'
+    resampled fp16 logits resident at the same time - N x heads x cropped voxels x 2 B (two members of a 61-class 512^3
+    case: 32.7 GB) - on top of one member's network-grid logits while it runs."""
+
+    def __init__(self, predictors: Sequence[nnUNetPredictor], fused_export: bool = True, compress_on_device: bool = False):
         predictors = list(predictors)
         if not 1 <= len(predictors) <= MAX_MEMBERS:
             raise ValueError(f'an ensemble has 1..{MAX_MEMBERS} members, got {len(predictors)}')
@@ -124,8 +137,13 @@ class nnUNetEnsemblePredictor(object):
         self.device = first.device
         self.label_manager = first.label_manager
         self.plans_manager = first.plans_manager
+        self.dataset_json = first.dataset_json
         self.verbose = first.verbose
+        self.fused_export = bool(fused_export)
+        self.compress_on_device = bool(compress_on_device)
+        self.export_stats = {'fused': 0, 'two-step': 0}
         self._postprocessing = None
+        self._rw = None
 
     def set_postprocessing(self, postprocessing):
         """As ``nnUNetPredictor.set_postprocessing``: applied to the ensemble's device label map on the raw grid
@@ -139,14 +157,25 @@ class nnUNetEnsemblePredictor(object):
         """Raw image ``[C, s0, s1, s2]`` + ``{'spacing': ...}`` -> ensembled label map on the raw grid (numpy, uint8 /
         uint16), or ``(labels, float32 average probabilities [heads, s0, s1, s2])`` with
         ``save_or_return_probabilities``: what ``merge_files`` makes of the members' exported probabilities.
-        ``segmentation_previous_stage``: None, or one entry per member (None for members that are no cascade stage)."""
+        ``segmentation_previous_stage``: None, or one entry per member (None for members that are no cascade stage).
+        Files are written by ``predict_from_files``."""
         if output_file_truncated is not None:
-            raise NotImplementedError('image file export is the caller\'s side (SURVEY.md 8: image I/O out of scope)')
+            raise NotImplementedError('predict_single_npy_array returns arrays; predict_from_files writes image files')
+        seg, avg, _ = self._predict_case(input_image, image_properties, segmentation_previous_stage,
+                                         save_or_return_probabilities)
+        return (seg, avg) if save_or_return_probabilities else seg
+
+    def _predict_case(self, input_image, image_properties: dict, segmentation_previous_stage=None,
+                      save_or_return_probabilities: bool = False, for_file: bool = False):
+        """-> (labels on the raw grid as ``_labels_out`` makes them, float32 average or None, the case's properties after
+        preprocessing).  ``input_image`` is a numpy array or a tensor (a resident one stays where it is): every member
+        preprocesses the same one."""
+        from .preprocess import case_label_export_plan, plan_ensemble_export
         n = len(self.predictors)
         prev = [None] * n if segmentation_previous_stage is None else list(segmentation_previous_stage)
         if len(prev) != n:
             raise ValueError(f'segmentation_previous_stage: {len(prev)} entries for {n} members')
-        resident, props0 = [], None
+        cases, props0 = [], None
         for p, sp in zip(self.predictors, prev):
             pp, data, props = p._preprocess_case(input_image, image_properties, sp)
             if props0 is None:
@@ -157,30 +186,135 @@ class nnUNetEnsemblePredictor(object):
                     tuple(props0['shape_after_cropping_and_before_resampling']) or \
                     tuple(props['shape_before_cropping']) != tuple(props0['shape_before_cropping']):
                 raise RuntimeError('members cropped the case differently: their probabilities cannot be averaged')
+            cases.append((p, pp, data, props,
+                          case_label_export_plan(data.shape[1:], p.plans_manager, p.configuration_manager, props)))
+        fused = self.fused_export and plan_ensemble_export([c[4] for c in cases]) == 'fused'
+        resident = []
+        while cases:
+            p, pp, data, props, plan = cases.pop(0)
             if self.verbose:
                 print('predicting')
             logits = p._predict_case_logits(data)
             del data
-            resident.append(pp.resample_logits_to_cropped_shape(logits, p.plans_manager, p.configuration_manager, props))
-            del logits
+            if not fused:
+                logits = pp.resample_logits_to_cropped_shape(logits, p.plans_manager, p.configuration_manager, props)
+            resident.append((logits, plan))
+        labels, avg = self._export_members(resident, fused, props0, save_or_return_probabilities)
+        del resident
+        out = nnUNetPredictor._labels_out(self, as_plain_labels(labels), props0, for_file=for_file)
+        return out, None if avg is None else avg.cpu().numpy(), props0
+
+    def _export_members(self, resident, fused: bool, props0: dict, want_average: bool):
+        """The step from the members' logits to the ensemble's labels: ``resident`` holds one (logits, label-export plan)
+        per member - network-grid logits when ``fused``, else logits of the cropped grid.  -> (device labels on the raw
+        grid, device float32 average or None)."""
         order, u16 = label_rule(self.label_manager)
         before = [int(i) for i in props0['shape_before_cropping']]
+        cropped = [int(i) for i in props0['shape_after_cropping_and_before_resampling']]
         tb = [int(i) for i in self.plans_manager.transpose_backward]
         grid = [before[j] for j in tb]
         with torch.cuda.device(self.device):
-            resident = [lg.contiguous() for lg in resident]
-            avg = torch.empty((resident[0].shape[0], *grid), dtype=torch.float32, device=self.device) \
-                if save_or_return_probabilities else None
+            lgs = [lg.contiguous() for lg, _ in resident]
+            heads = lgs[0].shape[0]
+            avg = torch.empty((heads, *grid), dtype=torch.float32, device=self.device) if want_average else None
             labels = torch.empty(grid, dtype=torch.int16 if u16 else torch.uint8, device=self.device)
-            capi.ensemble_export([lg.data_ptr() for lg in resident], [lg.dtype == torch.half for lg in resident],
-                                 resident[0].shape[0], order, props0['bbox_used_for_cropping'], before, tb,
-                                 None if avg is None else avg.data_ptr(), labels.data_ptr(), u16,
-                                 torch.cuda.current_stream(self.device).cuda_stream)
-            del resident
-        out = nnUNetPredictor._labels_out(self, as_plain_labels(labels), props0, for_file=False)
-        if save_or_return_probabilities:
-            return out, avg.cpu().numpy()
-        return out
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            avg_ptr = None if avg is None else avg.data_ptr()
+            if fused:
+                members = []
+                for lg, (_, plan) in zip(lgs, resident):
+                    if plan['path'] == 'same-grid' and [int(i) for i in lg.shape[1:]] != cropped:
+                        raise RuntimeError(f'logits of shape {tuple(lg.shape[1:])} are not resampled, the crop is {cropped}')
+                    members.append((lg.data_ptr(), lg.dtype == torch.half, lg.shape[1:],
+                                    capi.FNN_RESAMPLE_TORCH if plan['path'] == 'fused-torch' else capi.FNN_RESAMPLE_DEFAULT,
+                                    plan['separate_axis']))
+                capi.ensemble_resample_export(members, heads, order, props0['bbox_used_for_cropping'], before, tb, avg_ptr,
+                                              labels.data_ptr(), u16, stream)
+            else:
+                capi.ensemble_export([lg.data_ptr() for lg in lgs], [lg.dtype == torch.half for lg in lgs], heads, order,
+                                     props0['bbox_used_for_cropping'], before, tb, avg_ptr, labels.data_ptr(), u16, stream)
+        self.export_stats['fused' if fused else 'two-step'] += 1
+        return labels, avg
+
+    # ----------------------------------------------------------------- files
+    # what a predictor and an ensemble do alike around the cases of a files run is nnUNetPredictor's
+    _label_files = nnUNetPredictor._label_files
+    _labels_out = nnUNetPredictor._labels_out
+    _export_case = nnUNetPredictor._export_case
+    _result = staticmethod(nnUNetPredictor._result)
+    predict_from_files = nnUNetPredictor.predict_from_files
+    predict_from_files_sequential = nnUNetPredictor.predict_from_files_sequential
+
+    def _reader_writer(self):
+        """One instance of the members' common reader-writer class (``nnUNetPredictor._reader_writer``); members that read
+        or write differently are a ValueError."""
+        if self._rw is None:
+            from .imageio import prediction_reader_writer_class
+            classes = [prediction_reader_writer_class(p.plans_manager, p.dataset_json) for p in self.predictors]
+            if any(c is not classes[0] for c in classes):
+                raise ValueError(f'members read and write images differently: {sorted({c.__name__ for c in classes})}')
+            self._rw = classes[0](self.device)
+        return self._rw
+
+    def _prepare_files_run(self, call_kwargs: dict, sequential: bool):
+        """``nnUNetPredictor._prepare_files_run`` behind what only an ensemble can get wrong: members of different file
+        types, and previous-stage folders that are not one per member."""
+        endings = sorted({str(p.dataset_json['file_ending']) for p in self.predictors})
+        if len(endings) > 1:
+            raise ValueError(f'members have different file endings: {endings}')
+        folders = call_kwargs.get('folder_with_segs_from_prev_stage')
+        if folders is not None and (isinstance(folders, (str, os.PathLike)) or len(folders) != len(self.predictors)):
+            raise ValueError(f'folder_with_segs_from_prev_stage: None, or one entry per member ({len(self.predictors)}; None for '
+                             f'members that are no cascade stage)')
+        self._reader_writer()
+        return nnUNetPredictor._prepare_files_run(self, call_kwargs, sequential)
+
+    def _assert_prev_stage_folder(self, folders):
+        for p, folder in zip(self.predictors, folders if folders is not None else [None] * len(self.predictors)):
+            p._assert_prev_stage_folder(folder)
+
+    def _manage_input_and_output_lists(self, list_of_lists_or_source_folder, output_folder_or_list_of_truncated_output_files,
+                                       folder_with_segs_from_prev_stage=None, overwrite: bool = True, part_id: int = 0,
+                                       num_parts: int = 1, save_probabilities: bool = False):
+        """``nnUNetPredictor._manage_input_and_output_lists`` with the previous stage's files per member: the third list
+        holds, per case, None or one file name (or None) per member."""
+        cases, truncated, _ = nnUNetPredictor._manage_input_and_output_lists(
+            self, list_of_lists_or_source_folder, output_folder_or_list_of_truncated_output_files, None, overwrite,
+            part_id, num_parts, save_probabilities)
+        if folder_with_segs_from_prev_stage is None or all(f is None for f in folder_with_segs_from_prev_stage):
+            return cases, truncated, [None] * len(cases)
+        ending = self.dataset_json['file_ending']
+        caseids = [os.path.basename(c[0])[:-(len(ending) + 5)] for c in cases]
+        return cases, truncated, [[None if f is None else os.path.join(f, i + ending) for f in folder_with_segs_from_prev_stage]
+                                  for i in caseids]
+
+    @torch.inference_mode()
+    def _predict_cases(self, cases, truncated, prev, save_probabilities, read_thread: bool, write_thread: bool):
+        """The case loop of ``nnUNetPredictor._predict_cases`` with one previous-stage file per cascade member: the case is
+        read and decoded once, every member preprocesses that device tensor."""
+        rw = self._reader_writer()                              # (made by the calling thread)
+        if truncated is None:
+            truncated = [None] * len(cases)
+        n_slots = len(self.predictors) + 1
+
+        def stage(i):
+            slot = n_slots * (i % 2)
+            staged = rw.stage(cases[i], slot=slot)
+            staged_prev = [None if f is None else rw.stage([f], slot=slot + 1 + m) for m, f in enumerate(prev[i] or [])]
+            return lambda: (staged.fill(), [None if s is None else s.fill() for s in staged_prev])
+
+        def run(i, filled):
+            staged, staged_prev = filled
+            data, props = rw.decode(staged)
+            seg_prev = [None if s is None else rw.decode(s)[0] for s in staged_prev] or None
+            if staged.fnames and self.verbose:
+                print(f'predicting {os.path.basename(staged.fnames[0])}')
+            seg, avg, props = self._predict_case(data, props, seg_prev, save_probabilities, for_file=truncated[i] is not None)
+            if truncated[i] is None:
+                return self._result(seg, avg, save_probabilities), None
+            return None, (lambda: self._export_case(seg, avg, props, truncated[i]))
+
+        return run_pipeline(len(cases), stage, run, read_thread, write_thread)
 
 
 # ---- folders -----------------------------------------------------------------------------------------------------------

@@ -479,6 +479,14 @@ class nnUNetPredictor(object):
                   f'That\'s {len(todo)} cases.')
         return cases, truncated, prev
 
+    def _assert_prev_stage_folder(self, folder_prev):
+        """The reference's cascade assertion (predict_from_raw_data.py:232-236)."""
+        if self.configuration_manager.previous_stage_name is not None:
+            assert folder_prev is not None, \
+                f'The requested configuration is a cascaded network. It requires the segmentations of the previous ' \
+                f'stage ({self.configuration_manager.previous_stage_name}) as input. Please provide the folder where' \
+                f' they are located via folder_with_segs_from_prev_stage'
+
     def _prepare_files_run(self, call_kwargs: dict, sequential: bool):
         """What both file entry points do before the first case (predict_from_raw_data.py:221-261 / :691-730): the output
         folder with the call's arguments, dataset.json and plans.json; the cascade assertion; the lists."""
@@ -499,11 +507,7 @@ class nnUNetPredictor(object):
                 with open(os.path.join(output_folder, name), 'w') as f:
                     json.dump(obj, f, indent=4, sort_keys=sort)
         folder_prev = call_kwargs.get('folder_with_segs_from_prev_stage')
-        if self.configuration_manager.previous_stage_name is not None:
-            assert folder_prev is not None, \
-                f'The requested configuration is a cascaded network. It requires the segmentations of the previous ' \
-                f'stage ({self.configuration_manager.previous_stage_name}) as input. Please provide the folder where' \
-                f' they are located via folder_with_segs_from_prev_stage'
+        self._assert_prev_stage_folder(folder_prev)
         return self._manage_input_and_output_lists(
             call_kwargs['list_of_lists_or_source_folder'], target, folder_prev, call_kwargs['overwrite'],
             0 if sequential else call_kwargs['part_id'], 1 if sequential else call_kwargs['num_parts'],

@@ -131,6 +131,41 @@ def plan_label_export(fn_name: str, kwargs: Optional[dict], current_spacing, new
     return {'path': 'fused-default' if fused else 'two-step', 'separate_axis': int(axis) if do_sep else None}
 
 
+def plan_ensemble_export(member_plans: Sequence[dict]) -> str:
+    """How an ensemble's labels come out of its members' logits, from the members' ``plan_label_export`` results - without
+    a GPU.  -> ``'fused'``: every member is ``same-grid``, ``fused-default`` or ``fused-torch``, so one
+    ``fnn_ensemble_resample_export`` call reads the members' network-grid logits; ``'two-step'`` as soon as one member is
+    ``two-step`` (an order other than 1): every member's logits are resampled to the cropped grid first.  (A member whose
+    plan ``plan_resampling`` refuses never gets here: ``plan_label_export`` raised.)"""
+    member_plans = list(member_plans)
+    if not member_plans:
+        raise ValueError('an ensemble has at least one member')
+    for plan in member_plans:
+        if plan['path'] not in ('same-grid', 'fused-default', 'fused-torch', 'two-step'):
+            raise ValueError(f"unknown label export path {plan['path']!r}")
+    return 'two-step' if any(plan['path'] == 'two-step' for plan in member_plans) else 'fused'
+
+
+def probabilities_resampling(plans_manager, configuration_manager, properties_dict: dict):
+    """What export_prediction.py:26-35 resamples a case's logits with -> (``resampling_fn_probabilities`` name, its kwargs,
+    the spacing of the logits, the spacing of the cropped grid), all on the transposed axes."""
+    spacing_transposed = [properties_dict['spacing'][i] for i in plans_manager.transpose_forward]
+    target = list(configuration_manager.spacing)
+    current_spacing = target if len(target) == len(properties_dict['shape_after_cropping_and_before_resampling']) \
+        else [spacing_transposed[0], *target]
+    kw = getattr(configuration_manager, 'resampling_fn_probabilities_kwargs', None) or \
+        {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
+    fn = getattr(configuration_manager, 'resampling_fn_probabilities_name', DEFAULT_RESAMPLING_FN)
+    return fn, kw, current_spacing, spacing_transposed
+
+
+def case_label_export_plan(logits_shape, plans_manager, configuration_manager, properties_dict: dict) -> dict:
+    """``plan_label_export`` for logits ``[*logits_shape]`` (the network grid, without the heads) of a preprocessed case."""
+    fn, kw, current_spacing, spacing_transposed = probabilities_resampling(plans_manager, configuration_manager, properties_dict)
+    return plan_label_export(fn, kw, current_spacing, spacing_transposed, logits_shape,
+                             properties_dict['shape_after_cropping_and_before_resampling'])
+
+
 class DevicePreprocessor:
     def __init__(self, device: torch.device = torch.device('cuda'), verbose: bool = False):
         if device.type != 'cuda':
@@ -278,13 +313,8 @@ class DevicePreprocessor:
                                                                     properties_dict: dict) -> torch.Tensor:
         """inference/export_prediction.py:16-53 on the device: logits ``[heads, x, y, z]`` of the network grid ->
         label map on the original image grid.  ``predictor`` supplies the label rule (its ``label_manager``)."""
-        spacing_transposed = [properties_dict['spacing'][i] for i in plans_manager.transpose_forward]
-        target = list(configuration_manager.spacing)
-        current_spacing = target if len(target) == len(properties_dict['shape_after_cropping_and_before_resampling']) \
-            else [spacing_transposed[0], *target]
-        kw = getattr(configuration_manager, 'resampling_fn_probabilities_kwargs', None) or \
-            {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
-        fn = getattr(configuration_manager, 'resampling_fn_probabilities_name', DEFAULT_RESAMPLING_FN)
+        fn, kw, current_spacing, spacing_transposed = probabilities_resampling(plans_manager, configuration_manager,
+                                                                               properties_dict)
         cropped = properties_dict['shape_after_cropping_and_before_resampling']
         if getattr(predictor, 'fused_label_export', False):
             # no resampled logits [heads, *cropped] in between: interpolation and label rule in one pass
@@ -328,13 +358,9 @@ class DevicePreprocessor:
                                          properties_dict: dict) -> torch.Tensor:
         """The resampling step of export_prediction.py:26-35: logits of the network grid ->
         ``shape_after_cropping_and_before_resampling`` (returned as they are when the grids agree)."""
-        spacing_transposed = [properties_dict['spacing'][i] for i in plans_manager.transpose_forward]
-        target = list(configuration_manager.spacing)
+        fn, kw, current_spacing, spacing_transposed = probabilities_resampling(plans_manager, configuration_manager,
+                                                                               properties_dict)
         cropped = [int(i) for i in properties_dict['shape_after_cropping_and_before_resampling']]
-        current_spacing = target if len(target) == len(cropped) else [spacing_transposed[0], *target]
-        kw = getattr(configuration_manager, 'resampling_fn_probabilities_kwargs', None) or \
-            {'is_seg': False, 'order': 1, 'order_z': 0, 'force_separate_z': None}
-        fn = getattr(configuration_manager, 'resampling_fn_probabilities_name', DEFAULT_RESAMPLING_FN)
         logits = predicted_logits
         if [int(i) for i in logits.shape[1:]] != cropped:
             logits = self.resample(logits, cropped, current_spacing, spacing_transposed, kw, fn)

@@ -391,6 +391,26 @@ int fnn_ensemble_export(const void *const *member_logits, const int32_t *member_
 int fnn_average_probabilities(const float *const *member_probs, int n_members, int heads,
                               const int32_t *regions_class_order, int64_t n_vox, float *avg_probs, void *labels,
                               int label_dtype, void *stream);
+/* fnn_ensemble_export straight from the members' network grids (additive in ABI 4): member m's logits are
+ * [heads][shape] (device, transposed axes) and are resampled to the bbox extents inside the pass, each value formed
+ * and rounded to the member's dtype exactly as fnn_resample (family FNN_RESAMPLE_DEFAULT: order 1, order_z 0, that
+ * separate axis) or fnn_resample_torch (FNN_RESAMPLE_TORCH) would have stored it; a member whose shape equals the
+ * extents is taken as it is, whatever its family.  avg_probs and labels are bit for bit those of the per-member
+ * resampling calls followed by fnn_ensemble_export, without the resampled tensors.  1..16 members, any mix of dtypes,
+ * families and grids; at most 640 heads (the running sums of a voxel live in LDS; more: FNN_E_UNSUPPORTED).
+ * regions_class_order: host, heads entries, or NULL.  Allocates nothing proportional to the volume; synchronises the
+ * stream. */
+typedef struct fnn_ensemble_member {
+    const void *logits;        /* device, [heads][shape[0]][shape[1]][shape[2]]: the member's network grid, transposed axes */
+    int64_t shape[3];
+    int32_t dtype;             /* FNN_OUT_F16 / FNN_OUT_F32 */
+    int32_t family;            /* FNN_RESAMPLE_DEFAULT (order 1, order_z 0) / FNN_RESAMPLE_TORCH */
+    int32_t separate_axis;     /* -1 or 0..2 */
+} fnn_ensemble_member;
+int fnn_ensemble_resample_export(const fnn_ensemble_member *members, int n_members, int heads,
+                                 const int32_t *regions_class_order, const int64_t bbox[6],
+                                 const int64_t shape_before_cropping[3], const int32_t transpose_backward[3],
+                                 float *avg_probs, void *labels, int label_dtype, void *stream);
 
 /* Confusion counts of a reference label map against 1..4 predicted maps of the same voxel count (additive in ABI 4), for
  * compute_tp_fp_fn_tn (evaluation/evaluate_predictions.py:76-85) of every label at once.  ref and pred[p] (device,

@@ -4,8 +4,13 @@ raw grid (crop = grid, fp16 logits), 2 and 5 members, labels only and with the a
 probabilities) for comparison, on a smaller grid because one 61 x 512^3 float32 member alone is 32.7 GB.
 
 usage (repo root, GPU box): python tools/ensemble_bench.py [--n 512] [--heads 61] [--members 2 5] [--reps 5]
-                            [--numpy-n 128] [--out FILE]
+                            [--numpy-n 128] [--out FILE] [--section export|resample]
 Kernel times: run it under rocprofv3 --kernel-trace --stats.
+
+--section resample: the step from the members' network-grid logits to the ensemble's labels, both ways in one process -
+today's route (fnn_resample at order 1 per member into a fresh tensor of the cropped grid, then fnn_ensemble_export) and
+the one fnn_ensemble_resample_export call - for fp16 members on the network grids 320 x 410 x 410 and 256^3 in turn,
+default family, to a 512^3 crop = grid; with torch.cuda.max_memory_allocated of each route.
 """
 import argparse
 import os
@@ -21,6 +26,73 @@ sys.path.insert(0, ROOT)
 COPY_TBS = 6.29          # MI355X_MICROARCH: float4 copy, measured
 
 
+NETWORK_GRIDS = ((320, 410, 410), (256, 256, 256))
+
+
+def _median_ms(fn, reps, dev):
+    """Median, min and max of `reps` windows of fn() after one warm-up, events on the current stream."""
+    ts = []
+    for r in range(reps + 1):
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if r:
+            ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts)), min(ts), max(ts)
+
+
+def resample_section(a, capi, dev):
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    n, H = a.n, a.heads
+    bbox, before, tb = [[0, n]] * 3, (n, n, n), (0, 1, 2)
+    lines = [f'ensemble_bench --section resample: {H} heads, fp16 members on the network grids '
+             f'{" / ".join("x".join(map(str, g)) for g in NETWORK_GRIDS)} in turn, default family (order 1, order_z 0), to a '
+             f'{n}^3 crop = raw grid',
+             f'device {torch.cuda.get_device_name(dev)}; median of {a.reps} windows after one warm-up, events on the stream around '
+             f'the whole step; peak = torch.cuda.max_memory_allocated over one step (members\' network-grid logits, labels and '
+             f'the average included)']
+    g = torch.Generator(device=dev).manual_seed(5)
+    logits = []
+    labels = torch.empty((n, n, n), dtype=torch.uint8, device=dev)
+    rows = [(N, False) for N in sorted(a.members)] + [(min(a.members), True)]
+    for N, with_avg in rows:
+        while len(logits) < N:
+            logits.append(torch.randn((H, *NETWORK_GRIDS[len(logits) % 2]), generator=g, device=dev, dtype=torch.half) * 3)
+        members = logits[:N]
+        avg = torch.empty((H, n, n, n), dtype=torch.float32, device=dev) if with_avg else None
+        avg_ptr = None if avg is None else avg.data_ptr()
+
+        def two_step():
+            resampled = []
+            for lg in members:
+                out = torch.empty((H, n, n, n), dtype=torch.half, device=dev)
+                capi.resample(lg.data_ptr(), lg.shape, (n, n, n), 1, None, True, out.data_ptr(), stream, order_z=0)
+                resampled.append(out)
+            capi.ensemble_export([t.data_ptr() for t in resampled], [True] * N, H, None, bbox, before, tb, avg_ptr,
+                                 labels.data_ptr(), False, stream)
+
+        def fused():
+            capi.ensemble_resample_export([(lg.data_ptr(), True, lg.shape[1:], capi.FNN_RESAMPLE_DEFAULT, None) for lg in members],
+                                          H, None, bbox, before, tb, avg_ptr, labels.data_ptr(), False, stream)
+
+        got = {}
+        for name, fn in (('resample + fnn_ensemble_export', two_step), ('fnn_ensemble_resample_export  ', fused)):
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats(dev)
+            ms, lo, hi = _median_ms(fn, a.reps, dev)
+            got[name] = (ms, labels.clone(), None if avg is None else avg[:, ::64].clone())
+            lines.append(f'members {N}, {"labels + average" if with_avg else "labels only     "}, {name}: {ms:9.2f} ms  '
+                         f'min {lo:.2f} max {hi:.2f}  peak {torch.cuda.max_memory_allocated(dev) / 1e9:6.1f} GB')
+        (ms2, l2, a2), (ms1, l1, a1) = got.values()
+        same = torch.equal(l1, l2) and (a1 is None or torch.equal(a1.view(torch.int32), a2.view(torch.int32)))
+        lines.append(f'members {N}: fused / two-step = {ms1 / ms2:.3f}; same labels{" and average (every 64th plane)" if with_avg else ""}: {same}')
+        del avg, got, l1, l2, a1, a2
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
@@ -29,10 +101,18 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--numpy-n', type=int, default=128)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--section', choices=('export', 'resample'), default='export')
     a = ap.parse_args()
     from fast_nnunet_amd import capi
 
     dev = torch.device('cuda', 0)
+    if a.section == 'resample':
+        text = '\n'.join(resample_section(a, capi, dev))
+        print(text)
+        if a.out:
+            with open(a.out, 'w') as f:
+                f.write(text + '\n')
+        return
     stream = torch.cuda.current_stream(dev).cuda_stream
     n, H = a.n, a.heads
     vox = n ** 3
