@@ -473,6 +473,53 @@ int fnn_instance_overlaps(const void *ref, const void *pred, int label_dtype, co
                           const int32_t *group_of_label, int n_table, int n_groups, int32_t *records, int64_t cap,
                           int64_t n_out[3], void *stream);
 
+/* The surface of every region of a label map as triangles (additive in ABI 4), for a coloured 3-D model of a
+ * segmentation: what the reference's VTKModelGenerator is called for (its source is not part of the reference; the
+ * definition below is this project's own).  seg: device label map [shape[0]][shape[1]][shape[2]] = (z, y, x) of label_dtype
+ * (FNN_LABEL_U8 / U16), aligned to its element.  member, n_table, n_regions: as fnn_surface_count - 1..1024 regions, each a
+ * set of label values; everything outside the volume belongs to no region.
+ * Faces: every pair of 6-neighbours (v, n) with v in region r and n not in r (n may lie outside the volume) is one square
+ * face on the voxel boundary between them.  The faces of a region are ordered by the raster index of v, and inside one v by
+ * direction -z, +z, -y, +y, -x, +x.  Every face is two triangles.
+ * Vertices: the corners (cz, cy, cx) of the (Z+1)(Y+1)(X+1) corner grid whose 8 surrounding voxels are neither all in r nor
+ * all outside r, ordered by the raster index of the corner; every region has its own vertices, and the triangles index the
+ * concatenation of all regions' vertices.  The index-space position of a corner is (x, y, z) = (cx - 0.5, cy - 0.5,
+ * cz - 0.5) in float32.
+ * Triangles: with q0 < q1 < q2 < q3 the face's corners in raster order, the face is (q0, q1, q3), (q0, q3, q2) for the
+ * directions +z, -y, +x and (q0, q3, q1), (q0, q2, q3) for -z, +y, -x: (b - a) x (c - a) points out of the region when
+ * (x, y, z) is a right-handed triple.  When the determinant of the affine's 3x3 part is negative, the second and third
+ * index of every triangle are swapped, so that the same holds in world coordinates.
+ * Smoothing: smoothing_pairs times a pass with f = 0.5 and a pass with f = -0.53 (Taubin).  Two vertices of r are
+ * neighbours iff they are the ends of a lattice edge whose 4 surrounding voxels are neither all in r nor all outside r.
+ * A pass computes p' = p + f * (m - p) for every vertex from the positions before the pass, m = (0 + the present
+ * neighbours added in the order -x, +x, -y, +y, -z, +z) * float32(1 / their number); float32, every operation rounded
+ * on its own.  Regions do not see each other.
+ * World coordinates: row r of the point is ((A[r][0] * x + A[r][1] * y) + A[r][2] * z) + A[r][3] in float64, evaluated in
+ * that order without fused multiply-adds and rounded once to float32; affine = A, 16 doubles in row-major order, host.
+ * fnn_mesh_count: counts (host [n_regions][2]) receives the vertices and the faces of every region, boxes (host
+ * [n_regions][6]) the [lo, hi) box of its voxels as lo_z, hi_z, lo_y, hi_y, lo_x, hi_x - all zero for an empty region.
+ * fnn_mesh_emit writes region after region.  layout 0: points float32 [n][3], cells int32 [t][3], cell_region uint16 [t]
+ * (the index of the triangle's region).  layout 1: the same values big-endian and cells as [t][4] with a leading 3 - the
+ * payload of the POINTS and POLYGONS sections of a legacy-VTK binary file.  n is the sum of the vertices, t twice the sum
+ * of the faces; cap_points counts points and cap_cells triangles, and a cap below n or t writes nothing and is
+ * FNN_E_INVALID with the number needed in the message.  points: device, 4-byte aligned; cells: device, 4-byte (layout 0)
+ * or 16-byte (layout 1) aligned; cell_region: device, 2-byte aligned.  Nothing is read outside the map, nothing is written
+ * outside points[0, n), cells[0, t) and cell_region[0, t); no atomic cursor places anything: the same input gives the
+ * same bytes.  Both synchronise the stream.
+ * FNN_E_INVALID before any launch, with a message: NULL or host pointers, an unknown label dtype, n_regions outside
+ * 1..1024, a negative n_table, a negative extent, an affine that is not finite, negative smoothing_pairs, a layout other
+ * than 0 and 1, a negative cap, misaligned pointers; FNN_E_UNSUPPORTED: more than 2^31 - 1 voxels, vertices or triangles.
+ * A volume without voxels and regions without voxels give zeros and launch nothing for them.
+ * Scratch, allocated inside the call: 8 B + 24 B per region and 8 B per table value and 64 regions; per region with faces
+ * 36 B + 8 B; 196 B per 1024 corners of the regions' boxes (one bit per corner, a 4-byte prefix per 64 corners and per
+ * 1024 corners) + 4 B per 1024 voxels of the boxes (the faces' scan); fnn_mesh_emit also 12 B per vertex, and 48 B per
+ * vertex when it smooths (two position buffers for the Jacobi passes and six neighbour indices). */
+int fnn_mesh_count(const void *seg, int label_dtype, const int64_t shape[3], const uint8_t *member, int n_table,
+                   int n_regions, int64_t *counts, int64_t *boxes, void *stream);
+int fnn_mesh_emit(const void *seg, int label_dtype, const int64_t shape[3], const uint8_t *member, int n_table,
+                  int n_regions, const double affine[16], int smoothing_pairs, int layout, void *points,
+                  int64_t cap_points, void *cells, int64_t cap_cells, void *cell_region, void *stream);
+
 /* The voxels of an image file as the file holds them -> float32 (additive in ABI 4): what the reference's
  * NibabelIO.read_images ends with (imageio/nibabel_reader_writer.py:56 and :89 - get_fdata() in float64, then
  * np.vstack(..., dtype=float32, casting='unsafe')) for one file, without the host cast.  raw: device pointer to the first
