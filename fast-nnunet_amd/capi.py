@@ -78,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -152,6 +152,9 @@ def load_library() -> C.CDLL:
         lib.fnn_mesh_count.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(i64), C.POINTER(i64), vp]
         lib.fnn_mesh_emit.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_uint8), i32, i32, C.POINTER(C.c_double), i32, i32, vp, i64,
                                       vp, i64, vp, vp]
+    if hasattr(lib, 'fnn_mesh_decimate'):
+        lib.fnn_mesh_decimate.argtypes = [vp, i64, vp, vp, i64, C.POINTER(i64), i32, C.c_double, i32, vp, i64, vp, i64, vp, C.POINTER(i64),
+                                          C.POINTER(i64), vp]
     lib.fnn_decode_voxels.argtypes =[vp, i32, i32, i64, i32, C.c_double, C.c_double, vp, vp]
     lib.fnn_decode_labels.argtypes = [vp, i32, i32, i64, i32, C.c_double, C.c_double, i32, vp, vp, vp]
     lib.fnn_reorient.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, vp]
@@ -548,6 +551,26 @@ def mesh_emit(seg_ptr: int, uint16: bool, shape, member, affine, smoothing_pairs
     check(lib.fnn_mesh_emit(seg_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, (C.c_int64 * 3)(*[int(i) for i in shape]), mp,
                             int(n_table), int(n_regions), (C.c_double * 16)(*a.tolist()), int(smoothing_pairs), int(layout),
                             points_ptr, int(cap_points), cells_ptr, int(cap_cells), cell_region_ptr, stream), lib)
+
+
+def mesh_decimate(points_ptr: int, n: int, cells_ptr: int, cell_region_ptr: int, t: int, point_offsets, decimation_factor: float,
+                  layout: int, out_points_ptr: int, cap_points: int, out_cells_ptr: int, cap_cells: int, out_cell_region_ptr: int,
+                  stream: int = 0):
+    """fnn_mesh_decimate on a layout-0 device model of ``n`` points and ``t`` triangles; ``point_offsets`` int64
+    [n_regions + 1].  Returns (counts int64 [n_regions, 2] = points and triangles of every region, n_out, t_out, rounds,
+    exhausted)."""
+    lib = load_library()
+    if not hasattr(lib, 'fnn_mesh_decimate'):
+        raise EngineError(f'{LIB_PATH} has no fnn_mesh_decimate: rebuild the library')
+    off = np.ascontiguousarray(point_offsets, dtype=np.int64).reshape(-1)
+    n_regions = len(off) - 1
+    counts = np.zeros((max(n_regions, 1), 2), np.int64)
+    status = np.zeros(4, np.int64)
+    P64 = C.POINTER(C.c_int64)
+    check(lib.fnn_mesh_decimate(points_ptr, int(n), cells_ptr, cell_region_ptr, int(t), off.ctypes.data_as(P64), int(n_regions),
+                                float(decimation_factor), int(layout), out_points_ptr, int(cap_points), out_cells_ptr, int(cap_cells),
+                                out_cell_region_ptr, counts.ctypes.data_as(P64), status.ctypes.data_as(P64), stream), lib)
+    return counts[:n_regions], int(status[0]), int(status[1]), int(status[2]), int(status[3])
 
 
 INSTANCE_FIRST_CAPACITY = 65536        # records the first call of instance_overlaps has room for

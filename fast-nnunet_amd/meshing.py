@@ -1,5 +1,6 @@
 """Surface models of a label map: one closed triangle surface per label or region, made on the GPU by ``fnn_mesh_count`` /
-``fnn_mesh_emit`` (csrc/mesh.hip), and a legacy-VTK PolyData writer for them.
+``fnn_mesh_emit`` (csrc/mesh.hip), thinned there by ``fnn_mesh_decimate`` (csrc/mesh_decimate.hip), and a legacy-VTK
+PolyData writer for them.
 
 This is what the reference's front end calls ``VTKModelGenerator(color_file_path=...).generate_vtk_model(mask_path=...,
 output_path=..., smoothing_factor=0.5, decimation_factor=0.2)`` for.  The generator's own source is not part of the
@@ -7,7 +8,11 @@ reference, so the surface is this project's definition (include/fnn.h states it)
 everything else, Taubin-smoothed on the lattice graph, in world coordinates.  Differences a caller of the reference meets:
 
 * ``smoothing_factor`` s in [0, 1] means ``round(PAIRS_AT_FACTOR_ONE * s)`` Taubin pairs (f = 0.5, then f = -0.53);
-* decimation is not built: ``decimation_factor`` other than 0 raises NotImplementedError (the reference passes 0.2);
+* ``decimation_factor`` d in [0, 1) asks for ceil((1 - d) * triangles) triangles by rounds of quadric-error edge collapse
+  on the GPU (include/fnn.h states the rule); a surface whose non-manifold edges leave no candidate stops early and says so
+  (``exhausted``).  ``label_surfaces`` and ``decimate_surfaces`` take it; ``VTKModelGenerator`` honours it when it is made
+  with ``decimation=True`` and otherwise still raises NotImplementedError for a factor other than 0 (the reference passes
+  0.2), so that nobody gets a decimated model without asking;
 * no foreign reader has opened the files: ``read_vtk_polydata`` reads exactly what ``write_vtk_polydata`` makes.
 
 Colours: a region takes the colour of its smallest label id from the colour table (``read_color_table``: the reference's
@@ -38,13 +43,16 @@ VTK_TITLE = 'fast-nnunet_amd surface model'
 class SurfaceModel:
     """points float32 [n, 3] (world x, y, z); triangles int32 [m, 3] into points; triangle_region uint16 [m]: the index
     into ``regions`` (tuples of label ids); region k owns points[point_offsets[k]:point_offsets[k + 1]] and
-    triangles[triangle_offsets[k]:triangle_offsets[k + 1]]."""
+    triangles[triangle_offsets[k]:triangle_offsets[k + 1]].  rounds, exhausted: what a decimation reported (exhausted: it
+    stopped above its target because no edge could be collapsed any more, or at its limit of rounds)."""
     points: np.ndarray
     triangles: np.ndarray
     triangle_region: np.ndarray
     regions: List[Tuple[int, ...]]
     point_offsets: np.ndarray
     triangle_offsets: np.ndarray
+    rounds: int = 0
+    exhausted: int = 0
 
 
 def smoothing_pairs(smoothing_factor: float) -> int:
@@ -52,6 +60,13 @@ def smoothing_pairs(smoothing_factor: float) -> int:
     if not 0.0 <= s <= 1.0:                                         # (a NaN fails both comparisons)
         raise ValueError(f'smoothing_factor must lie in [0, 1], got {smoothing_factor}')
     return int(round(PAIRS_AT_FACTOR_ONE * s))
+
+
+def check_decimation(decimation_factor: float) -> float:
+    d = float(decimation_factor)
+    if not 0.0 <= d < 1.0:                                          # (a NaN fails both comparisons)
+        raise ValueError(f'decimation_factor must lie in [0, 1), got {decimation_factor}')
+    return d
 
 
 def fallback_color(label_id: int) -> Tuple[str, int, int, int, int]:
@@ -183,12 +198,30 @@ class _DeviceMesh:
         self.triangle_offsets = np.concatenate([[0], np.cumsum(2 * self.counts[:, 1])]).astype(np.int64)
         n, t = int(self.point_offsets[-1]), int(self.triangle_offsets[-1])
         self.n, self.t = n, t
+        self.triangle_counts = 2 * self.counts[:, 1]
+        self.rounds = self.exhausted = 0
         self.points = torch.empty(max(n, 1) * 12, dtype=torch.uint8, device=dev)
         self.cells = torch.empty(max(t, 1) * (16 if layout else 12), dtype=torch.uint8, device=dev)
         self.cell_region = torch.empty(max(t, 1) * 2, dtype=torch.uint8, device=dev)
         if t:
             capi.mesh_emit(seg.data_ptr(), u16, seg.shape, member, affine, pairs, layout, self.points.data_ptr(), n,
                            self.cells.data_ptr(), t, self.cell_region.data_ptr(), stream)
+
+    def decimated(self, decimation_factor: float, layout: int) -> '_DeviceMesh':
+        """fnn_mesh_decimate of this layout-0 mesh into buffers of their own, in ``layout``."""
+        assert self.layout == 0
+        out = object.__new__(_DeviceMesh)
+        out.regions, out.layout, out.boxes = self.regions, layout, self.boxes
+        out.points, out.cell_region = torch.empty_like(self.points), torch.empty_like(self.cell_region)
+        out.cells = torch.empty(max(self.t, 1) * (16 if layout else 12), dtype=torch.uint8, device=self.points.device)
+        counts, out.n, out.t, out.rounds, out.exhausted = capi.mesh_decimate(
+            self.points.data_ptr(), self.n, self.cells.data_ptr(), self.cell_region.data_ptr(), self.t, self.point_offsets, decimation_factor,
+            layout, out.points.data_ptr(), self.n, out.cells.data_ptr(), self.t, out.cell_region.data_ptr(),
+            torch.cuda.current_stream(self.points.device).cuda_stream)
+        out.counts, out.triangle_counts = counts, counts[:, 1].copy()
+        out.point_offsets = np.concatenate([[0], np.cumsum(counts[:, 0])]).astype(np.int64)
+        out.triangle_offsets = np.concatenate([[0], np.cumsum(counts[:, 1])]).astype(np.int64)
+        return out
 
     def payload(self) -> Tuple[bytes, bytes, bytes]:
         return (self.points[:self.n * 12].cpu().numpy().tobytes(), self.cells[:self.t * (16 if self.layout else 12)].cpu().numpy().tobytes(),
@@ -208,7 +241,7 @@ def _present_labels(seg: torch.Tensor, top: int) -> List[Tuple[int, ...]]:
     return present
 
 
-def _device_mesh(seg, labels_or_regions, a: np.ndarray, pairs: int, layout: int, device=None) -> _DeviceMesh:
+def _device_mesh(seg, labels_or_regions, a: np.ndarray, pairs: int, layout: int, device=None, decimation: float = 0.0) -> _DeviceMesh:
     regions = None if labels_or_regions is None else _check_regions(labels_or_regions)
     top = _check_map(seg)
     dev = seg.device if isinstance(seg, torch.Tensor) and seg.device.type == 'cuda' else (torch.device(device) if device is not None else _device())
@@ -216,21 +249,50 @@ def _device_mesh(seg, labels_or_regions, a: np.ndarray, pairs: int, layout: int,
         t = _to_device(seg, top, dev)
         if regions is None:
             regions = _present_labels(t, top) if t.numel() else []
-        return _DeviceMesh(t, regions, a, pairs, layout)
+        if decimation == 0.0:
+            return _DeviceMesh(t, regions, a, pairs, layout)
+        return _DeviceMesh(t, regions, a, pairs, 0).decimated(decimation, layout)   # emitted in layout 0, decimated into `layout`
 
 
 def label_surfaces(seg, labels_or_regions=None, affine=None, spacing=None, smoothing_factor: float = 0.0,
-                   coordinate_system: str = 'RAS') -> SurfaceModel:
+                   coordinate_system: str = 'RAS', decimation_factor: float = 0.0) -> SurfaceModel:
     """The surfaces of a label map (z, y, x; numpy, or a torch tensor that is used where it lies when it is on the GPU) as a
     ``SurfaceModel``.  ``labels_or_regions``: label ids or tuples of ids, None for every foreground value present.  Give a 4x4
     ``affine`` from index (x, y, z) to world, or a ``spacing`` (z, y, x) for diag(sx, sy, sz), or neither for the identity.
-    ``coordinate_system='LPS'`` negates the first two world axes.  An int16 device tensor carries uint16 bits."""
+    ``coordinate_system='LPS'`` negates the first two world axes.  An int16 device tensor carries uint16 bits.
+    ``decimation_factor`` d in [0, 1): the model is decimated on the device to ceil((1 - d) * triangles) triangles before it
+    is downloaded; 0 makes the GPU calls of a plain surface."""
     pairs = smoothing_pairs(smoothing_factor)
+    d = check_decimation(decimation_factor)
     a = _check_affine(affine, spacing, coordinate_system)
-    m = _device_mesh(seg, labels_or_regions, a, pairs, 0)
+    return _model_of(_device_mesh(seg, labels_or_regions, a, pairs, 0, decimation=d))
+
+
+def _model_of(m: _DeviceMesh) -> SurfaceModel:
     pts, cells, reg = m.payload()
     return SurfaceModel(np.frombuffer(pts, np.float32).reshape(-1, 3).copy(), np.frombuffer(cells, np.int32).reshape(-1, 3).copy(),
-                        np.frombuffer(reg, np.uint16).copy(), list(m.regions), m.point_offsets, m.triangle_offsets)
+                        np.frombuffer(reg, np.uint16).copy(), list(m.regions), m.point_offsets, m.triangle_offsets, m.rounds, m.exhausted)
+
+
+def decimate_surfaces(model: SurfaceModel, decimation_factor: float, device=None) -> SurfaceModel:
+    """``model`` with ceil((1 - decimation_factor) * triangles) triangles (fnn_mesh_decimate): what
+    ``label_surfaces(..., decimation_factor=...)`` gives for the map the model was made from."""
+    d = check_decimation(decimation_factor)
+    points = np.ascontiguousarray(model.points, np.float32).reshape(-1, 3)
+    triangles = np.ascontiguousarray(model.triangles, np.int32).reshape(-1, 3)
+    region = np.ascontiguousarray(model.triangle_region, np.uint16).reshape(-1)
+    offsets = np.asarray(model.point_offsets, np.int64).reshape(-1)
+    if len(region) != len(triangles) or len(offsets) != len(model.regions) + 1 or offsets[0] != 0 or offsets[-1] != len(points):
+        raise ValueError('the model\'s triangle_region or point_offsets do not fit its points, triangles and regions')
+    if len(triangles) and (triangles.min() < 0 or triangles.max() >= len(points) or (len(region) and region.max() >= len(model.regions))):
+        raise ValueError('a triangle of the model names a point or a region that is not there')
+    dev = torch.device(device) if device is not None else _device()
+    with torch.cuda.device(dev):
+        m = object.__new__(_DeviceMesh)
+        m.regions, m.layout, m.boxes, m.n, m.t = list(model.regions), 0, None, len(points), len(triangles)
+        up = lambda arr: torch.from_numpy(np.frombuffer(arr.tobytes() or b'\0', np.uint8).copy()).to(dev)
+        m.points, m.cells, m.cell_region, m.point_offsets = up(points), up(triangles), up(region), offsets
+        return _model_of(m.decimated(d, 0))
 
 
 def _vtk_file(path: str, n: int, t: int, points: bytes, cells: bytes, labels: np.ndarray, colors: np.ndarray) -> None:
@@ -332,22 +394,28 @@ class VTKModelGenerator:
     """The reference's generator: ``VTKModelGenerator(color_file_path).generate_vtk_model(mask_path, output_path, ...)`` turns
     a label file into a coloured legacy-VTK PolyData model, one surface per label present."""
 
-    def __init__(self, color_file_path: Optional[str] = None, device=None):
+    def __init__(self, color_file_path: Optional[str] = None, device=None, decimation: bool = False):
+        """``decimation=True``: honour ``decimation_factor`` in [0, 1) (the model is decimated on the device before it is
+        downloaded); the default refuses a factor other than 0, as before decimation was built."""
         self.colors = read_color_table(color_file_path) if color_file_path is not None else None
         self.device = device
+        self.decimation = bool(decimation)
 
-    @staticmethod
-    def _check(smoothing_factor, decimation_factor) -> int:
-        if decimation_factor != 0:
-            raise NotImplementedError(f'decimation_factor={decimation_factor}: decimation is not built, pass decimation_factor=0 '
-                                      f'(the reference passes 0.2)')
-        return smoothing_pairs(smoothing_factor)
+    def _check(self, smoothing_factor, decimation_factor) -> Tuple[int, float]:
+        if self.decimation:
+            d = check_decimation(decimation_factor)
+        elif decimation_factor != 0:
+            raise NotImplementedError(f'decimation_factor={decimation_factor}: this generator was not made to decimate, make it with '
+                                      f'VTKModelGenerator(..., decimation=True) or pass decimation_factor=0 (the reference passes 0.2)')
+        else:
+            d = 0.0
+        return smoothing_pairs(smoothing_factor), d
 
-    def _write(self, seg, affine, output_path: str, pairs: int, coordinate_system: str) -> str:
+    def _write(self, seg, affine, output_path: str, pairs_d: Tuple[int, float], coordinate_system: str) -> str:
         a = _check_affine(affine, None, coordinate_system)
-        m = _device_mesh(seg, None, a, pairs, 1, self.device)
+        m = _device_mesh(seg, None, a, pairs_d[0], 1, self.device, decimation=pairs_d[1])
         points, cells, _ = m.payload()                              # the file's POINTS and POLYGONS bytes as the device stored them
-        labels, rgba = _cell_data(m.regions, 2 * m.counts[:, 1], self.colors)
+        labels, rgba = _cell_data(m.regions, m.triangle_counts, self.colors)
         _vtk_file(str(output_path), m.n, m.t, points, cells, labels, rgba)
         return output_path
 

@@ -520,6 +520,68 @@ int fnn_mesh_emit(const void *seg, int label_dtype, const int64_t shape[3], cons
                   int n_regions, const double affine[16], int smoothing_pairs, int layout, void *points,
                   int64_t cap_points, void *cells, int64_t cap_cells, void *cell_region, void *stream);
 
+/* Fewer triangles for such a model (additive in ABI 4): data-parallel rounds of quadric-error edge collapse, what the
+ * reference's callers ask of VTKModelGenerator with decimation_factor = 0.2.  As with the surface, the rule below is this
+ * project's own; tests/mesh_decimate_ref.py restates it in numpy and the kernels are held to it bit for bit.
+ * Input: the layout-0 result of fnn_mesh_emit on the device - points float32 [n][3], cells int32 [t][3], cell_region
+ * uint16 [t] - and point_offsets (host [n_regions + 1], rising from 0 to n): region r owns the points [point_offsets[r],
+ * point_offsets[r + 1]).  Every cell must name three different points below n and a region below n_regions.  Nothing in
+ * the rule looks at regions: regions never share a point, so no edge crosses them.
+ * Target: target = ceil((1 - d) * t) in float64, d = decimation_factor in [0, 1).  d == 0 with layout 0 returns the input
+ * byte for byte by three device copies and launches nothing; d == 0 with layout 1 runs the output step alone.
+ * Quadrics: one symmetric 4x4 matrix per point as 10 float64 (xx xy xz xw yy yz yw zz zw ww).  For a triangle (a, b, c):
+ * n = (b - a) x (c - a) with n.x = uy vz - uz vy, n.y = uz vx - ux vz, n.z = ux vy - uy vx (u = b - a, v = c - a),
+ * k = -((n.x a.x + n.y a.y) + n.z a.z), K = (n, k); Q[p] = 0 + the 10 products K_i K_j of p's triangles in ascending
+ * triangle index.  From the input mesh, once; float64, every operation rounded on its own (no fused multiply-add), as
+ * everything below.  When b merges into a, Q[a] = Q[a] + Q[b].
+ * A round, numbered from 0.  valence(w) is the number of live triangles that hold w.  The undirected edge (a, b), a < b, is
+ * a candidate iff all of these hold:
+ *   valence(a) <= 32 and valence(b) <= 32 (the bound on the work of one candidate; part of the rule);
+ *   exactly one live triangle runs a -> b (it is (a, b, c1) up to rotation) and exactly one runs b -> a ((b, a, c2)) - so
+ *   exactly two triangles hold both ends, and an edge with four faces, where voxels touch along an edge only, is never
+ *   collapsed;
+ *   c1 != c2, valence(c1) > 3 and valence(c2) > 3;
+ *   no vertex other than c1 and c2 is a neighbour (shares a live triangle) of both a and b (the link condition);
+ *   with p the chosen position, every live triangle that holds exactly one of a, b has ((n0.x n1.x + n0.y n1.y) + n0.z n1.z)
+ *   > 0, n0 its normal as above from the current float32 positions and n1 the same with the end replaced by p.
+ * Position and cost: Qs = Q[a] + Q[b]; cost(p) = float32(max(c, 0)) with, for (x, y, z) = p in float64,
+ *   r0 = ((Qs.xx x + Qs.xy y) + Qs.xz z) + Qs.xw, r1 = ((Qs.xy x + Qs.yy y) + Qs.yz z) + Qs.yw,
+ *   r2 = ((Qs.xz x + Qs.yz y) + Qs.zz z) + Qs.zw, r3 = ((Qs.xw x + Qs.yw y) + Qs.zw z) + Qs.ww,
+ *   c = ((x r0 + y r1) + z r2) + r3 (a c that is not > 0 counts as 0).
+ * p is the midpoint (p[a] + p[b]) * 0.5f in float32, then p[a], then p[b]: a later one replaces an earlier one only when
+ * its cost is smaller.
+ * Key, a total order: (the bits of cost(p) as uint32, hash32(a, b, round), a, b), compared left to right;
+ *   hash32: x = (a * 0x9E3779B1) ^ (b * 0x85EBCA77) ^ (round * 0xC2B2AE3D); x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13;
+ *   x *= 0xC2B2AE35; x ^= x >> 16, all in uint32.
+ * Selection: best1[w] is the smallest key among the candidates with the end w, best2[w] the smallest best1 over w and its
+ * neighbours; an edge is selected iff its key equals best2 at both ends.  Selected edges share no vertex and no triangle.
+ * If the live triangles minus twice the selected edges would fall below target, only the ceil((live - target) / 2) selected
+ * edges with the smallest keys are applied.  Applying (a, b): p[a] = p, Q[a] = Q[a] + Q[b], every b in a triangle becomes
+ * a, and the two triangles that held both are dropped; the other triangles keep their order.
+ * End: the rounds stop when the live triangles are at most target (t_out is target or target - 1), or with exhausted = 1
+ * when a round has no candidate or 128 rounds have been applied.
+ * Output: the surviving triangles in their order, the points they name in their order, renumbered; winding untouched;
+ * every region's points and triangles stay contiguous.  layout 0 and 1 as fnn_mesh_emit defines them; out_points 4-byte,
+ * out_cells 4-byte (layout 0) or 16-byte (layout 1), out_cell_region 2-byte aligned, all device.  cap_points counts points
+ * and cap_cells triangles; a cap below the result writes nothing and is FNN_E_INVALID with the number needed in the
+ * message (n and t always suffice).  counts (host [n_regions][2]): the points and the triangles of every region.
+ * status: n_out, t_out, the rounds applied, exhausted.  Nothing is written outside out_*[0, result).  Two things are placed
+ * by an atomic cursor and neither decides a byte: the entries of a point's triangle list (sorted before the quadrics read
+ * them in order; everything else takes counts, minima and existence from them) and the keys of the selected edges, which
+ * the host reads only to cut the last round.  The same input gives the same bytes.  The stream is synchronised.
+ * FNN_E_INVALID before any launch, with a message: NULL point_offsets, counts or status, a negative n or t, n_regions
+ * outside 0..1024, a decimation_factor outside [0, 1) or not finite, a layout other than 0 and 1, a negative cap,
+ * point_offsets that do not rise from 0 to n, triangles without a region, misaligned pointers, NULL or host pointers for
+ * the model or the result; FNN_E_UNSUPPORTED: more than 2^31 - 1 points or triangle corners.  t == 0 gives zeros and
+ * launches nothing.  A cell that breaks the input's rule is FNN_E_INVALID after one checking kernel.
+ * Scratch, allocated inside the call: 144 B per point (position, quadric, list start, cursor, merge target, four key words,
+ * selected keys) + 95 B per triangle (two copies of the cells and regions, the lists, two key words and a choice per
+ * half-edge, the compaction's flags) + 4 B per 1024 of the larger + 40 B + 24 B per region. */
+int fnn_mesh_decimate(const float *points, int64_t n, const int32_t *cells, const uint16_t *cell_region, int64_t t,
+                      const int64_t *point_offsets, int n_regions, double decimation_factor, int layout, void *out_points,
+                      int64_t cap_points, void *out_cells, int64_t cap_cells, void *out_cell_region, int64_t *counts,
+                      int64_t status[4], void *stream);
+
 /* The voxels of an image file as the file holds them -> float32 (additive in ABI 4): what the reference's
  * NibabelIO.read_images ends with (imageio/nibabel_reader_writer.py:56 and :89 - get_fdata() in float64, then
  * np.vstack(..., dtype=float32, casting='unsafe')) for one file, without the host cast.  raw: device pointer to the first
