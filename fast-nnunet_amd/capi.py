@@ -78,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -161,6 +161,7 @@ def load_library() -> C.CDLL:
     lib.fnn_deflate_bound.argtypes = [i64]
     lib.fnn_deflate_bound.restype = i64
     lib.fnn_deflate_labels.argtypes = [vp, i32, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_uint32), vp]
+    lib.fnn_deflate_labels_dyn.argtypes = [vp, i32, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i32), C.POINTER(C.c_uint32), C.POINTER(i64), vp]
     lib.fnn_deflate_masks_work_bytes.argtypes = [i64, i32]
     lib.fnn_deflate_masks_work_bytes.restype = i64
     lib.fnn_deflate_masks_count.argtypes = [vp, i32, i64, C.POINTER(C.c_int32), i32, vp, i64, C.POINTER(i64), C.POINTER(C.c_uint32), vp]
@@ -407,6 +408,18 @@ def deflate_labels(in_ptr: int, in_elem_bytes: int, n_elems: int, narrow_if_fits
     check(lib.fnn_deflate_labels(in_ptr, int(in_elem_bytes), int(n_elems), int(bool(narrow_if_fits)), out_ptr, int(out_cap),
                                  C.byref(out_bytes), C.byref(file_elem), C.byref(crc), stream), lib)
     return int(out_bytes.value), int(file_elem.value), int(crc.value)
+
+
+def deflate_labels_dyn(in_ptr: int, in_elem_bytes: int, n_elems: int, narrow_if_fits: bool, out_ptr: int, out_cap: int,
+                       stream: int = 0) -> Tuple[int, int, int, int]:
+    """fnn_deflate_labels_dyn: ``deflate_labels`` with per-chunk dynamic Huffman tables - the same arguments and refusals.
+    Returns ``(bytes written, bytes per element in the file, CRC-32 of the file bytes, chunks that took their own
+    tables)``; synchronises `stream`."""
+    lib = load_library()
+    out_bytes, file_elem, crc, dynamic = C.c_int64(-1), C.c_int(0), C.c_uint32(0), C.c_int64(-1)
+    check(lib.fnn_deflate_labels_dyn(in_ptr, int(in_elem_bytes), int(n_elems), int(bool(narrow_if_fits)), out_ptr, int(out_cap),
+                                     C.byref(out_bytes), C.byref(file_elem), C.byref(crc), C.byref(dynamic), stream), lib)
+    return int(out_bytes.value), int(file_elem.value), int(crc.value), int(dynamic.value)
 
 
 def deflate_masks_work_bytes(n_elems: int, n_labels: int) -> int:

@@ -7,6 +7,7 @@
 """
 from __future__ import annotations
 
+import functools
 import os
 import pickle
 import queue
@@ -133,11 +134,31 @@ def as_plain_labels(labels: torch.Tensor) -> torch.Tensor:
     return labels if labels.dtype == torch.uint8 else labels.to(torch.int32) & 0xffff
 
 
-def device_compressor(rw, compress_on_device: bool, file_ending: str, method: str = 'compress_labels'):
+def compress_mode(compress_on_device):
+    """What the ``compress_on_device`` switch of the predictors and the folder commands accepts -> False, True (the fixed
+    Huffman code of ``fnn_deflate_labels``) or ``'dynamic'`` (per-chunk tables, ``fnn_deflate_labels_dyn``); anything else
+    is a ValueError."""
+    if isinstance(compress_on_device, str):
+        if compress_on_device == 'dynamic':
+            return 'dynamic'
+    elif isinstance(compress_on_device, (bool, int, np.bool_)) and compress_on_device in (0, 1):
+        return bool(compress_on_device)
+    raise ValueError(f"compress_on_device must be False, True or 'dynamic', got {compress_on_device!r}")
+
+
+def device_compressor(rw, compress_on_device, file_ending: str, method: str = 'compress_labels'):
     """The reader-writer's ``method`` (``compress_labels`` or ``compress_label_masks``) when labels bound for a file of
-    ``file_ending`` are to be compressed on the device and ``rw`` can; else None."""
-    if compress_on_device and str(file_ending).lower().endswith('.nii.gz'):
-        return getattr(rw, method, None)
+    ``file_ending`` are to be compressed on the device and ``rw`` can; else None.  ``compress_on_device='dynamic'`` is
+    ``compress_labels`` with ``tables='dynamic'``; the mask encoder has no dynamic tables (NotImplementedError)."""
+    mode = compress_mode(compress_on_device)
+    if mode == 'dynamic' and method != 'compress_labels':
+        raise NotImplementedError(f"compress_on_device='dynamic': {method} (the per-label mask encoder, csrc/deflate_masks.hip) "
+                                  "writes the fixed Huffman code only; use compress_on_device=True")
+    if mode and str(file_ending).lower().endswith('.nii.gz'):
+        fn = getattr(rw, method, None)
+        if fn is not None and mode == 'dynamic':
+            return functools.partial(fn, tables='dynamic')
+        return fn
     return None
 
 

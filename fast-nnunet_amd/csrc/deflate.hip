@@ -1,6 +1,8 @@
 // deflate.hip - a label map on the device -> the raw-deflate bytes of its .nii.gz voxel block, gfx950.
 //
-//   fnn_deflate_labels   1- or 2-byte labels -> a fragment of a deflate stream, its size, and the CRC-32 of the file bytes
+//   fnn_deflate_labels       1- or 2-byte labels -> a fragment of a deflate stream, its size, and the CRC-32 of the file bytes
+//   fnn_deflate_labels_dyn   the same call with per-chunk dynamic Huffman tables: this file's host code and max / scan
+//                            kernels, the count and emit kernels of csrc/deflate_dyn.hip
 //
 // The stream format, and what a lane does with its segment of a chunk, is deflate_core.h; the steps of a wave are
 // deflate_wave.h.  One wave encodes one chunk.  The rule - runs of equal elements become matches - finds what label maps
@@ -18,6 +20,7 @@
 // count kernel 17.5 KiB, the emit kernel 34.3 KiB.  Nothing is written outside out[0, out_bytes); no kernel keeps scratch.
 #include "fnn_device.h"
 #include "deflate_wave.h"
+#include "deflate_dyn_launch.h"
 #include "owned.h"
 #include "../../include/fnn.h"
 #include <climits>
@@ -40,46 +43,6 @@ __global__ __launch_bounds__(DF_MAX_THREADS) void deflate_max_kernel(const uint1
     if (blockIdx.x == 0 && threadIdx.x < (int)(n - vecs * 8)) m = max(m, (unsigned)in[vecs * 8 + threadIdx.x]);
     for (int s = 32; s > 0; s >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, s));
     if ((threadIdx.x & 63) == 0 && m) atomicMax(max_out, m);
-}
-
-// the file bytes [16 v, 16 v + 16) of chunk `c`, bytes past `len` (the chunk's length) as 0
-template <bool NARROW>
-static __device__ __forceinline__ u32x4 load_vec(const uint8_t *in, long long c, int v, int len) {
-    const int b0 = v * 16;
-    u32x4 d = {0u, 0u, 0u, 0u};
-    if (!NARROW) {
-        const uint8_t *p = in + c * DF_CHUNK + b0;
-        if (b0 + 16 <= len) return *(const u32x4 *)p;
-        for (int j = 0; b0 + j < len; ++j) d[j >> 2] |= (unsigned)p[j] << ((j & 3) * 8);
-    } else {
-        const uint16_t *p = (const uint16_t *)in + c * DF_CHUNK + b0;
-        if (b0 + 16 <= len) {
-            const u32x4 lo = ((const u32x4 *)p)[0], hi = ((const u32x4 *)p)[1];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                d[k] = (lo[2 * k] & 255u) | ((lo[2 * k] >> 8) & 0xFF00u) | ((lo[2 * k + 1] & 255u) << 16) | ((lo[2 * k + 1] & 0xFF0000u) << 8);
-                d[2 + k] = (hi[2 * k] & 255u) | ((hi[2 * k] >> 8) & 0xFF00u) | ((hi[2 * k + 1] & 255u) << 16) | ((hi[2 * k + 1] & 0xFF0000u) << 8);
-            }
-            return d;
-        }
-        for (int j = 0; b0 + j < len; ++j) d[j >> 2] |= ((unsigned)p[j] & 255u) << ((j & 3) * 8);
-    }
-    return d;
-}
-
-// chunk `c` of the file bytes -> s_in, segment s at dword s * DF_PITCH; -> the chunk's length in bytes
-template <bool NARROW>
-static __device__ __forceinline__ int load_chunk(const uint8_t *in, long long n_bytes, long long c, unsigned *s_in) {
-    const long long left = n_bytes - c * DF_CHUNK;
-    const int len = left < DF_CHUNK ? (int)left : DF_CHUNK;
-    const int vecs = (len + 15) / 16;
-    for (int v = threadIdx.x; v < vecs; v += DF_LANES) {
-        const u32x4 d = load_vec<NARROW>(in, c, v, len);
-        unsigned *q = s_in + (v >> 4) * DF_PITCH + (v & 15) * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = d[k];
-    }
-    return len;
 }
 
 template <int ELEM, bool NARROW>
@@ -171,8 +134,9 @@ extern "C" int64_t fnn_deflate_bound(int64_t n_bytes) {
     return (9 * n_bytes + 7) / 8 + 6 * ((n_bytes + DF_CHUNK - 1) / DF_CHUNK);
 }
 
-extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out,
-                                  int64_t out_cap, int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, void *stream) {
+// fnn_deflate_labels (dyn false) and fnn_deflate_labels_dyn: one contract, one prologue, the kernels of this file or of deflate_dyn.hip
+static int deflate_labels(bool dyn, const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
+                          int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, int64_t *dynamic_chunks, void *stream) {
     FnnOpKlog klog;
     if (!in || !out || !out_bytes || !file_elem_bytes || !crc32) return fnn_fail(FNN_E_INVALID, "NULL argument");
     if (in_elem_bytes != 1 && in_elem_bytes != 2) return fnn_fail(FNN_E_INVALID, "fnn_deflate_labels: labels of 1 or 2 bytes are served");
@@ -187,12 +151,14 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
     *out_bytes = 0;
     *crc32 = 0;
     *file_elem_bytes = narrow_if_fits ? 1 : in_elem_bytes;
+    if (dynamic_chunks) *dynamic_chunks = 0;
     if (n_elems == 0) return FNN_OK;
 
     const long long max_chunks = (in_bytes + DF_CHUNK - 1) / DF_CHUNK;
     const size_t o_max = 0, o_x2k = 16, o_off = o_x2k + sizeof(g_tables.x2k), o_bytes = o_off + df_align16((size_t)(max_chunks + 1) * 8),
                  o_crc = o_bytes + df_align16((size_t)max_chunks * 4), o_bits = o_crc + df_align16((size_t)max_chunks * 4),
-                 total = o_bits + (size_t)max_chunks * DF_LANES * 2;
+                 o_hdr = o_bits + df_align16((size_t)max_chunks * DF_LANES * 2), o_rec = o_hdr + (dyn ? df_align16((size_t)max_chunks * 4) : 0),
+                 total = o_rec + (dyn ? (size_t)max_chunks * DF_DYN_REC_DWORDS * 4 : 0);   // (not dyn: o_hdr is the end, as it was)
     DevBuf scratch;
     if (!scratch.alloc(total)) return fnn_fail(FNN_E_HIP, "hipMalloc failed (deflate scratch)");
     unsigned *d_max = scratch.as<unsigned>(o_max);
@@ -201,6 +167,7 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
     unsigned *d_bytes = scratch.as<unsigned>(o_bytes);
     uint32_t *d_crc = scratch.as<uint32_t>(o_crc);
     uint16_t *d_bits = scratch.as<uint16_t>(o_bits);
+    uint32_t *d_hdr = scratch.as<uint32_t>(o_hdr), *d_rec = scratch.as<uint32_t>(o_rec);   // dyn only
     hipStream_t st = (hipStream_t)stream;
     hipError_t r = hipMemcpyAsync(d_x2k, g_tables.x2k, sizeof(g_tables.x2k), hipMemcpyHostToDevice, st);
     int elem = in_elem_bytes;
@@ -219,10 +186,12 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
         if (r == hipSuccess && h_max < 255) elem = 1;
     }
     const bool narrow = elem != in_elem_bytes;
-    const long long n_bytes = (long long)n_elems * elem, chunks = (n_bytes + DF_CHUNK - 1) / DF_CHUNK;
     const uint8_t *src = (const uint8_t *)in;
+    const long long n_bytes = (long long)n_elems * elem, chunks = (n_bytes + DF_CHUNK - 1) / DF_CHUNK;
+    const DfDynArgs dyn_args{src, n_bytes, chunks, d_x2k, d_bits, d_bytes, d_crc, d_hdr, d_rec, d_off, (uint8_t *)out};
     for (int pass = 0; pass < 2 && r == hipSuccess; ++pass) {
-        if (narrow) launch_pair<1, true>(pass, src, n_bytes, chunks, d_x2k, d_bits, d_bytes, d_crc, d_off, (uint8_t *)out, st);
+        if (dyn) df_dyn_launch(pass, elem, narrow, dyn_args, st);
+        else if (narrow) launch_pair<1, true>(pass, src, n_bytes, chunks, d_x2k, d_bits, d_bytes, d_crc, d_off, (uint8_t *)out, st);
         else if (elem == 1) launch_pair<1, false>(pass, src, n_bytes, chunks, d_x2k, d_bits, d_bytes, d_crc, d_off, (uint8_t *)out, st);
         else launch_pair<2, false>(pass, src, n_bytes, chunks, d_x2k, d_bits, d_bytes, d_crc, d_off, (uint8_t *)out, st);
         r = hipGetLastError();
@@ -233,9 +202,10 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
         }
     }
     long long h_total = 0;
-    std::vector<uint32_t> h_crc((size_t)chunks);
+    std::vector<uint32_t> h_crc((size_t)chunks), h_hdr(dyn ? (size_t)chunks : 0);
     if (r == hipSuccess) r = hipMemcpyAsync(&h_total, d_off + chunks, 8, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipMemcpyAsync(h_crc.data(), d_crc, (size_t)chunks * 4, hipMemcpyDeviceToHost, st);
+    if (r == hipSuccess && dyn) r = hipMemcpyAsync(h_hdr.data(), d_hdr, (size_t)chunks * 4, hipMemcpyDeviceToHost, st);
     if (r == hipSuccess) r = hipStreamSynchronize(st);
     if (r != hipSuccess) return fnn_fail(FNN_E_HIP, hipGetErrorString(r));
     uint32_t crc = 0;
@@ -245,5 +215,17 @@ extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_e
     *out_bytes = h_total;
     *file_elem_bytes = elem;
     *crc32 = crc;
+    if (dynamic_chunks)
+        for (uint32_t h : h_hdr) *dynamic_chunks += h != 0;
     return FNN_OK;
+}
+
+extern "C" int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out,
+                                  int64_t out_cap, int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, void *stream) {
+    return deflate_labels(false, in, in_elem_bytes, n_elems, narrow_if_fits, out, out_cap, out_bytes, file_elem_bytes, crc32, nullptr, stream);
+}
+
+extern "C" int fnn_deflate_labels_dyn(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
+                                      int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, int64_t *dynamic_chunks, void *stream) {
+    return deflate_labels(true, in, in_elem_bytes, n_elems, narrow_if_fits, out, out_cap, out_bytes, file_elem_bytes, crc32, dynamic_chunks, stream);
 }

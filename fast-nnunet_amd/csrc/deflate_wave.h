@@ -1,5 +1,6 @@
 // deflate_wave.h - what one wave of DF_LANES lanes does with its lanes' segments (deflate_core.h), device only: the steps
-// the count and emit kernels of csrc/deflate.hip and csrc/deflate_masks.hip are made of.  `lane`: the lane's index in its wave.
+// the count and emit kernels of csrc/deflate.hip, csrc/deflate_dyn.hip and csrc/deflate_masks.hip are made of.  `lane`: the
+// lane's index in its wave.
 #pragma once
 #include "deflate_core.h"
 #include <hip/hip_runtime.h>
@@ -17,6 +18,47 @@ template <int THREADS> static __device__ __forceinline__ void df_crc_table(uint3
         for (int i = 0; i < 8; ++i) t = (t >> 1) ^ ((t & 1) ? DF_POLY : 0u);
         s_tab[tid * (256 / THREADS) + k] = t;
     }
+}
+
+// ---- a chunk of a label map -> LDS (csrc/deflate.hip, csrc/deflate_dyn.hip) -------------------------------------------
+// the file bytes [16 v, 16 v + 16) of chunk `c`, bytes past `len` (the chunk's length) as 0
+template <bool NARROW>
+static __device__ __forceinline__ u32x4 load_vec(const uint8_t *in, long long c, int v, int len) {
+    const int b0 = v * 16;
+    u32x4 d = {0u, 0u, 0u, 0u};
+    if (!NARROW) {
+        const uint8_t *p = in + c * DF_CHUNK + b0;
+        if (b0 + 16 <= len) return *(const u32x4 *)p;
+        for (int j = 0; b0 + j < len; ++j) d[j >> 2] |= (unsigned)p[j] << ((j & 3) * 8);
+    } else {
+        const uint16_t *p = (const uint16_t *)in + c * DF_CHUNK + b0;
+        if (b0 + 16 <= len) {
+            const u32x4 lo = ((const u32x4 *)p)[0], hi = ((const u32x4 *)p)[1];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                d[k] = (lo[2 * k] & 255u) | ((lo[2 * k] >> 8) & 0xFF00u) | ((lo[2 * k + 1] & 255u) << 16) | ((lo[2 * k + 1] & 0xFF0000u) << 8);
+                d[2 + k] = (hi[2 * k] & 255u) | ((hi[2 * k] >> 8) & 0xFF00u) | ((hi[2 * k + 1] & 255u) << 16) | ((hi[2 * k + 1] & 0xFF0000u) << 8);
+            }
+            return d;
+        }
+        for (int j = 0; b0 + j < len; ++j) d[j >> 2] |= ((unsigned)p[j] & 255u) << ((j & 3) * 8);
+    }
+    return d;
+}
+
+// chunk `c` of the file bytes -> s_in, segment s at dword s * DF_PITCH; -> the chunk's length in bytes
+template <bool NARROW>
+static __device__ __forceinline__ int load_chunk(const uint8_t *in, long long n_bytes, long long c, unsigned *s_in) {
+    const long long left = n_bytes - c * DF_CHUNK;
+    const int len = left < DF_CHUNK ? (int)left : DF_CHUNK;
+    const int vecs = (len + 15) / 16;
+    for (int v = threadIdx.x; v < vecs; v += DF_LANES) {
+        const u32x4 d = load_vec<NARROW>(in, c, v, len);
+        unsigned *q = s_in + (v >> 4) * DF_PITCH + (v & 15) * 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = d[k];
+    }
+    return len;
 }
 
 // the bytes of the lane's segment in a chunk of `chunk_len`
@@ -45,16 +87,21 @@ static __device__ __forceinline__ uint32_t df_wave_crc(uint32_t crc, int mylen, 
     return crc;
 }
 
-// the lanes' bit counts -> the lane's first bit in the chunk (lane 0 begins with the 3 bits of the block header) and, where
-// asked for, the bits of all lanes
-static __device__ __forceinline__ unsigned df_lane_first_bit(unsigned bits, int lane, unsigned *all_bits = nullptr) {
+// the lanes' bit counts -> the bits of the lanes before this one and, where asked for, the bits of all lanes
+static __device__ __forceinline__ unsigned df_lane_bits_before(unsigned bits, int lane, unsigned *all_bits = nullptr) {
     unsigned incl = bits;
     for (int s = 1; s < DF_LANES; s <<= 1) {
         const unsigned up = (unsigned)__shfl_up((int)incl, s);
         if (lane >= s) incl += up;
     }
     if (all_bits) *all_bits = (unsigned)__shfl((int)incl, DF_LANES - 1);
-    return lane == 0 ? 0u : 3u + incl - bits;
+    return incl - bits;
+}
+
+// ... -> the lane's first bit in a fixed-code chunk: lane 0 begins with the 3 bits of the block header
+static __device__ __forceinline__ unsigned df_lane_first_bit(unsigned bits, int lane, unsigned *all_bits = nullptr) {
+    const unsigned before = df_lane_bits_before(bits, lane, all_bits);
+    return lane == 0 ? 0u : 3u + before;
 }
 
 // The wave's bit buffer `out` is laid out so that its 16-byte vectors are the aligned 16-byte vectors of the chunk's place

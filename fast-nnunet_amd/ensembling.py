@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import capi
-from .case_pipeline import as_plain_labels, export_case_files, labels_for_writer, run_pipeline
+from .case_pipeline import as_plain_labels, compress_mode, export_case_files, labels_for_writer, run_pipeline
 from .plans import label_rule
 from .predictor import nnUNetPredictor
 
@@ -111,14 +111,15 @@ class nnUNetEnsemblePredictor(object):
                   order-1 default plans, torch-resampling plans, equal grids); False, or a member that resamples at another
                   order: every member's logits are resampled to the cropped grid first and ``fnn_ensemble_export`` reads
                   those - the same bytes.  ``export_stats`` counts the cases by the route they took.
-    compress_on_device  as ``nnUNetPredictor``'s: the ensemble's label file is compressed on the GPU.
+    compress_on_device  as ``nnUNetPredictor``'s (False, True or ``'dynamic'``): the ensemble's label file is compressed on
+                  the GPU.
 
     Memory: the fused step keeps only the members' network-grid logits resident (N x heads x network-grid voxels x 2 B; a
     ``3d_lowres`` member at twice the spacing is an eighth of the cropped grid).  The two-step route keeps the members'
     resampled fp16 logits resident at the same time - N x heads x cropped voxels x 2 B (two members of a 61-class 512^3
     case: 32.7 GB) - on top of one member's network-grid logits while it runs."""
 
-    def __init__(self, predictors: Sequence[nnUNetPredictor], fused_export: bool = True, compress_on_device: bool = False):
+    def __init__(self, predictors: Sequence[nnUNetPredictor], fused_export: bool = True, compress_on_device=False):
         predictors = list(predictors)
         if not 1 <= len(predictors) <= MAX_MEMBERS:
             raise ValueError(f'an ensemble has 1..{MAX_MEMBERS} members, got {len(predictors)}')
@@ -140,7 +141,7 @@ class nnUNetEnsemblePredictor(object):
         self.dataset_json = first.dataset_json
         self.verbose = first.verbose
         self.fused_export = bool(fused_export)
-        self.compress_on_device = bool(compress_on_device)
+        self.compress_on_device = compress_mode(compress_on_device)
         self.export_stats = {'fused': 0, 'two-step': 0}
         self._postprocessing = None
         self._rw = None

@@ -638,12 +638,19 @@ class NiftiIO:
             seg = seg.contiguous()
             return (seg.clone() if seg.data_ptr() % 16 else seg), affine
 
-    def compress_labels(self, seg, properties: dict) -> 'DeviceCompressedLabels':
+    def compress_labels(self, seg, properties: dict, tables: str = 'fixed') -> 'DeviceCompressedLabels':
         """A device label map (z, y, x; uint8, or the two-byte int16 / uint16) -> the deflate fragment of its voxels as the
         ``.nii.gz`` file holds them, made by ``fnn_deflate_labels`` on the current stream: what comes back from the device
         is the fragment, not the map.  The file type is ``_label_voxels``' (uint16 from a maximum of 255 on).  ``write_seg``
-        takes the result.  Synchronises."""
+        takes the result.  Synchronises.
+        ``tables='dynamic'``: ``fnn_deflate_labels_dyn`` - every chunk carries its own Huffman tables where they make it
+        smaller.  Such a file is laid out in chunks as before (``chunked_layout`` recognises it), but the device inflate
+        refuses dynamic blocks (``FNN_INFLATE_DYNAMIC``): a reader with ``inflate_on_device=True`` reads it with zlib,
+        counted under ``inflate_stats['fallback']``.  Any other value of ``tables`` is a ValueError."""
         import torch
+        if tables not in ('fixed', 'dynamic'):
+            raise ValueError(f"tables must be 'fixed' or 'dynamic', got {tables!r}")
+        deflate = capi.deflate_labels if tables == 'fixed' else capi.deflate_labels_dyn
         seg, affine = self._compressible(seg, properties, 'compress_labels', 'arrays on the host')
         with torch.cuda.device(seg.device):
             if seg.element_size() == 1 and seg.numel() > 0 and int(seg.max()) >= 255:
@@ -651,8 +658,8 @@ class NiftiIO:
             n, size = seg.numel(), seg.element_size()
             cap = capi.deflate_bound(n * size)
             out = torch.empty(max(cap, 16), dtype=torch.uint8, device=seg.device)
-            n_out, file_size, crc = capi.deflate_labels(seg.data_ptr(), size, n, True, out.data_ptr(), cap,
-                                                        torch.cuda.current_stream(seg.device).cuda_stream)
+            n_out, file_size, crc = deflate(seg.data_ptr(), size, n, True, out.data_ptr(), cap,
+                                            torch.cuda.current_stream(seg.device).cuda_stream)[:3]
             fragment = out[:n_out].cpu().numpy().tobytes()
         return DeviceCompressedLabels(fragment, crc, n * file_size, tuple(seg.shape), file_size == 2, affine)
 

@@ -12,7 +12,8 @@ once, and only then split into masks.
   uint8), ...)`` - byte for byte the file the reference's call makes through this package's writer.
 * ``compress_on_device=True`` and a ``.nii.gz`` ending: ``NiftiIO.compress_label_masks`` encodes all masks on the GPU in one
   pass (csrc/deflate_masks.hip) on the calling thread and the writer thread only assembles and writes the files - the same
-  headers and voxels behind another deflate stream.
+  headers and voxels behind another deflate stream.  ``compress_on_device='dynamic'`` is refused when the predictor is made:
+  the mask encoder writes the fixed Huffman code only.
 
 A region-based dataset is refused when the predictor is initialised: the reference's function keys a dict by the label
 value, which is a list there, and cannot serve those datasets either.
@@ -38,6 +39,12 @@ def mask_file_names(label_manager, dataset_json: dict, output_file_truncated: st
 
 
 class JHUPredictor(nnUNetPredictor):
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.compress_on_device == 'dynamic':                # (before any case runs)
+            raise NotImplementedError("JHUPredictor(compress_on_device='dynamic'): compress_label_masks, the per-label mask encoder "
+                                      "(csrc/deflate_masks.hip), writes the fixed Huffman code only; use compress_on_device=True")
+
     def _build_engine(self):
         if self.label_manager.has_regions:                      # (before any GPU work)
             raise NotImplementedError('JHUPredictor writes one mask file per label of a dataset with plain labels; '

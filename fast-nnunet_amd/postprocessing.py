@@ -21,6 +21,7 @@ thread; ``determine_postprocessing_on_folder`` is the reference's search on fold
 """
 from __future__ import annotations
 
+import functools
 import io
 import os
 import pickle
@@ -30,7 +31,7 @@ import numpy as np
 import torch
 
 from . import capi
-from .case_pipeline import as_plain_labels, labels_for_writer
+from .case_pipeline import as_plain_labels, compress_mode, labels_for_writer
 
 REFERENCE_NAME = ('nnunetv2.postprocessing.remove_connected_components',
                   'remove_all_but_largest_component_from_segmentation')
@@ -224,33 +225,43 @@ def determine_postprocessing(predictions, references, dataset_json_or_label_mana
 
 
 # ---- label files ---------------------------------------------------------------------------------------------------------
-def _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress_on_device: bool):
+def _compressor(rw, compress_on_device):
+    """``compress_on_device`` (False, True or ``'dynamic'``; anything else a ValueError) -> ``labels_for_writer``'s ``compress``."""
+    mode = compress_mode(compress_on_device)
+    if mode == 'dynamic':
+        return functools.partial(rw.compress_labels, tables='dynamic')
+    return rw.compress_labels if mode else None
+
+
+def _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress):
     """The GPU part of one file: decoded labels -> what ``rw.write_seg`` takes on a thread that makes no GPU call."""
     seg = apply_postprocessing(as_plain_labels(labels), pp_fns, pp_fn_kwargs)
-    return labels_for_writer(rw, seg, props, compress=rw.compress_labels if compress_on_device else None)
+    return labels_for_writer(rw, seg, props, compress=compress)
 
 
 def load_postprocess_save(segmentation_file: str, output_fname: str, image_reader_writer, pp_fns: Sequence[Callable],
-                          pp_fn_kwargs: Sequence[dict], compress_on_device: bool = False):
+                          pp_fn_kwargs: Sequence[dict], compress_on_device=False):
     """``load_postprocess_save`` (remove_connected_components.py:42-50): the file is read as labels on the device,
-    post-processed there and written with its own properties."""
+    post-processed there and written with its own properties.  ``compress_on_device``: False, True or ``'dynamic'``."""
+    compress = _compressor(image_reader_writer, compress_on_device)
     labels, props = image_reader_writer.read_label_map(segmentation_file)
-    out = _postprocessed_for_writer(image_reader_writer, labels, props, pp_fns, pp_fn_kwargs, compress_on_device)
+    out = _postprocessed_for_writer(image_reader_writer, labels, props, pp_fns, pp_fn_kwargs, compress)
     image_reader_writer.write_seg(out, output_fname, props)
 
 
 def apply_postprocessing_to_files(input_files: Sequence[str], output_files: Sequence[str], image_reader_writer,
-                                  pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict], compress_on_device: bool = False):
+                                  pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict], compress_on_device=False):
     """``load_postprocess_save`` for every pair of names, pipelined: a reader thread inflates the next file and a writer
     thread compresses and writes the previous one while the calling thread - the only one that touches the GPU - decodes
     and post-processes this one.  A file appears under its name only when it is complete."""
     from .label_folders import run_label_cases
     rw = image_reader_writer
     input_files, output_files = list(input_files), list(output_files)
+    compress = _compressor(rw, compress_on_device)
 
     def run(i, maps):
         labels, props = maps[0]
-        out = _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress_on_device)
+        out = _postprocessed_for_writer(rw, labels, props, pp_fns, pp_fn_kwargs, compress)
         return None, (lambda: rw.write_seg(out, output_files[i], props))
 
     run_label_cases(rw, [[f] for f in input_files], run, write_thread=True)
@@ -258,12 +269,14 @@ def apply_postprocessing_to_files(input_files: Sequence[str], output_files: Sequ
 
 def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict],
                                    plans_file_or_dict=None, dataset_json_file_or_dict=None, num_processes=8,
-                                   compress_on_device: bool = False, inflate_on_device: bool = False) -> None:
+                                   compress_on_device=False, inflate_on_device: bool = False) -> None:
     """``apply_postprocessing_to_folder`` (remove_connected_components.py:247-294).  If plans_file_or_dict or
     dataset_json_file_or_dict are None, they are looked for in input_folder.  ``num_processes`` is accepted and ignored;
-    ``compress_on_device`` writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded);
+    ``compress_on_device`` (True, or ``'dynamic'`` for per-chunk Huffman tables; anything but those and False is a
+    ValueError before any file is read) writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded);
     ``inflate_on_device`` reads input files that were written that way through ``fnn_inflate_segments`` (no zlib on the host)."""
     from .label_folders import folder_plans_and_dataset, subfiles
+    compress_mode(compress_on_device)
     _, dataset_json, rw = folder_plans_and_dataset(
         input_folder, plans_file_or_dict, dataset_json_file_or_dict,
         'Expected plans file missing: {}. The plans file should have been created while running nnUNetv2_predict. Sadge. '

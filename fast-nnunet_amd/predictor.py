@@ -26,7 +26,7 @@ import torch
 
 from . import capi
 from .arch import ArchSpec, check_against_plans, ops_from_plans, spec_from_state_dict, weight_blob
-from .case_pipeline import as_plain_labels, device_compressor, export_case_files, labels_for_writer, run_pipeline
+from .case_pipeline import as_plain_labels, compress_mode, device_compressor, export_case_files, labels_for_writer, run_pipeline
 from .label_folders import load_json
 from .plans import ConfigurationManager, PlansManager, determine_num_input_channels, label_rule
 from .sliding_window import compute_gaussian, compute_steps_for_sliding_window
@@ -46,7 +46,7 @@ class nnUNetPredictor(object):
                  patches_per_forward: int = 4,
                  compute_dtype: str = 'f16',
                  fused_label_export: bool = True,
-                 compress_on_device: bool = False):
+                 compress_on_device: Union[bool, str] = False):
         """Same knobs as the reference (:40-65) plus the engine's choices:
 
         accumulate_in  'fp16' reproduces the reference's half accumulators and their rounding per patch visit as the
@@ -64,7 +64,10 @@ class nnUNetPredictor(object):
         compress_on_device  labels bound for a ``.nii.gz`` file are compressed by ``fnn_deflate_labels`` on the GPU and
                        only the compressed bytes are downloaded; the file holds the same header and voxels behind another
                        (larger, valid) deflate stream.  False (default): the host's gzip, byte for byte as before.
-                       Returned arrays, ``.npz`` and ``.pkl`` are the same either way.
+                       Returned arrays, ``.npz`` and ``.pkl`` are the same either way.  ``'dynamic'``: the same route
+                       with per-chunk dynamic Huffman tables (``fnn_deflate_labels_dyn``) - smaller files, which
+                       ``NiftiIO(inflate_on_device=True)`` reads through its zlib fallback.  Anything but False, True
+                       and ``'dynamic'`` is a ValueError.
         """
         self.verbose = verbose
         self.verbose_preprocessing = verbose_preprocessing
@@ -88,7 +91,7 @@ class nnUNetPredictor(object):
             raise ValueError("compute_dtype must be 'f16' or 'f8'")
         self.compute_dtype = compute_dtype
         self.fused_label_export = bool(fused_label_export)
-        self.compress_on_device = bool(compress_on_device)
+        self.compress_on_device = compress_mode(compress_on_device)
         self._engine: Optional[capi.Engine] = None
         self._spec: Optional[ArchSpec] = None
         self._active_fold = 0

@@ -647,6 +647,28 @@ int64_t fnn_deflate_bound(int64_t n_bytes);
 int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
                        int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, void *stream);
 
+/* fnn_deflate_labels with per-chunk dynamic Huffman tables (additive in ABI 4): the same arguments, contract, refusals and
+ * bound, and the same chain of independent byte-aligned chunks of 16 KiB of file bytes that each end behind 00 00 FF FF.
+ * The stream rule: tokens are fnn_deflate_labels' (matches at the distance of one element inside 256-byte segments).  A
+ * chunk's block is BTYPE 10 with the chunk's own tables where that takes fewer bits than the fixed code, else (a tie
+ * included) fnn_deflate_labels' BTYPE 01 block; so no chunk is longer than fnn_deflate_labels'.  Own tables: literal /
+ * length frequencies from the chunk's tokens and one for 256.  Code lengths (limit 15): a Huffman tree from two queues - the
+ * used symbols ascending by (frequency, index), and the merged nodes in the order they are made; the smaller head is taken,
+ * the merged node on a tie.  Leaf depths above the limit count as the limit; while the Kraft sum exceeds 1, the deepest leaf
+ * above the last level moves one level down and a leaf of the last level becomes its brother (2^-limit off the sum).  The
+ * lengths are handed out longest first to the symbols in ascending (frequency, index) order; one used symbol gets length
+ * 1.  The result is complete but not claimed to be the optimal length-limited code.  Canonical codes (RFC 1951 3.2.2); a
+ * constant distance code of two 1-bit symbols (HDIST = 2, complete); HLIT from the last used symbol, at least 257; the
+ * HLIT + 2 lengths as one sequence (a run may cross into the distance lengths), coded greedily from the left - at a run of
+ * r equal values v: v = 0 and r >= 11 -> 18 with min(r, 138), v = 0 and r >= 3 -> 17 with r, v > 0 behind a v and r >= 3
+ * -> 16 with min(r, 6), else v itself - under a code-length code made by the same construction with limit 7; HCLEN
+ * trimmed along the permuted order, at least 4.
+ * csrc/deflate_dyn_core.h states the rule in full.  *dynamic_chunks (may be NULL): the chunks that took their own tables.
+ * fnn_inflate_segments refuses such a fragment with FNN_INFLATE_DYNAMIC; zlib reads it.  The bytes depend on the input
+ * alone.  Synchronises the stream.  Scratch, allocated inside the call: fnn_deflate_labels' and 420 B per chunk. */
+int fnn_deflate_labels_dyn(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
+                           int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, int64_t *dynamic_chunks, void *stream);
+
 /* One label map on the device -> one deflate fragment per requested label, of the uint8 mask m[i] = (in[i] == label): the
  * voxel bytes of the per-label mask files of JHU_inference.py's export (<case>/predictions/<label_name>.nii.gz), in one
  * pass over the map per phase (additive in ABI 4).  Stateless, in two phases, because no useful capacity is known before

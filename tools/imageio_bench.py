@@ -6,7 +6,9 @@ against predict_from_files_sequential on four cases; and (``--section reorient``
 n^3 case - float32 forward and uint8 backward, one orientation per kernel path - next to a device-to-device copy of the
 same bytes and to numpy's flip / transpose on the host; and (``--section deflate``, these rows alone) fnn_deflate_labels on
 a synthetic 61-label map of n^3 voxels as uint8 and uint16 and on the golden mask tiled to a similar size, next to a device
-copy of the same bytes, to zlib level 1 on this machine's CPU, and the download of the fragment next to that of the map; and
+copy of the same bytes, to zlib level 1 on this machine's CPU, and the download of the fragment next to that of the map, and
+fnn_deflate_labels_dyn (per-chunk dynamic Huffman tables) next to the fixed call in alternating windows, its fragment's size
+next to zlib levels 1 and 6 and its download (profiles/r31_deflate_dynamic.txt); and
 (``--section masks``, these rows alone) the per-label mask files of JHUPredictor: fnn_deflate_masks_count + fnn_deflate_masks_emit
 on synthetic maps of 61 and 118 labels and on the golden mask tiled, next to one fnn_deflate_labels call per mask materialised on
 the device, to zlib level 1 of a mask on the CPU times the number of labels, and the sizes that are downloaded and written; and
@@ -85,6 +87,24 @@ def events_batched(fn, calls, windows, dev):
     return float(np.median(ts)), min(ts), max(ts)
 
 
+def events_batched_pair(fa, fb, calls, windows, dev):
+    """``events_batched`` for two calls that are compared: their windows alternate, so that both see the same machine ->
+    the two (median, min, max)."""
+    ts = ([], [])
+    for r in range(windows + 1):                  # the first pair of windows is the warm-up
+        for k, fn in enumerate((fa, fb)):
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                fn()
+            e1.record()
+            e1.synchronize()
+            if r:
+                ts[k].append(e0.elapsed_time(e1) / calls)
+    return tuple((float(np.median(t)), min(t), max(t)) for t in ts)
+
+
 def synthetic_ct(shape, seed):
     rng = np.random.default_rng(seed)
     z, y, x = np.meshgrid(*[np.linspace(-1, 1, s, dtype=np.float32) for s in shape], indexing='ij', sparse=True)
@@ -133,7 +153,8 @@ def label_map(n, dev, seed=18, k=60):
 
 
 def bench_deflate(n, reps, dev, say, row):
-    """fnn_deflate_labels (csrc/deflate.hip) against zlib level 1 on this machine's CPU and a device copy of the same bytes."""
+    """fnn_deflate_labels (csrc/deflate.hip) against zlib level 1 on this machine's CPU and a device copy of the same bytes,
+    and fnn_deflate_labels_dyn (csrc/deflate_dyn.hip) against both."""
     import zlib
     from fast_nnunet_amd import capi
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -174,7 +195,29 @@ def bench_deflate(n, reps, dev, say, row):
             f'  {n_bytes / tz[0] / 1e6:.2f} GB/s; {len(tz[3]) / 2 ** 20:.2f} MiB: the fragment is {n_out / len(tz[3]):.2f}x that; '
             f'{tz[0] / t[0]:.0f}x the kernel\'s time')
         say(f'  the fragment inflates to the labels and the CRC is zlib\'s: {same}')
-        del out, raw, frag, labels
+        # per-chunk dynamic Huffman tables (csrc/deflate_dyn.hip) next to the fixed call, the yardstick, in alternating windows
+        out_d = torch.empty(cap, dtype=torch.uint8, device=dev)
+        res_d = []
+        tfix, tdyn = events_batched_pair(
+            lambda: capi.deflate_labels(labels.data_ptr(), labels.element_size(), labels.numel(), True, out.data_ptr(), cap, stream),
+            lambda: res_d.append(capi.deflate_labels_dyn(labels.data_ptr(), labels.element_size(), labels.numel(), True, out_d.data_ptr(), cap, stream)),
+            10, 5, dev)
+        n_dyn, _, crc_d, dynamic_chunks = res_d[-1]
+        row('  fnn_deflate_labels, 10 calls per window, 5 windows', tfix, f'  fragment {n_out / 2 ** 20:.2f} MiB')
+        row('  fnn_deflate_labels_dyn, the same windows in turn', tdyn,
+            f'  {tdyn[0] / tfix[0]:.2f}x the fixed call; fragment {n_dyn / 2 ** 20:.2f} MiB = {n_dyn / n_out:.2f}x the fixed one; '
+            f'{dynamic_chunks} of {-(-labels.numel() * file_size // 16384)} chunks took their own tables')
+        tfd = wall(lambda: out_d[:n_dyn].cpu(), reps)
+        row(f'  download of the dynamic fragment ({n_dyn / 2 ** 20:.2f} MiB, pageable)', tfd[:3], f'  the fixed one: {tf[0]:.2f} ms')
+        frag_d = tfd[3].numpy().tobytes()
+        d = zlib.decompressobj(-15)
+        same = d.decompress(frag_d + b'\x03\x00') == raw and crc_d == crc
+        tz6 = wall(lambda: zlib.compress(raw, 6), 1)
+        say(f'  sizes: dynamic {n_dyn} B, fixed {n_out} B, zlib level 1 {len(tz[3])} B ({n_dyn / len(tz[3]):.2f}x), zlib level 6 '
+            f'{len(tz6[3])} B ({n_dyn / len(tz6[3]):.2f}x; {tz6[0]:.0f} ms on the host)')
+        say(f'  zlib level 1 on the host takes {tz[0] / tdyn[0]:.0f}x the dynamic call\'s time; the dynamic fragment inflates to the '
+            f'labels and the CRC is zlib\'s: {same}')
+        del out, out_d, raw, frag, frag_d, labels
     del inputs, synth
 
 
