@@ -78,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -167,6 +167,7 @@ def load_library() -> C.CDLL:
     lib.fnn_deflate_masks_count.argtypes = [vp, i32, i64, C.POINTER(C.c_int32), i32, vp, i64, C.POINTER(i64), C.POINTER(C.c_uint32), vp]
     lib.fnn_deflate_masks_emit.argtypes = [vp, i32, i64, C.POINTER(C.c_int32), i32, vp, vp, i64, vp]
     lib.fnn_inflate_segments.argtypes = [vp, i64, C.POINTER(i64), i64, vp, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
+    lib.fnn_inflate_segments_dyn.argtypes = lib.fnn_inflate_segments.argtypes
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -462,6 +463,8 @@ FNN_INFLATE_SEGMENT_MAX = 16384
 INFLATE_REASONS = ('OK', 'DYNAMIC', 'BTYPE3', 'FINAL', 'SYMBOL', 'NLEN', 'DISTANCE', 'OUTPUT', 'INPUT', 'END', 'CHAIN', 'SIZE')   # FNN_INFLATE_*
 (FNN_INFLATE_OK, FNN_INFLATE_DYNAMIC, FNN_INFLATE_BTYPE3, FNN_INFLATE_FINAL, FNN_INFLATE_SYMBOL, FNN_INFLATE_NLEN,
  FNN_INFLATE_DISTANCE, FNN_INFLATE_OUTPUT, FNN_INFLATE_INPUT, FNN_INFLATE_END, FNN_INFLATE_CHAIN, FNN_INFLATE_SIZE) = range(12)
+FNN_INFLATE_TABLES = 12                                           # fnn_inflate_segments_dyn alone
+INFLATE_DYN_REASONS = INFLATE_REASONS + ('TABLES',)
 
 
 def inflate_segments(in_ptr: int, in_bytes: int, starts, out_ptr: int, out_bytes: int, stream: int = 0):
@@ -475,6 +478,18 @@ def inflate_segments(in_ptr: int, in_bytes: int, starts, out_ptr: int, out_bytes
     crc, status = C.c_uint32(0), C.c_int32(0)
     check(lib.fnn_inflate_segments(in_ptr, int(in_bytes), arr.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size), out_ptr,
                                    int(out_bytes), C.byref(crc), C.byref(status), stream), lib)
+    return int(status.value), int(crc.value)
+
+
+def inflate_segments_dyn(in_ptr: int, in_bytes: int, starts, out_ptr: int, out_bytes: int, stream: int = 0):
+    """fnn_inflate_segments_dyn: ``inflate_segments`` for chains whose segments may hold dynamic-Huffman blocks too (the
+    fragments of ``deflate_labels_dyn``, zlib's full-flush streams of any strategy).  The same arguments and result; the
+    status is one of ``INFLATE_DYN_REASONS``: never DYNAMIC, TABLES for a table header zlib's inflate would refuse."""
+    lib = load_library()
+    arr = np.ascontiguousarray(starts, dtype=np.int64)
+    crc, status = C.c_uint32(0), C.c_int32(0)
+    check(lib.fnn_inflate_segments_dyn(in_ptr, int(in_bytes), arr.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size), out_ptr,
+                                       int(out_bytes), C.byref(crc), C.byref(status), stream), lib)
     return int(status.value), int(crc.value)
 
 

@@ -1,8 +1,11 @@
 // inflate.hip - a raw deflate stream on the device that is a chain of byte-aligned segments -> its bytes, gfx950.
 //
-//   fnn_inflate_segments   candidates for segment starts -> the chain that covers the stream, its bytes and their CRC-32
+//   fnn_inflate_segments       candidates for segment starts -> the chain that covers the stream, its bytes and their CRC-32
+//   fnn_inflate_segments_dyn   the same for segments that may hold dynamic-Huffman blocks: the same host code here, the
+//                              kernels of inflate_dyn.hip
 //
-// The segment rule, and the decode step all passes share, is inflate_core.h.  One wave decodes one segment; the token loop
+// The segment rule, and the decode step all passes share, is inflate_core.h; what the kernels of both files share - the
+// register window, the LDS image, the CRC and the store of a finished image - is inflate_wave.h.  One wave decodes one segment; the token loop
 // is serial and wave-uniform - its bit reader, positions and branches live in scalar registers - and the 64 lanes share
 // the bytes of a token.
 //
@@ -21,86 +24,13 @@
 // The chain is followed on the host between the two passes (as fnn_deflate_labels folds its CRCs there).  Nothing is read
 // outside in[0, in_bytes) or written outside out[0, out_bytes); no kernel keeps scratch.
 #include "host_call.h"
-#include "deflate_wave.h"
-#include "inflate_core.h"
+#include "inflate_wave.h"
 #include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <vector>
 
 namespace {
-
-constexpr int INF_PIECE = 260;                   // the bytes of the image one lane takes the CRC of: 65 dwords, an odd pitch
-static_assert(INF_PIECE % 4 == 0 && DF_LANES * INF_PIECE >= 15 + FNN_INFLATE_SEGMENT_MAX, "64 pieces cover the image");
-
-struct InfMember {                               // a member of the chain: where its segment starts, where its bytes go
-    long long start, off;
-};
-struct InfMade {                                 // what the emit pass says of a member
-    uint32_t crc;
-    int len;                                     // the bytes stored; -1: the second decode was refused (never, for the same input)
-};
-
-// the stream as a window of 64 dwords, one per lane; everything but `cur` and `nxt` is wave-uniform
-struct InfWindow {
-    const uint8_t *in;
-    long long in_bytes, next_dw;                 // the dword index of the window after `nxt`
-    unsigned cur, nxt;
-    int idx, lane;
-    // dword `dw` of the stream, bytes from in_bytes on as 0 (and not loaded)
-    __device__ __forceinline__ unsigned load(long long dw) const {
-        const long long at = dw * 4;
-        if (at + 4 <= in_bytes) return *(const unsigned *)(in + at);
-        unsigned w = 0;
-        for (int k = 0; k < 4; ++k)
-            if (at + k < in_bytes) w |= (unsigned)in[at + k] << (8 * k);
-        return w;
-    }
-    __device__ __forceinline__ InfWindow(const uint8_t *in_, long long in_bytes_, long long start, int lane_)
-        : in(in_), in_bytes(in_bytes_), idx(0), lane(lane_) {
-        const long long dw = start >> 2;
-        cur = load(dw + lane);
-        nxt = load(dw + DF_LANES + lane);
-        next_dw = dw + 2 * DF_LANES;
-    }
-    __device__ __forceinline__ unsigned next() {
-        if (idx == DF_LANES) {
-            cur = nxt;
-            nxt = load(next_dw + lane);
-            next_dw += DF_LANES;
-            idx = 0;
-        }
-        const unsigned w = (unsigned)__builtin_amdgcn_readlane((int)cur, __builtin_amdgcn_readfirstlane(idx));
-        ++idx;
-        return w;
-    }
-};
-
-// the wave's image of the segment in LDS: position p of the output at img[p]
-struct InfImage {
-    uint8_t *img;
-    int lane;
-    __device__ __forceinline__ void literal(int pos, unsigned v) {
-        if (lane == 0) img[pos] = (uint8_t)v;
-    }
-    __device__ __forceinline__ void raw(int pos, unsigned w, int k) {
-        if (lane < k) img[pos + lane] = (uint8_t)(w >> (8 * lane));
-    }
-    // The source bytes [pos - dist, pos) are complete before the match begins and none of them is written by it, so the
-    // lanes need no order among themselves; the wave's LDS accesses are served in program order, so the stores of the
-    // tokens before are seen.
-    __device__ __forceinline__ void match(int pos, int len, int dist) {
-        const uint8_t *src = img + pos - dist;
-        if (dist >= len) {
-            for (int i = lane; i < len; i += DF_LANES) img[pos + i] = src[i];
-        } else if (dist == 1) {
-            const uint8_t v = src[0];
-            for (int i = lane; i < len; i += DF_LANES) img[pos + i] = v;
-        } else {
-            for (int i = lane; i < len; i += DF_LANES) img[pos + i] = src[(unsigned)i % (unsigned)dist];
-        }
-    }
-};
 
 __global__ __launch_bounds__(DF_LANES) void inflate_count_kernel(const uint8_t *in, long long in_bytes, const long long *starts,
                                                                 InfRecord *rec) {
@@ -129,32 +59,15 @@ __global__ __launch_bounds__(DF_LANES) void inflate_emit_kernel(const uint8_t *i
         if (lane == 0) made[blockIdx.x] = InfMade{0u, -1};
         return;
     }
-    // the CRC of image bytes [mis, mis + len): lane l takes those of [260 l, 260 l + 260), dword by dword
-    const int lo = max(mis, lane * INF_PIECE), hi = min(mis + r.len, (lane + 1) * INF_PIECE);
-    uint32_t crc = 0xFFFFFFFFu;
-    const unsigned *words = (const unsigned *)s_img;
-    for (int w = lo >> 2; w * 4 < hi; ++w) {
-        unsigned v = words[w];
-#pragma unroll
-        for (int k = 0; k < 4; ++k, v >>= 8) {
-            const int p = w * 4 + k;
-            if (p >= lo && p < hi) crc = s_tab[(crc ^ v) & 255u] ^ (crc >> 8);
-        }
-    }
-    const int mylen = hi > lo ? hi - lo : 0;
-    crc = df_wave_crc(mylen ? ~crc : 0u, mylen, s_x2k, lane);
-    if (lane == 0) made[blockIdx.x] = InfMade{crc, r.len};
-    df_wave_store(dst, mis, r.len, (mis + r.len + 15) / 16, s_img, lane);
+    inf_wave_finish(dst, mis, r.len, s_img, s_tab, s_x2k, made, lane);
 }
 
 static const DfTables g_tables;
 
-}  // namespace
-
-extern "C" int fnn_inflate_segments(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
-                                    int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream) {
+// the host side of both entries; `dyn`: the kernels of csrc/inflate_dyn.hip, which decode dynamic-Huffman blocks too
+int inflate_run(const char *who, bool dyn, const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
+                int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream) {
     FnnOpKlog klog;
-    const char *who = "fnn_inflate_segments";
     if (!in || !starts || !out || !crc32 || !status) return fnn_failf(FNN_E_INVALID, "%s: NULL argument", who);
     if (in_bytes < 0 || n_starts < 0 || out_bytes < 0) return fnn_failf(FNN_E_INVALID, "%s: negative size", who);
     if ((uintptr_t)in % 16) return fnn_failf(FNN_E_INVALID, "%s: in must be aligned to 16 bytes", who);
@@ -180,10 +93,18 @@ extern "C" int fnn_inflate_segments(const void *in, int64_t in_bytes, const int6
     if (!scratch.alloc(total)) return fnn_fail(FNN_E_HIP, "hipMalloc failed (inflate scratch)");
     HipCall c(stream);
     std::vector<InfRecord> rec(n);
-    c.copy(scratch.as<char>(o_starts), starts, n * 8, hipMemcpyHostToDevice)
-        .launch(inflate_count_kernel, dim3((unsigned)n), dim3(DF_LANES), 0, (const uint8_t *)in, (long long)in_bytes,
-                scratch.as<const long long>(o_starts), scratch.as<InfRecord>(o_rec));
-    fnn_note_kernel("inflate_count_kernel");
+    const InfDynArgs args{(const uint8_t *)in, (long long)in_bytes, scratch.as<const long long>(o_starts), scratch.as<InfRecord>(o_rec),
+                          scratch.as<const InfMember>(o_mem), scratch.as<const uint32_t>(o_x2k), (uint8_t *)out, scratch.as<InfMade>(o_made)};
+    c.copy(scratch.as<char>(o_starts), starts, n * 8, hipMemcpyHostToDevice);
+    if (dyn) {
+        if (c.ok()) {
+            inf_dyn_launch(0, (unsigned)n, args, c.st);
+            c.r = hipGetLastError();
+        }
+    } else {
+        c.launch(inflate_count_kernel, dim3((unsigned)n), dim3(DF_LANES), 0, args.in, args.in_bytes, args.starts, args.rec);
+        fnn_note_kernel("inflate_count_kernel");
+    }
     c.copy(rec.data(), scratch.as<char>(o_rec), n * sizeof(InfRecord), hipMemcpyDeviceToHost);
     if (!c.sync()) return c.fail();
 
@@ -207,10 +128,16 @@ extern "C" int fnn_inflate_segments(const void *in, int64_t in_bytes, const int6
     const size_t k = members.size();
     std::vector<InfMade> made(k);
     c.copy(scratch.as<char>(o_mem), members.data(), k * sizeof(InfMember), hipMemcpyHostToDevice)
-        .copy(scratch.as<char>(o_x2k), g_tables.x2k, sizeof(g_tables.x2k), hipMemcpyHostToDevice)
-        .launch(inflate_emit_kernel, dim3((unsigned)k), dim3(DF_LANES), 0, (const uint8_t *)in, (long long)in_bytes,
-                scratch.as<const InfMember>(o_mem), scratch.as<const uint32_t>(o_x2k), (uint8_t *)out, scratch.as<InfMade>(o_made));
-    fnn_note_kernel("inflate_emit_kernel");
+        .copy(scratch.as<char>(o_x2k), g_tables.x2k, sizeof(g_tables.x2k), hipMemcpyHostToDevice);
+    if (dyn) {
+        if (c.ok()) {
+            inf_dyn_launch(1, (unsigned)k, args, c.st);
+            c.r = hipGetLastError();
+        }
+    } else {
+        c.launch(inflate_emit_kernel, dim3((unsigned)k), dim3(DF_LANES), 0, args.in, args.in_bytes, args.members, args.x2k, args.out, args.made);
+        fnn_note_kernel("inflate_emit_kernel");
+    }
     c.copy(made.data(), scratch.as<char>(o_made), k * sizeof(InfMade), hipMemcpyDeviceToHost);
     if (!c.sync()) return c.fail();
     uint32_t crc = 0;
@@ -221,4 +148,16 @@ extern "C" int fnn_inflate_segments(const void *in, int64_t in_bytes, const int6
     }
     *crc32 = crc;
     return FNN_OK;
+}
+
+}  // namespace
+
+extern "C" int fnn_inflate_segments(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
+                                    int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream) {
+    return inflate_run("fnn_inflate_segments", false, in, in_bytes, starts, n_starts, out, out_bytes, crc32, status, stream);
+}
+
+extern "C" int fnn_inflate_segments_dyn(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
+                                        int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream) {
+    return inflate_run("fnn_inflate_segments_dyn", true, in, in_bytes, starts, n_starts, out, out_bytes, crc32, status, stream);
 }

@@ -98,6 +98,20 @@ DF_HD int inf_distance_base(int code, int &extra) {
     return 1 + ((2 + (code & 1)) << extra);
 }
 
+// ---- the two codes a block's tokens are read with -------------------------------------------------------------------------
+// What the segment rule asks of them.  `begin_fixed()`: a BTYPE 01 block begins.  `header(b, limit, end_bit)`: a BTYPE 10
+// block begins, its table header is next in `b` -> FNN_INFLATE_OK or why the segment stops there.  `lit(v, n)` / `dist(v, n)`:
+// the next literal / length or distance symbol from the 15 bits `v` (first bit lowest) and, in `n`, its bits; a negative
+// symbol for a bit pattern that belongs to none.  DYNAMIC: a token may take 48 bits, so the reader is filled once more
+// before the distance symbol.  These are the codes of this file's rule: BTYPE 10 is refused (inflate_dyn_core.h decodes it).
+struct InfFixedCodes {
+    static constexpr bool DYNAMIC = false;
+    DF_HD void begin_fixed() {}
+    template <class Bits> DF_HD int header(Bits &, long long, long long) { return FNN_INFLATE_DYNAMIC; }
+    DF_HD int lit(unsigned v, int &n) const { return inf_symbol(v, n); }
+    DF_HD int dist(unsigned v, int &n) const { n = 5; return (int)df_rev(v & 31u, 5); }
+};
+
 // ---- the segment rule ------------------------------------------------------------------------------------------------
 // Decodes the segment that starts at byte `start` of in[0, in_bytes) (`rd` begins at the dword start & ~3) and hands the
 // output to the sink, position by position from 0:
@@ -108,10 +122,11 @@ DF_HD int inf_distance_base(int code, int &extra) {
 //
 // Bound: the limit - the input's end or the budget, whichever comes first - is compared with used() behind everything an
 // iteration of the block loop or the token loop drops, and for a stored block before its first byte.  An iteration drops
-// at least 3 bits (a block header), 7 (a token) or 8 (a stored unit of up to 4 bytes), so at most 8 * INF_INPUT_MAX / 3 + 1
-// iterations run whatever the input holds, none of them past the limit by more than one token (48 bits): the reader is
-// asked for at most three dwords beyond it, which it answers with zeros.
-template <class Reader, class Sink> DF_HD InfRecord inf_segment(Reader rd, long long start, long long in_bytes, Sink &s) {
+// at least 3 bits (a block header), 1 (a token; 7 with the fixed code) or 8 (a stored unit of up to 4 bytes), so at most
+// 8 * INF_INPUT_MAX + 1 iterations run whatever the input holds, none of them past the limit by more than one token
+// (48 bits): the reader is asked for at most three dwords beyond it, which it answers with zeros.
+template <class Reader, class Sink, class Codes>
+DF_HD InfRecord inf_segment_with(Reader rd, long long start, long long in_bytes, Sink &s, Codes &codes) {
     InfBits<Reader> b(rd);
     const long long first = (start & 3) * 8;                                     // the segment's first bit
     const long long end_bit = (in_bytes - (start & ~3LL)) * 8, budget_bit = first + 8LL * INF_INPUT_MAX;
@@ -126,7 +141,6 @@ template <class Reader, class Sink> DF_HD InfRecord inf_segment(Reader rd, long 
         const unsigned hdr = b.take(3);
         if (b.used() > limit) return stop(over());
         if (hdr & 1u) return stop(FNN_INFLATE_FINAL);
-        if ((hdr >> 1) == 2u) return stop(FNN_INFLATE_DYNAMIC);
         if ((hdr >> 1) == 3u) return stop(FNN_INFLATE_BTYPE3);
         if ((hdr >> 1) == 0u) {
             b.drop((int)(-b.used() & 7));
@@ -146,24 +160,32 @@ template <class Reader, class Sink> DF_HD InfRecord inf_segment(Reader rd, long 
             }
             continue;
         }
+        if ((hdr >> 1) == 2u) {
+            const int why = codes.header(b, limit, end_bit);
+            if (why != FNN_INFLATE_OK) return stop(why);
+        } else {
+            codes.begin_fixed();
+        }
         for (;;) {
             b.fill();
             int n, extra;
-            const int sym = inf_symbol(b.peek(9), n);
+            const int sym = codes.lit(b.peek(15), n);
             b.drop(n);
             if (b.used() > limit) return stop(over());
-            if (sym < 256) {
+            if (sym >= 0 && sym < 256) {
                 if (pos >= FNN_INFLATE_SEGMENT_MAX) return stop(FNN_INFLATE_OUTPUT);
                 s.literal(pos, (unsigned)sym);
                 ++pos;
                 continue;
             }
             if (sym == 256) break;
-            if (sym > 285) return stop(FNN_INFLATE_SYMBOL);
+            if (sym < 0 || sym > 285) return stop(FNN_INFLATE_SYMBOL);
             int len = inf_length_base(sym - 257, extra);
             len += (int)b.take(extra);
-            const int code = (int)df_rev(b.take(5), 5);
-            if (code > 29) return stop(FNN_INFLATE_SYMBOL);
+            if (Codes::DYNAMIC) b.fill();
+            const int code = codes.dist(b.peek(15), n);
+            b.drop(n);
+            if (code < 0 || code > 29) return stop(FNN_INFLATE_SYMBOL);
             int dist = inf_distance_base(code, extra);
             dist += (int)b.take(extra);
             if (b.used() > limit) return stop(over());
@@ -173,6 +195,12 @@ template <class Reader, class Sink> DF_HD InfRecord inf_segment(Reader rd, long 
             pos += len;
         }
     }
+}
+
+// the rule of this file: stored and fixed blocks, FNN_INFLATE_DYNAMIC at the first BTYPE 10
+template <class Reader, class Sink> DF_HD InfRecord inf_segment(Reader rd, long long start, long long in_bytes, Sink &s) {
+    InfFixedCodes codes;
+    return inf_segment_with(rd, start, in_bytes, s, codes);
 }
 
 // the sink of a pass that only judges the segment

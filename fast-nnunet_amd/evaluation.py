@@ -696,11 +696,12 @@ def compute_metrics_on_folder(folder_ref: str, folder_pred: str, output_file: Op
 
 def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_file: str, plans_file: str,
                                output_file: Optional[str] = None, num_processes: int = DEFAULT_NUM_PROCESSES,
-                               chill: bool = False, inflate_on_device: bool = False, *, surface_metrics: bool = False,
+                               chill: bool = False, inflate_on_device=False, *, surface_metrics: bool = False,
                                spacing=None, nsd_tolerance=1.0, instance_metrics: bool = False):
     """compute_metrics_on_folder2 (:177-196): labels or regions, ignore label, file ending and the reader-writer from
     ``dataset.json`` and the plans; ``output_file`` defaults to ``<folder_pred>/summary.json``.  ``inflate_on_device``: label
-    files written with ``compress_on_device=True`` are inflated on the GPU (``NiftiIO(inflate_on_device=True)``).
+    files written with ``compress_on_device=True`` are inflated on the GPU (``NiftiIO(inflate_on_device=True)``);
+    ``inflate_on_device='dynamic'`` serves files written with ``compress_on_device='dynamic'`` too.
     ``surface_metrics`` / ``spacing`` / ``nsd_tolerance`` / ``instance_metrics``: as ``compute_metrics_on_files``."""
     from .imageio import determine_reader_writer_from_dataset_json
     from .label_folders import load_json
@@ -718,7 +719,7 @@ def compute_metrics_on_folder2(folder_ref: str, folder_pred: str, dataset_json_f
 
 def compute_metrics_on_folder_simple(folder_ref: str, folder_pred: str, labels: Sequence[int], output_file: Optional[str] = None,
                                      num_processes: int = DEFAULT_NUM_PROCESSES, ignore_label: Optional[int] = None,
-                                     chill: bool = False, inflate_on_device: bool = False, *, surface_metrics: bool = False,
+                                     chill: bool = False, inflate_on_device=False, *, surface_metrics: bool = False,
                                      spacing=None, nsd_tolerance=1.0, instance_metrics: bool = False):
     """compute_metrics_on_folder_simple (:199-212): the file ending is that of the first reference file (``.nii.gz``
     whole, where the reference's ``os.path.splitext`` would keep ``.gz`` and then match the same files).

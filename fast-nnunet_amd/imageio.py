@@ -33,6 +33,9 @@ front-ends (``evaluation.compute_metrics_on_folder``, ``postprocessing.apply_pos
 compressed file as it is when ``chunked_layout`` recognises it, and ``decode_label_maps`` lets ``fnn_inflate_segments``
 (csrc/inflate.hip) inflate it on the device, certified by the call's status and the gzip trailer's CRC-32.  Files written by
 zlib (references, scanner images), image files and everything the device refuses are inflated by zlib on the host, as ever.
+``fnn_inflate_segments`` refuses dynamic-Huffman blocks, so a file written with ``compress_on_device='dynamic'`` falls back;
+``NiftiIO(inflate_on_device='dynamic')`` takes ``fnn_inflate_segments_dyn`` (csrc/inflate_dyn.hip) instead, which decodes
+them and serves the files of both encoders.
 
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
@@ -402,6 +405,16 @@ def chunked_layout(file_bytes, hdr: NiftiHeader) -> Optional[ChunkedLayout]:
     return ChunkedLayout(m, end - m, starts, zlib.crc32(head), crc)
 
 
+def inflate_on_device_value(value):
+    """The ``inflate_on_device`` switch as the readers keep it: False, True or 'dynamic'.  Any other string is a ValueError;
+    what is no string counts by its truth, as before."""
+    if isinstance(value, str):
+        if value != 'dynamic':
+            raise ValueError(f"inflate_on_device must be False, True or 'dynamic', got {value!r}")
+        return value
+    return bool(value)
+
+
 class StagedCase:
     """The files of one case between the host and the device: headers (checked), and one pinned byte buffer per file that a
     host thread fills.  ``layouts[i]`` is None when buffer i holds the file's voxel bytes, and the ``ChunkedLayout`` when it
@@ -444,12 +457,13 @@ class NiftiIO:
     """``read_images`` / ``read_seg`` / ``write_seg`` of the reference's reader-writer classes for single-file NIfTI-1."""
     supported_file_endings = list(SUPPORTED_FILE_ENDINGS)
 
-    def __init__(self, device=None, inflate_on_device: bool = False):
+    def __init__(self, device=None, inflate_on_device=False):
         self._device = device
         self._pinned = {}                            # slot -> list of pinned uint8 tensors, grown on demand
         # opt-in: label files written with compress_on_device=True are inflated by fnn_inflate_segments (csrc/inflate.hip)
-        # instead of zlib; which route each label file took is counted here
-        self.inflate_on_device = bool(inflate_on_device)
+        # instead of zlib; 'dynamic': by fnn_inflate_segments_dyn (csrc/inflate_dyn.hip), which also serves the files of
+        # compress_on_device='dynamic'.  Which route each label file took is counted here
+        self.inflate_on_device = inflate_on_device_value(inflate_on_device)
         self.inflate_stats = {'device': 0, 'host': 0, 'fallback': 0}
 
     # ------------------------------------------------------------------ device side
@@ -524,9 +538,9 @@ class NiftiIO:
         the bits of uint16 (the engine's two-byte label type).  Every file's bytes are uploaded and decoded by
         ``fnn_decode_labels`` on the current stream - 1 byte wide for the 1-byte datatypes, else 2 bytes and narrowed to
         uint8 when the largest label is below 256.  RuntimeError naming the file when it holds what is no label.
-        A file staged compressed (``inflate_on_device``) is uploaded as it is and inflated by ``fnn_inflate_segments`` into
-        the same byte tensor; the result is taken only if the call certifies it (status 0) and its CRC-32, combined with the
-        header's, is the gzip trailer's - anything else re-reads the file with zlib on this thread, which is the route the
+        A file staged compressed (``inflate_on_device``) is uploaded as it is and inflated by ``fnn_inflate_segments``
+        (``inflate_on_device='dynamic'``: ``fnn_inflate_segments_dyn``) into the same byte tensor; the result is taken only
+        if the call certifies it (status 0) and its CRC-32, combined with the header's, is the gzip trailer's - anything else re-reads the file with zlib on this thread, which is the route the
         file takes without the flag and the one that says what is wrong with a corrupt file.
         Synchronises: the staging buffers are free again on return."""
         import torch
@@ -569,7 +583,8 @@ class NiftiIO:
         comp = torch.empty(max(16, lay.in_bytes), dtype=torch.uint8, device=raw.device)
         comp[:lay.in_bytes].copy_(b[lay.first:lay.first + lay.in_bytes], non_blocking=True)
         keep.append(comp)
-        status, crc = capi.inflate_segments(comp.data_ptr(), lay.in_bytes, lay.starts, raw.data_ptr(), h.n_bytes, stream.cuda_stream)
+        inflate = capi.inflate_segments_dyn if self.inflate_on_device == 'dynamic' else capi.inflate_segments
+        status, crc = inflate(comp.data_ptr(), lay.in_bytes, lay.starts, raw.data_ptr(), h.n_bytes, stream.cuda_stream)
         if status == capi.FNN_INFLATE_OK and crc32_combine(lay.header_crc, crc, h.n_bytes) == lay.crc32:
             self.inflate_stats['device'] += 1
             return True
@@ -644,9 +659,10 @@ class NiftiIO:
         is the fragment, not the map.  The file type is ``_label_voxels``' (uint16 from a maximum of 255 on).  ``write_seg``
         takes the result.  Synchronises.
         ``tables='dynamic'``: ``fnn_deflate_labels_dyn`` - every chunk carries its own Huffman tables where they make it
-        smaller.  Such a file is laid out in chunks as before (``chunked_layout`` recognises it), but the device inflate
-        refuses dynamic blocks (``FNN_INFLATE_DYNAMIC``): a reader with ``inflate_on_device=True`` reads it with zlib,
-        counted under ``inflate_stats['fallback']``.  Any other value of ``tables`` is a ValueError."""
+        smaller.  Such a file is laid out in chunks as before (``chunked_layout`` recognises it); a reader with
+        ``inflate_on_device='dynamic'`` inflates it on the device, while ``fnn_inflate_segments`` refuses dynamic blocks
+        (``FNN_INFLATE_DYNAMIC``): a reader with ``inflate_on_device=True`` reads it with zlib, counted under
+        ``inflate_stats['fallback']``.  Any other value of ``tables`` is a ValueError."""
         import torch
         if tables not in ('fixed', 'dynamic'):
             raise ValueError(f"tables must be 'fixed' or 'dynamic', got {tables!r}")

@@ -33,11 +33,12 @@ def run_label_cases(rw, cases: Sequence[Sequence[str]], run: Callable, write_thr
 
 def folder_plans_and_dataset(folder: str, plans_file_or_dict=None, dataset_json_file_or_dict=None,
                              missing_plans: Optional[str] = None, missing_dataset: Optional[str] = None,
-                             inflate_on_device: bool = False):
+                             inflate_on_device=False):
     """Plans and dataset.json as given (a dict or a file name), or looked for in ``folder`` -> (PlansManager, dataset.json,
     an instance of the reader-writer they name).  ``missing_*``: the caller's RuntimeError text for a file that is not in
     the folder, ``{}`` standing for its name (None: opening it raises).  ``inflate_on_device``: the reader-writer inflates
-    label files written with ``compress_on_device=True`` on the GPU (``NiftiIO(inflate_on_device=True)``)."""
+    label files written with ``compress_on_device=True`` on the GPU (``NiftiIO(inflate_on_device=True)``), with ``'dynamic'``
+    those written with ``compress_on_device='dynamic'`` too (``NiftiIO(inflate_on_device='dynamic')``)."""
     from .imageio import prediction_reader_writer_class
     from .plans import PlansManager
 

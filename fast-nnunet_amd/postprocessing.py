@@ -269,12 +269,14 @@ def apply_postprocessing_to_files(input_files: Sequence[str], output_files: Sequ
 
 def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict],
                                    plans_file_or_dict=None, dataset_json_file_or_dict=None, num_processes=8,
-                                   compress_on_device=False, inflate_on_device: bool = False) -> None:
+                                   compress_on_device=False, inflate_on_device=False) -> None:
     """``apply_postprocessing_to_folder`` (remove_connected_components.py:247-294).  If plans_file_or_dict or
     dataset_json_file_or_dict are None, they are looked for in input_folder.  ``num_processes`` is accepted and ignored;
     ``compress_on_device`` (True, or ``'dynamic'`` for per-chunk Huffman tables; anything but those and False is a
     ValueError before any file is read) writes the ``.nii.gz`` files through ``compress_labels`` (no label map is downloaded);
-    ``inflate_on_device`` reads input files that were written that way through ``fnn_inflate_segments`` (no zlib on the host)."""
+    ``inflate_on_device`` reads input files that were written that way through ``fnn_inflate_segments`` (no zlib on the host);
+    ``inflate_on_device='dynamic'`` through ``fnn_inflate_segments_dyn``, which serves files written with
+    ``compress_on_device='dynamic'`` too."""
     from .label_folders import folder_plans_and_dataset, subfiles
     compress_mode(compress_on_device)
     _, dataset_json, rw = folder_plans_and_dataset(
@@ -292,7 +294,7 @@ def apply_postprocessing_to_folder(input_folder: str, output_folder: str, pp_fns
 
 def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str, plans_file_or_dict=None,
                                        dataset_json_file_or_dict=None, num_processes: int = 8,
-                                       keep_postprocessed_files: bool = True, inflate_on_device: bool = False):
+                                       keep_postprocessed_files: bool = True, inflate_on_device=False):
     """The reference's ``determine_postprocessing`` (remove_connected_components.py:52-244) on folders of label files; see
     ``postprocessing_search.determine_postprocessing_on_folder``."""
     from .postprocessing_search import determine_postprocessing_on_folder as run

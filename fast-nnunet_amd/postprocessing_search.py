@@ -391,7 +391,7 @@ class FolderBackend(DeviceBackend):
 def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str, plans_file_or_dict=None,
                                        dataset_json_file_or_dict=None, num_processes: int = 8,
                                        keep_postprocessed_files: bool = True, verbose: bool = True,
-                                       inflate_on_device: bool = False):
+                                       inflate_on_device=False):
     """The reference's ``determine_postprocessing`` (remove_connected_components.py:52-244) on folders of label files.
 
     Leaves what the reference leaves: ``summary.json`` in ``folder_predictions`` (an existing one is reused, as the
@@ -399,7 +399,8 @@ def determine_postprocessing_on_folder(folder_predictions: str, folder_ref: str,
     False - ``postprocessed/<files>`` with ``postprocessed/summary.json``; no ``temp`` folder is made.  Plans or
     dataset.json given as None are looked for in ``folder_predictions``.  ``num_processes`` is accepted and ignored.
     ``inflate_on_device``: predictions written with ``compress_on_device=True``, which the search reads several times, are
-    inflated on the GPU (``NiftiIO(inflate_on_device=True)``).  Returns ``(pp_fns, pp_fn_kwargs)``."""
+    inflated on the GPU (``NiftiIO(inflate_on_device=True)``; ``'dynamic'``: those written with
+    ``compress_on_device='dynamic'`` too).  Returns ``(pp_fns, pp_fn_kwargs)``."""
     from .label_folders import folder_plans_and_dataset, subfiles
     missing = 'Expected plans file missing: {}. The plans files should have been created while running nnUNetv2_predict. Sadge.'
     plans_manager, dataset_json, rw = folder_plans_and_dataset(folder_predictions, plans_file_or_dict,

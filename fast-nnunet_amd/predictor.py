@@ -66,7 +66,8 @@ class nnUNetPredictor(object):
                        (larger, valid) deflate stream.  False (default): the host's gzip, byte for byte as before.
                        Returned arrays, ``.npz`` and ``.pkl`` are the same either way.  ``'dynamic'``: the same route
                        with per-chunk dynamic Huffman tables (``fnn_deflate_labels_dyn``) - smaller files, which
-                       ``NiftiIO(inflate_on_device=True)`` reads through its zlib fallback.  Anything but False, True
+                       ``NiftiIO(inflate_on_device='dynamic')`` inflates on the GPU (``inflate_on_device=True`` reads them
+                       through its zlib fallback).  Anything but False, True
                        and ``'dynamic'`` is a ValueError.
         """
         self.verbose = verbose

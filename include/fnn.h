@@ -664,8 +664,8 @@ int fnn_deflate_labels(const void *in, int in_elem_bytes, int64_t n_elems, int n
  * -> 16 with min(r, 6), else v itself - under a code-length code made by the same construction with limit 7; HCLEN
  * trimmed along the permuted order, at least 4.
  * csrc/deflate_dyn_core.h states the rule in full.  *dynamic_chunks (may be NULL): the chunks that took their own tables.
- * fnn_inflate_segments refuses such a fragment with FNN_INFLATE_DYNAMIC; zlib reads it.  The bytes depend on the input
- * alone.  Synchronises the stream.  Scratch, allocated inside the call: fnn_deflate_labels' and 420 B per chunk. */
+ * fnn_inflate_segments refuses such a fragment with FNN_INFLATE_DYNAMIC; fnn_inflate_segments_dyn and zlib read it.  The
+ * bytes depend on the input alone.  Synchronises the stream.  Scratch, allocated inside the call: fnn_deflate_labels' and 420 B per chunk. */
 int fnn_deflate_labels_dyn(const void *in, int in_elem_bytes, int64_t n_elems, int narrow_if_fits, void *out, int64_t out_cap,
                            int64_t *out_bytes, int *file_elem_bytes, uint32_t *crc32, int64_t *dynamic_chunks, void *stream);
 
@@ -747,6 +747,22 @@ int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t n_elems, c
 #define FNN_INFLATE_SIZE 11     /* the members' sizes do not sum to out_bytes                                           */
 int fnn_inflate_segments(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
                          int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream);
+
+/* fnn_inflate_segments for chains whose segments may hold dynamic-Huffman blocks too (additive in ABI 4): the fragments of
+ * fnn_deflate_labels_dyn, and what zlib writes with any strategy between Z_FULL_FLUSH points at most 16384 bytes apart.
+ * The same arguments, contract, chain rule, refusals before launch and scratch; the segment rule differs in one point: a
+ * BTYPE 10 block is decoded.  Its table header is accepted exactly where zlib's inflate accepts it - HLIT <= 286 and
+ * HDIST <= 30; a complete code-length code; the HLIT + HDIST lengths as one sequence, no 16 at position 0 and no run past
+ * the end; a code for symbol 256; literal / length and distance sets that are not over-subscribed and incomplete only with
+ * no code longer than 1 bit (a distance set of all zeros serves a block of literals only) - and refused with
+ * FNN_INFLATE_TABLES otherwise; a bit pattern that belongs to no symbol of an accepted incomplete set is
+ * FNN_INFLATE_SYMBOL.  FNN_INFLATE_DYNAMIC is never reported.  The two budgets of a segment are unchanged
+ * (csrc/inflate_dyn_core.h states the rule in full and the order of its checks).  On a stream without dynamic blocks the
+ * bytes, the CRC and the status are those of fnn_inflate_segments.  The kernels (csrc/inflate_dyn.hip) build each block's
+ * three canonical codes with the wave, in LDS. */
+#define FNN_INFLATE_TABLES 12   /* a dynamic block's table header that zlib's inflate would refuse (fnn_inflate_segments_dyn) */
+int fnn_inflate_segments_dyn(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
+                             int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream);
 
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one

@@ -20,7 +20,11 @@ profiles/r25_inflate.txt unless ``--out`` says otherwise) fnn_inflate_segments o
 n^3 map - 61 labels as uint8 and uint16 (long runs) and a map without runs (every byte a literal) - and on the fragments of
 60 masks, next to zlib's inflate of the same bytes on this machine's CPU and a device copy of the output, and
 compute_metrics_on_folder and apply_postprocessing_to_folder per case with ``inflate_on_device`` off and on over predictions
-written with ``compress_on_device=True``.  ``--section read`` runs the file -> device rows of both files alone and
+written with ``compress_on_device=True``; and (``--section inflate_dyn``, these rows alone, written to
+profiles/r32_inflate_dynamic.txt unless ``--out`` says otherwise) fnn_inflate_segments_dyn on the fragments
+fnn_deflate_labels_dyn makes of those maps and of the tiled golden mask, next to zlib's inflate and a device copy, the same
+entry next to fnn_inflate_segments on the fixed fragments, and the two folder commands over files written with
+``compress_on_device='dynamic'``, read with ``inflate_on_device=True`` (the zlib fallback) and ``'dynamic'``.  ``--section read`` runs the file -> device rows of both files alone and
 ``--section predict_files`` the two predict_from_files rows alone, with the defaults of the full run: for repeating those
 rows in many fresh processes (profiles/r24_host_prologue.txt).
 
@@ -28,7 +32,7 @@ The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, 
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient|deflate|masks|label_files|inflate|predict_files|read] [--out FILE]
+                                                          [--section all|reorient|deflate|masks|label_files|inflate|inflate_dyn|predict_files|read] [--out FILE]
 """
 import argparse
 import gzip
@@ -517,6 +521,123 @@ def bench_inflate(n, reps, cases, dev, say, row):
             row(f'  one case, both files device-written, flag {"on" if flag else "off"}: decode_label_maps', wall(lambda: rw.decode_label_maps(staged), reps)[:3])
 
 
+def bench_inflate_dyn(n, reps, cases, dev, say, row):
+    """fnn_inflate_segments_dyn (csrc/inflate_dyn.hip) on the fragments of fnn_deflate_labels_dyn against zlib's inflate on this
+    machine's CPU and a device copy of the output; the same entry on the fixed fragment next to fnn_inflate_segments (what
+    the general kernels cost a fixed-only file); and the folder commands on files written with compress_on_device='dynamic',
+    read with inflate_on_device=True (the zlib fallback) and 'dynamic'."""
+    import zlib
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import evaluation as ev
+    from fast_nnunet_amd import imageio as fio
+    from fast_nnunet_amd import postprocessing as pp
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    calls, windows = 10, max(reps, 5)
+    say(f'--- fnn_inflate_segments_dyn on fragments made by fnn_deflate_labels_dyn (dynamic) and fnn_deflate_labels (fixed); in and '
+        f'out allocated before, the call allocates its scratch and synchronises; ms per call from {calls} calls inside one pair of '
+        f'events, median (min, max) of {windows} such windows after a warm-up window, the windows of two calls that are compared '
+        f'in turn; zlib on this machine, one thread, by wall clock')
+
+    def candidates(frag):
+        return np.array([0] + [e for e in fio._marker_ends(frag, 0, len(frag)) if e < len(frag)], dtype=np.int64)
+
+    golden = os.path.join(ROOT, 'tests', 'golden', 'example_ct_sm_T300_output.nii.gz')
+    mask = np.frombuffer(gzip.decompress(open(golden, 'rb').read())[352:], np.uint8).reshape(30, 101, 122)
+    reps_of = [max(1, round(n / s)) for s in mask.shape]
+    synth = label_map(n, dev)
+    noise = torch.randint(0, 61, (n, n, n), dtype=torch.uint8, device=dev, generator=torch.Generator(dev).manual_seed(7))
+    inputs = [(f'61 labels, uint8 {n}^3 (long runs)', synth), (f'61 labels, uint16 {n}^3 (values x 1000; long runs)', synth.to(torch.int16) * 1000),
+              (f'golden mask tiled {reps_of} -> uint8 {tuple(r * s for r, s in zip(reps_of, mask.shape))}', torch.from_numpy(np.tile(mask, reps_of)).to(dev)),
+              (f'random labels 0 .. 60, uint8 {n}^3 (no runs: every byte a literal)', noise)]
+    for name, labels in inputs:
+        n_bytes = labels.numel() * labels.element_size()
+        cap = capi.deflate_bound(n_bytes)
+        made = {}
+        for kind in ('dynamic', 'fixed'):
+            buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+            if kind == 'dynamic':
+                n_in, _, crc_enc, dynamic_chunks = capi.deflate_labels_dyn(labels.data_ptr(), labels.element_size(), labels.numel(), False, buf.data_ptr(), cap, stream)
+            else:
+                n_in, _, crc_enc = capi.deflate_labels(labels.data_ptr(), labels.element_size(), labels.numel(), False, buf.data_ptr(), cap, stream)
+            frag = buf[:n_in].cpu().numpy().tobytes()
+            made[kind] = (buf, n_in, crc_enc, frag, candidates(frag))
+        out = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+        want = labels.reshape(-1).view(torch.uint8)
+        say(f'{name}: {n_bytes / 2 ** 20:.0f} MiB; dynamic fragment {made["dynamic"][1] / 2 ** 20:.2f} MiB ({dynamic_chunks} of '
+            f'{-(-n_bytes // 16384)} chunks with their own tables, {len(made["dynamic"][4])} candidates), fixed fragment '
+            f'{made["fixed"][1] / 2 ** 20:.2f} MiB ({len(made["fixed"][4])} candidates)')
+        buf, n_in, crc_enc, frag, starts = made['dynamic']
+        res = []
+        t = events_batched(lambda: res.append(capi.inflate_segments_dyn(buf.data_ptr(), n_in, starts, out.data_ptr(), n_bytes, stream)), calls, windows, dev)
+        same = res[-1] == (0, crc_enc) and bool((out == want).all())
+        row('  fnn_inflate_segments_dyn on the dynamic fragment', t,
+            f'  {n_bytes / t[0] / 1e6:.1f} GB/s of output; status and CRC good, bytes equal the map: {same}')
+        refused = capi.inflate_segments(buf.data_ptr(), n_in, starts, out.data_ptr(), n_bytes, stream)
+        say(f'  fnn_inflate_segments on the dynamic fragment: status {capi.INFLATE_REASONS[refused[0]]}')
+        tz = wall(lambda: zlib.decompressobj(-15).decompress(frag + b'\x03\x00'), reps)
+        row('  zlib inflate of the dynamic fragment (host)', tz[:3],
+            f'  {n_bytes / tz[0] / 1e6:.2f} GB/s; {tz[0] / t[0]:.1f}x the device call\'s time; CRC equal: {zlib.crc32(tz[3]) == res[-1][1]}')
+        dst = torch.empty_like(out)
+        tc = events_batched(lambda: dst.copy_(out), calls, windows, dev)
+        row('  device-to-device copy of the output bytes', tc, f'  {2 * n_bytes / tc[0] / 1e6:.0f} GB/s; the decoder takes {t[0] / tc[0]:.0f}x')
+        buf_f, n_f, crc_f, frag_f, starts_f = made['fixed']
+        res_a, res_b = [], []
+        tfix, tgen = events_batched_pair(
+            lambda: res_a.append(capi.inflate_segments(buf_f.data_ptr(), n_f, starts_f, out.data_ptr(), n_bytes, stream)),
+            lambda: res_b.append(capi.inflate_segments_dyn(buf_f.data_ptr(), n_f, starts_f, out.data_ptr(), n_bytes, stream)), calls, windows, dev)
+        row('  fnn_inflate_segments on the fixed fragment', tfix, f'  {n_bytes / tfix[0] / 1e6:.1f} GB/s of output')
+        row('  fnn_inflate_segments_dyn on the fixed fragment, windows in turn', tgen,
+            f'  {tgen[0] / tfix[0]:.2f}x the fixed entry; equal status and CRC: {res_a[-1] == res_b[-1] == (0, crc_f)}; the dynamic fragment '
+            f'takes {t[0] / tfix[0]:.2f}x the fixed route on the fixed fragment')
+        tzf = wall(lambda: zlib.decompressobj(-15).decompress(frag_f + b'\x03\x00'), reps)
+        row('  zlib inflate of the fixed fragment (host)', tzf[:3])
+        del made, buf, buf_f, out, dst, frag, frag_f, labels
+    del noise, inputs
+
+    wanted = list(range(1, 61))
+    say(f'--- folder commands, {cases} cases of {n}^3 voxels, 60 foreground labels: every file written with compress_on_device=\'dynamic\'; '
+        f'per-case wall clock with inflate_on_device=True (every file falls back to zlib) and \'dynamic\'')
+    plans = {'dataset_name': 'd', 'plans_name': 'p', 'image_reader_writer': 'NibabelIO', 'configurations': {}}
+    dj = {'labels': dict({'background': 0}, **{f'l{i}': i for i in wanted}), 'file_ending': '.nii.gz', 'channel_names': {'0': 'CT'}}
+    with tempfile.TemporaryDirectory() as tmp:
+        ref_d, pred_dir = (os.path.join(tmp, d) for d in ('ref_device', 'pred'))
+        for d in (ref_d, pred_dir):
+            os.makedirs(d)
+        writer = fio.NiftiIO(dev)
+        props = {'nibabel_stuff': {'original_affine': np.diag([0.8, 0.8, 1.25, 1.0])}}
+        for i in range(cases):
+            ref = label_map(n, dev, seed=30 + i)
+            pred = ref.clone()
+            pred[i::7] = 0
+            writer.write_seg(writer.compress_labels(ref, props, tables='dynamic'), os.path.join(ref_d, f'case{i}.nii.gz'), props)
+            writer.write_seg(writer.compress_labels(pred, props, tables='dynamic'), os.path.join(pred_dir, f'case{i}.nii.gz'), props)
+            del ref, pred
+        say(f'case0 on disk: reference {os.path.getsize(os.path.join(ref_d, "case0.nii.gz")) / 2 ** 20:.1f} MiB, prediction '
+            f'{os.path.getsize(os.path.join(pred_dir, "case0.nii.gz")) / 2 ** 20:.1f} MiB')
+        made = {}
+        for flag in (True, 'dynamic'):
+            rw = fio.NiftiIO(dev, inflate_on_device=flag)
+            ev.compute_metrics_on_folder(ref_d, pred_dir, None, rw, '.nii.gz', wanted)                       # warm-up
+            made[flag] = wall(lambda: ev.compute_metrics_on_folder(ref_d, pred_dir, None, rw, '.nii.gz', wanted), reps)
+            row(f'compute_metrics_on_folder, inflate_on_device={flag!r}', made[flag][:3], f'  {made[flag][0] / cases:.1f} ms per case; routes {rw.inflate_stats}')
+        say(f'  compute_metrics_on_folder: {made[True][0] / made["dynamic"][0]:.2f}x; equal results: {repr(made[True][3]) == repr(made["dynamic"][3])}')
+        fns, kwargs = [pp.remove_all_but_largest_component_from_segmentation], [{'labels_or_regions': wanted}]
+        made = {}
+        for flag in (True, 'dynamic'):
+            out_dir = os.path.join(tmp, f'post_{flag}')
+            run = lambda: pp.apply_postprocessing_to_folder(pred_dir, out_dir, fns, kwargs, plans, dj, compress_on_device='dynamic',   # noqa: E731
+                                                            inflate_on_device=flag)
+            run()                                                                                            # warm-up
+            made[flag] = wall(run, reps)
+            row(f'apply_postprocessing_to_folder (dynamic files out), inflate_on_device={flag!r}', made[flag][:3], f'  {made[flag][0] / cases:.1f} ms per case')
+        same = all(open(os.path.join(tmp, 'post_True', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'post_dynamic', f'case{i}.nii.gz'), 'rb').read()
+                   for i in range(cases))
+        say(f'  apply_postprocessing_to_folder: {made[True][0] / made["dynamic"][0]:.2f}x; identical output files: {same}')
+    say('--- decoder: the kernels decode canonically across lanes (ballot of 15 limits, one LDS read per symbol; 75 ballots '
+        'build a block\'s literal / length code).  The two-level lookup table was not built, so no row compares the two: the '
+        'cost of the general decoder is the "fixed fragment" pair of rows above, and what a table decoder would change is open.')
+
+
 def bench_predict_files(a, dev, say, row, tmp):
     """predict_from_files_sequential and predict_from_files on a.cases generated cases under tmp (``--section predict_files``
     runs these rows alone)."""
@@ -565,7 +686,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'inflate', 'predict_files', 'read'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'inflate', 'inflate_dyn', 'predict_files', 'read'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -594,6 +715,10 @@ def main():
     if a.section == 'inflate':
         bench_inflate(n, a.reps, a.cases, dev, say, row)
         write_out(a.out or os.path.join(ROOT, 'profiles', 'r25_inflate.txt'), lines)
+        return
+    if a.section == 'inflate_dyn':
+        bench_inflate_dyn(n, a.reps, a.cases, dev, say, row)
+        write_out(a.out or os.path.join(ROOT, 'profiles', 'r32_inflate_dynamic.txt'), lines)
         return
     if a.section == 'predict_files':
         with tempfile.TemporaryDirectory() as tmp:
