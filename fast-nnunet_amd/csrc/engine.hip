@@ -1,12 +1,13 @@
 // engine.hip - host side of the C ABI in include/fnn.h.
 //
-// Owns: the layer plan derived from fnn_arch_desc (what the reference builds
-// in PlainConvEncoder / UNetDecoder, nnUNetDistillationTrainer.py:141-173),
-// fp16 weight packing into MFMA fragment order, the activation / statistics /
-// accumulator arenas in HBM, and the sliding-window driver that replaces
+// Owns what runs: the activation / statistics / accumulator arenas in HBM, the
+// folds' packed weights, the streams, and the sliding-window driver that replaces
 // predict_from_raw_data.py:560-680 (x-major patch order, Gaussian weighting,
-// accumulate, normalise, un-pad; mirroring; fold ensembling).
+// accumulate, normalise, un-pad; mirroring; fold ensembling).  What the network
+// is - the layer list, the kernel per conv layer, every offset - is the
+// LayerPlan (layer_plan.h) that fnn_create makes once and everything here reads.
 #include "fnn_device.h"
+#include "layer_plan.h"
 #include "host_upload.h"
 #include "../../include/fnn.h"
 
@@ -26,42 +27,6 @@ namespace {
 
 thread_local std::string g_err;
 
-struct Layer {
-    enum Type { STEM, CONV, TCONV, POOL, COMBINE, GATHER } type;   // GATHER: the patches' input windows as an fp16 tensor (stem on the conv kernels)
-    int n_src = 1;
-    int cin_real[2] = {0, 0}, cin_pad[2] = {0, 0};
-    int cout_real = 0, cout_pad = 0;
-    int k[3] = {1, 1, 1}, s[3] = {1, 1, 1};
-    int in_dims[3], out_dims[3];
-    int src_layer[2] = {-1, -1};      // producing layer (-1 = the volume)
-    bool has_norm = true;             // a conv's output is normalised by its consumers; a tconv's / pool's / block's is not
-    bool act = true;                  // LeakyReLU after the norm (false: conv2 and the skip projection of a residual block)
-    bool has_bias = true;             // the skip projection of a residual block has no bias
-    // offsets
-    size_t w_off = 0;                 // halves, packed weights (STEM: floats in fparam)
-    size_t bias_off = 0, gamma_off = 0, beta_off = 0;   // floats
-    size_t stats_off = 0;             // doubles
-    size_t ss_off = 0;                // float2 (scale, shift) per channel
-    size_t out_off = 0;               // halves, activation arena (for batch = 1)
-    int64_t blob_w = 0, blob_b = 0, blob_g = 0, blob_beta = 0;
-    int ksteps = 0;                   // TCONV: k-steps of its packed weights
-    int stats_slots = FNN_STAT_REPL;  // rows per item in the stats buffer: atomics' replicas, or one row per tile
-    ConvChoice cc;                    // CONV: the kernel chosen when the engine was planned (conv_choose); its weights are packed
-                                      // for it, and stats_slots above is its
-    // conv3d_thin.hip: the stem as one MFMA per 16 voxels (w_off2 = its weight fragment in wpk); a CONV that recomputes
-    // its producer while staging (fuse = FUSE_STEM / FUSE_TCONV); a producer whose output is never written (virtual)
-    bool mfma_stem = false, virtual_out = false;
-    int pool_layer = -1;              // COMBINE: the POOL layer (the next stage's skip path) whose output this launch writes too; that POOL has pool_fused
-    bool pool_fused = false;
-    bool chunk_major = false;         // output stored [C / 16][voxels][16] (fnn_device.h, SrcDesc): convs / transposed convs whose consumers are convs
-    bool fp8 = false;                 // conv3d_zr8_kernel: e4m3 operands; oscale_off = per-cout output scales (floats)
-    size_t oscale_off = 0;
-    int fuse = 0;
-    size_t w_off2 = 0;
-    double flops = 0;                 // 2*MACs per patch
-    double bytes = 0;                 // algorithmic HBM bytes per patch: every input read once + the output written once (fp16)
-};
-
 struct FoldWeights {
     DevBuf wpk, fparam;                // f16 fragments; floats
     bool loaded = false;
@@ -73,34 +38,16 @@ struct Arena {
     DevBuf act, stats, ss;             // f16; double; float
 };
 
-inline int pad16(int c) { return (c + 15) / 16 * 16; }
 // z pitch of the volume accumulators: rows start 16-byte aligned for the vectorised read-modify-write
 inline long long zpitch(long long z) { return (z + 7) / 8 * 8; }
 
 }  // namespace
 
 struct fnn_engine {
-    fnn_arch_desc arch;
+    const LayerPlan plan;                   // what the network is: made by fnn_create before the engine, fixed for its life
+    explicit fnn_engine(LayerPlan &&p) : plan(std::move(p)) {}
     int device = 0;
-    int max_batch = 1;
     std::string err;
-    bool fuse_enabled = true;               // FNN_NO_FUSE (read when the engine is created) keeps every layer a kernel of its own
-    // FNN_FUSE_STEM = 0 | 1.  The transposed-conv fusion is always on (+1.2 % on the benchmark).  The stem
-    // fusion is on where the row-streaming kernels take both halves (conv_row_stem_kernel + stem_row_kernel's statistics
-    // pass, conv3d_row.hip); in tile form (FNN_FUSE_STEM=1 forces it) it is built and tested but slower than two kernels:
-    // its consumer is instruction-bound (one MFMA per 16 halo voxels needs ~45 instructions around it), 1020 + 340 us
-    // per batch against 575 + 756 us unfused.
-    int fuse_stem = -1;                     // -1: where the row kernels run it
-    ConvOverrides ov;                       // the test switches of the conv kernels' choice (read when the engine is created)
-    std::vector<Layer> layers;
-    int head_src = -1;                      // layer feeding the seg head
-    int hblocks = 0, head_ksteps = 0;
-    size_t head_w_off = 0, head_bias_off = 0;
-    int n_gpass = 1;                        // gather passes of <= 63 heads (GatherParams::n_pass); > 1: their own packs below
-    size_t gpass_w_off = 0, gpass_bias_off = 0;
-    int64_t blob_head_w = 0, blob_head_b = 0;
-    int64_t blob_count = 0;
-    size_t wpk_halves = 0, fparam_floats = 0, stats_doubles = 0, act_halves = 0, ss_count = 0;
     std::vector<FoldWeights> folds;
     // Batches in flight (fnn_accumulate / predict): one arena and one internal stream per batch in flight
     // (four by default since round 6, FNN_PIPES = 2..8; measured 2 -> 3: +1.5 %, 3 -> 4: +0.3 ... +0.9 %, beyond: nothing).  The network alternates between
@@ -132,7 +79,6 @@ struct fnn_engine {
     IntTable steps;                         // the tile-start / slot tables
     std::vector<std::string> klog;          // kernel variants of the last profiled call, one entry per launch (fnn_kernel_log)
     bool gather_enabled = true;             // FNN_NO_GATHER (read when the engine is created): always accumulate in HBM
-    double head_flops = 0, patch_flops = 0, patch_act_bytes = 0;
     // profiling
     bool profiling = false;
     struct Ev { Event a, b; int family; double flops, bytes; int layer; size_t klog_lo, klog_hi; };
@@ -170,356 +116,15 @@ int fail(fnn_engine *e, int code, const char *fmt, ...) {
         if (_r != hipSuccess) return fail(e, FNN_E_HIP, "%s failed: %s", #call, hipGetErrorString(_r)); \
     } while (0)
 
-// An arena's buffers in bytes - activations, statistics, scale / shift rows; returns their sum
-size_t arena_bytes(const fnn_engine *e, size_t b[3]) {
-    b[0] = e->act_halves * e->max_batch * sizeof(f16);
-    b[1] = e->stats_doubles * e->max_batch * sizeof(double);
-    b[2] = (e->ss_count * e->max_batch * 3 + 8) * sizeof(float);           // fp32 rows, then the fp16 rows (ssh_rows)
-    return b[0] + b[1] + b[2];
-}
-
 int arena_alloc(fnn_engine *e, Arena &A) {
     size_t b[3];
-    arena_bytes(e, b);
+    e->plan.arena_bytes(b);
     DevBuf *const buf[3] = {&A.act, &A.stats, &A.ss};
     static const char *const name[3] = {"activations", "stats", "scale/shift"};
     for (int i = 0; i < 3; ++i)
         if (hipError_t r = buf[i]->reserve(b[i])) { A = Arena{}; return fail(e, FNN_E_HIP, "hipMalloc(%s) failed: %s", name[i], hipGetErrorString(r)); }
     return 0;
 }
-
-// ---------------------------------------------------------------------------
-// plan
-// ---------------------------------------------------------------------------
-// The shape facts of a conv layer that its kernel's choice looks at (conv_choose); forward_batch launches the layer from
-// them.  fuse / T: recomputing its producer T
-ThinParams conv_shape(const fnn_engine *e, const Layer &L, int fuse = 0, const Layer *T = nullptr) {
-    ThinParams tp{};
-    ConvParams &q = tp.c;
-    q.plan_N = e->max_batch; q.N = e->max_batch; q.Cout = L.cout_pad; q.fp8 = L.fp8;
-    q.n_src = L.n_src; q.chunks = (L.cin_pad[0] + (L.n_src > 1 ? L.cin_pad[1] : 0)) / 16;
-    q.src[0].C = L.cin_pad[0]; q.src[1].C = L.n_src > 1 ? L.cin_pad[1] : 0;
-    q.Di = L.in_dims[0]; q.Hi = L.in_dims[1]; q.Wi = L.in_dims[2];
-    q.Do = L.out_dims[0]; q.Ho = L.out_dims[1]; q.Wo = L.out_dims[2];
-    q.kd = L.k[0]; q.kh = L.k[1]; q.kw = L.k[2]; q.sd = L.s[0]; q.sh = L.s[1]; q.sw = L.s[2];
-    tp.fuse = fuse;
-    if (T) {
-        tp.low.C = T->cin_pad[0];
-        tp.Dl = T->in_dims[0]; tp.Hl = T->in_dims[1]; tp.Wl = T->in_dims[2];
-        tp.tsd = T->s[0]; tp.tsh = T->s[1]; tp.tsw = T->s[2];
-    } else { tp.tsd = tp.tsh = tp.tsw = 1; }
-    return tp;
-}
-
-int build_plan(fnn_engine *e) {
-    const fnn_arch_desc &a = e->arch;
-    if (a.kind != FNN_NET_PLAIN && a.kind != FNN_NET_RESENC) return fail(e, FNN_E_UNSUPPORTED, "unknown network kind %d", a.kind);
-    if (a.n_stages < 2 || a.n_stages > FNN_MAX_STAGES) return fail(e, FNN_E_INVALID, "n_stages out of range");
-    if (a.in_channels < 1 || a.in_channels > 4096) return fail(e, FNN_E_UNSUPPORTED, "in_channels must be 1..4096");
-    if (a.num_heads < 1 || a.num_heads > 256) return fail(e, FNN_E_UNSUPPORTED, "num_heads must be 1..256");
-    for (int s = 0; s < a.n_stages; ++s)
-        for (int d = 0; d < 3; ++d) {
-            if (a.kernels[s][d] != 1 && a.kernels[s][d] != 3) return fail(e, FNN_E_UNSUPPORTED, "kernel sizes must be 1 or 3");
-            if (a.strides[s][d] != 1 && a.strides[s][d] != 2) return fail(e, FNN_E_UNSUPPORTED, "strides must be 1 or 2");
-            if (s == 0 && a.strides[s][d] != 1) return fail(e, FNN_E_UNSUPPORTED, "stage 0 must have stride 1");
-        }
-    if (a.spatial_dims != 0 && a.spatial_dims != 2 && a.spatial_dims != 3) return fail(e, FNN_E_INVALID, "spatial_dims must be 2 or 3");
-    if (a.spatial_dims == 2) {
-        if (a.patch[0] != 1) return fail(e, FNN_E_INVALID, "a 2-D configuration has patch[0] == 1");
-        for (int s = 0; s < a.n_stages; ++s)
-            if (a.kernels[s][0] != 1 || a.strides[s][0] != 1)
-                return fail(e, FNN_E_INVALID, "a 2-D configuration has kernel and stride 1 along the first axis");
-    }
-    int dims[FNN_MAX_STAGES][3];
-    for (int d = 0; d < 3; ++d) dims[0][d] = a.patch[d];
-    for (int s = 1; s < a.n_stages; ++s)
-        for (int d = 0; d < 3; ++d) {
-            const int k = a.kernels[s][d], st = a.strides[s][d], pad = (k - 1) / 2;
-            dims[s][d] = (dims[s - 1][d] + 2 * pad - k) / st + 1;
-            if (dims[s][d] * st != dims[s - 1][d])
-                return fail(e, FNN_E_INVALID, "patch size %d is not divisible by the pooling of axis %d", a.patch[d], d);
-        }
-    int64_t blob = 0;
-    bool next_has_bias = true, next_act = true;
-    auto add_conv = [&](Layer::Type type, int nsrc, const int cin[2], const int src[2], int cout, const int32_t *k,
-                        const int32_t *s, const int *in_d, const int *out_d) {
-        Layer L;
-        L.type = type; L.n_src = nsrc; L.has_bias = next_has_bias; L.act = next_act;
-        int cin_tot = 0;
-        for (int i = 0; i < nsrc; ++i) {
-            L.cin_real[i] = cin[i]; L.cin_pad[i] = (type == Layer::STEM) ? cin[i] : pad16(cin[i]);
-            L.src_layer[i] = src[i]; cin_tot += cin[i];
-        }
-        L.cout_real = cout; L.cout_pad = pad16(cout);
-        for (int d = 0; d < 3; ++d) { L.k[d] = k[d]; L.s[d] = s[d]; L.in_dims[d] = in_d[d]; L.out_dims[d] = out_d[d]; }
-        const int T = k[0] * k[1] * k[2];
-        L.blob_w = blob; blob += (int64_t)cout * cin_tot * T;
-        L.blob_b = blob; if (L.has_bias) blob += cout;
-        L.blob_g = blob; blob += cout;
-        L.blob_beta = blob; blob += cout;
-        L.flops = 2.0 * cout * cin_tot * T * out_d[0] * out_d[1] * out_d[2];
-        L.bytes = 2.0 * ((double)cin_tot * in_d[0] * in_d[1] * in_d[2] * (type == Layer::STEM ? 2 : 1)     // fp32 volume
-                         + (double)cout * out_d[0] * out_d[1] * out_d[2]);
-        e->layers.push_back(L);
-        return (int)e->layers.size() - 1;
-    };
-    const int32_t one[3] = {1, 1, 1};
-    int prev = -1, prev_c = a.in_channels;
-    int enc_last[FNN_MAX_STAGES];
-    auto add_aux = [&](Layer::Type type, int src0, int src1, int channels, const int32_t *st, const int *in_d, const int *out_d) {
-        Layer L;
-        L.type = type; L.n_src = src1 >= 0 ? 2 : 1; L.has_norm = false;
-        L.src_layer[0] = src0; L.src_layer[1] = src1;
-        L.cin_real[0] = channels; L.cin_pad[0] = pad16(channels);
-        L.cout_real = channels; L.cout_pad = pad16(channels);
-        for (int d = 0; d < 3; ++d) { L.s[d] = st[d]; L.in_dims[d] = in_d[d]; L.out_dims[d] = out_d[d]; }
-        e->layers.push_back(L);
-        return (int)e->layers.size() - 1;
-    };
-    // The first conv of the network.  One input channel in 3-D: the stem kernels (conv3d_thin.hip / conv3d_row.hip: the window
-    // of the fp32 volume in LDS, one MFMA per 16 voxels).  More channels (multi-modal MR, a cascade's one-hot channels) or a
-    // `2d` configuration (depth-1 tiles: a sixteenth of that kernel's tile): the patches' windows are first written as an fp16
-    // tensor with the channels padded to 16 (patch_input_kernel, body.hip) and the stem is an ordinary conv layer on the MFMA
-    // conv kernels - plan sweep, round 6: the generic multi-channel stem took 17 % (4 channels) to 55 % (14) of a forward.
-    auto add_stem = [&](int cin, int cout, const int32_t *k, const int *d) {
-        const bool via_conv = (cin >= 2 || a.spatial_dims == 2) && fnn_knob("FNN_STEM_DIRECT") == nullptr;   // (knob: A-B aid / the tests of the generic stem kernel)
-        const int c[2] = {cin, 0};
-        if (!via_conv) {
-            const int src[2] = {-1, -1};
-            return add_conv(Layer::STEM, 1, c, src, cout, k, one, d, d);
-        }
-        Layer G;
-        G.type = Layer::GATHER; G.n_src = 1; G.has_norm = false;
-        G.cin_real[0] = cin; G.cin_pad[0] = pad16(cin); G.cout_real = cin; G.cout_pad = pad16(cin);
-        for (int q = 0; q < 3; ++q) { G.in_dims[q] = d[q]; G.out_dims[q] = d[q]; }
-        e->layers.push_back(G);
-        const int src[2] = {(int)e->layers.size() - 1, -1};
-        const int li = add_conv(Layer::CONV, 1, c, src, cout, k, one, d, d);
-        e->layers[li].bytes += 2.0 * cin * (double)d[0] * d[1] * d[2];                  // the network input is fp32 in HBM
-        return li;
-    };
-    if (a.kind == FNN_NET_PLAIN) {
-        for (int s = 0; s < a.n_stages; ++s) {
-            if (a.n_conv_enc[s] < 1) return fail(e, FNN_E_INVALID, "n_conv_per_stage must be >= 1");
-            for (int i = 0; i < a.n_conv_enc[s]; ++i) {
-                const int cin[2] = {prev_c, 0}, src[2] = {prev, -1};
-                const bool first = (s == 0 && i == 0);
-                const int *in_d = (i == 0 && s > 0) ? dims[s - 1] : dims[s];
-                prev = first ? add_stem(prev_c, a.features[s], a.kernels[s], dims[s])
-                             : add_conv(Layer::CONV, 1, cin, src, a.features[s], a.kernels[s], i == 0 ? a.strides[s] : one, in_d, dims[s]);
-                prev_c = a.features[s];
-            }
-            enc_last[s] = prev;
-        }
-    } else {
-        // ResidualEncoderUNet: stem conv, then per stage n_conv_enc[s] BasicBlockD blocks
-        //   y = LeakyReLU(norm(conv2(act(norm(conv1(x))))) + skip(x)),  skip = [AvgPool(stride)] [1x1x1 conv (no bias) + norm]
-        {
-            prev = add_stem(a.in_channels, a.features[0], a.kernels[0], dims[0]);
-            prev_c = a.features[0];
-        }
-        for (int s = 0; s < a.n_stages; ++s) {
-            if (a.n_conv_enc[s] < 1) return fail(e, FNN_E_INVALID, "n_blocks_per_stage must be >= 1");
-            for (int b = 0; b < a.n_conv_enc[s]; ++b) {
-                const int32_t *st = b == 0 ? a.strides[s] : one;
-                const int *in_d = (b == 0 && s > 0) ? dims[s - 1] : dims[s];
-                const bool strided = st[0] != 1 || st[1] != 1 || st[2] != 1;
-                const int F = a.features[s];
-                const int cin1[2] = {prev_c, 0}, src1[2] = {prev, -1};
-                const int c1 = add_conv(Layer::CONV, 1, cin1, src1, F, a.kernels[s], st, in_d, dims[s]);
-                const int cin2[2] = {F, 0}, src2[2] = {c1, -1};
-                next_act = false;
-                const int c2 = add_conv(Layer::CONV, 1, cin2, src2, F, a.kernels[s], one, dims[s], dims[s]);
-                next_act = true;
-                int skip = prev;
-                if (strided) {
-                    skip = add_aux(Layer::POOL, prev, -1, prev_c, st, in_d, dims[s]);
-                    // the pooled tensor is written by the launch that forms the block output it pools (combine_pool_kernel)
-                    Layer &Cb = e->layers[prev];
-                    if (e->fuse_enabled && fnn_knob("FNN_NO_POOL_FUSE") == nullptr && Cb.type == Layer::COMBINE &&
-                        combine_pool_ok(in_d[0], in_d[1], in_d[2], st[0], st[1], st[2])) {
-                        Cb.pool_layer = skip; e->layers[skip].pool_fused = true;
-                    }
-                }
-                if (prev_c != F) {
-                    const int cinp[2] = {prev_c, 0}, srcp[2] = {skip, -1};
-                    next_has_bias = false; next_act = false;
-                    skip = add_conv(Layer::CONV, 1, cinp, srcp, F, one, one, dims[s], dims[s]);
-                    next_has_bias = true; next_act = true;
-                }
-                prev = add_aux(Layer::COMBINE, c2, skip, F, one, dims[s], dims[s]);
-                prev_c = F;
-            }
-            enc_last[s] = prev;
-        }
-    }
-    for (int d = 0; d < a.n_stages - 1; ++d) {
-        const int lvl = a.n_stages - 2 - d;           // encoder stage whose skip is consumed
-        const int below = prev_c, skip = a.features[lvl];
-        const int32_t *st = a.strides[lvl + 1];
-        Layer T;
-        T.type = Layer::TCONV; T.n_src = 1; T.has_norm = false;
-        T.cin_real[0] = below; T.cin_pad[0] = pad16(below); T.src_layer[0] = prev;
-        T.cout_real = skip; T.cout_pad = pad16(skip);
-        for (int q = 0; q < 3; ++q) { T.k[q] = st[q]; T.s[q] = st[q]; T.in_dims[q] = dims[lvl + 1][q]; T.out_dims[q] = dims[lvl][q]; }
-        const int taps = st[0] * st[1] * st[2];
-        T.blob_w = blob; blob += (int64_t)below * skip * taps;
-        T.blob_b = blob; blob += skip;
-        T.flops = 2.0 * below * skip * (double)dims[lvl][0] * dims[lvl][1] * dims[lvl][2];
-        e->layers.push_back(T);
-        const int tl = (int)e->layers.size() - 1;
-        if (a.n_conv_dec[d] < 1) return fail(e, FNN_E_INVALID, "n_conv_per_stage_decoder must be >= 1");
-        for (int i = 0; i < a.n_conv_dec[d]; ++i) {
-            if (i == 0) {
-                const int cin[2] = {skip, skip}, src[2] = {tl, enc_last[lvl]};
-                prev = add_conv(Layer::CONV, 2, cin, src, skip, a.kernels[lvl], one, dims[lvl], dims[lvl]);
-            } else {
-                const int cin[2] = {skip, 0}, src[2] = {prev, -1};
-                prev = add_conv(Layer::CONV, 1, cin, src, skip, a.kernels[lvl], one, dims[lvl], dims[lvl]);
-            }
-        }
-        prev_c = skip;
-    }
-    e->head_src = prev;
-    e->blob_head_w = blob; blob += (int64_t)a.num_heads * a.features[0];
-    e->blob_head_b = blob; blob += a.num_heads;
-    e->blob_count = blob;
-
-    for (Layer &L : e->layers)
-        if (L.type == Layer::STEM) {
-            if (!stem_mfma_ok(L.cin_real[0], L.k[0], L.k[1], L.k[2], L.cout_pad)) return fail(e, FNN_E_UNSUPPORTED, "stem conv shape");
-            L.mfma_stem = true;
-        }
-    // ---- producers recomputed inside their consumer's staging (conv3d_thin.hip, conv3d_row.hip): where a kernel takes the fused layer
-    if (a.spatial_dims != 2 && e->fuse_enabled) {
-        std::vector<int> consumers(e->layers.size(), 0);
-        for (const Layer &L : e->layers)
-            for (int i = 0; i < L.n_src; ++i) if (L.src_layer[i] >= 0) consumers[L.src_layer[i]]++;
-        for (Layer &L : e->layers) {
-            if (L.type != Layer::CONV || L.src_layer[0] < 0) continue;
-            Layer &P = e->layers[L.src_layer[0]];
-            if (consumers[L.src_layer[0]] != 1 || P.cout_pad != 16) continue;
-            ConvChoice c;
-            if (e->fuse_stem != 0 && L.n_src == 1 && P.type == Layer::STEM && P.mfma_stem && P.cin_real[0] == 1 && P.k[0] == L.k[0] &&
-                conv_choose(conv_shape(e, L, FUSE_STEM), e->ov, c)) {
-                // by default only where the row kernels take both halves: conv_row_stem_kernel + stem_row_kernel (statistics)
-                StemParams sp{};
-                sp.C = P.cin_real[0]; sp.kd = P.k[0]; sp.kh = P.k[1]; sp.kw = P.k[2]; sp.Cout = P.cout_pad;
-                sp.PD = P.out_dims[0]; sp.PH = P.out_dims[1]; sp.PW = P.out_dims[2];
-                if (e->fuse_stem == 1 || (c.kernel == CK_ROW_STEM && stem_row_ok(sp))) { L.fuse = FUSE_STEM; L.cc = c; P.virtual_out = true; }
-            } else if (L.n_src == 2 && P.type == Layer::TCONV && conv_choose(conv_shape(e, L, FUSE_TCONV, &P), e->ov, c)) {
-                L.fuse = FUSE_TCONV; L.cc = c; P.virtual_out = true;
-            }
-        }
-    }
-
-    // activation layouts: a tensor of more than 16 channels that only conv / transposed-conv kernels read is stored
-    // chunk-major, so that a consumer's 16-channel chunk is whole cache lines instead of 32 bytes of every record
-    if (fnn_knob("FNN_NO_CHUNK_MAJOR") == nullptr) {
-        const int cm_min = fnn_knob("FNN_CM_MIN") ? atoi(fnn_knob("FNN_CM_MIN")) : 16;       // A-B aid: chunk-major above this many channels
-        std::vector<int> ok(e->layers.size(), 1);
-        for (const Layer &L : e->layers)
-            for (int i = 0; i < L.n_src; ++i)
-                if (L.src_layer[i] >= 0 && L.type != Layer::CONV && L.type != Layer::TCONV && L.type != Layer::POOL &&
-                    L.type != Layer::COMBINE) ok[L.src_layer[i]] = 0;
-        for (size_t li = 0; li < e->layers.size(); ++li) {
-            Layer &L = e->layers[li];
-            L.chunk_major = ok[li] && (int)li != e->head_src &&
-                            (L.type == Layer::CONV || L.type == Layer::TCONV || L.type == Layer::POOL || L.type == Layer::COMBINE) &&
-                            L.cout_pad > cm_min && a.spatial_dims != 2;
-        }
-    }
-
-    // device offsets
-    size_t wpk = 0, fp = 0, st = 0, act = 0, ssn = 0;
-    double flops = 0, bytes = 0;
-    for (Layer &L : e->layers) {
-        const size_t ovox = (size_t)L.out_dims[0] * L.out_dims[1] * L.out_dims[2];
-        if (L.type == Layer::STEM) {
-            const int T = L.k[0] * L.k[1] * L.k[2];
-            L.w_off = fp; fp += (size_t)L.cin_real[0] * T * L.cout_pad;
-            if (L.mfma_stem) { L.w_off2 = wpk; wpk += (size_t)(L.cout_pad / 16) * stem_mfma_ksteps(L.cin_real[0], L.k[0] * L.k[1] * L.k[2]) * 512; }
-        } else if (L.type == Layer::CONV) {
-            if (!L.fuse) {
-                ThinParams tp = conv_shape(e, L);
-                // e4m3 operands where conv_choose_fp8 lets them stick (the stride-1 3x3x3 layers the fp8 ZR kernel takes)
-                tp.c.fp8 = a.precision == FNN_PREC_F8 &&
-                           !(L.src_layer[0] >= 0 && e->layers[L.src_layer[0]].type == Layer::GATHER);   // (the network input keeps fp16: the stem was never an fp8 layer)
-                if (tp.c.fp8 && e->ov.fp8_levels >= 0) {
-                    // sensitivity studies (tools/fp8_sensitivity.py): e4m3 operands only at the resolution levels of the bit mask
-                    // (level = how many times the patch's voxel count was divided by ~8 on the way to this layer's output)
-                    const double P = (double)a.patch[0] * a.patch[1] * a.patch[2];
-                    const int level = (int)std::lround(std::log2(P / (double)ovox) / 3.0);
-                    tp.c.fp8 = ((e->ov.fp8_levels >> level) & 1) != 0;
-                }
-                const bool ok = conv_choose_fp8(tp, e->ov, L.cc);
-                if (!ok) return fail(e, FNN_E_UNSUPPORTED, "no conv kernel takes layer %zu (%dx%dx%d, stride %dx%dx%d, %d -> %d channels)",
-                                     (size_t)(&L - e->layers.data()), L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2], tp.c.chunks * 16, L.cout_pad);
-                L.fp8 = tp.c.fp8 != 0;
-            }
-            L.w_off = wpk; wpk += conv_packed_halves(L.cc, L.cout_pad);
-        } else if (L.type == Layer::TCONV) {
-            const int taps = L.s[0] * L.s[1] * L.s[2];
-            L.ksteps = (L.cin_pad[0] + 31) / 32;
-            L.w_off = wpk; wpk += (size_t)taps * (L.cout_pad / 16) * L.ksteps * 512;
-        }
-        L.bias_off = fp; fp += L.cout_pad;
-        if (L.fp8) { L.oscale_off = fp; fp += L.cout_pad; }
-        if (L.has_norm) { L.gamma_off = fp; fp += L.cout_pad; L.beta_off = fp; fp += L.cout_pad; }
-        L.stats_slots = FNN_STAT_REPL;
-        if (L.type == Layer::STEM) L.stats_slots = stem_mfma_stats_slots(L.out_dims[0], L.out_dims[1], L.out_dims[2]);
-        else if (L.type == Layer::CONV) L.stats_slots = L.cc.stats_slots;
-        L.stats_off = st; if (L.has_norm) st += (size_t)L.stats_slots * L.cout_pad * 2;
-        L.ss_off = ssn; if (L.has_norm) ssn += L.cout_pad;
-        L.out_off = act; act += ovox * L.cout_pad;
-        flops += L.flops;
-        bytes += 2.0 * ovox * L.cout_real * 2.0;            // written once + read once, fp16
-    }
-    e->hblocks = (a.num_heads + 1 + 15) / 16;               // + the weight-sum channel (zero weights, bias 1: its "logit" is 1)
-    e->head_ksteps = (pad16(a.features[0]) + 31) / 32;
-    e->head_w_off = wpk; wpk += (size_t)e->hblocks * e->head_ksteps * 512;
-    e->head_bias_off = fp; fp += (size_t)e->hblocks * 16;
-    e->n_gpass = (a.num_heads + 62) / 63;
-    if (e->n_gpass > 1) {
-        e->gpass_w_off = wpk; wpk += (size_t)e->n_gpass * 4 * 512;
-        e->gpass_bias_off = fp; fp += (size_t)e->n_gpass * 64;
-    }
-    const double P = (double)a.patch[0] * a.patch[1] * a.patch[2];
-    e->head_flops = 2.0 * a.num_heads * a.features[0] * P;
-    e->patch_flops = flops + e->head_flops;
-    // skips are read twice (next encoder stage and decoder); network input read once
-    for (int s = 0; s < a.n_stages - 1; ++s) {
-        const Layer &L = e->layers[enc_last[s]];
-        bytes += (double)L.out_dims[0] * L.out_dims[1] * L.out_dims[2] * L.cout_real * 2.0;
-    }
-    e->patch_act_bytes = bytes;
-    e->wpk_halves = wpk; e->fparam_floats = fp; e->stats_doubles = st; e->act_halves = act; e->ss_count = ssn;
-    return 0;
-}
-
-// ---------------------------------------------------------------------------
-// weight packing (host)
-// ---------------------------------------------------------------------------
-}  // namespace
-// (declared in fnn_device.h: the single-op entry points pack a head the same way)
-void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, unsigned short *dst) {
-    for (int hb = 0; hb < hblocks; ++hb)
-        for (int ks = 0; ks < ksteps; ++ks)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int ci = ks * 32 + 8 * (lane >> 4) + j, h = hb * 16 + (lane & 15);
-                    float v = 0.f;
-                    if (ci < cin && h < heads) v = W[(size_t)h * cin + ci];
-                    dst[(((size_t)hb * ksteps + ks) * 64 + lane) * 8 + j] = fnn_half_bits(v);
-                }
-}
-
-// bias row of the head kernels, [hblocks * 16]: the heads' biases, then the weight-sum channel (zero weights in pack_head,
-// bias 1: its "logit" is 1 and 1 * gaussian is the weight itself), zeros behind it
-void pack_head_bias(int heads, int hblocks, const float *bias, float *dst) {
-    for (int h = 0; h < hblocks * 16; ++h) dst[h] = h < heads ? (bias ? bias[h] : 0.f) : (h == heads ? 1.f : 0.f);
-}
-namespace {
 
 // ---------------------------------------------------------------------------
 // profiling helpers
@@ -579,26 +184,20 @@ void collect_profile(fnn_engine *e, int64_t n_patches) {
 // ---------------------------------------------------------------------------
 // the fp16 scale / shift rows (SrcDesc::ssh) live behind the fp32 rows of the same arena: [ss_count * max_batch * 2 + 4] floats,
 // then ss_count * max_batch * 2 halves
-unsigned short *ssh_rows(const fnn_engine *e, const Arena &A) { return (unsigned short *)(A.ss.as<float>() + e->ss_count * e->max_batch * 2 + 4); }
+unsigned short *ssh_rows(const fnn_engine *e, const Arena &A) { return (unsigned short *)(A.ss.as<float>() + e->plan.ss_count * e->plan.max_batch * 2 + 4); }
 
-// A layer's output layout as SrcDesc::vs / cs: chunk-major (16, 16 x voxels), or channels-last - (0, 0), which the launch
-// parameters' out_vs / out_cs read as (C, 16)
-struct Layout { int vs; long long cs; };
-Layout layout(const Layer &L) {
-    return L.chunk_major ? Layout{16, 16LL * L.out_dims[0] * L.out_dims[1] * L.out_dims[2]} : Layout{0, 0};
-}
 
 SrcDesc make_src(const fnn_engine *e, const Arena &A, int layer) {
-    const Layer &L = e->layers[layer];
+    const Layer &L = e->plan.layers[layer];
     SrcDesc s{};
-    s.ptr = A.act.as<f16>() + L.out_off * e->max_batch;
+    s.ptr = A.act.as<f16>() + L.out_off * e->plan.max_batch;
     s.C = L.cout_pad;
-    const Layout lay = layout(L);
+    const Layout lay = LayerPlan::layout(L);
     s.vs = lay.vs ? lay.vs : L.cout_pad; s.cs = lay.vs ? lay.cs : 16;   // (spelled out: a one-source conv's src[1] is a copy with C = 0)
     if (L.has_norm) {
-        s.ss = A.ss.as<float>() + L.ss_off * e->max_batch * 2;
-        s.ssh = ssh_rows(e, A) + L.ss_off * e->max_batch * 2;        // halves: [N][C / 8][16] = 2 C per item
-        s.slope = L.act ? e->arch.slope : 1.f;
+        s.ss = A.ss.as<float>() + L.ss_off * e->plan.max_batch * 2;
+        s.ssh = ssh_rows(e, A) + L.ss_off * e->plan.max_batch * 2;        // halves: [N][C / 8][16] = 2 C per item
+        s.slope = L.act ? e->plan.arch.slope : 1.f;
     } else {
         s.ss = nullptr; s.ssh = nullptr; s.slope = 1.f;
     }
@@ -612,16 +211,17 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
                   float *head_ss = nullptr, unsigned short *head_ssh = nullptr) {
     f16 *const wpk = e->folds[fold].wpk.as<f16>(), *const act = A.act.as<f16>();
     float *const fparam = e->folds[fold].fparam.as<float>(), *const ss = A.ss.as<float>();
+    const LayerPlan &plan = e->plan;
     double *const stats = A.stats.as<double>();
-    HIPCHK(e, hipMemsetAsync(stats, 0, e->stats_doubles * e->max_batch * sizeof(double), st));
+    HIPCHK(e, hipMemsetAsync(stats, 0, plan.stats_doubles * plan.max_batch * sizeof(double), st));
     struct LayerMark { fnn_engine *e; ~LayerMark() { e->cur_layer = -1; } } mark{e};
-    for (size_t li = 0; li < e->layers.size(); ++li) {
-        const Layer &L = e->layers[li];
+    for (size_t li = 0; li < plan.layers.size(); ++li) {
+        const Layer &L = plan.layers[li];
         e->cur_layer = (int)li;
-        f16 *out = act + L.out_off * e->max_batch;
-        if (head_out && (int)li == e->head_src) out = head_out;
-        const Layout lay = layout(L);
-        double *stats_out = L.has_norm ? stats + L.stats_off * e->max_batch : nullptr;
+        f16 *out = act + L.out_off * plan.max_batch;
+        if (head_out && (int)li == plan.head_src) out = head_out;
+        const Layout lay = LayerPlan::layout(L);
+        double *stats_out = L.has_norm ? stats + L.stats_off * plan.max_batch : nullptr;
         int rc = 0;
         if (L.type == Layer::STEM) {
             StemParams p{};
@@ -638,8 +238,8 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
             if (L.virtual_out) p.out = nullptr;                       // statistics only: the consumer recomputes the values
             rc = launch_stem_mfma(p, wpk + L.w_off2, nb, st);
         } else if (L.type == Layer::CONV) {
-            const Layer *P = L.fuse ? &e->layers[L.src_layer[0]] : nullptr;        // the producer a fused layer recomputes
-            ThinParams tp = conv_shape(e, L, L.fuse, L.fuse == FUSE_TCONV ? P : nullptr);
+            const Layer *P = L.fuse ? &plan.layers[L.src_layer[0]] : nullptr;        // the producer a fused layer recomputes
+            ThinParams tp = plan.conv_shape(L, L.fuse, L.fuse == FUSE_TCONV ? P : nullptr);
             ConvParams &p = tp.c;
             p.N = nb;
             for (int i = 0; i < L.n_src; ++i) p.src[i] = make_src(e, A, L.src_layer[i]);
@@ -656,7 +256,7 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
                     tp.fw = wpk + P->w_off2;
                     tp.vol = vol; tp.vol_batch_stride = vol_batch_stride; tp.Y = vdim[1]; tp.Z = vdim[2];
                     tp.origins = origins_dev; tp.flip_d = flip[0]; tp.flip_h = flip[1]; tp.flip_w = flip[2];
-                    tp.fss = ss + P->ss_off * e->max_batch * 2; tp.fslope = e->arch.slope;
+                    tp.fss = ss + P->ss_off * plan.max_batch * 2; tp.fslope = plan.arch.slope;
                 } else {
                     tp.fw = wpk + P->w_off;
                     tp.low = make_src(e, A, P->src_layer[0]);
@@ -687,11 +287,11 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
             p.a = make_src(e, A, L.src_layer[0]);
             p.b = make_src(e, A, L.src_layer[1]);
             p.vox = (long long)L.out_dims[0] * L.out_dims[1] * L.out_dims[2];
-            p.N = nb; p.slope = e->arch.slope; p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs;
+            p.N = nb; p.slope = plan.arch.slope; p.out = out; p.out_vs = lay.vs; p.out_cs = lay.cs;
             if (L.pool_layer >= 0) {
-                const Layer &P = e->layers[L.pool_layer];
-                const Layout pool = layout(P);
-                p.pool_out = act + P.out_off * e->max_batch;
+                const Layer &P = plan.layers[L.pool_layer];
+                const Layout pool = LayerPlan::layout(P);
+                p.pool_out = act + P.out_off * plan.max_batch;
                 p.D = L.out_dims[0]; p.H = L.out_dims[1]; p.W = L.out_dims[2];
                 p.psd = P.s[0]; p.psh = P.s[1]; p.psw = P.s[2];
                 p.pool_vs = pool.vs; p.pool_cs = pool.cs;
@@ -713,11 +313,11 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
         if (L.has_norm) {
             StatsFinalizeParams q{};
             q.stats = stats_out; q.gamma = fparam + L.gamma_off; q.beta = fparam + L.beta_off;
-            q.ss = ss + L.ss_off * e->max_batch * 2; q.C = L.cout_pad; q.nrep = L.stats_slots;
-            q.ssh = ssh_rows(e, A) + L.ss_off * e->max_batch * 2;
-            if (head_ss && (int)li == e->head_src) q.ss = head_ss;
-            if (head_ssh && (int)li == e->head_src) q.ssh = head_ssh;
-            q.inv_count = 1.f / ((float)L.out_dims[0] * L.out_dims[1] * L.out_dims[2]); q.eps = e->arch.eps;
+            q.ss = ss + L.ss_off * plan.max_batch * 2; q.C = L.cout_pad; q.nrep = L.stats_slots;
+            q.ssh = ssh_rows(e, A) + L.ss_off * plan.max_batch * 2;
+            if (head_ss && (int)li == plan.head_src) q.ss = head_ss;
+            if (head_ssh && (int)li == plan.head_src) q.ssh = head_ssh;
+            q.inv_count = 1.f / ((float)L.out_dims[0] * L.out_dims[1] * L.out_dims[2]); q.eps = plan.arch.eps;
             if (launch_stats_finalize(q, nb, st) != 0) return fail(e, FNN_E_HIP, "stats finalize launch failed");
         }
     }
@@ -725,13 +325,13 @@ int forward_batch(fnn_engine *e, int fold, const Arena &A, const float *vol, lon
 }
 
 HeadParams make_head(const fnn_engine *e, const Arena &A, int fold, int b) {
-    const fnn_arch_desc &a = e->arch;
+    const fnn_arch_desc &a = e->plan.arch;
     const FoldWeights &fw = e->folds[fold];
     HeadParams h{};
-    h.src = make_src(e, A, e->head_src);
+    h.src = make_src(e, A, e->plan.head_src);
     h.b = b; h.PD = a.patch[0]; h.PH = a.patch[1]; h.PW = a.patch[2];
-    h.heads = a.num_heads; h.hblocks = e->hblocks; h.ksteps = e->head_ksteps;
-    h.wpk = fw.wpk.as<f16>() + e->head_w_off; h.bias = fw.fparam.as<float>() + e->head_bias_off;
+    h.heads = a.num_heads; h.hblocks = e->plan.hblocks; h.ksteps = e->plan.head_ksteps;
+    h.wpk = fw.wpk.as<f16>() + e->plan.head_w_off; h.bias = fw.fparam.as<float>() + e->plan.head_bias_off;
     h.fx = h.fy = h.fz = INT_MAX;                           // every voxel is read unless run_patches knows better
     return h;
 }
@@ -785,7 +385,7 @@ int plan_volume_p(const int32_t patch[3], const int64_t sp[3], double step, bool
 
 // The plan of a call's volume (shape [C][X][Y][Z]); the call fails when the shape and the step size make none
 int plan_volume(fnn_engine *e, const int64_t shape[4], const fnn_opts &o, VolPlan &vp) {
-    if (plan_volume_p(e->arch.patch, shape + 1, o.tile_step_size, e->arch.spatial_dims == 2, vp) != 0)
+    if (plan_volume_p(e->plan.arch.patch, shape + 1, o.tile_step_size, e->plan.arch.spatial_dims == 2, vp) != 0)
         return fail(e, FNN_E_INVALID, "invalid volume shape / step size");
     return 0;
 }
@@ -883,7 +483,7 @@ template <class Params> void place_patch(Params &p, const fnn_engine *e, const f
     const Box &box = t.box;
     p.gauss = (o.use_gaussian ? e->gauss : e->ones).as<f16>();
     p.acc = t.acc; p.AX = box.hi[0] - box.lo[0]; p.Y = box.hi[1] - box.lo[1]; p.Z = box.hi[2] - box.lo[2];
-    p.HP = acc_hp(e->arch); p.acc_fp32 = t.acc_fp32;
+    p.HP = acc_hp(e->plan.arch); p.acc_fp32 = t.acc_fp32;
     p.ox = oo[0] - (int)box.lo[0]; p.oy = oo[1] - (int)box.lo[1]; p.oz = oo[2] - (int)box.lo[2];
 }
 
@@ -894,7 +494,7 @@ int add_pipes(fnn_engine *e, int want, int *np) {
     int NP = std::clamp(want, 2, (int)fnn_engine::MAXP);
     if (e->n_pipe < NP) {
         size_t b[3], free_b = 0, total_b = 0;
-        const size_t arena = arena_bytes(e, b);
+        const size_t arena = e->plan.arena_bytes(b);
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && arena > 0) {
             const long long by_total = (long long)(total_b / 2 / arena), by_free = (long long)(free_b * 8 / 10 / arena) + e->n_pipe;
             const long long cap = std::max<long long>(2, std::min(by_total, by_free));
@@ -920,12 +520,12 @@ int add_pipes(fnn_engine *e, int want, int *np) {
 // from the host is waited for tile by tile under each batch (HostUpload::need).
 int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const fnn_opts &o,
                 const std::vector<int64_t> &ids, const int *ids_origins_dev, const Target &t, hipStream_t st) {
-    const fnn_arch_desc &a = e->arch;
+    const fnn_arch_desc &a = e->plan.arch;
     const AccBox *ab = std::get_if<AccBox>(&t);
     const FeatSlots *fs = std::get_if<FeatSlots>(&t);
     const long long vdim[3] = {(long long)vp.padded[0], (long long)vp.padded[1], (long long)vp.padded[2]};
-    int B = o.batch > 0 ? o.batch : e->max_batch;
-    if (B > e->max_batch) B = e->max_batch;
+    int B = o.batch > 0 ? o.batch : e->plan.max_batch;
+    if (B > e->plan.max_batch) B = e->plan.max_batch;
     const auto combos = mirror_combos(o);
     const bool tta = !combos.empty();
     const size_t P = (size_t)a.patch[0] * a.patch[1] * a.patch[2];
@@ -942,7 +542,7 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
             if (oo[d] < ab->box.lo[d] || oo[d] + a.patch[d] > ab->box.hi[d])
                 return fail(e, FNN_E_INVALID, "patch %lld lies outside the accumulator box", (long long)ids[i]);
     }
-    const size_t featC = fs ? (size_t)e->layers[e->head_src].cout_pad : 0;
+    const size_t featC = fs ? (size_t)e->plan.layers[e->plan.head_src].cout_pad : 0;
     static const bool no_pipe = fnn_knob("FNN_NO_PIPELINE") != nullptr;                // A-B aid
     static const int want_pipes = fnn_knob("FNN_PIPES") ? atoi(fnn_knob("FNN_PIPES")) : 4;   // round 6: four beat three by 0.3-0.9 % on C1 / C2 / C4 / C5 (profiles/r06_pipes_sweep.txt); beyond four: nothing
     const bool pipelined = !no_pipe && (!tta || fs) && !e->profiling && np > B;
@@ -1002,7 +602,7 @@ int run_patches(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp
                 h.flip_d = flip[0]; h.flip_h = flip[1]; h.flip_w = flip[2];
                 h.fx = first_visit(oo, 0); h.fy = first_visit(oo, 1); h.fz = first_visit(oo, 2);
                 if (tta) { h.mode = ci == 0 ? 1 : 2; h.patch_buf = e->patch_buf.as<float>() + (size_t)b * a.num_heads * P; }
-                Scope sc(e, bst, FAM_HEAD, e->head_flops);
+                Scope sc(e, bst, FAM_HEAD, e->plan.head_flops);
                 if (launch_head(h, bst) != 0) return fail(e, FNN_E_HIP, "seg head launch failed");
             }
             if (pipelined) HIPCHK(e, hipEventRecord(e->pipe[k].head, bst));
@@ -1077,20 +677,20 @@ FinalizeParams make_finalize(fnn_engine *e, const void *acc, const Box &box, con
     FinalizeParams f{};
     f.acc = acc;
     f.AX = box.hi[0] - box.lo[0]; f.Y = box.hi[1] - box.lo[1]; f.Z = box.hi[2] - box.lo[2];
-    f.HP = acc_hp(e->arch);
+    f.HP = acc_hp(e->plan.arch);
     f.lo_x = (int)(out_lo[0] + vp.lo[0] - box.lo[0]); f.lo_y = (int)(out_lo[1] + vp.lo[1] - box.lo[1]);
     f.lo_z = (int)(out_lo[2] + vp.lo[2] - box.lo[2]);
     f.OX = out_hi[0] - out_lo[0]; f.OY = out_hi[1] - out_lo[1]; f.OZ = out_hi[2] - out_lo[2];
     f.out_X = shape[1]; f.out_Y = shape[2]; f.out_Z = shape[3];
     f.out_x = out_lo[0]; f.out_y = out_lo[1]; f.out_z = out_lo[2];
-    f.heads = e->arch.num_heads; f.acc_fp32 = acc_fp32; f.out_fp32 = o.out_dtype == FNN_OUT_F32;
+    f.heads = e->plan.arch.num_heads; f.acc_fp32 = acc_fp32; f.out_fp32 = o.out_dtype == FNN_OUT_F32;
     f.mode = mode; f.out = out; f.inf_flag = e->inf_flag.as<int>();
     return f;
 }
 
 int accumulate_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const fnn_opts &o,
                             Box &box, hipStream_t st) {
-    const fnn_arch_desc &a = e->arch;
+    const fnn_arch_desc &a = e->plan.arch;
     const int acc_fp32 = o.accum == FNN_ACC_FP32;
     const size_t esz = acc_fp32 ? 4 : 2;
     const size_t nvox = (size_t)vp.padded[0] * vp.padded[1] * vp.padded[2];
@@ -1127,11 +727,11 @@ void gather_set_tables(GatherParams &g, const int *dev, const int off[3]) {
 // The gather kernel's parameters that follow from the engine, the fold, the volume's plan and shape, and the options.
 // Its callers add the feature buffers with their slots or ring, the tables, the output box and what is written.
 GatherParams gather_params(const fnn_engine *e, int fold, const VolPlan &vp, const int64_t shape[4], const fnn_opts &o) {
-    const fnn_arch_desc &a = e->arch;
-    const Layer &H = e->layers[e->head_src];
+    const fnn_arch_desc &a = e->plan.arch;
+    const Layer &H = e->plan.layers[e->plan.head_src];
     const FoldWeights &fw = e->folds[fold];
     GatherParams g{};
-    g.heads = a.num_heads; g.hblocks = e->hblocks; g.C = H.cout_pad; g.slope = H.act ? a.slope : 1.f;
+    g.heads = a.num_heads; g.hblocks = e->plan.hblocks; g.C = H.cout_pad; g.slope = H.act ? a.slope : 1.f;
     g.PD = a.patch[0]; g.PH = a.patch[1]; g.PW = a.patch[2];
     g.nx = (int)vp.steps[0].size(); g.ny = (int)vp.steps[1].size(); g.nz = (int)vp.steps[2].size();
     { int off[3]; g.windowed = gather_tables(a, vp, nullptr, off) ? 1 : 0; }
@@ -1139,8 +739,8 @@ GatherParams gather_params(const fnn_engine *e, int fold, const VolPlan &vp, con
     g.n_eval = 1 + (int)combos.size();
     for (size_t ci = 0; ci < combos.size() && ci + 1 < 8; ++ci)    // (flipmask[0] = 0: the plain evaluation)
         for (int ax : combos[ci]) g.flipmask[ci + 1] |= 1 << ax;
-    g.wpk = fw.wpk.as<f16>() + e->head_w_off; g.bias = fw.fparam.as<float>() + e->head_bias_off;
-    g.n_pass = e->n_gpass; g.pass_wpk = fw.wpk.as<f16>() + e->gpass_w_off; g.pass_bias = fw.fparam.as<float>() + e->gpass_bias_off;
+    g.wpk = fw.wpk.as<f16>() + e->plan.head_w_off; g.bias = fw.fparam.as<float>() + e->plan.head_bias_off;
+    g.n_pass = e->plan.n_gpass; g.pass_wpk = fw.wpk.as<f16>() + e->plan.gpass_w_off; g.pass_bias = fw.fparam.as<float>() + e->plan.gpass_bias_off;
     g.gauss = (o.use_gaussian ? e->gauss : e->ones).as<f16>();
     g.lo_x = (int)vp.lo[0]; g.lo_y = (int)vp.lo[1]; g.lo_z = (int)vp.lo[2];
     g.OX = shape[1]; g.OY = shape[2]; g.OZ = shape[3];
@@ -1159,11 +759,11 @@ GatherPlan gather_plan(fnn_engine *e, int fold, const VolPlan &vp, const int64_t
     GatherPlan gp;
     gp.why = "FNN_NO_GATHER is set or the output is not fp16";
     if (!e->gather_enabled || o.out_dtype != FNN_OUT_F16) return gp;
-    const Layer &H = e->layers[e->head_src];
+    const Layer &H = e->plan.layers[e->plan.head_src];
     const GatherParams g = gather_params(e, fold, vp, shape, o);
     gp.n_eval = g.n_eval;
     gp.why = "the network's head does not fit the gather kernel (a normalised last layer of <= 32 channels, <= 8 evaluations per patch, <= 64 tiles of one axis over a voxel)";
-    if (!H.has_norm || e->head_ksteps != 1 || !gather_ok(g)) return gp;
+    if (!H.has_norm || e->plan.head_ksteps != 1 || !gather_ok(g)) return gp;
     gp.why = "not enough free HBM for the patch activations that cover one output slab";
     const auto &sx = vp.steps[0];
     const int nx = (int)sx.size();
@@ -1192,7 +792,7 @@ GatherPlan gather_plan(fnn_engine *e, int fold, const VolPlan &vp, const int64_t
 
 int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const VolPlan &vp, const int64_t shape[4],
                         const fnn_opts &o, const GatherPlan &gp, int mode, void *out, void *labels, hipStream_t st) {
-    const Layer &H = e->layers[e->head_src];
+    const Layer &H = e->plan.layers[e->plan.head_src];
     if (gp.feat_bytes > e->feat.bytes) e->acc.free();
     HIPCHK(e, e->feat.reserve(gp.feat_bytes));
     const int64_t n_slots = (int64_t)gp.layer_items * gp.ring;
@@ -1200,7 +800,7 @@ int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const Vol
     HIPCHK(e, e->featssh.reserve((size_t)n_slots * gp.n_eval * 2 * H.cout_pad * sizeof(f16)));
     std::vector<int> steps;
     int win_off[3];
-    if (!gather_tables(e->arch, vp, &steps, win_off)) return fail(e, FNN_E_UNSUPPORTED, "more than 64 tiles of one axis over a voxel");
+    if (!gather_tables(e->plan.arch, vp, &steps, win_off)) return fail(e, FNN_E_UNSUPPORTED, "more than 64 tiles of one axis over a voxel");
     HIPCHK(e, e->steps.upload(steps.data(), steps.size(), st));
     GatherParams g = gather_params(e, fold, vp, shape, o);
     g.feat = e->feat.as<f16>(); g.fss = e->featss.as<float>(); g.fssh = e->featssh.as<unsigned short>();
@@ -1211,7 +811,7 @@ int gather_whole_volume(fnn_engine *e, int fold, const float *vol_dev, const Vol
     g.mode = mode; g.out = out; g.labels = labels;
     auto launch = [&](int x_lo, int x_hi, double n_patches) {
         g.x_lo = x_lo; g.x_hi = x_hi;
-        Scope sc(e, st, FAM_HEAD, e->head_flops * n_patches * gp.n_eval);
+        Scope sc(e, st, FAM_HEAD, e->plan.head_flops * n_patches * gp.n_eval);
         return launch_gather(g, st) == 0 ? 0 : fail(e, FNN_E_HIP, "gather launch failed");
     };
     const FeatSlots slots{e->feat.p, e->featss.as<float>(), e->featssh.as<unsigned short>(), 0, n_slots};
@@ -1238,7 +838,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     for (int f = fold0; f < fold0 + n_folds; ++f)
         if (int rc = check_ready(e, f, o)) return rc;
     if (!vol || (!out && !labels) || !shape) return fail(e, FNN_E_INVALID, "NULL argument");
-    const fnn_arch_desc &a = e->arch;
+    const fnn_arch_desc &a = e->plan.arch;
     if (shape[0] != a.in_channels) return fail(e, FNN_E_INVALID, "input has %lld channels, the network expects %d", (long long)shape[0], a.in_channels);
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)o->stream;
@@ -1260,7 +860,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     // come from materialised logits, the label map of a host caller - come out of its budget)
     size_t pending = 0;
     {
-        const bool maybe_direct = labels && !want_logits && n_folds == 1 && e->n_gpass == 1;
+        const bool maybe_direct = labels && !want_logits && n_folds == 1 && e->plan.n_gpass == 1;
         if (!maybe_direct && !out_on_dev && nout * osz > e->out_tmp.bytes) pending += nout * osz - e->out_tmp.bytes;
         if (labels && !lab_on_dev) pending += lab_bytes;
     }
@@ -1271,7 +871,7 @@ int predict_impl(fnn_engine *e, int fold0, int n_folds, const float *vol, const 
     // runs in passes over the heads, so the labels come from its logits
     // (accumulate path: labels_from_acc_coop_kernel covers up to 32 lanes of 8 channels per voxel - 254 classes; beyond, the
     // labels come from the logits like an ensemble's)
-    const bool labels_direct = labels && !want_logits && n_folds == 1 && !(gp.ok && e->n_gpass > 1) && (gp.ok || acc_hp(a) <= 256);
+    const bool labels_direct = labels && !want_logits && n_folds == 1 && !(gp.ok && e->plan.n_gpass > 1) && (gp.ok || acc_hp(a) <= 256);
     void *out_dev = out;
     if (!labels_direct && !out_on_dev) {
         HIPCHK(e, e->out_tmp.reserve(nout * osz));
@@ -1349,9 +949,9 @@ int finalize_box(fnn_engine *e, const char *who, const void *acc, const int64_t 
     void *dst = out ? out : labels;
     if (!acc || !dst || !box_lo || !box_hi || !out_lo || !out_hi) return fail(e, FNN_E_INVALID, "NULL argument");
     if (!fnn_dev_ptr(acc) || !fnn_dev_ptr(dst)) return fail(e, FNN_E_INVALID, "%s needs device pointers", who);
-    if (labels && acc_hp(e->arch) > 256)
-        return fail(e, FNN_E_UNSUPPORTED, "fnn_labels_box serves up to 254 classes (%d here): take the logits (fnn_normalize_box) and fnn_argmax_labels", e->arch.num_heads);
-    if (labels) if (int rc = check_u8_labels(e, e->arch.num_heads, U16_HINT)) return rc;
+    if (labels && acc_hp(e->plan.arch) > 256)
+        return fail(e, FNN_E_UNSUPPORTED, "fnn_labels_box serves up to 254 classes (%d here): take the logits (fnn_normalize_box) and fnn_argmax_labels", e->plan.arch.num_heads);
+    if (labels) if (int rc = check_u8_labels(e, e->plan.arch.num_heads, U16_HINT)) return rc;
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)opts->stream;
     VolPlan vp;
@@ -1378,38 +978,41 @@ int fnn_abi_version(void) { return FNN_ABI_VERSION; }
 
 const char *fnn_last_error(const fnn_engine *e) { return e ? e->err.c_str() : g_err.c_str(); }
 
-// up to 64 patches per forward, or - small patches (a 40 x 56 x 40 plan, a 2-D slice) - as many as give a forward 2^27 voxels
-// (64 patches of 128^3), at most 512: the deep layers of a small patch have too few voxels per item to fill the chip
-static int check_max_batch(const fnn_arch_desc *arch, int max_batch) {
-    const long long pv = (long long)arch->patch[0] * arch->patch[1] * arch->patch[2];
-    const long long cap = pv > 0 ? std::max<long long>(64, std::min<long long>(512, (1ll << 27) / pv)) : 64;
-    if (max_batch < 1 || max_batch > cap) return fail(nullptr, FNN_E_INVALID, "max_batch must be 1..%lld for this patch size", cap);
-    return 0;
+// The layer plan (layer_plan.h: host only, no HIP call) under the switches the environment holds now; a refusal is
+// the call's error
+static int make_plan(const fnn_arch_desc *arch, int max_batch, LayerPlan &plan) {
+    std::string err;
+    const int rc = plan_layers(*arch, max_batch, PlanSwitches::from_env(), plan, err);
+    return rc ? fail(nullptr, rc, "%s", err.c_str()) : 0;
 }
 
-// the engine's switches (read when it is created) and its layer plan; no HIP call
-static int plan_engine(fnn_engine *e, const fnn_arch_desc *arch, int max_batch) {
-    e->arch = *arch; e->max_batch = max_batch;
-    e->fuse_enabled = fnn_knob("FNN_NO_FUSE") == nullptr;
-    if (const char *v = fnn_knob("FNN_FUSE_STEM")) e->fuse_stem = atoi(v) != 0 ? 1 : 0;
-    e->ov = ConvOverrides::from_env();
-    e->gather_enabled = fnn_knob("FNN_NO_GATHER") == nullptr;
-    if (e->arch.eps <= 0) e->arch.eps = 1e-5f;
-    const int rc = build_plan(e);
-    if (rc != 0) g_err = e->err;
-    return rc;
+// text -> the caller's buffer (cut to cap - 1 characters, 0-terminated); returns the size that holds all of it
+static int64_t copy_text(const std::string &all, char *buf, int64_t cap) {
+    if (buf && cap > 0) {
+        const size_t n = std::min((size_t)cap - 1, all.size());
+        memcpy(buf, all.data(), n);
+        buf[n] = 0;
+    }
+    return (int64_t)all.size() + 1;
+}
+static std::string lines(const std::vector<std::string> &rows) {
+    std::string all;
+    for (const std::string &r : rows) { all += r; all += '\n'; }
+    return all;
 }
 
+// The plan is made before a device is looked for: a descriptor or batch size that cannot be planned is refused as such
 int fnn_create(const fnn_arch_desc *arch, int device, int max_batch, fnn_engine **out) {
     if (!arch || !out) return fail(nullptr, FNN_E_INVALID, "NULL argument");
-    if (int rc = check_max_batch(arch, max_batch)) return rc;
+    LayerPlan plan;
+    if (int rc = make_plan(arch, max_batch, plan)) return rc;
+    std::unique_ptr<fnn_engine> e(new fnn_engine(std::move(plan)));
+    e->gather_enabled = fnn_knob("FNN_NO_GATHER") == nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(nullptr, FNN_E_HIP, "no HIP device is available: the MI355X engine has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(nullptr, FNN_E_INVALID, "device %d out of range (%d visible)", device, ndev);
-    std::unique_ptr<fnn_engine> e(new fnn_engine());
     e->device = device;
-    if (int rc = plan_engine(e.get(), arch, max_batch)) return rc;
     HIPCHK(nullptr, hipSetDevice(device));
     if (int rc = arena_alloc(e.get(), e->pipe[0].arena)) return rc;
     HIPCHK(nullptr, e->inf_flag.reserve(sizeof(int)));
@@ -1432,50 +1035,19 @@ void fnn_destroy(fnn_engine *e) {
     delete e;
 }
 
-int64_t fnn_weight_count(const fnn_engine *e) { return e ? e->blob_count : -1; }
+int64_t fnn_weight_count(const fnn_engine *e) { return e ? e->plan.blob_count : -1; }
 
 int fnn_load_weights(fnn_engine *e, int fold, const float *blob, int64_t count) {
     if (!e) return FNN_E_INVALID;
     if (!blob) return fail(e, FNN_E_INVALID, "NULL blob");
-    if (count != e->blob_count) return fail(e, FNN_E_INVALID, "weight blob has %lld values, expected %lld", (long long)count, (long long)e->blob_count);
+    if (count != e->plan.blob_count) return fail(e, FNN_E_INVALID, "weight blob has %lld values, expected %lld", (long long)count, (long long)e->plan.blob_count);
     if (fold < 0 || fold >= 64) return fail(e, FNN_E_INVALID, "fold index out of range");
     HIPCHK(e, hipSetDevice(e->device));
     if ((int)e->folds.size() <= fold) e->folds.resize(fold + 1);
     FoldWeights &fw = e->folds[fold];
-    std::vector<uint16_t> wpk(e->wpk_halves, 0);
-    std::vector<float> fp(e->fparam_floats, 0.f);
-    for (const Layer &L : e->layers) {
-        if (L.type == Layer::POOL || L.type == Layer::COMBINE || L.type == Layer::GATHER) continue;
-        const float *W = blob + L.blob_w;
-        if (L.type == Layer::STEM) {
-            const int T = L.k[0] * L.k[1] * L.k[2], C = L.cin_real[0];
-            for (int c = 0; c < C; ++c)
-                for (int t = 0; t < T; ++t)
-                    for (int co = 0; co < L.cout_real; ++co)
-                        fp[L.w_off + ((size_t)c * T + t) * L.cout_pad + co] = W[((size_t)co * C + c) * T + t];
-            if (L.mfma_stem) stem_mfma_pack(W, C, T, L.cout_real, L.cout_pad, wpk.data() + L.w_off2);
-        } else if (L.type == Layer::CONV) {
-            conv_pack_weights(conv_shape(e, L).c, L.cc, L.cout_real, L.cin_real, W, wpk.data() + L.w_off,
-                              L.fp8 ? fp.data() + L.oscale_off : nullptr);
-        } else {
-            tconv_pack_weights(W, L.cin_real[0], L.cout_real, L.cout_pad, L.s[0] * L.s[1] * L.s[2], L.ksteps, wpk.data() + L.w_off);
-        }
-        for (int c = 0; c < L.cout_real; ++c) {
-            // A conv bias in front of an InstanceNorm cancels exactly (the norm removes the channel mean), so it is
-            // dropped: the raw conv outputs are stored in fp16, and a large bias would only cost them resolution
-            // (|bias| = 10 in front of a unit-variance channel: 2^-7 instead of 2^-11 of sigma).
-            fp[L.bias_off + c] = (L.has_bias && !L.has_norm) ? blob[L.blob_b + c] : 0.f;
-            if (L.has_norm) { fp[L.gamma_off + c] = blob[L.blob_g + c]; fp[L.beta_off + c] = blob[L.blob_beta + c]; }
-        }
-    }
-    pack_head(e->arch.num_heads, e->arch.features[0], e->hblocks, e->head_ksteps, blob + e->blob_head_w, wpk.data() + e->head_w_off);
-    pack_head_bias(e->arch.num_heads, e->hblocks, blob + e->blob_head_b, fp.data() + e->head_bias_off);
-    for (int k = 0; k < (e->n_gpass > 1 ? e->n_gpass : 0); ++k) {      // gather passes: heads 63 k .. + cnt - 1, then the weight-sum row
-        const int h0 = 63 * k, cnt = std::min(63, e->arch.num_heads - h0), cin = e->arch.features[0];
-        pack_head(cnt, cin, 4, 1, blob + e->blob_head_w + (size_t)h0 * cin, wpk.data() + e->gpass_w_off + (size_t)k * 4 * 512);
-        for (int h = 0; h < cnt; ++h) fp[e->gpass_bias_off + (size_t)k * 64 + h] = blob[e->blob_head_b + h0 + h];
-        fp[e->gpass_bias_off + (size_t)k * 64 + cnt] = 1.f;
-    }
+    std::vector<uint16_t> wpk;
+    std::vector<float> fp;
+    pack_fold_weights(e->plan, blob, wpk, fp);
     HIPCHK(e, fw.wpk.reserve(fnn_weight_alloc_bytes(wpk.size())));
     HIPCHK(e, fw.fparam.reserve(fp.size() * 4));
     HIPCHK(e, hipMemcpy(fw.wpk.p, wpk.data(), wpk.size() * 2, hipMemcpyHostToDevice));
@@ -1486,7 +1058,7 @@ int fnn_load_weights(fnn_engine *e, int fold, const float *blob, int64_t count) 
 
 int fnn_set_gaussian(fnn_engine *e, const uint16_t *half_bits, int64_t count) {
     if (!e) return FNN_E_INVALID;
-    const int64_t P = (int64_t)e->arch.patch[0] * e->arch.patch[1] * e->arch.patch[2];
+    const int64_t P = (int64_t)e->plan.arch.patch[0] * e->plan.arch.patch[1] * e->plan.arch.patch[2];
     if (!half_bits || count != P) return fail(e, FNN_E_INVALID, "gaussian must have %lld values", (long long)P);
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, e->gauss.reserve(P * 2));
@@ -1512,7 +1084,7 @@ int fnn_predict_labels(fnn_engine *e, int n_folds, const float *vol, const int64
     return predict_impl(e, 0, n_folds, vol, shape, opts, nullptr, labels);
 }
 
-int64_t fnn_accumulator_channels(const fnn_engine *e) { return e ? acc_hp(e->arch) : -1; }
+int64_t fnn_accumulator_channels(const fnn_engine *e) { return e ? acc_hp(e->plan.arch) : -1; }
 
 int fnn_accumulate_patches(fnn_engine *e, int fold, const float *vol, const int64_t shape[4], const fnn_opts *opts,
                            const int64_t *patch_ids, int64_t n_ids, const int64_t box_lo[3], const int64_t box_hi[3],
@@ -1544,7 +1116,7 @@ int fnn_labels_box(fnn_engine *e, const void *acc, const int64_t shape[4], const
     return finalize_box(e, "fnn_labels_box", acc, shape, opts, box_lo, box_hi, out_lo, out_hi, nullptr, labels);
 }
 
-int64_t fnn_feature_channels(const fnn_engine *e) { return e ? e->layers[e->head_src].cout_pad : -1; }
+int64_t fnn_feature_channels(const fnn_engine *e) { return e ? e->plan.layers[e->plan.head_src].cout_pad : -1; }
 
 int fnn_patch_features(fnn_engine *e, int fold, const float *vol, const int64_t shape[4], const fnn_opts *opts,
                        const int64_t *patch_ids, int64_t n_ids, void *feat, float *fss, int64_t slot0, int64_t n_slots) {
@@ -1553,7 +1125,7 @@ int fnn_patch_features(fnn_engine *e, int fold, const float *vol, const int64_t 
     if (!fnn_dev_ptr(feat) || !fnn_dev_ptr(fss)) return fail(e, FNN_E_INVALID, "feature buffers must be device memory");
     if (slot0 < 0 || n_slots < slot0 + n_ids) return fail(e, FNN_E_INVALID, "slots [%lld, %lld) do not fit %lld slots", (long long)slot0, (long long)(slot0 + n_ids), (long long)n_slots);
     if (1 + (int)mirror_combos(*opts).size() > 8) return fail(e, FNN_E_UNSUPPORTED, "more than 8 evaluations per patch");
-    if (!e->layers[e->head_src].has_norm) return fail(e, FNN_E_UNSUPPORTED, "the network's last layer has no InstanceNorm");
+    if (!e->plan.layers[e->plan.head_src].has_norm) return fail(e, FNN_E_UNSUPPORTED, "the network's last layer has no InstanceNorm");
     HIPCHK(e, hipSetDevice(e->device));
     VolPlan vp;
     if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
@@ -1573,15 +1145,15 @@ int fnn_gather_box(fnn_engine *e, int fold, const void *feat, const float *fss, 
     VolPlan vp;
     if (int rc = plan_volume(e, shape, *opts, vp)) return rc;
     if (int rc = check_out_box(e, vp, shape, out_lo, out_hi, nullptr)) return rc;
-    const Layer &H = e->layers[e->head_src];
+    const Layer &H = e->plan.layers[e->plan.head_src];
     GatherParams g = gather_params(e, fold, vp, shape, *opts);
     std::vector<int> tab;
     int win_off[3];
-    (void)gather_tables(e->arch, vp, &tab, win_off);          // (g.windowed: whether it could)
+    (void)gather_tables(e->plan.arch, vp, &tab, win_off);          // (g.windowed: whether it could)
     // (labels of more than 256 classes end here too: the uint8 limit needs no check of its own)
-    if (labels && e->n_gpass > 1)
-        return fail(e, FNN_E_UNSUPPORTED, "fnn_gather_box writes labels for <= 63 classes; with %d take the logits and fnn_argmax_labels", e->arch.num_heads);
-    if (!H.has_norm || e->head_ksteps != 1 || !gather_ok(g)) return fail(e, FNN_E_UNSUPPORTED, "this network's head does not fit the gather kernel");
+    if (labels && e->plan.n_gpass > 1)
+        return fail(e, FNN_E_UNSUPPORTED, "fnn_gather_box writes labels for <= 63 classes; with %d take the logits and fnn_argmax_labels", e->plan.arch.num_heads);
+    if (!H.has_norm || e->plan.head_ksteps != 1 || !gather_ok(g)) return fail(e, FNN_E_UNSUPPORTED, "this network's head does not fit the gather kernel");
     for (int64_t i = 0; i < vp.n_patches; ++i)
         if (slot_of_patch[i] >= n_slots) return fail(e, FNN_E_INVALID, "slot %d of patch %lld is beyond the %lld slots", slot_of_patch[i], (long long)i, (long long)n_slots);
     // tile starts (+ window bases), then the slot table, in one device buffer
@@ -1625,9 +1197,9 @@ static int region_copy(fnn_engine *e, void *feat, int64_t n_slots, const fnn_reg
     if (n > 65535) return fail(e, FNN_E_INVALID, "more than 65535 regions in one message");
     static_assert(sizeof(fnn_region) == 40, "fnn_region is ten 32-bit words");
     HIPCHK(e, hipSetDevice(e->device));
-    const fnn_arch_desc &a = e->arch;
+    const fnn_arch_desc &a = e->plan.arch;
     if (launch_region_copy(feat, n_slots, (const int *)regions, (int)n, message, a.patch[0], a.patch[1], a.patch[2],
-                           e->layers[e->head_src].cout_pad, pack, (hipStream_t)stream) != 0)
+                           e->plan.layers[e->plan.head_src].cout_pad, pack, (hipStream_t)stream) != 0)
         return fail(e, FNN_E_HIP, "region copy launch failed");
     return 0;
 }
@@ -1646,7 +1218,7 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
     if (!x || !logits || n < 1) return fail(e, FNN_E_INVALID, "bad argument");
     HIPCHK(e, hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
-    const fnn_arch_desc &a = e->arch;
+    const fnn_arch_desc &a = e->plan.arch;
     const size_t P = (size_t)a.patch[0] * a.patch[1] * a.patch[2];
     const size_t nin = (size_t)n * a.in_channels * P, nout = (size_t)n * a.num_heads * P;
     const float *xd = x;
@@ -1661,21 +1233,21 @@ int fnn_forward_patches(fnn_engine *e, int fold, const float *x, int n, float *l
         HIPCHK(e, e->out_tmp.reserve(nout * 4));
         od = e->out_tmp.as<float>();
     }
-    std::vector<int> zeros((size_t)e->max_batch * 3, 0);
+    std::vector<int> zeros((size_t)e->plan.max_batch * 3, 0);
     HIPCHK(e, e->origins.upload(zeros.data(), zeros.size(), st));
     HIPCHK(e, hipStreamSynchronize(st));
     const long long vdim[3] = {a.patch[0], a.patch[1], a.patch[2]};
     const int flip[3] = {0, 0, 0};
     e->ev_used = 0; e->klog.clear();
-    for (int p0 = 0; p0 < n; p0 += e->max_batch) {
-        const int nb = (n - p0 < e->max_batch) ? n - p0 : e->max_batch;
+    for (int p0 = 0; p0 < n; p0 += e->plan.max_batch) {
+        const int nb = (n - p0 < e->plan.max_batch) ? n - p0 : e->plan.max_batch;
         if (int rc = forward_batch(e, fold, e->pipe[0].arena, xd + (size_t)p0 * a.in_channels * P, (long long)(a.in_channels * P), vdim,
                                    e->origins.data(), nb, flip, st)) return rc;
         for (int b = 0; b < nb; ++b) {
             HeadParams h = make_head(e, e->pipe[0].arena, fold, b);
             h.mode = 1; h.patch_buf = od + (size_t)(p0 + b) * a.num_heads * P;
             h.acc_fp32 = 1;
-            Scope sc(e, st, FAM_HEAD, e->head_flops);
+            Scope sc(e, st, FAM_HEAD, e->plan.head_flops);
             if (launch_head(h, st) != 0) return fail(e, FNN_E_HIP, "seg head launch failed");
         }
     }
@@ -1690,14 +1262,14 @@ int fnn_set_label_rule(fnn_engine *e, int mode, const int32_t *regions_class_ord
     if ((mode != FNN_LABELS_ARGMAX && mode != FNN_LABELS_REGIONS) || (label_dtype != FNN_LABEL_U8 && label_dtype != FNN_LABEL_U16))
         return fail(e, FNN_E_INVALID, "unknown label mode / dtype");
     if (mode == FNN_LABELS_REGIONS) {
-        if (!regions_class_order || n_regions != e->arch.num_heads)
-            return fail(e, FNN_E_INVALID, "regions_class_order needs one entry per segmentation head (%d), got %d", e->arch.num_heads, n_regions);
+        if (!regions_class_order || n_regions != e->plan.arch.num_heads)
+            return fail(e, FNN_E_INVALID, "regions_class_order needs one entry per segmentation head (%d), got %d", e->plan.arch.num_heads, n_regions);
         const int limit = label_dtype == FNN_LABEL_U16 ? 65535 : 255;
         for (int i = 0; i < n_regions; ++i)
             if (regions_class_order[i] < 0 || regions_class_order[i] > limit)
                 return fail(e, FNN_E_INVALID, "regions_class_order[%d] = %d does not fit the label dtype", i, regions_class_order[i]);
         HIPCHK(e, hipSetDevice(e->device));
-        HIPCHK(e, e->label_order.reserve(sizeof(int) * (size_t)e->arch.num_heads));
+        HIPCHK(e, e->label_order.reserve(sizeof(int) * (size_t)e->plan.arch.num_heads));
         HIPCHK(e, hipMemcpy(e->label_order.p, regions_class_order, sizeof(int) * (size_t)n_regions, hipMemcpyHostToDevice));
     }
     e->label_mode = mode;
@@ -1709,7 +1281,7 @@ int fnn_argmax_labels(fnn_engine *e, const void *logits, int dtype, int heads, i
     if (!e) return FNN_E_INVALID;
     if (!logits || !labels || heads < 1) return fail(e, FNN_E_INVALID, "bad argument");
     const bool regions = e->label_mode == FNN_LABELS_REGIONS;
-    if (regions && heads != e->arch.num_heads) return fail(e, FNN_E_INVALID, "the region rule was set for %d heads, got %d", e->arch.num_heads, heads);
+    if (regions && heads != e->plan.arch.num_heads) return fail(e, FNN_E_INVALID, "the region rule was set for %d heads, got %d", e->plan.arch.num_heads, heads);
     if (int rc = check_u8_labels(e, heads, "")) return rc;
     if (!fnn_dev_ptr(logits) || !fnn_dev_ptr(labels)) return fail(e, FNN_E_INVALID, "fnn_argmax_labels needs device pointers");
     HIPCHK(e, hipSetDevice(e->device));
@@ -1753,63 +1325,23 @@ int fnn_set_profiling(fnn_engine *e, int enabled) { if (!e) return FNN_E_INVALID
 
 int fnn_get_profile(const fnn_engine *e, fnn_profile *out) { if (!e || !out) return FNN_E_INVALID; *out = e->prof; return 0; }
 
-int64_t fnn_kernel_log(const fnn_engine *e, char *buf, int64_t cap) {
-    if (!e) return FNN_E_INVALID;
-    std::string all;
-    for (const std::string &k : e->klog) { all += k; all += '\n'; }
-    if (buf && cap > 0) {
-        const size_t n = std::min((size_t)cap - 1, all.size());
-        memcpy(buf, all.data(), n);
-        buf[n] = 0;
-    }
-    return (int64_t)all.size() + 1;
-}
+int64_t fnn_kernel_log(const fnn_engine *e, char *buf, int64_t cap) { return e ? copy_text(lines(e->klog), buf, cap) : FNN_E_INVALID; }
 
-int64_t fnn_profile_launches(const fnn_engine *e, char *buf, int64_t cap) {
-    if (!e) return FNN_E_INVALID;
-    std::string all;
-    for (const std::string &k : e->launch_rows) { all += k; all += '\n'; }
-    if (buf && cap > 0) {
-        const size_t n = std::min((size_t)cap - 1, all.size());
-        memcpy(buf, all.data(), n);
-        buf[n] = 0;
-    }
-    return (int64_t)all.size() + 1;
-}
+int64_t fnn_profile_launches(const fnn_engine *e, char *buf, int64_t cap) { return e ? copy_text(lines(e->launch_rows), buf, cap) : FNN_E_INVALID; }
 
-int64_t fnn_layer_table(const fnn_engine *e, char *buf, int64_t cap) {
-    if (!e) return FNN_E_INVALID;
-    static const char *const ty[] = {"stem", "conv", "tconv", "pool", "combine", "input"};
-    std::string all;
-    for (size_t li = 0; li < e->layers.size(); ++li) {
-        const Layer &L = e->layers[li];
-        char row[320];
-        snprintf(row, sizeof row, "%zu\t%s\t%d\t%d\t%dx%dx%d\t%dx%dx%d\t%dx%dx%d\t%dx%dx%d\t%.6g\t%.6g\t%d\t%s\n", li, ty[L.type],
-                 L.cin_real[0] + (L.n_src > 1 ? L.cin_real[1] : 0), L.cout_real, L.k[0], L.k[1], L.k[2], L.s[0], L.s[1], L.s[2],
-                 L.in_dims[0], L.in_dims[1], L.in_dims[2], L.out_dims[0], L.out_dims[1], L.out_dims[2], L.flops, L.bytes,
-                 L.virtual_out ? 1 : (L.fuse ? 2 : 0), L.type == Layer::CONV ? L.cc.name : "-");
-        all += row;
-    }
-    if (buf && cap > 0) {
-        const size_t n = std::min((size_t)cap - 1, all.size());
-        memcpy(buf, all.data(), n);
-        buf[n] = 0;
-    }
-    return (int64_t)all.size() + 1;
-}
+int64_t fnn_layer_table(const fnn_engine *e, char *buf, int64_t cap) { return e ? copy_text(layer_table_text(e->plan), buf, cap) : FNN_E_INVALID; }
 
 int64_t fnn_plan_table(const fnn_arch_desc *arch, int max_batch, char *buf, int64_t cap) {
     if (!arch) return fail(nullptr, FNN_E_INVALID, "NULL argument");
-    if (int rc = check_max_batch(arch, max_batch)) return rc;
-    fnn_engine e;
-    if (int rc = plan_engine(&e, arch, max_batch)) return rc;
-    return fnn_layer_table(&e, buf, cap);
+    LayerPlan plan;
+    if (int rc = make_plan(arch, max_batch, plan)) return rc;
+    return copy_text(layer_table_text(plan), buf, cap);
 }
 
 int fnn_patch_work(const fnn_engine *e, double *flops, double *act_bytes) {
     if (!e) return FNN_E_INVALID;
-    if (flops) *flops = e->patch_flops;
-    if (act_bytes) *act_bytes = e->patch_act_bytes;
+    if (flops) *flops = e->plan.patch_flops;
+    if (act_bytes) *act_bytes = e->plan.patch_act_bytes;
     return 0;
 }
 

@@ -496,7 +496,7 @@ inline size_t fnn_weight_alloc_bytes(size_t halves) { return halves * 2 + 1024; 
 uint8_t f2e4m3(float f);              // OCP e4m3 ("fn"), round to nearest even, saturating at +-448
 inline unsigned short fnn_half_bits(float f) { return __builtin_bit_cast(unsigned short, (f16)f); }
 // transposed conv: W [cin][cout][taps] -> dst [tap][cout block][k-step][64][8] (TconvParams::wpk), ksteps = ceil(cin_pad / 32)
-// seg head (engine.hip): weights [heads][cin] -> MFMA A fragments [hblock][kstep][64][8] (zero rows from `heads` on: the
+// seg head (layer_plan.hip): weights [heads][cin] -> MFMA A fragments [hblock][kstep][64][8] (zero rows from `heads` on: the
 // weight-sum channel and the padding), and the bias row that goes with them ([hblocks * 16], 1 at `heads`)
 void pack_head(int heads, int cin, int hblocks, int ksteps, const float *W, unsigned short *dst);
 void pack_head_bias(int heads, int hblocks, const float *bias, float *dst);

@@ -26,7 +26,8 @@ class _Args:
         self.plan, self.workload, self.volume, self.batch, self.batch_given = plan, workload, 512, 32, False
 
 
-def _plan_rows(name):
+def plan_desc(name):
+    """-> (bench batch, fnn_arch_desc) of a sweep plan or BASELINE workload; tests/test_layer_plan_cpu.py plans the same"""
     plan, (workload, dtype) = PLANS.get(name), WORKLOADS.get(name, (None, 'f16'))
     args = _Args(plan, workload)
     w = bench.resolve_workload(args)
@@ -40,7 +41,12 @@ def _plan_rows(name):
         sd = bench.synthetic_checkpoint(features, kernels, strides, w['in_channels'], w['heads'], seed=1234)
     spec = spec_from_state_dict(sd, w['patch'])
     spec.precision = capi.FNN_PREC_F8 if dtype == 'f8' else capi.FNN_PREC_F16
-    return args.batch, capi.plan_table(spec.to_desc(), args.batch)
+    return args.batch, spec.to_desc()
+
+
+def _plan_rows(name):
+    batch, desc = plan_desc(name)
+    return batch, capi.plan_table(desc, batch)
 
 
 @pytest.mark.parametrize('name', sorted(GOLDEN))
