@@ -78,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_remove_small_components', 'fnn_fill_holes', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -137,6 +137,10 @@ def load_library() -> C.CDLL:
     lib.fnn_resample_torch_seg.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ResampleTorchDesc), vp, vp]
     lib.fnn_resample_labels.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64), i32, i32, vp, i32, vp, i32, vp]
     lib.fnn_keep_largest_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), vp]
+    if hasattr(lib, 'fnn_remove_small_components'):                # (absent from an older build picked with FNN_LIB for an A-B)
+        lib.fnn_remove_small_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), i32,
+                                                    C.POINTER(i64), vp]
+        lib.fnn_fill_holes.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, i32, C.POINTER(i64), vp]
     lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
                                         C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
     lib.fnn_average_probabilities.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(C.c_int32), i64, vp, vp, i32, vp]
@@ -504,6 +508,39 @@ def keep_largest_components(labels_ptr: int, uint16: bool, shape, group_of_label
                                           table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_groups),
                                           int(background_label), removed.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
     return removed[:int(n_groups)]
+
+
+def remove_small_components(labels_ptr: int, uint16: bool, shape, group_of_label, n_groups: int, background_label: int, min_size,
+                            connectivity: int = 26, stream: int = 0):
+    """fnn_remove_small_components on a device label map [X, Y, Z] in place: per set, components below ``min_size[set]``
+    voxels become background; returns the voxels removed per set."""
+    lib = load_library()
+    table = np.ascontiguousarray(group_of_label, dtype=np.int32)
+    sizes = np.ascontiguousarray(min_size, dtype=np.int64)
+    if sizes.shape != (int(n_groups),):
+        raise ValueError('min_size must have one entry per set')
+    sizes = np.concatenate([sizes, np.zeros(1, np.int64)])                  # never an empty buffer
+    removed = np.zeros(max(int(n_groups), 1), np.int64)
+    check(lib.fnn_remove_small_components(labels_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8,
+                                          (C.c_int64 * 3)(*[int(i) for i in shape]),
+                                          table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(n_groups),
+                                          int(background_label), sizes.ctypes.data_as(C.POINTER(C.c_int64)), int(connectivity),
+                                          removed.ctypes.data_as(C.POINTER(C.c_int64)), stream), lib)
+    return removed[:int(n_groups)]
+
+
+def fill_holes(labels_ptr: int, uint16: bool, shape, in_set, background_label: int, fill_label: int, border_axes: int = 7,
+               stream: int = 0) -> int:
+    """fnn_fill_holes on a device label map [X, Y, Z] in place: ``in_set[v]`` is 0 where label value v belongs to the set and
+    -1 where not; background voxels in the set's holes become ``fill_label``.  ``border_axes``: bit a - the faces of axis a
+    are borders (7 for a 3-D map, 6 for a 2-D map carried as [1, Y, Z]).  Returns the number of voxels filled."""
+    lib = load_library()
+    table = np.ascontiguousarray(in_set, dtype=np.int32)
+    filled = C.c_int64(0)
+    check(lib.fnn_fill_holes(labels_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, (C.c_int64 * 3)(*[int(i) for i in shape]),
+                             table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(background_label), int(fill_label),
+                             int(border_axes), C.byref(filled), stream), lib)
+    return int(filled.value)
 
 
 def confusion_counts(ref_ptr: int, pred_ptrs: Sequence[int], uint16: bool, n_vox: int, class_of_value, n_classes: int,

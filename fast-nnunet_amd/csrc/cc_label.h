@@ -1,15 +1,17 @@
-// cc_label.h - label-aware 3-D connected components (26-connectivity) by union-find over int32 voxel indices, gfx950: the
-// labelling that postprocess.hip (fnn_keep_largest_components) and instance.hip (fnn_instance_overlaps) share.
+// cc_label.h - label-aware 3-D connected components (26- or 6-connectivity, a compile-time choice; 26 is the default) by
+// union-find over int32 voxel indices, gfx950: the labelling that postprocess.hip (fnn_keep_largest_components,
+// fnn_remove_small_components, fnn_fill_holes) and instance.hip (fnn_instance_overlaps) share.
 //
 //   1. tile_merge    init + union inside a 1024-voxel tile through LDS; every voxel's global parent is the global
 //                    index of its tile-local root (-1 outside every set);
-//   2. cross_merge   the 13 "backward" neighbours (smaller linear index) that lie outside the voxel's tile, linked
-//                    lock-free: atomicMin(&parent[a], b) with a > b, retried on the returned value (Playne & Hawick);
+//   2. cross_merge   the 13 "backward" neighbours (smaller linear index; with 6-connectivity the 3 backward face
+//                    neighbours) that lie outside the voxel's tile, linked lock-free: atomicMin(&parent[a], b) with
+//                    a > b, retried on the returned value (Playne & Hawick);
 //   3. flatten       parent[i] = root(i);
 //   4. count         size[root] += 1, aggregated per thread run and per wave before the atomic.
 //
-// What a voxel belongs to comes from a loader L: L::group(i, n_table) is the set of voxel i, or -1.  Two 26-neighbours are
-// one component iff their groups are equal and not negative.
+// What a voxel belongs to comes from a loader L: L::group(i, n_table) is the set of voxel i, or -1.  Two neighbours (26 or
+// 6, the template's CONN) are one component iff their groups are equal and not negative.
 //
 // Invariants that make every phase end by construction (no spin on another workgroup's value, no recursion):
 // parent[i] <= i always, and parent[] changes only through atomicMin to a smaller index, so every find walks a
@@ -18,6 +20,9 @@
 // Per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores: inside phases 2 and 3 every
 // read of parent[] is an agent-scope relaxed atomic load (sc1), and every write an agent-scope atomic.  A stale read
 // only costs a retry: the atomicMin's returned value is the truth.
+// None of this depends on which neighbours are linked: CONN = 6 only offers fewer (a, b) pairs to the same local_union /
+// global_union, every backward neighbour still has the smaller index, so parent[i] <= i, atomicMin-only changes and the
+// agent-scope loads of phases 2 and 3 hold as written for the smaller set, and the root stays the first voxel in raster order.
 #pragma once
 #include "host_call.h"
 
@@ -38,6 +43,16 @@ struct CCGeom {
 __constant__ signed char c_back[13][3] = {
     {-1, -1, -1}, {-1, -1, 0}, {-1, -1, 1}, {-1, 0, -1}, {-1, 0, 0}, {-1, 0, 1}, {-1, 1, -1}, {-1, 1, 0}, {-1, 1, 1},
     {0, -1, -1}, {0, -1, 0}, {0, -1, 1}, {0, 0, -1}};
+// the backward neighbours of a connectivity: N of them, neighbour k's offset along axis a is d(k, a)
+template <int CONN> struct CCBack;
+template <> struct CCBack<26> {
+    static constexpr int N = 13;
+    static __device__ __forceinline__ int d(int k, int a) { return c_back[k][a]; }
+};
+template <> struct CCBack<6> {                             // k = 0: dx = -1, 1: dy = -1, 2: dz = -1
+    static constexpr int N = 3;
+    static __device__ __forceinline__ int d(int k, int a) { return k == a ? -1 : 0; }
+};
 
 template <typename T>
 __device__ __forceinline__ int group_of(const T *labels, int i, const int *table, int n_table) {
@@ -112,7 +127,7 @@ __device__ __forceinline__ void tile_origin(const CCGeom &g, int &x0, int &y0, i
 }
 
 // 1. init + merge inside the tile
-template <class L>
+template <class L, int CONN = 26>
 __global__ __launch_bounds__(CC_THREADS) void cc_tile_merge_kernel(L src, CCGeom g, int *parent) {
     __shared__ int lp[CC_TILE];
     __shared__ int lg[CC_TILE];
@@ -135,8 +150,8 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile_merge_kernel(L src, CCGeom
         int lx, ly, lz;
         tile_coords(g, l, lx, ly, lz);
 #pragma unroll
-        for (int k = 0; k < 13; ++k) {
-            const int nx = lx + c_back[k][0], ny = ly + c_back[k][1], nz = lz + c_back[k][2];
+        for (int k = 0; k < CCBack<CONN>::N; ++k) {
+            const int nx = lx + CCBack<CONN>::d(k, 0), ny = ly + CCBack<CONN>::d(k, 1), nz = lz + CCBack<CONN>::d(k, 2);
             if (nx < 0 || ny < 0 || nz < 0 || ny >= TY || nz >= TZ) continue;
             const int nl = (nx * TY + ny) * TZ + nz;
             if (lg[nl] == grp) local_union(lp, l, nl);
@@ -159,7 +174,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile_merge_kernel(L src, CCGeom
 }
 
 // 2. link across tile borders: the backward neighbours of a voxel that lie in another tile
-template <class L>
+template <class L, int CONN = 26>
 __global__ __launch_bounds__(CC_THREADS) void cc_cross_merge_kernel(L src, CCGeom g, int *parent) {
     int x0, y0, z0;
     tile_origin(g, x0, y0, z0);
@@ -167,17 +182,18 @@ __global__ __launch_bounds__(CC_THREADS) void cc_cross_merge_kernel(L src, CCGeo
     for (int l = threadIdx.x; l < CC_TILE; l += CC_THREADS) {
         int lx, ly, lz;
         tile_coords(g, l, lx, ly, lz);
-        // only voxels on a tile face have neighbours in another tile
-        if (lx > 0 && ly > 0 && lz > 0 && ly < TY - 1 && lz < TZ - 1) continue;
+        // only voxels on a tile face have neighbours in another tile (face neighbours: only on the three lower faces)
+        if (lx > 0 && ly > 0 && lz > 0 && (CONN == 6 || (ly < TY - 1 && lz < TZ - 1))) continue;
         const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
         if (x >= g.X || y >= g.Y || z >= g.Z) continue;
         const int i = (x * g.Y + y) * g.Z + z;
         const int grp = src.group(i, g.n_table);
         if (grp < 0) continue;
-        for (int k = 0; k < 13; ++k) {
-            const int ox = lx + c_back[k][0], oy = ly + c_back[k][1], oz = lz + c_back[k][2];
+        for (int k = 0; k < CCBack<CONN>::N; ++k) {
+            const int dx = CCBack<CONN>::d(k, 0), dy = CCBack<CONN>::d(k, 1), dz = CCBack<CONN>::d(k, 2);
+            const int ox = lx + dx, oy = ly + dy, oz = lz + dz;
             if (ox >= 0 && oy >= 0 && oz >= 0 && oy < TY && oz < TZ && ox < TX) continue;    // inside the tile: done by 1.
-            const int nx = x + c_back[k][0], ny = y + c_back[k][1], nz = z + c_back[k][2];
+            const int nx = x + dx, ny = y + dy, nz = z + dz;
             if (nx < 0 || ny < 0 || nz < 0 || ny >= g.Y || nz >= g.Z) continue;
             const int j = (nx * g.Y + ny) * g.Z + nz;
             if (src.group(j, g.n_table) == grp) global_union(parent, i, j);
@@ -252,11 +268,11 @@ inline unsigned cc_run_blocks(int n) {
 }
 
 // phases 1-3: parent[i] = the first voxel of i's component, -1 outside every set
-template <class L>
+template <class L, int CONN = 26>
 void cc_label(HipCall &call, const L &src, const CCGeom &g, int n, int *parent) {
     const dim3 block(CC_THREADS);
-    call.launch(cc_tile_merge_kernel<L>, dim3(cc_tiles(g)), block, 0, src, g, parent);
-    call.launch(cc_cross_merge_kernel<L>, dim3(cc_tiles(g)), block, 0, src, g, parent);
+    call.launch(cc_tile_merge_kernel<L, CONN>, dim3(cc_tiles(g)), block, 0, src, g, parent);
+    call.launch(cc_cross_merge_kernel<L, CONN>, dim3(cc_tiles(g)), block, 0, src, g, parent);
     call.launch(cc_flatten_kernel, dim3(cc_vox_blocks(n)), block, 0, parent, n);
 }
 // phase 4 into size [n], which must be zero

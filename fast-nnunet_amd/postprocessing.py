@@ -18,6 +18,16 @@ read as labels on the device, post-processed there and written by the prediction
 thread; ``determine_postprocessing_on_folder`` is the reference's search on folders (postprocessing_search.py).
 ``apply_postprocessing`` fuses consecutive steps into one pass where that gives the sequential result
 (``plan_passes``).  There is no CPU path for this module's own steps.
+
+Two more steps run on the device, the "small region filtering and hole filling" the reference's inference front end names
+without shipping their source; both are defined by scipy's published behaviour:
+
+* ``remove_small_components_from_segmentation`` (``fnn_remove_small_components``): the mask ``seg in S`` is labelled like
+  ``ndimage.label`` with ``generate_binary_structure(ndim, ndim)`` (``connectivity=26``) or ``(ndim, 1)`` (``6``); every
+  component with fewer voxels than ``min_size`` becomes ``background_label``, one of exactly ``min_size`` is kept;
+* ``fill_holes_in_segmentation`` (``fnn_fill_holes``): ``holes = ndimage.binary_fill_holes(seg in S) & ~(seg in S)``, default
+  (cross) structure, on the 2-D array for a 2-D map; hole voxels whose value is ``background_label`` become ``fill_label``,
+  another label that lies inside a hole stays.
 """
 from __future__ import annotations
 
@@ -25,7 +35,7 @@ import functools
 import io
 import os
 import pickle
-from typing import Callable, List, Sequence, Tuple, Union
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -55,17 +65,84 @@ def _is_ours(fn) -> bool:
     return (getattr(fn, '__module__', None), getattr(fn, '__qualname__', None)) == REFERENCE_NAME
 
 
+def _integer(value, name: str) -> int:
+    """``value`` as a Python int, or a ValueError naming the argument (bools and non-integral numbers are refused)."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) or value != int(value):
+        raise ValueError(f'{name} must be an integer, got {value!r}')
+    return int(value)
+
+
+def _small_component_sets(kw: dict) -> Tuple[List[frozenset], List[int], int]:
+    """The sets, their ``min_size`` and the connectivity of one ``remove_small_components_from_segmentation`` step, checked."""
+    lor, per_member = kw['labels_or_regions'], bool(kw.get('per_member', False))
+    conn = kw.get('connectivity', 26)
+    if isinstance(conn, (bool, np.bool_)) or conn not in (6, 26):
+        raise ValueError(f'connectivity must be 6 or 26, got {conn!r}')
+    sets = [label_set(m) for m in lor] if per_member and isinstance(lor, list) else [label_set(lor)]
+    for a in range(len(sets)):
+        for b in range(a):
+            if sets[a] & sets[b]:
+                raise ValueError(f'labels_or_regions: with per_member=True the members must be disjoint, '
+                                 f'{sorted(sets[a] & sets[b])} are in two of them')
+    min_size = kw['min_size']
+    if isinstance(min_size, (list, tuple, np.ndarray)):
+        if len(min_size) != len(sets):
+            raise ValueError(f'min_size has {len(min_size)} entries for {len(sets)} set(s)')
+        sizes = [_integer(v, 'min_size') for v in min_size]
+    else:
+        sizes = [_integer(min_size, 'min_size')] * len(sets)
+    if any(v < 0 for v in sizes):
+        raise ValueError(f'min_size must not be negative, got {min(sizes)}')
+    return sets, sizes, int(conn)
+
+
+def _hole_set(kw: dict) -> Tuple[frozenset, int, int]:
+    """The set, the background and the fill label of one ``fill_holes_in_segmentation`` step, checked."""
+    s = label_set(kw['labels_or_regions'])
+    bg = _integer(kw.get('background_label', 0), 'background_label')
+    fill = kw.get('fill_label')
+    if fill is None:
+        if len(s) != 1:
+            raise ValueError(f'fill_label is required when the set has {len(s)} labels: which of them fills the holes?')
+        fill = next(iter(s))
+    fill = _integer(fill, 'fill_label')
+    if fill == bg:
+        raise ValueError(f'fill_label equals background_label ({bg}): nothing would change')
+    return s, bg, fill
+
+
 def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> List[Tuple]:
-    """Group the steps into passes, in order.  Returns a list of ``('gpu', [(S, background_label, step), ...])`` and
-    ``('host', step)`` entries.  A step joins the open GPU pass only if its set is disjoint from every set already in
-    it, it has the same ``background_label``, and that background is not in its own set (otherwise voxels an earlier
-    step of the pass set to background would belong to its mask).  Any other callable runs on its own, on the host."""
+    """Group the steps into passes, in order: one entry per GPU call or host step.  Returns a list of
+
+    * ``('gpu', [(S, background_label, step), ...])`` - one ``fnn_keep_largest_components`` call;
+    * ``('gpu_small', [(S, background_label, step, min_size), ...])`` - one ``fnn_remove_small_components`` call, all of
+      its steps with one connectivity (``pp_fn_kwargs[step]``'s); a ``per_member`` step gives one entry per member;
+    * ``('gpu_holes', [(S, background_label, step, fill_label)])`` - one ``fnn_fill_holes`` call, always one step;
+    * ``('host', step)`` - any other callable, on its own, on the host.
+
+    A step joins the open pass of its own kind only if each of its sets is disjoint from every set already in it, it has
+    the same ``background_label``, and that background is not in its own sets (otherwise voxels an earlier step of the
+    pass set to background would belong to its mask).  The arguments of the new steps are checked here (ValueError)."""
     passes: List[Tuple] = []
     for k, (fn, kw) in enumerate(zip(pp_fns, pp_fn_kwargs)):
+        kw = dict(kw)
+        if fn is fill_holes_in_segmentation:
+            s, bg, fill = _hole_set(kw)
+            passes.append(('gpu_holes', [(s, bg, k, fill)]))
+            continue
+        if fn is remove_small_components_from_segmentation:
+            sets, sizes, conn = _small_component_sets(kw)
+            bg = _integer(kw.get('background_label', 0), 'background_label')
+            cur = passes[-1] if passes and passes[-1][0] == 'gpu_small' else None
+            if (cur is not None and pp_fn_kwargs[cur[1][0][2]].get('connectivity', 26) == conn and
+                    all(bg not in s and all(bg == e[1] and not (s & e[0]) for e in cur[1]) for s in sets)):
+                cur[1].extend((s, bg, k, m) for s, m in zip(sets, sizes))
+            else:
+                passes.append(('gpu_small', [(s, bg, k, m) for s, m in zip(sets, sizes)]))
+            continue
         if not _is_ours(fn):
             passes.append(('host', k))
             continue
-        kw = dict(kw)
         s = label_set(kw['labels_or_regions'])
         bg = int(kw.get('background_label', 0))
         cur = passes[-1] if passes and passes[-1][0] == 'gpu' else None
@@ -74,6 +151,26 @@ def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> Lis
         else:
             passes.append(('gpu', [(s, bg, k)]))
     return passes
+
+
+class GpuPass(NamedTuple):
+    """One GPU call of ``_run_passes``: which entry it is and what it takes."""
+    call: str                                   # 'largest', 'small' or 'holes'
+    sets: List[frozenset]                       # disjoint label sets, all labelled in this call ('holes': one)
+    background: int
+    min_size: Tuple[int, ...] = ()              # 'small': one per set
+    connectivity: int = 26                      # 'small'
+    fill_label: int = 0                         # 'holes'
+
+
+def _gpu_pass(kind: str, body, pp_fn_kwargs) -> GpuPass:
+    """A GPU entry of ``plan_passes`` as the call ``_run_passes`` makes."""
+    sets, bg = [e[0] for e in body], body[0][1]
+    if kind == 'gpu_small':
+        return GpuPass('small', sets, bg, tuple(e[3] for e in body), int(pp_fn_kwargs[body[0][2]].get('connectivity', 26)))
+    if kind == 'gpu_holes':
+        return GpuPass('holes', sets, bg, fill_label=body[0][3])
+    return GpuPass('largest', sets, bg)
 
 
 def _as_device_u(seg: torch.Tensor) -> Tuple[torch.Tensor, bool]:
@@ -90,30 +187,48 @@ def _as_device_u(seg: torch.Tensor) -> Tuple[torch.Tensor, bool]:
     return seg.to(torch.int32).to(torch.int16).contiguous(), True
 
 
-def _run_passes(work: torch.Tensor, u16: bool, groups: List[List[frozenset]], backgrounds: List[int]):
-    """Apply GPU passes in order to the [X, Y, Z] device tensor ``work`` (in place)."""
+def _check_passes(passes: Sequence[GpuPass], u16: bool):
+    """The labels a pass writes must fit the map's dtype: a ValueError naming the argument, before any GPU call."""
+    limit, name = (65536, 'uint16') if u16 else (256, 'uint8')
+    for p in passes:
+        if p.background < 0 or p.background >= limit:
+            raise ValueError(f'background_label {p.background} does not fit the label map ({name})')
+        if p.call == 'holes' and (p.fill_label < 0 or p.fill_label >= limit):
+            raise ValueError(f'fill_label {p.fill_label} does not fit the label map ({name})')
+
+
+def _run_passes(work: torch.Tensor, u16: bool, passes: Sequence[GpuPass], border_axes: int = 7):
+    """Apply GPU passes in order to the [X, Y, Z] device tensor ``work`` (in place).  ``border_axes``: ``fnn_fill_holes``'s,
+    6 for a 2-D map carried as [1, Y, Z]."""
     limit = 65536 if u16 else 256
+    _check_passes(passes, u16)
     with torch.cuda.device(work.device):
         stream = torch.cuda.current_stream(work.device).cuda_stream
-        for sets, bg in zip(groups, backgrounds):
-            if bg < 0 or bg >= limit:
-                raise ValueError(f'background_label {bg} does not fit the label map ({"uint16" if u16 else "uint8"})')
-            top = max((max(s) for s in sets if s), default=-1)
+        for p in passes:
+            top = max((max(s) for s in p.sets if s), default=-1)
             table = np.full(min(max(top + 1, 0), limit), -1, np.int32)
-            for g, s in enumerate(sets):
+            for g, s in enumerate(p.sets):
                 for v in s:
                     if 0 <= v < limit:
                         table[v] = g
-            capi.keep_largest_components(work.data_ptr(), u16, work.shape, table, len(sets), bg, stream)
+            if p.call == 'largest':
+                capi.keep_largest_components(work.data_ptr(), u16, work.shape, table, len(p.sets), p.background, stream)
+            elif p.call == 'small':
+                capi.remove_small_components(work.data_ptr(), u16, work.shape, table, len(p.sets), p.background, p.min_size,
+                                             p.connectivity, stream)
+            elif p.call == 'holes':
+                capi.fill_holes(work.data_ptr(), u16, work.shape, table, p.background, p.fill_label, border_axes, stream)
+            else:
+                raise ValueError(f'unknown GPU pass {p.call!r}')
 
 
-def _device_postprocess(seg: torch.Tensor, groups, backgrounds) -> torch.Tensor:
+def _device_postprocess(seg: torch.Tensor, passes: Sequence[GpuPass]) -> torch.Tensor:
     """Device tensor (2-D or 3-D) -> new device tensor of the same dtype and shape."""
     if seg.ndim not in (2, 3):
         raise ValueError(f'segmentation must be 2-D or 3-D, got shape {tuple(seg.shape)}')
     work, u16 = _as_device_u(seg)
     work3 = work.view(1, *work.shape) if work.ndim == 2 else work
-    _run_passes(work3, u16, groups, backgrounds)
+    _run_passes(work3, u16, passes, border_axes=6 if work.ndim == 2 else 7)
     if not u16:
         return work
     return as_plain_labels(work).to(seg.dtype)
@@ -125,23 +240,26 @@ def _device() -> torch.device:
     return torch.device('cuda', torch.cuda.current_device())
 
 
-def _postprocess(segmentation, groups, backgrounds):
-    """numpy in -> numpy out (same dtype); torch in -> new torch tensor on the input's device (CUDA work either way)."""
+def _postprocess(segmentation, passes: Sequence[GpuPass]):
+    """numpy in -> numpy out (same dtype); torch in -> new torch tensor on the input's device (CUDA work either way).
+    What can be refused from the arguments alone is refused before a GPU is asked for."""
     if isinstance(segmentation, torch.Tensor):
+        _check_passes(passes, segmentation.dtype != torch.uint8)
         if segmentation.device.type == 'cuda':
-            return _device_postprocess(segmentation, groups, backgrounds)
-        out = _device_postprocess(segmentation.to(_device()), groups, backgrounds)
+            return _device_postprocess(segmentation, passes)
+        out = _device_postprocess(segmentation.to(_device()), passes)
         return out.to(segmentation.device)
     arr = np.asarray(segmentation)
     if arr.dtype.kind not in 'iu':
         raise ValueError(f'label maps must have an integer dtype, got {arr.dtype}')
     if arr.size and (int(arr.min()) < 0 or int(arr.max()) > 65535):
         raise ValueError(f'label values must lie in 0..65535 (got {int(arr.min())}..{int(arr.max())})')
+    _check_passes(passes, arr.dtype != np.uint8)
     if arr.dtype == np.uint8:
         t = torch.from_numpy(np.ascontiguousarray(arr))
     else:
         t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.int32))
-    out = _device_postprocess(t.to(_device()), groups, backgrounds)
+    out = _device_postprocess(t.to(_device()), passes)
     return out.cpu().numpy().astype(arr.dtype, copy=False)
 
 
@@ -150,26 +268,55 @@ def remove_all_but_largest_component_from_segmentation(segmentation, labels_or_r
                                                        background_label: int = 0):
     """Reference signature (remove_connected_components.py:21-33).  ``segmentation``: numpy (returns numpy of the same
     dtype) or a torch tensor (returns a new tensor on its device), 2-D or 3-D, values 0..65535."""
-    return _postprocess(segmentation, [[label_set(labels_or_regions)]], [int(background_label)])
+    return _postprocess(segmentation, [GpuPass('largest', [label_set(labels_or_regions)], int(background_label))])
+
+
+def _one_step(fn, segmentation, kw: dict):
+    (kind, body), = plan_passes([fn], [kw])
+    return _postprocess(segmentation, [_gpu_pass(kind, body, [kw])])
+
+
+def remove_small_components_from_segmentation(segmentation, labels_or_regions, min_size, background_label: int = 0,
+                                              connectivity: int = 26, per_member: bool = False):
+    """Every connected component of the mask ``seg in S`` with fewer than ``min_size`` voxels becomes
+    ``background_label``; one of exactly ``min_size`` voxels is kept, ``min_size <= 1`` changes nothing.  S is the union
+    of ``labels_or_regions`` as in ``remove_all_but_largest_component_from_segmentation``; with a list and
+    ``per_member=True`` each member is a set of its own (they must be disjoint; ``min_size`` may then be a sequence, one
+    entry per member) and all of them are labelled on the input map in one pass.  ``connectivity``: 26 (8 in 2-D, a
+    voxel's full neighbourhood) or 6 (4 in 2-D, face neighbours).  ``min_size`` counts voxels: for a size in physical
+    units divide by the voxel volume first.  ``segmentation``, dtype and values: as the function above; the input is left alone."""
+    return _one_step(remove_small_components_from_segmentation, segmentation,
+                     dict(labels_or_regions=labels_or_regions, min_size=min_size, background_label=background_label,
+                          connectivity=connectivity, per_member=per_member))
+
+
+def fill_holes_in_segmentation(segmentation, labels_or_regions, fill_label: Optional[int] = None, background_label: int = 0):
+    """scipy's ``binary_fill_holes`` of the mask ``seg in S`` (default structure; the whole volume for a 3-D map, the plane
+    for a 2-D one): a hole is a face-connected part of the mask's complement that does not reach the border of the map.
+    Hole voxels whose value is ``background_label`` become ``fill_label`` - by default the label of S when it has exactly
+    one, otherwise it must be given - and any other label inside a hole (a tumour inside an organ) stays.
+    ``segmentation``, dtype and values: as the functions above; the input is left alone."""
+    return _one_step(fill_holes_in_segmentation, segmentation,
+                     dict(labels_or_regions=labels_or_regions, fill_label=fill_label, background_label=background_label))
 
 
 def apply_postprocessing(segmentation, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]):
     """``apply_postprocessing`` (remove_connected_components.py:36-39): every step in order, consecutive steps of
-    this module fused into one labelling pass where ``plan_passes`` allows it.  Other callables run as they are, on a
-    host (numpy) copy."""
+    this module fused into one labelling pass where ``plan_passes`` allows it; a chain of this module's steps of any
+    kind costs one upload and one download.  Other callables run as they are, on a host (numpy) copy."""
     is_torch = isinstance(segmentation, torch.Tensor)
     seg = segmentation
-    gpu: List[Tuple[List[frozenset], int]] = []          # consecutive GPU passes: one upload / download for all of them
+    gpu: List[GpuPass] = []                              # consecutive GPU passes: one upload / download for all of them
 
     def flush(seg):
         if gpu:
-            seg = _postprocess(seg, [g for g, _ in gpu], [b for _, b in gpu])
+            seg = _postprocess(seg, list(gpu))
             gpu.clear()
         return seg
 
     for kind, body in plan_passes(pp_fns, pp_fn_kwargs):
-        if kind == 'gpu':
-            gpu.append(([s for s, _, _ in body], body[0][1]))
+        if kind != 'host':
+            gpu.append(_gpu_pass(kind, body, pp_fn_kwargs))
             continue
         seg = flush(seg)
         host = seg.cpu().numpy() if isinstance(seg, torch.Tensor) else np.asarray(seg)
@@ -182,16 +329,21 @@ def apply_postprocessing(segmentation, pp_fns: Sequence[Callable], pp_fn_kwargs:
 
 
 class _RestrictedUnpickler(pickle.Unpickler):
-    """Reads ``postprocessing.pkl`` without nnunetv2: the reference's function maps onto this module's, numpy scalars
-    and dtypes may be rebuilt, every other global is refused."""
+    """Reads ``postprocessing.pkl`` without nnunetv2: the reference's function maps onto this module's, this module's own
+    two further steps load under this module's name, numpy scalars and dtypes may be rebuilt, every other global is refused."""
     _NUMPY = {('numpy', 'dtype'), ('numpy.core.multiarray', 'scalar'), ('numpy._core.multiarray', 'scalar')}
 
     def find_class(self, module, name):
         if (module, name) in (REFERENCE_NAME, (__name__, REFERENCE_NAME[1])):      # also a pkl written with this module
             return remove_all_but_largest_component_from_segmentation
+        if module == __name__ and name in _OWN_STEPS:                              # this module's steps beyond the reference's
+            return _OWN_STEPS[name]
         if (module, name) in self._NUMPY:
             return np.dtype if name == 'dtype' else _numpy_scalar
         raise pickle.UnpicklingError(f'postprocessing.pkl names a global that is not allowed: {module}.{name}')
+
+
+_OWN_STEPS = {f.__name__: f for f in (remove_small_components_from_segmentation, fill_holes_in_segmentation)}
 
 
 def _numpy_scalar(dtype, data=None):

@@ -182,7 +182,7 @@ class DeviceBackend:
 
     def keep_largest(self, seg, sets: List[frozenset]):
         """Every set labelled in one pass (the sets are disjoint), background 0."""
-        return pp._postprocess(seg, [sets], [0])
+        return pp._postprocess(seg, [pp.GpuPass('largest', sets, 0)])
 
     def counts(self, ref, maps, values, ignore):
         return ev.confusion_counts(ref, maps, values, ignore, checked=True)

@@ -373,6 +373,34 @@ int fnn_keep_largest_components(void *labels, int label_dtype, const int64_t sha
                                 const int32_t *group_of_label, int n_table, int n_groups,
                                 int background_label, int64_t *removed, void *stream);
 
+/* Small-region filtering for disjoint label sets at once (additive in ABI 4); the reference names the step in its inference
+ * front end and ships no source for it, the definition is scipy's ndimage.label + bincount.  labels, label_dtype, shape,
+ * group_of_label, n_table, n_groups, background_label, removed, the limits and the scratch: as
+ * fnn_keep_largest_components.  connectivity: 26 (a voxel's full neighbourhood, scipy's generate_binary_structure(3, 3)) or
+ * 6 (face neighbours, (3, 1)); any other value is FNN_E_UNSUPPORTED before any launch.  Two neighbours belong to one component
+ * iff their labels map to the same set.  min_size (host, n_groups entries): every component of set g with fewer than
+ * min_size[g] voxels becomes background_label, one of exactly min_size[g] is kept; min_size[g] <= 1 changes nothing for that
+ * set.  All sets are labelled in one pass. */
+int fnn_remove_small_components(void *labels, int label_dtype, const int64_t shape[3],
+                                const int32_t *group_of_label, int n_table, int n_groups,
+                                int background_label, const int64_t *min_size, int connectivity,
+                                int64_t *removed, void *stream);
+
+/* Hole filling for one label set S (additive in ABI 4); no source in the reference either, the definition is scipy's:
+ * holes = ndimage.binary_fill_holes(in_S) & ~in_S with the default (cross) structure.  labels [X][Y][Z] (FNN_LABEL_U8 / U16,
+ * device pointer) is changed in place.  group_of_label[v] (host, n_table entries) is 0 where label value v belongs to S and
+ * -1 where not; labels >= n_table are outside S.  A hole is a 6-connected component of the complement of S that reaches no
+ * face of the volume along an axis of border_axes (bit a set: the two faces of axis a are borders; 1..7).  Hole voxels whose
+ * value equals background_label become fill_label; another label inside a hole stays.  A 3-D map passes border_axes 7; a 2-D
+ * map is the volume [1][Y][Z] with border_axes 6 (with bit 0 set every voxel of it lies on a border and nothing is filled,
+ * as scipy does for an array of shape (1, Y, Z)).  filled (optional, host) receives the number of voxels changed.
+ * FNN_E_INVALID before any launch: a label outside the dtype, fill_label equal to background_label, border_axes outside
+ * 1..7, a table entry outside [-1, 0]; sizes as fnn_keep_largest_components.  Launches: one pass for the bounding box of S,
+ * read by the host (an empty S, or S filling its box, ends the call there); then the complement is labelled inside the box
+ * only.  Scratch, allocated inside the call: 8 B per voxel of the box.  Synchronises the stream. */
+int fnn_fill_holes(void *labels, int label_dtype, const int64_t shape[3], const int32_t *group_of_label, int n_table,
+                   int background_label, int fill_label, int border_axes, int64_t *filled, void *stream);
+
 /* Cross-configuration ensembling (additive in ABI 4): average_probabilities + merge_files without the image writer
  * (ensembling/ensemble.py:16-44), in one pass from the members' logits.  member_logits[m] (device, host array of
  * n_members pointers, 1..16) are [heads][bbox extents] of dtype member_dtype[m] (FNN_OUT_F16 / FNN_OUT_F32; members may

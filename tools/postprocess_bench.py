@@ -4,6 +4,10 @@ the scipy restatement's seconds on the host next to it.
 
 usage (repo root, GPU box): python tools/postprocess_bench.py [--n 512] [--reps 5] [--no-cpu] [--out FILE]
 Kernel times: run it under rocprofv3 --kernel-trace --stats.
+
+--section small_holes (profiles/r33_small_holes.txt): fnn_remove_small_components and fnn_fill_holes on evaluation_bench's two
+maps - 60 ellipsoids with cavities punched into them, and 20000 small lesions - next to fnn_keep_largest_components on the same
+map in the same run and to scipy on this machine's CPU (ndimage.label + bincount, binary_fill_holes in the label's box).
 """
 import argparse
 import os
@@ -30,13 +34,139 @@ def make_map(n, seed=61):
     return seg
 
 
+def punch_cavities(seg):
+    """A closed cavity (an ellipsoid of background, a third of the box's half-extents) at the centre of every label's box,
+    where the label itself lies there: holes for fnn_fill_holes to find.  Where another ellipsoid was painted over the
+    centre the label keeps no cavity."""
+    out = seg.copy()
+    for lab, box in enumerate(ndimage.find_objects(seg), 1):
+        if box is None:
+            continue
+        half = [max(1, (s.stop - s.start) // 6) for s in box]
+        centre = [(s.start + s.stop) // 2 for s in box]
+        z, y, x = np.ogrid[tuple(slice(-h, h + 1) for h in half)]
+        inside = (z / half[0]) ** 2 + (y / half[1]) ** 2 + (x / half[2]) ** 2 <= 1.0
+        sub = out[tuple(slice(c - h, c + h + 1) for c, h in zip(centre, half))]
+        sub[inside & (sub == lab)] = 0
+    return out
+
+
+def small_holes_section(a):
+    """fnn_remove_small_components (all sets in one call) and fnn_fill_holes (one call per label) against
+    fnn_keep_largest_components on the same map and scipy on the host."""
+    from fast_nnunet_amd import capi
+    from tools.evaluation_bench import lesion_map, organ_map
+    import pp_morph_ref as ref
+    dev = torch.device('cuda', 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    maps = {'organs': (punch_cavities(organ_map(a.n)), list(range(1, 61)), 50),
+            'lesions': (lesion_map(a.n), [1], 20)}
+    lines = [f'postprocess_bench --section small_holes: {a.n}^3 uint8 maps; device {torch.cuda.get_device_name(dev)}',
+             '  organs: 60 ellipsoids (evaluation_bench.organ_map) with an ellipsoidal cavity punched into the centre of each label box',
+             '  lesions: 20000 ellipsoids of label 1 with semi-axes 1..3 (evaluation_bench.lesion_map)',
+             f'device calls: median (min, max) of {a.reps} after one warm-up, events around the call on a fresh copy of the map (scratch '
+             f'allocation, launches and the synchronising copy-back of the counts included)']
+
+    def report(text):
+        lines.append(text)
+        print(text, flush=True)
+    for text in lines:
+        print(text, flush=True)
+
+    for name, (seg, labels, min_size) in maps.items():
+        table = np.full(max(labels) + 1, -1, np.int32)
+        table[labels] = np.arange(len(labels))
+        base = torch.from_numpy(seg).to(dev)
+        report(f'{name}: {len(labels)} label(s), foreground voxels {int((seg > 0).sum())}')
+
+        def timed(fn):
+            ts = []
+            for r in range(a.reps + 1):
+                w = base.clone()
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn(w)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                if r:
+                    ts.append(e0.elapsed_time(e1))
+            return float(np.median(ts)), min(ts), max(ts), w, out
+        ms, lo, hi, _, _ = timed(lambda w: capi.keep_largest_components(w.data_ptr(), False, w.shape, table, len(labels), 0, stream))
+        report(f'  fnn_keep_largest_components, all {len(labels)} set(s) in one labelling: {ms:.2f} ms (min {lo:.2f} max {hi:.2f})')
+        small = {}
+        for conn in (26, 6):
+            ms, lo, hi, w, removed = timed(lambda w: capi.remove_small_components(w.data_ptr(), False, w.shape, table, len(labels), 0,
+                                                                                  [min_size] * len(labels), conn, stream))
+            small[conn] = w.cpu().numpy()
+            report(f'  fnn_remove_small_components, all {len(labels)} set(s), min_size {min_size}, connectivity {conn}: {ms:.2f} ms '
+                   f'(min {lo:.2f} max {hi:.2f}); voxels removed {int(removed.sum())}')
+        per_label, filled_total = [], 0
+        w = base.clone()
+        in_set = np.full(max(labels) + 1, -1, np.int32)
+        for lab in labels:
+            in_set[:] = -1
+            in_set[lab] = 0
+            ts = []
+            for r in range(a.reps + 1):
+                w.copy_(base)
+                torch.cuda.synchronize(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                n_filled = capi.fill_holes(w.data_ptr(), False, w.shape, in_set, 0, lab, 7, stream)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                if r:
+                    ts.append(e0.elapsed_time(e1))
+            per_label.append(float(np.median(ts)))
+            filled_total += n_filled
+        report(f'  fnn_fill_holes, one call per label: {sum(per_label):.2f} ms for {len(labels)} label(s) (sum of the per-label medians); per '
+               f'label median {np.median(per_label):.2f} ms, min {min(per_label):.2f}, max {max(per_label):.2f}; voxels filled {filled_total}')
+        w.copy_(base)
+        t0 = time.perf_counter()
+        for lab in labels:
+            in_set[:] = -1
+            in_set[lab] = 0
+            capi.fill_holes(w.data_ptr(), False, w.shape, in_set, 0, lab, 7, stream)
+        torch.cuda.synchronize(dev)
+        report(f'  the same {len(labels)} call(s) one after another on one map, host clock: {(time.perf_counter() - t0) * 1e3:.2f} ms')
+        holes_dev = w.cpu().numpy()
+        if a.no_cpu:
+            continue
+        boxes = ndimage.find_objects(seg) if len(labels) > 1 else [tuple(slice(0, n) for n in seg.shape)]
+        for conn in (26, 6):
+            t0 = time.perf_counter()
+            want = seg.copy()
+            for lab in labels:
+                box = boxes[lab - 1]
+                if box is not None:
+                    want[box][ref.small_components_of_set(seg[box], [lab], min_size, conn)] = 0
+            report(f'  scipy ndimage.label + bincount, connectivity {conn}, per label in its find_objects box (one thread): '
+                   f'{time.perf_counter() - t0:.2f} s; device result bit-identical: {np.array_equal(small[conn], want)}')
+        t0 = time.perf_counter()
+        want = seg.copy()
+        for lab in labels:
+            box = ndimage.find_objects((seg == lab).astype(np.uint8))[0] if len(labels) == 1 else boxes[lab - 1]
+            if box is not None:
+                sub = want[box]
+                sub[ref.holes_of(seg[box] == lab) & (sub == 0)] = lab
+        report(f'  scipy binary_fill_holes, per label cropped to its box (one thread): {time.perf_counter() - t0:.2f} s; device result '
+               f'bit-identical: {np.array_equal(holes_dev, want)}')
+    if a.out:
+        with open(a.out, 'w') as fh:
+            fh.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--section', default='largest', choices=['largest', 'small_holes'])
     a = ap.parse_args()
+    if a.section == 'small_holes':
+        return small_holes_section(a)
     from fast_nnunet_amd import capi
     from fast_nnunet_amd import postprocessing as pp
 
