@@ -78,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_remove_small_components', 'fnn_fill_holes', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_remove_small_components', 'fnn_fill_holes', 'fnn_binary_morphology', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -141,6 +141,9 @@ def load_library() -> C.CDLL:
         lib.fnn_remove_small_components.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, C.POINTER(i64), i32,
                                                     C.POINTER(i64), vp]
         lib.fnn_fill_holes.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, i32, C.POINTER(i64), vp]
+    if hasattr(lib, 'fnn_binary_morphology'):
+        lib.fnn_binary_morphology.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32, i32,
+                                              C.POINTER(i64), vp]
     lib.fnn_ensemble_export.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), C.POINTER(i64),
                                         C.POINTER(i64), C.POINTER(C.c_int32), vp, vp, i32, vp]
     lib.fnn_average_probabilities.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(C.c_int32), i64, vp, vp, i32, vp]
@@ -541,6 +544,26 @@ def fill_holes(labels_ptr: int, uint16: bool, shape, in_set, background_label: i
                              table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(background_label), int(fill_label),
                              int(border_axes), C.byref(filled), stream), lib)
     return int(filled.value)
+
+
+FNN_MORPH_DILATE, FNN_MORPH_ERODE, FNN_MORPH_OPEN, FNN_MORPH_CLOSE = 0, 1, 2, 3
+
+
+def binary_morphology(labels_ptr: int, uint16: bool, shape, in_set, op: int, connectivity: int, iterations: int, border_value: int,
+                      background_label: int, fill_label: int, axes: int = 7, stream: int = 0) -> int:
+    """fnn_binary_morphology on a device label map [X, Y, Z] in place: ``in_set[v]`` is 0 where label value v belongs to the set
+    and -1 where not; ``op`` is FNN_MORPH_DILATE / ERODE / OPEN / CLOSE with scipy's structure of ``connectivity`` 6 / 18 / 26,
+    ``iterations`` and ``border_value``.  Dilation and closing give ``fill_label`` to the background voxels they add, erosion and
+    opening ``background_label`` to the voxels they remove.  ``axes``: bit a - the structure spans axis a (7 for a 3-D map, 6
+    for a 2-D map carried as [1, Y, Z]).  Returns the number of voxels written."""
+    lib = load_library()
+    table = np.ascontiguousarray(in_set, dtype=np.int32)
+    changed = C.c_int64(0)
+    check(lib.fnn_binary_morphology(labels_ptr, FNN_LABEL_U16 if uint16 else FNN_LABEL_U8, (C.c_int64 * 3)(*[int(i) for i in shape]),
+                                    table.ctypes.data_as(C.POINTER(C.c_int32)), int(table.size), int(op), int(connectivity),
+                                    int(iterations), int(border_value), int(background_label), int(fill_label), int(axes),
+                                    C.byref(changed), stream), lib)
+    return int(changed.value)
 
 
 def confusion_counts(ref_ptr: int, pred_ptrs: Sequence[int], uint16: bool, n_vox: int, class_of_value, n_classes: int,

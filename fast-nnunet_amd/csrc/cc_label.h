@@ -25,10 +25,10 @@
 // agent-scope loads of phases 2 and 3 hold as written for the smaller set, and the root stays the first voxel in raster order.
 #pragma once
 #include "host_call.h"
+#include "label_set.h"
 
 namespace {
 
-constexpr int CC_THREADS = 256;
 constexpr int CC_TILE = 1024;          // voxels per tile: 4 per thread
 constexpr int CC_RUN = 16;             // consecutive voxels per thread in the size count
 
@@ -53,12 +53,6 @@ template <> struct CCBack<6> {                             // k = 0: dx = -1, 1:
     static constexpr int N = 3;
     static __device__ __forceinline__ int d(int k, int a) { return k == a ? -1 : 0; }
 };
-
-template <typename T>
-__device__ __forceinline__ int group_of(const T *labels, int i, const int *table, int n_table) {
-    const int v = labels[i];
-    return v < n_table ? table[v] : -1;
-}
 
 // the loader of one label map: the set of a voxel is the table's entry of its value
 template <typename T>
@@ -212,12 +206,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int *parent, int
     if (r != p) (void)min_agent(parent + i, r);
 }
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // 4. component sizes: each thread counts a run of CC_RUN consecutive voxels, then the lanes of a wave that end on the
 // same root add together - a component of 10^7 voxels costs one atomic per wave, not one per voxel
 __global__ __launch_bounds__(CC_THREADS) void cc_count_kernel(const int *parent, int n, int *size) {
@@ -262,7 +250,6 @@ inline CCGeom cc_geom(const int64_t shape[3], int n_tab) {
     return g;
 }
 inline unsigned cc_tiles(const CCGeom &g) { return (unsigned)((long long)((g.X + (1 << g.sx) - 1) >> g.sx) * g.tiles_y * g.tiles_z); }
-inline unsigned cc_vox_blocks(int n) { return (unsigned)((n + CC_THREADS - 1) / CC_THREADS); }
 inline unsigned cc_run_blocks(int n) {
     return (unsigned)(((long long)n + (long long)CC_THREADS * CC_RUN - 1) / ((long long)CC_THREADS * CC_RUN));
 }

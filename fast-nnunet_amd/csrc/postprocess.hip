@@ -18,14 +18,15 @@
 // fnn_remove_small_components is 1-4 and 6 with the sets' min_size in the place of the maxima (no launch 5).
 //
 // fnn_fill_holes, five launches and one host read in between:
-//   a. box           the bounding box of the set S and its voxel count (LDS atomics per workgroup, then six global ones);
+//   a. box           the bounding box of the set S and its voxel count (LDS atomics per workgroup, then six global ones;
+//                    fill_holes_box_kernel.h, shared with morph.hip);
 //                    the host reads it: an empty S, or S filling its box, ends the call;
 //   1-3.             cc_label.h with 6-connectivity on the complement of S inside the box (a loader that maps box-local
 //                    indices to voxels); fill_holes_box.h says why the box is enough and which of its faces open a component;
 //   b. mark          open[root] = 1 for every complement voxel on an opening box face (the same plain store from many threads);
 //   c. fill          voxels of components that were not marked and whose value is background_label become fill_label.
 #include "cc_label.h"
-#include "fill_holes_box.h"
+#include "fill_holes_box_kernel.h"
 #include <climits>
 #include <vector>
 
@@ -166,13 +167,6 @@ int components_call(const char *who, void *labels, int label_dtype, const int64_
 }
 
 // ---- fnn_fill_holes
-struct FHVolume { int X, Y, Z; };
-
-template <typename T>
-__device__ __forceinline__ bool fh_in_set(const T *labels, int i, const int *table, int n_table) {
-    return group_of(labels, i, table, n_table) >= 0;
-}
-
 // the loader of the complement of S inside the box: voxel i of the box in raster order is in set 0 unless its value is in S
 template <typename T>
 struct CCBoxComplement {
@@ -186,36 +180,6 @@ struct CCBoxComplement {
     }
     __device__ __forceinline__ int group(int i, int n_table) const { return fh_in_set(labels, voxel(i), table, n_table) ? -1 : 0; }
 };
-
-// a. the box of S: raw[k] = (extent of axis k) - 1 - lowest coordinate, raw[3 + k] = highest coordinate (both grow, so the
-// buffer starts as all -1), and the number of voxels of S
-template <typename T>
-__global__ __launch_bounds__(CC_THREADS) void fh_box_kernel(const T *labels, const int *table, int n_table, FHVolume v, int *raw,
-                                                            unsigned long long *count) {
-    __shared__ int sraw[6];
-    __shared__ unsigned int scount;
-    if (threadIdx.x < 6) sraw[threadIdx.x] = -1;
-    if (threadIdx.x == 6) scount = 0;
-    __syncthreads();
-    const long long n = (long long)v.X * v.Y * v.Z;
-    int mine[6] = {-1, -1, -1, -1, -1, -1};
-    unsigned int cnt = 0;
-    for (long long i = (long long)blockIdx.x * CC_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * CC_THREADS) {
-        if (!fh_in_set(labels, (int)i, table, n_table)) continue;
-        const int z = (int)(i % v.Z), t = (int)(i / v.Z), y = t % v.Y, x = t / v.Y;
-        mine[0] = max(mine[0], v.X - 1 - x); mine[1] = max(mine[1], v.Y - 1 - y); mine[2] = max(mine[2], v.Z - 1 - z);
-        mine[3] = max(mine[3], x); mine[4] = max(mine[4], y); mine[5] = max(mine[5], z);
-        ++cnt;
-    }
-    if (cnt) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) atomicMax(sraw + k, mine[k]);
-        atomicAdd(&scount, cnt);
-    }
-    __syncthreads();
-    if (threadIdx.x < 6 && sraw[threadIdx.x] >= 0) atomicMax(raw + threadIdx.x, sraw[threadIdx.x]);
-    if (threadIdx.x == 6 && scount) atomicAdd(count, (unsigned long long)scount);
-}
 
 // b. a complement component with a voxel on an opening face of the box is no hole
 __global__ __launch_bounds__(CC_THREADS) void fh_mark_kernel(const int *parent, FHBox b, int open_faces, int n_box, int *open) {
@@ -287,7 +251,6 @@ int fnn_fill_holes(void *labels, int label_dtype, const int64_t shape[3], const 
     if (int rc = fnn_need_dev(who, {labels}, "a device label map")) return rc;
     const int n_tab = n_table < max_label + 1 ? n_table : max_label + 1;
     if (n_tab == 0) return FNN_OK;                                               // S is empty
-    const int n = (int)(shape[0] * shape[1] * shape[2]);
     const FHVolume vol{(int)shape[0], (int)shape[1], (int)shape[2]};
 
     // the small block: raw box [6] | pad [2] | voxels of S | filled | table [n_tab]
@@ -299,12 +262,10 @@ int fnn_fill_holes(void *labels, int label_dtype, const int64_t shape[3], const 
     call.fill(raw, 0xff, 32);
     call.fill(count, 0, 16);
     call.copy(table, group_of_label, (size_t)n_tab * 4, hipMemcpyHostToDevice);
-    const unsigned vox_blocks = cc_vox_blocks(n);
     const dim3 block(CC_THREADS);
     fnn_by_label(label_dtype, [&](auto lt) {
         using LT = decltype(lt);
-        call.launch(fh_box_kernel<LT>, dim3(vox_blocks < 2048u ? vox_blocks : 2048u), block, 0, (const LT *)labels, table, n_tab, vol,
-                    raw, count);
+        fh_launch_box(call, (const LT *)labels, table, n_tab, vol, raw, count);
     });
     struct { int raw[8]; unsigned long long count; } found;
     call.copy(&found, raw, 40, hipMemcpyDeviceToHost);

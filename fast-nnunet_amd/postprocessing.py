@@ -28,6 +28,20 @@ without shipping their source; both are defined by scipy's published behaviour:
 * ``fill_holes_in_segmentation`` (``fnn_fill_holes``): ``holes = ndimage.binary_fill_holes(seg in S) & ~(seg in S)``, default
   (cross) structure, on the 2-D array for a 2-D map; hole voxels whose value is ``background_label`` become ``fill_label``,
   another label that lies inside a hole stays.
+
+The "morphological operations" of that list run on the device too (``fnn_binary_morphology``, csrc/morph.hip):
+``binary_dilation_in_segmentation``, ``binary_erosion_in_segmentation``, ``binary_opening_in_segmentation`` and
+``binary_closing_in_segmentation``.  With ``M = seg in S``, R is scipy's ``binary_dilation`` / ``binary_erosion`` /
+``binary_opening`` / ``binary_closing`` of M with ``structure=generate_binary_structure(ndim, rank)``, ``iterations`` (1..1024;
+scipy's "below 1: until nothing changes" is refused) and ``border_value`` (0 or 1), everything else at its default;
+``connectivity`` 6, 18 or 26 is rank 1, 2 or 3 (on a 2-D map 18 and 26 both give the full 3x3, 6 the cross; 6 is scipy's
+default structure).  The label rule:
+
+* dilation and closing only add: voxels of ``R & ~M`` whose value is ``background_label`` become ``fill_label`` (by default
+  the label of S when it has exactly one, as for the holes), any other label there stays, and no voxel of M changes - with
+  ``border_value=0`` scipy's closing is not extensive at the border of the map, and what it would take away stays;
+* erosion and opening only remove: voxels of ``M & ~R`` become ``background_label`` and no voxel outside M changes - with
+  ``border_value=1`` scipy's opening is not anti-extensive, and what it would add is not added.
 """
 from __future__ import annotations
 
@@ -111,6 +125,38 @@ def _hole_set(kw: dict) -> Tuple[frozenset, int, int]:
     return s, bg, fill
 
 
+class MorphParams(NamedTuple):
+    """What a morphology step asks of ``fnn_binary_morphology`` beyond its set and background."""
+    op: int                                     # capi.FNN_MORPH_DILATE / ERODE / OPEN / CLOSE
+    connectivity: int                           # 6, 18 or 26
+    iterations: int                             # 1..1024
+    border_value: int                           # 0 or 1
+    fill_label: int                             # the adding ops'; 0 and unused for erosion and opening
+
+
+_MORPH_ADDS = (capi.FNN_MORPH_DILATE, capi.FNN_MORPH_CLOSE)
+
+
+def _morph_step(op: int, kw: dict) -> Tuple[frozenset, int, MorphParams]:
+    """The set, the background and the parameters of one morphology step, checked."""
+    if op in _MORPH_ADDS:
+        s, bg, fill = _hole_set(kw)
+    else:
+        if kw.get('fill_label') is not None:
+            raise ValueError('fill_label: erosion and opening add no voxel and take no fill_label')
+        s, bg, fill = label_set(kw['labels_or_regions']), _integer(kw.get('background_label', 0), 'background_label'), 0
+    iterations = _integer(kw.get('iterations', 1), 'iterations')
+    if not 1 <= iterations <= 1024:
+        raise ValueError(f'iterations must lie in 1..1024, got {iterations} (scipy\'s "below 1: until nothing changes" is not built)')
+    conn = kw.get('connectivity', 6)
+    if isinstance(conn, (bool, np.bool_)) or conn not in (6, 18, 26):
+        raise ValueError(f'connectivity must be 6, 18 or 26, got {conn!r}')
+    border = kw.get('border_value', 0)
+    if border not in (0, 1):
+        raise ValueError(f'border_value must be 0 or 1, got {border!r}')
+    return s, bg, MorphParams(op, int(conn), iterations, int(border), fill)
+
+
 def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> List[Tuple]:
     """Group the steps into passes, in order: one entry per GPU call or host step.  Returns a list of
 
@@ -118,6 +164,7 @@ def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> Lis
     * ``('gpu_small', [(S, background_label, step, min_size), ...])`` - one ``fnn_remove_small_components`` call, all of
       its steps with one connectivity (``pp_fn_kwargs[step]``'s); a ``per_member`` step gives one entry per member;
     * ``('gpu_holes', [(S, background_label, step, fill_label)])`` - one ``fnn_fill_holes`` call, always one step;
+    * ``('gpu_morph', [(S, background_label, step, MorphParams)])`` - one ``fnn_binary_morphology`` call, always one step;
     * ``('host', step)`` - any other callable, on its own, on the host.
 
     A step joins the open pass of its own kind only if each of its sets is disjoint from every set already in it, it has
@@ -129,6 +176,11 @@ def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> Lis
         if fn is fill_holes_in_segmentation:
             s, bg, fill = _hole_set(kw)
             passes.append(('gpu_holes', [(s, bg, k, fill)]))
+            continue
+        op = next((code for f, code in _MORPH_OPS if fn is f), None)      # by identity: a host step need not be hashable
+        if op is not None:
+            s, bg, params = _morph_step(op, kw)
+            passes.append(('gpu_morph', [(s, bg, k, params)]))
             continue
         if fn is remove_small_components_from_segmentation:
             sets, sizes, conn = _small_component_sets(kw)
@@ -155,12 +207,15 @@ def plan_passes(pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]) -> Lis
 
 class GpuPass(NamedTuple):
     """One GPU call of ``_run_passes``: which entry it is and what it takes."""
-    call: str                                   # 'largest', 'small' or 'holes'
-    sets: List[frozenset]                       # disjoint label sets, all labelled in this call ('holes': one)
+    call: str                                   # 'largest', 'small', 'holes' or 'morph'
+    sets: List[frozenset]                       # disjoint label sets, all labelled in this call ('holes', 'morph': one)
     background: int
     min_size: Tuple[int, ...] = ()              # 'small': one per set
-    connectivity: int = 26                      # 'small'
-    fill_label: int = 0                         # 'holes'
+    connectivity: int = 26                      # 'small'; 'morph': 6, 18 or 26
+    fill_label: int = 0                         # 'holes'; 'morph': the adding ops'
+    op: int = 0                                 # 'morph': capi.FNN_MORPH_*
+    iterations: int = 1                         # 'morph'
+    border_value: int = 0                       # 'morph'
 
 
 def _gpu_pass(kind: str, body, pp_fn_kwargs) -> GpuPass:
@@ -170,6 +225,10 @@ def _gpu_pass(kind: str, body, pp_fn_kwargs) -> GpuPass:
         return GpuPass('small', sets, bg, tuple(e[3] for e in body), int(pp_fn_kwargs[body[0][2]].get('connectivity', 26)))
     if kind == 'gpu_holes':
         return GpuPass('holes', sets, bg, fill_label=body[0][3])
+    if kind == 'gpu_morph':
+        m = body[0][3]
+        return GpuPass('morph', sets, bg, connectivity=m.connectivity, fill_label=m.fill_label, op=m.op, iterations=m.iterations,
+                       border_value=m.border_value)
     return GpuPass('largest', sets, bg)
 
 
@@ -193,13 +252,14 @@ def _check_passes(passes: Sequence[GpuPass], u16: bool):
     for p in passes:
         if p.background < 0 or p.background >= limit:
             raise ValueError(f'background_label {p.background} does not fit the label map ({name})')
-        if p.call == 'holes' and (p.fill_label < 0 or p.fill_label >= limit):
+        fills = p.call == 'holes' or (p.call == 'morph' and p.op in _MORPH_ADDS)
+        if fills and (p.fill_label < 0 or p.fill_label >= limit):
             raise ValueError(f'fill_label {p.fill_label} does not fit the label map ({name})')
 
 
 def _run_passes(work: torch.Tensor, u16: bool, passes: Sequence[GpuPass], border_axes: int = 7):
-    """Apply GPU passes in order to the [X, Y, Z] device tensor ``work`` (in place).  ``border_axes``: ``fnn_fill_holes``'s,
-    6 for a 2-D map carried as [1, Y, Z]."""
+    """Apply GPU passes in order to the [X, Y, Z] device tensor ``work`` (in place).  ``border_axes``: ``fnn_fill_holes``'s and
+    ``fnn_binary_morphology``'s ``axes``, 6 for a 2-D map carried as [1, Y, Z]."""
     limit = 65536 if u16 else 256
     _check_passes(passes, u16)
     with torch.cuda.device(work.device):
@@ -218,6 +278,9 @@ def _run_passes(work: torch.Tensor, u16: bool, passes: Sequence[GpuPass], border
                                              p.connectivity, stream)
             elif p.call == 'holes':
                 capi.fill_holes(work.data_ptr(), u16, work.shape, table, p.background, p.fill_label, border_axes, stream)
+            elif p.call == 'morph':
+                capi.binary_morphology(work.data_ptr(), u16, work.shape, table, p.op, p.connectivity, p.iterations, p.border_value,
+                                       p.background, p.fill_label, border_axes, stream)
             else:
                 raise ValueError(f'unknown GPU pass {p.call!r}')
 
@@ -300,6 +363,54 @@ def fill_holes_in_segmentation(segmentation, labels_or_regions, fill_label: Opti
                      dict(labels_or_regions=labels_or_regions, fill_label=fill_label, background_label=background_label))
 
 
+def binary_dilation_in_segmentation(segmentation, labels_or_regions, iterations: int = 1, connectivity: int = 6,
+                                    border_value: int = 0, fill_label: Optional[int] = None, background_label: int = 0):
+    """scipy's ``binary_dilation`` of the mask ``seg in S`` with ``generate_binary_structure(ndim, rank)`` - ``connectivity`` 6,
+    18 or 26 is rank 1, 2 or 3; on a 2-D map 6 is the cross and 18 and 26 the full 3x3 - ``iterations`` times (1..1024), the
+    outside of the map counting as ``border_value`` (0 or 1).  The voxels the mask gains whose value is ``background_label``
+    become ``fill_label`` - by default the label of S when it has exactly one, otherwise it must be given - and any other
+    label in the grown zone stays.  ``segmentation``, dtype and values: as the functions above; the input is left alone."""
+    return _one_step(binary_dilation_in_segmentation, segmentation,
+                     dict(labels_or_regions=labels_or_regions, iterations=iterations, connectivity=connectivity,
+                          border_value=border_value, fill_label=fill_label, background_label=background_label))
+
+
+def binary_closing_in_segmentation(segmentation, labels_or_regions, iterations: int = 1, connectivity: int = 6,
+                                   border_value: int = 0, fill_label: Optional[int] = None, background_label: int = 0):
+    """scipy's ``binary_closing`` of the mask ``seg in S``: ``iterations`` dilations, then as many erosions, structure and
+    ``border_value`` as in ``binary_dilation_in_segmentation``.  Closing only adds here: the voxels the mask gains whose value is
+    ``background_label`` become ``fill_label`` (default as above), any other label there stays, and no voxel of S changes -
+    with ``border_value=0`` scipy's closing erodes the mask from the faces of the map, and those voxels stay what they are."""
+    return _one_step(binary_closing_in_segmentation, segmentation,
+                     dict(labels_or_regions=labels_or_regions, iterations=iterations, connectivity=connectivity,
+                          border_value=border_value, fill_label=fill_label, background_label=background_label))
+
+
+def binary_erosion_in_segmentation(segmentation, labels_or_regions, iterations: int = 1, connectivity: int = 6,
+                                   border_value: int = 0, background_label: int = 0):
+    """scipy's ``binary_erosion`` of the mask ``seg in S``, structure, ``iterations`` and ``border_value`` as in
+    ``binary_dilation_in_segmentation``: the voxels the mask loses become ``background_label``; with ``border_value=0`` a set
+    that touches a face of the map is eroded from that face too, with 1 it is not.  No voxel outside S changes."""
+    return _one_step(binary_erosion_in_segmentation, segmentation,
+                     dict(labels_or_regions=labels_or_regions, iterations=iterations, connectivity=connectivity,
+                          border_value=border_value, background_label=background_label))
+
+
+def binary_opening_in_segmentation(segmentation, labels_or_regions, iterations: int = 1, connectivity: int = 6,
+                                   border_value: int = 0, background_label: int = 0):
+    """scipy's ``binary_opening`` of the mask ``seg in S``: ``iterations`` erosions, then as many dilations (thin bridges and
+    specks go, what is left comes back to its size).  Opening only removes here: the voxels the mask loses become
+    ``background_label`` and no voxel outside S changes - with ``border_value=1`` scipy's opening grows the mask from the faces
+    of the map, and those voxels are not added."""
+    return _one_step(binary_opening_in_segmentation, segmentation,
+                     dict(labels_or_regions=labels_or_regions, iterations=iterations, connectivity=connectivity,
+                          border_value=border_value, background_label=background_label))
+
+
+_MORPH_OPS = ((binary_dilation_in_segmentation, capi.FNN_MORPH_DILATE), (binary_erosion_in_segmentation, capi.FNN_MORPH_ERODE),
+              (binary_opening_in_segmentation, capi.FNN_MORPH_OPEN), (binary_closing_in_segmentation, capi.FNN_MORPH_CLOSE))
+
+
 def apply_postprocessing(segmentation, pp_fns: Sequence[Callable], pp_fn_kwargs: Sequence[dict]):
     """``apply_postprocessing`` (remove_connected_components.py:36-39): every step in order, consecutive steps of
     this module fused into one labelling pass where ``plan_passes`` allows it; a chain of this module's steps of any
@@ -330,7 +441,7 @@ def apply_postprocessing(segmentation, pp_fns: Sequence[Callable], pp_fn_kwargs:
 
 class _RestrictedUnpickler(pickle.Unpickler):
     """Reads ``postprocessing.pkl`` without nnunetv2: the reference's function maps onto this module's, this module's own
-    two further steps load under this module's name, numpy scalars and dtypes may be rebuilt, every other global is refused."""
+    further steps load under this module's name, numpy scalars and dtypes may be rebuilt, every other global is refused."""
     _NUMPY = {('numpy', 'dtype'), ('numpy.core.multiarray', 'scalar'), ('numpy._core.multiarray', 'scalar')}
 
     def find_class(self, module, name):
@@ -343,7 +454,7 @@ class _RestrictedUnpickler(pickle.Unpickler):
         raise pickle.UnpicklingError(f'postprocessing.pkl names a global that is not allowed: {module}.{name}')
 
 
-_OWN_STEPS = {f.__name__: f for f in (remove_small_components_from_segmentation, fill_holes_in_segmentation)}
+_OWN_STEPS = {f.__name__: f for f in (remove_small_components_from_segmentation, fill_holes_in_segmentation, *(f for f, _ in _MORPH_OPS))}
 
 
 def _numpy_scalar(dtype, data=None):

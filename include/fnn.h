@@ -401,6 +401,32 @@ int fnn_remove_small_components(void *labels, int label_dtype, const int64_t sha
 int fnn_fill_holes(void *labels, int label_dtype, const int64_t shape[3], const int32_t *group_of_label, int n_table,
                    int background_label, int fill_label, int border_axes, int64_t *filled, void *stream);
 
+/* Binary morphology of one label set S (additive in ABI 4): the last of the "morphological operations" the reference's
+ * inference front end names without source; the definition is scipy's.  With M = in_S, R is ndimage.binary_dilation,
+ * binary_erosion, binary_opening or binary_closing of M (op) with structure = generate_binary_structure(ndim, rank),
+ * iterations = iterations, border_value = border_value and every other argument at its default.  connectivity 6, 18 or 26 is
+ * rank 1, 2 or 3 (on a 2-D map 18 and 26 both give the full 3 x 3, 6 the cross).  iterations: 1..1024 (scipy's "below 1: until
+ * nothing changes" is refused).  The label rule:
+ *   - dilation and closing only add: voxels of R & ~M whose value equals background_label become fill_label, any other
+ *     label there stays, no voxel of M changes (with border_value 0 scipy's closing loses voxels of M at the volume's border:
+ *     they stay);
+ *   - erosion and opening only remove: voxels of M & ~R become background_label, no voxel outside M changes (with
+ *     border_value 1 scipy's opening gains voxels at the border: they are not added); fill_label is not read.
+ * labels, label_dtype, shape, group_of_label (0 = in S, -1 = not), n_table and the size limits: as fnn_fill_holes.  axes is a
+ * bit mask of the axes the structure spans (bit 0 x, 1 y, 2 z): 7 for a 3-D map, 6 for a 2-D map carried as [1][Y][Z]; with 7
+ * on [1][Y][Z] the x-neighbours lie outside the map and count as border_value, as scipy does for a (1, Y, Z) array.  changed
+ * (optional, host) receives the number of voxels written.  FNN_E_INVALID before any launch and before any device memory is
+ * asked for: op outside 0..3, connectivity not 6 / 18 / 26, iterations outside 1..1024, border_value not 0 / 1, a label outside
+ * the dtype, fill_label equal to background_label for an adding op, axes outside 1..7, a table entry outside [-1, 0].  A
+ * zero-size volume returns 0; more than 2^31 - 1 voxels give FNN_E_UNSUPPORTED.  Launches: with border_value 0 the box pass of
+ * fnn_fill_holes, read by the host (an empty S ends the call), and the work stays inside S's box (grown by iterations for the
+ * adding ops); the mask is packed to bit planes, every iteration is one launch on them, one pass applies the label rule.
+ * Scratch, allocated inside the call: 2 bits per voxel of the box.  Synchronises the stream. */
+enum { FNN_MORPH_DILATE = 0, FNN_MORPH_ERODE = 1, FNN_MORPH_OPEN = 2, FNN_MORPH_CLOSE = 3 };
+int fnn_binary_morphology(void *labels, int label_dtype, const int64_t shape[3], const int32_t *group_of_label, int n_table,
+                          int op, int connectivity, int iterations, int border_value, int background_label, int fill_label,
+                          int axes, int64_t *changed, void *stream);
+
 /* Cross-configuration ensembling (additive in ABI 4): average_probabilities + merge_files without the image writer
  * (ensembling/ensemble.py:16-44), in one pass from the members' logits.  member_logits[m] (device, host array of
  * n_members pointers, 1..16) are [heads][bbox extents] of dtype member_dtype[m] (FNN_OUT_F16 / FNN_OUT_F32; members may

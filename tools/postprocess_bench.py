@@ -2,12 +2,16 @@
 whole-foreground step plus one step per label, the shape of a typical postprocessing.pkl of a 61-class model), with
 the scipy restatement's seconds on the host next to it.
 
-usage (repo root, GPU box): python tools/postprocess_bench.py [--n 512] [--reps 5] [--no-cpu] [--out FILE]
+usage (repo root, GPU box): python tools/postprocess_bench.py [--n 512] [--reps 5] [--no-cpu] [--out FILE] [--section NAME]
 Kernel times: run it under rocprofv3 --kernel-trace --stats.
 
 --section small_holes (profiles/r33_small_holes.txt): fnn_remove_small_components and fnn_fill_holes on evaluation_bench's two
 maps - 60 ellipsoids with cavities punched into them, and 20000 small lesions - next to fnn_keep_largest_components on the same
 map in the same run and to scipy on this machine's CPU (ndimage.label + bincount, binary_fill_holes in the label's box).
+
+--section morphology (profiles/r34_morphology.txt): fnn_binary_morphology on the same two maps - dilate, erode, open and close
+at connectivity 6 and 26 with 1, 2, 5 and 10 iterations, one call per label and one call for the whole foreground as a region,
+next to scipy on this machine's CPU per label cropped to the label's box (--cpu-n: the iteration counts scipy runs for).
 """
 import argparse
 import os
@@ -157,16 +161,104 @@ def small_holes_section(a):
             fh.write('\n'.join(lines) + '\n')
 
 
+def morphology_section(a):
+    """fnn_binary_morphology: one call per label, one call for the whole foreground, and scipy per label in the label's box."""
+    from fast_nnunet_amd import capi
+    from tools.evaluation_bench import lesion_map, organ_map
+    import morph_ref as ref
+    dev = torch.device('cuda', 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    maps = {'organs': (organ_map(a.n), list(range(1, 61))), 'lesions': (lesion_map(a.n), [1])}
+    ops = [('dilation', capi.FNN_MORPH_DILATE), ('erosion', capi.FNN_MORPH_ERODE), ('opening', capi.FNN_MORPH_OPEN),
+           ('closing', capi.FNN_MORPH_CLOSE)]
+    cpu_n = [] if a.no_cpu else [int(v) for v in a.cpu_n.split(',') if v]
+    lines = []
+
+    def report(text):
+        lines.append(text)
+        print(text, flush=True)
+    report(f'postprocess_bench --section morphology: {a.n}^3 uint8 maps; device {torch.cuda.get_device_name(dev)}')
+    report('  organs: 60 ellipsoids (evaluation_bench.organ_map); lesions: 20000 ellipsoids of label 1 with semi-axes 1..3 (evaluation_bench.lesion_map)')
+    report(f'device calls: median (min, max) of {a.reps} after one warm-up, events around the call on a fresh copy of the map (the box pass and '
+           f'its host read, scratch allocation, one launch per iteration and the synchronising copy-back of the count included); border_value 0')
+    report('  per label: one call per label, the sum of the per-label medians, and the median, min and max over the labels')
+    report('  region: one call with every foreground label in the set (fill_label 1)')
+    report('  scipy: one thread, per label on the crop of its find_objects box (grown by n for dilation and closing), in label order on one map;')
+    report('  "same" says whether the device calls made in that order on one map give the same map, bit for bit')
+    report('step kernel: one launch per iteration')
+
+    def timed(base, w, fn):
+        ts = []
+        for r in range(a.reps + 1):
+            w.copy_(base)
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn(w)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            if r:
+                ts.append(e0.elapsed_time(e1))
+        return float(np.median(ts)), min(ts), max(ts)
+
+    for name, (seg, labels) in maps.items():
+        base = torch.from_numpy(seg).to(dev)
+        w = base.clone()
+        boxes = ndimage.find_objects(seg)
+        report(f'{name}: {len(labels)} label(s), foreground voxels {int((seg > 0).sum())}')
+        region = np.full(max(labels) + 1, -1, np.int32)
+        region[labels] = 0
+        in_set = np.full(max(labels) + 1, -1, np.int32)
+        for op, code in ops:
+            for conn in (6, 26):
+                for n in (1, 2, 5, 10):
+                    per_label = []
+                    for lab in labels:
+                        in_set[:] = -1
+                        in_set[lab] = 0
+                        per_label.append(timed(base, w, lambda w: capi.binary_morphology(w.data_ptr(), False, w.shape, in_set, code, conn, n, 0,
+                                                                                         0, lab, 7, stream))[0])
+                    ms, lo, hi = timed(base, w, lambda w: capi.binary_morphology(w.data_ptr(), False, w.shape, region, code, conn, n, 0, 0, 1, 7,
+                                                                                 stream))
+                    text = (f'  {op:8s} connectivity {conn:2d} n {n:2d}: per label {sum(per_label):8.2f} ms (median {np.median(per_label):.3f}, min '
+                            f'{min(per_label):.3f}, max {max(per_label):.3f}); region {ms:7.2f} ms (min {lo:.2f} max {hi:.2f})')
+                    if n in cpu_n:
+                        w.copy_(base)
+                        changed = 0
+                        for lab in labels:
+                            in_set[:] = -1
+                            in_set[lab] = 0
+                            changed += capi.binary_morphology(w.data_ptr(), False, w.shape, in_set, code, conn, n, 0, 0, lab, 7, stream)
+                        got = w.cpu().numpy()
+                        grow = n if op in ref.ADDS else 0
+                        want = seg.copy()
+                        t0 = time.perf_counter()
+                        for lab in labels:
+                            if lab - 1 >= len(boxes) or boxes[lab - 1] is None:
+                                continue
+                            box = tuple(slice(max(0, s.start - grow), min(d, s.stop + grow)) for s, d in zip(boxes[lab - 1], seg.shape))
+                            kw = dict(labels_or_regions=lab, iterations=n, connectivity=conn, border_value=0)
+                            want[box] = ref.morph_ref(want[box], op, **kw)
+                        text += f'; scipy {time.perf_counter() - t0:6.2f} s, same {np.array_equal(got, want)}, voxels written {changed}'
+                    report(text)
+    if a.out:
+        with open(a.out, 'w') as fh:
+            fh.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=512)
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', default='largest', choices=['largest', 'small_holes'])
+    ap.add_argument('--section', default='largest', choices=['largest', 'small_holes', 'morphology'])
+    ap.add_argument('--cpu-n', default='1,2,5,10', help='--section morphology: the iteration counts scipy runs for (comma-separated)')
     a = ap.parse_args()
     if a.section == 'small_holes':
         return small_holes_section(a)
+    if a.section == 'morphology':
+        return morphology_section(a)
     from fast_nnunet_amd import capi
     from fast_nnunet_amd import postprocessing as pp
 
