@@ -78,7 +78,7 @@ class Profile(C.Structure):
 
 EXPORTS = ['fnn_abi_version', 'fnn_last_error', 'fnn_create', 'fnn_destroy', 'fnn_weight_count', 'fnn_load_weights',
            'fnn_set_gaussian', 'fnn_predict_volume', 'fnn_predict_volume_ensemble', 'fnn_predict_labels',
-           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_remove_small_components', 'fnn_fill_holes', 'fnn_binary_morphology', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
+           'fnn_set_label_rule', 'fnn_accumulator_channels', 'fnn_accumulate_patches', 'fnn_normalize_box', 'fnn_labels_box', 'fnn_feature_channels', 'fnn_patch_features', 'fnn_gather_box', 'fnn_pack_regions', 'fnn_unpack_regions', 'fnn_forward_patches', 'fnn_argmax_labels', 'fnn_nonzero_bbox', 'fnn_preprocess', 'fnn_revert_labels', 'fnn_export_probabilities', 'fnn_resample', 'fnn_resample_torch', 'fnn_resample_torch_seg', 'fnn_resample_labels', 'fnn_keep_largest_components', 'fnn_remove_small_components', 'fnn_fill_holes', 'fnn_binary_morphology', 'fnn_ensemble_export', 'fnn_average_probabilities', 'fnn_ensemble_resample_export', 'fnn_confusion_counts', 'fnn_surface_count', 'fnn_surface_distances', 'fnn_instance_overlaps', 'fnn_mesh_count', 'fnn_mesh_emit', 'fnn_mesh_decimate', 'fnn_decode_voxels', 'fnn_decode_labels', 'fnn_reorient', 'fnn_deflate_bound', 'fnn_deflate_labels', 'fnn_deflate_labels_dyn', 'fnn_deflate_masks_work_bytes', 'fnn_deflate_masks_count', 'fnn_deflate_masks_emit', 'fnn_inflate_segments', 'fnn_inflate_segments_dyn', 'fnn_inflate_find_blocks', 'fnn_inflate_stream', 'fnn_compute_steps', 'fnn_plan_volume', 'fnn_fp8_e4m3_encode',
            'fnn_set_profiling', 'fnn_get_profile', 'fnn_kernel_log', 'fnn_profile_launches', 'fnn_layer_table', 'fnn_plan_table', 'fnn_patch_work', 'fnn_op_conv3d', 'fnn_op_conv_transpose3d', 'fnn_op_avgpool', 'fnn_op_combine', 'fnn_op_seg_head', 'fnn_op_patch_acc', 'fnn_op_patch_input', 'fnn_op_stem', 'fnn_op_conv_fused', 'fnn_op_quotient_check', 'fnn_op_last_kernels', 'fnn_clock_probe_start', 'fnn_clock_probe_stop']
 
 _lib = None
@@ -175,6 +175,8 @@ def load_library() -> C.CDLL:
     lib.fnn_deflate_masks_emit.argtypes = [vp, i32, i64, C.POINTER(C.c_int32), i32, vp, vp, i64, vp]
     lib.fnn_inflate_segments.argtypes = [vp, i64, C.POINTER(i64), i64, vp, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
     lib.fnn_inflate_segments_dyn.argtypes = lib.fnn_inflate_segments.argtypes
+    lib.fnn_inflate_find_blocks.argtypes = [vp, i64, vp, i64, C.POINTER(i64), vp]
+    lib.fnn_inflate_stream.argtypes = [vp, i64, vp, i64, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), vp]
     lib.fnn_compute_steps.argtypes = [i64, i64, C.c_double, C.POINTER(i64), i32]
     lib.fnn_plan_volume.argtypes = [C.POINTER(C.c_int32), C.POINTER(i64), C.c_double, C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(i64), C.POINTER(C.c_int32), i64]
@@ -497,6 +499,28 @@ def inflate_segments_dyn(in_ptr: int, in_bytes: int, starts, out_ptr: int, out_b
     crc, status = C.c_uint32(0), C.c_int32(0)
     check(lib.fnn_inflate_segments_dyn(in_ptr, int(in_bytes), arr.ctypes.data_as(C.POINTER(C.c_int64)), int(arr.size), out_ptr,
                                        int(out_bytes), C.byref(crc), C.byref(status), stream), lib)
+    return int(status.value), int(crc.value)
+
+
+def inflate_find_blocks(in_ptr: int, in_bytes: int, positions_ptr: int = 0, cap: int = 0, stream: int = 0) -> int:
+    """fnn_inflate_find_blocks: the bit positions of the raw deflate stream of in_bytes bytes at in_ptr (device, 16-byte
+    aligned) at which a decode may begin - bit 0 and wherever a non-final dynamic block's table header stands that zlib
+    would accept.  Returns how many there are; the first ``min(n, cap)`` are written, ascending, to the ``cap`` int64 at
+    positions_ptr (device).  Synchronises the stream."""
+    lib = load_library()
+    n = C.c_int64(0)
+    check(lib.fnn_inflate_find_blocks(in_ptr, int(in_bytes), positions_ptr or None, int(cap), C.byref(n), stream), lib)
+    return int(n.value)
+
+
+def inflate_stream(in_ptr: int, in_bytes: int, out_ptr: int, out_bytes: int, stream: int = 0):
+    """fnn_inflate_stream: any raw deflate stream of in_bytes bytes at in_ptr (device, 16-byte aligned) - what zlib writes -
+    inflated into the out_bytes bytes at out_ptr (device, 16-byte aligned), speculatively from every position
+    ``inflate_find_blocks`` finds.  Returns ``(status, crc32)`` as ``inflate_segments`` does; the status is one of
+    ``INFLATE_DYN_REASONS``.  Synchronises the stream."""
+    lib = load_library()
+    crc, status = C.c_uint32(0), C.c_int32(0)
+    check(lib.fnn_inflate_stream(in_ptr, int(in_bytes), out_ptr, int(out_bytes), C.byref(crc), C.byref(status), stream), lib)
     return int(status.value), int(crc.value)
 
 

@@ -1,6 +1,7 @@
-// inflate_wave.h - what the kernels of csrc/inflate.hip and csrc/inflate_dyn.hip share: the stream as a register window,
-// the wave's LDS image of a segment, the CRC-32 and the store of a finished image, the records the two passes leave, and
-// how the host code of the two entries (csrc/inflate.hip) launches the kernels of csrc/inflate_dyn.hip.
+// inflate_wave.h - what the kernels of csrc/inflate.hip, csrc/inflate_dyn.hip and csrc/inflate_any.hip share: the stream as a
+// register window, the wave's LDS image of a segment, the CRC-32 and the store of a finished image, the records the passes
+// leave, and how the host code of the entries (csrc/inflate.hip) launches the kernels of csrc/inflate_dyn.hip and
+// csrc/inflate_any.hip.
 #pragma once
 #include "deflate_wave.h"
 #include "inflate_core.h"
@@ -114,3 +115,30 @@ struct InfDynArgs {
     InfMade *made;
 };
 void inf_dyn_launch(int pass, unsigned n, const InfDynArgs &a, hipStream_t st);
+
+// ---- fnn_inflate_find_blocks, fnn_inflate_stream: the passes of csrc/inflate_any.hip ----------------------------------------
+struct InfAnyRecord;
+constexpr int INF_ANY_SLICE = 2048;                              // the input bytes of one workgroup of the block finder
+constexpr int INF_ANY_SLICE_MASKS = INF_ANY_SLICE * 8 / 64;      // its 64-bit masks: one bit per bit position
+struct InfAnyMember {                                            // a member of the chain: its first bit, where its entries go (in
+    long long start, off, end, len;                              // entries: output bytes), the bit behind it and its length
+};
+enum { INF_ANY_MARK_PASS, INF_ANY_SCAN, INF_ANY_WRITE, INF_ANY_COUNT, INF_ANY_EMIT, INF_ANY_WINDOW_PASS, INF_ANY_RESOLVE };
+struct InfAnyArgs {
+    const uint8_t *in;
+    long long in_bytes, out_bytes;
+    unsigned long long *masks;                                   // per slice INF_ANY_SLICE_MASKS
+    unsigned *counts;                                            // per slice
+    long long *offsets, *total;                                  // per slice; one
+    long long *positions, cap;                                   // the candidates, ascending; how many `positions` holds
+    InfAnyRecord *rec;                                           // per candidate
+    const InfAnyMember *members;
+    uint16_t *work;                                              // one entry per output byte
+    int *made;                                                   // per member: 1, or 0 where the second decode differed (never)
+    uint8_t *windows;                                            // per member but the last, 32 KiB
+    const uint32_t *x2k;
+    uint8_t *out;
+    uint32_t *crcs;                                              // per DF_CHUNK of the output
+};
+// MARK_PASS, WRITE: n slices; SCAN: n slices in one wave; COUNT: n candidates; EMIT, WINDOW_PASS, RESOLVE: n members.  Host only.
+void inf_any_launch(int pass, unsigned n, const InfAnyArgs &a, hipStream_t st);

@@ -35,7 +35,11 @@ compressed file as it is when ``chunked_layout`` recognises it, and ``decode_lab
 zlib (references, scanner images), image files and everything the device refuses are inflated by zlib on the host, as ever.
 ``fnn_inflate_segments`` refuses dynamic-Huffman blocks, so a file written with ``compress_on_device='dynamic'`` falls back;
 ``NiftiIO(inflate_on_device='dynamic')`` takes ``fnn_inflate_segments_dyn`` (csrc/inflate_dyn.hip) instead, which decodes
-them and serves the files of both encoders.
+them and serves the files of both encoders.  ``NiftiIO(inflate_on_device='any')`` does that and stages every other
+single-member ``.nii.gz`` label file too - what zlib, nibabel, SimpleITK or nnU-Net wrote (``stream_layout``) - for
+``fnn_inflate_stream`` (csrc/inflate_any.hip), which inflates one deflate stream speculatively from every bit position at which a
+dynamic block may begin; certified in the same way, with the same fallback.  On label maps, which zlib cuts into few blocks,
+that route is slower than zlib on the host (profiles/r35_inflate_any.txt): it is an opt-in for streams of many blocks.
 
 The header is untrusted: every length is checked against the file before anything is uploaded or launched.
 """
@@ -405,12 +409,54 @@ def chunked_layout(file_bytes, hdr: NiftiHeader) -> Optional[ChunkedLayout]:
     return ChunkedLayout(m, end - m, starts, zlib.crc32(head), crc)
 
 
+def gzip_member_start(blob: bytes) -> Optional[int]:
+    """Where the deflate stream of a gzip member begins (RFC 1952): behind the 10 fixed bytes and what FLG announces - FEXTRA
+    (a 2-byte length and that many bytes), FNAME and FCOMMENT (zero-terminated), FHCRC (2 bytes).  None for what is no gzip
+    header of a deflate member, has a reserved flag set or ends inside its header."""
+    n = len(blob)
+    if n < 18 or blob[:3] != b'\x1f\x8b\x08' or blob[3] & 0xE0:
+        return None
+    flg, at = blob[3], 10
+    if flg & 4:
+        if at + 2 > n:
+            return None
+        at += 2 + struct.unpack_from('<H', blob, at)[0]
+    for bit in (8, 16):
+        if flg & bit:
+            if at >= n:
+                return None
+            at = blob.find(b'\x00', at) + 1
+            if at == 0:
+                return None
+    if flg & 2:
+        at += 2
+    return at if at < n - 8 else None
+
+
+def stream_layout(file_bytes, hdr: NiftiHeader) -> Optional[ChunkedLayout]:
+    """The layout of a whole ``.nii.gz`` file that anybody's zlib wrote, for ``fnn_inflate_stream``: the raw deflate bytes
+    ``file[first:len - 8]`` are claimed to inflate to the ``vox_offset`` header bytes and the voxel bytes, ``crc32`` is the
+    trailer's (``starts`` is None: the device finds where to begin).  None - the host inflates the file - for a header that
+    ``gzip_member_start`` does not read, an ISIZE that is not ``(vox_offset + n_bytes) mod 2^32`` and a ``vox_offset`` that
+    is no multiple of 16 (``fnn_decode_labels`` reads behind it).  A second member or bytes behind the trailer are not
+    looked for here: the device call then ends with a status (the final block is not the input's end) and the host reads
+    the file.  Nothing here is trusted later."""
+    blob = bytes(file_bytes)
+    first = gzip_member_start(blob)
+    if first is None or hdr.vox_offset % 16:
+        return None
+    crc, isize = struct.unpack('<II', blob[-8:])
+    if isize != (hdr.vox_offset + hdr.n_bytes) & 0xFFFFFFFF:
+        return None
+    return ChunkedLayout(first, len(blob) - 8 - first, None, 0, crc)
+
+
 def inflate_on_device_value(value):
-    """The ``inflate_on_device`` switch as the readers keep it: False, True or 'dynamic'.  Any other string is a ValueError;
-    what is no string counts by its truth, as before."""
+    """The ``inflate_on_device`` switch as the readers keep it: False, True, 'dynamic' or 'any'.  Any other string is a
+    ValueError; what is no string counts by its truth, as before."""
     if isinstance(value, str):
-        if value != 'dynamic':
-            raise ValueError(f"inflate_on_device must be False, True or 'dynamic', got {value!r}")
+        if value not in ('dynamic', 'any'):
+            raise ValueError(f"inflate_on_device must be False, True, 'dynamic' or 'any', got {value!r}")
         return value
     return bool(value)
 
@@ -420,26 +466,32 @@ class StagedCase:
     host thread fills.  ``layouts[i]`` is None when buffer i holds the file's voxel bytes, and the ``ChunkedLayout`` when it
     holds the whole compressed file for the device to inflate (label files of a reader with ``inflate_on_device``)."""
 
-    def __init__(self, fnames, hdrs, buffers, inflate_on_device: bool = False):
+    def __init__(self, fnames, hdrs, buffers, inflate_on_device=False):
         self.fnames, self.hdrs, self.buffers = list(fnames), list(hdrs), list(buffers)
         self.inflate_on_device = bool(inflate_on_device)
+        self.any_stream = inflate_on_device == 'any'             # files that are no chain of segments are staged too (stream_layout)
         self.layouts = [None] * len(self.fnames)
 
     def _stage_compressed(self, fname: str, hdr: NiftiHeader, buf) -> Optional[ChunkedLayout]:
-        """The whole file into ``buf`` when it is a chunked ``.nii.gz`` that fits (the buffer is sized by the voxel bytes)."""
+        """The whole file into ``buf`` when it is a chunked ``.nii.gz`` that fits (the buffer is sized by the voxel bytes);
+        with ``inflate_on_device='any'`` every other single-member ``.nii.gz`` that fits too (``stream_layout``)."""
         if not str(fname).lower().endswith('.nii.gz'):
             return None
+        anybodys = self.any_stream
         with open(fname, 'rb') as f:
             size = os.fstat(f.fileno()).st_size
             if size > buf.numel() or size < 32:
                 return None
             head10 = f.read(10)
             f.seek(size - 14)
-            if not _chunked_by_its_ends(head10, f.read(14)):
+            chunked = _chunked_by_its_ends(head10, f.read(14))
+            if not chunked and not anybodys:
                 return None
             f.seek(0)
             blob = f.read()
-        layout = chunked_layout(blob, hdr)
+        layout = chunked_layout(blob, hdr) if chunked else None      # (the segment route: more parallelism)
+        if layout is None and anybodys:
+            layout = stream_layout(blob, hdr)
         if layout is not None:
             buf.numpy()[:len(blob)] = np.frombuffer(blob, dtype=np.uint8)
         return layout
@@ -462,7 +514,9 @@ class NiftiIO:
         self._pinned = {}                            # slot -> list of pinned uint8 tensors, grown on demand
         # opt-in: label files written with compress_on_device=True are inflated by fnn_inflate_segments (csrc/inflate.hip)
         # instead of zlib; 'dynamic': by fnn_inflate_segments_dyn (csrc/inflate_dyn.hip), which also serves the files of
-        # compress_on_device='dynamic'.  Which route each label file took is counted here
+        # compress_on_device='dynamic'; 'any': those as with 'dynamic', and every other single-member .nii.gz - what zlib,
+        # nibabel, SimpleITK or nnU-Net wrote - by fnn_inflate_stream (csrc/inflate_any.hip).  Which route each label file
+        # took is counted here
         self.inflate_on_device = inflate_on_device_value(inflate_on_device)
         self.inflate_stats = {'device': 0, 'host': 0, 'fallback': 0}
 
@@ -539,7 +593,8 @@ class NiftiIO:
         ``fnn_decode_labels`` on the current stream - 1 byte wide for the 1-byte datatypes, else 2 bytes and narrowed to
         uint8 when the largest label is below 256.  RuntimeError naming the file when it holds what is no label.
         A file staged compressed (``inflate_on_device``) is uploaded as it is and inflated by ``fnn_inflate_segments``
-        (``inflate_on_device='dynamic'``: ``fnn_inflate_segments_dyn``) into the same byte tensor; the result is taken only
+        (``inflate_on_device='dynamic'``: ``fnn_inflate_segments_dyn``; ``'any'``: that, or ``fnn_inflate_stream`` for a file
+        that is no chain of segments) into the same byte tensor; the result is taken only
         if the call certifies it (status 0) and its CRC-32, combined with the header's, is the gzip trailer's - anything else re-reads the file with zlib on this thread, which is the route the
         file takes without the flag and the one that says what is wrong with a corrupt file.
         Synchronises: the staging buffers are free again on return."""
@@ -554,15 +609,16 @@ class NiftiIO:
                 raw = torch.empty(max(16, h.n_bytes), dtype=torch.uint8, device=dev)      # (the allocator aligns to 512 bytes)
                 if staged.layouts[i] is None:
                     self.inflate_stats['host'] += 1
-                    inflated = False
+                    inflated = None
                 else:
                     inflated = self._inflate_staged(staged, i, raw, stream, keep)
-                if not inflated:
+                if inflated is None:
                     raw[:h.n_bytes].copy_(b[:h.n_bytes], non_blocking=True)
+                    inflated = raw
                 keep.append(raw)
                 wide = label_bytes(h) == 2
                 out = torch.empty(h.shape, dtype=torch.int16 if wide else torch.uint8, device=dev)
-                capi.decode_labels(raw.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter, 2 if wide else 1,
+                capi.decode_labels(inflated.data_ptr(), h.datatype, h.byteswap, h.n_vox, h.scale, h.slope, h.inter, 2 if wide else 1,
                                    out.data_ptr(), status[i].data_ptr(), stream.cuda_stream)
                 maps.append(out)
             said = status.cpu().numpy()                          # (waits for the stream)
@@ -575,23 +631,32 @@ class NiftiIO:
                 made.append(self._label_frame(staged, i, m))
         return made
 
-    def _inflate_staged(self, staged: StagedCase, i: int, raw, stream, keep: list) -> bool:
-        """File i, staged compressed -> its voxel bytes in ``raw`` by the device inflate: True.  False: the device route
-        refused it, and the staging buffer now holds the voxel bytes ``read_voxel_bytes`` made of the file."""
+    def _inflate_staged(self, staged: StagedCase, i: int, raw, stream, keep: list):
+        """File i, staged compressed -> the device tensor that holds its voxel bytes, made by the device inflate: ``raw`` for
+        a chain of segments; for a stream that anybody's zlib wrote (``stream_layout``) the part behind ``vox_offset`` of a
+        tensor of its own, which ``fnn_inflate_stream`` fills with the header bytes and the voxel bytes.  None: the device
+        route refused it, and the staging buffer now holds the voxel bytes ``read_voxel_bytes`` made of the file."""
         import torch
         h, b, lay = staged.hdrs[i], staged.buffers[i], staged.layouts[i]
         comp = torch.empty(max(16, lay.in_bytes), dtype=torch.uint8, device=raw.device)
         comp[:lay.in_bytes].copy_(b[lay.first:lay.first + lay.in_bytes], non_blocking=True)
         keep.append(comp)
-        inflate = capi.inflate_segments_dyn if self.inflate_on_device == 'dynamic' else capi.inflate_segments
-        status, crc = inflate(comp.data_ptr(), lay.in_bytes, lay.starts, raw.data_ptr(), h.n_bytes, stream.cuda_stream)
-        if status == capi.FNN_INFLATE_OK and crc32_combine(lay.header_crc, crc, h.n_bytes) == lay.crc32:
+        if lay.starts is None:
+            whole = torch.empty(h.vox_offset + max(16, h.n_bytes), dtype=torch.uint8, device=raw.device)
+            keep.append(whole)
+            status, crc = capi.inflate_stream(comp.data_ptr(), lay.in_bytes, whole.data_ptr(), h.vox_offset + h.n_bytes, stream.cuda_stream)
+            certified, made = crc == lay.crc32, whole[h.vox_offset:]
+        else:
+            inflate = capi.inflate_segments if self.inflate_on_device is True else capi.inflate_segments_dyn
+            status, crc = inflate(comp.data_ptr(), lay.in_bytes, lay.starts, raw.data_ptr(), h.n_bytes, stream.cuda_stream)
+            certified, made = crc32_combine(lay.header_crc, crc, h.n_bytes) == lay.crc32, raw
+        if status == capi.FNN_INFLATE_OK and certified:
             self.inflate_stats['device'] += 1
-            return True
+            return made
         self.inflate_stats['fallback'] += 1                      # (the call synchronised: the staging buffer is free)
         staged.layouts[i] = None
         read_voxel_bytes(staged.fnames[i], h, b.numpy())
-        return False
+        return None
 
     def read_label_map(self, fname: str, on_device: bool = True):
         """A label file as labels -> ``(labels (z, y, x), properties)``: on the device ``decode_label_maps``' tensor; with

@@ -38,7 +38,8 @@ def folder_plans_and_dataset(folder: str, plans_file_or_dict=None, dataset_json_
     an instance of the reader-writer they name).  ``missing_*``: the caller's RuntimeError text for a file that is not in
     the folder, ``{}`` standing for its name (None: opening it raises).  ``inflate_on_device``: the reader-writer inflates
     label files written with ``compress_on_device=True`` on the GPU (``NiftiIO(inflate_on_device=True)``), with ``'dynamic'``
-    those written with ``compress_on_device='dynamic'`` too (``NiftiIO(inflate_on_device='dynamic')``)."""
+    those written with ``compress_on_device='dynamic'`` too (``NiftiIO(inflate_on_device='dynamic')``), with ``'any'`` every
+    single-member ``.nii.gz`` label file, whoever wrote it (``NiftiIO(inflate_on_device='any')``)."""
     from .imageio import prediction_reader_writer_class
     from .plans import PlansManager
 

@@ -761,9 +761,10 @@ int fnn_deflate_masks_emit(const void *in, int in_elem_bytes, int64_t n_elems, c
                            const void *work, void *out, int64_t out_cap, void *stream);
 
 /* A raw deflate stream on the device that is a chain of byte-aligned segments -> its bytes (additive in ABI 4; no
- * counterpart in the reference, which inflates with zlib on the host).  A general deflate stream cannot be inflated in
- * parallel; the fragments of fnn_deflate_labels and fnn_deflate_masks_emit, and what zlib writes with Z_FIXED between
- * Z_FULL_FLUSH points, can.  A segment starts at a byte and is a run of non-final blocks, stored (LEN / NLEN checked) or
+ * counterpart in the reference, which inflates with zlib on the host).  A single decoder cannot inflate a general deflate stream in
+ * parallel - a speculative one can, and fnn_inflate_stream below is one; this entry serves the streams that need no
+ * speculation: the fragments of fnn_deflate_labels and fnn_deflate_masks_emit, and what zlib writes with Z_FIXED between
+ * Z_FULL_FLUSH points.  A segment starts at a byte and is a run of non-final blocks, stored (LEN / NLEN checked) or
  * fixed Huffman, up to and including the first empty stored block (.. 00 00 FF FF), behind which it ends on a byte; no
  * match reaches back past its own first output byte, it makes at most FNN_INFLATE_SEGMENT_MAX output bytes and takes at
  * most 18480 input bytes (csrc/inflate_core.h derives the number).
@@ -817,6 +818,41 @@ int fnn_inflate_segments(const void *in, int64_t in_bytes, const int64_t *starts
 #define FNN_INFLATE_TABLES 12   /* a dynamic block's table header that zlib's inflate would refuse (fnn_inflate_segments_dyn) */
 int fnn_inflate_segments_dyn(const void *in, int64_t in_bytes, const int64_t *starts, int64_t n_starts, void *out,
                              int64_t out_bytes, uint32_t *crc32, int32_t *status, void *stream);
+
+/* Any raw deflate stream on the device -> its bytes, speculatively and block-parallel (additive in ABI 4): what zlib, and so
+ * nibabel, SimpleITK and nnU-Net, write.  csrc/inflate_any_core.h states the rule in full.
+ * A CANDIDATE is a bit position where a decode may begin: bit 0, and every bit position at which BFINAL 0, BTYPE 10 stand
+ * in front of a table header that passes the checks of fnn_inflate_segments_dyn (exactly zlib's accepted set) and ends
+ * inside the input.  A true non-final dynamic block start is always one; zlib cuts a block every 16 K symbols at the most.
+ * fnn_inflate_find_blocks: all candidates of in[0, in_bytes), ascending.  positions: DEVICE array of cap int64 (may be
+ * NULL with cap == 0); *n (host): how many there are - the first min(*n, cap) are written.  Synchronises.
+ * fnn_inflate_stream: in (device, 16-byte aligned) inflates to exactly out_bytes bytes at out (device, 16-byte aligned).
+ *   find    the candidates (a cheap test of 74 bits per bit position and lane, the survivors by the full rule; compacted
+ *           in ascending order by count, scan and write)
+ *   count   one wave per candidate decodes its MEMBER - block after block, stored and fixed ones included, until a
+ *           non-final block ends at a candidate or a final block ends at the input's last byte - keeping nothing, and
+ *           records the end bit, the 64-bit length, the reason and how far before its own first byte its matches reach
+ *   chain   on the host: member 0 starts at bit 0, a member's end is the stream's end or the next member; a member that
+ *           was refused gives its reason, one that reaches back before output byte 0 FNN_INFLATE_DISTANCE, sizes that do
+ *           not sum to out_bytes FNN_INFLATE_SIZE; a member that would pass out_bytes is FNN_INFLATE_OUTPUT.  Candidates
+ *           off the chain are ignored.  For a valid stream the chain always closes.
+ *   emit    one wave per member decodes again into 16-bit entries: a byte as 0 .. 255, a match source before the member's
+ *           first byte as 0x8000 | its index in the 32 KiB of output in front of the member
+ *   window  one workgroup walks the members in order and makes each one's 32 KiB window of resolved bytes
+ *   resolve parallel over the output: entries and windows -> bytes, and their CRC-32 per 16 KiB, folded on the host
+ * There is no limit on a member's output or input here; every loop is bounded by the input's bits.  The contract is
+ * fnn_inflate_segments': returns 0 with a status word; with FNN_INFLATE_OK out holds the bytes and *crc32 zlib's CRC-32 of
+ * them, the same on every run; on any other status out's contents are unspecified and nothing was launched past the point
+ * of knowing; nothing is read outside in[0, in_bytes) or written outside out[0, out_bytes); it synchronises.  The reasons
+ * are those above but FNN_INFLATE_DYNAMIC and FNN_INFLATE_INPUT; FNN_INFLATE_FINAL: bytes follow the final block.
+ * in_bytes == 0: nothing is launched, FNN_INFLATE_OK when out_bytes == 0 too and FNN_INFLATE_SIZE otherwise.
+ * FNN_E_INVALID before any launch: NULL arguments, negative sizes, a misaligned in or out, host pointers.
+ * Scratch, allocated inside the call: in_bytes + 12 B per 2 KiB of input (the finder's masks), 32 B per candidate,
+ * 32 B + 4 B + a 32 KiB window per member, 2 B per output byte and 4 B per 16 KiB of output.  A stream of few blocks has few
+ * members and so little parallelism: one stored or fixed-only stream is decoded by one wave. */
+int fnn_inflate_find_blocks(const void *in, int64_t in_bytes, int64_t *positions, int64_t cap, int64_t *n, void *stream);
+int fnn_inflate_stream(const void *in, int64_t in_bytes, void *out, int64_t out_bytes, uint32_t *crc32, int32_t *status,
+                       void *stream);
 
 /* ---- host-side integer logic (no GPU needed) ------------------------------ */
 /* compute_steps_for_sliding_window (sliding_window_prediction.py:30-54) for one

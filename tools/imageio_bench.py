@@ -24,7 +24,10 @@ written with ``compress_on_device=True``; and (``--section inflate_dyn``, these 
 profiles/r32_inflate_dynamic.txt unless ``--out`` says otherwise) fnn_inflate_segments_dyn on the fragments
 fnn_deflate_labels_dyn makes of those maps and of the tiled golden mask, next to zlib's inflate and a device copy, the same
 entry next to fnn_inflate_segments on the fixed fragments, and the two folder commands over files written with
-``compress_on_device='dynamic'``, read with ``inflate_on_device=True`` (the zlib fallback) and ``'dynamic'``.  ``--section read`` runs the file -> device rows of both files alone and
+``compress_on_device='dynamic'``, read with ``inflate_on_device=True`` (the zlib fallback) and ``'dynamic'``; and
+(``--section inflate_any``, these rows alone, written to profiles/r35_inflate_any.txt unless ``--out`` says otherwise)
+fnn_inflate_stream on streams that zlib wrote against zlib's inflate on this machine and the folder commands on folders that
+zlib wrote, read with ``inflate_on_device=True`` and ``'any'``.  ``--section read`` runs the file -> device rows of both files alone and
 ``--section predict_files`` the two predict_from_files rows alone, with the defaults of the full run: for repeating those
 rows in many fresh processes (profiles/r24_host_prologue.txt).
 
@@ -32,7 +35,7 @@ The volume is synthetic: an int16 "CT" of n^3 voxels (smooth structure + noise, 
 as .nii.gz (level 1, like the writer) and as .nii.
 
 usage (repo root, GPU box): python tools/imageio_bench.py [--n 512] [--reps 3] [--cases 4] [--case-shape 96 192 192]
-                                                          [--section all|reorient|deflate|masks|label_files|inflate|inflate_dyn|predict_files|read] [--out FILE]
+                                                          [--section all|reorient|deflate|masks|label_files|inflate|inflate_dyn|inflate_any|predict_files|read] [--out FILE]
 """
 import argparse
 import gzip
@@ -638,6 +641,114 @@ def bench_inflate_dyn(n, reps, cases, dev, say, row):
         'cost of the general decoder is the "fixed fragment" pair of rows above, and what a table decoder would change is open.')
 
 
+def bench_inflate_any(n, reps, cases, dev, say, row):
+    """fnn_inflate_stream (csrc/inflate_any.hip) on streams that zlib wrote - label maps at levels 1 and 6 as uint8 and uint16,
+    their level-0 and Z_FIXED streams (one member: the worst cases) and a synthetic int16 CT volume at level 6 - against zlib's
+    inflate of the same stream on this machine's CPU in the same run and fnn_inflate_segments_dyn on the project's own
+    dynamic fragment of the same map; the block finder alone (fnn_inflate_find_blocks); and the folder commands on folders
+    that zlib wrote, read with inflate_on_device=True (the parent's behaviour: every file on the host) and 'any'.  The times
+    of the single kernels and the number of members (the emit kernel's grid) come from a kernel trace of this section."""
+    import zlib
+    from fast_nnunet_amd import capi
+    from fast_nnunet_amd import evaluation as ev
+    from fast_nnunet_amd import imageio as fio
+    from fast_nnunet_amd import postprocessing as pp
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    calls, windows = 10, max(reps, 5)
+    say(f'--- fnn_inflate_stream on raw deflate streams made by zlib on this machine; in and out allocated before, the call allocates '
+        f'its scratch and synchronises; ms per call from {calls} calls inside one pair of events (1 call for the one-member streams), '
+        f'median (min, max) of {windows} such windows after a warm-up window; zlib on this machine, one thread, by wall clock')
+    golden = os.path.join(ROOT, 'tests', 'golden', 'example_ct_sm_T300_output.nii.gz')
+    mask = np.frombuffer(gzip.decompress(open(golden, 'rb').read())[352:], np.uint8).reshape(30, 101, 122)
+    reps_of = [max(1, round(n / s)) for s in mask.shape]
+    synth = label_map(n, dev)
+    tiled = torch.from_numpy(np.tile(mask, reps_of)).to(dev)
+    maps = [(f'61 labels {n}^3', synth), (f'golden mask tiled to {tuple(tiled.shape)}', tiled)]
+    inputs = []
+    for name, m in maps:
+        for wide in (False, True):
+            labels = m.to(torch.int16) * 1000 if wide else m
+            for what, level, strategy in (('level 1', 1, zlib.Z_DEFAULT_STRATEGY), ('level 6', 6, zlib.Z_DEFAULT_STRATEGY)) + \
+                    (() if wide else (('level 0 (stored: one member)', 0, zlib.Z_DEFAULT_STRATEGY), ('level 6 Z_FIXED (one member)', 6, zlib.Z_FIXED))):
+                inputs.append((f'{name}, {"uint16 (values x 1000)" if wide else "uint8"}, {what}', labels, level, strategy, (name, wide)))
+    ct = torch.from_numpy(synthetic_ct((n, n, n), 1)).to(dev)
+    inputs.append((f'synthetic CT int16 {n}^3, level 6', ct, 6, zlib.Z_DEFAULT_STRATEGY, None))
+    own = {}
+    for name, labels, level, strategy, key in inputs:                 # key: the map whose own dynamic fragment is the comparison
+        data = labels.reshape(-1).view(torch.uint8).cpu().numpy().tobytes()
+        n_bytes = len(data)
+        z = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+        t0 = time.perf_counter()
+        raw = z.compress(data) + z.flush()
+        t_def = (time.perf_counter() - t0) * 1e3
+        src = torch.zeros((len(raw) + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+        src[:len(raw)] = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+        out = torch.empty(n_bytes, dtype=torch.uint8, device=dev)
+        one = level == 0 or strategy == zlib.Z_FIXED
+        k = 1 if one else calls
+        n_cand = capi.inflate_find_blocks(src.data_ptr(), len(raw), 0, 0, stream)
+        say(f'{name}: {n_bytes / 2 ** 20:.0f} MiB -> {len(raw) / 2 ** 20:.2f} MiB (zlib deflate took {t_def:.0f} ms); {n_cand} candidates')
+        tf = events_batched(lambda: capi.inflate_find_blocks(src.data_ptr(), len(raw), 0, 0, stream), k, windows, dev)
+        row('  fnn_inflate_find_blocks (mark and scan; no positions written)', tf, f'  {len(raw) / tf[0] / 1e6:.2f} GB/s of input')
+        res = []
+        t = events_batched(lambda: res.append(capi.inflate_stream(src.data_ptr(), len(raw), out.data_ptr(), n_bytes, stream)), k, windows, dev)
+        same = res[-1] == (0, zlib.crc32(data)) and bool((out == labels.reshape(-1).view(torch.uint8)).all())
+        row('  fnn_inflate_stream', t, f'  {n_bytes / t[0] / 1e6:.2f} GB/s of output; status and CRC good, bytes equal: {same}')
+        tz = wall(lambda: zlib.decompressobj(-15).decompress(raw), reps)
+        verdict = 'the device call WINS' if tz[0] > t[0] else 'the device call LOSES to host zlib'
+        row('  zlib inflate of the same stream (host)', tz[:3], f'  {n_bytes / tz[0] / 1e6:.2f} GB/s; {tz[0] / t[0]:.2f}x the device call\'s time: {verdict}')
+        if key is not None:
+            if key not in own:
+                cap = capi.deflate_bound(n_bytes)
+                buf = torch.empty(cap, dtype=torch.uint8, device=dev)
+                n_in, _, crc_enc, _ = capi.deflate_labels_dyn(labels.data_ptr(), labels.element_size(), labels.numel(), False, buf.data_ptr(), cap, stream)
+                frag = buf[:n_in].cpu().numpy().tobytes()
+                starts = np.array([0] + [e for e in fio._marker_ends(frag, 0, len(frag)) if e < len(frag)], dtype=np.int64)
+                own[key] = events_batched(lambda: capi.inflate_segments_dyn(buf.data_ptr(), n_in, starts, out.data_ptr(), n_bytes, stream), calls, windows, dev)
+                del buf
+            row('  fnn_inflate_segments_dyn on the project\'s own dynamic fragment of the map', own[key], f'  fnn_inflate_stream on zlib\'s stream takes {t[0] / own[key][0]:.1f}x that')
+        del src, out, data, raw
+    del inputs, ct, tiled
+
+    wanted = list(range(1, 61))
+    say(f'--- folder commands, {cases} cases of {n}^3 voxels, 60 foreground labels: every file written by zlib on the host '
+        f'(compress_on_device=False); per-case wall clock with inflate_on_device=True (every file on the host, as before) and \'any\'')
+    plans = {'dataset_name': 'd', 'plans_name': 'p', 'image_reader_writer': 'NibabelIO', 'configurations': {}}
+    dj = {'labels': dict({'background': 0}, **{f'l{i}': i for i in wanted}), 'file_ending': '.nii.gz', 'channel_names': {'0': 'CT'}}
+    with tempfile.TemporaryDirectory() as tmp:
+        ref_d, pred_dir = (os.path.join(tmp, d) for d in ('ref', 'pred'))
+        for d in (ref_d, pred_dir):
+            os.makedirs(d)
+        affine = np.diag([0.8, 0.8, 1.25, 1.0])
+        for i in range(cases):
+            ref = label_map(n, dev, seed=30 + i)
+            pred = ref.clone()
+            pred[i::7] = 0
+            fio.write_label_file(ref.cpu().numpy(), os.path.join(ref_d, f'case{i}.nii.gz'), affine)
+            fio.write_label_file(pred.cpu().numpy(), os.path.join(pred_dir, f'case{i}.nii.gz'), affine)
+            del ref, pred
+        say(f'case0 on disk: reference {os.path.getsize(os.path.join(ref_d, "case0.nii.gz")) / 2 ** 20:.2f} MiB, prediction '
+            f'{os.path.getsize(os.path.join(pred_dir, "case0.nii.gz")) / 2 ** 20:.2f} MiB')
+        made = {}
+        for flag in (True, 'any'):
+            rw = fio.NiftiIO(dev, inflate_on_device=flag)
+            ev.compute_metrics_on_folder(ref_d, pred_dir, None, rw, '.nii.gz', wanted)                       # warm-up
+            made[flag] = wall(lambda: ev.compute_metrics_on_folder(ref_d, pred_dir, None, rw, '.nii.gz', wanted), reps)
+            row(f'compute_metrics_on_folder, inflate_on_device={flag!r}', made[flag][:3], f'  {made[flag][0] / cases:.1f} ms per case; routes {rw.inflate_stats}')
+        say(f'  compute_metrics_on_folder: \'any\' takes {made["any"][0] / made[True][0]:.2f}x the time of True; equal results: {repr(made[True][3]) == repr(made["any"][3])}')
+        fns, kwargs = [pp.remove_all_but_largest_component_from_segmentation], [{'labels_or_regions': wanted}]
+        made = {}
+        for flag in (True, 'any'):
+            out_dir = os.path.join(tmp, f'post_{flag}')
+            run = lambda: pp.apply_postprocessing_to_folder(pred_dir, out_dir, fns, kwargs, plans, dj, inflate_on_device=flag)   # noqa: E731
+            run()                                                                                            # warm-up
+            made[flag] = wall(run, reps)
+            row(f'apply_postprocessing_to_folder, inflate_on_device={flag!r}', made[flag][:3], f'  {made[flag][0] / cases:.1f} ms per case')
+        same = all(open(os.path.join(tmp, 'post_True', f'case{i}.nii.gz'), 'rb').read() == open(os.path.join(tmp, 'post_any', f'case{i}.nii.gz'), 'rb').read()
+                   for i in range(cases))
+        say(f'  apply_postprocessing_to_folder: \'any\' takes {made["any"][0] / made[True][0]:.2f}x the time of True; identical output files: {same}')
+
+
 def bench_predict_files(a, dev, say, row, tmp):
     """predict_from_files_sequential and predict_from_files on a.cases generated cases under tmp (``--section predict_files``
     runs these rows alone)."""
@@ -686,7 +797,7 @@ def main():
     ap.add_argument('--cases', type=int, default=4)
     ap.add_argument('--case-shape', type=int, nargs=3, default=(96, 192, 192))
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'inflate', 'inflate_dyn', 'predict_files', 'read'), default='all')
+    ap.add_argument('--section', choices=('all', 'reorient', 'deflate', 'masks', 'label_files', 'inflate', 'inflate_dyn', 'inflate_any', 'predict_files', 'read'), default='all')
     a = ap.parse_args()
     from fast_nnunet_amd import capi, nnUNetPredictor
     from fast_nnunet_amd import imageio as fio
@@ -719,6 +830,10 @@ def main():
     if a.section == 'inflate_dyn':
         bench_inflate_dyn(n, a.reps, a.cases, dev, say, row)
         write_out(a.out or os.path.join(ROOT, 'profiles', 'r32_inflate_dynamic.txt'), lines)
+        return
+    if a.section == 'inflate_any':
+        bench_inflate_any(n, a.reps, a.cases, dev, say, row)
+        write_out(a.out or os.path.join(ROOT, 'profiles', 'r35_inflate_any.txt'), lines)
         return
     if a.section == 'predict_files':
         with tempfile.TemporaryDirectory() as tmp:
